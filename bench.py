@@ -10,6 +10,7 @@ over that batch: clear the table, count every canonical k-mer (insert mode,
 pairs are written to a preallocated HBM buffer (discovery/pipeline.py:207-226).
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--config count|parent_filter]
+                    [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  When no launcher set WORLD_SIZE, bench.py starts its
 own N ranks (a `torch.distributed.run` child, before anything touches the GPU)
@@ -24,10 +25,17 @@ and exits with the child's code.  Every step then does what the N = 1 step does
 (discovery/pipeline.py:377-443): synthetic 64 Mbp trio at 30x, the child's
 non-reference k-mers as the filter, one parent's reads counted per step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` for the dominant kernel and `cpu_baseline` (the oracle's threaded C
-port timed on this box's host cores on a bounded sample -- a reported baseline,
-not the target).
+Prints ONE JSON line on rank 0, including `roofline` for the dominant kernel
+(HIP events around its launches in the timed steps themselves).  A plain run
+does only that: set up, warm up, time the --steps steps, print.
+
+--full adds what takes time of its own: `cpu_baseline` (the oracle's threaded C
+port timed on the host's cores on a bounded sample -- a reported baseline, not
+the target) and its comparison with the GPU result.
+
+--dump-outputs DIR (N = 1): after the timed steps, the (key, count) pairs the
+last step produced are written to DIR as float64 .npy files (dump_outputs()).
+The inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -52,6 +60,53 @@ def b_alg(k: int, L: int, probe_only: bool = False) -> float:
     return L / (4 * (L - k + 1)) + (8 if k <= 32 else 16) + (0 if probe_only else 8)
 
 
+DUMP_SAMPLE = 1 << 20                # pairs kept of a larger dump: at most 40 MB of .npy (k > 32)
+DUMP_SEED = 20260417
+_MIX1, _MIX2 = 0x27D4EB2F165667C5, 0x165667B19E3779F9
+_MASK52 = (1 << 52) - 1              # digests stay exact in float64
+
+
+def dump_outputs(path, lo, hi, cnt, n, scalars):
+    """--dump-outputs: the first n (key, count) pairs of the device arrays lo / hi (None at k <= 32) / cnt,
+    sorted by key (the engine dumps in table order, which depends on where the keys landed), as float64 .npy:
+      kmer_keys.npy    [m, 2 or 4]  the key's 64-bit words lo[, hi], each split into exact 32-bit halves, low first
+      kmer_counts.npy  [m]          the counts
+    m = n, or DUMP_SAMPLE pairs at sorted positions drawn with DUMP_SEED when n is larger.  Over all n pairs:
+      n_kmers.npy, count_sum.npy, key_digest.npy, key_count_digest.npy  (order-free wrap-around sums of a key
+      hash, and of hash x count, modulo 2**52), and one .npy per entry of `scalars`."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    lo = lo[:n]
+    hi = hi[:n] if hi is not None else None
+    cnt = cnt[:n].to(torch.int64)
+    order = torch.argsort(lo, stable=True)
+    if hi is not None:
+        order = order[torch.argsort(hi[order], stable=True)]
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        order = order[torch.from_numpy(idx).to(order.device)]
+    words = []
+    for w in ([lo] if hi is None else [lo, hi]):
+        w = w[order]
+        words += [w & 0xFFFFFFFF, (w >> 32) & 0xFFFFFFFF]
+    h = lo * _MIX1 + (hi * _MIX2 if hi is not None else 0)
+    h = (h ^ (h >> 31)) * _MIX2
+    arrays = {
+        "kmer_keys": torch.stack(words, dim=1),
+        "kmer_counts": cnt[order],
+        "n_kmers": n,
+        "count_sum": int(cnt.sum().item()),
+        "key_digest": int(h.sum().item()) & _MASK52,
+        "key_count_digest": int((h * cnt).sum().item()) & _MASK52,
+        **scalars,
+    }
+    for name, a in arrays.items():
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.array([a])
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+    print(f"[bench] wrote {len(arrays)} arrays ({min(n, DUMP_SAMPLE)} of {n} pairs) to {path}", file=sys.stderr)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,7 +121,13 @@ def parse_args(argv=None):
     ap.add_argument("--genome", type=int, default=100_000_000)
     ap.add_argument("--path", choices=["auto", "direct", "binned"], default="auto",
                     help="count pipeline (auto: the engine's choice; the others force it, for profiles and A/B runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what a plain run leaves out: the CPU baseline and its comparison "
+                         "with the GPU result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last step's (key, count) pairs to DIR/*.npy (float64; a seeded sample of "
+                         "at most %d pairs, sorted by key)" % DUMP_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-reads", type=int, default=10_000_000)
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N > 1 ranks on ONE GPU: gloo with host-staged collectives instead of RCCL "
@@ -101,6 +162,8 @@ def launch_ranks(args, argv) -> int:
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("bench.py: --dump-outputs is for --gpus 1 (at N > 1 every rank holds only its share)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -238,8 +301,9 @@ def run_count(args, world, rank, local_rank):
             dist.barrier()
         torch.cuda.synchronize()
 
+    n_last = 0                                           # entries of the last step's dump (--dump-outputs)
     for _ in range(args.warmup):
-        step()
+        n_last = step()
     if merger is None:
         _, distinct, windows = eng.stats()
     else:
@@ -250,7 +314,7 @@ def run_count(args, world, rank, local_rank):
     t0 = time.perf_counter()
     n_ge3 = 0
     for _ in range(args.steps):
-        n_ge3 = step()
+        n_ge3 = n_last = step()
     barrier()
     dt = time.perf_counter() - t0
     merge_ms[0] = sum(a.elapsed_time(b) for a, b in merge_events)
@@ -344,7 +408,10 @@ def run_count(args, world, rank, local_rank):
         },
     }
 
-    if world == 1 and not args.no_cpu_baseline and len(streams) == 1:
+    if args.dump_outputs:
+        _, d_last, w_last = eng.stats()
+        dump_outputs(args.dump_outputs, out_lo, out_hi, out_cnt, n_last, {"windows": w_last, "distinct": d_last})
+    if args.full and world == 1 and not args.no_cpu_baseline and len(streams) == 1:
         _cpu_baseline_count(out, ds, args, k, distinct, n_ge3, windows)
     print(json.dumps(out), flush=True)
     if world > 1:
@@ -429,15 +496,16 @@ def run_parent_filter(args, world, rank, local_rank):
             dist.barrier()
         torch.cuda.synchronize()
 
+    survivors_last = 0                       # of the last step, warm-up or timed (--dump-outputs)
     for _ in range(args.warmup):
-        step()
+        survivors_last = step()
     merge_s[0] = 0.0
     barrier()
     feng.profile(True)
     t0 = time.perf_counter()
     survivors = 0
     for _ in range(args.steps):
-        survivors = step()
+        survivors = survivors_last = step()
     barrier()
     dt = time.perf_counter() - t0
     kernel_ms, launches, positions = feng.profile_read()
@@ -487,7 +555,9 @@ def run_parent_filter(args, world, rank, local_rank):
             "model": "probe-only: 2-bit input read once + one 8 B key slot per window (windows that miss write nothing)",
         },
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, filt, None, counts, n_filter, {"survivors": survivors_last})
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from kmer_denovo_filter_amd.synth import stream_to_ascii
         from oracle import oracle as O
         O.build()
