@@ -23,6 +23,17 @@
  *     of the k-mer and its reverse complement (== kmer_utils.canonicalize,
  *     src/kmer_denovo_filter/kmer_utils.py:35-38).  k <= 32: one uint64 (lo);
  *     33 <= k <= 63: (lo, hi) pair.  `hi` arrays may be NULL when k <= 32.
+ *   - long keys, odd k from 65 to 201 (utils.py:299-311 accepts any odd k up to
+ *     201): W = ceil(2k/64) = 3..7 words per key, ROW-MAJOR (key i is words
+ *     [i*W, i*W + W)), word 0 the least significant 64 bits.  Engines for such k
+ *     take the `_w` entry points below; their (lo, hi) forms return
+ *     KDF_ERR_INVALID and name the `_w` form.  The read-stream entry points
+ *     (count / count --if / scan, host or device, the double-buffered upload)
+ *     work unchanged for every k.  A long engine always counts through the direct
+ *     kernels (no binned pipeline, sieve or fused dump: force_path 2 / 4 and
+ *     fused_dump 1 are KDF_ERR_INVALID) and is single-GPU only (kdf_export_parts*,
+ *     kdf_add_pairs_multi_dev, kdf_set_counts_dev and hash_shift are
+ *     KDF_ERR_INVALID).
  *
  * Read streams
  *   Reads are handed over as ONE 2-bit-packed base stream plus a 1-bit
@@ -56,7 +67,7 @@ typedef struct kdf_reader kdf_reader;
 
 /* ---------------------------------------------------------------- engine -- */
 
-/* Create an engine on HIP device `device` for k-mers of length k (1..63) with
+/* Create an engine on HIP device `device` for k-mers of length k (1..63, or odd 65..201) with
  * room for at least capacity_hint distinct keys before the first grow.
  * Replaces the process launch + `-m k -s SIZE` of `jellyfish count`
  * (core/jellyfish_wrappers.py:167-176,313-321; discovery/pipeline.py:114-122). */
@@ -368,6 +379,28 @@ const char *kdf_reader_error(const kdf_reader *r);
 int kdf_bam_write_subset(const char *src_bam, const char *dst_bam, const uint64_t *ordinals, uint64_t n,
                          const uint8_t *aux, const uint64_t *aux_offsets, int sort_and_index, int threads,
                          uint64_t *n_written);
+
+/* ------------------------------------------- long keys (odd k 65..201) ---- */
+
+/* Words per key of an engine for k: 1 (k <= 32), 2 (33..63), ceil(2k/64) for odd 65..201; 0 if no engine takes k. */
+int kdf_key_words(int k);
+/* Canonical key of one ASCII k-mer as ceil(2k/64) words, word 0 least significant (any k in 1..201;
+ * KDF_ERR_INVALID on a non-ACGT byte).  kmer_utils.canonicalize + kmer_to_int, split into words. */
+int kdf_canonical_w(const char *kmer, int k, uint64_t *words_out);
+/* kdf_add_pairs / kdf_load_filter / kdf_query / kdf_export_ge (and their _dev forms) for long engines: `keys`
+ * are n x W row-major words.  Same semantics as the (lo, hi) forms; KDF_ERR_INVALID on a k <= 63 engine.
+ * kdf_export_ge_w writes ascending key order (lexicographic from the top word down); kdf_export_ge_w_dev
+ * does when sorted != 0 (needs the counts array; at most 2^32 entries). */
+int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts, uint64_t n);
+int kdf_add_pairs_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts, uint64_t n);
+int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n);
+int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n);
+int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *counts_out);
+int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_counts_out);
+int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint32_t *counts_out,
+                    uint64_t cap, uint64_t *n_out);
+int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, void *d_counts_out,
+                        uint64_t cap, int sorted, uint64_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,17 @@ SYMBOLS = [
     ("kdf_reader_ref_name", c_char_p, [_P, c_int]),
     ("kdf_reader_close", None, [_P]),
     ("kdf_reader_error", c_char_p, [_P]),
+    # long keys (odd k 65..201): n x W row-major words
+    ("kdf_key_words", c_int, [c_int]),
+    ("kdf_canonical_w", c_int, [c_char_p, c_int, POINTER(c_uint64)]),
+    ("kdf_add_pairs_w", c_int, [_P, _P, _P, c_uint64]),
+    ("kdf_add_pairs_w_dev", c_int, [_P, _P, _P, c_uint64]),
+    ("kdf_load_filter_w", c_int, [_P, _P, c_uint64]),
+    ("kdf_load_filter_w_dev", c_int, [_P, _P, c_uint64]),
+    ("kdf_query_w", c_int, [_P, _P, c_uint64, _P]),
+    ("kdf_query_w_dev", c_int, [_P, _P, c_uint64, _P]),
+    ("kdf_export_ge_w", c_int, [_P, c_uint32, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_export_ge_w_dev", c_int, [_P, c_uint32, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
 ]
 
 _lib = None

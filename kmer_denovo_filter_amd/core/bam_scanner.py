@@ -24,7 +24,7 @@ import numpy as np
 
 from .. import jf_io
 from .._native import KdfError
-from ..engine import KmerEngine, hit_positions
+from ..engine import KmerEngine, mirror_engine, hit_positions
 from ..kmer_fasta import read_kmer_fasta_keys
 from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys
 
@@ -67,7 +67,7 @@ def _init_scan_worker(proband_data, kmer_size, min_distinct_kmers_per_read=1, de
         _worker_engine = None
     try:
         if isinstance(proband_data, str) and proband_data.endswith(".jf"):
-            eng = KmerEngine(kmer_size, capacity_hint=max(jf_io.index_records(proband_data), 1), device=device)
+            eng = mirror_engine(kmer_size, capacity_hint=max(jf_io.index_records(proband_data), 1), device=device)
             jf_io.load_index_into(eng, proband_data, expect_k=kmer_size)
             lo = None
         elif isinstance(proband_data, str):
@@ -77,7 +77,7 @@ def _init_scan_worker(proband_data, kmer_size, min_distinct_kmers_per_read=1, de
             lo, hi = kmers_to_keys(list(proband_data), kmer_size)
             cnt = np.ones(len(lo), np.uint32)
         if lo is not None:
-            eng = KmerEngine(kmer_size, capacity_hint=max(len(lo), 1), device=device)
+            eng = mirror_engine(kmer_size, capacity_hint=max(len(lo), 1), device=device)
             eng.add_pairs(lo, hi, cnt)
     except (KdfError, ValueError, OSError) as e:
         raise RuntimeError(f"jellyfish query failed: {e}") from e

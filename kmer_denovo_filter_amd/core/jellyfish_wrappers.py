@@ -21,7 +21,7 @@ import numpy as np
 
 from .. import dist_env, jf_io
 from .._native import KdfError
-from ..engine import KmerEngine
+from ..engine import mirror_engine
 from ..kmer_fasta import read_kmer_fasta_keys
 from ..reads import bam_reader, fasta_reader, keys_to_kmers, stream_batches_overlapped
 
@@ -149,7 +149,7 @@ def _scan_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent_
         lo, hi = read_kmer_fasta_keys(kmer_fasta, kmer_size)
         logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)",
                     kmer_size, threads, len(lo))
-        with KmerEngine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:
+        with mirror_engine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:
             eng.load_filter(lo, hi)
             _stream_bam(eng, parent_bam, ref_fasta, threads, filtered=True)
             _merge_filter_counts(eng, lo, hi)                  # (several ranks: every table now holds the summed counts)
@@ -196,7 +196,7 @@ def _merge_filter_counts(eng, lo, hi, dlo=None, dhi=None):
 
 
 def _count_fasta_to_index(fasta_path, kmer_size, out_path, capacity_hint, cmdline):
-    with KmerEngine(kmer_size, capacity_hint=capacity_hint) as eng:
+    with mirror_engine(kmer_size, capacity_hint=capacity_hint) as eng:
         with fasta_reader(fasta_path, kmer_size, max_bases=BATCH_BASES) as rd:
             for batch in rd:
                 eng.count(batch)
@@ -237,7 +237,7 @@ def _merge_jf_files(jf_files, merged_path, threads=4):
     merge_start = time.monotonic()
     try:
         k0, lo, hi, cnt = jf_io.read_index(jf_files[0])
-        with KmerEngine(k0, capacity_hint=max(len(lo), 1)) as eng:
+        with mirror_engine(k0, capacity_hint=max(len(lo), 1)) as eng:
             eng.add_pairs(lo, hi, cnt)
             for f in jf_files[1:]:
                 k1, lo, hi, cnt = jf_io.read_index(f, expect_k=k0)

@@ -4,6 +4,7 @@
 // runs on the GPU or returns an error.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +19,7 @@
 // sorted export lives in kdf_sort.hip (rocPRIM radix sort)
 int kdf_sort_pairs_device(uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt, uint64_t n,
                           hipStream_t stream, std::string &err);
+int kdf_sort_rows_device(uint64_t *d_keys, int words, uint32_t *d_cnt, uint64_t n, hipStream_t stream, std::string &err);
 
 // ===========================================================================
 // kernels
@@ -298,6 +300,9 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
     }
 }
 
+// long keys (odd k 65..201): table layout, claim protocol and kernels
+#include "kdf_long.h"
+
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
 // (discovery/pipeline.py:377-443: a whole parent's reads against the child's candidate k-mers), so partitioning
@@ -440,7 +445,7 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 struct kdf_engine {
     int device = 0;
     int k = 0;
-    int kw = 1;
+    int kw = 1;                   // key words: 1 narrow, 2 wide, 3..7 long (kdf_long.h)
     int n_cu = 256;               // compute units of the device (persistent-kernel grids)
     uint64_t dev_total_bytes = 0; // HBM of the device (sizes the entry ring's budget)
     KdfTable t{};                 // live table
@@ -567,7 +572,7 @@ static int table_alloc(kdf_engine *h, uint32_t log2cap, KdfTable &t, bool clear 
     t.hshift = h->opt_hash_shift;
     {
         hipError_t e = hipMalloc((void **)&t.lo, cap * 8);
-        if (e == hipSuccess && h->kw == 2) e = hipMalloc((void **)&t.hi, cap * 8);
+        if (e == hipSuccess && h->kw >= 2) e = hipMalloc((void **)&t.hi, cap * 8 * (h->kw - 1));   // long keys: words 1 .. W-1
         if (e == hipSuccess) e = hipMalloc((void **)&t.cnt, cap * 4);
         if (e != hipSuccess) {
             if (t.lo) (void)hipFree(t.lo);
@@ -582,7 +587,7 @@ static int table_alloc(kdf_engine *h, uint32_t log2cap, KdfTable &t, bool clear 
     }
     if (!clear) return KDF_OK;                       // the caller keeps the engine's deferred-clear flag set
     HIPCHK(h, hipMemsetAsync(t.lo, 0xFF, cap * 8, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemsetAsync(t.hi, 0xFF, cap * 8, h->stream));
+    if (h->kw >= 2) HIPCHK(h, hipMemsetAsync(t.hi, 0xFF, cap * 8 * (h->kw - 1), h->stream));
     HIPCHK(h, hipMemsetAsync(t.cnt, 0, cap * 4, h->stream));
     return KDF_OK;
 }
@@ -598,7 +603,7 @@ static void table_free(KdfTable &t) {
 static int materialize(kdf_engine *h) {
     if (!h->lazy_empty) return KDF_OK;
     HIPCHK(h, hipMemsetAsync(h->t.lo, 0xFF, h->cap * 8, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemsetAsync(h->t.hi, 0xFF, h->cap * 8, h->stream));
+    if (h->kw >= 2) HIPCHK(h, hipMemsetAsync(h->t.hi, 0xFF, h->cap * 8 * (h->kw - 1), h->stream));
     HIPCHK(h, hipMemsetAsync(h->t.cnt, 0, h->cap * 4, h->stream));
     h->lazy_empty = false;
     return KDF_OK;
@@ -638,6 +643,20 @@ static int ctl_reset(kdf_engine *h, bool keep_windows) {
 
 template <typename F>
 static int by_width(kdf_engine *h, F &&f) { return h->kw == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{}); }
+// long engines: W = 3 .. 7
+static bool is_long(const kdf_engine *h) { return h->kw > 2; }
+// bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
+static int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
+template <typename F>
+static int by_long(kdf_engine *h, F &&f) {
+    switch (h->kw) {
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return f(std::integral_constant<int, 7>{});
+    }
+}
 
 // rehash the live table into one with 2^new_log2 slots
 static int table_rehash(kdf_engine *h, uint32_t new_log2) {
@@ -664,7 +683,15 @@ static int table_rehash(kdf_engine *h, uint32_t new_log2) {
     for (uint64_t off = 0; off < old_cap; off += 1ull << 30) {
         const uint64_t n = std::min<uint64_t>(1ull << 30, old_cap - off);
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (h->kw == 1)
+        if (is_long(h))
+            by_long(h, [&](auto Wc) {
+                constexpr int W = decltype(Wc)::value;
+                hipLaunchKernelGGL(kdf_long_insert_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, (const uint64_t *)h->t.lo + off,
+                                   (const uint64_t *)h->t.hi + off, (uint64_t)1, old_cap, (const uint32_t *)h->t.cnt + off, n, nt, h->ctl, 1,
+                                   long_top_bits(h));
+                return 0;
+            });
+        else if (h->kw == 1)
             hipLaunchKernelGGL(kdf_insert_keys_kernel<1>, dim3(blocks), dim3(256), 0, h->stream,
                                (const uint64_t *)h->t.lo + off, (const uint64_t *)nullptr, (const uint32_t *)h->t.cnt + off, n, nt, h->ctl, 1, 1);
         else
@@ -690,14 +717,21 @@ static int table_rehash(kdf_engine *h, uint32_t new_log2) {
 
 template <int MODE>
 static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid,
-                          uint64_t tile0, uint64_t n_tiles, uint64_t *d_hits) {
+                          uint64_t tile0, uint64_t n_tiles, uint64_t *d_hits, uint64_t n_bases) {
     const unsigned blocks = (unsigned)((n_tiles + 255) / 256);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (h->prof) {
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, h->stream);
     }
-    if (h->kw == 1)
+    if (is_long(h))       // (n_bases: the long kernel clamps its loads to the buffers kdf_stream_words(n_bases) sizes)
+        by_long(h, [&](auto Wc) {
+            constexpr int W = decltype(Wc)::value;
+            hipLaunchKernelGGL((kdf_long_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
+                               d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
+            return 0;
+        });
+    else if (h->kw == 1)
         hipLaunchKernelGGL((kdf_stream_kernel<1, MODE>), dim3(blocks), dim3(256), 0, h->stream,
                            d_packed, d_invalid, tile0, n_tiles, h->k, h->t, h->ctl, d_hits);
     else
@@ -1115,6 +1149,7 @@ static int kb_flush_ring(kdf_engine *h) {
 
 // can the binned pipeline work on this engine's table at all?
 static bool kb_eligible(const kdf_engine *h) {
+    if (is_long(h)) return false;                              // long keys: the direct kernels only (kdf_long.h)
     if (h->opt_hash_shift) return false;                       // an owner table: the bins assume home = top hash bits
     if (h->t.log2cap <= h->t.bucket_bits) return false;        // a single bucket: nothing to partition
     return h->opt_force_path != 1;
@@ -1152,7 +1187,7 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
             continue;
         }
         uint64_t chunk = std::min<uint64_t>(n_tiles - tile, std::max<uint64_t>(room / KDF_TILE, 1));
-        launch_stream<MODE_INSERT>(h, d_packed, d_invalid, tile, chunk, nullptr);
+        launch_stream<MODE_INSERT>(h, d_packed, d_invalid, tile, chunk, nullptr, n_bases);
         HIPCHK(h, hipGetLastError());
         bool full = false;
         int rc = ctl_sync(h, &full);
@@ -1274,7 +1309,7 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
     }
     { int rc0 = kb_flush_ring(h); if (rc0) return rc0; }           // (binned --if passes pending from earlier batches)
     h->last_path = 0;
-    launch_stream<MODE_FILTERED>(h, d_packed, d_invalid, 0, n_tiles, nullptr);
+    launch_stream<MODE_FILTERED>(h, d_packed, d_invalid, 0, n_tiles, nullptr, n_bases);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
@@ -1309,6 +1344,13 @@ static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *
 // C ABI
 // ===========================================================================
 
+// The (lo, hi) key forms take k <= 63 engines only; a long engine names the W-word form to use instead.  The multi-GPU
+// entry points are single-GPU-only for long keys.
+#define KDF_REFUSE_LONG(h, fn, wfn) \
+    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: k=%d takes %d-word keys: use %s", fn, (h)->k, (h)->kw, wfn); } while (0)
+#define KDF_REFUSE_LONG_MULTI(h, fn) \
+    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: not available for k > 63 (long keys count on one GPU)", fn); } while (0)
+
 extern "C" {
 
 const char *kdf_last_error(const kdf_engine *h) { return h ? h->err.c_str() : g_err.c_str(); }
@@ -1316,14 +1358,15 @@ const char *kdf_last_error(const kdf_engine *h) { return h ? h->err.c_str() : g_
 int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     if (!out) return fail(nullptr, KDF_ERR_INVALID, "kdf_create: out is NULL");
     *out = nullptr;
-    if (k < 1 || k > 63) return fail(nullptr, KDF_ERR_INVALID, "kdf_create: k=%d out of range 1..63", k);
+    if (k < 1 || k > KDF_LONG_MAX_K || (k > 63 && k % 2 == 0))
+        return fail(nullptr, KDF_ERR_INVALID, "kdf_create: k=%d out of range (1..63, or odd 65..%d)", k, KDF_LONG_MAX_K);
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0)
         return fail(nullptr, KDF_ERR_HIP, "kdf_create: no HIP device available (%s)", hipGetErrorString(e));
     if (device < 0 || device >= ndev) return fail(nullptr, KDF_ERR_INVALID, "kdf_create: device %d of %d", device, ndev);
     kdf_engine *h = new kdf_engine();
-    h->device = device; h->k = k; h->kw = k <= 32 ? 1 : 2;
+    h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
@@ -1593,6 +1636,7 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
 
 int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, uint64_t n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_load_filter", "kdf_load_filter_w");
     if (n && (!keys_lo || (h->kw == 2 && !keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_load_filter: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
@@ -1609,6 +1653,7 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
 
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_load_filter_dev", "kdf_load_filter_w_dev");
     if (n && (!d_keys_lo || (h->kw == 2 && !d_keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     return load_filter_core(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, n);
@@ -1724,6 +1769,7 @@ static int add_pairs_dev(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_
 int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_keys_lo, const void *const *d_keys_hi,
                             const void *const *d_counts, const uint64_t *n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG_MULTI(h, "kdf_add_pairs_multi_dev");
     if (nseg == 0) return KDF_OK;
     if (!d_keys_lo || !n || !d_counts) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_multi_dev: NULL pointer");
     if (h->kw == 2 && !d_keys_hi) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_multi_dev: wide keys need the hi words");
@@ -1740,6 +1786,7 @@ int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_k
 
 int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_add_pairs_dev", "kdf_add_pairs_w_dev");
     if (n && (!d_keys_lo || (h->kw == 2 && !d_keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     return add_pairs_dev(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, (const uint32_t *)d_counts, n);
@@ -1747,6 +1794,7 @@ int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_h
 
 int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, const uint32_t *counts, uint64_t n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_add_pairs", "kdf_add_pairs_w");
     if (n == 0) return KDF_OK;
     if (!keys_lo || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1767,6 +1815,7 @@ int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_h
 
 int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG_MULTI(h, "kdf_set_counts_dev");
     if (n == 0) return KDF_OK;
     if (!d_keys_lo || !d_counts || (h->kw == 2 && !d_keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_set_counts_dev: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1809,6 +1858,7 @@ int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed, const uint64
 
 int kdf_query_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n, void *d_counts_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_query_dev", "kdf_query_w_dev");
     if (n == 0) return KDF_OK;
     if (!d_keys_lo || !d_counts_out || (h->kw == 2 && !d_keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_query_dev: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1827,6 +1877,7 @@ int kdf_query_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, u
 
 int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, uint64_t n, uint32_t *counts_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_REFUSE_LONG(h, "kdf_query", "kdf_query_w");
     if (n == 0) return KDF_OK;
     if (!keys_lo || !counts_out || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_query: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
@@ -1856,7 +1907,14 @@ static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *
     HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor
     const uint64_t waves = (h->cap + KDF_EXPORT_ROWS * 64 - 1) / (KDF_EXPORT_ROWS * 64);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    if (write) {                                            // one read of the table (any min_count: occupancy is tested on the key)
+    if (is_long(h)) {                                       // rows of W words into olo
+        by_long(h, [&](auto Wc) {
+            constexpr int W = decltype(Wc)::value;
+            if (write) hipLaunchKernelGGL((kdf_long_export_kernel<W, true>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ocnt, out_cap);
+            else hipLaunchKernelGGL((kdf_long_export_kernel<W, false>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ocnt, out_cap);
+            return 0;
+        });
+    } else if (write) {                                            // one read of the table (any min_count: occupancy is tested on the key)
         const unsigned rows = h->kw == 1 ? KDF_EXPORT1_ROWS : KDF_EXPORT1_ROWS / 2;
         const uint64_t w1 = (h->cap + rows * 64 - 1) / (rows * 64);
         const unsigned wpb = KDF_EXPORT1_THREADS / 64;
@@ -1935,6 +1993,7 @@ static int export_parts(kdf_engine *h, uint32_t min_count, uint32_t parts, bool 
 int kdf_export_parts_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void *d_keys_lo_out, void *d_keys_hi_out,
                          void *d_counts_out, uint64_t cap, uint64_t *part_counts_out, uint64_t *n_out) {
     if (!h || !n_out || !part_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_export_parts_dev: NULL pointer");
+    KDF_REFUSE_LONG_MULTI(h, "kdf_export_parts_dev");
     return export_parts(h, min_count, parts, false, d_keys_lo_out, d_keys_hi_out, d_counts_out, cap, part_counts_out, nullptr, n_out,
                         "kdf_export_parts_dev");
 }
@@ -1942,6 +2001,7 @@ int kdf_export_parts_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void
 int kdf_export_parts_packed_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void *d_buf, uint64_t cap_bytes,
                                 uint64_t *part_counts_out, uint64_t *part_bytes_out, uint64_t *n_out) {
     if (!h || !n_out || !part_counts_out || !part_bytes_out) return fail(h, KDF_ERR_INVALID, "kdf_export_parts_packed_dev: NULL pointer");
+    KDF_REFUSE_LONG_MULTI(h, "kdf_export_parts_packed_dev");
     return export_parts(h, min_count, parts, true, d_buf, nullptr, nullptr, cap_bytes, part_counts_out, part_bytes_out, n_out,
                         "kdf_export_parts_packed_dev");
 }
@@ -1965,6 +2025,7 @@ int kdf_count_ge(kdf_engine *h, uint32_t min_count, uint64_t *n_out) {
 int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out, uint64_t *keys_hi_out,
                   uint32_t *counts_out, uint64_t cap, uint64_t *n_out) {
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge: NULL pointer");
+    KDF_REFUSE_LONG(h, "kdf_export_ge", "kdf_export_ge_w");
     HIPCHK(h, hipSetDevice(h->device));
     uint64_t n = 0;
     int rc = export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, &n);
@@ -1997,6 +2058,7 @@ int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out, uint
 int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out, void *d_keys_hi_out,
                       void *d_counts_out, uint64_t cap, int sorted, uint64_t *n_out) {
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_dev: NULL pointer");
+    KDF_REFUSE_LONG(h, "kdf_export_ge_dev", "kdf_export_ge_w_dev");
     HIPCHK(h, hipSetDevice(h->device));
     if (cap && (!d_keys_lo_out || (h->kw == 2 && !d_keys_hi_out))) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_dev: NULL key output");
     // ONE pass over the table: entries are appended through the cursor, nothing is written past `cap`, and the
@@ -2027,7 +2089,7 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
     { int rcf = pending_flush(h); if (rcf) return rcf; }
     { int rc0 = materialize(h); if (rc0) return rc0; }
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if (h->opt_force_path != 1 && n_tiles * KDF_TILE < (1ull << 32)) {
+    if (!is_long(h) && h->opt_force_path != 1 && n_tiles * KDF_TILE < (1ull << 32)) {
         // through the membership sieve (section 3.5 of DESIGN.md): an index that was loaded with kdf_add_pairs has none yet
         int rc;
         if (!h->sieve_valid) {
@@ -2059,7 +2121,7 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
             return KDF_OK;
         }
     }
-    launch_stream<MODE_SCAN>(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, 0, n_tiles, (uint64_t *)d_hit_bits);
+    launch_stream<MODE_SCAN>(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, 0, n_tiles, (uint64_t *)d_hit_bits, n_bases);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
@@ -2078,6 +2140,16 @@ static inline void host_window_key(const uint64_t *packed, uint64_t p, int k, ui
     for (int j = 0; j < k; ++j) fwd |= ((e >> (2 * j)) & 3) << (2 * (k - 1 - j));
     const unsigned __int128 c = fwd < rc ? fwd : rc;
     klo = (uint64_t)c; khi = (uint64_t)(c >> 64);
+}
+
+// the same for long keys: ceil(2k/64) words, word 0 least significant (kdf_canonical_w's rule)
+static inline void host_window_key_w(const uint64_t *packed, uint64_t p, int k, uint64_t *w) {
+    std::string s((size_t)k, 'A');
+    for (int j = 0; j < k; ++j) {
+        const uint64_t q = p + j;
+        s[(size_t)j] = "ACGT"[(packed[q >> 5] >> ((q & 31) * 2)) & 3];
+    }
+    (void)kdf_canonical_w(s.data(), k, w);
 }
 
 int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
@@ -2102,9 +2174,10 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     if (!read_offsets || !distinct_out) return KDF_OK;
     // distinct hit k-mers per read: only reads with hits are touched
     std::vector<std::pair<uint64_t, uint64_t>> keys;
+    std::vector<std::array<uint64_t, 7>> keys_w;             // long keys: W <= 7 words (unused words 0)
     for (int64_t r = 0; r < n_reads; ++r) {
         const uint64_t b = (uint64_t)read_offsets[r], e = (uint64_t)read_offsets[r + 1];
-        keys.clear();
+        keys.clear(); keys_w.clear();
         for (uint64_t wd = b >> 6; wd <= (e ? (e - 1) >> 6 : 0) && wd < n_tiles; ++wd) {
             uint64_t bits = hit_bits[wd];
             while (bits) {
@@ -2112,15 +2185,236 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
                 bits &= bits - 1;
                 const uint64_t p = (wd << 6) + bit;
                 if (p < b || p >= e) continue;
+                if (is_long(h)) {
+                    std::array<uint64_t, 7> w{};
+                    host_window_key_w(packed, p, h->k, w.data());
+                    keys_w.push_back(w);
+                    continue;
+                }
                 uint64_t lo, hi;
                 host_window_key(packed, p, h->k, lo, hi);
                 keys.emplace_back(hi, lo);
             }
         }
+        if (!keys_w.empty()) {
+            std::sort(keys_w.begin(), keys_w.end());
+            distinct_out[r] = (uint32_t)(std::unique(keys_w.begin(), keys_w.end()) - keys_w.begin());
+        }
         if (keys.empty()) continue;
         std::sort(keys.begin(), keys.end());
         distinct_out[r] = (uint32_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
     }
+    return KDF_OK;
+}
+
+// ---- long keys (odd k 65..201): W-word keys, row-major -----------------------------------------------------------
+#define KDF_NEED_LONG(h, fn) \
+    do { if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: takes engines for odd k 65..%d only (k=%d: use the (lo, hi) form)", fn, KDF_LONG_MAX_K, (h)->k); } while (0)
+
+static void long_insert_launch(kdf_engine *h, const uint64_t *d_keys, const uint32_t *d_cnt, uint64_t n) {
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    by_long(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        hipLaunchKernelGGL(kdf_long_insert_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, d_keys, d_keys + 1, (uint64_t)W, (uint64_t)1,
+                           d_cnt, n, h->t, h->ctl, 0, long_top_bits(h));
+        return 0;
+    });
+}
+
+__global__ void kdf_ctl_clear_error_bits_kernel(KdfCtl *ctl, unsigned int bits) { atomicAnd(&ctl->error, ~bits); }
+
+// after a long_insert_launch of caller keys: a key with a top-word bit at or above 2k - 64 (W - 1) was refused (error
+// bit 4).  Only that bit is cleared: a bucket overflow of the same launch (bit 1) stays raised and is reported too.
+static int long_bad_keys(kdf_engine *h, const char *fn) {
+    const unsigned int err = (unsigned int)h->h_out4[2];
+    if (!(err & 4)) return KDF_OK;
+    hipLaunchKernelGGL(kdf_ctl_clear_error_bits_kernel, dim3(1), dim3(1), 0, h->stream, h->ctl, 4u);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return fail(h, KDF_ERR_INVALID, "%s: a key's top word has bits at or above bit %d (no k-mer of k=%d); it was left out%s", fn,
+                long_top_bits(h), h->k, (err & 1) ? "; a bucket also overflowed (KDF_ERR_TABLE_FULL)" : "");
+}
+
+// insert-or-add n row-major keys (device) with optional counts; grows first so that they fit at load <= 0.5
+static int long_add_pairs(kdf_engine *h, const uint64_t *d_keys, const uint32_t *d_cnt, uint64_t n) {
+    if (n == 0) return KDF_OK;
+    int rc;
+    if ((rc = pending_flush(h))) return rc;
+    if ((rc = ctl_sync(h, nullptr))) return rc;
+    const uint32_t want = cap_log2_for(h->distinct + n);
+    if (want > h->t.log2cap && (rc = table_rehash(h, want))) return rc;
+    if ((rc = materialize(h))) return rc;
+    for (uint64_t off = 0; off < n; off += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
+        const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+        long_insert_launch(h, d_keys + off * h->kw, d_cnt ? d_cnt + off : nullptr, m);
+    }
+    HIPCHK(h, hipGetLastError());
+    bool full = false;
+    if ((rc = ctl_sync(h, &full))) return rc;
+    if ((rc = long_bad_keys(h, "kdf_add_pairs_w"))) return rc;
+    if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_add_pairs_w: bucket overflow");
+    return KDF_OK;
+}
+
+static int long_load_filter(kdf_engine *h, const uint64_t *d_keys, uint64_t n) {
+    int rc;
+    h->sieve_valid = false;
+    if ((rc = pending_drop(h))) return rc;
+    const uint32_t want = cap_log2_for(n);
+    if (want != h->t.log2cap) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        table_free(h->t);
+        if ((rc = table_alloc(h, want, h->t))) return rc;
+        h->cap = 1ull << want;
+        if ((rc = ctl_reset(h, false))) return rc;
+        h->distinct = 0; h->windows = 0; h->lazy_empty = false; h->filter_mode = false;
+    } else if ((rc = kdf_clear(h))) return rc;
+    if ((rc = materialize(h))) return rc;
+    h->filter_mode = true;
+    if (n) {
+        long_insert_launch(h, d_keys, nullptr, n);
+        HIPCHK(h, hipGetLastError());
+        bool full = false;
+        if ((rc = ctl_sync(h, &full))) return rc;
+        if ((rc = long_bad_keys(h, "kdf_load_filter_w"))) return rc;
+        if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_load_filter_w: bucket overflow");
+    }
+    return KDF_OK;
+}
+
+int kdf_key_words(int k) {
+    if (k >= 1 && k <= 32) return 1;
+    if (k >= 33 && k <= 63) return 2;
+    if (k >= KDF_LONG_MIN_K && k <= KDF_LONG_MAX_K && k % 2 == 1) return (2 * k + 63) / 64;
+    return 0;
+}
+
+int kdf_add_pairs_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts, uint64_t n) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_add_pairs_w_dev");
+    if (n && !d_keys) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_w_dev: NULL keys");
+    HIPCHK(h, hipSetDevice(h->device));
+    h->sieve_valid = false;
+    return long_add_pairs(h, (const uint64_t *)d_keys, (const uint32_t *)d_counts, n);
+}
+
+int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts, uint64_t n) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_add_pairs_w");
+    if (n == 0) return KDF_OK;
+    if (!keys) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_w: NULL keys");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
+    if (counts) {
+        if ((rc = stage_reserve(h, 0, n * 4))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->stage[0], counts, n * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    return long_add_pairs(h, (const uint64_t *)h->stage[2], counts ? (const uint32_t *)h->stage[0] : nullptr, n);
+}
+
+int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_load_filter_w_dev");
+    if (n && !d_keys) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_w_dev: NULL keys");
+    HIPCHK(h, hipSetDevice(h->device));
+    return long_load_filter(h, (const uint64_t *)d_keys, n);
+}
+
+int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_load_filter_w");
+    if (n && !keys) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_w: NULL keys");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (n) {
+        int rc;
+        if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
+    }
+    return long_load_filter(h, (const uint64_t *)h->stage[2], n);
+}
+
+int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_counts_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_query_w_dev");
+    if (n == 0) return KDF_OK;
+    if (!d_keys || !d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_query_w_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    { int rc0 = materialize(h); if (rc0) return rc0; }
+    for (uint64_t off = 0; off < n; off += 1ull << 30) {
+        const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+        by_long(h, [&](auto Wc) {
+            constexpr int W = decltype(Wc)::value;
+            hipLaunchKernelGGL(kdf_long_query_kernel<W>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream,
+                               (const uint64_t *)d_keys + off * W, m, h->t, (uint32_t *)d_counts_out + off, long_top_bits(h));
+            return 0;
+        });
+    }
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *counts_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_query_w");
+    if (n == 0) return KDF_OK;
+    if (!keys || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_query_w: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
+    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
+    if ((rc = kdf_query_w_dev(h, h->stage[2], n, h->stage[0]))) return rc;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, void *d_counts_out, uint64_t cap,
+                        int sorted, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: NULL pointer");
+    KDF_NEED_LONG(h, "kdf_export_ge_w_dev");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (cap && !d_keys_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: NULL key output");
+    uint64_t n = 0;
+    int rc = export_pass(h, min_count, true, (uint64_t *)d_keys_out, nullptr, (uint32_t *)d_counts_out, cap, &n);
+    if (rc) return rc;
+    *n_out = n;
+    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: %llu entries, room for %llu",
+                             (unsigned long long)n, (unsigned long long)cap);
+    if (sorted && n) {
+        if (!d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: sorted export needs the counts array");
+        std::string serr;
+        if (kdf_sort_rows_device((uint64_t *)d_keys_out, h->kw, (uint32_t *)d_counts_out, n, h->stream, serr))
+            return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: sort failed: %s", serr.c_str());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint32_t *counts_out, uint64_t cap,
+                    uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL pointer");
+    KDF_NEED_LONG(h, "kdf_export_ge_w");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t n = 0;
+    int rc = export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, &n);
+    if (rc) return rc;
+    *n_out = n;
+    if (n == 0) return KDF_OK;
+    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: %llu entries, room for %llu",
+                             (unsigned long long)n, (unsigned long long)cap);
+    if (!keys_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL key output");
+    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
+    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
+    uint64_t n2 = 0;
+    if ((rc = kdf_export_ge_w_dev(h, min_count, h->stage[2], h->stage[0], n, 1, &n2))) return rc;
+    if (n2 != n) return fail(h, KDF_ERR_STATE, "kdf_export_ge_w: table changed between passes");
+    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[2], n * 8 * h->kw, hipMemcpyDeviceToHost, h->stream));
+    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
@@ -2175,10 +2469,15 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
         const uint32_t bb = std::min<uint32_t>(h->t.log2cap, KB_BB_SMALL(h->kw) + (h->t.log2cap >= h->opt_big_bucket_log2cap ? 1u : 0u));
         if (bb != h->t.bucket_bits) { int rc = table_rehash(h, h->t.log2cap); if (rc) return rc; }     // same slots, other buckets
     }
-    else if (n == "force_path") h->opt_force_path = (int)value;
+    else if (n == "force_path") {
+        if (is_long(h) && (value == 2 || value == 4))
+            return fail(h, KDF_ERR_INVALID, "force_path %lld: k=%d counts through the direct kernels only (no binned pipeline or sieve for k > 63)", (long long)value, h->k);
+        h->opt_force_path = (int)value;
+    }
     else if (n == "merge_min_pairs") h->opt_merge_min_pairs = (uint64_t)value;
     else if (n == "hash_shift") {
         if (value > 8) return fail(h, KDF_ERR_INVALID, "hash_shift must be 0..8");
+        if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "hash_shift: not available for k > 63 (long keys count on one GPU)");
         if ((uint32_t)value != h->opt_hash_shift) {
             int rc = ctl_sync(h, nullptr);
             if (rc) return rc;
@@ -2188,7 +2487,10 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "defer") h->opt_defer = value != 0;
     else if (n == "defer_max_bytes") h->opt_defer_max_bytes = (uint64_t)value;
-    else if (n == "fused_dump") h->opt_fused_dump = value != 0;
+    else if (n == "fused_dump") {
+        if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "fused_dump: not available for k > 63 (no binned pipeline for long keys)");
+        h->opt_fused_dump = value != 0;
+    }
     else if (n == "l1_positions") h->opt_l1_positions = (uint64_t)std::max<int64_t>(value, KDF_TILE);
     else if (n == "l1_direct_positions") h->opt_l1_direct_positions = (uint64_t)std::max<int64_t>(value, 0);
     else if (n == "sieve_bits") h->opt_sieve_bits = (int)value;

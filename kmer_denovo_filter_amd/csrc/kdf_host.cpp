@@ -816,6 +816,26 @@ int kdf_canonical(const char *kmer, int k, uint64_t *lo, uint64_t *hi) {
     return KDF_OK;
 }
 
+int kdf_canonical_w(const char *kmer, int k, uint64_t *words_out) {
+    if (!kmer || !words_out || k < 1 || k > 201) return KDF_ERR_INVALID;
+    const int W = (2 * k + 63) / 64;
+    uint64_t f[7] = {0}, r[7] = {0};
+    for (int i = 0; i < k; ++i) {
+        const uint8_t c = kCode.t[(uint8_t)kmer[i]];
+        if (c > 3) return KDF_ERR_INVALID;
+        // forward: (f << 2) | c; reverse complement: base i lands at bits 2i of r
+        for (int j = W - 1; j >= 1; --j) f[j] = (f[j] << 2) | (f[j - 1] >> 62);
+        f[0] = (f[0] << 2) | c;
+        r[i >> 5] |= (uint64_t)(3 - c) << (2 * (i & 31));
+    }
+    const int tb = 2 * k - 64 * (W - 1);
+    if (tb < 64) f[W - 1] &= (1ull << tb) - 1;
+    bool lt = false;
+    for (int j = W - 1; j >= 0; --j) if (f[j] != r[j]) { lt = f[j] < r[j]; break; }
+    for (int j = 0; j < W; ++j) words_out[j] = lt ? f[j] : r[j];
+    return KDF_OK;
+}
+
 int kdf_pack_reads(const char *ascii, const int64_t *offsets, int64_t n_reads, uint64_t *packed_out,
                    uint64_t *invalid_out, int64_t *stream_offsets_out, uint64_t *n_bases_out) {
     if (n_reads < 0 || (n_reads && (!ascii || !offsets)) || !packed_out || !invalid_out) return KDF_ERR_INVALID;

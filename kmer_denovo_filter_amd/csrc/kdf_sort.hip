@@ -1,7 +1,8 @@
 // kdf_sort.hip -- ascending key order for kdf_export_ge (deterministic dump
 // order).  Not on the hot path: rocPRIM's radix sort is used as a library sort.
 // Narrow keys: one pair sort (key -> count).  Wide keys: LSD over the two
-// words with an index permutation (rocPRIM's radix sort is stable).
+// words with an index permutation (rocPRIM's radix sort is stable).  Long keys
+// (W = 3..7 row-major words): the same LSD over W passes, word 0 first.
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -69,6 +70,53 @@ int kdf_sort_pairs_device(uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt, uint6
     SCHK(hipMemcpyAsync(d_lo, k0, n * 8, hipMemcpyDeviceToDevice, stream));
     SCHK(hipMemcpyAsync(d_hi, k1, n * 8, hipMemcpyDeviceToDevice, stream));
     SCHK(hipMemcpyAsync(d_cnt, b.p[5], n * 4, hipMemcpyDeviceToDevice, stream));
+    SCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+namespace {
+// word j of the row that idx[i] names (the key word of the next LSD pass)
+__global__ void gather_word_kernel(const uint64_t *__restrict__ rows, int words, int j, const uint32_t *__restrict__ idx,
+                                   uint64_t *__restrict__ dst, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = rows[(uint64_t)idx[i] * words + j];
+}
+__global__ void gather_rows_kernel(const uint64_t *__restrict__ rows, int words, const uint32_t *__restrict__ idx,
+                                   uint64_t *__restrict__ dst, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) for (int j = 0; j < words; ++j) dst[i * words + j] = rows[(uint64_t)idx[i] * words + j];
+}
+}  // namespace
+
+// Long keys: ascending = lexicographic from the top word (words - 1) down.  d_cnt may be NULL.
+int kdf_sort_rows_device(uint64_t *d_keys, int words, uint32_t *d_cnt, uint64_t n, hipStream_t stream, std::string &err) {
+    if (n < 2) return 0;
+    if (n > 0xFFFFFFFFull) { err = "long-key export larger than 2^32 entries"; return 1; }
+    Bufs b;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    uint32_t *idx0, *idx1; uint64_t *k0, *k1;
+    SCHK(hipMalloc(&b.p[0], n * 4)); idx0 = (uint32_t *)b.p[0];
+    SCHK(hipMalloc(&b.p[1], n * 4)); idx1 = (uint32_t *)b.p[1];
+    SCHK(hipMalloc(&b.p[2], n * 8)); k0 = (uint64_t *)b.p[2];
+    SCHK(hipMalloc(&b.p[3], n * 8)); k1 = (uint64_t *)b.p[3];
+    hipLaunchKernelGGL(iota_kernel, dim3(blocks), dim3(256), 0, stream, idx0, n);
+    size_t tmp = 0;
+    SCHK(rocprim::radix_sort_pairs(nullptr, tmp, k0, k1, idx0, idx1, n, 0, 64, stream));
+    SCHK(hipMalloc(&b.p[4], tmp ? tmp : 8));
+    for (int j = 0; j < words; ++j) {          // stable passes carry the permutation: idx0 in, idx1 out, swapped
+        hipLaunchKernelGGL(gather_word_kernel, dim3(blocks), dim3(256), 0, stream, (const uint64_t *)d_keys, words, j, (const uint32_t *)idx0, k0, n);
+        SCHK(rocprim::radix_sort_pairs(b.p[4], tmp, k0, k1, idx0, idx1, n, 0, 64, stream));
+        std::swap(idx0, idx1);
+    }
+    SCHK(hipMalloc(&b.p[5], n * 8 * words));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks), dim3(256), 0, stream, (const uint64_t *)d_keys, words, (const uint32_t *)idx0, (uint64_t *)b.p[5], n);
+    SCHK(hipMemcpyAsync(d_keys, b.p[5], n * 8 * words, hipMemcpyDeviceToDevice, stream));
+    if (d_cnt) {
+        SCHK(hipMalloc(&b.p[6], n * 4));
+        hipLaunchKernelGGL(gather_kernel<uint32_t>, dim3(blocks), dim3(256), 0, stream, (const uint32_t *)d_cnt, (const uint32_t *)idx0, (uint32_t *)b.p[6], n);
+        SCHK(hipMemcpyAsync(d_cnt, b.p[6], n * 4, hipMemcpyDeviceToDevice, stream));
+    }
+    SCHK(hipGetLastError());
     SCHK(hipStreamSynchronize(stream));
     return 0;
 }

@@ -8,6 +8,9 @@ mirror keeps that contract -- every file is still written, in the reference's
 this registry takes the keys from device memory (``kdf_load_filter_dev`` /
 ``kdf_query_dev``) instead of parsing the text back and copying it up again.
 torch is the holder of the device arrays here, nothing more.
+
+Long k-mers (odd k from 65 to 201): one (n, W) int64 tensor of key rows in place of
+(lo, hi), hi = None -- the form a long KmerEngine takes in the lo position.
 """
 from __future__ import annotations
 
@@ -55,7 +58,9 @@ def forget(path: str):
 
 
 def to_host(lo, hi) -> Tuple[np.ndarray, np.ndarray]:
-    """Device key tensors -> the (lo, hi) uint64 arrays the FASTA writer takes."""
+    """Device key tensors -> the (lo, hi) uint64 arrays the FASTA writer takes (long keys: ((n, W) rows, None))."""
+    if lo.dim() == 2:
+        return lo.cpu().numpy().view(np.uint64), None
     hlo = lo.cpu().numpy().view(np.uint64)
     hhi = hi.cpu().numpy().view(np.uint64) if hi is not None else np.zeros(len(hlo), np.uint64)
     return hlo, hhi
@@ -65,6 +70,8 @@ def from_host(lo: np.ndarray, hi: Optional[np.ndarray], wide: bool, device: int 
     import torch
     dev = torch.device("cuda", device)
     tlo = torch.from_numpy(np.ascontiguousarray(lo, dtype=np.uint64).view(np.int64)).to(dev)
+    if tlo.dim() == 2:                                   # long keys: (n, W) rows
+        return tlo, None
     thi = torch.from_numpy(np.ascontiguousarray(hi, dtype=np.uint64).view(np.int64)).to(dev) if wide else None
     return tlo, thi
 
@@ -75,8 +82,12 @@ def dump_ge(eng, min_count: int, device: int = 0):
     import torch
     dev = torch.device("cuda", device)
     n = eng.count_ge(min_count)
-    lo = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    hi = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if eng.wide else None
+    if getattr(eng, "long", False):                      # (n, W) rows, no hi
+        lo = torch.empty((max(n, 1), eng.key_words), dtype=torch.int64, device=dev)
+        hi = None
+    else:
+        lo = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        hi = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if eng.wide else None
     cnt = torch.empty(max(n, 1), dtype=torch.int32, device=dev)      # (the device sort carries the counts along)
     torch.cuda.current_stream(dev).synchronize()
     got = eng.export_ge_dev(min_count, lo.data_ptr(), hi.data_ptr() if hi is not None else None, cnt.data_ptr(), n,
@@ -90,9 +101,10 @@ def query(eng, lo, hi, device: int = 0):
     """``jellyfish query``: uint32 counts (as int64 values) of the keys, input order, on the device."""
     import torch
     dev = torch.device("cuda", device)
-    out = torch.zeros(lo.numel(), dtype=torch.int32, device=dev)
-    if lo.numel():
+    n = lo.shape[0]                                      # (long keys: rows)
+    out = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n:
         torch.cuda.current_stream(dev).synchronize()
-        eng.query_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, lo.numel(), out.data_ptr())
+        eng.query_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, n, out.data_ptr())
         eng.synchronize()
     return out.to(torch.int64) & 0xFFFFFFFF

@@ -31,17 +31,19 @@ from ..core.jellyfish_wrappers import (
     _merge_filter_counts,
     _stream_bam,
 )
-from ..engine import KmerEngine
+from ..engine import key_words, mirror_engine
 from ..kmer_fasta import read_kmer_fasta_keys, remove_with_sidecar, write_kmer_fasta
 
 logger = logging.getLogger(__name__)
 
 
-def _child_key_parts(child_bam, device=0, world=1):
+def _child_key_parts(child_bam, device=0, world=1, kmer_size=31):
     """Slices of the key space for the child count: ``KDF_KEY_PARTS`` when set, else from the BAM size and
     the free HBM.  Rule of thumb (30x human WGS: ~0.6 BAM bytes per base, ~0.14 distinct 31-mers per base with
     0.5 % errors): distinct ~ 0.23 x BAM bytes, table bytes ~ 12 x distinct / 0.6 ~ 4.6 x BAM bytes; the table
-    may take 70 % of what is free (the rest is partition scratch and growth).  Small inputs give 1."""
+    may take 70 % of what is free (the rest is partition scratch and growth).  Long k-mers (odd 65..201): slots of
+    8 W + 4 bytes instead of 12 (W = 3..7 key words, 28..60 bytes), so the estimate grows by that ratio.  Small
+    inputs give 1."""
     env = os.environ.get("KDF_KEY_PARTS")
     if env:
         return max(1, int(env))
@@ -50,6 +52,9 @@ def _child_key_parts(child_bam, device=0, world=1):
     free, total = c_uint64(0), c_uint64(0)
     _native.check(_native.load().kdf_device_memory(device, byref(free), byref(total)))
     need = 4.6 * os.path.getsize(child_bam) / max(1, world)      # (several ranks: every rank holds its share of the keys twice -- local + owned)
+    W = key_words(kmer_size)
+    if W > 2:
+        need *= (8 * W + 4) / 12.0
     return max(1, int(-(-need // max(1.0, 0.7 * free.value))))
 
 
@@ -67,11 +72,11 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     # 288 GB of HBM holds.  KDF_KEY_PARTS = P counts the key space in P slices, one pass over the BAM each
     # (Jellyfish's answer to the same problem is to spill and merge hash files, jellyfish_wrappers.py:335-366).
     world, rank, host = dist_env.world_rank()
-    parts = _child_key_parts(child_bam, _device(), world)
+    parts = _child_key_parts(child_bam, _device(), world, kmer_size)
     owner_eng = merger = None
     try:
         local_hint = max(1, _engine_capacity_hint(jf_hash_size, child_bam) // parts)
-        with KmerEngine(kmer_size, capacity_hint=max(1, local_hint // world) if world > 1 else local_hint, device=_device()) as eng:
+        with mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world) if world > 1 else local_hint, device=_device()) as eng:
             if world > 1:
                 # one process per GPU: every rank counts its ranges of the BAM into a local table, one owner-partitioned
                 # exchange moves each (k-mer, count) pair to the rank that owns the k-mer, the owner sums -- and `dump -L`
@@ -79,7 +84,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                 import torch
                 from ..distributed import EngineOps, OwnerPartitionedCount
                 dev = torch.device("cuda", eng.device)
-                owner_eng = KmerEngine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
+                owner_eng = mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
                 merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
             los, his = [], []
             dev_sets = []
@@ -107,10 +112,12 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                 dev_sets.append((dlo, dhi))
                 lo, hi = devkeys.to_host(dlo, dhi)
                 los.append(lo); his.append(hi)
-            lo, hi = (np.concatenate(los), np.concatenate(his)) if parts > 1 else (los[0], his[0])
-            if parts > 1:
+            if parts > 1:                                          # (long keys: (n, W) rows, no hi words)
+                lo, hi = np.concatenate(los), (np.concatenate(his) if his[0] is not None else None)
                 import torch
-                dev_sets = [(torch.cat([d[0] for d in dev_sets]), torch.cat([d[1] for d in dev_sets]) if eng.wide else None)]
+                dev_sets = [(torch.cat([d[0] for d in dev_sets]), torch.cat([d[1] for d in dev_sets]) if dev_sets[0][1] is not None else None)]
+            else:
+                lo, hi = los[0], his[0]
     except KdfError as e:
         raise RuntimeError(f"jellyfish count (child) failed: {e}") from e
     finally:
@@ -152,7 +159,7 @@ def _subtract_reference_kmers(ref_jf, child_candidates_fa, tmpdir):
             dev = devkeys.from_host(lo, hi, k > 32) if len(lo) else None
         world, rank, host = dist_env.world_rank()
         if dev is not None and dev[0].numel():
-            with KmerEngine(k, capacity_hint=max(jf_io.index_records(ref_jf) // world, 1), device=_device()) as eng:
+            with mirror_engine(k, capacity_hint=max(jf_io.index_records(ref_jf) // world, 1), device=_device()) as eng:
                 # memory-mapped, block by block (a human index is 30 GB); several ranks: every rank loads ITS share of the
                 # index's records and answers for all candidates, one all-reduce(sum) gives `jellyfish query`'s counts
                 jf_io.load_index_into(eng, ref_jf, part=rank, parts=world)
@@ -194,7 +201,7 @@ def _count_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent
         lo, hi = read_kmer_fasta_keys(kmer_fasta, kmer_size)
         logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)",
                     kmer_size, threads, len(lo))
-        with KmerEngine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:
+        with mirror_engine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:
             eng.load_filter(lo, hi)
             _stream_bam(eng, parent_bam, ref_fasta, threads, filtered=True)
             _merge_filter_counts(eng, lo, hi)                  # (several ranks: the sum of their shards' counts)
@@ -213,7 +220,7 @@ def _count_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent
 def _query_index(jf_path, lo, hi, k, what):
     """``jellyfish query jf -s kmers.fa``: counts in input order."""
     try:
-        with KmerEngine(k, capacity_hint=max(jf_io.index_records(jf_path), 1)) as eng:
+        with mirror_engine(k, capacity_hint=max(jf_io.index_records(jf_path), 1)) as eng:
             jf_io.load_index_into(eng, jf_path, expect_k=k)
             return eng.query(lo, hi)
     except (KdfError, ValueError, OSError) as e:
@@ -225,10 +232,11 @@ def _count_parent_on_device(parent_bam, ref_fasta, dlo, dhi, kmer_size, threads,
     caller queries it and closes it: no ``parent.jf`` is written only to be read back)."""
     logger.info("%s: scanning BAM (%s): %s", label, _format_file_size(parent_bam), parent_bam)
     scan_start = time.monotonic()
-    logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)", kmer_size, threads, dlo.numel())
-    eng = KmerEngine(kmer_size, capacity_hint=max(int(dlo.numel()), 1), device=_device())
+    n = int(dlo.shape[0])                                      # (long keys: rows of W words)
+    logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)", kmer_size, threads, n)
+    eng = mirror_engine(kmer_size, capacity_hint=max(n, 1), device=_device())
     try:
-        eng.load_filter_dev(dlo.data_ptr(), dhi.data_ptr() if dhi is not None else None, int(dlo.numel()))
+        eng.load_filter_dev(dlo.data_ptr(), dhi.data_ptr() if dhi is not None else None, n)
         _stream_bam(eng, parent_bam, ref_fasta, threads, filtered=True)
         _merge_filter_counts(eng, None, None, dlo, dhi)        # (several ranks: one all-reduce of the per-key counts)
     except Exception:
@@ -257,7 +265,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
         raise RuntimeError(f"jellyfish count (Mother) failed: {e}") from e
     dlo, dhi = dev
     devkeys.forget(child_non_ref_fa)                             # taken: the registry must not pin GBs of HBM for the life of the process
-    n_input = int(dlo.numel())
+    n_input = int(dlo.shape[0])
     if n_input == 0:
         return 0, None
     logger.info("Filtering %d non-reference k-mers against parents…", n_input)
@@ -276,7 +284,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
 
     dlo, dhi = one_parent(mother_bam, "Mother", dlo, dhi)
     after_mother_fa = os.path.join(tmpdir, "after_mother.fa")
-    n_surviving = int(dlo.numel())
+    n_surviving = int(dlo.shape[0])
     if dist_env.is_root():                                         # (the contract files are written once; every rank holds the same sets)
         write_kmer_fasta(after_mother_fa, *devkeys.to_host(dlo, dhi), kmer_size)
     logger.info("Mother: %d / %d non-ref k-mers found (count > %d), %d surviving",
@@ -286,7 +294,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
 
     dlo, dhi = one_parent(father_bam, "Father", dlo, dhi)
     proband_unique_fa = os.path.join(tmpdir, "proband_unique.fa")
-    n_proband = int(dlo.numel())
+    n_proband = int(dlo.shape[0])
     if dist_env.is_root():
         write_kmer_fasta(proband_unique_fa, *devkeys.to_host(dlo, dhi), kmer_size)
         remove_with_sidecar(after_mother_fa)

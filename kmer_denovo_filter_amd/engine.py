@@ -10,6 +10,13 @@ shells out to ("External op" table):
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
 
+Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
+keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
+significant, passed and returned in the ``lo`` position with ``hi=None`` (so
+``export_ge`` returns ``(keys, None, counts)``).  The read-stream methods are the
+same for every k.  Long engines are single-GPU only (no owner-ordered dump,
+multi-segment merge or set_counts).
+
 No CPU fallback: constructing an engine without libkdf.so or without a GPU
 raises.
 """
@@ -28,14 +35,31 @@ def _vp(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
 
 
+def key_words(k: int) -> int:
+    """Words per key of an engine for k: 1 (k <= 32), 2 (33..63), ceil(2k/64) for odd 65..201; 0 if no engine takes k
+    (the rule of ``kdf_key_words``, restated so that it is checked before any device call)."""
+    k = int(k)
+    if 1 <= k <= 32:
+        return 1
+    if 33 <= k <= 63:
+        return 2
+    if KmerEngine.LONG_MIN_K <= k <= KmerEngine.LONG_MAX_K and k % 2 == 1:
+        return (2 * k + 63) // 64
+    return 0
+
+
 class KmerEngine:
-    MAX_K = 63
+    MAX_K = 63                 # (lo, hi) keys
+    LONG_MIN_K, LONG_MAX_K = 65, 201   # long engines: odd k only, (n, key_words) keys
 
     def __init__(self, k: int, capacity_hint: int = 1 << 20, device: int = 0):
-        if not (1 <= int(k) <= self.MAX_K):
-            raise ValueError(f"k={k} outside the engine's range 1..{self.MAX_K}")
+        if key_words(k) == 0:
+            raise ValueError(f"k={k} outside the engine's range 1..{self.MAX_K} or odd "
+                             f"{self.LONG_MIN_K}..{self.LONG_MAX_K}")
         self._lib = _native.load()
         self.k = int(k)
+        self.key_words = key_words(self.k)
+        self.long = self.key_words > 2
         self.wide = self.k > 32
         self.device = int(device)
         h = c_void_p()
@@ -125,6 +149,15 @@ class KmerEngine:
     def profile_stage_names(self):
         return list(self._STAGES)
 
+    def _rows(self, keys) -> np.ndarray:
+        """Long engines: keys as an (n, key_words) C-contiguous uint64 array."""
+        a = np.ascontiguousarray(keys, dtype=np.uint64)
+        if a.ndim == 1 and a.size == 0:
+            a = a.reshape(0, self.key_words)
+        if a.ndim != 2 or a.shape[1] != self.key_words:
+            raise ValueError(f"k={self.k}: keys must be an (n, {self.key_words}) uint64 array, got shape {a.shape}")
+        return a
+
     # -- count / filter ----------------------------------------------------
     def count(self, stream: ReadStream):
         self._ck(self._lib.kdf_count_reads(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases))
@@ -149,6 +182,11 @@ class KmerEngine:
 
     def add_pairs(self, lo: np.ndarray, hi: Optional[np.ndarray] = None, counts: Optional[np.ndarray] = None):
         """Insert-or-add (key, count) pairs (index load / `jellyfish merge`)."""
+        if self.long:
+            keys = self._rows(lo)
+            cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+            self._ck(self._lib.kdf_add_pairs_w(self._h, _vp(keys), _vp(cnt), len(keys)))
+            return self
         lo = np.ascontiguousarray(lo, dtype=np.uint64)
         hi = np.ascontiguousarray(hi, dtype=np.uint64) if self.wide else None
         cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
@@ -156,6 +194,9 @@ class KmerEngine:
         return self
 
     def add_pairs_dev(self, d_lo: int, d_hi: Optional[int], d_counts: Optional[int], n: int):
+        if self.long:          # d_lo: n x key_words row-major words
+            self._ck(self._lib.kdf_add_pairs_w_dev(self._h, c_void_p(d_lo), c_void_p(d_counts) if d_counts else None, int(n)))
+            return self
         self._ck(self._lib.kdf_add_pairs_dev(self._h, c_void_p(d_lo), c_void_p(d_hi) if d_hi else None,
                                              c_void_p(d_counts) if d_counts else None, int(n)))
         return self
@@ -180,6 +221,10 @@ class KmerEngine:
         return self
 
     def load_filter(self, lo: np.ndarray, hi: Optional[np.ndarray] = None):
+        if self.long:
+            keys = self._rows(lo)
+            self._ck(self._lib.kdf_load_filter_w(self._h, _vp(keys), len(keys)))
+            return self
         lo = np.ascontiguousarray(lo, dtype=np.uint64)
         if self.wide:
             if hi is None:
@@ -192,6 +237,9 @@ class KmerEngine:
 
     def load_filter_dev(self, d_lo: int, d_hi: Optional[int], n: int):
         """Filter keys already resident in HBM (raw device pointers)."""
+        if self.long:
+            self._ck(self._lib.kdf_load_filter_w_dev(self._h, c_void_p(d_lo), int(n)))
+            return self
         self._ck(self._lib.kdf_load_filter_dev(self._h, c_void_p(d_lo), c_void_p(d_hi) if d_hi else None, int(n)))
         return self
 
@@ -212,6 +260,11 @@ class KmerEngine:
 
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
+        if self.long:
+            keys = self._rows(lo)
+            out = np.zeros(len(keys), dtype=np.uint32)
+            self._ck(self._lib.kdf_query_w(self._h, _vp(keys), len(keys), _vp(out)))
+            return out
         lo = np.ascontiguousarray(lo, dtype=np.uint64)
         hi = np.ascontiguousarray(hi, dtype=np.uint64) if (self.wide and hi is not None) else None
         if self.wide and hi is None:
@@ -221,6 +274,9 @@ class KmerEngine:
         return out
 
     def query_dev(self, d_lo: int, d_hi: Optional[int], n: int, d_out: int):
+        if self.long:
+            self._ck(self._lib.kdf_query_w_dev(self._h, c_void_p(d_lo), int(n), c_void_p(d_out)))
+            return
         self._ck(self._lib.kdf_query_dev(self._h, c_void_p(d_lo), c_void_p(d_hi) if d_hi else None, int(n),
                                          c_void_p(d_out)))
 
@@ -230,8 +286,17 @@ class KmerEngine:
         return n.value
 
     def export_ge(self, min_count: int = 0):
-        """(lo, hi, counts) of entries with count >= min_count, ascending key order."""
+        """(lo, hi, counts) of entries with count >= min_count, ascending key order
+        (long engines: (keys (n, key_words), None, counts))."""
         n = self.count_ge(min_count)
+        if self.long:
+            keys = np.zeros((n, self.key_words), np.uint64)
+            cnt = np.zeros(n, np.uint32)
+            got = c_uint64(0)
+            self._ck(self._lib.kdf_export_ge_w(self._h, int(min_count), _vp(keys), _vp(cnt), n, byref(got)))
+            if got.value != n:
+                raise _native.KdfError(_native.KDF_ERR_STATE, "export size changed between passes")
+            return keys, None, cnt
         lo = np.zeros(n, np.uint64)
         hi = np.zeros(n, np.uint64)
         cnt = np.zeros(n, np.uint32)
@@ -243,8 +308,14 @@ class KmerEngine:
 
     def export_ge_dev(self, min_count: int, d_lo: int, d_hi: Optional[int], d_cnt: Optional[int], cap: int,
                       sorted_: bool = False) -> int:
-        """Dump into caller-owned device buffers; returns the number of entries."""
+        """Dump into caller-owned device buffers; returns the number of entries (long engines: d_lo holds
+        cap x key_words row-major words, d_hi is ignored)."""
         n = c_uint64(0)
+        if self.long:
+            self._ck(self._lib.kdf_export_ge_w_dev(self._h, int(min_count), c_void_p(d_lo),
+                                                   c_void_p(d_cnt) if d_cnt else None, int(cap),
+                                                   1 if sorted_ else 0, byref(n)))
+            return n.value
         self._ck(self._lib.kdf_export_ge_dev(self._h, int(min_count), c_void_p(d_lo),
                                              c_void_p(d_hi) if d_hi else None,
                                              c_void_p(d_cnt) if d_cnt else None, int(cap),
@@ -287,6 +358,20 @@ class KmerEngine:
     def scan_dev(self, d_packed: int, d_invalid: int, n_bases: int, d_hits: int):
         self._ck(self._lib.kdf_scan_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
                                               c_void_p(d_hits)))
+
+
+def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:
+    """The engine the reference-interface mirrors (discovery chain, Module 3, the Jellyfish wrappers) count with.
+    Long k-mers (odd 65..201) run in one process; under a process group of several ranks the mirrors shard through the
+    multi-GPU exchange (owner-ordered dump, set_counts, merges), which takes k <= 63 only -- refused here, before any
+    device call."""
+    if int(k) > KmerEngine.MAX_K:
+        from . import dist_env
+        world = dist_env.world_rank()[0]
+        if world > 1:
+            raise ValueError(f"k={k}: long k-mers (odd {KmerEngine.LONG_MIN_K}..{KmerEngine.LONG_MAX_K}) run in one "
+                             f"process; the multi-GPU mirrors ({world} ranks) take k <= {KmerEngine.MAX_K}")
+    return KmerEngine(k, *args, **kwargs)
 
 
 def hit_positions(hit_bits: np.ndarray, start: int, end: int) -> np.ndarray:

@@ -18,6 +18,13 @@ copy under its matrix gives the same bytes, tests/test_jf_helpers.py); that a re
 ``jellyfish query`` accepts a header generated HERE is unverified -- there is no
 Jellyfish in this image.  ``KDF_JF_FORMAT=jellyfish``
 makes the mirrors write ``{ref}.k{k}.jf`` that way.
+
+Long k-mers (odd k from 65 to 201): records of ceil(2k/8) key bytes, and keys as
+``(n, W)`` uint64 rows (W = ceil(2k/64), word 0 least significant) in the ``lo``
+position with ``hi = None`` -- what a long KmerEngine takes and returns.  A real
+Jellyfish ``binary/sorted`` file at k > 63 is read with the same byte layout
+(little-endian key bytes, as at k <= 63); no such fixture exists, so that reading
+is unpinned.  ``write_jellyfish_index`` refuses k > 63.
 """
 from __future__ import annotations
 
@@ -57,8 +64,8 @@ def _index_layout(path: str, expect_k: Optional[int]):
     k = key_len // 2
     if expect_k is not None and k != expect_k:
         raise ValueError(f"{path}: index has k={k}, expected k={expect_k}")
-    if k > 64:
-        raise ValueError(f"{path}: k={k} is beyond the engine's key width")
+    if k > 64 and not (k <= 201 and k % 2 == 1):
+        raise ValueError(f"{path}: k={k} is beyond the engine's key width (1..63, odd 65..201)")
     kb, cb = (key_len + 7) // 8, int(header["counter_len"])
     rec = np.dtype([("k", "u1", (kb,)), ("c", "u1", (cb,))])
     n = (os.path.getsize(path) - off) // rec.itemsize
@@ -72,10 +79,16 @@ def index_records(path: str) -> int:
 
 def _decode(data, kb: int, cb: int):
     """One block of records -> (lo, hi or None, counts uint32).  Little-endian byte strings of any length up to 16 / 8
-    bytes; the usual widths (8-byte keys, 4-byte counters) are plain views of one contiguous copy per field."""
+    bytes; the usual widths (8-byte keys, 4-byte counters) are plain views of one contiguous copy per field.  Keys of
+    more than 16 bytes (long k-mers) come back as (n, W) uint64 rows in the lo position, hi = None."""
     n = len(data)
     kraw = np.ascontiguousarray(data["k"])
-    if kb == 8:
+    if kb > 16:
+        W = (kb + 7) // 8
+        kbytes = np.zeros((n, 8 * W), dtype=np.uint8)
+        kbytes[:, :kb] = kraw
+        lo, hi = kbytes.view("<u8").reshape(n, W).astype(np.uint64, copy=False), None
+    elif kb == 8:
         lo, hi = kraw.view("<u8").reshape(n), None
     else:
         kbytes = np.zeros((n, 16), dtype=np.uint8)
@@ -129,9 +142,17 @@ def load_index_into(engine, path: str, expect_k: Optional[int] = None, chunk_rec
 
 
 def read_index(path: str, expect_k: Optional[int] = None):
-    """-> (k, lo, hi, counts) ; hi is all zero for k <= 32.  Counts saturate at 2^32-1.  Whole file in memory:
-    callers that only feed an engine use `load_index_into`."""
+    """-> (k, lo, hi, counts) ; hi is all zero for k <= 32; long k: lo = (n, W) rows, hi = None.  Counts saturate at
+    2^32-1.  Whole file in memory: callers that only feed an engine use `load_index_into`."""
     k = _index_layout(path, expect_k)[0]
+    if k > 64:
+        rows, cnts = [], []
+        for _, keys, _, counts in iter_index(path, expect_k):
+            rows.append(keys); cnts.append(counts)
+        W = (2 * k + 63) // 64
+        if not rows:
+            return k, np.zeros((0, W), np.uint64), None, np.zeros(0, np.uint32)
+        return k, np.concatenate(rows), None, np.concatenate(cnts)
     los, his, cnts = [], [], []
     for _, lo, hi, counts in iter_index(path, expect_k):
         los.append(lo); his.append(hi if hi is not None else np.zeros(len(lo), np.uint64)); cnts.append(counts)
@@ -142,10 +163,19 @@ def read_index(path: str, expect_k: Optional[int] = None):
 
 def write_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.ndarray], counts: np.ndarray,
                 cmdline=None) -> str:
-    """Write a ``kdf/sorted`` index (keys must already be in ascending order)."""
+    """Write a ``kdf/sorted`` index (keys must already be in ascending order; long k: ``lo`` = (n, W) rows)."""
     n = len(lo)
     key_len = 2 * k
     kb = (key_len + 7) // 8
+    if k > 64:
+        W = (key_len + 63) // 64
+        rows = np.ascontiguousarray(lo, dtype="<u8").reshape(n, W)
+        kbytes = rows.view(np.uint8).reshape(n, 8 * W)
+    else:
+        kbytes = np.zeros((n, 16), dtype=np.uint8)
+        kbytes[:, :8] = np.ascontiguousarray(lo, dtype="<u8").view(np.uint8).reshape(n, 8)
+        if hi is not None and k > 32:
+            kbytes[:, 8:] = np.ascontiguousarray(hi, dtype="<u8").view(np.uint8).reshape(n, 8)
     header = {
         "alignment": 8, "canonical": True, "cmdline": list(cmdline or []), "counter_len": 4,
         "format": KDF_FORMAT, "key_len": key_len, "size": int(n),
@@ -157,10 +187,6 @@ def write_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.ndarray], cou
     body += b"\0" * pad
     rec = np.dtype([("k", "u1", (kb,)), ("c", "<u4")])
     data = np.zeros(n, dtype=rec)
-    kbytes = np.zeros((n, 16), dtype=np.uint8)
-    kbytes[:, :8] = np.ascontiguousarray(lo, dtype="<u8").view(np.uint8).reshape(n, 8)
-    if hi is not None and k > 32:
-        kbytes[:, 8:] = np.ascontiguousarray(hi, dtype="<u8").view(np.uint8).reshape(n, 8)
     data["k"] = kbytes[:, :kb]
     data["c"] = np.asarray(counts, dtype=np.uint32)
     tmp = path + ".tmp"
@@ -227,6 +253,8 @@ def write_jellyfish_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.nda
     `size` (a power of two; default: the first >= 2 n, at least 2^10) and `matrix_columns` describe the hash the
     records are ordered by; `header` (a dict parsed from another Jellyfish file) supplies both, and every other field,
     unchanged -- re-writing a real Jellyfish file from its own records and header gives its bytes back."""
+    if k > 63:
+        raise ValueError(f"k={k}: the Jellyfish binary/sorted writer takes k <= 63 (write_index writes kdf/sorted at any k)")
     n = len(lo)
     key_len = 2 * k
     kb = (key_len + 7) // 8

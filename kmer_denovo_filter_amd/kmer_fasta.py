@@ -6,6 +6,10 @@ binary sidecar so that stages running on the engine skip the text round trip.
 The FASTA stays the contract (callers and users may read it); the sidecar
 ``<path>.kdfkeys.npz`` is only trusted when it records the FASTA's exact size and
 mtime.
+
+Long k-mers (odd k from 65 to 201) use the engine's long-key form: keys are
+``(n, W)`` uint64 rows (W = ceil(2k/64), word 0 least significant) in the ``lo``
+position and ``hi`` is None.
 """
 from __future__ import annotations
 
@@ -26,6 +30,11 @@ def _sidecar(path: str) -> str:
 def _decode_matrix(lo: np.ndarray, hi: Optional[np.ndarray], k: int) -> np.ndarray:
     n = len(lo)
     out = np.empty((n, k), dtype=np.uint8)
+    if k > 64:                                           # long keys: lo = (n, W) rows
+        for i in range(k):
+            sh = 2 * (k - 1 - i)
+            out[:, i] = _DEC[((lo[:, sh >> 6] >> np.uint64(sh & 63)) & np.uint64(3)).astype(np.intp)]
+        return out
     for i in range(k):
         sh = 2 * (k - 1 - i)
         src = (hi >> np.uint64(sh - 64)) if sh >= 64 else (lo >> np.uint64(sh))
@@ -35,14 +44,18 @@ def _decode_matrix(lo: np.ndarray, hi: Optional[np.ndarray], k: int) -> np.ndarr
 
 def write_kmer_fasta(path: str, lo: np.ndarray, hi: Optional[np.ndarray], k: int,
                      sidecar: bool = True) -> int:
-    """Write keys as ``>{i}\\n{KMER}\\n`` (i from 0).  Returns the number written."""
+    """Write keys as ``>{i}\\n{KMER}\\n`` (i from 0).  Returns the number written.  Long k: ``lo`` = (n, W) rows."""
     lo = np.ascontiguousarray(lo, dtype=np.uint64)
     n = len(lo)
-    hi = np.zeros(n, np.uint64) if hi is None else np.ascontiguousarray(hi, dtype=np.uint64)
+    if k > 64:
+        lo = lo.reshape(n, (2 * k + 63) // 64)
+        hi = np.zeros(0, np.uint64)                      # (unused; keeps the sidecar's fields)
+    else:
+        hi = np.zeros(n, np.uint64) if hi is None else np.ascontiguousarray(hi, dtype=np.uint64)
     with open(path, "wb") as fh:
         for a in range(0, n, _CHUNK):
             b = min(n, a + _CHUNK)
-            seqs = _decode_matrix(lo[a:b], hi[a:b], k)
+            seqs = _decode_matrix(lo[a:b], None if k > 64 else hi[a:b], k)
             idx = np.arange(a, b, dtype=np.int64)
             ndig = np.ones(b - a, dtype=np.int64)
             t = idx // 10
@@ -70,7 +83,7 @@ def write_kmer_fasta(path: str, lo: np.ndarray, hi: Optional[np.ndarray], k: int
 
 
 def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.ndarray, np.ndarray]:
-    """Sequence lines of a k-mer FASTA -> (lo, hi) keys, file order.
+    """Sequence lines of a k-mer FASTA -> (lo, hi) keys, file order (long k: ((n, W) rows, None)).
 
     With ``canonical`` the keys are canonicalised, as Jellyfish does with an
     ``--if`` / ``query -s`` file under ``-C``.
@@ -81,12 +94,14 @@ def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.
             z = np.load(sc)
             st = os.stat(path)
             if int(z["k"]) == k and int(z["size"]) == st.st_size and int(z["mtime_ns"]) == st.st_mtime_ns:
-                return z["lo"], z["hi"]
+                return (z["lo"], None) if k > 64 else (z["lo"], z["hi"])
         except Exception:  # noqa: BLE001  (stale or unreadable sidecar: fall back to the text)
             pass
+    W = (2 * k + 63) // 64
+    empty = (np.zeros((0, W), np.uint64), None) if k > 64 else (np.zeros(0, np.uint64), np.zeros(0, np.uint64))
     data = np.fromfile(path, dtype=np.uint8)
     if data.size == 0:
-        return np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        return empty
     if data[-1] != 10:
         data = np.append(data, np.uint8(10))
     nl = np.flatnonzero(data == 10)
@@ -100,7 +115,7 @@ def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.
     is_seq = (lens > 0) & (data[starts] != ord(">"))
     s, ln = starts[is_seq], lens[is_seq]
     if len(s) == 0:
-        return np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        return empty
     if not (ln == k).all():
         raise ValueError(f"{path}: sequence line of length != k={k}")
     codes = _ENC[data[s[:, None] + np.arange(k)[None, :]]]
@@ -118,6 +133,27 @@ def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.
             else:
                 plo |= c[:, i] << np.uint64(sh)
         return plo, phi
+
+    if k > 64:
+        def pack_rows(c):
+            rows = np.zeros((len(c), W), np.uint64)
+            for i in range(k):
+                sh = 2 * (k - 1 - i)
+                rows[:, sh >> 6] |= c[:, i] << np.uint64(sh & 63)
+            return rows
+
+        f = pack_rows(codes)
+        if not canonical:
+            return f, None
+        r = pack_rows((np.uint64(3) - codes)[:, ::-1])
+        # numeric minimum: the first differing word from the top decides
+        lt = np.zeros(len(f), bool)
+        undecided = np.ones(len(f), bool)
+        for j in range(W - 1, -1, -1):
+            d = undecided & (f[:, j] != r[:, j])
+            lt |= d & (f[:, j] < r[:, j])
+            undecided &= ~d
+        return np.where((lt | undecided)[:, None], f, r), None
 
     flo, fhi = pack(codes)
     if not canonical:

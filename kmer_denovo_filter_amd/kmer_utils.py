@@ -17,7 +17,7 @@ import numpy as np
 
 from . import jf_io
 from ._native import KdfError
-from .engine import KmerEngine, hit_positions
+from .engine import KmerEngine, mirror_engine, hit_positions
 from .reads import ReadStream, keys_to_kmers, kmers_to_keys
 
 _COMP = str.maketrans("ACGTacgt", "TGCAtgca")
@@ -141,7 +141,7 @@ class KmerAutomaton:
     def _ensure_engine(self) -> KmerEngine:
         if self._engine is None:
             lo, hi = kmers_to_keys(self._kmers, self.kmer_size, canonical=True)
-            eng = KmerEngine(self.kmer_size, capacity_hint=max(len(lo), 1), device=self._device)
+            eng = mirror_engine(self.kmer_size, capacity_hint=max(len(lo), 1), device=self._device)
             eng.add_pairs(lo, hi, np.ones(len(lo), np.uint32))
             self._engine = eng
         return self._engine
@@ -190,7 +190,7 @@ class JellyfishKmerQuery:
         if self._engine is None:
             try:
                 k = int(jf_io.read_header(self.jf_path)[0]["key_len"]) // 2
-                eng = KmerEngine(k, capacity_hint=max(jf_io.index_records(self.jf_path), 1), device=self._device)
+                eng = mirror_engine(k, capacity_hint=max(jf_io.index_records(self.jf_path), 1), device=self._device)
                 jf_io.load_index_into(eng, self.jf_path)
             except (KdfError, ValueError, OSError) as e:
                 raise RuntimeError(f"jellyfish query failed: {e}") from e

@@ -112,10 +112,17 @@ def _variant_key(var):
     return f"{var['chrom']}:{var['pos']}:{var['ref']}:{var['alt'] if var['alt'] is not None else '.'}"
 
 
+def _require_vcf_k(kmer_size):
+    """VCF mode takes k <= 63 (its k-mer sets are exchanged as (lo, hi) keys); long k-mers run in discovery mode."""
+    if int(kmer_size) > 63:
+        raise ValueError(f"k={kmer_size}: VCF mode takes k <= 63; long k-mers (odd 65..201) run in discovery mode only")
+
+
 def _collect_child_kmers(child_bam, ref_fasta, variants, kmer_size, min_baseq, min_mapq, debug_kmers, kmer_fasta,
                          flush_threshold=500_000):
     """Variant-spanning child k-mers -> ``kmer_fasta`` (``>{i}\\n{KMER}\\n``, de-duplicated
     per flush batch).  Returns (total_written, {variant key: [(read name, k-mers, supports_alt)]})."""
+    _require_vcf_k(kmer_size)
     by_chrom = collections.defaultdict(list)
     for v in variants:
         by_chrom[v["chrom"]].append(v)
@@ -170,6 +177,7 @@ def _collect_child_kmers(child_bam, ref_fasta, variants, kmer_size, min_baseq, m
 def scan_parents(mother_bam, father_bam, ref_fasta, kmer_fasta, kmer_size, tmpdir, threads, total_child_kmers):
     """Step 3: both parents are scanned for the child k-mers with the engine and
     their counts are ADDED (Counter.update, reference :1592,1609)."""
+    _require_vcf_k(kmer_size)
     found = collections.Counter()
     for label, bam in (("mother", mother_bam), ("father", father_bam)):
         found.update(_scan_parent_jellyfish(bam, ref_fasta, kmer_fasta, kmer_size, os.path.join(tmpdir, label),
