@@ -641,21 +641,51 @@ static int ctl_reset(kdf_engine *h, bool keep_windows) {
     return KDF_OK;
 }
 
+// code for k <= 63 only (the binned pipeline, merge, sieve): W = 1 or 2
 template <typename F>
 static int by_width(kdf_engine *h, F &&f) { return h->kw == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{}); }
-// long engines: W = 3 .. 7
-static bool is_long(const kdf_engine *h) { return h->kw > 2; }
-// bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
-static int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
+// code for every key width: W = 1, 2 (kdf_device.h) or 3 .. 7 (long keys, kdf_long.h)
 template <typename F>
-static int by_long(kdf_engine *h, F &&f) {
+static int by_words(kdf_engine *h, F &&f) {
     switch (h->kw) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
     case 3: return f(std::integral_constant<int, 3>{});
     case 4: return f(std::integral_constant<int, 4>{});
     case 5: return f(std::integral_constant<int, 5>{});
     case 6: return f(std::integral_constant<int, 6>{});
     default: return f(std::integral_constant<int, 7>{});
     }
+}
+// long engines: W = 3 .. 7
+static bool is_long(const kdf_engine *h) { return h->kw > 2; }
+// bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
+static int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
+
+// Insert-or-add n keys into table t, adding add[i] (NULL: 0).  Caller keys (stored = false) are the (lo, hi) arrays of
+// k <= 63 or the row-major W-word rows at lo of long keys; stored = true: lo / hi are the arrays of the live table,
+// which is being rehashed into t.  (A launch holds fewer than 2^32 threads: it goes in pieces of 2^30 keys.)
+static void insert_keys(kdf_engine *h, const KdfTable &t, const uint64_t *lo, const uint64_t *hi, const uint32_t *add,
+                        uint64_t n, bool stored) {
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        for (uint64_t off = 0; off < n; off += 1ull << 30) {
+            const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+            const unsigned blocks = (unsigned)((m + 255) / 256);
+            const uint32_t *a = add ? add + off : nullptr;
+            if constexpr (W <= 2) {
+                hipLaunchKernelGGL(kdf_insert_keys_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, lo + off,
+                                   W == 2 ? hi + off : nullptr, a, m, t, h->ctl, (int)stored, (int)stored);
+            } else {
+                // word j of key i: src[i * rs + j * ws] (kdf_long_read_key)
+                const uint64_t rs = stored ? 1 : W, ws = stored ? h->cap : 1;
+                const uint64_t *up = stored ? hi : lo + 1;
+                hipLaunchKernelGGL(kdf_long_insert_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, lo + off * rs, up + off * rs,
+                                   rs, ws, a, m, t, h->ctl, (int)stored, long_top_bits(h));
+            }
+        }
+        return 0;
+    });
 }
 
 // rehash the live table into one with 2^new_log2 slots
@@ -675,29 +705,10 @@ static int table_rehash(kdf_engine *h, uint32_t new_log2) {
     KdfTable nt;
     int rc = table_alloc(h, new_log2, nt);
     if (rc) { table_free(nt); return rc; }
-    const uint64_t old_cap = h->cap;
     const uint64_t windows = h->windows;
     rc = ctl_reset(h, false);
     if (rc) { table_free(nt); return rc; }
-    // (a launch holds fewer than 2^32 threads: tables of 2^32 slots and more go in pieces of 2^30 slots)
-    for (uint64_t off = 0; off < old_cap; off += 1ull << 30) {
-        const uint64_t n = std::min<uint64_t>(1ull << 30, old_cap - off);
-        const unsigned blocks = (unsigned)((n + 255) / 256);
-        if (is_long(h))
-            by_long(h, [&](auto Wc) {
-                constexpr int W = decltype(Wc)::value;
-                hipLaunchKernelGGL(kdf_long_insert_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, (const uint64_t *)h->t.lo + off,
-                                   (const uint64_t *)h->t.hi + off, (uint64_t)1, old_cap, (const uint32_t *)h->t.cnt + off, n, nt, h->ctl, 1,
-                                   long_top_bits(h));
-                return 0;
-            });
-        else if (h->kw == 1)
-            hipLaunchKernelGGL(kdf_insert_keys_kernel<1>, dim3(blocks), dim3(256), 0, h->stream,
-                               (const uint64_t *)h->t.lo + off, (const uint64_t *)nullptr, (const uint32_t *)h->t.cnt + off, n, nt, h->ctl, 1, 1);
-        else
-            hipLaunchKernelGGL(kdf_insert_keys_kernel<2>, dim3(blocks), dim3(256), 0, h->stream,
-                               (const uint64_t *)h->t.lo + off, (const uint64_t *)h->t.hi + off, (const uint32_t *)h->t.cnt + off, n, nt, h->ctl, 1, 1);
-    }
+    insert_keys(h, nt, h->t.lo, h->t.hi, h->t.cnt, h->cap, true);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { table_free(nt); return fail(h, KDF_ERR_HIP, "rehash launch failed: %s", hipGetErrorString(e)); }
     bool full = false;
@@ -724,19 +735,16 @@ static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_
         (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
         (void)hipEventRecord(e0, h->stream);
     }
-    if (is_long(h))       // (n_bases: the long kernel clamps its loads to the buffers kdf_stream_words(n_bases) sizes)
-        by_long(h, [&](auto Wc) {
-            constexpr int W = decltype(Wc)::value;
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W <= 2)
+            hipLaunchKernelGGL((kdf_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
+                               d_packed, d_invalid, tile0, n_tiles, h->k, h->t, h->ctl, d_hits);
+        else              // (n_bases: the long kernel clamps its loads to the buffers kdf_stream_words(n_bases) sizes)
             hipLaunchKernelGGL((kdf_long_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
                                d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
-            return 0;
-        });
-    else if (h->kw == 1)
-        hipLaunchKernelGGL((kdf_stream_kernel<1, MODE>), dim3(blocks), dim3(256), 0, h->stream,
-                           d_packed, d_invalid, tile0, n_tiles, h->k, h->t, h->ctl, d_hits);
-    else
-        hipLaunchKernelGGL((kdf_stream_kernel<2, MODE>), dim3(blocks), dim3(256), 0, h->stream,
-                           d_packed, d_invalid, tile0, n_tiles, h->k, h->t, h->ctl, d_hits);
+        return 0;
+    });
     if (h->prof) {
         (void)hipEventRecord(e1, h->stream);
         h->prof_ev.emplace_back(e0, e1);
@@ -1010,7 +1018,7 @@ static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const ui
     for (uint64_t off = 0; off < n_bases; off += step) {
         const uint64_t len = std::min<uint64_t>(step, n_bases - off);
         const uint64_t *p = d_packed + off / 32, *m = d_invalid + off / 64;
-        int rc = h->kw == 1 ? kb_partition<1>(h, p, m, len, filtered) : kb_partition<2>(h, p, m, len, filtered);
+        int rc = by_width(h, [&](auto KWc) { return kb_partition<decltype(KWc)::value>(h, p, m, len, filtered); });
         if (rc) return rc;
     }
     return KDF_OK;
@@ -1092,16 +1100,16 @@ static int kb_flush_ring(kdf_engine *h) {
     if (heavy) {
         // the buckets the skewed instantiation left aside
         const size_t lds_h = ((size_t)(8 * h->kw + 4) << plan.bucket_bits) + KB_RI_LDS_BYTES;
-        if (filtered) {                                            // the keys stay put: the slices add to the counts in HBM
-            if (h->kw == 1) hipLaunchKernelGGL(kb_heavy_filtered_kernel<1>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t);
-            else hipLaunchKernelGGL(kb_heavy_filtered_kernel<2>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t);
-        } else if (h->kw == 1) {
-            hipLaunchKernelGGL(kb_heavy_slice_kernel<1>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s);
-            hipLaunchKernelGGL(kb_heavy_combine_kernel<1>, dim3(KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t, h->ctl, nonempty);
-        } else {
-            hipLaunchKernelGGL(kb_heavy_slice_kernel<2>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s);
-            hipLaunchKernelGGL(kb_heavy_combine_kernel<2>, dim3(KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t, h->ctl, nonempty);
-        }
+        by_width(h, [&](auto KWc) {
+            constexpr int KW = decltype(KWc)::value;
+            if (filtered) {                                        // the keys stay put: the slices add to the counts in HBM
+                hipLaunchKernelGGL(kb_heavy_filtered_kernel<KW>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t);
+            } else {
+                hipLaunchKernelGGL(kb_heavy_slice_kernel<KW>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s);
+                hipLaunchKernelGGL(kb_heavy_combine_kernel<KW>, dim3(KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t, h->ctl, nonempty);
+            }
+            return 0;
+        });
     }
     HIPCHK(h, hipGetLastError());
     if (h->prof) {
@@ -1131,8 +1139,10 @@ static int kb_flush_ring(kdf_engine *h) {
         const uint64_t worst = h->distinct + std::min<uint64_t>(n_entries, n_failed * ((n_entries / std::max<uint64_t>(nb_table, 1)) * 4 + 4096));
         const uint32_t want = std::max<uint32_t>(h->t.log2cap + 1, cap_log2_for(worst));
         if ((rc = table_rehash(h, want))) { (void)kb_ring_reset(h); return rc; }
-        if (h->kw == 1) hipLaunchKernelGGL(kb_replay_kernel<1>, dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
-        else hipLaunchKernelGGL(kb_replay_kernel<2>, dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
+        by_width(h, [&](auto KWc) {
+            hipLaunchKernelGGL(kb_replay_kernel<decltype(KWc)::value>, dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
+            return 0;
+        });
         HIPCHK(h, hipGetLastError());
         if ((rc = ctl_sync(h, &full))) { (void)kb_ring_reset(h); return rc; }
         if (full) { (void)kb_ring_reset(h); return fail(h, KDF_ERR_TABLE_FULL, "binned count: bucket overflow during replay (capacity 2^%u)", h->t.log2cap); }
@@ -1275,27 +1285,36 @@ static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint6
     return KDF_OK;
 }
 
+// kdf_sieve_count_kernel: persistent workgroups over slabs of 1024 x WPT positions.  hits: the scan's hit bits (zeroed by
+// the caller), or NULL for a count --if; in_lds: every workgroup copies the sieve into LDS first
+static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles,
+                         unsigned long long *hits, bool in_lds) {
+    by_width(h, [&](auto KWc) {
+        constexpr int KW = decltype(KWc)::value;
+        const uint64_t tiles_per_slab = KB_THREADS / (64 / KbCfg<KW>::WPT);
+        const uint64_t n_slabs = (n_tiles + tiles_per_slab - 1) / tiles_per_slab;
+        const uint32_t n_wg = (uint32_t)std::min<uint64_t>(n_slabs, (uint64_t)h->n_cu * 8);
+        const uint32_t spw = (uint32_t)((n_slabs + n_wg - 1) / n_wg);
+        const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
+        KdfSieve sv{h->sieve, h->sieve_words - 1};
+#define SV_LAUNCH(L, S) hipLaunchKernelGGL((kdf_sieve_count_kernel<KW, L, S>), dim3(grid), dim3(KB_THREADS), 0, h->stream, \
+                                           d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw, hits)
+        if (hits) { if (in_lds) SV_LAUNCH(true, true); else SV_LAUNCH(false, true); }
+        else { if (in_lds) SV_LAUNCH(true, false); else SV_LAUNCH(false, false); }
+#undef SV_LAUNCH
+        return 0;
+    });
+}
+
 static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (!h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads_filtered: no filter loaded (kdf_load_filter)");
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     if (n_tiles == 0) return KDF_OK;
     { int rc0 = materialize(h); if (rc0) return rc0; }
     if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
-        // persistent workgroups over slabs of 1024 x WPT positions
-        const int WPT = h->kw == 1 ? KbCfg<1>::WPT : KbCfg<2>::WPT;
-        const uint64_t tiles_per_slab = KB_THREADS / (64 / WPT);
-        const uint64_t n_slabs = (n_tiles + tiles_per_slab - 1) / tiles_per_slab;
-        const uint32_t n_wg = (uint32_t)std::min<uint64_t>(n_slabs, (uint64_t)h->n_cu * 8);
-        const uint32_t spw = (uint32_t)((n_slabs + n_wg - 1) / n_wg);
-        const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
-        KdfSieve sv{h->sieve, h->sieve_words - 1};
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->prof) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, h->stream); }
-        const bool in_lds = h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048);
-        if (h->kw == 1 && in_lds) hipLaunchKernelGGL((kdf_sieve_count_kernel<1, true>), dim3(grid), dim3(KB_THREADS), 0, h->stream, d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw);
-        else if (h->kw == 1) hipLaunchKernelGGL((kdf_sieve_count_kernel<1, false>), dim3(grid), dim3(KB_THREADS), 0, h->stream, d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw);
-        else if (in_lds) hipLaunchKernelGGL((kdf_sieve_count_kernel<2, true>), dim3(grid), dim3(KB_THREADS), 0, h->stream, d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw);
-        else hipLaunchKernelGGL((kdf_sieve_count_kernel<2, false>), dim3(grid), dim3(KB_THREADS), 0, h->stream, d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw);
+        launch_sieve(h, d_packed, d_invalid, n_tiles, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
         if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_ev.emplace_back(e0, e1); h->prof_tiles.push_back(n_tiles); }
         HIPCHK(h, hipGetLastError());
         h->last_path = 3;
@@ -1316,6 +1335,23 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
 
 __global__ void kdf_mask_tail_kernel(uint64_t *word, uint64_t bits) { *word |= bits; }
 
+// copy n_bases > 0 positions into device buffers of kdf_stream_words(n_bases) words, on stream s.  The caller's arrays
+// hold ceil(n/32) packed / ceil(n/64) mask words: the rest is padded with 0 / 0xFF, and the bits past n_bases in the
+// last mask word must read "invalid" too.
+static int upload_padded(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                         uint64_t *d_packed, uint64_t *d_invalid, hipStream_t s) {
+    uint64_t pw, mw;
+    kdf_stream_words(n_bases, &pw, &mw);
+    const uint64_t pw_in = (n_bases + 31) / 32, mw_in = (n_bases + 63) / 64;
+    if (pw > pw_in) HIPCHK(h, hipMemsetAsync(d_packed + pw_in, 0, (pw - pw_in) * 8, s));
+    if (mw > mw_in) HIPCHK(h, hipMemsetAsync(d_invalid + mw_in, 0xFF, (mw - mw_in) * 8, s));
+    HIPCHK(h, hipMemcpyAsync(d_packed, packed, pw_in * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d_invalid, invalid, mw_in * 8, hipMemcpyHostToDevice, s));
+    if (n_bases % 64) hipLaunchKernelGGL(kdf_mask_tail_kernel, dim3(1), dim3(1), 0, s, d_invalid + (mw_in - 1), ~0ull << (n_bases % 64));
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
 static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
                          uint64_t **d_packed, uint64_t **d_invalid) {
     uint64_t pw, mw;
@@ -1323,21 +1359,28 @@ static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *
     int rc;
     if ((rc = stage_reserve(h, 0, pw * 8))) return rc;
     if ((rc = stage_reserve(h, 1, mw * 8))) return rc;
-    // the caller's arrays hold ceil(n/32) / ceil(n/64) meaningful words; pad on device
-    const uint64_t pw_in = (n_bases + 31) / 32, mw_in = (n_bases + 63) / 64;
-    HIPCHK(h, hipMemsetAsync(h->stage[0], 0, pw * 8, h->stream));
-    HIPCHK(h, hipMemsetAsync(h->stage[1], 0xFF, mw * 8, h->stream));
-    if (pw_in) HIPCHK(h, hipMemcpyAsync(h->stage[0], packed, pw_in * 8, hipMemcpyHostToDevice, h->stream));
-    if (mw_in) HIPCHK(h, hipMemcpyAsync(h->stage[1], invalid, mw_in * 8, hipMemcpyHostToDevice, h->stream));
-    // bits past n_bases in the last mask word must read "invalid"
-    if (n_bases % 64) {
-        uint64_t last = invalid[mw_in - 1] | (~0ull << (n_bases % 64));
-        HIPCHK(h, hipMemcpyAsync((uint64_t *)h->stage[1] + (mw_in - 1), &last, 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));     // `last` is a stack temporary
-    }
     *d_packed = (uint64_t *)h->stage[0];
     *d_invalid = (uint64_t *)h->stage[1];
+    return upload_padded(h, packed, invalid, n_bases, *d_packed, *d_invalid, h->stream);
+}
+
+// stage_reserve + a copy of `bytes` host bytes into staging slot i (stream order)
+static int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn) {
+    int rc = stage_reserve(h, i, bytes);
+    if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(h->stage[i], src, bytes, hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "%s: copy of %zu bytes to the device failed: %s", fn, bytes, hipGetErrorString(e));
     return KDF_OK;
+}
+
+// words per key of a host form's first key array: 1 for the (lo, hi) forms, W for the rows of the _w forms
+static uint64_t lo_words(const kdf_engine *h) { return is_long(h) ? h->kw : 1; }
+
+// n keys of a host form into staging slots 2 (lo, or the rows of long keys) and 3 (hi, k 33..63)
+static int stage_keys(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uint64_t n, const char *fn) {
+    int rc = stage_in(h, 2, lo, n * 8 * lo_words(h), fn);
+    if (!rc && h->kw == 2) rc = stage_in(h, 3, hi, n * 8, fn);
+    return rc;
 }
 
 // ===========================================================================
@@ -1535,15 +1578,8 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
     if (n_bases == 0) { h->up_valid[slot] = true; return KDF_OK; }
     hipStream_t cs = h->copy_stream;
     if (h->use_done[slot]) HIPCHK(h, hipStreamWaitEvent(cs, h->use_done[slot], 0));   // the count that last read this slot
-    const uint64_t pw_in = (n_bases + 31) / 32, mw_in = (n_bases + 63) / 64;
-    // the caller's arrays hold ceil(n/32) / ceil(n/64) meaningful words: pad the rest on the device
-    if (pw > pw_in) HIPCHK(h, hipMemsetAsync((uint64_t *)h->up_buf[slot][0] + pw_in, 0, (pw - pw_in) * 8, cs));
-    if (mw > mw_in) HIPCHK(h, hipMemsetAsync((uint64_t *)h->up_buf[slot][1] + mw_in, 0xFF, (mw - mw_in) * 8, cs));
-    HIPCHK(h, hipMemcpyAsync(h->up_buf[slot][0], packed, pw_in * 8, hipMemcpyHostToDevice, cs));
-    HIPCHK(h, hipMemcpyAsync(h->up_buf[slot][1], invalid, mw_in * 8, hipMemcpyHostToDevice, cs));
-    if (n_bases % 64)                                           // bits past n_bases in the last mask word must read "invalid"
-        hipLaunchKernelGGL(kdf_mask_tail_kernel, dim3(1), dim3(1), 0, cs, (uint64_t *)h->up_buf[slot][1] + (mw_in - 1), ~0ull << (n_bases % 64));
-    HIPCHK(h, hipGetLastError());
+    int rc = upload_padded(h, packed, invalid, n_bases, (uint64_t *)h->up_buf[slot][0], (uint64_t *)h->up_buf[slot][1], cs);
+    if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->up_done[slot], cs));
     h->up_valid[slot] = true;
     return KDF_OK;
@@ -1595,8 +1631,22 @@ static int sieve_prepare(kdf_engine *h, uint64_t n) {
     return KDF_OK;
 }
 
-// the table becomes exactly the n keys at d_lo / d_hi (device arrays) with count 0
-static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t n) {
+__global__ void kdf_ctl_clear_error_bits_kernel(KdfCtl *ctl, unsigned int bits) { atomicAnd(&ctl->error, ~bits); }
+
+// after an insert of caller keys and a ctl_sync: a long key with a top-word bit at or above 2k - 64 (W - 1) was refused
+// (error bit 4).  Only that bit is cleared: a bucket overflow of the same launch (bit 1) stays raised and is reported too.
+static int long_bad_keys(kdf_engine *h, const char *fn) {
+    const unsigned int err = (unsigned int)h->h_out4[2];
+    if (!(err & 4)) return KDF_OK;
+    hipLaunchKernelGGL(kdf_ctl_clear_error_bits_kernel, dim3(1), dim3(1), 0, h->stream, h->ctl, 4u);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return fail(h, KDF_ERR_INVALID, "%s: a key's top word has bits at or above bit %d (no k-mer of k=%d); it was left out%s", fn,
+                long_top_bits(h), h->k, (err & 1) ? "; a bucket also overflowed (KDF_ERR_TABLE_FULL)" : "");
+}
+
+// the table becomes exactly the n keys at d_lo / d_hi (device arrays; long keys: the rows at d_lo) with count 0
+static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t n, const char *fn) {
     int rc;
     h->sieve_valid = false;
     if ((rc = pending_drop(h))) return rc;            // the table becomes the filter: whatever was pending goes with the old contents
@@ -1612,23 +1662,22 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
     } else if ((rc = kdf_clear(h))) return rc;
     if ((rc = materialize(h))) return rc;
     h->filter_mode = true;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
     if (n) {
-        if (h->kw == 1)
-            hipLaunchKernelGGL(kdf_insert_keys_kernel<1>, dim3(blocks), dim3(256), 0, h->stream,
-                               d_lo, (const uint64_t *)nullptr, (const uint32_t *)nullptr, n, h->t, h->ctl, 0, 0);
-        else
-            hipLaunchKernelGGL(kdf_insert_keys_kernel<2>, dim3(blocks), dim3(256), 0, h->stream,
-                               d_lo, d_hi, (const uint32_t *)nullptr, n, h->t, h->ctl, 0, 0);
+        insert_keys(h, h->t, d_lo, d_hi, nullptr, n, false);
         HIPCHK(h, hipGetLastError());
         bool full = false;
         if ((rc = ctl_sync(h, &full))) return rc;
-        if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_load_filter: bucket overflow");
+        if ((rc = long_bad_keys(h, fn))) return rc;
+        if (full) return fail(h, KDF_ERR_TABLE_FULL, "%s: bucket overflow", fn);
     }
+    if (is_long(h)) return KDF_OK;                   // (no sieve for long keys)
     if ((rc = sieve_prepare(h, n)) != KDF_OK) return rc;
     if (h->sieve_valid && n) {
-        if (h->kw == 1) hipLaunchKernelGGL(kdf_sieve_build_kernel<1>, dim3(blocks), dim3(256), 0, h->stream, d_lo, (const uint64_t *)nullptr, n, h->sieve, h->sieve_words - 1);
-        else hipLaunchKernelGGL(kdf_sieve_build_kernel<2>, dim3(blocks), dim3(256), 0, h->stream, d_lo, d_hi, n, h->sieve, h->sieve_words - 1);
+        by_width(h, [&](auto KWc) {
+            hipLaunchKernelGGL(kdf_sieve_build_kernel<decltype(KWc)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                               d_lo, d_hi, n, h->sieve, h->sieve_words - 1);
+            return 0;
+        });
         HIPCHK(h, hipGetLastError());
     }
     return KDF_OK;
@@ -1640,15 +1689,8 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
     if (n && (!keys_lo || (h->kw == 2 && !keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_load_filter: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if (n) {
-        if ((rc = stage_reserve(h, 2, n * 8))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[2], keys_lo, n * 8, hipMemcpyHostToDevice, h->stream));
-        if (h->kw == 2) {
-            if ((rc = stage_reserve(h, 3, n * 8))) return rc;
-            HIPCHK(h, hipMemcpyAsync(h->stage[3], keys_hi, n * 8, hipMemcpyHostToDevice, h->stream));
-        }
-    }
-    return load_filter_core(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3], n);
+    if (n && (rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_load_filter"))) return rc;
+    return load_filter_core(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3], n, "kdf_load_filter");
 }
 
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n) {
@@ -1656,7 +1698,7 @@ int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys
     KDF_REFUSE_LONG(h, "kdf_load_filter_dev", "kdf_load_filter_w_dev");
     if (n && (!d_keys_lo || (h->kw == 2 && !d_keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    return load_filter_core(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, n);
+    return load_filter_core(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, n, "kdf_load_filter");
 }
 
 int kdf_reset_counts(kdf_engine *h) {
@@ -1682,9 +1724,10 @@ static int merge_reserve(kdf_engine *h, size_t bytes) {
 // insert-or-add (key, count) pairs resident in HBM, in `nseg` segments (one per source rank of a merge); grows the
 // table first so the pairs fit at load <= 0.5 even if all of them are new.  Hash-layout tables take segments of any
 // order: km_bounds_kernel tests on the device whether every segment is grouped by table bucket (a dump made by
-// kdf_export_parts_dev is) and the LDS bucket merge or the atomic insert runs accordingly -- no host decision.
+// kdf_export_parts_dev is) and the LDS bucket merge or the atomic insert runs accordingly -- no host decision.  Long keys
+// (the rows at d_lo) take the atomic insert.
 static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *d_lo, const uint64_t *const *d_hi,
-                           const uint32_t *const *d_cnt, const uint64_t *n) {
+                           const uint32_t *const *d_cnt, const uint64_t *n, const char *fn) {
     uint64_t total = 0, nmax = 0;
     bool counts = true;
     for (uint32_t s = 0; s < nseg; ++s) { total += n[s]; nmax = std::max(nmax, n[s]); if (n[s] && !d_cnt[s]) counts = false; }
@@ -1694,27 +1737,12 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
     if ((rc = pending_flush(h))) return rc;
     if ((rc = ctl_sync(h, nullptr))) return rc;
     const uint32_t want = cap_log2_for(h->distinct + total);
-    if (want > h->t.log2cap) {
-        if (h->lazy_empty) {                         // nothing to carry over: a new table, still to be cleared
-            KdfTable nt;
-            if ((rc = table_alloc(h, want, nt, false))) return rc;
-            HIPCHK(h, hipStreamSynchronize(h->stream));          // (nothing in flight may still touch the old arrays)
-            table_free(h->t);
-            h->t = nt; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
-            h->cap = 1ull << want;
-        } else if ((rc = table_rehash(h, want))) return rc;
-    }
-    const bool lds = counts && total >= h->opt_merge_min_pairs && nseg <= KM_MAX_SEGS && nmax < 0xFFFFFFFFull;
+    if (want > h->t.log2cap && (rc = table_rehash(h, want))) return rc;
+    const bool lds = !is_long(h) && counts && total >= h->opt_merge_min_pairs && nseg <= KM_MAX_SEGS && nmax < 0xFFFFFFFFull;
     if (!lds) {
         if ((rc = materialize(h))) return rc;
-        for (uint32_t s = 0; s < nseg; ++s) {
-            if (!n[s]) continue;
-            const unsigned blocks = (unsigned)((n[s] + 255) / 256);
-            if (h->kw == 1)
-                hipLaunchKernelGGL(kdf_insert_keys_kernel<1>, dim3(blocks), dim3(256), 0, h->stream, d_lo[s], (const uint64_t *)nullptr, d_cnt[s], n[s], h->t, h->ctl, 0, 0);
-            else
-                hipLaunchKernelGGL(kdf_insert_keys_kernel<2>, dim3(blocks), dim3(256), 0, h->stream, d_lo[s], d_hi[s], d_cnt[s], n[s], h->t, h->ctl, 0, 0);
-        }
+        for (uint32_t s = 0; s < nseg; ++s)
+            if (n[s]) insert_keys(h, h->t, d_lo[s], d_hi[s], d_cnt[s], n[s], false);
         h->last_merge_path = 2;
     } else {
         KmSegs sg{};
@@ -1758,12 +1786,13 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
     bool full = false;
     if ((rc = ctl_sync(h, &full))) return rc;
     if (h->last_merge_path == 1 && h->merge_flag_host) h->last_merge_path = 2;     // a segment was not grouped: the atomic kernel did the work
-    if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_add_pairs: bucket overflow");
+    if ((rc = long_bad_keys(h, fn))) return rc;
+    if (full) return fail(h, KDF_ERR_TABLE_FULL, "%s: bucket overflow", fn);
     return KDF_OK;
 }
 
-static int add_pairs_dev(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_hi, const uint32_t *d_cnt, uint64_t n) {
-    return add_pairs_multi(h, 1, &d_lo, &d_hi, &d_cnt, &n);
+static int add_pairs_dev(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_hi, const uint32_t *d_cnt, uint64_t n, const char *fn) {
+    return add_pairs_multi(h, 1, &d_lo, &d_hi, &d_cnt, &n, fn);
 }
 
 int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_keys_lo, const void *const *d_keys_hi,
@@ -1781,7 +1810,7 @@ int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_k
         if (n[s] && (!lo[s] || (h->kw == 2 && !hi[s]))) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_multi_dev: segment %u has NULL keys", s);
     }
     HIPCHK(h, hipSetDevice(h->device));
-    return add_pairs_multi(h, nseg, lo.data(), hi.data(), cnt.data(), n);
+    return add_pairs_multi(h, nseg, lo.data(), hi.data(), cnt.data(), n, "kdf_add_pairs");
 }
 
 int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
@@ -1789,7 +1818,7 @@ int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_h
     KDF_REFUSE_LONG(h, "kdf_add_pairs_dev", "kdf_add_pairs_w_dev");
     if (n && (!d_keys_lo || (h->kw == 2 && !d_keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    return add_pairs_dev(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, (const uint32_t *)d_counts, n);
+    return add_pairs_dev(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, (const uint32_t *)d_counts, n, "kdf_add_pairs");
 }
 
 int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, const uint32_t *counts, uint64_t n) {
@@ -1799,18 +1828,10 @@ int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_h
     if (!keys_lo || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = stage_reserve(h, 2, n * 8))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys_lo, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (h->kw == 2) {
-        if ((rc = stage_reserve(h, 3, n * 8))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[3], keys_hi, n * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    if (counts) {
-        if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[0], counts, n * 4, hipMemcpyHostToDevice, h->stream));
-    }
+    if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_add_pairs"))) return rc;
+    if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs"))) return rc;
     return add_pairs_dev(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3],
-                         counts ? (const uint32_t *)h->stage[0] : nullptr, n);
+                         counts ? (const uint32_t *)h->stage[0] : nullptr, n, "kdf_add_pairs");
 }
 
 int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
@@ -1822,9 +1843,12 @@ int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_
     int rc;
     if ((rc = pending_flush(h))) return rc;
     if ((rc = materialize(h))) return rc;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (h->kw == 1) hipLaunchKernelGGL(kdf_set_counts_kernel<1>, dim3(blocks), dim3(256), 0, h->stream, (const uint64_t *)d_keys_lo, (const uint64_t *)nullptr, (const uint32_t *)d_counts, n, h->t, h->ctl);
-    else hipLaunchKernelGGL(kdf_set_counts_kernel<2>, dim3(blocks), dim3(256), 0, h->stream, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, (const uint32_t *)d_counts, n, h->t, h->ctl);
+    by_width(h, [&](auto KWc) {
+        constexpr int KW = decltype(KWc)::value;
+        hipLaunchKernelGGL(kdf_set_counts_kernel<KW>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_keys_lo,
+                           KW == 2 ? (const uint64_t *)d_keys_hi : nullptr, (const uint32_t *)d_counts, n, h->t, h->ctl);
+        return 0;
+    });
     HIPCHK(h, hipGetLastError());
     bool bad = false;
     if ((rc = ctl_sync(h, &bad))) return rc;
@@ -1856,23 +1880,33 @@ int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed, const uint64
     return KDF_OK;
 }
 
+// the counts of n keys (device: the (lo, hi) arrays of k <= 63, the rows at lo of long keys) into out (0: absent)
+static int query_core(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uint64_t n, uint32_t *out) {
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    { int rc0 = materialize(h); if (rc0) return rc0; }
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        for (uint64_t off = 0; off < n; off += 1ull << 30) {             // (a launch holds fewer than 2^32 threads)
+            const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+            const unsigned blocks = (unsigned)((m + 255) / 256);
+            if constexpr (W <= 2)
+                hipLaunchKernelGGL(kdf_query_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, lo + off, W == 2 ? hi + off : nullptr, m, h->t, out + off);
+            else
+                hipLaunchKernelGGL(kdf_long_query_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, lo + off * W, m, h->t, out + off, long_top_bits(h));
+        }
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
 int kdf_query_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n, void *d_counts_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     KDF_REFUSE_LONG(h, "kdf_query_dev", "kdf_query_w_dev");
     if (n == 0) return KDF_OK;
     if (!d_keys_lo || !d_counts_out || (h->kw == 2 && !d_keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_query_dev: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    { int rcf = pending_flush(h); if (rcf) return rcf; }
-    { int rc0 = materialize(h); if (rc0) return rc0; }
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (h->kw == 1)
-        hipLaunchKernelGGL(kdf_query_kernel<1>, dim3(blocks), dim3(256), 0, h->stream,
-                           (const uint64_t *)d_keys_lo, (const uint64_t *)nullptr, n, h->t, (uint32_t *)d_counts_out);
-    else
-        hipLaunchKernelGGL(kdf_query_kernel<2>, dim3(blocks), dim3(256), 0, h->stream,
-                           (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, n, h->t, (uint32_t *)d_counts_out);
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
+    return query_core(h, (const uint64_t *)d_keys_lo, (const uint64_t *)d_keys_hi, n, (uint32_t *)d_counts_out);
 }
 
 int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, uint64_t n, uint32_t *counts_out) {
@@ -1882,14 +1916,9 @@ int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, u
     if (!keys_lo || !counts_out || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_query: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = stage_reserve(h, 2, n * 8))) return rc;
+    if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_query"))) return rc;
     if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys_lo, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (h->kw == 2) {
-        if ((rc = stage_reserve(h, 3, n * 8))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[3], keys_hi, n * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = kdf_query_dev(h, h->stage[2], h->stage[3], n, h->stage[0]))) return rc;
+    if ((rc = query_core(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3], n, (uint32_t *)h->stage[0]))) return rc;
     HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
@@ -1907,24 +1936,21 @@ static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *
     HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor
     const uint64_t waves = (h->cap + KDF_EXPORT_ROWS * 64 - 1) / (KDF_EXPORT_ROWS * 64);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    if (is_long(h)) {                                       // rows of W words into olo
-        by_long(h, [&](auto Wc) {
-            constexpr int W = decltype(Wc)::value;
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W > 2) {                                     // rows of W words into olo
             if (write) hipLaunchKernelGGL((kdf_long_export_kernel<W, true>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ocnt, out_cap);
             else hipLaunchKernelGGL((kdf_long_export_kernel<W, false>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ocnt, out_cap);
-            return 0;
-        });
-    } else if (write) {                                            // one read of the table (any min_count: occupancy is tested on the key)
-        const unsigned rows = h->kw == 1 ? KDF_EXPORT1_ROWS : KDF_EXPORT1_ROWS / 2;
-        const uint64_t w1 = (h->cap + rows * 64 - 1) / (rows * 64);
-        const unsigned wpb = KDF_EXPORT1_THREADS / 64;
-        if (h->kw == 1) hipLaunchKernelGGL(kdf_export1_kernel<1>, dim3((unsigned)((w1 + wpb - 1) / wpb)), dim3(KDF_EXPORT1_THREADS), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
-        else hipLaunchKernelGGL(kdf_export1_kernel<2>, dim3((unsigned)((w1 + wpb - 1) / wpb)), dim3(KDF_EXPORT1_THREADS), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
-    } else if (h->kw == 1) {
-        hipLaunchKernelGGL((kdf_export_kernel<1, false>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
-    } else {
-        hipLaunchKernelGGL((kdf_export_kernel<2, false>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
-    }
+        } else if (write) {                                        // one read of the table (any min_count: occupancy is tested on the key)
+            const unsigned rows = W == 1 ? KDF_EXPORT1_ROWS : KDF_EXPORT1_ROWS / 2;
+            const uint64_t w1 = (h->cap + rows * 64 - 1) / (rows * 64);
+            const unsigned wpb = KDF_EXPORT1_THREADS / 64;
+            hipLaunchKernelGGL(kdf_export1_kernel<W>, dim3((unsigned)((w1 + wpb - 1) / wpb)), dim3(KDF_EXPORT1_THREADS), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
+        } else {
+            hipLaunchKernelGGL((kdf_export_kernel<W, false>), dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, h->ctl, olo, ohi, ocnt, out_cap);
+        }
+        return 0;
+    });
     HIPCHK(h, hipGetLastError());
     uint64_t cursor = 0;
     int rc = ctl_sync(h, nullptr, &cursor);
@@ -2022,37 +2048,60 @@ int kdf_count_ge(kdf_engine *h, uint32_t min_count, uint64_t *n_out) {
     return export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, n_out);
 }
 
-int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out, uint64_t *keys_hi_out,
-                  uint32_t *counts_out, uint64_t cap, uint64_t *n_out) {
-    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge: NULL pointer");
-    KDF_REFUSE_LONG(h, "kdf_export_ge", "kdf_export_ge_w");
+// The entries with count >= min_count into device buffers (the (lo, hi) arrays of k <= 63 with hi NULL for k <= 32, the
+// rows at lo of long keys), sorted if asked; sort_err: the entry point's code for a failed sort.  ONE pass over the table:
+// entries are appended through the cursor, nothing is written past `cap`, and the cursor's final value is the number of
+// entries the dump holds (kdf_count_ge gives it beforehand).
+static int export_core(kdf_engine *h, uint32_t min_count, uint64_t *lo, uint64_t *hi, uint32_t *cnt, uint64_t cap, bool sorted,
+                       uint64_t *n_out, const char *fn, int sort_err) {
+    uint64_t n = 0;
+    int rc = export_pass(h, min_count, true, lo, hi, cnt, cap, &n);
+    if (rc) return rc;
+    *n_out = n;
+    if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
+    if (sorted && n) {
+        if (!cnt) return fail(h, KDF_ERR_INVALID, "%s: sorted export needs the counts array", fn);
+        std::string serr;
+        if (is_long(h) ? kdf_sort_rows_device(lo, h->kw, cnt, n, h->stream, serr) : kdf_sort_pairs_device(lo, hi, cnt, n, h->stream, serr))
+            return fail(h, sort_err, "%s: sort failed: %s", fn, serr.c_str());
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+// the host forms: a counting pass sizes the dump, which is staged, sorted and copied back
+static int export_host(kdf_engine *h, uint32_t min_count, uint64_t *lo_out, uint64_t *hi_out, uint32_t *cnt_out, uint64_t cap,
+                       uint64_t *n_out, const char *fn, int sort_err) {
     HIPCHK(h, hipSetDevice(h->device));
     uint64_t n = 0;
     int rc = export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, &n);
     if (rc) return rc;
     *n_out = n;
     if (n == 0) return KDF_OK;
-    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge: %llu entries, room for %llu",
-                             (unsigned long long)n, (unsigned long long)cap);
-    if (!keys_lo_out || (h->kw == 2 && !keys_hi_out)) return fail(h, KDF_ERR_INVALID, "kdf_export_ge: NULL key output");
-    if ((rc = stage_reserve(h, 2, n * 8))) return rc;
+    if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
+    if (!lo_out || (h->kw == 2 && !hi_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL key output", fn);
+    const size_t lo_bytes = n * 8 * lo_words(h);
+    if ((rc = stage_reserve(h, 2, lo_bytes))) return rc;
     if ((rc = stage_reserve(h, 0, n * 4))) return rc;
     if (h->kw == 2 && (rc = stage_reserve(h, 3, n * 8))) return rc;
     uint64_t n2 = 0;
-    rc = export_pass(h, min_count, true, (uint64_t *)h->stage[2], h->kw == 2 ? (uint64_t *)h->stage[3] : nullptr,
-                     (uint32_t *)h->stage[0], n, &n2);
+    rc = export_core(h, min_count, (uint64_t *)h->stage[2], h->kw == 2 ? (uint64_t *)h->stage[3] : nullptr, (uint32_t *)h->stage[0],
+                     n, true, &n2, fn, sort_err);
     if (rc) return rc;
-    if (n2 != n) return fail(h, KDF_ERR_STATE, "kdf_export_ge: table changed between passes");
-    std::string serr;
-    if (kdf_sort_pairs_device((uint64_t *)h->stage[2], h->kw == 2 ? (uint64_t *)h->stage[3] : nullptr,
-                              (uint32_t *)h->stage[0], n, h->stream, serr))
-        return fail(h, KDF_ERR_HIP, "kdf_export_ge: sort failed: %s", serr.c_str());
-    HIPCHK(h, hipMemcpyAsync(keys_lo_out, h->stage[2], n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(keys_hi_out, h->stage[3], n * 8, hipMemcpyDeviceToHost, h->stream));
-    else if (keys_hi_out) memset(keys_hi_out, 0, n * 8);
-    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (n2 != n) return fail(h, KDF_ERR_STATE, "%s: table changed between passes", fn);
+    HIPCHK(h, hipMemcpyAsync(lo_out, h->stage[2], lo_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3], n * 8, hipMemcpyDeviceToHost, h->stream));
+    else if (hi_out) memset(hi_out, 0, n * 8);
+    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
+}
+
+int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out, uint64_t *keys_hi_out,
+                  uint32_t *counts_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge: NULL pointer");
+    KDF_REFUSE_LONG(h, "kdf_export_ge", "kdf_export_ge_w");
+    return export_host(h, min_count, keys_lo_out, keys_hi_out, counts_out, cap, n_out, "kdf_export_ge", KDF_ERR_HIP);
 }
 
 int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out, void *d_keys_hi_out,
@@ -2061,24 +2110,8 @@ int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out, vo
     KDF_REFUSE_LONG(h, "kdf_export_ge_dev", "kdf_export_ge_w_dev");
     HIPCHK(h, hipSetDevice(h->device));
     if (cap && (!d_keys_lo_out || (h->kw == 2 && !d_keys_hi_out))) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_dev: NULL key output");
-    // ONE pass over the table: entries are appended through the cursor, nothing is written past `cap`, and the
-    // cursor's final value is the number of entries the dump holds (kdf_count_ge gives it beforehand)
-    uint64_t n = 0;
-    int rc = export_pass(h, min_count, true, (uint64_t *)d_keys_lo_out, h->kw == 2 ? (uint64_t *)d_keys_hi_out : nullptr,
-                         (uint32_t *)d_counts_out, cap, &n);
-    if (rc) return rc;
-    *n_out = n;
-    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_dev: %llu entries, room for %llu",
-                             (unsigned long long)n, (unsigned long long)cap);
-    if (sorted && n) {
-        if (!d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_dev: sorted export needs the counts array");
-        std::string serr;
-        if (kdf_sort_pairs_device((uint64_t *)d_keys_lo_out, h->kw == 2 ? (uint64_t *)d_keys_hi_out : nullptr,
-                                  (uint32_t *)d_counts_out, n, h->stream, serr))
-            return fail(h, KDF_ERR_HIP, "kdf_export_ge_dev: sort failed: %s", serr.c_str());
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    return export_core(h, min_count, (uint64_t *)d_keys_lo_out, h->kw == 2 ? (uint64_t *)d_keys_hi_out : nullptr, (uint32_t *)d_counts_out,
+                       cap, sorted != 0, n_out, "kdf_export_ge_dev", KDF_ERR_HIP);
 }
 
 int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, void *d_hit_bits) {
@@ -2096,27 +2129,18 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
             if ((rc = ctl_sync(h, nullptr))) return rc;
             if ((rc = sieve_prepare(h, h->distinct))) return rc;
             if (h->sieve_valid) {
-                const unsigned tb = (unsigned)((h->cap + 255) / 256);
-                if (h->kw == 1) hipLaunchKernelGGL(kdf_sieve_from_table_kernel<1>, dim3(tb), dim3(256), 0, h->stream, h->t, h->sieve, h->sieve_words - 1);
-                else hipLaunchKernelGGL(kdf_sieve_from_table_kernel<2>, dim3(tb), dim3(256), 0, h->stream, h->t, h->sieve, h->sieve_words - 1);
+                by_width(h, [&](auto KWc) {
+                    hipLaunchKernelGGL(kdf_sieve_from_table_kernel<decltype(KWc)::value>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0,
+                                       h->stream, h->t, h->sieve, h->sieve_words - 1);
+                    return 0;
+                });
                 HIPCHK(h, hipGetLastError());
             }
         }
         if (h->sieve_valid) {
             HIPCHK(h, hipMemsetAsync(d_hit_bits, 0, n_tiles * 8, h->stream));
-            const int WPT = h->kw == 1 ? KbCfg<1>::WPT : KbCfg<2>::WPT;
-            const uint64_t tiles_per_slab = KB_THREADS / (64 / WPT);
-            const uint64_t n_slabs = (n_tiles + tiles_per_slab - 1) / tiles_per_slab;
-            const uint32_t n_wg = (uint32_t)std::min<uint64_t>(n_slabs, (uint64_t)h->n_cu * 8);
-            const uint32_t spw = (uint32_t)((n_slabs + n_wg - 1) / n_wg);
-            const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
-            KdfSieve sv{h->sieve, h->sieve_words - 1};
-            unsigned long long *hb = (unsigned long long *)d_hit_bits;
-            const bool in_lds = h->sieve_words <= KDF_SV_LDS_WORDS;
-#define SV_SCAN(KWV, L) hipLaunchKernelGGL((kdf_sieve_count_kernel<KWV, L, true>), dim3(grid), dim3(KB_THREADS), 0, h->stream, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw, hb)
-            if (h->kw == 1) { if (in_lds) SV_SCAN(1, true); else SV_SCAN(1, false); }
-            else { if (in_lds) SV_SCAN(2, true); else SV_SCAN(2, false); }
-#undef SV_SCAN
+            launch_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, (unsigned long long *)d_hit_bits,
+                         h->sieve_words <= KDF_SV_LDS_WORDS);
             HIPCHK(h, hipGetLastError());
             return KDF_OK;
         }
@@ -2126,30 +2150,25 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
     return KDF_OK;
 }
 
-// host-side canonical key of the window at stream position p (used to count
-// the DISTINCT hit k-mers of the few reads that carry hits)
-static inline void host_window_key(const uint64_t *packed, uint64_t p, int k, uint64_t &klo, uint64_t &khi) {
-    unsigned __int128 e = 0;
-    for (int j = 0; j < k; ++j) {
-        const uint64_t q = p + j;
-        const unsigned __int128 b = (packed[q >> 5] >> ((q & 31) * 2)) & 3;
-        e |= b << (2 * j);
+// host-side canonical key of the window at stream position p, used to count the DISTINCT hit k-mers of the few reads
+// that carry hits: the smaller of the forward and reverse-complement codes, ceil(2k/64) words, word 0 least significant
+// (kdf_canonical_w's rule), the unused words 0
+static std::array<uint64_t, 7> host_window_key(const uint64_t *packed, uint64_t p, int k) {
+    const int W = (2 * k + 63) / 64;
+    uint64_t f[7] = {0}, r[7] = {0};
+    for (int i = 0; i < k; ++i) {
+        const uint64_t q = p + i;
+        const uint64_t c = (packed[q >> 5] >> ((q & 31) * 2)) & 3;
+        // forward: (f << 2) | c; reverse complement: base i lands at bits 2i of r
+        for (int j = W - 1; j >= 1; --j) f[j] = (f[j] << 2) | (f[j - 1] >> 62);
+        f[0] = (f[0] << 2) | c;
+        r[i >> 5] |= (3 - c) << (2 * (i & 31));
     }
-    const unsigned __int128 mask = (((unsigned __int128)1) << (2 * k)) - 1;
-    unsigned __int128 rc = ~e & mask, fwd = 0;
-    for (int j = 0; j < k; ++j) fwd |= ((e >> (2 * j)) & 3) << (2 * (k - 1 - j));
-    const unsigned __int128 c = fwd < rc ? fwd : rc;
-    klo = (uint64_t)c; khi = (uint64_t)(c >> 64);
-}
-
-// the same for long keys: ceil(2k/64) words, word 0 least significant (kdf_canonical_w's rule)
-static inline void host_window_key_w(const uint64_t *packed, uint64_t p, int k, uint64_t *w) {
-    std::string s((size_t)k, 'A');
-    for (int j = 0; j < k; ++j) {
-        const uint64_t q = p + j;
-        s[(size_t)j] = "ACGT"[(packed[q >> 5] >> ((q & 31) * 2)) & 3];
-    }
-    (void)kdf_canonical_w(s.data(), k, w);
+    bool lt = false;
+    for (int j = W - 1; j >= 0; --j) if (f[j] != r[j]) { lt = f[j] < r[j]; break; }
+    std::array<uint64_t, 7> key{};
+    for (int j = 0; j < W; ++j) key[j] = lt ? f[j] : r[j];
+    return key;
 }
 
 int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
@@ -2173,11 +2192,10 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!read_offsets || !distinct_out) return KDF_OK;
     // distinct hit k-mers per read: only reads with hits are touched
-    std::vector<std::pair<uint64_t, uint64_t>> keys;
-    std::vector<std::array<uint64_t, 7>> keys_w;             // long keys: W <= 7 words (unused words 0)
+    std::vector<std::array<uint64_t, 7>> keys;
     for (int64_t r = 0; r < n_reads; ++r) {
         const uint64_t b = (uint64_t)read_offsets[r], e = (uint64_t)read_offsets[r + 1];
-        keys.clear(); keys_w.clear();
+        keys.clear();
         for (uint64_t wd = b >> 6; wd <= (e ? (e - 1) >> 6 : 0) && wd < n_tiles; ++wd) {
             uint64_t bits = hit_bits[wd];
             while (bits) {
@@ -2185,20 +2203,8 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
                 bits &= bits - 1;
                 const uint64_t p = (wd << 6) + bit;
                 if (p < b || p >= e) continue;
-                if (is_long(h)) {
-                    std::array<uint64_t, 7> w{};
-                    host_window_key_w(packed, p, h->k, w.data());
-                    keys_w.push_back(w);
-                    continue;
-                }
-                uint64_t lo, hi;
-                host_window_key(packed, p, h->k, lo, hi);
-                keys.emplace_back(hi, lo);
+                keys.push_back(host_window_key(packed, p, h->k));
             }
-        }
-        if (!keys_w.empty()) {
-            std::sort(keys_w.begin(), keys_w.end());
-            distinct_out[r] = (uint32_t)(std::unique(keys_w.begin(), keys_w.end()) - keys_w.begin());
         }
         if (keys.empty()) continue;
         std::sort(keys.begin(), keys.end());
@@ -2210,77 +2216,6 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
 // ---- long keys (odd k 65..201): W-word keys, row-major -----------------------------------------------------------
 #define KDF_NEED_LONG(h, fn) \
     do { if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: takes engines for odd k 65..%d only (k=%d: use the (lo, hi) form)", fn, KDF_LONG_MAX_K, (h)->k); } while (0)
-
-static void long_insert_launch(kdf_engine *h, const uint64_t *d_keys, const uint32_t *d_cnt, uint64_t n) {
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    by_long(h, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        hipLaunchKernelGGL(kdf_long_insert_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, d_keys, d_keys + 1, (uint64_t)W, (uint64_t)1,
-                           d_cnt, n, h->t, h->ctl, 0, long_top_bits(h));
-        return 0;
-    });
-}
-
-__global__ void kdf_ctl_clear_error_bits_kernel(KdfCtl *ctl, unsigned int bits) { atomicAnd(&ctl->error, ~bits); }
-
-// after a long_insert_launch of caller keys: a key with a top-word bit at or above 2k - 64 (W - 1) was refused (error
-// bit 4).  Only that bit is cleared: a bucket overflow of the same launch (bit 1) stays raised and is reported too.
-static int long_bad_keys(kdf_engine *h, const char *fn) {
-    const unsigned int err = (unsigned int)h->h_out4[2];
-    if (!(err & 4)) return KDF_OK;
-    hipLaunchKernelGGL(kdf_ctl_clear_error_bits_kernel, dim3(1), dim3(1), 0, h->stream, h->ctl, 4u);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return fail(h, KDF_ERR_INVALID, "%s: a key's top word has bits at or above bit %d (no k-mer of k=%d); it was left out%s", fn,
-                long_top_bits(h), h->k, (err & 1) ? "; a bucket also overflowed (KDF_ERR_TABLE_FULL)" : "");
-}
-
-// insert-or-add n row-major keys (device) with optional counts; grows first so that they fit at load <= 0.5
-static int long_add_pairs(kdf_engine *h, const uint64_t *d_keys, const uint32_t *d_cnt, uint64_t n) {
-    if (n == 0) return KDF_OK;
-    int rc;
-    if ((rc = pending_flush(h))) return rc;
-    if ((rc = ctl_sync(h, nullptr))) return rc;
-    const uint32_t want = cap_log2_for(h->distinct + n);
-    if (want > h->t.log2cap && (rc = table_rehash(h, want))) return rc;
-    if ((rc = materialize(h))) return rc;
-    for (uint64_t off = 0; off < n; off += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
-        const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
-        long_insert_launch(h, d_keys + off * h->kw, d_cnt ? d_cnt + off : nullptr, m);
-    }
-    HIPCHK(h, hipGetLastError());
-    bool full = false;
-    if ((rc = ctl_sync(h, &full))) return rc;
-    if ((rc = long_bad_keys(h, "kdf_add_pairs_w"))) return rc;
-    if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_add_pairs_w: bucket overflow");
-    return KDF_OK;
-}
-
-static int long_load_filter(kdf_engine *h, const uint64_t *d_keys, uint64_t n) {
-    int rc;
-    h->sieve_valid = false;
-    if ((rc = pending_drop(h))) return rc;
-    const uint32_t want = cap_log2_for(n);
-    if (want != h->t.log2cap) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        table_free(h->t);
-        if ((rc = table_alloc(h, want, h->t))) return rc;
-        h->cap = 1ull << want;
-        if ((rc = ctl_reset(h, false))) return rc;
-        h->distinct = 0; h->windows = 0; h->lazy_empty = false; h->filter_mode = false;
-    } else if ((rc = kdf_clear(h))) return rc;
-    if ((rc = materialize(h))) return rc;
-    h->filter_mode = true;
-    if (n) {
-        long_insert_launch(h, d_keys, nullptr, n);
-        HIPCHK(h, hipGetLastError());
-        bool full = false;
-        if ((rc = ctl_sync(h, &full))) return rc;
-        if ((rc = long_bad_keys(h, "kdf_load_filter_w"))) return rc;
-        if (full) return fail(h, KDF_ERR_TABLE_FULL, "kdf_load_filter_w: bucket overflow");
-    }
-    return KDF_OK;
-}
 
 int kdf_key_words(int k) {
     if (k >= 1 && k <= 32) return 1;
@@ -2294,8 +2229,7 @@ int kdf_add_pairs_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts,
     KDF_NEED_LONG(h, "kdf_add_pairs_w_dev");
     if (n && !d_keys) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_w_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    h->sieve_valid = false;
-    return long_add_pairs(h, (const uint64_t *)d_keys, (const uint32_t *)d_counts, n);
+    return add_pairs_dev(h, (const uint64_t *)d_keys, nullptr, (const uint32_t *)d_counts, n, "kdf_add_pairs_w");
 }
 
 int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts, uint64_t n) {
@@ -2305,13 +2239,9 @@ int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts,
     if (!keys) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_w: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
-    if (counts) {
-        if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[0], counts, n * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    return long_add_pairs(h, (const uint64_t *)h->stage[2], counts ? (const uint32_t *)h->stage[0] : nullptr, n);
+    if ((rc = stage_keys(h, keys, nullptr, n, "kdf_add_pairs_w"))) return rc;
+    if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs_w"))) return rc;
+    return add_pairs_dev(h, (const uint64_t *)h->stage[2], nullptr, counts ? (const uint32_t *)h->stage[0] : nullptr, n, "kdf_add_pairs_w");
 }
 
 int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n) {
@@ -2319,7 +2249,7 @@ int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n) {
     KDF_NEED_LONG(h, "kdf_load_filter_w_dev");
     if (n && !d_keys) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_w_dev: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    return long_load_filter(h, (const uint64_t *)d_keys, n);
+    return load_filter_core(h, (const uint64_t *)d_keys, nullptr, n, "kdf_load_filter_w");
 }
 
 int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n) {
@@ -2327,12 +2257,9 @@ int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n) {
     KDF_NEED_LONG(h, "kdf_load_filter_w");
     if (n && !keys) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_w: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    if (n) {
-        int rc;
-        if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
-    }
-    return long_load_filter(h, (const uint64_t *)h->stage[2], n);
+    int rc;
+    if (n && (rc = stage_keys(h, keys, nullptr, n, "kdf_load_filter_w"))) return rc;
+    return load_filter_core(h, (const uint64_t *)h->stage[2], nullptr, n, "kdf_load_filter_w");
 }
 
 int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_counts_out) {
@@ -2341,19 +2268,7 @@ int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_count
     if (n == 0) return KDF_OK;
     if (!d_keys || !d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_query_w_dev: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    { int rcf = pending_flush(h); if (rcf) return rcf; }
-    { int rc0 = materialize(h); if (rc0) return rc0; }
-    for (uint64_t off = 0; off < n; off += 1ull << 30) {
-        const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
-        by_long(h, [&](auto Wc) {
-            constexpr int W = decltype(Wc)::value;
-            hipLaunchKernelGGL(kdf_long_query_kernel<W>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream,
-                               (const uint64_t *)d_keys + off * W, m, h->t, (uint32_t *)d_counts_out + off, long_top_bits(h));
-            return 0;
-        });
-    }
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
+    return query_core(h, (const uint64_t *)d_keys, nullptr, n, (uint32_t *)d_counts_out);
 }
 
 int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *counts_out) {
@@ -2363,10 +2278,9 @@ int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *count
     if (!keys || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_query_w: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
+    if ((rc = stage_keys(h, keys, nullptr, n, "kdf_query_w"))) return rc;
     if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->stage[2], keys, n * 8 * h->kw, hipMemcpyHostToDevice, h->stream));
-    if ((rc = kdf_query_w_dev(h, h->stage[2], n, h->stage[0]))) return rc;
+    if ((rc = query_core(h, (const uint64_t *)h->stage[2], nullptr, n, (uint32_t *)h->stage[0]))) return rc;
     HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
@@ -2378,44 +2292,15 @@ int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, voi
     KDF_NEED_LONG(h, "kdf_export_ge_w_dev");
     HIPCHK(h, hipSetDevice(h->device));
     if (cap && !d_keys_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: NULL key output");
-    uint64_t n = 0;
-    int rc = export_pass(h, min_count, true, (uint64_t *)d_keys_out, nullptr, (uint32_t *)d_counts_out, cap, &n);
-    if (rc) return rc;
-    *n_out = n;
-    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: %llu entries, room for %llu",
-                             (unsigned long long)n, (unsigned long long)cap);
-    if (sorted && n) {
-        if (!d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: sorted export needs the counts array");
-        std::string serr;
-        if (kdf_sort_rows_device((uint64_t *)d_keys_out, h->kw, (uint32_t *)d_counts_out, n, h->stream, serr))
-            return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w_dev: sort failed: %s", serr.c_str());
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    return export_core(h, min_count, (uint64_t *)d_keys_out, nullptr, (uint32_t *)d_counts_out, cap, sorted != 0, n_out,
+                       "kdf_export_ge_w_dev", KDF_ERR_INVALID);
 }
 
 int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint32_t *counts_out, uint64_t cap,
                     uint64_t *n_out) {
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL pointer");
     KDF_NEED_LONG(h, "kdf_export_ge_w");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t n = 0;
-    int rc = export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, &n);
-    if (rc) return rc;
-    *n_out = n;
-    if (n == 0) return KDF_OK;
-    if (n > cap) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: %llu entries, room for %llu",
-                             (unsigned long long)n, (unsigned long long)cap);
-    if (!keys_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL key output");
-    if ((rc = stage_reserve(h, 2, n * 8 * h->kw))) return rc;
-    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    uint64_t n2 = 0;
-    if ((rc = kdf_export_ge_w_dev(h, min_count, h->stage[2], h->stage[0], n, 1, &n2))) return rc;
-    if (n2 != n) return fail(h, KDF_ERR_STATE, "kdf_export_ge_w: table changed between passes");
-    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[2], n * 8 * h->kw, hipMemcpyDeviceToHost, h->stream));
-    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    return export_host(h, min_count, keys_out, nullptr, counts_out, cap, n_out, "kdf_export_ge_w", KDF_ERR_INVALID);
 }
 
 int kdf_profile(kdf_engine *h, int enable) {
