@@ -19,6 +19,8 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from . import keys
+
 _registry: Dict[str, Tuple[object, Optional[object], int, Tuple[int, int]]] = {}
 
 
@@ -59,21 +61,29 @@ def forget(path: str):
 
 def to_host(lo, hi) -> Tuple[np.ndarray, np.ndarray]:
     """Device key tensors -> the (lo, hi) uint64 arrays the FASTA writer takes (long keys: ((n, W) rows, None))."""
-    if lo.dim() == 2:
-        return lo.cpu().numpy().view(np.uint64), None
-    hlo = lo.cpu().numpy().view(np.uint64)
-    hhi = hi.cpu().numpy().view(np.uint64) if hi is not None else np.zeros(len(hlo), np.uint64)
-    return hlo, hhi
+    return keys.to_pair(keys.from_pair(*(None if t is None else t.cpu().numpy().view(np.uint64) for t in (lo, hi))))
 
 
 def from_host(lo: np.ndarray, hi: Optional[np.ndarray], wide: bool, device: int = 0):
+    """Host keys -> device key tensors (hi None unless ``wide``; long keys: ((n, W) rows, None))."""
     import torch
     dev = torch.device("cuda", device)
-    tlo = torch.from_numpy(np.ascontiguousarray(lo, dtype=np.uint64).view(np.int64)).to(dev)
-    if tlo.dim() == 2:                                   # long keys: (n, W) rows
-        return tlo, None
-    thi = torch.from_numpy(np.ascontiguousarray(hi, dtype=np.uint64).view(np.int64)).to(dev) if wide else None
-    return tlo, thi
+    pair = keys.to_pair(keys.from_pair(lo, hi if wide else None), zero_hi=False)
+    return tuple(None if a is None else torch.from_numpy(a.view(np.int64)).to(dev) for a in pair)
+
+
+def select(sets, idx=None):
+    """One device key set from ``sets`` (a list of (lo, hi or None) sets, concatenated in order), masked or reordered
+    by ``idx`` (a bool mask or an index tensor) when given; contiguous."""
+    import torch
+    out = []
+    for parts in zip(*sets):
+        if parts[0] is None:
+            out.append(None)
+            continue
+        t = torch.cat(parts) if len(parts) > 1 else parts[0]
+        out.append(t if idx is None else t[idx].contiguous())
+    return tuple(out)
 
 
 def dump_ge(eng, min_count: int, device: int = 0):

@@ -20,7 +20,7 @@ import time
 
 import numpy as np
 
-from .. import devkeys, dist_env, jf_io
+from .. import devkeys, dist_env, jf_io, keys
 from .._native import KdfError
 from ..core.jellyfish_wrappers import (
     _device,
@@ -31,7 +31,7 @@ from ..core.jellyfish_wrappers import (
     _merge_filter_counts,
     _stream_bam,
 )
-from ..engine import key_words, mirror_engine
+from ..engine import mirror_engine
 from ..kmer_fasta import read_kmer_fasta_keys, remove_with_sidecar, write_kmer_fasta
 
 logger = logging.getLogger(__name__)
@@ -52,7 +52,7 @@ def _child_key_parts(child_bam, device=0, world=1, kmer_size=31):
     free, total = c_uint64(0), c_uint64(0)
     _native.check(_native.load().kdf_device_memory(device, byref(free), byref(total)))
     need = 4.6 * os.path.getsize(child_bam) / max(1, world)      # (several ranks: every rank holds its share of the keys twice -- local + owned)
-    W = key_words(kmer_size)
+    W = keys.key_words(kmer_size)
     if W > 2:
         need *= (8 * W + 4) / 12.0
     return max(1, int(-(-need // max(1.0, 0.7 * free.value))))
@@ -86,7 +86,6 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                 dev = torch.device("cuda", eng.device)
                 owner_eng = mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
                 merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
-            los, his = [], []
             dev_sets = []
             if parts > 1:
                 eng.set_option("key_parts", parts)
@@ -110,30 +109,23 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                     dlo, dhi = devkeys.dump_ge(owner_eng, min_child_count, eng.device)
                     dlo, dhi = dist_env.all_gather_keys(dlo, dhi)           # every rank holds the whole candidate set
                 dev_sets.append((dlo, dhi))
-                lo, hi = devkeys.to_host(dlo, dhi)
-                los.append(lo); his.append(hi)
-            if parts > 1:                                          # (long keys: (n, W) rows, no hi words)
-                lo, hi = np.concatenate(los), (np.concatenate(his) if his[0] is not None else None)
-                import torch
-                dev_sets = [(torch.cat([d[0] for d in dev_sets]), torch.cat([d[1] for d in dev_sets]) if dev_sets[0][1] is not None else None)]
-            else:
-                lo, hi = los[0], his[0]
+            cand = devkeys.select(dev_sets)
+            lo, hi = devkeys.to_host(*cand)
     except KdfError as e:
         raise RuntimeError(f"jellyfish count (child) failed: {e}") from e
     finally:
         if owner_eng is not None:
             owner_eng.close()
     if world > 1:                                                  # (rank order of the gathered sets is not key order)
-        order = np.lexsort((lo, hi))
-        lo, hi = lo[order], hi[order]
         import torch
-        o = torch.from_numpy(order).to(dev_sets[0][0].device)
-        dev_sets = [(dev_sets[0][0][o].contiguous(), dev_sets[0][1][o].contiguous() if dev_sets[0][1] is not None else None)]
+        order = keys.order(keys.from_pair(lo, hi, kmer_size))
+        lo, hi = lo[order], hi[order]
+        cand = devkeys.select([cand], torch.from_numpy(order).to(cand[0].device))
     n_candidates = len(lo)
     if rank == 0:
         write_kmer_fasta(child_candidates_fa, lo, hi, kmer_size)
     dist_env.barrier()                                             # the file exists (and has its final size) on every rank
-    devkeys.register(child_candidates_fa, dev_sets[0][0], dev_sets[0][1], kmer_size)
+    devkeys.register(child_candidates_fa, *cand, kmer_size)
     logger.info("Child k-mer dump complete (%s, %d candidates, FASTA: %s)",
                 _format_elapsed(time.monotonic() - dump_start), n_candidates,
                 _format_file_size(child_candidates_fa))
@@ -169,7 +161,7 @@ def _subtract_reference_kmers(ref_jf, child_candidates_fa, tmpdir):
                     import torch
                     from ..distributed import EngineOps, ShardedFilterCount
                     keep = ShardedFilterCount(EngineOps(eng, torch.device("cuda", eng.device)), stage_through_host=host).merged_counts(dev[0], dev[1]) == 0
-            dlo, dhi = dev[0][keep].contiguous(), (dev[1][keep].contiguous() if dev[1] is not None else None)
+            dlo, dhi = devkeys.select([dev], keep)
             lo, hi = devkeys.to_host(dlo, dhi)
         else:
             dlo = dhi = None
@@ -280,7 +272,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
                 eng.close()
         except (KdfError, ValueError, OSError) as e:
             raise RuntimeError(f"jellyfish count ({label}) failed: {e}") from e
-        return dlo[keep].contiguous(), (dhi[keep].contiguous() if dhi is not None else None)
+        return devkeys.select([(dlo, dhi)], keep)
 
     dlo, dhi = one_parent(mother_bam, "Mother", dlo, dhi)
     after_mother_fa = os.path.join(tmpdir, "after_mother.fa")

@@ -28,24 +28,12 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native
+from .keys import key_words
 from .reads import ReadStream, stream_words
 
 
 def _vp(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
-
-
-def key_words(k: int) -> int:
-    """Words per key of an engine for k: 1 (k <= 32), 2 (33..63), ceil(2k/64) for odd 65..201; 0 if no engine takes k
-    (the rule of ``kdf_key_words``, restated so that it is checked before any device call)."""
-    k = int(k)
-    if 1 <= k <= 32:
-        return 1
-    if 33 <= k <= 63:
-        return 2
-    if KmerEngine.LONG_MIN_K <= k <= KmerEngine.LONG_MAX_K and k % 2 == 1:
-        return (2 * k + 63) // 64
-    return 0
 
 
 class KmerEngine:

@@ -34,6 +34,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from . import keys
+
 KDF_FORMAT = "kdf/sorted"
 JF_FORMAT = "binary/sorted"
 
@@ -82,19 +84,7 @@ def _decode(data, kb: int, cb: int):
     bytes; the usual widths (8-byte keys, 4-byte counters) are plain views of one contiguous copy per field.  Keys of
     more than 16 bytes (long k-mers) come back as (n, W) uint64 rows in the lo position, hi = None."""
     n = len(data)
-    kraw = np.ascontiguousarray(data["k"])
-    if kb > 16:
-        W = (kb + 7) // 8
-        kbytes = np.zeros((n, 8 * W), dtype=np.uint8)
-        kbytes[:, :kb] = kraw
-        lo, hi = kbytes.view("<u8").reshape(n, W).astype(np.uint64, copy=False), None
-    elif kb == 8:
-        lo, hi = kraw.view("<u8").reshape(n), None
-    else:
-        kbytes = np.zeros((n, 16), dtype=np.uint8)
-        kbytes[:, :kb] = kraw
-        lo = np.ascontiguousarray(kbytes[:, :8]).view("<u8").reshape(n)
-        hi = np.ascontiguousarray(kbytes[:, 8:]).view("<u8").reshape(n) if kb > 8 else None
+    lo, hi = keys.to_pair(keys.from_bytes(np.ascontiguousarray(data["k"])), zero_hi=False)
     craw = np.ascontiguousarray(data["c"])
     if cb == 4:
         counts = craw.view("<u4").reshape(n)
@@ -145,37 +135,17 @@ def read_index(path: str, expect_k: Optional[int] = None):
     """-> (k, lo, hi, counts) ; hi is all zero for k <= 32; long k: lo = (n, W) rows, hi = None.  Counts saturate at
     2^32-1.  Whole file in memory: callers that only feed an engine use `load_index_into`."""
     k = _index_layout(path, expect_k)[0]
-    if k > 64:
-        rows, cnts = [], []
-        for _, keys, _, counts in iter_index(path, expect_k):
-            rows.append(keys); cnts.append(counts)
-        W = (2 * k + 63) // 64
-        if not rows:
-            return k, np.zeros((0, W), np.uint64), None, np.zeros(0, np.uint32)
-        return k, np.concatenate(rows), None, np.concatenate(cnts)
-    los, his, cnts = [], [], []
-    for _, lo, hi, counts in iter_index(path, expect_k):
-        los.append(lo); his.append(hi if hi is not None else np.zeros(len(lo), np.uint64)); cnts.append(counts)
-    if not los:
-        return k, np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
-    return k, np.concatenate(los), np.concatenate(his), np.concatenate(cnts)
+    blocks = [b[1:] for b in iter_index(path, expect_k)] or [(np.zeros(0, np.uint64), None, np.zeros(0, np.uint32))]
+    lo, hi, counts = (None if b[0] is None else np.concatenate(b) for b in zip(*blocks))
+    return (k, *keys.to_pair(keys.from_pair(lo, hi, k)), counts)
 
 
 def write_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.ndarray], counts: np.ndarray,
                 cmdline=None) -> str:
     """Write a ``kdf/sorted`` index (keys must already be in ascending order; long k: ``lo`` = (n, W) rows)."""
-    n = len(lo)
+    kbytes = keys.to_bytes(keys.from_pair(lo, hi, k), k)
+    n, kb = kbytes.shape
     key_len = 2 * k
-    kb = (key_len + 7) // 8
-    if k > 64:
-        W = (key_len + 63) // 64
-        rows = np.ascontiguousarray(lo, dtype="<u8").reshape(n, W)
-        kbytes = rows.view(np.uint8).reshape(n, 8 * W)
-    else:
-        kbytes = np.zeros((n, 16), dtype=np.uint8)
-        kbytes[:, :8] = np.ascontiguousarray(lo, dtype="<u8").view(np.uint8).reshape(n, 8)
-        if hi is not None and k > 32:
-            kbytes[:, 8:] = np.ascontiguousarray(hi, dtype="<u8").view(np.uint8).reshape(n, 8)
     header = {
         "alignment": 8, "canonical": True, "cmdline": list(cmdline or []), "counter_len": 4,
         "format": KDF_FORMAT, "key_len": key_len, "size": int(n),
@@ -187,7 +157,7 @@ def write_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.ndarray], cou
     body += b"\0" * pad
     rec = np.dtype([("k", "u1", (kb,)), ("c", "<u4")])
     data = np.zeros(n, dtype=rec)
-    data["k"] = kbytes[:, :kb]
+    data["k"] = kbytes
     data["c"] = np.asarray(counts, dtype=np.uint32)
     tmp = path + ".tmp"
     with open(tmp, "wb") as fh:
@@ -234,16 +204,13 @@ def jf_positions(columns, key_len: int, lo: np.ndarray, hi: Optional[np.ndarray]
     """Hash position of every key under a header's matrix1: XOR of columns[i] over the set bits key_len - 1 - i of the key
     (bit 0 = the last base's low bit; bits >= 64 live in `hi`).  The bit order is the one under which the reference's
     real Jellyfish file is sorted; for key_len > 64 it is the natural extension and pinned by nothing."""
-    lo = np.ascontiguousarray(lo, dtype=np.uint64)
-    out = np.zeros(len(lo), dtype=np.uint64)
-    one = np.uint64(1)
+    words = keys.from_pair(lo, hi, key_len // 2)
+    out = np.zeros(len(words[0]), dtype=np.uint64)
     for i, col in enumerate(columns):
         b = key_len - 1 - i
         if b < 0:
             break
-        word = lo if b < 64 else np.ascontiguousarray(hi, dtype=np.uint64)
-        bit = (word >> np.uint64(b & 63)) & one
-        out ^= (np.uint64(0) - bit) & np.uint64(col)
+        out ^= (np.uint64(0) - keys.bit(words, b)) & np.uint64(col)
     return out
 
 
@@ -255,7 +222,8 @@ def write_jellyfish_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.nda
     unchanged -- re-writing a real Jellyfish file from its own records and header gives its bytes back."""
     if k > 63:
         raise ValueError(f"k={k}: the Jellyfish binary/sorted writer takes k <= 63 (write_index writes kdf/sorted at any k)")
-    n = len(lo)
+    words = keys.from_pair(lo, hi, k)
+    n = len(words[0])
     key_len = 2 * k
     kb = (key_len + 7) // 8
     if header is not None:
@@ -281,11 +249,8 @@ def write_jellyfish_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.nda
         }
     if int(hd.get("counter_len", 4)) != 4:
         raise ValueError("only 4-byte counters are written")
-    lo = np.ascontiguousarray(lo, dtype=np.uint64)
-    wide = k > 32
-    hi = np.ascontiguousarray(hi, dtype=np.uint64) if wide else None
     pos = jf_positions(matrix_columns, key_len, lo, hi) & np.uint64(size - 1)
-    order = np.lexsort((lo, hi, pos)) if wide else np.lexsort((lo, pos))     # position, then key
+    order = keys.order(words, pos)                          # position, then key
     body = json.dumps(hd).encode()
     body += b"\0" * ((-(9 + len(body))) % 8)
     rec = np.dtype([("k", "u1", (kb,)), ("c", "<u4")])
@@ -297,11 +262,7 @@ def write_jellyfish_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.nda
         for a in range(0, n, step):                         # (records are assembled a slice at a time)
             o = order[a:a + step]
             data = np.zeros(len(o), dtype=rec)
-            kbytes = np.zeros((len(o), 16), dtype=np.uint8)
-            kbytes[:, :8] = lo[o].astype("<u8").view(np.uint8).reshape(len(o), 8)
-            if wide:
-                kbytes[:, 8:] = hi[o].astype("<u8").view(np.uint8).reshape(len(o), 8)
-            data["k"] = kbytes[:, :kb]
+            data["k"] = keys.to_bytes([w[o] for w in words], k)
             data["c"] = np.asarray(counts, dtype=np.uint32)[o]
             data.tofile(fh)
     os.replace(tmp, path)

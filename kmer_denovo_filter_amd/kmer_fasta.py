@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from .reads import _DEC, _ENC
+from . import keys
 
 _CHUNK = 1 << 22
 
@@ -27,35 +27,15 @@ def _sidecar(path: str) -> str:
     return path + ".kdfkeys.npz"
 
 
-def _decode_matrix(lo: np.ndarray, hi: Optional[np.ndarray], k: int) -> np.ndarray:
-    n = len(lo)
-    out = np.empty((n, k), dtype=np.uint8)
-    if k > 64:                                           # long keys: lo = (n, W) rows
-        for i in range(k):
-            sh = 2 * (k - 1 - i)
-            out[:, i] = _DEC[((lo[:, sh >> 6] >> np.uint64(sh & 63)) & np.uint64(3)).astype(np.intp)]
-        return out
-    for i in range(k):
-        sh = 2 * (k - 1 - i)
-        src = (hi >> np.uint64(sh - 64)) if sh >= 64 else (lo >> np.uint64(sh))
-        out[:, i] = _DEC[(src & np.uint64(3)).astype(np.intp)]
-    return out
-
-
 def write_kmer_fasta(path: str, lo: np.ndarray, hi: Optional[np.ndarray], k: int,
                      sidecar: bool = True) -> int:
     """Write keys as ``>{i}\\n{KMER}\\n`` (i from 0).  Returns the number written.  Long k: ``lo`` = (n, W) rows."""
-    lo = np.ascontiguousarray(lo, dtype=np.uint64)
-    n = len(lo)
-    if k > 64:
-        lo = lo.reshape(n, (2 * k + 63) // 64)
-        hi = np.zeros(0, np.uint64)                      # (unused; keeps the sidecar's fields)
-    else:
-        hi = np.zeros(n, np.uint64) if hi is None else np.ascontiguousarray(hi, dtype=np.uint64)
+    words = keys.from_pair(lo, hi, k)
+    n = len(words[0])
     with open(path, "wb") as fh:
         for a in range(0, n, _CHUNK):
             b = min(n, a + _CHUNK)
-            seqs = _decode_matrix(lo[a:b], None if k > 64 else hi[a:b], k)
+            seqs = keys.to_ascii([w[a:b] for w in words], k)
             idx = np.arange(a, b, dtype=np.int64)
             ndig = np.ones(b - a, dtype=np.int64)
             t = idx // 10
@@ -77,6 +57,8 @@ def write_kmer_fasta(path: str, lo: np.ndarray, hi: Optional[np.ndarray], k: int
                 fh.write(line.tobytes())
     if sidecar:
         st = os.stat(path)
+        lo, hi = keys.to_pair(words)
+        hi = np.zeros(0, np.uint64) if hi is None else hi    # (long keys: unused; keeps the sidecar's fields)
         np.savez(_sidecar(path), lo=lo, hi=hi, k=np.int64(k), size=np.int64(st.st_size),
                  mtime_ns=np.int64(st.st_mtime_ns))
     return n
@@ -94,19 +76,14 @@ def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.
             z = np.load(sc)
             st = os.stat(path)
             if int(z["k"]) == k and int(z["size"]) == st.st_size and int(z["mtime_ns"]) == st.st_mtime_ns:
-                return (z["lo"], None) if k > 64 else (z["lo"], z["hi"])
+                return keys.to_pair(keys.from_pair(z["lo"], z["hi"], k))
         except Exception:  # noqa: BLE001  (stale or unreadable sidecar: fall back to the text)
             pass
-    W = (2 * k + 63) // 64
-    empty = (np.zeros((0, W), np.uint64), None) if k > 64 else (np.zeros(0, np.uint64), np.zeros(0, np.uint64))
     data = np.fromfile(path, dtype=np.uint8)
-    if data.size == 0:
-        return empty
-    if data[-1] != 10:
+    if data.size and data[-1] != 10:
         data = np.append(data, np.uint8(10))
     nl = np.flatnonzero(data == 10)
-    starts = np.empty_like(nl)
-    starts[0] = 0
+    starts = np.zeros_like(nl)
     starts[1:] = nl[:-1] + 1
     lens = nl - starts
     # strip one trailing \r if present
@@ -114,53 +91,12 @@ def read_kmer_fasta_keys(path: str, k: int, canonical: bool = True) -> Tuple[np.
     lens = lens - cr
     is_seq = (lens > 0) & (data[starts] != ord(">"))
     s, ln = starts[is_seq], lens[is_seq]
-    if len(s) == 0:
-        return empty
     if not (ln == k).all():
         raise ValueError(f"{path}: sequence line of length != k={k}")
-    codes = _ENC[data[s[:, None] + np.arange(k)[None, :]]]
+    codes = keys.encode(data[s[:, None] + np.arange(k)[None, :]])
     if (codes > 3).any():
         raise ValueError(f"{path}: non-ACGT base in k-mer FASTA")
-    codes = codes.astype(np.uint64)
-
-    def pack(c):
-        plo = np.zeros(len(c), np.uint64)
-        phi = np.zeros(len(c), np.uint64)
-        for i in range(k):
-            sh = 2 * (k - 1 - i)
-            if sh >= 64:
-                phi |= c[:, i] << np.uint64(sh - 64)
-            else:
-                plo |= c[:, i] << np.uint64(sh)
-        return plo, phi
-
-    if k > 64:
-        def pack_rows(c):
-            rows = np.zeros((len(c), W), np.uint64)
-            for i in range(k):
-                sh = 2 * (k - 1 - i)
-                rows[:, sh >> 6] |= c[:, i] << np.uint64(sh & 63)
-            return rows
-
-        f = pack_rows(codes)
-        if not canonical:
-            return f, None
-        r = pack_rows((np.uint64(3) - codes)[:, ::-1])
-        # numeric minimum: the first differing word from the top decides
-        lt = np.zeros(len(f), bool)
-        undecided = np.ones(len(f), bool)
-        for j in range(W - 1, -1, -1):
-            d = undecided & (f[:, j] != r[:, j])
-            lt |= d & (f[:, j] < r[:, j])
-            undecided &= ~d
-        return np.where((lt | undecided)[:, None], f, r), None
-
-    flo, fhi = pack(codes)
-    if not canonical:
-        return flo, fhi
-    rlo, rhi = pack((np.uint64(3) - codes)[:, ::-1])
-    fw = (fhi < rhi) | ((fhi == rhi) & (flo <= rlo))
-    return np.where(fw, flo, rlo), np.where(fw, fhi, rhi)
+    return keys.to_pair(keys.from_codes(codes, canonical))
 
 
 def remove_with_sidecar(path: str):

@@ -14,7 +14,7 @@ from typing import Iterator, List, Optional, Sequence
 
 import numpy as np
 
-from . import _native
+from . import _native, keys
 
 # samtools fasta -F 0xD00: SECONDARY | DUPLICATE | SUPPLEMENTARY
 FLAG_OFF_SAMTOOLS_FASTA = 0xD00
@@ -402,97 +402,18 @@ def fasta_reader(path: str, k: int, max_bases: int = 1 << 26, max_reads: int = 1
     return _Reader(h, max_bases, max_reads, want_meta)
 
 
-# --------------------------------------------------------------------------
-# k-mer string <-> key codec (Jellyfish encoding, A=0 C=1 G=2 T=3, MSB first)
-# --------------------------------------------------------------------------
-
-_ENC = np.full(256, 255, dtype=np.uint8)
-for _i, _c in enumerate(b"ACGT"):
-    _ENC[_c] = _i
-    _ENC[_c + 32] = _i          # lower case
-_DEC = np.frombuffer(b"ACGT", dtype=np.uint8)
-
-
-def _pack_rows(c: np.ndarray, k: int) -> np.ndarray:
-    """2-bit codes [n, k] -> (n, W) uint64 rows of the Jellyfish value, word 0 least significant (long k-mers)."""
-    rows = np.zeros((len(c), (2 * k + 63) // 64), np.uint64)
-    for i in range(k):
-        sh = 2 * (k - 1 - i)
-        rows[:, sh >> 6] |= c[:, i] << np.uint64(sh & 63)
-    return rows
-
-
 def kmers_to_keys(kmers: Sequence[str], k: int, canonical: bool = True):
     """K-mer strings -> (lo, hi) uint64 arrays of (canonical) keys; long k (> 64): ((n, W) rows, None)."""
     n = len(kmers)
-    if k > 64:
-        if n == 0:
-            return np.zeros((0, (2 * k + 63) // 64), np.uint64), None
-        raw = np.frombuffer("".join(kmers).encode(), dtype=np.uint8)
-        if raw.size != n * k:
-            raise ValueError("k-mer of wrong length in input")
-        codes = _ENC[raw].reshape(n, k)
-        if (codes > 3).any():
-            raise ValueError("non-ACGT base in k-mer")
-        codes = codes.astype(np.uint64)
-        f = _pack_rows(codes, k)
-        if not canonical:
-            return f, None
-        r = _pack_rows((np.uint64(3) - codes)[:, ::-1], k)
-        lt = np.zeros(n, bool)
-        undecided = np.ones(n, bool)
-        for j in range(f.shape[1] - 1, -1, -1):           # numeric minimum: the first differing word from the top
-            d = undecided & (f[:, j] != r[:, j])
-            lt |= d & (f[:, j] < r[:, j])
-            undecided &= ~d
-        return np.where((lt | undecided)[:, None], f, r), None
-    lo = np.zeros(n, np.uint64)
-    hi = np.zeros(n, np.uint64)
-    if n == 0:
-        return lo, hi
     raw = np.frombuffer("".join(kmers).encode(), dtype=np.uint8)
     if raw.size != n * k:
         raise ValueError("k-mer of wrong length in input")
-    codes = _ENC[raw].reshape(n, k)
+    codes = keys.encode(raw.reshape(n, k))
     if (codes > 3).any():
         raise ValueError("non-ACGT base in k-mer")
-    codes = codes.astype(np.uint64)
-
-    def pack(c):
-        plo = np.zeros(n, np.uint64)
-        phi = np.zeros(n, np.uint64)
-        for i in range(k):
-            sh = 2 * (k - 1 - i)
-            if sh >= 64:
-                phi |= c[:, i] << np.uint64(sh - 64)
-            else:
-                plo |= c[:, i] << np.uint64(sh)
-        return plo, phi
-
-    flo, fhi = pack(codes)
-    if not canonical:
-        return flo, fhi
-    rlo, rhi = pack((np.uint64(3) - codes)[:, ::-1])
-    fw = (fhi < rhi) | ((fhi == rhi) & (flo <= rlo))
-    return np.where(fw, flo, rlo), np.where(fw, fhi, rhi)
+    return keys.to_pair(keys.from_codes(codes, canonical))
 
 
 def keys_to_kmers(lo: np.ndarray, hi: Optional[np.ndarray], k: int) -> List[str]:
-    n = len(lo)
-    if n == 0:
-        return []
-    lo = np.asarray(lo, np.uint64)
-    out = np.empty((n, k), dtype=np.uint8)
-    if lo.ndim == 2:                                      # long k: (n, W) rows
-        for i in range(k):
-            sh = 2 * (k - 1 - i)
-            out[:, i] = _DEC[((lo[:, sh >> 6] >> np.uint64(sh & 63)) & np.uint64(3)).astype(np.intp)]
-        flat = out.tobytes().decode()
-        return [flat[i * k:(i + 1) * k] for i in range(n)]
-    hi = np.zeros(n, np.uint64) if hi is None else np.asarray(hi, np.uint64)
-    for i in range(k):
-        sh = 2 * (k - 1 - i)
-        src = (hi >> np.uint64(sh - 64)) if sh >= 64 else (lo >> np.uint64(sh))
-        out[:, i] = _DEC[(src & np.uint64(3)).astype(np.intp)]
-    flat = out.tobytes().decode()
-    return [flat[i * k:(i + 1) * k] for i in range(n)]
+    flat = keys.to_ascii(keys.from_pair(lo, hi, k), k).tobytes().decode()
+    return [flat[i * k:(i + 1) * k] for i in range(len(lo))]

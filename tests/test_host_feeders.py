@@ -116,6 +116,20 @@ def test_key_codec_matches_oracle(oracle):
         for s, l, h in zip(ks, lo, hi):
             assert ((int(h) << 64) | int(l)) == oracle.canonical_key(s)
         assert keys_to_kmers(lo, hi, k) == [oracle.canonicalize(s) for s in ks]
+    for k in (65, 101, 201):                            # long k-mers: (n, W) rows, word 0 least significant
+        ks = ["".join(rng.choice(list("ACGT"), size=k)) for _ in range(50)]
+        rows, hi = kmers_to_keys(ks, k)
+        assert hi is None and rows.shape == (50, (2 * k + 63) // 64)
+        for s, row in zip(ks, rows):
+            assert sum(int(x) << (64 * j) for j, x in enumerate(row)) == oracle.kmer_to_int(oracle.canonicalize(s))
+        assert keys_to_kmers(rows, None, k) == [oracle.canonicalize(s) for s in ks]
+    for k in (3, 31, 32, 33, 63, 65, 101, 201):         # canonical=False: the forward value
+        ks = ["".join(rng.choice(list("ACGT"), size=k)) for _ in range(50)]
+        lo, hi = kmers_to_keys(ks, k, canonical=False)
+        rows = lo if hi is None else np.stack([lo, hi], axis=1)
+        for s, row in zip(ks, rows):
+            assert sum(int(x) << (64 * j) for j, x in enumerate(row)) == oracle.kmer_to_int(s)
+        assert keys_to_kmers(lo, hi, k) == ks
     with pytest.raises(ValueError):
         kmers_to_keys(["ACGN"], 4)
 
