@@ -90,8 +90,8 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
 
 /* Count calls in insert mode are DEFERRED: a call partitions its batch (or, for small batches, only appends it to a
  * pending stream) and returns; the table itself is updated when something reads it -- kdf_stats, kdf_query*,
- * kdf_count_ge, kdf_export_*, kdf_scan_*, kdf_add_pairs*, kdf_reserve, kdf_set_option -- or when the pending work
- * fills its budget, so that a sample streamed in hundreds of batches pays the table rewrite of the binned pipeline
+ * kdf_count_ge, kdf_histogram*, kdf_count_stats, kdf_export_*, kdf_scan_*, kdf_add_pairs*, kdf_reserve, kdf_set_option
+ * -- or when the pending work fills its budget, so that a sample streamed in hundreds of batches pays the table rewrite of the binned pipeline
  * once per flush, not once per batch (`jellyfish count` over the whole `samtools fasta` pipe,
  * discovery/pipeline.py:106-172).  kdf_flush applies everything pending now; errors of deferred work (a table that
  * cannot grow ...) surface there or in the call that triggered the flush.  kdf_clear drops pending work. */
@@ -128,7 +128,7 @@ int kdf_flush(kdf_engine *h);
  *            "pending_positions", "ring_bytes", "replayed_buckets", "heavy_buckets" (buckets of skewed flushes that
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_merge_path" (1 LDS bucket
- *            merge, 2 global atomics); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
+ *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
 int kdf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
@@ -227,6 +227,25 @@ int kdf_query_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi,
 /* `jellyfish dump -c -L min_count`: number of entries with count >= min_count
  * (min_count = 0 returns every stored key, counts 0 included). */
 int kdf_count_ge(kdf_engine *h, uint32_t min_count, uint64_t *n_out);
+/* `jellyfish histo -h high`: bins_out[c], 0 <= c <= high, = number of STORED keys whose count is exactly c;
+ * bins_out[high + 1] = number whose count is above `high` (high + 2 uint64 words in all; Jellyfish's default high is
+ * 10000).  bins_out[0] counts the keys stored with count 0 -- a `count --if` filter key never seen, a pair added with
+ * a NULL / zero count -- exactly as kdf_count_ge(h, 0) counts them; empty slots are in no bin.  So
+ * sum(bins) == kdf_count_ge(h, 0) and sum(bins[m ..]) == kdf_count_ge(h, m) for every m <= high + 1.
+ * ONE pass over the 4-byte count array, the same for every key width (the key words are read only for slots with
+ * count 0, and only when the table can hold such keys); the table is not modified and a loaded filter's sieve stays
+ * valid.  Works in insert and in filter mode, on owner tables (hash_shift), and with key_parts set (it then
+ * describes the slice the table holds, like kdf_stats).  high <= 2^24 - 1 (KDF_ERR_INVALID above).
+ * The reference has no call for it: the histogram is what a user reads --min-child-count and --parent-max-count
+ * off.  The _dev form writes the bins to caller-owned HBM (e.g. a torch int64 tensor that is then all-reduced over
+ * the owner ranks); both synchronise the engine's stream.  Under kdf_profile(h, 1) the kernel (kdf_histo_kernel) is
+ * timed with HIP events: stats "histo_us" (summed microseconds) and "histo_passes". */
+int kdf_histogram(kdf_engine *h, uint32_t high, uint64_t *bins_out);
+int kdf_histogram_dev(kdf_engine *h, uint32_t high, void *d_bins_out);
+/* `jellyfish stats`: unique = keys with count 1, distinct = keys with count >= 1, total = the sum of all counts
+ * (counters saturate at 2^32 - 1 and are summed as stored), max_count = the largest stored count (0 for an empty
+ * table).  Any pointer may be NULL.  The same single pass (the histogram kernel with high = 1). */
+int kdf_count_stats(kdf_engine *h, uint64_t *unique, uint64_t *distinct, uint64_t *total, uint64_t *max_count);
 /* ... and the entries themselves, ASCENDING key order (deterministic; the
  * reference does not rely on Jellyfish's hash order).  cap = room in the out
  * arrays; *n_out = entries written.  keys_hi_out / counts_out may be NULL.

@@ -51,6 +51,9 @@ SYMBOLS = [
     ("kdf_query", c_int, [_P, _P, _P, c_uint64, _P]),
     ("kdf_query_dev", c_int, [_P, _P, _P, c_uint64, _P]),
     ("kdf_count_ge", c_int, [_P, c_uint32, POINTER(c_uint64)]),
+    ("kdf_histogram", c_int, [_P, c_uint32, _P]),
+    ("kdf_histogram_dev", c_int, [_P, c_uint32, _P]),
+    ("kdf_count_stats", c_int, [_P, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_export_ge", c_int, [_P, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_export_ge_dev", c_int, [_P, c_uint32, _P, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
     ("kdf_export_parts_dev", c_int, [_P, c_uint32, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -276,3 +276,62 @@ def _build_proband_jf_index(proband_unique_fa, kmer_size, tmpdir, n_proband_uniq
     logger.info("Proband Jellyfish index built (%s, index: %s)", _format_elapsed(time.monotonic() - build_start),
                 _format_file_size(proband_jf))
     return proband_jf
+
+
+def _source_histogram(source, high):
+    """bins uint64[high + 2] of a live KmerEngine or of an index file."""
+    if isinstance(source, (str, os.PathLike)):
+        return jf_io.index_histogram(os.fspath(source), high)
+    return source.histogram(high)
+
+
+def _jellyfish_histo(source, low=1, high=10000, out_path=None):
+    """``jellyfish histo -l low -h high``: ``[(count, number of distinct k-mers with that count), ...]`` for
+    ``low <= count <= high`` plus ``(high + 1, number with a count above high)``, bins that hold nothing left out.
+    ``source`` is a live ``KmerEngine`` (one pass over its count array on the device, ``kdf_histogram``) or the path
+    of an index file (``binary/sorted`` or ``kdf/sorted``, read on the host).  With ``out_path`` the pairs are also
+    written as ``"{count} {number}\\n"`` lines.  The reference never calls ``jellyfish histo`` (its thresholds
+    ``--min-child-count`` / ``--parent-max-count`` are what a user reads off this distribution).
+
+    The NUMBERS are pinned (against ``numpy.bincount`` of the reference's real Jellyfish file and of the oracle's
+    tables); the TEXT layout and Jellyfish's treatment of ``low > 1`` (here: counts below ``low`` are simply left
+    out) are unpinned at the Jellyfish boundary: there is no Jellyfish binary and no histo fixture to compare with."""
+    low, high = int(low), int(high)
+    if low < 0 or high < low:
+        raise ValueError(f"jellyfish histo: need 0 <= low <= high, got low={low} high={high}")
+    try:
+        bins = _source_histogram(source, high)
+    except (KdfError, OSError) as e:
+        raise RuntimeError(f"jellyfish histo failed: {e}") from e
+    rows = [(c, int(bins[c])) for c in range(low, high + 2) if bins[c]]
+    if out_path is not None:
+        tmp = out_path + ".tmp"
+        with open(tmp, "w") as fh:
+            fh.writelines("%d %d\n" % r for r in rows)
+        os.replace(tmp, out_path)
+    return rows
+
+
+def _format_jellyfish_stats(stats):
+    """The four lines ``jellyfish stats`` prints (layout unpinned, see `_jellyfish_histo`)."""
+    return ("Unique:    %d\nDistinct:  %d\nTotal:     %d\nMax_count: %d\n"
+            % (stats["unique"], stats["distinct"], stats["total"], stats["max_count"]))
+
+
+def _jellyfish_stats(source, out_path=None):
+    """``jellyfish stats``: ``{"unique", "distinct", "total", "max_count"}`` of a live ``KmerEngine``
+    (``kdf_count_stats``: the histogram kernel's pass) or of an index file; with ``out_path`` the
+    ``Unique: / Distinct: / Total: / Max_count:`` lines of `_format_jellyfish_stats` are written there."""
+    try:
+        if isinstance(source, (str, os.PathLike)):
+            stats = jf_io.index_stats(os.fspath(source))
+        else:
+            stats = source.count_stats()
+    except (KdfError, OSError) as e:
+        raise RuntimeError(f"jellyfish stats failed: {e}") from e
+    if out_path is not None:
+        tmp = out_path + ".tmp"
+        with open(tmp, "w") as fh:
+            fh.write(_format_jellyfish_stats(stats))
+        os.replace(tmp, out_path)
+    return stats

@@ -15,6 +15,7 @@
 #include "kdf_device.h"
 #include "kdf_binned.h"
 #include "kdf_merge.h"
+#include "kdf_histo.h"
 
 // sorted export lives in kdf_sort.hip (rocPRIM radix sort)
 int kdf_sort_pairs_device(uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt, uint64_t n,
@@ -459,6 +460,7 @@ struct kdf_engine {
     uint64_t windows = 0;
     bool filter_mode = false;
     bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
+    bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
     // grow-only device staging for the host-buffer entry points
     void *stage[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t stage_bytes[4] = {0, 0, 0, 0};
@@ -534,6 +536,8 @@ struct kdf_engine {
     std::vector<std::vector<hipEvent_t>> prof_stage_ev;   // 4 events: a partition (A0, A1, B); 2 events: a flush (C)
     double prof_stage_ms[4] = {0, 0, 0, 0};
     uint64_t prof_stage_passes = 0;
+    double prof_histo_ms = 0.0;                      // kdf_histo_kernel under kdf_profile (stats "histo_us", "histo_passes")
+    uint64_t prof_histo_passes = 0;
     std::string err;
 };
 
@@ -1481,7 +1485,7 @@ int kdf_clear(kdf_engine *h) {
     int rc = ctl_reset(h, false);
     if (rc) return rc;
     h->distinct = 0; h->windows = 0; h->filter_mode = false;
-    h->lazy_empty = true; h->sieve_valid = false;
+    h->lazy_empty = true; h->sieve_valid = false; h->zero_keys = false;
     h->grow_ratio = 0.0;
     if ((rc = pending_drop(h))) return rc;     // what was counted but not yet applied is dropped with the rest
     return KDF_OK;
@@ -1661,7 +1665,7 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
         h->distinct = 0; h->windows = 0; h->lazy_empty = false; h->filter_mode = false;
     } else if ((rc = kdf_clear(h))) return rc;
     if ((rc = materialize(h))) return rc;
-    h->filter_mode = true;
+    h->filter_mode = true; h->zero_keys = true;
     if (n) {
         insert_keys(h, h->t, d_lo, d_hi, nullptr, n, false);
         HIPCHK(h, hipGetLastError());
@@ -1709,7 +1713,7 @@ int kdf_reset_counts(kdf_engine *h) {
     if ((rc = materialize(h))) return rc;
     HIPCHK(h, hipMemsetAsync(h->t.cnt, 0, h->cap * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->ctl->windows, 0, sizeof(h->ctl->windows), h->stream));
-    h->windows = 0;
+    h->windows = 0; h->zero_keys = true;
     return KDF_OK;
 }
 
@@ -1733,6 +1737,7 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
     for (uint32_t s = 0; s < nseg; ++s) { total += n[s]; nmax = std::max(nmax, n[s]); if (n[s] && !d_cnt[s]) counts = false; }
     if (total == 0) return KDF_OK;
     h->sieve_valid = false;                          // keys may join the table that the sieve has not seen
+    h->zero_keys = true;                             // ... with a count of 0 (NULL counts, a 0 in the array)
     int rc;
     if ((rc = pending_flush(h))) return rc;
     if ((rc = ctl_sync(h, nullptr))) return rc;
@@ -1843,6 +1848,7 @@ int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_
     int rc;
     if ((rc = pending_flush(h))) return rc;
     if ((rc = materialize(h))) return rc;
+    h->zero_keys = true;
     by_width(h, [&](auto KWc) {
         constexpr int KW = decltype(KWc)::value;
         hipLaunchKernelGGL(kdf_set_counts_kernel<KW>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_keys_lo,
@@ -2046,6 +2052,64 @@ int kdf_count_ge(kdf_engine *h, uint32_t min_count, uint64_t *n_out) {
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_count_ge: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
     return export_pass(h, min_count, false, nullptr, nullptr, nullptr, 0, n_out);
+}
+
+// `jellyfish histo` / `jellyfish stats` on the live table (kdf_histo.h): ONE pass over the count array fills the bins
+// (device, high + 2 words) and {sum of counts, largest count} in d_out4[0..1]; h_out4[0..1] holds them on return.
+static int histo_pass(kdf_engine *h, uint32_t high, unsigned long long *d_bins, const char *fn) {
+    if (high > KH_MAX_HIGH) return fail(h, KDF_ERR_INVALID, "%s: high = %u is above the limit of %u", fn, high, KH_MAX_HIGH);
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    { int rc0 = materialize(h); if (rc0) return rc0; }
+    HIPCHK(h, hipMemsetAsync(d_bins, 0, ((size_t)high + 2) * 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_out4, 0, 2 * sizeof(unsigned long long), h->stream));
+    // the word that tells an empty slot from a key with count 0, read only when the table can hold such keys
+    const uint64_t *occ = !h->zero_keys ? nullptr : h->kw == 1 ? h->t.lo : h->t.hi + ((uint64_t)(h->kw - 2) << h->t.log2cap);
+    const uint64_t wgs = (h->cap / 4 + (uint64_t)KH_THREADS * KH_UNROLL - 1) / ((uint64_t)KH_THREADS * KH_UNROLL);
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)h->n_cu * KH_WG_PER_CU));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (h->prof) { HIPCHK(h, hipEventCreate(&ev[0])); HIPCHK(h, hipEventCreate(&ev[1])); HIPCHK(h, hipEventRecord(ev[0], h->stream)); }
+    hipLaunchKernelGGL(kdf_histo_kernel, dim3(grid), dim3(KH_THREADS), 0, h->stream, h->t.cnt, occ, h->cap, high, d_bins, h->d_out4);
+    hipError_t le = hipGetLastError();
+    if (h->prof && le == hipSuccess) le = hipEventRecord(ev[1], h->stream);
+    if (le == hipSuccess) le = hipMemcpyAsync(h->h_out4, h->d_out4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+    if (le == hipSuccess) le = hipStreamSynchronize(h->stream);
+    if (h->prof) {
+        float ms = 0.f;
+        if (le == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { h->prof_histo_ms += ms; h->prof_histo_passes++; }
+        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
+    }
+    HIPCHK(h, le);
+    return KDF_OK;
+}
+
+int kdf_histogram_dev(kdf_engine *h, uint32_t high, void *d_bins_out) {
+    if (!h || !d_bins_out) return fail(h, KDF_ERR_INVALID, "kdf_histogram_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    return histo_pass(h, high, (unsigned long long *)d_bins_out, "kdf_histogram_dev");
+}
+
+int kdf_histogram(kdf_engine *h, uint32_t high, uint64_t *bins_out) {
+    if (!h || !bins_out) return fail(h, KDF_ERR_INVALID, "kdf_histogram: NULL pointer");
+    if (high > KH_MAX_HIGH) return fail(h, KDF_ERR_INVALID, "kdf_histogram: high = %u is above the limit of %u", high, KH_MAX_HIGH);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes = ((size_t)high + 2) * 8;
+    int rc = stage_reserve(h, 1, bytes);
+    if (rc) return rc;
+    if ((rc = histo_pass(h, high, (unsigned long long *)h->stage[1], "kdf_histogram"))) return rc;
+    HIPCHK(h, hipMemcpy(bins_out, h->stage[1], bytes, hipMemcpyDeviceToHost));
+    return KDF_OK;
+}
+
+int kdf_count_stats(kdf_engine *h, uint64_t *unique, uint64_t *distinct, uint64_t *total, uint64_t *max_count) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    uint64_t bins[3] = {0, 0, 0};                      // count 0, count 1, above 1: the same kernel with high = 1
+    int rc = kdf_histogram(h, 1, bins);
+    if (rc) return rc;
+    if (unique) *unique = bins[1];
+    if (distinct) *distinct = bins[1] + bins[2];
+    if (total) *total = h->h_out4[0];
+    if (max_count) *max_count = h->h_out4[1];
+    return KDF_OK;
 }
 
 // The entries with count >= min_count into device buffers (the (lo, hi) arrays of k <= 63 with hi NULL for k <= 32, the
@@ -2310,6 +2374,7 @@ int kdf_profile(kdf_engine *h, int enable) {
     h->prof_ms = 0.0; h->prof_launches = 0; h->prof_positions = 0;
     for (double &m : h->prof_stage_ms) m = 0.0;
     h->prof_stage_passes = 0;
+    h->prof_histo_ms = 0.0; h->prof_histo_passes = 0;
     return KDF_OK;
 }
 
@@ -2389,6 +2454,8 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     const std::string n(name);
     if (n == "binned_passes") *value = (int64_t)h->stat_binned_passes;
     else if (n == "replayed_buckets") *value = (int64_t)h->stat_replayed_buckets;
+    else if (n == "histo_us") *value = (int64_t)(h->prof_histo_ms * 1000.0 + 0.5);
+    else if (n == "histo_passes") *value = (int64_t)h->prof_histo_passes;
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     else if (n == "pending_passes") *value = (int64_t)h->n_pass;
     else if (n == "pending_positions") *value = (int64_t)(h->pend_positions + h->l1_tiles * KDF_TILE);

@@ -69,6 +69,8 @@ class TableOps:
     def query(self, lo: torch.Tensor, hi: Optional[torch.Tensor]) -> torch.Tensor: raise NotImplementedError
     def count_ge(self, min_count: int) -> int: raise NotImplementedError
     def stats(self) -> Tuple[int, int, int]: raise NotImplementedError
+    def histogram(self, high: int) -> torch.Tensor: raise NotImplementedError   # int64[high + 2] on self.device
+    def count_stats(self) -> dict: raise NotImplementedError
 
     def add_pairs_segments(self, segments):
         """Sum the segments [(lo, hi, cnt), ...] received from the source ranks (a table that can merge them
@@ -187,6 +189,16 @@ class EngineOps(TableOps):
 
     def stats(self):
         return self.e.stats()
+
+    def histogram(self, high):
+        """int64[high + 2] in HBM, written by ``kdf_histogram_dev`` (bin high + 1: counts above ``high``)."""
+        bins = torch.empty(int(high) + 2, dtype=torch.int64, device=self.device)
+        self._sync()
+        self.e.histogram_dev(int(high), bins.data_ptr())           # synchronises the engine's stream
+        return bins
+
+    def count_stats(self):
+        return self.e.count_stats()
 
 
 def _u32(t: torch.Tensor) -> torch.Tensor:
@@ -361,6 +373,31 @@ class OwnerPartitionedCount:
         if self.world > 1:
             dist.all_reduce(n, op=dist.ReduceOp.SUM, group=self.group)
         return int(n.item())
+
+    def histogram(self, high: int = 10000) -> torch.Tensor:
+        """Global count histogram (`jellyfish histo` of the merged table) as int64[high + 2]; call after
+        ``exchange()``: every key then lives on exactly one owner, so the global bins are ONE all-reduce(sum) of
+        the owners' bins.  With one rank it is the local table's."""
+        bins = self.owner.histogram(int(high))
+        if self.world > 1:
+            red = bins.cpu() if self.host else bins
+            dist.all_reduce(red, op=dist.ReduceOp.SUM, group=self.group)
+            bins = red.to(bins.device) if self.host else red
+        return bins
+
+    def count_stats(self) -> dict:
+        """Global `jellyfish stats` after ``exchange()``: unique / distinct / total by all-reduce(sum) of the
+        owners' numbers, max_count by all-reduce(max)."""
+        st = self.owner.count_stats()
+        if self.world > 1:
+            cdev = "cpu" if self.host else self.device
+            sums = torch.tensor([st["unique"], st["distinct"], st["total"]], dtype=torch.int64, device=cdev)
+            mx = torch.tensor([st["max_count"]], dtype=torch.int64, device=cdev)
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=self.group)
+            u, d, t = (int(x) for x in sums.tolist())
+            st = {"unique": u, "distinct": d, "total": t, "max_count": int(mx.item())}
+        return st
 
     def count_and_merge(self, packed, invalid, n_bases: int, min_count: int = 1) -> int:
         """clear -> count the local shard -> exchange -> global number of keys

@@ -7,6 +7,8 @@ shells out to ("External op" table):
     load_filter(keys)        --if filter.fa
     count_filtered(stream)   jellyfish count -m k -C --if ...
     export_ge(n)             jellyfish dump -c -L n             (ascending keys)
+    histogram(high)          jellyfish histo -h high
+    count_stats()            jellyfish stats
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
 
@@ -272,6 +274,31 @@ class KmerEngine:
         n = c_uint64(0)
         self._ck(self._lib.kdf_count_ge(self._h, int(min_count), byref(n)))
         return n.value
+
+    HISTO_MAX_HIGH = (1 << 24) - 1   # kdf_histogram's limit on `high`
+
+    def histogram(self, high: int = 10000) -> np.ndarray:
+        """`jellyfish histo -h high`: uint64[high + 2]; bins[c] = stored keys with count exactly c (bins[0]: keys
+        stored with count 0, as count_ge(0) counts them), bins[high + 1] = keys with a count above ``high``."""
+        if not 0 <= int(high) <= self.HISTO_MAX_HIGH:
+            raise ValueError(f"high={high} outside 0..{self.HISTO_MAX_HIGH}")
+        bins = np.zeros(int(high) + 2, np.uint64)
+        self._ck(self._lib.kdf_histogram(self._h, int(high), _vp(bins)))
+        return bins
+
+    def histogram_dev(self, high: int, d_bins: int):
+        """The same into caller-owned HBM: ``d_bins`` is a raw device pointer to high + 2 64-bit words."""
+        if not 0 <= int(high) <= self.HISTO_MAX_HIGH:
+            raise ValueError(f"high={high} outside 0..{self.HISTO_MAX_HIGH}")
+        self._ck(self._lib.kdf_histogram_dev(self._h, int(high), c_void_p(d_bins)))
+        return self
+
+    def count_stats(self) -> dict:
+        """`jellyfish stats`: {"unique": keys with count 1, "distinct": keys with count >= 1, "total": sum of all
+        counts, "max_count": largest count (0 for an empty table)}."""
+        u, d, t, m = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0)
+        self._ck(self._lib.kdf_count_stats(self._h, byref(u), byref(d), byref(t), byref(m)))
+        return {"unique": u.value, "distinct": d.value, "total": t.value, "max_count": m.value}
 
     def export_ge(self, min_count: int = 0):
         """(lo, hi, counts) of entries with count >= min_count, ascending key order

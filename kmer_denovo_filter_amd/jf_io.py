@@ -140,6 +140,34 @@ def read_index(path: str, expect_k: Optional[int] = None):
     return (k, *keys.to_pair(keys.from_pair(lo, hi, k)), counts)
 
 
+def index_histogram(path: str, high: int = 10000, expect_k: Optional[int] = None,
+                    chunk_records: int = 1 << 24) -> np.ndarray:
+    """`jellyfish histo -h high file.jf` of an index FILE (``binary/sorted`` or ``kdf/sorted``, any k), on the host:
+    uint64[high + 2], bins[c] = records whose count is exactly c, bins[high + 1] = records with a count above
+    ``high`` -- the layout of ``KmerEngine.histogram`` (bins[0]: records stored with count 0).  Memory-mapped and
+    decoded block by block through `iter_index`; an index is already a compact (key, count) list, so no device."""
+    high = int(high)
+    if high < 0:
+        raise ValueError(f"high={high} must be >= 0")
+    bins = np.zeros(high + 2, np.uint64)
+    for _, _, _, counts in iter_index(path, expect_k, chunk_records):
+        c = np.minimum(counts, np.uint32(min(high + 1, 0xFFFFFFFF))).astype(np.int64)
+        bins += np.bincount(c, minlength=high + 2)[:high + 2].astype(np.uint64)
+    return bins
+
+
+def index_stats(path: str, expect_k: Optional[int] = None, chunk_records: int = 1 << 24) -> dict:
+    """`jellyfish stats file.jf`: {"unique": records with count 1, "distinct": records with count >= 1, "total":
+    sum of all counts (as stored: saturated at 2^32 - 1), "max_count": largest count, 0 for an empty index}."""
+    unique = distinct = total = mx = 0
+    for _, _, _, counts in iter_index(path, expect_k, chunk_records):
+        unique += int(np.count_nonzero(counts == 1))
+        distinct += int(np.count_nonzero(counts))
+        total += int(counts.sum(dtype=np.uint64))
+        mx = max(mx, int(counts.max()) if len(counts) else 0)
+    return {"unique": unique, "distinct": distinct, "total": total, "max_count": mx}
+
+
 def write_index(path: str, k: int, lo: np.ndarray, hi: Optional[np.ndarray], counts: np.ndarray,
                 cmdline=None) -> str:
     """Write a ``kdf/sorted`` index (keys must already be in ascending order; long k: ``lo`` = (n, W) rows)."""
