@@ -99,7 +99,8 @@ int kdf_flush(kdf_engine *h);
 
 /* Tuning knobs and counters (tests force either kernel path through these):
  *   options  "force_path" 0 auto / 1 direct global-table kernels / 2 binned LDS-bucket pipeline (every count call
- *            partitions its batch at once) / 4 count --if through the sieve only; "binned_min_positions" (pending
+ *            partitions its batch at once) / 4 count --if through the sieve only -- any other value is refused with
+ *            KDF_ERR_INVALID and the option keeps its value; "binned_min_positions" (pending
  *            positions below which a flush uses the direct kernels); "key_parts" / "key_part" (count only
  *            the windows whose key lies in slice key_part of key_parts of the key space --
  *            ranges of the LOW 16 hash bits, so a slice spreads over the whole table -- so that

@@ -2420,6 +2420,8 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
         if (bb != h->t.bucket_bits) { int rc = table_rehash(h, h->t.log2cap); if (rc) return rc; }     // same slots, other buckets
     }
     else if (n == "force_path") {
+        if (value != 0 && value != 1 && value != 2 && value != 4)
+            return fail(h, KDF_ERR_INVALID, "force_path %lld: must be 0 (auto), 1 (direct), 2 (binned) or 4 (sieve, count --if only)", (long long)value);
         if (is_long(h) && (value == 2 || value == 4))
             return fail(h, KDF_ERR_INVALID, "force_path %lld: k=%d counts through the direct kernels only (no binned pipeline or sieve for k > 63)", (long long)value, h->k);
         h->opt_force_path = (int)value;

@@ -1,8 +1,10 @@
 """The BASELINE.json configurations at FULL size on the GPU.  The oracle cannot follow at these
 sizes inside a test, so the checks are: the totals the 16-core oracle produced for the exact bench workload
-(BENCH_r01.json cpu_baseline: it counted the whole batch), bit-for-bit agreement of the independent GPU paths
-(direct global-table kernels / binned LDS-bucket pipeline / super-k-mer pipeline), conservation (sum of counts ==
-valid windows), and a slice of the same reads against the oracle."""
+(BENCH_r01.json cpu_baseline: it counted the whole batch), bit-for-bit agreement of the GPU paths (binned LDS-bucket
+pipeline forced / the auto path with its deferred flush / direct global-table kernels, each with the kdf_get_stat
+witness that it ran), conservation (sum of counts == valid windows), and a slice of the same reads against the oracle.
+The per-key truth of the same workloads at full size (tests/stream_truth.py) is compared in
+tests/test_gpu_full_size_truth.py (cases a, b); the parent-filter chain below is compared with it here."""
 import numpy as np
 import pytest
 
@@ -31,10 +33,19 @@ def test_config1_exact_bench_workload_all_paths():
     ds = synth_stream(10_000_000, 150, 100_000_000, seed=20260417, device="cuda:0", genome_seed=20260417)
     torch.cuda.synchronize()
     ref = None
-    for path in (2, 3, 1):                                   # binned, super-k-mer, direct
+    for path in (2, 0, 1):                                   # binned, auto (deferred: ended by flush()), direct
         with KmerEngine(31, capacity_hint=1 << 28) as e:
             e.set_option("force_path", path)
             e.count_dev(ds.packed.data_ptr(), ds.invalid.data_ptr(), ds.n_bases)
+            # the witness that this path ran: one partition pass waiting for its flush, or the direct kernels and no pass
+            if path == 1:
+                assert e.last_count_path() == "direct"
+                assert (e.get_stat("binned_passes"), e.get_stat("pending_passes"), e.get_stat("flushes")) == (0, 0, 0)
+            else:
+                assert e.last_count_path() == "binned"
+                assert (e.get_stat("binned_passes"), e.get_stat("pending_passes"), e.get_stat("flushes")) == (1, 1, 0)
+                e.flush()
+                assert (e.get_stat("binned_passes"), e.get_stat("pending_passes"), e.get_stat("flushes")) == (1, 0, 1)
             cap, distinct, windows = e.stats()
             assert (windows, distinct, e.count_ge(3)) == (BENCH_WINDOWS, BENCH_DISTINCT, BENCH_GE3), path
             lo, _, cnt = _sorted_dump(e, 0, distinct)
@@ -65,6 +76,8 @@ def test_config4_k63_full_size_and_oracle_slice(oracle):
         with KmerEngine(63, capacity_hint=1 << 28) as e:
             e.set_option("force_path", path)
             e.count_dev(ds.packed.data_ptr(), ds.invalid.data_ptr(), ds.n_bases)
+            assert e.last_count_path() == ("binned" if path == 2 else "direct")
+            assert e.get_stat("binned_passes") == (1 if path == 2 else 0)
             cap, distinct, windows = e.stats()
             lo, hi, cnt = _sorted_dump(e, 0, distinct)
             assert int((cnt.to(torch.int64) & 0xFFFFFFFF).sum().item()) == windows
@@ -87,14 +100,14 @@ def test_config4_k63_full_size_and_oracle_slice(oracle):
 
 def test_config2_parent_filter_chain_full_64mbp():
     """configs[2] substitute at FULL size (64 Mbp, 30x trio): the chain's sets shrink monotonically, the planted
-    SNVs survive, and the sieve path's per-key parent counts equal the binned path's and the direct path's."""
-    import os
-    import sys
+    SNVs survive, every set of the chain is the set computed from the truths of the four streams
+    (tests/stream_truth.py), and the sieve path's per-key parent counts of the survivors equal the binned path's and
+    the direct path's (all zero: test_gpu_full_size_truth.py case e counts the CANDIDATES, whose counts are not)."""
     import torch
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "benchmarks"))
-    import parent_filter
+    import test_gpu_full_size_truth as full
     from kmer_denovo_filter_amd import KmerEngine, devkeys
-    res, (lo, hi), streams = parent_filter.run(64_000_000, 30, 31, 20260418, "cuda:0")
+    res, (lo, hi), streams, truths = full.WORKLOADS.get("parent filter", full._parent_filter)
+    full.assert_chain_equals_truth(res, (lo, hi), truths)
     assert res["candidates"] > res["non_ref"] > res["after_mother"] > res["after_father"] == res["proband_unique"] > 0
     # 64 000 planted SNVs x up to 31 k-mers each, seen >= 3 times at 30x: the bulk of the non-reference set
     assert 1_500_000 < res["proband_unique"] < 64_000 * 31

@@ -107,7 +107,7 @@ def test_empty_inputs(oracle):
 
 def test_errors_are_loud():
     from kmer_denovo_filter_amd import KmerEngine, ReadStream
-    from kmer_denovo_filter_amd._native import KdfError
+    from kmer_denovo_filter_amd._native import KDF_ERR_INVALID, KdfError
     with pytest.raises(ValueError):
         KmerEngine(64)
     with KmerEngine(31) as e:
@@ -116,6 +116,14 @@ def test_errors_are_loud():
         e.load_filter(np.array([5], np.uint64))
         with pytest.raises(KdfError):
             e.count(ReadStream.from_strings(["ACGT" * 20]))            # filter mode: insert refused
+    with KmerEngine(31) as e:
+        e.set_option("force_path", 2)
+        for v in (3, 5, -1):                                           # no such pipeline: refused, the earlier choice stays
+            with pytest.raises(KdfError, match="force_path") as err:
+                e.set_option("force_path", v)
+            assert err.value.code == KDF_ERR_INVALID
+        e.count(ReadStream.from_strings(["ACGT" * 20]))
+        assert e.last_count_path() == "binned"
 
 
 # --------------------------------------------------------------------------
