@@ -44,6 +44,17 @@
  *   records).  A window [i, i+k) is counted iff none of its k positions is
  *   invalid.  This keeps the kernels free of per-read bookkeeping and load
  *   balanced for ragged reads.
+ *
+ *   What lies at and past n_bases (every entry point that takes a stream, host or device, every k, every path):
+ *   1. a position >= n_bases is INVALID whatever the caller's buffers hold there -- the bits of the last mask word
+ *      past n_bases % 64, the 2 padding mask words and 4 padding packed words that kdf_stream_words(n_bases) adds,
+ *      the bases of the last packed words past n_bases.  A producer may pad with zeros or hand over a prefix of a
+ *      longer stream (any n_bases, also one that cuts a read): no window reaches past n_bases.
+ *   2. the device forms read at most the kdf_stream_words(n_bases) words of each buffer, so the buffers need be no
+ *      longer than that; the host forms read ceil(n_bases / 32) packed and ceil(n_bases / 64) mask words.  The engine
+ *      never writes to a caller's stream.
+ *   3. kdf_scan_reads*: in hit words 0 .. ceil(n_bases / 64) - 1 every bit at a position > n_bases - k is 0.
+ *   4. kdf_stats' `windows` counts only windows that lie wholly below n_bases.
  */
 #ifndef KDF_H
 #define KDF_H
@@ -128,7 +139,7 @@ int kdf_flush(kdf_engine *h);
  *   stats    "binned_passes" (partition passes), "flushes" (kernel C launches), "pending_passes",
  *            "pending_positions", "ring_bytes", "replayed_buckets", "heavy_buckets" (buckets of skewed flushes that
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
- *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_merge_path" (1 LDS bucket
+ *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
@@ -154,8 +165,10 @@ int kdf_profile_stages(kdf_engine *h, double *stage_ms4, uint64_t *passes);
  * _ensure_ref_jf (core/jellyfish_wrappers.py:313-326).  Host buffers. */
 int kdf_count_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid,
                     uint64_t n_bases);
-/* Same with the stream already resident in HBM (device pointers, padded as
- * kdf_stream_words() says). */
+/* Same with the stream already resident in HBM (device pointers to buffers of the kdf_stream_words(n_bases) sizes).
+ * The words at and past n_bases may hold anything ("Read streams", points 1-2): the last k - 1 positions before
+ * n_bases start no window, on every path (pending stream, direct, binned, key_parts, long keys), so a batch small
+ * enough to wait in the pending stream and one that is partitioned where it lies give the same table. */
 int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid,
                         uint64_t n_bases);
 
@@ -210,6 +223,8 @@ int kdf_reset_counts(kdf_engine *h);
  * (discovery/pipeline.py:322-459). */
 int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed,
                              const uint64_t *invalid, uint64_t n_bases);
+/* (device form: buffers of the kdf_stream_words(n_bases) sizes whose words at and past n_bases may hold anything,
+ * "Read streams" points 1-2 -- through the sieve, the binned pipeline and the direct kernel alike) */
 int kdf_count_reads_filtered_dev(kdf_engine *h, const void *d_packed,
                                  const void *d_invalid, uint64_t n_bases);
 
@@ -299,7 +314,10 @@ int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_
  * kdf_pack_reads() returns them) distinct_out[r] = number of DISTINCT canonical
  * k-mers hit in read r (len(unique_in_read), core/bam_scanner.py:435-442).
  * Replaces the inner loop of _scan_contig_for_hits (core/bam_scanner.py:396-474)
- * and JellyfishKmerQuery.scan_read (kmer_utils.py:209-238). */
+ * and JellyfishKmerQuery.scan_read (kmer_utils.py:209-238).
+ * The device form writes hit words 0 .. ceil(n_bases / 64) - 1; a bit at a position > n_bases - k is never set,
+ * whatever the stream's words hold at and past n_bases ("Read streams" points 1-3).  Stat "last_scan_path": the
+ * kernel the last scan ran through (0 direct, 3 sieve). */
 int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid,
                    uint64_t n_bases, const int64_t *read_offsets, int64_t n_reads,
                    uint64_t *hit_bits, uint32_t *distinct_out);
@@ -309,7 +327,9 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
 /* ------------------------------------------------------- host utilities -- */
 
 /* Words a stream of n_bases needs (padding included): the packed array must
- * hold *packed_words uint64, the invalid / hit arrays *mask_words uint64. */
+ * hold *packed_words uint64 (2 * ceil(n_bases / 64) + 4), the invalid / hit arrays *mask_words uint64
+ * (ceil(n_bases / 64) + 2).  This is a SIZE: the kernels may read every one of those words, and none beyond; what the
+ * words at and past n_bases hold does not matter ("Read streams" points 1-2). */
 void kdf_stream_words(uint64_t n_bases, uint64_t *packed_words, uint64_t *mask_words);
 
 /* Pack ASCII records (A/C/G/T any case; everything else invalid) into a stream

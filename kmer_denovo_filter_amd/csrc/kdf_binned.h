@@ -261,9 +261,10 @@ struct KbWindows {
     uint64_t g0, g1;      // narrow keys: the span with its 2-bit groups reversed, pre-shifted (forward k-mers)
     uint64_t gw[3], hmask;   // wide keys: the same for the 192-bit span, and the mask of the key's high word
     int p0_;
+    uint32_t rem_;        // positions from this tile's first to the end of the stream, capped at 128 (kdf_mask_past_end)
     bool in_range;
     __device__ __forceinline__ void issue(const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid,
-                                          uint64_t tile, uint64_t n_tiles, int part, int k_) {
+                                          uint64_t tile, uint64_t n_tiles, uint64_t n_end, int part, int k_) {
         k = k_; p0_ = part * WPT;
         kmask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
         in_range = tile < n_tiles;
@@ -273,6 +274,7 @@ struct KbWindows {
         const uint64_t t = in_range ? tile : n_tiles - 1;
         const uint64_t *src = packed + t * 2 + (p0_ >> 5);
         m0 = invalid[t]; m1 = invalid[t + 1];
+        rem_ = (uint32_t)min(n_end - t * KDF_TILE, (uint64_t)(2 * KDF_TILE));      // (t < n_tiles <= ceil(n_end / 64))
 #pragma unroll
         for (int i = 0; i <= NE; ++i) raw[i] = src[i];       // within the padded tail (kdf_stream_words)
     }
@@ -280,6 +282,7 @@ struct KbWindows {
         const int sh = (p0_ & 31) * 2;
 #pragma unroll
         for (int i = 0; i < NE; ++i) e[i] = kdf_funnel(raw[i], raw[i + 1], sh);
+        kdf_mask_past_end(rem_, m0, m1);
         const uint64_t v = kdf_valid_windows(m0, m1, k);
         valid = in_range ? (uint32_t)((v >> p0_) & ((1ull << WPT) - 1)) : 0u;
         if constexpr (KW == 1) {
@@ -305,8 +308,8 @@ struct KbWindows {
         }
     }
     __device__ __forceinline__ void load(const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid,
-                                         uint64_t tile, uint64_t n_tiles, int part, int k_) {
-        issue(packed, invalid, tile, n_tiles, part, k_);
+                                         uint64_t tile, uint64_t n_tiles, uint64_t n_end, int part, int k_) {
+        issue(packed, invalid, tile, n_tiles, n_end, part, k_);
         finish();
     }
     __device__ __forceinline__ void key(int u, uint64_t &lo, uint64_t &hi) const {   // u: compile-time
@@ -343,7 +346,7 @@ __device__ __forceinline__ void kb_lds_barrier() {
 // tmp[slab * SLAB ...] and the slab's offset row to off[slab][0 .. nbins] (off[slab][nbins] = its valid windows).
 template <int KW, bool SLICED>
 __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
-    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, int k,
+    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_end, int k,
     KbPlan plan, KbScratch s, uint32_t slabs_per_wg)
 {
     constexpr int WPT = KbCfg<KW>::WPT, TPT = 64 / WPT, SLAB = KbCfg<KW>::SLAB, NT = KB_A_THREADS;
@@ -365,7 +368,7 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
     const uint64_t slab0 = (uint64_t)blockIdx.x * slabs_per_wg;
     if (slab0 * TILES_PER_SLAB >= n_tiles) return;                     // uniform
     KbWindows<KW> win;
-    win.load(packed, invalid, slab0 * TILES_PER_SLAB + threadIdx.x / TPT, n_tiles, threadIdx.x % TPT, k);
+    win.load(packed, invalid, slab0 * TILES_PER_SLAB + threadIdx.x / TPT, n_tiles, n_end, threadIdx.x % TPT, k);
     KB_T_INIT;
     for (uint32_t sl = 0; sl < slabs_per_wg; ++sl) {
         const uint64_t slab = slab0 + sl;
@@ -376,7 +379,7 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
             // prefetch of the next slab's words: loads only; (tile >= n_tiles handles "no next slab")
             const bool more = sl + 1 < slabs_per_wg;
             nxt.issue(packed, invalid, more ? (slab + 1) * TILES_PER_SLAB + threadIdx.x / TPT : n_tiles,
-                      n_tiles, threadIdx.x % TPT, k);
+                      n_tiles, n_end, threadIdx.x % TPT, k);
         }
         // Branch-free ranking: invalid windows (~4 %) go to a dummy counter
         // hist[DUMMY], so the WPT returning LDS atomics issue back to back with

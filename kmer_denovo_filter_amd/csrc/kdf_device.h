@@ -260,6 +260,16 @@ __device__ __forceinline__ uint64_t kdf_valid_windows(uint64_t m0, uint64_t m1, 
     return a0;
 }
 
+// Positions at or past the end of the caller's stream are invalid WHATEVER its buffers hold there (include/kdf.h, "Read
+// streams"): the tail of the last mask word, the padding words.  rem = stream end - first position of the tile, >= 1;
+// only the last two tiles of a stream have rem < 128, so every other tile pays one compare.
+__device__ __forceinline__ void kdf_mask_past_end(uint64_t rem, uint64_t &m0, uint64_t &m1) {
+    if (rem < 2 * KDF_TILE) {
+        if (rem < KDF_TILE) m0 |= ~0ull << rem;
+        m1 = rem <= KDF_TILE ? ~0ull : (m1 | (~0ull << (rem - KDF_TILE)));
+    }
+}
+
 template <int KW> struct KdfKey;
 template <> struct KdfKey<1> { uint64_t lo; };
 template <> struct KdfKey<2> { uint64_t lo, hi; };

@@ -34,7 +34,7 @@ enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2 };
 template <int KW, int MODE>
 __global__ __launch_bounds__(256) void kdf_stream_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid,
-    uint64_t tile0, uint64_t n_tiles, int k, KdfTable t, KdfCtl *ctl,
+    uint64_t tile0, uint64_t n_tiles, uint64_t n_bases, int k, KdfTable t, KdfCtl *ctl,
     uint64_t *__restrict__ hit_bits)
 {
     const uint64_t tile = tile0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -42,7 +42,8 @@ __global__ __launch_bounds__(256) void kdf_stream_kernel(
     uint32_t claimed = 0, nwin = 0;
     bool full = false;
     if (active) {
-        const uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
+        uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
+        kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
         uint64_t valid = kdf_valid_windows(m0, m1, k);
         nwin = __popcll(valid);
         const bool sliced = MODE == MODE_INSERT && t.key_parts > 1;       // count only this key-space slice (KdfTable::key_parts)
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(256) void kdf_sieve_from_table_kernel(KdfTable t, u
 // window's bit in hit_bits (zeroed by the host first); nothing is counted.
 template <int KW, bool IN_LDS = false, bool SCAN = false>
 __global__ __launch_bounds__(KB_THREADS) void kdf_sieve_count_kernel(
-    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, int k,
+    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
     KdfTable t, KdfCtl *ctl, KdfSieve sv, uint32_t slabs_per_wg, unsigned long long *__restrict__ hit_bits = nullptr)
 {
     constexpr int WPT = KbCfg<KW>::WPT, TPT = 64 / WPT;
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(KB_THREADS) void kdf_sieve_count_kernel(
         if ((slab0 + sl) * TILES_PER_SLAB >= n_tiles) break;
         const uint64_t tile = (slab0 + sl) * TILES_PER_SLAB + threadIdx.x / TPT;
         KbWindows<KW> win;
-        win.load(packed, invalid, tile, n_tiles, threadIdx.x % TPT, k);
+        win.load(packed, invalid, tile, n_tiles, n_bases, threadIdx.x % TPT, k);
         nwin += __popc(win.valid);
         // eight sieve words in flight per lane; only the word and 12 hash bits are kept per window (the key of a
         // survivor is taken again from the registers that hold the stream), so eight waves fit a SIMD
@@ -521,6 +522,7 @@ struct kdf_engine {
     bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
     bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
     int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve
+    int last_scan_path = 0;                          // kernel of the last kdf_scan_reads_dev: 0 direct, 3 sieve
     uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
     uint64_t sieve_words = 0, sieve_alloc = 0;
     bool sieve_valid = false;
@@ -743,7 +745,7 @@ static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_
         constexpr int W = decltype(Wc)::value;
         if constexpr (W <= 2)
             hipLaunchKernelGGL((kdf_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
-                               d_packed, d_invalid, tile0, n_tiles, h->k, h->t, h->ctl, d_hits);
+                               d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
         else              // (n_bases: the long kernel clamps its loads to the buffers kdf_stream_words(n_bases) sizes)
             hipLaunchKernelGGL((kdf_long_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
                                d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
@@ -931,7 +933,7 @@ static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, ui
 
 // ONE partition pass (A, P, B) of a device-resident stream of at most opt_binned_max_positions positions into the ring
 template <int KW>
-static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, bool filtered) {
+static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t n_end, bool filtered) {
     constexpr int WPT = KbCfg<KW>::WPT, TPT = 64 / WPT, CHUNK = KbCfg<KW>::CHUNK, SLAB = KbCfg<KW>::SLAB;
     constexpr uint32_t TILES_PER_SLAB = KB_A_THREADS / TPT;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
@@ -983,8 +985,8 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     // A: a workgroup takes a few consecutive slabs (the next slab's words are prefetched under the current one)
     const uint32_t slabs_per_wg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, n_slabs / ((uint64_t)h->n_cu * 8)));
     const unsigned grid_a = (unsigned)((n_slabs + slabs_per_wg - 1) / slabs_per_wg);
-    if (sliced) hipLaunchKernelGGL((kb_slabsort_kernel<KW, true>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, h->k, plan, s, slabs_per_wg);
-    else hipLaunchKernelGGL((kb_slabsort_kernel<KW, false>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, h->k, plan, s, slabs_per_wg);
+    if (sliced) hipLaunchKernelGGL((kb_slabsort_kernel<KW, true>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
+    else hipLaunchKernelGGL((kb_slabsort_kernel<KW, false>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
     stamp();                                                   // end of A
     hipLaunchKernelGGL(kb_groupsum_kernel, dim3((unsigned)n_groups, (unsigned)((nbins + 63) / 64)), dim3(256), 0, h->stream, plan, s);
     hipLaunchKernelGGL(kb_binscan_kernel<CHUNK>, dim3((unsigned)nbins), dim3(256), 0, h->stream, plan, s);
@@ -1022,7 +1024,7 @@ static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const ui
     for (uint64_t off = 0; off < n_bases; off += step) {
         const uint64_t len = std::min<uint64_t>(step, n_bases - off);
         const uint64_t *p = d_packed + off / 32, *m = d_invalid + off / 64;
-        int rc = by_width(h, [&](auto KWc) { return kb_partition<decltype(KWc)::value>(h, p, m, len, filtered); });
+        int rc = by_width(h, [&](auto KWc) { return kb_partition<decltype(KWc)::value>(h, p, m, len, n_bases - off, filtered); });
         if (rc) return rc;
     }
     return KDF_OK;
@@ -1213,9 +1215,11 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
     return KDF_OK;
 }
 
-// L1: append a batch to the pending stream (tile aligned; the copy forces the mask bits past n_bases to "invalid")
+// L1: append a batch to the pending stream (tile aligned; the copy forces the mask bits past n_bases to "invalid").
+// A batch that fills its last tile keeps the all-invalid padding tile behind it: the next batch starts one tile later,
+// or a window of this batch's last k - 1 positions would run on into the next batch's first bases.
 static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    const uint64_t n_tiles = n_bases / KDF_TILE + 1;
     if (h->l1_tiles + n_tiles > h->l1_cap_tiles) {
         // grow (the pending stream moves): up to the size at which it is partitioned anyway
         const uint64_t target = std::max<uint64_t>((h->opt_l1_positions + h->opt_l1_direct_positions) / KDF_TILE + 1, h->l1_tiles + n_tiles);
@@ -1233,7 +1237,7 @@ static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_
         if (h->l1_mask) (void)hipFree(h->l1_mask);
         h->l1_packed = np; h->l1_mask = nm; h->l1_cap_tiles = cap;
     }
-    const unsigned blocks = (unsigned)((2 * n_tiles + 4 + 255) / 256);
+    const unsigned blocks = (unsigned)((2 * n_tiles + 4 + 255) / 256);               // (covers the kernel's ceil(n_bases / 64) tiles + padding)
     hipLaunchKernelGGL(kb_append_kernel, dim3(blocks), dim3(256), 0, h->stream, h->l1_packed + 2 * h->l1_tiles, h->l1_mask + h->l1_tiles,
                        d_packed, d_invalid, n_bases);
     HIPCHK(h, hipGetLastError());
@@ -1291,7 +1295,7 @@ static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint6
 
 // kdf_sieve_count_kernel: persistent workgroups over slabs of 1024 x WPT positions.  hits: the scan's hit bits (zeroed by
 // the caller), or NULL for a count --if; in_lds: every workgroup copies the sieve into LDS first
-static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles,
+static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles, uint64_t n_bases,
                          unsigned long long *hits, bool in_lds) {
     by_width(h, [&](auto KWc) {
         constexpr int KW = decltype(KWc)::value;
@@ -1302,7 +1306,7 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
         const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
         KdfSieve sv{h->sieve, h->sieve_words - 1};
 #define SV_LAUNCH(L, S) hipLaunchKernelGGL((kdf_sieve_count_kernel<KW, L, S>), dim3(grid), dim3(KB_THREADS), 0, h->stream, \
-                                           d_packed, d_invalid, n_tiles, h->k, h->t, h->ctl, sv, spw, hits)
+                                           d_packed, d_invalid, n_tiles, n_bases, h->k, h->t, h->ctl, sv, spw, hits)
         if (hits) { if (in_lds) SV_LAUNCH(true, true); else SV_LAUNCH(false, true); }
         else { if (in_lds) SV_LAUNCH(true, false); else SV_LAUNCH(false, false); }
 #undef SV_LAUNCH
@@ -1318,7 +1322,7 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
     if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (h->prof) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, h->stream); }
-        launch_sieve(h, d_packed, d_invalid, n_tiles, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+        launch_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
         if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_ev.emplace_back(e0, e1); h->prof_tiles.push_back(n_tiles); }
         HIPCHK(h, hipGetLastError());
         h->last_path = 3;
@@ -2203,12 +2207,14 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
         }
         if (h->sieve_valid) {
             HIPCHK(h, hipMemsetAsync(d_hit_bits, 0, n_tiles * 8, h->stream));
-            launch_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, (unsigned long long *)d_hit_bits,
+            h->last_scan_path = 3;
+            launch_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, n_bases, (unsigned long long *)d_hit_bits,
                          h->sieve_words <= KDF_SV_LDS_WORDS);
             HIPCHK(h, hipGetLastError());
             return KDF_OK;
         }
     }
+    h->last_scan_path = 0;
     launch_stream<MODE_SCAN>(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, 0, n_tiles, (uint64_t *)d_hit_bits, n_bases);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
@@ -2464,6 +2470,7 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "ring_bytes") *value = (int64_t)(h->ring_entries * 8 * h->kw);
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
+    else if (n == "last_scan_path") *value = h->last_scan_path;
     else if (n == "last_merge_path") *value = h->last_merge_path;
     else if (n == "heavy_buckets") *value = (int64_t)h->stat_heavy_buckets;
     else if (n == "fused_dumps") *value = (int64_t)h->stat_fused_dumps;

@@ -164,7 +164,8 @@ class KmerEngine:
         return self
 
     def count_dev(self, d_packed: int, d_invalid: int, n_bases: int):
-        """Stream resident in HBM (raw device pointers, padded per stream_words).
+        """Stream resident in HBM (raw device pointers to buffers of the stream_words(n_bases) sizes; positions at or
+        past n_bases are invalid whatever those words hold, so zero padding or a prefix of a longer stream is fine).
         The engine launches on its own stream unless set_stream() was called:
         the buffers must be complete (synchronise the producer) before the call."""
         self._ck(self._lib.kdf_count_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases)))

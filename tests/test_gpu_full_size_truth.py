@@ -390,15 +390,11 @@ def test_d_one_call_past_2_32_positions(workloads, path):
     assert (distinct, windows, ge3) == t and int(dump[2].sum().item()) == windows
 
 
-def test_d_one_call_just_over_2_31_positions(workloads):
-    """The first 14 222 336 reads of the same stream (2^31 + 89 088 positions: two partition passes, the second one
-    tiny), against a truth taken key slice by key slice over the whole prefix."""
+def _check_prefix(ds, n, what):
+    """one count_dev of the stream's first n positions, on auto and direct, against the truth of that prefix"""
     import torch
-    ds, _ = workloads.get("30 M reads", _big_stream)
-    n = OVER_2_31_READS * 151
-    assert (1 << 31) < n < (1 << 31) + (1 << 17) and n % 64 == 0
     prefix = (ds.packed, ds.invalid, n)
-    halves = [timed_truth(f"2^31 prefix, key slice {s} of 2", prefix, 31, key_slice=(s, 2)) for s in range(2)]
+    halves = [timed_truth(f"{what}, key slice {s} of 2", prefix, 31, key_slice=(s, 2)) for s in range(2)]
     assert halves[0][3] == halves[1][3]
     truth = tuple(torch.cat([h[i] for h in halves]) for i in range(3)) + (halves[0][3],)
     del halves
@@ -413,7 +409,23 @@ def test_d_one_call_just_over_2_31_positions(workloads):
                 assert e.get_stat("flushes") == before + 1 and e.get_stat("pending_passes") == 0
             else:
                 assert e.last_count_path() == "direct" and e.get_stat("binned_passes") == 0
-            assert_table_equals_truth(e, truth, f"2^31 prefix, {path}")
+            assert_table_equals_truth(e, truth, f"{what}, {path}")
+    return truth[3]
+
+
+def test_d_one_call_just_over_2_31_positions(workloads):
+    """The first 14 222 336 reads of the same stream (2^31 + 89 088 positions: two partition passes, the second one
+    tiny), against a truth taken key slice by key slice over the whole prefix.  Then a prefix that is cut in the MIDDLE
+    of the next read, 75 bases in, with n % 64 != 0: the words past it are the rest of the stream (valid bases, mask
+    bits 0), and no window may reach into them (include/kdf.h, "Read streams")."""
+    ds, _ = workloads.get("30 M reads", _big_stream)
+    n = OVER_2_31_READS * 151
+    assert (1 << 31) < n < (1 << 31) + (1 << 17) and n % 64 == 0
+    aligned = _check_prefix(ds, n, "2^31 prefix")
+    n2 = n + 75
+    assert n2 % 64 != 0 and n2 % 151 == 75 and ds.read_len == 150
+    cut = _check_prefix(ds, n2, "2^31 prefix cut inside a read")
+    assert aligned <= cut <= aligned + 75 - 31 + 1             # the cut read adds at most its 45 whole windows
 
 
 # ---------------------------------------------------------------------------------------------------------------------
