@@ -203,6 +203,59 @@ int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_h
 int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_keys_lo,
                             const void *const *d_keys_hi, const void *const *d_counts, const uint64_t *n);
 
+/* ------------------------------------------------- two-pass counting ---- */
+
+/* Keep k-mers seen fewer than L times out of the table (`jellyfish bc` + `jellyfish count --bc`, made exact).  The
+ * child count of the discovery chain is `jellyfish count` followed by `dump -L min_child_count`
+ * (discovery/pipeline.py:114-226); in a sequenced sample most distinct k-mers are sequencing errors seen once, and
+ * each of them costs a table slot only to be dropped by the dump.  With a prefilter the reads are streamed twice:
+ *
+ *   pass 1  kdf_prefilter_begin, kdf_prefilter_add_* over every batch (TALLY: no key is stored), kdf_prefilter_arm
+ *   pass 2  the usual insert-mode count calls over the same batches: a window is counted iff its cell reads >= L
+ *   then    dumps / queries as usual; kdf_prefilter_drop frees the sieve, counts are ungated again
+ *
+ * The sieve.  2^s cells, 16 <= s <= 38, HALF A BYTE each.  cell(key) = h >> (64 - s), the TOP s bits of the key's
+ * 64-bit stored form h: kdf_mix64(key) = (key ^ (key >> 32)) * 0x9FB21C651E98DF25 for k <= 32,
+ * kdf_mix64(lo ^ rotl(hi, 37)) for 33 <= k <= 63, and for long keys kdf_mix64(w0 ^ f) with f folded from the top word
+ * down, f = 0; f = kdf_mix64(f ^ w_j) + 0x632BE59BD9B4E019 for j = W-1 .. 1 (all mod 2^64).  The value of a cell is
+ * min(number of tallied windows whose key maps to it, 3), whatever the order or concurrency of the tally calls.
+ *
+ * Exactness.  Pass 1 only tallies and pass 2 counts every admitted window in full, so the table holds exactly
+ * {(key, full count) : value(cell(key)) >= L}: every key with count >= L (its own sightings bring its cell to L), plus
+ * those rarer keys that share a cell with enough other sightings.  `dump -L m` for every m >= L is therefore identical
+ * to the plain count's.  kdf_stats' `windows` counts admitted windows only (as it does for key_parts).
+ *
+ * State machine, every violation an error that names the rule:
+ *   - off -> begin -> tallying -> arm -> armed -> drop -> off.  begin flushes pending count work, allocates and zeroes
+ *     the sieve (KDF_ERR_NOMEM when it does not fit).  min_count L must be 2 or 3 (KDF_ERR_INVALID: 1 is the plain
+ *     count, above 3 the cell saturates -- for `-L 5` ask for 3 and dump with 5).  log2_cells 16..38, or 0: the engine
+ *     takes ceil(log2(8 x capacity_hint of kdf_create)) clamped to that range.
+ *   - kdf_prefilter_add_* and kdf_prefilter_arm only while tallying; begin while tallying or armed: KDF_ERR_STATE.
+ *   - while TALLYING insert-mode count calls are KDF_ERR_STATE (such a count would be neither gated nor known to be
+ *     meant ungated); while ARMED they are gated, on every path (direct, binned, pending stream, force_path, defer,
+ *     fused_dump, growth of the table).  count --if, queries, dumps, histogram, scan, kdf_add_pairs*, kdf_load_filter*
+ *     are never affected.
+ *   - drop flushes pending count work first (it was admitted under the sieve).  kdf_clear empties the table and leaves
+ *     the prefilter as it is; kdf_destroy frees it.
+ *   - refused together (KDF_ERR_STATE, either order): key_parts > 1 and a prefilter; hash_shift != 0 and a prefilter.
+ *   - every key width: k <= 32, 33..63, long engines (odd 65..201).
+ * Single GPU only: a rank of a sharded count sees only its share of the reads, so its tallies under-count; the sieves
+ * would have to be merged with a saturating sum first.  The mirrors do not use the prefilter when world > 1.
+ * Stats (kdf_get_stat): "prefilter_state" (0 off / 1 tallying / 2 armed), "prefilter_min_count",
+ * "prefilter_log2_cells", "prefilter_bytes", "prefilter_windows" (windows tallied), and under kdf_profile(h, 1)
+ * "prefilter_us" / "prefilter_passes" (the tally kernel, HIP events). */
+int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells);
+/* Tally one batch of the read stream (host buffers / device buffers of the kdf_stream_words(n_bases) sizes / the batch
+ * an upload slot holds, kdf_upload_reads_async).  The stream is read exactly as the count reads it ("Read streams":
+ * positions at or past n_bases are invalid whatever the buffers hold). */
+int kdf_prefilter_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases);
+int kdf_prefilter_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases);
+int kdf_prefilter_add_uploaded(kdf_engine *h, int slot);
+int kdf_prefilter_arm(kdf_engine *h);
+int kdf_prefilter_drop(kdf_engine *h);
+/* cells_by_value[v] = number of cells that read v, v = 0 .. 3 (their sum is 2^log2_cells); tallying or armed. */
+int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]);
+
 /* ------------------------------------------------ count --if (filter) ---- */
 
 /* Load the `--if` filter: the table becomes exactly these canonical keys with

@@ -26,7 +26,9 @@ int kdf_sort_rows_device(uint64_t *d_keys, int words, uint32_t *d_cnt, uint64_t 
 // kernels
 // ===========================================================================
 
-enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2 };
+enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2, MODE_GATED = 3 };
+// MODE_GATED: an insert-mode count behind an armed prefilter (kdf_prefilter.h).  `hit_bits` then is an INPUT: word
+// [tile] holds the tile's admitted windows, written by the gate kernel, and is ANDed into the validity bitmap.
 
 // One thread = one tile of 64 window starts.  Windows are processed in batches
 // of 8: the 8 home-slot key loads are issued back to back before any of them is
@@ -45,6 +47,7 @@ __global__ __launch_bounds__(256) void kdf_stream_kernel(
         uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
         kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
         uint64_t valid = kdf_valid_windows(m0, m1, k);
+        if constexpr (MODE == MODE_GATED) valid &= hit_bits[tile];
         nwin = __popcll(valid);
         const bool sliced = MODE == MODE_INSERT && t.key_parts > 1;       // count only this key-space slice (KdfTable::key_parts)
         uint64_t hits = 0;
@@ -86,10 +89,10 @@ __global__ __launch_bounds__(256) void kdf_stream_kernel(
                         if (s != ~0ull && t.cnt[s] != 0) hits |= 1ull << (b + u);
                     } else if constexpr (KW == 1) {
                         if (!ok) continue;
-                        if (!kdf_add_narrow<MODE == MODE_INSERT>(t, klo[u], 1u, slot[u], cur[u], claimed)) full = true;
+                        if (!kdf_add_narrow<MODE != MODE_FILTERED>(t, klo[u], 1u, slot[u], cur[u], claimed)) full = true;
                     } else {
                         // every lane that reached this batch calls in; idle lanes pass todo = false
-                        if (!kdf_add_wide<MODE == MODE_INSERT>(t, ok, klo[u], khi[u], 1u, slot[u], claimed)) full = true;
+                        if (!kdf_add_wide<MODE != MODE_FILTERED>(t, ok, klo[u], khi[u], 1u, slot[u], claimed)) full = true;
                     }
                 }
             }
@@ -304,6 +307,8 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 
 // long keys (odd k 65..201): table layout, claim protocol and kernels
 #include "kdf_long.h"
+// the counting sieve of the two-pass count: tally, gate and fill kernels
+#include "kdf_prefilter.h"
 
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
@@ -444,6 +449,7 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 // ===========================================================================
 
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
+enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -540,6 +546,15 @@ struct kdf_engine {
     uint64_t prof_stage_passes = 0;
     double prof_histo_ms = 0.0;                      // kdf_histo_kernel under kdf_profile (stats "histo_us", "histo_passes")
     uint64_t prof_histo_passes = 0;
+    // ---- two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off ------------------------
+    int pf_state = PF_OFF;
+    KdfPrefilter pf{};                               // the sieve (device), its size and the gate's threshold
+    unsigned long long *pf_ctr = nullptr;            // device: sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
+    uint64_t *pf_admit = nullptr; uint64_t pf_admit_words = 0;   // the gate's output for the stream being counted (grow-only)
+    uint64_t capacity_hint = 0;                      // kdf_create's: sizes the sieve when the caller leaves that to the engine
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pf_ev;   // tally kernels under kdf_profile (stats "prefilter_us", "prefilter_passes")
+    double prof_pf_ms = 0.0;
+    uint64_t prof_pf_passes = 0;
     std::string err;
 };
 
@@ -836,6 +851,7 @@ template <int KW>
 static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t hv) {
     HIPCHK(h, hipFuncSetAttribute((const void *)(kb_slabsort_kernel<KW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a));
     HIPCHK(h, hipFuncSetAttribute((const void *)(kb_slabsort_kernel<KW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a));
+    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_slabsort_gated_kernel<KW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_piecesort_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_piecesort_more_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_piecesort_pipe_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
@@ -933,7 +949,8 @@ static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, ui
 
 // ONE partition pass (A, P, B) of a device-resident stream of at most opt_binned_max_positions positions into the ring
 template <int KW>
-static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t n_end, bool filtered) {
+static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t n_end, bool filtered,
+                        const uint64_t *admit) {
     constexpr int WPT = KbCfg<KW>::WPT, TPT = 64 / WPT, CHUNK = KbCfg<KW>::CHUNK, SLAB = KbCfg<KW>::SLAB;
     constexpr uint32_t TILES_PER_SLAB = KB_A_THREADS / TPT;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
@@ -985,7 +1002,9 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     // A: a workgroup takes a few consecutive slabs (the next slab's words are prefetched under the current one)
     const uint32_t slabs_per_wg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, n_slabs / ((uint64_t)h->n_cu * 8)));
     const unsigned grid_a = (unsigned)((n_slabs + slabs_per_wg - 1) / slabs_per_wg);
-    if (sliced) hipLaunchKernelGGL((kb_slabsort_kernel<KW, true>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
+    // (admit: the windows an armed prefilter lets through, one word per tile of this pass -- never together with a key slice)
+    if (admit) hipLaunchKernelGGL((kb_slabsort_gated_kernel<KW>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg, admit);
+    else if (sliced) hipLaunchKernelGGL((kb_slabsort_kernel<KW, true>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
     else hipLaunchKernelGGL((kb_slabsort_kernel<KW, false>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
     stamp();                                                   // end of A
     hipLaunchKernelGGL(kb_groupsum_kernel, dim3((unsigned)n_groups, (unsigned)((nbins + 63) / 64)), dim3(256), 0, h->stream, plan, s);
@@ -1019,12 +1038,15 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
 // partition a stream of any length: passes of at most opt_binned_max_positions
 // positions, each starting on a tile boundary (windows that start in a pass may read on
 // into the next tiles: the stream is one buffer)
+static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit);
 static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, bool filtered) {
     const uint64_t step = h->opt_binned_max_positions;
+    const uint64_t *admit = nullptr;                      // armed prefilter: the gate runs once over the whole stream
+    if (!filtered) { int rcg = pf_gate(h, d_packed, d_invalid, n_bases, &admit); if (rcg) return rcg; }
     for (uint64_t off = 0; off < n_bases; off += step) {
         const uint64_t len = std::min<uint64_t>(step, n_bases - off);
         const uint64_t *p = d_packed + off / 32, *m = d_invalid + off / 64;
-        int rc = by_width(h, [&](auto KWc) { return kb_partition<decltype(KWc)::value>(h, p, m, len, n_bases - off, filtered); });
+        int rc = by_width(h, [&](auto KWc) { return kb_partition<decltype(KWc)::value>(h, p, m, len, n_bases - off, filtered, admit ? admit + off / 64 : nullptr); });
         if (rc) return rc;
     }
     return KDF_OK;
@@ -1193,6 +1215,8 @@ static bool use_binned(const kdf_engine *h, uint64_t n_bases, bool filtered) {
 static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     { int rc0 = materialize(h); if (rc0) return rc0; }
+    const uint64_t *admit = nullptr;                      // armed prefilter: the gate runs once over the whole stream
+    { int rcg = pf_gate(h, d_packed, d_invalid, n_bases, &admit); if (rcg) return rcg; }
     h->last_path = 0;
     uint64_t tile = 0;
     while (tile < n_tiles) {
@@ -1203,7 +1227,8 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
             continue;
         }
         uint64_t chunk = std::min<uint64_t>(n_tiles - tile, std::max<uint64_t>(room / KDF_TILE, 1));
-        launch_stream<MODE_INSERT>(h, d_packed, d_invalid, tile, chunk, nullptr, n_bases);
+        if (admit) launch_stream<MODE_GATED>(h, d_packed, d_invalid, tile, chunk, const_cast<uint64_t *>(admit), n_bases);
+        else launch_stream<MODE_INSERT>(h, d_packed, d_invalid, tile, chunk, nullptr, n_bases);
         HIPCHK(h, hipGetLastError());
         bool full = false;
         int rc = ctl_sync(h, &full);
@@ -1268,9 +1293,13 @@ static int pending_drop(kdf_engine *h) {
     return kb_ring_reset(h);
 }
 
+#define PF_TALLYING_MSG "insert-mode count while the prefilter is tallying: such a count would be neither gated nor known to be meant " \
+                       "ungated -- kdf_prefilter_arm (gated counts) or kdf_prefilter_drop (plain counts) first"
+
 // insert-mode count over a device-resident stream
 static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads: a filter is loaded; call kdf_clear first");
+    if (h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
     h->sieve_valid = false;                          // new keys join the table: a sieve built from it earlier (scan) is stale
     h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;       // (tables are re-created by reserve / rehash: set per call)
     if (n_bases == 0) return KDF_OK;
@@ -1381,6 +1410,79 @@ static int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const c
     return KDF_OK;
 }
 
+// ---------------------------------------------------------------------------
+// two-pass counting (kdf_prefilter.h)
+
+// tally (admit == NULL) or gate (admit[tile] written) over a device-resident stream
+static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t *admit) {
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        for (uint64_t t0 = 0; t0 < n_tiles; t0 += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
+            const uint64_t m = std::min<uint64_t>(1ull << 30, n_tiles - t0);
+            const unsigned blocks = (unsigned)((m + 255) / 256);
+            // the piece is a stream of its own that starts at tile t0 and ends where the whole stream ends
+            const uint64_t *p = d_packed + 2 * t0, *mk = d_invalid + t0;
+            const uint64_t nb = n_bases - t0 * KDF_TILE;
+#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->pf, h->pf_ctr, admit ? admit + t0 : nullptr)
+            if constexpr (W <= 2) { if (admit) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
+            else { if (admit) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
+#undef PF_LAUNCH
+        }
+        return 0;
+    });
+}
+
+// Armed: *admit = one word per tile of the stream, bit i = window i is valid and its cell reads >= min_count (stream
+// order: the buffer is reused by the next gated stream).  Not armed: *admit = NULL, the count is not gated.
+static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit) {
+    *admit = nullptr;
+    if (h->pf_state != PF_ARMED || n_bases == 0) return KDF_OK;
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    if (h->pf_admit_words < n_tiles) {
+        if (h->pf_admit) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->pf_admit); h->pf_admit = nullptr; h->pf_admit_words = 0; }
+        const uint64_t want = n_tiles + n_tiles / 8 + 512;
+        HIPCHK(h, hipMalloc((void **)&h->pf_admit, want * 8));
+        h->pf_admit_words = want;
+    }
+    pf_launch(h, d_packed, d_invalid, n_bases, h->pf_admit);
+    HIPCHK(h, hipGetLastError());
+    *admit = h->pf_admit;
+    return KDF_OK;
+}
+
+static int pf_tally_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
+    if (n_bases == 0) return KDF_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    pf_launch(h, d_packed, d_invalid, n_bases, nullptr);
+    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_pf_ev.emplace_back(e0, e1); }
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+static void pf_prof_collect(kdf_engine *h) {
+    for (auto &ev : h->prof_pf_ev) {
+        float ms = 0.f;
+        (void)hipEventSynchronize(ev.second);
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_pf_ms += ms; h->prof_pf_passes++; }
+        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+    }
+    h->prof_pf_ev.clear();
+}
+
+static void pf_free(kdf_engine *h) {
+    if (h->pf.words) (void)hipFree(h->pf.words);
+    if (h->pf_ctr) (void)hipFree(h->pf_ctr);
+    if (h->pf_admit) (void)hipFree(h->pf_admit);
+    h->pf = KdfPrefilter{}; h->pf_ctr = nullptr; h->pf_admit = nullptr; h->pf_admit_words = 0;
+    h->pf_state = PF_OFF;
+}
+
+#define PF_NEED_TALLYING(h, fn) \
+    do { if ((h)->pf_state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
+                                                       fn, (h)->pf_state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
+
 // words per key of a host form's first key array: 1 for the (lo, hi) forms, W for the rows of the _w forms
 static uint64_t lo_words(const kdf_engine *h) { return is_long(h) ? h->kw : 1; }
 
@@ -1417,6 +1519,7 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
         return fail(nullptr, KDF_ERR_HIP, "kdf_create: no HIP device available (%s)", hipGetErrorString(e));
     if (device < 0 || device >= ndev) return fail(nullptr, KDF_ERR_INVALID, "kdf_create: device %d of %d", device, ndev);
     kdf_engine *h = new kdf_engine();
+    h->capacity_hint = capacity_hint;
     h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
@@ -1444,6 +1547,8 @@ void kdf_destroy(kdf_engine *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     table_free(h->t);
     prof_collect(h);
+    pf_prof_collect(h);
+    pf_free(h);
     for (int i = 0; i < 4; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
     for (int i = 0; i < 8; ++i) if (h->kb_buf[i]) (void)hipFree(h->kb_buf[i]);
     if (h->l1_packed) (void)hipFree(h->l1_packed);
@@ -1596,6 +1701,7 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
 int kdf_count_uploaded(kdf_engine *h, int slot, int filtered) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: nothing was uploaded into slot %d", slot);
+    if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);      // (the slot keeps its batch)
     HIPCHK(h, hipSetDevice(h->device));
     h->up_valid[slot] = false;
     const uint64_t n = h->up_n[slot];
@@ -2287,6 +2393,113 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
 #define KDF_NEED_LONG(h, fn) \
     do { if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: takes engines for odd k 65..%d only (k=%d: use the (lo, hi) form)", fn, KDF_LONG_MAX_K, (h)->k); } while (0)
 
+// ------------------------------------------------------------ two-pass counting ----
+
+int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->pf_state != PF_OFF)
+        return fail(h, KDF_ERR_STATE, "kdf_prefilter_begin: a prefilter is already %s; kdf_prefilter_drop first", h->pf_state == PF_ARMED ? "armed" : "tallying");
+    if (min_count != 2 && min_count != 3)
+        return fail(h, KDF_ERR_INVALID, "kdf_prefilter_begin: min_count %u: must be 2 or 3 (1 is the plain count; a cell saturates at 3: for a dump "
+                                        "with -L above 3 ask for 3 and dump with the larger bound)", min_count);
+    if (log2_cells != 0 && (log2_cells < KDF_PF_MIN_LOG2 || log2_cells > KDF_PF_MAX_LOG2))
+        return fail(h, KDF_ERR_INVALID, "kdf_prefilter_begin: log2_cells %u: must be %d..%d, or 0 for the engine's choice", log2_cells, KDF_PF_MIN_LOG2, KDF_PF_MAX_LOG2);
+    if (h->opt_key_parts > 1) return fail(h, KDF_ERR_STATE, "kdf_prefilter_begin: key_parts = %u is set: a prefilter counts the whole key space in one table (set key_parts to 0 first)", h->opt_key_parts);
+    if (h->opt_hash_shift) return fail(h, KDF_ERR_STATE, "kdf_prefilter_begin: hash_shift = %u is set: an owner table of the multi-GPU merge takes no prefilter (a rank sees only its shard of the reads)", h->opt_hash_shift);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    if (log2_cells == 0) log2_cells = std::min<uint32_t>(KDF_PF_MAX_LOG2, std::max<uint32_t>(KDF_PF_MIN_LOG2, log2ceil(8 * std::max<uint64_t>(h->capacity_hint, 1))));
+    const uint64_t bytes = 1ull << (log2_cells - 1);              // half a byte per cell
+    unsigned long long *words = nullptr, *ctr = nullptr;
+    hipError_t e = hipMalloc((void **)&words, bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&ctr, (KDF_SHARDS * 16 + 4) * 8);
+    if (e != hipSuccess) {
+        if (words) (void)hipFree(words);
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "kdf_prefilter_begin: a sieve of 2^%u cells (%.1f GB) does not fit the device (%s)",
+                    log2_cells, (double)bytes / 1e9, hipGetErrorString(e));
+    }
+    h->pf.words = words; h->pf.log2_cells = log2_cells; h->pf.min_count = min_count; h->pf_ctr = ctr;
+    HIPCHK(h, hipMemsetAsync(words, 0, bytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(ctr, 0, (KDF_SHARDS * 16 + 4) * 8, h->stream));
+    h->pf_state = PF_TALLYING;
+    return KDF_OK;
+}
+
+int kdf_prefilter_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    PF_NEED_TALLYING(h, "kdf_prefilter_add_reads_dev");
+    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_add_reads_dev: NULL stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    return pf_tally_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+}
+
+int kdf_prefilter_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    PF_NEED_TALLYING(h, "kdf_prefilter_add_reads");
+    if (n_bases == 0) return KDF_OK;
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_add_reads: NULL stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
+    if (rc) return rc;
+    return pf_tally_dev(h, dp, dm, n_bases);
+}
+
+int kdf_prefilter_add_uploaded(kdf_engine *h, int slot) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    PF_NEED_TALLYING(h, "kdf_prefilter_add_uploaded");
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_prefilter_add_uploaded: nothing was uploaded into slot %d", slot);
+    HIPCHK(h, hipSetDevice(h->device));
+    h->up_valid[slot] = false;
+    const uint64_t n = h->up_n[slot];
+    if (n == 0) return KDF_OK;
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
+    HIPCHK(h, hipEventSynchronize(h->up_done[slot]));              // (the caller recycles its source buffer on return: kdf_count_uploaded)
+    const int rc = pf_tally_dev(h, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
+    (void)hipEventRecord(h->use_done[slot], h->stream);
+    return rc;
+}
+
+int kdf_prefilter_arm(kdf_engine *h) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->pf_state != PF_TALLYING)
+        return fail(h, KDF_ERR_STATE, "kdf_prefilter_arm: the prefilter is %s; only a tallying prefilter (kdf_prefilter_begin) is armed", h->pf_state == PF_ARMED ? "armed already" : "off");
+    h->pf_state = PF_ARMED;
+    return KDF_OK;
+}
+
+int kdf_prefilter_drop(kdf_engine *h) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_drop: no prefilter (kdf_prefilter_begin)");
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcf = pending_flush(h); if (rcf) return rcf; }           // what is pending was admitted under this sieve
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    pf_prof_collect(h);
+    pf_free(h);
+    return KDF_OK;
+}
+
+int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]) {
+    if (!h || !cells_by_value) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_fill: NULL pointer");
+    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_fill: no prefilter (kdf_prefilter_begin)");
+    HIPCHK(h, hipSetDevice(h->device));
+    unsigned long long *out3 = h->pf_ctr + KDF_SHARDS * 16;
+    const uint64_t n_words = 1ull << (h->pf.log2_cells - 4);
+    HIPCHK(h, hipMemsetAsync(out3, 0, 3 * 8, h->stream));
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_words + 1023) / 1024, (uint64_t)h->n_cu * 8));
+    hipLaunchKernelGGL(kdf_pf_fill_kernel, dim3(grid), dim3(256), 0, h->stream, h->pf.words, n_words, out3);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long ge[3] = {0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(ge, out3, sizeof ge, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    cells_by_value[0] = (1ull << h->pf.log2_cells) - ge[0];
+    cells_by_value[1] = ge[0] - ge[1];
+    cells_by_value[2] = ge[1] - ge[2];
+    cells_by_value[3] = ge[2];
+    return KDF_OK;
+}
+
 int kdf_key_words(int k) {
     if (k >= 1 && k <= 32) return 1;
     if (k >= 33 && k <= 63) return 2;
@@ -2381,6 +2594,8 @@ int kdf_profile(kdf_engine *h, int enable) {
     for (double &m : h->prof_stage_ms) m = 0.0;
     h->prof_stage_passes = 0;
     h->prof_histo_ms = 0.0; h->prof_histo_passes = 0;
+    pf_prof_collect(h);
+    h->prof_pf_ms = 0.0; h->prof_pf_passes = 0;
     return KDF_OK;
 }
 
@@ -2410,6 +2625,8 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
         const uint32_t parts = n == "key_parts" ? (uint32_t)value : h->opt_key_parts, part = n == "key_part" ? (uint32_t)value : h->opt_key_part;
         if (value < 0 || parts > 65536 || (n == "key_part" && part >= std::max<uint32_t>(parts, 1)))
             return fail(h, KDF_ERR_INVALID, "key_parts must be 0..65536 and key_part below it");
+        if (parts > 1 && h->pf_state != PF_OFF)
+            return fail(h, KDF_ERR_STATE, "key_parts = %u with a prefilter: a prefilter counts the whole key space in one table (kdf_prefilter_drop first)", parts);
         h->opt_key_parts = parts; h->opt_key_part = n == "key_parts" ? 0 : part;
     }
     else if (n == "binned_min_positions") h->opt_binned_min_positions = (uint64_t)value;
@@ -2436,6 +2653,8 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     else if (n == "hash_shift") {
         if (value > 8) return fail(h, KDF_ERR_INVALID, "hash_shift must be 0..8");
         if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "hash_shift: not available for k > 63 (long keys count on one GPU)");
+        if (value != 0 && h->pf_state != PF_OFF)
+            return fail(h, KDF_ERR_STATE, "hash_shift = %lld with a prefilter: an owner table of the multi-GPU merge takes no prefilter (kdf_prefilter_drop first)", (long long)value);
         if ((uint32_t)value != h->opt_hash_shift) {
             int rc = ctl_sync(h, nullptr);
             if (rc) return rc;
@@ -2464,6 +2683,22 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "replayed_buckets") *value = (int64_t)h->stat_replayed_buckets;
     else if (n == "histo_us") *value = (int64_t)(h->prof_histo_ms * 1000.0 + 0.5);
     else if (n == "histo_passes") *value = (int64_t)h->prof_histo_passes;
+    else if (n == "prefilter_state") *value = h->pf_state;
+    else if (n == "prefilter_min_count") *value = h->pf.min_count;
+    else if (n == "prefilter_log2_cells") *value = h->pf.log2_cells;
+    else if (n == "prefilter_bytes") *value = h->pf_state == PF_OFF ? 0 : (int64_t)(1ull << (h->pf.log2_cells - 1));
+    else if (n == "prefilter_windows") {
+        *value = 0;
+        if (h->pf_ctr) {                                              // the sharded device counter, summed here
+            std::vector<unsigned long long> c(KDF_SHARDS * 16);
+            HIPCHK(h, hipSetDevice(h->device));
+            HIPCHK(h, hipMemcpyAsync(c.data(), h->pf_ctr, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            for (int i = 0; i < KDF_SHARDS; ++i) *value += (int64_t)c[i * 16];
+        }
+    }
+    else if (n == "prefilter_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pf_ms * 1000.0 + 0.5); }
+    else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     else if (n == "pending_passes") *value = (int64_t)h->n_pass;
     else if (n == "pending_positions") *value = (int64_t)(h->pend_positions + h->l1_tiles * KDF_TILE);

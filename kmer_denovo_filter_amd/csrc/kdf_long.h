@@ -176,6 +176,9 @@ __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
     bool full = false;
     uint64_t hits = 0;
     const bool sliced = MODE == MODE_INSERT && t.key_parts > 1;
+    constexpr bool INS = MODE == MODE_INSERT || MODE == MODE_GATED;       // keys are inserted (MODE_GATED: behind a prefilter,
+    uint64_t adm = ~0ull;                                                 // hit_bits[tile] = the tile's admitted windows)
+    if constexpr (MODE == MODE_GATED) adm = active ? hit_bits[tile] : 0ull;
     // (inactive lanes still run the loops with every window invalid: the probe loops are wave-uniform)
     KdfRoll<W> st;
 #pragma unroll
@@ -200,6 +203,7 @@ __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
             push();                                                // base o - 1 = b + u + k - 1 closes window b + u
             st.canon(key[u]);
             ok[u] = active && st.run >= k;
+            if constexpr (MODE == MODE_GATED) ok[u] = ok[u] && ((adm >> (b + u)) & 1);
             h[u] = kdf_long_hash<W>(key[u]);
             slot[u] = kdf_home(t, h[u]);
             if (sliced && ok[u] && kdf_slice(h[u], t.key_parts) != t.key_part) ok[u] = false;
@@ -208,7 +212,7 @@ __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
             const uint64_t *ptop = kdf_long_word<W>(t, W - 1, slot[u]);
-            pre[u] = ok[u] ? (MODE == MODE_INSERT ? kdf_ld(ptop) : *ptop) : KDF_EMPTY;
+            pre[u] = ok[u] ? (INS ? kdf_ld(ptop) : *ptop) : KDF_EMPTY;
         }
 #pragma unroll
         for (int u = 0; u < NB; ++u) {
@@ -218,7 +222,7 @@ __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
                     if (s != ~0ull && t.cnt[s] != 0) hits |= 1ull << (b + u);
                 }
             } else {
-                if (!kdf_add_long<W, MODE == MODE_INSERT>(t, ok[u], h[u], key[u], 1u, slot[u], pre[u], true, claimed)) full = true;
+                if (!kdf_add_long<W, INS>(t, ok[u], h[u], key[u], 1u, slot[u], pre[u], true, claimed)) full = true;
             }
         }
     }

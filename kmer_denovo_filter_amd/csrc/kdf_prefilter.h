@@ -1,0 +1,179 @@
+// kdf_prefilter.h -- the counting sieve of the two-pass count (include/kdf.h, "two-pass counting").
+//
+// Pass 1 (TALLY) walks the read stream exactly like the direct count kernel and bumps one saturating cell per valid
+// window; pass 2 (GATE) walks the stream the count is about to take and writes, per tile of 64 window starts, one
+// 64-bit "admitted" word (bit i: window i is valid and its cell reads >= min_count) which the count kernels AND into
+// their validity bitmap.  The sieve is immutable between kdf_prefilter_arm and kdf_prefilter_drop, so the gate may run
+// whenever the windows are formed: per call on the direct path, at partition time for the pending stream.
+//
+// Cells.  2^s cells, 16 <= s <= 38; cell(key) = h >> (64 - s), h the key's 64-bit stored form / hash (kdf_mix64(key),
+// kdf_hash(lo, hi), kdf_long_hash(words)): the TOP bits, so a table bucket owns a contiguous range of cells.
+// A cell is one nibble: HALF A BYTE per cell, sixteen cells per 64-bit word, cell c in bits [4 (c & 15), +4) of word
+// c >> 4.  Bits 0..2 of the nibble are three planes A, B, C; bit 3 is unused.  A sighting sets the lowest plane that is
+// not yet set, with a ladder of RETURNING atomic ORs: OR in A; if A was already set OR in B; if B was already set OR in
+// C.  Whatever the order and the concurrency of the sightings, after n of them min(n, 3) planes are set: the first
+// OR to reach a plane sets it, every other one moves on.  value(cell) = number of planes set = min(sightings, 3).
+// No compare-and-swap loop, and no lane ever waits for another lane.  The word is LOADED first and the atomics are
+// skipped when the cell already reads 3: in a 15-30x sample that is most windows, and it keeps a homopolymer key
+// with 10^6 sightings from hammering one word (a stale read only costs atomics that change nothing).
+#pragma once
+#include "kdf_device.h"
+#include "kdf_long.h"
+
+#define KDF_PF_MIN_LOG2 16
+#define KDF_PF_MAX_LOG2 38
+
+struct KdfPrefilter {
+    unsigned long long *words;   // 2^(log2_cells - 4) words
+    uint32_t log2_cells;
+    uint32_t min_count;          // 2 or 3: the gate admits cells that read >= min_count
+};
+
+__device__ __forceinline__ void kdf_pf_locate(const KdfPrefilter &pf, uint64_t h, uint64_t &word, uint32_t &sh) {
+    const uint64_t cell = h >> (64 - pf.log2_cells);
+    word = cell >> 4;
+    sh = (uint32_t)(cell & 15) * 4;
+}
+
+// one sighting of the cell at (w, sh); `cur`: the word as loaded before
+__device__ __forceinline__ void kdf_pf_bump(unsigned long long *w, uint32_t sh, uint64_t cur) {
+    if (((cur >> sh) & 7) == 7) return;                               // saturated: nothing left to set
+    unsigned long long old = atomicOr(w, 1ull << sh);
+    if (!((old >> sh) & 1)) return;                                   // this sighting set plane A
+    old = atomicOr(w, 2ull << sh);
+    if (!((old >> sh) & 2)) return;                                   // ... plane B
+    if (!((old >> sh) & 4)) atomicOr(w, 4ull << sh);                  // ... plane C (or it is set already)
+}
+
+__device__ __forceinline__ bool kdf_pf_admits(const KdfPrefilter &pf, uint64_t cur, uint32_t sh) {
+    return (uint32_t)__popc((uint32_t)(cur >> sh) & 7u) >= pf.min_count;
+}
+
+// wave-reduced window count into a sharded counter (one 128-byte line per shard)
+__device__ __forceinline__ void kdf_pf_add_windows(unsigned long long *windows, uint32_t nwin) {
+    uint32_t n = nwin;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
+    if ((threadIdx.x & 63) == 0 && n)
+        atomicAdd(&windows[((blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)n);
+}
+
+// k <= 63.  One thread = one tile of 64 window starts, the stream read as kdf_stream_kernel reads it (positions at or
+// past n_bases invalid); windows are taken 8 at a time so that 8 sieve words are in flight per
+// lane.  GATE = false: tally (windows: sharded counter of tallied windows).  GATE = true: admit[tile] is written.
+template <int KW, bool GATE>
+__global__ __launch_bounds__(256) void kdf_pf_stream_kernel(
+    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
+    KdfPrefilter pf, unsigned long long *__restrict__ windows, uint64_t *__restrict__ admit)
+{
+    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t nwin = 0;
+    if (tile < n_tiles) {
+        uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
+        kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
+        const uint64_t valid = kdf_valid_windows(m0, m1, k);
+        nwin = __popcll(valid);
+        uint64_t adm = 0;
+        if (valid) {
+            constexpr int NW = KW == 1 ? 3 : 4;
+            uint64_t w[NW];
+#pragma unroll
+            for (int i = 0; i < NW; ++i) w[i] = packed[tile * 2 + i];
+            const uint64_t kmask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
+#pragma unroll
+            for (int b = 0; b < KDF_TILE; b += 8) {
+                if (((valid >> b) & 0xFF) == 0) continue;
+                uint64_t word[8], cur[8]; uint32_t sh[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    uint64_t klo, khi = 0;
+                    if constexpr (KW == 1) klo = kdf_window_narrow((const uint64_t (&)[3])w, b + u, k, kmask);
+                    else kdf_window_wide((const uint64_t (&)[4])w, b + u, k, klo, khi);
+                    kdf_pf_locate(pf, kdf_hash(klo, khi), word[u], sh[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) cur[u] = ((valid >> (b + u)) & 1) ? pf.words[word[u]] : 0ull;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (!((valid >> (b + u)) & 1)) continue;
+                    if constexpr (GATE) { if (kdf_pf_admits(pf, cur[u], sh[u])) adm |= 1ull << (b + u); }
+                    else kdf_pf_bump(&pf.words[word[u]], sh[u], cur[u]);
+                }
+            }
+        }
+        if constexpr (GATE) admit[tile] = adm;
+    }
+    if constexpr (!GATE) kdf_pf_add_windows(windows, nwin);
+}
+
+// long keys (odd k 65..201): the rolling registers and clamped loads of kdf_long_stream_kernel
+template <int W, bool GATE>
+__global__ __launch_bounds__(256) void kdf_pf_long_kernel(
+    const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
+    KdfPrefilter pf, unsigned long long *__restrict__ windows, uint64_t *__restrict__ admit)
+{
+    constexpr int NB = 4;
+    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = tile < n_tiles;
+    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    const uint64_t pw = 2 * T + 4, mw = T + 2;                   // kdf_stream_words(n_bases)
+    const int tb = 2 * k - 64 * (W - 1);
+    uint32_t nwin = 0;
+    uint64_t adm = 0;
+    KdfRoll<W> st;
+#pragma unroll
+    for (int j = 0; j < W; ++j) { st.f[j] = 0; st.r[j] = 0; }
+    st.run = 0;
+    const uint64_t p0 = tile * KDF_TILE;
+    uint64_t curw = 0, curm = ~0ull;
+    int o = 0;
+    auto push = [&]() {
+        if ((o & 31) == 0) { const uint64_t q = 2 * tile + (o >> 5); curw = (active && q < pw) ? packed[q] : 0; }
+        if ((o & 63) == 0) { const uint64_t q = tile + (o >> 6); curm = (active && q < mw) ? invalid[q] : ~0ull; }
+        const bool inv = (curm & 1) || p0 + (uint64_t)o >= n_bases;
+        st.push((uint32_t)(curw & 3), inv, tb);
+        curw >>= 2; curm >>= 1; ++o;
+    };
+    for (int i = 0; i < k - 1; ++i) push();
+    for (int b = 0; b < KDF_TILE; b += NB) {
+        uint64_t word[NB], cur[NB]; uint32_t sh[NB];
+        bool ok[NB];
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            uint64_t key[W];
+            push();                                                // base o - 1 = b + u + k - 1 closes window b + u
+            st.canon(key);
+            ok[u] = active && st.run >= k;
+            if (ok[u]) ++nwin;
+            kdf_pf_locate(pf, kdf_long_hash<W>(key), word[u], sh[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) cur[u] = ok[u] ? pf.words[word[u]] : 0ull;
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            if (!ok[u]) continue;
+            if constexpr (GATE) { if (kdf_pf_admits(pf, cur[u], sh[u])) adm |= 1ull << (b + u); }
+            else kdf_pf_bump(&pf.words[word[u]], sh[u], cur[u]);
+        }
+    }
+    if constexpr (GATE) { if (active) admit[tile] = adm; }
+    else kdf_pf_add_windows(windows, nwin);
+}
+
+// cells by value: out3 += {cells reading >= 1, >= 2, 3} (the planes are nested: B is only set after A, C after B)
+__global__ __launch_bounds__(256) void kdf_pf_fill_kernel(const unsigned long long *__restrict__ words, uint64_t n_words,
+                                                         unsigned long long *__restrict__ out3)
+{
+    unsigned long long a = 0, b = 0, c = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long w = words[i];
+        a += __popcll(w & 0x1111111111111111ull); b += __popcll(w & 0x2222222222222222ull); c += __popcll(w & 0x4444444444444444ull);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); c += __shfl_down(c, o); }
+    if ((threadIdx.x & 63) == 0) {
+        if (a) atomicAdd(&out3[0], a);
+        if (b) atomicAdd(&out3[1], b);
+        if (c) atomicAdd(&out3[2], c);
+    }
+}

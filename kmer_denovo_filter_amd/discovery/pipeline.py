@@ -58,6 +58,47 @@ def _child_key_parts(child_bam, device=0, world=1, kmer_size=31):
     return max(1, int(-(-need // max(1.0, 0.7 * free.value))))
 
 
+def _child_prefilter_min(min_child_count, world):
+    """The L of the two-pass child count, or 0 when it is off: opt-in (``KDF_PREFILTER=1``), one process (a rank of a
+    sharded count sees only its share of the reads: its tallies would under-count), and a dump bound of at least 2.
+    A cell of the sieve saturates at 3, so ``-L 5`` tallies with 3 and dumps with 5."""
+    if os.environ.get("KDF_PREFILTER") != "1" or world != 1 or min_child_count < 2:
+        return 0
+    return min(int(min_child_count), 3)
+
+
+def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start):
+    """`jellyfish bc` + `count --bc` made exact: stream the BAM twice -- tally every window into the counting sieve, arm,
+    count -- so that only k-mers whose cell was seen >= L times get a table slot, each with its full count; then
+    ``dump -L min_child_count`` as usual, one slice.  Returns the candidates (device keys), or None when the sieve plus the
+    table of the admitted keys do not fit the device (the caller then counts in key_parts slices without a prefilter)."""
+    from .. import _native
+    L = _child_prefilter_min(min_child_count, 1)
+    hint = _engine_capacity_hint(jf_hash_size, child_bam)            # distinct k-mers expected, errors included
+    log2_cells = min(38, max(16, (8 * max(int(hint), 1) - 1).bit_length()))
+    with mirror_engine(kmer_size, capacity_hint=1 << 16, device=_device()) as eng:
+        try:
+            eng.prefilter_begin(L, log2_cells)
+            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=True)
+            fill = eng.prefilter_fill()
+            eng.prefilter_arm()
+            eng.reserve(fill[L] + (fill[3] if L == 2 else 0) + 1)    # about one admitted key per cell that reads >= L
+            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+            cap, distinct, windows = eng.stats()
+        except KdfError as e:
+            if e.code != _native.KDF_ERR_NOMEM:
+                raise
+            logger.info("Two-pass child count: a sieve of 2^%d cells plus the table of the admitted k-mers do not fit the device "
+                        "(%s); counting in key-space slices without a prefilter", log2_cells, e)
+            return None
+        logger.info("Child k-mer counting complete (%s, two passes, L=%d, sieve 2^%d cells reading 0/1/2/3: %d/%d/%d/%d, "
+                    "%d of %d windows admitted, %d distinct stored, table %d slots)", _format_elapsed(time.monotonic() - extract_start),
+                    L, log2_cells, fill[0], fill[1], fill[2], fill[3], windows, eng.get_stat("prefilter_windows"), distinct, cap)
+        logger.info("Dumping child k-mers with count >= %d…", min_child_count)
+        dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
+        return devkeys.select([(dlo, dhi)])
+
+
 def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_count, threads, tmpdir,
                                    jf_hash_size=None):
     """Module 1: count every canonical child k-mer, keep count >= min_child_count.
@@ -74,43 +115,50 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     world, rank, host = dist_env.world_rank()
     parts = _child_key_parts(child_bam, _device(), world, kmer_size)
     owner_eng = merger = None
+    dump_start = time.monotonic()
     try:
-        local_hint = max(1, _engine_capacity_hint(jf_hash_size, child_bam) // parts)
-        with mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world) if world > 1 else local_hint, device=_device()) as eng:
-            if world > 1:
-                # one process per GPU: every rank counts its ranges of the BAM into a local table, one owner-partitioned
-                # exchange moves each (k-mer, count) pair to the rank that owns the k-mer, the owner sums -- and `dump -L`
-                # runs on the owners' tables (distributed.OwnerPartitionedCount; SURVEY.md section 8e "full count stage")
-                import torch
-                from ..distributed import EngineOps, OwnerPartitionedCount
-                dev = torch.device("cuda", eng.device)
-                owner_eng = mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
-                merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
-            dev_sets = []
-            if parts > 1:
-                eng.set_option("key_parts", parts)
-            for part in range(parts):
-                if parts > 1:
-                    eng.clear(); eng.set_option("key_part", part)
-                    if owner_eng is not None:
-                        owner_eng.clear()
-                _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
-                cap, distinct, windows = eng.stats()
-                logger.info("Child k-mer counting complete (%s, slice %d of %d, %d windows, %d distinct, table %d slots)",
-                            _format_elapsed(time.monotonic() - extract_start), part + 1, parts, windows, distinct, cap)
-                logger.info("Dumping child k-mers with count >= %d…", min_child_count)
-                dump_start = time.monotonic()
-                # the dump stays in HBM for the next stage (ascending keys: Jellyfish's dump order is not reproducible and
-                # nothing downstream relies on it, but the contract files are then the same bytes on every run)
-                if merger is None:
-                    dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
-                else:
-                    merger.exchange()
-                    dlo, dhi = devkeys.dump_ge(owner_eng, min_child_count, eng.device)
-                    dlo, dhi = dist_env.all_gather_keys(dlo, dhi)           # every rank holds the whole candidate set
-                dev_sets.append((dlo, dhi))
-            cand = devkeys.select(dev_sets)
+        cand = None
+        if _child_prefilter_min(min_child_count, world):
+            cand = _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start)
+        if cand is not None:
             lo, hi = devkeys.to_host(*cand)
+        else:
+            local_hint = max(1, _engine_capacity_hint(jf_hash_size, child_bam) // parts)
+            with mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world) if world > 1 else local_hint, device=_device()) as eng:
+                if world > 1:
+                    # one process per GPU: every rank counts its ranges of the BAM into a local table, one owner-partitioned
+                    # exchange moves each (k-mer, count) pair to the rank that owns the k-mer, the owner sums -- and `dump -L`
+                    # runs on the owners' tables (distributed.OwnerPartitionedCount; SURVEY.md section 8e "full count stage")
+                    import torch
+                    from ..distributed import EngineOps, OwnerPartitionedCount
+                    dev = torch.device("cuda", eng.device)
+                    owner_eng = mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
+                    merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
+                dev_sets = []
+                if parts > 1:
+                    eng.set_option("key_parts", parts)
+                for part in range(parts):
+                    if parts > 1:
+                        eng.clear(); eng.set_option("key_part", part)
+                        if owner_eng is not None:
+                            owner_eng.clear()
+                    _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+                    cap, distinct, windows = eng.stats()
+                    logger.info("Child k-mer counting complete (%s, slice %d of %d, %d windows, %d distinct, table %d slots)",
+                                _format_elapsed(time.monotonic() - extract_start), part + 1, parts, windows, distinct, cap)
+                    logger.info("Dumping child k-mers with count >= %d…", min_child_count)
+                    dump_start = time.monotonic()
+                    # the dump stays in HBM for the next stage (ascending keys: Jellyfish's dump order is not reproducible and
+                    # nothing downstream relies on it, but the contract files are then the same bytes on every run)
+                    if merger is None:
+                        dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
+                    else:
+                        merger.exchange()
+                        dlo, dhi = devkeys.dump_ge(owner_eng, min_child_count, eng.device)
+                        dlo, dhi = dist_env.all_gather_keys(dlo, dhi)           # every rank holds the whole candidate set
+                    dev_sets.append((dlo, dhi))
+                cand = devkeys.select(dev_sets)
+                lo, hi = devkeys.to_host(*cand)
     except KdfError as e:
         raise RuntimeError(f"jellyfish count (child) failed: {e}") from e
     finally:

@@ -9,6 +9,7 @@ shells out to ("External op" table):
     export_ge(n)             jellyfish dump -c -L n             (ascending keys)
     histogram(high)          jellyfish histo -h high
     count_stats()            jellyfish stats
+    prefilter_*()            jellyfish bc + count --bc          (exact: two passes)
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
 
@@ -248,6 +249,41 @@ class KmerEngine:
         self._ck(self._lib.kdf_count_reads_filtered_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid),
                                                         int(n_bases)))
         return self
+
+    # -- two-pass counting (kdf.h "two-pass counting") ----------------------
+    def prefilter_begin(self, min_count: int = 3, log2_cells: int = 0):
+        """Start pass 1: a counting sieve of 2^log2_cells cells (0: sized from the capacity hint).  Tally every batch
+        with prefilter_add*, then prefilter_arm(); the insert-mode counts that follow only store keys whose cell
+        reads >= min_count (2 or 3), with their full counts."""
+        self._ck(self._lib.kdf_prefilter_begin(self._h, int(min_count), int(log2_cells)))
+        return self
+
+    def prefilter_add(self, stream: ReadStream):
+        self._ck(self._lib.kdf_prefilter_add_reads(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases))
+        return self
+
+    def prefilter_add_dev(self, d_packed: int, d_invalid: int, n_bases: int):
+        self._ck(self._lib.kdf_prefilter_add_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases)))
+        return self
+
+    def prefilter_add_uploaded(self, slot: int):
+        """Tally the batch upload_async() put into staging slot 0 / 1."""
+        self._ck(self._lib.kdf_prefilter_add_uploaded(self._h, int(slot)))
+        return self
+
+    def prefilter_arm(self):
+        self._ck(self._lib.kdf_prefilter_arm(self._h))
+        return self
+
+    def prefilter_drop(self):
+        self._ck(self._lib.kdf_prefilter_drop(self._h))
+        return self
+
+    def prefilter_fill(self):
+        """[cells reading 0, 1, 2, 3] of the sieve."""
+        v = (c_uint64 * 4)()
+        self._ck(self._lib.kdf_prefilter_fill(self._h, v))
+        return [int(x) for x in v]
 
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:

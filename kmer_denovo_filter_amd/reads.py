@@ -289,12 +289,13 @@ def _pinned_ring(ring: int, max_bases: int) -> PinnedBatches:
     return pb
 
 
-def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0) -> int:
+def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, tally: bool = False) -> int:
     """Count every batch of ``readers`` (one reader, or several readers of disjoint ranges of one file:
     ``bam_reader(part=, parts=)``) on ``engine`` as a three-stage pipeline: one reader thread PER READER decodes batches
     into pinned buffers (the native reader releases the GIL; inflate, chunking and parsing of the ranges run side by
     side), the copy stream uploads batch i + 1, the engine counts batch i.  Batches arrive in any order: counting does
-    not care.  Returns the number of reads."""
+    not care.  ``tally``: pass 1 of a two-pass count -- every batch goes to the engine's prefilter
+    (``prefilter_add_uploaded``) instead of its table.  Returns the number of reads."""
     import queue
     import threading
     if not isinstance(readers, (list, tuple)):
@@ -326,6 +327,7 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0) ->
     threads = [threading.Thread(target=produce, args=(rd,), name="kdf-reader", daemon=True) for rd in readers]
     for th in threads:
         th.start()
+    take = engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
     pending = None                                           # (slot, buffer) uploaded, not yet counted
     slot = 0
     live = len(threads)
@@ -341,12 +343,12 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0) ->
             engine.upload_async(slot, st)                    # returns at once: the buffer is pinned
             n_reads += st.n_reads
             if pending is not None:
-                engine.count_uploaded(pending[0], filtered)
+                take(pending[0])
                 free.put(pending[1])                         # count_uploaded waited (on the HOST) for this buffer's copy
             pending = (slot, i)
             slot ^= 1
         if pending is not None:
-            engine.count_uploaded(pending[0], filtered)
+            take(pending[0])
             pending = None
     finally:
         stop.set()
