@@ -28,7 +28,7 @@
  *     [i*W, i*W + W)), word 0 the least significant 64 bits.  Engines for such k
  *     take the `_w` entry points below; their (lo, hi) forms return
  *     KDF_ERR_INVALID and name the `_w` form.  The read-stream entry points
- *     (count / count --if / scan, host or device, the double-buffered upload)
+ *     (count / count --if / scan / window counts / read depth, host or device, the double-buffered upload)
  *     work unchanged for every k.  A long engine always counts through the direct
  *     kernels (no binned pipeline, sieve or fused dump: force_path 2 / 4 and
  *     fused_dump 1 are KDF_ERR_INVALID) and is single-GPU only (kdf_export_parts*,
@@ -53,7 +53,8 @@
  *   2. the device forms read at most the kdf_stream_words(n_bases) words of each buffer, so the buffers need be no
  *      longer than that; the host forms read ceil(n_bases / 32) packed and ceil(n_bases / 64) mask words.  The engine
  *      never writes to a caller's stream.
- *   3. kdf_scan_reads*: in hit words 0 .. ceil(n_bases / 64) - 1 every bit at a position > n_bases - k is 0.
+ *   3. kdf_scan_reads*: in hit words 0 .. ceil(n_bases / 64) - 1 every bit at a position > n_bases - k is 0.  The valid
+ *      words of kdf_window_counts* follow the same rule, and kdf_window_counts* / kdf_read_depth* see no window there.
  *   4. kdf_stats' `windows` counts only windows that lie wholly below n_bases.
  */
 #ifndef KDF_H
@@ -101,7 +102,8 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
 
 /* Count calls in insert mode are DEFERRED: a call partitions its batch (or, for small batches, only appends it to a
  * pending stream) and returns; the table itself is updated when something reads it -- kdf_stats, kdf_query*,
- * kdf_count_ge, kdf_histogram*, kdf_count_stats, kdf_export_*, kdf_scan_*, kdf_add_pairs*, kdf_reserve, kdf_set_option
+ * kdf_count_ge, kdf_histogram*, kdf_count_stats, kdf_export_*, kdf_scan_*, kdf_window_counts*, kdf_read_depth*,
+ * kdf_add_pairs*, kdf_reserve, kdf_set_option
  * -- or when the pending work fills its budget, so that a sample streamed in hundreds of batches pays the table rewrite of the binned pipeline
  * once per flush, not once per batch (`jellyfish count` over the whole `samtools fasta` pipe,
  * discovery/pipeline.py:106-172).  kdf_flush applies everything pending now; errors of deferred work (a table that
@@ -140,7 +142,8 @@ int kdf_flush(kdf_engine *h);
  *            "pending_positions", "ring_bytes", "replayed_buckets", "heavy_buckets" (buckets of skewed flushes that
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_merge_path" (1 LDS bucket
- *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
+ *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
+ *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
 int kdf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
@@ -376,6 +379,47 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
                    uint64_t *hit_bits, uint32_t *distinct_out);
 int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid,
                        uint64_t n_bases, void *d_hit_bits);
+
+/* ------------------------------------------- count profile of a stream ---- */
+
+/* `jellyfish query idx -s reads.fa` over a whole read stream: counts_out[i], 0 <= i < n_bases, is the stored count of
+ * the canonical k-mer of window [i, i + k) -- 0 when the key is not stored, when it is stored with count 0 (a
+ * `count --if` filter key never seen) and when the window is not valid; a saturated counter reads 2^32 - 1 as stored.
+ * JellyfishKmerQuery (kmer_utils.py:152-183) runs exactly this query and keeps one bit of it (parts[1] != "0");
+ * kdf_scan_reads* is that bit: (counts_out[i] != 0) == bit i of its hit words, for every i, on every scan path.
+ * valid_bits_out may be NULL; otherwise bit i % 64 of word i / 64 is set iff window i is valid ("Read streams"); it has
+ * the size of a hit array (kdf_stream_words' mask words), words 0 .. ceil(n_bases / 64) - 1 are written and no bit at a
+ * position > n_bases - k is set, whatever the buffers hold at and past n_bases.
+ * The device form writes exactly n_bases counts and reads at most the kdf_stream_words(n_bases) words of each stream
+ * buffer; n_bases == 0 is KDF_OK and writes nothing.  It does not synchronise (stream order, like kdf_scan_reads_dev).
+ * Every key width, insert and filter mode, owner tables (hash_shift); with key_parts set the counts are those of the
+ * slice the table holds (as kdf_histogram).  The table is only read: pending count work is applied first, a loaded
+ * filter's sieve stays valid, an armed prefilter is not consulted, force_path does not matter.
+ * Single GPU: an owner-partitioned table holds a share of the keys and cannot answer alone; a replicated table (the
+ * parent-filter layout) can, with the reads sharded by the caller and no collective. */
+int kdf_window_counts_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                          void *d_counts_out, void *d_valid_bits_out);
+int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                      uint32_t *counts_out, uint64_t *valid_bits_out);
+
+/* The same lookups reduced per read where they are made (no per-position array): rows_out is n_reads x 6 uint64,
+ * row-major: `windows` (valid windows of the read), `present` (of those, count > 0), `low` (of those, count <= low_max;
+ * absent keys count as 0, so they are included), `min`, `max` (over the valid windows, absent = 0; both 0 when
+ * `windows` is 0), `sum` (of the counts, 64-bit, counters summed as stored).  The read-level form of the discovery
+ * chain's per-k-mer filter (child count >= min_child_count, parent count <= parent_max_count,
+ * discovery/pipeline.py:207-226,515-612): how many windows of a read are absent or rare in a parent's table.
+ * read_offsets are the n_reads + 1 stream offsets kdf_pack_reads / kdf_reader_next return: window i belongs to read r
+ * iff offsets[r] <= i < offsets[r + 1] and the window is valid (a valid window never spans a separator).  Positions
+ * below offsets[0], at or above offsets[n_reads] or at or above n_bases belong to no read: a prefix of a longer stream
+ * is allowed.  All fields are integer sums, minima and maxima: the result is bit-identical from run to run and between
+ * the host and device forms.
+ * Host form: n_reads < 0, a negative offset or offsets that decrease are KDF_ERR_INVALID before any device work.
+ * Device form: the offsets are a precondition, but whatever they hold no write lands outside the n_reads rows.
+ * n_reads == 0 is KDF_OK.  Same widths, modes, tables and single-GPU note as kdf_window_counts. */
+int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                       const void *d_read_offsets, int64_t n_reads, uint32_t low_max, void *d_rows_out);
+int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                   const int64_t *read_offsets, int64_t n_reads, uint32_t low_max, uint64_t *rows_out);
 
 /* ------------------------------------------------------- host utilities -- */
 

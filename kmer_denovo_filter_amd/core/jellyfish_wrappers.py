@@ -23,7 +23,7 @@ from .. import dist_env, jf_io
 from .._native import KdfError
 from ..engine import mirror_engine
 from ..kmer_fasta import read_kmer_fasta_keys
-from ..reads import bam_reader, fasta_reader, keys_to_kmers, stream_batches_overlapped
+from ..reads import ReadStream, bam_reader, fasta_reader, keys_to_kmers, stream_batches_overlapped
 
 logger = logging.getLogger(__name__)
 
@@ -336,3 +336,34 @@ def _jellyfish_stats(source, out_path=None):
             fh.write(_format_jellyfish_stats(stats))
         os.replace(tmp, out_path)
     return stats
+
+
+def _jellyfish_query_sequences(source, sequences):
+    """``jellyfish query idx -s reads.fa``: per sequence, the ``(offset, count)`` pairs of its valid windows in offset
+    order -- the windows that hold only A/C/G/T (any case); ``count`` is the stored count of the window's canonical
+    k-mer, 0 when the index does not hold it.  ``source`` is a live ``KmerEngine`` (one pass of ``kdf_window_counts``
+    over all the sequences) or the path of an index file, which is first loaded into a table of its own with
+    ``add_pairs``.  The reference runs this query inside ``JellyfishKmerQuery`` and keeps only ``count != 0``."""
+    sequences = list(sequences)
+    own = None
+    try:
+        if isinstance(source, (str, os.PathLike)):
+            path = os.fspath(source)
+            k = int(jf_io.read_header(path)[0]["key_len"]) // 2
+            own = mirror_engine(k, capacity_hint=max(jf_io.index_records(path), 1), device=_device())
+            jf_io.load_index_into(own, path)
+        eng = own if own is not None else source
+        st = ReadStream.from_strings(sequences)
+        counts, valid = eng.window_counts(st, want_valid=True)
+    except (KdfError, ValueError, OSError) as e:
+        raise RuntimeError(f"jellyfish query failed: {e}") from e
+    finally:
+        if own is not None:
+            own.close()
+    ok = np.unpackbits(valid.view(np.uint8), bitorder="little")[:st.n_bases].astype(bool)
+    out = []
+    for r in range(st.n_reads):
+        a, b = int(st.offsets[r]), int(st.offsets[r + 1])
+        pos = np.flatnonzero(ok[a:b])
+        out.append(list(zip(pos.tolist(), counts[a:b][pos].tolist())))
+    return out

@@ -309,6 +309,8 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 #include "kdf_long.h"
 // the counting sieve of the two-pass count: tally, gate and fill kernels
 #include "kdf_prefilter.h"
+// per-window counts and per-read depth rows of a read stream
+#include "kdf_depth.h"
 
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
@@ -555,6 +557,9 @@ struct kdf_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pf_ev;   // tally kernels under kdf_profile (stats "prefilter_us", "prefilter_passes")
     double prof_pf_ms = 0.0;
     uint64_t prof_pf_passes = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_depth_ev;   // kdf_depth_kernel under kdf_profile (stats "depth_us", "depth_passes")
+    double prof_depth_ms = 0.0;
+    uint64_t prof_depth_passes = 0;
     std::string err;
 };
 
@@ -1471,6 +1476,16 @@ static void pf_prof_collect(kdf_engine *h) {
     h->prof_pf_ev.clear();
 }
 
+static void depth_prof_collect(kdf_engine *h) {
+    for (auto &ev : h->prof_depth_ev) {
+        float ms = 0.f;
+        (void)hipEventSynchronize(ev.second);
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_depth_ms += ms; h->prof_depth_passes++; }
+        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+    }
+    h->prof_depth_ev.clear();
+}
+
 static void pf_free(kdf_engine *h) {
     if (h->pf.words) (void)hipFree(h->pf.words);
     if (h->pf_ctr) (void)hipFree(h->pf_ctr);
@@ -1548,6 +1563,7 @@ void kdf_destroy(kdf_engine *h) {
     table_free(h->t);
     prof_collect(h);
     pf_prof_collect(h);
+    depth_prof_collect(h);
     pf_free(h);
     for (int i = 0; i < 4; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
     for (int i = 0; i < 8; ++i) if (h->kb_buf[i]) (void)hipFree(h->kb_buf[i]);
@@ -2389,6 +2405,110 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     return KDF_OK;
 }
 
+// ------------------------------------------------ count profile of a read stream (kdf_depth.h) ----
+
+// One launch of kdf_depth_kernel over the stream: the per-window form (rows == NULL) or the per-read form.  The table is
+// only read; pending count work is applied first, as the scan does.
+static int depth_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint32_t *d_counts,
+                      unsigned long long *d_valid, const int64_t *d_offs, int64_t n_reads, uint32_t low_max, unsigned long long *d_rows) {
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    { int rc0 = materialize(h); if (rc0) return rc0; }
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    const uint64_t waves = (n_tiles + KD_WAVE_TILES - 1) / KD_WAVE_TILES;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    if (d_rows) HIPCHK(h, hipMemsetAsync(d_rows, 0, (size_t)n_reads * KD_ROW_WORDS * 8, h->stream));
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if (d_rows)
+            hipLaunchKernelGGL((kdf_depth_kernel<W, true>), dim3(blocks), dim3(256), 0, h->stream, d_packed, d_invalid, n_bases, h->k, h->t,
+                               (uint32_t *)nullptr, (unsigned long long *)nullptr, d_offs, n_reads, low_max, d_rows);
+        else
+            hipLaunchKernelGGL((kdf_depth_kernel<W, false>), dim3(blocks), dim3(256), 0, h->stream, d_packed, d_invalid, n_bases, h->k, h->t,
+                               d_counts, d_valid, (const int64_t *)nullptr, (int64_t)0, 0u, (unsigned long long *)nullptr);
+        return 0;
+    });
+    if (d_rows) hipLaunchKernelGGL(kd_rows_fix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, d_rows, n_reads);
+    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_depth_ev.emplace_back(e0, e1); }
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_window_counts_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, void *d_counts_out,
+                          void *d_valid_bits_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_bases == 0) return KDF_OK;
+    if (!d_packed || !d_invalid || !d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_window_counts_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    return depth_pass(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, (uint32_t *)d_counts_out,
+                      (unsigned long long *)d_valid_bits_out, nullptr, 0, 0, nullptr);
+}
+
+int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, uint32_t *counts_out,
+                      uint64_t *valid_bits_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    uint64_t pw, mw;
+    kdf_stream_words(n_bases, &pw, &mw);
+    if (valid_bits_out) memset(valid_bits_out, 0, mw * 8);
+    if (n_bases == 0) return KDF_OK;
+    if (!packed || !invalid || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_window_counts: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
+    if (rc) return rc;
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    if ((rc = stage_reserve(h, 2, n_bases * 4))) return rc;
+    if (valid_bits_out && (rc = stage_reserve(h, 3, n_tiles * 8))) return rc;
+    if ((rc = kdf_window_counts_dev(h, dp, dm, n_bases, h->stage[2], valid_bits_out ? h->stage[3] : nullptr))) return rc;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[2], n_bases * 4, hipMemcpyDeviceToHost, h->stream));
+    if (valid_bits_out) HIPCHK(h, hipMemcpyAsync(valid_bits_out, h->stage[3], n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
+                       int64_t n_reads, uint32_t low_max, void *d_rows_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads == 0) return KDF_OK;
+    if (!d_read_offsets || !d_rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (n_bases == 0) {                                             // no window: every row is zero
+        HIPCHK(h, hipMemsetAsync(d_rows_out, 0, (size_t)n_reads * KD_ROW_WORDS * 8, h->stream));
+        return KDF_OK;
+    }
+    if (!d_packed || !d_invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: NULL stream");
+    return depth_pass(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, nullptr, nullptr,
+                      (const int64_t *)d_read_offsets, n_reads, low_max, (unsigned long long *)d_rows_out);
+}
+
+int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
+                   int64_t n_reads, uint32_t low_max, uint64_t *rows_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads == 0) return KDF_OK;
+    if (!read_offsets || !rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL pointer");
+    if (read_offsets[0] < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: read_offsets[0] = %lld is negative", (long long)read_offsets[0]);
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (read_offsets[r + 1] < read_offsets[r])
+            return fail(h, KDF_ERR_INVALID, "kdf_read_depth: read_offsets decrease at read %lld (%lld after %lld)", (long long)r,
+                        (long long)read_offsets[r + 1], (long long)read_offsets[r]);
+    const size_t row_bytes = (size_t)n_reads * KD_ROW_WORDS * 8;
+    if (n_bases == 0) { memset(rows_out, 0, row_bytes); return KDF_OK; }
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
+    if (rc) return rc;
+    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_depth"))) return rc;
+    if ((rc = stage_reserve(h, 3, row_bytes))) return rc;
+    if ((rc = kdf_read_depth_dev(h, dp, dm, n_bases, h->stage[2], n_reads, low_max, h->stage[3]))) return rc;
+    HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3], row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
 // ---- long keys (odd k 65..201): W-word keys, row-major -----------------------------------------------------------
 #define KDF_NEED_LONG(h, fn) \
     do { if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: takes engines for odd k 65..%d only (k=%d: use the (lo, hi) form)", fn, KDF_LONG_MAX_K, (h)->k); } while (0)
@@ -2596,6 +2716,8 @@ int kdf_profile(kdf_engine *h, int enable) {
     h->prof_histo_ms = 0.0; h->prof_histo_passes = 0;
     pf_prof_collect(h);
     h->prof_pf_ms = 0.0; h->prof_pf_passes = 0;
+    depth_prof_collect(h);
+    h->prof_depth_ms = 0.0; h->prof_depth_passes = 0;
     return KDF_OK;
 }
 
@@ -2699,6 +2821,8 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     }
     else if (n == "prefilter_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pf_ms * 1000.0 + 0.5); }
     else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
+    else if (n == "depth_us") { depth_prof_collect(h); *value = (int64_t)(h->prof_depth_ms * 1000.0 + 0.5); }
+    else if (n == "depth_passes") { depth_prof_collect(h); *value = (int64_t)h->prof_depth_passes; }
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     else if (n == "pending_passes") *value = (int64_t)h->n_pass;
     else if (n == "pending_positions") *value = (int64_t)(h->pend_positions + h->l1_tiles * KDF_TILE);

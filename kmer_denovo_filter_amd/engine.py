@@ -411,6 +411,45 @@ class KmerEngine:
         self._ck(self._lib.kdf_scan_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
                                               c_void_p(d_hits)))
 
+    # -- count profile of a stream -------------------------------------------
+    def window_counts(self, stream: ReadStream, want_valid: bool = False):
+        """`jellyfish query -s reads.fa` over a whole stream: uint32[n_bases], the stored count of the canonical k-mer
+        of every window start (0: absent, stored with count 0, or not a valid window).  ``want_valid``: -> (counts,
+        valid_bits uint64[mask words]) with bit i set iff window i is valid.  Per read: slice with ``stream.offsets``."""
+        counts = np.zeros(stream.n_bases, np.uint32)
+        valid = np.zeros(stream_words(stream.n_bases)[1], np.uint64) if want_valid else None
+        self._ck(self._lib.kdf_window_counts(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases,
+                                             _vp(counts), _vp(valid)))
+        return (counts, valid) if want_valid else counts
+
+    def window_counts_dev(self, d_packed: int, d_invalid: int, n_bases: int, d_counts: int, d_valid: Optional[int] = None):
+        """The same between device buffers (raw pointers): n_bases uint32 counts, and ceil(n_bases / 64) valid words
+        when ``d_valid`` is given.  Stream order on the engine's stream; does not synchronise."""
+        self._ck(self._lib.kdf_window_counts_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
+                                                 c_void_p(d_counts), c_void_p(d_valid) if d_valid else None))
+
+    def read_depth(self, stream: ReadStream, low_max: int = 0) -> np.ndarray:
+        """Per-read summary of the window counts: uint64 (n_reads, 6), columns ``READ_DEPTH_COLUMNS`` -- valid
+        windows, of those with count > 0, of those with count <= ``low_max`` (absent keys included), min, max and sum
+        of the counts over the valid windows (absent = 0; min = max = 0 for a read without windows)."""
+        if not 0 <= int(low_max) <= 0xFFFFFFFF:
+            raise ValueError(f"low_max={low_max} outside 0..2^32 - 1")
+        rows = np.zeros((stream.n_reads, len(READ_DEPTH_COLUMNS)), np.uint64)
+        offs = np.ascontiguousarray(stream.offsets, dtype=np.int64)
+        self._ck(self._lib.kdf_read_depth(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases, _vp(offs),
+                                          stream.n_reads, int(low_max), _vp(rows)))
+        return rows
+
+    def read_depth_dev(self, d_packed: int, d_invalid: int, n_bases: int, d_offsets: int, n_reads: int, low_max: int,
+                       d_rows: int):
+        """The same between device buffers: ``d_offsets`` int64[n_reads + 1], ``d_rows`` uint64[n_reads x 6]."""
+        self._ck(self._lib.kdf_read_depth_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
+                                              c_void_p(d_offsets), int(n_reads), int(low_max), c_void_p(d_rows)))
+
+
+# columns of KmerEngine.read_depth's rows
+READ_DEPTH_COLUMNS = ("windows", "present", "low", "min", "max", "sum")
+
 
 def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:
     """The engine the reference-interface mirrors (discovery chain, Module 3, the Jellyfish wrappers) count with.

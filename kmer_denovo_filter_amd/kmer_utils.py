@@ -251,6 +251,25 @@ class JellyfishKmerQuery:
             self._cache[c] = True
         return unique_in_read, set(pos.tolist())
 
+    def query_read(self, seq, kmer_size):
+        """The count under every window of one read, what ``jellyfish query idx -s read.fa`` prints and the reference
+        reduces to ``parts[1] != "0"``: a list of ``len(seq) - kmer_size + 1`` entries, the stored count of the
+        window's canonical k-mer (0 when absent) or ``None`` for a window that holds a base other than A/C/G/T (any
+        case) -- Jellyfish prints no line for those.  ``[]`` for a read shorter than k.  One launch over the read."""
+        if len(seq) < kmer_size:
+            return []
+        eng = self._ensure_engine()
+        if kmer_size != eng.k:
+            raise RuntimeError(f"jellyfish query failed: index has k={eng.k}, asked for k={kmer_size}")
+        st = ReadStream.from_strings([seq])
+        try:
+            counts, valid = eng.window_counts(st, want_valid=True)
+        except KdfError as e:
+            raise RuntimeError(f"jellyfish query failed: {e}") from e
+        n = len(seq) - kmer_size + 1
+        ok = np.unpackbits(valid.view(np.uint8), bitorder="little")[:n]
+        return [int(c) if v else None for c, v in zip(counts[:n].tolist(), ok.tolist())]
+
     def close(self):
         """Clear the result cache (reference :240-242); the table stays resident."""
         self._cache.clear()
