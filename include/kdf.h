@@ -88,13 +88,18 @@ void kdf_destroy(kdf_engine *h);
 const char *kdf_last_error(const kdf_engine *h);
 
 /* Use an externally created hipStream_t (e.g. torch's current stream) for all
- * subsequent launches; NULL restores the engine's own stream. */
+ * subsequent launches; NULL restores the engine's own stream.  Pending count work is applied and the old stream
+ * synchronised first, so nothing of the engine's is left in flight on it; table, mode, options, upload slots and the
+ * prefilter (tallying or armed) carry over unchanged. */
 int kdf_set_stream(kdf_engine *h, void *hip_stream);
 int kdf_synchronize(kdf_engine *h);
 
-/* Empty the table (all keys and counts dropped). */
+/* Empty the table (all keys and counts dropped): `windows` is 0, the engine is back in insert mode (a loaded filter is
+ * gone), pending count work is dropped.  Options keep their values, and so do the upload slots and the prefilter:
+ * cleared while TALLYING it goes on tallying with the tallies it has, cleared while armed it stays armed. */
 int kdf_clear(kdf_engine *h);
-/* Make room for at least n_keys distinct keys (rehashes the live entries). */
+/* Make room for at least n_keys distinct keys (rehashes the live entries).  Pending count work is applied first; the
+ * contents, `windows` and the mode do not change, and a table never shrinks. */
 int kdf_reserve(kdf_engine *h, uint64_t n_keys);
 /* capacity in slots, distinct keys currently stored, valid windows processed
  * by the count calls since the last clear.  Any pointer may be NULL. */
@@ -129,9 +134,11 @@ int kdf_flush(kdf_engine *h);
  *            called while partition passes are pending is written by the flush that applies them -- kernel C dumps every
  *            bucket it holds -- instead of by a pass over the table afterwards; falls back to that pass when a bucket
  *            overflowed or was split as heavy; env KDF_FUSED_DUMP=1 sets the default);
- *            "hash_shift" (0..8, empty table only: the home slot ignores that many top hash bits -- the table of
- *            an OWNER rank of the multi-GPU merge, see kdf_add_pairs_multi_dev; such an engine counts through the
- *            direct kernels only); "merge_min_pairs" (below this many pairs kdf_add_pairs* skips the bucket merge);
+ *            "hash_shift" (0..8: the home slot ignores that many top hash bits -- the table of an OWNER rank of the
+ *            multi-GPU merge, see kdf_add_pairs_multi_dev; such an engine counts through the direct kernels only.  It
+ *            changes on an empty table only, KDF_ERR_STATE otherwise: a table is empty after kdf_clear and after
+ *            kdf_load_filter* of zero keys, and is not while it holds keys whose counts kdf_reset_counts zeroed);
+ *            "merge_min_pairs" (below this many pairs kdf_add_pairs* skips the bucket merge);
  *            "big_bucket_log2cap" (default 32; KDF_BIG_BUCKET_LOG2CAP: tables of 2^that slots and more have buckets of
  *            twice the slots -- an internal layout: dumps, queries and index files do not depend on it; a live table
  *            is re-bucketed when the option changes its bucket size); "debug_flags" (experiments: 64 one piece per
@@ -180,7 +187,13 @@ int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_inval
  * device staging slot 0 or 1 on a copy stream of the engine's own and returns at once when the host arrays are pinned
  * (kdf_host_alloc; pageable arrays work too, the copy is then synchronous); kdf_count_uploaded counts the batch a
  * slot holds (filtered != 0: count --if) on the engine's stream.  Upload batch i + 1, then count batch i: the copy
- * runs under the count.  The host arrays of a batch may be rewritten once kdf_count_uploaded for THAT batch returned. */
+ * runs under the count.  The host arrays of a batch may be rewritten once kdf_count_uploaded for THAT batch returned.
+ * A slot holds its batch until a count or a prefilter tally takes it: kdf_count_uploaded on a slot that holds none is
+ * KDF_ERR_STATE, and a call refused for the engine's state (count with a filter loaded or while the prefilter is tallying,
+ * count --if without a filter or under force_path 4 without a sieve) leaves the batch in the slot.  An empty batch
+ * (n_bases = 0) asks nothing of the sieve, here as in kdf_count_reads_filtered*: it is KDF_OK under force_path 4 too.  kdf_clear,
+ * kdf_load_filter* and kdf_set_stream do not touch the slots: a batch uploaded before kdf_set_stream is counted on the new
+ * stream, after its copy. */
 int kdf_host_alloc(uint64_t bytes, void **out);
 int kdf_host_free(void *p);
 int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, const uint64_t *invalid,
@@ -191,7 +204,11 @@ int kdf_count_uploaded(kdf_engine *h, int slot, int filtered);
  * NULL adds 0, i.e. plain insertion).  Loads an on-disk index into the table
  * (`jellyfish query` mmaps the .jf; discovery/pipeline.py:286-288) and merges
  * per-GPU partial counts after the owner-partitioned exchange (`jellyfish
- * merge`, core/jellyfish_wrappers.py:335-366). */
+ * merge`, core/jellyfish_wrappers.py:335-366).  A key that occurs twice in one call gains both counts; sums saturate at
+ * 2^32 - 1.  Works in insert and in filter mode, is never gated by key_parts or an armed prefilter, and leaves `windows`
+ * alone.  Keys added while a filter is loaded are filter keys like the others (kdf_count_reads_filtered* counts them on
+ * every path); the filter's sieve does not know them, so option force_path 4 is KDF_ERR_STATE from then on, until
+ * kdf_scan_reads* has rebuilt the sieve from the table or a filter is loaded again. */
 int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi,
                   const uint32_t *counts, uint64_t n);
 int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi,
@@ -263,7 +280,9 @@ int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]);
 
 /* Load the `--if` filter: the table becomes exactly these canonical keys with
  * count 0 (core/jellyfish_wrappers.py:173, discovery/pipeline.py:383).  Keys
- * must already be canonical (the reference's filter files are). */
+ * must already be canonical (the reference's filter files are).  Whatever the table held is gone, pending count work
+ * included; kdf_stats' `windows` reads 0; a key given twice is stored once; n = 0 loads the empty filter (filter mode, no
+ * keys).  Options, the upload slots and the prefilter are not touched. */
 int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi,
                     uint64_t n);
 /* The same with the keys already resident in HBM (device pointers): the hand-off between the discovery stages
@@ -271,7 +290,11 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
  * without a host round trip. */
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n);
 /* Zero every count, keep the keys (and the filter mode): the same filter counted against the next parent
- * (discovery/pipeline.py:462-612 builds a fresh --if table per parent). */
+ * (discovery/pipeline.py:462-612 builds a fresh --if table per parent).  `windows` reads 0 and pending count --if work is
+ * dropped (its counts would be zeroed anyway).  In insert mode pending count work is applied first, since it brings keys,
+ * and then the same happens: the keys stay stored with count 0 -- they are in kdf_count_ge(h, 0) and in bin 0 of the
+ * histogram, kdf_scan_reads* does not hit them, "hash_shift" still sees a table that holds keys -- and the next counts
+ * add to them. */
 int kdf_reset_counts(kdf_engine *h);
 /* `jellyfish count -C --if`: only windows whose canonical k-mer is in the table
  * are counted; nothing is inserted.  Replaces _scan_parent_jellyfish

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void kdf_stream_kernel(
     if ((threadIdx.x & 63) == 0) {
         const int shard = (blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS;
         if (c) atomicAdd(&ctl->distinct[shard * 16], (unsigned long long)c);
-        if (n) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);
+        if (n && MODE != MODE_SCAN) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);   // (a scan counts nothing: kdf_stats' windows are the count calls')
     }
 }
 
@@ -1717,7 +1717,12 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
 int kdf_count_uploaded(kdf_engine *h, int slot, int filtered) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: nothing was uploaded into slot %d", slot);
-    if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);      // (the slot keeps its batch)
+    // (a call refused for the engine's state keeps the slot's batch: a refused call changes nothing)
+    if (!filtered && h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: a filter is loaded; call kdf_clear first");
+    if (filtered && !h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: no filter loaded (kdf_load_filter)");
+    if (filtered && h->up_n[slot] && h->opt_force_path == 4 && !h->sieve_valid)      // (an empty batch asks nothing of the sieve: kdf_count_reads_filtered*)
+        return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: force_path 4 (sieve): no sieve for this filter (keys were added after kdf_load_filter)");
+    if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
     HIPCHK(h, hipSetDevice(h->device));
     h->up_valid[slot] = false;
     const uint64_t n = h->up_n[slot];
@@ -1834,7 +1839,9 @@ int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys
 int kdf_reset_counts(kdf_engine *h) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = pending_drop(h);                         // counts that were never applied need not be
+    // filter mode: counts that were never applied need not be.  Insert mode: pending windows also bring KEYS, and the keys
+    // stay -- what the table holds afterwards must not depend on whether a flush happened to come first.
+    int rc = h->filter_mode ? pending_drop(h) : pending_flush(h);
     if (rc) return rc;
     if ((rc = materialize(h))) return rc;
     HIPCHK(h, hipMemsetAsync(h->t.cnt, 0, h->cap * 4, h->stream));

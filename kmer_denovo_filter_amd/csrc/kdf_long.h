@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
     if ((threadIdx.x & 63) == 0) {
         const int shard = (blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS;
         if (c) atomicAdd(&ctl->distinct[shard * 16], (unsigned long long)c);
-        if (n) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);
+        if (n && MODE != MODE_SCAN) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);   // (a scan counts nothing)
     }
 }
 
