@@ -107,8 +107,8 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
 
 /* Count calls in insert mode are DEFERRED: a call partitions its batch (or, for small batches, only appends it to a
  * pending stream) and returns; the table itself is updated when something reads it -- kdf_stats, kdf_query*,
- * kdf_count_ge, kdf_histogram*, kdf_count_stats, kdf_export_*, kdf_scan_*, kdf_window_counts*, kdf_read_depth*,
- * kdf_add_pairs*, kdf_reserve, kdf_set_option
+ * kdf_count_ge, kdf_histogram*, kdf_count_stats, kdf_export_*, kdf_scan_*, kdf_read_hits*, kdf_window_counts*,
+ * kdf_read_depth*, kdf_add_pairs*, kdf_reserve, kdf_set_option
  * -- or when the pending work fills its budget, so that a sample streamed in hundreds of batches pays the table rewrite of the binned pipeline
  * once per flush, not once per batch (`jellyfish count` over the whole `samtools fasta` pipe,
  * discovery/pipeline.py:106-172).  kdf_flush applies everything pending now; errors of deferred work (a table that
@@ -150,7 +150,9 @@ int kdf_flush(kdf_engine *h);
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
- *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
+ *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
+ *            "hits_us" / "hits_passes" (the kh_* kernels of kdf_read_hits* / kdf_hit_list* under kdf_profile, the scan kernel
+ *            not included; one pass per call); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
 int kdf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
@@ -402,6 +404,50 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
                    uint64_t *hit_bits, uint32_t *distinct_out);
 int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid,
                        uint64_t n_bases, void *d_hit_bits);
+
+/* ------------------------------------- per-read hits of the Module-3 scan ---- */
+
+/* The scan and its per-read reduction without leaving the device: what Module 3 filters on
+ * (len(unique_in_read) >= min_distinct_kmers_per_read, core/bam_scanner.py:435-442).  rows_out is n_reads x 2 uint32,
+ * row-major: `hits` (valid windows of the read whose canonical key is stored with count > 0) and `distinct` (distinct
+ * canonical keys among those windows).  A window belongs to a read by the rule of kdf_read_depth: window i belongs to
+ * read r iff offsets[r] <= i < offsets[r + 1]; positions below offsets[0], at or past offsets[n_reads] or at or past
+ * n_bases belong to no read, so a prefix of a longer stream is allowed.  hit_bits may be NULL; otherwise it receives
+ * exactly what kdf_scan_reads* writes (the same words, the same tail rule: "Read streams" point 3; the device form
+ * writes words 0 .. ceil(n_bases / 64) - 1, the host form zeroes all kdf_stream_words' mask words first).
+ * Contract:
+ *   - hits[r] equals column `present` of kdf_read_depth*, distinct[r] equals distinct_out[r] of kdf_scan_reads, and
+ *     distinct <= hits.  A key stored with count 0 is no hit.
+ *   - every key width (k <= 32, 33..63, long engines), insert and filter mode, owner tables (hash_shift); with
+ *     key_parts set the hits are those of the slice the table holds.
+ *   - the table is only read: pending count work is applied first and a loaded filter's sieve stays valid.  The bits
+ *     come from the scan (the sieve, or the direct kernel under force_path 1); the result does not depend on which.
+ *   - exact for a read of any length (a whole contig as one read), work linear in the number of hits: the hit mask is
+ *     compacted to a position list and each hit puts the pair (read, table slot of its key) into a scratch set in HBM.
+ *     The engine owns that scratch and keeps it between calls: 8 bytes per hit for the list, 16 to 32 for the set
+ *     (KDF_ERR_NOMEM when it does not fit).  Read index and slot index must fit 63 bits together: n_reads <=
+ *     2^(63 - log2cap), KDF_ERR_INVALID beyond (never hashed down inexactly).  hits[r] is reported modulo 2^32.
+ *   - n_reads == 0 and n_bases == 0 are KDF_OK (n_bases == 0: rows zero, no hit word written).
+ *   - host form: n_reads < 0, a negative offset and decreasing offsets are KDF_ERR_INVALID before any device work.
+ *     Device form: the offsets are a precondition, but whatever they hold no write lands outside the n_reads rows.
+ *   - all results are integer counts: bit-identical from run to run and between the host and device forms.
+ *   - the device form SYNCHRONISES the engine's stream once (it learns the number of hits to size its scratch); the
+ *     rows are complete in stream order when it returns. */
+int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                      const void *d_read_offsets, int64_t n_reads, void *d_hit_bits, void *d_rows_out);
+int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                  const int64_t *read_offsets, int64_t n_reads, uint64_t *hit_bits, uint32_t *rows_out);
+
+/* The set bits of a hit mask (usually the one kdf_read_hits* just wrote) below n_bases as a list: positions_out[e] is
+ * the position of the e-th set bit, ASCENDING, uint64.  When reads_out is non-NULL, reads_out[e] (int64) is the read
+ * that holds the position by the rule above, or -1 for none; read_offsets may be NULL exactly when reads_out is NULL.
+ * *n_out = number of set bits.  At most `cap` entries are written; when *n_out exceeds cap the call returns
+ * KDF_ERR_INVALID with *n_out set (the convention of kdf_export_ge_dev).  The table is not touched (no flush).  Both
+ * forms synchronise the engine's stream. */
+int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets,
+                     int64_t n_reads, void *d_positions_out, void *d_reads_out, uint64_t cap, uint64_t *n_out);
+int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets,
+                 int64_t n_reads, uint64_t *positions_out, int64_t *reads_out, uint64_t cap, uint64_t *n_out);
 
 /* ------------------------------------------- count profile of a stream ---- */
 

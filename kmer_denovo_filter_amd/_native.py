@@ -60,6 +60,10 @@ SYMBOLS = [
     ("kdf_export_parts_packed_dev", c_int, [_P, c_uint32, c_uint32, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_scan_reads", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P]),
     ("kdf_scan_reads_dev", c_int, [_P, _P, _P, c_uint64, _P]),
+    ("kdf_read_hits_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P]),
+    ("kdf_read_hits", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P]),
+    ("kdf_hit_list_dev", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_hit_list", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),

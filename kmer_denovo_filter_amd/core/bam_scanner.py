@@ -86,6 +86,24 @@ def _init_scan_worker(proband_data, kmer_size, min_distinct_kmers_per_read=1, de
     _worker_min_distinct_kmers_per_read = min_distinct_kmers_per_read
 
 
+def _scan_batch(eng: KmerEngine, batch):
+    """One batch through the probe -> (distinct uint32[n_reads], hits_of(r) -> int64 query start indices of read r's
+    hit windows).  Default: ``KmerEngine.scan`` (the mask comes back, the engine's host loop counts the distinct
+    k-mers).  ``KDF_DEVICE_HITS=1``, read here at every call: ``KmerEngine.scan_hits`` -- the per-read rows and the
+    compacted hit list are made on the device and only they come back.  Same values either way."""
+    offs = batch.offsets
+    if os.environ.get("KDF_DEVICE_HITS") == "1":
+        rows, pos = eng.scan_hits(batch)
+
+        def hits_of(r):
+            s = int(offs[r])
+            a, b = np.searchsorted(pos, (s, int(offs[r + 1]) - 1))
+            return pos[a:b] - s
+        return rows[:, 1], hits_of
+    hits, distinct = eng.scan(batch)
+    return distinct, lambda r: hit_positions(hits, int(offs[r]), int(offs[r + 1]) - 1)
+
+
 def scan_bam_for_hits(child_bam, engine: Optional[KmerEngine] = None, min_dk_per_read: Optional[int] = None,
                       batch_bases: int = SCAN_BATCH_BASES) -> Iterator[Tuple[int, List[InformativeRead]]]:
     """Scan every non-SECONDARY, non-DUPLICATE record (supplementary kept, no
@@ -99,14 +117,13 @@ def scan_bam_for_hits(child_bam, engine: Optional[KmerEngine] = None, min_dk_per
                     max_reads=1 << 20, threads=READER_THREADS, want_meta=True) as rd:
         for batch in rd:
             try:
-                hits, distinct = eng.scan(batch)
+                distinct, hits_of = _scan_batch(eng, batch)
             except KdfError as e:
                 raise RuntimeError(f"jellyfish query failed: {e}") from e
             out = []
             for r in np.flatnonzero(distinct >= max(min_dk, 1)).tolist():
-                s, e_ = int(batch.offsets[r]), int(batch.offsets[r + 1]) - 1
                 out.append(InformativeRead(batch.name(r), int(batch.flags[r]), int(batch.ref_ids[r]),
-                                           int(batch.positions[r]), hit_positions(hits, s, e_),
+                                           int(batch.positions[r]), hits_of(r),
                                            int(distinct[r])))
             if min_dk <= 0:
                 # reference: `len(unique_in_read) < min_dk_per_read` never true for 0 -> every read kept
@@ -261,13 +278,12 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
         for batch in rd:
             total_scanned += batch.n_reads
             try:
-                hits, distinct = eng.scan(batch)
+                distinct, hits_of = _scan_batch(eng, batch)
             except KdfError as e:
                 raise RuntimeError(f"jellyfish query failed: {e}") from e
             keep = np.flatnonzero(distinct >= min_dk) if min_dk > 0 else np.arange(batch.n_reads)
             for r in keep.tolist():
-                s, e_ = int(batch.offsets[r]), int(batch.offsets[r + 1]) - 1
-                idx = hit_positions(hits, s, e_)
+                idx = hits_of(r)
                 seq = _decode_read(batch, r)
                 rec = {
                     "name": batch.name(r), "flag": int(batch.flags[r]), "ref_id": int(batch.ref_ids[r]),

@@ -311,6 +311,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 #include "kdf_prefilter.h"
 // per-window counts and per-read depth rows of a read stream
 #include "kdf_depth.h"
+#include "kdf_hits.h"
 
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
@@ -560,6 +561,13 @@ struct kdf_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_depth_ev;   // kdf_depth_kernel under kdf_profile (stats "depth_us", "depth_passes")
     double prof_depth_ms = 0.0;
     uint64_t prof_depth_passes = 0;
+    // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
+    void *hit_buf[4] = {nullptr, nullptr, nullptr, nullptr};    // 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
+    size_t hit_bytes[4] = {0, 0, 0, 0};
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_hits_ev;    // the kh_* kernels under kdf_profile (stats "hits_us", "hits_passes")
+    std::vector<bool> prof_hits_first;                              // the pair opens a call (a call that finds hits records two pairs)
+    double prof_hits_ms = 0.0;
+    uint64_t prof_hits_passes = 0;
     std::string err;
 };
 
@@ -1486,6 +1494,17 @@ static void depth_prof_collect(kdf_engine *h) {
     h->prof_depth_ev.clear();
 }
 
+static void hits_prof_collect(kdf_engine *h) {
+    for (size_t i = 0; i < h->prof_hits_ev.size(); ++i) {
+        auto &ev = h->prof_hits_ev[i];
+        float ms = 0.f;
+        (void)hipEventSynchronize(ev.second);
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_hits_ms += ms; if (h->prof_hits_first[i]) h->prof_hits_passes++; }
+        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+    }
+    h->prof_hits_ev.clear(); h->prof_hits_first.clear();
+}
+
 static void pf_free(kdf_engine *h) {
     if (h->pf.words) (void)hipFree(h->pf.words);
     if (h->pf_ctr) (void)hipFree(h->pf_ctr);
@@ -1564,8 +1583,10 @@ void kdf_destroy(kdf_engine *h) {
     prof_collect(h);
     pf_prof_collect(h);
     depth_prof_collect(h);
+    hits_prof_collect(h);
     pf_free(h);
     for (int i = 0; i < 4; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
+    for (int i = 0; i < 4; ++i) if (h->hit_buf[i]) (void)hipFree(h->hit_buf[i]);
     for (int i = 0; i < 8; ++i) if (h->kb_buf[i]) (void)hipFree(h->kb_buf[i]);
     if (h->l1_packed) (void)hipFree(h->l1_packed);
     if (h->l1_mask) (void)hipFree(h->l1_mask);
@@ -2516,6 +2537,205 @@ int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     return KDF_OK;
 }
 
+// ------------------------------------------------ per-read hits of the scan (kdf_hits.h) ----
+
+static int hits_reserve(kdf_engine *h, int i, size_t bytes, const char *what) {
+    if (h->hit_bytes[i] >= bytes) return KDF_OK;
+    if (h->hit_buf[i]) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->hit_buf[i]); h->hit_buf[i] = nullptr; h->hit_bytes[i] = 0; }
+    const size_t want = bytes + bytes / 8 + 4096;
+    const hipError_t e = hipMalloc(&h->hit_buf[i], want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "the %s of the hit reduction (%.2f GB) does not fit the device (%s)",
+                    what, (double)want / 1e9, hipGetErrorString(e));
+    }
+    h->hit_bytes[i] = want;
+    return KDF_OK;
+}
+
+struct HitsProf {                                     // HIP events around a group of kh_* launches under kdf_profile
+    kdf_engine *h; hipEvent_t e0 = nullptr, e1 = nullptr; bool first;
+    HitsProf(kdf_engine *h_, bool first_) : h(h_), first(first_) {
+        if (h->prof && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, h->stream);
+    }
+    void stop() {
+        if (!e1) return;
+        (void)hipEventRecord(e1, h->stream);
+        h->prof_hits_ev.emplace_back(e0, e1); h->prof_hits_first.push_back(first);
+        e0 = e1 = nullptr;
+    }
+};
+
+// Steps 1-2 of kdf_hits.h over the mask words of n_bases positions (n_bases >= 1): hit_buf[1] then holds the exclusive
+// prefix of every block of KH_BLOCK_WORDS words and, behind them, the number of set bits below n_bases.
+static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, uint64_t *n_blocks_out) {
+    const uint64_t n_words = (n_bases + 63) / 64;
+    const uint64_t n_blocks = (n_words + KH_BLOCK_WORDS - 1) / KH_BLOCK_WORDS;
+    if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "a hit mask of %llu positions is beyond the 2^47 a call takes", (unsigned long long)n_bases);
+    int rc = hits_reserve(h, 1, (n_blocks + 1) * 8, "block sums");
+    if (rc) return rc;
+    unsigned long long *sums = (unsigned long long *)h->hit_buf[1];
+    hipLaunchKernelGGL(kh_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_bits, n_bases, sums);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
+    HIPCHK(h, hipGetLastError());
+    *n_blocks_out = n_blocks;
+    return KDF_OK;
+}
+
+// the total hits_count left, on the host (synchronises)
+static int hits_total(kdf_engine *h, uint64_t n_blocks, uint64_t *n_hits) {
+    HIPCHK(h, hipMemcpyAsync(h->h_out4, (unsigned long long *)h->hit_buf[1] + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *n_hits = h->h_out4[0];
+    return KDF_OK;
+}
+
+int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
+                      int64_t n_reads, void *d_hit_bits, void *d_rows_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads > 0 && (!d_read_offsets || !d_rows_out)) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t row_bytes = (size_t)n_reads * KH_ROW_WORDS * 4;
+    if (n_bases == 0) {                                             // no window: every row is zero, no hit word is written
+        if (n_reads) HIPCHK(h, hipMemsetAsync(d_rows_out, 0, row_bytes, h->stream));
+        return KDF_OK;
+    }
+    if (!d_packed || !d_invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: NULL stream");
+    int rc;
+    uint64_t *bits = (uint64_t *)d_hit_bits;
+    if (!bits) {
+        if ((rc = hits_reserve(h, 0, (n_bases + 63) / 64 * 8, "hit mask"))) return rc;
+        bits = (uint64_t *)h->hit_buf[0];
+    }
+    if ((rc = kdf_scan_reads_dev(h, d_packed, d_invalid, n_bases, bits))) return rc;     // (applies pending count work)
+    if (n_reads == 0) return KDF_OK;
+    // a (read, slot) pair must fit 63 bits: bit 63 keeps every pair apart from the set's empty word
+    if (log2ceil((uint64_t)n_reads) + h->t.log2cap > 63)
+        return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: %lld reads against a table of 2^%u slots: read index and slot index must fit 63 bits "
+                    "together (at most 2^%u reads per call for this table)", (long long)n_reads, h->t.log2cap, 63 - h->t.log2cap);
+    uint64_t n_blocks = 0, n_hits = 0;
+    HitsProf p1(h, true);
+    HIPCHK(h, hipMemsetAsync(d_rows_out, 0, row_bytes, h->stream));
+    if ((rc = hits_count(h, bits, n_bases, &n_blocks))) return rc;
+    p1.stop();
+    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
+    if (n_hits == 0) return KDF_OK;
+    uint32_t log2set = log2ceil(2 * n_hits);
+    if ((rc = hits_reserve(h, 2, n_hits * 8, "hit list"))) return rc;
+    if ((rc = hits_reserve(h, 3, (size_t)8 << log2set, "set of (read, k-mer) pairs"))) return rc;
+    uint64_t *pos = (uint64_t *)h->hit_buf[2];
+    unsigned long long *set = (unsigned long long *)h->hit_buf[3];
+    const int64_t *offs = (const int64_t *)d_read_offsets;
+    HitsProf p2(h, false);
+    HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
+    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, (const unsigned long long *)h->hit_buf[1],
+                       pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
+    hipLaunchKernelGGL(kh_hits_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads,
+                       (uint32_t *)d_rows_out);
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        hipLaunchKernelGGL(kh_distinct_kernel<W>, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_packed, n_bases,
+                           h->k, h->t, pos, n_hits, offs, n_reads, set, log2set, (uint32_t *)d_rows_out);
+        return 0;
+    });
+    p2.stop();
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+// n_reads >= 0, offsets[0] >= 0 and no decrease, or KDF_ERR_INVALID (the host forms check before any device work)
+static int hits_check_offsets(kdf_engine *h, const char *fn, const int64_t *read_offsets, int64_t n_reads) {
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "%s: n_reads = %lld is negative", fn, (long long)n_reads);
+    if (n_reads == 0) return KDF_OK;
+    if (!read_offsets) return fail(h, KDF_ERR_INVALID, "%s: read_offsets is NULL", fn);
+    if (read_offsets[0] < 0) return fail(h, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld is negative", fn, (long long)read_offsets[0]);
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (read_offsets[r + 1] < read_offsets[r])
+            return fail(h, KDF_ERR_INVALID, "%s: read_offsets decrease at read %lld (%lld after %lld)", fn, (long long)r,
+                        (long long)read_offsets[r + 1], (long long)read_offsets[r]);
+    return KDF_OK;
+}
+
+int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
+                  int64_t n_reads, uint64_t *hit_bits, uint32_t *rows_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    int rc = hits_check_offsets(h, "kdf_read_hits", read_offsets, n_reads);
+    if (rc) return rc;
+    if (n_reads > 0 && !rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: rows_out is NULL");
+    uint64_t pw, mw;
+    kdf_stream_words(n_bases, &pw, &mw);
+    const size_t row_bytes = (size_t)n_reads * KH_ROW_WORDS * 4;
+    if (hit_bits) memset(hit_bits, 0, mw * 8);
+    if (n_bases == 0) { if (n_reads) memset(rows_out, 0, row_bytes); return KDF_OK; }
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: NULL stream");
+    if (n_reads == 0 && !hit_bits) return KDF_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
+    if (n_reads) {
+        if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_hits"))) return rc;
+        if ((rc = stage_reserve(h, 3, row_bytes))) return rc;
+    }
+    if ((rc = kdf_read_hits_dev(h, dp, dm, n_bases, n_reads ? h->stage[2] : nullptr, n_reads, nullptr, n_reads ? h->stage[3] : nullptr))) return rc;
+    if (n_reads) HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3], row_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0], (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets, int64_t n_reads,
+                     void *d_positions_out, void *d_reads_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: NULL pointer");
+    *n_out = 0;
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (d_reads_out && !d_read_offsets) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: reads_out needs read_offsets");
+    if (n_bases == 0) return KDF_OK;
+    if (!d_hit_bits || (cap && !d_positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t n_blocks = 0, n_hits = 0;
+    int rc;
+    HitsProf p(h, true);
+    if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_bases, &n_blocks))) return rc;
+    if (cap)
+        hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_bases,
+                           (const unsigned long long *)h->hit_buf[1], (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
+                           (const int64_t *)d_read_offsets, n_reads, cap);
+    p.stop();
+    HIPCHK(h, hipGetLastError());
+    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
+    *n_out = n_hits;
+    if (n_hits > cap)
+        return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: the mask holds %llu hits, the buffers %llu", (unsigned long long)n_hits, (unsigned long long)cap);
+    return KDF_OK;
+}
+
+int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets, int64_t n_reads,
+                 uint64_t *positions_out, int64_t *reads_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
+    *n_out = 0;
+    if (reads_out && !read_offsets) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: reads_out needs read_offsets");
+    int rc = hits_check_offsets(h, "kdf_hit_list", read_offsets, read_offsets ? n_reads : (n_reads < 0 ? n_reads : 0));
+    if (rc) return rc;
+    if (n_bases == 0) return KDF_OK;
+    if (!hit_bits || (cap && !positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_list"))) return rc;
+    if (reads_out && (rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_list"))) return rc;
+    if ((rc = stage_reserve(h, 1, cap * 8))) return rc;
+    if (reads_out && (rc = stage_reserve(h, 3, cap * 8))) return rc;
+    const int rcl = kdf_hit_list_dev(h, h->stage[0], n_bases, reads_out ? h->stage[2] : nullptr, reads_out ? n_reads : 0, h->stage[1],
+                                     reads_out ? h->stage[3] : nullptr, cap, n_out);
+    if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
+    const uint64_t n = std::min<uint64_t>(*n_out, cap);
+    if (n) {
+        HIPCHK(h, hipMemcpyAsync(positions_out, h->stage[1], n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (reads_out) HIPCHK(h, hipMemcpyAsync(reads_out, h->stage[3], n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return rcl;
+}
+
 // ---- long keys (odd k 65..201): W-word keys, row-major -----------------------------------------------------------
 #define KDF_NEED_LONG(h, fn) \
     do { if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: takes engines for odd k 65..%d only (k=%d: use the (lo, hi) form)", fn, KDF_LONG_MAX_K, (h)->k); } while (0)
@@ -2725,6 +2945,8 @@ int kdf_profile(kdf_engine *h, int enable) {
     h->prof_pf_ms = 0.0; h->prof_pf_passes = 0;
     depth_prof_collect(h);
     h->prof_depth_ms = 0.0; h->prof_depth_passes = 0;
+    hits_prof_collect(h);
+    h->prof_hits_ms = 0.0; h->prof_hits_passes = 0;
     return KDF_OK;
 }
 
@@ -2830,6 +3052,8 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
     else if (n == "depth_us") { depth_prof_collect(h); *value = (int64_t)(h->prof_depth_ms * 1000.0 + 0.5); }
     else if (n == "depth_passes") { depth_prof_collect(h); *value = (int64_t)h->prof_depth_passes; }
+    else if (n == "hits_us") { hits_prof_collect(h); *value = (int64_t)(h->prof_hits_ms * 1000.0 + 0.5); }
+    else if (n == "hits_passes") { hits_prof_collect(h); *value = (int64_t)h->prof_hits_passes; }
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     else if (n == "pending_passes") *value = (int64_t)h->n_pass;
     else if (n == "pending_positions") *value = (int64_t)(h->pend_positions + h->l1_tiles * KDF_TILE);

@@ -366,7 +366,7 @@ def _write_informative_reads_discovery(child_bam, ref_fasta, proband_unique_kmer
                         max_bases=bam_scanner.SCAN_BATCH_BASES, max_reads=1 << 20, threads=threads,
                         want_meta=True) as rd:
             for batch in rd:
-                _hits, distinct = eng.scan(batch)
+                distinct, _hits_of = bam_scanner._scan_batch(eng, batch)      # (KDF_DEVICE_HITS=1: reduced on the device)
                 for r in np.flatnonzero(distinct >= 1).tolist():
                     key = (batch.name(r), bool(int(batch.flags[r]) & 0x800))
                     if key not in written:

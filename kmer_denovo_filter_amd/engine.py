@@ -12,6 +12,7 @@ shells out to ("External op" table):
     prefilter_*()            jellyfish bc + count --bc          (exact: two passes)
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
+    read_hits(stream)        ... and its per-read hits / distinct on the device
 
 Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
 keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
@@ -411,6 +412,103 @@ class KmerEngine:
         self._ck(self._lib.kdf_scan_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
                                               c_void_p(d_hits)))
 
+    # -- per-read hits of the scan, on the device -----------------------------
+    def read_hits(self, stream: ReadStream, want_bits: bool = False):
+        """The scan reduced per read where it is made: uint32 (n_reads, 2), columns ``READ_HITS_COLUMNS`` -- windows of
+        the read whose k-mer is stored with count > 0, and the distinct k-mers among them (what Module 3 filters on).
+        ``hits`` equals column ``present`` of read_depth, ``distinct`` equals scan()'s.  ``want_bits``: -> (rows,
+        hit_bits uint64[mask words]), the mask scan() returns."""
+        rows = np.zeros((stream.n_reads, len(READ_HITS_COLUMNS)), np.uint32)
+        bits = np.zeros(stream_words(stream.n_bases)[1], np.uint64) if want_bits else None
+        offs = np.ascontiguousarray(stream.offsets, dtype=np.int64)
+        self._ck(self._lib.kdf_read_hits(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases, _vp(offs),
+                                         stream.n_reads, _vp(bits), _vp(rows)))
+        return (rows, bits) if want_bits else rows
+
+    def read_hits_dev(self, d_packed: int, d_invalid: int, n_bases: int, d_offsets: int, n_reads: int,
+                      d_hit_bits: Optional[int], d_rows: int):
+        """The same between device buffers: ``d_offsets`` int64[n_reads + 1], ``d_rows`` uint32[n_reads x 2],
+        ``d_hit_bits`` uint64[ceil(n_bases / 64)] or None.  Synchronises the engine's stream once; the rows are complete
+        in stream order."""
+        self._ck(self._lib.kdf_read_hits_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases),
+                                             c_void_p(d_offsets) if d_offsets else None, int(n_reads),
+                                             c_void_p(d_hit_bits) if d_hit_bits else None, c_void_p(d_rows) if d_rows else None))
+
+    def hit_list(self, hit_bits: np.ndarray, n_bases: int, offsets: Optional[np.ndarray] = None, cap: Optional[int] = None):
+        """Positions of the set bits of a hit mask below ``n_bases``, ascending: uint64[n]; with ``offsets`` (int64
+        [n_reads + 1]) -> (positions, reads int64[n]) where reads[e] is the read that holds positions[e] or -1.
+        ``cap`` (default: as many as there are) bounds the output: more hits than that raise, like export_ge_dev."""
+        bits = np.ascontiguousarray(hit_bits, dtype=np.uint64)
+        if len(bits) * 64 < int(n_bases):
+            raise ValueError(f"a mask of {len(bits)} words does not cover {n_bases} positions")
+        if cap is None:
+            cap = int(np.unpackbits(bits[:(int(n_bases) + 63) // 64].view(np.uint8), bitorder="little")[:int(n_bases)].sum())
+        pos = np.zeros(int(cap), np.uint64)
+        offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        reads = None if offs is None else np.zeros(int(cap), np.int64)
+        n = c_uint64(0)
+        self._ck(self._lib.kdf_hit_list(self._h, _vp(bits), int(n_bases), _vp(offs), 0 if offs is None else len(offs) - 1,
+                                        _vp(pos), _vp(reads), int(cap), byref(n)))
+        return pos[:n.value] if offs is None else (pos[:n.value], reads[:n.value])
+
+    def _hit_list_dev(self, d_hit_bits, n_bases, d_offsets, n_reads, d_positions, d_reads, cap):
+        n = c_uint64(0)
+        rc = self._lib.kdf_hit_list_dev(self._h, c_void_p(d_hit_bits), int(n_bases), c_void_p(d_offsets) if d_offsets else None,
+                                        int(n_reads), c_void_p(d_positions) if d_positions else None,
+                                        c_void_p(d_reads) if d_reads else None, int(cap), byref(n))
+        return rc, n.value
+
+    def hit_list_dev(self, d_hit_bits: int, n_bases: int, d_offsets: Optional[int], n_reads: int, d_positions: int,
+                     d_reads: Optional[int], cap: int) -> int:
+        """The same between device buffers (``d_positions`` uint64[cap], ``d_reads`` int64[cap] or None); returns the
+        number of hits and raises when it exceeds ``cap`` (at most ``cap`` entries are written).  Synchronises."""
+        rc, n = self._hit_list_dev(d_hit_bits, n_bases, d_offsets, n_reads, d_positions, d_reads, cap)
+        self._ck(rc)
+        return n
+
+    def scan_hits(self, stream: ReadStream):
+        """-> (rows uint32 (n_reads, 2), positions int64[n] ascending): read_hits_dev + hit_list_dev over a stream
+        uploaded once.  Only the rows and the compacted list come back to the host, never the mask."""
+        import torch
+        n, nr = int(stream.n_bases), int(stream.n_reads)
+        if n == 0 or nr == 0:
+            return np.zeros((nr, len(READ_HITS_COLUMNS)), np.uint32), np.zeros(0, np.int64)
+        dev = torch.device("cuda", self.device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt).view(np.int64)).to(dev)
+        pw, mw = stream_words(n)
+        if len(stream.packed) < pw or len(stream.invalid) < mw:
+            raise ValueError(f"stream arrays are smaller than stream_words({n}) = ({pw}, {mw})")
+        dp, dm = up(stream.packed[:pw], np.uint64), up(stream.invalid[:mw], np.uint64)
+        do = up(stream.offsets, np.int64)
+        dbits = torch.empty((n + 63) // 64, dtype=torch.int64, device=dev)
+        drows = torch.empty(nr, dtype=torch.int64, device=dev)               # one row = 2 x uint32
+        torch.cuda.synchronize(dev)
+        self.read_hits_dev(dp.data_ptr(), dm.data_ptr(), n, do.data_ptr(), nr, dbits.data_ptr(), drows.data_ptr())
+        self.synchronize()
+        rows = drows.cpu().numpy().view(np.uint32).reshape(nr, 2)
+        cap = int(rows[:, 0].sum(dtype=np.int64))
+        while True:
+            dpos = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            torch.cuda.synchronize(dev)
+            rc, got = self._hit_list_dev(dbits.data_ptr(), n, None, 0, dpos.data_ptr(), None, cap)
+            if got <= cap:
+                self._ck(rc)
+                break
+            cap = got                                                     # (hits outside every read: not in the rows)
+        return rows, dpos[:got].cpu().numpy()
+
+    def scan_informative(self, stream: ReadStream, min_distinct: int = 1):
+        """Module 3's selection on the device: -> (read_indices int64[m], distinct uint32[m], [hit offsets int64 of each
+        of those reads, relative to the read's start]) for the reads with at least ``min_distinct`` distinct hit
+        k-mers (``min_distinct`` <= 0: every read, as the reference keeps them)."""
+        rows, pos = self.scan_hits(stream)
+        offs = np.asarray(stream.offsets, dtype=np.int64)
+        keep = np.flatnonzero(rows[:, 1] >= min_distinct) if min_distinct > 0 else np.arange(stream.n_reads)
+        lo = np.searchsorted(pos, offs[keep], side="left")
+        hi = np.searchsorted(pos, offs[keep + 1], side="left") if len(keep) else lo
+        per_read = [pos[a:b] - s for a, b, s in zip(lo.tolist(), hi.tolist(), offs[keep].tolist())]
+        return keep.astype(np.int64), rows[keep, 1].copy(), per_read
+
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):
         """`jellyfish query -s reads.fa` over a whole stream: uint32[n_bases], the stored count of the canonical k-mer
@@ -449,6 +547,8 @@ class KmerEngine:
 
 # columns of KmerEngine.read_depth's rows
 READ_DEPTH_COLUMNS = ("windows", "present", "low", "min", "max", "sum")
+# columns of KmerEngine.read_hits' rows
+READ_HITS_COLUMNS = ("hits", "distinct")
 
 
 def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:
