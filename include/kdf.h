@@ -130,10 +130,10 @@ int kdf_flush(kdf_engine *h);
  *            "defer" (1 default; 0: every count call ends with a flush), "defer_max_bytes" (budget of the ring of
  *            partitioned entries, 0 = 40 % of the device's memory), "l1_positions" (size from which the pending
  *            stream of small batches is partitioned, default 2^30), "l1_direct_positions" (batches from this size on
- *            are partitioned where they lie, default 2^28); "fused_dump" (0 default; 1: kdf_export_ge_dev with min_count >= 1
+ *            are partitioned where they lie, default 2^28); "fused_dump" (1 default, 0 for k > 63; 1: kdf_export_ge_dev with min_count >= 1
  *            called while partition passes are pending is written by the flush that applies them -- kernel C dumps every
  *            bucket it holds -- instead of by a pass over the table afterwards; falls back to that pass when a bucket
- *            overflowed or was split as heavy; env KDF_FUSED_DUMP=1 sets the default);
+ *            overflowed or was split as heavy, same entries in another order; 0: always that pass; env KDF_FUSED_DUMP=0 / 1 sets the default);
  *            "hash_shift" (0..8: the home slot ignores that many top hash bits -- the table of an OWNER rank of the
  *            multi-GPU merge, see kdf_add_pairs_multi_dev; such an engine counts through the direct kernels only.  It
  *            changes on an empty table only, KDF_ERR_STATE otherwise: a table is empty after kdf_clear and after

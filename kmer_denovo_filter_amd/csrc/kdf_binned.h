@@ -68,6 +68,9 @@
 #ifndef KB_C_WPE
 #define KB_C_WPE 6                       // waves per SIMD the register allocation aims at
 #endif
+#ifndef KB_DUMP_EARLY
+#define KB_DUMP_EARLY 1                  // fused dump into an empty table: reserve the bucket's output range before the write-back (0: after it, as into a live table)
+#endif
 static_assert(KB_C_EPB_N % 4 == 0 && KB_C_EPB_W % 4 == 0, "kernel C resolves entries four at a time");
 static_assert(KB_C_THREADS % 256 == 0 && KB_C_THREADS <= 1024 && KB_C_THREADS_W % 256 == 0 && KB_C_THREADS_W <= KB_C_THREADS, "whole waves on every SIMD");
 #define KB_C_CT(KW) ((KW) == 2 ? KB_C_THREADS_W : KB_C_THREADS)
@@ -1419,6 +1422,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
     // two slots per lane and step: 16-byte LDS reads and HBM stores for the keys, 8-byte ones for the counts
     // (slot0 is a multiple of B, B is even: everything stays aligned)
     if (KB_ABL(plan, 512)) return;                                         // (ablation 512: no write-back -- timing only)
+    if constexpr (!DUMP) {
     for (uint32_t i = threadIdx.x; i < B / 2; i += CT) {
         if constexpr (MODE == KB_MODE_INSERT) {
             ((ulonglong2 *)(t.lo + slot0))[i] = ((const ulonglong2 *)tlo)[i];
@@ -1430,59 +1434,112 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             if (c2.x < o.x || c2.y < o.y) {
                 if (c2.x < o.x) c2.x = 0xFFFFFFFFu;
                 if (c2.y < o.y) c2.y = 0xFFFFFFFFu;
-                if constexpr (DUMP) ((uint2 *)tcnt)[i] = c2;     // (the dump below reads the counts from LDS)
             }
         }
         ((uint2 *)(t.cnt + slot0))[i] = c2;
     }
     if (threadIdx.x == 0 && sh_claimed)
         atomicAdd(&ctl->distinct[(bucket % KDF_SHARDS) * 16], (unsigned long long)sh_claimed);
+    } else {
     // DUMP: `dump -L dump_min` while the bucket is here.  The last flush before a dump sees every key's final count (every
     // flush rewrites every bucket), so the separate pass over the table -- 6.4 GB for the bench's 2^29 slots, 1.4 ms -- is
-    // saved.  A thread counts what it keeps among the slot pairs it has just written back (its own LDS words: no barrier),
-    // the waves add up in LDS, ONE global atomic per bucket reserves the range, and the kept slots go out as (key, count).
-    // Buckets that failed or were left to the heavy-bucket kernels never get here: the host then dumps the usual way.
-    // (Measured the same: the reservation issued BEFORE the write-back, to hide its round trip under those stores,
-    // profiles/r03b_fused_dump.txt.)
-    if constexpr (DUMP) {
-        const uint32_t dm = plan.dump_min;
-        uint32_t n = 0;
-        for (uint32_t i = threadIdx.x; i < B / 2; i += CT) {
-            const uint2 c2 = ((const uint2 *)tcnt)[i];
-            n += (c2.x >= dm) + (c2.y >= dm);
-        }
-        uint32_t inc = n;
+    // saved.  Buckets that failed or were left to the heavy-bucket kernels never get here: the host then dumps the usual way.
+    //
+    // The write-back is unrolled (NIT slot pairs per thread, the last step partial) and keeps what it read from LDS in
+    // registers -- the insert phase's registers are free by now.  What a wave keeps is a pair of ballots per step (even and
+    // odd slots): wave-uniform, so they sit in SGPRs, and their popcounts are the wave's total.  Lane 0 of every wave takes
+    // the wave's base inside the bucket (one returning LDS atomic), ONE global atomic per bucket reserves the range in
+    // ctl->cursor between two barriers, and an entry's place is base + wave base + popcounts of the earlier masks + mbcnt
+    // of its own: a store instruction writes consecutive entries, from registers.
+    // Into an empty table (!table_nonempty: no saturation fix-up, the counts in LDS are final) the reservation comes
+    // FIRST, so that its round trip runs under the write-back stores (KB_DUMP_EARLY).
+    constexpr uint32_t BMAX = 1u << (KB_BB_SMALL(KW) + (BIG ? 1u : 0u));     // (table_alloc: a binned table's buckets)
+    constexpr uint32_t NIT = (BMAX / 2 + CT - 1) / CT;
+    const uint32_t dm = plan.dump_min;
+    const bool early = KB_DUMP_EARLY && !table_nonempty;
+    ulonglong2 kl[NIT], kh[KW == 2 ? NIT : 1]; uint2 cc[NIT];
+    unsigned long long mx[NIT], my[NIT];
+    uint32_t wb = 0; unsigned long long rsv = 0;
+    // counts of this thread's slot pairs from LDS (a thread past B / 2 holds zeros: below any dump_min)
+    auto load_counts = [&]() {
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(inc, o); if ((int)(threadIdx.x & 63) >= o) inc += v; }
-        uint32_t wb = 0;
-        if ((threadIdx.x & 63) == 63 && inc) wb = atomicAdd(&wsum[0], inc);
-        wb = __shfl(wb, 63);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t tot = wsum[0];
-            *(unsigned long long *)(wsum + 2) = tot ? atomicAdd(&ctl->cursor, (unsigned long long)tot) : 0ull;
+        for (uint32_t it = 0; it < NIT; ++it) {
+            const uint32_t i = threadIdx.x + it * CT;
+            cc[it] = uint2{0u, 0u};
+            if (i < B / 2) cc[it] = ((const uint2 *)tcnt)[i];
         }
-        __syncthreads();
-        if (n) {
-            unsigned long long pos = *(const unsigned long long *)(wsum + 2) + wb + (inc - n);
-            for (uint32_t i = threadIdx.x; i < B / 2; i += CT) {
-                const uint2 c2 = ((const uint2 *)tcnt)[i];
+    };
+    auto write_back = [&]() {
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const uint32_t cv = e ? c2.y : c2.x;
-                    if (cv >= dm) {
-                        if (pos < s.dump_cap) {
-                            uint64_t hi = 0;
-                            if constexpr (KW == 2) hi = thi[2 * i + e];
-                            s.dump_lo[pos] = kdf_key_lo(tlo[2 * i + e], hi);
-                            if constexpr (KW == 2) if (s.dump_hi) s.dump_hi[pos] = hi;
-                            if (s.dump_cnt) s.dump_cnt[pos] = cv;
-                        }
-                        ++pos;
-                    }
+        for (uint32_t it = 0; it < NIT; ++it) {
+            const uint32_t i = threadIdx.x + it * CT;
+            if (i < B / 2) {
+                kl[it] = ((const ulonglong2 *)tlo)[i];
+                ((ulonglong2 *)(t.lo + slot0))[i] = kl[it];
+                if constexpr (KW == 2) { kh[it] = ((const ulonglong2 *)thi)[i]; ((ulonglong2 *)(t.hi + slot0))[i] = kh[it]; }
+                if (table_nonempty) {
+                    const uint2 o = ((const uint2 *)(t.cnt + slot0))[i];
+                    if (cc[it].x < o.x) cc[it].x = 0xFFFFFFFFu;
+                    if (cc[it].y < o.y) cc[it].y = 0xFFFFFFFFu;
                 }
+                ((uint2 *)(t.cnt + slot0))[i] = cc[it];
             }
         }
+    };
+    // masks, the wave's base, the bucket's reservation (issued by thread 0: its answer is awaited in `rsv` later)
+    auto reserve = [&]() {
+        uint32_t wn = 0;
+#pragma unroll
+        for (uint32_t it = 0; it < NIT; ++it) {
+            mx[it] = __ballot(cc[it].x >= dm); my[it] = __ballot(cc[it].y >= dm);
+            wn += (uint32_t)__popcll(mx[it]) + (uint32_t)__popcll(my[it]);
+        }
+        // (both atomics below are issued by ONE lane: their addresses get an index 0 that went through an empty asm, which
+        // hides from the compiler that they are uniform -- its wave-reduction wrapper for uniform-address atomics would
+        // wait for the answer on the spot, and the global one is to be awaited only after the write-back)
+        uint32_t z = 0; asm volatile("" : "+v"(z));
+        if ((threadIdx.x & 63) == 0 && wn) wb = atomicAdd(&wsum[z], wn);
+        wb = __builtin_amdgcn_readfirstlane(wb);
+        KB_T(s.trash, 41);                                    // dump: masks, wave base
+        __syncthreads();
+        KB_T(s.trash, 42);                                    // ... the other waves
+        if (threadIdx.x == 0) {
+            const uint32_t tot = wsum[0];
+            if (tot) rsv = atomicAdd(&ctl->cursor + z, (unsigned long long)tot);  // (nothing kept: nothing reserved)
+        }
+    };
+    load_counts();
+    if (early) reserve();
+    write_back();
+    if (threadIdx.x == 0 && sh_claimed)
+        atomicAdd(&ctl->distinct[(bucket % KDF_SHARDS) * 16], (unsigned long long)sh_claimed);
+    KB_T(s.trash, 39);                                        // write-back issued
+    if (!early) reserve();
+    if (threadIdx.x == 0) *(unsigned long long *)(wsum + 2) = rsv;
+    KB_T(s.trash, 43);                                        // dump: the reservation's round trip
+    __syncthreads();
+    unsigned long long pos = *(const unsigned long long *)(wsum + 2) + wb;
+    KB_T(s.trash, 44);                                        // ... the other waves
+#pragma unroll
+    for (uint32_t it = 0; it < NIT; ++it) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const unsigned long long m = e ? my[it] : mx[it];
+            const uint32_t cv = e ? cc[it].y : cc[it].x;
+            if (cv >= dm) {
+                const unsigned long long p = pos + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                if (p < s.dump_cap) {
+                    uint64_t hi = 0;
+                    if constexpr (KW == 2) hi = e ? kh[it].y : kh[it].x;
+                    s.dump_lo[p] = kdf_key_lo(e ? kl[it].y : kl[it].x, hi);
+                    if constexpr (KW == 2) if (s.dump_hi) s.dump_hi[p] = hi;
+                    if (s.dump_cnt) s.dump_cnt[p] = cv;
+                }
+            }
+            pos += (uint32_t)__popcll(m);
+        }
+    }
+    KB_T(s.trash, 45);                                        // dump: stores issued
     }
 #ifdef KB_TIMING
     KB_T(s.trash, 39);                                        // write-back issued

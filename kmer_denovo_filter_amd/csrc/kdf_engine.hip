@@ -506,11 +506,10 @@ struct kdf_engine {
     int opt_force_path = 0;                          // 0 auto, 1 direct, 2 binned, 4 sieve only (count --if)
     int opt_defer = 1;                               // 1: kernel C is deferred over the pending passes; 0: every count call ends with a flush
     uint64_t opt_defer_max_bytes = 0;                // budget of the entry ring (0: 40 % of the device's memory)
-    // 1: a dump (min_count >= 1, caller-sized device buffers) asked for while passes are pending is written by the flush itself
-    // -- kernel C holds every bucket anyway (kb_bucket_kernel<.., DUMP>).  Off by default: at bench size the step is 13.1 ->
-    // 12.6 ms (the 1.4 ms table pass of the dump saved), but kernel C takes 0.9 ms longer for it (two barriers and a global
-    // reservation per bucket); option "fused_dump" / env KDF_FUSED_DUMP=1
-    int opt_fused_dump = [] { const char *e = getenv("KDF_FUSED_DUMP"); return e ? atoi(e) != 0 : 0; }();
+    // 1 (the default): a dump (min_count >= 1, caller-sized device buffers) asked for while passes are pending is written by the
+    // flush itself -- kernel C holds every bucket anyway (kb_bucket_kernel<.., DUMP>), and the dump's pass over the table is
+    // saved.  Option "fused_dump" / env KDF_FUSED_DUMP=0 turn it off; long engines have no binned pipeline: 0
+    int opt_fused_dump = [] { const char *e = getenv("KDF_FUSED_DUMP"); return e ? atoi(e) != 0 : 1; }();
     // the request a dump hands to the LAST flush before it (fuse_min > 0), and what came of it
     uint32_t fuse_min = 0; uint64_t *fuse_lo = nullptr, *fuse_hi = nullptr; uint32_t *fuse_cnt = nullptr; uint64_t fuse_cap = 0;
     bool fuse_done = false; uint64_t fuse_n = 0;
@@ -1555,6 +1554,7 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     kdf_engine *h = new kdf_engine();
     h->capacity_hint = capacity_hint;
     h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
+    if (is_long(h)) h->opt_fused_dump = 0;
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
