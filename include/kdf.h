@@ -102,7 +102,8 @@ int kdf_clear(kdf_engine *h);
  * contents, `windows` and the mode do not change, and a table never shrinks. */
 int kdf_reserve(kdf_engine *h, uint64_t n_keys);
 /* capacity in slots, distinct keys currently stored, valid windows processed
- * by the count calls since the last clear.  Any pointer may be NULL. */
+ * by the count calls since the last clear.  Any pointer may be NULL.  Answers from the counters of a dump-only
+ * flush (option "lazy_table") without materialising the table. */
 int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *windows);
 
 /* Count calls in insert mode are DEFERRED: a call partitions its batch (or, for small batches, only appends it to a
@@ -134,6 +135,9 @@ int kdf_flush(kdf_engine *h);
  *            called while partition passes are pending is written by the flush that applies them -- kernel C dumps every
  *            bucket it holds -- instead of by a pass over the table afterwards; falls back to that pass when a bucket
  *            overflowed or was split as heavy, same entries in another order; 0: always that pass; env KDF_FUSED_DUMP=0 / 1 sets the default);
+ *            "lazy_table" (1 default, 0 for k > 63; 1: such a fused dump into a table that is still empty since kdf_clear writes the dump
+ *            and the counters only -- the table is materialised, from the passes kept in the ring, by the first call that reads or
+ *            changes it; 0: the flush writes the table as well; env KDF_LAZY_TABLE=0 / 1 sets the default);
  *            "hash_shift" (0..8: the home slot ignores that many top hash bits -- the table of an OWNER rank of the
  *            multi-GPU merge, see kdf_add_pairs_multi_dev; such an engine counts through the direct kernels only.  It
  *            changes on an empty table only, KDF_ERR_STATE otherwise: a table is empty after kdf_clear and after
@@ -148,6 +152,8 @@ int kdf_flush(kdf_engine *h);
  *   stats    "binned_passes" (partition passes), "flushes" (kernel C launches), "pending_passes",
  *            "pending_positions", "ring_bytes", "replayed_buckets", "heavy_buckets" (buckets of skewed flushes that
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
+ *            "lazy_table", "dump_only_flushes" (flushes that wrote a dump and no table), "retained_passes" (passes such a flush applied,
+ *            kept for the table: no longer "pending_passes"), "materialisations" (tables written later from retained passes),
  *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
  *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
@@ -356,7 +362,9 @@ int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out,
  * unless sorted != 0.  ONE pass over the table: at most `cap` entries are written,
  * *n_out is the number the dump holds; KDF_ERR_INVALID when that exceeds cap
  * (kdf_count_ge sizes the buffers).  d_keys_hi_out may be NULL for k <= 32,
- * d_counts_out may be NULL when sorted == 0.  Synchronises the engine's stream. */
+ * d_counts_out may be NULL when sorted == 0.  Synchronises the engine's stream.  With min_count >= 1, count passes
+ * pending and a table still empty since kdf_clear, the dump is all that is written (option "lazy_table"): the table is
+ * materialised by the next call that reads or changes it, kdf_clear drops it unwritten. */
 int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out,
                       void *d_keys_hi_out, void *d_counts_out, uint64_t cap,
                       int sorted, uint64_t *n_out);

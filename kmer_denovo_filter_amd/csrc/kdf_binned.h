@@ -1032,13 +1032,18 @@ __device__ __forceinline__ void kb_probe_wide_wave(uint64_t *tlo, uint64_t *thi,
 #define KB_C_LDS_T(KW, BB, CT_, RUNS_) (((size_t)8 * (KW) + 4) * ((size_t)1 << (BB)) + (2 + 32 + (RUNS_)) * 4 + (size_t)(RUNS_) * 8 + ((KW) == 2 ? (size_t)(RUNS_) * 4 : 0) \
                           + KB_C_QCAPT(KW, CT_) * ((KW) == 2 ? 18 : 10) + 16 + ((RUNS_) + 4) * 4 + KB_RI_LDS_BYTES)
 #define KB_C_LDS(KW, BB) KB_C_LDS_T(KW, BB, KB_C_CTB(KW, (BB) > KB_BB_SMALL(KW)), KB_C_RUNS_T(KW, (BB) > KB_BB_SMALL(KW)))
-template <int KW, int MODE, int VAR, bool BIG = false, bool DUMP = false>
+// DUMP: the flush also writes `dump -L dump_min` (below).  LAZY (with DUMP, into an empty table only): the dump-only flush --
+// the bucket is built and dumped, the ctl counters are kept, and the slice is NOT written back to t.lo / t.hi / t.cnt: the
+// host keeps the passes in the ring and applies them again if anything asks for the table.
+template <int KW, int MODE, int VAR, bool BIG = false, bool DUMP = false, bool LAZY = false>
 __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_eu(BIG ? 4 : KB_C_WPE, BIG ? 4 : KB_C_WPE))) void kb_bucket_kernel(
     KbPlan plan, KbScratch s, KdfTable t, KdfCtl *ctl, int table_nonempty)
 {
     constexpr uint32_t CT = KB_C_CTB(KW, BIG), QCAP = KB_C_QCAPT(KW, CT);      // threads and queue entries per workgroup
     constexpr uint32_t RUNS = KB_C_RUNS_T(KW, BIG);                                // runs staged per round
     static_assert(RUNS <= CT, "a thread per run");
+    static_assert(!LAZY || (DUMP && MODE == KB_MODE_INSERT && VAR == 1), "the dump-only flush: insert mode, no heavy-bucket split");
+    if constexpr (LAZY) table_nonempty = 0;                  // (the host launches it on a logically empty table only)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const uint32_t B = 1u << plan.bucket_bits;
     uint64_t *tlo = (uint64_t *)smem;                         // [B]
@@ -1400,6 +1405,10 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
     if (claimed) atomicAdd(&sh_claimed, claimed);
     if (DUMP && threadIdx.x == 0) wsum[0] = 0;               // (the fused dump's counter; the scans are over)
     __syncthreads();
+    // What a bucket leaves behind outside the table: s.failed + totals[2] (here), ctl->distinct, and for DUMP ctl->cursor and
+    // the dump buffers (below); VAR 2 also hv_ctr / hv_bucket.  The host's fallback from a dump-only flush (kb_flush_ring,
+    // `if (lazy)`) runs this kernel a second time over the same passes and undoes exactly these: a further accumulator
+    // added here must be reset there too.
     if (sh_failed) {
         // leave the bucket as it was in HBM; flag it for replay.  A lazily
         // cleared table holds garbage there: write an empty slice instead.
@@ -1407,7 +1416,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             atomicOr(&s.failed[bucket >> 5], 1u << (bucket & 31));
             atomicAdd(&s.totals[2], 1ull);
         }
-        if (!table_nonempty) {
+        if (!LAZY && !table_nonempty) {                          // (LAZY: the table is not written at all; the host flushes again)
             for (uint32_t i = threadIdx.x; i < B; i += CT) {
                 t.lo[slot0 + i] = KDF_EMPTY;
                 if constexpr (KW == 2) t.hi[slot0 + i] = KDF_EMPTY;
@@ -1475,6 +1484,9 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             const uint32_t i = threadIdx.x + it * CT;
             if (i < B / 2) {
                 kl[it] = ((const ulonglong2 *)tlo)[i];
+                if constexpr (LAZY) {                                     // dump-only: the keys are wanted in registers, not in HBM
+                    if constexpr (KW == 2) kh[it] = ((const ulonglong2 *)thi)[i];
+                } else {
                 ((ulonglong2 *)(t.lo + slot0))[i] = kl[it];
                 if constexpr (KW == 2) { kh[it] = ((const ulonglong2 *)thi)[i]; ((ulonglong2 *)(t.hi + slot0))[i] = kh[it]; }
                 if (table_nonempty) {
@@ -1483,6 +1495,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
                     if (cc[it].y < o.y) cc[it].y = 0xFFFFFFFFu;
                 }
                 ((uint2 *)(t.cnt + slot0))[i] = cc[it];
+                }
             }
         }
     };

@@ -514,6 +514,15 @@ struct kdf_engine {
     uint32_t fuse_min = 0; uint64_t *fuse_lo = nullptr, *fuse_hi = nullptr; uint32_t *fuse_cnt = nullptr; uint64_t fuse_cap = 0;
     bool fuse_done = false; uint64_t fuse_n = 0;
     uint64_t stat_fused_dumps = 0;
+    // 1 (the default): such a dump into a table that is still only logically empty (kdf_clear, nothing applied since) runs the
+    // DUMP-ONLY flush -- kb_bucket_kernel<.., DUMP, LAZY> writes the dump and the ctl counters and leaves the table alone.  The
+    // passes stay in the ring (the first n_dumped of n_pass); whatever needs the table later applies them with the ordinary
+    // flush, into the still empty table.  Option "lazy_table" / env KDF_LAZY_TABLE=0 turn it off.
+    int opt_lazy_table = [] { const char *e = getenv("KDF_LAZY_TABLE"); return e ? atoi(e) != 0 : 1; }();
+    uint32_t n_dumped = 0;                           // pending passes a dump-only flush has applied: kept for the table, reported as flushed
+    uint64_t dumped_positions = 0;                   // ... and their stream positions
+    uint64_t acct_entries = 0, acct_positions = 0;   // what of the pending passes dens_windows / dens_positions already hold
+    uint64_t stat_dump_only = 0, stat_materialisations = 0;
     uint64_t opt_l1_positions = 1ull << 30;          // pending-stream size from which it is partitioned
     uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
     // double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
@@ -878,6 +887,8 @@ static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t 
     KB_SETV(1)
     KB_SETV(2)
 #undef KB_SETV
+    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, 1, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c));
+    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, 1, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cbig));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_slice_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_combine_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_filtered_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
@@ -921,11 +932,12 @@ static int kb_scratch(kdf_engine *h, KbScratch &s) {
 // the ring is empty again: nothing pending, the flush-wide counters zeroed
 static int kb_ring_reset(kdf_engine *h) {
     h->n_pass = 0; h->ring_used = 0; h->rows_used = 0; h->pend_positions = 0;
+    h->n_dumped = 0; h->dumped_positions = 0; h->acct_entries = 0; h->acct_positions = 0;
     if (h->kb_small) HIPCHK(h, hipMemsetAsync(h->kb_small, 0, 16 * 8, h->stream));
     return KDF_OK;
 }
 
-static int kb_flush_ring(kdf_engine *h);
+static int kb_flush_ring(kdf_engine *h, bool lazy_ok = false);
 
 // Room for a pass of need_e entries (upper bound: its stream positions) in need_r pieces.  A full ring is applied to the
 // table first; a ring that was too small for the pending passes plus this one grows (doubling, up to the budget) while
@@ -1065,7 +1077,11 @@ static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const ui
 }
 
 // Kernel C over every pending pass: the ring is applied to the table and emptied.
-static int kb_flush_ring(kdf_engine *h) {
+// lazy_ok (a dump is waiting and would be this flush's only reader): the dump-only flush is allowed -- the dump and the
+// counters are written, the table is not, and the passes stay in the ring until something needs the table.  Passes a
+// dump-only flush has applied (n_dumped) are applied AGAIN here, dump-only or not: the table is still empty, so the result
+// is what the first application would have left.
+static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
     if (h->n_pass == 0) return KDF_OK;
     int rc;
     KbScratch s;
@@ -1075,14 +1091,24 @@ static int kb_flush_ring(kdf_engine *h) {
     HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
     if ((rc = ctl_sync(h, nullptr))) return rc;
     const uint64_t n_entries = h->kb_totals_host[0];
-    h->dens_windows += n_entries; h->dens_positions += h->pend_positions;
+    h->dens_windows += n_entries - h->acct_entries; h->dens_positions += h->pend_positions - h->acct_positions;
+    h->acct_entries = n_entries; h->acct_positions = h->pend_positions;
+    // passes a dump-only flush has applied: kernel C counts their keys again, so the counter restarts at 0 (the table is
+    // empty) -- just before the launch below, after everything that can still fail or return
+    const bool redo = h->n_dumped > 0;
     const bool skewed = h->kb_totals_host[7] != 0 || (h->opt_debug_flags & 4096);          // (debug flag 4096 forces VAR 2: fuzzing)
-    const uint64_t distinct_before = h->distinct;
+    const uint64_t distinct_before = redo ? 0 : h->distinct;
     // Grow BEFORE the flush when the last flush's rate of new keys says the pending entries will not fit: growing now
     // rehashes the smaller table, and kernel C resolves the extra bucket bits itself (sub_bits) -- no failed buckets, no
     // replay through the global-atomic path.  (First flush of a table: the caller's capacity hint is trusted.)
-    if (!filtered && h->grow_ratio > 0.0) {
-        const double est = (double)h->distinct + h->grow_ratio * (double)n_entries;
+    const double est = (double)distinct_before + h->grow_ratio * (double)n_entries;
+    const bool grow_first = !filtered && h->grow_ratio > 0.0 && est > 0.6 * (double)h->cap && h->t.log2cap < 40;
+    // the dump-only flush: everything that gates the fused dump, an empty table, passes no flush has seen, and nothing that
+    // would send a bucket another way (skew: the heavy-bucket split; a table about to grow).  Counts of one key slice
+    // (key_parts) and counts behind a prefilter keep the ordinary flush: their dumps are followed by reads of the table.
+    const bool lazy = lazy_ok && h->opt_lazy_table && h->fuse_min && !filtered && h->lazy_empty && !skewed && !grow_first &&
+                      h->n_pass > h->n_dumped && h->pend_plan.key_parts <= 1 && h->pf_state == PF_OFF && !(h->opt_debug_flags & 2048);
+    if (grow_first) {
         while (est > 0.6 * (double)h->cap && h->t.log2cap < 40) {
             if (h->lazy_empty) {                                  // nothing to carry over: a new table, still to be cleared
                 KdfTable nt;
@@ -1125,16 +1151,24 @@ static int kb_flush_ring(kdf_engine *h) {
     if (heavy) {
         HIPCHK(h, hipMemsetAsync(s.hv_ctr, 0, (4 + 3 * KB_HV_MAX) * 4, h->stream));
     }
+    if (redo) {
+        HIPCHK(h, hipMemsetAsync(h->ctl->distinct, 0, sizeof(h->ctl->distinct), h->stream));
+        h->distinct = 0;
+        if (!lazy) h->stat_materialisations++;
+    }
     by_width(h, [&](auto KWc) {
         constexpr int KW = decltype(KWc)::value;
         const size_t lds_c = KB_C_LDS(KW, plan.bucket_bits);
         const bool big = plan.bucket_bits > KB_BB_SMALL(KW);
-#define KB_LV(M, V, D) do { if (big) hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, true, D>), dim3((unsigned)nb_table), dim3(KB_C_CT_BIG), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); \
-                         else hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, false, D>), dim3((unsigned)nb_table), dim3(KB_C_CT(KW)), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); } while (0)
-        if (filtered) { if (skewed) KB_LV(KB_MODE_FILTERED, 2, false); else KB_LV(KB_MODE_FILTERED, 1, false); }
+#define KB_LVL(M, V, D, L) do { if (big) hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, true, D, L>), dim3((unsigned)nb_table), dim3(KB_C_CT_BIG), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); \
+                         else hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, false, D, L>), dim3((unsigned)nb_table), dim3(KB_C_CT(KW)), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); } while (0)
+#define KB_LV(M, V, D) KB_LVL(M, V, D, false)
+        if (lazy) KB_LVL(KB_MODE_INSERT, 1, true, true);
+        else if (filtered) { if (skewed) KB_LV(KB_MODE_FILTERED, 2, false); else KB_LV(KB_MODE_FILTERED, 1, false); }
         else if (fuse_min) { if (skewed) KB_LV(KB_MODE_INSERT, 2, true); else KB_LV(KB_MODE_INSERT, 1, true); }
         else { if (skewed) KB_LV(KB_MODE_INSERT, 2, false); else KB_LV(KB_MODE_INSERT, 1, false); }
 #undef KB_LV
+#undef KB_LVL
         return 0;
     });
     if (heavy) {
@@ -1163,10 +1197,29 @@ static int kb_flush_ring(kdf_engine *h) {
     bool full = false;
     uint64_t cursor = 0;
     if ((rc = ctl_sync(h, &full, &cursor))) return rc;
+    if (lazy) {
+        // whole (no bucket failed) and the table need not grow for what comes next: the dump is the caller's, the passes stay
+        if (h->kb_totals_host[2] == 0 && h->distinct * 10 <= h->cap * 7) {
+            h->fuse_done = true; h->fuse_n = cursor; h->stat_fused_dumps++; h->stat_flushes++; h->stat_dump_only++;
+            if (n_entries >= 100000) h->grow_ratio = (double)(h->distinct - distinct_before) / (double)n_entries;
+            h->n_dumped = h->n_pass; h->dumped_positions = h->pend_positions;
+            return KDF_OK;
+        }
+        // otherwise: what the parent path does, from the start -- the ordinary flush of the same passes into the empty table
+        // (it dumps too, replays the failed buckets, grows the table); nothing of this attempt is counted.  Undone here is
+        // EVERYTHING kernel C<.., LAZY> accumulates into (the list at "what a bucket leaves behind" in kdf_binned.h):
+        // totals[2] and ctl->distinct below; s.failed, ctl->tally / cursor and the dump buffers are reset or rewritten on
+        // re-entry.  Under kdf_profile the discarded launch stays in the C stage slot as a second C.
+        HIPCHK(h, hipMemsetAsync(s.totals + 2, 0, 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->ctl->distinct, 0, sizeof(h->ctl->distinct), h->stream));
+        h->distinct = 0;
+        h->fuse_min = fuse_min;
+        return kb_flush_ring(h, false);
+    }
     // the fused dump is whole only if every bucket went through kernel C's write-back (none failed, none was left to the
     // heavy-bucket kernels); otherwise the caller dumps from the table as usual
     if (fuse_min && h->kb_totals_host[2] == 0 && h->kb_totals_host[4] == 0) { h->fuse_done = true; h->fuse_n = cursor; h->stat_fused_dumps++; }
-    h->stat_flushes++;
+    if (h->n_pass > h->n_dumped) h->stat_flushes++;           // (only retained passes: their dump-only flush was counted)
     h->lazy_empty = false;
     h->stat_heavy_buckets += h->kb_totals_host[4];
     const uint64_t n_failed = h->kb_totals_host[2];
@@ -1287,6 +1340,16 @@ static int pending_flush(kdf_engine *h, bool fuse = false) {
     int rc;
     const uint32_t want_fuse = fuse ? h->fuse_min : 0u;
     h->fuse_min = 0; h->fuse_done = false;                     // (only the LAST flush below may dump: earlier ones see counts that are not final)
+    if (h->l1_tiles && h->n_dumped && h->n_pass == h->n_dumped) {
+        // small batches behind passes that only a dump-only flush has applied: without lazy_table the ring would be empty
+        // and the table live here.  Choose as that engine would; a batch it sends through the direct kernels gets the
+        // table first (same last_count_path / binned_passes, and no second rewrite of the table for a few reads)
+        const bool le = h->lazy_empty;
+        h->lazy_empty = false;
+        const bool binned = use_binned(h, h->l1_tiles * KDF_TILE, false);
+        h->lazy_empty = le;
+        if (!binned && (rc = kb_flush_ring(h))) return rc;
+    }
     if (h->l1_tiles) {
         const uint64_t n = h->l1_tiles * KDF_TILE;
         h->l1_tiles = 0;
@@ -1295,7 +1358,7 @@ static int pending_flush(kdf_engine *h, bool fuse = false) {
         if (rc) return rc;
     }
     h->fuse_min = want_fuse;
-    rc = kb_flush_ring(h);
+    rc = kb_flush_ring(h, fuse);
     h->fuse_min = 0;
     return rc;
 }
@@ -1554,7 +1617,7 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     kdf_engine *h = new kdf_engine();
     h->capacity_hint = capacity_hint;
     h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
-    if (is_long(h)) h->opt_fused_dump = 0;
+    if (is_long(h)) { h->opt_fused_dump = 0; h->opt_lazy_table = 0; }
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
@@ -1651,7 +1714,8 @@ int kdf_reserve(kdf_engine *h, uint64_t n_keys) {
 int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *windows) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     HIPCHK(h, hipSetDevice(h->device));
-    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    // (passes a dump-only flush has applied: their keys and windows are in the counters already, the table is not needed)
+    if (h->l1_tiles || h->n_pass > h->n_dumped) { int rcf = pending_flush(h); if (rcf) return rcf; }
     bool full = false;
     int rc = ctl_sync(h, &full);
     if (rc) return rc;
@@ -2088,7 +2152,7 @@ static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *
                        uint32_t *ocnt, uint64_t out_cap, uint64_t *n_out) {
     // passes pending: the flush that applies them holds every bucket of the table in LDS once -- it writes the dump too
     // (kb_bucket_kernel, KbPlan::dump_min) unless a bucket took another way (overflow replay, heavy-bucket split)
-    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->n_pass > 0 || h->l1_tiles > 0);
+    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->n_pass > h->n_dumped || h->l1_tiles > 0);
     if (fuse) { h->fuse_min = min_count; h->fuse_lo = olo; h->fuse_hi = ohi; h->fuse_cnt = ocnt; h->fuse_cap = out_cap; }
     { int rcf = pending_flush(h, fuse); if (rcf) return rcf; }
     if (fuse && h->fuse_done) { h->fuse_done = false; *n_out = h->fuse_n; return KDF_OK; }
@@ -3019,6 +3083,10 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
         if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "fused_dump: not available for k > 63 (no binned pipeline for long keys)");
         h->opt_fused_dump = value != 0;
     }
+    else if (n == "lazy_table") {
+        if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "lazy_table: not available for k > 63 (no binned pipeline for long keys)");
+        h->opt_lazy_table = value != 0;
+    }
     else if (n == "l1_positions") h->opt_l1_positions = (uint64_t)std::max<int64_t>(value, KDF_TILE);
     else if (n == "l1_direct_positions") h->opt_l1_direct_positions = (uint64_t)std::max<int64_t>(value, 0);
     else if (n == "sieve_bits") h->opt_sieve_bits = (int)value;
@@ -3055,8 +3123,14 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "hits_us") { hits_prof_collect(h); *value = (int64_t)(h->prof_hits_ms * 1000.0 + 0.5); }
     else if (n == "hits_passes") { hits_prof_collect(h); *value = (int64_t)h->prof_hits_passes; }
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
-    else if (n == "pending_passes") *value = (int64_t)h->n_pass;
-    else if (n == "pending_positions") *value = (int64_t)(h->pend_positions + h->l1_tiles * KDF_TILE);
+    // (pending: not yet applied by any flush.  Passes a dump-only flush has applied are kept in the ring -- "retained_passes" --
+    // until the table is asked for or cleared)
+    else if (n == "pending_passes") *value = (int64_t)(h->n_pass - h->n_dumped);
+    else if (n == "pending_positions") *value = (int64_t)(h->pend_positions - h->dumped_positions + h->l1_tiles * KDF_TILE);
+    else if (n == "retained_passes") *value = (int64_t)h->n_dumped;
+    else if (n == "dump_only_flushes") *value = (int64_t)h->stat_dump_only;
+    else if (n == "materialisations") *value = (int64_t)h->stat_materialisations;
+    else if (n == "lazy_table") *value = h->opt_lazy_table;
     else if (n == "ring_bytes") *value = (int64_t)(h->ring_entries * 8 * h->kw);
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
