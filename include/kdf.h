@@ -267,11 +267,18 @@ int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_k
  *     the prefilter as it is; kdf_destroy frees it.
  *   - refused together (KDF_ERR_STATE, either order): key_parts > 1 and a prefilter; hash_shift != 0 and a prefilter.
  *   - every key width: k <= 32, 33..63, long engines (odd 65..201).
- * Single GPU only: a rank of a sharded count sees only its share of the reads, so its tallies under-count; the sieves
- * would have to be merged with a saturating sum first.  The mirrors do not use the prefilter when world > 1.
+ * Several ranks (a sharded count: every rank streams its share of the reads).  A rank's own tallies under-count, but a
+ * cell is min(sightings, 3), so the SATURATING SUM of the ranks' cells is exactly the cell one engine would have
+ * tallied over the whole sample.  Every rank tallies its share into a sieve of the SAME log2_cells, the sieves are
+ * merged (kdf_prefilter_export* / kdf_prefilter_merge* below) until every rank holds the merged sieve, every rank arms
+ * and counts its share again: all ranks admit the same keys, and after the owner exchange of the local tables
+ * (kdf_export_parts*, kdf_add_pairs_multi_dev) the owners hold exactly {(key, full count) : value(cell(key)) >= L} --
+ * the contract above; `dump -L m`, m >= L, is identical to the plain sharded count's.  The owner tables themselves
+ * never take a prefilter (hash_shift, refused above).  So far this has only run as several ranks on ONE GPU.
  * Stats (kdf_get_stat): "prefilter_state" (0 off / 1 tallying / 2 armed), "prefilter_min_count",
- * "prefilter_log2_cells", "prefilter_bytes", "prefilter_windows" (windows tallied), and under kdf_profile(h, 1)
- * "prefilter_us" / "prefilter_passes" (the tally kernel, HIP events). */
+ * "prefilter_log2_cells", "prefilter_bytes", "prefilter_windows" (windows THIS engine tallied: a merge does not touch
+ * it), "prefilter_merged_words" (words written by merges since begin), and under kdf_profile(h, 1) "prefilter_us" /
+ * "prefilter_passes" (the tally kernel, HIP events), "prefilter_merge_us" / "prefilter_merge_passes" (the merge kernel). */
 int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells);
 /* Tally one batch of the read stream (host buffers / device buffers of the kdf_stream_words(n_bases) sizes / the batch
  * an upload slot holds, kdf_upload_reads_async).  The stream is read exactly as the count reads it ("Read streams":
@@ -283,6 +290,32 @@ int kdf_prefilter_arm(kdf_engine *h);
 int kdf_prefilter_drop(kdf_engine *h);
 /* cells_by_value[v] = number of cells that read v, v = 0 .. 3 (their sum is 2^log2_cells); tallying or armed. */
 int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]);
+/* The sieve as words: sixteen cells per 64-bit word, cell c in bits [4 (c & 15), +4) of word c >> 4; bits 0..2 of a
+ * nibble are a thermometer code (0 / 1 / 3 / 7 for the values 0..3), bit 3 is clear.  *n_words = 2^(log2_cells - 4).
+ * Tallying or armed; off: KDF_ERR_STATE. */
+int kdf_prefilter_words(kdf_engine *h, uint64_t *n_words);
+/* Copy words [first_word, first_word + n_words) out, to device / host memory.  Read-only, tallying or armed (off:
+ * KDF_ERR_STATE); runs in stream order after the pending tallies and merges and returns when the copy is complete.
+ * A range past the sieve is KDF_ERR_INVALID; n_words == 0 is KDF_OK and copies nothing. */
+int kdf_prefilter_export_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, void *d_words_out);
+int kdf_prefilter_export(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint64_t *words_out);
+/* Saturating sum of `nseg` segments (n_words words each, word i of a segment belongs to sieve word first_word + i)
+ * into the sieve: per cell new = min(own + sum of the segments' values, 3); with replace != 0 the engine's own value
+ * is left out, new = min(sum, 3) -- how a rank takes over a slice another rank has merged.  The value of an incoming
+ * nibble is popcount(bits 0..2), the rule the gate reads by: bit 3 is ignored and a non-thermometer code such as
+ * 0b101 reads as 2; what is written is always 0 / 1 / 3 / 7, so garbage in a segment can never put a code into the
+ * sieve that the tally does not produce.  One kernel launch for all segments; "prefilter_windows" is not changed.
+ *   - only while TALLYING (KDF_ERR_STATE while armed -- the sieve is immutable between arm and drop, partition-time
+ *     gates rely on that -- or off);
+ *   - a range past the sieve, nseg == 0, nseg > 64, a NULL segment: KDF_ERR_INVALID, and nothing is written;
+ *   - n_words == 0 is KDF_OK.
+ * _dev: d_segs is a HOST array of nseg device pointers; the segments must be complete before the call and stay
+ * untouched until kdf_synchronize (the kernel runs in stream order).  The host form stages the segments through the
+ * engine and returns when the merge is complete. */
+int kdf_prefilter_merge_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint32_t nseg,
+                            const void *const *d_segs, int replace);
+int kdf_prefilter_merge(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint32_t nseg,
+                        const uint64_t *const *segs, int replace);
 
 /* ------------------------------------------------ count --if (filter) ---- */
 

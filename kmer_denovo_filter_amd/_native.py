@@ -108,6 +108,11 @@ SYMBOLS = [
     ("kdf_prefilter_arm", c_int, [_P]),
     ("kdf_prefilter_drop", c_int, [_P]),
     ("kdf_prefilter_fill", c_int, [_P, POINTER(c_uint64)]),
+    ("kdf_prefilter_words", c_int, [_P, POINTER(c_uint64)]),
+    ("kdf_prefilter_export_dev", c_int, [_P, c_uint64, c_uint64, _P]),
+    ("kdf_prefilter_export", c_int, [_P, c_uint64, c_uint64, _P]),
+    ("kdf_prefilter_merge_dev", c_int, [_P, c_uint64, c_uint64, c_uint32, _P, c_int]),
+    ("kdf_prefilter_merge", c_int, [_P, c_uint64, c_uint64, c_uint32, _P, c_int]),
 ]
 
 _lib = None

@@ -566,6 +566,10 @@ struct kdf_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pf_ev;   // tally kernels under kdf_profile (stats "prefilter_us", "prefilter_passes")
     double prof_pf_ms = 0.0;
     uint64_t prof_pf_passes = 0;
+    uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pfm_ev;  // kdf_pf_merge_kernel under kdf_profile (stats "prefilter_merge_us", "prefilter_merge_passes")
+    double prof_pfm_ms = 0.0;
+    uint64_t prof_pfm_passes = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_depth_ev;   // kdf_depth_kernel under kdf_profile (stats "depth_us", "depth_passes")
     double prof_depth_ms = 0.0;
     uint64_t prof_depth_passes = 0;
@@ -1544,6 +1548,32 @@ static void pf_prof_collect(kdf_engine *h) {
         (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
     }
     h->prof_pf_ev.clear();
+    for (auto &ev : h->prof_pfm_ev) {
+        float ms = 0.f;
+        (void)hipEventSynchronize(ev.second);
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_pfm_ms += ms; h->prof_pfm_passes++; }
+        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+    }
+    h->prof_pfm_ev.clear();
+}
+
+// merge `nseg` device segments of n_words words into sieve words [first_word, first_word + n_words): one launch
+static int pf_merge_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint32_t nseg, const unsigned long long *const *d_segs, bool replace) {
+    if (n_words == 0) return KDF_OK;
+    KdfPfSegs sg{};
+    for (uint32_t s = 0; s < nseg; ++s) sg.seg[s] = d_segs[s];
+    sg.nseg = nseg;
+    const uint32_t head = (uint32_t)(first_word & 1);             // the word before the first pair of 16 aligned bytes
+    const uint64_t n_pairs = (n_words - head) / 2;
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_pairs + 255) / 256, (uint64_t)h->n_cu * 8));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    if (replace) hipLaunchKernelGGL(kdf_pf_merge_kernel<true>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
+    else hipLaunchKernelGGL(kdf_pf_merge_kernel<false>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
+    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_pfm_ev.emplace_back(e0, e1); }
+    HIPCHK(h, hipGetLastError());
+    h->stat_pf_merged_words += n_words;
+    return KDF_OK;
 }
 
 static void depth_prof_collect(kdf_engine *h) {
@@ -2834,6 +2864,7 @@ int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells) 
     HIPCHK(h, hipMemsetAsync(words, 0, bytes, h->stream));
     HIPCHK(h, hipMemsetAsync(ctr, 0, (KDF_SHARDS * 16 + 4) * 8, h->stream));
     h->pf_state = PF_TALLYING;
+    h->stat_pf_merged_words = 0;
     return KDF_OK;
 }
 
@@ -2908,6 +2939,87 @@ int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]) {
     cells_by_value[1] = ge[0] - ge[1];
     cells_by_value[2] = ge[1] - ge[2];
     cells_by_value[3] = ge[2];
+    return KDF_OK;
+}
+
+// [first_word, first_word + n_words) inside the sieve (the prefilter is not off)
+#define PF_NEED_RANGE(h, fn) \
+    do { const uint64_t total_ = 1ull << ((h)->pf.log2_cells - 4); \
+         if (first_word > total_ || n_words > total_ - first_word) \
+             return fail(h, KDF_ERR_INVALID, "%s: words [%llu, +%llu) reach past the sieve's %llu words (kdf_prefilter_words)", fn, \
+                         (unsigned long long)first_word, (unsigned long long)n_words, (unsigned long long)total_); } while (0)
+
+int kdf_prefilter_words(kdf_engine *h, uint64_t *n_words) {
+    if (!h || !n_words) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_words: NULL pointer");
+    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_words: no prefilter (kdf_prefilter_begin)");
+    *n_words = 1ull << (h->pf.log2_cells - 4);
+    return KDF_OK;
+}
+
+int kdf_prefilter_export_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, void *d_words_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export_dev: no prefilter (kdf_prefilter_begin)");
+    PF_NEED_RANGE(h, "kdf_prefilter_export_dev");
+    if (n_words == 0) return KDF_OK;
+    if (!d_words_out) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_export_dev: NULL output");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(d_words_out, h->pf.words + first_word, n_words * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_prefilter_export(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint64_t *words_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export: no prefilter (kdf_prefilter_begin)");
+    PF_NEED_RANGE(h, "kdf_prefilter_export");
+    if (n_words == 0) return KDF_OK;
+    if (!words_out) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_export: NULL output");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(words_out, h->pf.words + first_word, n_words * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+// the checks both merge forms share (nothing is written when one fails)
+static int pf_merge_check(kdf_engine *h, const char *fn, uint64_t first_word, uint64_t n_words, uint32_t nseg, const void *const *segs) {
+    if (h->pf_state != PF_TALLYING)
+        return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; sieves are merged between kdf_prefilter_begin and kdf_prefilter_arm", fn,
+                    h->pf_state == PF_ARMED ? "armed (its sieve is immutable: partition-time gates rely on that)" : "off");
+    PF_NEED_RANGE(h, fn);
+    if (nseg == 0 || nseg > KDF_PF_MAX_SEGS) return fail(h, KDF_ERR_INVALID, "%s: nseg %u: must be 1..%d", fn, nseg, KDF_PF_MAX_SEGS);
+    if (!segs) return fail(h, KDF_ERR_INVALID, "%s: NULL segment array", fn);
+    for (uint32_t s = 0; s < nseg; ++s)
+        if (!segs[s]) return fail(h, KDF_ERR_INVALID, "%s: segment %u is NULL", fn, s);
+    return KDF_OK;
+}
+
+int kdf_prefilter_merge_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint32_t nseg, const void *const *d_segs, int replace) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    { int rc = pf_merge_check(h, "kdf_prefilter_merge_dev", first_word, n_words, nseg, d_segs); if (rc) return rc; }
+    HIPCHK(h, hipSetDevice(h->device));
+    return pf_merge_dev(h, first_word, n_words, nseg, (const unsigned long long *const *)d_segs, replace != 0);
+}
+
+int kdf_prefilter_merge(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint32_t nseg, const uint64_t *const *segs, int replace) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    { int rc = pf_merge_check(h, "kdf_prefilter_merge", first_word, n_words, nseg, (const void *const *)segs); if (rc) return rc; }
+    if (n_words == 0) return KDF_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    // staged piece by piece (at most 256 MB of staging): segment s of a piece at stage[0] + s * piece words
+    const uint64_t piece = std::max<uint64_t>(2, std::min<uint64_t>(n_words + (n_words & 1), ((1ull << 25) / nseg) & ~1ull));
+    { int rc = stage_reserve(h, 0, (size_t)piece * nseg * 8); if (rc) return rc; }
+    unsigned long long *st = (unsigned long long *)h->stage[0];
+    const unsigned long long *d[KDF_PF_MAX_SEGS];
+    for (uint64_t w0 = 0; w0 < n_words; w0 += piece) {
+        const uint64_t m = std::min<uint64_t>(piece, n_words - w0);
+        for (uint32_t s = 0; s < nseg; ++s) {
+            HIPCHK(h, hipMemcpyAsync(st + (size_t)s * piece, segs[s] + w0, m * 8, hipMemcpyHostToDevice, h->stream));
+            d[s] = st + (size_t)s * piece;
+        }
+        int rc = pf_merge_dev(h, first_word + w0, m, nseg, d, replace != 0);
+        if (rc) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));                  // (the caller's arrays are free again on return)
     return KDF_OK;
 }
 
@@ -3007,6 +3119,7 @@ int kdf_profile(kdf_engine *h, int enable) {
     h->prof_histo_ms = 0.0; h->prof_histo_passes = 0;
     pf_prof_collect(h);
     h->prof_pf_ms = 0.0; h->prof_pf_passes = 0;
+    h->prof_pfm_ms = 0.0; h->prof_pfm_passes = 0;
     depth_prof_collect(h);
     h->prof_depth_ms = 0.0; h->prof_depth_passes = 0;
     hits_prof_collect(h);
@@ -3118,6 +3231,9 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     }
     else if (n == "prefilter_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pf_ms * 1000.0 + 0.5); }
     else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
+    else if (n == "prefilter_merged_words") *value = h->pf_state == PF_OFF ? 0 : (int64_t)h->stat_pf_merged_words;
+    else if (n == "prefilter_merge_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pfm_ms * 1000.0 + 0.5); }
+    else if (n == "prefilter_merge_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pfm_passes; }
     else if (n == "depth_us") { depth_prof_collect(h); *value = (int64_t)(h->prof_depth_ms * 1000.0 + 0.5); }
     else if (n == "depth_passes") { depth_prof_collect(h); *value = (int64_t)h->prof_depth_passes; }
     else if (n == "hits_us") { hits_prof_collect(h); *value = (int64_t)(h->prof_hits_ms * 1000.0 + 0.5); }

@@ -177,3 +177,83 @@ __global__ __launch_bounds__(256) void kdf_pf_fill_kernel(const unsigned long lo
         if (c) atomicAdd(&out3[2], c);
     }
 }
+
+// ---- merge of sieves (include/kdf.h, "two-pass counting": several ranks) -----------------------------------------------------
+// A cell is min(sightings, 3), so the saturating sum of the ranks' cells is the cell one engine would have tallied over
+// all of their reads.  SWAR on whole words, sixteen cells at a time: the value of a nibble is the number of its planes
+// A, B, C that are set (what kdf_pf_admits reads; bit 3 is ignored, a non-thermometer code such as 0b101 reads as 2),
+// values are summed with a clamp at 3 after every segment (3 + 3 = 6 still fits a nibble), and the result is written
+// as the code the tally writes: 0 / 1 / 3 / 7, bit 3 clear -- whatever a segment holds, no other code reaches the sieve.
+#define KDF_PF_MAX_SEGS 64
+
+struct KdfPfSegs {                        // the segments of one merge call (device pointers), by value
+    const unsigned long long *seg[KDF_PF_MAX_SEGS];
+    uint32_t nseg;
+};
+
+// two words at an address that is only known to be a multiple of 8 (a segment need not start where a sieve word pair does)
+typedef unsigned long long kdf_pf_w2 __attribute__((ext_vector_type(2), aligned(8)));
+
+__device__ __forceinline__ uint64_t kdf_pf_values(uint64_t w) {           // per nibble: planes set, 0..3
+    const uint64_t M1 = 0x1111111111111111ull;
+    return (w & M1) + ((w >> 1) & M1) + ((w >> 2) & M1);
+}
+
+__device__ __forceinline__ uint64_t kdf_pf_sat_add(uint64_t acc, uint64_t v) {   // per nibble: min(acc + v, 3), both <= 3
+    const uint64_t s = acc + v;                                                  // <= 6: no carry into the next nibble
+    const uint64_t g = (s >> 2) & 0x1111111111111111ull;                         // 4, 5, 6 have bit 2 set
+    return (s | g | (g << 1)) & 0x3333333333333333ull;
+}
+
+__device__ __forceinline__ uint64_t kdf_pf_encode(uint64_t v) {           // per nibble: 0 / 1 / 2 / 3 -> 0 / 1 / 3 / 7
+    const uint64_t M1 = 0x1111111111111111ull;
+    const uint64_t b0 = v & M1, b1 = (v >> 1) & M1;
+    return (b0 | b1) | (b1 << 1) | ((b0 & b1) << 2);
+}
+
+template <bool REPLACE>
+__device__ __forceinline__ void kdf_pf_merge_word(unsigned long long *__restrict__ own, const KdfPfSegs &sg, uint64_t i) {
+    uint64_t acc = REPLACE ? 0ull : kdf_pf_values(own[i]);
+    for (uint32_t s = 0; s < sg.nseg; ++s) acc = kdf_pf_sat_add(acc, kdf_pf_values(sg.seg[s][i]));
+    own[i] = kdf_pf_encode(acc);
+}
+
+// own: the engine's slice (own[i] is sieve word first_word + i), seg[s][i] the same word of segment s.  `head` (0 / 1)
+// words come before the first sieve word pair, `n_pairs` pairs of 16 aligned bytes follow (one pair per lane per
+// load, grid-stride), and what is left (0 / 1 word) is the tail.  No atomics, no LDS: (nseg + 1) reads and 1 write per word
+// (nseg reads with REPLACE).  nseg and the pointers are uniform: scalar loads from the kernel arguments.
+template <bool REPLACE>
+__global__ __launch_bounds__(256) void kdf_pf_merge_kernel(unsigned long long *__restrict__ own, KdfPfSegs sg,
+                                                          uint64_t n_words, uint32_t head, uint64_t n_pairs)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t == 0 && head) kdf_pf_merge_word<REPLACE>(own, sg, 0);
+    if (t == 1 && head + 2 * n_pairs < n_words) kdf_pf_merge_word<REPLACE>(own, sg, n_words - 1);
+    const uint64_t M1 = 0x1111111111111111ull;
+    for (uint64_t p = t; p < n_pairs; p += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = head + 2 * p;
+        uint64_t a0 = 0, a1 = 0;
+        if constexpr (!REPLACE) {
+            const kdf_pf_w2 o = *(const kdf_pf_w2 *)(own + i);
+            a0 = kdf_pf_values(o.x); a1 = kdf_pf_values(o.y);
+        }
+        uint32_t s = 0;
+        for (; s + 4 <= sg.nseg; s += 4) {                         // four 16-byte loads in flight, one clamp: 3 + 4 x 3 = 15 fits a nibble
+            kdf_pf_w2 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *(const kdf_pf_w2 *)(sg.seg[s + u] + i);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { a0 += kdf_pf_values(v[u].x); a1 += kdf_pf_values(v[u].y); }
+            const uint64_t g0 = ((a0 >> 2) | (a0 >> 3)) & M1, g1 = ((a1 >> 2) | (a1 >> 3)) & M1;   // >= 4: bit 2 or bit 3
+            a0 = (a0 | g0 | (g0 << 1)) & 0x3333333333333333ull;
+            a1 = (a1 | g1 | (g1 << 1)) & 0x3333333333333333ull;
+        }
+        for (; s < sg.nseg; ++s) {
+            const kdf_pf_w2 v = *(const kdf_pf_w2 *)(sg.seg[s] + i);
+            a0 = kdf_pf_sat_add(a0, kdf_pf_values(v.x)); a1 = kdf_pf_sat_add(a1, kdf_pf_values(v.y));
+        }
+        kdf_pf_w2 r;
+        r.x = kdf_pf_encode(a0); r.y = kdf_pf_encode(a1);
+        *(kdf_pf_w2 *)(own + i) = r;
+    }
+}

@@ -58,11 +58,16 @@ def _child_key_parts(child_bam, device=0, world=1, kmer_size=31):
     return max(1, int(-(-need // max(1.0, 0.7 * free.value))))
 
 
+# How the last child count of this process ran: {"mode": "plain" | "two_pass" | "two_pass_sharded", "L", "log2_cells",
+# "world"} (L and log2_cells 0 without a prefilter).  For logs and tests; nothing reads it to decide anything.
+LAST_CHILD_COUNT = None
+
+
 def _child_prefilter_min(min_child_count, world):
-    """The L of the two-pass child count, or 0 when it is off: opt-in (``KDF_PREFILTER=1``), one process (a rank of a
-    sharded count sees only its share of the reads: its tallies would under-count), and a dump bound of at least 2.
-    A cell of the sieve saturates at 3, so ``-L 5`` tallies with 3 and dumps with 5."""
-    if os.environ.get("KDF_PREFILTER") != "1" or world != 1 or min_child_count < 2:
+    """The L of the two-pass child count, or 0 when it is off: opt-in (``KDF_PREFILTER=1``) and a dump bound of at least
+    2.  A cell of the sieve saturates at 3, so ``-L 5`` tallies with 3 and dumps with 5.  Several ranks: every rank
+    tallies its share of the reads and the sieves are merged before any rank counts (_child_count_two_pass_sharded)."""
+    if os.environ.get("KDF_PREFILTER") != "1" or min_child_count < 2:
         return 0
     return min(int(min_child_count), 3)
 
@@ -73,6 +78,7 @@ def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, thre
     ``dump -L min_child_count`` as usual, one slice.  Returns the candidates (device keys), or None when the sieve plus the
     table of the admitted keys do not fit the device (the caller then counts in key_parts slices without a prefilter)."""
     from .. import _native
+    global LAST_CHILD_COUNT
     L = _child_prefilter_min(min_child_count, 1)
     hint = _engine_capacity_hint(jf_hash_size, child_bam)            # distinct k-mers expected, errors included
     log2_cells = min(38, max(16, (8 * max(int(hint), 1) - 1).bit_length()))
@@ -96,7 +102,86 @@ def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, thre
                     L, log2_cells, fill[0], fill[1], fill[2], fill[3], windows, eng.get_stat("prefilter_windows"), distinct, cap)
         logger.info("Dumping child k-mers with count >= %d…", min_child_count)
         dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
+        LAST_CHILD_COUNT = {"mode": "two_pass", "L": L, "log2_cells": log2_cells, "world": 1}
         return devkeys.select([(dlo, dhi)])
+
+
+def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start):
+    """The two-pass child count over several ranks (kdf.h "two-pass counting": several ranks).  Every rank tallies its
+    BGZF ranges; the sieves are merged with a saturating sum, so every rank holds the sieve of the WHOLE sample and
+    admits the same keys; every rank counts its ranges again, gated; then the owner exchange and ``dump -L`` on the
+    owners as in the plain sharded count.  The owner engine never has a prefilter.  Returns the gathered candidates, or
+    None -- ON EVERY RANK -- when the sieve or a table did not fit on ANY rank: a rank that runs out of memory must not
+    leave the others waiting in a collective, so the ranks all-reduce an "it went through here" flag after every step
+    that can fail locally and before the next collective."""
+    import torch
+    from .. import _native
+    from ..distributed import EngineOps, OwnerPartitionedCount
+    global LAST_CHILD_COUNT
+    world, rank, host = dist_env.world_rank()
+    L = _child_prefilter_min(min_child_count, world)
+    hint = _engine_capacity_hint(jf_hash_size, child_bam)            # distinct k-mers expected in the WHOLE sample
+    proposal = min(38, max(16, (8 * max(int(hint), 1) - 1).bit_length()))
+    eng = owner_eng = None
+    try:
+        eng = mirror_engine(kmer_size, capacity_hint=1 << 16, device=_device())
+        owner_eng = mirror_engine(kmer_size, capacity_hint=1 << 16, device=eng.device)
+        dev = torch.device("cuda", eng.device)
+        merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
+        log2_cells = merger.agree_log2_cells(proposal)
+        state = {"why": None}
+
+        def step(fn):
+            """run a rank-local step; True iff it went through on EVERY rank"""
+            ok = True
+            try:
+                fn()
+            except KdfError as e:
+                if e.code != _native.KDF_ERR_NOMEM:
+                    raise
+                ok, state["why"] = False, str(e)
+            return merger.all_ok(ok)
+
+        def give_up(what):
+            logger.info("Two-pass child count over %d ranks: %s did not fit the device on %s (%s); counting in key-space "
+                        "slices without a prefilter", world, what, "this rank" if state["why"] else "another rank", state["why"] or "-")
+            return None
+
+        def tally():
+            eng.prefilter_begin(L, log2_cells)
+            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=True)
+
+        if not step(tally):
+            return give_up("a sieve of 2^%d cells" % log2_cells)
+        merger.prefilter_merge()                                     # ends armed: every rank holds the sieve of all reads
+        fill = eng.prefilter_fill()                                  # (the same on every rank: the global fill)
+        tallied = merger.prefilter_windows()
+        st = {}
+
+        def count():
+            eng.reserve(fill[L] + (fill[3] if L == 2 else 0) + 1)    # at most about one admitted key per cell that reads >= L
+            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+            st["stats"] = eng.stats()
+
+        if not step(count):
+            return give_up("the table of the admitted k-mers")
+        cap, distinct, windows = st["stats"]
+        logger.info("Child k-mer counting complete (%s, two passes over %d ranks, L=%d, sieve 2^%d cells reading 0/1/2/3: %d/%d/%d/%d "
+                    "(all ranks), %d windows tallied by all ranks; this rank: %d windows admitted, %d distinct stored, table %d slots)",
+                    _format_elapsed(time.monotonic() - extract_start), world, L, log2_cells, fill[0], fill[1], fill[2], fill[3],
+                    tallied, windows, distinct, cap)
+        logger.info("Dumping child k-mers with count >= %d…", min_child_count)
+        if not step(merger.exchange):
+            return give_up("an owner table")
+        dlo, dhi = devkeys.dump_ge(owner_eng, min_child_count, eng.device)
+        dlo, dhi = dist_env.all_gather_keys(dlo, dhi)               # every rank holds the whole candidate set
+        LAST_CHILD_COUNT = {"mode": "two_pass_sharded", "L": L, "log2_cells": log2_cells, "world": world,
+                            "exchange_pairs": merger.last_exchange_pairs}
+        return devkeys.select([(dlo, dhi)])
+    finally:
+        for e in (owner_eng, eng):
+            if e is not None:
+                e.close()
 
 
 def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_count, threads, tmpdir,
@@ -104,6 +189,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     """Module 1: count every canonical child k-mer, keep count >= min_child_count.
 
     Returns (child_candidates_fa, n_candidates)."""
+    global LAST_CHILD_COUNT
     if jf_hash_size is None:
         jf_hash_size = _estimate_jf_hash_size(child_bam, kmer_size, default="1G")
     logger.info("Extracting child k-mers from BAM (k=%d, jf hash size=%s)…", kmer_size, jf_hash_size)
@@ -118,8 +204,10 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     dump_start = time.monotonic()
     try:
         cand = None
+        LAST_CHILD_COUNT = {"mode": "plain", "L": 0, "log2_cells": 0, "world": world}
         if _child_prefilter_min(min_child_count, world):
-            cand = _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start)
+            two_pass = _child_count_two_pass if world == 1 else _child_count_two_pass_sharded
+            cand = two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start)
         if cand is not None:
             lo, hi = devkeys.to_host(*cand)
         else:

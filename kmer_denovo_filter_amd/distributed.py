@@ -21,6 +21,12 @@ SURVEY.md section 8e rather than a reference file:
   global number of survivors.  This is Jellyfish's ``merge`` (jellyfish_wrappers.py:335-366)
   done over xGMI.
 
+  With the two-pass count (``prefilter_begin`` / ``tally_local`` / ``prefilter_merge``, kdf.h "two-pass counting")
+  every rank first tallies its shard into a counting sieve; the sieves are merged with a saturating sum (a
+  hand-made reduce-scatter + all-gather, the sum runs in ``kdf_pf_merge_kernel``) so that every rank holds the
+  sieve of the WHOLE sample, and the local counts that follow store only the keys that sieve admits: smaller local
+  tables and a smaller all-to-all, the same ``dump -L``.
+
 Both classes are written against a tiny adapter (``TableOps``) so that the
 sharding / exchange logic runs under gloo on CPU tensors in the tests, with the
 oracle standing in for the table; on a GPU the adapter is ``EngineOps`` (the HIP
@@ -71,6 +77,16 @@ class TableOps:
     def stats(self) -> Tuple[int, int, int]: raise NotImplementedError
     def histogram(self, high: int) -> torch.Tensor: raise NotImplementedError   # int64[high + 2] on self.device
     def count_stats(self) -> dict: raise NotImplementedError
+
+    # two-pass counting: the counting sieve of kdf.h.  Words travel as int64 tensors on self.device.
+    def prefilter_begin(self, min_count: int, log2_cells: int): raise NotImplementedError
+    def prefilter_tally_stream(self, packed: torch.Tensor, invalid: torch.Tensor, n_bases: int): raise NotImplementedError
+    def prefilter_words(self) -> int: raise NotImplementedError
+    def prefilter_export(self, first: int, n: int) -> torch.Tensor: raise NotImplementedError
+    def prefilter_merge(self, first: int, segments: List[torch.Tensor], replace: bool = False): raise NotImplementedError
+    def prefilter_arm(self): raise NotImplementedError
+    def prefilter_drop(self): raise NotImplementedError
+    def prefilter_windows(self) -> int: raise NotImplementedError            # windows THIS table tallied
 
     def add_pairs_segments(self, segments):
         """Sum the segments [(lo, hi, cnt), ...] received from the source ranks (a table that can merge them
@@ -173,6 +189,41 @@ class EngineOps(TableOps):
         order is the table's bucket order.  (world not a power of two: the owner's keys cover
         2^floor(log2 world) / world of the table; ask for that much more capacity.)"""
         self.e.set_option("hash_shift", max(0, int(world).bit_length() - 1))
+
+    def prefilter_begin(self, min_count, log2_cells):
+        self.e.prefilter_begin(min_count, log2_cells)
+
+    def prefilter_tally_stream(self, packed, invalid, n_bases):
+        self._sync()
+        self.e.prefilter_add_dev(packed.data_ptr(), invalid.data_ptr(), n_bases)
+
+    def prefilter_words(self):
+        return self.e.prefilter_words()
+
+    def prefilter_export(self, first, n):
+        out = torch.empty(int(n), dtype=torch.int64, device=self.device)
+        if n:
+            self._sync()
+            self.e.prefilter_export_dev(out.data_ptr(), first, n)   # complete on return
+        return out
+
+    def prefilter_merge(self, first, segments, replace=False):
+        """All segments (int64 tensors of one length in HBM) in ONE kernel launch (``kdf_pf_merge_kernel``)."""
+        segs = [s.contiguous() for s in segments]
+        if not segs or segs[0].numel() == 0:
+            return
+        self._sync()
+        self.e.prefilter_merge_dev([s.data_ptr() for s in segs], first, segs[0].numel(), replace)
+        self.e.synchronize()                                        # (the segments are the caller's again)
+
+    def prefilter_arm(self):
+        self.e.prefilter_arm()
+
+    def prefilter_drop(self):
+        self.e.prefilter_drop()
+
+    def prefilter_windows(self):
+        return self.e.get_stat("prefilter_windows")
 
     def query(self, lo, hi):
         out = torch.zeros(lo.numel(), dtype=torch.int32, device=self.device)
@@ -277,6 +328,7 @@ class OwnerPartitionedCount:
             self.owner.prepare_owner(self.world)
         self._local_stats = (0, 0, 0)
         self.last_exchange_pairs = 0
+        self.last_prefilter_rounds = 0
 
     def local_stats(self):
         """(capacity, distinct, windows) of this rank's LOCAL table.  Reading them applies what the count calls have
@@ -364,6 +416,101 @@ class OwnerPartitionedCount:
         if isinstance(packed, int):
             raise TypeError("pass the stream tensors, not raw pointers")
         self.local.count_stream(packed, invalid, n_bases)
+
+    # ---- two-pass counting over the ranks (kdf.h "two-pass counting": several ranks) ----------------------------------
+    # prefilter_begin -> tally_local over every batch of the shard -> prefilter_merge (ends armed) -> count_local over
+    # the same batches (gated by the engine) -> exchange / merge as always -> prefilter_drop.  The owner table never
+    # has a prefilter.
+
+    def _cdev(self):
+        return torch.device("cpu") if self.host else self.device
+
+    def all_ok(self, ok: bool) -> bool:
+        """True iff ``ok`` on every rank (one scalar all-reduce): the ranks decide TOGETHER whether a step that can fail
+        on one of them alone (a sieve or a table that does not fit its device) went through, before any of them enters
+        the next collective."""
+        if self.world == 1:
+            return bool(ok)
+        f = torch.tensor([1 if ok else 0], dtype=torch.int64, device=self._cdev())
+        dist.all_reduce(f, op=dist.ReduceOp.MIN, group=self.group)
+        return bool(f.item())
+
+    def agree_log2_cells(self, log2_cells: int) -> int:
+        """The largest of the ranks' proposals (all-reduce(max)): the merge needs sieves of one size."""
+        if self.world == 1:
+            return int(log2_cells)
+        if not log2_cells:
+            raise ValueError("OwnerPartitionedCount.prefilter_begin: with more than one rank log2_cells must be given "
+                             "(the engine's own choice depends on each rank's capacity hint; the sieves must have one size)")
+        t = torch.tensor([int(log2_cells)], dtype=torch.int64, device=self._cdev())
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        return int(t.item())
+
+    def prefilter_begin(self, min_count: int, log2_cells: int = 0) -> int:
+        """Start pass 1 on the LOCAL table with the sieve size the ranks agree on; returns that log2_cells."""
+        s = self.agree_log2_cells(log2_cells)
+        self.local.prefilter_begin(int(min_count), s)
+        return s
+
+    def tally_local(self, packed, invalid, n_bases: int):
+        """Tally one more batch of this rank's read shard into its sieve (no communication)."""
+        if isinstance(packed, int):
+            raise TypeError("pass the stream tensors, not raw pointers")
+        self.local.prefilter_tally_stream(packed, invalid, n_bases)
+
+    def prefilter_slices(self, n_words: int) -> List[int]:
+        """world + 1 bounds: rank r merges sieve words [floor(r n / world), floor((r + 1) n / world))."""
+        return [r * n_words // self.world for r in range(self.world + 1)]
+
+    def prefilter_merge(self, chunk_words: Optional[int] = None):
+        """Saturating sum of every rank's sieve into every rank's sieve, then arm.  A hand-made reduce-scatter +
+        all-gather: every rank sends slice j to rank j (``all_to_all_single``), rank j merges the world - 1 received
+        segments into its own slice with ONE ``prefilter_merge`` call, the merged slices are all-gathered and written
+        with replace.  Per-rank traffic 2 x sieve bytes x (world - 1) / world, in rounds of at most ``chunk_words``
+        words per peer (default: staging below 1 GB)."""
+        if self.world > 1:
+            n = self.local.prefilter_words()
+            W, me = self.world, self.rank
+            if chunk_words is None:
+                chunk_words = max(2, (10 ** 9 // (8 * 3 * W)) & ~1)     # send + receive + gather buffers: 3 W chunk words
+            chunk_words = max(1, int(chunk_words))
+            b = self.prefilter_slices(n)
+            longest = max(b[j + 1] - b[j] for j in range(W))
+            cdev = self._cdev()
+            self.last_prefilter_rounds = 0
+            for off in range(0, longest, chunk_words):
+                first = [min(b[j] + off, b[j + 1]) for j in range(W)]
+                c = [min(chunk_words, b[j + 1] - first[j]) for j in range(W)]   # this round's piece of slice j (the last ones are ragged)
+                # reduce-scatter: piece j goes to rank j
+                s_split = [0 if j == me else c[j] for j in range(W)]
+                r_split = [0 if j == me else c[me] for j in range(W)]
+                send = torch.cat([self.local.prefilter_export(first[j], s_split[j]) for j in range(W)]).to(cdev)
+                recv = torch.empty(sum(r_split), dtype=torch.int64, device=cdev)
+                dist.all_to_all_single(recv, send, output_split_sizes=r_split, input_split_sizes=s_split, group=self.group)
+                if c[me]:
+                    recv = recv.to(self.device)
+                    self.local.prefilter_merge(first[me], list(recv.split(c[me])), replace=False)
+                # all-gather of the merged pieces (padded to the longest piece of the round)
+                cmax = max(c)
+                mine = torch.zeros(cmax, dtype=torch.int64, device=cdev)
+                mine[:c[me]] = self.local.prefilter_export(first[me], c[me]).to(cdev)
+                outs = [torch.empty_like(mine) for _ in range(W)]
+                dist.all_gather(outs, mine, group=self.group)
+                for j in range(W):
+                    if j != me and c[j]:
+                        self.local.prefilter_merge(first[j], [outs[j][:c[j]].to(self.device)], replace=True)
+                self.last_prefilter_rounds += 1
+        self.local.prefilter_arm()
+
+    def prefilter_drop(self):
+        self.local.prefilter_drop()
+
+    def prefilter_windows(self) -> int:
+        """Windows tallied by all ranks together: all-reduce(sum) of the ranks' ``prefilter_windows``."""
+        t = torch.tensor([int(self.local.prefilter_windows())], dtype=torch.int64, device=self._cdev())
+        if self.world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return int(t.item())
 
     def merge(self, min_count: int = 1) -> int:
         """Exchange the local (key, count) pairs to their owners; returns the global

@@ -286,6 +286,46 @@ class KmerEngine:
         self._ck(self._lib.kdf_prefilter_fill(self._h, v))
         return [int(x) for x in v]
 
+    def prefilter_words(self) -> int:
+        """Number of 64-bit words of the sieve (sixteen cells each): 2^(log2_cells - 4)."""
+        n = c_uint64(0)
+        self._ck(self._lib.kdf_prefilter_words(self._h, byref(n)))
+        return n.value
+
+    def prefilter_export(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Words [first, first + n) of the sieve (n None: to its end) as a numpy uint64 array; tallying or armed."""
+        if n is None:
+            n = self.prefilter_words() - int(first)
+        out = np.empty(max(int(n), 0), dtype=np.uint64)
+        self._ck(self._lib.kdf_prefilter_export(self._h, int(first), int(n), _vp(out)))
+        return out
+
+    def prefilter_export_dev(self, d_out: int, first: int, n: int):
+        """The same into HBM (raw device pointer to n words); complete on return."""
+        self._ck(self._lib.kdf_prefilter_export_dev(self._h, int(first), int(n), c_void_p(d_out) if d_out else None))
+        return self
+
+    def prefilter_merge(self, segments, first: int = 0, replace: bool = False):
+        """Saturating sum of the segments (uint64 arrays of one length: other engines' exports of the same words) into
+        words [first, first + len) of the sieve; ``replace``: the sieve's own values are left out.  Only while tallying."""
+        segs = [np.ascontiguousarray(s, dtype=np.uint64) for s in segments]
+        n = len(segs[0]) if segs else 0
+        if any(s.ndim != 1 or len(s) != n for s in segs):
+            raise ValueError("prefilter_merge: the segments must be 1-d arrays of one length")
+        if n == 0:                                                  # (an empty array need not have an address)
+            segs = [np.zeros(1, dtype=np.uint64) for _ in segs]
+        ptrs = (c_void_p * max(len(segs), 1))(*[s.ctypes.data for s in segs])
+        self._ck(self._lib.kdf_prefilter_merge(self._h, int(first), n, len(segs), ptrs, 1 if replace else 0))
+        return self
+
+    def prefilter_merge_dev(self, d_segments, first: int, n: int, replace: bool = False):
+        """The same with the segments in HBM (raw device pointers to n words each), ONE kernel launch for all of them;
+        runs in stream order: synchronize() before the segments are reused."""
+        segs = list(d_segments)
+        ptrs = (c_void_p * max(len(segs), 1))(*[p or None for p in segs])
+        self._ck(self._lib.kdf_prefilter_merge_dev(self._h, int(first), int(n), len(segs), ptrs, 1 if replace else 0))
+        return self
+
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
         if self.long:
