@@ -649,6 +649,78 @@ int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint3
 int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, void *d_counts_out,
                         uint64_t cap, int sorted, uint64_t *n_out);
 
+/* -------------------------------------------------------- read spool ---- */
+
+/* Keep a sample's packed read stream resident and replay it.  Every pass over a BAM goes through the host feeder, which
+ * is many times slower than the count, and a sample counted in key-space slices ("key_parts") or
+ * in two passes (kdf_prefilter_*) is read once per pass.  The packed stream is 3 bits per position: a spool keeps the
+ * batches of the FIRST pass, and every later pass replays them into an engine at the device's rate.
+ *
+ * A spool is an object of its own, not part of an engine: one spool feeds any number of engines on its device (the
+ * tally engine, the count engine, a fresh engine per slice), any number of times.  A handle is not thread-safe.
+ *
+ * Layout.  A spool is a list of SEGMENTS; a segment is one read stream in the layout of "Read streams" above: a packed
+ * and a mask buffer of the kdf_stream_words(segment positions) sizes, handed to the `_dev` stream entry points as it lies.
+ *   - a tile is 64 positions (one mask word, two packed words).  A batch of n_bases positions is appended at a tile
+ *     boundary and occupies n_bases / 64 + 1 tiles: its mask bits at and past n_bases, up to the end of its last tile,
+ *     are set and its packed bases there are zero.  A batch whose length is a multiple of 64 so keeps a whole
+ *     all-invalid tile behind it (the engine's pending stream follows the same rule): no window runs from one batch into
+ *     the next.
+ *   - a segment of T tiles is a stream of 64 T positions: T mask and 2 T packed words, then the 2 (all ones) and 4 (zero)
+ *     padding words of kdf_stream_words.
+ *   - the bytes of a segment are a pure function of the appended (packed, invalid, n_bases) triples: whatever the
+ *     sources held at and past n_bases does not reach the spool (the bases of invalid positions BELOW n_bases are kept
+ *     as given).  An append reads at most the kdf_stream_words(n_bases) words of each source buffer.
+ *   - a batch is never split: one that does not fit the room left in the last segment starts a new segment, one longer
+ *     than option "segment_positions" gets a segment of its own size.  A batch of more than 2^31 positions is
+ *     KDF_ERR_INVALID (before anything is allocated); n_bases == 0 is KDF_OK and stores nothing.
+ * Tiers.  Segments are allocated one at a time, when a batch needs one: in HBM (hipMalloc) while "hbm_bytes" stays within
+ * hbm_budget_bytes and the allocation succeeds, then in pinned host memory (hipHostMalloc) within host_budget_bytes,
+ * and after that the append returns KDF_ERR_NOMEM and the spool is OVERFLOWED: further appends and every replay are
+ * KDF_ERR_STATE (a replay would silently count a part of the sample), the segments stored stay readable
+ * (kdf_spool_read_segment), kdf_spool_clear frees everything and resets the mark.  A host-tier batch is normalised by
+ * the same kernel into a device staging buffer and copied out asynchronously; that staging (one batch) and the staging
+ * of kdf_spool_append's host sources are the spool's own and are not charged to the HBM budget.
+ * Ordering.  kdf_spool_append_dev runs on the stream it is given (the source must be complete in that stream's order);
+ * kdf_spool_append_uploaded on the engine's stream, behind the slot's copy, and the slot KEEPS its batch: the caller
+ * then counts or tallies it as before.  kdf_spool_append (host arrays) returns when the arrays may be reused.  Every
+ * append is ordered behind the one before it, whatever streams they ran on, and the spool records an event behind each.
+ * kdf_spool_replay makes the engine's stream wait for the last such event -- no host synchronisation for the HBM tier --
+ * and calls, for every segment in order, kdf_count_reads_dev (mode 0), kdf_count_reads_filtered_dev (mode 1) or
+ * kdf_prefilter_add_reads_dev (mode 2).  Host-tier segments go through the engine's two upload slots
+ * (kdf_upload_reads_async, then kdf_count_uploaded / kdf_prefilter_add_uploaded): the copy of the next host-tier segment
+ * runs under the count of this one; the host waits once for the last append.  A slot that holds a caller's batch when a
+ * replay needs the slots is KDF_ERR_STATE and nothing is replayed.  Every state rule of the target entry point applies
+ * unchanged (count while tallying, count --if without a filter, ...): its error code is returned and its message is
+ * passed on behind "segment i:"; such a refusal comes from the first segment, so nothing was replayed.  Spool and
+ * engine must be on the same device (KDF_ERR_INVALID).  Every key width works, long engines included: the spool knows
+ * nothing about k.
+ * Contract.  After kdf_spool_replay the engine is in exactly the state it would be in had the appended batches been
+ * given to the same entry point one by one: the same (key, count) set, the same `windows`, the same sieve words, the
+ * same gating under "key_parts" and an armed prefilter.  A replay does not change the spool.  Segments must outlive the
+ * work replayed from them: kdf_spool_clear and kdf_spool_destroy synchronise the device first.
+ * Not kept: read offsets.  kdf_scan_reads*, kdf_read_hits* and kdf_read_depth* over a spool need them and are a later
+ * step; Module 3 reads the BAM with another flag filter (0x500) and cannot share the count's spool.
+ * Options (kdf_spool_set_option): "segment_positions" (default 2^30, 2^12 .. 2^31; segments allocated later take it),
+ * "profile" (1: HIP events around every append kernel).  Stats (kdf_spool_get_stat): "segments", "batches", "positions"
+ * (stream positions stored, padding included: 64 x tiles), "bases" (sum of the appended n_bases), "hbm_bytes",
+ * "host_bytes" (segment bytes per tier), "overflowed", "replays", "segment_positions", and under "profile" "append_us" /
+ * "append_passes".  Errors: kdf_spool_error(sp), or kdf_spool_error(NULL) for kdf_spool_create. */
+typedef struct kdf_spool kdf_spool;
+int kdf_spool_create(int device, uint64_t hbm_budget_bytes, uint64_t host_budget_bytes, kdf_spool **out);
+void kdf_spool_destroy(kdf_spool *sp);
+const char *kdf_spool_error(const kdf_spool *sp);
+int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value);
+int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value);
+int kdf_spool_append(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases);
+int kdf_spool_append_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases);
+int kdf_spool_append_uploaded(kdf_spool *sp, kdf_engine *h, int slot);
+int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode);
+/* One segment to host arrays of the kdf_stream_words(*n_positions_out) sizes (tests, debugging); with both arrays NULL
+ * only the size is returned.  Waits for the last append. */
+int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, uint64_t *invalid_out, uint64_t *n_positions_out);
+int kdf_spool_clear(kdf_spool *sp);
+
 #ifdef __cplusplus
 }
 #endif

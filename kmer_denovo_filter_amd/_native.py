@@ -113,6 +113,18 @@ SYMBOLS = [
     ("kdf_prefilter_export", c_int, [_P, c_uint64, c_uint64, _P]),
     ("kdf_prefilter_merge_dev", c_int, [_P, c_uint64, c_uint64, c_uint32, _P, c_int]),
     ("kdf_prefilter_merge", c_int, [_P, c_uint64, c_uint64, c_uint32, _P, c_int]),
+    # read spool: a sample's packed stream kept resident and replayed
+    ("kdf_spool_create", c_int, [c_int, c_uint64, c_uint64, POINTER(_P)]),
+    ("kdf_spool_destroy", None, [_P]),
+    ("kdf_spool_error", c_char_p, [_P]),
+    ("kdf_spool_set_option", c_int, [_P, c_char_p, c_int64]),
+    ("kdf_spool_get_stat", c_int, [_P, c_char_p, POINTER(c_int64)]),
+    ("kdf_spool_append", c_int, [_P, _P, _P, c_uint64]),
+    ("kdf_spool_append_dev", c_int, [_P, _P, _P, _P, c_uint64]),
+    ("kdf_spool_append_uploaded", c_int, [_P, _P, c_int]),
+    ("kdf_spool_replay", c_int, [_P, _P, c_int]),
+    ("kdf_spool_read_segment", c_int, [_P, c_uint64, _P, _P, POINTER(c_uint64)]),
+    ("kdf_spool_clear", c_int, [_P]),
 ]
 
 _lib = None
@@ -177,6 +189,13 @@ def check(rc: int, handle=None):
     if rc != KDF_OK:
         lib = load()
         msg = lib.kdf_last_error(handle)
+        raise KdfError(rc, msg.decode(errors="replace") if msg else "unknown error")
+
+
+def check_spool(rc: int, spool=None):
+    if rc != KDF_OK:
+        lib = load()
+        msg = lib.kdf_spool_error(spool)
         raise KdfError(rc, msg.decode(errors="replace") if msg else "unknown error")
 
 

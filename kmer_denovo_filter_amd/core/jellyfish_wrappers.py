@@ -102,9 +102,10 @@ def _engine_capacity_hint(hash_size, bam_path=None):
     return max(1 << 16, want)
 
 
-def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False):
+def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False, spool=None):
     """``samtools fasta -F 0xD00 bam | jellyfish count ... /dev/fd/0``.  ``tally``: the same reader pipelines feed
-    pass 1 of a two-pass count (the engine's prefilter) instead of the table."""
+    pass 1 of a two-pass count (the engine's prefilter) instead of the table.  ``spool``: a ``ReadSpool`` that also
+    keeps every batch of this pass (``stream_batches_overlapped``)."""
     if str(bam_path).endswith(".cram"):
         raise RuntimeError(
             "jellyfish count failed: CRAM input needs htslib, which the MI355X engine does not link; "
@@ -123,6 +124,8 @@ def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False):
         for j in range(local):
             readers.append(bam_reader(bam_path, max_bases=BATCH_BASES, max_reads=1 << 21, threads=per,
                                       part=rank * local + j, parts=world * local))
+        if spool is not None:
+            return stream_batches_overlapped(engine, readers, filtered, tally=tally, spool=spool)
         return stream_batches_overlapped(engine, readers, filtered, tally=tally)
     finally:
         for rd in readers:

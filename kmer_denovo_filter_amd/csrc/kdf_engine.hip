@@ -312,6 +312,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 // per-window counts and per-read depth rows of a read stream
 #include "kdf_depth.h"
 #include "kdf_hits.h"
+#include "kdf_spool.h"
 
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
@@ -3267,6 +3268,328 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
         *value = (int64_t)v;
     }
     else return fail(h, KDF_ERR_INVALID, "kdf_get_stat: unknown stat %s", name);
+    return KDF_OK;
+}
+
+// ===========================================================================
+// read spool (kdf.h "read spool", kdf_spool.h): a sample's packed stream kept resident and replayed
+// ===========================================================================
+
+struct KsSegment {
+    uint64_t *packed = nullptr, *mask = nullptr;     // 2 cap_tiles + 4 / cap_tiles + 2 words: HBM, or pinned host memory
+    uint64_t cap_tiles = 0, tiles = 0;               // room / used; the segment is a stream of tiles x 64 positions
+    uint64_t bytes = 0;
+    bool host = false;
+};
+struct kdf_spool {
+    int device = 0;
+    uint64_t hbm_budget = 0, host_budget = 0;
+    uint64_t opt_segment_positions = 1ull << 30;
+    std::vector<KsSegment> segs;
+    uint64_t hbm_bytes = 0, host_bytes = 0, batches = 0, bases = 0, replays = 0;
+    bool overflowed = false;
+    hipStream_t stream = nullptr;                    // kdf_spool_append (host sources) runs here
+    hipEvent_t last = nullptr; bool have_last = false;   // behind the latest append, whatever stream it ran on
+    void *stage[4] = {nullptr, nullptr, nullptr, nullptr};   // grow-only: 0/1 a host source's words, 2/3 a host-tier batch before its copy out
+    size_t stage_bytes[4] = {0, 0, 0, 0};
+    bool prof = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
+    double prof_ms = 0.0; uint64_t prof_passes = 0;
+    std::string err;
+};
+
+static int ks_fail(kdf_spool *sp, int code, const char *fmt, ...) {
+    char buf[768];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    if (sp) sp->err = buf; else g_err = buf;
+    return code;
+}
+#define KSCHK(sp, call)                                                                 \
+    do {                                                                                \
+        hipError_t e_ = (call);                                                         \
+        if (e_ != hipSuccess)                                                           \
+            return ks_fail(sp, e_ == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, \
+                           "%s failed: %s", #call, hipGetErrorString(e_));              \
+    } while (0)
+
+static void ks_prof_collect(kdf_spool *sp) {
+    for (auto &pr : sp->prof_ev) {
+        float ms = 0.f;
+        if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
+            sp->prof_ms += ms; ++sp->prof_passes;
+        } else (void)hipGetLastError();
+        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
+    }
+    sp->prof_ev.clear();
+}
+
+// grow-only staging; the buffer's last user is an append, and every append is behind sp->last
+static int ks_stage_reserve(kdf_spool *sp, int i, size_t bytes) {
+    if (sp->stage_bytes[i] >= bytes) return KDF_OK;
+    if (sp->stage[i]) {
+        if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
+        (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0;
+    }
+    const size_t want = bytes + bytes / 8 + 4096;
+    const hipError_t e = hipMalloc(&sp->stage[i], want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); sp->stage[i] = nullptr;
+        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of staging do not fit the device (%s)", want, hipGetErrorString(e));
+    }
+    sp->stage_bytes[i] = want;
+    return KDF_OK;
+}
+
+static void ks_free_all(kdf_spool *sp) {
+    (void)hipSetDevice(sp->device);
+    (void)hipDeviceSynchronize();                    // replays read the segments on their engines' streams
+    ks_prof_collect(sp);
+    for (auto &s : sp->segs) {
+        if (s.host) { if (s.packed) (void)hipHostFree(s.packed); if (s.mask) (void)hipHostFree(s.mask); }
+        else { if (s.packed) (void)hipFree(s.packed); if (s.mask) (void)hipFree(s.mask); }
+    }
+    sp->segs.clear();
+    for (int i = 0; i < 4; ++i) { if (sp->stage[i]) (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0; }
+    sp->hbm_bytes = sp->host_bytes = sp->batches = sp->bases = 0;
+    sp->overflowed = false; sp->have_last = false;
+}
+
+// The segment and tile at which a batch of n_tiles goes: the last segment while it has room, a new one otherwise (HBM
+// within its budget, then pinned host memory within its, then KDF_ERR_NOMEM and the spool is marked overflowed).
+static int spool_place(kdf_spool *sp, uint64_t n_tiles, KsSegment **seg_out) {
+    if (!sp->segs.empty() && sp->segs.back().tiles + n_tiles <= sp->segs.back().cap_tiles) { *seg_out = &sp->segs.back(); return KDF_OK; }
+    KsSegment s;
+    s.cap_tiles = std::max<uint64_t>(sp->opt_segment_positions / KDF_TILE, n_tiles);
+    const uint64_t pb = (2 * s.cap_tiles + 4) * 8, mb = (s.cap_tiles + 2) * 8;
+    s.bytes = pb + mb;
+    if (sp->hbm_bytes + s.bytes <= sp->hbm_budget) {
+        hipError_t e = hipMalloc((void **)&s.packed, pb);
+        if (e == hipSuccess && (e = hipMalloc((void **)&s.mask, mb)) != hipSuccess) { (void)hipFree(s.packed); s.packed = nullptr; }
+        if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }      // an expected event: the next tier takes it
+    }
+    if (!s.packed && sp->host_bytes + s.bytes <= sp->host_budget) {
+        hipError_t e = hipHostMalloc((void **)&s.packed, pb, hipHostMallocDefault);
+        if (e == hipSuccess && (e = hipHostMalloc((void **)&s.mask, mb, hipHostMallocDefault)) != hipSuccess) { (void)hipHostFree(s.packed); s.packed = nullptr; }
+        if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }
+        else s.host = true;
+    }
+    if (!s.packed) {
+        sp->overflowed = true;
+        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: a segment of %llu bytes fits neither budget (HBM %llu of %llu bytes used, host %llu of %llu): "
+                       "the spool is overflowed -- stream the source again, or kdf_spool_clear",
+                       (unsigned long long)s.bytes, (unsigned long long)sp->hbm_bytes, (unsigned long long)sp->hbm_budget,
+                       (unsigned long long)sp->host_bytes, (unsigned long long)sp->host_budget);
+    }
+    (s.host ? sp->host_bytes : sp->hbm_bytes) += s.bytes;
+    sp->segs.push_back(s);
+    *seg_out = &sp->segs.back();
+    return KDF_OK;
+}
+
+static int ks_check_append(kdf_spool *sp, const void *p, const void *m, uint64_t n_bases, const char *fn) {
+    if (n_bases > (1ull << 31)) return ks_fail(sp, KDF_ERR_INVALID, "%s: a batch of %llu positions (at most 2^31)", fn, (unsigned long long)n_bases);
+    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed (kdf_spool_clear)", fn);
+    if (n_bases && (!p || !m)) return ks_fail(sp, KDF_ERR_INVALID, "%s: NULL stream", fn);
+    return KDF_OK;
+}
+
+// one batch from DEVICE buffers, on stream s (behind every earlier append)
+static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
+    const uint64_t n_tiles = n_bases / KDF_TILE + 1;
+    KsSegment *seg = nullptr;
+    int rc = spool_place(sp, n_tiles, &seg);
+    if (rc) return rc;
+    uint64_t *dp = seg->packed + 2 * seg->tiles, *dm = seg->mask + seg->tiles;
+    if (seg->host) {
+        if ((rc = ks_stage_reserve(sp, 2, (2 * n_tiles + 4) * 8)) || (rc = ks_stage_reserve(sp, 3, (n_tiles + 2) * 8))) { sp->overflowed = true; return rc; }
+        dp = (uint64_t *)sp->stage[2]; dm = (uint64_t *)sp->stage[3];
+    }
+    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(s, sp->last, 0));
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n_tiles + 2 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (sp->prof) {
+        KSCHK(sp, hipEventCreate(&e0)); KSCHK(sp, hipEventCreate(&e1));
+        KSCHK(sp, hipEventRecord(e0, s));
+    }
+    hipLaunchKernelGGL(ks_append_kernel, dim3(blocks), dim3(KS_THREADS), 0, s, dp, dm, d_packed, d_invalid, n_bases, n_tiles,
+                       (int)(((uintptr_t)d_packed & 15) == 0));
+    KSCHK(sp, hipGetLastError());
+    if (sp->prof) { KSCHK(sp, hipEventRecord(e1, s)); sp->prof_ev.emplace_back(e0, e1); }
+    if (seg->host) {
+        KSCHK(sp, hipMemcpyAsync(seg->packed + 2 * seg->tiles, dp, (2 * n_tiles + 4) * 8, hipMemcpyDeviceToHost, s));
+        KSCHK(sp, hipMemcpyAsync(seg->mask + seg->tiles, dm, (n_tiles + 2) * 8, hipMemcpyDeviceToHost, s));
+    }
+    KSCHK(sp, hipEventRecord(sp->last, s));
+    sp->have_last = true;
+    seg->tiles += n_tiles;
+    ++sp->batches; sp->bases += n_bases;
+    return KDF_OK;
+}
+
+int kdf_spool_create(int device, uint64_t hbm_budget_bytes, uint64_t host_budget_bytes, kdf_spool **out) {
+    if (!out) return ks_fail(nullptr, KDF_ERR_INVALID, "kdf_spool_create: out is NULL");
+    *out = nullptr;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev == 0) return ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: no HIP device available (%s)", hipGetErrorString(e));
+    if (device < 0 || device >= ndev) return ks_fail(nullptr, KDF_ERR_INVALID, "kdf_spool_create: device %d of %d", device, ndev);
+    if ((e = hipSetDevice(device)) != hipSuccess) return ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: %s", hipGetErrorString(e));
+    kdf_spool *sp = new kdf_spool();
+    sp->device = device; sp->hbm_budget = hbm_budget_bytes; sp->host_budget = host_budget_bytes;
+    if ((e = hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sp->last, hipEventDisableTiming)) != hipSuccess) {
+        ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: %s", hipGetErrorString(e));
+        kdf_spool_destroy(sp);
+        return KDF_ERR_HIP;
+    }
+    *out = sp;
+    return KDF_OK;
+}
+
+void kdf_spool_destroy(kdf_spool *sp) {
+    if (!sp) return;
+    ks_free_all(sp);
+    if (sp->last) (void)hipEventDestroy(sp->last);
+    if (sp->stream) (void)hipStreamDestroy(sp->stream);
+    delete sp;
+}
+
+const char *kdf_spool_error(const kdf_spool *sp) { return sp ? sp->err.c_str() : g_err.c_str(); }
+
+int kdf_spool_clear(kdf_spool *sp) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    ks_free_all(sp);
+    return KDF_OK;
+}
+
+int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value) {
+    if (!sp || !name) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: NULL argument");
+    const std::string n(name);
+    if (n == "segment_positions") {
+        if (value < (1ll << 12) || value > (1ll << 31)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: segment_positions must be 2^12 .. 2^31");
+        sp->opt_segment_positions = (uint64_t)value;               // (segments already allocated keep their size)
+    } else if (n == "profile") {
+        if (!value) { (void)hipSetDevice(sp->device); ks_prof_collect(sp); }
+        sp->prof = value != 0;
+    } else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: unknown option %s", name);
+    return KDF_OK;
+}
+
+int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value) {
+    if (!sp || !name || !value) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: NULL argument");
+    const std::string n(name);
+    if (n == "segments") *value = (int64_t)sp->segs.size();
+    else if (n == "batches") *value = (int64_t)sp->batches;
+    else if (n == "positions") { uint64_t t = 0; for (auto &s : sp->segs) t += s.tiles; *value = (int64_t)(t * KDF_TILE); }
+    else if (n == "bases") *value = (int64_t)sp->bases;
+    else if (n == "hbm_bytes") *value = (int64_t)sp->hbm_bytes;
+    else if (n == "host_bytes") *value = (int64_t)sp->host_bytes;
+    else if (n == "overflowed") *value = sp->overflowed ? 1 : 0;
+    else if (n == "replays") *value = (int64_t)sp->replays;
+    else if (n == "segment_positions") *value = (int64_t)sp->opt_segment_positions;
+    else if (n == "append_us") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)(sp->prof_ms * 1000.0 + 0.5); }
+    else if (n == "append_passes") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)sp->prof_passes; }
+    else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: unknown stat %s", name);
+    return KDF_OK;
+}
+
+int kdf_spool_append_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    int rc = ks_check_append(sp, d_packed, d_invalid, n_bases, "kdf_spool_append_dev");
+    if (rc || n_bases == 0) return rc;
+    KSCHK(sp, hipSetDevice(sp->device));
+    return spool_append_dev(sp, (hipStream_t)hip_stream, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+}
+
+int kdf_spool_append(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    int rc = ks_check_append(sp, packed, invalid, n_bases, "kdf_spool_append");
+    if (rc || n_bases == 0) return rc;
+    KSCHK(sp, hipSetDevice(sp->device));
+    const uint64_t src_tiles = (n_bases + 63) / 64;                 // (the words the kernel loads, no more)
+    if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
+    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));   // (the staging's last reader)
+    KSCHK(sp, hipMemcpyAsync(sp->stage[0], packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    KSCHK(sp, hipMemcpyAsync(sp->stage[1], invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0], (const uint64_t *)sp->stage[1], n_bases);
+    KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
+    return rc;
+}
+
+int kdf_spool_append_uploaded(kdf_spool *sp, kdf_engine *h, int slot) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: NULL engine");
+    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: the spool is on device %d, the engine on %d", sp->device, h->device);
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_append_uploaded: nothing was uploaded into slot %d", slot);
+    const uint64_t n = h->up_n[slot];
+    int rc = ks_check_append(sp, h->up_buf[slot][0], h->up_buf[slot][1], n, "kdf_spool_append_uploaded");
+    if (rc || n == 0) return rc;
+    KSCHK(sp, hipSetDevice(sp->device));
+    KSCHK(sp, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
+    rc = spool_append_dev(sp, h->stream, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
+    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
+    return rc;
+}
+
+int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, uint64_t *invalid_out, uint64_t *n_positions_out) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_read_segment: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
+    const KsSegment &s = sp->segs[seg];
+    if (n_positions_out) *n_positions_out = s.tiles * KDF_TILE;
+    if (!packed_out && !invalid_out) return KDF_OK;
+    KSCHK(sp, hipSetDevice(sp->device));
+    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
+    const hipMemcpyKind kind = s.host ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
+    if (packed_out) KSCHK(sp, hipMemcpy(packed_out, s.packed, (2 * s.tiles + 4) * 8, kind));
+    if (invalid_out) KSCHK(sp, hipMemcpy(invalid_out, s.mask, (s.tiles + 2) * 8, kind));
+    return KDF_OK;
+}
+
+int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: NULL engine");
+    if (mode < 0 || mode > 2) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: mode %d (0 count, 1 count --if, 2 prefilter tally)", mode);
+    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: the spool is on device %d, the engine on %d", sp->device, h->device);
+    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_replay: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)");
+    const size_t ns = sp->segs.size();
+    size_t next_host = ns;                                         // the host-tier segment whose upload comes next
+    for (size_t i = 0; i < ns; ++i) if (sp->segs[i].host) { next_host = i; break; }
+    if (next_host < ns && (h->up_valid[0] || h->up_valid[1]))
+        return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_replay: host-tier segments go through the engine's upload slots, and slot %d holds a batch "
+                       "that was not counted", h->up_valid[0] ? 0 : 1);
+    KSCHK(sp, hipSetDevice(sp->device));
+    if (sp->have_last) {
+        KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
+        if (next_host < ns) KSCHK(sp, hipEventSynchronize(sp->last));   // (the upload reads host memory on the engine's copy stream)
+    }
+    auto pass = [&](size_t i, int rc) {
+        if (!rc) return KDF_OK;
+        h->up_valid[0] = h->up_valid[1] = false;                   // (both were free on entry: what they hold is the spool's)
+        return ks_fail(sp, rc, "kdf_spool_replay: segment %zu: %s", i, h->err.c_str());
+    };
+    auto upload = [&](size_t i, int slot) {
+        const KsSegment &s = sp->segs[i];
+        return kdf_upload_reads_async(h, slot, s.packed, s.mask, s.tiles * KDF_TILE);
+    };
+    int slot = 0, rc;
+    if (next_host < ns && (rc = upload(next_host, slot))) return pass(next_host, rc);
+    for (size_t i = 0; i < ns; ++i) {
+        const KsSegment &s = sp->segs[i];
+        const uint64_t n = s.tiles * KDF_TILE;
+        if (!s.host) {
+            rc = mode == 0 ? kdf_count_reads_dev(h, s.packed, s.mask, n) : mode == 1 ? kdf_count_reads_filtered_dev(h, s.packed, s.mask, n)
+                           : kdf_prefilter_add_reads_dev(h, s.packed, s.mask, n);
+            if (rc) return pass(i, rc);
+            continue;
+        }
+        size_t j = i + 1;
+        while (j < ns && !sp->segs[j].host) ++j;
+        if (j < ns && (rc = upload(j, slot ^ 1))) return pass(j, rc);   // its copy runs under this segment's count
+        rc = mode == 2 ? kdf_prefilter_add_uploaded(h, slot) : kdf_count_uploaded(h, slot, mode == 1);
+        if (rc) return pass(i, rc);
+        slot ^= 1;
+    }
+    ++sp->replays;
     return KDF_OK;
 }
 

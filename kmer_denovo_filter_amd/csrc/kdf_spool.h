@@ -1,0 +1,59 @@
+// kdf_spool.h -- the read spool's one kernel (kdf.h "read spool"; the host side is in kdf_engine.hip).
+//
+// A spool keeps the batches of a read stream resident, packed as they arrive (3 bits per position), as a list of SEGMENTS.
+// A segment is one read stream in the layout of kdf.h "Read streams"; a batch of n_bases positions occupies
+// n_bases / 64 + 1 tiles of it (a tile = 64 positions = one mask word + two packed words), so that at least one invalid
+// position -- for a batch that fills its last tile, a whole all-invalid tile -- lies between two batches and no window runs
+// from one into the next (the rule of l1_append, kdf_engine.hip).
+#ifndef KDF_SPOOL_H
+#define KDF_SPOOL_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define KS_THREADS 256
+#define KS_MAX_BLOCKS 2048u      // a streaming copy: 8 workgroups per CU fill the device, the rest is a grid stride
+
+// ks_append_kernel: normalise one batch into its place in a segment.  dp / dm point at the batch's first tile in the
+// segment (16-byte aligned: a tile is 16 bytes of packed words and the segment buffers come from hipMalloc).  Item i is
+// tile i of the batch: ONE mask word and its TWO packed words, one 16-byte store and one 8-byte store per lane, lanes on
+// consecutive tiles.
+//   i < ceil(n_bases / 64)   the source's words; in the tile that holds position n_bases the mask bits at and past it are
+//                            set and the bases there zeroed, in registers
+//   i < n_tiles              (n_bases a multiple of 64: the padding tile) all invalid, bases 0 -- nothing is loaded
+//   i < n_tiles + 2          the 2 mask / 4 packed padding words of kdf_stream_words behind the segment's last batch;
+//                            the next batch, if one comes, overwrites them (appends are ordered by the spool's event)
+// Source loads: mask words 0 .. ceil(n_bases / 64) - 1 and packed words 0 .. 2 ceil(n_bases / 64) - 1 only, which
+// kdf_stream_words(n_bases) covers.  src16: the packed source is 16-byte aligned (one 16-byte load per lane; two 8-byte
+// loads otherwise).  The room behind dp / dm is the host's to check (spool_place).
+__global__ __launch_bounds__(KS_THREADS) void ks_append_kernel(uint64_t *__restrict__ dp, uint64_t *__restrict__ dm,
+                                                               const uint64_t *__restrict__ sp, const uint64_t *__restrict__ sm,
+                                                               uint64_t n_bases, uint64_t n_tiles, int src16) {
+    const uint64_t src_tiles = (n_bases + 63) >> 6;
+    const uint64_t cut = n_bases >> 6;                 // the tile that holds position n_bases
+    const uint32_t r = (uint32_t)(n_bases & 63);
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < n_tiles + 2; i += stride) {
+        uint64_t m = ~0ull, p0 = 0ull, p1 = 0ull;
+        if (i < src_tiles) {
+            m = sm[i];
+            if (src16) {
+                const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(sp + 2 * i);
+                p0 = v.x; p1 = v.y;
+            } else {
+                p0 = sp[2 * i]; p1 = sp[2 * i + 1];
+            }
+            if (i == cut) {                             // (r != 0 here: cut < src_tiles)
+                m |= ~0ull << r;
+                if (r < 32) { p0 &= (1ull << (2 * r)) - 1; p1 = 0ull; }
+                else if (r > 32) p1 &= (1ull << (2 * (r - 32))) - 1;
+                else p1 = 0ull;
+            }
+        }
+        ulonglong2 o; o.x = p0; o.y = p1;
+        *reinterpret_cast<ulonglong2 *>(dp + 2 * i) = o;
+        dm[i] = m;
+    }
+}
+
+#endif /* KDF_SPOOL_H */

@@ -47,20 +47,89 @@ def _child_key_parts(child_bam, device=0, world=1, kmer_size=31):
     env = os.environ.get("KDF_KEY_PARTS")
     if env:
         return max(1, int(env))
+    need = _child_table_bytes(child_bam, world, kmer_size)
+    return max(1, int(-(-need // max(1.0, 0.7 * _device_free_bytes(device)))))
+
+
+def _device_free_bytes(device):
     from ctypes import byref, c_uint64
     from .. import _native
     free, total = c_uint64(0), c_uint64(0)
     _native.check(_native.load().kdf_device_memory(device, byref(free), byref(total)))
+    return free.value
+
+
+def _child_table_bytes(child_bam, world=1, kmer_size=31):
+    """Table bytes the rule of thumb of _child_key_parts plans for the whole key space of one rank."""
     need = 4.6 * os.path.getsize(child_bam) / max(1, world)      # (several ranks: every rank holds its share of the keys twice -- local + owned)
     W = keys.key_words(kmer_size)
     if W > 2:
         need *= (8 * W + 4) / 12.0
-    return max(1, int(-(-need // max(1.0, 0.7 * free.value))))
+    return need
 
 
 # How the last child count of this process ran: {"mode": "plain" | "two_pass" | "two_pass_sharded", "L", "log2_cells",
 # "world"} (L and log2_cells 0 without a prefilter).  For logs and tests; nothing reads it to decide anything.
 LAST_CHILD_COUNT = None
+
+
+# What the read spool of the last child count did: {"used" (KDF_SPOOL=1 and a spool was created), "segments", "positions",
+# "hbm_bytes", "host_bytes", "overflowed", "bam_passes" (passes of THIS rank through the BAM feeder)}.  For logs and tests.
+LAST_CHILD_SPOOL = None
+
+
+class _ChildPasses:
+    """The passes of one child count over the child BAM.  Without ``KDF_SPOOL=1`` every pass is ``_stream_bam``, as it
+    always was.  With it the first pass also fills a read spool (kdf.h "read spool") and every later pass is a replay of
+    the spool; a spool that overflows its budgets is logged and dropped, and the later passes stream the BAM again -- the
+    counts are the same either way.  Budgets: ``KDF_SPOOL_HBM_GB`` (default: the HBM that is free now, minus
+    ``reserve_bytes`` -- the table the slice planner plans for and the sieve -- never negative) and ``KDF_SPOOL_HOST_GB``
+    (pinned host memory, default 0: nobody has measured what these hosts can pin)."""
+
+    def __init__(self, device, reserve_bytes=0):
+        self.spool, self.filled, self.bam_passes = None, False, 0
+        self.info = {"used": False, "segments": 0, "positions": 0, "hbm_bytes": 0, "host_bytes": 0, "overflowed": False}
+        if os.environ.get("KDF_SPOOL") != "1":
+            return
+        from ..spool import ReadSpool
+        env = os.environ.get("KDF_SPOOL_HBM_GB")
+        hbm = float(env) * 1e9 if env else _device_free_bytes(device) - reserve_bytes
+        host = float(os.environ.get("KDF_SPOOL_HOST_GB") or 0) * 1e9
+        self.spool = ReadSpool(device, max(0, int(hbm)), max(0, int(host)))
+        self.info["used"] = True
+        logger.info("Read spool on: up to %.1f GB of HBM and %.1f GB of pinned host memory", max(0.0, hbm) / 1e9, max(0.0, host) / 1e9)
+
+    def _note(self):
+        for name in ("segments", "positions", "hbm_bytes", "host_bytes"):
+            self.info[name] = self.spool.stat(name)
+
+    def run(self, eng, child_bam, ref_fasta, threads, tally=False):
+        if self.spool is None:
+            self.bam_passes += 1
+            return _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=tally)
+        if self.filled:
+            return self.spool.replay(eng, self.spool.TALLY if tally else self.spool.COUNT)
+        self.bam_passes += 1
+        n = _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=tally, spool=self.spool)
+        self._note()
+        if self.spool.stat("overflowed"):
+            logger.info("Read spool overflowed after %d positions (%.1f GB of HBM, %.1f GB of host memory): dropped, the "
+                        "remaining passes stream the BAM", self.info["positions"], self.info["hbm_bytes"] / 1e9, self.info["host_bytes"] / 1e9)
+            self.info["overflowed"] = True
+            self.spool.close()
+            self.spool = None
+        else:
+            self.filled = True
+            logger.info("Read spool holds the sample: %d positions in %d segments (%.1f GB of HBM, %.1f GB of host memory)",
+                        self.info["positions"], self.info["segments"], self.info["hbm_bytes"] / 1e9, self.info["host_bytes"] / 1e9)
+        return n
+
+    def close(self):
+        global LAST_CHILD_SPOOL
+        if self.spool is not None:
+            self.spool.close()
+            self.spool = None
+        LAST_CHILD_SPOOL = dict(self.info, bam_passes=self.bam_passes)
 
 
 def _child_prefilter_min(min_child_count, world):
@@ -83,13 +152,14 @@ def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, thre
     hint = _engine_capacity_hint(jf_hash_size, child_bam)            # distinct k-mers expected, errors included
     log2_cells = min(38, max(16, (8 * max(int(hint), 1) - 1).bit_length()))
     with mirror_engine(kmer_size, capacity_hint=1 << 16, device=_device()) as eng:
+        passes = _ChildPasses(eng.device, _child_table_bytes(child_bam, 1, kmer_size) + (1 << (log2_cells - 1)))
         try:
             eng.prefilter_begin(L, log2_cells)
-            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=True)
+            passes.run(eng, child_bam, ref_fasta, threads, tally=True)
             fill = eng.prefilter_fill()
             eng.prefilter_arm()
             eng.reserve(fill[L] + (fill[3] if L == 2 else 0) + 1)    # about one admitted key per cell that reads >= L
-            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+            passes.run(eng, child_bam, ref_fasta, threads)
             cap, distinct, windows = eng.stats()
         except KdfError as e:
             if e.code != _native.KDF_ERR_NOMEM:
@@ -97,6 +167,8 @@ def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, thre
             logger.info("Two-pass child count: a sieve of 2^%d cells plus the table of the admitted k-mers do not fit the device "
                         "(%s); counting in key-space slices without a prefilter", log2_cells, e)
             return None
+        finally:
+            passes.close()
         logger.info("Child k-mer counting complete (%s, two passes, L=%d, sieve 2^%d cells reading 0/1/2/3: %d/%d/%d/%d, "
                     "%d of %d windows admitted, %d distinct stored, table %d slots)", _format_elapsed(time.monotonic() - extract_start),
                     L, log2_cells, fill[0], fill[1], fill[2], fill[3], windows, eng.get_stat("prefilter_windows"), distinct, cap)
@@ -122,13 +194,15 @@ def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_cou
     L = _child_prefilter_min(min_child_count, world)
     hint = _engine_capacity_hint(jf_hash_size, child_bam)            # distinct k-mers expected in the WHOLE sample
     proposal = min(38, max(16, (8 * max(int(hint), 1) - 1).bit_length()))
-    eng = owner_eng = None
+    eng = owner_eng = passes = None
     try:
         eng = mirror_engine(kmer_size, capacity_hint=1 << 16, device=_device())
         owner_eng = mirror_engine(kmer_size, capacity_hint=1 << 16, device=eng.device)
         dev = torch.device("cuda", eng.device)
         merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
         log2_cells = merger.agree_log2_cells(proposal)
+        # (every rank spools its own BGZF ranges: the reader of a pass is this rank's share of the file)
+        passes = _ChildPasses(eng.device, _child_table_bytes(child_bam, world, kmer_size) + (1 << (log2_cells - 1)))
         state = {"why": None}
 
         def step(fn):
@@ -149,7 +223,7 @@ def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_cou
 
         def tally():
             eng.prefilter_begin(L, log2_cells)
-            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=True)
+            passes.run(eng, child_bam, ref_fasta, threads, tally=True)
 
         if not step(tally):
             return give_up("a sieve of 2^%d cells" % log2_cells)
@@ -160,7 +234,7 @@ def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_cou
 
         def count():
             eng.reserve(fill[L] + (fill[3] if L == 2 else 0) + 1)    # at most about one admitted key per cell that reads >= L
-            _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+            passes.run(eng, child_bam, ref_fasta, threads)
             st["stats"] = eng.stats()
 
         if not step(count):
@@ -179,6 +253,8 @@ def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_cou
                             "exchange_pairs": merger.last_exchange_pairs}
         return devkeys.select([(dlo, dhi)])
     finally:
+        if passes is not None:
+            passes.close()
         for e in (owner_eng, eng):
             if e is not None:
                 e.close()
@@ -200,7 +276,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     # (Jellyfish's answer to the same problem is to spill and merge hash files, jellyfish_wrappers.py:335-366).
     world, rank, host = dist_env.world_rank()
     parts = _child_key_parts(child_bam, _device(), world, kmer_size)
-    owner_eng = merger = None
+    owner_eng = merger = passes = None
     dump_start = time.monotonic()
     try:
         cand = None
@@ -225,12 +301,14 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                 dev_sets = []
                 if parts > 1:
                     eng.set_option("key_parts", parts)
+                # (slice 0 streams the BAM; with KDF_SPOOL=1 it also spools it and slices 1 .. P-1 replay the spool)
+                passes = _ChildPasses(eng.device, _child_table_bytes(child_bam, world, kmer_size) / parts)
                 for part in range(parts):
                     if parts > 1:
                         eng.clear(); eng.set_option("key_part", part)
                         if owner_eng is not None:
                             owner_eng.clear()
-                    _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False)
+                    passes.run(eng, child_bam, ref_fasta, threads)
                     cap, distinct, windows = eng.stats()
                     logger.info("Child k-mer counting complete (%s, slice %d of %d, %d windows, %d distinct, table %d slots)",
                                 _format_elapsed(time.monotonic() - extract_start), part + 1, parts, windows, distinct, cap)
@@ -250,6 +328,8 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     except KdfError as e:
         raise RuntimeError(f"jellyfish count (child) failed: {e}") from e
     finally:
+        if passes is not None:
+            passes.close()                                         # (synchronises the device: no replayed count still reads a segment)
         if owner_eng is not None:
             owner_eng.close()
     if world > 1:                                                  # (rank order of the gathered sets is not key order)

@@ -289,13 +289,16 @@ def _pinned_ring(ring: int, max_bases: int) -> PinnedBatches:
     return pb
 
 
-def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, tally: bool = False) -> int:
+def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, tally: bool = False, spool=None) -> int:
     """Count every batch of ``readers`` (one reader, or several readers of disjoint ranges of one file:
     ``bam_reader(part=, parts=)``) on ``engine`` as a three-stage pipeline: one reader thread PER READER decodes batches
     into pinned buffers (the native reader releases the GIL; inflate, chunking and parsing of the ranges run side by
     side), the copy stream uploads batch i + 1, the engine counts batch i.  Batches arrive in any order: counting does
     not care.  ``tally``: pass 1 of a two-pass count -- every batch goes to the engine's prefilter
-    (``prefilter_add_uploaded``) instead of its table.  Returns the number of reads."""
+    (``prefilter_add_uploaded``) instead of its table.  ``spool``: a ``spool.ReadSpool`` on the engine's device -- every
+    batch is also appended to it from its upload slot, before it is counted or tallied, so that later passes replay the
+    spool and not the file.  A spool that overflows stops taking batches (it reads ``stat("overflowed")``: the caller
+    streams the file again for the later passes); the pass itself goes on.  Returns the number of reads."""
     import queue
     import threading
     if not isinstance(readers, (list, tuple)):
@@ -327,7 +330,20 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
     threads = [threading.Thread(target=produce, args=(rd,), name="kdf-reader", daemon=True) for rd in readers]
     for th in threads:
         th.start()
-    take = engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
+    take_slot = engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
+    spooling = [spool]
+
+    def take(slot):
+        # the spool's copy runs on the engine's stream right before the count of the same slot (not at upload time: the
+        # engine's stream would then wait for the copy of batch i + 1 before it counts batch i); the slot keeps the batch
+        if spooling[0] is not None:
+            try:
+                spooling[0].append_uploaded(engine, slot)
+            except _native.KdfError as ex:
+                if ex.code != _native.KDF_ERR_NOMEM:
+                    raise
+                spooling[0] = None                               # overflowed: neither budget holds the next segment
+        take_slot(slot)
     pending = None                                           # (slot, buffer) uploaded, not yet counted
     slot = 0
     live = len(threads)
