@@ -699,13 +699,16 @@ int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, voi
  * given to the same entry point one by one: the same (key, count) set, the same `windows`, the same sieve words, the
  * same gating under "key_parts" and an armed prefilter.  A replay does not change the spool.  Segments must outlive the
  * work replayed from them: kdf_spool_clear and kdf_spool_destroy synchronise the device first.
- * Not kept: read offsets.  kdf_scan_reads*, kdf_read_hits* and kdf_read_depth* over a spool need them and are a later
- * step; Module 3 reads the BAM with another flag filter (0x500) and cannot share the count's spool.
+ * Not kept: read names and alignment data (flags, positions, CIGAR); Module 3 reads the BAM with another flag filter
+ * (0x500) than the count (0xD00), so its spool is one of its own ("Reads in a spool" below).
  * Options (kdf_spool_set_option): "segment_positions" (default 2^30, 2^12 .. 2^31; segments allocated later take it),
- * "profile" (1: HIP events around every append kernel).  Stats (kdf_spool_get_stat): "segments", "batches", "positions"
- * (stream positions stored, padding included: 64 x tiles), "bases" (sum of the appended n_bases), "hbm_bytes",
- * "host_bytes" (segment bytes per tier), "overflowed", "replays", "segment_positions", and under "profile" "append_us" /
- * "append_passes".  Errors: kdf_spool_error(sp), or kdf_spool_error(NULL) for kdf_spool_create. */
+ * "offsets_chunk" (default 2^16 entries, 1 .. 2^28: the unit a segment's offsets array is sized and grown in), "profile"
+ * (1: HIP events around every append kernel and every offsets kernel).  Stats (kdf_spool_get_stat): "segments", "batches",
+ * "positions" (stream positions stored, padding included: 64 x tiles), "bases" (sum of the appended n_bases), "hbm_bytes",
+ * "host_bytes" (segment bytes per tier, offsets arrays included), "overflowed", "replays", "segment_positions", "reads",
+ * "keeps_reads", "offset_bytes" (bytes of the offsets arrays, both tiers), and under "profile" "append_us" /
+ * "append_passes" and "offsets_us" / "offsets_passes".  Errors: kdf_spool_error(sp), or kdf_spool_error(NULL) for
+ * kdf_spool_create. */
 typedef struct kdf_spool kdf_spool;
 int kdf_spool_create(int device, uint64_t hbm_budget_bytes, uint64_t host_budget_bytes, kdf_spool **out);
 void kdf_spool_destroy(kdf_spool *sp);
@@ -720,6 +723,77 @@ int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode);
  * only the size is returned.  Waits for the last append. */
 int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, uint64_t *invalid_out, uint64_t *n_positions_out);
 int kdf_spool_clear(kdf_spool *sp);
+
+/* Reads in a spool.  The per-read consumers -- kdf_scan_reads* with a hit list, kdf_read_hits*, kdf_read_depth* -- need the
+ * read boundaries, and they are the calls a user repeats over the same reads against different tables (the child's reads
+ * against either parent's table, or against one candidate k-mer set per threshold).  A spool filled through the
+ * `_reads` appends keeps each batch's read offsets beside its segment and replays those consumers too.
+ * Mode.  A spool either keeps reads or does not: the first append since create or clear decides ("keeps_reads").  The
+ * other kind of append is KDF_ERR_STATE afterwards and stores nothing.  A spool never given offsets behaves exactly as
+ * described above: nothing is allocated or launched for offsets.
+ * Offsets.  read_offsets are the n_reads + 1 stream offsets kdf_pack_reads / kdf_reader_next hand out: offsets[0] == 0,
+ * non-decreasing (a read of length 0 is allowed), offsets[n_reads] == n_bases.  The host forms (kdf_spool_append_reads,
+ * kdf_spool_append_uploaded_reads) check this before any device work: a violation, or n_reads < 0, is KDF_ERR_INVALID
+ * and no stat changes.  For kdf_spool_append_reads_dev it is a precondition; whatever the array holds, nothing is
+ * written outside the n_reads + 1 entries the batch owns.  n_bases == 0 with n_reads == 0 is KDF_OK, stores nothing and
+ * decides nothing; n_bases == 0 with n_reads > 0 is KDF_ERR_INVALID in every form (a batch without positions has no
+ * place in a segment; empty reads are kept with a batch that has positions).
+ * kdf_spool_append_uploaded_reads copies the offsets (into pinned memory, one buffer per upload slot) before it returns:
+ * the caller's array is its own again at once.
+ * Layout.  Every segment has an int64 array in its own tier with n_reads(segment) + 1 entries in SEGMENT coordinates: a
+ * batch placed at tile t0 writes 64 t0 + offsets[i] for i = 0 .. n_reads (ks_offsets_kernel, on the stream of the batch's
+ * append kernel; for the host tier through a staging buffer and the same asynchronous copy out).  The batch's last entry,
+ * 64 t0 + n_bases, is overwritten by the first entry of the next batch in the segment, 64 t1 with t1 = t0 + n_bases / 64
+ * + 1 (appends are ordered).  THE GAP: the last read of a batch so formally extends over the positions 64 t0 + n_bases ..
+ * 64 t1 - 1 behind it.  Every one of them is invalid by the append kernel's rule and there is at least one, so no window
+ * that starts in the gap or runs into it is valid, no hit bit lies in it, and -- because offsets[n_reads] == n_bases: no
+ * position of the batch lies outside its reads -- the windows and hits of every read are exactly those it has in the
+ * batch alone.  Without that rule positions behind the last read would silently join it.  A batch is never split, so a
+ * read never spans segments.  Reads are numbered globally in append order; segment s owns reads first_read(s) ..
+ * first_read(s) + n_reads(s) - 1.  The array is sized for the whole segment when its first batch arrives (from that
+ * batch's reads per position) and grows in units of "offsets_chunk" when that was too little; its bytes are charged to
+ * the tier's budget and reported in "hbm_bytes" / "host_bytes".  A new segment is placed in the first tier whose budget
+ * holds the segment TOGETHER WITH that first offsets array, so the array never overflows a spool whose other tier had
+ * room.  An array that grows later stays in its segment's tier: when the tier's budget does not hold the growth, the
+ * spool overflows as for a segment that fits neither tier (KDF_ERR_NOMEM, "overflowed", nothing of the batch is stored).
+ * Replays.  kdf_spool_read_hits / kdf_spool_read_depth make the engine's stream wait for the last append, walk the
+ * segments in order and call kdf_read_hits_dev (d_hit_bits NULL) / kdf_read_depth_dev on each, with the segment's
+ * stream, offsets and read count, writing into the caller's rows at first_read(s): n_reads x 2 uint32 / n_reads x 6
+ * uint64 for "reads" reads, every row written exactly once.  The rows equal the concatenation, in append order, of what
+ * the same entry point returns for each appended batch alone -- every key width, insert and filter mode, "key_parts".
+ * A host-tier segment is first copied into a device staging buffer of the spool's own (one segment's packed, mask and
+ * offsets words; grow-only; not charged to the HBM budget); copy and compute do not overlap.  Refusals: a spool that
+ * keeps no reads and an overflowed spool are KDF_ERR_STATE, another device KDF_ERR_INVALID, an engine's refusal is
+ * passed on behind "segment i:".  A spool with no reads is KDF_OK and writes nothing.  Synchronisation is the entry
+ * point's: kdf_read_hits_dev synchronises the engine's stream once per segment; the rows are complete in the order of
+ * the engine's stream.
+ * kdf_spool_select_reads: the reads with distinct >= min_distinct among "reads" rows of kdf_spool_read_hits, as their
+ * ASCENDING global indices (uint64) -- the device half of Module 3's selection at sample scale, where the rows are 8
+ * bytes x 10^9 and the list is short.  An order-preserving compaction (ks_select_*: count, scan, write).  d_hit_rows
+ * must be COMPLETE when the call is made (kdf_synchronize the engine that wrote them); the call runs on the spool's own
+ * stream and synchronises it once.  At most 2^34 rows a call (KDF_ERR_INVALID beyond).  *n_out is always set; when it exceeds cap the call returns KDF_ERR_INVALID and at
+ * most cap entries are written (the convention of kdf_hit_list_dev).  It depends on the rows alone: bit-identical from
+ * run to run. */
+int kdf_spool_append_reads(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                           const int64_t *read_offsets, int64_t n_reads);
+int kdf_spool_append_reads_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                               const void *d_read_offsets, int64_t n_reads);
+int kdf_spool_append_uploaded_reads(kdf_spool *sp, kdf_engine *h, int slot, const int64_t *read_offsets, int64_t n_reads);
+/* The twin of kdf_spool_read_segment: a segment's *n_reads_out + 1 offsets to a host array; out == NULL returns only
+ * first_read and n_reads.  Waits for the last append.  KDF_ERR_STATE for a spool that keeps no reads. */
+int kdf_spool_read_offsets(kdf_spool *sp, uint64_t seg, int64_t *out, uint64_t *first_read_out, uint64_t *n_reads_out);
+/* The device pointers of an HBM-tier segment, to run any `_dev` entry point over it in place (kdf_scan_reads_dev,
+ * kdf_hit_list_dev, kdf_window_counts_dev, ...): a stream of *n_positions positions and, for a spool that keeps reads,
+ * its *n_reads + 1 offsets (*d_offsets is NULL otherwise).  Any out pointer may be NULL.  The call waits on the host
+ * for the last append, so the buffers are complete for whatever stream reads them; they stay valid until the next
+ * kdf_spool_clear / destroy, the offsets only until the next append (the array may move when it grows).  A host-tier
+ * segment is KDF_ERR_STATE: kdf_spool_read_segment copies it out. */
+int kdf_spool_segment_dev(kdf_spool *sp, uint64_t seg, const void **d_packed, const void **d_invalid, uint64_t *n_positions,
+                          const void **d_offsets, uint64_t *first_read, uint64_t *n_reads);
+int kdf_spool_read_hits(kdf_spool *sp, kdf_engine *h, void *d_rows_out);
+int kdf_spool_read_depth(kdf_spool *sp, kdf_engine *h, uint32_t low_max, void *d_rows_out);
+int kdf_spool_select_reads(kdf_spool *sp, const void *d_hit_rows, uint32_t min_distinct, void *d_reads_out, uint64_t cap,
+                           uint64_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,16 @@ SYMBOLS = [
     ("kdf_spool_replay", c_int, [_P, _P, c_int]),
     ("kdf_spool_read_segment", c_int, [_P, c_uint64, _P, _P, POINTER(c_uint64)]),
     ("kdf_spool_clear", c_int, [_P]),
+    # ... with read offsets: the per-read consumers over a spool
+    ("kdf_spool_append_reads", c_int, [_P, _P, _P, c_uint64, _P, c_int64]),
+    ("kdf_spool_append_reads_dev", c_int, [_P, _P, _P, _P, c_uint64, _P, c_int64]),
+    ("kdf_spool_append_uploaded_reads", c_int, [_P, _P, c_int, _P, c_int64]),
+    ("kdf_spool_read_offsets", c_int, [_P, c_uint64, _P, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_spool_segment_dev", c_int, [_P, c_uint64, POINTER(_P), POINTER(_P), POINTER(c_uint64), POINTER(_P), POINTER(c_uint64),
+                                      POINTER(c_uint64)]),
+    ("kdf_spool_read_hits", c_int, [_P, _P, _P]),
+    ("kdf_spool_read_depth", c_int, [_P, _P, c_uint32, _P]),
+    ("kdf_spool_select_reads", c_int, [_P, _P, c_uint32, _P, c_uint64, POINTER(c_uint64)]),
 ]
 
 _lib = None

@@ -23,7 +23,7 @@ from typing import Iterator, List, Optional, Set, Tuple
 import numpy as np
 
 from .. import jf_io
-from .._native import KdfError
+from .._native import KDF_ERR_NOMEM, KdfError
 from ..engine import KmerEngine, mirror_engine, hit_positions
 from ..kmer_fasta import read_kmer_fasta_keys
 from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys
@@ -105,10 +105,14 @@ def _scan_batch(eng: KmerEngine, batch):
 
 
 def scan_bam_for_hits(child_bam, engine: Optional[KmerEngine] = None, min_dk_per_read: Optional[int] = None,
-                      batch_bases: int = SCAN_BATCH_BASES) -> Iterator[Tuple[int, List[InformativeRead]]]:
+                      batch_bases: int = SCAN_BATCH_BASES, spool=None) -> Iterator[Tuple[int, List[InformativeRead]]]:
     """Scan every non-SECONDARY, non-DUPLICATE record (supplementary kept, no
     QNAME collapse: reference :405-409).  Yields (reads_scanned_in_batch,
-    [InformativeRead ...]) per batch, records in file order."""
+    [InformativeRead ...]) per batch, records in file order.  ``spool``: a
+    ``spool.ReadSpool`` that takes every scanned batch with its read offsets and
+    BAM ordinals, so that another k-mer set is evaluated over the same reads by
+    ``spool.read_hits`` / ``select_reads`` and not by a second pass over the BAM
+    (a spool that overflows stops taking batches; ``spool.stat("overflowed")``)."""
     eng = engine or _worker_engine
     if eng is None:
         raise RuntimeError("scan worker not initialised (_init_scan_worker)")
@@ -116,6 +120,13 @@ def scan_bam_for_hits(child_bam, engine: Optional[KmerEngine] = None, min_dk_per
     with bam_reader(child_bam, flag_off=FLAG_OFF_MODULE3, collapse=False, max_bases=batch_bases,
                     max_reads=1 << 20, threads=READER_THREADS, want_meta=True) as rd:
         for batch in rd:
+            if spool is not None and not spool.stat("overflowed"):
+                try:
+                    spool.append(batch, keep_reads=True)
+                except KdfError as e:                           # neither budget holds the next segment: the scan goes on
+                    if e.code != KDF_ERR_NOMEM:
+                        raise                                   # (the spool's own error, not a failed query)
+                    logger.info("Read spool overflowed after %d reads: %s", spool.n_reads, e)
             try:
                 distinct, hits_of = _scan_batch(eng, batch)
             except KdfError as e:

@@ -105,7 +105,8 @@ def _engine_capacity_hint(hash_size, bam_path=None):
 def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False, spool=None):
     """``samtools fasta -F 0xD00 bam | jellyfish count ... /dev/fd/0``.  ``tally``: the same reader pipelines feed
     pass 1 of a two-pass count (the engine's prefilter) instead of the table.  ``spool``: a ``ReadSpool`` that also
-    keeps every batch of this pass (``stream_batches_overlapped``)."""
+    keeps every batch of this pass (``stream_batches_overlapped``) -- with its read offsets when ``spool.keep_reads``
+    is set."""
     if str(bam_path).endswith(".cram"):
         raise RuntimeError(
             "jellyfish count failed: CRAM input needs htslib, which the MI355X engine does not link; "

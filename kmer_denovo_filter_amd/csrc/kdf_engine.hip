@@ -3275,26 +3275,49 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
 // read spool (kdf.h "read spool", kdf_spool.h): a sample's packed stream kept resident and replayed
 // ===========================================================================
 
+#define KS_STAGES 6
 struct KsSegment {
     uint64_t *packed = nullptr, *mask = nullptr;     // 2 cap_tiles + 4 / cap_tiles + 2 words: HBM, or pinned host memory
     uint64_t cap_tiles = 0, tiles = 0;               // room / used; the segment is a stream of tiles x 64 positions
     uint64_t bytes = 0;
     bool host = false;
+    // a spool that keeps reads: offs[0 .. n_reads] in SEGMENT coordinates, in the segment's tier (room for offs_cap entries)
+    int64_t *offs = nullptr;
+    uint64_t offs_cap = 0, n_reads = 0, first_read = 0;
 };
+enum { KS_MODE_OPEN = 0, KS_MODE_STREAM = 1, KS_MODE_READS = 2 };   // decided by the first append since create / clear
 struct kdf_spool {
     int device = 0;
     uint64_t hbm_budget = 0, host_budget = 0;
     uint64_t opt_segment_positions = 1ull << 30;
     std::vector<KsSegment> segs;
     uint64_t hbm_bytes = 0, host_bytes = 0, batches = 0, bases = 0, replays = 0;
+    int mode = KS_MODE_OPEN;
+    uint64_t reads = 0, offset_bytes = 0;
+    uint64_t opt_offsets_chunk = 1ull << 16;         // entries: the unit an offsets array is sized and grown in
     bool overflowed = false;
     hipStream_t stream = nullptr;                    // kdf_spool_append (host sources) runs here
     hipEvent_t last = nullptr; bool have_last = false;   // behind the latest append, whatever stream it ran on
-    void *stage[4] = {nullptr, nullptr, nullptr, nullptr};   // grow-only: 0/1 a host source's words, 2/3 a host-tier batch before its copy out
-    size_t stage_bytes[4] = {0, 0, 0, 0};
+    // grow-only: 0/1 a host source's words, 2/3 a host-tier batch before its copy out, 4 a host source's offsets, 5 a
+    // host-tier batch's offsets before their copy out
+    void *stage[KS_STAGES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t stage_bytes[KS_STAGES] = {0, 0, 0, 0, 0, 0};
+    // kdf_spool_append_uploaded_reads: the caller's offsets pass through pinned memory, so the copy is truly asynchronous
+    // and the caller's array is its own again at once; pin_done is behind the copy that read it last
+    // (one buffer per upload slot: the host never waits for the append it queued last)
+    int64_t *pin_offs[2] = {nullptr, nullptr}; size_t pin_entries[2] = {0, 0};
+    hipEvent_t pin_done[2] = {nullptr, nullptr}; bool have_pin_done[2] = {false, false};
+    // replays of the per-read consumers: one host-tier segment's packed, mask and offsets words on the device (grow-only,
+    // not charged to the budget); rep_done is behind the consumer that read them last, whatever engine it ran on
+    void *rep[3] = {nullptr, nullptr, nullptr};
+    size_t rep_bytes[3] = {0, 0, 0};
+    hipEvent_t rep_done = nullptr; bool have_rep_done = false;
+    // kdf_spool_select_reads: block sums (device) and the total (pinned)
+    void *sel_buf = nullptr; size_t sel_bytes = 0;
+    unsigned long long *sel_total = nullptr;
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
-    double prof_ms = 0.0; uint64_t prof_passes = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev, prof_offs_ev;
+    double prof_ms = 0.0, prof_offs_ms = 0.0; uint64_t prof_passes = 0, prof_offs_passes = 0;
     std::string err;
 };
 
@@ -3312,15 +3335,19 @@ static int ks_fail(kdf_spool *sp, int code, const char *fmt, ...) {
                            "%s failed: %s", #call, hipGetErrorString(e_));              \
     } while (0)
 
-static void ks_prof_collect(kdf_spool *sp) {
-    for (auto &pr : sp->prof_ev) {
+static void ks_prof_collect(std::vector<std::pair<hipEvent_t, hipEvent_t>> &evs, double &total_ms, uint64_t &passes) {
+    for (auto &pr : evs) {
         float ms = 0.f;
         if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-            sp->prof_ms += ms; ++sp->prof_passes;
+            total_ms += ms; ++passes;
         } else (void)hipGetLastError();
         (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
     }
-    sp->prof_ev.clear();
+    evs.clear();
+}
+static void ks_prof_collect(kdf_spool *sp) {
+    ks_prof_collect(sp->prof_ev, sp->prof_ms, sp->prof_passes);
+    ks_prof_collect(sp->prof_offs_ev, sp->prof_offs_ms, sp->prof_offs_passes);
 }
 
 // grow-only staging; the buffer's last user is an append, and every append is behind sp->last
@@ -3345,29 +3372,56 @@ static void ks_free_all(kdf_spool *sp) {
     (void)hipDeviceSynchronize();                    // replays read the segments on their engines' streams
     ks_prof_collect(sp);
     for (auto &s : sp->segs) {
-        if (s.host) { if (s.packed) (void)hipHostFree(s.packed); if (s.mask) (void)hipHostFree(s.mask); }
-        else { if (s.packed) (void)hipFree(s.packed); if (s.mask) (void)hipFree(s.mask); }
+        if (s.host) { if (s.packed) (void)hipHostFree(s.packed); if (s.mask) (void)hipHostFree(s.mask); if (s.offs) (void)hipHostFree(s.offs); }
+        else { if (s.packed) (void)hipFree(s.packed); if (s.mask) (void)hipFree(s.mask); if (s.offs) (void)hipFree(s.offs); }
     }
     sp->segs.clear();
-    for (int i = 0; i < 4; ++i) { if (sp->stage[i]) (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0; }
-    sp->hbm_bytes = sp->host_bytes = sp->batches = sp->bases = 0;
-    sp->overflowed = false; sp->have_last = false;
+    for (int i = 0; i < KS_STAGES; ++i) { if (sp->stage[i]) (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0; }
+    for (int i = 0; i < 3; ++i) { if (sp->rep[i]) (void)hipFree(sp->rep[i]); sp->rep[i] = nullptr; sp->rep_bytes[i] = 0; }
+    for (int i = 0; i < 2; ++i) {
+        if (sp->pin_offs[i]) (void)hipHostFree(sp->pin_offs[i]);
+        sp->pin_offs[i] = nullptr; sp->pin_entries[i] = 0; sp->have_pin_done[i] = false;
+    }
+    if (sp->sel_buf) (void)hipFree(sp->sel_buf);
+    sp->sel_buf = nullptr; sp->sel_bytes = 0;
+    sp->hbm_bytes = sp->host_bytes = sp->batches = sp->bases = sp->reads = sp->offset_bytes = 0;
+    sp->mode = KS_MODE_OPEN;
+    sp->overflowed = false; sp->have_last = false; sp->have_rep_done = false;
 }
 
 // The segment and tile at which a batch of n_tiles goes: the last segment while it has room, a new one otherwise (HBM
 // within its budget, then pinned host memory within its, then KDF_ERR_NOMEM and the spool is marked overflowed).
-static int spool_place(kdf_spool *sp, uint64_t n_tiles, KsSegment **seg_out) {
+// entries of an offsets array that must hold `need`: a new one (have == 0) is sized for the whole segment from the read
+// density of the batch that opens it (at most one read per 32 positions is assumed), a grown one by at least an eighth;
+// both in units of option "offsets_chunk"
+static uint64_t ks_offsets_want(const kdf_spool *sp, uint64_t cap_tiles, uint64_t have, uint64_t need, uint64_t n_bases, uint64_t n_reads) {
+    uint64_t want;
+    if (!have) {
+        const uint64_t cap_pos = cap_tiles * KDF_TILE;
+        const double est = (double)cap_pos * (double)(n_reads + 1) / (double)std::max<uint64_t>(n_bases, 1) * 1.125;
+        want = std::max<uint64_t>(need, (uint64_t)std::min<double>(est, (double)(cap_pos / 32)));
+    } else want = std::max<uint64_t>(need, have + have / 8);
+    const uint64_t chunk = sp->opt_offsets_chunk;
+    return (want + chunk - 1) / chunk * chunk;
+}
+
+// keep_reads / keep_bases: the batch brings keep_reads > 0 reads, and a NEW segment must fit its tier's budget together with
+// its first offsets array (so that array's allocation does not overflow a spool whose other tier has room)
+static int spool_place(kdf_spool *sp, uint64_t n_tiles, KsSegment **seg_out, bool *fresh = nullptr, uint64_t keep_reads = 0, uint64_t keep_bases = 0) {
+    if (fresh) *fresh = false;
     if (!sp->segs.empty() && sp->segs.back().tiles + n_tiles <= sp->segs.back().cap_tiles) { *seg_out = &sp->segs.back(); return KDF_OK; }
     KsSegment s;
+    s.first_read = sp->reads;
     s.cap_tiles = std::max<uint64_t>(sp->opt_segment_positions / KDF_TILE, n_tiles);
     const uint64_t pb = (2 * s.cap_tiles + 4) * 8, mb = (s.cap_tiles + 2) * 8;
     s.bytes = pb + mb;
-    if (sp->hbm_bytes + s.bytes <= sp->hbm_budget) {
+    const uint64_t ob = keep_reads ? ks_offsets_want(sp, s.cap_tiles, 0, keep_reads + 1, keep_bases, keep_reads) * 8 : 0;
+    if (sp->hbm_bytes + s.bytes + ob <= sp->hbm_budget) {
         hipError_t e = hipMalloc((void **)&s.packed, pb);
         if (e == hipSuccess && (e = hipMalloc((void **)&s.mask, mb)) != hipSuccess) { (void)hipFree(s.packed); s.packed = nullptr; }
         if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }      // an expected event: the next tier takes it
     }
-    if (!s.packed && sp->host_bytes + s.bytes <= sp->host_budget) {
+    if (!s.packed && sp->host_bytes + s.bytes + ob <= sp->host_budget) {
         hipError_t e = hipHostMalloc((void **)&s.packed, pb, hipHostMallocDefault);
         if (e == hipSuccess && (e = hipHostMalloc((void **)&s.mask, mb, hipHostMallocDefault)) != hipSuccess) { (void)hipHostFree(s.packed); s.packed = nullptr; }
         if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }
@@ -3375,36 +3429,116 @@ static int spool_place(kdf_spool *sp, uint64_t n_tiles, KsSegment **seg_out) {
     }
     if (!s.packed) {
         sp->overflowed = true;
-        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: a segment of %llu bytes fits neither budget (HBM %llu of %llu bytes used, host %llu of %llu): "
+        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: a segment of %llu bytes (with its read offsets, if it keeps any) fits neither budget (HBM %llu of %llu bytes used, host %llu of %llu): "
                        "the spool is overflowed -- stream the source again, or kdf_spool_clear",
-                       (unsigned long long)s.bytes, (unsigned long long)sp->hbm_bytes, (unsigned long long)sp->hbm_budget,
+                       (unsigned long long)(s.bytes + ob), (unsigned long long)sp->hbm_bytes, (unsigned long long)sp->hbm_budget,
                        (unsigned long long)sp->host_bytes, (unsigned long long)sp->host_budget);
     }
     (s.host ? sp->host_bytes : sp->hbm_bytes) += s.bytes;
     sp->segs.push_back(s);
     *seg_out = &sp->segs.back();
+    if (fresh) *fresh = true;
     return KDF_OK;
 }
 
-static int ks_check_append(kdf_spool *sp, const void *p, const void *m, uint64_t n_bases, const char *fn) {
+// Room for `need` entries in the segment's offsets array, in the segment's tier and within its budget; the entries
+// stored so far move along.  A new array is sized for the whole segment from the read density of the batch that opens it
+// (at most one read per 32 positions is assumed; more than that grows), in units of option "offsets_chunk", so that
+// growing -- which waits for the device: replays may be reading the old array -- stays rare.
+static int ks_offsets_reserve(kdf_spool *sp, KsSegment *seg, uint64_t need, uint64_t n_bases, uint64_t n_reads) {
+    if (seg->offs_cap >= need) return KDF_OK;
+    const uint64_t want = ks_offsets_want(sp, seg->cap_tiles, seg->offs_cap, need, n_bases, n_reads);
+    const uint64_t add = (want - seg->offs_cap) * 8;
+    uint64_t &used = seg->host ? sp->host_bytes : sp->hbm_bytes;
+    const uint64_t budget = seg->host ? sp->host_budget : sp->hbm_budget;
+    int64_t *fresh = nullptr;
+    hipError_t e = hipErrorOutOfMemory;
+    if (used + add <= budget) {
+        e = seg->host ? hipHostMalloc((void **)&fresh, want * 8, hipHostMallocDefault) : hipMalloc((void **)&fresh, want * 8);
+        if (e != hipSuccess) { (void)hipGetLastError(); fresh = nullptr; }
+    }
+    if (!fresh) {
+        sp->overflowed = true;
+        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %llu bytes of read offsets do not fit the %s budget (%llu of %llu bytes used): the spool is "
+                       "overflowed -- stream the source again, or kdf_spool_clear", (unsigned long long)add, seg->host ? "host" : "HBM",
+                       (unsigned long long)used, (unsigned long long)budget);
+    }
+    if (seg->offs) {
+        e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(fresh, seg->offs, (seg->n_reads + 1) * 8, seg->host ? hipMemcpyHostToHost : hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (seg->host) (void)hipHostFree(fresh); else (void)hipFree(fresh);
+            return ks_fail(sp, KDF_ERR_HIP, "read spool: moving a segment's read offsets failed: %s", hipGetErrorString(e));
+        }
+        if (seg->host) (void)hipHostFree(seg->offs); else (void)hipFree(seg->offs);
+    }
+    seg->offs = fresh; seg->offs_cap = want;
+    used += add; seg->bytes += add; sp->offset_bytes += add;
+    return KDF_OK;
+}
+
+// n_reads >= 0, offsets[0] == 0, no decrease, offsets[n_reads] == n_bases: what kdf_pack_reads and kdf_reader_next hand out
+static int ks_check_offsets(kdf_spool *sp, const char *fn, const int64_t *offs, int64_t n_reads, uint64_t n_bases) {
+    if (n_reads < 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: n_reads = %lld is negative", fn, (long long)n_reads);
+    if (n_reads == 0) {
+        if (n_bases) return ks_fail(sp, KDF_ERR_INVALID, "%s: %llu positions in no read (read_offsets[n_reads] must be n_bases)", fn, (unsigned long long)n_bases);
+        return KDF_OK;
+    }
+    if (n_bases == 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: %lld reads in a batch of no positions (a batch without positions has no place in a segment)", fn, (long long)n_reads);
+    if (!offs) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets is NULL", fn);
+    if (offs[0] != 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld, not 0", fn, (long long)offs[0]);
+    for (int64_t r = 0; r < n_reads; ++r)
+        if (offs[r + 1] < offs[r])
+            return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets decrease at read %lld (%lld after %lld)", fn, (long long)r, (long long)offs[r + 1],
+                           (long long)offs[r]);
+    if ((uint64_t)offs[n_reads] != n_bases)
+        return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[n_reads] = %lld, not n_bases = %llu (the last read must end where the batch ends)", fn,
+                       (long long)offs[n_reads], (unsigned long long)n_bases);
+    return KDF_OK;
+}
+
+// keep: this append brings read offsets.  The first append since create / clear decides what the spool keeps.
+static int ks_check_append(kdf_spool *sp, const void *p, const void *m, uint64_t n_bases, const char *fn, bool keep = false) {
+    if (sp->mode != KS_MODE_OPEN && (sp->mode == KS_MODE_READS) != keep)
+        return ks_fail(sp, KDF_ERR_STATE, keep ? "%s: the spool keeps no read offsets (its first append brought none): kdf_spool_append* or kdf_spool_clear"
+                                               : "%s: the spool keeps read offsets: kdf_spool_append*_reads or kdf_spool_clear", fn);
     if (n_bases > (1ull << 31)) return ks_fail(sp, KDF_ERR_INVALID, "%s: a batch of %llu positions (at most 2^31)", fn, (unsigned long long)n_bases);
     if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed (kdf_spool_clear)", fn);
     if (n_bases && (!p || !m)) return ks_fail(sp, KDF_ERR_INVALID, "%s: NULL stream", fn);
     return KDF_OK;
 }
 
-// one batch from DEVICE buffers, on stream s (behind every earlier append)
-static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
+// one batch from DEVICE buffers, on stream s (behind every earlier append).  keep: with its n_reads + 1 read offsets,
+// either on the device (d_offs) or in host memory that stays valid until the copy queued here has run (h_offs).
+static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases,
+                            bool keep = false, const int64_t *d_offs = nullptr, const int64_t *h_offs = nullptr, uint64_t n_reads = 0) {
     const uint64_t n_tiles = n_bases / KDF_TILE + 1;
     KsSegment *seg = nullptr;
-    int rc = spool_place(sp, n_tiles, &seg);
+    bool fresh = false;
+    int rc = spool_place(sp, n_tiles, &seg, &fresh, keep ? n_reads : 0, n_bases);
     if (rc) return rc;
-    uint64_t *dp = seg->packed + 2 * seg->tiles, *dm = seg->mask + seg->tiles;
-    if (seg->host) {
-        if ((rc = ks_stage_reserve(sp, 2, (2 * n_tiles + 4) * 8)) || (rc = ks_stage_reserve(sp, 3, (n_tiles + 2) * 8))) { sp->overflowed = true; return rc; }
-        dp = (uint64_t *)sp->stage[2]; dm = (uint64_t *)sp->stage[3];
+    if (keep && (rc = ks_offsets_reserve(sp, seg, seg->n_reads + n_reads + 1, n_bases, n_reads))) {
+        if (fresh) {                                               // nothing of this batch stays behind
+            if (seg->host) { (void)hipHostFree(seg->packed); (void)hipHostFree(seg->mask); sp->host_bytes -= seg->bytes; }
+            else { (void)hipFree(seg->packed); (void)hipFree(seg->mask); sp->hbm_bytes -= seg->bytes; }
+            sp->segs.pop_back();
+        }
+        return rc;
     }
+    uint64_t *dp = seg->packed + 2 * seg->tiles, *dm = seg->mask + seg->tiles;
+    int64_t *doffs = keep ? seg->offs + seg->n_reads : nullptr;
+    if (seg->host) {
+        if ((rc = ks_stage_reserve(sp, 2, (2 * n_tiles + 4) * 8)) || (rc = ks_stage_reserve(sp, 3, (n_tiles + 2) * 8)) ||
+            (keep && (rc = ks_stage_reserve(sp, 5, (n_reads + 1) * 8)))) { sp->overflowed = true; return rc; }
+        dp = (uint64_t *)sp->stage[2]; dm = (uint64_t *)sp->stage[3];
+        if (keep) doffs = (int64_t *)sp->stage[5];
+    }
+    if (keep && h_offs && (rc = ks_stage_reserve(sp, 4, (n_reads + 1) * 8))) return rc;
     if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(s, sp->last, 0));
+    if (keep && h_offs) {
+        KSCHK(sp, hipMemcpyAsync(sp->stage[4], h_offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+        d_offs = (const int64_t *)sp->stage[4];
+    }
     const unsigned blocks = (unsigned)std::min<uint64_t>((n_tiles + 2 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (sp->prof) {
@@ -3415,14 +3549,29 @@ static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_pack
                        (int)(((uintptr_t)d_packed & 15) == 0));
     KSCHK(sp, hipGetLastError());
     if (sp->prof) { KSCHK(sp, hipEventRecord(e1, s)); sp->prof_ev.emplace_back(e0, e1); }
+    if (keep) {
+        // entries n_reads(seg) .. n_reads(seg) + n_reads: the first overwrites the last entry of the batch before (kdf.h: the gap)
+        const unsigned oblocks = (unsigned)std::min<uint64_t>((n_reads + 1 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
+        hipEvent_t o0 = nullptr, o1 = nullptr;
+        if (sp->prof) {
+            KSCHK(sp, hipEventCreate(&o0)); KSCHK(sp, hipEventCreate(&o1));
+            KSCHK(sp, hipEventRecord(o0, s));
+        }
+        hipLaunchKernelGGL(ks_offsets_kernel, dim3(oblocks), dim3(KS_THREADS), 0, s, doffs, d_offs, n_reads + 1, (int64_t)(seg->tiles * KDF_TILE));
+        KSCHK(sp, hipGetLastError());
+        if (sp->prof) { KSCHK(sp, hipEventRecord(o1, s)); sp->prof_offs_ev.emplace_back(o0, o1); }
+    }
     if (seg->host) {
         KSCHK(sp, hipMemcpyAsync(seg->packed + 2 * seg->tiles, dp, (2 * n_tiles + 4) * 8, hipMemcpyDeviceToHost, s));
         KSCHK(sp, hipMemcpyAsync(seg->mask + seg->tiles, dm, (n_tiles + 2) * 8, hipMemcpyDeviceToHost, s));
+        if (keep) KSCHK(sp, hipMemcpyAsync(seg->offs + seg->n_reads, doffs, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
     }
     KSCHK(sp, hipEventRecord(sp->last, s));
     sp->have_last = true;
     seg->tiles += n_tiles;
     ++sp->batches; sp->bases += n_bases;
+    if (keep) { seg->n_reads += n_reads; sp->reads += n_reads; }
+    sp->mode = keep ? KS_MODE_READS : KS_MODE_STREAM;
     return KDF_OK;
 }
 
@@ -3437,7 +3586,10 @@ int kdf_spool_create(int device, uint64_t hbm_budget_bytes, uint64_t host_budget
     kdf_spool *sp = new kdf_spool();
     sp->device = device; sp->hbm_budget = hbm_budget_bytes; sp->host_budget = host_budget_bytes;
     if ((e = hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sp->last, hipEventDisableTiming)) != hipSuccess) {
+        (e = hipEventCreateWithFlags(&sp->last, hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sp->pin_done[0], hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sp->pin_done[1], hipEventDisableTiming)) != hipSuccess ||
+        (e = hipEventCreateWithFlags(&sp->rep_done, hipEventDisableTiming)) != hipSuccess) {
         ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: %s", hipGetErrorString(e));
         kdf_spool_destroy(sp);
         return KDF_ERR_HIP;
@@ -3450,6 +3602,9 @@ void kdf_spool_destroy(kdf_spool *sp) {
     if (!sp) return;
     ks_free_all(sp);
     if (sp->last) (void)hipEventDestroy(sp->last);
+    for (int i = 0; i < 2; ++i) if (sp->pin_done[i]) (void)hipEventDestroy(sp->pin_done[i]);
+    if (sp->rep_done) (void)hipEventDestroy(sp->rep_done);
+    if (sp->sel_total) (void)hipHostFree(sp->sel_total);
     if (sp->stream) (void)hipStreamDestroy(sp->stream);
     delete sp;
 }
@@ -3468,6 +3623,9 @@ int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value) {
     if (n == "segment_positions") {
         if (value < (1ll << 12) || value > (1ll << 31)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: segment_positions must be 2^12 .. 2^31");
         sp->opt_segment_positions = (uint64_t)value;               // (segments already allocated keep their size)
+    } else if (n == "offsets_chunk") {
+        if (value < 1 || value > (1ll << 28)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: offsets_chunk must be 1 .. 2^28 entries");
+        sp->opt_offsets_chunk = (uint64_t)value;                   // (arrays already allocated keep their size)
     } else if (n == "profile") {
         if (!value) { (void)hipSetDevice(sp->device); ks_prof_collect(sp); }
         sp->prof = value != 0;
@@ -3487,6 +3645,12 @@ int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value) {
     else if (n == "overflowed") *value = sp->overflowed ? 1 : 0;
     else if (n == "replays") *value = (int64_t)sp->replays;
     else if (n == "segment_positions") *value = (int64_t)sp->opt_segment_positions;
+    else if (n == "offsets_chunk") *value = (int64_t)sp->opt_offsets_chunk;
+    else if (n == "reads") *value = (int64_t)sp->reads;
+    else if (n == "keeps_reads") *value = sp->mode == KS_MODE_READS ? 1 : 0;
+    else if (n == "offset_bytes") *value = (int64_t)sp->offset_bytes;
+    else if (n == "offsets_us") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)(sp->prof_offs_ms * 1000.0 + 0.5); }
+    else if (n == "offsets_passes") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)sp->prof_offs_passes; }
     else if (n == "append_us") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)(sp->prof_ms * 1000.0 + 0.5); }
     else if (n == "append_passes") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)sp->prof_passes; }
     else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: unknown stat %s", name);
@@ -3529,6 +3693,207 @@ int kdf_spool_append_uploaded(kdf_spool *sp, kdf_engine *h, int slot) {
     rc = spool_append_dev(sp, h->stream, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
     (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
     return rc;
+}
+
+// ---- appends that bring their read offsets ----
+
+int kdf_spool_append_reads_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                               const void *d_read_offsets, int64_t n_reads) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    int rc = ks_check_append(sp, d_packed, d_invalid, n_bases, "kdf_spool_append_reads_dev", true);
+    if (rc) return rc;
+    if (n_reads < 0) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_reads_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads == 0) return n_bases ? ks_check_offsets(sp, "kdf_spool_append_reads_dev", nullptr, 0, n_bases) : KDF_OK;
+    if (n_bases == 0) return ks_check_offsets(sp, "kdf_spool_append_reads_dev", nullptr, n_reads, 0);
+    if (!d_read_offsets) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_reads_dev: read_offsets is NULL");
+    KSCHK(sp, hipSetDevice(sp->device));
+    return spool_append_dev(sp, (hipStream_t)hip_stream, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, true,
+                            (const int64_t *)d_read_offsets, nullptr, (uint64_t)n_reads);
+}
+
+int kdf_spool_append_reads(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
+                           int64_t n_reads) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    int rc = ks_check_append(sp, packed, invalid, n_bases, "kdf_spool_append_reads", true);
+    if (rc || (rc = ks_check_offsets(sp, "kdf_spool_append_reads", read_offsets, n_reads, n_bases)) || n_reads == 0) return rc;
+    KSCHK(sp, hipSetDevice(sp->device));
+    const uint64_t src_tiles = (n_bases + 63) / 64;                 // (>= 1: a batch with reads has positions)
+    if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
+    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));
+    KSCHK(sp, hipMemcpyAsync(sp->stage[0], packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    KSCHK(sp, hipMemcpyAsync(sp->stage[1], invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0], (const uint64_t *)sp->stage[1], n_bases, true, nullptr, read_offsets,
+                          (uint64_t)n_reads);
+    KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
+    return rc;
+}
+
+int kdf_spool_append_uploaded_reads(kdf_spool *sp, kdf_engine *h, int slot, const int64_t *read_offsets, int64_t n_reads) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: NULL engine");
+    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: the spool is on device %d, the engine on %d", sp->device, h->device);
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_append_uploaded_reads: nothing was uploaded into slot %d", slot);
+    const uint64_t n = h->up_n[slot];
+    int rc = ks_check_append(sp, h->up_buf[slot][0], h->up_buf[slot][1], n, "kdf_spool_append_uploaded_reads", true);
+    if (rc || (rc = ks_check_offsets(sp, "kdf_spool_append_uploaded_reads", read_offsets, n_reads, n)) || n_reads == 0) return rc;
+    KSCHK(sp, hipSetDevice(sp->device));
+    // through pinned memory: the copy is queued behind the engine's work and the caller's array is not read after this returns
+    const size_t entries = (size_t)n_reads + 1;
+    if (sp->have_pin_done[slot]) KSCHK(sp, hipEventSynchronize(sp->pin_done[slot]));   // (the slot's append before this one)
+    if (sp->pin_entries[slot] < entries) {
+        if (sp->pin_offs[slot]) (void)hipHostFree(sp->pin_offs[slot]);
+        sp->pin_offs[slot] = nullptr; sp->pin_entries[slot] = 0;
+        const size_t want = entries + entries / 8 + 512;
+        const hipError_t e = hipHostMalloc((void **)&sp->pin_offs[slot], want * 8, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); sp->pin_offs[slot] = nullptr; return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of pinned staging: %s", want * 8, hipGetErrorString(e)); }
+        sp->pin_entries[slot] = want;
+    }
+    memcpy(sp->pin_offs[slot], read_offsets, entries * 8);
+    KSCHK(sp, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
+    rc = spool_append_dev(sp, h->stream, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n, true, nullptr, sp->pin_offs[slot],
+                          (uint64_t)n_reads);
+    if (hipEventRecord(sp->pin_done[slot], h->stream) == hipSuccess) sp->have_pin_done[slot] = true;
+    else { (void)hipGetLastError(); (void)hipStreamSynchronize(h->stream); sp->have_pin_done[slot] = false; }
+    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
+    return rc;
+}
+
+int kdf_spool_read_offsets(kdf_spool *sp, uint64_t seg, int64_t *out, uint64_t *first_read_out, uint64_t *n_reads_out) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_read_offsets: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
+    if (sp->mode != KS_MODE_READS) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_read_offsets: the spool keeps no read offsets (kdf_spool_append*_reads)");
+    const KsSegment &s = sp->segs[seg];
+    if (first_read_out) *first_read_out = s.first_read;
+    if (n_reads_out) *n_reads_out = s.n_reads;
+    if (!out) return KDF_OK;
+    KSCHK(sp, hipSetDevice(sp->device));
+    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
+    KSCHK(sp, hipMemcpy(out, s.offs, (s.n_reads + 1) * 8, s.host ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
+    return KDF_OK;
+}
+
+int kdf_spool_segment_dev(kdf_spool *sp, uint64_t seg, const void **d_packed, const void **d_invalid, uint64_t *n_positions,
+                          const void **d_offsets, uint64_t *first_read, uint64_t *n_reads) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_segment_dev: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
+    const KsSegment &s = sp->segs[seg];
+    if (s.host)
+        return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_segment_dev: segment %llu is in host memory, no device pointer exists (kdf_spool_read_segment "
+                       "copies it out)", (unsigned long long)seg);
+    KSCHK(sp, hipSetDevice(sp->device));
+    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));  // complete for every stream the caller may use
+    if (d_packed) *d_packed = s.packed;
+    if (d_invalid) *d_invalid = s.mask;
+    if (n_positions) *n_positions = s.tiles * KDF_TILE;
+    if (d_offsets) *d_offsets = sp->mode == KS_MODE_READS ? s.offs : nullptr;
+    if (first_read) *first_read = s.first_read;
+    if (n_reads) *n_reads = s.n_reads;
+    return KDF_OK;
+}
+
+// ---- replays of the per-read consumers ----
+
+static int ks_rep_reserve(kdf_spool *sp, int i, size_t bytes) {
+    if (sp->rep_bytes[i] >= bytes) return KDF_OK;
+    if (sp->rep[i]) {
+        KSCHK(sp, hipDeviceSynchronize());                         // (its last reader ran on some engine's stream)
+        (void)hipFree(sp->rep[i]); sp->rep[i] = nullptr; sp->rep_bytes[i] = 0;
+    }
+    const size_t want = bytes + bytes / 8 + 4096;
+    const hipError_t e = hipMalloc(&sp->rep[i], want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); sp->rep[i] = nullptr;
+        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of staging for a host-tier segment do not fit the device (%s)", want, hipGetErrorString(e));
+    }
+    sp->rep_bytes[i] = want;
+    return KDF_OK;
+}
+
+// Every segment in order through kdf_read_hits_dev (depth false; 8 bytes a row) or kdf_read_depth_dev (48 bytes a row),
+// rows of segment s at first_read(s).
+static int spool_replay_reads(kdf_spool *sp, kdf_engine *h, const char *fn, bool depth, uint32_t low_max, void *d_rows_out) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "%s: NULL engine", fn);
+    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "%s: the spool is on device %d, the engine on %d", fn, sp->device, h->device);
+    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)", fn);
+    if (sp->mode == KS_MODE_STREAM) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool keeps no read offsets (fill it through kdf_spool_append*_reads)", fn);
+    if (sp->reads == 0) return KDF_OK;
+    if (!d_rows_out) return ks_fail(sp, KDF_ERR_INVALID, "%s: rows_out is NULL", fn);
+    KSCHK(sp, hipSetDevice(sp->device));
+    bool any_host = false;
+    for (auto &s : sp->segs) any_host |= s.host && s.n_reads;
+    if (sp->have_last) {
+        KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
+        if (any_host) KSCHK(sp, hipEventSynchronize(sp->last));    // (the copies below read host memory)
+    }
+    const size_t row_bytes = depth ? KD_ROW_WORDS * 8 : KH_ROW_WORDS * 4;
+    for (size_t i = 0; i < sp->segs.size(); ++i) {
+        const KsSegment &s = sp->segs[i];
+        if (s.n_reads == 0) continue;
+        const uint64_t n = s.tiles * KDF_TILE;
+        const void *p = s.packed, *m = s.mask, *o = s.offs;
+        if (s.host) {
+            const size_t pb = (2 * s.tiles + 4) * 8, mb = (s.tiles + 2) * 8, ob = (s.n_reads + 1) * 8;
+            int rc;
+            if ((rc = ks_rep_reserve(sp, 0, pb)) || (rc = ks_rep_reserve(sp, 1, mb)) || (rc = ks_rep_reserve(sp, 2, ob))) return rc;
+            if (sp->have_rep_done) KSCHK(sp, hipStreamWaitEvent(h->stream, sp->rep_done, 0));
+            KSCHK(sp, hipMemcpyAsync(sp->rep[0], s.packed, pb, hipMemcpyHostToDevice, h->stream));
+            KSCHK(sp, hipMemcpyAsync(sp->rep[1], s.mask, mb, hipMemcpyHostToDevice, h->stream));
+            KSCHK(sp, hipMemcpyAsync(sp->rep[2], s.offs, ob, hipMemcpyHostToDevice, h->stream));
+            p = sp->rep[0]; m = sp->rep[1]; o = sp->rep[2];
+        }
+        char *rows = (char *)d_rows_out + s.first_read * row_bytes;
+        const int rc = depth ? kdf_read_depth_dev(h, p, m, n, o, (int64_t)s.n_reads, low_max, rows)
+                             : kdf_read_hits_dev(h, p, m, n, o, (int64_t)s.n_reads, nullptr, rows);
+        if (s.host) { KSCHK(sp, hipEventRecord(sp->rep_done, h->stream)); sp->have_rep_done = true; }
+        if (rc) return ks_fail(sp, rc, "%s: segment %zu: %s", fn, i, h->err.c_str());
+    }
+    ++sp->replays;
+    return KDF_OK;
+}
+
+int kdf_spool_read_hits(kdf_spool *sp, kdf_engine *h, void *d_rows_out) {
+    return spool_replay_reads(sp, h, "kdf_spool_read_hits", false, 0, d_rows_out);
+}
+
+int kdf_spool_read_depth(kdf_spool *sp, kdf_engine *h, uint32_t low_max, void *d_rows_out) {
+    return spool_replay_reads(sp, h, "kdf_spool_read_depth", true, low_max, d_rows_out);
+}
+
+int kdf_spool_select_reads(kdf_spool *sp, const void *d_hit_rows, uint32_t min_distinct, void *d_reads_out, uint64_t cap, uint64_t *n_out) {
+    if (!sp || !n_out) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: NULL pointer");
+    *n_out = 0;
+    if (sp->mode == KS_MODE_STREAM) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_select_reads: the spool keeps no read offsets (fill it through kdf_spool_append*_reads)");
+    const uint64_t n_rows = sp->reads;
+    if (n_rows == 0) return KDF_OK;
+    if (!d_hit_rows || (cap && !d_reads_out)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: NULL pointer");
+    const uint64_t n_blocks = (n_rows + KS_SELECT_ROWS - 1) / KS_SELECT_ROWS;
+    if (n_blocks >= (1ull << 24))                                  // (a grid of 256-thread blocks stays below 2^32 threads)
+        return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: %llu rows are beyond the 2^34 a call takes", (unsigned long long)n_rows);
+    KSCHK(sp, hipSetDevice(sp->device));
+    if (!sp->sel_total) KSCHK(sp, hipHostMalloc((void **)&sp->sel_total, 8, hipHostMallocDefault));
+    if (sp->sel_bytes < (n_blocks + 1) * 8) {                      // (every earlier use ended in a synchronise)
+        if (sp->sel_buf) (void)hipFree(sp->sel_buf);
+        sp->sel_buf = nullptr; sp->sel_bytes = 0;
+        const size_t want = (n_blocks + 1) * 8 + n_blocks + 4096;
+        const hipError_t e = hipMalloc(&sp->sel_buf, want);
+        if (e != hipSuccess) { (void)hipGetLastError(); sp->sel_buf = nullptr; return ks_fail(sp, KDF_ERR_NOMEM, "kdf_spool_select_reads: %zu bytes of block sums: %s", want, hipGetErrorString(e)); }
+        sp->sel_bytes = want;
+    }
+    unsigned long long *sums = (unsigned long long *)sp->sel_buf;
+    const int rows16 = (int)(((uintptr_t)d_hit_rows & 15) == 0);
+    hipLaunchKernelGGL(ks_select_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, sp->stream, (const uint64_t *)d_hit_rows, n_rows, min_distinct, rows16, sums);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, sp->stream, sums, n_blocks);
+    if (cap)
+        hipLaunchKernelGGL(ks_select_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, sp->stream, (const uint64_t *)d_hit_rows, n_rows, min_distinct,
+                           rows16, (const unsigned long long *)sums, (uint64_t *)d_reads_out, cap);
+    KSCHK(sp, hipGetLastError());
+    KSCHK(sp, hipMemcpyAsync(sp->sel_total, sums + n_blocks, 8, hipMemcpyDeviceToHost, sp->stream));
+    KSCHK(sp, hipStreamSynchronize(sp->stream));
+    *n_out = *sp->sel_total;
+    if (*n_out > cap)
+        return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: %llu reads are selected, the buffer holds %llu", (unsigned long long)*n_out, (unsigned long long)cap);
+    return KDF_OK;
 }
 
 int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, uint64_t *invalid_out, uint64_t *n_positions_out) {

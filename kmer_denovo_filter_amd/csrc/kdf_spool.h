@@ -1,4 +1,4 @@
-// kdf_spool.h -- the read spool's one kernel (kdf.h "read spool"; the host side is in kdf_engine.hip).
+// kdf_spool.h -- the read spool's kernels (kdf.h "read spool"; the host side is in kdf_engine.hip).
 //
 // A spool keeps the batches of a read stream resident, packed as they arrive (3 bits per position), as a list of SEGMENTS.
 // A segment is one read stream in the layout of kdf.h "Read streams"; a batch of n_bases positions occupies
@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "kdf_hits.h"            // kh_block_excl, kh_scan_kernel: the block scan the ks_select_* kernels share with kh_*
 
 #define KS_THREADS 256
 #define KS_MAX_BLOCKS 2048u      // a streaming copy: 8 workgroups per CU fill the device, the rest is a grid stride
@@ -54,6 +55,64 @@ __global__ __launch_bounds__(KS_THREADS) void ks_append_kernel(uint64_t *__restr
         *reinterpret_cast<ulonglong2 *>(dp + 2 * i) = o;
         dm[i] = m;
     }
+}
+
+// ks_offsets_kernel: rebase one batch's read offsets into SEGMENT coordinates.  dst points at the batch's first entry in
+// the segment's offsets array (the entry the batch before it wrote last, which this batch owns now), src at the batch's
+// n = n_reads + 1 offsets, base = 64 x the batch's first tile.  One 8-byte load and one 8-byte store per lane; entries
+// dst[0 .. n) are written and nothing else, whatever src holds.
+__global__ __launch_bounds__(KS_THREADS) void ks_offsets_kernel(int64_t *__restrict__ dst, const int64_t *__restrict__ src,
+                                                                uint64_t n, int64_t base) {
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < n; i += stride) dst[i] = src[i] + base;
+}
+
+// ks_select_*: the reads whose `distinct` (the second uint32 of a kdf_read_hits row) is at least min_distinct, as the
+// ASCENDING list of their indices -- an order-preserving compaction in the shape of kh_count / kh_scan / kh_write:
+//   1. ks_select_count_kernel   KS_SELECT_ROWS rows per workgroup, 4 consecutive rows per thread -> block sums
+//   2. kh_scan_kernel           exclusive scan of the block sums, the total behind them
+//   3. ks_select_write_kernel   the same rows again, a workgroup scan of the per-thread counts, every thread writes the
+//                               indices of its rows: entry e < cap only
+// A row is one 8-byte word (hits in the low half, distinct in the high half); rows16: the rows are 16-byte aligned, so a
+// thread's 4 rows (row index a multiple of 4) are two 16-byte loads.  Rows at and past n_rows are not loaded.
+#define KS_SELECT_ROWS 1024
+
+__device__ __forceinline__ uint32_t ks_select_mask(const uint64_t *__restrict__ rows, uint64_t r0, uint64_t n_rows, uint32_t min_distinct,
+                                                   int rows16) {
+    uint64_t x[4] = {0, 0, 0, 0};
+    if (r0 + 4 <= n_rows && rows16) {
+        const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(rows + r0), b = *reinterpret_cast<const ulonglong2 *>(rows + r0 + 2);
+        x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (r0 + j < n_rows) x[j] = rows[r0 + j];
+    }
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (r0 + j < n_rows && (uint32_t)(x[j] >> 32) >= min_distinct) m |= 1u << j;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void ks_select_count_kernel(const uint64_t *__restrict__ rows, uint64_t n_rows, uint32_t min_distinct,
+                                                              int rows16, unsigned long long *__restrict__ block_sums) {
+    __shared__ uint32_t ws[4];
+    const uint64_t r0 = (uint64_t)blockIdx.x * KS_SELECT_ROWS + threadIdx.x * 4;
+    uint32_t total;
+    kh_block_excl((uint32_t)__popc(ks_select_mask(rows, r0, n_rows, min_distinct, rows16)), ws, total);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void ks_select_write_kernel(const uint64_t *__restrict__ rows, uint64_t n_rows, uint32_t min_distinct,
+                                                              int rows16, const unsigned long long *__restrict__ block_off,
+                                                              uint64_t *__restrict__ out, uint64_t cap) {
+    __shared__ uint32_t ws[4];
+    const uint64_t r0 = (uint64_t)blockIdx.x * KS_SELECT_ROWS + threadIdx.x * 4;
+    const uint32_t m = ks_select_mask(rows, r0, n_rows, min_distinct, rows16);
+    uint32_t total;
+    uint64_t o = block_off[blockIdx.x] + kh_block_excl((uint32_t)__popc(m), ws, total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (m >> j & 1) { if (o < cap) out[o] = r0 + j; ++o; }
 }
 
 #endif /* KDF_SPOOL_H */

@@ -298,7 +298,9 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
     (``prefilter_add_uploaded``) instead of its table.  ``spool``: a ``spool.ReadSpool`` on the engine's device -- every
     batch is also appended to it from its upload slot, before it is counted or tallied, so that later passes replay the
     spool and not the file.  A spool that overflows stops taking batches (it reads ``stat("overflowed")``: the caller
-    streams the file again for the later passes); the pass itself goes on.  Returns the number of reads."""
+    streams the file again for the later passes); the pass itself goes on.  A spool whose ``keep_reads`` attribute is set
+    also gets every batch's read offsets (``ReadSpool.read_hits`` / ``read_depth`` / ``select_reads`` over it afterwards).
+    Returns the number of reads."""
     import queue
     import threading
     if not isinstance(readers, (list, tuple)):
@@ -332,13 +334,17 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
         th.start()
     take_slot = engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
     spooling = [spool]
+    keep_reads = bool(getattr(spool, "keep_reads", False))
 
-    def take(slot):
+    def take(slot, st):
         # the spool's copy runs on the engine's stream right before the count of the same slot (not at upload time: the
         # engine's stream would then wait for the copy of batch i + 1 before it counts batch i); the slot keeps the batch
         if spooling[0] is not None:
             try:
-                spooling[0].append_uploaded(engine, slot)
+                if keep_reads:
+                    spooling[0].append_uploaded(engine, slot, offsets=st.offsets)
+                else:
+                    spooling[0].append_uploaded(engine, slot)
             except _native.KdfError as ex:
                 if ex.code != _native.KDF_ERR_NOMEM:
                     raise
@@ -359,12 +365,12 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
             engine.upload_async(slot, st)                    # returns at once: the buffer is pinned
             n_reads += st.n_reads
             if pending is not None:
-                take(pending[0])
+                take(pending[0], pending[2])
                 free.put(pending[1])                         # count_uploaded waited (on the HOST) for this buffer's copy
-            pending = (slot, i)
+            pending = (slot, i, st)
             slot ^= 1
         if pending is not None:
-            take(pending[0])
+            take(pending[0], pending[2])
             pending = None
     finally:
         stop.set()
