@@ -795,6 +795,70 @@ int kdf_spool_read_depth(kdf_spool *sp, kdf_engine *h, uint32_t low_max, void *d
 int kdf_spool_select_reads(kdf_spool *sp, const void *d_hit_rows, uint32_t min_distinct, void *d_reads_out, uint64_t cap,
                            uint64_t *n_out);
 
+/* ------------------------------------------------- distinct k-mer sketch ---- */
+
+/* How many distinct canonical k-mers does a read stream hold -- answered WITHOUT storing them, so that a table, the
+ * number of key slices ("key_parts") and an owner table are sized from the reads before any key is inserted (SURVEY.md
+ * section 8a row A13: "sizes from a distinct-count estimate").  A HyperLogLog sketch (Flajolet, Fusy, Gandouet, Meunier
+ * 2007) of m = 2^p one-byte registers, owned by an engine because the engine knows k and the key kernels, and
+ * independent of everything else the engine holds: it never flushes, reads or writes the table; it works in insert
+ * mode, in filter mode and while a prefilter is tallying or armed; it survives kdf_clear, kdf_load_filter* and
+ * kdf_set_stream; kdf_destroy frees it.  The kernel only walks the stream (kdf_sketch.h): a sketch pass rides on the
+ * pass that fills a read spool, or replays one (kdf_spool_sketch).
+ *
+ * Contract (tests/sketch_model.py restates it in numpy from this text alone):
+ *   - a window is sketched iff it is valid by "Read streams" points 1-2, on every path (host, device, uploaded, spool):
+ *     positions at or past n_bases are invalid whatever the buffers hold.  "key_parts" and an armed prefilter are NOT
+ *     consulted: the sketch describes the whole stream.
+ *   - its key is the canonical key; h is the key's stored form as defined under "two-pass counting": kdf_mix64(key)
+ *     for k <= 32, the pair (h, hi) with h = kdf_mix64(lo ^ rotl(hi, 37)) for 33 <= k <= 63, the folded
+ *     h = kdf_mix64(w0 ^ f) for long keys.
+ *   - x = h for k <= 32 and for long keys, x = h + hi * 0xD6E8FEB86659FD93 for 33 <= k <= 63 (both words of the stored
+ *     pair, so two keys whose lo ^ rotl(hi, 37) agree stay two keys); g = fin(x), the finaliser of splitmix64:
+ *         x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31      (mod 2^64)
+ *     kdf_mix64 ends in a multiply: bit i of h depends on the key bits at and below i only, so its top bits (which
+ *     address the table) see the whole key and the bits further down do not -- and the rank is read from the bits below
+ *     the index.  The two further xorshift-multiply rounds bring every key bit to every bit of g.
+ *   - register index j = g >> (64 - p); rank r = 1 + clz((g << p) | (1 << (p - 1))) (64-bit), so 1 <= r <= 65 - p;
+ *     reg[j] = max over all sketched windows (0: no window yet).
+ *   - because this is a max, the registers do not depend on batch order, batch boundaries, concurrency or path: they
+ *     are bit-identical from run to run, between the host, device and uploaded forms, and between one engine over the
+ *     whole sample and the merge of engines over its shards (reads are sharded, so no window is lost at a boundary).
+ * Estimate (host, double, the registers summed in index order: reproducible): m = 2^p, alpha = 0.7213 / (1 + 1.079 / m),
+ * E = alpha m^2 / sum_j 2^(-reg[j]); if E <= 2.5 m and V = #{j : reg[j] = 0} > 0 then E = m ln(m / V) (linear
+ * counting).  The standard error is 1.04 / sqrt(m) (0.41 % at the default p = 16, 1.6 % at p = 12).  Between 2.5 m and
+ * 5 m the classic estimator is biased by a few percent (no bias table is applied): a consumer that sizes memory adds its
+ * own margin.  There is no large-range correction: g has 64 bits.
+ * State: off -> kdf_sketch_begin -> on -> kdf_sketch_drop -> off.  begin: p = 10..18, 0 = 16 (else KDF_ERR_INVALID);
+ * zeroes the registers; begin while a sketch is on is KDF_ERR_STATE.  Every other call without a sketch is
+ * KDF_ERR_STATE.  The add calls take a stream exactly as the count takes it; n_bases == 0 is KDF_OK; they run in stream
+ * order and do not synchronise, kdf_sketch_registers* and kdf_sketch_estimate do.  kdf_sketch_add_uploaded reads the
+ * batch a slot holds (kdf_upload_reads_async) and the slot KEEPS it, as for kdf_spool_append_uploaded: the caller counts
+ * or tallies it next; the call returns once the slot's copy is complete (the engine's stream is not synchronised), so a pass
+ * that only sketches may rewrite the batch's host arrays then, as after kdf_count_uploaded.  kdf_sketch_registers writes the 2^p bytes to host memory, the _dev form to caller-owned HBM.
+ * kdf_sketch_merge: reg = max(own, given) over 2^p host bytes (another engine's registers of the same p: another rank's
+ * after an all-reduce(MAX), another shard's); a byte above 65 - p is KDF_ERR_INVALID and nothing is written; complete on
+ * return.  kdf_sketch_estimate_registers is the estimate as a pure host function (no engine, no GPU): p = 10..18, a
+ * byte above 65 - p is KDF_ERR_INVALID.
+ * kdf_spool_sketch adds every segment of a spool in order: HBM-tier segments as they lie, host-tier segments through
+ * the engine's two upload slots (they are free again afterwards), as kdf_spool_replay does, with the same refusals
+ * (an overflowed spool and a slot that holds a caller's batch KDF_ERR_STATE, another device KDF_ERR_INVALID; no sketch
+ * on: KDF_ERR_STATE).  The spool does not change ("replays" counts kdf_spool_replay only).
+ * Stats (kdf_get_stat): "sketch_state" (0 / 1), "sketch_log2_registers", "sketch_windows" (windows THIS engine added
+ * since begin: a merge does not change it), and under kdf_profile(h, 1) "sketch_us" / "sketch_passes" (the add
+ * kernels, HIP events). */
+int kdf_sketch_begin(kdf_engine *h, uint32_t log2_registers);
+int kdf_sketch_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases);
+int kdf_sketch_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases);
+int kdf_sketch_add_uploaded(kdf_engine *h, int slot);
+int kdf_sketch_registers(kdf_engine *h, uint8_t *regs_out);
+int kdf_sketch_registers_dev(kdf_engine *h, void *d_regs_out);
+int kdf_sketch_merge(kdf_engine *h, const uint8_t *regs);
+int kdf_sketch_estimate(kdf_engine *h, double *distinct_out);
+int kdf_sketch_drop(kdf_engine *h);
+int kdf_sketch_estimate_registers(const uint8_t *regs, uint32_t log2_registers, double *distinct_out);
+int kdf_spool_sketch(kdf_spool *sp, kdf_engine *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,18 @@ SYMBOLS = [
     ("kdf_spool_read_hits", c_int, [_P, _P, _P]),
     ("kdf_spool_read_depth", c_int, [_P, _P, c_uint32, _P]),
     ("kdf_spool_select_reads", c_int, [_P, _P, c_uint32, _P, c_uint64, POINTER(c_uint64)]),
+    # distinct k-mer sketch (HyperLogLog registers over the canonical k-mers of read streams)
+    ("kdf_sketch_begin", c_int, [_P, c_uint32]),
+    ("kdf_sketch_add_reads", c_int, [_P, _P, _P, c_uint64]),
+    ("kdf_sketch_add_reads_dev", c_int, [_P, _P, _P, c_uint64]),
+    ("kdf_sketch_add_uploaded", c_int, [_P, c_int]),
+    ("kdf_sketch_registers", c_int, [_P, _P]),
+    ("kdf_sketch_registers_dev", c_int, [_P, _P]),
+    ("kdf_sketch_merge", c_int, [_P, _P]),
+    ("kdf_sketch_estimate", c_int, [_P, POINTER(ctypes.c_double)]),
+    ("kdf_sketch_drop", c_int, [_P]),
+    ("kdf_sketch_estimate_registers", c_int, [_P, c_uint32, POINTER(ctypes.c_double)]),
+    ("kdf_spool_sketch", c_int, [_P, _P]),
 ]
 
 _lib = None

@@ -23,7 +23,7 @@ from .. import dist_env, jf_io
 from .._native import KdfError
 from ..engine import mirror_engine
 from ..kmer_fasta import read_kmer_fasta_keys
-from ..reads import ReadStream, bam_reader, fasta_reader, keys_to_kmers, stream_batches_overlapped
+from ..reads import ReadStream, bam_reader, fasta_reader, keys_to_kmers, sketch_batches_overlapped, stream_batches_overlapped
 
 logger = logging.getLogger(__name__)
 
@@ -107,6 +107,16 @@ def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False, spo
     pass 1 of a two-pass count (the engine's prefilter) instead of the table.  ``spool``: a ``ReadSpool`` that also
     keeps every batch of this pass (``stream_batches_overlapped``) -- with its read offsets when ``spool.keep_reads``
     is set."""
+    return _stream_bam_pass(engine, bam_path, threads, filtered, tally, spool, False)
+
+
+def _sketch_bam(engine, bam_path, ref_fasta, threads, spool=None):
+    """The same readers as a sizing pass into the engine's distinct k-mer sketch (``sketch_batches_overlapped``):
+    nothing is counted; a ``spool`` is filled on the way."""
+    return _stream_bam_pass(engine, bam_path, threads, False, False, spool, True)
+
+
+def _stream_bam_pass(engine, bam_path, threads, filtered, tally, spool, sketch):
     if str(bam_path).endswith(".cram"):
         raise RuntimeError(
             "jellyfish count failed: CRAM input needs htslib, which the MI355X engine does not link; "
@@ -125,6 +135,8 @@ def _stream_bam(engine, bam_path, ref_fasta, threads, filtered, tally=False, spo
         for j in range(local):
             readers.append(bam_reader(bam_path, max_bases=BATCH_BASES, max_reads=1 << 21, threads=per,
                                       part=rank * local + j, parts=world * local))
+        if sketch:
+            return sketch_batches_overlapped(engine, readers, spool=spool)
         if spool is not None:
             return stream_batches_overlapped(engine, readers, filtered, tally=tally, spool=spool)
         return stream_batches_overlapped(engine, readers, filtered, tally=tally)

@@ -309,6 +309,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 #include "kdf_long.h"
 // the counting sieve of the two-pass count: tally, gate and fill kernels
 #include "kdf_prefilter.h"
+#include "kdf_sketch.h"
 // per-window counts and per-read depth rows of a read stream
 #include "kdf_depth.h"
 #include "kdf_hits.h"
@@ -581,6 +582,14 @@ struct kdf_engine {
     std::vector<bool> prof_hits_first;                              // the pair opens a call (a call that finds hits records two pairs)
     double prof_hits_ms = 0.0;
     uint64_t prof_hits_passes = 0;
+    // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
+    bool sk_on = false;
+    KdfSketch sk{};                                  // the register cells (device) and p
+    uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
+    unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_sk_ev;   // the sketch kernels under kdf_profile (stats "sketch_us", "sketch_passes")
+    double prof_sk_ms = 0.0;
+    uint64_t prof_sk_passes = 0;
     std::string err;
 };
 
@@ -1606,6 +1615,61 @@ static void pf_free(kdf_engine *h) {
     h->pf_state = PF_OFF;
 }
 
+// ---------------------------------------------------------------------------
+// distinct k-mer sketch (kdf_sketch.h)
+
+static int sk_add_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
+    if (n_bases == 0) return KDF_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        for (uint64_t t0 = 0; t0 < n_tiles; t0 += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
+            const uint64_t m = std::min<uint64_t>(1ull << 30, n_tiles - t0);
+            const unsigned blocks = (unsigned)((m + 255) / 256);
+            // the piece is a stream of its own that starts at tile t0 and ends where the whole stream ends
+            const uint64_t *p = d_packed + 2 * t0, *mk = d_invalid + t0;
+            const uint64_t nb = n_bases - t0 * KDF_TILE;
+            if constexpr (W <= 2) hipLaunchKernelGGL((kdf_sk_stream_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->sk, h->sk_ctr);
+            else hipLaunchKernelGGL((kdf_sk_long_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->sk, h->sk_ctr);
+        }
+        return 0;
+    });
+    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_sk_ev.emplace_back(e0, e1); }
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+static void sk_prof_collect(kdf_engine *h) {
+    for (auto &ev : h->prof_sk_ev) {
+        float ms = 0.f;
+        (void)hipEventSynchronize(ev.second);
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_sk_ms += ms; h->prof_sk_passes++; }
+        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
+    }
+    h->prof_sk_ev.clear();
+}
+
+static void sk_free(kdf_engine *h) {
+    if (h->sk.cells) (void)hipFree(h->sk.cells);
+    if (h->sk_bytes) (void)hipFree(h->sk_bytes);
+    if (h->sk_ctr) (void)hipFree(h->sk_ctr);
+    h->sk = KdfSketch{}; h->sk_bytes = nullptr; h->sk_ctr = nullptr;
+    h->sk_on = false;
+}
+
+// the registers as bytes in `d_out` (device), in stream order
+static int sk_pack(kdf_engine *h, uint8_t *d_out) {
+    const uint32_t m = 1u << h->sk.p;
+    hipLaunchKernelGGL(kdf_sk_pack_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.cells, m, d_out);
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+#define SK_NEED_ON(h, fn) \
+    do { if (!(h)->sk_on) return fail(h, KDF_ERR_STATE, "%s: no sketch is on (kdf_sketch_begin)", fn); } while (0)
+
 #define PF_NEED_TALLYING(h, fn) \
     do { if ((h)->pf_state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
                                                        fn, (h)->pf_state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
@@ -1679,6 +1743,8 @@ void kdf_destroy(kdf_engine *h) {
     depth_prof_collect(h);
     hits_prof_collect(h);
     pf_free(h);
+    sk_prof_collect(h);
+    sk_free(h);
     for (int i = 0; i < 4; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
     for (int i = 0; i < 4; ++i) if (h->hit_buf[i]) (void)hipFree(h->hit_buf[i]);
     for (int i = 0; i < 8; ++i) if (h->kb_buf[i]) (void)hipFree(h->kb_buf[i]);
@@ -2943,6 +3009,128 @@ int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]) {
     return KDF_OK;
 }
 
+// ------------------------------------------------------ distinct k-mer sketch ----
+
+int kdf_sketch_begin(kdf_engine *h, uint32_t log2_registers) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (h->sk_on) return fail(h, KDF_ERR_STATE, "kdf_sketch_begin: a sketch is already on (2^%u registers); kdf_sketch_drop first", h->sk.p);
+    if (log2_registers == 0) log2_registers = KDF_SK_DEFAULT_LOG2;
+    if (log2_registers < KDF_SK_MIN_LOG2 || log2_registers > KDF_SK_MAX_LOG2)
+        return fail(h, KDF_ERR_INVALID, "kdf_sketch_begin: log2_registers %u: must be %d..%d, or 0 for %d", log2_registers, KDF_SK_MIN_LOG2, KDF_SK_MAX_LOG2, KDF_SK_DEFAULT_LOG2);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t m = (size_t)1 << log2_registers;
+    uint32_t *cells = nullptr; uint8_t *bytes = nullptr; unsigned long long *ctr = nullptr;
+    hipError_t e = hipMalloc((void **)&cells, m * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&bytes, m);
+    if (e == hipSuccess) e = hipMalloc((void **)&ctr, KDF_SHARDS * 16 * 8);
+    if (e != hipSuccess) {
+        if (cells) (void)hipFree(cells);
+        if (bytes) (void)hipFree(bytes);
+        (void)hipGetLastError();
+        return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "kdf_sketch_begin: 2^%u registers do not fit the device (%s)", log2_registers, hipGetErrorString(e));
+    }
+    h->sk.cells = cells; h->sk.p = log2_registers; h->sk_bytes = bytes; h->sk_ctr = ctr;
+    h->sk_on = true;
+    HIPCHK(h, hipMemsetAsync(cells, 0, m * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(ctr, 0, KDF_SHARDS * 16 * 8, h->stream));
+    return KDF_OK;
+}
+
+int kdf_sketch_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    SK_NEED_ON(h, "kdf_sketch_add_reads_dev");
+    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_sketch_add_reads_dev: NULL stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    return sk_add_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+}
+
+int kdf_sketch_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    SK_NEED_ON(h, "kdf_sketch_add_reads");
+    if (n_bases == 0) return KDF_OK;
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_sketch_add_reads: NULL stream");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
+    if (rc) return rc;
+    return sk_add_dev(h, dp, dm, n_bases);
+}
+
+int kdf_sketch_add_uploaded(kdf_engine *h, int slot) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    SK_NEED_ON(h, "kdf_sketch_add_uploaded");
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_sketch_add_uploaded: nothing was uploaded into slot %d", slot);
+    const uint64_t n = h->up_n[slot];
+    if (n == 0) return KDF_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
+    HIPCHK(h, hipEventSynchronize(h->up_done[slot]));              // (a sketch-only pass recycles its source buffer on return: kdf_count_uploaded)
+    const int rc = sk_add_dev(h, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
+    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
+    return rc;                                                     // the slot KEEPS its batch: the caller counts or tallies it next
+}
+
+int kdf_sketch_registers_dev(kdf_engine *h, void *d_regs_out) {
+    if (!h || !d_regs_out) return fail(h, KDF_ERR_INVALID, "kdf_sketch_registers_dev: NULL pointer");
+    SK_NEED_ON(h, "kdf_sketch_registers_dev");
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = sk_pack(h, (uint8_t *)d_regs_out); if (rc) return rc; }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_sketch_registers(kdf_engine *h, uint8_t *regs_out) {
+    if (!h || !regs_out) return fail(h, KDF_ERR_INVALID, "kdf_sketch_registers: NULL pointer");
+    SK_NEED_ON(h, "kdf_sketch_registers");
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rc = sk_pack(h, h->sk_bytes); if (rc) return rc; }
+    HIPCHK(h, hipMemcpyAsync(regs_out, h->sk_bytes, (size_t)1 << h->sk.p, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_sketch_merge(kdf_engine *h, const uint8_t *regs) {
+    if (!h || !regs) return fail(h, KDF_ERR_INVALID, "kdf_sketch_merge: NULL pointer");
+    SK_NEED_ON(h, "kdf_sketch_merge");
+    const uint32_t m = 1u << h->sk.p, top = 65 - h->sk.p;
+    for (uint32_t i = 0; i < m; ++i)
+        if (regs[i] > top) return fail(h, KDF_ERR_INVALID, "kdf_sketch_merge: register %u reads %u: a sketch of 2^%u registers holds ranks 0..%u", i, (unsigned)regs[i], h->sk.p, top);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpyAsync(h->sk_bytes, regs, m, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(kdf_sk_merge_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.cells, m, (const uint8_t *)h->sk_bytes);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));                    // (the caller's array is its own again)
+    return KDF_OK;
+}
+
+int kdf_sketch_estimate_registers(const uint8_t *regs, uint32_t log2_registers, double *distinct_out) {
+    if (!regs || !distinct_out) return fail(nullptr, KDF_ERR_INVALID, "kdf_sketch_estimate_registers: NULL pointer");
+    if (log2_registers < KDF_SK_MIN_LOG2 || log2_registers > KDF_SK_MAX_LOG2)
+        return fail(nullptr, KDF_ERR_INVALID, "kdf_sketch_estimate_registers: log2_registers %u: must be %d..%d", log2_registers, KDF_SK_MIN_LOG2, KDF_SK_MAX_LOG2);
+    if (!kdf_sk_estimate_host(regs, log2_registers, distinct_out))
+        return fail(nullptr, KDF_ERR_INVALID, "kdf_sketch_estimate_registers: a register is above %u, the largest rank of 2^%u registers", 65 - log2_registers, log2_registers);
+    return KDF_OK;
+}
+
+int kdf_sketch_estimate(kdf_engine *h, double *distinct_out) {
+    if (!h || !distinct_out) return fail(h, KDF_ERR_INVALID, "kdf_sketch_estimate: NULL pointer");
+    SK_NEED_ON(h, "kdf_sketch_estimate");
+    std::vector<uint8_t> regs((size_t)1 << h->sk.p);
+    { int rc = kdf_sketch_registers(h, regs.data()); if (rc) return rc; }
+    if (!kdf_sk_estimate_host(regs.data(), h->sk.p, distinct_out)) return fail(h, KDF_ERR_STATE, "kdf_sketch_estimate: a register is out of range");
+    return KDF_OK;
+}
+
+int kdf_sketch_drop(kdf_engine *h) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    SK_NEED_ON(h, "kdf_sketch_drop");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    sk_prof_collect(h);
+    sk_free(h);
+    return KDF_OK;
+}
+
 // [first_word, first_word + n_words) inside the sieve (the prefilter is not off)
 #define PF_NEED_RANGE(h, fn) \
     do { const uint64_t total_ = 1ull << ((h)->pf.log2_cells - 4); \
@@ -3125,6 +3313,8 @@ int kdf_profile(kdf_engine *h, int enable) {
     h->prof_depth_ms = 0.0; h->prof_depth_passes = 0;
     hits_prof_collect(h);
     h->prof_hits_ms = 0.0; h->prof_hits_passes = 0;
+    sk_prof_collect(h);
+    h->prof_sk_ms = 0.0; h->prof_sk_passes = 0;
     return KDF_OK;
 }
 
@@ -3230,6 +3420,22 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
             for (int i = 0; i < KDF_SHARDS; ++i) *value += (int64_t)c[i * 16];
         }
     }
+    else if (n == "sketch_state") *value = h->sk_on ? 1 : 0;
+    else if (n == "sketch_log2_registers") *value = h->sk_on ? (int64_t)h->sk.p : 0;
+    else if (n == "sketch_windows") {
+        *value = 0;
+        if (h->sk_on) {                                               // the sharded device counter, summed here
+            HIPCHK(h, hipSetDevice(h->device));
+            std::vector<unsigned long long> c(KDF_SHARDS * 16);
+            HIPCHK(h, hipMemcpyAsync(c.data(), h->sk_ctr, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            unsigned long long t = 0;
+            for (int i = 0; i < KDF_SHARDS; ++i) t += c[(size_t)i * 16];
+            *value = (int64_t)t;
+        }
+    }
+    else if (n == "sketch_us") { sk_prof_collect(h); *value = (int64_t)(h->prof_sk_ms * 1000.0 + 0.5); }
+    else if (n == "sketch_passes") { sk_prof_collect(h); *value = (int64_t)h->prof_sk_passes; }
     else if (n == "prefilter_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pf_ms * 1000.0 + 0.5); }
     else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
     else if (n == "prefilter_merged_words") *value = h->pf_state == PF_OFF ? 0 : (int64_t)h->stat_pf_merged_words;
@@ -3910,18 +4116,36 @@ int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, ui
     return KDF_OK;
 }
 
+// every segment in order into one stream entry point of the engine: mode 0 count, 1 count --if, 2 prefilter tally
+// (kdf_spool_replay), 3 sketch (kdf_spool_sketch)
+static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode);
+
 int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
     if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
     if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: NULL engine");
     if (mode < 0 || mode > 2) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: mode %d (0 count, 1 count --if, 2 prefilter tally)", mode);
-    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: the spool is on device %d, the engine on %d", sp->device, h->device);
-    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_replay: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)");
+    return spool_walk(sp, h, mode);
+}
+
+int kdf_spool_sketch(kdf_spool *sp, kdf_engine *h) {
+    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
+    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_sketch: NULL engine");
+    if (!h->sk_on) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_sketch: no sketch is on (kdf_sketch_begin)");
+    return spool_walk(sp, h, 3);
+}
+
+}  // extern "C"
+
+static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode) {
+    const char *fn = mode == 3 ? "kdf_spool_sketch" : "kdf_spool_replay";
+    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "%s: the spool is on device %d, the engine on %d", fn, sp->device, h->device);
+    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)", fn);
     const size_t ns = sp->segs.size();
     size_t next_host = ns;                                         // the host-tier segment whose upload comes next
     for (size_t i = 0; i < ns; ++i) if (sp->segs[i].host) { next_host = i; break; }
     if (next_host < ns && (h->up_valid[0] || h->up_valid[1]))
-        return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_replay: host-tier segments go through the engine's upload slots, and slot %d holds a batch "
-                       "that was not counted", h->up_valid[0] ? 0 : 1);
+        return ks_fail(sp, KDF_ERR_STATE, "%s: host-tier segments go through the engine's upload slots, and slot %d holds a batch "
+                       "that was not counted", fn, h->up_valid[0] ? 0 : 1);
     KSCHK(sp, hipSetDevice(sp->device));
     if (sp->have_last) {
         KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
@@ -3930,7 +4154,7 @@ int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
     auto pass = [&](size_t i, int rc) {
         if (!rc) return KDF_OK;
         h->up_valid[0] = h->up_valid[1] = false;                   // (both were free on entry: what they hold is the spool's)
-        return ks_fail(sp, rc, "kdf_spool_replay: segment %zu: %s", i, h->err.c_str());
+        return ks_fail(sp, rc, "%s: segment %zu: %s", fn, i, h->err.c_str());
     };
     auto upload = [&](size_t i, int slot) {
         const KsSegment &s = sp->segs[i];
@@ -3943,19 +4167,18 @@ int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
         const uint64_t n = s.tiles * KDF_TILE;
         if (!s.host) {
             rc = mode == 0 ? kdf_count_reads_dev(h, s.packed, s.mask, n) : mode == 1 ? kdf_count_reads_filtered_dev(h, s.packed, s.mask, n)
-                           : kdf_prefilter_add_reads_dev(h, s.packed, s.mask, n);
+                 : mode == 2 ? kdf_prefilter_add_reads_dev(h, s.packed, s.mask, n) : kdf_sketch_add_reads_dev(h, s.packed, s.mask, n);
             if (rc) return pass(i, rc);
             continue;
         }
         size_t j = i + 1;
         while (j < ns && !sp->segs[j].host) ++j;
         if (j < ns && (rc = upload(j, slot ^ 1))) return pass(j, rc);   // its copy runs under this segment's count
-        rc = mode == 2 ? kdf_prefilter_add_uploaded(h, slot) : kdf_count_uploaded(h, slot, mode == 1);
+        if (mode == 3) { rc = kdf_sketch_add_uploaded(h, slot); h->up_valid[slot] = false; }   // (the sketch leaves a batch in its slot: this one is the spool's)
+        else rc = mode == 2 ? kdf_prefilter_add_uploaded(h, slot) : kdf_count_uploaded(h, slot, mode == 1);
         if (rc) return pass(i, rc);
         slot ^= 1;
     }
-    ++sp->replays;
+    if (mode != 3) ++sp->replays;
     return KDF_OK;
 }
-
-}  // extern "C"

@@ -29,6 +29,7 @@ from ..core.jellyfish_wrappers import (
     _format_elapsed,
     _format_file_size,
     _merge_filter_counts,
+    _sketch_bam,
     _stream_bam,
 )
 from ..engine import mirror_engine
@@ -78,6 +79,78 @@ LAST_CHILD_COUNT = None
 LAST_CHILD_SPOOL = None
 
 
+# What the sketch-sized child count (KDF_SIZE_FROM_SKETCH=1) planned: {"log2_registers", "windows" (this rank's), "local_estimate",
+# "global_estimate", "capacity_hint" (of the local engine, per key slice), "key_parts" (agreed by all ranks), "world"}; None
+# when the mode is off.  LAST_CHILD_SKETCH_REGISTERS: the (merged) registers, uint8[2^p].  For logs and tests.
+LAST_CHILD_SKETCH = None
+LAST_CHILD_SKETCH_REGISTERS = None
+
+
+def _sketch_margin(log2_registers):
+    """What a table sized from the sketch's estimate adds to it: five standard errors of HyperLogLog (1.04 / sqrt(m):
+    8.1 % at p = 12, 2.0 % at p = 16) plus 5 % for the classic estimator's bias between 2.5 m and 5 m (kdf.h)."""
+    return 1.05 + 5 * 1.04 / float(1 << int(log2_registers)) ** 0.5
+
+
+def _table_bytes(n_keys, kmer_size):
+    """Bytes of the table kdf_create allocates for a capacity hint: 2^ceil(log2(2 n)) slots (at least 2^10) of 8 W + 4 bytes."""
+    slots = max(1 << 10, 1 << (2 * max(int(n_keys), 1) - 1).bit_length())
+    return slots * (8 * keys.key_words(kmer_size) + 4)
+
+
+def _child_sketch_plan(passes, child_bam, ref_fasta, kmer_size, threads):
+    """The sizing pass of KDF_SIZE_FROM_SKETCH=1: sketch every window of this rank's reads (kdf.h "distinct k-mer sketch") --
+    on the pass that fills the read spool when there is one, as an extra pass over the BAM otherwise -- merge the ranks'
+    sketches, and plan from the estimates: the local engine's capacity hint (the local estimate), the owner engine's (the
+    global estimate x this rank's share of the key space, 1 / world) and the number of key slices, from the bytes of both
+    tables and the HBM that is free now.  ``key_parts`` (``KDF_KEY_PARTS`` when set) is agreed with an all-reduce(MAX):
+    every rank plans from its own free HBM, and ranks that disagreed would hang in mismatched collectives.  Returns
+    (key_parts, local capacity hint, owner capacity hint) per slice."""
+    global LAST_CHILD_SKETCH, LAST_CHILD_SKETCH_REGISTERS
+    from ..distributed import agree_max
+    world, rank, host = dist_env.world_rank()
+    device = _device()
+    dev = None
+    if world > 1:
+        import torch
+        dev = torch.device("cuda", device)
+    p = agree_max(int(os.environ.get("KDF_SKETCH_LOG2M") or 0) or 16, None, host, dev)
+    with mirror_engine(kmer_size, capacity_hint=1, device=device) as sk:      # (its table stays empty: the sketch stores no key)
+        sk.sketch_begin(p)
+        if passes.spool is None:
+            logger.info("Sizing the child count from a sketch without a read spool (KDF_SPOOL=1): an extra pass over the BAM")
+        passes.run(sk, child_bam, ref_fasta, threads, sketch=True)
+        windows = sk.get_stat("sketch_windows")
+        if world > 1:
+            from ..distributed import EngineOps, sketch_merge_ranks
+            local_est, global_est = sketch_merge_ranks(EngineOps(sk, dev), None, host)
+        else:
+            local_est = global_est = sk.sketch_estimate()
+        LAST_CHILD_SKETCH_REGISTERS = sk.sketch_registers()
+        sk.sketch_drop()
+    margin = _sketch_margin(p)
+    local_keys = local_est * margin
+    owner_keys = global_est / world * margin if world > 1 else 0.0
+    env = os.environ.get("KDF_KEY_PARTS")
+    if env:
+        parts = max(1, int(env))
+    else:
+        room = 0.7 * _device_free_bytes(device)                  # (the rest: partition scratch and growth, as in _child_key_parts)
+        parts = 1
+        while parts < (1 << 16) and (_table_bytes(local_keys / parts, kmer_size)
+                                     + (_table_bytes(owner_keys / parts, kmer_size) if world > 1 else 0)) > room:
+            parts += 1
+    parts = agree_max(parts, None, host, dev)
+    local_cap = max(1, int(-(-local_keys // parts)))
+    owner_cap = max(1, int(-(-owner_keys // parts)))
+    LAST_CHILD_SKETCH = {"log2_registers": p, "windows": windows, "local_estimate": local_est, "global_estimate": global_est,
+                         "capacity_hint": local_cap, "key_parts": parts, "world": world}
+    logger.info("Child count sized from a sketch of 2^%d registers: %d windows, about %.0f distinct k-mers in this rank's reads, "
+                "%.0f in all ranks' (%d); capacity hint %d (owner table %d), %d key slice(s)",
+                p, windows, local_est, global_est, world, local_cap, owner_cap, parts)
+    return parts, local_cap, owner_cap
+
+
 class _ChildPasses:
     """The passes of one child count over the child BAM.  Without ``KDF_SPOOL=1`` every pass is ``_stream_bam``, as it
     always was.  With it the first pass also fills a read spool (kdf.h "read spool") and every later pass is a replay of
@@ -103,14 +176,22 @@ class _ChildPasses:
         for name in ("segments", "positions", "hbm_bytes", "host_bytes"):
             self.info[name] = self.spool.stat(name)
 
-    def run(self, eng, child_bam, ref_fasta, threads, tally=False):
+    def run(self, eng, child_bam, ref_fasta, threads, tally=False, sketch=False):
+        """One pass: count, or ``tally`` into the prefilter, or ``sketch`` (nothing is counted: the sizing pass)."""
         if self.spool is None:
             self.bam_passes += 1
+            if sketch:
+                return _sketch_bam(eng, child_bam, ref_fasta, threads)
             return _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=tally)
         if self.filled:
+            if sketch:
+                return self.spool.sketch(eng)
             return self.spool.replay(eng, self.spool.TALLY if tally else self.spool.COUNT)
         self.bam_passes += 1
-        n = _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=tally, spool=self.spool)
+        if sketch:
+            n = _sketch_bam(eng, child_bam, ref_fasta, threads, spool=self.spool)
+        else:
+            n = _stream_bam(eng, child_bam, ref_fasta, threads, filtered=False, tally=tally, spool=self.spool)
         self._note()
         if self.spool.stat("overflowed"):
             logger.info("Read spool overflowed after %d positions (%.1f GB of HBM, %.1f GB of host memory): dropped, the "
@@ -265,7 +346,8 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     """Module 1: count every canonical child k-mer, keep count >= min_child_count.
 
     Returns (child_candidates_fa, n_candidates)."""
-    global LAST_CHILD_COUNT
+    global LAST_CHILD_COUNT, LAST_CHILD_SKETCH, LAST_CHILD_SKETCH_REGISTERS
+    LAST_CHILD_SKETCH = LAST_CHILD_SKETCH_REGISTERS = None
     if jf_hash_size is None:
         jf_hash_size = _estimate_jf_hash_size(child_bam, kmer_size, default="1G")
     logger.info("Extracting child k-mers from BAM (k=%d, jf hash size=%s)…", kmer_size, jf_hash_size)
@@ -288,7 +370,12 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
             lo, hi = devkeys.to_host(*cand)
         else:
             local_hint = max(1, _engine_capacity_hint(jf_hash_size, child_bam) // parts)
-            with mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world) if world > 1 else local_hint, device=_device()) as eng:
+            local_cap, owner_cap = max(1, local_hint // world) if world > 1 else local_hint, max(1, local_hint // world)
+            if os.environ.get("KDF_SIZE_FROM_SKETCH") == "1":
+                # opt-in: tables and key slices sized from a distinct-count sketch of the reads, not from the BAM's size
+                passes = _ChildPasses(_device(), _child_table_bytes(child_bam, world, kmer_size) / parts)
+                parts, local_cap, owner_cap = _child_sketch_plan(passes, child_bam, ref_fasta, kmer_size, threads)
+            with mirror_engine(kmer_size, capacity_hint=local_cap, device=_device()) as eng:
                 if world > 1:
                     # one process per GPU: every rank counts its ranges of the BAM into a local table, one owner-partitioned
                     # exchange moves each (k-mer, count) pair to the rank that owns the k-mer, the owner sums -- and `dump -L`
@@ -296,13 +383,14 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                     import torch
                     from ..distributed import EngineOps, OwnerPartitionedCount
                     dev = torch.device("cuda", eng.device)
-                    owner_eng = mirror_engine(kmer_size, capacity_hint=max(1, local_hint // world), device=eng.device)
+                    owner_eng = mirror_engine(kmer_size, capacity_hint=owner_cap, device=eng.device)
                     merger = OwnerPartitionedCount(EngineOps(eng, dev), device=dev, owner_ops=EngineOps(owner_eng, dev), stage_through_host=host)
                 dev_sets = []
                 if parts > 1:
                     eng.set_option("key_parts", parts)
                 # (slice 0 streams the BAM; with KDF_SPOOL=1 it also spools it and slices 1 .. P-1 replay the spool)
-                passes = _ChildPasses(eng.device, _child_table_bytes(child_bam, world, kmer_size) / parts)
+                if passes is None:
+                    passes = _ChildPasses(eng.device, _child_table_bytes(child_bam, world, kmer_size) / parts)
                 for part in range(parts):
                     if parts > 1:
                         eng.clear(); eng.set_option("key_part", part)

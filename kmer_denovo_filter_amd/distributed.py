@@ -88,6 +88,14 @@ class TableOps:
     def prefilter_drop(self): raise NotImplementedError
     def prefilter_windows(self) -> int: raise NotImplementedError            # windows THIS table tallied
 
+    # distinct k-mer sketch (kdf.h "distinct k-mer sketch").  Registers travel as uint8 tensors on the CPU: 2^p bytes.
+    def sketch_begin(self, log2_registers: int): raise NotImplementedError
+    def sketch_add_stream(self, packed: torch.Tensor, invalid: torch.Tensor, n_bases: int): raise NotImplementedError
+    def sketch_registers(self) -> torch.Tensor: raise NotImplementedError
+    def sketch_merge(self, regs: torch.Tensor): raise NotImplementedError    # reg = max(own, regs)
+    def sketch_estimate(self) -> float: raise NotImplementedError
+    def sketch_drop(self): raise NotImplementedError
+
     def add_pairs_segments(self, segments):
         """Sum the segments [(lo, hi, cnt), ...] received from the source ranks (a table that can merge them
         in one pass overrides this)."""
@@ -225,6 +233,25 @@ class EngineOps(TableOps):
     def prefilter_windows(self):
         return self.e.get_stat("prefilter_windows")
 
+    def sketch_begin(self, log2_registers):
+        self.e.sketch_begin(log2_registers)
+
+    def sketch_add_stream(self, packed, invalid, n_bases):
+        self._sync()
+        self.e.sketch_add_dev(packed.data_ptr(), invalid.data_ptr(), n_bases)
+
+    def sketch_registers(self):
+        return torch.from_numpy(self.e.sketch_registers())
+
+    def sketch_merge(self, regs):
+        self.e.sketch_merge(regs.cpu().numpy())
+
+    def sketch_estimate(self):
+        return self.e.sketch_estimate()
+
+    def sketch_drop(self):
+        self.e.sketch_drop()
+
     def query(self, lo, hi):
         out = torch.zeros(lo.numel(), dtype=torch.int32, device=self.device)
         if lo.numel():
@@ -294,6 +321,29 @@ class ShardedFilterCount:
             self.last_reduce_dtype = torch.int64
             out = torch.clamp(wide, max=_U32_MAX)
         return out.to(keys_lo.device) if self.host else out
+
+
+def agree_max(value: int, group=None, stage_through_host: bool = False, device=None) -> int:
+    """The largest of the ranks' integers (one scalar all-reduce(MAX)); ``value`` itself without a process group."""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return int(value)
+    t = torch.tensor([int(value)], dtype=torch.int64, device=torch.device("cpu") if stage_through_host or device is None else device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return int(t.item())
+
+
+def sketch_merge_ranks(ops: TableOps, group=None, stage_through_host: bool = False) -> Tuple[float, float]:
+    """Merge the ranks' distinct k-mer sketches (kdf.h "distinct k-mer sketch"): ONE all-reduce(MAX) over the uint8
+    registers -- on CPU copies under ``stage_through_host`` -- and every rank takes the result with ``sketch_merge``, so
+    every rank holds the registers of the whole sample.  Returns (local estimate, taken before the merge; global
+    estimate)."""
+    local = float(ops.sketch_estimate())
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return local, local
+    regs = ops.sketch_registers().to(torch.device("cpu") if stage_through_host else ops.device).contiguous()
+    dist.all_reduce(regs, op=dist.ReduceOp.MAX, group=group)
+    ops.sketch_merge(regs.cpu())
+    return local, float(ops.sketch_estimate())
 
 
 def _round8(n: int) -> int:
@@ -511,6 +561,29 @@ class OwnerPartitionedCount:
         if self.world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
         return int(t.item())
+
+    # ---- distinct k-mer sketch over the ranks (kdf.h "distinct k-mer sketch") ------------------------------------------
+    # sketch_begin -> sketch_local over every batch of the shard -> sketch_merge: a register is a max over windows, so the
+    # element-wise max of the ranks' registers is the sketch of the whole sample, and every rank ends up holding it --
+    # whatever the ranks size from it, they size alike.
+
+    def sketch_begin(self, log2_registers: int = 0) -> int:
+        """Start a sketch on the LOCAL table's engine with the register count the ranks agree on (the largest
+        proposal; 0: the engine's default, 16); returns that log2_registers."""
+        p = agree_max(int(log2_registers) or 16, self.group, self.host, self.device)
+        self.local.sketch_begin(p)
+        return p
+
+    def sketch_local(self, packed, invalid, n_bases: int):
+        """Sketch one more batch of this rank's read shard (no communication)."""
+        if isinstance(packed, int):
+            raise TypeError("pass the stream tensors, not raw pointers")
+        self.local.sketch_add_stream(packed, invalid, n_bases)
+
+    def sketch_merge(self) -> Tuple[float, float]:
+        """ONE all-reduce(MAX) over the uint8 registers; every rank then holds the sample's registers.  Returns
+        (local estimate, taken before the merge; global estimate)."""
+        return sketch_merge_ranks(self.local, self.group, self.host)
 
     def merge(self, min_count: int = 1) -> int:
         """Exchange the local (key, count) pairs to their owners; returns the global

@@ -10,6 +10,7 @@ shells out to ("External op" table):
     histogram(high)          jellyfish histo -h high
     count_stats()            jellyfish stats
     prefilter_*()            jellyfish bc + count --bc          (exact: two passes)
+    sketch_*()               (no Jellyfish call) distinct k-mers of a stream, estimated without storing them
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
     read_hits(stream)        ... and its per-read hits / distinct on the device
@@ -326,6 +327,58 @@ class KmerEngine:
         self._ck(self._lib.kdf_prefilter_merge_dev(self._h, int(first), int(n), len(segs), ptrs, 1 if replace else 0))
         return self
 
+    # -- distinct k-mer sketch (kdf.h "distinct k-mer sketch") ----------------
+    def sketch_begin(self, log2_registers: int = 0):
+        """Start a HyperLogLog sketch of 2^log2_registers registers (10..18; 0: 16) over the canonical k-mers of the
+        streams given to sketch_add*.  Independent of the table, the mode and a prefilter; survives clear()."""
+        self._ck(self._lib.kdf_sketch_begin(self._h, int(log2_registers)))
+        return self
+
+    def sketch_add(self, stream: ReadStream):
+        self._ck(self._lib.kdf_sketch_add_reads(self._h, _vp(stream.packed), _vp(stream.invalid), stream.n_bases))
+        return self
+
+    def sketch_add_dev(self, d_packed: int, d_invalid: int, n_bases: int):
+        """Stream resident in HBM (raw device pointers, as count_dev); stream order, does not synchronise."""
+        self._ck(self._lib.kdf_sketch_add_reads_dev(self._h, c_void_p(d_packed), c_void_p(d_invalid), int(n_bases)))
+        return self
+
+    def sketch_add_uploaded(self, slot: int):
+        """Sketch the batch upload_async() put into staging slot 0 / 1; the slot keeps it (count or tally it next)."""
+        self._ck(self._lib.kdf_sketch_add_uploaded(self._h, int(slot)))
+        return self
+
+    def sketch_registers(self) -> np.ndarray:
+        """The registers, uint8[2^log2_registers]."""
+        out = np.zeros(1 << self.get_stat("sketch_log2_registers"), np.uint8)
+        self._ck(self._lib.kdf_sketch_registers(self._h, _vp(out)))
+        return out
+
+    def sketch_registers_dev(self, d_out: int):
+        """The same into caller-owned HBM (raw device pointer to 2^log2_registers bytes); complete on return."""
+        self._ck(self._lib.kdf_sketch_registers_dev(self._h, c_void_p(d_out) if d_out else None))
+        return self
+
+    def sketch_merge(self, regs):
+        """reg = max(own, regs): another engine's registers of the same size (another rank's, another shard's)."""
+        regs = np.ascontiguousarray(regs, dtype=np.uint8)
+        m = 1 << self.get_stat("sketch_log2_registers")
+        if self.get_stat("sketch_state") and (regs.ndim != 1 or len(regs) != m):      # (no sketch: the engine says so)
+            raise ValueError(f"sketch_merge: {regs.shape} registers for a sketch of {m}")
+        self._ck(self._lib.kdf_sketch_merge(self._h, _vp(regs)))
+        return self
+
+    def sketch_estimate(self) -> float:
+        """Estimated number of distinct canonical k-mers among the windows sketched (and merged) so far."""
+        import ctypes
+        v = ctypes.c_double(0.0)
+        self._ck(self._lib.kdf_sketch_estimate(self._h, byref(v)))
+        return v.value
+
+    def sketch_drop(self):
+        self._ck(self._lib.kdf_sketch_drop(self._h))
+        return self
+
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
         if self.long:
@@ -589,6 +642,19 @@ class KmerEngine:
 READ_DEPTH_COLUMNS = ("windows", "present", "low", "min", "max", "sum")
 # columns of KmerEngine.read_hits' rows
 READ_HITS_COLUMNS = ("hits", "distinct")
+
+
+def estimate_from_registers(regs) -> float:
+    """The sketch's estimate from exported registers (uint8[2^p], p = 10..18) -- a pure host function of libkdf: no
+    engine, no GPU."""
+    import ctypes
+    regs = np.ascontiguousarray(regs, dtype=np.uint8)
+    m = len(regs)
+    if regs.ndim != 1 or m < 2 or m & (m - 1):
+        raise ValueError(f"estimate_from_registers: {regs.shape} is not 2^p registers")
+    v = ctypes.c_double(0.0)
+    _native.check(_native.load().kdf_sketch_estimate_registers(_vp(regs), m.bit_length() - 1, byref(v)), None)
+    return v.value
 
 
 def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:

@@ -301,6 +301,20 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
     streams the file again for the later passes); the pass itself goes on.  A spool whose ``keep_reads`` attribute is set
     also gets every batch's read offsets (``ReadSpool.read_hits`` / ``read_depth`` / ``select_reads`` over it afterwards).
     Returns the number of reads."""
+    return _stream_batches(engine, readers, filtered, ring, tally, spool, False)
+
+
+def sketch_batches_overlapped(engine, readers, ring: int = 0, spool=None) -> int:
+    """The same pipeline as a SIZING pass: every batch goes to the engine's distinct k-mer sketch
+    (``sketch_add_uploaded``) and is neither counted nor tallied; a ``spool`` is filled as in
+    ``stream_batches_overlapped``.  The sketch leaves a batch in its upload slot (``kdf_sketch_add_uploaded``), so the
+    engine's two slots still hold the last two batches afterwards: the next ``upload_async`` overwrites them, and a replay
+    of host-tier spool segments into THIS engine is refused until they are taken -- the sizing pass of the discovery chain
+    uses an engine of its own and closes it.  Returns the number of reads."""
+    return _stream_batches(engine, readers, False, ring, False, spool, True)
+
+
+def _stream_batches(engine, readers, filtered, ring, tally, spool, sketch) -> int:
     import queue
     import threading
     if not isinstance(readers, (list, tuple)):
@@ -332,7 +346,7 @@ def stream_batches_overlapped(engine, readers, filtered: bool, ring: int = 0, ta
     threads = [threading.Thread(target=produce, args=(rd,), name="kdf-reader", daemon=True) for rd in readers]
     for th in threads:
         th.start()
-    take_slot = engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
+    take_slot = engine.sketch_add_uploaded if sketch else engine.prefilter_add_uploaded if tally else (lambda slot: engine.count_uploaded(slot, filtered))
     spooling = [spool]
     keep_reads = bool(getattr(spool, "keep_reads", False))
 

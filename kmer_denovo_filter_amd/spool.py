@@ -165,6 +165,12 @@ class ReadSpool:
         self._ck(self._lib.kdf_spool_replay(self._h, engine._h, int(mode)))
         return self
 
+    def sketch(self, engine):
+        """Every segment, in order, into the distinct k-mer sketch of ``engine`` (engine.sketch_begin first); the spool
+        and the engine's table, mode and upload slots are not changed."""
+        self._ck(self._lib.kdf_spool_sketch(self._h, engine._h))
+        return self
+
     def read_segment(self, seg: int):
         """(packed, invalid, n_positions) of one segment as host arrays of the stream_words(n_positions) sizes."""
         n = c_uint64(0)
