@@ -13,6 +13,7 @@
 
 #include "kdf.h"
 #include "kdf_device.h"
+#include "kdf_hostutil.h"
 #include "kdf_binned.h"
 #include "kdf_merge.h"
 #include "kdf_histo.h"
@@ -455,6 +456,11 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
+// every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COUNT = BUF_UP + 4 };
+// the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo"};
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -473,14 +479,12 @@ struct kdf_engine {
     bool filter_mode = false;
     bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
     bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
-    // grow-only device staging for the host-buffer entry points
-    void *stage[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[4] = {0, 0, 0, 0};
+    DevBuf buf[BUF_COUNT];                           // released together (kdf_destroy); used through the views below
+    DevBuf *const stage = buf + BUF_STAGE;           // [4] staging for the host-buffer entry points
     // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
     unsigned long long *kb_small = nullptr;   // totals[16]
     unsigned long long *kb_totals_host = nullptr;   // pinned [16]
-    void *kb_buf[8] = {nullptr};                     // ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
-    size_t kb_bytes[8] = {0};
+    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
     KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
     // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
     // table is needed or the ring is full (kb_flush).  Reserved by upper bounds (one entry per stream position), so no
@@ -529,12 +533,12 @@ struct kdf_engine {
     uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
     // double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
     // stream of their own, so the H2D copy of batch i + 1 runs under the count of batch i
-    void *up_buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}; size_t up_bytes[2][2] = {{0, 0}, {0, 0}};
+    DevBuf (*const up_buf)[2] = (DevBuf (*)[2])(buf + BUF_UP);      // [slot][packed, mask]
     uint64_t up_n[2] = {0, 0}; bool up_valid[2] = {false, false};
     hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr}, use_done[2] = {nullptr, nullptr};
     uint64_t stat_heavy_buckets = 0;
     void *kb_heavy = nullptr;                        // heavy buckets of skewed flushes (kdf_binned.h kb_heavy_slice_kernel)
-    void *merge_buf = nullptr; size_t merge_bytes = 0;   // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge
+    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly)
     uint32_t merge_flag_host = 0;
     int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
     int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
@@ -547,49 +551,29 @@ struct kdf_engine {
     bool sieve_valid = false;
     uint32_t opt_debug_flags = 0;                    // experiments only (KbPlan::dbg)
     uint64_t stat_binned_passes = 0, stat_replayed_buckets = 0;
-    // optional HIP-event timing of the dominant (stream) kernel
+    // optional HIP-event timing (kdf_profile).  T_STREAM, the dominant kernels: a span's tag is its tiles, so passes are the
+    // launches and tag_sum x 64 the positions (a flush is timed with tag 0: its positions were counted with the passes it
+    // applies).  T_HITS: tag 1 for the span that opens a call, 0 for the second span of a call that finds hits.
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;   // pending start/stop pairs
-    std::vector<uint64_t> prof_tiles;
-    double prof_ms = 0.0;
-    uint64_t prof_launches = 0, prof_positions = 0;
+    EvTimer timer[T_COUNT];
     // binned path: events around each stage (A0 hist, A1 scatter, B finesort | C bucket)
     std::vector<std::vector<hipEvent_t>> prof_stage_ev;   // 4 events: a partition (A0, A1, B); 2 events: a flush (C)
     double prof_stage_ms[4] = {0, 0, 0, 0};
     uint64_t prof_stage_passes = 0;
-    double prof_histo_ms = 0.0;                      // kdf_histo_kernel under kdf_profile (stats "histo_us", "histo_passes")
-    uint64_t prof_histo_passes = 0;
     // ---- two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off ------------------------
     int pf_state = PF_OFF;
     KdfPrefilter pf{};                               // the sieve (device), its size and the gate's threshold
     unsigned long long *pf_ctr = nullptr;            // device: sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
     uint64_t *pf_admit = nullptr; uint64_t pf_admit_words = 0;   // the gate's output for the stream being counted (grow-only)
     uint64_t capacity_hint = 0;                      // kdf_create's: sizes the sieve when the caller leaves that to the engine
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pf_ev;   // tally kernels under kdf_profile (stats "prefilter_us", "prefilter_passes")
-    double prof_pf_ms = 0.0;
-    uint64_t prof_pf_passes = 0;
     uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pfm_ev;  // kdf_pf_merge_kernel under kdf_profile (stats "prefilter_merge_us", "prefilter_merge_passes")
-    double prof_pfm_ms = 0.0;
-    uint64_t prof_pfm_passes = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_depth_ev;   // kdf_depth_kernel under kdf_profile (stats "depth_us", "depth_passes")
-    double prof_depth_ms = 0.0;
-    uint64_t prof_depth_passes = 0;
     // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
-    void *hit_buf[4] = {nullptr, nullptr, nullptr, nullptr};    // 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
-    size_t hit_bytes[4] = {0, 0, 0, 0};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_hits_ev;    // the kh_* kernels under kdf_profile (stats "hits_us", "hits_passes")
-    std::vector<bool> prof_hits_first;                              // the pair opens a call (a call that finds hits records two pairs)
-    double prof_hits_ms = 0.0;
-    uint64_t prof_hits_passes = 0;
+    DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
     // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
     bool sk_on = false;
     KdfSketch sk{};                                  // the register cells (device) and p
     uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
     unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_sk_ev;   // the sketch kernels under kdf_profile (stats "sketch_us", "sketch_passes")
-    double prof_sk_ms = 0.0;
-    uint64_t prof_sk_passes = 0;
     std::string err;
 };
 
@@ -665,13 +649,16 @@ static int materialize(kdf_engine *h) {
     return KDF_OK;
 }
 
-static int stage_reserve(kdf_engine *h, int i, size_t bytes) {
-    if (h->stage_bytes[i] >= bytes) return KDF_OK;
-    if (h->stage[i]) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->stage[i]); h->stage[i] = nullptr; h->stage_bytes[i] = 0; }
-    size_t want = bytes + bytes / 8 + 4096;
-    HIPCHK(h, hipMalloc(&h->stage[i], want));
-    h->stage_bytes[i] = want;
-    return KDF_OK;
+// Room for `bytes` in one of the engine's buffers whose readers all run on the engine's stream (staging, binned scratch,
+// merge scratch, hit reduction): slack(bytes) are allocated (the site's rule), the stream is drained before a free.
+// what: the buffer's name in the message of a failed allocation (NULL: the plain HIP error text).
+static int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t) = slack_8th, const char *what = nullptr) {
+    const size_t want = slack(bytes);
+    const hipError_t e = dev_reserve(b, bytes, want, [&] { (void)hipStreamSynchronize(h->stream); return hipSuccess; });
+    if (e == hipSuccess) return KDF_OK;
+    const int code = e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP;
+    if (!what) return fail(h, code, "hipMalloc of %zu bytes of device scratch failed: %s", want, hipGetErrorString(e));
+    return fail(h, code, "the %s of the hit reduction (%.2f GB) does not fit the device (%s)", what, (double)want / 1e9, hipGetErrorString(e));
 }
 
 // read distinct / windows / error from the control block (synchronises)
@@ -786,11 +773,7 @@ template <int MODE>
 static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid,
                           uint64_t tile0, uint64_t n_tiles, uint64_t *d_hits, uint64_t n_bases) {
     const unsigned blocks = (unsigned)((n_tiles + 255) / 256);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, h->stream);
-    }
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
     by_words(h, [&](auto Wc) {
         constexpr int W = decltype(Wc)::value;
         if constexpr (W <= 2)
@@ -801,25 +784,11 @@ static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_
                                d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
         return 0;
     });
-    if (h->prof) {
-        (void)hipEventRecord(e1, h->stream);
-        h->prof_ev.emplace_back(e0, e1);
-        h->prof_tiles.push_back(n_tiles);
-    }
+    span.stop();
 }
 
-// fold finished event pairs into the running totals (synchronises on them)
-static void prof_collect(kdf_engine *h) {
-    for (size_t i = 0; i < h->prof_ev.size(); ++i) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(h->prof_ev[i].second);
-        if (hipEventElapsedTime(&ms, h->prof_ev[i].first, h->prof_ev[i].second) == hipSuccess) {
-            h->prof_ms += ms; h->prof_positions += h->prof_tiles[i] * KDF_TILE;
-            if (h->prof_tiles[i]) h->prof_launches++;                // (a flush has no positions of its own: its time belongs to the passes it applies)
-        }
-        (void)hipEventDestroy(h->prof_ev[i].first); (void)hipEventDestroy(h->prof_ev[i].second);
-    }
-    h->prof_ev.clear(); h->prof_tiles.clear();
+// fold the finished stage records of the binned path into the running totals (synchronises on them)
+static void stage_collect(kdf_engine *h) {
     for (auto &ev : h->prof_stage_ev) {
         if (ev.size() == 4) {                                     // a partition pass: A0, A1, B
             (void)hipEventSynchronize(ev[3]);
@@ -838,15 +807,6 @@ static void prof_collect(kdf_engine *h) {
 
 // ---------------------------------------------------------------------------
 // binned path (kdf_binned.h): partition passes into the entry ring, deferred kernel C
-
-static int kb_reserve(kdf_engine *h, int i, size_t bytes, bool exact = false) {
-    if (h->kb_bytes[i] >= bytes) return KDF_OK;
-    if (h->kb_buf[i]) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->kb_buf[i]); h->kb_buf[i] = nullptr; h->kb_bytes[i] = 0; }
-    const size_t want = exact ? bytes + 4096 : bytes + bytes / 16 + 4096;
-    HIPCHK(h, hipMalloc(&h->kb_buf[i], want));
-    h->kb_bytes[i] = want;
-    return KDF_OK;
-}
 
 // the partition geometry for a table: coarse / fine bits; sub_bits = what the bucket kernel resolves itself
 static KbPlan kb_make_plan(const kdf_engine *h, const KdfTable &t) {
@@ -934,11 +894,11 @@ static int kb_scratch(kdf_engine *h, KbScratch &s) {
         s.hv_cnt = (uint32_t *)(s.hv_key + hv_pairs * h->kw);
         s.hv_ctr = s.hv_cnt + hv_pairs; s.hv_bucket = s.hv_ctr + 4; s.hv_n = s.hv_bucket + KB_HV_MAX; s.hv_failed = s.hv_n + KB_HV_MAX;
     }
-    s.ent = (uint64_t *)h->kb_buf[0]; s.tmp = (uint64_t *)h->kb_buf[1];
-    s.chunk_off = (uint32_t *)h->kb_buf[2]; s.failed = (uint32_t *)h->kb_buf[3];
-    s.off = (uint16_t *)h->kb_buf[4];
+    s.ent = (uint64_t *)h->kb_buf[0].p; s.tmp = (uint64_t *)h->kb_buf[1].p;
+    s.chunk_off = (uint32_t *)h->kb_buf[2].p; s.failed = (uint32_t *)h->kb_buf[3].p;
+    s.off = (uint16_t *)h->kb_buf[4].p;
     // row tables of the ring: row_ent u64 | row_len u32, ring_rows of each
-    s.row_ent = (unsigned long long *)h->kb_buf[6];
+    s.row_ent = (unsigned long long *)h->kb_buf[6].p;
     s.row_len = (uint32_t *)(s.row_ent + h->ring_rows);
     return KDF_OK;
 }
@@ -958,7 +918,7 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok = false);
 // it is empty.
 static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, uint32_t off_stride) {
     int rc;
-    const uint64_t rows_cap = std::min<uint64_t>(h->ring_rows, h->kb_bytes[2] / ((uint64_t)off_stride * 4));
+    const uint64_t rows_cap = std::min<uint64_t>(h->ring_rows, h->kb_buf[2].bytes / ((uint64_t)off_stride * 4));
     bool forced = false;
     if (h->n_pass >= KB_MAX_PASS || h->ring_used + need_e > h->ring_entries || h->rows_used + need_r > rows_cap) {
         forced = h->n_pass > 0;
@@ -975,12 +935,12 @@ static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, ui
     const uint64_t want_r = std::max<uint64_t>(need_r, (uint64_t)((double)need_r * ((double)want_e / (double)need_e))) + 4096;
     if (want_e > h->ring_entries || need_r > rows_cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = kb_reserve(h, 0, want_e * esz, true))) return rc;
-        if ((rc = kb_reserve(h, 2, want_r * (uint64_t)off_stride * 4, true))) return rc;
-        if ((rc = kb_reserve(h, 6, want_r * 12, true))) return rc;
+        if ((rc = eng_reserve(h, h->kb_buf[0], want_e * esz, slack_page))) return rc;
+        if ((rc = eng_reserve(h, h->kb_buf[2], want_r * (uint64_t)off_stride * 4, slack_page))) return rc;
+        if ((rc = eng_reserve(h, h->kb_buf[6], want_r * 12, slack_page))) return rc;
         h->ring_entries = std::max(h->ring_entries, want_e); h->ring_rows = std::max(h->ring_rows, want_r);
-        // (kb_reserve only ever grows a buffer: the row tables are laid out for ring_rows rows)
-        if (h->kb_bytes[6] < h->ring_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
+        // (a buffer only ever grows: the row tables are laid out for ring_rows rows)
+        if (h->kb_buf[6].bytes < h->ring_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
     }
     return KDF_OK;
 }
@@ -1017,22 +977,21 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
         h->attrs_set[KW] = true;
     }
     // the pass's own buffers: slab-sorted entries, offset rows, planning arrays (reused by the next pass: stream order)
-    if ((rc = kb_reserve(h, 1, n_slabs * (uint64_t)SLAB * 8 * KW))) return rc;
-    if ((rc = kb_reserve(h, 4, n_slabs * (uint64_t)(nbins + 1) * 2 + 64))) return rc;
+    if ((rc = eng_reserve(h, h->kb_buf[1], n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb_buf[4], n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
     const uint64_t n_pairs = n_groups * nbins;
     const uint64_t ovf_cap = n_entries_max / CHUNK + 1;       // pieces beyond the first of their pair: sum (np - 1) <= entries / CHUNK
-    if ((rc = kb_reserve(h, 5, n_pairs * 16 + (size_t)nb1 * 12 + (2 * ovf_cap + 2) * 4 + 64))) return rc;
+    if ((rc = eng_reserve(h, h->kb_buf[5], n_pairs * 16 + (size_t)nb1 * 12 + (2 * ovf_cap + 2) * 4 + 64, slack_16th))) return rc;
     KbScratch s;
     if ((rc = kb_scratch(h, s))) return rc;
-    s.gpre_ent = (unsigned long long *)h->kb_buf[5];
+    s.gpre_ent = (unsigned long long *)h->kb_buf[5].p;
     s.bin_ent = s.gpre_ent + n_pairs;
     s.gn = (uint32_t *)(s.bin_ent + nb1); s.gpre_row = s.gn + n_pairs; s.bin_rows = s.gpre_row + n_pairs; s.ovf = s.bin_rows + nb1;
     s.ovf_cap = (uint32_t)ovf_cap;
 
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     std::vector<hipEvent_t> sev;
     auto stamp = [&]() { if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); } };
-    if (h->prof) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, h->stream); }
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
     stamp();                                                   // start of A
 
     const uint32_t pass_idx = h->n_pass;
@@ -1059,12 +1018,8 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     hipLaunchKernelGGL(kb_piecesort_more_kernel<KW>, dim3((unsigned)std::min<uint64_t>(ovf_cap, (uint64_t)h->n_cu)), dim3(KB_THREADS), lds_b, h->stream, plan, s, pass_idx);
     stamp();                                                   // end of B
     HIPCHK(h, hipGetLastError());
-    if (h->prof) {
-        (void)hipEventRecord(e1, h->stream);
-        h->prof_ev.emplace_back(e0, e1);
-        h->prof_tiles.push_back(n_tiles);
-        h->prof_stage_ev.push_back(sev);
-    }
+    span.stop();
+    if (h->prof) h->prof_stage_ev.push_back(sev);
     h->n_pass++;
     h->ring_used += n_entries_max; h->rows_used += n_rows_max;
     h->pend_positions += n_entries_max;
@@ -1150,16 +1105,13 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
     plan.sub_bits = (h->t.log2cap - h->t.bucket_bits) - plan.c1 - plan.c2;       // a table that grew since the partition: more sub-buckets
     const uint64_t nb_table = 1ull << (plan.c1 + plan.c2 + plan.sub_bits);
     const size_t failed_bytes = (size_t)((nb_table + 31) / 32) * 4;
-    if ((rc = kb_reserve(h, 3, failed_bytes))) return rc;
-    s.failed = (uint32_t *)h->kb_buf[3];
+    if ((rc = eng_reserve(h, h->kb_buf[3], failed_bytes, slack_16th))) return rc;
+    s.failed = (uint32_t *)h->kb_buf[3].p;
     HIPCHK(h, hipMemsetAsync(s.failed, 0, failed_bytes, h->stream));
     const int nonempty = h->lazy_empty ? 0 : 1;   // 0: kernel C rewrites every bucket (this IS the clear)
     std::vector<hipEvent_t> sev;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) {
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, h->stream);
-        hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e);
-    }
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, 0);      // (tag 0: its positions were counted with the partition passes)
+    if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); }
     if (plan.dbg & 2048) return kb_ring_reset(h);                 // (ablation: the partition passes are timed alone, what they wrote is dropped)
     const bool heavy = skewed && s.hv_ctr && plan.sub_bits == 0;
     if (heavy) {
@@ -1200,13 +1152,8 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
         });
     }
     HIPCHK(h, hipGetLastError());
-    if (h->prof) {
-        hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e);
-        (void)hipEventRecord(e1, h->stream);
-        h->prof_ev.emplace_back(e0, e1);
-        h->prof_tiles.push_back(0);                            // (its positions were counted with the partition passes)
-        h->prof_stage_ev.push_back(sev);
-    }
+    if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); h->prof_stage_ev.push_back(sev); }
+    span.stop();
     HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
     bool full = false;
     uint64_t cursor = 0;
@@ -1438,10 +1385,9 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
     if (n_tiles == 0) return KDF_OK;
     { int rc0 = materialize(h); if (rc0) return rc0; }
     if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (h->prof) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, h->stream); }
+        EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
         launch_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
-        if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_ev.emplace_back(e0, e1); h->prof_tiles.push_back(n_tiles); }
+        span.stop();
         HIPCHK(h, hipGetLastError());
         h->last_path = 3;
         return KDF_OK;
@@ -1483,20 +1429,76 @@ static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *
     uint64_t pw, mw;
     kdf_stream_words(n_bases, &pw, &mw);
     int rc;
-    if ((rc = stage_reserve(h, 0, pw * 8))) return rc;
-    if ((rc = stage_reserve(h, 1, mw * 8))) return rc;
-    *d_packed = (uint64_t *)h->stage[0];
-    *d_invalid = (uint64_t *)h->stage[1];
+    if ((rc = eng_reserve(h, h->stage[0], pw * 8))) return rc;
+    if ((rc = eng_reserve(h, h->stage[1], mw * 8))) return rc;
+    *d_packed = (uint64_t *)h->stage[0].p;
+    *d_invalid = (uint64_t *)h->stage[1].p;
     return upload_padded(h, packed, invalid, n_bases, *d_packed, *d_invalid, h->stream);
 }
 
-// stage_reserve + a copy of `bytes` host bytes into staging slot i (stream order)
+// room for, and a copy of, `bytes` host bytes in staging slot i (stream order)
 static int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn) {
-    int rc = stage_reserve(h, i, bytes);
+    int rc = eng_reserve(h, h->stage[i], bytes);
     if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(h->stage[i], src, bytes, hipMemcpyHostToDevice, h->stream);
+    const hipError_t e = hipMemcpyAsync(h->stage[i].p, src, bytes, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "%s: copy of %zu bytes to the device failed: %s", fn, bytes, hipGetErrorString(e));
     return KDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Where a consumer's read stream comes from (count, count --if, prefilter tally, sketch, a spool's append): device
+// pointers, host arrays or an upload slot.  Each maker holds its form's refusals, worded with the caller's name; an
+// entry point is "refuse by state, make a source, run the _dev core, release".
+
+struct StreamSrc { const uint64_t *packed = nullptr, *invalid = nullptr; uint64_t n_bases = 0; int slot = -1; };
+
+// where the message of a refusal goes: this engine's error string (a spool has its own sink)
+struct EngSink {
+    kdf_engine *h;
+    template <typename... A> int operator()(int code, const char *fmt, A... a) const { return fail(h, code, fmt, a...); }
+};
+struct NoRefusal { int operator()(const StreamSrc &) const { return KDF_OK; } };
+
+static int src_dev(kdf_engine *h, const char *fn, const void *d_packed, const void *d_invalid, uint64_t n_bases, StreamSrc &src) {
+    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "%s: NULL stream", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    src = StreamSrc{(const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, -1};
+    return KDF_OK;
+}
+
+// host arrays, staged on the engine's stream (upload_stream); n_bases == 0: an empty source, nothing is asked or touched
+static int src_host(kdf_engine *h, const char *fn, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, StreamSrc &src) {
+    src = StreamSrc{};
+    if (n_bases == 0) return KDF_OK;
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "%s: NULL stream", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    const int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
+    if (!rc) src = StreamSrc{dp, dm, n_bases, -1};
+    return rc;
+}
+
+// The batch of upload slot `slot` (kdf_upload_reads_async), or KDF_ERR_STATE.  also_refuse(src) holds the refusals the
+// caller tests AFTER the slot's: a refused call changes nothing, the slot keeps its batch.  consume: the slot is empty
+// afterwards (count, tally), else it keeps the batch for the next consumer (sketch, spool).  The engine's stream waits for
+// the copy; host_wait: so does the host -- the caller of a count, tally or sketch recycles its (pinned) source buffer as
+// soon as the call returns, and the copy was issued a whole batch ago.  An empty batch (n_bases 0) needs no wait.
+template <typename S, typename R>
+static int src_slot(S &&sink, const char *fn, kdf_engine *h, int slot, bool consume, bool host_wait, StreamSrc &src, R &&also_refuse) {
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return sink(KDF_ERR_STATE, "%s: nothing was uploaded into slot %d", fn, slot);
+    src = StreamSrc{(const uint64_t *)h->up_buf[slot][0].p, (const uint64_t *)h->up_buf[slot][1].p, h->up_n[slot], slot};
+    if (const int rc = also_refuse(src)) return rc;
+    if (consume) h->up_valid[slot] = false;
+    if (src.n_bases == 0) return KDF_OK;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->up_done[slot], 0);
+    if (e == hipSuccess && host_wait) e = hipEventSynchronize(h->up_done[slot]);
+    if (e != hipSuccess) return sink(e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "%s: waiting for the copy into slot %d failed: %s", fn, slot, hipGetErrorString(e));
+    return KDF_OK;
+}
+// behind the consumer's last launch: the slot's next upload waits for this reader
+static void src_release(kdf_engine *h, const StreamSrc &src) {
+    if (src.slot >= 0) (void)hipEventRecord(h->use_done[src.slot], h->stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1542,29 +1544,11 @@ static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_in
 
 static int pf_tally_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (n_bases == 0) return KDF_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    EvSpan span(h->timer[T_PF], h->prof, h->stream);
     pf_launch(h, d_packed, d_invalid, n_bases, nullptr);
-    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_pf_ev.emplace_back(e0, e1); }
+    span.stop();
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
-}
-
-static void pf_prof_collect(kdf_engine *h) {
-    for (auto &ev : h->prof_pf_ev) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(ev.second);
-        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_pf_ms += ms; h->prof_pf_passes++; }
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    h->prof_pf_ev.clear();
-    for (auto &ev : h->prof_pfm_ev) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(ev.second);
-        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_pfm_ms += ms; h->prof_pfm_passes++; }
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    h->prof_pfm_ev.clear();
 }
 
 // merge `nseg` device segments of n_words words into sieve words [first_word, first_word + n_words): one launch
@@ -1576,35 +1560,13 @@ static int pf_merge_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, ui
     const uint32_t head = (uint32_t)(first_word & 1);             // the word before the first pair of 16 aligned bytes
     const uint64_t n_pairs = (n_words - head) / 2;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_pairs + 255) / 256, (uint64_t)h->n_cu * 8));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    EvSpan span(h->timer[T_PFM], h->prof, h->stream);
     if (replace) hipLaunchKernelGGL(kdf_pf_merge_kernel<true>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
     else hipLaunchKernelGGL(kdf_pf_merge_kernel<false>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
-    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_pfm_ev.emplace_back(e0, e1); }
+    span.stop();
     HIPCHK(h, hipGetLastError());
     h->stat_pf_merged_words += n_words;
     return KDF_OK;
-}
-
-static void depth_prof_collect(kdf_engine *h) {
-    for (auto &ev : h->prof_depth_ev) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(ev.second);
-        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_depth_ms += ms; h->prof_depth_passes++; }
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    h->prof_depth_ev.clear();
-}
-
-static void hits_prof_collect(kdf_engine *h) {
-    for (size_t i = 0; i < h->prof_hits_ev.size(); ++i) {
-        auto &ev = h->prof_hits_ev[i];
-        float ms = 0.f;
-        (void)hipEventSynchronize(ev.second);
-        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_hits_ms += ms; if (h->prof_hits_first[i]) h->prof_hits_passes++; }
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    h->prof_hits_ev.clear(); h->prof_hits_first.clear();
 }
 
 static void pf_free(kdf_engine *h) {
@@ -1620,8 +1582,7 @@ static void pf_free(kdf_engine *h) {
 
 static int sk_add_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (n_bases == 0) return KDF_OK;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    EvSpan span(h->timer[T_SK], h->prof, h->stream);
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     by_words(h, [&](auto Wc) {
         constexpr int W = decltype(Wc)::value;
@@ -1636,19 +1597,9 @@ static int sk_add_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
         }
         return 0;
     });
-    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_sk_ev.emplace_back(e0, e1); }
+    span.stop();
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
-}
-
-static void sk_prof_collect(kdf_engine *h) {
-    for (auto &ev : h->prof_sk_ev) {
-        float ms = 0.f;
-        (void)hipEventSynchronize(ev.second);
-        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { h->prof_sk_ms += ms; h->prof_sk_passes++; }
-        (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-    }
-    h->prof_sk_ev.clear();
 }
 
 static void sk_free(kdf_engine *h) {
@@ -1738,23 +1689,16 @@ void kdf_destroy(kdf_engine *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     table_free(h->t);
-    prof_collect(h);
-    pf_prof_collect(h);
-    depth_prof_collect(h);
-    hits_prof_collect(h);
+    for (EvTimer &t : h->timer) t.collect();
+    stage_collect(h);
     pf_free(h);
-    sk_prof_collect(h);
     sk_free(h);
-    for (int i = 0; i < 4; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
-    for (int i = 0; i < 4; ++i) if (h->hit_buf[i]) (void)hipFree(h->hit_buf[i]);
-    for (int i = 0; i < 8; ++i) if (h->kb_buf[i]) (void)hipFree(h->kb_buf[i]);
+    for (DevBuf &b : h->buf) b.release();
     if (h->l1_packed) (void)hipFree(h->l1_packed);
     if (h->l1_mask) (void)hipFree(h->l1_mask);
     if (h->kb_pass) (void)hipFree(h->kb_pass);
-    if (h->merge_buf) (void)hipFree(h->merge_buf);
     if (h->kb_heavy) (void)hipFree(h->kb_heavy);
     for (int sl = 0; sl < 2; ++sl) {
-        for (int j = 0; j < 2; ++j) if (h->up_buf[sl][j]) (void)hipFree(h->up_buf[sl][j]);
         if (h->up_done[sl]) (void)hipEventDestroy(h->up_done[sl]);
         if (h->use_done[sl]) (void)hipEventDestroy(h->use_done[sl]);
     }
@@ -1831,20 +1775,16 @@ int kdf_flush(kdf_engine *h) {
 
 int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_count_reads_dev: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    return count_insert_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+    StreamSrc src;
+    const int rc = src_dev(h, "kdf_count_reads_dev", d_packed, d_invalid, n_bases, src);
+    return rc ? rc : count_insert_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_count_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_count_reads: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    return count_insert_dev(h, dp, dm, n_bases);
+    StreamSrc src;
+    const int rc = src_host(h, "kdf_count_reads", packed, invalid, n_bases, src);
+    return rc || !src.n_bases ? rc : count_insert_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_host_alloc(uint64_t bytes, void **out) {
@@ -1874,22 +1814,17 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
     uint64_t pw, mw;
     kdf_stream_words(n_bases, &pw, &mw);
     const size_t want[2] = {(size_t)pw * 8, (size_t)mw * 8};
-    for (int j = 0; j < 2; ++j) {
-        if (h->up_bytes[slot][j] >= want[j]) continue;
-        HIPCHK(h, hipStreamSynchronize(h->stream));            // (the slot's last count may still read the old buffer)
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        if (h->up_buf[slot][j]) (void)hipFree(h->up_buf[slot][j]);
-        h->up_buf[slot][j] = nullptr; h->up_bytes[slot][j] = 0;
-        const size_t sz = want[j] + want[j] / 8 + 4096;
-        HIPCHK(h, hipMalloc(&h->up_buf[slot][j], sz));
-        h->up_bytes[slot][j] = sz;
-    }
+    auto both_streams = [&] {                                  // (the slot's last count may still read the old buffer)
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(h->copy_stream);
+    };
+    for (int j = 0; j < 2; ++j) HIPCHK(h, dev_reserve(h->up_buf[slot][j], want[j], slack_8th(want[j]), both_streams));
     h->up_valid[slot] = false;
     h->up_n[slot] = n_bases;
     if (n_bases == 0) { h->up_valid[slot] = true; return KDF_OK; }
     hipStream_t cs = h->copy_stream;
     if (h->use_done[slot]) HIPCHK(h, hipStreamWaitEvent(cs, h->use_done[slot], 0));   // the count that last read this slot
-    int rc = upload_padded(h, packed, invalid, n_bases, (uint64_t *)h->up_buf[slot][0], (uint64_t *)h->up_buf[slot][1], cs);
+    int rc = upload_padded(h, packed, invalid, n_bases, (uint64_t *)h->up_buf[slot][0].p, (uint64_t *)h->up_buf[slot][1].p, cs);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->up_done[slot], cs));
     h->up_valid[slot] = true;
@@ -1898,25 +1833,19 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
 
 int kdf_count_uploaded(kdf_engine *h, int slot, int filtered) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: nothing was uploaded into slot %d", slot);
+    StreamSrc src;
     // (a call refused for the engine's state keeps the slot's batch: a refused call changes nothing)
-    if (!filtered && h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: a filter is loaded; call kdf_clear first");
-    if (filtered && !h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: no filter loaded (kdf_load_filter)");
-    if (filtered && h->up_n[slot] && h->opt_force_path == 4 && !h->sieve_valid)      // (an empty batch asks nothing of the sieve: kdf_count_reads_filtered*)
-        return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: force_path 4 (sieve): no sieve for this filter (keys were added after kdf_load_filter)");
-    if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
-    HIPCHK(h, hipSetDevice(h->device));
-    h->up_valid[slot] = false;
-    const uint64_t n = h->up_n[slot];
-    if (n == 0) return KDF_OK;
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
-    // The HOST waits for the copy as well: the caller recycles its (pinned) source buffer as soon as this call returns,
-    // and a filtered count returns without any host synchronisation.  The copy was issued a whole batch ago and has
-    // normally long finished.
-    HIPCHK(h, hipEventSynchronize(h->up_done[slot]));
-    const uint64_t *dp = (const uint64_t *)h->up_buf[slot][0], *dm = (const uint64_t *)h->up_buf[slot][1];
-    const int rc = filtered ? count_filtered_dev(h, dp, dm, n) : count_insert_dev(h, dp, dm, n);
-    (void)hipEventRecord(h->use_done[slot], h->stream);
+    int rc = src_slot(EngSink{h}, "kdf_count_uploaded", h, slot, true, true, src, [&](const StreamSrc &b) {
+        if (!filtered && h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: a filter is loaded; call kdf_clear first");
+        if (filtered && !h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: no filter loaded (kdf_load_filter)");
+        if (filtered && b.n_bases && h->opt_force_path == 4 && !h->sieve_valid)      // (an empty batch asks nothing of the sieve: kdf_count_reads_filtered*)
+            return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: force_path 4 (sieve): no sieve for this filter (keys were added after kdf_load_filter)");
+        if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
+        return (int)KDF_OK;
+    });
+    if (rc || !src.n_bases) return rc;
+    rc = filtered ? count_filtered_dev(h, src.packed, src.invalid, src.n_bases) : count_insert_dev(h, src.packed, src.invalid, src.n_bases);
+    src_release(h, src);
     return rc;
 }
 
@@ -2007,7 +1936,7 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (n && (rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_load_filter"))) return rc;
-    return load_filter_core(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3], n, "kdf_load_filter");
+    return load_filter_core(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p, n, "kdf_load_filter");
 }
 
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n) {
@@ -2029,14 +1958,6 @@ int kdf_reset_counts(kdf_engine *h) {
     HIPCHK(h, hipMemsetAsync(h->t.cnt, 0, h->cap * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->ctl->windows, 0, sizeof(h->ctl->windows), h->stream));
     h->windows = 0; h->zero_keys = true;
-    return KDF_OK;
-}
-
-static int merge_reserve(kdf_engine *h, size_t bytes) {
-    if (h->merge_bytes >= bytes) return KDF_OK;
-    if (h->merge_buf) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->merge_buf); h->merge_buf = nullptr; h->merge_bytes = 0; }
-    HIPCHK(h, hipMalloc(&h->merge_buf, bytes));
-    h->merge_bytes = bytes;
     return KDF_OK;
 }
 
@@ -2074,9 +1995,9 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
         sg.nseg = m;
         const uint32_t nb = (uint32_t)(h->cap >> h->t.bucket_bits);
         const size_t words = (size_t)m * nb * 2 + 16;
-        if ((rc = merge_reserve(h, words * 4))) return rc;
-        uint32_t *first = (uint32_t *)h->merge_buf, *last = first + (size_t)m * nb, *flag = last + (size_t)m * nb;
-        HIPCHK(h, hipMemsetAsync(h->merge_buf, 0, words * 4, h->stream));
+        if ((rc = eng_reserve(h, *h->merge_buf, words * 4, slack_exact))) return rc;
+        uint32_t *first = (uint32_t *)h->merge_buf->p, *last = first + (size_t)m * nb, *flag = last + (size_t)m * nb;
+        HIPCHK(h, hipMemsetAsync(h->merge_buf->p, 0, words * 4, h->stream));
         const dim3 pg((unsigned)((nmax + 255) / 256), m);
         const size_t lds_bytes = ((size_t)8 * h->kw + 4) << h->t.bucket_bits;
         const bool fresh = h->lazy_empty;            // the kernel writes every bucket: it IS the deferred clear
@@ -2150,8 +2071,8 @@ int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_h
     int rc;
     if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_add_pairs"))) return rc;
     if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs"))) return rc;
-    return add_pairs_dev(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3],
-                         counts ? (const uint32_t *)h->stage[0] : nullptr, n, "kdf_add_pairs");
+    return add_pairs_dev(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p,
+                         counts ? (const uint32_t *)h->stage[0].p : nullptr, n, "kdf_add_pairs");
 }
 
 int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
@@ -2182,21 +2103,17 @@ int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_
 
 int kdf_count_reads_filtered_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_count_reads_filtered_dev: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    return count_filtered_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+    StreamSrc src;
+    const int rc = src_dev(h, "kdf_count_reads_filtered_dev", d_packed, d_invalid, n_bases, src);
+    return rc ? rc : count_filtered_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     if (!h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads_filtered: no filter loaded (kdf_load_filter)");
-    if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_count_reads_filtered: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    if ((rc = count_filtered_dev(h, dp, dm, n_bases))) return rc;
+    StreamSrc src;
+    int rc = src_host(h, "kdf_count_reads_filtered", packed, invalid, n_bases, src);
+    if (rc || !src.n_bases || (rc = count_filtered_dev(h, src.packed, src.invalid, src.n_bases))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));   // staging buffers are reused by the next call
     return KDF_OK;
 }
@@ -2238,9 +2155,9 @@ int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, u
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_query"))) return rc;
-    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    if ((rc = query_core(h, (const uint64_t *)h->stage[2], (const uint64_t *)h->stage[3], n, (uint32_t *)h->stage[0]))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
+    if ((rc = query_core(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p, n, (uint32_t *)h->stage[0].p))) return rc;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -2295,9 +2212,9 @@ static int export_parts(kdf_engine *h, uint32_t min_count, uint32_t parts, bool 
     const uint64_t nblk = h->cap / KM_BLOCK_SLOTS;
     // scratch: blk_off u64[nblk + 1] | part_first u64[S] | part_off u64[S + 1] | part_base u64[S + 1] | blk_cnt u32[nblk]
     const size_t off_words = nblk + 1 + KDF_SHARDS + 2 * (KDF_SHARDS + 1);
-    int rc = merge_reserve(h, off_words * 8 + nblk * 4);
+    int rc = eng_reserve(h, *h->merge_buf, off_words * 8 + nblk * 4, slack_exact);
     if (rc) return rc;
-    unsigned long long *blk_off = (unsigned long long *)h->merge_buf;
+    unsigned long long *blk_off = (unsigned long long *)h->merge_buf->p;
     uint64_t *part_first = (uint64_t *)(blk_off + nblk + 1);
     unsigned long long *part_off = (unsigned long long *)(part_first + KDF_SHARDS);
     unsigned long long *part_base = part_off + KDF_SHARDS + 1;
@@ -2381,19 +2298,12 @@ static int histo_pass(kdf_engine *h, uint32_t high, unsigned long long *d_bins, 
     const uint64_t *occ = !h->zero_keys ? nullptr : h->kw == 1 ? h->t.lo : h->t.hi + ((uint64_t)(h->kw - 2) << h->t.log2cap);
     const uint64_t wgs = (h->cap / 4 + (uint64_t)KH_THREADS * KH_UNROLL - 1) / ((uint64_t)KH_THREADS * KH_UNROLL);
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(wgs, (uint64_t)h->n_cu * KH_WG_PER_CU));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (h->prof) { HIPCHK(h, hipEventCreate(&ev[0])); HIPCHK(h, hipEventCreate(&ev[1])); HIPCHK(h, hipEventRecord(ev[0], h->stream)); }
+    EvSpan span(h->timer[T_HISTO], h->prof, h->stream);
     hipLaunchKernelGGL(kdf_histo_kernel, dim3(grid), dim3(KH_THREADS), 0, h->stream, h->t.cnt, occ, h->cap, high, d_bins, h->d_out4);
-    hipError_t le = hipGetLastError();
-    if (h->prof && le == hipSuccess) le = hipEventRecord(ev[1], h->stream);
-    if (le == hipSuccess) le = hipMemcpyAsync(h->h_out4, h->d_out4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
-    if (le == hipSuccess) le = hipStreamSynchronize(h->stream);
-    if (h->prof) {
-        float ms = 0.f;
-        if (le == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) { h->prof_histo_ms += ms; h->prof_histo_passes++; }
-        (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
-    }
-    HIPCHK(h, le);
+    HIPCHK(h, hipGetLastError());                                    // (a launch that failed is not timed)
+    span.stop();
+    HIPCHK(h, hipMemcpyAsync(h->h_out4, h->d_out4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
@@ -2408,10 +2318,10 @@ int kdf_histogram(kdf_engine *h, uint32_t high, uint64_t *bins_out) {
     if (high > KH_MAX_HIGH) return fail(h, KDF_ERR_INVALID, "kdf_histogram: high = %u is above the limit of %u", high, KH_MAX_HIGH);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t bytes = ((size_t)high + 2) * 8;
-    int rc = stage_reserve(h, 1, bytes);
+    int rc = eng_reserve(h, h->stage[1], bytes);
     if (rc) return rc;
-    if ((rc = histo_pass(h, high, (unsigned long long *)h->stage[1], "kdf_histogram"))) return rc;
-    HIPCHK(h, hipMemcpy(bins_out, h->stage[1], bytes, hipMemcpyDeviceToHost));
+    if ((rc = histo_pass(h, high, (unsigned long long *)h->stage[1].p, "kdf_histogram"))) return rc;
+    HIPCHK(h, hipMemcpy(bins_out, h->stage[1].p, bytes, hipMemcpyDeviceToHost));
     return KDF_OK;
 }
 
@@ -2460,18 +2370,18 @@ static int export_host(kdf_engine *h, uint32_t min_count, uint64_t *lo_out, uint
     if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
     if (!lo_out || (h->kw == 2 && !hi_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL key output", fn);
     const size_t lo_bytes = n * 8 * lo_words(h);
-    if ((rc = stage_reserve(h, 2, lo_bytes))) return rc;
-    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    if (h->kw == 2 && (rc = stage_reserve(h, 3, n * 8))) return rc;
+    if ((rc = eng_reserve(h, h->stage[2], lo_bytes))) return rc;
+    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
+    if (h->kw == 2 && (rc = eng_reserve(h, h->stage[3], n * 8))) return rc;
     uint64_t n2 = 0;
-    rc = export_core(h, min_count, (uint64_t *)h->stage[2], h->kw == 2 ? (uint64_t *)h->stage[3] : nullptr, (uint32_t *)h->stage[0],
+    rc = export_core(h, min_count, (uint64_t *)h->stage[2].p, h->kw == 2 ? (uint64_t *)h->stage[3].p : nullptr, (uint32_t *)h->stage[0].p,
                      n, true, &n2, fn, sort_err);
     if (rc) return rc;
     if (n2 != n) return fail(h, KDF_ERR_STATE, "%s: table changed between passes", fn);
-    HIPCHK(h, hipMemcpyAsync(lo_out, h->stage[2], lo_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3], n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(lo_out, h->stage[2].p, lo_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
     else if (hi_out) memset(hi_out, 0, n * 8);
-    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -2566,10 +2476,10 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     uint64_t *dp, *dm;
     int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
     if (rc) return rc;
-    if ((rc = stage_reserve(h, 2, mw * 8))) return rc;
-    if ((rc = kdf_scan_reads_dev(h, dp, dm, n_bases, h->stage[2]))) return rc;
+    if ((rc = eng_reserve(h, h->stage[2], mw * 8))) return rc;
+    if ((rc = kdf_scan_reads_dev(h, dp, dm, n_bases, h->stage[2].p))) return rc;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    HIPCHK(h, hipMemcpyAsync(hit_bits, h->stage[2], n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(hit_bits, h->stage[2].p, n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!read_offsets || !distinct_out) return KDF_OK;
     // distinct hit k-mers per read: only reads with hits are touched
@@ -2605,8 +2515,7 @@ static int depth_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     const uint64_t waves = (n_tiles + KD_WAVE_TILES - 1) / KD_WAVE_TILES;
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->prof) { HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1)); HIPCHK(h, hipEventRecord(e0, h->stream)); }
+    EvSpan span(h->timer[T_DEPTH], h->prof, h->stream);
     if (d_rows) HIPCHK(h, hipMemsetAsync(d_rows, 0, (size_t)n_reads * KD_ROW_WORDS * 8, h->stream));
     by_words(h, [&](auto Wc) {
         constexpr int W = decltype(Wc)::value;
@@ -2619,7 +2528,7 @@ static int depth_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
         return 0;
     });
     if (d_rows) hipLaunchKernelGGL(kd_rows_fix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, d_rows, n_reads);
-    if (h->prof) { (void)hipEventRecord(e1, h->stream); h->prof_depth_ev.emplace_back(e0, e1); }
+    span.stop();
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
@@ -2647,11 +2556,11 @@ int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *inv
     int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
     if (rc) return rc;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if ((rc = stage_reserve(h, 2, n_bases * 4))) return rc;
-    if (valid_bits_out && (rc = stage_reserve(h, 3, n_tiles * 8))) return rc;
-    if ((rc = kdf_window_counts_dev(h, dp, dm, n_bases, h->stage[2], valid_bits_out ? h->stage[3] : nullptr))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[2], n_bases * 4, hipMemcpyDeviceToHost, h->stream));
-    if (valid_bits_out) HIPCHK(h, hipMemcpyAsync(valid_bits_out, h->stage[3], n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = eng_reserve(h, h->stage[2], n_bases * 4))) return rc;
+    if (valid_bits_out && (rc = eng_reserve(h, h->stage[3], n_tiles * 8))) return rc;
+    if ((rc = kdf_window_counts_dev(h, dp, dm, n_bases, h->stage[2].p, valid_bits_out ? h->stage[3].p : nullptr))) return rc;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[2].p, n_bases * 4, hipMemcpyDeviceToHost, h->stream));
+    if (valid_bits_out) HIPCHK(h, hipMemcpyAsync(valid_bits_out, h->stage[3].p, n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -2675,14 +2584,9 @@ int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invali
 int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
                    int64_t n_reads, uint32_t low_max, uint64_t *rows_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads > 0 && (!read_offsets || !rows_out)) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL pointer");
+    if (const int rc = check_read_offsets(EngSink{h}, "kdf_read_depth", read_offsets, n_reads)) return rc;
     if (n_reads == 0) return KDF_OK;
-    if (!read_offsets || !rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL pointer");
-    if (read_offsets[0] < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: read_offsets[0] = %lld is negative", (long long)read_offsets[0]);
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (read_offsets[r + 1] < read_offsets[r])
-            return fail(h, KDF_ERR_INVALID, "kdf_read_depth: read_offsets decrease at read %lld (%lld after %lld)", (long long)r,
-                        (long long)read_offsets[r + 1], (long long)read_offsets[r]);
     const size_t row_bytes = (size_t)n_reads * KD_ROW_WORDS * 8;
     if (n_bases == 0) { memset(rows_out, 0, row_bytes); return KDF_OK; }
     if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL stream");
@@ -2691,41 +2595,14 @@ int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
     if (rc) return rc;
     if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_depth"))) return rc;
-    if ((rc = stage_reserve(h, 3, row_bytes))) return rc;
-    if ((rc = kdf_read_depth_dev(h, dp, dm, n_bases, h->stage[2], n_reads, low_max, h->stage[3]))) return rc;
-    HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3], row_bytes, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
+    if ((rc = kdf_read_depth_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, low_max, h->stage[3].p))) return rc;
+    HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
 // ------------------------------------------------ per-read hits of the scan (kdf_hits.h) ----
-
-static int hits_reserve(kdf_engine *h, int i, size_t bytes, const char *what) {
-    if (h->hit_bytes[i] >= bytes) return KDF_OK;
-    if (h->hit_buf[i]) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->hit_buf[i]); h->hit_buf[i] = nullptr; h->hit_bytes[i] = 0; }
-    const size_t want = bytes + bytes / 8 + 4096;
-    const hipError_t e = hipMalloc(&h->hit_buf[i], want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "the %s of the hit reduction (%.2f GB) does not fit the device (%s)",
-                    what, (double)want / 1e9, hipGetErrorString(e));
-    }
-    h->hit_bytes[i] = want;
-    return KDF_OK;
-}
-
-struct HitsProf {                                     // HIP events around a group of kh_* launches under kdf_profile
-    kdf_engine *h; hipEvent_t e0 = nullptr, e1 = nullptr; bool first;
-    HitsProf(kdf_engine *h_, bool first_) : h(h_), first(first_) {
-        if (h->prof && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, h->stream);
-    }
-    void stop() {
-        if (!e1) return;
-        (void)hipEventRecord(e1, h->stream);
-        h->prof_hits_ev.emplace_back(e0, e1); h->prof_hits_first.push_back(first);
-        e0 = e1 = nullptr;
-    }
-};
 
 // Steps 1-2 of kdf_hits.h over the mask words of n_bases positions (n_bases >= 1): hit_buf[1] then holds the exclusive
 // prefix of every block of KH_BLOCK_WORDS words and, behind them, the number of set bits below n_bases.
@@ -2733,9 +2610,9 @@ static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, u
     const uint64_t n_words = (n_bases + 63) / 64;
     const uint64_t n_blocks = (n_words + KH_BLOCK_WORDS - 1) / KH_BLOCK_WORDS;
     if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "a hit mask of %llu positions is beyond the 2^47 a call takes", (unsigned long long)n_bases);
-    int rc = hits_reserve(h, 1, (n_blocks + 1) * 8, "block sums");
+    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
     if (rc) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1];
+    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
     hipLaunchKernelGGL(kh_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_bits, n_bases, sums);
     hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
     HIPCHK(h, hipGetLastError());
@@ -2745,7 +2622,7 @@ static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, u
 
 // the total hits_count left, on the host (synchronises)
 static int hits_total(kdf_engine *h, uint64_t n_blocks, uint64_t *n_hits) {
-    HIPCHK(h, hipMemcpyAsync(h->h_out4, (unsigned long long *)h->hit_buf[1] + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_out4, (unsigned long long *)h->hit_buf[1].p + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_hits = h->h_out4[0];
     return KDF_OK;
@@ -2766,8 +2643,8 @@ int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid
     int rc;
     uint64_t *bits = (uint64_t *)d_hit_bits;
     if (!bits) {
-        if ((rc = hits_reserve(h, 0, (n_bases + 63) / 64 * 8, "hit mask"))) return rc;
-        bits = (uint64_t *)h->hit_buf[0];
+        if ((rc = eng_reserve(h, h->hit_buf[0], (n_bases + 63) / 64 * 8, slack_8th, "hit mask"))) return rc;
+        bits = (uint64_t *)h->hit_buf[0].p;
     }
     if ((rc = kdf_scan_reads_dev(h, d_packed, d_invalid, n_bases, bits))) return rc;     // (applies pending count work)
     if (n_reads == 0) return KDF_OK;
@@ -2776,21 +2653,21 @@ int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid
         return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: %lld reads against a table of 2^%u slots: read index and slot index must fit 63 bits "
                     "together (at most 2^%u reads per call for this table)", (long long)n_reads, h->t.log2cap, 63 - h->t.log2cap);
     uint64_t n_blocks = 0, n_hits = 0;
-    HitsProf p1(h, true);
+    EvSpan p1(h->timer[T_HITS], h->prof, h->stream, 1);           // (opens the call: counted as its pass)
     HIPCHK(h, hipMemsetAsync(d_rows_out, 0, row_bytes, h->stream));
     if ((rc = hits_count(h, bits, n_bases, &n_blocks))) return rc;
     p1.stop();
     if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
     if (n_hits == 0) return KDF_OK;
     uint32_t log2set = log2ceil(2 * n_hits);
-    if ((rc = hits_reserve(h, 2, n_hits * 8, "hit list"))) return rc;
-    if ((rc = hits_reserve(h, 3, (size_t)8 << log2set, "set of (read, k-mer) pairs"))) return rc;
-    uint64_t *pos = (uint64_t *)h->hit_buf[2];
-    unsigned long long *set = (unsigned long long *)h->hit_buf[3];
+    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
+    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (read, k-mer) pairs"))) return rc;
+    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
+    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
     const int64_t *offs = (const int64_t *)d_read_offsets;
-    HitsProf p2(h, false);
+    EvSpan p2(h->timer[T_HITS], h->prof, h->stream, 0);           // (the same call's second group: time only)
     HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
-    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, (const unsigned long long *)h->hit_buf[1],
+    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, (const unsigned long long *)h->hit_buf[1].p,
                        pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
     hipLaunchKernelGGL(kh_hits_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads,
                        (uint32_t *)d_rows_out);
@@ -2805,23 +2682,10 @@ int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid
     return KDF_OK;
 }
 
-// n_reads >= 0, offsets[0] >= 0 and no decrease, or KDF_ERR_INVALID (the host forms check before any device work)
-static int hits_check_offsets(kdf_engine *h, const char *fn, const int64_t *read_offsets, int64_t n_reads) {
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "%s: n_reads = %lld is negative", fn, (long long)n_reads);
-    if (n_reads == 0) return KDF_OK;
-    if (!read_offsets) return fail(h, KDF_ERR_INVALID, "%s: read_offsets is NULL", fn);
-    if (read_offsets[0] < 0) return fail(h, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld is negative", fn, (long long)read_offsets[0]);
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (read_offsets[r + 1] < read_offsets[r])
-            return fail(h, KDF_ERR_INVALID, "%s: read_offsets decrease at read %lld (%lld after %lld)", fn, (long long)r,
-                        (long long)read_offsets[r + 1], (long long)read_offsets[r]);
-    return KDF_OK;
-}
-
 int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
                   int64_t n_reads, uint64_t *hit_bits, uint32_t *rows_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    int rc = hits_check_offsets(h, "kdf_read_hits", read_offsets, n_reads);
+    int rc = check_read_offsets(EngSink{h}, "kdf_read_hits", read_offsets, n_reads);       // (before any device work)
     if (rc) return rc;
     if (n_reads > 0 && !rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: rows_out is NULL");
     uint64_t pw, mw;
@@ -2836,11 +2700,11 @@ int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid
     if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
     if (n_reads) {
         if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_hits"))) return rc;
-        if ((rc = stage_reserve(h, 3, row_bytes))) return rc;
+        if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
     }
-    if ((rc = kdf_read_hits_dev(h, dp, dm, n_bases, n_reads ? h->stage[2] : nullptr, n_reads, nullptr, n_reads ? h->stage[3] : nullptr))) return rc;
-    if (n_reads) HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3], row_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0], (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kdf_read_hits_dev(h, dp, dm, n_bases, n_reads ? h->stage[2].p : nullptr, n_reads, nullptr, n_reads ? h->stage[3].p : nullptr))) return rc;
+    if (n_reads) HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0].p, (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -2856,11 +2720,11 @@ int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, co
     HIPCHK(h, hipSetDevice(h->device));
     uint64_t n_blocks = 0, n_hits = 0;
     int rc;
-    HitsProf p(h, true);
+    EvSpan p(h->timer[T_HITS], h->prof, h->stream, 1);
     if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_bases, &n_blocks))) return rc;
     if (cap)
         hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_bases,
-                           (const unsigned long long *)h->hit_buf[1], (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
+                           (const unsigned long long *)h->hit_buf[1].p, (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
                            (const int64_t *)d_read_offsets, n_reads, cap);
     p.stop();
     HIPCHK(h, hipGetLastError());
@@ -2876,22 +2740,22 @@ int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, cons
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
     *n_out = 0;
     if (reads_out && !read_offsets) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: reads_out needs read_offsets");
-    int rc = hits_check_offsets(h, "kdf_hit_list", read_offsets, read_offsets ? n_reads : (n_reads < 0 ? n_reads : 0));
+    int rc = check_read_offsets(EngSink{h}, "kdf_hit_list", read_offsets, read_offsets ? n_reads : (n_reads < 0 ? n_reads : 0));
     if (rc) return rc;
     if (n_bases == 0) return KDF_OK;
     if (!hit_bits || (cap && !positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
     if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_list"))) return rc;
     if (reads_out && (rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_list"))) return rc;
-    if ((rc = stage_reserve(h, 1, cap * 8))) return rc;
-    if (reads_out && (rc = stage_reserve(h, 3, cap * 8))) return rc;
-    const int rcl = kdf_hit_list_dev(h, h->stage[0], n_bases, reads_out ? h->stage[2] : nullptr, reads_out ? n_reads : 0, h->stage[1],
-                                     reads_out ? h->stage[3] : nullptr, cap, n_out);
+    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
+    if (reads_out && (rc = eng_reserve(h, h->stage[3], cap * 8))) return rc;
+    const int rcl = kdf_hit_list_dev(h, h->stage[0].p, n_bases, reads_out ? h->stage[2].p : nullptr, reads_out ? n_reads : 0, h->stage[1].p,
+                                     reads_out ? h->stage[3].p : nullptr, cap, n_out);
     if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
     const uint64_t n = std::min<uint64_t>(*n_out, cap);
     if (n) {
-        HIPCHK(h, hipMemcpyAsync(positions_out, h->stage[1], n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (reads_out) HIPCHK(h, hipMemcpyAsync(reads_out, h->stage[3], n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(positions_out, h->stage[1].p, n * 8, hipMemcpyDeviceToHost, h->stream));
+        if (reads_out) HIPCHK(h, hipMemcpyAsync(reads_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return rcl;
@@ -2938,35 +2802,27 @@ int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells) 
 int kdf_prefilter_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     PF_NEED_TALLYING(h, "kdf_prefilter_add_reads_dev");
-    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_add_reads_dev: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    return pf_tally_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+    StreamSrc src;
+    const int rc = src_dev(h, "kdf_prefilter_add_reads_dev", d_packed, d_invalid, n_bases, src);
+    return rc ? rc : pf_tally_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_prefilter_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     PF_NEED_TALLYING(h, "kdf_prefilter_add_reads");
-    if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_add_reads: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    return pf_tally_dev(h, dp, dm, n_bases);
+    StreamSrc src;
+    const int rc = src_host(h, "kdf_prefilter_add_reads", packed, invalid, n_bases, src);
+    return rc ? rc : pf_tally_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_prefilter_add_uploaded(kdf_engine *h, int slot) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     PF_NEED_TALLYING(h, "kdf_prefilter_add_uploaded");
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_prefilter_add_uploaded: nothing was uploaded into slot %d", slot);
-    HIPCHK(h, hipSetDevice(h->device));
-    h->up_valid[slot] = false;
-    const uint64_t n = h->up_n[slot];
-    if (n == 0) return KDF_OK;
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
-    HIPCHK(h, hipEventSynchronize(h->up_done[slot]));              // (the caller recycles its source buffer on return: kdf_count_uploaded)
-    const int rc = pf_tally_dev(h, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
-    (void)hipEventRecord(h->use_done[slot], h->stream);
+    StreamSrc src;
+    int rc = src_slot(EngSink{h}, "kdf_prefilter_add_uploaded", h, slot, true, true, src, NoRefusal{});
+    if (rc || !src.n_bases) return rc;
+    rc = pf_tally_dev(h, src.packed, src.invalid, src.n_bases);
+    src_release(h, src);
     return rc;
 }
 
@@ -2984,7 +2840,6 @@ int kdf_prefilter_drop(kdf_engine *h) {
     HIPCHK(h, hipSetDevice(h->device));
     { int rcf = pending_flush(h); if (rcf) return rcf; }           // what is pending was admitted under this sieve
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    pf_prof_collect(h);
     pf_free(h);
     return KDF_OK;
 }
@@ -3039,35 +2894,28 @@ int kdf_sketch_begin(kdf_engine *h, uint32_t log2_registers) {
 int kdf_sketch_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     SK_NEED_ON(h, "kdf_sketch_add_reads_dev");
-    if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "kdf_sketch_add_reads_dev: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    return sk_add_dev(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
+    StreamSrc src;
+    const int rc = src_dev(h, "kdf_sketch_add_reads_dev", d_packed, d_invalid, n_bases, src);
+    return rc ? rc : sk_add_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_sketch_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     SK_NEED_ON(h, "kdf_sketch_add_reads");
-    if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_sketch_add_reads: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    return sk_add_dev(h, dp, dm, n_bases);
+    StreamSrc src;
+    const int rc = src_host(h, "kdf_sketch_add_reads", packed, invalid, n_bases, src);
+    return rc ? rc : sk_add_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
 int kdf_sketch_add_uploaded(kdf_engine *h, int slot) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     SK_NEED_ON(h, "kdf_sketch_add_uploaded");
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return fail(h, KDF_ERR_STATE, "kdf_sketch_add_uploaded: nothing was uploaded into slot %d", slot);
-    const uint64_t n = h->up_n[slot];
-    if (n == 0) return KDF_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
-    HIPCHK(h, hipEventSynchronize(h->up_done[slot]));              // (a sketch-only pass recycles its source buffer on return: kdf_count_uploaded)
-    const int rc = sk_add_dev(h, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
-    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
-    return rc;                                                     // the slot KEEPS its batch: the caller counts or tallies it next
+    StreamSrc src;                                                 // the slot KEEPS its batch: the caller counts or tallies it next
+    int rc = src_slot(EngSink{h}, "kdf_sketch_add_uploaded", h, slot, false, true, src, NoRefusal{});
+    if (rc || !src.n_bases) return rc;
+    rc = sk_add_dev(h, src.packed, src.invalid, src.n_bases);
+    src_release(h, src);
+    return rc;
 }
 
 int kdf_sketch_registers_dev(kdf_engine *h, void *d_regs_out) {
@@ -3126,7 +2974,6 @@ int kdf_sketch_drop(kdf_engine *h) {
     SK_NEED_ON(h, "kdf_sketch_drop");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    sk_prof_collect(h);
     sk_free(h);
     return KDF_OK;
 }
@@ -3196,8 +3043,8 @@ int kdf_prefilter_merge(kdf_engine *h, uint64_t first_word, uint64_t n_words, ui
     HIPCHK(h, hipSetDevice(h->device));
     // staged piece by piece (at most 256 MB of staging): segment s of a piece at stage[0] + s * piece words
     const uint64_t piece = std::max<uint64_t>(2, std::min<uint64_t>(n_words + (n_words & 1), ((1ull << 25) / nseg) & ~1ull));
-    { int rc = stage_reserve(h, 0, (size_t)piece * nseg * 8); if (rc) return rc; }
-    unsigned long long *st = (unsigned long long *)h->stage[0];
+    { int rc = eng_reserve(h, h->stage[0], (size_t)piece * nseg * 8); if (rc) return rc; }
+    unsigned long long *st = (unsigned long long *)h->stage[0].p;
     const unsigned long long *d[KDF_PF_MAX_SEGS];
     for (uint64_t w0 = 0; w0 < n_words; w0 += piece) {
         const uint64_t m = std::min<uint64_t>(piece, n_words - w0);
@@ -3236,7 +3083,7 @@ int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts,
     int rc;
     if ((rc = stage_keys(h, keys, nullptr, n, "kdf_add_pairs_w"))) return rc;
     if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs_w"))) return rc;
-    return add_pairs_dev(h, (const uint64_t *)h->stage[2], nullptr, counts ? (const uint32_t *)h->stage[0] : nullptr, n, "kdf_add_pairs_w");
+    return add_pairs_dev(h, (const uint64_t *)h->stage[2].p, nullptr, counts ? (const uint32_t *)h->stage[0].p : nullptr, n, "kdf_add_pairs_w");
 }
 
 int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n) {
@@ -3254,7 +3101,7 @@ int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n) {
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if (n && (rc = stage_keys(h, keys, nullptr, n, "kdf_load_filter_w"))) return rc;
-    return load_filter_core(h, (const uint64_t *)h->stage[2], nullptr, n, "kdf_load_filter_w");
+    return load_filter_core(h, (const uint64_t *)h->stage[2].p, nullptr, n, "kdf_load_filter_w");
 }
 
 int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_counts_out) {
@@ -3274,9 +3121,9 @@ int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *count
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
     if ((rc = stage_keys(h, keys, nullptr, n, "kdf_query_w"))) return rc;
-    if ((rc = stage_reserve(h, 0, n * 4))) return rc;
-    if ((rc = query_core(h, (const uint64_t *)h->stage[2], nullptr, n, (uint32_t *)h->stage[0]))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0], n * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
+    if ((rc = query_core(h, (const uint64_t *)h->stage[2].p, nullptr, n, (uint32_t *)h->stage[0].p))) return rc;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -3300,27 +3147,17 @@ int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint3
 
 int kdf_profile(kdf_engine *h, int enable) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    prof_collect(h);
+    for (EvTimer &t : h->timer) t.reset();
+    stage_collect(h);
     h->prof = enable != 0;
-    h->prof_ms = 0.0; h->prof_launches = 0; h->prof_positions = 0;
     for (double &m : h->prof_stage_ms) m = 0.0;
     h->prof_stage_passes = 0;
-    h->prof_histo_ms = 0.0; h->prof_histo_passes = 0;
-    pf_prof_collect(h);
-    h->prof_pf_ms = 0.0; h->prof_pf_passes = 0;
-    h->prof_pfm_ms = 0.0; h->prof_pfm_passes = 0;
-    depth_prof_collect(h);
-    h->prof_depth_ms = 0.0; h->prof_depth_passes = 0;
-    hits_prof_collect(h);
-    h->prof_hits_ms = 0.0; h->prof_hits_passes = 0;
-    sk_prof_collect(h);
-    h->prof_sk_ms = 0.0; h->prof_sk_passes = 0;
     return KDF_OK;
 }
 
 int kdf_profile_stages(kdf_engine *h, double *stage_ms4, uint64_t *passes) {
     if (!h || !stage_ms4) return fail(h, KDF_ERR_INVALID, "kdf_profile_stages: NULL pointer");
-    prof_collect(h);
+    stage_collect(h);
     for (int i = 0; i < 4; ++i) stage_ms4[i] = h->prof_stage_ms[i];
     if (passes) *passes = h->prof_stage_passes;
     return KDF_OK;
@@ -3328,10 +3165,11 @@ int kdf_profile_stages(kdf_engine *h, double *stage_ms4, uint64_t *passes) {
 
 int kdf_profile_read(kdf_engine *h, double *kernel_ms, uint64_t *launches, uint64_t *positions) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    prof_collect(h);
-    if (kernel_ms) *kernel_ms = h->prof_ms;
-    if (launches) *launches = h->prof_launches;
-    if (positions) *positions = h->prof_positions;
+    EvTimer &t = h->timer[T_STREAM];
+    t.collect();
+    if (kernel_ms) *kernel_ms = t.ms;
+    if (launches) *launches = t.passes;
+    if (positions) *positions = t.tag_sum * KDF_TILE;
     return KDF_OK;
 }
 
@@ -3402,10 +3240,10 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
 int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     if (!h || !name || !value) return fail(h, KDF_ERR_INVALID, "kdf_get_stat: NULL argument");
     const std::string n(name);
-    if (n == "binned_passes") *value = (int64_t)h->stat_binned_passes;
+    bool us = false;
+    if (EvTimer *t = timer_of_stat(h->timer, TIMER_NAME, T_COUNT, n, &us)) *value = us ? t->us() : (t->collect(), (int64_t)t->passes);
+    else if (n == "binned_passes") *value = (int64_t)h->stat_binned_passes;
     else if (n == "replayed_buckets") *value = (int64_t)h->stat_replayed_buckets;
-    else if (n == "histo_us") *value = (int64_t)(h->prof_histo_ms * 1000.0 + 0.5);
-    else if (n == "histo_passes") *value = (int64_t)h->prof_histo_passes;
     else if (n == "prefilter_state") *value = h->pf_state;
     else if (n == "prefilter_min_count") *value = h->pf.min_count;
     else if (n == "prefilter_log2_cells") *value = h->pf.log2_cells;
@@ -3434,17 +3272,7 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
             *value = (int64_t)t;
         }
     }
-    else if (n == "sketch_us") { sk_prof_collect(h); *value = (int64_t)(h->prof_sk_ms * 1000.0 + 0.5); }
-    else if (n == "sketch_passes") { sk_prof_collect(h); *value = (int64_t)h->prof_sk_passes; }
-    else if (n == "prefilter_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pf_ms * 1000.0 + 0.5); }
-    else if (n == "prefilter_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pf_passes; }
     else if (n == "prefilter_merged_words") *value = h->pf_state == PF_OFF ? 0 : (int64_t)h->stat_pf_merged_words;
-    else if (n == "prefilter_merge_us") { pf_prof_collect(h); *value = (int64_t)(h->prof_pfm_ms * 1000.0 + 0.5); }
-    else if (n == "prefilter_merge_passes") { pf_prof_collect(h); *value = (int64_t)h->prof_pfm_passes; }
-    else if (n == "depth_us") { depth_prof_collect(h); *value = (int64_t)(h->prof_depth_ms * 1000.0 + 0.5); }
-    else if (n == "depth_passes") { depth_prof_collect(h); *value = (int64_t)h->prof_depth_passes; }
-    else if (n == "hits_us") { hits_prof_collect(h); *value = (int64_t)(h->prof_hits_ms * 1000.0 + 0.5); }
-    else if (n == "hits_passes") { hits_prof_collect(h); *value = (int64_t)h->prof_hits_passes; }
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     // (pending: not yet applied by any flush.  Passes a dump-only flush has applied are kept in the ring -- "retained_passes" --
     // until the table is asked for or cleared)
@@ -3482,6 +3310,8 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
 // ===========================================================================
 
 #define KS_STAGES 6
+enum { KT_APPEND = 0, KT_OFFSETS, KT_COUNT };          // a spool's timers (option "profile"): stats "append_*", "offsets_*"
+static const char *const KS_TIMER_NAME[KT_COUNT] = {"append", "offsets"};
 struct KsSegment {
     uint64_t *packed = nullptr, *mask = nullptr;     // 2 cap_tiles + 4 / cap_tiles + 2 words: HBM, or pinned host memory
     uint64_t cap_tiles = 0, tiles = 0;               // room / used; the segment is a stream of tiles x 64 positions
@@ -3504,26 +3334,24 @@ struct kdf_spool {
     bool overflowed = false;
     hipStream_t stream = nullptr;                    // kdf_spool_append (host sources) runs here
     hipEvent_t last = nullptr; bool have_last = false;   // behind the latest append, whatever stream it ran on
-    // grow-only: 0/1 a host source's words, 2/3 a host-tier batch before its copy out, 4 a host source's offsets, 5 a
-    // host-tier batch's offsets before their copy out
-    void *stage[KS_STAGES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t stage_bytes[KS_STAGES] = {0, 0, 0, 0, 0, 0};
+    DevBuf buf[KS_STAGES + 4];                       // every grow-only device buffer (released together), through the views below
+    // 0/1 a host source's words, 2/3 a host-tier batch before its copy out, 4 a host source's offsets, 5 a host-tier
+    // batch's offsets before their copy out; the last user is an append, and every append is behind `last`
+    DevBuf *const stage = buf;
     // kdf_spool_append_uploaded_reads: the caller's offsets pass through pinned memory, so the copy is truly asynchronous
     // and the caller's array is its own again at once; pin_done is behind the copy that read it last
     // (one buffer per upload slot: the host never waits for the append it queued last)
     int64_t *pin_offs[2] = {nullptr, nullptr}; size_t pin_entries[2] = {0, 0};
     hipEvent_t pin_done[2] = {nullptr, nullptr}; bool have_pin_done[2] = {false, false};
-    // replays of the per-read consumers: one host-tier segment's packed, mask and offsets words on the device (grow-only,
-    // not charged to the budget); rep_done is behind the consumer that read them last, whatever engine it ran on
-    void *rep[3] = {nullptr, nullptr, nullptr};
-    size_t rep_bytes[3] = {0, 0, 0};
+    // replays of the per-read consumers: one host-tier segment's packed, mask and offsets words on the device (not
+    // charged to the budget); rep_done is behind the consumer that read them last, whatever engine it ran on
+    DevBuf *const rep = buf + KS_STAGES;
     hipEvent_t rep_done = nullptr; bool have_rep_done = false;
     // kdf_spool_select_reads: block sums (device) and the total (pinned)
-    void *sel_buf = nullptr; size_t sel_bytes = 0;
+    DevBuf *const sel_buf = buf + KS_STAGES + 3;
     unsigned long long *sel_total = nullptr;
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev, prof_offs_ev;
-    double prof_ms = 0.0, prof_offs_ms = 0.0; uint64_t prof_passes = 0, prof_offs_passes = 0;
+    EvTimer timer[KT_COUNT];                         // never reset: turning "profile" off keeps what was recorded
     std::string err;
 };
 
@@ -3541,55 +3369,42 @@ static int ks_fail(kdf_spool *sp, int code, const char *fmt, ...) {
                            "%s failed: %s", #call, hipGetErrorString(e_));              \
     } while (0)
 
-static void ks_prof_collect(std::vector<std::pair<hipEvent_t, hipEvent_t>> &evs, double &total_ms, uint64_t &passes) {
-    for (auto &pr : evs) {
-        float ms = 0.f;
-        if (hipEventSynchronize(pr.second) == hipSuccess && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-            total_ms += ms; ++passes;
-        } else (void)hipGetLastError();
-        (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second);
-    }
-    evs.clear();
-}
-static void ks_prof_collect(kdf_spool *sp) {
-    ks_prof_collect(sp->prof_ev, sp->prof_ms, sp->prof_passes);
-    ks_prof_collect(sp->prof_offs_ev, sp->prof_offs_ms, sp->prof_offs_passes);
-}
+extern "C++" {                                      // (templates: this section lies inside the extern "C" block)
+struct KsSink {                                      // where the message of a refusal goes: this spool's error string
+    kdf_spool *sp;
+    template <typename... A> int operator()(int code, const char *fmt, A... a) const { return ks_fail(sp, code, fmt, a...); }
+};
 
-// grow-only staging; the buffer's last user is an append, and every append is behind sp->last
+// Room for `bytes` in one of the spool's buffers (dev_reserve): `want` bytes are allocated, quiesce() waits for the old
+// buffer's last reader (a failed wait is a KDF_ERR_HIP).  fmt words a failed allocation: (%zu bytes wanted, %s HIP's text).
+template <typename Q>
+static int ks_reserve(kdf_spool *sp, DevBuf &b, size_t bytes, size_t want, Q &&quiesce, const char *fmt) {
+    hipError_t qe = hipSuccess;
+    const hipError_t e = dev_reserve(b, bytes, want, [&] { return qe = quiesce(); });
+    if (qe != hipSuccess) return ks_fail(sp, KDF_ERR_HIP, "read spool: waiting for a buffer's last reader failed: %s", hipGetErrorString(qe));
+    return e == hipSuccess ? KDF_OK : ks_fail(sp, KDF_ERR_NOMEM, fmt, want, hipGetErrorString(e));
+}
+}  // extern "C++"
+// staging: the buffer's last user is an append, and every append is behind sp->last
 static int ks_stage_reserve(kdf_spool *sp, int i, size_t bytes) {
-    if (sp->stage_bytes[i] >= bytes) return KDF_OK;
-    if (sp->stage[i]) {
-        if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
-        (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 4096;
-    const hipError_t e = hipMalloc(&sp->stage[i], want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); sp->stage[i] = nullptr;
-        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of staging do not fit the device (%s)", want, hipGetErrorString(e));
-    }
-    sp->stage_bytes[i] = want;
-    return KDF_OK;
+    return ks_reserve(sp, sp->stage[i], bytes, slack_8th(bytes), [&] { return sp->have_last ? hipEventSynchronize(sp->last) : hipSuccess; },
+                      "read spool: %zu bytes of staging do not fit the device (%s)");
 }
 
 static void ks_free_all(kdf_spool *sp) {
     (void)hipSetDevice(sp->device);
     (void)hipDeviceSynchronize();                    // replays read the segments on their engines' streams
-    ks_prof_collect(sp);
+    for (EvTimer &t : sp->timer) t.collect();
     for (auto &s : sp->segs) {
         if (s.host) { if (s.packed) (void)hipHostFree(s.packed); if (s.mask) (void)hipHostFree(s.mask); if (s.offs) (void)hipHostFree(s.offs); }
         else { if (s.packed) (void)hipFree(s.packed); if (s.mask) (void)hipFree(s.mask); if (s.offs) (void)hipFree(s.offs); }
     }
     sp->segs.clear();
-    for (int i = 0; i < KS_STAGES; ++i) { if (sp->stage[i]) (void)hipFree(sp->stage[i]); sp->stage[i] = nullptr; sp->stage_bytes[i] = 0; }
-    for (int i = 0; i < 3; ++i) { if (sp->rep[i]) (void)hipFree(sp->rep[i]); sp->rep[i] = nullptr; sp->rep_bytes[i] = 0; }
+    for (DevBuf &b : sp->buf) b.release();
     for (int i = 0; i < 2; ++i) {
         if (sp->pin_offs[i]) (void)hipHostFree(sp->pin_offs[i]);
         sp->pin_offs[i] = nullptr; sp->pin_entries[i] = 0; sp->have_pin_done[i] = false;
     }
-    if (sp->sel_buf) (void)hipFree(sp->sel_buf);
-    sp->sel_buf = nullptr; sp->sel_bytes = 0;
     sp->hbm_bytes = sp->host_bytes = sp->batches = sp->bases = sp->reads = sp->offset_bytes = 0;
     sp->mode = KS_MODE_OPEN;
     sp->overflowed = false; sp->have_last = false; sp->have_rep_done = false;
@@ -3685,18 +3500,11 @@ static int ks_offsets_reserve(kdf_spool *sp, KsSegment *seg, uint64_t need, uint
 
 // n_reads >= 0, offsets[0] == 0, no decrease, offsets[n_reads] == n_bases: what kdf_pack_reads and kdf_reader_next hand out
 static int ks_check_offsets(kdf_spool *sp, const char *fn, const int64_t *offs, int64_t n_reads, uint64_t n_bases) {
-    if (n_reads < 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: n_reads = %lld is negative", fn, (long long)n_reads);
-    if (n_reads == 0) {
-        if (n_bases) return ks_fail(sp, KDF_ERR_INVALID, "%s: %llu positions in no read (read_offsets[n_reads] must be n_bases)", fn, (unsigned long long)n_bases);
-        return KDF_OK;
-    }
-    if (n_bases == 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: %lld reads in a batch of no positions (a batch without positions has no place in a segment)", fn, (long long)n_reads);
-    if (!offs) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets is NULL", fn);
-    if (offs[0] != 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld, not 0", fn, (long long)offs[0]);
-    for (int64_t r = 0; r < n_reads; ++r)
-        if (offs[r + 1] < offs[r])
-            return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets decrease at read %lld (%lld after %lld)", fn, (long long)r, (long long)offs[r + 1],
-                           (long long)offs[r]);
+    if (n_reads == 0 && n_bases) return ks_fail(sp, KDF_ERR_INVALID, "%s: %llu positions in no read (read_offsets[n_reads] must be n_bases)", fn, (unsigned long long)n_bases);
+    if (n_reads > 0 && n_bases == 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: %lld reads in a batch of no positions (a batch without positions has no place in a segment)", fn, (long long)n_reads);
+    if (n_reads > 0 && offs && offs[0] != 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld, not 0", fn, (long long)offs[0]);
+    const int rc = check_read_offsets(KsSink{sp}, fn, offs, n_reads);                  // negative n_reads, NULL, a decrease
+    if (rc || n_reads == 0) return rc;
     if ((uint64_t)offs[n_reads] != n_bases)
         return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[n_reads] = %lld, not n_bases = %llu (the last read must end where the batch ends)", fn,
                        (long long)offs[n_reads], (unsigned long long)n_bases);
@@ -3736,36 +3544,28 @@ static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_pack
     if (seg->host) {
         if ((rc = ks_stage_reserve(sp, 2, (2 * n_tiles + 4) * 8)) || (rc = ks_stage_reserve(sp, 3, (n_tiles + 2) * 8)) ||
             (keep && (rc = ks_stage_reserve(sp, 5, (n_reads + 1) * 8)))) { sp->overflowed = true; return rc; }
-        dp = (uint64_t *)sp->stage[2]; dm = (uint64_t *)sp->stage[3];
-        if (keep) doffs = (int64_t *)sp->stage[5];
+        dp = (uint64_t *)sp->stage[2].p; dm = (uint64_t *)sp->stage[3].p;
+        if (keep) doffs = (int64_t *)sp->stage[5].p;
     }
     if (keep && h_offs && (rc = ks_stage_reserve(sp, 4, (n_reads + 1) * 8))) return rc;
     if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(s, sp->last, 0));
     if (keep && h_offs) {
-        KSCHK(sp, hipMemcpyAsync(sp->stage[4], h_offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-        d_offs = (const int64_t *)sp->stage[4];
+        KSCHK(sp, hipMemcpyAsync(sp->stage[4].p, h_offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
+        d_offs = (const int64_t *)sp->stage[4].p;
     }
     const unsigned blocks = (unsigned)std::min<uint64_t>((n_tiles + 2 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (sp->prof) {
-        KSCHK(sp, hipEventCreate(&e0)); KSCHK(sp, hipEventCreate(&e1));
-        KSCHK(sp, hipEventRecord(e0, s));
-    }
+    EvSpan span(sp->timer[KT_APPEND], sp->prof, s);
     hipLaunchKernelGGL(ks_append_kernel, dim3(blocks), dim3(KS_THREADS), 0, s, dp, dm, d_packed, d_invalid, n_bases, n_tiles,
                        (int)(((uintptr_t)d_packed & 15) == 0));
     KSCHK(sp, hipGetLastError());
-    if (sp->prof) { KSCHK(sp, hipEventRecord(e1, s)); sp->prof_ev.emplace_back(e0, e1); }
+    span.stop();
     if (keep) {
         // entries n_reads(seg) .. n_reads(seg) + n_reads: the first overwrites the last entry of the batch before (kdf.h: the gap)
         const unsigned oblocks = (unsigned)std::min<uint64_t>((n_reads + 1 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
-        hipEvent_t o0 = nullptr, o1 = nullptr;
-        if (sp->prof) {
-            KSCHK(sp, hipEventCreate(&o0)); KSCHK(sp, hipEventCreate(&o1));
-            KSCHK(sp, hipEventRecord(o0, s));
-        }
+        EvSpan ospan(sp->timer[KT_OFFSETS], sp->prof, s);
         hipLaunchKernelGGL(ks_offsets_kernel, dim3(oblocks), dim3(KS_THREADS), 0, s, doffs, d_offs, n_reads + 1, (int64_t)(seg->tiles * KDF_TILE));
         KSCHK(sp, hipGetLastError());
-        if (sp->prof) { KSCHK(sp, hipEventRecord(o1, s)); sp->prof_offs_ev.emplace_back(o0, o1); }
+        ospan.stop();
     }
     if (seg->host) {
         KSCHK(sp, hipMemcpyAsync(seg->packed + 2 * seg->tiles, dp, (2 * n_tiles + 4) * 8, hipMemcpyDeviceToHost, s));
@@ -3833,7 +3633,7 @@ int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value) {
         if (value < 1 || value > (1ll << 28)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: offsets_chunk must be 1 .. 2^28 entries");
         sp->opt_offsets_chunk = (uint64_t)value;                   // (arrays already allocated keep their size)
     } else if (n == "profile") {
-        if (!value) { (void)hipSetDevice(sp->device); ks_prof_collect(sp); }
+        if (!value) { (void)hipSetDevice(sp->device); for (EvTimer &t : sp->timer) t.collect(); }
         sp->prof = value != 0;
     } else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: unknown option %s", name);
     return KDF_OK;
@@ -3842,7 +3642,12 @@ int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value) {
 int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value) {
     if (!sp || !name || !value) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: NULL argument");
     const std::string n(name);
-    if (n == "segments") *value = (int64_t)sp->segs.size();
+    bool us = false;
+    if (EvTimer *t = timer_of_stat(sp->timer, KS_TIMER_NAME, KT_COUNT, n, &us)) {
+        (void)hipSetDevice(sp->device);
+        *value = us ? t->us() : (t->collect(), (int64_t)t->passes);
+    }
+    else if (n == "segments") *value = (int64_t)sp->segs.size();
     else if (n == "batches") *value = (int64_t)sp->batches;
     else if (n == "positions") { uint64_t t = 0; for (auto &s : sp->segs) t += s.tiles; *value = (int64_t)(t * KDF_TILE); }
     else if (n == "bases") *value = (int64_t)sp->bases;
@@ -3855,10 +3660,6 @@ int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value) {
     else if (n == "reads") *value = (int64_t)sp->reads;
     else if (n == "keeps_reads") *value = sp->mode == KS_MODE_READS ? 1 : 0;
     else if (n == "offset_bytes") *value = (int64_t)sp->offset_bytes;
-    else if (n == "offsets_us") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)(sp->prof_offs_ms * 1000.0 + 0.5); }
-    else if (n == "offsets_passes") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)sp->prof_offs_passes; }
-    else if (n == "append_us") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)(sp->prof_ms * 1000.0 + 0.5); }
-    else if (n == "append_passes") { (void)hipSetDevice(sp->device); ks_prof_collect(sp); *value = (int64_t)sp->prof_passes; }
     else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: unknown stat %s", name);
     return KDF_OK;
 }
@@ -3879,9 +3680,9 @@ int kdf_spool_append(kdf_spool *sp, const uint64_t *packed, const uint64_t *inva
     const uint64_t src_tiles = (n_bases + 63) / 64;                 // (the words the kernel loads, no more)
     if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
     if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));   // (the staging's last reader)
-    KSCHK(sp, hipMemcpyAsync(sp->stage[0], packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[1], invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0], (const uint64_t *)sp->stage[1], n_bases);
+    KSCHK(sp, hipMemcpyAsync(sp->stage[0].p, packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    KSCHK(sp, hipMemcpyAsync(sp->stage[1].p, invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0].p, (const uint64_t *)sp->stage[1].p, n_bases);
     KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
     return rc;
 }
@@ -3890,14 +3691,13 @@ int kdf_spool_append_uploaded(kdf_spool *sp, kdf_engine *h, int slot) {
     if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
     if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: NULL engine");
     if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: the spool is on device %d, the engine on %d", sp->device, h->device);
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_append_uploaded: nothing was uploaded into slot %d", slot);
-    const uint64_t n = h->up_n[slot];
-    int rc = ks_check_append(sp, h->up_buf[slot][0], h->up_buf[slot][1], n, "kdf_spool_append_uploaded");
-    if (rc || n == 0) return rc;
-    KSCHK(sp, hipSetDevice(sp->device));
-    KSCHK(sp, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
-    rc = spool_append_dev(sp, h->stream, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n);
-    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
+    StreamSrc src;                                                 // (the slot keeps its batch; the host does not wait for the copy)
+    int rc = src_slot(KsSink{sp}, "kdf_spool_append_uploaded", h, slot, false, false, src, [&](const StreamSrc &b) {
+        return ks_check_append(sp, b.packed, b.invalid, b.n_bases, "kdf_spool_append_uploaded");
+    });
+    if (rc || !src.n_bases) return rc;
+    rc = spool_append_dev(sp, h->stream, src.packed, src.invalid, src.n_bases);
+    src_release(h, src);                                           // (the slot's next upload waits for this reader as for a count)
     return rc;
 }
 
@@ -3926,9 +3726,9 @@ int kdf_spool_append_reads(kdf_spool *sp, const uint64_t *packed, const uint64_t
     const uint64_t src_tiles = (n_bases + 63) / 64;                 // (>= 1: a batch with reads has positions)
     if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
     if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[0], packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[1], invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0], (const uint64_t *)sp->stage[1], n_bases, true, nullptr, read_offsets,
+    KSCHK(sp, hipMemcpyAsync(sp->stage[0].p, packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    KSCHK(sp, hipMemcpyAsync(sp->stage[1].p, invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
+    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0].p, (const uint64_t *)sp->stage[1].p, n_bases, true, nullptr, read_offsets,
                           (uint64_t)n_reads);
     KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
     return rc;
@@ -3938,11 +3738,12 @@ int kdf_spool_append_uploaded_reads(kdf_spool *sp, kdf_engine *h, int slot, cons
     if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
     if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: NULL engine");
     if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: the spool is on device %d, the engine on %d", sp->device, h->device);
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_append_uploaded_reads: nothing was uploaded into slot %d", slot);
-    const uint64_t n = h->up_n[slot];
-    int rc = ks_check_append(sp, h->up_buf[slot][0], h->up_buf[slot][1], n, "kdf_spool_append_uploaded_reads", true);
-    if (rc || (rc = ks_check_offsets(sp, "kdf_spool_append_uploaded_reads", read_offsets, n_reads, n)) || n_reads == 0) return rc;
-    KSCHK(sp, hipSetDevice(sp->device));
+    StreamSrc src;
+    int rc = src_slot(KsSink{sp}, "kdf_spool_append_uploaded_reads", h, slot, false, false, src, [&](const StreamSrc &b) {
+        const int rcb = ks_check_append(sp, b.packed, b.invalid, b.n_bases, "kdf_spool_append_uploaded_reads", true);
+        return rcb ? rcb : ks_check_offsets(sp, "kdf_spool_append_uploaded_reads", read_offsets, n_reads, b.n_bases);
+    });
+    if (rc || n_reads == 0) return rc;
     // through pinned memory: the copy is queued behind the engine's work and the caller's array is not read after this returns
     const size_t entries = (size_t)n_reads + 1;
     if (sp->have_pin_done[slot]) KSCHK(sp, hipEventSynchronize(sp->pin_done[slot]));   // (the slot's append before this one)
@@ -3955,12 +3756,10 @@ int kdf_spool_append_uploaded_reads(kdf_spool *sp, kdf_engine *h, int slot, cons
         sp->pin_entries[slot] = want;
     }
     memcpy(sp->pin_offs[slot], read_offsets, entries * 8);
-    KSCHK(sp, hipStreamWaitEvent(h->stream, h->up_done[slot], 0));
-    rc = spool_append_dev(sp, h->stream, (const uint64_t *)h->up_buf[slot][0], (const uint64_t *)h->up_buf[slot][1], n, true, nullptr, sp->pin_offs[slot],
-                          (uint64_t)n_reads);
+    rc = spool_append_dev(sp, h->stream, src.packed, src.invalid, src.n_bases, true, nullptr, sp->pin_offs[slot], (uint64_t)n_reads);
     if (hipEventRecord(sp->pin_done[slot], h->stream) == hipSuccess) sp->have_pin_done[slot] = true;
     else { (void)hipGetLastError(); (void)hipStreamSynchronize(h->stream); sp->have_pin_done[slot] = false; }
-    (void)hipEventRecord(h->use_done[slot], h->stream);            // (the slot's next upload waits for this reader as for a count)
+    src_release(h, src);                                           // (the slot's next upload waits for this reader as for a count)
     return rc;
 }
 
@@ -3999,20 +3798,10 @@ int kdf_spool_segment_dev(kdf_spool *sp, uint64_t seg, const void **d_packed, co
 
 // ---- replays of the per-read consumers ----
 
+// a replay buffer's last reader ran on some engine's stream: the whole device is drained before a free
 static int ks_rep_reserve(kdf_spool *sp, int i, size_t bytes) {
-    if (sp->rep_bytes[i] >= bytes) return KDF_OK;
-    if (sp->rep[i]) {
-        KSCHK(sp, hipDeviceSynchronize());                         // (its last reader ran on some engine's stream)
-        (void)hipFree(sp->rep[i]); sp->rep[i] = nullptr; sp->rep_bytes[i] = 0;
-    }
-    const size_t want = bytes + bytes / 8 + 4096;
-    const hipError_t e = hipMalloc(&sp->rep[i], want);
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); sp->rep[i] = nullptr;
-        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of staging for a host-tier segment do not fit the device (%s)", want, hipGetErrorString(e));
-    }
-    sp->rep_bytes[i] = want;
-    return KDF_OK;
+    return ks_reserve(sp, sp->rep[i], bytes, slack_8th(bytes), [] { return hipDeviceSynchronize(); },
+                      "read spool: %zu bytes of staging for a host-tier segment do not fit the device (%s)");
 }
 
 // Every segment in order through kdf_read_hits_dev (depth false; 8 bytes a row) or kdf_read_depth_dev (48 bytes a row),
@@ -4043,10 +3832,10 @@ static int spool_replay_reads(kdf_spool *sp, kdf_engine *h, const char *fn, bool
             int rc;
             if ((rc = ks_rep_reserve(sp, 0, pb)) || (rc = ks_rep_reserve(sp, 1, mb)) || (rc = ks_rep_reserve(sp, 2, ob))) return rc;
             if (sp->have_rep_done) KSCHK(sp, hipStreamWaitEvent(h->stream, sp->rep_done, 0));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[0], s.packed, pb, hipMemcpyHostToDevice, h->stream));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[1], s.mask, mb, hipMemcpyHostToDevice, h->stream));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[2], s.offs, ob, hipMemcpyHostToDevice, h->stream));
-            p = sp->rep[0]; m = sp->rep[1]; o = sp->rep[2];
+            KSCHK(sp, hipMemcpyAsync(sp->rep[0].p, s.packed, pb, hipMemcpyHostToDevice, h->stream));
+            KSCHK(sp, hipMemcpyAsync(sp->rep[1].p, s.mask, mb, hipMemcpyHostToDevice, h->stream));
+            KSCHK(sp, hipMemcpyAsync(sp->rep[2].p, s.offs, ob, hipMemcpyHostToDevice, h->stream));
+            p = sp->rep[0].p; m = sp->rep[1].p; o = sp->rep[2].p;
         }
         char *rows = (char *)d_rows_out + s.first_read * row_bytes;
         const int rc = depth ? kdf_read_depth_dev(h, p, m, n, o, (int64_t)s.n_reads, low_max, rows)
@@ -4078,15 +3867,10 @@ int kdf_spool_select_reads(kdf_spool *sp, const void *d_hit_rows, uint32_t min_d
         return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: %llu rows are beyond the 2^34 a call takes", (unsigned long long)n_rows);
     KSCHK(sp, hipSetDevice(sp->device));
     if (!sp->sel_total) KSCHK(sp, hipHostMalloc((void **)&sp->sel_total, 8, hipHostMallocDefault));
-    if (sp->sel_bytes < (n_blocks + 1) * 8) {                      // (every earlier use ended in a synchronise)
-        if (sp->sel_buf) (void)hipFree(sp->sel_buf);
-        sp->sel_buf = nullptr; sp->sel_bytes = 0;
-        const size_t want = (n_blocks + 1) * 8 + n_blocks + 4096;
-        const hipError_t e = hipMalloc(&sp->sel_buf, want);
-        if (e != hipSuccess) { (void)hipGetLastError(); sp->sel_buf = nullptr; return ks_fail(sp, KDF_ERR_NOMEM, "kdf_spool_select_reads: %zu bytes of block sums: %s", want, hipGetErrorString(e)); }
-        sp->sel_bytes = want;
-    }
-    unsigned long long *sums = (unsigned long long *)sp->sel_buf;
+    // (nothing to wait for before a free: every earlier use ended in a synchronise)
+    if (const int rc = ks_reserve(sp, *sp->sel_buf, (n_blocks + 1) * 8, (n_blocks + 1) * 8 + n_blocks + 4096, [] { return hipSuccess; },
+                                  "kdf_spool_select_reads: %zu bytes of block sums: %s")) return rc;
+    unsigned long long *sums = (unsigned long long *)sp->sel_buf->p;
     const int rows16 = (int)(((uintptr_t)d_hit_rows & 15) == 0);
     hipLaunchKernelGGL(ks_select_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, sp->stream, (const uint64_t *)d_hit_rows, n_rows, min_distinct, rows16, sums);
     hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, sp->stream, sums, n_blocks);
