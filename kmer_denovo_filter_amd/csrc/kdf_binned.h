@@ -68,9 +68,6 @@
 #ifndef KB_C_WPE
 #define KB_C_WPE 6                       // waves per SIMD the register allocation aims at
 #endif
-#ifndef KB_DUMP_EARLY
-#define KB_DUMP_EARLY 1                  // fused dump into an empty table: reserve the bucket's output range before the write-back (0: after it, as into a live table)
-#endif
 static_assert(KB_C_EPB_N % 4 == 0 && KB_C_EPB_W % 4 == 0, "kernel C resolves entries four at a time");
 static_assert(KB_C_THREADS % 256 == 0 && KB_C_THREADS <= 1024 && KB_C_THREADS_W % 256 == 0 && KB_C_THREADS_W <= KB_C_THREADS, "whole waves on every SIMD");
 #define KB_C_CT(KW) ((KW) == 2 ? KB_C_THREADS_W : KB_C_THREADS)
@@ -1260,7 +1257,8 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
                 for (int g = 0; g < G; ++g) {
                     const uint32_t ei = wbase + QSTEP * (q0 + g);
                     const uint64_t home = bklo[q0 + g] >> hsh_r;                  // the entry is the hash
-                    td[g] = ei < total && !(plan.sub_bits && (home >> plan.bucket_bits) != bucket);
+                    if constexpr (LAZY) td[g] = ei < total;                       // (the host launches it with sub_bits == 0 only)
+                    else td[g] = ei < total && !(plan.sub_bits && (home >> plan.bucket_bits) != bucket);
                     sl0[g] = (uint32_t)home & bmask;
 #pragma unroll
                     // (Measured and dropped: a mirror of slot 0 at tlo[B], so that the two slots are always adjacent and
@@ -1335,7 +1333,8 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
                 for (int g = 0; g < G; ++g) {
                     const uint32_t ei = wbase + QSTEP * (q0 + g);
                     const uint64_t home = bklo[q0 + g] >> hsh_r;                  // the entry's first word is the hash
-                    td[g] = ei < total && !(plan.sub_bits && (home >> plan.bucket_bits) != bucket);
+                    if constexpr (LAZY) td[g] = ei < total;                       // (the host launches it with sub_bits == 0 only)
+                    else td[g] = ei < total && !(plan.sub_bits && (home >> plan.bucket_bits) != bucket);
                     if (td[g] && bklo[q0 + g] == KDF_EMPTY) { failed = true; td[g] = false; }   // (2^-64: the replay path stores it)
                     sl0[g] = (uint32_t)home & bmask;
 #pragma unroll
@@ -1457,50 +1456,49 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
     // The write-back is unrolled (NIT slot pairs per thread, the last step partial) and keeps what it read from LDS in
     // registers -- the insert phase's registers are free by now.  What a wave keeps is a pair of ballots per step (even and
     // odd slots): wave-uniform, so they sit in SGPRs, and their popcounts are the wave's total.  Lane 0 of every wave takes
-    // the wave's base inside the bucket (one returning LDS atomic), ONE global atomic per bucket reserves the range in
-    // ctl->cursor between two barriers, and an entry's place is base + wave base + popcounts of the earlier masks + mbcnt
-    // of its own: a store instruction writes consecutive entries, from registers.
-    // Into an empty table (!table_nonempty: no saturation fix-up, the counts in LDS are final) the reservation comes
-    // FIRST, so that its round trip runs under the write-back stores (KB_DUMP_EARLY).
+    // the wave's base inside the bucket (one returning LDS atomic), and ONE global atomic per bucket reserves the range in
+    // ctl->cursor between two barriers.  By the first barrier every thread holds its slots in registers, so the slice in
+    // LDS is dead: under the reservation's round trip the kept slots (about a fifth of them at the bench's load) are
+    // compacted in place -- stored form and count to tlo / thi / tcnt[wave base + popcounts of the earlier masks + mbcnt],
+    // LDS writes under the slot's exec mask, nothing else -- and after the second barrier the workgroup writes the compact
+    // entries out densely: one un-mix and one full-wave store per array and 64 KEPT entries, not per 64 slots.
     constexpr uint32_t BMAX = 1u << (KB_BB_SMALL(KW) + (BIG ? 1u : 0u));     // (table_alloc: a binned table's buckets)
     constexpr uint32_t NIT = (BMAX / 2 + CT - 1) / CT;
     const uint32_t dm = plan.dump_min;
-    const bool early = KB_DUMP_EARLY && !table_nonempty;
     ulonglong2 kl[NIT], kh[KW == 2 ? NIT : 1]; uint2 cc[NIT];
     unsigned long long mx[NIT], my[NIT];
     uint32_t wb = 0; unsigned long long rsv = 0;
     // counts of this thread's slot pairs from LDS (a thread past B / 2 holds zeros: below any dump_min)
-    auto load_counts = [&]() {
 #pragma unroll
-        for (uint32_t it = 0; it < NIT; ++it) {
-            const uint32_t i = threadIdx.x + it * CT;
-            cc[it] = uint2{0u, 0u};
-            if (i < B / 2) cc[it] = ((const uint2 *)tcnt)[i];
-        }
-    };
-    auto write_back = [&]() {
+    for (uint32_t it = 0; it < NIT; ++it) {
+        const uint32_t i = threadIdx.x + it * CT;
+        cc[it] = uint2{0u, 0u};
+        if (i < B / 2) cc[it] = ((const uint2 *)tcnt)[i];
+    }
 #pragma unroll
-        for (uint32_t it = 0; it < NIT; ++it) {
-            const uint32_t i = threadIdx.x + it * CT;
-            if (i < B / 2) {
-                kl[it] = ((const ulonglong2 *)tlo)[i];
-                if constexpr (LAZY) {                                     // dump-only: the keys are wanted in registers, not in HBM
-                    if constexpr (KW == 2) kh[it] = ((const ulonglong2 *)thi)[i];
-                } else {
-                ((ulonglong2 *)(t.lo + slot0))[i] = kl[it];
-                if constexpr (KW == 2) { kh[it] = ((const ulonglong2 *)thi)[i]; ((ulonglong2 *)(t.hi + slot0))[i] = kh[it]; }
-                if (table_nonempty) {
-                    const uint2 o = ((const uint2 *)(t.cnt + slot0))[i];
-                    if (cc[it].x < o.x) cc[it].x = 0xFFFFFFFFu;
-                    if (cc[it].y < o.y) cc[it].y = 0xFFFFFFFFu;
-                }
-                ((uint2 *)(t.cnt + slot0))[i] = cc[it];
-                }
+    for (uint32_t it = 0; it < NIT; ++it) {
+        const uint32_t i = threadIdx.x + it * CT;
+        if (i < B / 2) {
+            kl[it] = ((const ulonglong2 *)tlo)[i];
+            if constexpr (LAZY) {                                     // dump-only: the keys are wanted in registers, not in HBM
+                if constexpr (KW == 2) kh[it] = ((const ulonglong2 *)thi)[i];
+            } else {
+            ((ulonglong2 *)(t.lo + slot0))[i] = kl[it];
+            if constexpr (KW == 2) { kh[it] = ((const ulonglong2 *)thi)[i]; ((ulonglong2 *)(t.hi + slot0))[i] = kh[it]; }
+            if (table_nonempty) {
+                const uint2 o = ((const uint2 *)(t.cnt + slot0))[i];
+                if (cc[it].x < o.x) cc[it].x = 0xFFFFFFFFu;
+                if (cc[it].y < o.y) cc[it].y = 0xFFFFFFFFu;
+            }
+            ((uint2 *)(t.cnt + slot0))[i] = cc[it];
             }
         }
-    };
+    }
+    if (threadIdx.x == 0 && sh_claimed)
+        atomicAdd(&ctl->distinct[(bucket % KDF_SHARDS) * 16], (unsigned long long)sh_claimed);
+    KB_T(s.trash, 39);                                        // write-back issued
     // masks, the wave's base, the bucket's reservation (issued by thread 0: its answer is awaited in `rsv` later)
-    auto reserve = [&]() {
+    {
         uint32_t wn = 0;
 #pragma unroll
         for (uint32_t it = 0; it < NIT; ++it) {
@@ -1509,7 +1507,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
         }
         // (both atomics below are issued by ONE lane: their addresses get an index 0 that went through an empty asm, which
         // hides from the compiler that they are uniform -- its wave-reduction wrapper for uniform-address atomics would
-        // wait for the answer on the spot, and the global one is to be awaited only after the write-back)
+        // wait for the answer on the spot, and the global one is to be awaited only after the compaction)
         uint32_t z = 0; asm volatile("" : "+v"(z));
         if ((threadIdx.x & 63) == 0 && wn) wb = atomicAdd(&wsum[z], wn);
         wb = __builtin_amdgcn_readfirstlane(wb);
@@ -1520,42 +1518,53 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             const uint32_t tot = wsum[0];
             if (tot) rsv = atomicAdd(&ctl->cursor + z, (unsigned long long)tot);  // (nothing kept: nothing reserved)
         }
-    };
-    load_counts();
-    if (early) reserve();
-    write_back();
-    if (threadIdx.x == 0 && sh_claimed)
-        atomicAdd(&ctl->distinct[(bucket % KDF_SHARDS) * 16], (unsigned long long)sh_claimed);
-    KB_T(s.trash, 39);                                        // write-back issued
-    if (!early) reserve();
+    }
+    // compact in place (kept <= B: it fits; tcnt[B], tcnt[B + 1] and wsum lie outside the slice)
+    {
+        uint32_t ci = wb;
+#pragma unroll
+        for (uint32_t it = 0; it < NIT; ++it) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const unsigned long long m = e ? my[it] : mx[it];
+                const uint32_t cv = e ? cc[it].y : cc[it].x;
+                if (cv >= dm) {
+                    const uint32_t idx = ci + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    tlo[idx] = e ? kl[it].y : kl[it].x;
+                    if constexpr (KW == 2) thi[idx] = e ? kh[it].y : kh[it].x;
+                    tcnt[idx] = cv;
+                }
+                ci += (uint32_t)__popcll(m);
+            }
+        }
+    }
+    KB_T(s.trash, 46);                                        // dump: compacted in LDS
     if (threadIdx.x == 0) *(unsigned long long *)(wsum + 2) = rsv;
     KB_T(s.trash, 43);                                        // dump: the reservation's round trip
     __syncthreads();
-    unsigned long long pos = *(const unsigned long long *)(wsum + 2) + wb;
+    const unsigned long long base = *(const unsigned long long *)(wsum + 2);
+    const uint32_t tot = wsum[0];
     KB_T(s.trash, 44);                                        // ... the other waves
-#pragma unroll
-    for (uint32_t it = 0; it < NIT; ++it) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const unsigned long long m = e ? my[it] : mx[it];
-            const uint32_t cv = e ? cc[it].y : cc[it].x;
-            if (cv >= dm) {
-                const unsigned long long p = pos + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if (p < s.dump_cap) {
-                    uint64_t hi = 0;
-                    if constexpr (KW == 2) hi = e ? kh[it].y : kh[it].x;
-                    s.dump_lo[p] = kdf_key_lo(e ? kl[it].y : kl[it].x, hi);
-                    if constexpr (KW == 2) if (s.dump_hi) s.dump_hi[p] = hi;
-                    if (s.dump_cnt) s.dump_cnt[p] = cv;
-                }
-            }
-            pos += (uint32_t)__popcll(m);
+    // the dense pass: entries [0, n) of the compact slice to [base, base + n) of the dump (nothing at or past dump_cap)
+    const uint32_t n = base >= s.dump_cap ? 0u : (uint32_t)(s.dump_cap - base < tot ? s.dump_cap - base : tot);
+    auto dense = [&](auto HI, auto CNT) {
+        for (uint32_t i = threadIdx.x; i < n; i += CT) {
+            uint64_t hi = 0;
+            if constexpr (KW == 2) hi = thi[i];
+            s.dump_lo[base + i] = kdf_key_lo(tlo[i], hi);
+            if constexpr (decltype(HI)::value) s.dump_hi[base + i] = hi;
+            if constexpr (decltype(CNT)::value) s.dump_cnt[base + i] = tcnt[i];
         }
-    }
+    };
+    // (the host fuses a wide dump only with a high-word array -- export_pass -- so for KW == 2 dump_hi is never null today:
+    // its test, kept as KbScratch's contract states it, is defensive and costs one uniform branch outside the loop)
+    const bool whi = KW == 2 && s.dump_hi;
+    if (s.dump_cnt) { if (whi) dense(std::true_type{}, std::true_type{}); else dense(std::false_type{}, std::true_type{}); }
+    else { if (whi) dense(std::true_type{}, std::false_type{}); else dense(std::false_type{}, std::false_type{}); }
     KB_T(s.trash, 45);                                        // dump: stores issued
     }
 #ifdef KB_TIMING
-    KB_T(s.trash, 39);                                        // write-back issued
+    KB_T(s.trash, 39);                                        // write-back issued (DUMP: stamped above already -- this adds the few cycles since stamp 45 to the same slot)
     if (threadIdx.x == 0) atomicAdd((unsigned long long *)&s.trash[8 + 40], 1ull);
 #endif
 }

@@ -1075,7 +1075,10 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
     // the dump-only flush: everything that gates the fused dump, an empty table, passes no flush has seen, and nothing that
     // would send a bucket another way (skew: the heavy-bucket split; a table about to grow).  Counts of one key slice
     // (key_parts) and counts behind a prefilter keep the ordinary flush: their dumps are followed by reads of the table.
-    const bool lazy = lazy_ok && h->opt_lazy_table && h->fuse_min && !filtered && h->lazy_empty && !skewed && !grow_first &&
+    // A table that grew since the partition has more buckets than the partition made: kernel C resolves the extra bits itself
+    // (a per-key test the dump-only instantiation leaves out: such a table takes the ordinary flush).
+    auto sub_bits_now = [&] { return (h->t.log2cap - h->t.bucket_bits) - h->pend_plan.c1 - h->pend_plan.c2; };
+    const bool lazy = lazy_ok && h->opt_lazy_table && h->fuse_min && !filtered && h->lazy_empty && !skewed && !grow_first && sub_bits_now() == 0 &&
                       h->n_pass > h->n_dumped && h->pend_plan.key_parts <= 1 && h->pf_state == PF_OFF && !(h->opt_debug_flags & 2048);
     if (grow_first) {
         while (est > 0.6 * (double)h->cap && h->t.log2cap < 40) {
@@ -1102,7 +1105,7 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
         s.dump_lo = h->fuse_lo; s.dump_hi = h->fuse_hi; s.dump_cnt = h->fuse_cnt; s.dump_cap = h->fuse_cap;
         HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor: ctl_sync reports their sum (a kdf_count_ge before this leaves its tally behind)
     }
-    plan.sub_bits = (h->t.log2cap - h->t.bucket_bits) - plan.c1 - plan.c2;       // a table that grew since the partition: more sub-buckets
+    plan.sub_bits = sub_bits_now();                   // a table that grew since the partition (just now, perhaps): more sub-buckets
     const uint64_t nb_table = 1ull << (plan.c1 + plan.c2 + plan.sub_bits);
     const size_t failed_bytes = (size_t)((nb_table + 31) / 32) * 4;
     if ((rc = eng_reserve(h, h->kb_buf[3], failed_bytes, slack_16th))) return rc;

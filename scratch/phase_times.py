@@ -31,3 +31,9 @@ with KmerEngine(k, capacity_hint=1 << 28) as e:
     print("buckets", nc, "cycles per bucket", round(tot / nc))
     for nm, v in zip(names_c, d[30:40]):
         print(f"  {nm:36s} {v / nc:9.0f} cycles  {100 * v / tot:5.1f} %")
+    names_d = ["masks + wave base", "first barrier", "reservation's answer", "second barrier", "dense stores", "compaction in LDS"]
+    tot = sum(d[30:40]) + sum(d[41:47])
+    if sum(d[41:47]):
+        print("fused dump tail (DUMP instantiations), share of the bucket's cycles")
+        for nm, v in zip(names_d, d[41:47]):
+            print(f"  {nm:36s} {v / nc:9.0f} cycles  {100 * v / tot:5.1f} %")
