@@ -120,8 +120,8 @@ __global__ __launch_bounds__(256) void kdf_depth_kernel(
     constexpr int NB = KdCfg<W>::NB;
     const int lane = threadIdx.x & 63;
     const uint64_t wave = (uint64_t)blockIdx.x * 4 + (uint64_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    const uint64_t pw = 2 * T + 4, mw = T + 2;                      // kdf_stream_words(n_bases)
+    const KdfStreamGeom g = kdf_stream_geom(n_bases);
+    const uint64_t T = g.tiles, pw = g.packed_words, mw = g.mask_words;
     const uint64_t tile_begin = wave * KD_WAVE_TILES;
     const uint64_t tile_end = tile_begin + KD_WAVE_TILES < T ? tile_begin + KD_WAVE_TILES : T;
     if (tile_begin >= tile_end) return;

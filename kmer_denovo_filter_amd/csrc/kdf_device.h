@@ -2,13 +2,28 @@
 // key type, hash, window extraction from the 2-bit stream, table views.
 // gfx950 only (wave = 64 lanes).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#if defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define KDF_HD __host__ __device__ __forceinline__
+#else                                       // a host-only source (kdf_host.cpp): the constants and the stream geometry alone
+#define KDF_HD inline
+#endif
 
 #define KDF_EMPTY   0xFFFFFFFFFFFFFFFFull
 #define KDF_PENDING 0x8000000000000000ull   // wide keys: hi word claimed, lo not yet published
 #define KDF_TILE    64                      // window starts per thread = one mask word
 #define KDF_SHARDS  64                      // sharded statistics counters
+
+// Geometry of a read stream of n_bases positions (include/kdf.h, "Read streams"): T tiles, and the buffer sizes
+// kdf_stream_words reports -- a tile reads packed words [2t, 2t + 3] and mask words [t, t + 1].
+struct KdfStreamGeom { uint64_t tiles, packed_words, mask_words; };
+KDF_HD KdfStreamGeom kdf_stream_geom(uint64_t n_bases) {
+    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    return KdfStreamGeom{T, 2 * T + 4, T + 2};
+}
+
+#if defined(__HIP__)                        // everything below is device code
 
 // ---------------------------------------------------------------------------
 // hash: fold the high half into the low half, then ONE 64-bit multiply by an odd
@@ -113,6 +128,15 @@ __device__ __forceinline__ void kdf_sat_add(uint32_t *p, uint32_t add) {
     // on a saturated counter leaves UINT32_MAX.
     uint32_t old = atomicAdd(p, add);
     if (old + add < old || old + add == 0xFFFFFFFFu) atomicMax(p, 0xFFFFFFFFu);
+}
+
+// Statistics: the wave's sum of v goes into one of KDF_SHARDS counters (one 128-byte line each) with one atomic per
+// wave.  Reached by every lane of the wave.
+__device__ __forceinline__ void kdf_shard_add(unsigned long long *counter, uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    if ((threadIdx.x & 63) == 0 && v)
+        atomicAdd(&counter[((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)v);
 }
 
 // ---- narrow keys (k <= 32) -------------------------------------------------
@@ -312,31 +336,15 @@ __device__ __forceinline__ uint64_t kdf_funnel32(uint64_t lo, uint64_t hi, int s
 // canonical key of the window starting at local position p (0..63), narrow.
 __device__ __forceinline__ uint64_t kdf_window_narrow(const uint64_t (&w)[3], int p, int k, uint64_t kmask) {
     const int word = p >> 5, sh = (p & 31) * 2;
-    uint64_t lo = w[word], hi = w[word + 1];
-    uint64_t e = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
-    e &= kmask;
-    uint64_t rc = ~e & kmask;
-    uint64_t fwd = kdf_rev2(e) >> (64 - 2 * k);
-    return fwd < rc ? fwd : rc;
+    return kdf_canon_narrow(kdf_funnel(w[word], w[word + 1], sh), k, kmask);
 }
 
 // wide: window E is 2k <= 126 bits taken from 3 consecutive words.
 __device__ __forceinline__ void kdf_window_wide(const uint64_t (&w)[4], int p, int k,
                                                 uint64_t &klo, uint64_t &khi) {
     const int word = p >> 5, sh = (p & 31) * 2;
-    uint64_t x0 = w[word], x1 = w[word + 1], x2 = (word + 2 < 4) ? w[word + 2] : 0;
-    uint64_t e0 = sh ? ((x0 >> sh) | (x1 << (64 - sh))) : x0;
-    uint64_t e1 = sh ? ((x1 >> sh) | (x2 << (64 - sh))) : x1;
-    const int hb = 2 * k - 64;                         // bits used in the high word, 2..62
-    const uint64_t hmask = (1ull << hb) - 1;
-    e1 &= hmask;
-    uint64_t rlo = ~e0, rhi = ~e1 & hmask;              // reverse complement
-    // forward: reverse the 2-bit groups of the 128-bit value, shift right by 128-2k
-    uint64_t f1 = kdf_rev2(e0), f0 = kdf_rev2(e1);     // (f1:f0) = rev2 over 128 bits
-    const int s = 128 - 2 * k;                          // 2..62
-    uint64_t flo = (f0 >> s) | (f1 << (64 - s));
-    uint64_t fhi = f1 >> s;
-    bool fw = (fhi < rhi) || (fhi == rhi && flo < rlo);
-    klo = fw ? flo : rlo;
-    khi = fw ? fhi : rhi;
+    const uint64_t x1 = w[word + 1], x2 = (word + 2 < 4) ? w[word + 2] : 0;
+    kdf_canon_wide(kdf_funnel(w[word], x1, sh), kdf_funnel(x1, x2, sh), k, klo, khi);
 }
+
+#endif  // __HIP__

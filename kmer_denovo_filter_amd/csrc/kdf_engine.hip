@@ -13,6 +13,7 @@
 
 #include "kdf.h"
 #include "kdf_device.h"
+#include "kdf_tilewalk.h"
 #include "kdf_hostutil.h"
 #include "kdf_binned.h"
 #include "kdf_merge.h"
@@ -31,59 +32,41 @@ enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2, MODE_GATED = 3 };
 // MODE_GATED: an insert-mode count behind an armed prefilter (kdf_prefilter.h).  `hit_bits` then is an INPUT: word
 // [tile] holds the tile's admitted windows, written by the gate kernel, and is ANDed into the validity bitmap.
 
-// One thread = one tile of 64 window starts.  Windows are processed in batches
+// One thread = one tile of 64 window starts (kdf_walk_tile, kdf_tilewalk.h).  Windows are processed in batches
 // of 8: the 8 home-slot key loads are issued back to back before any of them is
 // resolved, so a wave keeps 8 x 64 random HBM reads in flight.
 template <int KW, int MODE>
 __global__ __launch_bounds__(256) void kdf_stream_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid,
-    uint64_t tile0, uint64_t n_tiles, uint64_t n_bases, int k, KdfTable t, KdfCtl *ctl,
+    uint64_t n_tiles, uint64_t n_bases, int k, KdfTable t, KdfCtl *ctl,
     uint64_t *__restrict__ hit_bits)
 {
-    const uint64_t tile = tile0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = tile < tile0 + n_tiles;
+    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t claimed = 0, nwin = 0;
     bool full = false;
-    if (active) {
-        uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
-        kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
-        uint64_t valid = kdf_valid_windows(m0, m1, k);
-        if constexpr (MODE == MODE_GATED) valid &= hit_bits[tile];
-        nwin = __popcll(valid);
+    if (tile < n_tiles) {
         const bool sliced = MODE == MODE_INSERT && t.key_parts > 1;       // count only this key-space slice (KdfTable::key_parts)
         uint64_t hits = 0;
-        if (valid) {
-            constexpr int NW = KW == 1 ? 3 : 4;
-            uint64_t w[NW];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) w[i] = packed[tile * 2 + i];
-            const uint64_t kmask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-#pragma unroll
-            for (int b = 0; b < KDF_TILE; b += 8) {
-                if (((valid >> b) & 0xFF) == 0) continue;
-                uint64_t klo[8], khi[8], slot[8], cur[8];
+        uint32_t dropped = 0;
+        nwin = kdf_walk_tile<KW>(packed, invalid, tile, n_bases, k, MODE == MODE_GATED ? hit_bits[tile] : ~0ull,
+            [&](int b, uint64_t (&klo)[8], const uint64_t (&khi)[8], uint32_t vb) __attribute__((always_inline)) {
+                uint64_t slot[8], cur[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    if constexpr (KW == 1) {
-                        klo[u] = kdf_window_narrow((const uint64_t (&)[3])w, b + u, k, kmask);
-                        khi[u] = 0;
-                    } else {
-                        kdf_window_wide((const uint64_t (&)[4])w, b + u, k, klo[u], khi[u]);
-                    }
                     const uint64_t hsh = kdf_hash(klo[u], khi[u]);
                     klo[u] = hsh;                                  // from here on the key is its stored form (kdf_device.h)
                     slot[u] = kdf_home(t, hsh);
-                    if (sliced && ((valid >> (b + u)) & 1) && kdf_slice(hsh, t.key_parts) != t.key_part) { valid &= ~(1ull << (b + u)); --nwin; }
+                    if (sliced && ((vb >> u) & 1) && kdf_slice(hsh, t.key_parts) != t.key_part) { vb &= ~(1u << u); ++dropped; }
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const bool ok = (valid >> (b + u)) & 1;
+                    const bool ok = (vb >> u) & 1;
                     if constexpr (KW == 1) cur[u] = ok ? t.lo[slot[u]] : 0;
                     else cur[u] = 0;
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    const bool ok = (valid >> (b + u)) & 1;
+                    const bool ok = (vb >> u) & 1;
                     if constexpr (MODE == MODE_SCAN) {
                         if (!ok) continue;
                         uint64_t s = KW == 1 ? kdf_find_narrow(t, klo[u]) : kdf_find_wide(t, klo[u], khi[u]);
@@ -96,20 +79,13 @@ __global__ __launch_bounds__(256) void kdf_stream_kernel(
                         if (!kdf_add_wide<MODE != MODE_FILTERED>(t, ok, klo[u], khi[u], 1u, slot[u], claimed)) full = true;
                     }
                 }
-            }
-        }
+            });
+        nwin -= dropped;
         if constexpr (MODE == MODE_SCAN) hit_bits[tile] = hits;
     }
     if (full) atomicOr(&ctl->error, 1u);
-    // statistics: wave-reduce, one atomic per wave into a sharded counter
-    uint32_t c = claimed, n = nwin;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { c += __shfl_down(c, o); n += __shfl_down(n, o); }
-    if ((threadIdx.x & 63) == 0) {
-        const int shard = (blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS;
-        if (c) atomicAdd(&ctl->distinct[shard * 16], (unsigned long long)c);
-        if (n && MODE != MODE_SCAN) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);   // (a scan counts nothing: kdf_stats' windows are the count calls')
-    }
+    kdf_shard_add(ctl->distinct, claimed);
+    if constexpr (MODE != MODE_SCAN) kdf_shard_add(ctl->windows, nwin);   // (a scan counts nothing: kdf_stats' windows are the count calls')
 }
 
 // thread per key: insert with an explicit add (filter load: add = 0; rehash: add = count).
@@ -136,12 +112,7 @@ __global__ __launch_bounds__(256) void kdf_insert_keys_kernel(
         }
     }
     if (full) atomicOr(&ctl->error, 1u);
-    uint32_t c = claimed;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0 && c)
-        atomicAdd(&ctl->distinct[((blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16],
-                  (unsigned long long)c);
+    kdf_shard_add(ctl->distinct, claimed);
 }
 
 template <int KW>
@@ -436,10 +407,7 @@ __global__ __launch_bounds__(KB_THREADS) void kdf_sieve_count_kernel(
     }
     if (wq_n) drain(0, wq_n);
     if (full) atomicOr(&ctl->error, 1u);
-    uint32_t n = nwin;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if (!SCAN && lane == 0 && n) atomicAdd(&ctl->windows[((blockIdx.x * 16 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)n);
+    if constexpr (!SCAN) kdf_shard_add(ctl->windows, nwin);
 }
 
 __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
@@ -769,20 +737,37 @@ static int table_rehash(kdf_engine *h, uint32_t new_log2) {
     return KDF_OK;
 }
 
-template <int MODE>
-static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid,
-                          uint64_t tile0, uint64_t n_tiles, uint64_t *d_hits, uint64_t n_bases) {
-    const unsigned blocks = (unsigned)((n_tiles + 255) / 256);
-    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
+// The one launcher of the thread-per-tile stream kernels (kdf_tilewalk.h).  A launch holds fewer than 2^32 threads, so
+// the stream goes in pieces of at most 2^30 tiles; a piece is a stream of its own that starts at tile t0 and ends where
+// the whole stream ends.  launch(W, blocks, packed, invalid, n_tiles, n_bases, per_tile) starts the kernel of the
+// engine's key width W on one piece; per_tile: the hit / admit words of the stream, one per tile (may be NULL).
+// n_tiles may be fewer than the tiles of n_bases: the stream then goes on behind what is walked (direct_insert).
+template <typename F>
+static void launch_tiles(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles, uint64_t n_bases,
+                         uint64_t *per_tile, F &&launch) {
     by_words(h, [&](auto Wc) {
+        for (uint64_t t0 = 0; t0 < n_tiles; t0 += 1ull << 30) {
+            const uint64_t m = std::min<uint64_t>(1ull << 30, n_tiles - t0);
+            launch(Wc, (unsigned)((m + 255) / 256), d_packed + 2 * t0, d_invalid + t0, m, n_bases - t0 * KDF_TILE,
+                   per_tile ? per_tile + t0 : nullptr);
+        }
+        return 0;
+    });
+}
+
+template <int MODE>
+static void launch_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles, uint64_t n_bases,
+                          uint64_t *d_hits) {
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
+    launch_tiles(h, d_packed, d_invalid, n_tiles, n_bases, d_hits,
+                 [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *hits) {
         constexpr int W = decltype(Wc)::value;
         if constexpr (W <= 2)
             hipLaunchKernelGGL((kdf_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
-                               d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
-        else              // (n_bases: the long kernel clamps its loads to the buffers kdf_stream_words(n_bases) sizes)
+                               p, m, nt, nb, h->k, h->t, h->ctl, hits);
+        else
             hipLaunchKernelGGL((kdf_long_stream_kernel<W, MODE>), dim3(blocks), dim3(256), 0, h->stream,
-                               d_packed, d_invalid, tile0, n_tiles, n_bases, h->k, h->t, h->ctl, d_hits);
-        return 0;
+                               p, m, nt, nb, h->k, h->t, h->ctl, hits);
     });
     span.stop();
 }
@@ -1256,8 +1241,11 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
             continue;
         }
         uint64_t chunk = std::min<uint64_t>(n_tiles - tile, std::max<uint64_t>(room / KDF_TILE, 1));
-        if (admit) launch_stream<MODE_GATED>(h, d_packed, d_invalid, tile, chunk, const_cast<uint64_t *>(admit), n_bases);
-        else launch_stream<MODE_INSERT>(h, d_packed, d_invalid, tile, chunk, nullptr, n_bases);
+        // the chunk is a stream of its own that starts at tile `tile` and ends where the whole stream ends
+        const uint64_t *p = d_packed + 2 * tile, *m = d_invalid + tile;
+        const uint64_t nb = n_bases - tile * KDF_TILE;
+        if (admit) launch_stream<MODE_GATED>(h, p, m, chunk, nb, const_cast<uint64_t *>(admit) + tile);
+        else launch_stream<MODE_INSERT>(h, p, m, chunk, nb, nullptr);
         HIPCHK(h, hipGetLastError());
         bool full = false;
         int rc = ctl_sync(h, &full);
@@ -1403,7 +1391,7 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
     }
     { int rc0 = kb_flush_ring(h); if (rc0) return rc0; }           // (binned --if passes pending from earlier batches)
     h->last_path = 0;
-    launch_stream<MODE_FILTERED>(h, d_packed, d_invalid, 0, n_tiles, nullptr, n_bases);
+    launch_stream<MODE_FILTERED>(h, d_packed, d_invalid, n_tiles, n_bases, nullptr);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
@@ -1509,21 +1497,13 @@ static void src_release(kdf_engine *h, const StreamSrc &src) {
 
 // tally (admit == NULL) or gate (admit[tile] written) over a device-resident stream
 static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t *admit) {
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    by_words(h, [&](auto Wc) {
+    launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, admit,
+                 [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *adm) {
         constexpr int W = decltype(Wc)::value;
-        for (uint64_t t0 = 0; t0 < n_tiles; t0 += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
-            const uint64_t m = std::min<uint64_t>(1ull << 30, n_tiles - t0);
-            const unsigned blocks = (unsigned)((m + 255) / 256);
-            // the piece is a stream of its own that starts at tile t0 and ends where the whole stream ends
-            const uint64_t *p = d_packed + 2 * t0, *mk = d_invalid + t0;
-            const uint64_t nb = n_bases - t0 * KDF_TILE;
-#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->pf, h->pf_ctr, admit ? admit + t0 : nullptr)
-            if constexpr (W <= 2) { if (admit) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
-            else { if (admit) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
+#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->pf, h->pf_ctr, adm)
+        if constexpr (W <= 2) { if (adm) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
+        else { if (adm) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
 #undef PF_LAUNCH
-        }
-        return 0;
     });
 }
 
@@ -1586,19 +1566,11 @@ static void pf_free(kdf_engine *h) {
 static int sk_add_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (n_bases == 0) return KDF_OK;
     EvSpan span(h->timer[T_SK], h->prof, h->stream);
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    by_words(h, [&](auto Wc) {
+    launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, nullptr,
+                 [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *) {
         constexpr int W = decltype(Wc)::value;
-        for (uint64_t t0 = 0; t0 < n_tiles; t0 += 1ull << 30) {          // (a launch holds fewer than 2^32 threads)
-            const uint64_t m = std::min<uint64_t>(1ull << 30, n_tiles - t0);
-            const unsigned blocks = (unsigned)((m + 255) / 256);
-            // the piece is a stream of its own that starts at tile t0 and ends where the whole stream ends
-            const uint64_t *p = d_packed + 2 * t0, *mk = d_invalid + t0;
-            const uint64_t nb = n_bases - t0 * KDF_TILE;
-            if constexpr (W <= 2) hipLaunchKernelGGL((kdf_sk_stream_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->sk, h->sk_ctr);
-            else hipLaunchKernelGGL((kdf_sk_long_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, mk, m, nb, h->k, h->sk, h->sk_ctr);
-        }
-        return 0;
+        if constexpr (W <= 2) hipLaunchKernelGGL((kdf_sk_stream_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk, h->sk_ctr);
+        else hipLaunchKernelGGL((kdf_sk_long_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk, h->sk_ctr);
     });
     span.stop();
     HIPCHK(h, hipGetLastError());
@@ -2439,7 +2411,7 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
         }
     }
     h->last_scan_path = 0;
-    launch_stream<MODE_SCAN>(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, 0, n_tiles, (uint64_t *)d_hit_bits, n_bases);
+    launch_stream<MODE_SCAN>(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, n_bases, (uint64_t *)d_hit_bits);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }

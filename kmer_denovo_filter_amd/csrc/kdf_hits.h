@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void kh_distinct_kernel(
 {
     const int lane = threadIdx.x & 63;
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t pw = 2 * ((n_bases + KDF_TILE - 1) / KDF_TILE) + 4;    // kdf_stream_words(n_bases)
+    const uint64_t pw = kdf_stream_geom(n_bases).packed_words;
     long long r = -1;
     bool isnew = false;
     if (i < n_hits) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kdf.h"
+#include "kdf_device.h"      // KDF_TILE, kdf_stream_geom (host-only here: no device code)
 
 namespace {
 
@@ -796,9 +797,9 @@ void ParsePipe::pop() {
 extern "C" {
 
 void kdf_stream_words(uint64_t n_bases, uint64_t *packed_words, uint64_t *mask_words) {
-    const uint64_t tiles = (n_bases + 63) / 64;        // a kernel tile = 64 window starts
-    if (packed_words) *packed_words = tiles * 2 + 4;   // a tile reads packed words [2t, 2t+3]
-    if (mask_words) *mask_words = tiles + 2;           // and mask words [t, t+1]
+    const KdfStreamGeom g = kdf_stream_geom(n_bases);
+    if (packed_words) *packed_words = g.packed_words;
+    if (mask_words) *mask_words = g.mask_words;
 }
 
 int kdf_canonical(const char *kmer, int k, uint64_t *lo, uint64_t *hi) {

@@ -14,6 +14,7 @@
 // only in their upper words (w0 shared, or everything but the top word shared) collide into one home slot.
 #pragma once
 #include "kdf_device.h"
+#include "kdf_tilewalk.h"
 
 #define KDF_LONG_MIN_K 65
 #define KDF_LONG_MAX_K 201
@@ -123,119 +124,61 @@ __device__ __forceinline__ uint64_t kdf_find_long(const KdfTable &t, uint64_t h,
 }
 
 // ---- read stream -> canonical long keys -----------------------------------------------------------------------------
-// One thread = one tile of 64 window starts (as kdf_stream_kernel), so the hit bitmap of MODE_SCAN is still one
-// uint64 store per tile.  The thread rolls a forward and a reverse-complement register of W words base by base over
-// the 64 + k - 1 bases of its tile and keeps validity as the run length of valid bases since the last invalid
-// position (kdf_valid_windows assumes k <= 64).  Loads are clamped to the words kdf_stream_words(n_bases) told the
-// caller to allocate (packed [0, 2T + 4), mask [0, T + 2), T = ceil(n_bases / 64)) and positions at or past n_bases
-// are invalid, so no k reads past those buffers.  Windows are resolved NB at a time: the NB top-word loads of their
+// One thread = one tile of 64 window starts, walked by kdf_walk_tile_long (kdf_tilewalk.h), so the hit bitmap of
+// MODE_SCAN is still one uint64 store per tile.  Windows are resolved NB at a time: the NB top-word loads of their
 // home slots are issued back to back before any of them is used.
 template <int W> struct KdfLongCfg { static constexpr int NB = W == 3 ? 8 : 4; };   // (W = 4 at 8: SGPR spills in MODE_SCAN)
-
-template <int W>
-struct KdfRoll {
-    uint64_t f[W], r[W];
-    int run;
-    __device__ __forceinline__ void push(uint32_t b, bool inv, int tb) {
-        // forward: (f << 2) | b over W words, top word masked to tb bits
-#pragma unroll
-        for (int j = W - 1; j >= 1; --j) f[j] = (f[j] << 2) | (f[j - 1] >> 62);
-        f[0] = (f[0] << 2) | b;
-        f[W - 1] &= (1ull << tb) - 1;
-        // reverse complement: (r >> 2) | ((3 - b) << (2k - 2))
-#pragma unroll
-        for (int j = 0; j < W - 1; ++j) r[j] = (r[j] >> 2) | (r[j + 1] << 62);
-        r[W - 1] = (r[W - 1] >> 2) | ((uint64_t)(3u - b) << (tb - 2));
-        run = inv ? 0 : run + 1;
-    }
-    // canonical = numeric minimum (odd k: never a tie)
-    __device__ __forceinline__ void canon(uint64_t (&w)[W]) const {
-        bool lt = false, decided = false;
-#pragma unroll
-        for (int j = W - 1; j >= 0; --j) {
-            if (!decided && f[j] != r[j]) { lt = f[j] < r[j]; decided = true; }
-        }
-#pragma unroll
-        for (int j = 0; j < W; ++j) w[j] = lt ? f[j] : r[j];
-    }
-};
 
 template <int W, int MODE>
 __global__ __launch_bounds__(256) void kdf_long_stream_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid,
-    uint64_t tile0, uint64_t n_tiles, uint64_t n_bases, int k, KdfTable t, KdfCtl *ctl,
+    uint64_t n_tiles, uint64_t n_bases, int k, KdfTable t, KdfCtl *ctl,
     uint64_t *__restrict__ hit_bits)
 {
     constexpr int NB = KdfLongCfg<W>::NB;
-    const uint64_t tile = tile0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = tile < tile0 + n_tiles;
-    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    const uint64_t pw = 2 * T + 4, mw = T + 2;                   // kdf_stream_words(n_bases)
-    const int tb = 2 * k - 64 * (W - 1);                          // bits of the top word, 2 .. 62
-    uint32_t claimed = 0, nwin = 0;
+    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = tile < n_tiles;
+    uint32_t claimed = 0, dropped = 0;
     bool full = false;
     uint64_t hits = 0;
     const bool sliced = MODE == MODE_INSERT && t.key_parts > 1;
     constexpr bool INS = MODE == MODE_INSERT || MODE == MODE_GATED;       // keys are inserted (MODE_GATED: behind a prefilter,
     uint64_t adm = ~0ull;                                                 // hit_bits[tile] = the tile's admitted windows)
     if constexpr (MODE == MODE_GATED) adm = active ? hit_bits[tile] : 0ull;
-    // (inactive lanes still run the loops with every window invalid: the probe loops are wave-uniform)
-    KdfRoll<W> st;
+    uint64_t key[NB][W], h[NB], slot[NB];
+    bool ok[NB];
+    const uint32_t nwin = kdf_walk_tile_long<W, NB>(packed, invalid, tile, active, n_bases, k, adm,
+        [&](int u, const uint64_t (&kw)[W], bool okw) __attribute__((always_inline)) {
 #pragma unroll
-    for (int j = 0; j < W; ++j) { st.f[j] = 0; st.r[j] = 0; }
-    st.run = 0;
-    const uint64_t p0 = tile * KDF_TILE;
-    uint64_t cur = 0, curm = ~0ull;
-    int o = 0;                                                    // bases pushed so far (local offset)
-    auto push = [&]() {
-        if ((o & 31) == 0) { const uint64_t q = 2 * tile + (o >> 5); cur = (active && q < pw) ? packed[q] : 0; }
-        if ((o & 63) == 0) { const uint64_t q = tile + (o >> 6); curm = (active && q < mw) ? invalid[q] : ~0ull; }
-        const bool inv = (curm & 1) || p0 + (uint64_t)o >= n_bases;
-        st.push((uint32_t)(cur & 3), inv, tb);
-        cur >>= 2; curm >>= 1; ++o;
-    };
-    for (int i = 0; i < k - 1; ++i) push();
-    for (int b = 0; b < KDF_TILE; b += NB) {
-        uint64_t key[NB][W], h[NB], slot[NB], pre[NB];
-        bool ok[NB];
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            push();                                                // base o - 1 = b + u + k - 1 closes window b + u
-            st.canon(key[u]);
-            ok[u] = active && st.run >= k;
-            if constexpr (MODE == MODE_GATED) ok[u] = ok[u] && ((adm >> (b + u)) & 1);
-            h[u] = kdf_long_hash<W>(key[u]);
+            for (int j = 0; j < W; ++j) key[u][j] = kw[j];
+            h[u] = kdf_long_hash<W>(kw);
             slot[u] = kdf_home(t, h[u]);
-            if (sliced && ok[u] && kdf_slice(h[u], t.key_parts) != t.key_part) ok[u] = false;
-            else if (ok[u]) ++nwin;
-        }
+            ok[u] = okw;
+            if (sliced && okw && kdf_slice(h[u], t.key_parts) != t.key_part) { ok[u] = false; ++dropped; }
+        },
+        [&](int b) __attribute__((always_inline)) {
+            uint64_t pre[NB];
 #pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            const uint64_t *ptop = kdf_long_word<W>(t, W - 1, slot[u]);
-            pre[u] = ok[u] ? (INS ? kdf_ld(ptop) : *ptop) : KDF_EMPTY;
-        }
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            if constexpr (MODE == MODE_SCAN) {
-                if (ok[u] && pre[u] != KDF_EMPTY) {
-                    const uint64_t s = kdf_find_long<W>(t, h[u], key[u]);
-                    if (s != ~0ull && t.cnt[s] != 0) hits |= 1ull << (b + u);
-                }
-            } else {
-                if (!kdf_add_long<W, INS>(t, ok[u], h[u], key[u], 1u, slot[u], pre[u], true, claimed)) full = true;
+            for (int u = 0; u < NB; ++u) {
+                const uint64_t *ptop = kdf_long_word<W>(t, W - 1, slot[u]);
+                pre[u] = ok[u] ? (INS ? kdf_ld(ptop) : *ptop) : KDF_EMPTY;
             }
-        }
-    }
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                if constexpr (MODE == MODE_SCAN) {
+                    if (ok[u] && pre[u] != KDF_EMPTY) {
+                        const uint64_t s = kdf_find_long<W>(t, h[u], key[u]);
+                        if (s != ~0ull && t.cnt[s] != 0) hits |= 1ull << (b + u);
+                    }
+                } else {
+                    if (!kdf_add_long<W, INS>(t, ok[u], h[u], key[u], 1u, slot[u], pre[u], true, claimed)) full = true;
+                }
+            }
+        });
     if (MODE == MODE_SCAN && active) hit_bits[tile] = hits;
     if (full) atomicOr(&ctl->error, 1u);
-    uint32_t c = claimed, n = nwin;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { c += __shfl_down(c, off); n += __shfl_down(n, off); }
-    if ((threadIdx.x & 63) == 0) {
-        const int shard = (blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS;
-        if (c) atomicAdd(&ctl->distinct[shard * 16], (unsigned long long)c);
-        if (n && MODE != MODE_SCAN) atomicAdd(&ctl->windows[shard * 16], (unsigned long long)n);   // (a scan counts nothing)
-    }
+    kdf_shard_add(ctl->distinct, claimed);
+    if constexpr (MODE != MODE_SCAN) kdf_shard_add(ctl->windows, nwin - dropped);   // (a scan counts nothing)
 }
 
 // ---- key kernels --------------------------------------------------------------------------------------------------
@@ -275,11 +218,7 @@ __global__ __launch_bounds__(256) void kdf_long_insert_kernel(
         if (!kdf_add_long<W, true>(t, todo, h, w, a, slot, 0, false, claimed)) full = true;
     }
     if (full) atomicOr(&ctl->error, 1u);
-    uint32_t c = claimed;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-    if ((threadIdx.x & 63) == 0 && c)
-        atomicAdd(&ctl->distinct[((blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)c);
+    kdf_shard_add(ctl->distinct, claimed);
 }
 
 template <int W>

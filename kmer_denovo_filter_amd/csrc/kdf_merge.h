@@ -396,8 +396,5 @@ __global__ __launch_bounds__(256) void km_insert_guarded_kernel(KdfTable t, KmSe
         }
     }
     if (full) atomicOr(&ctl->error, 1u);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) claimed += __shfl_down(claimed, o);
-    if ((threadIdx.x & 63) == 0 && claimed)
-        atomicAdd(&ctl->distinct[((blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)claimed);
+    kdf_shard_add(ctl->distinct, claimed);
 }

@@ -1,6 +1,6 @@
 // kdf_prefilter.h -- the counting sieve of the two-pass count (include/kdf.h, "two-pass counting").
 //
-// Pass 1 (TALLY) walks the read stream exactly like the direct count kernel and bumps one saturating cell per valid
+// Pass 1 (TALLY) walks the read stream tile by tile (kdf_tilewalk.h) and bumps one saturating cell per valid
 // window; pass 2 (GATE) walks the stream the count is about to take and writes, per tile of 64 window starts, one
 // 64-bit "admitted" word (bit i: window i is valid and its cell reads >= min_count) which the count kernels AND into
 // their validity bitmap.  The sieve is immutable between kdf_prefilter_arm and kdf_prefilter_drop, so the gate may run
@@ -49,18 +49,9 @@ __device__ __forceinline__ bool kdf_pf_admits(const KdfPrefilter &pf, uint64_t c
     return (uint32_t)__popc((uint32_t)(cur >> sh) & 7u) >= pf.min_count;
 }
 
-// wave-reduced window count into a sharded counter (one 128-byte line per shard)
-__device__ __forceinline__ void kdf_pf_add_windows(unsigned long long *windows, uint32_t nwin) {
-    uint32_t n = nwin;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-    if ((threadIdx.x & 63) == 0 && n)
-        atomicAdd(&windows[((blockIdx.x * 4 + (threadIdx.x >> 6)) % KDF_SHARDS) * 16], (unsigned long long)n);
-}
-
-// k <= 63.  One thread = one tile of 64 window starts, the stream read as kdf_stream_kernel reads it (positions at or
-// past n_bases invalid); windows are taken 8 at a time so that 8 sieve words are in flight per
-// lane.  GATE = false: tally (windows: sharded counter of tallied windows).  GATE = true: admit[tile] is written.
+// k <= 63.  One thread = one tile of 64 window starts (kdf_walk_tile, kdf_tilewalk.h); windows are taken 8 at a time so
+// that 8 sieve words are in flight per lane.  GATE = false: tally (windows: sharded counter of tallied windows).
+// GATE = true: admit[tile] is written.
 template <int KW, bool GATE>
 __global__ __launch_bounds__(256) void kdf_pf_stream_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
@@ -69,44 +60,29 @@ __global__ __launch_bounds__(256) void kdf_pf_stream_kernel(
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t nwin = 0;
     if (tile < n_tiles) {
-        uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
-        kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
-        const uint64_t valid = kdf_valid_windows(m0, m1, k);
-        nwin = __popcll(valid);
         uint64_t adm = 0;
-        if (valid) {
-            constexpr int NW = KW == 1 ? 3 : 4;
-            uint64_t w[NW];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) w[i] = packed[tile * 2 + i];
-            const uint64_t kmask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-#pragma unroll
-            for (int b = 0; b < KDF_TILE; b += 8) {
-                if (((valid >> b) & 0xFF) == 0) continue;
+        nwin = kdf_walk_tile<KW>(packed, invalid, tile, n_bases, k, ~0ull,
+            [&](int b, const uint64_t (&klo)[8], const uint64_t (&khi)[8], uint32_t vb) __attribute__((always_inline)) {
                 uint64_t word[8], cur[8]; uint32_t sh[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    uint64_t klo, khi = 0;
-                    if constexpr (KW == 1) klo = kdf_window_narrow((const uint64_t (&)[3])w, b + u, k, kmask);
-                    else kdf_window_wide((const uint64_t (&)[4])w, b + u, k, klo, khi);
-                    kdf_pf_locate(pf, kdf_hash(klo, khi), word[u], sh[u]);
-                }
+                for (int u = 0; u < 8; ++u) kdf_pf_locate(pf, kdf_hash(klo[u], khi[u]), word[u], sh[u]);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) cur[u] = ((valid >> (b + u)) & 1) ? pf.words[word[u]] : 0ull;
+                for (int u = 0; u < 8; ++u) cur[u] = ((vb >> u) & 1) ? pf.words[word[u]] : 0ull;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    if (!((valid >> (b + u)) & 1)) continue;
+                    if (!((vb >> u) & 1)) continue;
                     if constexpr (GATE) { if (kdf_pf_admits(pf, cur[u], sh[u])) adm |= 1ull << (b + u); }
                     else kdf_pf_bump(&pf.words[word[u]], sh[u], cur[u]);
                 }
-            }
-        }
+            });
         if constexpr (GATE) admit[tile] = adm;
     }
-    if constexpr (!GATE) kdf_pf_add_windows(windows, nwin);
+    if constexpr (!GATE) kdf_shard_add(windows, nwin);
 }
 
-// long keys (odd k 65..201): the rolling registers and clamped loads of kdf_long_stream_kernel
+// long keys (odd k 65..201), 4 sieve words in flight per lane.  The kernel keeps a reader of its own, the loop of
+// kdf_walk_tile_long (kdf_tilewalk.h): over the walker the k = 101 tally of 10 M x 150 bp reads measured 24.10 ms
+// against 22.99 ms (profiles/tile_walk_bench.txt, second table).
 template <int W, bool GATE>
 __global__ __launch_bounds__(256) void kdf_pf_long_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
@@ -115,8 +91,8 @@ __global__ __launch_bounds__(256) void kdf_pf_long_kernel(
     constexpr int NB = 4;
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = tile < n_tiles;
-    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    const uint64_t pw = 2 * T + 4, mw = T + 2;                   // kdf_stream_words(n_bases)
+    const KdfStreamGeom g = kdf_stream_geom(n_bases);
+    const uint64_t pw = g.packed_words, mw = g.mask_words;
     const int tb = 2 * k - 64 * (W - 1);
     uint32_t nwin = 0;
     uint64_t adm = 0;
@@ -157,7 +133,7 @@ __global__ __launch_bounds__(256) void kdf_pf_long_kernel(
         }
     }
     if constexpr (GATE) { if (active) admit[tile] = adm; }
-    else kdf_pf_add_windows(windows, nwin);
+    else kdf_shard_add(windows, nwin);
 }
 
 // cells by value: out3 += {cells reading >= 1, >= 2, 3} (the planes are nested: B is only set after A, C after B)

@@ -1,8 +1,7 @@
 // kdf_sketch.h -- the distinct k-mer sketch (include/kdf.h, "distinct k-mer sketch"): a HyperLogLog over the canonical
 // k-mers of read streams, so that tables, key slices and owner tables are sized from the reads before any key is stored.
 //
-// A pure STREAM kernel: it walks the read stream exactly like the prefilter's tally (kdf_prefilter.h) -- the direct
-// window extraction for k <= 63, the rolling registers of kdf_long.h for long keys -- and touches no table.  Per valid
+// A pure STREAM kernel: it walks the read stream tile by tile (kdf_tilewalk.h) and touches no table.  Per valid
 // window: the key's 64-bit stored form h, the finaliser g (below), register j = top p bits of g, rank r = 1 + leading
 // zeros of the bits behind them; reg[j] = max(reg[j], r).
 //
@@ -14,7 +13,6 @@
 #pragma once
 #include "kdf_device.h"
 #include "kdf_long.h"
-#include "kdf_prefilter.h"     // kdf_pf_add_windows: the wave-reduced sharded window counter
 
 #include <math.h>
 
@@ -48,8 +46,8 @@ __device__ __forceinline__ void kdf_sk_locate(uint32_t p, uint64_t g, uint32_t &
     r = 1u + (uint32_t)__clzll((long long)((g << p) | (1ull << (p - 1))));   // the guard bit: 1 <= r <= 65 - p
 }
 
-// k <= 63.  One thread = one tile of 64 window starts, the stream read as kdf_pf_stream_kernel reads it (positions at or
-// past n_bases invalid); windows are taken 8 at a time so that 8 cell loads are in flight per lane.
+// k <= 63.  One thread = one tile of 64 window starts (kdf_walk_tile, kdf_tilewalk.h); windows are taken 8 at a time so
+// that 8 cell loads are in flight per lane.
 template <int KW>
 __global__ __launch_bounds__(256) void kdf_sk_stream_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
@@ -58,38 +56,24 @@ __global__ __launch_bounds__(256) void kdf_sk_stream_kernel(
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t nwin = 0;
     if (tile < n_tiles) {
-        uint64_t m0 = invalid[tile], m1 = invalid[tile + 1];
-        kdf_mask_past_end(n_bases - tile * KDF_TILE, m0, m1);          // (tile < ceil(n_bases / 64): the host's n_tiles)
-        const uint64_t valid = kdf_valid_windows(m0, m1, k);
-        nwin = __popcll(valid);
-        if (valid) {
-            constexpr int NW = KW == 1 ? 3 : 4;
-            uint64_t w[NW];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) w[i] = packed[tile * 2 + i];
-            const uint64_t kmask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-#pragma unroll
-            for (int b = 0; b < KDF_TILE; b += 8) {
-                if (((valid >> b) & 0xFF) == 0) continue;
+        nwin = kdf_walk_tile<KW>(packed, invalid, tile, n_bases, k, ~0ull,
+            [&](int, const uint64_t (&klo)[8], const uint64_t (&khi)[8], uint32_t vb) __attribute__((always_inline)) {
                 uint32_t j[8], r[8], cur[8];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
-                    uint64_t klo, khi = 0, g;
-                    if constexpr (KW == 1) { klo = kdf_window_narrow((const uint64_t (&)[3])w, b + u, k, kmask); g = kdf_sketch_g(kdf_mix64(klo)); }
-                    else { kdf_window_wide((const uint64_t (&)[4])w, b + u, k, klo, khi); g = kdf_sketch_g_wide(kdf_hash(klo, khi), khi); }
-                    kdf_sk_locate(sk.p, g, j[u], r[u]);
+                    const uint64_t h = kdf_hash(klo[u], khi[u]);
+                    kdf_sk_locate(sk.p, KW == 1 ? kdf_sketch_g(h) : kdf_sketch_g_wide(h, khi[u]), j[u], r[u]);
                 }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) cur[u] = ((valid >> (b + u)) & 1) ? sk.cells[j[u]] : 0xFFFFFFFFu;
+                for (int u = 0; u < 8; ++u) cur[u] = ((vb >> u) & 1) ? sk.cells[j[u]] : 0xFFFFFFFFu;   // (invalid: nothing is above it)
 #pragma unroll
                 for (int u = 0; u < 8; ++u) if (r[u] > cur[u]) atomicMax(&sk.cells[j[u]], r[u]);
-            }
-        }
+            });
     }
-    kdf_pf_add_windows(windows, nwin);
+    kdf_shard_add(windows, nwin);
 }
 
-// long keys (odd k 65..201): the rolling registers and clamped loads of kdf_pf_long_kernel
+// long keys (odd k 65..201): kdf_walk_tile_long, 4 cell loads in flight per lane
 template <int W>
 __global__ __launch_bounds__(256) void kdf_sk_long_kernel(
     const uint64_t *__restrict__ packed, const uint64_t *__restrict__ invalid, uint64_t n_tiles, uint64_t n_bases, int k,
@@ -97,44 +81,19 @@ __global__ __launch_bounds__(256) void kdf_sk_long_kernel(
 {
     constexpr int NB = 4;
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool active = tile < n_tiles;
-    const uint64_t T = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    const uint64_t pw = 2 * T + 4, mw = T + 2;                   // kdf_stream_words(n_bases)
-    const int tb = 2 * k - 64 * (W - 1);
-    uint32_t nwin = 0;
-    KdfRoll<W> st;
-#pragma unroll
-    for (int j = 0; j < W; ++j) { st.f[j] = 0; st.r[j] = 0; }
-    st.run = 0;
-    const uint64_t p0 = tile * KDF_TILE;
-    uint64_t curw = 0, curm = ~0ull;
-    int o = 0;
-    auto push = [&]() {
-        if ((o & 31) == 0) { const uint64_t q = 2 * tile + (o >> 5); curw = (active && q < pw) ? packed[q] : 0; }
-        if ((o & 63) == 0) { const uint64_t q = tile + (o >> 6); curm = (active && q < mw) ? invalid[q] : ~0ull; }
-        const bool inv = (curm & 1) || p0 + (uint64_t)o >= n_bases;
-        st.push((uint32_t)(curw & 3), inv, tb);
-        curw >>= 2; curm >>= 1; ++o;
-    };
-    for (int i = 0; i < k - 1; ++i) push();
-    for (int b = 0; b < KDF_TILE; b += NB) {
-        uint32_t j[NB], r[NB], cur[NB];
-#pragma unroll
-        for (int u = 0; u < NB; ++u) {
-            uint64_t key[W];
-            push();                                                // base o - 1 = b + u + k - 1 closes window b + u
-            st.canon(key);
-            const bool ok = active && st.run >= k;
-            if (ok) ++nwin;
+    uint32_t j[NB], r[NB], cur[NB];
+    const uint32_t nwin = kdf_walk_tile_long<W, NB>(packed, invalid, tile, tile < n_tiles, n_bases, k, ~0ull,
+        [&](int u, const uint64_t (&key)[W], bool ok) __attribute__((always_inline)) {
             kdf_sk_locate(sk.p, kdf_sketch_g(kdf_long_hash<W>(key)), j[u], r[u]);
             if (!ok) r[u] = 0;                                     // (rank 0 raises nothing)
-        }
+        },
+        [&](int) __attribute__((always_inline)) {
 #pragma unroll
-        for (int u = 0; u < NB; ++u) cur[u] = r[u] ? sk.cells[j[u]] : 0xFFFFFFFFu;
+            for (int u = 0; u < NB; ++u) cur[u] = r[u] ? sk.cells[j[u]] : 0xFFFFFFFFu;
 #pragma unroll
-        for (int u = 0; u < NB; ++u) if (r[u] > cur[u]) atomicMax(&sk.cells[j[u]], r[u]);
-    }
-    kdf_pf_add_windows(windows, nwin);
+            for (int u = 0; u < NB; ++u) if (r[u] > cur[u]) atomicMax(&sk.cells[j[u]], r[u]);
+        });
+    kdf_shard_add(windows, nwin);
 }
 
 // cells -> one byte per register (the exported form)
