@@ -158,7 +158,8 @@ int kdf_flush(kdf_engine *h);
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
  *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
  *            "hits_us" / "hits_passes" (the kh_* kernels of kdf_read_hits* / kdf_hit_list* under kdf_profile, the scan kernel
- *            not included; one pass per call); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
+ *            not included; one pass per call); "coverage_us" / "coverage_passes" (the kc_* kernels of kdf_hit_coverage* /
+ *            kdf_coverage_list* under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
 int kdf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
@@ -490,6 +491,80 @@ int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, co
 int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets,
                  int64_t n_reads, uint64_t *positions_out, int64_t *reads_out, uint64_t cap, uint64_t *n_out);
 
+/* ---------------------------------------- hits in reference coordinates ---- */
+
+/* Module 3's step from "which windows of a read hit" to "which reference positions carry the hit k-mers": the two
+ * per-position sums behind .kmer_coverage.bedgraph and .read_coverage.bed (core/bam_scanner.py:97-117
+ * _collect_kmer_ref_positions, summed over the informative reads, discovery/pipeline.py:840-860).  Inputs: a hit mask
+ * (kdf_scan_reads* / kdf_read_hits*), the read offsets of the stream, per read a linear reference start and its CIGAR.
+ * kmer_cov and read_cov are two arrays of `span` uint32 words that the CALLER owns and zeroes.
+ *   Hits.   A hit is a set bit p of the mask with p + k <= n_bases (k: the engine's).  Bits at and past that, and
+ *           whatever the words hold past n_bases, are ignored (the masking of kdf_hit_list*).  A hit belongs to read r
+ *           by the rule of kdf_read_hits*: offsets[r] <= p < offsets[r + 1]; a hit that belongs to no read
+ *           contributes nothing.
+ *   Depth.  For a read r and a stream position q with offsets[r] <= q < offsets[r + 1], depth(r, q) is the number of
+ *           hits p of read r with p <= q < p + k.  Hits of one read never add depth to a position of another read,
+ *           however close the reads lie in the stream; a window that runs past its read's end is cut there.
+ *   CIGAR.  cigar[cigar_offsets[r] .. cigar_offsets[r + 1]) are read r's operations in BAM encoding (len << 4 | op),
+ *           exactly what kdf_reader_last_aux hands out.  Walk them with (qc, rc) = (0, 0).  For M, = and X (op 0, 7,
+ *           8): query index c = q - offsets[r] is ALIGNED at reference offset d = rc + (c - qc) iff qc <= c < qc + len;
+ *           then both counters advance by len.  I and S (1, 4) advance qc.  D and N (2, 3) advance rc.  H, P and the
+ *           codes 9..15 advance nothing.  A query index that no aligned operation covers has no reference position:
+ *           inserted and clipped bases, a read longer than its CIGAR consumes, an empty CIGAR.
+ *   Sums.   A read with ref_start[r] < 0 is skipped entirely (unmapped, not selected, de-duplicated by the caller).
+ *           Otherwise, for every aligned q of the read with depth(r, q) > 0 and g = ref_start[r] + d < span:
+ *           kmer_cov[g] += depth(r, q) and read_cov[g] += 1.  A g >= span is dropped: not wrapped, nothing written.
+ *           The call only ADDS, modulo 2^32, so several batches accumulate into one pair of arrays.  ref_start is a
+ *           linear coordinate the caller defines: contig offset + leftmost reference base (kdf_reader_ref_length).
+ *   - all sums are integer: bit-identical from run to run, between the host and device forms, and between one call and
+ *     the same reads split over several calls.
+ *   - work is linear in hits x k plus the CIGAR operations of the reads that hold hits; exact for a read of any length
+ *     (a 20 kb read with hundreds of operations, a contig as one read): the operation of a query index is found by
+ *     binary search in per-operation prefix sums, never by a walk per hit.  Scratch, owned by the engine and kept
+ *     between calls: 8 bytes per hit, 16 per CIGAR operation (KDF_ERR_NOMEM when it does not fit).
+ *   - the table is not touched (no flush), as for kdf_hit_list*; every key width is accepted, only k matters.
+ *   - n_reads == 0 and n_bases == 0 are KDF_OK and add nothing.
+ *   - device form: offsets, cigar_offsets and ref_start are preconditions, but whatever they hold no write lands
+ *     outside the two span-word arrays and no CIGAR word outside [0, n_cigar) is read (indices are clamped).  The call
+ *     synchronises the engine's stream once (it learns the number of hits to size its scratch); the sums are complete
+ *     in stream order when it returns.  n_reads < 0 is KDF_ERR_INVALID.
+ *   - host form: n_reads < 0, bad read offsets (negative, decreasing), cigar_offsets[0] != 0, decreasing
+ *     cigar_offsets and a last cigar_offsets entry != n_cigar are KDF_ERR_INVALID before any device work; the arrays
+ *     are then untouched.
+ *   - under kdf_profile(h, 1) the kernels of kdf_hit_coverage* and kdf_coverage_list* are timed with HIP events:
+ *     stats "coverage_us" / "coverage_passes" (one pass per call that launches). */
+int kdf_hit_coverage_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets,
+                         int64_t n_reads, const void *d_ref_start, const void *d_cigar, uint64_t n_cigar,
+                         const void *d_cigar_offsets, void *d_kmer_cov, void *d_read_cov, uint64_t span);
+int kdf_hit_coverage(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets,
+                     int64_t n_reads, const int64_t *ref_start, const uint32_t *cigar, uint64_t n_cigar,
+                     const int64_t *cigar_offsets, uint32_t *kmer_cov, uint32_t *read_cov, uint64_t span);
+
+/* The covered positions as a list: the g in [first, first + n) with read_cov[g] >= max(min_reads, 1), ASCENDING (what
+ * the bedGraph writer needs: no sort anywhere): pos_out[e] = g (uint64), kmer_out[e] = kmer_cov[g], read_out[e] =
+ * read_cov[g] (uint32; either may be NULL, and kmer_cov may be NULL when kmer_out is).  first + n must not exceed the
+ * arrays' length.  *n_out = number of such positions, always set; at most `cap` entries are written, and when *n_out
+ * exceeds cap the call returns KDF_ERR_INVALID (the convention of kdf_hit_list_dev).  n == 0 is KDF_OK.  An
+ * order-preserving compaction (count per block, scan, write).  Both forms synchronise the engine's stream. */
+int kdf_coverage_list_dev(kdf_engine *h, const void *d_kmer_cov, const void *d_read_cov, uint64_t first, uint64_t n,
+                          uint32_t min_reads, void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap,
+                          uint64_t *n_out);
+int kdf_coverage_list(kdf_engine *h, const uint32_t *kmer_cov, const uint32_t *read_cov, uint64_t first, uint64_t n,
+                      uint32_t min_reads, uint64_t *pos_out, uint32_t *kmer_out, uint32_t *read_out, uint64_t cap,
+                      uint64_t *n_out);
+
+/* The canonical keys of listed windows (unique_in_read, core/bam_scanner.py:435-442, without decoding a read to a
+ * string): row e of keys_out, W = kdf_key_words(k) uint64 words, word 0 least significant, for every key width, is the
+ * canonical key of window [positions[e], positions[e] + k) of the packed stream.  A position with p + k > n_bases gets
+ * a row of all-ones words, which is never a canonical key.  Whether the window is VALID is the caller's business:
+ * positions come from a hit list, and hits are valid windows.  The table is not touched.  The device form (packed of
+ * the kdf_stream_words(n_bases) size, positions uint64[n], keys uint64[n x W]) runs in stream order and does not
+ * synchronise; the host form reads ceil(n_bases / 32) packed words. */
+int kdf_hit_keys_dev(kdf_engine *h, const void *d_packed, uint64_t n_bases, const void *d_positions, uint64_t n,
+                     void *d_keys_out);
+int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const uint64_t *positions, uint64_t n,
+                 uint64_t *keys_out);
+
 /* ------------------------------------------- count profile of a stream ---- */
 
 /* `jellyfish query idx -s reads.fa` over a whole read stream: counts_out[i], 0 <= i < n_bases, is the stored count of
@@ -612,6 +687,9 @@ int kdf_reader_last_ordinals(kdf_reader *r, const uint64_t **ordinals);
 /* Reference sequence names of a BAM reader (header order = ref_id). */
 int kdf_reader_ref_count(kdf_reader *r);
 const char *kdf_reader_ref_name(kdf_reader *r, int i);
+/* Reference length of sequence i of a BAM reader's header (l_ref), -1 for a bad index: the contig offsets of
+ * kdf_hit_coverage's linear coordinate are their running sum. */
+int kdf_reader_ref_length(kdf_reader *r, int i);
 void kdf_reader_close(kdf_reader *r);
 const char *kdf_reader_error(const kdf_reader *r);
 

@@ -64,6 +64,13 @@ SYMBOLS = [
     ("kdf_read_hits", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P]),
     ("kdf_hit_list_dev", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_hit_list", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    # hits in reference coordinates
+    ("kdf_hit_coverage_dev", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, _P, _P, _P, c_uint64]),
+    ("kdf_hit_coverage", c_int, [_P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, _P, _P, _P, c_uint64]),
+    ("kdf_coverage_list_dev", c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_coverage_list", c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_hit_keys_dev", c_int, [_P, _P, c_uint64, _P, c_uint64, _P]),
+    ("kdf_hit_keys", c_int, [_P, _P, c_uint64, _P, c_uint64, _P]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),
@@ -87,6 +94,7 @@ SYMBOLS = [
     ("kdf_bam_write_subset", c_int, [c_char_p, c_char_p, _P, c_uint64, _P, _P, c_int, c_int, POINTER(c_uint64)]),
     ("kdf_reader_ref_count", c_int, [_P]),
     ("kdf_reader_ref_name", c_char_p, [_P, c_int]),
+    ("kdf_reader_ref_length", c_int, [_P, c_int]),
     ("kdf_reader_close", None, [_P]),
     ("kdf_reader_error", c_char_p, [_P]),
     # long keys (odd k 65..201): n x W row-major words

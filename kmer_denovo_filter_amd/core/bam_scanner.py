@@ -26,7 +26,7 @@ from .. import jf_io
 from .._native import KDF_ERR_NOMEM, KdfError
 from ..engine import KmerEngine, mirror_engine, hit_positions
 from ..kmer_fasta import read_kmer_fasta_keys
-from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys
+from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys, stream_words
 
 logger = logging.getLogger(__name__)
 
@@ -259,6 +259,140 @@ def _decode_read(batch, r):
     return chars.tobytes().decode()
 
 
+class _DeviceCoverage:
+    """``KDF_DEVICE_COVERAGE=1``: Module 3's two coverage sums kept on the device.  Two uint32 accumulators of the
+    genome's linear length (contig offsets = running sum of the header's reference lengths); per batch the hit mask,
+    the read offsets and the CIGAR arrays stay in HBM and ``hit_coverage_dev`` adds the contributing reads; the per-read
+    k-mer sets come from ``hit_keys_dev`` (one ``keys_to_kmers`` per distinct key of a read, no read is decoded).  The
+    host decides WHICH reads contribute, because it has the names: kept by ``min_dk``, mapped, and the first kept
+    record with its (ref_id, name, is_supplementary) in file order -- the reference's de-duplication inside a contig's
+    task; coverage is a commutative sum, so the order of the tasks does not matter."""
+
+    def __init__(self, eng: KmerEngine, ref_lengths):
+        import torch
+        self.eng = eng
+        self.torch = torch
+        self.dev = torch.device("cuda", eng.device)
+        self.contig_off = np.concatenate(([0], np.cumsum(np.asarray(ref_lengths, dtype=np.int64)))).astype(np.int64)
+        self.span = int(self.contig_off[-1])
+        self.kcov = torch.zeros(max(self.span, 1), dtype=torch.int32, device=self.dev)
+        self.rcov = torch.zeros(max(self.span, 1), dtype=torch.int32, device=self.dev)
+        self.seen = set()
+
+    @staticmethod
+    def fits(eng: KmerEngine, ref_lengths) -> bool:
+        """both accumulators within half of the free HBM"""
+        from ctypes import byref, c_uint64
+        from .. import _native
+        free, total = c_uint64(0), c_uint64(0)
+        _native.check(_native.load().kdf_device_memory(eng.device, byref(free), byref(total)), None)
+        need = 8 * int(sum(int(x) for x in ref_lengths))
+        if need > free.value // 2:
+            logger.info("KDF_DEVICE_COVERAGE: two accumulators of %d bytes do not fit half of the %d free bytes of HBM; "
+                        "coverage is summed on the host", need, free.value)
+            return False
+        return True
+
+    def _up(self, a, dt):
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.nbytes % 8:                                                 # (uint32 arrays of odd length)
+            a = np.concatenate((a, np.zeros(1, dt)))
+        if a.nbytes == 0:
+            a = np.zeros(1, np.int64)
+        return self.torch.from_numpy(a.view(np.int64)).to(self.dev)
+
+    def batch(self, batch, min_dk: int, k: int):
+        """-> (keep int64[m], hit offsets of each kept read relative to its start, k-mer set of each kept read); the
+        contributing reads among them are added to the accumulators."""
+        from ..reads import keys_to_kmers
+        eng, torch = self.eng, self.torch
+        n, nr = int(batch.n_bases), int(batch.n_reads)
+        offs = np.asarray(batch.offsets, dtype=np.int64)
+        pw, mw = stream_words(n)
+        dp, dm, do = self._up(batch.packed[:pw], np.uint64), self._up(batch.invalid[:mw], np.uint64), self._up(offs, np.int64)
+        dbits = torch.empty((n + 63) // 64, dtype=torch.int64, device=self.dev)
+        drows = torch.empty(nr, dtype=torch.int64, device=self.dev)          # one row = 2 x uint32
+        torch.cuda.synchronize(self.dev)
+        eng.read_hits_dev(dp.data_ptr(), dm.data_ptr(), n, do.data_ptr(), nr, dbits.data_ptr(), drows.data_ptr())
+        eng.synchronize()
+        rows = drows.cpu().numpy().view(np.uint32).reshape(nr, 2)
+        keep = np.flatnonzero(rows[:, 1] >= min_dk) if min_dk > 0 else np.arange(nr)
+        # the hit list and the key of every hit: the list stays on the device for hit_keys_dev
+        cap = int(rows[:, 0].sum(dtype=np.int64))
+        while True:
+            dpos = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev)
+            torch.cuda.synchronize(self.dev)
+            rc, got = eng._hit_list_dev(dbits.data_ptr(), n, None, 0, dpos.data_ptr(), None, cap)
+            if got <= cap:
+                eng._ck(rc)
+                break
+            cap = got
+        W = eng.key_words
+        dkeys = torch.empty(max(got, 1) * W, dtype=torch.int64, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        eng.hit_keys_dev(dp.data_ptr(), n, dpos.data_ptr(), got, dkeys.data_ptr())
+        eng.synchronize()
+        pos = dpos[:got].cpu().numpy()
+        key_rows = dkeys[:got * W].cpu().numpy().view(np.uint64).reshape(got, W)
+        lo = np.searchsorted(pos, offs[keep], side="left")
+        hi = np.searchsorted(pos, offs[keep + 1] - 1, side="left") if len(keep) else lo
+        hit_idx, kmers = [], []
+        for a, b, s in zip(lo.tolist(), hi.tolist(), offs[keep].tolist()):
+            hit_idx.append(pos[a:b] - s)
+            if a == b:
+                kmers.append(set())
+                continue
+            u = np.unique(key_rows[a:b], axis=0)
+            kmers.append(set(keys_to_kmers(u if W > 2 else np.ascontiguousarray(u[:, 0]),
+                                           np.ascontiguousarray(u[:, 1]) if W == 2 else None, k)))
+        # which reads contribute
+        ref_start = np.full(nr, -1, np.int64)
+        for r in keep.tolist():
+            flag, ref_id = int(batch.flags[r]), int(batch.ref_ids[r])
+            key = (ref_id, batch.name(r), bool(flag & 0x800))
+            if key in self.seen:
+                continue
+            self.seen.add(key)
+            if flag & 0x4 or ref_id < 0 or ref_id + 1 >= len(self.contig_off):
+                continue
+            ref_start[r] = int(self.contig_off[ref_id]) + int(batch.positions[r])
+        if (ref_start >= 0).any() and self.span:
+            drs, dcg, dco = self._up(ref_start, np.int64), self._up(batch.cigar, np.uint32), self._up(batch.cigar_offsets, np.int64)
+            torch.cuda.synchronize(self.dev)
+            eng.hit_coverage_dev(dbits.data_ptr(), n, do.data_ptr(), nr, drs.data_ptr(), dcg.data_ptr(), len(batch.cigar),
+                                 dco.data_ptr(), self.kcov.data_ptr(), self.rcov.data_ptr(), self.span)
+            eng.synchronize()
+        return keep, hit_idx, kmers
+
+    def counters(self, refs):
+        """the ascending list of covered positions -> ({chrom: Counter position -> hit k-mers}, {chrom: Counter
+        position -> reads}) in contig coordinates"""
+        import collections
+        eng, torch = self.eng, self.torch
+        kc, rc = collections.defaultdict(collections.Counter), collections.defaultdict(collections.Counter)
+        if not self.span:
+            return kc, rc
+        torch.cuda.synchronize(self.dev)
+        _, m = eng._coverage_list_dev(self.kcov.data_ptr(), self.rcov.data_ptr(), 0, self.span, 1, None, None, None, 0)
+        if m == 0:
+            return kc, rc
+        dpos = torch.empty(m, dtype=torch.int64, device=self.dev)
+        dk = torch.empty(m, dtype=torch.int32, device=self.dev)
+        dr = torch.empty(m, dtype=torch.int32, device=self.dev)
+        torch.cuda.synchronize(self.dev)
+        eng.coverage_list_dev(self.kcov.data_ptr(), self.rcov.data_ptr(), 0, self.span, 1, dpos.data_ptr(), dk.data_ptr(),
+                              dr.data_ptr(), m)
+        g = dpos.cpu().numpy()
+        kv, rv = dk.cpu().numpy().view(np.uint32), dr.cpu().numpy().view(np.uint32)
+        ci = np.searchsorted(self.contig_off, g, side="right") - 1
+        for c in np.unique(ci).tolist():
+            sel = ci == c
+            p = (g[sel] - self.contig_off[c]).tolist()
+            kc[refs[c]].update(dict(zip(p, kv[sel].tolist())))
+            rc[refs[c]].update(dict(zip(p, rv[sel].tolist())))
+        return kc, rc
+
+
 def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=None,
                      batch_bases: int = SCAN_BATCH_BASES):
     """Module 3 over a whole BAM with the reference's task structure: one task per
@@ -271,6 +405,9 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
       (read_hits, reads_seen, unmapped_informative, total_reads_scanned,
        read_sv_meta, kmer_coverage, read_coverage)
     with read_hits = [(ref_name, ref_start, ref_end, query_name, unique_in_read, is_supplementary)].
+
+    ``KDF_DEVICE_COVERAGE=1``: the two coverage sums and the per-read k-mer sets are made on the device
+    (``_DeviceCoverage``); the tuple is the same.
     """
     import collections
     from ..kmer_utils import canonicalize
@@ -285,9 +422,28 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
     rd = bam_reader(child_bam, flag_off=FLAG_OFF_MODULE3, collapse=False, max_bases=batch_bases,
                     max_reads=1 << 20, threads=READER_THREADS, want_aux=True)
     refs = rd.references()
+    # KDF_DEVICE_COVERAGE=1, read here at every call (it implies the device hits path): the coverage sums stay in HBM
+    dcov = None
+    if os.environ.get("KDF_DEVICE_COVERAGE") == "1":
+        lengths = rd.reference_lengths()
+        if _DeviceCoverage.fits(eng, lengths):
+            dcov = _DeviceCoverage(eng, lengths)
     with rd:
         for batch in rd:
             total_scanned += batch.n_reads
+            if dcov is not None:
+                try:
+                    keep, hit_idx, kmers = dcov.batch(batch, min_dk, k)
+                except KdfError as e:
+                    raise RuntimeError(f"jellyfish query failed: {e}") from e
+                for r, idx, km in zip(keep.tolist(), hit_idx, kmers):
+                    rec = {
+                        "name": batch.name(r), "flag": int(batch.flags[r]), "ref_id": int(batch.ref_ids[r]),
+                        "pos": int(batch.positions[r]), "cigar": batch.cigartuples(r), "sa": batch.sa_tag(r),
+                        "qlen": int(batch.offsets[r + 1] - batch.offsets[r]) - 1, "hit_idx": idx, "kmers": km,
+                    }
+                    per_task.setdefault(rec["ref_id"], []).append(rec)
+                continue
             try:
                 distinct, hits_of = _scan_batch(eng, batch)
             except KdfError as e:
@@ -321,10 +477,13 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
                 unmapped_informative += 1
                 continue
             chrom = refs[rec["ref_id"]]
-            cov = _collect_kmer_ref_positions(rec["pos"], rec["cigar"], rec["qlen"], rec["hit_idx"], k)
-            kmer_coverage[chrom].update(cov)
-            for p in cov:
-                read_coverage[chrom][p] += 1
+            if dcov is None:
+                cov = _collect_kmer_ref_positions(rec["pos"], rec["cigar"], rec["qlen"], rec["hit_idx"], k)
+                kmer_coverage[chrom].update(cov)
+                for p in cov:
+                    read_coverage[chrom][p] += 1
+            else:
+                kmer_coverage[chrom]                    # (the host path leaves an entry for every contig met here)
             paired = bool(rec["flag"] & 0x1)
             if key not in read_sv_meta:
                 read_sv_meta[key] = {
@@ -340,5 +499,14 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
             read_hits.append((chrom, rec["pos"], reference_end(rec["pos"], rec["cigar"]), rec["name"],
                               rec["kmers"], is_supp))
         reads_seen |= seen_local
+    if dcov is not None:
+        try:
+            kc, rc = dcov.counters(refs)
+        except KdfError as e:
+            raise RuntimeError(f"jellyfish query failed: {e}") from e
+        for chrom, c in kc.items():
+            kmer_coverage[chrom].update(c)
+        for chrom, c in rc.items():
+            read_coverage[chrom].update(c)
     return (read_hits, reads_seen, unmapped_informative, total_scanned, read_sv_meta,
             kmer_coverage, read_coverage)

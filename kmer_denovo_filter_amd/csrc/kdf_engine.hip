@@ -285,6 +285,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 // per-window counts and per-read depth rows of a read stream
 #include "kdf_depth.h"
 #include "kdf_hits.h"
+#include "kdf_coverage.h"
 #include "kdf_spool.h"
 
 // ---------------------------------------------------------------------------
@@ -425,10 +426,10 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COUNT = BUF_UP + 4 };
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_COUNT = BUF_COV + 6 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage"};
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -537,6 +538,8 @@ struct kdf_engine {
     uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
     // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
     DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
+    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch and the staging of the host forms -------------
+    DevBuf *const cov_buf = buf + BUF_COV;           // [6] 0 CIGAR prefix sums, 1 ref_start, 2 cigar, 3 cigar_offsets, 4 kmer_cov, 5 read_cov
     // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
     bool sk_on = false;
     KdfSketch sk{};                                  // the register cells (device) and p
@@ -2734,6 +2737,185 @@ int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, cons
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return rcl;
+}
+
+// ------------------------------------------------ hits in reference coordinates (kdf_coverage.h) ----
+
+int kdf_hit_coverage_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets, int64_t n_reads,
+                         const void *d_ref_start, const void *d_cigar, uint64_t n_cigar, const void *d_cigar_offsets,
+                         void *d_kmer_cov, void *d_read_cov, uint64_t span) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads == 0 || n_bases == 0) return KDF_OK;
+    if (!d_hit_bits || !d_read_offsets || !d_ref_start || !d_cigar_offsets || (n_cigar && !d_cigar) || (span && (!d_kmer_cov || !d_read_cov)))
+        return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage_dev: NULL pointer");
+    // a hit is a set bit p with p + k <= n_bases: the list is cut from the first n_bases - k + 1 bits; without an
+    // operation or an accumulator word nothing can be added
+    if (n_bases < (uint64_t)h->k || n_cigar == 0 || span == 0) return KDF_OK;
+    const uint64_t n_starts = n_bases - (uint64_t)h->k + 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t n_blocks = 0, n_hits = 0;
+    int rc;
+    EvSpan p1(h->timer[T_COV], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
+    if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_starts, &n_blocks))) return rc;
+    p1.stop();
+    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
+    if (n_hits == 0) return KDF_OK;
+    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
+    if ((rc = eng_reserve(h, h->cov_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
+    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
+    unsigned long long *pre = (unsigned long long *)h->cov_buf[0].p;
+    const int64_t *offs = (const int64_t *)d_read_offsets, *rs = (const int64_t *)d_ref_start, *co = (const int64_t *)d_cigar_offsets;
+    const uint32_t *cig = (const uint32_t *)d_cigar;
+    EvSpan p2(h->timer[T_COV], h->prof, h->stream, 0);            // (the same call's second group: time only)
+    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_starts,
+                       (const unsigned long long *)h->hit_buf[1].p, pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
+    hipLaunchKernelGGL(kc_prefix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads, rs,
+                       cig, n_cigar, co, pre);
+    hipLaunchKernelGGL(kc_accum_kernel, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, h->k, offs, n_reads, rs,
+                       cig, n_cigar, co, (const unsigned long long *)pre, (uint32_t *)d_kmer_cov, (uint32_t *)d_read_cov, span);
+    p2.stop();
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_hit_coverage(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets, int64_t n_reads,
+                     const int64_t *ref_start, const uint32_t *cigar, uint64_t n_cigar, const int64_t *cigar_offsets,
+                     uint32_t *kmer_cov, uint32_t *read_cov, uint64_t span) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    int rc = check_read_offsets(EngSink{h}, "kdf_hit_coverage", read_offsets, n_reads);  // (before any device work)
+    if (rc) return rc;
+    if (n_reads > 0) {
+        if (!cigar_offsets || !ref_start) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: NULL pointer");
+        if (cigar_offsets[0] != 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets[0] = %lld, not 0", (long long)cigar_offsets[0]);
+        for (int64_t r = 0; r < n_reads; ++r)
+            if (cigar_offsets[r + 1] < cigar_offsets[r])
+                return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets decrease at read %lld (%lld after %lld)", (long long)r,
+                            (long long)cigar_offsets[r + 1], (long long)cigar_offsets[r]);
+        if ((uint64_t)cigar_offsets[n_reads] != n_cigar)
+            return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets end at %lld, n_cigar is %llu", (long long)cigar_offsets[n_reads],
+                        (unsigned long long)n_cigar);
+    }
+    if (n_reads == 0 || n_bases == 0 || n_cigar == 0 || span == 0) return KDF_OK;
+    if (!hit_bits || !cigar || !kmer_cov || !read_cov) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_coverage"))) return rc;
+    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_coverage"))) return rc;
+    const void *src[5] = {ref_start, cigar, cigar_offsets, kmer_cov, read_cov};
+    const size_t bytes[5] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, (size_t)span * 4, (size_t)span * 4};
+    for (int i = 0; i < 5; ++i) {
+        if ((rc = eng_reserve(h, h->cov_buf[1 + i], bytes[i]))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cov_buf[1 + i].p, src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
+    }
+    if ((rc = kdf_hit_coverage_dev(h, h->stage[0].p, n_bases, h->stage[2].p, n_reads, h->cov_buf[1].p, h->cov_buf[2].p, n_cigar,
+                                   h->cov_buf[3].p, h->cov_buf[4].p, h->cov_buf[5].p, span))) return rc;
+    HIPCHK(h, hipMemcpyAsync(kmer_cov, h->cov_buf[4].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(read_cov, h->cov_buf[5].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+// d_kmer_cov / d_read_cov point at position `first`
+static int coverage_list_core(kdf_engine *h, const char *fn, const uint32_t *d_kc, const uint32_t *d_rc, uint64_t first, uint64_t n,
+                              uint32_t min_reads, void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap, uint64_t *n_out) {
+    const uint64_t n_blocks = (n + KC_BLOCK_ELEMS - 1) / KC_BLOCK_ELEMS;
+    if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "%s: a window of %llu positions is beyond the 2^41 a call takes", fn, (unsigned long long)n);
+    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
+    if (rc) return rc;
+    const uint32_t thr = std::max<uint32_t>(min_reads, 1);
+    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    EvSpan p(h->timer[T_COV], h->prof, h->stream, 1);
+    hipLaunchKernelGGL(kc_list_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_rc, n, thr, sums);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
+    if (cap)
+        hipLaunchKernelGGL(kc_list_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_kc, d_rc, first, n, thr,
+                           (const unsigned long long *)sums, (uint64_t *)d_pos_out, (uint32_t *)d_kmer_out, (uint32_t *)d_read_out, cap);
+    p.stop();
+    HIPCHK(h, hipGetLastError());
+    uint64_t n_list = 0;
+    if ((rc = hits_total(h, n_blocks, &n_list))) return rc;
+    *n_out = n_list;
+    if (n_list > cap)
+        return fail(h, KDF_ERR_INVALID, "%s: the list holds %llu positions, the buffers %llu", fn, (unsigned long long)n_list, (unsigned long long)cap);
+    return KDF_OK;
+}
+
+int kdf_coverage_list_dev(kdf_engine *h, const void *d_kmer_cov, const void *d_read_cov, uint64_t first, uint64_t n, uint32_t min_reads,
+                          void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list_dev: NULL pointer");
+    *n_out = 0;
+    if (n == 0) return KDF_OK;
+    if (!d_read_cov || (cap && !d_pos_out) || (d_kmer_out && !d_kmer_cov)) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    return coverage_list_core(h, "kdf_coverage_list_dev", d_kmer_cov ? (const uint32_t *)d_kmer_cov + first : nullptr,
+                              (const uint32_t *)d_read_cov + first, first, n, min_reads, d_pos_out, d_kmer_out, d_read_out, cap, n_out);
+}
+
+int kdf_coverage_list(kdf_engine *h, const uint32_t *kmer_cov, const uint32_t *read_cov, uint64_t first, uint64_t n, uint32_t min_reads,
+                      uint64_t *pos_out, uint32_t *kmer_out, uint32_t *read_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list: NULL pointer");
+    *n_out = 0;
+    if (n == 0) return KDF_OK;
+    if (!read_cov || (cap && !pos_out) || (kmer_out && !kmer_cov)) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    // the window alone is staged: cov_buf 4 / 5 the sums, stage 1 the positions, stage 0 / 3 the two value columns
+    if ((rc = eng_reserve(h, h->cov_buf[5], (size_t)n * 4))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->cov_buf[5].p, read_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    if (kmer_out) {
+        if ((rc = eng_reserve(h, h->cov_buf[4], (size_t)n * 4))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->cov_buf[4].p, kmer_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+        if ((rc = eng_reserve(h, h->stage[0], cap * 4))) return rc;
+    }
+    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
+    if (read_out && (rc = eng_reserve(h, h->stage[3], cap * 4))) return rc;
+    const int rcl = coverage_list_core(h, "kdf_coverage_list", kmer_out ? (const uint32_t *)h->cov_buf[4].p : nullptr, (const uint32_t *)h->cov_buf[5].p,
+                                       first, n, min_reads, h->stage[1].p, kmer_out ? h->stage[0].p : nullptr, read_out ? h->stage[3].p : nullptr, cap, n_out);
+    if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
+    const uint64_t m = std::min<uint64_t>(*n_out, cap);
+    if (m) {
+        HIPCHK(h, hipMemcpyAsync(pos_out, h->stage[1].p, m * 8, hipMemcpyDeviceToHost, h->stream));
+        if (kmer_out) HIPCHK(h, hipMemcpyAsync(kmer_out, h->stage[0].p, m * 4, hipMemcpyDeviceToHost, h->stream));
+        if (read_out) HIPCHK(h, hipMemcpyAsync(read_out, h->stage[3].p, m * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    return rcl;
+}
+
+int kdf_hit_keys_dev(kdf_engine *h, const void *d_packed, uint64_t n_bases, const void *d_positions, uint64_t n, void *d_keys_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n == 0) return KDF_OK;
+    if (!d_positions || !d_keys_out || (n_bases && !d_packed)) return fail(h, KDF_ERR_INVALID, "kdf_hit_keys_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        hipLaunchKernelGGL(kc_keys_kernel<W>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_packed, n_bases, h->k,
+                           (const uint64_t *)d_positions, n, (uint64_t *)d_keys_out);
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const uint64_t *positions, uint64_t n, uint64_t *keys_out) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n == 0) return KDF_OK;
+    if (!positions || !keys_out || (n_bases && !packed)) return fail(h, KDF_ERR_INVALID, "kdf_hit_keys: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t pw, mw;
+    kdf_stream_words(n_bases, &pw, &mw);
+    const uint64_t pw_in = (n_bases + 31) / 32;
+    const size_t key_bytes = (size_t)n * 8 * (size_t)h->kw;
+    int rc;
+    if ((rc = eng_reserve(h, h->stage[0], pw * 8))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->stage[0].p, 0, pw * 8, h->stream));
+    if (pw_in) HIPCHK(h, hipMemcpyAsync(h->stage[0].p, packed, pw_in * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = stage_in(h, 1, positions, (size_t)n * 8, "kdf_hit_keys"))) return rc;
+    if ((rc = eng_reserve(h, h->stage[3], key_bytes))) return rc;
+    if ((rc = kdf_hit_keys_dev(h, h->stage[0].p, n_bases, h->stage[1].p, n, h->stage[3].p))) return rc;
+    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[3].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
 }
 
 // ---- long keys (odd k 65..201): W-word keys, row-major -----------------------------------------------------------

@@ -1310,6 +1310,11 @@ const char *kdf_reader_ref_name(kdf_reader *r, int i) {
     return r->ref_names[(size_t)i].c_str();
 }
 
+int kdf_reader_ref_length(kdf_reader *r, int i) {
+    if (!r || i < 0 || i >= (int)r->ref_lens.size()) return -1;
+    return (int)r->ref_lens[(size_t)i];
+}
+
 }  // extern "C"
 
 // ---- N4: subset BAM writer (BGZF + coordinate sort + BAI) ----------------------

@@ -14,6 +14,7 @@ shells out to ("External op" table):
     query(keys)              jellyfish query idx -s kmers.fa    (input order)
     scan(stream)             JellyfishKmerQuery / Module-3 probe
     read_hits(stream)        ... and its per-read hits / distinct on the device
+    hit_coverage(...)        ... and its hits in reference coordinates (k-mer / read coverage)
 
 Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
 keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
@@ -601,6 +602,90 @@ class KmerEngine:
         hi = np.searchsorted(pos, offs[keep + 1], side="left") if len(keep) else lo
         per_read = [pos[a:b] - s for a, b, s in zip(lo.tolist(), hi.tolist(), offs[keep].tolist())]
         return keep.astype(np.int64), rows[keep, 1].copy(), per_read
+
+    # -- hits in reference coordinates ------------------------------------------
+    def hit_coverage(self, hit_bits: np.ndarray, n_bases: int, offsets: np.ndarray, ref_start: np.ndarray,
+                     cigar: np.ndarray, cigar_offsets: np.ndarray, kmer_cov: np.ndarray, read_cov: np.ndarray):
+        """Add the hits of a mask to two per-position sums in reference coordinates (``include/kdf.h``, "hits in
+        reference coordinates"): ``kmer_cov[g]`` gains the number of hit k-mers of a read that cover reference position
+        g, ``read_cov[g]`` gains 1 per such read.  ``offsets`` int64[n_reads + 1], ``ref_start`` int64[n_reads] (the
+        linear coordinate of each read's leftmost base, < 0: the read is skipped), ``cigar`` uint32 in BAM encoding with
+        ``cigar_offsets`` int64[n_reads + 1] (``ReadStream.cigar`` / ``cigar_offsets``).  The two accumulators are
+        C-contiguous uint32 arrays of one length, changed IN PLACE and only added to: batches accumulate."""
+        bits = np.ascontiguousarray(hit_bits, dtype=np.uint64)
+        if len(bits) * 64 < int(n_bases):
+            raise ValueError(f"a mask of {len(bits)} words does not cover {n_bases} positions")
+        for a in (kmer_cov, read_cov):
+            if a.dtype != np.uint32 or not a.flags.c_contiguous or a.ndim != 1 or len(a) != len(kmer_cov):
+                raise ValueError("kmer_cov and read_cov must be C-contiguous uint32 arrays of one length")
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        rs = np.ascontiguousarray(ref_start, dtype=np.int64)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint32)
+        co = np.ascontiguousarray(cigar_offsets, dtype=np.int64)
+        n_reads = len(offs) - 1
+        if n_reads > 0 and (len(rs) != n_reads or len(co) != n_reads + 1):
+            raise ValueError(f"{n_reads} reads, {len(rs)} ref_start and {len(co)} cigar_offsets entries")
+        self._ck(self._lib.kdf_hit_coverage(self._h, _vp(bits), int(n_bases), _vp(offs), n_reads, _vp(rs), _vp(cg), len(cg),
+                                            _vp(co), _vp(kmer_cov), _vp(read_cov), len(kmer_cov)))
+
+    def hit_coverage_dev(self, d_hit_bits: int, n_bases: int, d_offsets: int, n_reads: int, d_ref_start: int, d_cigar: int,
+                         n_cigar: int, d_cigar_offsets: int, d_kmer_cov: int, d_read_cov: int, span: int):
+        """The same between device buffers: ``d_ref_start`` int64[n_reads], ``d_cigar`` uint32[n_cigar],
+        ``d_cigar_offsets`` int64[n_reads + 1], ``d_kmer_cov`` / ``d_read_cov`` uint32[span].  Synchronises the engine's
+        stream once; the sums are complete in stream order."""
+        p = lambda x: c_void_p(x) if x else None
+        self._ck(self._lib.kdf_hit_coverage_dev(self._h, p(d_hit_bits), int(n_bases), p(d_offsets), int(n_reads), p(d_ref_start),
+                                                p(d_cigar), int(n_cigar), p(d_cigar_offsets), p(d_kmer_cov), p(d_read_cov),
+                                                int(span)))
+
+    def coverage_list(self, kmer_cov: np.ndarray, read_cov: np.ndarray, first: int = 0, n: Optional[int] = None,
+                      min_reads: int = 1, cap: Optional[int] = None):
+        """-> (positions uint64[m] ascending, kmer uint32[m], reads uint32[m]): the positions g of [first, first + n)
+        with ``read_cov[g] >= max(min_reads, 1)`` and the two sums there.  ``cap`` (default: as many as there are)
+        bounds the output: more entries than that raise, like hit_list."""
+        kc = np.ascontiguousarray(kmer_cov, dtype=np.uint32)
+        rc = np.ascontiguousarray(read_cov, dtype=np.uint32)
+        n = len(rc) - int(first) if n is None else int(n)
+        if first < 0 or n < 0 or int(first) + n > len(rc) or len(kc) != len(rc):
+            raise ValueError(f"window [{first}, {first}+{n}) outside accumulators of {len(rc)} / {len(kc)} positions")
+        if cap is None:
+            cap = int((rc[first:first + n] >= max(int(min_reads), 1)).sum())
+        pos, ko, ro = np.zeros(int(cap), np.uint64), np.zeros(int(cap), np.uint32), np.zeros(int(cap), np.uint32)
+        m = c_uint64(0)
+        self._ck(self._lib.kdf_coverage_list(self._h, _vp(kc), _vp(rc), int(first), n, int(min_reads), _vp(pos), _vp(ko),
+                                             _vp(ro), int(cap), byref(m)))
+        return pos[:m.value], ko[:m.value], ro[:m.value]
+
+    def _coverage_list_dev(self, d_kmer_cov, d_read_cov, first, n, min_reads, d_pos, d_kmer, d_read, cap):
+        m = c_uint64(0)
+        p = lambda x: c_void_p(x) if x else None
+        rc = self._lib.kdf_coverage_list_dev(self._h, p(d_kmer_cov), p(d_read_cov), int(first), int(n), int(min_reads),
+                                             p(d_pos), p(d_kmer), p(d_read), int(cap), byref(m))
+        return rc, m.value
+
+    def coverage_list_dev(self, d_kmer_cov: Optional[int], d_read_cov: int, first: int, n: int, min_reads: int, d_pos: int,
+                          d_kmer: Optional[int], d_read: Optional[int], cap: int) -> int:
+        """The same between device buffers (``d_pos`` uint64[cap], ``d_kmer`` / ``d_read`` uint32[cap] or None);
+        returns the number of entries and raises when it exceeds ``cap`` (at most ``cap`` are written).  Synchronises."""
+        rc, m = self._coverage_list_dev(d_kmer_cov, d_read_cov, first, n, min_reads, d_pos, d_kmer, d_read, cap)
+        self._ck(rc)
+        return m
+
+    def hit_keys(self, stream: ReadStream, positions: np.ndarray) -> np.ndarray:
+        """uint64 (n, key_words): the canonical key of window [p, p + k) of the stream for every listed position, word
+        0 least significant (k <= 32: column 0 is ``lo``; 33..63: ``lo``, ``hi``).  A window that ends past the stream
+        gets a row of all-ones words.  Positions come from a hit list: whether a window is valid is not checked."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint64)
+        keys = np.zeros((len(pos), self.key_words), np.uint64)
+        self._ck(self._lib.kdf_hit_keys(self._h, _vp(stream.packed), int(stream.n_bases), _vp(pos), len(pos), _vp(keys)))
+        return keys
+
+    def hit_keys_dev(self, d_packed: int, n_bases: int, d_positions: int, n: int, d_keys: int):
+        """The same between device buffers: ``d_positions`` uint64[n], ``d_keys`` uint64[n x key_words].  Stream order
+        on the engine's stream; does not synchronise."""
+        self._ck(self._lib.kdf_hit_keys_dev(self._h, c_void_p(d_packed) if d_packed else None, int(n_bases),
+                                            c_void_p(d_positions) if d_positions else None, int(n),
+                                            c_void_p(d_keys) if d_keys else None))
 
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):

@@ -143,6 +143,11 @@ class _Reader:
         n = self._lib.kdf_reader_ref_count(self._h)
         return [self._lib.kdf_reader_ref_name(self._h, i).decode() for i in range(max(n, 0))]
 
+    def reference_lengths(self) -> List[int]:
+        """Lengths of the header's reference sequences (BAM readers), in ``references()`` order."""
+        n = self._lib.kdf_reader_ref_count(self._h)
+        return [int(self._lib.kdf_reader_ref_length(self._h, i)) for i in range(max(n, 0))]
+
     def close(self):
         if self._h:
             self._lib.kdf_reader_close(self._h)
