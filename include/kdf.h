@@ -159,7 +159,8 @@ int kdf_flush(kdf_engine *h);
  *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
  *            "hits_us" / "hits_passes" (the kh_* kernels of kdf_read_hits* / kdf_hit_list* under kdf_profile, the scan kernel
  *            not included; one pass per call); "coverage_us" / "coverage_passes" (the kc_* kernels of kdf_hit_coverage* /
- *            kdf_coverage_list* under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
+ *            kdf_coverage_list* under kdf_profile); "variants_us" / "variants_passes" (the kv_* kernels of
+ *            kdf_variant_windows* / kdf_variant_evidence* under kdf_profile); "trash0" .. "trash63" (phase cycle sums of -DKB_TIMING variant builds) */
 int kdf_set_option(kdf_engine *h, const char *name, int64_t value);
 /* Free / total HBM of a device (hipMemGetInfo): the child-count mirror sizes "key_parts" with it. */
 int kdf_device_memory(int device, uint64_t *free_bytes, uint64_t *total_bytes);
@@ -564,6 +565,119 @@ int kdf_hit_keys_dev(kdf_engine *h, const void *d_packed, uint64_t n_bases, cons
                      void *d_keys_out);
 int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const uint64_t *positions, uint64_t n,
                  uint64_t *keys_out);
+
+/* -------------------------------------------------- VCF mode on the device ---- */
+
+/* VCF mode's step from "the reads over a candidate variant" to "the windows of each read that span it, and whether the
+ * read spells the ALT": extract_variant_spanning_kmers and read_supports_alt (kmer_utils.py:1104-1172, :1037-1101) for
+ * every (read, variant) at once, as positions in the stream instead of k-mer strings.  kdf_hit_keys* turns the
+ * positions into keys: kdf_hit_keys_dev(d_packed, n_bases, d_entry_pos, n_entries, d_keys).
+ *   Inputs.
+ *     - a read stream (packed, invalid, n_bases) and read_offsets[n_reads + 1]: query index c of read r is stream
+ *       position offsets[r] + c; the read's stream range is [offsets[r], min(offsets[r + 1], n_bases)).
+ *     - ref_start[n_reads] (int64): the linear coordinate of the read's leftmost reference base (as for
+ *       kdf_hit_coverage); a read with ref_start[r] < 0 is skipped entirely.
+ *     - cigar[n_cigar] / cigar_offsets[n_reads + 1]: exactly what kdf_hit_coverage* takes.
+ *     - base qualities, optional: qual[n_qual] (uint8, one byte per read base, no separators), qual_offsets[n_reads + 1]
+ *       and min_baseq.  Query index c of read r has quality qual[qual_offsets[r] + c] when
+ *       c < qual_offsets[r + 1] - qual_offsets[r], and otherwise has none: a read may be given an empty range, so the
+ *       caller uploads qualities only for the reads that can matter.  qual == NULL or min_baseq == 0: no quality rule.
+ *     - n_var variants (< 2^32), ASCENDING by var_pos (int64, the same linear coordinate; equal positions allowed), each
+ *       with var_span (uint32: the number of read bases the variant occupies -- len(alt) for a literal ALT, 1 for a
+ *       missing ALT, 0: the variant is skipped entirely, which is what the caller passes for a symbolic ALT),
+ *       var_ref_len (uint32, len(ref)) and its ALT as ASCII bytes alt[alt_offsets[v] .. alt_offsets[v + 1]) of
+ *       alt[n_alt].  Empty bytes, or any byte outside ACGTacgt, mean that the ALT never matches.
+ *   Semantics, for every read r with ref_start[r] >= 0 and every variant v with var_span[v] > 0:
+ *     Anchor.    Walk the CIGAR by the rules of kdf_hit_coverage (M, = and X align; I and S advance the query; D and N
+ *                advance the reference; everything else advances nothing).  `at` is the query index that is aligned at
+ *                reference offset var_pos[v] - ref_start[r].  When no query index is (the position lies in a D or N,
+ *                before or behind the read's reference interval, or the CIGAR is empty) there is no pair.
+ *     Bad.       Stream position q of the read's stream range is BAD when it is invalid ("Read streams" points 1-2: its
+ *                mask bit is set -- N, IUPAC, the separator), or when the quality rule is on and its query index has a
+ *                quality < min_baseq.
+ *     Windows.   The candidate starts are the stream positions p = offsets[r] + s with
+ *                max(0, at - k + 1) <= s <= at + var_span[v] - 1 and p + k <= min(offsets[r + 1], n_bases).  A candidate
+ *                is an ENTRY iff none of its k positions is bad.
+ *     Pair.      (r, v) is a PAIR iff it has at least one entry (`if not kmers: continue`, vcf/pipeline.py:619-726).
+ *     supports_alt.  Let E = var_pos[v] + var_ref_len[v] - ref_start[r].  qe is the number of query bases the walk has
+ *                consumed when it first stands on a reference offset >= E inside an M, =, X, D or N operation (inserted
+ *                and clipped bases directly in front of that base are therefore consumed; inside an aligned operation
+ *                qe counts the bases of the operation before that offset); when the walk never gets there, qe is the
+ *                number of query bases the whole CIGAR consumes.  The pair supports the ALT iff len(alt) > 0,
+ *                qe - at == len(alt), the query indices at .. qe - 1 all lie in the read's stream range, none of their
+ *                stream positions is bad, and their bases spell the ALT, case-insensitively.
+ *   Outputs (device form: caller-owned HBM; host form: host arrays, staged through the engine's scratch).
+ *     - pairs, ascending by (read, variant index): pair_read (int64), pair_var (uint32), pair_flags (uint8, bit 0 =
+ *       supports_alt, the other bits 0).
+ *     - entries, ascending by (pair, position): entry_pos (uint64, the stream position of the window's start) and
+ *       entry_pair (uint64, index into the pair list of this call).
+ *     - *n_pairs_out and *n_entries_out are always set.  At most pair_cap pairs and entry_cap entries are written; when
+ *       either count exceeds its cap the call returns KDF_ERR_INVALID (the convention of kdf_hit_list_dev).  With both
+ *       caps 0 and every out pointer NULL the call is a SIZING call: KDF_OK with the two counts.
+ *   - the table is not touched and nothing is flushed; every key width is accepted, only k matters.
+ *   - n_reads == 0, n_var == 0 and n_bases == 0 are KDF_OK with both counts 0.
+ *   - work is linear in (candidate pairs) x (k + span) plus the CIGAR operations of the reads that are not skipped,
+ *     never a walk per window: a read finds its candidate variants by binary search of var_pos over [ref_start,
+ *     ref_start + reference bases its CIGAR consumes), the anchor by binary search in per-operation prefix sums.
+ *     Scratch, owned by the engine and kept between calls: 16 bytes per CIGAR operation and per read, 5 per candidate.
+ *   - device form: offsets, cigar_offsets, qual_offsets, alt_offsets and the order of var_pos are preconditions, but
+ *     whatever they hold no write lands outside the cap-sized outputs and no stream word, CIGAR word, quality byte or
+ *     ALT byte is read outside its array (indices are clamped, as kdf_hit_coverage_dev does).  It SYNCHRONISES the
+ *     engine's stream TWICE: once for the number of (read, variant) candidates, which sizes its scratch (a call without
+ *     candidates returns after that one), once for the two counts; the lists are complete in stream order when it returns.
+ *   - host form: n_reads < 0, bad read offsets (negative, decreasing), cigar_offsets / alt_offsets / qual_offsets (when
+ *     qual is given) that do not start at 0, that decrease or that do not end at n_cigar / n_alt / n_qual, and a
+ *     decreasing var_pos are KDF_ERR_INVALID before any device work.
+ *   - all outputs are integers and positions: bit-identical from run to run, between the host and device forms, and
+ *     between one call and the same reads split over several calls (concatenate, and re-base entry_pair by the pairs
+ *     of the calls before).
+ *   - under kdf_profile(h, 1) the kv_* kernels of these calls and of kdf_variant_evidence* are timed with HIP events:
+ *     stats "variants_us" / "variants_passes" (one pass per call that launches). */
+int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases,
+                            const void *d_read_offsets, int64_t n_reads, const void *d_ref_start, const void *d_cigar,
+                            uint64_t n_cigar, const void *d_cigar_offsets, const void *d_qual, uint64_t n_qual,
+                            const void *d_qual_offsets, uint32_t min_baseq, const void *d_var_pos, const void *d_var_span,
+                            const void *d_var_ref_len, uint64_t n_var, const void *d_alt, uint64_t n_alt,
+                            const void *d_alt_offsets, void *d_pair_read, void *d_pair_var, void *d_pair_flags,
+                            uint64_t pair_cap, void *d_entry_pos, void *d_entry_pair, uint64_t entry_cap,
+                            uint64_t *n_pairs_out, uint64_t *n_entries_out);
+int kdf_variant_windows(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+                        const int64_t *read_offsets, int64_t n_reads, const int64_t *ref_start, const uint32_t *cigar,
+                        uint64_t n_cigar, const int64_t *cigar_offsets, const uint8_t *qual, uint64_t n_qual,
+                        const int64_t *qual_offsets, uint32_t min_baseq, const int64_t *var_pos, const uint32_t *var_span,
+                        const uint32_t *var_ref_len, uint64_t n_var, const uint8_t *alt, uint64_t n_alt,
+                        const int64_t *alt_offsets, int64_t *pair_read, uint32_t *pair_var, uint8_t *pair_flags,
+                        uint64_t pair_cap, uint64_t *entry_pos, uint64_t *entry_pair, uint64_t entry_cap,
+                        uint64_t *n_pairs_out, uint64_t *n_entries_out);
+
+/* VCF mode's annotation (annotate_variants, vcf/pipeline.py:1640-1724) against the table the engine holds -- the child's
+ * keys loaded as a filter with both parents counted into it by `count --if`, so that a count is mother + father.
+ * Inputs: keys (n_entries x W uint64 rows, as kdf_hit_keys* writes them; a row of all-ones words is no key and counts as
+ * not stored), entry_pair[n_entries] (uint64), pair_var[n_pairs] (uint32), pair_flags[n_pairs] (uint8) and n_var.
+ * Entries and pairs may come from many kdf_variant_windows* calls concatenated, in any order of variants.
+ *   pair_rows  n_pairs x 2 uint32: `windows` (the entries of the pair) and `absent` (those whose key is not stored, or
+ *              is stored with count 0).  A pair is informative iff absent > 0 (`not kmers.issubset(parent_set)`).
+ *   var_rows   n_var x 8 uint64: n, sum, min, max and n_alt, sum_alt, min_alt, max_alt of the stored counts, taken over
+ *              the DISTINCT keys with stored count > 0 among the variant's entries -- all its pairs for the first four,
+ *              only the pairs with bit 0 of their flags set for the last four; min and max are 0 when n is 0
+ *              (max_pkc / avg_pkc / min_pkc[_alt]; the caller forms the average as sum / n).
+ *   - an entry whose entry_pair is >= n_pairs, and every entry of a pair whose pair_var is >= n_var, contributes nothing
+ *     to either output; nothing is written outside the two outputs.  Both are written in full (rows without entries
+ *     are zero); n_entries == 0 is KDF_OK.
+ *   - distinctness is exact: a stored key and its slot are one-to-one, so the distinct keys of a variant are the
+ *     distinct words (variant, tag, slot), tag 1 for the alt columns, in the engine's open-addressing scratch set (as
+ *     kdf_read_hits*: 32 to 64 bytes per entry, KDF_ERR_NOMEM when it does not fit).  Variant index, tag and slot index
+ *     must fit 63 bits together (the top bit keeps a word apart from the set's empty word): log2ceil(n_var) + 1 +
+ *     log2cap <= 63, KDF_ERR_INVALID beyond, never hashed down.  All results are integer sums, minima and maxima.
+ *   - the table is only read: pending count work is applied first and a loaded filter's sieve stays valid; every key
+ *     width, insert and filter mode.
+ *   - the device form runs in stream order and does not synchronise.  Timed into "variants_us" / "variants_passes". */
+int kdf_variant_evidence_dev(kdf_engine *h, const void *d_keys, const void *d_entry_pair, uint64_t n_entries,
+                             const void *d_pair_var, const void *d_pair_flags, uint64_t n_pairs, uint64_t n_var,
+                             void *d_pair_rows, void *d_var_rows);
+int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *entry_pair, uint64_t n_entries,
+                         const uint32_t *pair_var, const uint8_t *pair_flags, uint64_t n_pairs, uint64_t n_var,
+                         uint32_t *pair_rows, uint64_t *var_rows);
 
 /* ------------------------------------------- count profile of a stream ---- */
 

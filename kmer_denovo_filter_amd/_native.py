@@ -71,6 +71,13 @@ SYMBOLS = [
     ("kdf_coverage_list", c_int, [_P, _P, _P, c_uint64, c_uint64, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_hit_keys_dev", c_int, [_P, _P, c_uint64, _P, c_uint64, _P]),
     ("kdf_hit_keys", c_int, [_P, _P, c_uint64, _P, c_uint64, _P]),
+    # VCF mode on the device
+    ("kdf_variant_windows_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P, _P, c_uint64,
+                                        _P, c_uint64, _P, _P, _P, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_variant_windows", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P, c_uint64, _P, _P, c_uint64, _P, c_uint32, _P, _P, _P, c_uint64,
+                                    _P, c_uint64, _P, _P, _P, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_variant_evidence_dev", c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P]),
+    ("kdf_variant_evidence", c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),

@@ -286,6 +286,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 #include "kdf_depth.h"
 #include "kdf_hits.h"
 #include "kdf_coverage.h"
+#include "kdf_variants.h"
 #include "kdf_spool.h"
 
 // ---------------------------------------------------------------------------
@@ -426,10 +427,10 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_COUNT = BUF_COV + 6 };
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_COUNT = BUF_VAR + 5 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants"};
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -540,6 +541,8 @@ struct kdf_engine {
     DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
     // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch and the staging of the host forms -------------
     DevBuf *const cov_buf = buf + BUF_COV;           // [6] 0 CIGAR prefix sums, 1 ref_start, 2 cigar, 3 cigar_offsets, 4 kmer_cov, 5 read_cov
+    // ---- VCF mode (kdf_variants.h): grow-only scratch and the staging of the host forms -------------------------------------
+    DevBuf *const var_buf = buf + BUF_VAR;           // [5] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags, 3 / 4 host forms: inputs / outputs
     // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
     bool sk_on = false;
     KdfSketch sk{};                                  // the register cells (device) and p
@@ -2914,6 +2917,237 @@ int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const 
     if ((rc = eng_reserve(h, h->stage[3], key_bytes))) return rc;
     if ((rc = kdf_hit_keys_dev(h, h->stage[0].p, n_bases, h->stage[1].p, n, h->stage[3].p))) return rc;
     HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[3].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+// ------------------------------------------------ VCF mode on the device (kdf_variants.h) ----
+
+// several host arrays side by side in ONE device buffer, each at a multiple of 16 bytes
+struct Arena {
+    size_t off[16]; size_t bytes = 0; int n = 0;
+    int add(size_t b) { off[n] = bytes; bytes += (b + 15) / 16 * 16; return n++; }
+};
+// offsets that start at 0, do not decrease and end at `total` (cigar_offsets, qual_offsets, alt_offsets)
+static int check_offsets0(kdf_engine *h, const char *fn, const char *what, const int64_t *o, uint64_t n, uint64_t total) {
+    if (!o) return fail(h, KDF_ERR_INVALID, "%s: %s is NULL", fn, what);
+    if (o[0] != 0) return fail(h, KDF_ERR_INVALID, "%s: %s[0] = %lld, not 0", fn, what, (long long)o[0]);
+    for (uint64_t i = 0; i < n; ++i)
+        if (o[i + 1] < o[i])
+            return fail(h, KDF_ERR_INVALID, "%s: %s decrease at %llu (%lld after %lld)", fn, what, (unsigned long long)i, (long long)o[i + 1], (long long)o[i]);
+    if ((uint64_t)o[n] != total) return fail(h, KDF_ERR_INVALID, "%s: %s end at %lld, the array holds %llu", fn, what, (long long)o[n], (unsigned long long)total);
+    return KDF_OK;
+}
+
+int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
+                            int64_t n_reads, const void *d_ref_start, const void *d_cigar, uint64_t n_cigar, const void *d_cigar_offsets,
+                            const void *d_qual, uint64_t n_qual, const void *d_qual_offsets, uint32_t min_baseq, const void *d_var_pos,
+                            const void *d_var_span, const void *d_var_ref_len, uint64_t n_var, const void *d_alt, uint64_t n_alt,
+                            const void *d_alt_offsets, void *d_pair_read, void *d_pair_var, void *d_pair_flags, uint64_t pair_cap,
+                            void *d_entry_pos, void *d_entry_pair, uint64_t entry_cap, uint64_t *n_pairs_out, uint64_t *n_entries_out) {
+    if (!h || !n_pairs_out || !n_entries_out) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: NULL pointer");
+    *n_pairs_out = *n_entries_out = 0;
+    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: n_reads = %lld is negative", (long long)n_reads);
+    if (n_reads == 0 || n_var == 0 || n_bases == 0) return KDF_OK;
+    if (!d_packed || !d_invalid || !d_read_offsets || !d_ref_start || !d_cigar_offsets || (n_cigar && !d_cigar) || !d_var_pos || !d_var_span ||
+        !d_var_ref_len || !d_alt_offsets || (n_alt && !d_alt) || (d_qual && !d_qual_offsets) ||
+        (pair_cap && (!d_pair_read || !d_pair_var || !d_pair_flags)) || (entry_cap && (!d_entry_pos || !d_entry_pair)))
+        return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: NULL pointer");
+    if (n_var >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu variants: pair_var holds 32 bits", (unsigned long long)n_var);
+    if (n_bases < (uint64_t)h->k || n_cigar == 0) return KDF_OK;     // no window, or no aligned base
+    HIPCHK(h, hipSetDevice(h->device));
+    const uint64_t nbr = ((uint64_t)n_reads + 255) / 256;
+    if (nbr >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %lld reads are beyond the 2^39 a call takes", (long long)n_reads);
+    int rc;
+    if ((rc = eng_reserve(h, h->hit_buf[1], (nbr + 1) * 8, slack_8th, "block sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var_buf[1], (size_t)(2 * (uint64_t)n_reads + 1) * 8, slack_8th, "candidate ranges"))) return rc;
+    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    uint64_t *cand_lo = (uint64_t *)h->var_buf[1].p;
+    unsigned long long *cand_off = (unsigned long long *)h->var_buf[1].p + n_reads;
+    KvArgs a{};
+    a.packed = (const uint64_t *)d_packed; a.invalid = (const uint64_t *)d_invalid; a.n_bases = n_bases; a.k = h->k;
+    a.offs = (const int64_t *)d_read_offsets; a.n_reads = n_reads; a.ref_start = (const int64_t *)d_ref_start;
+    a.cigar = (const uint32_t *)d_cigar; a.n_cigar = n_cigar; a.cig_offs = (const int64_t *)d_cigar_offsets;
+    a.qual = min_baseq ? (const uint8_t *)d_qual : nullptr; a.n_qual = n_qual; a.qual_offs = (const int64_t *)d_qual_offsets; a.min_baseq = min_baseq;
+    a.var_pos = (const int64_t *)d_var_pos; a.var_span = (const uint32_t *)d_var_span; a.var_ref_len = (const uint32_t *)d_var_ref_len; a.n_var = n_var;
+    a.alt = (const uint8_t *)d_alt; a.n_alt = n_alt; a.alt_offs = (const int64_t *)d_alt_offsets;
+    a.pre = (const unsigned long long *)h->var_buf[0].p; a.cand_lo = cand_lo; a.cand_off = cand_off;
+    EvSpan p1(h->timer[T_VAR], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
+    hipLaunchKernelGGL(kv_range_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, a.ref_start, a.cigar, n_cigar, a.cig_offs, a.var_pos,
+                       n_var, (unsigned long long *)h->var_buf[0].p, cand_lo, cand_off, sums);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, nbr);
+    hipLaunchKernelGGL(kv_offsets_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, (const unsigned long long *)sums, cand_off);
+    p1.stop();
+    HIPCHK(h, hipGetLastError());
+    uint64_t n_cand = 0;
+    if ((rc = hits_total(h, nbr, &n_cand))) return rc;               // (first synchronisation: sizes the per-candidate scratch)
+    if (n_cand == 0) return KDF_OK;
+    const uint64_t nbc = (n_cand + 255) / 256;
+    if (nbc >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu (read, variant) candidates are beyond the 2^39 a call takes", (unsigned long long)n_cand);
+    if ((rc = eng_reserve(h, h->hit_buf[1], 2 * (nbc + 1) * 8, slack_8th, "block sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var_buf[2], (size_t)n_cand * 5, slack_8th, "candidate counts"))) return rc;
+    sums = (unsigned long long *)h->hit_buf[1].p;
+    unsigned long long *sums_p = sums, *sums_e = sums + nbc + 1;
+    uint32_t *ent_cnt = (uint32_t *)h->var_buf[2].p;
+    uint8_t *cflags = (uint8_t *)(ent_cnt + n_cand);
+    a.n_cand = n_cand;
+    EvSpan p2(h->timer[T_VAR], h->prof, h->stream, 0);            // (the same call's later groups: time only)
+    hipLaunchKernelGGL(kv_count_kernel, dim3((unsigned)nbc), dim3(256), 0, h->stream, a, ent_cnt, cflags, sums_p, sums_e);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums_p, nbc);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums_e, nbc);
+    p2.stop();
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->h_out4, sums_p + nbc, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_out4 + 1, sums_e + nbc, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                      // (second synchronisation: the two counts)
+    const uint64_t n_pairs = h->h_out4[0], n_entries = h->h_out4[1];
+    *n_pairs_out = n_pairs;
+    *n_entries_out = n_entries;
+    if (pair_cap == 0 && entry_cap == 0) {
+        if (!d_pair_read && !d_pair_var && !d_pair_flags && !d_entry_pos && !d_entry_pair) return KDF_OK;       // a sizing call
+    } else if (n_pairs) {
+        EvSpan p3(h->timer[T_VAR], h->prof, h->stream, 0);
+        hipLaunchKernelGGL(kv_write_kernel, dim3((unsigned)nbc), dim3(256), 0, h->stream, a, (const uint32_t *)ent_cnt, (const uint8_t *)cflags,
+                           (const unsigned long long *)sums_p, (const unsigned long long *)sums_e, (int64_t *)d_pair_read, (uint32_t *)d_pair_var,
+                           (uint8_t *)d_pair_flags, pair_cap, (uint64_t *)d_entry_pos, (uint64_t *)d_entry_pair, entry_cap);
+        p3.stop();
+        HIPCHK(h, hipGetLastError());
+    }
+    if (n_pairs > pair_cap || n_entries > entry_cap)
+        return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu pairs and %llu entries, the buffers hold %llu and %llu", (unsigned long long)n_pairs,
+                    (unsigned long long)n_entries, (unsigned long long)pair_cap, (unsigned long long)entry_cap);
+    return KDF_OK;
+}
+
+int kdf_variant_windows(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
+                        int64_t n_reads, const int64_t *ref_start, const uint32_t *cigar, uint64_t n_cigar, const int64_t *cigar_offsets,
+                        const uint8_t *qual, uint64_t n_qual, const int64_t *qual_offsets, uint32_t min_baseq, const int64_t *var_pos,
+                        const uint32_t *var_span, const uint32_t *var_ref_len, uint64_t n_var, const uint8_t *alt, uint64_t n_alt,
+                        const int64_t *alt_offsets, int64_t *pair_read, uint32_t *pair_var, uint8_t *pair_flags, uint64_t pair_cap,
+                        uint64_t *entry_pos, uint64_t *entry_pair, uint64_t entry_cap, uint64_t *n_pairs_out, uint64_t *n_entries_out) {
+    static const char *const fn = "kdf_variant_windows";
+    if (!h || !n_pairs_out || !n_entries_out) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    *n_pairs_out = *n_entries_out = 0;
+    int rc = check_read_offsets(EngSink{h}, fn, read_offsets, n_reads);                  // (before any device work)
+    if (rc) return rc;
+    if (n_reads > 0) {
+        if (!ref_start) return fail(h, KDF_ERR_INVALID, "%s: ref_start is NULL", fn);
+        if ((rc = check_offsets0(h, fn, "cigar_offsets", cigar_offsets, (uint64_t)n_reads, n_cigar))) return rc;
+        if (qual && (rc = check_offsets0(h, fn, "qual_offsets", qual_offsets, (uint64_t)n_reads, n_qual))) return rc;
+    }
+    if (n_var > 0) {
+        if (!var_pos || !var_span || !var_ref_len) return fail(h, KDF_ERR_INVALID, "%s: NULL variant array", fn);
+        for (uint64_t v = 1; v < n_var; ++v)
+            if (var_pos[v] < var_pos[v - 1])
+                return fail(h, KDF_ERR_INVALID, "%s: var_pos decreases at variant %llu (%lld after %lld)", fn, (unsigned long long)v, (long long)var_pos[v], (long long)var_pos[v - 1]);
+        if ((rc = check_offsets0(h, fn, "alt_offsets", alt_offsets, n_var, n_alt))) return rc;
+    }
+    if (n_reads == 0 || n_var == 0 || n_bases == 0 || n_cigar == 0) return KDF_OK;
+    if (!packed || !invalid || !cigar || (n_alt && !alt) || (pair_cap && (!pair_read || !pair_var || !pair_flags)) || (entry_cap && (!entry_pos || !entry_pair)))
+        return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *dp, *dm;
+    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
+    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, fn))) return rc;
+    const bool q = qual && min_baseq;
+    const void *src[10] = {ref_start, cigar, cigar_offsets, q ? qual : nullptr, q ? qual_offsets : nullptr, var_pos, var_span, var_ref_len, alt, alt_offsets};
+    const size_t bytes[10] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, q ? (size_t)n_qual : 0, q ? (size_t)(n_reads + 1) * 8 : 0,
+                              (size_t)n_var * 8, (size_t)n_var * 4, (size_t)n_var * 4, (size_t)n_alt, (size_t)(n_var + 1) * 8};
+    Arena in, out;
+    for (int i = 0; i < 10; ++i) in.add(bytes[i]);
+    const size_t obytes[5] = {(size_t)pair_cap * 8, (size_t)pair_cap * 4, (size_t)pair_cap, (size_t)entry_cap * 8, (size_t)entry_cap * 8};
+    for (int i = 0; i < 5; ++i) out.add(obytes[i]);
+    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
+    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
+    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
+    for (int i = 0; i < 10; ++i)
+        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
+    auto ip = [&](int i) -> const void * { return di + in.off[i]; };
+    auto op = [&](int i) -> void * { return obytes[i] ? dout + out.off[i] : nullptr; };
+    const int rcl = kdf_variant_windows_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, ip(0), ip(1), n_cigar, ip(2), q ? ip(3) : nullptr, q ? n_qual : 0,
+                                            q ? ip(4) : nullptr, min_baseq, ip(5), ip(6), ip(7), n_var, ip(8), n_alt, ip(9), op(0), op(1), op(2), pair_cap,
+                                            op(3), op(4), entry_cap, n_pairs_out, n_entries_out);
+    if (rcl && !(rcl == KDF_ERR_INVALID && (*n_pairs_out > pair_cap || *n_entries_out > entry_cap))) return rcl;
+    const uint64_t np = std::min<uint64_t>(*n_pairs_out, pair_cap), ne = std::min<uint64_t>(*n_entries_out, entry_cap);
+    if (np) {
+        HIPCHK(h, hipMemcpyAsync(pair_read, op(0), np * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pair_var, op(1), np * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(pair_flags, op(2), np, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (ne) {
+        HIPCHK(h, hipMemcpyAsync(entry_pos, op(3), ne * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(entry_pair, op(4), ne * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return rcl;
+}
+
+int kdf_variant_evidence_dev(kdf_engine *h, const void *d_keys, const void *d_entry_pair, uint64_t n_entries, const void *d_pair_var,
+                             const void *d_pair_flags, uint64_t n_pairs, uint64_t n_var, void *d_pair_rows, void *d_var_rows) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if ((n_pairs && !d_pair_rows) || (n_var && !d_var_rows)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: NULL pointer");
+    const bool work = n_entries && n_pairs && n_var;
+    if (work && (!d_keys || !d_entry_pair || !d_pair_var || !d_pair_flags)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: NULL pointer");
+    // (variant, tag, slot) must fit 63 bits: bit 63 keeps every word apart from the set's empty word.  Refused before
+    // anything is written, and once more below when pending work has grown the table
+    if (n_var >= (1ull << 62) || log2ceil(n_var) + 1 + h->t.log2cap > 63)
+        return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu variants against a table of 2^%u slots: variant index, tag and slot index must "
+                    "fit 63 bits together", (unsigned long long)n_var, h->t.log2cap);
+    if ((n_entries + 255) / 256 >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu entries are beyond the 2^39 a call takes", (unsigned long long)n_entries);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (work) {
+        { int rcf = pending_flush(h); if (rcf) return rcf; }
+        { int rc0 = materialize(h); if (rc0) return rc0; }
+        if (log2ceil(n_var) + 1 + h->t.log2cap > 63)
+            return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu variants against a table of 2^%u slots: variant index, tag and slot index "
+                        "must fit 63 bits together", (unsigned long long)n_var, h->t.log2cap);
+    }
+    if (n_pairs) HIPCHK(h, hipMemsetAsync(d_pair_rows, 0, (size_t)n_pairs * KV_PAIR_WORDS * 4, h->stream));
+    if (n_var) HIPCHK(h, hipMemsetAsync(d_var_rows, 0, (size_t)n_var * KV_VAR_WORDS * 8, h->stream));
+    if (!work) return KDF_OK;
+    const uint32_t log2set = log2ceil(4 * n_entries);              // two words per entry at most, load <= 0.5
+    int rc;
+    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (variant, k-mer) pairs"))) return rc;
+    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
+    EvSpan p(h->timer[T_VAR], h->prof, h->stream, 1);
+    HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        hipLaunchKernelGGL(kv_evidence_kernel<W>, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, h->stream, h->t, (const uint64_t *)d_keys,
+                           (const uint64_t *)d_entry_pair, n_entries, (const uint32_t *)d_pair_var, (const uint8_t *)d_pair_flags, n_pairs, n_var, set,
+                           log2set, (uint32_t *)d_pair_rows, (unsigned long long *)d_var_rows);
+        return 0;
+    });
+    hipLaunchKernelGGL(kv_rows_fix_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, h->stream, (unsigned long long *)d_var_rows, n_var);
+    p.stop();
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *entry_pair, uint64_t n_entries, const uint32_t *pair_var,
+                         const uint8_t *pair_flags, uint64_t n_pairs, uint64_t n_var, uint32_t *pair_rows, uint64_t *var_rows) {
+    static const char *const fn = "kdf_variant_evidence";
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if ((n_pairs && (!pair_rows || !pair_var || !pair_flags)) || (n_var && !var_rows) || (n_entries && (!keys || !entry_pair)))
+        return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t bytes[4] = {(size_t)n_entries * 8 * (size_t)h->kw, (size_t)n_entries * 8, (size_t)n_pairs * 4, (size_t)n_pairs};
+    const void *src[4] = {keys, entry_pair, pair_var, pair_flags};
+    const size_t obytes[2] = {(size_t)n_pairs * KV_PAIR_WORDS * 4, (size_t)n_var * KV_VAR_WORDS * 8};
+    Arena in, out;
+    for (int i = 0; i < 4; ++i) in.add(bytes[i]);
+    for (int i = 0; i < 2; ++i) out.add(obytes[i]);
+    int rc;
+    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
+    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
+    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
+    for (int i = 0; i < 4; ++i)
+        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
+    if ((rc = kdf_variant_evidence_dev(h, di + in.off[0], di + in.off[1], n_entries, di + in.off[2], di + in.off[3], n_pairs, n_var,
+                                       obytes[0] ? dout + out.off[0] : nullptr, obytes[1] ? dout + out.off[1] : nullptr))) return rc;
+    if (obytes[0]) HIPCHK(h, hipMemcpyAsync(pair_rows, dout + out.off[0], obytes[0], hipMemcpyDeviceToHost, h->stream));
+    if (obytes[1]) HIPCHK(h, hipMemcpyAsync(var_rows, dout + out.off[1], obytes[1], hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }

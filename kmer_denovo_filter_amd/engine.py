@@ -687,6 +687,104 @@ class KmerEngine:
                                             c_void_p(d_positions) if d_positions else None, int(n),
                                             c_void_p(d_keys) if d_keys else None))
 
+    # -- VCF mode on the device ------------------------------------------------
+    def variant_windows(self, stream: ReadStream, ref_start: np.ndarray, cigar: np.ndarray, cigar_offsets: np.ndarray,
+                        var_pos: np.ndarray, var_span: np.ndarray, var_ref_len: np.ndarray, alt: bytes,
+                        alt_offsets: np.ndarray, qual: Optional[np.ndarray] = None, qual_offsets: Optional[np.ndarray] = None,
+                        min_baseq: int = 0, pair_cap: Optional[int] = None, entry_cap: Optional[int] = None,
+                        n_bases: Optional[int] = None):
+        """Which windows of which reads span which variant (``include/kdf.h``, "VCF mode on the device").  ``ref_start``
+        int64[n_reads] (< 0: the read is skipped), ``cigar`` / ``cigar_offsets`` as for :meth:`hit_coverage`; the
+        variants ascend by ``var_pos`` int64, with ``var_span`` / ``var_ref_len`` uint32 and their ALT bytes
+        ``alt[alt_offsets[v]:alt_offsets[v + 1]]``; ``qual`` uint8 with ``qual_offsets`` int64[n_reads + 1] and
+        ``min_baseq`` switch the quality rule on.  -> (pair_read int64[p], pair_var uint32[p], pair_flags uint8[p],
+        entry_pos uint64[e], entry_pair uint64[e]): pairs ascending by (read, variant), entries by (pair, position).
+        Without caps the call sizes itself first; with caps, more pairs or entries than that raise.  ``n_bases``
+        (default: the stream's) takes a prefix of the stream."""
+        n = int(stream.n_bases if n_bases is None else n_bases)
+        offs = np.ascontiguousarray(stream.offsets, dtype=np.int64)
+        rs = np.ascontiguousarray(ref_start, dtype=np.int64)
+        cg = np.ascontiguousarray(cigar, dtype=np.uint32)
+        co = np.ascontiguousarray(cigar_offsets, dtype=np.int64)
+        vp = np.ascontiguousarray(var_pos, dtype=np.int64)
+        vs = np.ascontiguousarray(var_span, dtype=np.uint32)
+        vr = np.ascontiguousarray(var_ref_len, dtype=np.uint32)
+        al = np.frombuffer(bytes(alt), dtype=np.uint8)
+        ao = np.ascontiguousarray(alt_offsets, dtype=np.int64)
+        ql = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
+        qo = None if qual is None else np.ascontiguousarray(qual_offsets, dtype=np.int64)
+        n_reads, n_var = len(offs) - 1, len(vp)
+        if n_reads > 0 and (len(rs) != n_reads or len(co) != n_reads + 1 or (qo is not None and len(qo) != n_reads + 1)):
+            raise ValueError(f"{n_reads} reads, {len(rs)} ref_start, {len(co)} cigar_offsets entries")
+        if len(vs) != n_var or len(vr) != n_var or len(ao) != n_var + 1:
+            raise ValueError(f"{n_var} variants, {len(vs)} var_span, {len(vr)} var_ref_len, {len(ao)} alt_offsets entries")
+
+        def call(pc, ec):
+            out = (np.zeros(pc, np.int64), np.zeros(pc, np.uint32), np.zeros(pc, np.uint8), np.zeros(ec, np.uint64), np.zeros(ec, np.uint64))
+            npairs, nent = c_uint64(0), c_uint64(0)
+            o = [_vp(x) if len(x) else None for x in out]
+            rc = self._lib.kdf_variant_windows(self._h, _vp(stream.packed), _vp(stream.invalid), n, _vp(offs), n_reads, _vp(rs), _vp(cg), len(cg),
+                                               _vp(co), _vp(ql), 0 if ql is None else len(ql), _vp(qo), int(min_baseq), _vp(vp), _vp(vs), _vp(vr),
+                                               n_var, _vp(al) if len(al) else None, len(al), _vp(ao), o[0], o[1], o[2], pc, o[3], o[4], ec,
+                                               byref(npairs), byref(nent))
+            return rc, npairs.value, nent.value, out
+        if pair_cap is None or entry_cap is None:
+            rc, pc, ec, _ = call(0, 0)
+            self._ck(rc)
+            pair_cap = pc if pair_cap is None else pair_cap
+            entry_cap = ec if entry_cap is None else entry_cap
+        rc, pc, ec, out = call(int(pair_cap), int(entry_cap))
+        self._ck(rc)
+        return out[0][:pc], out[1][:pc], out[2][:pc], out[3][:ec], out[4][:ec]
+
+    def variant_windows_dev(self, d_packed: int, d_invalid: int, n_bases: int, d_offsets: int, n_reads: int, d_ref_start: int,
+                            d_cigar: int, n_cigar: int, d_cigar_offsets: int, d_qual: Optional[int], n_qual: int,
+                            d_qual_offsets: Optional[int], min_baseq: int, d_var_pos: int, d_var_span: int, d_var_ref_len: int,
+                            n_var: int, d_alt: Optional[int], n_alt: int, d_alt_offsets: int, d_pair_read: Optional[int],
+                            d_pair_var: Optional[int], d_pair_flags: Optional[int], pair_cap: int, d_entry_pos: Optional[int],
+                            d_entry_pair: Optional[int], entry_cap: int, check: bool = True):
+        """The same between device buffers: ``d_pair_read`` int64[pair_cap], ``d_pair_var`` uint32[pair_cap],
+        ``d_pair_flags`` uint8[pair_cap], ``d_entry_pos`` / ``d_entry_pair`` uint64[entry_cap].  -> (n_pairs,
+        n_entries); with both caps 0 and no output buffers it is a sizing call.  More pairs or entries than the caps
+        raise (``check=False``: the counts are returned instead, at most the caps were written).  Synchronises the
+        engine's stream twice."""
+        p = lambda x: c_void_p(x) if x else None
+        npairs, nent = c_uint64(0), c_uint64(0)
+        rc = self._lib.kdf_variant_windows_dev(self._h, p(d_packed), p(d_invalid), int(n_bases), p(d_offsets), int(n_reads), p(d_ref_start),
+                                               p(d_cigar), int(n_cigar), p(d_cigar_offsets), p(d_qual), int(n_qual), p(d_qual_offsets),
+                                               int(min_baseq), p(d_var_pos), p(d_var_span), p(d_var_ref_len), int(n_var), p(d_alt), int(n_alt),
+                                               p(d_alt_offsets), p(d_pair_read), p(d_pair_var), p(d_pair_flags), int(pair_cap), p(d_entry_pos),
+                                               p(d_entry_pair), int(entry_cap), byref(npairs), byref(nent))
+        if check or not (npairs.value > pair_cap or nent.value > entry_cap):
+            self._ck(rc)
+        return npairs.value, nent.value
+
+    def variant_evidence(self, keys: np.ndarray, entry_pair: np.ndarray, pair_var: np.ndarray, pair_flags: np.ndarray, n_var: int):
+        """Per-pair and per-variant evidence of listed windows against the table (``include/kdf.h``): ``keys`` uint64
+        (n_entries, key_words) as :meth:`hit_keys` returns them, ``entry_pair`` uint64[n_entries], ``pair_var``
+        uint32[n_pairs], ``pair_flags`` uint8[n_pairs].  -> (pair_rows uint32 (n_pairs, 2): windows, absent; var_rows
+        uint64 (n_var, 8): n, sum, min, max and the same over the alt-supporting pairs, of the distinct stored keys
+        with count > 0)."""
+        ks = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, self.key_words)
+        ep = np.ascontiguousarray(entry_pair, dtype=np.uint64)
+        pv = np.ascontiguousarray(pair_var, dtype=np.uint32)
+        pf = np.ascontiguousarray(pair_flags, dtype=np.uint8)
+        if len(ks) != len(ep) or len(pv) != len(pf):
+            raise ValueError(f"{len(ks)} key rows for {len(ep)} entries, {len(pv)} pair_var for {len(pf)} pair_flags")
+        pair_rows = np.zeros((len(pv), 2), np.uint32)
+        var_rows = np.zeros((int(n_var), 8), np.uint64)
+        v = lambda a: _vp(a) if a.size else None
+        self._ck(self._lib.kdf_variant_evidence(self._h, v(ks), v(ep), len(ep), v(pv), v(pf), len(pv), int(n_var), v(pair_rows), v(var_rows)))
+        return pair_rows, var_rows
+
+    def variant_evidence_dev(self, d_keys: int, d_entry_pair: int, n_entries: int, d_pair_var: int, d_pair_flags: int, n_pairs: int,
+                             n_var: int, d_pair_rows: int, d_var_rows: int):
+        """The same between device buffers: ``d_pair_rows`` uint32[n_pairs x 2], ``d_var_rows`` uint64[n_var x 8], both
+        written in full.  Stream order on the engine's stream; does not synchronise."""
+        p = lambda x: c_void_p(x) if x else None
+        self._ck(self._lib.kdf_variant_evidence_dev(self._h, p(d_keys), p(d_entry_pair), int(n_entries), p(d_pair_var), p(d_pair_flags),
+                                                    int(n_pairs), int(n_var), p(d_pair_rows), p(d_var_rows)))
+
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):
         """`jellyfish query -s reads.fa` over a whole stream: uint32[n_bases], the stored count of the canonical k-mer
