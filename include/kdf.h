@@ -29,9 +29,10 @@
  *     take the `_w` entry points below; their (lo, hi) forms return
  *     KDF_ERR_INVALID and name the `_w` form.  The read-stream entry points
  *     (count / count --if / scan / window counts / read depth, host or device, the double-buffered upload)
- *     work unchanged for every k.  A long engine always counts through the direct
- *     kernels (no binned pipeline, sieve or fused dump: force_path 2 / 4 and
- *     fused_dump 1 are KDF_ERR_INVALID) and is single-GPU only (kdf_export_parts*,
+ *     work unchanged for every k.  A long engine counts through the direct
+ *     kernels (no binned pipeline or fused dump: force_path 2 / 4 and
+ *     fused_dump 1 are KDF_ERR_INVALID; count --if and the scan go through the
+ *     membership sieve only under option "long_sieve") and is single-GPU only (kdf_export_parts*,
  *     kdf_add_pairs_multi_dev, kdf_set_counts_dev and hash_shift are
  *     KDF_ERR_INVALID).
  *
@@ -126,7 +127,11 @@ int kdf_flush(kdf_engine *h);
  *            a sample whose distinct k-mers exceed one table is counted slice by slice over
  *            the same stream; insert mode only; 0/1 = everything); "binned_max_positions" (positions per
  *            partition pass, <= 2^31: longer streams take several passes); "binned_filtered_min_log2cap";
- *            "sieve_bits" (bits per filter key; 0 = by size); "binned_bytes_per_position" (a flush goes
+ *            "sieve_bits" (bits per filter key; 0 = by size); "long_sieve" (k > 63 only, KDF_ERR_INVALID otherwise; 0 default,
+ *            env KDF_LONG_SIEVE=0 / 1 sets the default; 1: kdf_count_reads_filtered* and kdf_scan_reads* of a long engine go through
+ *            the membership sieve where the keys fit one, "last_count_path" / "last_scan_path" 3 -- the sieve is built by
+ *            kdf_load_filter_w*, or from the table by the next count --if or scan when there is none, and dropped when keys
+ *            join the table; force_path 1 keeps the direct kernels; 0 drops the sieve); "binned_bytes_per_position" (a flush goes
  *            binned only when pending positions x this >= table bytes: kernel C rewrites the whole table; default 70);
  *            "defer" (1 default; 0: every count call ends with a flush), "defer_max_bytes" (budget of the ring of
  *            partitioned entries, 0 = 40 % of the device's memory), "l1_positions" (size from which the pending
@@ -146,7 +151,8 @@ int kdf_flush(kdf_engine *h);
  *            "big_bucket_log2cap" (default 32; KDF_BIG_BUCKET_LOG2CAP: tables of 2^that slots and more have buckets of
  *            twice the slots -- an internal layout: dumps, queries and index files do not depend on it; a live table
  *            is re-bucketed when the option changes its bucket size); "debug_flags" (experiments: 64 one piece per
- *            workgroup in the piece sort, 2048 partition without the bucket kernel, 4096 force the skew instantiation).
+ *            workgroup in the piece sort, 2048 partition without the bucket kernel, 4096 force the skew instantiation,
+ *            8192 long_sieve's LDS form on a grid of two workgroups: small streams take several rounds).
  *            Environment, read when a partition is planned (experiments: DESIGN.md section 3.2 has what they measured):
  *            KDF_C1 (coarse bits of the partition), KDF_PIECE_FILL (how full the pieces are planned, default 0.98)
  *   stats    "binned_passes" (partition passes), "flushes" (kernel C launches), "pending_passes",
@@ -154,7 +160,9 @@ int kdf_flush(kdf_engine *h);
  *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "lazy_table", "dump_only_flushes" (flushes that wrote a dump and no table), "retained_passes" (passes such a flush applied,
  *            kept for the table: no longer "pending_passes"), "materialisations" (tables written later from retained passes),
- *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_merge_path" (1 LDS bucket
+ *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_sieve_in_lds" (the last
+ *            sieve kernel, count --if or scan, read the sieve from LDS: 1, or from L2: 0), "last_sieve_rounds" (long engines: tiles per
+ *            thread of that kernel, 1 for the L2 form), "long_sieve" (the option; 0 for k <= 63), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
  *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
  *            "hits_us" / "hits_passes" (the kh_* kernels of kdf_read_hits* / kdf_hit_list* under kdf_profile, the scan kernel

@@ -412,6 +412,9 @@ __global__ __launch_bounds__(KB_THREADS) void kdf_sieve_count_kernel(
     if constexpr (!SCAN) kdf_shard_add(ctl->windows, nwin);
 }
 
+// long keys through the same sieve (option "long_sieve")
+#include "kdf_long_sieve.h"
+
 __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
     // out3 = {distinct, windows, error}; single wave
     unsigned long long d = ctl->distinct[threadIdx.x * 16], w = ctl->windows[threadIdx.x * 16], y = ctl->tally[threadIdx.x * 16];
@@ -512,6 +515,10 @@ struct kdf_engine {
     uint32_t merge_flag_host = 0;
     int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
     int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
+    // long engines take the sieve only when asked to (option "long_sieve" / env KDF_LONG_SIEVE=1; k <= 63: always): their
+    // count --if and scan then go through kdf_long_sieve_kernel (kdf_long_sieve.h)
+    int opt_long_sieve = [] { const char *e = getenv("KDF_LONG_SIEVE"); return e ? atoi(e) != 0 : 0; }();
+    int last_sieve_in_lds = 0;                       // the last sieve kernel read the sieve from LDS (1) or from L2 (0)
     bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
     bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
     int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve
@@ -519,6 +526,9 @@ struct kdf_engine {
     uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
     uint64_t sieve_words = 0, sieve_alloc = 0;
     bool sieve_valid = false;
+    bool sieve_unfit = false;                        // long_sieve_ensure found the table's keys too many for a sieve: not asked again
+                                                     // until the keys, the filter or the sizing options change (sieve_drop)
+    uint32_t last_sieve_rounds = 0;                  // tiles per thread of the last sieve kernel of a long engine (LDS form; L2 form: 1)
     uint32_t opt_debug_flags = 0;                    // experiments only (KbPlan::dbg)
     uint64_t stat_binned_passes = 0, stat_replayed_buckets = 0;
     // optional HIP-event timing (kdf_profile).  T_STREAM, the dominant kernels: a span's tag is its tiles, so passes are the
@@ -676,6 +686,8 @@ static int by_words(kdf_engine *h, F &&f) {
 }
 // long engines: W = 3 .. 7
 static bool is_long(const kdf_engine *h) { return h->kw > 2; }
+// the sieve no longer describes the table (keys joined it, it was cleared, a new filter, other sizing options)
+static void sieve_drop(kdf_engine *h) { h->sieve_valid = false; h->sieve_unfit = false; }
 // bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
 static int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
 
@@ -1333,7 +1345,7 @@ static int pending_drop(kdf_engine *h) {
 static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads: a filter is loaded; call kdf_clear first");
     if (h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
-    h->sieve_valid = false;                          // new keys join the table: a sieve built from it earlier (scan) is stale
+    sieve_drop(h);                                   // new keys join the table: a sieve built from it earlier (scan) is stale
     h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;       // (tables are re-created by reserve / rehash: set per call)
     if (n_bases == 0) return KDF_OK;
     int rc;
@@ -1367,6 +1379,7 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
         const uint32_t spw = (uint32_t)((n_slabs + n_wg - 1) / n_wg);
         const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
         KdfSieve sv{h->sieve, h->sieve_words - 1};
+        h->last_sieve_in_lds = in_lds;
 #define SV_LAUNCH(L, S) hipLaunchKernelGGL((kdf_sieve_count_kernel<KW, L, S>), dim3(grid), dim3(KB_THREADS), 0, h->stream, \
                                            d_packed, d_invalid, n_tiles, n_bases, h->k, h->t, h->ctl, sv, spw, hits)
         if (hits) { if (in_lds) SV_LAUNCH(true, true); else SV_LAUNCH(false, true); }
@@ -1376,12 +1389,93 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
     });
 }
 
+static int sieve_prepare(kdf_engine *h, uint64_t n);
+
+// long engines, option "long_sieve": the sieve over the keys the table holds now (kdf_long_sieve_from_table_kernel)
+// unless there is one; sieve_valid tells whether the keys fit one (sieve_prepare)
+static int long_sieve_ensure(kdf_engine *h) {
+    if (h->sieve_valid || h->sieve_unfit) return KDF_OK;          // (unfit: the direct kernels, without a host round trip per call)
+    int rc;
+    if ((rc = ctl_sync(h, nullptr))) return rc;
+    if ((rc = sieve_prepare(h, h->distinct))) return rc;
+    if (!h->sieve_valid) { h->sieve_unfit = true; return KDF_OK; }
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W > 2)
+            hipLaunchKernelGGL(kdf_long_sieve_from_table_kernel<W>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, h->stream,
+                               h->t, h->sieve, h->sieve_words - 1);
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+// kdf_long_sieve_kernel over a whole stream of any length.  hits: the scan's hit words, one store per tile, or NULL for a
+// count --if.  in_lds: every workgroup copies the sieve into LDS first, so the grid is what the device holds at once and
+// every thread walks `rounds` tiles; otherwise one tile per thread, in the pieces of launch_tiles.  How many workgroups
+// of 512 a CU holds depends on the instantiation (a workgroup is 2 waves per SIMD: one workgroup where the kernel has
+// 3 waves per SIMD -- count --if at W = 3, 6, 7 -- two at 4 or 5, and the sieve's LDS bytes permitting), so the
+// runtime is asked.  debug_flags 8192 (tests): a grid of two workgroups, so that small streams take several rounds.
+static void launch_long_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles, uint64_t n_bases,
+                              uint64_t *hits, bool in_lds) {
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
+    KdfSieve sv{h->sieve, h->sieve_words - 1};
+    h->last_sieve_in_lds = in_lds;
+    h->last_sieve_rounds = 1;
+#define LSV_LAUNCH(L, S, grid, threads, lds, p, m, nt, nb, rounds, hw) \
+    hipLaunchKernelGGL((kdf_long_sieve_kernel<W, L, S>), dim3(grid), dim3(threads), lds, h->stream, p, m, nt, nb, h->k, h->t, h->ctl, sv, rounds, hw)
+    if (in_lds) {
+        const size_t lds = (size_t)h->sieve_words * 8;
+        by_words(h, [&](auto Wc) {
+            constexpr int W = decltype(Wc)::value;
+            if constexpr (W > 2) {
+                int per_cu = 0;
+                const hipError_t eo = hits ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kdf_long_sieve_kernel<W, true, true>, KDF_LSV_LDS_THREADS, lds)
+                                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kdf_long_sieve_kernel<W, true, false>, KDF_LSV_LDS_THREADS, lds);
+                if (eo != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
+                uint64_t max_wg = (uint64_t)h->n_cu * (uint64_t)std::min(std::max(per_cu, 1), 4);
+                if (h->opt_debug_flags & 8192) max_wg = 2;
+                const unsigned grid = (unsigned)std::min<uint64_t>((n_tiles + KDF_LSV_LDS_THREADS - 1) / KDF_LSV_LDS_THREADS, max_wg);
+                const uint64_t per_round = (uint64_t)grid * KDF_LSV_LDS_THREADS;
+                const uint32_t rounds = (uint32_t)((n_tiles + per_round - 1) / per_round);
+                h->last_sieve_rounds = rounds;
+                if (hits) LSV_LAUNCH(true, true, grid, KDF_LSV_LDS_THREADS, lds, d_packed, d_invalid, n_tiles, n_bases, rounds, hits);
+                else LSV_LAUNCH(true, false, grid, KDF_LSV_LDS_THREADS, lds, d_packed, d_invalid, n_tiles, n_bases, rounds, hits);
+            }
+            return 0;
+        });
+    } else {
+        static_assert(KDF_LSV_THREADS == 256, "launch_tiles counts workgroups of 256");
+        launch_tiles(h, d_packed, d_invalid, n_tiles, n_bases, hits,
+                     [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *hw) {
+            constexpr int W = decltype(Wc)::value;
+            if constexpr (W > 2) {
+                if (hits) LSV_LAUNCH(false, true, blocks, KDF_LSV_THREADS, 0, p, m, nt, nb, 1u, hw);
+                else LSV_LAUNCH(false, false, blocks, KDF_LSV_THREADS, 0, p, m, nt, nb, 1u, hw);
+            }
+        });
+    }
+#undef LSV_LAUNCH
+    span.stop();
+}
+
 static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (!h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads_filtered: no filter loaded (kdf_load_filter)");
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     if (n_tiles == 0) return KDF_OK;
     { int rc0 = materialize(h); if (rc0) return rc0; }
-    if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
+    if (is_long(h)) {
+        if (h->opt_long_sieve && h->opt_force_path != 1) {
+            int rc = long_sieve_ensure(h);                         // (the option was set, or keys were added, after the filter was loaded)
+            if (rc) return rc;
+            if (h->sieve_valid) {
+                launch_long_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+                HIPCHK(h, hipGetLastError());
+                h->last_path = 3;
+                return KDF_OK;
+            }
+        }
+    } else if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
         EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
         launch_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
         span.stop();
@@ -1645,6 +1739,7 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     h->capacity_hint = capacity_hint;
     h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
     if (is_long(h)) { h->opt_fused_dump = 0; h->opt_lazy_table = 0; }
+    else h->opt_long_sieve = 0;                      // (KDF_LONG_SIEVE is for long engines: k <= 63 takes its sieve anyway)
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
@@ -1716,7 +1811,7 @@ int kdf_clear(kdf_engine *h) {
     int rc = ctl_reset(h, false);
     if (rc) return rc;
     h->distinct = 0; h->windows = 0; h->filter_mode = false;
-    h->lazy_empty = true; h->sieve_valid = false; h->zero_keys = false;
+    h->lazy_empty = true; sieve_drop(h); h->zero_keys = false;
     h->grow_ratio = 0.0;
     if ((rc = pending_drop(h))) return rc;     // what was counted but not yet applied is dropped with the rest
     return KDF_OK;
@@ -1875,7 +1970,7 @@ static int long_bad_keys(kdf_engine *h, const char *fn) {
 // the table becomes exactly the n keys at d_lo / d_hi (device arrays; long keys: the rows at d_lo) with count 0
 static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t n, const char *fn) {
     int rc;
-    h->sieve_valid = false;
+    sieve_drop(h);
     if ((rc = pending_drop(h))) return rc;            // the table becomes the filter: whatever was pending goes with the old contents
     // size the table for n keys at load <= 0.5, then start from empty
     const uint32_t want = cap_log2_for(n);
@@ -1897,7 +1992,7 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
         if ((rc = long_bad_keys(h, fn))) return rc;
         if (full) return fail(h, KDF_ERR_TABLE_FULL, "%s: bucket overflow", fn);
     }
-    if (is_long(h)) return KDF_OK;                   // (no sieve for long keys)
+    if (is_long(h)) return h->opt_long_sieve ? long_sieve_ensure(h) : KDF_OK;     // (long keys: from the table just loaded, and only when asked to)
     if ((rc = sieve_prepare(h, n)) != KDF_OK) return rc;
     if (h->sieve_valid && n) {
         by_width(h, [&](auto KWc) {
@@ -1953,7 +2048,7 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
     bool counts = true;
     for (uint32_t s = 0; s < nseg; ++s) { total += n[s]; nmax = std::max(nmax, n[s]); if (n[s] && !d_cnt[s]) counts = false; }
     if (total == 0) return KDF_OK;
-    h->sieve_valid = false;                          // keys may join the table that the sieve has not seen
+    sieve_drop(h);                                   // keys may join the table that the sieve has not seen
     h->zero_keys = true;                             // ... with a count of 0 (NULL counts, a 0 in the array)
     int rc;
     if ((rc = pending_flush(h))) return rc;
@@ -2392,6 +2487,18 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
     { int rcf = pending_flush(h); if (rcf) return rcf; }
     { int rc0 = materialize(h); if (rc0) return rc0; }
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    if (is_long(h) && h->opt_long_sieve && h->opt_force_path != 1) {
+        // long keys (option "long_sieve"): survivors probe in place and the tile's hit word is stored whole -- any stream length
+        int rc = long_sieve_ensure(h);
+        if (rc) return rc;
+        if (h->sieve_valid) {
+            h->last_scan_path = 3;
+            launch_long_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, n_bases, (uint64_t *)d_hit_bits,
+                              h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+            HIPCHK(h, hipGetLastError());
+            return KDF_OK;
+        }
+    }
     if (!is_long(h) && h->opt_force_path != 1 && n_tiles * KDF_TILE < (1ull << 32)) {
         // through the membership sieve (section 3.5 of DESIGN.md): an index that was loaded with kdf_add_pairs has none yet
         int rc;
@@ -3622,7 +3729,13 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "l1_positions") h->opt_l1_positions = (uint64_t)std::max<int64_t>(value, KDF_TILE);
     else if (n == "l1_direct_positions") h->opt_l1_direct_positions = (uint64_t)std::max<int64_t>(value, 0);
-    else if (n == "sieve_bits") h->opt_sieve_bits = (int)value;
+    else if (n == "sieve_bits") { h->opt_sieve_bits = (int)value; h->sieve_unfit = false; }     // (other sizing: the keys may fit now)
+    else if (n == "long_sieve") {
+        if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "long_sieve: k=%d always takes the sieve where it fits (the option is for k > 63)", h->k);
+        if (value != 0 && value != 1) return fail(h, KDF_ERR_INVALID, "long_sieve %lld: must be 0 or 1", (long long)value);
+        if (!value) sieve_drop(h);                    // off: the direct kernels from now on; on: built from the table by the next count --if or scan
+        h->opt_long_sieve = (int)value;
+    }
     else if (n == "debug_flags") h->opt_debug_flags = (uint32_t)value;
     else return fail(h, KDF_ERR_INVALID, "kdf_set_option: unknown option %s", name);
     return KDF_OK;
@@ -3677,6 +3790,9 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
     else if (n == "last_scan_path") *value = h->last_scan_path;
+    else if (n == "last_sieve_in_lds") *value = h->last_sieve_in_lds;
+    else if (n == "last_sieve_rounds") *value = h->last_sieve_rounds;
+    else if (n == "long_sieve") *value = h->opt_long_sieve;
     else if (n == "last_merge_path") *value = h->last_merge_path;
     else if (n == "heavy_buckets") *value = (int64_t)h->stat_heavy_buckets;
     else if (n == "fused_dumps") *value = (int64_t)h->stat_fused_dumps;
