@@ -815,6 +815,91 @@ int kdf_reader_ref_length(kdf_reader *r, int i);
 void kdf_reader_close(kdf_reader *r);
 const char *kdf_reader_error(const kdf_reader *r);
 
+/* ---------------------------------------------------- device BAM feeder ---- */
+
+/* The feeder with the heavy part on the device: the host reads the COMPRESSED bytes of a BAM and
+ * plans the batch (kdf_bamraw_*, host only, no GPU needed); the device inflates the BGZF blocks, walks the records
+ * with the semantics of kdf_bam_open and writes the packed stream straight into HBM (kdf_bamdev_decode_dev).  It
+ * serves the counting legs: sequence only -- no names, ordinals, CIGAR, qualities or SA.
+ *
+ * One BGZF block of a batch.  All fields come from the block's gzip header and trailer alone. */
+typedef struct {
+    uint64_t comp_off;   /* offset of the raw DEFLATE payload in the batch's compressed buffer */
+    uint64_t out_off;    /* offset of the block's inflated bytes in the batch's inflated span (running sum of isize) */
+    uint64_t file_off;   /* where the block starts in the file (error messages) */
+    uint32_t comp_len;   /* payload bytes (header, extra field and trailer are not copied) */
+    uint32_t isize;      /* inflated bytes (the trailer's ISIZE); 0: nothing to decode */
+} kdf_bgzf_block;
+/* One sub-range of a batch: the records a range reader (kdf_bam_open_range) over the same file cuts would yield.
+ * start: offset in the inflated span of the sub-range's first record (KDF_SUB_NONE: the sub-range is empty).
+ * stop: offset of its END ZONE, the first BGZF block at or after the next cut (KDF_SUB_NONE: the file's end).  The walk
+ * runs from start; once a record STARTS at or after stop, only the QNAME run that straddles stop is finished (collapse
+ * = 0: the walk ends at that record).  flags bit 0 (KDF_SUB_AT_EOF): the batch's inflated span ends where the file
+ * ends, so running out of bytes is the end of the file and not a short tail. */
+typedef struct { uint64_t start, stop, flags; } kdf_bam_subrange;
+#define KDF_SUB_NONE   0xFFFFFFFFFFFFFFFFull
+#define KDF_SUB_AT_EOF 1ull
+/* sub_status of kdf_bamdev_decode_dev */
+#define KDF_SUB_DONE       0
+#define KDF_SUB_UNFINISHED 1   /* the batch's bytes ended before the stop record and the file has more: replay with a longer tail */
+#define KDF_SUB_CORRUPT    2   /* block_size < 32, field sizes beyond block_size, negative l_seq, or a record cut off by the file's end */
+
+/* The raw range planner.  Part `part` of `parts` of the file (the same cuts as kdf_bam_open_range) is cut again every
+ * subrange_bytes of FILE (0: 1 MiB).  Opening reads the BAM header once; the start of each sub-range is located when a
+ * batch first needs it, exactly as kdf_bam_open_range locates a part's start -- the only inflating the host does. */
+typedef struct kdf_bamraw kdf_bamraw;
+int kdf_bamraw_open(const char *path, uint32_t flag_off, int collapse, int part, int parts, uint64_t subrange_bytes,
+                    kdf_bamraw **out);
+/* Sub-ranges of the part (0 for a BAM without records). */
+int kdf_bamraw_subranges(kdf_bamraw *r, uint64_t *n_subranges);
+/* The next batch: a contiguous run of whole BGZF blocks, their payloads copied back to back into comp_buf (comp_cap
+ * bytes; page-locked memory of kdf_host_alloc is meant, pageable works), with the block table (cap_blocks entries) and
+ * the sub-range table (cap_subs entries).  It holds as many consecutive sub-ranges, from the cursor on, as fit with
+ * `tail_blocks` further blocks behind the last sub-range's stop block (0: 2) -- the walk of a sub-range runs past
+ * `stop` to its stop record; sub-ranges inside a batch need no tail, the next one's bytes follow.  *n_subs = 0: the
+ * part is done.  *first_sub: index in the part of subs[0].  KDF_ERR_INVALID when not even one sub-range fits. */
+int kdf_bamraw_next(kdf_bamraw *r, void *comp_buf, uint64_t comp_cap, uint32_t tail_blocks,
+                    kdf_bgzf_block *blocks, uint64_t cap_blocks, kdf_bam_subrange *subs, uint64_t cap_subs,
+                    uint64_t *n_blocks, uint64_t *n_subs, uint64_t *first_sub, uint64_t *comp_bytes,
+                    uint64_t *inflated_bytes);
+/* Move the cursor: the next batch starts with sub-range `sub` of the part (the replay of an unfinished sub-range). */
+int kdf_bamraw_seek(kdf_bamraw *r, uint64_t sub);
+void kdf_bamraw_close(kdf_bamraw *r);
+const char *kdf_bamraw_error(const kdf_bamraw *r);
+
+/* Inflate n_blocks BGZF blocks on the device, on the engine's stream: block b's payload d_comp[comp_off, + comp_len)
+ * -> d_out[out_off, + isize).  Raw DEFLATE: stored, fixed and dynamic blocks, any number of them per BGZF block.  No
+ * byte outside the payload is read and none outside [out_off, out_off + isize) is written, whatever the payload holds;
+ * a table entry that does not fit d_out's out_cap bytes, or states more than 64 KB, is not decoded at all (status
+ * KDF_INF_BOUNDS; the call returns KDF_ERR_INVALID).  A block the device decoder rejects (its KDF_INF_* status,
+ * csrc/kdf_inflate.h; d_block_status, n_blocks uint32 on the device, may be NULL) does not fail the call: it is inflated
+ * again with zlib on the host and its bytes are patched into d_out (stat "bamdev_fallback_blocks" counts them); only a
+ * block zlib rejects too is KDF_ERR_IO, with its file offset in the message.  Synchronises.  No CRC is checked (the host
+ * reader checks none).  The INPUT side of the table is trusted: the entry point does not know how large d_comp is, so
+ * comp_off + comp_len of every entry must lie inside it (kdf_bamraw_next's tables do); inside a payload the decoder
+ * never reads past comp_len.  Option "bamdev_host_inflate" = 1 sends EVERY block through that zlib path (tells a decoder
+ * fault from a file fault; the tests reach the patch path with it: no block zlib wrote is rejected on the device).  It is
+ * a diagnostic, not for timing: every patched block drains the stream twice. */
+int kdf_bgzf_inflate_dev(kdf_engine *h, const void *d_comp, const void *d_blocks, uint64_t n_blocks,
+                         void *d_out, uint64_t out_cap, void *d_block_status);
+/* Decode one planned batch into a read stream in caller-owned device memory, in exactly the layout kdf_reader_next
+ * produces: d_packed / d_invalid hold kdf_stream_words(cap_bases) words, d_offsets cap_reads + 1 int64.  Inflate, walk
+ * (one walker per sub-range), scan, pack; one synchronisation, because the sizes are learnt on the way.  The stream
+ * holds the sub-ranges' reads in sub-range order UP TO the first sub-range that is not KDF_SUB_DONE: *n_reads and
+ * *n_bases count those, sub_status[n_sub] (host) says where and why it ended.  The caller replays from the first
+ * KDF_SUB_UNFINISHED sub-range with a longer tail (kdf_bamraw_seek); nothing is lost or doubled.  KDF_SUB_CORRUPT
+ * returns KDF_ERR_IO, a stream larger than cap_bases / cap_reads KDF_ERR_INVALID (nothing is written then).  Every
+ * word below kdf_stream_words(*n_bases) is written: positions at and past *n_bases are invalid in the mask and zero in
+ * the packed array.  The call returns with its last kernels (the walk's write pass and the pack) queued on the engine's
+ * stream, and they read d_blocks, d_subranges and the engine's scratch: none of the inputs may be overwritten -- by a copy
+ * on another stream, say -- before the stream has reached that point (an event recorded on it after the call orders that;
+ * reads.stream_bam_device does so).  Stats: "bamdev_fallback_blocks", and under kdf_profile "bamdev_inflate_us", "bamdev_walk_us",
+ * "bamdev_pack_us" with their "_passes". */
+int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_blocks, uint64_t n_blocks,
+                          const void *d_subranges, uint64_t n_sub, uint32_t flag_off, int collapse,
+                          void *d_packed, void *d_invalid, uint64_t cap_bases, void *d_offsets, uint64_t cap_reads,
+                          uint64_t *n_bases, uint64_t *n_reads, uint32_t *sub_status);
+
 /* N4: the informative-reads BAM (discovery/pipeline.py:1979-2079 `_write_informative_reads_discovery`,
  * vcf/pipeline.py:1307-1357 `_write_informative_reads`: pysam write + `samtools sort` + `samtools index`).
  * Copies the records ordinals[0..n) (strictly ascending file record numbers, see

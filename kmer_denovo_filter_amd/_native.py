@@ -162,6 +162,17 @@ SYMBOLS = [
     ("kdf_sketch_drop", c_int, [_P]),
     ("kdf_sketch_estimate_registers", c_int, [_P, c_uint32, POINTER(ctypes.c_double)]),
     ("kdf_spool_sketch", c_int, [_P, _P]),
+    # device BAM feeder: the raw range planner (host) and the batch decoder (device)
+    ("kdf_bamraw_open", c_int, [c_char_p, c_uint32, c_int, c_int, c_int, c_uint64, POINTER(_P)]),
+    ("kdf_bamraw_subranges", c_int, [_P, POINTER(c_uint64)]),
+    ("kdf_bamraw_next", c_int, [_P, _P, c_uint64, c_uint32, _P, c_uint64, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64),
+                                POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_bamraw_seek", c_int, [_P, c_uint64]),
+    ("kdf_bamraw_close", None, [_P]),
+    ("kdf_bamraw_error", c_char_p, [_P]),
+    ("kdf_bgzf_inflate_dev", c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P]),
+    ("kdf_bamdev_decode_dev", c_int, [_P, _P, _P, c_uint64, _P, c_uint64, c_uint32, c_int, _P, _P, c_uint64, _P, c_uint64,
+                                      POINTER(c_uint64), POINTER(c_uint64), _P]),
 ]
 
 _lib = None
@@ -233,6 +244,13 @@ def check_spool(rc: int, spool=None):
     if rc != KDF_OK:
         lib = load()
         msg = lib.kdf_spool_error(spool)
+        raise KdfError(rc, msg.decode(errors="replace") if msg else "unknown error")
+
+
+def check_bamraw(rc: int, reader=None):
+    if rc != KDF_OK:
+        lib = load()
+        msg = lib.kdf_bamraw_error(reader)
         raise KdfError(rc, msg.decode(errors="replace") if msg else "unknown error")
 
 

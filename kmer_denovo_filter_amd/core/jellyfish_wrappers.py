@@ -129,6 +129,10 @@ def _stream_bam_pass(engine, bam_path, threads, filtered, tally, spool, sketch):
     # chunk / parse pipeline (one pipeline's chunker is a serial stage: 2.0 Gbase/s whatever the thread count).
     world, rank, _ = dist_env.world_rank()
     local = _reader_pipelines(threads)
+    if os.environ.get("KDF_DEVICE_FEEDER", "0") not in ("", "0"):
+        return _stream_bam_device_pass(engine, bam_path, threads, filtered, tally, spool, sketch, world, rank, local)
+    global LAST_FEEDER
+    LAST_FEEDER = {"path": "host"}
     per = max(1, threads // local)
     readers = []
     try:
@@ -143,6 +147,24 @@ def _stream_bam_pass(engine, bam_path, threads, filtered, tally, spool, sketch):
     finally:
         for rd in readers:
             rd.close()
+
+
+LAST_FEEDER = None            # the feeder of the last BAM pass: {"path": "host"} or stream_bam_device's record (batches, fallback blocks, replays)
+
+
+def _stream_bam_device_pass(engine, bam_path, threads, filtered, tally, spool, sketch, world, rank, local):
+    """KDF_DEVICE_FEEDER=1 (opt-in): the same pass with the heavy part of the feeder on the device -- the host threads
+    only plan batches of compressed BGZF blocks, the GPU inflates them, walks the records and packs the stream
+    (``reads.stream_bam_device``).  The file is cut into the same parts, a rank takes the same contiguous share of them;
+    KDF_FEEDER_SUBRANGE_MB sets the cut inside a part (file MiB per walker; default 1)."""
+    global LAST_FEEDER
+    from .. import reads
+    sub = int(float(os.environ.get("KDF_FEEDER_SUBRANGE_MB", "1")) * (1 << 20))
+    parts = [(rank * local + j, world * local) for j in range(local)]
+    n = reads.stream_bam_device(engine, str(bam_path), parts, filtered=filtered, tally=tally, sketch=sketch, spool=spool,
+                                subrange_bytes=max(sub, 1 << 12), producers=min(max(1, int(threads)), 16))
+    LAST_FEEDER = reads.LAST_FEEDER
+    return n
 
 
 def _reader_pipelines(threads):

@@ -3,6 +3,7 @@
 // kernel.  No CPU fallback exists in this library: every entry point either
 // runs on the GPU or returns an error.
 #include <hip/hip_runtime.h>
+#include <zlib.h>
 #include <algorithm>
 #include <array>
 #include <cstdarg>
@@ -288,6 +289,7 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 #include "kdf_coverage.h"
 #include "kdf_variants.h"
 #include "kdf_spool.h"
+#include "kdf_bamdev.h"
 
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
@@ -430,10 +432,10 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_COUNT = BUF_VAR + 5 };
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_BD = BUF_VAR + 5, BUF_COUNT = BUF_BD + 3 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack"};
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -558,6 +560,12 @@ struct kdf_engine {
     KdfSketch sk{};                                  // the register cells (device) and p
     uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
     unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
+    // ---- device BAM feeder (kdf_bamdev.h): grow-only scratch kept between batches ---------------------------------------------
+    DevBuf *const bd_buf = buf + BUF_BD;             // [3] 0 inflated span, 1 block / sub-range status, counts, bases and totals, 2 per-read sequence offsets
+    // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
+    // "bamdev_host_inflate": tells a decoder fault from a file fault, and lets the tests walk the patch path, which no file zlib wrote takes)
+    int opt_bd_host_inflate = 0;
+    uint64_t stat_bd_fallback = 0;                   // blocks the device decoder rejected and zlib inflated (stat "bamdev_fallback_blocks")
     std::string err;
 };
 
@@ -3362,6 +3370,156 @@ int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]) {
     return KDF_OK;
 }
 
+// ------------------------------------------------------ device BAM feeder (kdf_bamdev.h) ----
+
+// Blocks the device decoder rejected (status[b] != 0, host copy): inflate each again with zlib and patch its bytes into
+// d_out.  The block table (one copy) and the flagged payloads come back from the device: this path is rare (never taken
+// for zlib-made files), and the caller owns no host copy of them.  Drains the stream, twice per patched block.
+static int bd_fallback(kdf_engine *h, const char *fn, const uint8_t *d_comp, const kdf_bgzf_block *d_blocks, uint64_t n_blocks,
+                       uint8_t *d_out, const uint32_t *status) {
+    std::vector<uint8_t> comp, data;
+    std::vector<kdf_bgzf_block> table;                                // fetched once, when the first flagged block is met
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        if (status[b] == KDF_INF_OK) continue;
+        if (status[b] == KDF_INF_BOUNDS)
+            return fail(h, KDF_ERR_INVALID, "%s: block table entry %llu does not fit the inflated buffer (or states more than 64 KB)", fn, (unsigned long long)b);
+        if (table.empty()) {
+            table.resize(n_blocks);
+            HIPCHK(h, hipMemcpyAsync(table.data(), d_blocks, n_blocks * sizeof(kdf_bgzf_block), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+        const kdf_bgzf_block blk = table[b];
+        if (blk.isize == 0) continue;                                // (nothing to inflate, as the host reader's bgzf_inflate)
+        comp.resize((size_t)blk.comp_len + 1); data.resize((size_t)blk.isize + 1);
+        if (blk.comp_len) HIPCHK(h, hipMemcpyAsync(comp.data(), d_comp + blk.comp_off, blk.comp_len, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        z_stream zs; memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) return fail(h, KDF_ERR_NOMEM, "%s: inflateInit2 failed", fn);
+        zs.next_in = comp.data(); zs.avail_in = blk.comp_len;
+        zs.next_out = data.data(); zs.avail_out = blk.isize;
+        const int zr = inflate(&zs, Z_FINISH);
+        const bool ok = zr == Z_STREAM_END && zs.avail_out == 0;
+        inflateEnd(&zs);
+        if (!ok)
+            return fail(h, KDF_ERR_IO, "%s: the BGZF block at file offset %llu does not inflate (device status %u, zlib %d)", fn,
+                        (unsigned long long)blk.file_off, status[b], zr);
+        HIPCHK(h, hipMemcpyAsync(d_out + blk.out_off, data.data(), blk.isize, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));                  // (data is reused by the next block)
+        h->stat_bd_fallback++;
+    }
+    return KDF_OK;
+}
+
+static int bd_inflate_launch(kdf_engine *h, const void *d_comp, const void *d_blocks, uint64_t n_blocks, void *d_out, uint64_t out_cap, uint32_t *d_status) {
+    if (!n_blocks) return KDF_OK;
+    EvSpan span(h->timer[T_BD_INF], h->prof, h->stream);
+    hipLaunchKernelGGL(kdf_bd_inflate_kernel, dim3((unsigned)((n_blocks + KDF_BD_WAVES - 1) / KDF_BD_WAVES)), dim3(64 * KDF_BD_WAVES), 0, h->stream,
+                       (const uint8_t *)d_comp, (const kdf_bgzf_block *)d_blocks, n_blocks, (uint8_t *)d_out, out_cap, d_status);
+    HIPCHK(h, hipGetLastError());
+    span.stop();
+    return KDF_OK;
+}
+
+int kdf_bgzf_inflate_dev(kdf_engine *h, const void *d_comp, const void *d_blocks, uint64_t n_blocks, void *d_out, uint64_t out_cap,
+                         void *d_block_status) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n_blocks && (!d_comp || !d_blocks || !d_out)) return fail(h, KDF_ERR_INVALID, "kdf_bgzf_inflate_dev: NULL pointer");
+    if (n_blocks > (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_bgzf_inflate_dev: %llu blocks in one call", (unsigned long long)n_blocks);
+    if (!n_blocks) return KDF_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    uint32_t *d_status = (uint32_t *)d_block_status;
+    if (!d_status) {
+        const int rc = eng_reserve(h, h->bd_buf[1], n_blocks * 4);
+        if (rc) return rc;
+        d_status = (uint32_t *)h->bd_buf[1].p;
+    }
+    { const int rc = bd_inflate_launch(h, d_comp, d_blocks, n_blocks, d_out, out_cap, d_status); if (rc) return rc; }
+    std::vector<uint32_t> status(n_blocks);
+    HIPCHK(h, hipMemcpyAsync(status.data(), d_status, n_blocks * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->opt_bd_host_inflate) for (uint32_t &st : status) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
+    return bd_fallback(h, "kdf_bgzf_inflate_dev", (const uint8_t *)d_comp, (const kdf_bgzf_block *)d_blocks, n_blocks, (uint8_t *)d_out, status.data());
+}
+
+int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_blocks, uint64_t n_blocks, const void *d_subranges, uint64_t n_sub,
+                          uint32_t flag_off, int collapse, void *d_packed, void *d_invalid, uint64_t cap_bases, void *d_offsets,
+                          uint64_t cap_reads, uint64_t *n_bases, uint64_t *n_reads, uint32_t *sub_status) {
+    const char *fn = "kdf_bamdev_decode_dev";
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (!d_packed || !d_invalid || !d_offsets || !n_bases || !n_reads || (n_sub && (!d_subranges || !sub_status)) || (n_blocks && (!d_comp || !d_blocks)))
+        return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    if (n_blocks > (1ull << 24) || n_sub > (1ull << 24))
+        return fail(h, KDF_ERR_INVALID, "%s: %llu blocks / %llu sub-ranges in one batch", fn, (unsigned long long)n_blocks, (unsigned long long)n_sub);
+    HIPCHK(h, hipSetDevice(h->device));
+    *n_bases = *n_reads = 0;
+    // scratch: [0] the inflated span (a BGZF block inflates to <= 64 KB) | [1] block status u32[nb] . sub status u32[ns] .
+    // counts[ns] . bases[ns] . totals u64[4] | [2] per-read sequence offsets u64[cap_reads]
+    const uint64_t out_cap = n_blocks * KDF_BGZF_MAX_ISIZE;
+    const size_t o_sub = (size_t)((n_blocks * 4 + 15) & ~15ull), o_cnt = o_sub + (size_t)((n_sub * 4 + 15) & ~15ull);
+    const size_t o_base = o_cnt + (size_t)n_sub * sizeof(KdfBdSubCount), o_tot = o_base + (size_t)n_sub * sizeof(KdfBdSubCount);
+    int rc;
+    if ((rc = eng_reserve(h, h->bd_buf[0], (size_t)out_cap + 8))) return rc;
+    if ((rc = eng_reserve(h, h->bd_buf[1], o_tot + 32))) return rc;
+    if ((rc = eng_reserve(h, h->bd_buf[2], (size_t)(cap_reads + 1) * 8))) return rc;
+    uint8_t *d_out = (uint8_t *)h->bd_buf[0].p, *small = (uint8_t *)h->bd_buf[1].p;
+    uint32_t *d_bst = (uint32_t *)small, *d_sst = (uint32_t *)(small + o_sub);
+    KdfBdSubCount *d_cnt = (KdfBdSubCount *)(small + o_cnt), *d_base = (KdfBdSubCount *)(small + o_base);
+    uint64_t *d_tot = (uint64_t *)(small + o_tot), *d_src = (uint64_t *)h->bd_buf[2].p;
+    const kdf_bgzf_block *blocks = (const kdf_bgzf_block *)d_blocks;
+    const kdf_bam_subrange *subs = (const kdf_bam_subrange *)d_subranges;
+    std::vector<uint32_t> bst(n_blocks);
+    uint64_t tot[4] = {0, 0, 0, 0};
+    const unsigned walk_grid = (unsigned)((n_sub + 63) / 64);
+
+    if ((rc = bd_inflate_launch(h, d_comp, d_blocks, n_blocks, d_out, out_cap, d_bst))) return rc;
+    // count, scan, read the sizes back; a second turn only when a block had to be inflated on the host
+    for (int turn = 0; turn < 2; ++turn) {
+        EvSpan span(h->timer[T_BD_WALK], h->prof, h->stream, turn == 0);
+        if (n_sub) {
+            hipLaunchKernelGGL(kdf_bd_walk_kernel<false>, dim3(walk_grid), dim3(64), 0, h->stream, d_out, blocks, n_blocks, out_cap, subs, n_sub,
+                               flag_off, collapse, d_cnt, d_sst, (const KdfBdSubCount *)nullptr, (int64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0);
+            HIPCHK(h, hipGetLastError());
+        }
+        hipLaunchKernelGGL(kdf_bd_scan_kernel, dim3(1), dim3(1), 0, h->stream, d_cnt, d_sst, n_sub, d_base, d_tot, (int64_t *)d_offsets, cap_reads);
+        HIPCHK(h, hipGetLastError());
+        span.stop();
+        if (turn == 0 && n_blocks) HIPCHK(h, hipMemcpyAsync(bst.data(), d_bst, n_blocks * 4, hipMemcpyDeviceToHost, h->stream));
+        if (n_sub) HIPCHK(h, hipMemcpyAsync(sub_status, d_sst, n_sub * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        bool flagged = false;
+        if (turn == 0 && h->opt_bd_host_inflate) for (uint32_t &st : bst) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
+        if (turn == 0) for (uint64_t b = 0; b < n_blocks; ++b) flagged |= bst[b] != KDF_INF_OK;
+        if (!flagged) break;
+        if ((rc = bd_fallback(h, fn, (const uint8_t *)d_comp, blocks, n_blocks, d_out, bst.data()))) return rc;
+    }
+    const uint64_t nr = tot[0], nbases = tot[1], first_bad = tot[2];
+    if (first_bad < n_sub && sub_status[first_bad] == KDF_SUB_CORRUPT)
+        return fail(h, KDF_ERR_IO, "%s: corrupt BAM record in sub-range %llu of the batch (field sizes, or a record cut off by the end of the file)", fn,
+                    (unsigned long long)first_bad);
+    if (nr > cap_reads || nbases > cap_bases)
+        return fail(h, KDF_ERR_INVALID, "%s: the batch holds %llu reads / %llu stream positions, the buffers %llu / %llu", fn, (unsigned long long)nr,
+                    (unsigned long long)nbases, (unsigned long long)cap_reads, (unsigned long long)cap_bases);
+    if (first_bad) {
+        EvSpan span(h->timer[T_BD_WALK], h->prof, h->stream, 0);
+        hipLaunchKernelGGL(kdf_bd_walk_kernel<true>, dim3((unsigned)((first_bad + 63) / 64)), dim3(64), 0, h->stream, d_out, blocks, n_blocks, out_cap, subs,
+                           first_bad, flag_off, collapse, (KdfBdSubCount *)nullptr, (uint32_t *)nullptr, (const KdfBdSubCount *)d_base, (int64_t *)d_offsets,
+                           d_src, cap_reads);
+        HIPCHK(h, hipGetLastError());
+        span.stop();
+    }
+    {
+        EvSpan span(h->timer[T_BD_PACK], h->prof, h->stream);
+        const uint64_t n_words = kdf_stream_geom(nbases).mask_words;
+        hipLaunchKernelGGL(kdf_bd_pack_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, h->stream, d_out, (const int64_t *)d_offsets,
+                           d_src, nr, nbases, n_words, (uint64_t *)d_packed, (uint64_t *)d_invalid);
+        HIPCHK(h, hipGetLastError());
+        span.stop();
+    }
+    *n_reads = nr; *n_bases = nbases;
+    return KDF_OK;
+}
+
 // ------------------------------------------------------ distinct k-mer sketch ----
 
 int kdf_sketch_begin(kdf_engine *h, uint32_t log2_registers) {
@@ -3719,6 +3877,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "defer") h->opt_defer = value != 0;
     else if (n == "defer_max_bytes") h->opt_defer_max_bytes = (uint64_t)value;
+    else if (n == "bamdev_host_inflate") h->opt_bd_host_inflate = value != 0;
     else if (n == "fused_dump") {
         if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "fused_dump: not available for k > 63 (no binned pipeline for long keys)");
         h->opt_fused_dump = value != 0;
@@ -3762,6 +3921,7 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
             for (int i = 0; i < KDF_SHARDS; ++i) *value += (int64_t)c[i * 16];
         }
     }
+    else if (n == "bamdev_fallback_blocks") *value = (int64_t)h->stat_bd_fallback;
     else if (n == "sketch_state") *value = h->sk_on ? 1 : 0;
     else if (n == "sketch_log2_registers") *value = h->sk_on ? (int64_t)h->sk.p : 0;
     else if (n == "sketch_windows") {

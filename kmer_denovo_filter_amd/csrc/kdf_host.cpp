@@ -1035,40 +1035,70 @@ int locate_range_start(const char *path, uint64_t F, uint64_t file_size, int32_t
 
 }  // namespace
 
+namespace {
+
+// What a range reader or a raw planner needs to know of a BAM before it cuts it: the header (read ONCE, through a plain
+// sequential reader that is handed back), the virtual offset of the first record and the file's size.
+struct BamLayout {
+    kdf_reader *hr = nullptr;          // the header reader (the caller closes it)
+    bool has_records = false;
+    uint64_t data_block = 0; size_t data_uoff = 0;
+    int32_t n_ref = 0;
+    uint64_t file_size = 0;
+    uint64_t cut(int p, int parts) const {
+        const uint64_t span = file_size > data_block ? file_size - data_block : 0;
+        return data_block + (uint64_t)((unsigned __int128)span * (unsigned)p / (unsigned)parts);
+    }
+};
+
+int bam_layout(const char *path, uint32_t flag_off, int collapse, BamLayout &L) {
+    int rc = kdf_bam_open(path, flag_off, collapse, 1, &L.hr);
+    if (rc) return rc;
+    // the first record's virtual offset: the header ended at inbuf[inpos]; the sequential reader appended whole blocks
+    FILE *fp = fopen(path, "rb");
+    if (!fp) { kdf_reader_close(L.hr); L.hr = nullptr; return rfail(nullptr, KDF_ERR_IO, "cannot open %s", path); }
+    MiniBgzf mz(fp); std::string e;
+    const size_t hdr_end = L.hr->inpos;
+    while (mz.buf.size() <= hdr_end) if (!mz.more(e)) break;
+    fseeko(fp, 0, SEEK_END); L.file_size = (uint64_t)ftello(fp);
+    fclose(fp);
+    if (!e.empty()) { kdf_reader_close(L.hr); L.hr = nullptr; return rfail(nullptr, KDF_ERR_IO, "%s: %s", path, e.c_str()); }
+    L.n_ref = (int32_t)L.hr->ref_names.size();
+    L.has_records = mz.buf.size() > hdr_end;
+    if (!L.has_records) return KDF_OK;
+    size_t bi = mz.blocks.size() - 1;
+    while (mz.blocks[bi].first > hdr_end) --bi;
+    L.data_block = mz.blocks[bi].second; L.data_uoff = hdr_end - mz.blocks[bi].first;
+    return KDF_OK;
+}
+
+}  // namespace
+
 int kdf_bam_open_range(const char *path, uint32_t flag_off, int collapse, int threads, int part, int parts, kdf_reader **out) {
     if (!path || !out) return rfail(nullptr, KDF_ERR_INVALID, "kdf_bam_open_range: NULL argument");
     if (parts < 1 || part < 0 || part >= parts) return rfail(nullptr, KDF_ERR_INVALID, "kdf_bam_open_range: part %d of %d", part, parts);
     *out = nullptr;
-    // the header (reference names, where the records begin) through a plain sequential reader
-    kdf_reader *hr = nullptr;
-    int rc = kdf_bam_open(path, flag_off, collapse, 1, &hr);
-    if (rc) return rc;
-    if (parts == 1) { kdf_reader_close(hr); return kdf_bam_open(path, flag_off, collapse, threads, out); }
-    // the first record's virtual offset: the header ended at inbuf[inpos]; the sequential reader appended whole blocks
-    uint64_t data_block = 0; size_t data_uoff = 0;
-    {
-        FILE *fp = fopen(path, "rb");
-        if (!fp) { kdf_reader_close(hr); return rfail(nullptr, KDF_ERR_IO, "cannot open %s", path); }
-        MiniBgzf mz(fp); std::string e;
-        const size_t hdr_end = hr->inpos;
-        while (mz.buf.size() <= hdr_end) if (!mz.more(e)) break;
-        fclose(fp);
-        if (!e.empty()) { kdf_reader_close(hr); return rfail(nullptr, KDF_ERR_IO, "%s: %s", path, e.c_str()); }
-        if (mz.buf.size() <= hdr_end) {                          // a BAM without records: part 0 reads it (nothing), the others are empty
-            kdf_reader_close(hr);
-            rc = kdf_bam_open(path, flag_off, collapse, 1, out);
-            if (rc == KDF_OK && part > 0) { (*out)->range_done = true; (*out)->eof = true; (*out)->inbuf.clear(); (*out)->inpos = 0; }
-            return rc;
-        }
-        size_t bi = mz.blocks.size() - 1;
-        while (mz.blocks[bi].first > hdr_end) --bi;
-        data_block = mz.blocks[bi].second; data_uoff = hdr_end - mz.blocks[bi].first;
+    if (parts == 1) {                                        // (the header is checked by the reader itself)
+        kdf_reader *hr = nullptr;
+        int rc1 = kdf_bam_open(path, flag_off, collapse, 1, &hr);
+        if (rc1) return rc1;
+        kdf_reader_close(hr);
+        return kdf_bam_open(path, flag_off, collapse, threads, out);
     }
-    const int32_t n_ref = (int32_t)hr->ref_names.size();
-    uint64_t file_size = 0;
-    { FILE *fp = fopen(path, "rb"); if (fp) { fseeko(fp, 0, SEEK_END); file_size = (uint64_t)ftello(fp); fclose(fp); } }
-    const uint64_t span = file_size > data_block ? file_size - data_block : 0;
-    auto cut = [&](int p) { return data_block + (uint64_t)((unsigned __int128)span * (unsigned)p / (unsigned)parts); };
+    BamLayout lay;
+    int rc = bam_layout(path, flag_off, collapse, lay);
+    if (rc) return rc;
+    kdf_reader *hr = lay.hr;
+    if (!lay.has_records) {                                  // a BAM without records: part 0 reads it (nothing), the others are empty
+        kdf_reader_close(hr);
+        rc = kdf_bam_open(path, flag_off, collapse, 1, out);
+        if (rc == KDF_OK && part > 0) { (*out)->range_done = true; (*out)->eof = true; (*out)->inbuf.clear(); (*out)->inpos = 0; }
+        return rc;
+    }
+    const uint64_t data_block = lay.data_block; const size_t data_uoff = lay.data_uoff;
+    const int32_t n_ref = lay.n_ref;
+    const uint64_t file_size = lay.file_size;
+    auto cut = [&](int p) { return lay.cut(p, parts); };
     uint64_t blk_off = data_block; size_t uoff = data_uoff; bool found = true;
     std::string e;
     if (part > 0) {
@@ -1095,6 +1125,171 @@ int kdf_bam_open_range(const char *path, uint32_t flag_off, int collapse, int th
     // (a start that already lies past this range's end -- a range smaller than a run -- is an empty range: the walk's
     // first record is in the end zone and opens a run)
     *out = r;
+    return KDF_OK;
+}
+
+// ---- the raw range planner (kdf.h "device BAM feeder") ---------------------------------------------------------------
+// Batches of COMPRESSED BGZF blocks with a block table and a sub-range table: the device inflates and walks them
+// (kdf_bamdev.h).  The host inflates nothing here but what locate_range_start inflates to find a sub-range's start.
+struct kdf_bamraw {
+    std::string path, err;
+    uint32_t flag_off = 0; bool collapse = false;
+    BamLayout lay;                                     // (its header reader is closed at open)
+    uint64_t lo = 0, hi = UINT64_MAX;                  // the part's file range; hi = UINT64_MAX: to the end of the file
+    uint64_t step = 1 << 20;
+    uint64_t n_sub = 0, cursor = 0;
+    struct Start { bool known = false, found = false; uint64_t blk_off = 0; size_t uoff = 0; };
+    std::vector<Start> starts;                         // located on first use, kept for a replay
+    FILE *fp = nullptr;
+    BgzfBlock blk;
+    uint64_t cut_of(uint64_t j) const { return j >= n_sub ? hi : lo + j * step; }   // sub-range j is [cut_of(j), cut_of(j + 1))
+};
+
+namespace {
+int bfail(kdf_bamraw *r, int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    if (r) r->err = buf; else g_host_err = buf;
+    return code;
+}
+}  // namespace
+
+const char *kdf_bamraw_error(const kdf_bamraw *r) { return r ? r->err.c_str() : g_host_err.c_str(); }
+
+int kdf_bamraw_open(const char *path, uint32_t flag_off, int collapse, int part, int parts, uint64_t subrange_bytes, kdf_bamraw **out) {
+    if (!path || !out) return bfail(nullptr, KDF_ERR_INVALID, "kdf_bamraw_open: NULL argument");
+    if (parts < 1 || part < 0 || part >= parts) return bfail(nullptr, KDF_ERR_INVALID, "kdf_bamraw_open: part %d of %d", part, parts);
+    *out = nullptr;
+    std::unique_ptr<kdf_bamraw> r(new kdf_bamraw());
+    r->path = path; r->flag_off = flag_off; r->collapse = collapse != 0;
+    if (subrange_bytes) r->step = subrange_bytes;
+    const int rc = bam_layout(path, flag_off, collapse, r->lay);          // (CRAM and bad magic are refused here, as by kdf_bam_open)
+    if (rc) return rc;
+    kdf_reader_close(r->lay.hr); r->lay.hr = nullptr;
+    if (r->lay.has_records) {
+        r->lo = r->lay.cut(part, parts);
+        r->hi = part + 1 < parts ? r->lay.cut(part + 1, parts) : UINT64_MAX;
+        const uint64_t end = part + 1 < parts ? r->hi : r->lay.file_size;
+        r->n_sub = end > r->lo ? (end - r->lo + r->step - 1) / r->step : 0;
+        if (r->n_sub == 0 && parts == 1) r->n_sub = 1;
+    } else if (part == 0) {
+        r->n_sub = 0;                                                     // a BAM without records
+    }
+    r->starts.resize(r->n_sub);
+    r->fp = fopen(path, "rb");
+    if (!r->fp) return bfail(nullptr, KDF_ERR_IO, "cannot open %s", path);
+    setvbuf(r->fp, nullptr, _IOFBF, 1 << 20);
+    *out = r.release();
+    return KDF_OK;
+}
+
+int kdf_bamraw_subranges(kdf_bamraw *r, uint64_t *n_subranges) {
+    if (!r || !n_subranges) return bfail(r, KDF_ERR_INVALID, "kdf_bamraw_subranges: NULL argument");
+    *n_subranges = r->n_sub;
+    return KDF_OK;
+}
+
+int kdf_bamraw_seek(kdf_bamraw *r, uint64_t sub) {
+    if (!r || sub > r->n_sub) return bfail(r, KDF_ERR_INVALID, "kdf_bamraw_seek: sub-range %llu of %llu", (unsigned long long)sub, (unsigned long long)(r ? r->n_sub : 0));
+    r->cursor = sub;
+    return KDF_OK;
+}
+
+void kdf_bamraw_close(kdf_bamraw *r) {
+    if (!r) return;
+    if (r->fp) fclose(r->fp);
+    delete r;
+}
+
+namespace {
+// S(cut_of(j)): where sub-range j's first record lies (kdf_bam_open_range's rule)
+int bamraw_start(kdf_bamraw *r, uint64_t j) {
+    kdf_bamraw::Start &s = r->starts[j];
+    if (s.known) return KDF_OK;
+    if (r->cut_of(j) <= r->lay.data_block) { s.found = true; s.blk_off = r->lay.data_block; s.uoff = r->lay.data_uoff; }
+    else {
+        std::string e;
+        const int rc = locate_range_start(r->path.c_str(), r->cut_of(j), r->lay.file_size, r->lay.n_ref, r->flag_off, r->collapse,
+                                          r->lay.data_block, r->lay.data_uoff, s.blk_off, s.uoff, s.found, e);
+        if (rc) return bfail(r, rc, "%s: %s", r->path.c_str(), e.c_str());
+    }
+    s.known = true;
+    return KDF_OK;
+}
+}  // namespace
+
+int kdf_bamraw_next(kdf_bamraw *r, void *comp_buf, uint64_t comp_cap, uint32_t tail_blocks, kdf_bgzf_block *blocks, uint64_t cap_blocks,
+                    kdf_bam_subrange *subs, uint64_t cap_subs, uint64_t *n_blocks, uint64_t *n_subs, uint64_t *first_sub,
+                    uint64_t *comp_bytes, uint64_t *inflated_bytes) {
+    if (!r || !comp_buf || !blocks || !subs || !n_blocks || !n_subs || !cap_subs)
+        return bfail(r, KDF_ERR_INVALID, "kdf_bamraw_next: bad argument");
+    if (!tail_blocks) tail_blocks = 2;
+    *n_blocks = *n_subs = 0;
+    if (first_sub) *first_sub = r->cursor;
+    if (comp_bytes) *comp_bytes = 0;
+    if (inflated_bytes) *inflated_bytes = 0;
+    const uint64_t j0 = r->cursor;
+    if (j0 >= r->n_sub) return KDF_OK;
+    int rc = bamraw_start(r, j0);
+    if (rc) return rc;
+    if (!r->starts[j0].found) {
+        // nothing starts at or after this cut: this sub-range and every later one of the part is empty
+        uint64_t n = std::min<uint64_t>(cap_subs, r->n_sub - j0);
+        for (uint64_t i = 0; i < n; ++i) subs[i] = kdf_bam_subrange{KDF_SUB_NONE, KDF_SUB_NONE, KDF_SUB_AT_EOF};
+        *n_subs = n; r->cursor = j0 + n;
+        return KDF_OK;
+    }
+    // read blocks from the first sub-range's start block until the buffers are full, the part (and its tail) is in, or the file ends
+    if (fseeko(r->fp, (off_t)r->starts[j0].blk_off, SEEK_SET) != 0) return bfail(r, KDF_ERR_IO, "%s: seek failed", r->path.c_str());
+    uint8_t *dst = (uint8_t *)comp_buf;
+    uint64_t nb = 0, used = 0, inflated = 0;
+    std::vector<uint64_t> stop_idx;                    // per sub-range j0 + i: the table index of its stop block
+    bool eof = false, full = false;
+    uint64_t j = j0;                                   // the sub-range whose stop block is looked for
+    const uint64_t j_max = std::min<uint64_t>(r->n_sub, j0 + cap_subs);
+    while (!eof && !full) {
+        if (j >= j_max && nb >= stop_idx.back() + tail_blocks) break;          // everything asked for, and the tail, is in
+        std::string e;
+        const int br = bgzf_read_raw(r->fp, r->blk, e);
+        if (br < 0) return bfail(r, KDF_ERR_IO, "%s: %s", r->path.c_str(), e.c_str());
+        if (br == 1) { eof = true; break; }
+        if (nb >= cap_blocks || used + (uint64_t)r->blk.cdata > comp_cap) { full = true; break; }
+        while (j < j_max && r->cut_of(j + 1) != UINT64_MAX && r->blk.file_off >= r->cut_of(j + 1)) { stop_idx.push_back(nb); ++j; }
+        blocks[nb] = kdf_bgzf_block{used, inflated, r->blk.file_off, (uint32_t)r->blk.cdata, r->blk.isize};
+        memcpy(dst + used, r->blk.comp.data(), (size_t)r->blk.cdata);
+        used += (uint64_t)r->blk.cdata; inflated += r->blk.isize; ++nb;
+    }
+    // sub-ranges that are whole in the batch: stop block and tail in, or the file ended
+    uint64_t ns = 0, keep = nb;
+    if (eof) ns = j_max - j0;
+    else {
+        while (ns < stop_idx.size() && stop_idx[ns] + tail_blocks <= nb) ++ns;
+        if (ns) keep = std::min<uint64_t>(nb, stop_idx[ns - 1] + tail_blocks);
+    }
+    if (ns == 0)
+        return bfail(r, KDF_ERR_INVALID, "kdf_bamraw_next: a sub-range of %llu file bytes with a tail of %u blocks does not fit %llu bytes / %llu blocks",
+                     (unsigned long long)r->step, tail_blocks, (unsigned long long)comp_cap, (unsigned long long)cap_blocks);
+    const bool at_eof = eof && keep == nb;
+    const uint64_t span = keep ? blocks[keep - 1].out_off + blocks[keep - 1].isize : 0;
+    for (uint64_t i = 0; i < ns; ++i) {
+        if ((rc = bamraw_start(r, j0 + i))) return rc;
+        const kdf_bamraw::Start &s = r->starts[j0 + i];
+        kdf_bam_subrange sr{KDF_SUB_NONE, KDF_SUB_NONE, at_eof ? KDF_SUB_AT_EOF : 0};
+        const bool has_stop = i < stop_idx.size() && stop_idx[i] < keep;
+        if (has_stop) sr.stop = blocks[stop_idx[i]].out_off;
+        else if (i < stop_idx.size() || r->cut_of(j0 + i + 1) != UINT64_MAX) sr.stop = span;   // (the next cut lies at or behind the file's last block)
+        if (s.found && keep && s.blk_off <= blocks[keep - 1].file_off) {
+            // the table entry of the start block (blocks are in file order)
+            uint64_t a = 0, b = keep;
+            while (a + 1 < b) { const uint64_t m = (a + b) / 2; if (blocks[m].file_off <= s.blk_off) a = m; else b = m; }
+            if (blocks[a].file_off == s.blk_off) sr.start = blocks[a].out_off + s.uoff;
+        }
+        if (sr.start != KDF_SUB_NONE && sr.stop != KDF_SUB_NONE && sr.start >= sr.stop) sr.start = KDF_SUB_NONE;   // a cut smaller than a run
+        subs[i] = sr;
+    }
+    *n_blocks = keep; *n_subs = ns; r->cursor = j0 + ns;
+    if (comp_bytes) *comp_bytes = keep ? blocks[keep - 1].comp_off + blocks[keep - 1].comp_len : 0;
+    if (inflated_bytes) *inflated_bytes = span;
     return KDF_OK;
 }
 

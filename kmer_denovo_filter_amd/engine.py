@@ -380,6 +380,30 @@ class KmerEngine:
         self._ck(self._lib.kdf_sketch_drop(self._h))
         return self
 
+    # -- device BAM feeder (kdf.h "device BAM feeder") ---------------------------
+    def bgzf_inflate_dev(self, d_comp: int, d_blocks: int, n_blocks: int, d_out: int, out_cap: int, d_status: Optional[int] = None):
+        """Inflate ``n_blocks`` BGZF blocks on the device (raw device pointers: payload bytes, the block table of
+        ``reads.BGZF_BLOCK_DTYPE``, the output of ``out_cap`` bytes, optionally uint32[n_blocks] for the decoder's
+        statuses).  Blocks the device decoder rejects are inflated by zlib and patched in (stat
+        ``bamdev_fallback_blocks``); one zlib rejects too raises KDF_ERR_IO.  Complete on return."""
+        self._ck(self._lib.kdf_bgzf_inflate_dev(self._h, c_void_p(d_comp) if d_comp else None, c_void_p(d_blocks) if d_blocks else None,
+                                                int(n_blocks), c_void_p(d_out) if d_out else None, int(out_cap),
+                                                c_void_p(d_status) if d_status else None))
+        return self
+
+    def bamdev_decode_dev(self, d_comp: int, d_blocks: int, n_blocks: int, d_subs: int, n_sub: int, flag_off: int, collapse: bool,
+                          d_packed: int, d_invalid: int, cap_bases: int, d_offsets: int, cap_reads: int):
+        """One planned batch (``reads.bam_raw_reader``) -> the packed stream in caller-owned HBM, in the layout of
+        the host readers.  -> (n_bases, n_reads, sub_status uint32[n_sub]); the stream holds the sub-ranges before the
+        first whose status is not 0.  Synchronises once; the stream itself is complete in the engine's stream order."""
+        nb, nr = c_uint64(0), c_uint64(0)
+        status = np.zeros(max(int(n_sub), 1), np.uint32)
+        self._ck(self._lib.kdf_bamdev_decode_dev(self._h, c_void_p(d_comp) if d_comp else None, c_void_p(d_blocks) if d_blocks else None,
+                                                 int(n_blocks), c_void_p(d_subs) if d_subs else None, int(n_sub), int(flag_off),
+                                                 1 if collapse else 0, c_void_p(d_packed), c_void_p(d_invalid), int(cap_bases),
+                                                 c_void_p(d_offsets), int(cap_reads), byref(nb), byref(nr), _vp(status)))
+        return nb.value, nr.value, status[:int(n_sub)]
+
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
         if self.long:

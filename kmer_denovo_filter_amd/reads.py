@@ -415,6 +415,355 @@ def bam_reader(path: str, flag_off: int = FLAG_OFF_SAMTOOLS_FASTA, collapse: boo
     return _Reader(h, max_bases, max_reads, want_meta, want_aux, is_bam=True)
 
 
+# ---- the device BAM feeder (kdf.h "device BAM feeder") ------------------------------------------------------------------
+# the two tables of a planned batch, as include/kdf.h lays them out
+BGZF_BLOCK_DTYPE = np.dtype([("comp_off", "<u8"), ("out_off", "<u8"), ("file_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4")])
+SUBRANGE_DTYPE = np.dtype([("start", "<u8"), ("stop", "<u8"), ("flags", "<u8")])
+SUB_NONE = 0xFFFFFFFFFFFFFFFF
+SUB_AT_EOF = 1
+SUB_DONE, SUB_UNFINISHED, SUB_CORRUPT = 0, 1, 2
+
+
+@dataclass
+class RawBatch:
+    """One planned batch of compressed BGZF blocks (``kdf_bamraw_next``)."""
+    comp: np.ndarray              # uint8: the blocks' DEFLATE payloads back to back (a view of the caller's buffer)
+    blocks: np.ndarray            # BGZF_BLOCK_DTYPE[n_blocks]
+    subs: np.ndarray              # SUBRANGE_DTYPE[n_subs]
+    first_sub: int                # index in the part of subs[0]
+    inflated_bytes: int           # the batch's inflated span
+
+
+class _RawReader:
+    """The raw range planner of one part of a BAM (host only: it reads compressed bytes and inflates nothing but what
+    locating a sub-range's start takes)."""
+
+    def __init__(self, handle, comp_cap: int, tail_blocks: int, args):
+        self._h = handle
+        self._lib = _native.load()
+        self.comp_cap = int(comp_cap)
+        self.tail_blocks = int(tail_blocks)
+        self.cap_blocks = self.comp_cap // 512 + 1024
+        self.args = args                                       # (path, flag_off, collapse, part, parts, subrange_bytes): a replay opens its own planner
+        n = c_uint64(0)
+        _native.check_bamraw(self._lib.kdf_bamraw_subranges(self._h, byref(n)), self._h)
+        self.n_subranges = n.value
+        self.cap_subs = max(1, min(self.n_subranges, 1 << 16))
+
+    def close(self):
+        if self._h:
+            self._lib.kdf_bamraw_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def seek(self, sub: int):
+        _native.check_bamraw(self._lib.kdf_bamraw_seek(self._h, int(sub)), self._h)
+
+    def next_into(self, comp_buf: np.ndarray, tail_blocks: Optional[int] = None, max_subs: Optional[int] = None):
+        """The next batch into ``comp_buf`` (uint8, e.g. a page-locked array) -> RawBatch, or None when the part is done."""
+        if not self._h:
+            return None
+        cap_subs = self.cap_subs if max_subs is None else max(1, min(int(max_subs), self.cap_subs))
+        blocks = np.zeros(self.cap_blocks, BGZF_BLOCK_DTYPE)
+        subs = np.zeros(cap_subs, SUBRANGE_DTYPE)
+        nb, ns, first, cb, ib = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0)
+        rc = self._lib.kdf_bamraw_next(self._h, _vp(comp_buf), min(len(comp_buf), self.comp_cap),
+                                       self.tail_blocks if tail_blocks is None else int(tail_blocks), _vp(blocks), len(blocks),
+                                       _vp(subs), len(subs), byref(nb), byref(ns), byref(first), byref(cb), byref(ib))
+        _native.check_bamraw(rc, self._h)
+        if ns.value == 0:
+            return None
+        return RawBatch(comp_buf[:cb.value], blocks[:nb.value], subs[:ns.value], first.value, ib.value)
+
+    def __iter__(self) -> Iterator[RawBatch]:
+        while True:
+            b = self.next_into(np.empty(self.comp_cap, np.uint8))
+            if b is None:
+                break
+            yield b
+
+
+def bam_raw_reader(path: str, flag_off: int = FLAG_OFF_SAMTOOLS_FASTA, collapse: bool = True, part: int = 0, parts: int = 1,
+                   subrange_bytes: int = 1 << 20, comp_cap: int = 1 << 26, tail_blocks: int = 0) -> _RawReader:
+    """The raw planner of part ``part`` of ``parts`` of a BAM (the cuts of ``bam_reader(part=, parts=)``), cut again
+    every ``subrange_bytes`` of file: batches of at most ``comp_cap`` compressed bytes with their block and sub-range
+    tables, for ``KmerEngine.bamdev_decode_dev``.  ``tail_blocks``: blocks kept behind a batch's last sub-range (0: 2)."""
+    h = c_void_p()
+    rc = _native.load().kdf_bamraw_open(path.encode(), flag_off, 1 if collapse else 0, int(part), int(parts), int(subrange_bytes), byref(h))
+    _native.check_bamraw(rc, None)
+    return _RawReader(h, comp_cap, tail_blocks, (path, flag_off, collapse, int(part), int(parts), int(subrange_bytes)))
+
+
+class PinnedBytes:
+    """A ring of page-locked byte buffers (the compressed batches of the device feeder)."""
+
+    def __init__(self, n: int, nbytes: int):
+        self._lib = _native.load()
+        self._ptrs, self.buffers = [], []
+        try:
+            for _ in range(n):
+                p = c_void_p()
+                _native.check(self._lib.kdf_host_alloc(nbytes, byref(p)), None)
+                self._ptrs.append(p)
+                self.buffers.append(np.ctypeslib.as_array(ctypes.cast(p, POINTER(ctypes.c_uint8)), (nbytes,)))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        self.buffers = []
+        for p in self._ptrs:
+            self._lib.kdf_host_free(p)
+        self._ptrs = []
+
+
+_pinned_bytes_cache = {}      # (ring, nbytes) -> PinnedBytes, kept for the life of the process (as _pinned_cache: page-locking costs more than a batch)
+
+
+def _pinned_bytes(ring: int, nbytes: int) -> PinnedBytes:
+    key = (ring, nbytes)
+    pb = _pinned_bytes_cache.get(key)
+    if pb is None or not pb.buffers:
+        for old in list(_pinned_bytes_cache.values()):
+            old.close()
+        _pinned_bytes_cache.clear()
+        pb = _pinned_bytes_cache[key] = PinnedBytes(ring, nbytes)
+    return pb
+
+
+def decode_capacity(inflated_bytes: int):
+    """(cap_bases, cap_reads) that hold whatever ``inflated_bytes`` of BAM records decode to: a record is >= 36 bytes and
+    carries (l_seq + 1) / 2 sequence bytes, so positions <= 2 x bytes + one separator per record."""
+    cap_reads = inflated_bytes // 36 + 1
+    return 2 * inflated_bytes + cap_reads + 64, cap_reads
+
+
+class _DeviceSlot:
+    """Device buffers of one batch in flight (grow-only torch tensors on the feeder's stream)."""
+
+    def __init__(self, torch, dev):
+        self.torch, self.dev = torch, dev
+        self.comp = self.blocks = self.subs = self.packed = self.invalid = self.offsets = None
+        self.copied = None
+        self.used = None                                       # recorded on the work stream behind the last kernels that read this slot
+        self.grew = False
+
+    def _room(self, name, n, dtype):
+        t = getattr(self, name)
+        if t is None or t.numel() < n:
+            t = self.torch.empty(int(n + n // 8 + 64), dtype=dtype, device=self.dev)
+            setattr(self, name, t)
+            self.grew = True
+        return t
+
+    def upload(self, batch: RawBatch, copy_stream):
+        torch = self.torch
+        cap_bases, cap_reads = decode_capacity(batch.inflated_bytes)
+        pw, mw = stream_words(cap_bases)
+        self._room("packed", pw, torch.int64); self._room("invalid", mw, torch.int64); self._room("offsets", cap_reads + 1, torch.int64)
+        views = (("comp", batch.comp, torch.uint8), ("blocks", batch.blocks.view(np.uint8), torch.uint8), ("subs", batch.subs.view(np.uint8), torch.uint8))
+        for name, arr, dt in views:
+            self._room(name, max(len(arr), 1), dt)
+        if self.grew:                                                  # (memory the allocator hands out again may still be in use on this stream)
+            torch.cuda.current_stream(self.dev).synchronize()
+            self.grew = False
+        with torch.cuda.stream(copy_stream):
+            # the decode of the batch this slot held returns with its write pass and its pack still queued on the work
+            # stream, and they read the slot's tables: the copies that overwrite them wait for those kernels
+            if self.used is not None:
+                copy_stream.wait_event(self.used)
+            for name, arr, dt in views:
+                if len(arr):
+                    getattr(self, name)[:len(arr)].copy_(torch.from_numpy(arr), non_blocking=True)
+            self.copied = torch.cuda.Event()
+            self.copied.record(copy_stream)
+        self.batch, self.cap_bases, self.cap_reads = batch, cap_bases, cap_reads
+
+
+LAST_FEEDER = None            # what the last stream_bam_device call did: {"path", "batches", "fallback_blocks", "replays", ...}
+
+
+def stream_bam_device(engine, path: str, parts_of_this_process, filtered: bool = False, tally: bool = False, sketch: bool = False,
+                      spool=None, flag_off: int = FLAG_OFF_SAMTOOLS_FASTA, collapse: bool = True, subrange_bytes: int = 1 << 20,
+                      comp_cap: int = 1 << 26, tail_blocks: int = 0, producers: int = 4) -> int:
+    """Count (``filtered``: count --if; ``tally``: prefilter pass 1; ``sketch``: sizing pass) a BAM through the DEVICE
+    feeder: producer threads plan batches of compressed BGZF blocks into page-locked buffers (``bam_raw_reader``), a copy
+    stream uploads batch i + 1 while the engine inflates, walks and packs batch i on the device (``bamdev_decode_dev``)
+    and takes the stream where it lies in HBM.  ``parts_of_this_process``: [(part, parts), ...] -- the shares of the file
+    this process reads (a rank's contiguous parts).  ``spool``: as in ``stream_batches_overlapped``; it is filled from the
+    device buffers (with the device read offsets when ``spool.keep_reads`` is set) before the batch is counted.  A
+    sub-range whose walk ran off the batch's bytes is replayed with a longer tail; nothing is lost or doubled.  For the
+    call's duration the engine runs on a stream of the feeder's; it is back on its own stream afterwards.  Returns the
+    number of reads; ``LAST_FEEDER`` records batches, fallback blocks, replays and the planner's time."""
+    global LAST_FEEDER
+    import queue
+    import threading
+    import time
+    import torch
+    dev = torch.device("cuda", engine.device)
+    readers = [bam_raw_reader(path, flag_off, collapse, p, n, subrange_bytes, comp_cap, tail_blocks) for p, n in parts_of_this_process]
+    ring = min(len(readers), max(1, int(producers))) + 2
+    pinned = _pinned_bytes(ring, comp_cap)
+    free, ready = queue.Queue(), queue.Queue()
+    for i in range(ring):
+        free.put(i)
+    todo = queue.Queue()
+    for rd in readers:
+        todo.put(rd)
+    stop = threading.Event()
+    plan_s = [0.0]
+    lock = threading.Lock()
+
+    def produce():
+        try:
+            while not stop.is_set():
+                try:
+                    rd = todo.get_nowait()
+                except queue.Empty:
+                    break
+                while not stop.is_set():
+                    i = free.get()
+                    if i is None:
+                        free.put(None)
+                        return
+                    t0 = time.perf_counter()
+                    b = rd.next_into(pinned.buffers[i])
+                    with lock:
+                        plan_s[0] += time.perf_counter() - t0
+                    if b is None:
+                        free.put(i)
+                        break
+                    ready.put((rd, i, b))
+            ready.put(None)
+        except BaseException as ex:  # noqa: BLE001 -- handed to the consumer
+            ready.put(ex)
+
+    n_threads = min(len(readers), max(1, int(producers)))
+    threads = [threading.Thread(target=produce, name="kdf-rawplan", daemon=True) for _ in range(n_threads)]
+    work, copy_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    engine.synchronize()
+    engine.set_stream(work.cuda_stream)
+    fallback0 = engine.get_stat("bamdev_fallback_blocks")
+    info = {"path": "device", "batches": 0, "replays": 0, "h2d_bytes": 0, "subranges": sum(r.n_subranges for r in readers)}
+    spooling = [spool]
+    keep_reads = bool(getattr(spool, "keep_reads", False))
+    n_reads = 0
+
+    def consume(slot):
+        """decode the slot's batch and hand the stream to the engine -> reads, index of the first sub-range not taken"""
+        b = slot.batch
+        nb, nr, status = engine.bamdev_decode_dev(slot.comp.data_ptr(), slot.blocks.data_ptr(), len(b.blocks), slot.subs.data_ptr(), len(b.subs),
+                                                  flag_off, collapse, slot.packed.data_ptr(), slot.invalid.data_ptr(), slot.cap_bases,
+                                                  slot.offsets.data_ptr(), slot.cap_reads)
+        bad = np.flatnonzero(status != SUB_DONE)
+        taken = int(bad[0]) if len(bad) else len(b.subs)
+        if nb:
+            dp, dm = slot.packed.data_ptr(), slot.invalid.data_ptr()
+            if spooling[0] is not None:
+                try:
+                    if keep_reads:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream, d_offsets=slot.offsets.data_ptr(), n_reads=nr)
+                    else:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream)
+                except _native.KdfError as ex:
+                    if ex.code != _native.KDF_ERR_NOMEM:
+                        raise
+                    spooling[0] = None                               # overflowed: the pass itself goes on
+            if sketch:
+                engine.sketch_add_dev(dp, dm, nb)
+            elif tally:
+                engine.prefilter_add_dev(dp, dm, nb)
+            elif filtered:
+                engine.count_filtered_dev(dp, dm, nb)
+            else:
+                engine.count_dev(dp, dm, nb)
+        slot.used = torch.cuda.Event()
+        slot.used.record(work)                                   # (behind the decode's last kernels and the consumer's)
+        info["batches"] += 1
+        return nr, taken
+
+    def replay(rd, first, last):
+        """sub-ranges [first, last) of rd's part, one at a time through a planner of their own, the tail doubled until the walk ends"""
+        got = 0
+        slot = _DeviceSlot(torch, dev)
+        with bam_raw_reader(*rd.args, comp_cap=comp_cap) as rp, torch.cuda.stream(work):
+            buf = np.empty(comp_cap, np.uint8)
+            for sub in range(first, last):
+                tail = max(rd.tail_blocks, 2) * 4
+                while True:
+                    rp.seek(sub)
+                    b = rp.next_into(buf, tail_blocks=tail, max_subs=1)
+                    slot.upload(b, copy_stream)
+                    slot.copied.synchronize()
+                    info["h2d_bytes"] += len(b.comp)
+                    nr, taken = consume(slot)
+                    engine.synchronize()                             # (the slot is reused at once)
+                    info["replays"] += 1
+                    if taken == 1:
+                        got += nr
+                        break
+                    tail *= 4
+        return got
+
+    slots = [_DeviceSlot(torch, dev), _DeviceSlot(torch, dev)]
+    try:
+        for th in threads:
+            th.start()
+        live, cur, pending = len(threads), 0, None                   # pending: (slot, reader, pinned index) uploaded, not yet decoded
+        with torch.cuda.stream(work):
+            def finish(p):
+                nonlocal n_reads
+                slot, rd, i = p
+                slot.copied.synchronize()
+                free.put(i)                                          # the copy is done: the pinned buffer goes back to the producers
+                nr, taken = consume(slot)
+                n_reads += nr
+                if taken < len(slot.batch.subs):
+                    n_reads += replay(rd, slot.batch.first_sub + taken, slot.batch.first_sub + len(slot.batch.subs))
+            while live:
+                item = ready.get()
+                if item is None:
+                    live -= 1
+                    continue
+                if isinstance(item, BaseException):
+                    raise item
+                rd, i, b = item
+                slots[cur].upload(b, copy_stream)                    # returns at once: the buffer is page-locked
+                info["h2d_bytes"] += len(b.comp) + b.blocks.nbytes + b.subs.nbytes
+                if pending is not None:
+                    finish(pending)
+                pending = (slots[cur], rd, i)
+                cur ^= 1
+            if pending is not None:
+                finish(pending)
+    finally:
+        stop.set()
+        free.put(None)
+        for th in threads:
+            if th.is_alive() or th.ident is not None:
+                th.join()
+        try:
+            engine.synchronize()
+        finally:
+            engine.set_stream(None)
+            copy_stream.synchronize()                                # no copy may still read a pinned buffer the next caller will fill
+            for rd in readers:
+                rd.close()
+    info["fallback_blocks"] = engine.get_stat("bamdev_fallback_blocks") - fallback0
+    info["plan_seconds"] = plan_s[0]
+    info["reads"] = n_reads
+    LAST_FEEDER = info
+    return n_reads
+
+
 def write_bam_subset(src_bam: str, dst_bam: str, ordinals, aux_fields=None, sort_and_index: bool = True,
                      threads: int = 1) -> int:
     """Copy the records ``ordinals`` (ReadStream.ordinals values) of ``src_bam`` into
