@@ -32,9 +32,9 @@
  *     work unchanged for every k.  A long engine counts through the direct
  *     kernels (no binned pipeline or fused dump: force_path 2 / 4 and
  *     fused_dump 1 are KDF_ERR_INVALID; count --if and the scan go through the
- *     membership sieve only under option "long_sieve") and is single-GPU only (kdf_export_parts*,
- *     kdf_add_pairs_multi_dev, kdf_set_counts_dev and hash_shift are
- *     KDF_ERR_INVALID).
+ *     membership sieve only under option "long_sieve").  Across ranks a long engine has its own owner
+ *     exchange (kdf_export_parts_w_packed_dev, kdf_set_counts_w_dev, "long keys" below); kdf_export_parts*,
+ *     kdf_add_pairs_multi_dev, kdf_set_counts_dev and hash_shift stay KDF_ERR_INVALID.
  *
  * Read streams
  *   Reads are handed over as ONE 2-bit-packed base stream plus a 1-bit
@@ -933,6 +933,34 @@ int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint3
                     uint64_t cap, uint64_t *n_out);
 int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, void *d_counts_out,
                         uint64_t cap, int sorted, uint64_t *n_out);
+
+/* Long keys across ranks: the owner exchange for W-word keys (csrc/kdf_long_merge.h; distributed.py carries it, and
+ * the mirrors use it only under KDF_LONG_RANKS=1).  The owner of a long key comes from bits 16..31 of its hash,
+ *     h     = kdf_mix64(w0 ^ fold(w1 .. w_{W-1}))        (the stored form; kdf_long.h `kdf_long_hash`)
+ *     owner = (((h >> 16) & 0xFFFF) * parts) >> 16,      parts = 1 .. 64
+ * not from the top 16 bits as for k <= 63: the home slot takes the top log2cap bits and the key_parts slice the low
+ * 16, so an owner's keys spread over the whole of an ordinary table -- an owner table needs no hash_shift (which long
+ * engines keep refusing) and the rule is independent of the active key slice.  With log2cap > 32, more than any long
+ * table fits in 288 GB, one or two owner bits would also be home bits; that costs probe locality, not correctness.
+ *
+ * kdf_export_parts_w_packed_dev dumps every entry with count >= min_count (0: every occupied slot, as
+ * kdf_export_ge_w_dev) into d_buf (device, cap_bytes bytes) grouped by owner: part p is one byte segment
+ *     [keys: n_p x W uint64, row-major | counts: n_p uint32]
+ * at d_buf + part_offsets[p]; segments lie back to back, every start rounded up to 8 bytes, part_offsets[parts] is
+ * the total; part_counts[parts] and part_offsets[parts + 1] are host arrays, *n_out the number of entries.  The
+ * order inside a part is unspecified.  Any capacity, insert and filter mode, with a key_parts slice active or a
+ * prefilter armed: it dumps what the table holds.  The sizes are known before anything is written: when cap_bytes is
+ * too small the call returns KDF_ERR_INVALID, the message names the bytes needed (the outputs hold them too), and
+ * d_buf is untouched.  KDF_ERR_INVALID on a k <= 63 engine and for parts outside 1..64.  Complete on return.
+ * The owner adds each received segment with one kdf_add_pairs_w_dev call.
+ *
+ * kdf_set_counts_w_dev is kdf_set_counts_dev for n x W rows: the count of every listed stored key becomes
+ * counts[i], in insert and in filter mode; a row that is not stored -- or whose top word has a bit at or above
+ * 2k - 64 (W - 1), which is no k-mer, as in kdf_query_w_dev -- is not inserted and makes the call return
+ * KDF_ERR_INVALID after the stored keys of the list were set. */
+int kdf_export_parts_w_packed_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void *d_buf, uint64_t cap_bytes,
+                                  uint64_t *n_out, uint64_t *part_counts, uint64_t *part_offsets);
+int kdf_set_counts_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts, uint64_t n);
 
 /* -------------------------------------------------------- read spool ---- */
 

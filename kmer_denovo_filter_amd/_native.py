@@ -115,6 +115,9 @@ SYMBOLS = [
     ("kdf_query_w_dev", c_int, [_P, _P, c_uint64, _P]),
     ("kdf_export_ge_w", c_int, [_P, c_uint32, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_export_ge_w_dev", c_int, [_P, c_uint32, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
+    # ... across ranks: the dump grouped by owner rank, set_counts
+    ("kdf_export_parts_w_packed_dev", c_int, [_P, c_uint32, c_uint32, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_set_counts_w_dev", c_int, [_P, _P, _P, c_uint64]),
     # two-pass counting: the counting sieve
     ("kdf_prefilter_begin", c_int, [_P, c_uint32, c_uint32]),
     ("kdf_prefilter_add_reads", c_int, [_P, _P, _P, c_uint64]),

@@ -23,7 +23,7 @@ _SOURCES = [
     ("kdf_host.cpp", ["-O2", "-x", "c++"]),          # host only: no device pass
 ]
 # every header any source includes: a header-only edit must trigger a rebuild
-_DEPS = ["kdf_device.h", "kdf_hostutil.h", "kdf_tilewalk.h", "kdf_long.h", "kdf_long_sieve.h", "kdf_binned.h", "kdf_binned_slabsort.inc", "kdf_merge.h", "kdf_histo.h", "kdf_prefilter.h", "kdf_sketch.h", "kdf_depth.h", "kdf_hits.h", "kdf_coverage.h", "kdf_variants.h", "kdf_spool.h", "kdf_bamdev.h", "kdf_inflate.h", os.path.join(_INC, "kdf.h")]
+_DEPS = ["kdf_device.h", "kdf_hostutil.h", "kdf_tilewalk.h", "kdf_long.h", "kdf_long_merge.h", "kdf_long_sieve.h", "kdf_binned.h", "kdf_binned_slabsort.inc", "kdf_merge.h", "kdf_histo.h", "kdf_prefilter.h", "kdf_sketch.h", "kdf_depth.h", "kdf_hits.h", "kdf_coverage.h", "kdf_variants.h", "kdf_spool.h", "kdf_bamdev.h", "kdf_inflate.h", os.path.join(_INC, "kdf.h")]
 
 
 def _newer(target: str, deps) -> bool:

@@ -225,12 +225,17 @@ def _merge_filter_counts(eng, lo, hi, dlo=None, dhi=None):
         if len(lo) == 0:
             return
         dlo, dhi = devkeys.from_host(lo, hi, eng.wide, eng.device)
-    if dlo.numel() == 0:
+    n = int(dlo.shape[0])                                    # (long keys: rows of W words)
+    if n == 0:
         return
     merged = ShardedFilterCount(EngineOps(eng, dev), stage_through_host=host).merged_counts(dlo, dhi)
     m32 = merged.to(torch.int32).contiguous()                # (values < 2^32: the bit pattern is the uint32 count)
     torch.cuda.current_stream(dev).synchronize()
-    eng.set_counts_dev(dlo.data_ptr(), dhi.data_ptr() if dhi is not None else None, m32.data_ptr(), int(dlo.numel()))
+    if getattr(eng, "long", False):                          # (KDF_LONG_RANKS=1: kdf_set_counts_w_dev)
+        dlo = dlo.contiguous()
+        eng.set_counts_w_dev(dlo.data_ptr(), m32.data_ptr(), n)
+    else:
+        eng.set_counts_dev(dlo.data_ptr(), dhi.data_ptr() if dhi is not None else None, m32.data_ptr(), n)
     eng.synchronize()
 
 

@@ -280,6 +280,8 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
 
 // long keys (odd k 65..201): table layout, claim protocol and kernels
 #include "kdf_long.h"
+// ... across ranks: the dump grouped by owner rank, set_counts
+#include "kdf_long_merge.h"
 // the counting sieve of the two-pass count: tally, gate and fill kernels
 #include "kdf_prefilter.h"
 #include "kdf_sketch.h"
@@ -3799,6 +3801,89 @@ int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint3
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL pointer");
     KDF_NEED_LONG(h, "kdf_export_ge_w");
     return export_host(h, min_count, keys_out, nullptr, counts_out, cap, n_out, "kdf_export_ge_w", KDF_ERR_INVALID);
+}
+
+// The sender's half of the owner exchange for long keys (kdf_long_merge.h): two passes over the table and one
+// synchronisation between them, where the segment offsets are made from the per-owner totals.
+int kdf_export_parts_w_packed_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void *d_buf, uint64_t cap_bytes,
+                                  uint64_t *n_out, uint64_t *part_counts, uint64_t *part_offsets) {
+    const char *who = "kdf_export_parts_w_packed_dev";
+    if (!h || !n_out || !part_counts || !part_offsets) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", who);
+    KDF_NEED_LONG(h, who);
+    if (parts < 1 || parts > KLM_MAX_PARTS) return fail(h, KDF_ERR_INVALID, "%s: parts must be 1..%d", who, KLM_MAX_PARTS);
+    HIPCHK(h, hipSetDevice(h->device));
+    { int rcf = pending_flush(h); if (rcf) return rcf; }
+    { int rc0 = materialize(h); if (rc0) return rc0; }
+    // scratch: part_cnt u64[64] | cursor u64[64] | part_base u64[64]
+    int rc = eng_reserve(h, *h->merge_buf, 3 * KLM_MAX_PARTS * 8, slack_exact);
+    if (rc) return rc;
+    unsigned long long *part_cnt = (unsigned long long *)h->merge_buf->p, *cursor = part_cnt + KLM_MAX_PARTS, *part_base = cursor + KLM_MAX_PARTS;
+    HIPCHK(h, hipMemsetAsync(part_cnt, 0, 2 * KLM_MAX_PARTS * 8, h->stream));        // part_cnt | cursor
+    const uint64_t waves = (h->cap + KDF_EXPORT_ROWS * 64 - 1) / (KDF_EXPORT_ROWS * 64);
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    const uint64_t *top = h->t.hi + ((uint64_t)(h->kw - 2) << h->t.log2cap);
+    hipLaunchKernelGGL(kdf_long_parts_count_kernel, dim3(blocks), dim3(256), 0, h->stream, h->t, top, min_count, parts, part_cnt);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long cnt[KLM_MAX_PARTS], base[KLM_MAX_PARTS];
+    HIPCHK(h, hipMemcpyAsync(cnt, part_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const uint64_t esz = 8ull * h->kw + 4;
+    uint64_t n = 0, off = 0;
+    for (uint32_t p = 0; p < KLM_MAX_PARTS; ++p) {
+        base[p] = off;
+        if (p >= parts) continue;
+        part_counts[p] = cnt[p];
+        part_offsets[p] = off;
+        n += cnt[p];
+        off += (cnt[p] * esz + 7) & ~7ull;                     // every segment starts on 8 bytes
+    }
+    part_offsets[parts] = off;
+    *n_out = n;
+    if (n == 0) return KDF_OK;
+    if (off > cap_bytes)                                        // (nothing was written: pass 2 has not run)
+        return fail(h, KDF_ERR_INVALID, "%s: %llu bytes needed, room for %llu", who, (unsigned long long)off, (unsigned long long)cap_bytes);
+    if (!d_buf) return fail(h, KDF_ERR_INVALID, "%s: NULL output", who);
+    HIPCHK(h, hipMemcpyAsync(part_base, base, sizeof(base), hipMemcpyHostToDevice, h->stream));
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W > 2)
+            hipLaunchKernelGGL(kdf_long_parts_write_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, h->t, min_count, parts,
+                               (const unsigned long long *)part_cnt, (const unsigned long long *)part_base, cursor, (unsigned char *)d_buf);
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (`base` is pageable; the dump is complete on return)
+    return KDF_OK;
+}
+
+int kdf_set_counts_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts, uint64_t n) {
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    KDF_NEED_LONG(h, "kdf_set_counts_w_dev");
+    if (n == 0) return KDF_OK;
+    if (!d_keys || !d_counts) return fail(h, KDF_ERR_INVALID, "kdf_set_counts_w_dev: NULL pointer");
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc;
+    if ((rc = pending_flush(h))) return rc;
+    if ((rc = materialize(h))) return rc;
+    h->zero_keys = true;
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W > 2)
+            for (uint64_t off = 0; off < n; off += 1ull << 30) {     // (a launch holds fewer than 2^32 threads)
+                const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+                hipLaunchKernelGGL(kdf_long_set_counts_kernel<W>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream,
+                                   (const uint64_t *)d_keys + off * W, (const uint32_t *)d_counts + off, m, h->t, h->ctl, long_top_bits(h));
+            }
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    bool bad = false;
+    if ((rc = ctl_sync(h, &bad))) return rc;
+    if (bad) {
+        HIPCHK(h, hipMemsetAsync(&h->ctl->error, 0, 4, h->stream));
+        return fail(h, KDF_ERR_INVALID, "kdf_set_counts_w_dev: a key is not stored in the table");
+    }
+    return KDF_OK;
 }
 
 int kdf_profile(kdf_engine *h, int enable) {

@@ -423,7 +423,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     if world > 1:                                                  # (rank order of the gathered sets is not key order)
         import torch
         order = keys.order(keys.from_pair(lo, hi, kmer_size))
-        lo, hi = lo[order], hi[order]
+        lo, hi = lo[order], (hi[order] if hi is not None else None)   # (long keys: rows, no hi)
         cand = devkeys.select([cand], torch.from_numpy(order).to(cand[0].device))
     n_candidates = len(lo)
     if rank == 0:

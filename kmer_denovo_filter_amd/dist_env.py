@@ -32,22 +32,23 @@ def barrier():
 
 
 def all_gather_keys(lo, hi):
-    """Every rank's (lo, hi) device key tensors, concatenated in rank order on every rank (ragged sizes)."""
+    """Every rank's (lo, hi) device key tensors, concatenated in rank order on every rank (ragged sizes).  Long keys:
+    ``lo`` holds (n, W) rows and ``hi`` is None; the rows are gathered whole."""
     w, _, host = world_rank()
     if w == 1:
         return lo, hi
     import torch
     import torch.distributed as dist
     dev = lo.device
-    n = torch.tensor([lo.numel()], dtype=torch.int64, device="cpu" if host else dev)
+    n = torch.tensor([lo.shape[0]], dtype=torch.int64, device="cpu" if host else dev)
     sizes = [torch.zeros_like(n) for _ in range(w)]
     dist.all_gather(sizes, n)
     sizes = [int(s.item()) for s in sizes]
     mx = max(sizes + [1])
 
     def gather(t):
-        pad = torch.zeros(mx, dtype=t.dtype, device="cpu" if host else dev)
-        pad[:t.numel()] = t.cpu() if host else t
+        pad = torch.zeros((mx,) + tuple(t.shape[1:]), dtype=t.dtype, device="cpu" if host else dev)
+        pad[:t.shape[0]] = t.cpu() if host else t
         outs = [torch.empty_like(pad) for _ in range(w)]
         dist.all_gather(outs, pad)
         return torch.cat([o[:s] for o, s in zip(outs, sizes)]).to(dev)

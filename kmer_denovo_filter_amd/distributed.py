@@ -27,6 +27,11 @@ SURVEY.md section 8e rather than a reference file:
   sieve of the WHOLE sample, and the local counts that follow store only the keys that sieve admits: smaller local
   tables and a smaller all-to-all, the same ``dump -L``.
 
+Long k-mers (odd k from 65 to 201, keys as (n, W) rows with ``hi`` None) go through both classes too: owners come
+from ``owner_of_w``, an entry on the wire is 8 W + 4 bytes, the engine dumps by owner at any table size
+(``kdf_export_parts_w_packed_dev``) and the owner adds each received segment with one ``kdf_add_pairs_w_dev``.  The
+mirrors take this only under ``KDF_LONG_RANKS=1``; it has run as several ranks on one GPU over gloo, never over RCCL.
+
 Both classes are written against a tiny adapter (``TableOps``) so that the
 sharding / exchange logic runs under gloo on CPU tensors in the tests, with the
 oracle standing in for the table; on a GPU the adapter is ``EngineOps`` (the HIP
@@ -62,10 +67,48 @@ def owner_of(lo: torch.Tensor, hi: Optional[torch.Tensor], world: int) -> torch.
     return (_lsr(h, 48) * world) >> 16
 
 
+_MIX_MUL = -0x604DE39AE16720DB                            # KDF_MIX_MUL = 0x9FB21C651E98DF25 as int64
+_FOLD_ADD = 0x632BE59BD9B4E019                            # kdf_long_fold_step's constant
+
+
+def _mix64(x: torch.Tensor) -> torch.Tensor:
+    """csrc/kdf_device.h ``kdf_mix64`` on int64 bit patterns (int64 arithmetic wraps like uint64)."""
+    return (x ^ _lsr(x, 32)) * _MIX_MUL
+
+
+def long_hash(keys: torch.Tensor) -> torch.Tensor:
+    """The stored form of long key rows, csrc/kdf_long.h ``kdf_long_hash``: ``keys`` is an (n, W) int64 tensor of key
+    words (bit patterns), word 0 the least significant, W = 3..7."""
+    f = torch.zeros(keys.shape[0], dtype=torch.int64, device=keys.device)
+    for j in range(keys.shape[1] - 1, 0, -1):             # the fold runs from the top word down
+        f = _mix64(f ^ keys[:, j]) + _FOLD_ADD
+    return _mix64(keys[:, 0] ^ f)
+
+
+def owner_of_w(keys: torch.Tensor, world: int) -> torch.Tensor:
+    """Owner rank of each long key row: ``(((h >> 16) & 0xFFFF) * world) >> 16`` with h = ``long_hash(keys)``, world
+    1..64 -- bits 16..31 of the table's hash, where ``owner_of`` takes the top 16.  The home slot is the TOP log2cap
+    bits of h and the ``key_parts`` slice its LOW 16, so an owner's keys spread over the whole of an ordinary long table
+    (no ``hash_shift``), whatever key slice is active; the engine groups its dump by this rule key by key
+    (``kdf_export_parts_w_packed_dev``)."""
+    if not 1 <= int(world) <= 64:
+        raise ValueError(f"owner_of_w: world={world} outside 1..64")
+    if keys.dim() != 2 or not 3 <= keys.shape[1] <= 7:
+        raise ValueError(f"owner_of_w: keys must be (n, 3..7) rows of key words, got shape {tuple(keys.shape)}")
+    return ((_lsr(long_hash(keys), 16) & 0xFFFF) * int(world)) >> 16
+
+
+def _entry_bytes(wide: bool, key_words: int = 0) -> int:
+    """Bytes of one (key, count) entry on the wire: 12 / 20 for (lo) / (lo, hi) keys, 8 W + 4 for rows of W words."""
+    return 8 * key_words + 4 if key_words > 2 else (20 if wide else 12)
+
+
 class TableOps:
-    """What the distributed logic needs from a table (see EngineOps)."""
+    """What the distributed logic needs from a table (see EngineOps).  A table of long keys (``key_words`` = W >= 3)
+    takes and returns its keys as (n, W) rows in the ``lo`` position with ``hi`` None."""
     wide: bool
     device: torch.device
+    key_words: int = 0                                    # 3..7: long keys; anything else: (lo, hi)
 
     def clear(self): raise NotImplementedError
     def count_stream(self, packed: torch.Tensor, invalid: torch.Tensor, n_bases: int): raise NotImplementedError
@@ -113,6 +156,8 @@ class EngineOps(TableOps):
     def __init__(self, engine, device: torch.device):
         self.e = engine
         self.wide = engine.wide
+        self.long = bool(getattr(engine, "long", False))
+        self.key_words = int(engine.key_words) if self.long else 0
         self.device = device
 
     def clear(self):
@@ -131,8 +176,8 @@ class EngineOps(TableOps):
 
     def export_pairs(self, min_count):
         n = self.e.count_ge(min_count)
-        lo = torch.empty(n, dtype=torch.int64, device=self.device)
-        hi = torch.empty(n, dtype=torch.int64, device=self.device) if self.wide else None
+        lo = torch.empty((n, self.key_words) if self.long else n, dtype=torch.int64, device=self.device)
+        hi = torch.empty(n, dtype=torch.int64, device=self.device) if self.wide and not self.long else None
         cnt = torch.empty(n, dtype=torch.int32, device=self.device)
         self._sync()
         if n:
@@ -143,8 +188,8 @@ class EngineOps(TableOps):
 
     def export_pairs_by_owner(self, world: int):
         """(lo, hi, cnt, per-owner counts) already grouped by owner rank, or None when
-        the table is too small for the engine's owner-ordered dump."""
-        if self.e.get_stat("log2cap") < 28 or world > 64 or self.e.get_stat("hash_shift"):
+        the table is too small for the engine's owner-ordered dump (and for long keys: they travel packed)."""
+        if self.long or self.e.get_stat("log2cap") < 28 or world > 64 or self.e.get_stat("hash_shift"):
             return None
         _, distinct, _ = self.e.stats()
         lo = torch.empty(distinct, dtype=torch.int64, device=self.device)
@@ -159,7 +204,17 @@ class EngineOps(TableOps):
     def export_packed_by_owner(self, world: int):
         """(send buffer uint8, per-owner pair counts, per-owner byte offsets [world + 1]): the owner-ordered dump written
         by the engine straight into the layout `OwnerPartitionedCount.exchange` sends -- no (lo, hi, cnt) temporaries, no
-        packing copies.  None when the table cannot be dumped by owner (see export_pairs_by_owner)."""
+        packing copies.  None when the table cannot be dumped by owner (see export_pairs_by_owner).  A long engine groups
+        its dump by `owner_of_w` key by key (``kdf_export_parts_w_packed_dev``), at any table size: never None."""
+        if self.long:
+            if not 1 <= world <= 64:
+                raise ValueError(f"long keys: the owner exchange takes 1..64 ranks, not {world}")
+            _, distinct, _ = self.e.stats()
+            cap = distinct * _entry_bytes(False, self.key_words) + 8 * world + 8
+            buf = torch.empty(cap, dtype=torch.uint8, device=self.device)
+            self._sync()
+            n, counts, offs = self.e.export_parts_w_packed_dev(0, world, buf.data_ptr(), cap)   # complete on return
+            return buf[:offs[world]], counts, offs
         if self.e.get_stat("log2cap") < 28 or world > 64 or self.e.get_stat("hash_shift"):
             return None
         _, distinct, _ = self.e.stats()
@@ -171,17 +226,22 @@ class EngineOps(TableOps):
         return buf[:offs[world]], counts, offs
 
     def add_pairs(self, lo, hi, cnt):
-        if lo.numel() == 0:
+        if lo.shape[0] == 0:
             return
         lo, cnt = lo.contiguous(), cnt.contiguous()
         hi = hi.contiguous() if hi is not None else None
         self._sync()
-        self.e.add_pairs_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, cnt.data_ptr(), lo.numel())
+        self.e.add_pairs_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, cnt.data_ptr(), lo.shape[0])
         self.e.synchronize()
 
     def add_pairs_segments(self, segments):
         """All source ranks' segments in ONE engine call: when they arrive in hash order (the engine's
-        owner-ordered dump) every table bucket is merged in LDS and written once (csrc/kdf_merge.h)."""
+        owner-ordered dump) every table bucket is merged in LDS and written once (csrc/kdf_merge.h).  Long keys: one
+        ``kdf_add_pairs_w_dev`` call per segment."""
+        if self.long:
+            for lo, hi, cnt in segments:
+                self.add_pairs(lo, hi, cnt)
+            return
         segs = [(lo.contiguous(), hi.contiguous() if hi is not None else None, cnt.contiguous())
                 for lo, hi, cnt in segments if lo.numel()]
         if not segs:
@@ -195,7 +255,10 @@ class EngineOps(TableOps):
         """An owner only ever sees keys whose top hash bits name it: its table drops floor(log2(world)) of them
         from the home slot (engine option ``hash_shift``), so the whole table is used and the senders' hash
         order is the table's bucket order.  (world not a power of two: the owner's keys cover
-        2^floor(log2 world) / world of the table; ask for that much more capacity.)"""
+        2^floor(log2 world) / world of the table; ask for that much more capacity.)  Long keys: nothing to do -- their
+        owner bits (`owner_of_w`) are not home-slot bits."""
+        if self.long:
+            return
         self.e.set_option("hash_shift", max(0, int(world).bit_length() - 1))
 
     def prefilter_begin(self, min_count, log2_cells):
@@ -253,12 +316,13 @@ class EngineOps(TableOps):
         self.e.sketch_drop()
 
     def query(self, lo, hi):
-        out = torch.zeros(lo.numel(), dtype=torch.int32, device=self.device)
-        if lo.numel():
+        n = lo.shape[0]                                              # (long keys: rows)
+        out = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if n:
             lo = lo.contiguous()
             hi = hi.contiguous() if hi is not None else None
             self._sync()
-            self.e.query_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, lo.numel(), out.data_ptr())
+            self.e.query_dev(lo.data_ptr(), hi.data_ptr() if hi is not None else None, n, out.data_ptr())
             self.e.synchronize()
         return out
 
@@ -296,7 +360,8 @@ class ShardedFilterCount:
 
     def merged_counts(self, keys_lo: torch.Tensor, keys_hi: Optional[torch.Tensor]) -> torch.Tensor:
         """Global count of every filter key (same key order on every rank), saturating at
-        2^32-1, as int64 values.  Call after each rank counted its own shard.
+        2^32-1, as int64 values.  Call after each rank counted its own shard.  Long keys: ``keys_lo`` holds the
+        (n, W) rows and ``keys_hi`` is None.
 
         The counts travel as ONE all-reduce(sum) of 4-byte words (the `ncclUint32` reduce of
         SURVEY.md section 8e): a scalar all-reduce(max) of the largest local count first
@@ -387,12 +452,15 @@ class OwnerPartitionedCount:
 
     def exchange(self):
         """Move every locally counted (key, count) pair to its owner rank: one count exchange and ONE
-        packed all-to-all (per destination a byte segment [lo words | hi words | counts], starts aligned to 8)."""
+        packed all-to-all (per destination a byte segment [lo words | hi words | counts], starts aligned to 8; long
+        keys, rows of W words: [keys: n x W words, row-major | counts], 8 W + 4 bytes per entry, owners by `owner_of_w`)."""
         if self.world == 1:
             return
         packed = self.local.export_packed_by_owner(self.world) if hasattr(self.local, "export_packed_by_owner") else None
         wide = bool(getattr(self.local, "wide", False))
-        esz = 20 if wide else 12
+        kw = int(getattr(self.local, "key_words", 0) or 0)
+        kw = kw if kw > 2 else 0
+        esz = _entry_bytes(wide, kw)
         cdev = torch.device("cpu") if self.host else self.device
         if packed is not None:                       # the engine wrote the send buffer itself, owner by owner, in hash order
             send, s_list, offs = packed
@@ -405,21 +473,22 @@ class OwnerPartitionedCount:
                 send_counts = torch.tensor(counts, dtype=torch.int64)
             else:
                 lo, hi, cnt = self.local.export_pairs(0)
-                own = owner_of(lo, hi, self.world)
+                own = owner_of_w(lo, self.world) if kw else owner_of(lo, hi, self.world)
                 order = torch.argsort(own, stable=True)
                 lo, cnt = lo[order], cnt[order]
                 hi = hi[order] if hi is not None else None
                 send_counts = torch.bincount(own, minlength=self.world).to(torch.int64).cpu()
             wide = hi is not None
-            esz = 20 if wide else 12
+            esz = _entry_bytes(wide, kw)
+            kwords = kw or 1                         # words of the first key block of a segment
             s_list = send_counts.tolist()
             s_bytes = [_round8(n * esz) for n in s_list]
             send = torch.empty(sum(s_bytes), dtype=torch.uint8, device=lo.device)
             off = a = 0
             for n, nb in zip(s_list, s_bytes):       # 2-3 contiguous device copies per destination
                 if n:
-                    send[off:off + 8 * n].view(torch.int64).copy_(lo[a:a + n])
-                    o2 = off + 8 * n
+                    send[off:off + 8 * kwords * n].view(torch.int64).copy_(lo[a:a + n].reshape(-1))
+                    o2 = off + 8 * kwords * n
                     if hi is not None:
                         send[o2:o2 + 8 * n].view(torch.int64).copy_(hi[a:a + n])
                         o2 += 8 * n
@@ -441,10 +510,13 @@ class OwnerPartitionedCount:
         segments = []
         for n, nb in zip(r_list, r_bytes):           # the owner sums straight from the received segments, all sources at once
             if n:
-                rlo = recv[off:off + 8 * n].view(torch.int64)
-                o2 = off + 8 * n
+                kwords = kw or 1
+                rlo = recv[off:off + 8 * kwords * n].view(torch.int64)
+                if kw:
+                    rlo = rlo.view(n, kw)
+                o2 = off + 8 * kwords * n
                 rhi = None
-                if wide:
+                if wide and not kw:
                     rhi = recv[o2:o2 + 8 * n].view(torch.int64)
                     o2 += 8 * n
                 segments.append((rlo, rhi, recv[o2:o2 + 4 * n].view(torch.int32)))

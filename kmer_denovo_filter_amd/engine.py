@@ -20,8 +20,12 @@ Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
 keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
 significant, passed and returned in the ``lo`` position with ``hi=None`` (so
 ``export_ge`` returns ``(keys, None, counts)``).  The read-stream methods are the
-same for every k.  Long engines are single-GPU only (no owner-ordered dump,
-multi-segment merge or set_counts).
+same for every k.  Across ranks a long engine has its own owner exchange:
+``export_parts_w_packed_dev`` (the dump grouped by ``distributed.owner_of_w``),
+``add_pairs_dev`` per received segment and ``set_counts_w_dev``; the (lo, hi)
+owner-ordered dump, the multi-segment merge, ``set_counts_dev`` and ``hash_shift``
+stay refused.  The mirrors take that path only under ``KDF_LONG_RANKS=1``; it has
+run as several ranks on one GPU over gloo, never over RCCL.
 
 No CPU fallback: constructing an engine without libkdf.so or without a GPU
 raises.
@@ -199,6 +203,13 @@ class KmerEngine:
     def set_counts_dev(self, d_lo: int, d_hi: Optional[int], d_counts: int, n: int):
         """The count of every listed (stored) key becomes d_counts[i] (``kdf_set_counts_dev``)."""
         self._ck(self._lib.kdf_set_counts_dev(self._h, c_void_p(d_lo), c_void_p(d_hi) if d_hi else None, c_void_p(d_counts), int(n)))
+        return self
+
+    def set_counts_w_dev(self, d_keys: int, d_counts: int, n: int):
+        """Long engines: the count of every listed (stored) key row becomes d_counts[i] (``kdf_set_counts_w_dev``;
+        ``d_keys``: n x key_words row-major words).  A row that is not stored raises, after the stored ones were set."""
+        self._ck(self._lib.kdf_set_counts_w_dev(self._h, c_void_p(d_keys) if d_keys else None,
+                                                c_void_p(d_counts) if d_counts else None, int(n)))
         return self
 
     def add_pairs_multi_dev(self, segments):
@@ -513,6 +524,18 @@ class KmerEngine:
         self._ck(self._lib.kdf_export_parts_packed_dev(self._h, int(min_count), int(parts), c_void_p(d_buf), int(cap_bytes),
                                                        counts, offs, byref(n)))
         return n.value, [int(x) for x in counts], [int(x) for x in offs]
+
+    def export_parts_w_packed_dev(self, min_count: int, parts: int, d_buf: Optional[int], cap_bytes: int):
+        """Long engines: the dump grouped by owner rank (``distributed.owner_of_w``) in the packed all-to-all layout --
+        per owner one byte segment ``[keys: n_p x key_words uint64 row-major | counts: n_p uint32]``, starts aligned
+        to 8; returns (entries, per-owner counts, segment byte offsets [parts + 1]).  Any table size, insert or filter
+        mode.  Too few ``cap_bytes`` raise (the message names the bytes needed) and nothing is written."""
+        n = c_uint64(0)
+        counts = (c_uint64 * max(int(parts), 1))()
+        offs = (c_uint64 * (max(int(parts), 1) + 1))()
+        self._ck(self._lib.kdf_export_parts_w_packed_dev(self._h, int(min_count), int(parts), c_void_p(d_buf) if d_buf else None,
+                                                         int(cap_bytes), byref(n), counts, offs))
+        return n.value, [int(x) for x in counts[:int(parts)]], [int(x) for x in offs[:int(parts) + 1]]
 
     # -- Module-3 scan -----------------------------------------------------
     def scan(self, stream: ReadStream, want_distinct: bool = True):
@@ -866,13 +889,16 @@ def estimate_from_registers(regs) -> float:
 
 def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:
     """The engine the reference-interface mirrors (discovery chain, Module 3, the Jellyfish wrappers) count with.
-    Long k-mers (odd 65..201) run in one process; under a process group of several ranks the mirrors shard through the
-    multi-GPU exchange (owner-ordered dump, set_counts, merges), which takes k <= 63 only -- refused here, before any
-    device call."""
+    Long k-mers (odd 65..201) run in one process by default: under a process group of several ranks the mirrors shard
+    through the multi-GPU exchange, and the (lo, hi) exchange takes k <= 63 only -- refused here, before any device
+    call.  ``KDF_LONG_RANKS=1`` opts in to the owner exchange for W-word keys (distributed.owner_of_w,
+    kdf_export_parts_w_packed_dev, kdf_set_counts_w_dev): the mirrors then shard long k as they shard k <= 63.  That
+    path has run as several ranks on one GPU over gloo only; RCCL and real scaling are unmeasured."""
     if int(k) > KmerEngine.MAX_K:
+        import os
         from . import dist_env
         world = dist_env.world_rank()[0]
-        if world > 1:
+        if world > 1 and os.environ.get("KDF_LONG_RANKS") != "1":
             raise ValueError(f"k={k}: long k-mers (odd {KmerEngine.LONG_MIN_K}..{KmerEngine.LONG_MAX_K}) run in one "
                              f"process; the multi-GPU mirrors ({world} ranks) take k <= {KmerEngine.MAX_K}")
     return KmerEngine(k, *args, **kwargs)
