@@ -117,19 +117,7 @@ struct __attribute__((aligned(16))) KbEnt2 { uint64_t lo, hi; };
                                          // one slab per thread, capped the groups of tables with 1024 coarse bins at 84 % full pieces)
 #endif
 
-struct KbPlan {
-    uint32_t c1;            // coarse bits
-    uint32_t c2;            // fine bits (<= KB_F_BITS_MAX)
-    uint32_t sub_bits;      // table buckets per partition bucket = 2^sub_bits (a table that grew since the partition: more)
-    uint32_t log2cap, bucket_bits;
-    uint32_t off_stride;    // words per row of chunk_off = 2^KB_F_BITS_MAX + 1 (fixed: the rows of passes of any geometry share the array)
-    uint32_t key_parts, key_part;   // KdfTable::key_parts: windows of other key-space slices are dropped in A
-    uint32_t dbg;           // experiments only
-    uint32_t n_pass;        // pending passes kernel C applies (1 .. KB_MAX_PASS)
-    uint32_t group;         // G: slabs per group
-    uint32_t n_groups, n_slabs;
-    uint32_t dump_min;      // the DUMP instantiations of kernel C (insert mode) also dump every slot with count >= dump_min >= 1 while they hold the bucket (KbScratch::dump_*)
-};
+// (struct KbPlan, the partition geometry: kdf_device.h, beside the other state that kernels take by value)
 
 // One partitioned pass in the ring (device resident, written by kb_binfirst_kernel).  Pieces are numbered BIN-MAJOR: the
 // pieces of bin c are rows row_base + binrow_first[c] .. binrow_first[c + 1]) and lie one after the other in the ring.

@@ -27,7 +27,7 @@
 #include "kdf_long.h"
 
 #define KD_WAVE_TILES 64                  // tiles per wave: 4096 stream positions
-#define KD_ROW_WORDS  6                   // windows, present, low, min, max, sum
+// (KD_ROW_WORDS = 6 -- windows, present, low, min, max, sum -- is in kdf_device.h: a spool's replay strides by it)
 
 template <int W> struct KdCfg { static constexpr int NB = W <= 3 ? 8 : 4; };      // tiles resolved together (long keys: registers)
 

@@ -14,6 +14,12 @@
 #define KDF_PENDING 0x8000000000000000ull   // wide keys: hi word claimed, lo not yet published
 #define KDF_TILE    64                      // window starts per thread = one mask word
 #define KDF_SHARDS  64                      // sharded statistics counters
+#define KDF_EXPORT_ROWS 32                  // dump -L: a wave owns KDF_EXPORT_ROWS x 64 consecutive slots (kdf_export_kernel, kdf_long_export_kernel)
+
+// modes of the stream kernels (kdf_stream_kernel in kdf_engine.hip, kdf_long_stream_kernel in kdf_long.h)
+enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2, MODE_GATED = 3 };
+// MODE_GATED: an insert-mode count behind an armed prefilter (kdf_prefilter.h).  `hit_bits` then is an INPUT: word
+// [tile] holds the tile's admitted windows, written by the gate kernel, and is ANDed into the validity bitmap.
 
 // Geometry of a read stream of n_bases positions (include/kdf.h, "Read streams"): T tiles, and the buffer sizes
 // kdf_stream_words reports -- a tile reads packed words [2t, 2t + 3] and mask words [t, t + 1].
@@ -117,6 +123,57 @@ struct KdfCtl {            // device-resident control block (one per engine)
     unsigned int error;                            // != 0: a bucket overflowed
     unsigned int pad;
 };
+
+// ---- engine state that kernels take by value: here, so that the host-only kdf_engine_priv.h needs no kernel header ----
+
+// the partition geometry of the binned path (kdf_binned.h)
+struct KbPlan {
+    uint32_t c1;            // coarse bits
+    uint32_t c2;            // fine bits (<= KB_F_BITS_MAX)
+    uint32_t sub_bits;      // table buckets per partition bucket = 2^sub_bits (a table that grew since the partition: more)
+    uint32_t log2cap, bucket_bits;
+    uint32_t off_stride;    // words per row of chunk_off = 2^KB_F_BITS_MAX + 1 (fixed: the rows of passes of any geometry share the array)
+    uint32_t key_parts, key_part;   // KdfTable::key_parts: windows of other key-space slices are dropped in A
+    uint32_t dbg;           // experiments only
+    uint32_t n_pass;        // pending passes kernel C applies (1 .. KB_MAX_PASS)
+    uint32_t group;         // G: slabs per group
+    uint32_t n_groups, n_slabs;
+    uint32_t dump_min;      // the DUMP instantiations of kernel C (insert mode) also dump every slot with count >= dump_min >= 1 while they hold the bucket (KbScratch::dump_*)
+};
+
+// the counting sieve of the two-pass count (kdf_prefilter.h)
+struct KdfPrefilter {
+    unsigned long long *words;   // 2^(log2_cells - 4) words
+    uint32_t log2_cells;
+    uint32_t min_count;          // 2 or 3: the gate admits cells that read >= min_count
+};
+
+// the distinct k-mer sketch (kdf_sketch.h)
+struct KdfSketch {
+    uint32_t *cells;       // 2^p cells, cell j = register j (0 .. 65 - p)
+    uint32_t p;
+};
+
+// words per row of the per-read results: what their kernels write and what a spool's replay strides by
+#define KD_ROW_WORDS  6                   // kdf_depth.h (uint64): windows, present, low, min, max, sum
+#define KH_ROW_WORDS   2                  // kdf_hits.h (uint32): hits, distinct
+
+// exclusive prefix of v over the 256 threads of the workgroup and their total; ws: 4 words of LDS
+// (the block scan of the kh_* kernels of kdf_hits.h and the ks_select_* kernels of kdf_spool.h)
+__device__ __forceinline__ uint32_t kh_block_excl(uint32_t v, uint32_t *ws, uint32_t &total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    uint32_t pre = 0;
+    total = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const uint32_t s = ws[j]; pre += j < wv ? s : 0; total += s; }
+    __syncthreads();                                                  // (ws is written again by the caller's next scan)
+    return pre + inc - v;
+}
 
 __device__ __forceinline__ uint64_t kdf_home(const KdfTable &t, uint64_t h) {
     return (h << t.hshift) >> (64 - t.log2cap);

@@ -1,7 +1,9 @@
-// kdf_engine.hip -- libkdf.so: HIP kernels (gfx950) + engine + the C ABI of
-// include/kdf.h.  See DESIGN.md for the data layout and the roofline of each
-// kernel.  No CPU fallback exists in this library: every entry point either
-// runs on the GPU or returns an error.
+// kdf_engine.hip -- libkdf.so, the core unit: the table, the direct kernels, the sieve, the host side of the binned
+// pipeline and the merge, the long-key paths, the counting sieve, the sketch, the device BAM feeder, and the engine's C
+// ABI of include/kdf.h (create and destroy, count, count --if, query, export, profile, options and stats).  The
+// per-read consumers live in kdf_engine_reads.hip, the read spool in kdf_spool.hip; kdf_engine_priv.h is what they
+// share.  See DESIGN.md for the data layout and the roofline of each kernel.  No CPU fallback exists in this library:
+// every entry point either runs on the GPU or returns an error.
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 #include <algorithm>
@@ -12,13 +14,19 @@
 #include <string>
 #include <vector>
 
-#include "kdf.h"
-#include "kdf_device.h"
+#include "kdf_engine_priv.h"
 #include "kdf_tilewalk.h"
-#include "kdf_hostutil.h"
 #include "kdf_binned.h"
 #include "kdf_merge.h"
 #include "kdf_histo.h"
+// long keys (odd k 65..201): table layout, claim protocol and kernels
+#include "kdf_long.h"
+// ... across ranks: the dump grouped by owner rank, set_counts
+#include "kdf_long_merge.h"
+// the counting sieve of the two-pass count: tally, gate and fill kernels
+#include "kdf_prefilter.h"
+#include "kdf_sketch.h"
+#include "kdf_bamdev.h"
 
 // sorted export lives in kdf_sort.hip (rocPRIM radix sort)
 int kdf_sort_pairs_device(uint64_t *d_lo, uint64_t *d_hi, uint32_t *d_cnt, uint64_t n,
@@ -28,10 +36,6 @@ int kdf_sort_rows_device(uint64_t *d_keys, int words, uint32_t *d_cnt, uint64_t 
 // ===========================================================================
 // kernels
 // ===========================================================================
-
-enum { MODE_INSERT = 0, MODE_FILTERED = 1, MODE_SCAN = 2, MODE_GATED = 3 };
-// MODE_GATED: an insert-mode count behind an armed prefilter (kdf_prefilter.h).  `hit_bits` then is an INPUT: word
-// [tile] holds the tile's admitted windows, written by the gate kernel, and is ANDed into the validity bitmap.
 
 // One thread = one tile of 64 window starts (kdf_walk_tile, kdf_tilewalk.h).  Windows are processed in batches
 // of 8: the 8 home-slot key loads are issued back to back before any of them is
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256) void kdf_set_counts_kernel(
 // chunk of EXPORT_ROWS x 64 consecutive slots: it counts its matches, reserves
 // its output range with ONE atomic, then re-reads the (cache-resident) chunk and
 // writes.  One same-address atomic per 2048 slots instead of one per 64.
-#define KDF_EXPORT_ROWS 32
+// (KDF_EXPORT_ROWS = 32: kdf_device.h, the dumps of long keys use it too)
 template <int KW, bool WRITE>
 __global__ __launch_bounds__(256) void kdf_export_kernel(
     KdfTable t, uint32_t min_count, KdfCtl *ctl, uint64_t *__restrict__ olo,
@@ -278,21 +282,6 @@ __global__ __launch_bounds__(KDF_EXPORT1_THREADS) void kdf_export1_kernel(KdfTab
     }
 }
 
-// long keys (odd k 65..201): table layout, claim protocol and kernels
-#include "kdf_long.h"
-// ... across ranks: the dump grouped by owner rank, set_counts
-#include "kdf_long_merge.h"
-// the counting sieve of the two-pass count: tally, gate and fill kernels
-#include "kdf_prefilter.h"
-#include "kdf_sketch.h"
-// per-window counts and per-read depth rows of a read stream
-#include "kdf_depth.h"
-#include "kdf_hits.h"
-#include "kdf_coverage.h"
-#include "kdf_variants.h"
-#include "kdf_spool.h"
-#include "kdf_bamdev.h"
-
 // ---------------------------------------------------------------------------
 // count --if through a membership sieve.  In the parent-filter / VCF stages almost every window MISSES the filter
 // (discovery/pipeline.py:377-443: a whole parent's reads against the child's candidate k-mers), so partitioning
@@ -317,7 +306,6 @@ __global__ __launch_bounds__(256) void kdf_sieve_build_kernel(const uint64_t *__
     kdf_sieve_bits(kdf_hash(klo[i], KW == 2 ? khi[i] : 0), wmask, w, b);
     atomicOr((unsigned long long *)&words[w], (unsigned long long)b);
 }
-
 
 // the sieve over the keys the (hash-layout) table holds NOW: an index that was loaded with kdf_add_pairs or counted has
 // none (kdf_load_filter builds one from the key list)
@@ -431,164 +419,14 @@ __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
 // engine
 // ===========================================================================
 
-#define KDF_MERGE_MIN_PAIRS (1u << 16)
-enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
-// every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_BD = BUF_VAR + 5, BUF_COUNT = BUF_BD + 3 };
-// the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack"};
-struct kdf_engine {
-    int device = 0;
-    int k = 0;
-    int kw = 1;                   // key words: 1 narrow, 2 wide, 3..7 long (kdf_long.h)
-    int n_cu = 256;               // compute units of the device (persistent-kernel grids)
-    uint64_t dev_total_bytes = 0; // HBM of the device (sizes the entry ring's budget)
-    KdfTable t{};                 // live table
-    uint64_t cap = 0;
-    KdfCtl *ctl = nullptr;        // device
-    unsigned long long *d_out4 = nullptr;   // device scratch for ctl readback
-    unsigned long long *h_out4 = nullptr;   // pinned host mirror
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    uint64_t distinct = 0;        // host mirror after the last sync
-    uint64_t windows = 0;
-    bool filter_mode = false;
-    bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
-    bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
-    DevBuf buf[BUF_COUNT];                           // released together (kdf_destroy); used through the views below
-    DevBuf *const stage = buf + BUF_STAGE;           // [4] staging for the host-buffer entry points
-    // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
-    unsigned long long *kb_small = nullptr;   // totals[16]
-    unsigned long long *kb_totals_host = nullptr;   // pinned [16]
-    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
-    KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
-    // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
-    // table is needed or the ring is full (kb_flush).  Reserved by upper bounds (one entry per stream position), so no
-    // host round trip sits between the stages.
-    uint64_t ring_entries = 0, ring_rows = 0;        // capacity: entries (8 B x kw each), rows (pieces)
-    uint64_t ring_used = 0, rows_used = 0;           // reserved by the pending passes
-    uint32_t n_pass = 0;
-    uint64_t pend_positions = 0;                     // stream positions of the pending passes (upper bound of their entries)
-    KbPlan pend_plan{};                              // geometry (c1, c2, key slice) the pending passes were partitioned with
-    bool pend_filtered = false;                      // the pending passes are count --if passes
-    uint64_t stat_flushes = 0;
-    double grow_ratio = 0.0;                         // new distinct keys per counted window at the last flush (0: unknown)
-    uint64_t dens_windows = 0, dens_positions = 0;   // valid windows / stream positions of every pass this engine has flushed: sizes the piece groups
-    // L1: small insert batches are concatenated (packed) in a pending stream first; the partition runs over ~2^30 positions
-    uint64_t *l1_packed = nullptr, *l1_mask = nullptr;
-    uint64_t l1_cap_tiles = 0, l1_tiles = 0;
-    uint32_t opt_key_parts = 0, opt_key_part = 0;    // count only one slice of the key space (KdfTable::key_parts)
-    uint64_t opt_binned_min_positions = 1ull << 22;  // fewer pending positions at flush time use the direct global-table kernels
-    uint64_t opt_binned_bytes_per_position = 70;     // ... and so does a flush of fewer than table_bytes / 70 positions (use_binned)
-    uint64_t opt_binned_max_positions = 1ull << 31;  // longer streams are partitioned in several passes
-    uint32_t opt_binned_filtered_min_log2cap = 23;   // count --if goes binned from 2^23 slots (measured crossover)
-    uint32_t opt_big_bucket_log2cap = 32;            // tables from 2^32 slots on have buckets of twice the slots (KDF_BIG_BUCKET_LOG2CAP / option big_bucket_log2cap)
-    uint64_t opt_merge_min_pairs = KDF_MERGE_MIN_PAIRS;   // below this many pairs a merge goes straight to the atomic insert (tests lower it)
-    uint32_t opt_hash_shift = 0;                     // KdfTable::hshift of the tables this engine creates (owner tables)
-    int opt_force_path = 0;                          // 0 auto, 1 direct, 2 binned, 4 sieve only (count --if)
-    int opt_defer = 1;                               // 1: kernel C is deferred over the pending passes; 0: every count call ends with a flush
-    uint64_t opt_defer_max_bytes = 0;                // budget of the entry ring (0: 40 % of the device's memory)
-    // 1 (the default): a dump (min_count >= 1, caller-sized device buffers) asked for while passes are pending is written by the
-    // flush itself -- kernel C holds every bucket anyway (kb_bucket_kernel<.., DUMP>), and the dump's pass over the table is
-    // saved.  Option "fused_dump" / env KDF_FUSED_DUMP=0 turn it off; long engines have no binned pipeline: 0
-    int opt_fused_dump = [] { const char *e = getenv("KDF_FUSED_DUMP"); return e ? atoi(e) != 0 : 1; }();
-    // the request a dump hands to the LAST flush before it (fuse_min > 0), and what came of it
-    uint32_t fuse_min = 0; uint64_t *fuse_lo = nullptr, *fuse_hi = nullptr; uint32_t *fuse_cnt = nullptr; uint64_t fuse_cap = 0;
-    bool fuse_done = false; uint64_t fuse_n = 0;
-    uint64_t stat_fused_dumps = 0;
-    // 1 (the default): such a dump into a table that is still only logically empty (kdf_clear, nothing applied since) runs the
-    // DUMP-ONLY flush -- kb_bucket_kernel<.., DUMP, LAZY> writes the dump and the ctl counters and leaves the table alone.  The
-    // passes stay in the ring (the first n_dumped of n_pass); whatever needs the table later applies them with the ordinary
-    // flush, into the still empty table.  Option "lazy_table" / env KDF_LAZY_TABLE=0 turn it off.
-    int opt_lazy_table = [] { const char *e = getenv("KDF_LAZY_TABLE"); return e ? atoi(e) != 0 : 1; }();
-    uint32_t n_dumped = 0;                           // pending passes a dump-only flush has applied: kept for the table, reported as flushed
-    uint64_t dumped_positions = 0;                   // ... and their stream positions
-    uint64_t acct_entries = 0, acct_positions = 0;   // what of the pending passes dens_windows / dens_positions already hold
-    uint64_t stat_dump_only = 0, stat_materialisations = 0;
-    uint64_t opt_l1_positions = 1ull << 30;          // pending-stream size from which it is partitioned
-    uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
-    // double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
-    // stream of their own, so the H2D copy of batch i + 1 runs under the count of batch i
-    DevBuf (*const up_buf)[2] = (DevBuf (*)[2])(buf + BUF_UP);      // [slot][packed, mask]
-    uint64_t up_n[2] = {0, 0}; bool up_valid[2] = {false, false};
-    hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr}, use_done[2] = {nullptr, nullptr};
-    uint64_t stat_heavy_buckets = 0;
-    void *kb_heavy = nullptr;                        // heavy buckets of skewed flushes (kdf_binned.h kb_heavy_slice_kernel)
-    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly)
-    uint32_t merge_flag_host = 0;
-    int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
-    int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
-    // long engines take the sieve only when asked to (option "long_sieve" / env KDF_LONG_SIEVE=1; k <= 63: always): their
-    // count --if and scan then go through kdf_long_sieve_kernel (kdf_long_sieve.h)
-    int opt_long_sieve = [] { const char *e = getenv("KDF_LONG_SIEVE"); return e ? atoi(e) != 0 : 0; }();
-    int last_sieve_in_lds = 0;                       // the last sieve kernel read the sieve from LDS (1) or from L2 (0)
-    bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
-    bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
-    int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve
-    int last_scan_path = 0;                          // kernel of the last kdf_scan_reads_dev: 0 direct, 3 sieve
-    uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
-    uint64_t sieve_words = 0, sieve_alloc = 0;
-    bool sieve_valid = false;
-    bool sieve_unfit = false;                        // long_sieve_ensure found the table's keys too many for a sieve: not asked again
-                                                     // until the keys, the filter or the sizing options change (sieve_drop)
-    uint32_t last_sieve_rounds = 0;                  // tiles per thread of the last sieve kernel of a long engine (LDS form; L2 form: 1)
-    uint32_t opt_debug_flags = 0;                    // experiments only (KbPlan::dbg)
-    uint64_t stat_binned_passes = 0, stat_replayed_buckets = 0;
-    // optional HIP-event timing (kdf_profile).  T_STREAM, the dominant kernels: a span's tag is its tiles, so passes are the
-    // launches and tag_sum x 64 the positions (a flush is timed with tag 0: its positions were counted with the passes it
-    // applies).  T_HITS: tag 1 for the span that opens a call, 0 for the second span of a call that finds hits.
-    bool prof = false;
-    EvTimer timer[T_COUNT];
-    // binned path: events around each stage (A0 hist, A1 scatter, B finesort | C bucket)
-    std::vector<std::vector<hipEvent_t>> prof_stage_ev;   // 4 events: a partition (A0, A1, B); 2 events: a flush (C)
-    double prof_stage_ms[4] = {0, 0, 0, 0};
-    uint64_t prof_stage_passes = 0;
-    // ---- two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off ------------------------
-    int pf_state = PF_OFF;
-    KdfPrefilter pf{};                               // the sieve (device), its size and the gate's threshold
-    unsigned long long *pf_ctr = nullptr;            // device: sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
-    uint64_t *pf_admit = nullptr; uint64_t pf_admit_words = 0;   // the gate's output for the stream being counted (grow-only)
-    uint64_t capacity_hint = 0;                      // kdf_create's: sizes the sieve when the caller leaves that to the engine
-    uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
-    // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
-    DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
-    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch and the staging of the host forms -------------
-    DevBuf *const cov_buf = buf + BUF_COV;           // [6] 0 CIGAR prefix sums, 1 ref_start, 2 cigar, 3 cigar_offsets, 4 kmer_cov, 5 read_cov
-    // ---- VCF mode (kdf_variants.h): grow-only scratch and the staging of the host forms -------------------------------------
-    DevBuf *const var_buf = buf + BUF_VAR;           // [5] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags, 3 / 4 host forms: inputs / outputs
-    // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
-    bool sk_on = false;
-    KdfSketch sk{};                                  // the register cells (device) and p
-    uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
-    unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
-    // ---- device BAM feeder (kdf_bamdev.h): grow-only scratch kept between batches ---------------------------------------------
-    DevBuf *const bd_buf = buf + BUF_BD;             // [3] 0 inflated span, 1 block / sub-range status, counts, bases and totals, 2 per-read sequence offsets
-    // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
-    // "bamdev_host_inflate": tells a decoder fault from a file fault, and lets the tests walk the patch path, which no file zlib wrote takes)
-    int opt_bd_host_inflate = 0;
-    uint64_t stat_bd_fallback = 0;                   // blocks the device decoder rejected and zlib inflated (stat "bamdev_fallback_blocks")
-    std::string err;
-};
+thread_local std::string g_err;
 
-static thread_local std::string g_err;
-
-static int fail(kdf_engine *h, int code, const char *fmt, ...) {
+int fail(kdf_engine *h, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     if (h) h->err = buf; else g_err = buf;
     return code;
 }
-
-#define HIPCHK(h, call)                                                                 \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return fail(h, e_ == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP,     \
-                        "%s failed: %s", #call, hipGetErrorString(e_));                 \
-    } while (0)
-
-static uint32_t log2ceil(uint64_t x) { uint32_t l = 0; while ((1ull << l) < x) ++l; return l; }
 
 // slots needed so that n keys sit at load <= 0.5 (narrow: 8192-slot buckets,
 // wide: 4096-slot buckets = what one workgroup can hold in LDS)
@@ -634,7 +472,7 @@ static void table_free(KdfTable &t) {
 
 // kdf_clear defers the 12 B/slot memset: a binned insert into an empty table
 // rewrites every bucket anyway.  Everything else calls this first.
-static int materialize(kdf_engine *h) {
+int materialize(kdf_engine *h) {
     if (!h->lazy_empty) return KDF_OK;
     HIPCHK(h, hipMemsetAsync(h->t.lo, 0xFF, h->cap * 8, h->stream));
     if (h->kw >= 2) HIPCHK(h, hipMemsetAsync(h->t.hi, 0xFF, h->cap * 8 * (h->kw - 1), h->stream));
@@ -646,7 +484,7 @@ static int materialize(kdf_engine *h) {
 // Room for `bytes` in one of the engine's buffers whose readers all run on the engine's stream (staging, binned scratch,
 // merge scratch, hit reduction): slack(bytes) are allocated (the site's rule), the stream is drained before a free.
 // what: the buffer's name in the message of a failed allocation (NULL: the plain HIP error text).
-static int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t) = slack_8th, const char *what = nullptr) {
+int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t), const char *what) {
     const size_t want = slack(bytes);
     const hipError_t e = dev_reserve(b, bytes, want, [&] { (void)hipStreamSynchronize(h->stream); return hipSuccess; });
     if (e == hipSuccess) return KDF_OK;
@@ -678,28 +516,8 @@ static int ctl_reset(kdf_engine *h, bool keep_windows) {
     return KDF_OK;
 }
 
-// code for k <= 63 only (the binned pipeline, merge, sieve): W = 1 or 2
-template <typename F>
-static int by_width(kdf_engine *h, F &&f) { return h->kw == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{}); }
-// code for every key width: W = 1, 2 (kdf_device.h) or 3 .. 7 (long keys, kdf_long.h)
-template <typename F>
-static int by_words(kdf_engine *h, F &&f) {
-    switch (h->kw) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 5: return f(std::integral_constant<int, 5>{});
-    case 6: return f(std::integral_constant<int, 6>{});
-    default: return f(std::integral_constant<int, 7>{});
-    }
-}
-// long engines: W = 3 .. 7
-static bool is_long(const kdf_engine *h) { return h->kw > 2; }
 // the sieve no longer describes the table (keys joined it, it was cleared, a new filter, other sizing options)
 static void sieve_drop(kdf_engine *h) { h->sieve_valid = false; h->sieve_unfit = false; }
-// bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
-static int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
 
 // Insert-or-add n keys into table t, adding add[i] (NULL: 0).  Caller keys (stored = false) are the (lo, hi) arrays of
 // k <= 63 or the row-major W-word rows at lo of long keys; stored = true: lo / hi are the arrays of the live table,
@@ -882,8 +700,6 @@ static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t 
     return KDF_OK;
 }
 
-static int table_rehash(kdf_engine *h, uint32_t new_log2);
-
 // the small device arrays of the binned path, allocated once per engine; fills the pointers of `s` from the engine's buffers
 static int kb_scratch(kdf_engine *h, KbScratch &s) {
     if (!h->kb_small) {
@@ -1041,10 +857,39 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     return KDF_OK;
 }
 
+// tally (admit == NULL) or gate (admit[tile] written) over a device-resident stream
+static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t *admit) {
+    launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, admit,
+                 [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *adm) {
+        constexpr int W = decltype(Wc)::value;
+#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->pf, h->pf_ctr, adm)
+        if constexpr (W <= 2) { if (adm) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
+        else { if (adm) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
+#undef PF_LAUNCH
+    });
+}
+
+// Armed: *admit = one word per tile of the stream, bit i = window i is valid and its cell reads >= min_count (stream
+// order: the buffer is reused by the next gated stream).  Not armed: *admit = NULL, the count is not gated.
+static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit) {
+    *admit = nullptr;
+    if (h->pf_state != PF_ARMED || n_bases == 0) return KDF_OK;
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    if (h->pf_admit_words < n_tiles) {
+        if (h->pf_admit) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->pf_admit); h->pf_admit = nullptr; h->pf_admit_words = 0; }
+        const uint64_t want = n_tiles + n_tiles / 8 + 512;
+        HIPCHK(h, hipMalloc((void **)&h->pf_admit, want * 8));
+        h->pf_admit_words = want;
+    }
+    pf_launch(h, d_packed, d_invalid, n_bases, h->pf_admit);
+    HIPCHK(h, hipGetLastError());
+    *admit = h->pf_admit;
+    return KDF_OK;
+}
+
 // partition a stream of any length: passes of at most opt_binned_max_positions
 // positions, each starting on a tile boundary (windows that start in a pass may read on
 // into the next tiles: the stream is one buffer)
-static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit);
 static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, bool filtered) {
     const uint64_t step = h->opt_binned_max_positions;
     const uint64_t *admit = nullptr;                      // armed prefilter: the gate runs once over the whole stream
@@ -1316,7 +1161,7 @@ static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_
 }
 
 // everything pending (the concatenated small batches, the partitioned passes) goes into the table
-static int pending_flush(kdf_engine *h, bool fuse = false) {
+int pending_flush(kdf_engine *h, bool fuse) {
     int rc;
     const uint32_t want_fuse = fuse ? h->fuse_min : 0u;
     h->fuse_min = 0; h->fuse_done = false;                     // (only the LAST flush below may dump: earlier ones see counts that are not final)
@@ -1399,7 +1244,33 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
     });
 }
 
-static int sieve_prepare(kdf_engine *h, uint64_t n);
+// Size, allocate and zero the membership sieve for n keys (sieve_valid says whether there is one).  Every window costs
+// one random 8-byte read of it, i.e. one L2 request: measured on the parent-filter workload (1.49 G windows, 1.9 M keys)
+// 8.3 ms with a 2 MB sieve, 9.1 ms with 4 MB, 16 ms with 8 MB, 24 ms with 16 MB -- it must sit in the 4 MB L2 of every XCD
+// beside the streamed reads.  So: the most bits per key out of 32 / 16 / 8 that keep it within 2 MB, 8 bits per key beyond
+// that, and no sieve (the binned path) once even that passes 16 MB.  Up to 64 K keys it is shrunk to the 64 KB that the
+// kernel copies into LDS (no L2 request per window at all: ~700 Gk-mer/s for the filters of VCF mode and Module 3).
+static int sieve_prepare(kdf_engine *h, uint64_t n) {
+    h->sieve_valid = false;
+    uint64_t bpk = h->opt_sieve_bits ? (uint64_t)h->opt_sieve_bits : 32;
+    if (!h->opt_sieve_bits) {
+        while (bpk > 8 && n * bpk > (16ull << 20)) bpk >>= 1;
+        if (n * 8 <= (uint64_t)KDF_SV_LDS_WORDS * 64) while (bpk > 8 && n * bpk > (uint64_t)KDF_SV_LDS_WORDS * 64) bpk >>= 1;
+    }
+    if (!(h->opt_sieve_bits || n * bpk <= (128ull << 20))) return KDF_OK;
+    const uint64_t bits = n * bpk;
+    const uint64_t words = std::max<uint64_t>(1024, 1ull << log2ceil((bits + 63) / 64));
+    if (h->sieve_alloc < words) {
+        if (h->sieve) (void)hipFree(h->sieve);
+        h->sieve = nullptr; h->sieve_alloc = 0;
+        HIPCHK(h, hipMalloc((void **)&h->sieve, words * 8));
+        h->sieve_alloc = words;
+    }
+    h->sieve_words = words;
+    HIPCHK(h, hipMemsetAsync(h->sieve, 0, words * 8, h->stream));
+    h->sieve_valid = true;
+    return KDF_OK;
+}
 
 // long engines, option "long_sieve": the sieve over the keys the table holds now (kdf_long_sieve_from_table_kernel)
 // unless there is one; sieve_valid tells whether the keys fit one (sieve_prepare)
@@ -1525,7 +1396,7 @@ static int upload_padded(kdf_engine *h, const uint64_t *packed, const uint64_t *
     return KDF_OK;
 }
 
-static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
+int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
                          uint64_t **d_packed, uint64_t **d_invalid) {
     uint64_t pw, mw;
     kdf_stream_words(n_bases, &pw, &mw);
@@ -1538,27 +1409,13 @@ static int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *
 }
 
 // room for, and a copy of, `bytes` host bytes in staging slot i (stream order)
-static int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn) {
+int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn) {
     int rc = eng_reserve(h, h->stage[i], bytes);
     if (rc) return rc;
     const hipError_t e = hipMemcpyAsync(h->stage[i].p, src, bytes, hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "%s: copy of %zu bytes to the device failed: %s", fn, bytes, hipGetErrorString(e));
     return KDF_OK;
 }
-
-// ---------------------------------------------------------------------------
-// Where a consumer's read stream comes from (count, count --if, prefilter tally, sketch, a spool's append): device
-// pointers, host arrays or an upload slot.  Each maker holds its form's refusals, worded with the caller's name; an
-// entry point is "refuse by state, make a source, run the _dev core, release".
-
-struct StreamSrc { const uint64_t *packed = nullptr, *invalid = nullptr; uint64_t n_bases = 0; int slot = -1; };
-
-// where the message of a refusal goes: this engine's error string (a spool has its own sink)
-struct EngSink {
-    kdf_engine *h;
-    template <typename... A> int operator()(int code, const char *fmt, A... a) const { return fail(h, code, fmt, a...); }
-};
-struct NoRefusal { int operator()(const StreamSrc &) const { return KDF_OK; } };
 
 static int src_dev(kdf_engine *h, const char *fn, const void *d_packed, const void *d_invalid, uint64_t n_bases, StreamSrc &src) {
     if (n_bases && (!d_packed || !d_invalid)) return fail(h, KDF_ERR_INVALID, "%s: NULL stream", fn);
@@ -1579,61 +1436,13 @@ static int src_host(kdf_engine *h, const char *fn, const uint64_t *packed, const
     return rc;
 }
 
-// The batch of upload slot `slot` (kdf_upload_reads_async), or KDF_ERR_STATE.  also_refuse(src) holds the refusals the
-// caller tests AFTER the slot's: a refused call changes nothing, the slot keeps its batch.  consume: the slot is empty
-// afterwards (count, tally), else it keeps the batch for the next consumer (sketch, spool).  The engine's stream waits for
-// the copy; host_wait: so does the host -- the caller of a count, tally or sketch recycles its (pinned) source buffer as
-// soon as the call returns, and the copy was issued a whole batch ago.  An empty batch (n_bases 0) needs no wait.
-template <typename S, typename R>
-static int src_slot(S &&sink, const char *fn, kdf_engine *h, int slot, bool consume, bool host_wait, StreamSrc &src, R &&also_refuse) {
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return sink(KDF_ERR_STATE, "%s: nothing was uploaded into slot %d", fn, slot);
-    src = StreamSrc{(const uint64_t *)h->up_buf[slot][0].p, (const uint64_t *)h->up_buf[slot][1].p, h->up_n[slot], slot};
-    if (const int rc = also_refuse(src)) return rc;
-    if (consume) h->up_valid[slot] = false;
-    if (src.n_bases == 0) return KDF_OK;
-    hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->up_done[slot], 0);
-    if (e == hipSuccess && host_wait) e = hipEventSynchronize(h->up_done[slot]);
-    if (e != hipSuccess) return sink(e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "%s: waiting for the copy into slot %d failed: %s", fn, slot, hipGetErrorString(e));
-    return KDF_OK;
-}
 // behind the consumer's last launch: the slot's next upload waits for this reader
-static void src_release(kdf_engine *h, const StreamSrc &src) {
+void src_release(kdf_engine *h, const StreamSrc &src) {
     if (src.slot >= 0) (void)hipEventRecord(h->use_done[src.slot], h->stream);
 }
 
 // ---------------------------------------------------------------------------
 // two-pass counting (kdf_prefilter.h)
-
-// tally (admit == NULL) or gate (admit[tile] written) over a device-resident stream
-static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t *admit) {
-    launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, admit,
-                 [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *adm) {
-        constexpr int W = decltype(Wc)::value;
-#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->pf, h->pf_ctr, adm)
-        if constexpr (W <= 2) { if (adm) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
-        else { if (adm) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
-#undef PF_LAUNCH
-    });
-}
-
-// Armed: *admit = one word per tile of the stream, bit i = window i is valid and its cell reads >= min_count (stream
-// order: the buffer is reused by the next gated stream).  Not armed: *admit = NULL, the count is not gated.
-static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit) {
-    *admit = nullptr;
-    if (h->pf_state != PF_ARMED || n_bases == 0) return KDF_OK;
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if (h->pf_admit_words < n_tiles) {
-        if (h->pf_admit) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->pf_admit); h->pf_admit = nullptr; h->pf_admit_words = 0; }
-        const uint64_t want = n_tiles + n_tiles / 8 + 512;
-        HIPCHK(h, hipMalloc((void **)&h->pf_admit, want * 8));
-        h->pf_admit_words = want;
-    }
-    pf_launch(h, d_packed, d_invalid, n_bases, h->pf_admit);
-    HIPCHK(h, hipGetLastError());
-    *admit = h->pf_admit;
-    return KDF_OK;
-}
 
 static int pf_tally_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (n_bases == 0) return KDF_OK;
@@ -1710,9 +1519,6 @@ static int sk_pack(kdf_engine *h, uint8_t *d_out) {
     do { if ((h)->pf_state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
                                                        fn, (h)->pf_state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
 
-// words per key of a host form's first key array: 1 for the (lo, hi) forms, W for the rows of the _w forms
-static uint64_t lo_words(const kdf_engine *h) { return is_long(h) ? h->kw : 1; }
-
 // n keys of a host form into staging slots 2 (lo, or the rows of long keys) and 3 (hi, k 33..63)
 static int stage_keys(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uint64_t n, const char *fn) {
     int rc = stage_in(h, 2, lo, n * 8 * lo_words(h), fn);
@@ -1723,13 +1529,6 @@ static int stage_keys(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uin
 // ===========================================================================
 // C ABI
 // ===========================================================================
-
-// The (lo, hi) key forms take k <= 63 engines only; a long engine names the W-word form to use instead.  The multi-GPU
-// entry points are single-GPU-only for long keys.
-#define KDF_REFUSE_LONG(h, fn, wfn) \
-    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: k=%d takes %d-word keys: use %s", fn, (h)->k, (h)->kw, wfn); } while (0)
-#define KDF_REFUSE_LONG_MULTI(h, fn) \
-    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: not available for k > 63 (long keys count on one GPU)", fn); } while (0)
 
 extern "C" {
 
@@ -1933,34 +1732,6 @@ int kdf_count_uploaded(kdf_engine *h, int slot, int filtered) {
     rc = filtered ? count_filtered_dev(h, src.packed, src.invalid, src.n_bases) : count_insert_dev(h, src.packed, src.invalid, src.n_bases);
     src_release(h, src);
     return rc;
-}
-
-// Size, allocate and zero the membership sieve for n keys (sieve_valid says whether there is one).  Every window costs
-// one random 8-byte read of it, i.e. one L2 request: measured on the parent-filter workload (1.49 G windows, 1.9 M keys)
-// 8.3 ms with a 2 MB sieve, 9.1 ms with 4 MB, 16 ms with 8 MB, 24 ms with 16 MB -- it must sit in the 4 MB L2 of every XCD
-// beside the streamed reads.  So: the most bits per key out of 32 / 16 / 8 that keep it within 2 MB, 8 bits per key beyond
-// that, and no sieve (the binned path) once even that passes 16 MB.  Up to 64 K keys it is shrunk to the 64 KB that the
-// kernel copies into LDS (no L2 request per window at all: ~700 Gk-mer/s for the filters of VCF mode and Module 3).
-static int sieve_prepare(kdf_engine *h, uint64_t n) {
-    h->sieve_valid = false;
-    uint64_t bpk = h->opt_sieve_bits ? (uint64_t)h->opt_sieve_bits : 32;
-    if (!h->opt_sieve_bits) {
-        while (bpk > 8 && n * bpk > (16ull << 20)) bpk >>= 1;
-        if (n * 8 <= (uint64_t)KDF_SV_LDS_WORDS * 64) while (bpk > 8 && n * bpk > (uint64_t)KDF_SV_LDS_WORDS * 64) bpk >>= 1;
-    }
-    if (!(h->opt_sieve_bits || n * bpk <= (128ull << 20))) return KDF_OK;
-    const uint64_t bits = n * bpk;
-    const uint64_t words = std::max<uint64_t>(1024, 1ull << log2ceil((bits + 63) / 64));
-    if (h->sieve_alloc < words) {
-        if (h->sieve) (void)hipFree(h->sieve);
-        h->sieve = nullptr; h->sieve_alloc = 0;
-        HIPCHK(h, hipMalloc((void **)&h->sieve, words * 8));
-        h->sieve_alloc = words;
-    }
-    h->sieve_words = words;
-    HIPCHK(h, hipMemsetAsync(h->sieve, 0, words * 8, h->stream));
-    h->sieve_valid = true;
-    return KDF_OK;
 }
 
 __global__ void kdf_ctl_clear_error_bits_kernel(KdfCtl *ctl, unsigned int bits) { atomicAnd(&ctl->error, ~bits); }
@@ -2599,673 +2370,6 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
         std::sort(keys.begin(), keys.end());
         distinct_out[r] = (uint32_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
     }
-    return KDF_OK;
-}
-
-// ------------------------------------------------ count profile of a read stream (kdf_depth.h) ----
-
-// One launch of kdf_depth_kernel over the stream: the per-window form (rows == NULL) or the per-read form.  The table is
-// only read; pending count work is applied first, as the scan does.
-static int depth_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint32_t *d_counts,
-                      unsigned long long *d_valid, const int64_t *d_offs, int64_t n_reads, uint32_t low_max, unsigned long long *d_rows) {
-    { int rcf = pending_flush(h); if (rcf) return rcf; }
-    { int rc0 = materialize(h); if (rc0) return rc0; }
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    const uint64_t waves = (n_tiles + KD_WAVE_TILES - 1) / KD_WAVE_TILES;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
-    EvSpan span(h->timer[T_DEPTH], h->prof, h->stream);
-    if (d_rows) HIPCHK(h, hipMemsetAsync(d_rows, 0, (size_t)n_reads * KD_ROW_WORDS * 8, h->stream));
-    by_words(h, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        if (d_rows)
-            hipLaunchKernelGGL((kdf_depth_kernel<W, true>), dim3(blocks), dim3(256), 0, h->stream, d_packed, d_invalid, n_bases, h->k, h->t,
-                               (uint32_t *)nullptr, (unsigned long long *)nullptr, d_offs, n_reads, low_max, d_rows);
-        else
-            hipLaunchKernelGGL((kdf_depth_kernel<W, false>), dim3(blocks), dim3(256), 0, h->stream, d_packed, d_invalid, n_bases, h->k, h->t,
-                               d_counts, d_valid, (const int64_t *)nullptr, (int64_t)0, 0u, (unsigned long long *)nullptr);
-        return 0;
-    });
-    if (d_rows) hipLaunchKernelGGL(kd_rows_fix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, d_rows, n_reads);
-    span.stop();
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
-}
-
-int kdf_window_counts_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, void *d_counts_out,
-                          void *d_valid_bits_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_bases == 0) return KDF_OK;
-    if (!d_packed || !d_invalid || !d_counts_out) return fail(h, KDF_ERR_INVALID, "kdf_window_counts_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    return depth_pass(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, (uint32_t *)d_counts_out,
-                      (unsigned long long *)d_valid_bits_out, nullptr, 0, 0, nullptr);
-}
-
-int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, uint32_t *counts_out,
-                      uint64_t *valid_bits_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    uint64_t pw, mw;
-    kdf_stream_words(n_bases, &pw, &mw);
-    if (valid_bits_out) memset(valid_bits_out, 0, mw * 8);
-    if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_window_counts: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if ((rc = eng_reserve(h, h->stage[2], n_bases * 4))) return rc;
-    if (valid_bits_out && (rc = eng_reserve(h, h->stage[3], n_tiles * 8))) return rc;
-    if ((rc = kdf_window_counts_dev(h, dp, dm, n_bases, h->stage[2].p, valid_bits_out ? h->stage[3].p : nullptr))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[2].p, n_bases * 4, hipMemcpyDeviceToHost, h->stream));
-    if (valid_bits_out) HIPCHK(h, hipMemcpyAsync(valid_bits_out, h->stage[3].p, n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
-}
-
-int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
-                       int64_t n_reads, uint32_t low_max, void *d_rows_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (n_reads == 0) return KDF_OK;
-    if (!d_read_offsets || !d_rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    if (n_bases == 0) {                                             // no window: every row is zero
-        HIPCHK(h, hipMemsetAsync(d_rows_out, 0, (size_t)n_reads * KD_ROW_WORDS * 8, h->stream));
-        return KDF_OK;
-    }
-    if (!d_packed || !d_invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth_dev: NULL stream");
-    return depth_pass(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, nullptr, nullptr,
-                      (const int64_t *)d_read_offsets, n_reads, low_max, (unsigned long long *)d_rows_out);
-}
-
-int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
-                   int64_t n_reads, uint32_t low_max, uint64_t *rows_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_reads > 0 && (!read_offsets || !rows_out)) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL pointer");
-    if (const int rc = check_read_offsets(EngSink{h}, "kdf_read_depth", read_offsets, n_reads)) return rc;
-    if (n_reads == 0) return KDF_OK;
-    const size_t row_bytes = (size_t)n_reads * KD_ROW_WORDS * 8;
-    if (n_bases == 0) { memset(rows_out, 0, row_bytes); return KDF_OK; }
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL stream");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_depth"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
-    if ((rc = kdf_read_depth_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, low_max, h->stage[3].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
-}
-
-// ------------------------------------------------ per-read hits of the scan (kdf_hits.h) ----
-
-// Steps 1-2 of kdf_hits.h over the mask words of n_bases positions (n_bases >= 1): hit_buf[1] then holds the exclusive
-// prefix of every block of KH_BLOCK_WORDS words and, behind them, the number of set bits below n_bases.
-static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, uint64_t *n_blocks_out) {
-    const uint64_t n_words = (n_bases + 63) / 64;
-    const uint64_t n_blocks = (n_words + KH_BLOCK_WORDS - 1) / KH_BLOCK_WORDS;
-    if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "a hit mask of %llu positions is beyond the 2^47 a call takes", (unsigned long long)n_bases);
-    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
-    if (rc) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
-    hipLaunchKernelGGL(kh_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_bits, n_bases, sums);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
-    HIPCHK(h, hipGetLastError());
-    *n_blocks_out = n_blocks;
-    return KDF_OK;
-}
-
-// the total hits_count left, on the host (synchronises)
-static int hits_total(kdf_engine *h, uint64_t n_blocks, uint64_t *n_hits) {
-    HIPCHK(h, hipMemcpyAsync(h->h_out4, (unsigned long long *)h->hit_buf[1].p + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_hits = h->h_out4[0];
-    return KDF_OK;
-}
-
-int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
-                      int64_t n_reads, void *d_hit_bits, void *d_rows_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (n_reads > 0 && (!d_read_offsets || !d_rows_out)) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t row_bytes = (size_t)n_reads * KH_ROW_WORDS * 4;
-    if (n_bases == 0) {                                             // no window: every row is zero, no hit word is written
-        if (n_reads) HIPCHK(h, hipMemsetAsync(d_rows_out, 0, row_bytes, h->stream));
-        return KDF_OK;
-    }
-    if (!d_packed || !d_invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: NULL stream");
-    int rc;
-    uint64_t *bits = (uint64_t *)d_hit_bits;
-    if (!bits) {
-        if ((rc = eng_reserve(h, h->hit_buf[0], (n_bases + 63) / 64 * 8, slack_8th, "hit mask"))) return rc;
-        bits = (uint64_t *)h->hit_buf[0].p;
-    }
-    if ((rc = kdf_scan_reads_dev(h, d_packed, d_invalid, n_bases, bits))) return rc;     // (applies pending count work)
-    if (n_reads == 0) return KDF_OK;
-    // a (read, slot) pair must fit 63 bits: bit 63 keeps every pair apart from the set's empty word
-    if (log2ceil((uint64_t)n_reads) + h->t.log2cap > 63)
-        return fail(h, KDF_ERR_INVALID, "kdf_read_hits_dev: %lld reads against a table of 2^%u slots: read index and slot index must fit 63 bits "
-                    "together (at most 2^%u reads per call for this table)", (long long)n_reads, h->t.log2cap, 63 - h->t.log2cap);
-    uint64_t n_blocks = 0, n_hits = 0;
-    EvSpan p1(h->timer[T_HITS], h->prof, h->stream, 1);           // (opens the call: counted as its pass)
-    HIPCHK(h, hipMemsetAsync(d_rows_out, 0, row_bytes, h->stream));
-    if ((rc = hits_count(h, bits, n_bases, &n_blocks))) return rc;
-    p1.stop();
-    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
-    if (n_hits == 0) return KDF_OK;
-    uint32_t log2set = log2ceil(2 * n_hits);
-    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
-    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (read, k-mer) pairs"))) return rc;
-    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
-    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
-    const int64_t *offs = (const int64_t *)d_read_offsets;
-    EvSpan p2(h->timer[T_HITS], h->prof, h->stream, 0);           // (the same call's second group: time only)
-    HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
-    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, (const unsigned long long *)h->hit_buf[1].p,
-                       pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
-    hipLaunchKernelGGL(kh_hits_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads,
-                       (uint32_t *)d_rows_out);
-    by_words(h, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        hipLaunchKernelGGL(kh_distinct_kernel<W>, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_packed, n_bases,
-                           h->k, h->t, pos, n_hits, offs, n_reads, set, log2set, (uint32_t *)d_rows_out);
-        return 0;
-    });
-    p2.stop();
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
-}
-
-int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
-                  int64_t n_reads, uint64_t *hit_bits, uint32_t *rows_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    int rc = check_read_offsets(EngSink{h}, "kdf_read_hits", read_offsets, n_reads);       // (before any device work)
-    if (rc) return rc;
-    if (n_reads > 0 && !rows_out) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: rows_out is NULL");
-    uint64_t pw, mw;
-    kdf_stream_words(n_bases, &pw, &mw);
-    const size_t row_bytes = (size_t)n_reads * KH_ROW_WORDS * 4;
-    if (hit_bits) memset(hit_bits, 0, mw * 8);
-    if (n_bases == 0) { if (n_reads) memset(rows_out, 0, row_bytes); return KDF_OK; }
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: NULL stream");
-    if (n_reads == 0 && !hit_bits) return KDF_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
-    if (n_reads) {
-        if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_hits"))) return rc;
-        if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
-    }
-    if ((rc = kdf_read_hits_dev(h, dp, dm, n_bases, n_reads ? h->stage[2].p : nullptr, n_reads, nullptr, n_reads ? h->stage[3].p : nullptr))) return rc;
-    if (n_reads) HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0].p, (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
-}
-
-int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets, int64_t n_reads,
-                     void *d_positions_out, void *d_reads_out, uint64_t cap, uint64_t *n_out) {
-    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: NULL pointer");
-    *n_out = 0;
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (d_reads_out && !d_read_offsets) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: reads_out needs read_offsets");
-    if (n_bases == 0) return KDF_OK;
-    if (!d_hit_bits || (cap && !d_positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t n_blocks = 0, n_hits = 0;
-    int rc;
-    EvSpan p(h->timer[T_HITS], h->prof, h->stream, 1);
-    if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_bases, &n_blocks))) return rc;
-    if (cap)
-        hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_bases,
-                           (const unsigned long long *)h->hit_buf[1].p, (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
-                           (const int64_t *)d_read_offsets, n_reads, cap);
-    p.stop();
-    HIPCHK(h, hipGetLastError());
-    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
-    *n_out = n_hits;
-    if (n_hits > cap)
-        return fail(h, KDF_ERR_INVALID, "kdf_hit_list_dev: the mask holds %llu hits, the buffers %llu", (unsigned long long)n_hits, (unsigned long long)cap);
-    return KDF_OK;
-}
-
-int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets, int64_t n_reads,
-                 uint64_t *positions_out, int64_t *reads_out, uint64_t cap, uint64_t *n_out) {
-    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
-    *n_out = 0;
-    if (reads_out && !read_offsets) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: reads_out needs read_offsets");
-    int rc = check_read_offsets(EngSink{h}, "kdf_hit_list", read_offsets, read_offsets ? n_reads : (n_reads < 0 ? n_reads : 0));
-    if (rc) return rc;
-    if (n_bases == 0) return KDF_OK;
-    if (!hit_bits || (cap && !positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_list"))) return rc;
-    if (reads_out && (rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_list"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
-    if (reads_out && (rc = eng_reserve(h, h->stage[3], cap * 8))) return rc;
-    const int rcl = kdf_hit_list_dev(h, h->stage[0].p, n_bases, reads_out ? h->stage[2].p : nullptr, reads_out ? n_reads : 0, h->stage[1].p,
-                                     reads_out ? h->stage[3].p : nullptr, cap, n_out);
-    if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
-    const uint64_t n = std::min<uint64_t>(*n_out, cap);
-    if (n) {
-        HIPCHK(h, hipMemcpyAsync(positions_out, h->stage[1].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (reads_out) HIPCHK(h, hipMemcpyAsync(reads_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return rcl;
-}
-
-// ------------------------------------------------ hits in reference coordinates (kdf_coverage.h) ----
-
-int kdf_hit_coverage_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets, int64_t n_reads,
-                         const void *d_ref_start, const void *d_cigar, uint64_t n_cigar, const void *d_cigar_offsets,
-                         void *d_kmer_cov, void *d_read_cov, uint64_t span) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (n_reads == 0 || n_bases == 0) return KDF_OK;
-    if (!d_hit_bits || !d_read_offsets || !d_ref_start || !d_cigar_offsets || (n_cigar && !d_cigar) || (span && (!d_kmer_cov || !d_read_cov)))
-        return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage_dev: NULL pointer");
-    // a hit is a set bit p with p + k <= n_bases: the list is cut from the first n_bases - k + 1 bits; without an
-    // operation or an accumulator word nothing can be added
-    if (n_bases < (uint64_t)h->k || n_cigar == 0 || span == 0) return KDF_OK;
-    const uint64_t n_starts = n_bases - (uint64_t)h->k + 1;
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t n_blocks = 0, n_hits = 0;
-    int rc;
-    EvSpan p1(h->timer[T_COV], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
-    if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_starts, &n_blocks))) return rc;
-    p1.stop();
-    if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
-    if (n_hits == 0) return KDF_OK;
-    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
-    if ((rc = eng_reserve(h, h->cov_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
-    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
-    unsigned long long *pre = (unsigned long long *)h->cov_buf[0].p;
-    const int64_t *offs = (const int64_t *)d_read_offsets, *rs = (const int64_t *)d_ref_start, *co = (const int64_t *)d_cigar_offsets;
-    const uint32_t *cig = (const uint32_t *)d_cigar;
-    EvSpan p2(h->timer[T_COV], h->prof, h->stream, 0);            // (the same call's second group: time only)
-    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_starts,
-                       (const unsigned long long *)h->hit_buf[1].p, pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
-    hipLaunchKernelGGL(kc_prefix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads, rs,
-                       cig, n_cigar, co, pre);
-    hipLaunchKernelGGL(kc_accum_kernel, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, h->k, offs, n_reads, rs,
-                       cig, n_cigar, co, (const unsigned long long *)pre, (uint32_t *)d_kmer_cov, (uint32_t *)d_read_cov, span);
-    p2.stop();
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
-}
-
-int kdf_hit_coverage(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, const int64_t *read_offsets, int64_t n_reads,
-                     const int64_t *ref_start, const uint32_t *cigar, uint64_t n_cigar, const int64_t *cigar_offsets,
-                     uint32_t *kmer_cov, uint32_t *read_cov, uint64_t span) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    int rc = check_read_offsets(EngSink{h}, "kdf_hit_coverage", read_offsets, n_reads);  // (before any device work)
-    if (rc) return rc;
-    if (n_reads > 0) {
-        if (!cigar_offsets || !ref_start) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: NULL pointer");
-        if (cigar_offsets[0] != 0) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets[0] = %lld, not 0", (long long)cigar_offsets[0]);
-        for (int64_t r = 0; r < n_reads; ++r)
-            if (cigar_offsets[r + 1] < cigar_offsets[r])
-                return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets decrease at read %lld (%lld after %lld)", (long long)r,
-                            (long long)cigar_offsets[r + 1], (long long)cigar_offsets[r]);
-        if ((uint64_t)cigar_offsets[n_reads] != n_cigar)
-            return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: cigar_offsets end at %lld, n_cigar is %llu", (long long)cigar_offsets[n_reads],
-                        (unsigned long long)n_cigar);
-    }
-    if (n_reads == 0 || n_bases == 0 || n_cigar == 0 || span == 0) return KDF_OK;
-    if (!hit_bits || !cigar || !kmer_cov || !read_cov) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_coverage"))) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_coverage"))) return rc;
-    const void *src[5] = {ref_start, cigar, cigar_offsets, kmer_cov, read_cov};
-    const size_t bytes[5] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, (size_t)span * 4, (size_t)span * 4};
-    for (int i = 0; i < 5; ++i) {
-        if ((rc = eng_reserve(h, h->cov_buf[1 + i], bytes[i]))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cov_buf[1 + i].p, src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = kdf_hit_coverage_dev(h, h->stage[0].p, n_bases, h->stage[2].p, n_reads, h->cov_buf[1].p, h->cov_buf[2].p, n_cigar,
-                                   h->cov_buf[3].p, h->cov_buf[4].p, h->cov_buf[5].p, span))) return rc;
-    HIPCHK(h, hipMemcpyAsync(kmer_cov, h->cov_buf[4].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(read_cov, h->cov_buf[5].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
-}
-
-// d_kmer_cov / d_read_cov point at position `first`
-static int coverage_list_core(kdf_engine *h, const char *fn, const uint32_t *d_kc, const uint32_t *d_rc, uint64_t first, uint64_t n,
-                              uint32_t min_reads, void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap, uint64_t *n_out) {
-    const uint64_t n_blocks = (n + KC_BLOCK_ELEMS - 1) / KC_BLOCK_ELEMS;
-    if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "%s: a window of %llu positions is beyond the 2^41 a call takes", fn, (unsigned long long)n);
-    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
-    if (rc) return rc;
-    const uint32_t thr = std::max<uint32_t>(min_reads, 1);
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
-    EvSpan p(h->timer[T_COV], h->prof, h->stream, 1);
-    hipLaunchKernelGGL(kc_list_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_rc, n, thr, sums);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
-    if (cap)
-        hipLaunchKernelGGL(kc_list_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_kc, d_rc, first, n, thr,
-                           (const unsigned long long *)sums, (uint64_t *)d_pos_out, (uint32_t *)d_kmer_out, (uint32_t *)d_read_out, cap);
-    p.stop();
-    HIPCHK(h, hipGetLastError());
-    uint64_t n_list = 0;
-    if ((rc = hits_total(h, n_blocks, &n_list))) return rc;
-    *n_out = n_list;
-    if (n_list > cap)
-        return fail(h, KDF_ERR_INVALID, "%s: the list holds %llu positions, the buffers %llu", fn, (unsigned long long)n_list, (unsigned long long)cap);
-    return KDF_OK;
-}
-
-int kdf_coverage_list_dev(kdf_engine *h, const void *d_kmer_cov, const void *d_read_cov, uint64_t first, uint64_t n, uint32_t min_reads,
-                          void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap, uint64_t *n_out) {
-    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list_dev: NULL pointer");
-    *n_out = 0;
-    if (n == 0) return KDF_OK;
-    if (!d_read_cov || (cap && !d_pos_out) || (d_kmer_out && !d_kmer_cov)) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    return coverage_list_core(h, "kdf_coverage_list_dev", d_kmer_cov ? (const uint32_t *)d_kmer_cov + first : nullptr,
-                              (const uint32_t *)d_read_cov + first, first, n, min_reads, d_pos_out, d_kmer_out, d_read_out, cap, n_out);
-}
-
-int kdf_coverage_list(kdf_engine *h, const uint32_t *kmer_cov, const uint32_t *read_cov, uint64_t first, uint64_t n, uint32_t min_reads,
-                      uint64_t *pos_out, uint32_t *kmer_out, uint32_t *read_out, uint64_t cap, uint64_t *n_out) {
-    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list: NULL pointer");
-    *n_out = 0;
-    if (n == 0) return KDF_OK;
-    if (!read_cov || (cap && !pos_out) || (kmer_out && !kmer_cov)) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    // the window alone is staged: cov_buf 4 / 5 the sums, stage 1 the positions, stage 0 / 3 the two value columns
-    if ((rc = eng_reserve(h, h->cov_buf[5], (size_t)n * 4))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->cov_buf[5].p, read_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    if (kmer_out) {
-        if ((rc = eng_reserve(h, h->cov_buf[4], (size_t)n * 4))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cov_buf[4].p, kmer_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-        if ((rc = eng_reserve(h, h->stage[0], cap * 4))) return rc;
-    }
-    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
-    if (read_out && (rc = eng_reserve(h, h->stage[3], cap * 4))) return rc;
-    const int rcl = coverage_list_core(h, "kdf_coverage_list", kmer_out ? (const uint32_t *)h->cov_buf[4].p : nullptr, (const uint32_t *)h->cov_buf[5].p,
-                                       first, n, min_reads, h->stage[1].p, kmer_out ? h->stage[0].p : nullptr, read_out ? h->stage[3].p : nullptr, cap, n_out);
-    if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
-    const uint64_t m = std::min<uint64_t>(*n_out, cap);
-    if (m) {
-        HIPCHK(h, hipMemcpyAsync(pos_out, h->stage[1].p, m * 8, hipMemcpyDeviceToHost, h->stream));
-        if (kmer_out) HIPCHK(h, hipMemcpyAsync(kmer_out, h->stage[0].p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        if (read_out) HIPCHK(h, hipMemcpyAsync(read_out, h->stage[3].p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return rcl;
-}
-
-int kdf_hit_keys_dev(kdf_engine *h, const void *d_packed, uint64_t n_bases, const void *d_positions, uint64_t n, void *d_keys_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n == 0) return KDF_OK;
-    if (!d_positions || !d_keys_out || (n_bases && !d_packed)) return fail(h, KDF_ERR_INVALID, "kdf_hit_keys_dev: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    by_words(h, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        hipLaunchKernelGGL(kc_keys_kernel<W>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const uint64_t *)d_packed, n_bases, h->k,
-                           (const uint64_t *)d_positions, n, (uint64_t *)d_keys_out);
-        return 0;
-    });
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
-}
-
-int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const uint64_t *positions, uint64_t n, uint64_t *keys_out) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (n == 0) return KDF_OK;
-    if (!positions || !keys_out || (n_bases && !packed)) return fail(h, KDF_ERR_INVALID, "kdf_hit_keys: NULL pointer");
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t pw, mw;
-    kdf_stream_words(n_bases, &pw, &mw);
-    const uint64_t pw_in = (n_bases + 31) / 32;
-    const size_t key_bytes = (size_t)n * 8 * (size_t)h->kw;
-    int rc;
-    if ((rc = eng_reserve(h, h->stage[0], pw * 8))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->stage[0].p, 0, pw * 8, h->stream));
-    if (pw_in) HIPCHK(h, hipMemcpyAsync(h->stage[0].p, packed, pw_in * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = stage_in(h, 1, positions, (size_t)n * 8, "kdf_hit_keys"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[3], key_bytes))) return rc;
-    if ((rc = kdf_hit_keys_dev(h, h->stage[0].p, n_bases, h->stage[1].p, n, h->stage[3].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[3].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
-}
-
-// ------------------------------------------------ VCF mode on the device (kdf_variants.h) ----
-
-// several host arrays side by side in ONE device buffer, each at a multiple of 16 bytes
-struct Arena {
-    size_t off[16]; size_t bytes = 0; int n = 0;
-    int add(size_t b) { off[n] = bytes; bytes += (b + 15) / 16 * 16; return n++; }
-};
-// offsets that start at 0, do not decrease and end at `total` (cigar_offsets, qual_offsets, alt_offsets)
-static int check_offsets0(kdf_engine *h, const char *fn, const char *what, const int64_t *o, uint64_t n, uint64_t total) {
-    if (!o) return fail(h, KDF_ERR_INVALID, "%s: %s is NULL", fn, what);
-    if (o[0] != 0) return fail(h, KDF_ERR_INVALID, "%s: %s[0] = %lld, not 0", fn, what, (long long)o[0]);
-    for (uint64_t i = 0; i < n; ++i)
-        if (o[i + 1] < o[i])
-            return fail(h, KDF_ERR_INVALID, "%s: %s decrease at %llu (%lld after %lld)", fn, what, (unsigned long long)i, (long long)o[i + 1], (long long)o[i]);
-    if ((uint64_t)o[n] != total) return fail(h, KDF_ERR_INVALID, "%s: %s end at %lld, the array holds %llu", fn, what, (long long)o[n], (unsigned long long)total);
-    return KDF_OK;
-}
-
-int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
-                            int64_t n_reads, const void *d_ref_start, const void *d_cigar, uint64_t n_cigar, const void *d_cigar_offsets,
-                            const void *d_qual, uint64_t n_qual, const void *d_qual_offsets, uint32_t min_baseq, const void *d_var_pos,
-                            const void *d_var_span, const void *d_var_ref_len, uint64_t n_var, const void *d_alt, uint64_t n_alt,
-                            const void *d_alt_offsets, void *d_pair_read, void *d_pair_var, void *d_pair_flags, uint64_t pair_cap,
-                            void *d_entry_pos, void *d_entry_pair, uint64_t entry_cap, uint64_t *n_pairs_out, uint64_t *n_entries_out) {
-    if (!h || !n_pairs_out || !n_entries_out) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: NULL pointer");
-    *n_pairs_out = *n_entries_out = 0;
-    if (n_reads < 0) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (n_reads == 0 || n_var == 0 || n_bases == 0) return KDF_OK;
-    if (!d_packed || !d_invalid || !d_read_offsets || !d_ref_start || !d_cigar_offsets || (n_cigar && !d_cigar) || !d_var_pos || !d_var_span ||
-        !d_var_ref_len || !d_alt_offsets || (n_alt && !d_alt) || (d_qual && !d_qual_offsets) ||
-        (pair_cap && (!d_pair_read || !d_pair_var || !d_pair_flags)) || (entry_cap && (!d_entry_pos || !d_entry_pair)))
-        return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: NULL pointer");
-    if (n_var >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu variants: pair_var holds 32 bits", (unsigned long long)n_var);
-    if (n_bases < (uint64_t)h->k || n_cigar == 0) return KDF_OK;     // no window, or no aligned base
-    HIPCHK(h, hipSetDevice(h->device));
-    const uint64_t nbr = ((uint64_t)n_reads + 255) / 256;
-    if (nbr >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %lld reads are beyond the 2^39 a call takes", (long long)n_reads);
-    int rc;
-    if ((rc = eng_reserve(h, h->hit_buf[1], (nbr + 1) * 8, slack_8th, "block sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[1], (size_t)(2 * (uint64_t)n_reads + 1) * 8, slack_8th, "candidate ranges"))) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
-    uint64_t *cand_lo = (uint64_t *)h->var_buf[1].p;
-    unsigned long long *cand_off = (unsigned long long *)h->var_buf[1].p + n_reads;
-    KvArgs a{};
-    a.packed = (const uint64_t *)d_packed; a.invalid = (const uint64_t *)d_invalid; a.n_bases = n_bases; a.k = h->k;
-    a.offs = (const int64_t *)d_read_offsets; a.n_reads = n_reads; a.ref_start = (const int64_t *)d_ref_start;
-    a.cigar = (const uint32_t *)d_cigar; a.n_cigar = n_cigar; a.cig_offs = (const int64_t *)d_cigar_offsets;
-    a.qual = min_baseq ? (const uint8_t *)d_qual : nullptr; a.n_qual = n_qual; a.qual_offs = (const int64_t *)d_qual_offsets; a.min_baseq = min_baseq;
-    a.var_pos = (const int64_t *)d_var_pos; a.var_span = (const uint32_t *)d_var_span; a.var_ref_len = (const uint32_t *)d_var_ref_len; a.n_var = n_var;
-    a.alt = (const uint8_t *)d_alt; a.n_alt = n_alt; a.alt_offs = (const int64_t *)d_alt_offsets;
-    a.pre = (const unsigned long long *)h->var_buf[0].p; a.cand_lo = cand_lo; a.cand_off = cand_off;
-    EvSpan p1(h->timer[T_VAR], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
-    hipLaunchKernelGGL(kv_range_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, a.ref_start, a.cigar, n_cigar, a.cig_offs, a.var_pos,
-                       n_var, (unsigned long long *)h->var_buf[0].p, cand_lo, cand_off, sums);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, nbr);
-    hipLaunchKernelGGL(kv_offsets_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, (const unsigned long long *)sums, cand_off);
-    p1.stop();
-    HIPCHK(h, hipGetLastError());
-    uint64_t n_cand = 0;
-    if ((rc = hits_total(h, nbr, &n_cand))) return rc;               // (first synchronisation: sizes the per-candidate scratch)
-    if (n_cand == 0) return KDF_OK;
-    const uint64_t nbc = (n_cand + 255) / 256;
-    if (nbc >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu (read, variant) candidates are beyond the 2^39 a call takes", (unsigned long long)n_cand);
-    if ((rc = eng_reserve(h, h->hit_buf[1], 2 * (nbc + 1) * 8, slack_8th, "block sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[2], (size_t)n_cand * 5, slack_8th, "candidate counts"))) return rc;
-    sums = (unsigned long long *)h->hit_buf[1].p;
-    unsigned long long *sums_p = sums, *sums_e = sums + nbc + 1;
-    uint32_t *ent_cnt = (uint32_t *)h->var_buf[2].p;
-    uint8_t *cflags = (uint8_t *)(ent_cnt + n_cand);
-    a.n_cand = n_cand;
-    EvSpan p2(h->timer[T_VAR], h->prof, h->stream, 0);            // (the same call's later groups: time only)
-    hipLaunchKernelGGL(kv_count_kernel, dim3((unsigned)nbc), dim3(256), 0, h->stream, a, ent_cnt, cflags, sums_p, sums_e);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums_p, nbc);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums_e, nbc);
-    p2.stop();
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->h_out4, sums_p + nbc, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->h_out4 + 1, sums_e + nbc, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                      // (second synchronisation: the two counts)
-    const uint64_t n_pairs = h->h_out4[0], n_entries = h->h_out4[1];
-    *n_pairs_out = n_pairs;
-    *n_entries_out = n_entries;
-    if (pair_cap == 0 && entry_cap == 0) {
-        if (!d_pair_read && !d_pair_var && !d_pair_flags && !d_entry_pos && !d_entry_pair) return KDF_OK;       // a sizing call
-    } else if (n_pairs) {
-        EvSpan p3(h->timer[T_VAR], h->prof, h->stream, 0);
-        hipLaunchKernelGGL(kv_write_kernel, dim3((unsigned)nbc), dim3(256), 0, h->stream, a, (const uint32_t *)ent_cnt, (const uint8_t *)cflags,
-                           (const unsigned long long *)sums_p, (const unsigned long long *)sums_e, (int64_t *)d_pair_read, (uint32_t *)d_pair_var,
-                           (uint8_t *)d_pair_flags, pair_cap, (uint64_t *)d_entry_pos, (uint64_t *)d_entry_pair, entry_cap);
-        p3.stop();
-        HIPCHK(h, hipGetLastError());
-    }
-    if (n_pairs > pair_cap || n_entries > entry_cap)
-        return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu pairs and %llu entries, the buffers hold %llu and %llu", (unsigned long long)n_pairs,
-                    (unsigned long long)n_entries, (unsigned long long)pair_cap, (unsigned long long)entry_cap);
-    return KDF_OK;
-}
-
-int kdf_variant_windows(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
-                        int64_t n_reads, const int64_t *ref_start, const uint32_t *cigar, uint64_t n_cigar, const int64_t *cigar_offsets,
-                        const uint8_t *qual, uint64_t n_qual, const int64_t *qual_offsets, uint32_t min_baseq, const int64_t *var_pos,
-                        const uint32_t *var_span, const uint32_t *var_ref_len, uint64_t n_var, const uint8_t *alt, uint64_t n_alt,
-                        const int64_t *alt_offsets, int64_t *pair_read, uint32_t *pair_var, uint8_t *pair_flags, uint64_t pair_cap,
-                        uint64_t *entry_pos, uint64_t *entry_pair, uint64_t entry_cap, uint64_t *n_pairs_out, uint64_t *n_entries_out) {
-    static const char *const fn = "kdf_variant_windows";
-    if (!h || !n_pairs_out || !n_entries_out) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
-    *n_pairs_out = *n_entries_out = 0;
-    int rc = check_read_offsets(EngSink{h}, fn, read_offsets, n_reads);                  // (before any device work)
-    if (rc) return rc;
-    if (n_reads > 0) {
-        if (!ref_start) return fail(h, KDF_ERR_INVALID, "%s: ref_start is NULL", fn);
-        if ((rc = check_offsets0(h, fn, "cigar_offsets", cigar_offsets, (uint64_t)n_reads, n_cigar))) return rc;
-        if (qual && (rc = check_offsets0(h, fn, "qual_offsets", qual_offsets, (uint64_t)n_reads, n_qual))) return rc;
-    }
-    if (n_var > 0) {
-        if (!var_pos || !var_span || !var_ref_len) return fail(h, KDF_ERR_INVALID, "%s: NULL variant array", fn);
-        for (uint64_t v = 1; v < n_var; ++v)
-            if (var_pos[v] < var_pos[v - 1])
-                return fail(h, KDF_ERR_INVALID, "%s: var_pos decreases at variant %llu (%lld after %lld)", fn, (unsigned long long)v, (long long)var_pos[v], (long long)var_pos[v - 1]);
-        if ((rc = check_offsets0(h, fn, "alt_offsets", alt_offsets, n_var, n_alt))) return rc;
-    }
-    if (n_reads == 0 || n_var == 0 || n_bases == 0 || n_cigar == 0) return KDF_OK;
-    if (!packed || !invalid || !cigar || (n_alt && !alt) || (pair_cap && (!pair_read || !pair_var || !pair_flags)) || (entry_cap && (!entry_pos || !entry_pair)))
-        return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
-    HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, fn))) return rc;
-    const bool q = qual && min_baseq;
-    const void *src[10] = {ref_start, cigar, cigar_offsets, q ? qual : nullptr, q ? qual_offsets : nullptr, var_pos, var_span, var_ref_len, alt, alt_offsets};
-    const size_t bytes[10] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, q ? (size_t)n_qual : 0, q ? (size_t)(n_reads + 1) * 8 : 0,
-                              (size_t)n_var * 8, (size_t)n_var * 4, (size_t)n_var * 4, (size_t)n_alt, (size_t)(n_var + 1) * 8};
-    Arena in, out;
-    for (int i = 0; i < 10; ++i) in.add(bytes[i]);
-    const size_t obytes[5] = {(size_t)pair_cap * 8, (size_t)pair_cap * 4, (size_t)pair_cap, (size_t)entry_cap * 8, (size_t)entry_cap * 8};
-    for (int i = 0; i < 5; ++i) out.add(obytes[i]);
-    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
-    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
-    for (int i = 0; i < 10; ++i)
-        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    auto ip = [&](int i) -> const void * { return di + in.off[i]; };
-    auto op = [&](int i) -> void * { return obytes[i] ? dout + out.off[i] : nullptr; };
-    const int rcl = kdf_variant_windows_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, ip(0), ip(1), n_cigar, ip(2), q ? ip(3) : nullptr, q ? n_qual : 0,
-                                            q ? ip(4) : nullptr, min_baseq, ip(5), ip(6), ip(7), n_var, ip(8), n_alt, ip(9), op(0), op(1), op(2), pair_cap,
-                                            op(3), op(4), entry_cap, n_pairs_out, n_entries_out);
-    if (rcl && !(rcl == KDF_ERR_INVALID && (*n_pairs_out > pair_cap || *n_entries_out > entry_cap))) return rcl;
-    const uint64_t np = std::min<uint64_t>(*n_pairs_out, pair_cap), ne = std::min<uint64_t>(*n_entries_out, entry_cap);
-    if (np) {
-        HIPCHK(h, hipMemcpyAsync(pair_read, op(0), np * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pair_var, op(1), np * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pair_flags, op(2), np, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (ne) {
-        HIPCHK(h, hipMemcpyAsync(entry_pos, op(3), ne * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(entry_pair, op(4), ne * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return rcl;
-}
-
-int kdf_variant_evidence_dev(kdf_engine *h, const void *d_keys, const void *d_entry_pair, uint64_t n_entries, const void *d_pair_var,
-                             const void *d_pair_flags, uint64_t n_pairs, uint64_t n_var, void *d_pair_rows, void *d_var_rows) {
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if ((n_pairs && !d_pair_rows) || (n_var && !d_var_rows)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: NULL pointer");
-    const bool work = n_entries && n_pairs && n_var;
-    if (work && (!d_keys || !d_entry_pair || !d_pair_var || !d_pair_flags)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: NULL pointer");
-    // (variant, tag, slot) must fit 63 bits: bit 63 keeps every word apart from the set's empty word.  Refused before
-    // anything is written, and once more below when pending work has grown the table
-    if (n_var >= (1ull << 62) || log2ceil(n_var) + 1 + h->t.log2cap > 63)
-        return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu variants against a table of 2^%u slots: variant index, tag and slot index must "
-                    "fit 63 bits together", (unsigned long long)n_var, h->t.log2cap);
-    if ((n_entries + 255) / 256 >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu entries are beyond the 2^39 a call takes", (unsigned long long)n_entries);
-    HIPCHK(h, hipSetDevice(h->device));
-    if (work) {
-        { int rcf = pending_flush(h); if (rcf) return rcf; }
-        { int rc0 = materialize(h); if (rc0) return rc0; }
-        if (log2ceil(n_var) + 1 + h->t.log2cap > 63)
-            return fail(h, KDF_ERR_INVALID, "kdf_variant_evidence_dev: %llu variants against a table of 2^%u slots: variant index, tag and slot index "
-                        "must fit 63 bits together", (unsigned long long)n_var, h->t.log2cap);
-    }
-    if (n_pairs) HIPCHK(h, hipMemsetAsync(d_pair_rows, 0, (size_t)n_pairs * KV_PAIR_WORDS * 4, h->stream));
-    if (n_var) HIPCHK(h, hipMemsetAsync(d_var_rows, 0, (size_t)n_var * KV_VAR_WORDS * 8, h->stream));
-    if (!work) return KDF_OK;
-    const uint32_t log2set = log2ceil(4 * n_entries);              // two words per entry at most, load <= 0.5
-    int rc;
-    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (variant, k-mer) pairs"))) return rc;
-    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
-    EvSpan p(h->timer[T_VAR], h->prof, h->stream, 1);
-    HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
-    by_words(h, [&](auto Wc) {
-        constexpr int W = decltype(Wc)::value;
-        hipLaunchKernelGGL(kv_evidence_kernel<W>, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, h->stream, h->t, (const uint64_t *)d_keys,
-                           (const uint64_t *)d_entry_pair, n_entries, (const uint32_t *)d_pair_var, (const uint8_t *)d_pair_flags, n_pairs, n_var, set,
-                           log2set, (uint32_t *)d_pair_rows, (unsigned long long *)d_var_rows);
-        return 0;
-    });
-    hipLaunchKernelGGL(kv_rows_fix_kernel, dim3((unsigned)((n_var + 255) / 256)), dim3(256), 0, h->stream, (unsigned long long *)d_var_rows, n_var);
-    p.stop();
-    HIPCHK(h, hipGetLastError());
-    return KDF_OK;
-}
-
-int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *entry_pair, uint64_t n_entries, const uint32_t *pair_var,
-                         const uint8_t *pair_flags, uint64_t n_pairs, uint64_t n_var, uint32_t *pair_rows, uint64_t *var_rows) {
-    static const char *const fn = "kdf_variant_evidence";
-    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if ((n_pairs && (!pair_rows || !pair_var || !pair_flags)) || (n_var && !var_rows) || (n_entries && (!keys || !entry_pair)))
-        return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t bytes[4] = {(size_t)n_entries * 8 * (size_t)h->kw, (size_t)n_entries * 8, (size_t)n_pairs * 4, (size_t)n_pairs};
-    const void *src[4] = {keys, entry_pair, pair_var, pair_flags};
-    const size_t obytes[2] = {(size_t)n_pairs * KV_PAIR_WORDS * 4, (size_t)n_var * KV_VAR_WORDS * 8};
-    Arena in, out;
-    for (int i = 0; i < 4; ++i) in.add(bytes[i]);
-    for (int i = 0; i < 2; ++i) out.add(obytes[i]);
-    int rc;
-    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
-    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
-    for (int i = 0; i < 4; ++i)
-        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    if ((rc = kdf_variant_evidence_dev(h, di + in.off[0], di + in.off[1], n_entries, di + in.off[2], di + in.off[3], n_pairs, n_var,
-                                       obytes[0] ? dout + out.off[0] : nullptr, obytes[1] ? dout + out.off[1] : nullptr))) return rc;
-    if (obytes[0]) HIPCHK(h, hipMemcpyAsync(pair_rows, dout + out.off[0], obytes[0], hipMemcpyDeviceToHost, h->stream));
-    if (obytes[1]) HIPCHK(h, hipMemcpyAsync(var_rows, dout + out.off[1], obytes[1], hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
@@ -4057,664 +3161,4 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     return KDF_OK;
 }
 
-// ===========================================================================
-// read spool (kdf.h "read spool", kdf_spool.h): a sample's packed stream kept resident and replayed
-// ===========================================================================
-
-#define KS_STAGES 6
-enum { KT_APPEND = 0, KT_OFFSETS, KT_COUNT };          // a spool's timers (option "profile"): stats "append_*", "offsets_*"
-static const char *const KS_TIMER_NAME[KT_COUNT] = {"append", "offsets"};
-struct KsSegment {
-    uint64_t *packed = nullptr, *mask = nullptr;     // 2 cap_tiles + 4 / cap_tiles + 2 words: HBM, or pinned host memory
-    uint64_t cap_tiles = 0, tiles = 0;               // room / used; the segment is a stream of tiles x 64 positions
-    uint64_t bytes = 0;
-    bool host = false;
-    // a spool that keeps reads: offs[0 .. n_reads] in SEGMENT coordinates, in the segment's tier (room for offs_cap entries)
-    int64_t *offs = nullptr;
-    uint64_t offs_cap = 0, n_reads = 0, first_read = 0;
-};
-enum { KS_MODE_OPEN = 0, KS_MODE_STREAM = 1, KS_MODE_READS = 2 };   // decided by the first append since create / clear
-struct kdf_spool {
-    int device = 0;
-    uint64_t hbm_budget = 0, host_budget = 0;
-    uint64_t opt_segment_positions = 1ull << 30;
-    std::vector<KsSegment> segs;
-    uint64_t hbm_bytes = 0, host_bytes = 0, batches = 0, bases = 0, replays = 0;
-    int mode = KS_MODE_OPEN;
-    uint64_t reads = 0, offset_bytes = 0;
-    uint64_t opt_offsets_chunk = 1ull << 16;         // entries: the unit an offsets array is sized and grown in
-    bool overflowed = false;
-    hipStream_t stream = nullptr;                    // kdf_spool_append (host sources) runs here
-    hipEvent_t last = nullptr; bool have_last = false;   // behind the latest append, whatever stream it ran on
-    DevBuf buf[KS_STAGES + 4];                       // every grow-only device buffer (released together), through the views below
-    // 0/1 a host source's words, 2/3 a host-tier batch before its copy out, 4 a host source's offsets, 5 a host-tier
-    // batch's offsets before their copy out; the last user is an append, and every append is behind `last`
-    DevBuf *const stage = buf;
-    // kdf_spool_append_uploaded_reads: the caller's offsets pass through pinned memory, so the copy is truly asynchronous
-    // and the caller's array is its own again at once; pin_done is behind the copy that read it last
-    // (one buffer per upload slot: the host never waits for the append it queued last)
-    int64_t *pin_offs[2] = {nullptr, nullptr}; size_t pin_entries[2] = {0, 0};
-    hipEvent_t pin_done[2] = {nullptr, nullptr}; bool have_pin_done[2] = {false, false};
-    // replays of the per-read consumers: one host-tier segment's packed, mask and offsets words on the device (not
-    // charged to the budget); rep_done is behind the consumer that read them last, whatever engine it ran on
-    DevBuf *const rep = buf + KS_STAGES;
-    hipEvent_t rep_done = nullptr; bool have_rep_done = false;
-    // kdf_spool_select_reads: block sums (device) and the total (pinned)
-    DevBuf *const sel_buf = buf + KS_STAGES + 3;
-    unsigned long long *sel_total = nullptr;
-    bool prof = false;
-    EvTimer timer[KT_COUNT];                         // never reset: turning "profile" off keeps what was recorded
-    std::string err;
-};
-
-static int ks_fail(kdf_spool *sp, int code, const char *fmt, ...) {
-    char buf[768];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    if (sp) sp->err = buf; else g_err = buf;
-    return code;
-}
-#define KSCHK(sp, call)                                                                 \
-    do {                                                                                \
-        hipError_t e_ = (call);                                                         \
-        if (e_ != hipSuccess)                                                           \
-            return ks_fail(sp, e_ == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, \
-                           "%s failed: %s", #call, hipGetErrorString(e_));              \
-    } while (0)
-
-extern "C++" {                                      // (templates: this section lies inside the extern "C" block)
-struct KsSink {                                      // where the message of a refusal goes: this spool's error string
-    kdf_spool *sp;
-    template <typename... A> int operator()(int code, const char *fmt, A... a) const { return ks_fail(sp, code, fmt, a...); }
-};
-
-// Room for `bytes` in one of the spool's buffers (dev_reserve): `want` bytes are allocated, quiesce() waits for the old
-// buffer's last reader (a failed wait is a KDF_ERR_HIP).  fmt words a failed allocation: (%zu bytes wanted, %s HIP's text).
-template <typename Q>
-static int ks_reserve(kdf_spool *sp, DevBuf &b, size_t bytes, size_t want, Q &&quiesce, const char *fmt) {
-    hipError_t qe = hipSuccess;
-    const hipError_t e = dev_reserve(b, bytes, want, [&] { return qe = quiesce(); });
-    if (qe != hipSuccess) return ks_fail(sp, KDF_ERR_HIP, "read spool: waiting for a buffer's last reader failed: %s", hipGetErrorString(qe));
-    return e == hipSuccess ? KDF_OK : ks_fail(sp, KDF_ERR_NOMEM, fmt, want, hipGetErrorString(e));
-}
-}  // extern "C++"
-// staging: the buffer's last user is an append, and every append is behind sp->last
-static int ks_stage_reserve(kdf_spool *sp, int i, size_t bytes) {
-    return ks_reserve(sp, sp->stage[i], bytes, slack_8th(bytes), [&] { return sp->have_last ? hipEventSynchronize(sp->last) : hipSuccess; },
-                      "read spool: %zu bytes of staging do not fit the device (%s)");
-}
-
-static void ks_free_all(kdf_spool *sp) {
-    (void)hipSetDevice(sp->device);
-    (void)hipDeviceSynchronize();                    // replays read the segments on their engines' streams
-    for (EvTimer &t : sp->timer) t.collect();
-    for (auto &s : sp->segs) {
-        if (s.host) { if (s.packed) (void)hipHostFree(s.packed); if (s.mask) (void)hipHostFree(s.mask); if (s.offs) (void)hipHostFree(s.offs); }
-        else { if (s.packed) (void)hipFree(s.packed); if (s.mask) (void)hipFree(s.mask); if (s.offs) (void)hipFree(s.offs); }
-    }
-    sp->segs.clear();
-    for (DevBuf &b : sp->buf) b.release();
-    for (int i = 0; i < 2; ++i) {
-        if (sp->pin_offs[i]) (void)hipHostFree(sp->pin_offs[i]);
-        sp->pin_offs[i] = nullptr; sp->pin_entries[i] = 0; sp->have_pin_done[i] = false;
-    }
-    sp->hbm_bytes = sp->host_bytes = sp->batches = sp->bases = sp->reads = sp->offset_bytes = 0;
-    sp->mode = KS_MODE_OPEN;
-    sp->overflowed = false; sp->have_last = false; sp->have_rep_done = false;
-}
-
-// The segment and tile at which a batch of n_tiles goes: the last segment while it has room, a new one otherwise (HBM
-// within its budget, then pinned host memory within its, then KDF_ERR_NOMEM and the spool is marked overflowed).
-// entries of an offsets array that must hold `need`: a new one (have == 0) is sized for the whole segment from the read
-// density of the batch that opens it (at most one read per 32 positions is assumed), a grown one by at least an eighth;
-// both in units of option "offsets_chunk"
-static uint64_t ks_offsets_want(const kdf_spool *sp, uint64_t cap_tiles, uint64_t have, uint64_t need, uint64_t n_bases, uint64_t n_reads) {
-    uint64_t want;
-    if (!have) {
-        const uint64_t cap_pos = cap_tiles * KDF_TILE;
-        const double est = (double)cap_pos * (double)(n_reads + 1) / (double)std::max<uint64_t>(n_bases, 1) * 1.125;
-        want = std::max<uint64_t>(need, (uint64_t)std::min<double>(est, (double)(cap_pos / 32)));
-    } else want = std::max<uint64_t>(need, have + have / 8);
-    const uint64_t chunk = sp->opt_offsets_chunk;
-    return (want + chunk - 1) / chunk * chunk;
-}
-
-// keep_reads / keep_bases: the batch brings keep_reads > 0 reads, and a NEW segment must fit its tier's budget together with
-// its first offsets array (so that array's allocation does not overflow a spool whose other tier has room)
-static int spool_place(kdf_spool *sp, uint64_t n_tiles, KsSegment **seg_out, bool *fresh = nullptr, uint64_t keep_reads = 0, uint64_t keep_bases = 0) {
-    if (fresh) *fresh = false;
-    if (!sp->segs.empty() && sp->segs.back().tiles + n_tiles <= sp->segs.back().cap_tiles) { *seg_out = &sp->segs.back(); return KDF_OK; }
-    KsSegment s;
-    s.first_read = sp->reads;
-    s.cap_tiles = std::max<uint64_t>(sp->opt_segment_positions / KDF_TILE, n_tiles);
-    const uint64_t pb = (2 * s.cap_tiles + 4) * 8, mb = (s.cap_tiles + 2) * 8;
-    s.bytes = pb + mb;
-    const uint64_t ob = keep_reads ? ks_offsets_want(sp, s.cap_tiles, 0, keep_reads + 1, keep_bases, keep_reads) * 8 : 0;
-    if (sp->hbm_bytes + s.bytes + ob <= sp->hbm_budget) {
-        hipError_t e = hipMalloc((void **)&s.packed, pb);
-        if (e == hipSuccess && (e = hipMalloc((void **)&s.mask, mb)) != hipSuccess) { (void)hipFree(s.packed); s.packed = nullptr; }
-        if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }      // an expected event: the next tier takes it
-    }
-    if (!s.packed && sp->host_bytes + s.bytes + ob <= sp->host_budget) {
-        hipError_t e = hipHostMalloc((void **)&s.packed, pb, hipHostMallocDefault);
-        if (e == hipSuccess && (e = hipHostMalloc((void **)&s.mask, mb, hipHostMallocDefault)) != hipSuccess) { (void)hipHostFree(s.packed); s.packed = nullptr; }
-        if (e != hipSuccess) { (void)hipGetLastError(); s.packed = s.mask = nullptr; }
-        else s.host = true;
-    }
-    if (!s.packed) {
-        sp->overflowed = true;
-        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: a segment of %llu bytes (with its read offsets, if it keeps any) fits neither budget (HBM %llu of %llu bytes used, host %llu of %llu): "
-                       "the spool is overflowed -- stream the source again, or kdf_spool_clear",
-                       (unsigned long long)(s.bytes + ob), (unsigned long long)sp->hbm_bytes, (unsigned long long)sp->hbm_budget,
-                       (unsigned long long)sp->host_bytes, (unsigned long long)sp->host_budget);
-    }
-    (s.host ? sp->host_bytes : sp->hbm_bytes) += s.bytes;
-    sp->segs.push_back(s);
-    *seg_out = &sp->segs.back();
-    if (fresh) *fresh = true;
-    return KDF_OK;
-}
-
-// Room for `need` entries in the segment's offsets array, in the segment's tier and within its budget; the entries
-// stored so far move along.  A new array is sized for the whole segment from the read density of the batch that opens it
-// (at most one read per 32 positions is assumed; more than that grows), in units of option "offsets_chunk", so that
-// growing -- which waits for the device: replays may be reading the old array -- stays rare.
-static int ks_offsets_reserve(kdf_spool *sp, KsSegment *seg, uint64_t need, uint64_t n_bases, uint64_t n_reads) {
-    if (seg->offs_cap >= need) return KDF_OK;
-    const uint64_t want = ks_offsets_want(sp, seg->cap_tiles, seg->offs_cap, need, n_bases, n_reads);
-    const uint64_t add = (want - seg->offs_cap) * 8;
-    uint64_t &used = seg->host ? sp->host_bytes : sp->hbm_bytes;
-    const uint64_t budget = seg->host ? sp->host_budget : sp->hbm_budget;
-    int64_t *fresh = nullptr;
-    hipError_t e = hipErrorOutOfMemory;
-    if (used + add <= budget) {
-        e = seg->host ? hipHostMalloc((void **)&fresh, want * 8, hipHostMallocDefault) : hipMalloc((void **)&fresh, want * 8);
-        if (e != hipSuccess) { (void)hipGetLastError(); fresh = nullptr; }
-    }
-    if (!fresh) {
-        sp->overflowed = true;
-        return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %llu bytes of read offsets do not fit the %s budget (%llu of %llu bytes used): the spool is "
-                       "overflowed -- stream the source again, or kdf_spool_clear", (unsigned long long)add, seg->host ? "host" : "HBM",
-                       (unsigned long long)used, (unsigned long long)budget);
-    }
-    if (seg->offs) {
-        e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipMemcpy(fresh, seg->offs, (seg->n_reads + 1) * 8, seg->host ? hipMemcpyHostToHost : hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            if (seg->host) (void)hipHostFree(fresh); else (void)hipFree(fresh);
-            return ks_fail(sp, KDF_ERR_HIP, "read spool: moving a segment's read offsets failed: %s", hipGetErrorString(e));
-        }
-        if (seg->host) (void)hipHostFree(seg->offs); else (void)hipFree(seg->offs);
-    }
-    seg->offs = fresh; seg->offs_cap = want;
-    used += add; seg->bytes += add; sp->offset_bytes += add;
-    return KDF_OK;
-}
-
-// n_reads >= 0, offsets[0] == 0, no decrease, offsets[n_reads] == n_bases: what kdf_pack_reads and kdf_reader_next hand out
-static int ks_check_offsets(kdf_spool *sp, const char *fn, const int64_t *offs, int64_t n_reads, uint64_t n_bases) {
-    if (n_reads == 0 && n_bases) return ks_fail(sp, KDF_ERR_INVALID, "%s: %llu positions in no read (read_offsets[n_reads] must be n_bases)", fn, (unsigned long long)n_bases);
-    if (n_reads > 0 && n_bases == 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: %lld reads in a batch of no positions (a batch without positions has no place in a segment)", fn, (long long)n_reads);
-    if (n_reads > 0 && offs && offs[0] != 0) return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[0] = %lld, not 0", fn, (long long)offs[0]);
-    const int rc = check_read_offsets(KsSink{sp}, fn, offs, n_reads);                  // negative n_reads, NULL, a decrease
-    if (rc || n_reads == 0) return rc;
-    if ((uint64_t)offs[n_reads] != n_bases)
-        return ks_fail(sp, KDF_ERR_INVALID, "%s: read_offsets[n_reads] = %lld, not n_bases = %llu (the last read must end where the batch ends)", fn,
-                       (long long)offs[n_reads], (unsigned long long)n_bases);
-    return KDF_OK;
-}
-
-// keep: this append brings read offsets.  The first append since create / clear decides what the spool keeps.
-static int ks_check_append(kdf_spool *sp, const void *p, const void *m, uint64_t n_bases, const char *fn, bool keep = false) {
-    if (sp->mode != KS_MODE_OPEN && (sp->mode == KS_MODE_READS) != keep)
-        return ks_fail(sp, KDF_ERR_STATE, keep ? "%s: the spool keeps no read offsets (its first append brought none): kdf_spool_append* or kdf_spool_clear"
-                                               : "%s: the spool keeps read offsets: kdf_spool_append*_reads or kdf_spool_clear", fn);
-    if (n_bases > (1ull << 31)) return ks_fail(sp, KDF_ERR_INVALID, "%s: a batch of %llu positions (at most 2^31)", fn, (unsigned long long)n_bases);
-    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed (kdf_spool_clear)", fn);
-    if (n_bases && (!p || !m)) return ks_fail(sp, KDF_ERR_INVALID, "%s: NULL stream", fn);
-    return KDF_OK;
-}
-
-// one batch from DEVICE buffers, on stream s (behind every earlier append).  keep: with its n_reads + 1 read offsets,
-// either on the device (d_offs) or in host memory that stays valid until the copy queued here has run (h_offs).
-static int spool_append_dev(kdf_spool *sp, hipStream_t s, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases,
-                            bool keep = false, const int64_t *d_offs = nullptr, const int64_t *h_offs = nullptr, uint64_t n_reads = 0) {
-    const uint64_t n_tiles = n_bases / KDF_TILE + 1;
-    KsSegment *seg = nullptr;
-    bool fresh = false;
-    int rc = spool_place(sp, n_tiles, &seg, &fresh, keep ? n_reads : 0, n_bases);
-    if (rc) return rc;
-    if (keep && (rc = ks_offsets_reserve(sp, seg, seg->n_reads + n_reads + 1, n_bases, n_reads))) {
-        if (fresh) {                                               // nothing of this batch stays behind
-            if (seg->host) { (void)hipHostFree(seg->packed); (void)hipHostFree(seg->mask); sp->host_bytes -= seg->bytes; }
-            else { (void)hipFree(seg->packed); (void)hipFree(seg->mask); sp->hbm_bytes -= seg->bytes; }
-            sp->segs.pop_back();
-        }
-        return rc;
-    }
-    uint64_t *dp = seg->packed + 2 * seg->tiles, *dm = seg->mask + seg->tiles;
-    int64_t *doffs = keep ? seg->offs + seg->n_reads : nullptr;
-    if (seg->host) {
-        if ((rc = ks_stage_reserve(sp, 2, (2 * n_tiles + 4) * 8)) || (rc = ks_stage_reserve(sp, 3, (n_tiles + 2) * 8)) ||
-            (keep && (rc = ks_stage_reserve(sp, 5, (n_reads + 1) * 8)))) { sp->overflowed = true; return rc; }
-        dp = (uint64_t *)sp->stage[2].p; dm = (uint64_t *)sp->stage[3].p;
-        if (keep) doffs = (int64_t *)sp->stage[5].p;
-    }
-    if (keep && h_offs && (rc = ks_stage_reserve(sp, 4, (n_reads + 1) * 8))) return rc;
-    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(s, sp->last, 0));
-    if (keep && h_offs) {
-        KSCHK(sp, hipMemcpyAsync(sp->stage[4].p, h_offs, (n_reads + 1) * 8, hipMemcpyHostToDevice, s));
-        d_offs = (const int64_t *)sp->stage[4].p;
-    }
-    const unsigned blocks = (unsigned)std::min<uint64_t>((n_tiles + 2 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
-    EvSpan span(sp->timer[KT_APPEND], sp->prof, s);
-    hipLaunchKernelGGL(ks_append_kernel, dim3(blocks), dim3(KS_THREADS), 0, s, dp, dm, d_packed, d_invalid, n_bases, n_tiles,
-                       (int)(((uintptr_t)d_packed & 15) == 0));
-    KSCHK(sp, hipGetLastError());
-    span.stop();
-    if (keep) {
-        // entries n_reads(seg) .. n_reads(seg) + n_reads: the first overwrites the last entry of the batch before (kdf.h: the gap)
-        const unsigned oblocks = (unsigned)std::min<uint64_t>((n_reads + 1 + KS_THREADS - 1) / KS_THREADS, KS_MAX_BLOCKS);
-        EvSpan ospan(sp->timer[KT_OFFSETS], sp->prof, s);
-        hipLaunchKernelGGL(ks_offsets_kernel, dim3(oblocks), dim3(KS_THREADS), 0, s, doffs, d_offs, n_reads + 1, (int64_t)(seg->tiles * KDF_TILE));
-        KSCHK(sp, hipGetLastError());
-        ospan.stop();
-    }
-    if (seg->host) {
-        KSCHK(sp, hipMemcpyAsync(seg->packed + 2 * seg->tiles, dp, (2 * n_tiles + 4) * 8, hipMemcpyDeviceToHost, s));
-        KSCHK(sp, hipMemcpyAsync(seg->mask + seg->tiles, dm, (n_tiles + 2) * 8, hipMemcpyDeviceToHost, s));
-        if (keep) KSCHK(sp, hipMemcpyAsync(seg->offs + seg->n_reads, doffs, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
-    }
-    KSCHK(sp, hipEventRecord(sp->last, s));
-    sp->have_last = true;
-    seg->tiles += n_tiles;
-    ++sp->batches; sp->bases += n_bases;
-    if (keep) { seg->n_reads += n_reads; sp->reads += n_reads; }
-    sp->mode = keep ? KS_MODE_READS : KS_MODE_STREAM;
-    return KDF_OK;
-}
-
-int kdf_spool_create(int device, uint64_t hbm_budget_bytes, uint64_t host_budget_bytes, kdf_spool **out) {
-    if (!out) return ks_fail(nullptr, KDF_ERR_INVALID, "kdf_spool_create: out is NULL");
-    *out = nullptr;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) return ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: no HIP device available (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= ndev) return ks_fail(nullptr, KDF_ERR_INVALID, "kdf_spool_create: device %d of %d", device, ndev);
-    if ((e = hipSetDevice(device)) != hipSuccess) return ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: %s", hipGetErrorString(e));
-    kdf_spool *sp = new kdf_spool();
-    sp->device = device; sp->hbm_budget = hbm_budget_bytes; sp->host_budget = host_budget_bytes;
-    if ((e = hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sp->last, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sp->pin_done[0], hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sp->pin_done[1], hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&sp->rep_done, hipEventDisableTiming)) != hipSuccess) {
-        ks_fail(nullptr, KDF_ERR_HIP, "kdf_spool_create: %s", hipGetErrorString(e));
-        kdf_spool_destroy(sp);
-        return KDF_ERR_HIP;
-    }
-    *out = sp;
-    return KDF_OK;
-}
-
-void kdf_spool_destroy(kdf_spool *sp) {
-    if (!sp) return;
-    ks_free_all(sp);
-    if (sp->last) (void)hipEventDestroy(sp->last);
-    for (int i = 0; i < 2; ++i) if (sp->pin_done[i]) (void)hipEventDestroy(sp->pin_done[i]);
-    if (sp->rep_done) (void)hipEventDestroy(sp->rep_done);
-    if (sp->sel_total) (void)hipHostFree(sp->sel_total);
-    if (sp->stream) (void)hipStreamDestroy(sp->stream);
-    delete sp;
-}
-
-const char *kdf_spool_error(const kdf_spool *sp) { return sp ? sp->err.c_str() : g_err.c_str(); }
-
-int kdf_spool_clear(kdf_spool *sp) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    ks_free_all(sp);
-    return KDF_OK;
-}
-
-int kdf_spool_set_option(kdf_spool *sp, const char *name, int64_t value) {
-    if (!sp || !name) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: NULL argument");
-    const std::string n(name);
-    if (n == "segment_positions") {
-        if (value < (1ll << 12) || value > (1ll << 31)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: segment_positions must be 2^12 .. 2^31");
-        sp->opt_segment_positions = (uint64_t)value;               // (segments already allocated keep their size)
-    } else if (n == "offsets_chunk") {
-        if (value < 1 || value > (1ll << 28)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: offsets_chunk must be 1 .. 2^28 entries");
-        sp->opt_offsets_chunk = (uint64_t)value;                   // (arrays already allocated keep their size)
-    } else if (n == "profile") {
-        if (!value) { (void)hipSetDevice(sp->device); for (EvTimer &t : sp->timer) t.collect(); }
-        sp->prof = value != 0;
-    } else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_set_option: unknown option %s", name);
-    return KDF_OK;
-}
-
-int kdf_spool_get_stat(kdf_spool *sp, const char *name, int64_t *value) {
-    if (!sp || !name || !value) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: NULL argument");
-    const std::string n(name);
-    bool us = false;
-    if (EvTimer *t = timer_of_stat(sp->timer, KS_TIMER_NAME, KT_COUNT, n, &us)) {
-        (void)hipSetDevice(sp->device);
-        *value = us ? t->us() : (t->collect(), (int64_t)t->passes);
-    }
-    else if (n == "segments") *value = (int64_t)sp->segs.size();
-    else if (n == "batches") *value = (int64_t)sp->batches;
-    else if (n == "positions") { uint64_t t = 0; for (auto &s : sp->segs) t += s.tiles; *value = (int64_t)(t * KDF_TILE); }
-    else if (n == "bases") *value = (int64_t)sp->bases;
-    else if (n == "hbm_bytes") *value = (int64_t)sp->hbm_bytes;
-    else if (n == "host_bytes") *value = (int64_t)sp->host_bytes;
-    else if (n == "overflowed") *value = sp->overflowed ? 1 : 0;
-    else if (n == "replays") *value = (int64_t)sp->replays;
-    else if (n == "segment_positions") *value = (int64_t)sp->opt_segment_positions;
-    else if (n == "offsets_chunk") *value = (int64_t)sp->opt_offsets_chunk;
-    else if (n == "reads") *value = (int64_t)sp->reads;
-    else if (n == "keeps_reads") *value = sp->mode == KS_MODE_READS ? 1 : 0;
-    else if (n == "offset_bytes") *value = (int64_t)sp->offset_bytes;
-    else return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_get_stat: unknown stat %s", name);
-    return KDF_OK;
-}
-
-int kdf_spool_append_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    int rc = ks_check_append(sp, d_packed, d_invalid, n_bases, "kdf_spool_append_dev");
-    if (rc || n_bases == 0) return rc;
-    KSCHK(sp, hipSetDevice(sp->device));
-    return spool_append_dev(sp, (hipStream_t)hip_stream, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases);
-}
-
-int kdf_spool_append(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    int rc = ks_check_append(sp, packed, invalid, n_bases, "kdf_spool_append");
-    if (rc || n_bases == 0) return rc;
-    KSCHK(sp, hipSetDevice(sp->device));
-    const uint64_t src_tiles = (n_bases + 63) / 64;                 // (the words the kernel loads, no more)
-    if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
-    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));   // (the staging's last reader)
-    KSCHK(sp, hipMemcpyAsync(sp->stage[0].p, packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[1].p, invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0].p, (const uint64_t *)sp->stage[1].p, n_bases);
-    KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
-    return rc;
-}
-
-int kdf_spool_append_uploaded(kdf_spool *sp, kdf_engine *h, int slot) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: NULL engine");
-    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded: the spool is on device %d, the engine on %d", sp->device, h->device);
-    StreamSrc src;                                                 // (the slot keeps its batch; the host does not wait for the copy)
-    int rc = src_slot(KsSink{sp}, "kdf_spool_append_uploaded", h, slot, false, false, src, [&](const StreamSrc &b) {
-        return ks_check_append(sp, b.packed, b.invalid, b.n_bases, "kdf_spool_append_uploaded");
-    });
-    if (rc || !src.n_bases) return rc;
-    rc = spool_append_dev(sp, h->stream, src.packed, src.invalid, src.n_bases);
-    src_release(h, src);                                           // (the slot's next upload waits for this reader as for a count)
-    return rc;
-}
-
-// ---- appends that bring their read offsets ----
-
-int kdf_spool_append_reads_dev(kdf_spool *sp, void *hip_stream, const void *d_packed, const void *d_invalid, uint64_t n_bases,
-                               const void *d_read_offsets, int64_t n_reads) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    int rc = ks_check_append(sp, d_packed, d_invalid, n_bases, "kdf_spool_append_reads_dev", true);
-    if (rc) return rc;
-    if (n_reads < 0) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_reads_dev: n_reads = %lld is negative", (long long)n_reads);
-    if (n_reads == 0) return n_bases ? ks_check_offsets(sp, "kdf_spool_append_reads_dev", nullptr, 0, n_bases) : KDF_OK;
-    if (n_bases == 0) return ks_check_offsets(sp, "kdf_spool_append_reads_dev", nullptr, n_reads, 0);
-    if (!d_read_offsets) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_reads_dev: read_offsets is NULL");
-    KSCHK(sp, hipSetDevice(sp->device));
-    return spool_append_dev(sp, (hipStream_t)hip_stream, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_bases, true,
-                            (const int64_t *)d_read_offsets, nullptr, (uint64_t)n_reads);
-}
-
-int kdf_spool_append_reads(kdf_spool *sp, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, const int64_t *read_offsets,
-                           int64_t n_reads) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    int rc = ks_check_append(sp, packed, invalid, n_bases, "kdf_spool_append_reads", true);
-    if (rc || (rc = ks_check_offsets(sp, "kdf_spool_append_reads", read_offsets, n_reads, n_bases)) || n_reads == 0) return rc;
-    KSCHK(sp, hipSetDevice(sp->device));
-    const uint64_t src_tiles = (n_bases + 63) / 64;                 // (>= 1: a batch with reads has positions)
-    if ((rc = ks_stage_reserve(sp, 0, 2 * src_tiles * 8)) || (rc = ks_stage_reserve(sp, 1, src_tiles * 8))) return rc;
-    if (sp->have_last) KSCHK(sp, hipStreamWaitEvent(sp->stream, sp->last, 0));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[0].p, packed, 2 * src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    KSCHK(sp, hipMemcpyAsync(sp->stage[1].p, invalid, src_tiles * 8, hipMemcpyHostToDevice, sp->stream));
-    rc = spool_append_dev(sp, sp->stream, (const uint64_t *)sp->stage[0].p, (const uint64_t *)sp->stage[1].p, n_bases, true, nullptr, read_offsets,
-                          (uint64_t)n_reads);
-    KSCHK(sp, hipStreamSynchronize(sp->stream));                   // the caller's arrays are its own again
-    return rc;
-}
-
-int kdf_spool_append_uploaded_reads(kdf_spool *sp, kdf_engine *h, int slot, const int64_t *read_offsets, int64_t n_reads) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: NULL engine");
-    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_append_uploaded_reads: the spool is on device %d, the engine on %d", sp->device, h->device);
-    StreamSrc src;
-    int rc = src_slot(KsSink{sp}, "kdf_spool_append_uploaded_reads", h, slot, false, false, src, [&](const StreamSrc &b) {
-        const int rcb = ks_check_append(sp, b.packed, b.invalid, b.n_bases, "kdf_spool_append_uploaded_reads", true);
-        return rcb ? rcb : ks_check_offsets(sp, "kdf_spool_append_uploaded_reads", read_offsets, n_reads, b.n_bases);
-    });
-    if (rc || n_reads == 0) return rc;
-    // through pinned memory: the copy is queued behind the engine's work and the caller's array is not read after this returns
-    const size_t entries = (size_t)n_reads + 1;
-    if (sp->have_pin_done[slot]) KSCHK(sp, hipEventSynchronize(sp->pin_done[slot]));   // (the slot's append before this one)
-    if (sp->pin_entries[slot] < entries) {
-        if (sp->pin_offs[slot]) (void)hipHostFree(sp->pin_offs[slot]);
-        sp->pin_offs[slot] = nullptr; sp->pin_entries[slot] = 0;
-        const size_t want = entries + entries / 8 + 512;
-        const hipError_t e = hipHostMalloc((void **)&sp->pin_offs[slot], want * 8, hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipGetLastError(); sp->pin_offs[slot] = nullptr; return ks_fail(sp, KDF_ERR_NOMEM, "read spool: %zu bytes of pinned staging: %s", want * 8, hipGetErrorString(e)); }
-        sp->pin_entries[slot] = want;
-    }
-    memcpy(sp->pin_offs[slot], read_offsets, entries * 8);
-    rc = spool_append_dev(sp, h->stream, src.packed, src.invalid, src.n_bases, true, nullptr, sp->pin_offs[slot], (uint64_t)n_reads);
-    if (hipEventRecord(sp->pin_done[slot], h->stream) == hipSuccess) sp->have_pin_done[slot] = true;
-    else { (void)hipGetLastError(); (void)hipStreamSynchronize(h->stream); sp->have_pin_done[slot] = false; }
-    src_release(h, src);                                           // (the slot's next upload waits for this reader as for a count)
-    return rc;
-}
-
-int kdf_spool_read_offsets(kdf_spool *sp, uint64_t seg, int64_t *out, uint64_t *first_read_out, uint64_t *n_reads_out) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_read_offsets: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
-    if (sp->mode != KS_MODE_READS) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_read_offsets: the spool keeps no read offsets (kdf_spool_append*_reads)");
-    const KsSegment &s = sp->segs[seg];
-    if (first_read_out) *first_read_out = s.first_read;
-    if (n_reads_out) *n_reads_out = s.n_reads;
-    if (!out) return KDF_OK;
-    KSCHK(sp, hipSetDevice(sp->device));
-    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
-    KSCHK(sp, hipMemcpy(out, s.offs, (s.n_reads + 1) * 8, s.host ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
-    return KDF_OK;
-}
-
-int kdf_spool_segment_dev(kdf_spool *sp, uint64_t seg, const void **d_packed, const void **d_invalid, uint64_t *n_positions,
-                          const void **d_offsets, uint64_t *first_read, uint64_t *n_reads) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_segment_dev: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
-    const KsSegment &s = sp->segs[seg];
-    if (s.host)
-        return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_segment_dev: segment %llu is in host memory, no device pointer exists (kdf_spool_read_segment "
-                       "copies it out)", (unsigned long long)seg);
-    KSCHK(sp, hipSetDevice(sp->device));
-    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));  // complete for every stream the caller may use
-    if (d_packed) *d_packed = s.packed;
-    if (d_invalid) *d_invalid = s.mask;
-    if (n_positions) *n_positions = s.tiles * KDF_TILE;
-    if (d_offsets) *d_offsets = sp->mode == KS_MODE_READS ? s.offs : nullptr;
-    if (first_read) *first_read = s.first_read;
-    if (n_reads) *n_reads = s.n_reads;
-    return KDF_OK;
-}
-
-// ---- replays of the per-read consumers ----
-
-// a replay buffer's last reader ran on some engine's stream: the whole device is drained before a free
-static int ks_rep_reserve(kdf_spool *sp, int i, size_t bytes) {
-    return ks_reserve(sp, sp->rep[i], bytes, slack_8th(bytes), [] { return hipDeviceSynchronize(); },
-                      "read spool: %zu bytes of staging for a host-tier segment do not fit the device (%s)");
-}
-
-// Every segment in order through kdf_read_hits_dev (depth false; 8 bytes a row) or kdf_read_depth_dev (48 bytes a row),
-// rows of segment s at first_read(s).
-static int spool_replay_reads(kdf_spool *sp, kdf_engine *h, const char *fn, bool depth, uint32_t low_max, void *d_rows_out) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "%s: NULL engine", fn);
-    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "%s: the spool is on device %d, the engine on %d", fn, sp->device, h->device);
-    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)", fn);
-    if (sp->mode == KS_MODE_STREAM) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool keeps no read offsets (fill it through kdf_spool_append*_reads)", fn);
-    if (sp->reads == 0) return KDF_OK;
-    if (!d_rows_out) return ks_fail(sp, KDF_ERR_INVALID, "%s: rows_out is NULL", fn);
-    KSCHK(sp, hipSetDevice(sp->device));
-    bool any_host = false;
-    for (auto &s : sp->segs) any_host |= s.host && s.n_reads;
-    if (sp->have_last) {
-        KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
-        if (any_host) KSCHK(sp, hipEventSynchronize(sp->last));    // (the copies below read host memory)
-    }
-    const size_t row_bytes = depth ? KD_ROW_WORDS * 8 : KH_ROW_WORDS * 4;
-    for (size_t i = 0; i < sp->segs.size(); ++i) {
-        const KsSegment &s = sp->segs[i];
-        if (s.n_reads == 0) continue;
-        const uint64_t n = s.tiles * KDF_TILE;
-        const void *p = s.packed, *m = s.mask, *o = s.offs;
-        if (s.host) {
-            const size_t pb = (2 * s.tiles + 4) * 8, mb = (s.tiles + 2) * 8, ob = (s.n_reads + 1) * 8;
-            int rc;
-            if ((rc = ks_rep_reserve(sp, 0, pb)) || (rc = ks_rep_reserve(sp, 1, mb)) || (rc = ks_rep_reserve(sp, 2, ob))) return rc;
-            if (sp->have_rep_done) KSCHK(sp, hipStreamWaitEvent(h->stream, sp->rep_done, 0));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[0].p, s.packed, pb, hipMemcpyHostToDevice, h->stream));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[1].p, s.mask, mb, hipMemcpyHostToDevice, h->stream));
-            KSCHK(sp, hipMemcpyAsync(sp->rep[2].p, s.offs, ob, hipMemcpyHostToDevice, h->stream));
-            p = sp->rep[0].p; m = sp->rep[1].p; o = sp->rep[2].p;
-        }
-        char *rows = (char *)d_rows_out + s.first_read * row_bytes;
-        const int rc = depth ? kdf_read_depth_dev(h, p, m, n, o, (int64_t)s.n_reads, low_max, rows)
-                             : kdf_read_hits_dev(h, p, m, n, o, (int64_t)s.n_reads, nullptr, rows);
-        if (s.host) { KSCHK(sp, hipEventRecord(sp->rep_done, h->stream)); sp->have_rep_done = true; }
-        if (rc) return ks_fail(sp, rc, "%s: segment %zu: %s", fn, i, h->err.c_str());
-    }
-    ++sp->replays;
-    return KDF_OK;
-}
-
-int kdf_spool_read_hits(kdf_spool *sp, kdf_engine *h, void *d_rows_out) {
-    return spool_replay_reads(sp, h, "kdf_spool_read_hits", false, 0, d_rows_out);
-}
-
-int kdf_spool_read_depth(kdf_spool *sp, kdf_engine *h, uint32_t low_max, void *d_rows_out) {
-    return spool_replay_reads(sp, h, "kdf_spool_read_depth", true, low_max, d_rows_out);
-}
-
-int kdf_spool_select_reads(kdf_spool *sp, const void *d_hit_rows, uint32_t min_distinct, void *d_reads_out, uint64_t cap, uint64_t *n_out) {
-    if (!sp || !n_out) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: NULL pointer");
-    *n_out = 0;
-    if (sp->mode == KS_MODE_STREAM) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_select_reads: the spool keeps no read offsets (fill it through kdf_spool_append*_reads)");
-    const uint64_t n_rows = sp->reads;
-    if (n_rows == 0) return KDF_OK;
-    if (!d_hit_rows || (cap && !d_reads_out)) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: NULL pointer");
-    const uint64_t n_blocks = (n_rows + KS_SELECT_ROWS - 1) / KS_SELECT_ROWS;
-    if (n_blocks >= (1ull << 24))                                  // (a grid of 256-thread blocks stays below 2^32 threads)
-        return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: %llu rows are beyond the 2^34 a call takes", (unsigned long long)n_rows);
-    KSCHK(sp, hipSetDevice(sp->device));
-    if (!sp->sel_total) KSCHK(sp, hipHostMalloc((void **)&sp->sel_total, 8, hipHostMallocDefault));
-    // (nothing to wait for before a free: every earlier use ended in a synchronise)
-    if (const int rc = ks_reserve(sp, *sp->sel_buf, (n_blocks + 1) * 8, (n_blocks + 1) * 8 + n_blocks + 4096, [] { return hipSuccess; },
-                                  "kdf_spool_select_reads: %zu bytes of block sums: %s")) return rc;
-    unsigned long long *sums = (unsigned long long *)sp->sel_buf->p;
-    const int rows16 = (int)(((uintptr_t)d_hit_rows & 15) == 0);
-    hipLaunchKernelGGL(ks_select_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, sp->stream, (const uint64_t *)d_hit_rows, n_rows, min_distinct, rows16, sums);
-    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, sp->stream, sums, n_blocks);
-    if (cap)
-        hipLaunchKernelGGL(ks_select_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, sp->stream, (const uint64_t *)d_hit_rows, n_rows, min_distinct,
-                           rows16, (const unsigned long long *)sums, (uint64_t *)d_reads_out, cap);
-    KSCHK(sp, hipGetLastError());
-    KSCHK(sp, hipMemcpyAsync(sp->sel_total, sums + n_blocks, 8, hipMemcpyDeviceToHost, sp->stream));
-    KSCHK(sp, hipStreamSynchronize(sp->stream));
-    *n_out = *sp->sel_total;
-    if (*n_out > cap)
-        return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_select_reads: %llu reads are selected, the buffer holds %llu", (unsigned long long)*n_out, (unsigned long long)cap);
-    return KDF_OK;
-}
-
-int kdf_spool_read_segment(kdf_spool *sp, uint64_t seg, uint64_t *packed_out, uint64_t *invalid_out, uint64_t *n_positions_out) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (seg >= sp->segs.size()) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_read_segment: segment %llu of %zu", (unsigned long long)seg, sp->segs.size());
-    const KsSegment &s = sp->segs[seg];
-    if (n_positions_out) *n_positions_out = s.tiles * KDF_TILE;
-    if (!packed_out && !invalid_out) return KDF_OK;
-    KSCHK(sp, hipSetDevice(sp->device));
-    if (sp->have_last) KSCHK(sp, hipEventSynchronize(sp->last));
-    const hipMemcpyKind kind = s.host ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
-    if (packed_out) KSCHK(sp, hipMemcpy(packed_out, s.packed, (2 * s.tiles + 4) * 8, kind));
-    if (invalid_out) KSCHK(sp, hipMemcpy(invalid_out, s.mask, (s.tiles + 2) * 8, kind));
-    return KDF_OK;
-}
-
-// every segment in order into one stream entry point of the engine: mode 0 count, 1 count --if, 2 prefilter tally
-// (kdf_spool_replay), 3 sketch (kdf_spool_sketch)
-static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode);
-
-int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: NULL engine");
-    if (mode < 0 || mode > 2) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_replay: mode %d (0 count, 1 count --if, 2 prefilter tally)", mode);
-    return spool_walk(sp, h, mode);
-}
-
-int kdf_spool_sketch(kdf_spool *sp, kdf_engine *h) {
-    if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
-    if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_sketch: NULL engine");
-    if (!h->sk_on) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_sketch: no sketch is on (kdf_sketch_begin)");
-    return spool_walk(sp, h, 3);
-}
-
 }  // extern "C"
-
-static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode) {
-    const char *fn = mode == 3 ? "kdf_spool_sketch" : "kdf_spool_replay";
-    if (h->device != sp->device) return ks_fail(sp, KDF_ERR_INVALID, "%s: the spool is on device %d, the engine on %d", fn, sp->device, h->device);
-    if (sp->overflowed) return ks_fail(sp, KDF_ERR_STATE, "%s: the spool is overflowed: it does not hold the whole stream (kdf_spool_clear)", fn);
-    const size_t ns = sp->segs.size();
-    size_t next_host = ns;                                         // the host-tier segment whose upload comes next
-    for (size_t i = 0; i < ns; ++i) if (sp->segs[i].host) { next_host = i; break; }
-    if (next_host < ns && (h->up_valid[0] || h->up_valid[1]))
-        return ks_fail(sp, KDF_ERR_STATE, "%s: host-tier segments go through the engine's upload slots, and slot %d holds a batch "
-                       "that was not counted", fn, h->up_valid[0] ? 0 : 1);
-    KSCHK(sp, hipSetDevice(sp->device));
-    if (sp->have_last) {
-        KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
-        if (next_host < ns) KSCHK(sp, hipEventSynchronize(sp->last));   // (the upload reads host memory on the engine's copy stream)
-    }
-    auto pass = [&](size_t i, int rc) {
-        if (!rc) return KDF_OK;
-        h->up_valid[0] = h->up_valid[1] = false;                   // (both were free on entry: what they hold is the spool's)
-        return ks_fail(sp, rc, "%s: segment %zu: %s", fn, i, h->err.c_str());
-    };
-    auto upload = [&](size_t i, int slot) {
-        const KsSegment &s = sp->segs[i];
-        return kdf_upload_reads_async(h, slot, s.packed, s.mask, s.tiles * KDF_TILE);
-    };
-    int slot = 0, rc;
-    if (next_host < ns && (rc = upload(next_host, slot))) return pass(next_host, rc);
-    for (size_t i = 0; i < ns; ++i) {
-        const KsSegment &s = sp->segs[i];
-        const uint64_t n = s.tiles * KDF_TILE;
-        if (!s.host) {
-            rc = mode == 0 ? kdf_count_reads_dev(h, s.packed, s.mask, n) : mode == 1 ? kdf_count_reads_filtered_dev(h, s.packed, s.mask, n)
-                 : mode == 2 ? kdf_prefilter_add_reads_dev(h, s.packed, s.mask, n) : kdf_sketch_add_reads_dev(h, s.packed, s.mask, n);
-            if (rc) return pass(i, rc);
-            continue;
-        }
-        size_t j = i + 1;
-        while (j < ns && !sp->segs[j].host) ++j;
-        if (j < ns && (rc = upload(j, slot ^ 1))) return pass(j, rc);   // its copy runs under this segment's count
-        if (mode == 3) { rc = kdf_sketch_add_uploaded(h, slot); h->up_valid[slot] = false; }   // (the sketch leaves a batch in its slot: this one is the spool's)
-        else rc = mode == 2 ? kdf_prefilter_add_uploaded(h, slot) : kdf_count_uploaded(h, slot, mode == 1);
-        if (rc) return pass(i, rc);
-        slot ^= 1;
-    }
-    if (mode != 3) ++sp->replays;
-    return KDF_OK;
-}

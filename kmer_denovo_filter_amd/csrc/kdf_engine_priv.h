@@ -1,0 +1,257 @@
+// kdf_engine_priv.h -- what the units of libkdf.so share of the engine (host only, no kernel): kdf_engine.hip (the
+// core, which defines every function declared here unless noted), kdf_engine_reads.hip and kdf_spool.hip.  Nothing
+// here is exported: include/kdf.h is the library's interface.
+//
+// One kernel, one unit: a __global__ function is compiled by exactly one unit (a non-template kernel in a header two
+// units include would not link, a template instantiated by two would double its device code).  So this header pulls in
+// no kernel header -- the structs of engine state that kernels take by value are in kdf_device.h -- and a kernel that a
+// second unit needs gets a host launcher declared below (kh_scan_launch).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "kdf.h"
+#include "kdf_device.h"
+#include "kdf_hostutil.h"
+
+struct KbPass;                            // kdf_binned.h (the core)
+
+#define KDF_MERGE_MIN_PAIRS (1u << 16)
+enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
+// every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_BD = BUF_VAR + 5, BUF_COUNT = BUF_BD + 3 };
+// the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack"};
+struct kdf_engine {
+    int device = 0;
+    int k = 0;
+    int kw = 1;                   // key words: 1 narrow, 2 wide, 3..7 long (kdf_long.h)
+    int n_cu = 256;               // compute units of the device (persistent-kernel grids)
+    uint64_t dev_total_bytes = 0; // HBM of the device (sizes the entry ring's budget)
+    KdfTable t{};                 // live table
+    uint64_t cap = 0;
+    KdfCtl *ctl = nullptr;        // device
+    unsigned long long *d_out4 = nullptr;   // device scratch for ctl readback
+    unsigned long long *h_out4 = nullptr;   // pinned host mirror
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
+    uint64_t distinct = 0;        // host mirror after the last sync
+    uint64_t windows = 0;
+    bool filter_mode = false;
+    bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
+    bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
+    DevBuf buf[BUF_COUNT];                           // released together (kdf_destroy); used through the views below
+    DevBuf *const stage = buf + BUF_STAGE;           // [4] staging for the host-buffer entry points
+    // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
+    unsigned long long *kb_small = nullptr;   // totals[16]
+    unsigned long long *kb_totals_host = nullptr;   // pinned [16]
+    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
+    KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
+    // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
+    // table is needed or the ring is full (kb_flush).  Reserved by upper bounds (one entry per stream position), so no
+    // host round trip sits between the stages.
+    uint64_t ring_entries = 0, ring_rows = 0;        // capacity: entries (8 B x kw each), rows (pieces)
+    uint64_t ring_used = 0, rows_used = 0;           // reserved by the pending passes
+    uint32_t n_pass = 0;
+    uint64_t pend_positions = 0;                     // stream positions of the pending passes (upper bound of their entries)
+    KbPlan pend_plan{};                              // geometry (c1, c2, key slice) the pending passes were partitioned with
+    bool pend_filtered = false;                      // the pending passes are count --if passes
+    uint64_t stat_flushes = 0;
+    double grow_ratio = 0.0;                         // new distinct keys per counted window at the last flush (0: unknown)
+    uint64_t dens_windows = 0, dens_positions = 0;   // valid windows / stream positions of every pass this engine has flushed: sizes the piece groups
+    // L1: small insert batches are concatenated (packed) in a pending stream first; the partition runs over ~2^30 positions
+    uint64_t *l1_packed = nullptr, *l1_mask = nullptr;
+    uint64_t l1_cap_tiles = 0, l1_tiles = 0;
+    uint32_t opt_key_parts = 0, opt_key_part = 0;    // count only one slice of the key space (KdfTable::key_parts)
+    uint64_t opt_binned_min_positions = 1ull << 22;  // fewer pending positions at flush time use the direct global-table kernels
+    uint64_t opt_binned_bytes_per_position = 70;     // ... and so does a flush of fewer than table_bytes / 70 positions (use_binned)
+    uint64_t opt_binned_max_positions = 1ull << 31;  // longer streams are partitioned in several passes
+    uint32_t opt_binned_filtered_min_log2cap = 23;   // count --if goes binned from 2^23 slots (measured crossover)
+    uint32_t opt_big_bucket_log2cap = 32;            // tables from 2^32 slots on have buckets of twice the slots (KDF_BIG_BUCKET_LOG2CAP / option big_bucket_log2cap)
+    uint64_t opt_merge_min_pairs = KDF_MERGE_MIN_PAIRS;   // below this many pairs a merge goes straight to the atomic insert (tests lower it)
+    uint32_t opt_hash_shift = 0;                     // KdfTable::hshift of the tables this engine creates (owner tables)
+    int opt_force_path = 0;                          // 0 auto, 1 direct, 2 binned, 4 sieve only (count --if)
+    int opt_defer = 1;                               // 1: kernel C is deferred over the pending passes; 0: every count call ends with a flush
+    uint64_t opt_defer_max_bytes = 0;                // budget of the entry ring (0: 40 % of the device's memory)
+    // 1 (the default): a dump (min_count >= 1, caller-sized device buffers) asked for while passes are pending is written by the
+    // flush itself -- kernel C holds every bucket anyway (kb_bucket_kernel<.., DUMP>), and the dump's pass over the table is
+    // saved.  Option "fused_dump" / env KDF_FUSED_DUMP=0 turn it off; long engines have no binned pipeline: 0
+    int opt_fused_dump = [] { const char *e = getenv("KDF_FUSED_DUMP"); return e ? atoi(e) != 0 : 1; }();
+    // the request a dump hands to the LAST flush before it (fuse_min > 0), and what came of it
+    uint32_t fuse_min = 0; uint64_t *fuse_lo = nullptr, *fuse_hi = nullptr; uint32_t *fuse_cnt = nullptr; uint64_t fuse_cap = 0;
+    bool fuse_done = false; uint64_t fuse_n = 0;
+    uint64_t stat_fused_dumps = 0;
+    // 1 (the default): such a dump into a table that is still only logically empty (kdf_clear, nothing applied since) runs the
+    // DUMP-ONLY flush -- kb_bucket_kernel<.., DUMP, LAZY> writes the dump and the ctl counters and leaves the table alone.  The
+    // passes stay in the ring (the first n_dumped of n_pass); whatever needs the table later applies them with the ordinary
+    // flush, into the still empty table.  Option "lazy_table" / env KDF_LAZY_TABLE=0 turn it off.
+    int opt_lazy_table = [] { const char *e = getenv("KDF_LAZY_TABLE"); return e ? atoi(e) != 0 : 1; }();
+    uint32_t n_dumped = 0;                           // pending passes a dump-only flush has applied: kept for the table, reported as flushed
+    uint64_t dumped_positions = 0;                   // ... and their stream positions
+    uint64_t acct_entries = 0, acct_positions = 0;   // what of the pending passes dens_windows / dens_positions already hold
+    uint64_t stat_dump_only = 0, stat_materialisations = 0;
+    uint64_t opt_l1_positions = 1ull << 30;          // pending-stream size from which it is partitioned
+    uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
+    // double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
+    // stream of their own, so the H2D copy of batch i + 1 runs under the count of batch i
+    DevBuf (*const up_buf)[2] = (DevBuf (*)[2])(buf + BUF_UP);      // [slot][packed, mask]
+    uint64_t up_n[2] = {0, 0}; bool up_valid[2] = {false, false};
+    hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr}, use_done[2] = {nullptr, nullptr};
+    uint64_t stat_heavy_buckets = 0;
+    void *kb_heavy = nullptr;                        // heavy buckets of skewed flushes (kdf_binned.h kb_heavy_slice_kernel)
+    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly)
+    uint32_t merge_flag_host = 0;
+    int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
+    int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
+    // long engines take the sieve only when asked to (option "long_sieve" / env KDF_LONG_SIEVE=1; k <= 63: always): their
+    // count --if and scan then go through kdf_long_sieve_kernel (kdf_long_sieve.h)
+    int opt_long_sieve = [] { const char *e = getenv("KDF_LONG_SIEVE"); return e ? atoi(e) != 0 : 0; }();
+    int last_sieve_in_lds = 0;                       // the last sieve kernel read the sieve from LDS (1) or from L2 (0)
+    bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
+    bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
+    int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve
+    int last_scan_path = 0;                          // kernel of the last kdf_scan_reads_dev: 0 direct, 3 sieve
+    uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
+    uint64_t sieve_words = 0, sieve_alloc = 0;
+    bool sieve_valid = false;
+    bool sieve_unfit = false;                        // long_sieve_ensure found the table's keys too many for a sieve: not asked again
+                                                     // until the keys, the filter or the sizing options change (sieve_drop)
+    uint32_t last_sieve_rounds = 0;                  // tiles per thread of the last sieve kernel of a long engine (LDS form; L2 form: 1)
+    uint32_t opt_debug_flags = 0;                    // experiments only (KbPlan::dbg)
+    uint64_t stat_binned_passes = 0, stat_replayed_buckets = 0;
+    // optional HIP-event timing (kdf_profile).  T_STREAM, the dominant kernels: a span's tag is its tiles, so passes are the
+    // launches and tag_sum x 64 the positions (a flush is timed with tag 0: its positions were counted with the passes it
+    // applies).  T_HITS: tag 1 for the span that opens a call, 0 for the second span of a call that finds hits.
+    bool prof = false;
+    EvTimer timer[T_COUNT];
+    // binned path: events around each stage (A0 hist, A1 scatter, B finesort | C bucket)
+    std::vector<std::vector<hipEvent_t>> prof_stage_ev;   // 4 events: a partition (A0, A1, B); 2 events: a flush (C)
+    double prof_stage_ms[4] = {0, 0, 0, 0};
+    uint64_t prof_stage_passes = 0;
+    // ---- two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off ------------------------
+    int pf_state = PF_OFF;
+    KdfPrefilter pf{};                               // the sieve (device), its size and the gate's threshold
+    unsigned long long *pf_ctr = nullptr;            // device: sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
+    uint64_t *pf_admit = nullptr; uint64_t pf_admit_words = 0;   // the gate's output for the stream being counted (grow-only)
+    uint64_t capacity_hint = 0;                      // kdf_create's: sizes the sieve when the caller leaves that to the engine
+    uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
+    // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
+    DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
+    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch and the staging of the host forms -------------
+    DevBuf *const cov_buf = buf + BUF_COV;           // [6] 0 CIGAR prefix sums, 1 ref_start, 2 cigar, 3 cigar_offsets, 4 kmer_cov, 5 read_cov
+    // ---- VCF mode (kdf_variants.h): grow-only scratch and the staging of the host forms -------------------------------------
+    DevBuf *const var_buf = buf + BUF_VAR;           // [5] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags, 3 / 4 host forms: inputs / outputs
+    // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
+    bool sk_on = false;
+    KdfSketch sk{};                                  // the register cells (device) and p
+    uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
+    unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
+    // ---- device BAM feeder (kdf_bamdev.h): grow-only scratch kept between batches ---------------------------------------------
+    DevBuf *const bd_buf = buf + BUF_BD;             // [3] 0 inflated span, 1 block / sub-range status, counts, bases and totals, 2 per-read sequence offsets
+    // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
+    // "bamdev_host_inflate": tells a decoder fault from a file fault, and lets the tests walk the patch path, which no file zlib wrote takes)
+    int opt_bd_host_inflate = 0;
+    uint64_t stat_bd_fallback = 0;                   // blocks the device decoder rejected and zlib inflated (stat "bamdev_fallback_blocks")
+    std::string err;
+};
+
+// ---- internal functions that more than one unit calls ----------------------------------------------------------------
+#pragma GCC visibility push(hidden)
+extern thread_local std::string g_err;    // the error text of calls without an engine or a spool
+int fail(kdf_engine *h, int code, const char *fmt, ...);
+// kdf_clear defers the table's memset: everything that reads or probes the table calls this first
+int materialize(kdf_engine *h);
+// everything pending (the concatenated small batches, the partitioned passes) goes into the table
+int pending_flush(kdf_engine *h, bool fuse = false);
+// room for `bytes` in one of the engine's buffers whose readers all run on the engine's stream
+int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t) = slack_8th, const char *what = nullptr);
+// host arrays into staging slots 0 / 1 as a padded stream; `bytes` host bytes into staging slot i (stream order)
+int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, uint64_t **d_packed, uint64_t **d_invalid);
+int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn);
+// kdf_engine_reads.hip: kh_scan_kernel (kdf_hits.h) on stream s, for the spool's kdf_spool_select_reads
+void kh_scan_launch(hipStream_t s, unsigned long long *sums, uint64_t n);
+#pragma GCC visibility pop
+
+#define HIPCHK(h, call)                                                                 \
+    do {                                                                                \
+        hipError_t e_ = (call);                                                         \
+        if (e_ != hipSuccess)                                                           \
+            return fail(h, e_ == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP,     \
+                        "%s failed: %s", #call, hipGetErrorString(e_));                 \
+    } while (0)
+
+static inline uint32_t log2ceil(uint64_t x) { uint32_t l = 0; while ((1ull << l) < x) ++l; return l; }
+
+// code for k <= 63 only (the binned pipeline, merge, sieve): W = 1 or 2
+template <typename F>
+static inline int by_width(kdf_engine *h, F &&f) { return h->kw == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{}); }
+// code for every key width: W = 1, 2 (kdf_device.h) or 3 .. 7 (long keys, kdf_long.h)
+template <typename F>
+static inline int by_words(kdf_engine *h, F &&f) {
+    switch (h->kw) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return f(std::integral_constant<int, 7>{});
+    }
+}
+// long engines: W = 3 .. 7
+static inline bool is_long(const kdf_engine *h) { return h->kw > 2; }
+// bits of a long key's top word: 2k - 64 (W - 1), 2 .. 62 for odd k
+static inline int long_top_bits(const kdf_engine *h) { return 2 * h->k - 64 * (h->kw - 1); }
+
+// words per key of a host form's first key array: 1 for the (lo, hi) forms, W for the rows of the _w forms
+static inline uint64_t lo_words(const kdf_engine *h) { return is_long(h) ? h->kw : 1; }
+
+// The (lo, hi) key forms take k <= 63 engines only; a long engine names the W-word form to use instead.  The multi-GPU
+// entry points are single-GPU-only for long keys.
+#define KDF_REFUSE_LONG(h, fn, wfn) \
+    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: k=%d takes %d-word keys: use %s", fn, (h)->k, (h)->kw, wfn); } while (0)
+#define KDF_REFUSE_LONG_MULTI(h, fn) \
+    do { if (is_long(h)) return fail(h, KDF_ERR_INVALID, "%s: not available for k > 63 (long keys count on one GPU)", fn); } while (0)
+
+// ---------------------------------------------------------------------------
+// Where a consumer's read stream comes from (count, count --if, prefilter tally, sketch, a spool's append): device
+// pointers, host arrays or an upload slot.  Each maker holds its form's refusals, worded with the caller's name; an
+// entry point is "refuse by state, make a source, run the _dev core, release".
+
+struct StreamSrc { const uint64_t *packed = nullptr, *invalid = nullptr; uint64_t n_bases = 0; int slot = -1; };
+
+// where the message of a refusal goes: this engine's error string (a spool has its own sink)
+struct EngSink {
+    kdf_engine *h;
+    template <typename... A> int operator()(int code, const char *fmt, A... a) const { return fail(h, code, fmt, a...); }
+};
+struct NoRefusal { int operator()(const StreamSrc &) const { return KDF_OK; } };
+
+#pragma GCC visibility push(hidden)
+// behind the consumer's last launch: the slot's next upload waits for this reader
+void src_release(kdf_engine *h, const StreamSrc &src);
+#pragma GCC visibility pop
+
+// The batch of upload slot `slot` (kdf_upload_reads_async), or KDF_ERR_STATE.  also_refuse(src) holds the refusals the
+// caller tests AFTER the slot's: a refused call changes nothing, the slot keeps its batch.  consume: the slot is empty
+// afterwards (count, tally), else it keeps the batch for the next consumer (sketch, spool).  The engine's stream waits for
+// the copy; host_wait: so does the host -- the caller of a count, tally or sketch recycles its (pinned) source buffer as
+// soon as the call returns, and the copy was issued a whole batch ago.  An empty batch (n_bases 0) needs no wait.
+template <typename S, typename R>
+static int src_slot(S &&sink, const char *fn, kdf_engine *h, int slot, bool consume, bool host_wait, StreamSrc &src, R &&also_refuse) {
+    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return sink(KDF_ERR_STATE, "%s: nothing was uploaded into slot %d", fn, slot);
+    src = StreamSrc{(const uint64_t *)h->up_buf[slot][0].p, (const uint64_t *)h->up_buf[slot][1].p, h->up_n[slot], slot};
+    if (const int rc = also_refuse(src)) return rc;
+    if (consume) h->up_valid[slot] = false;
+    if (src.n_bases == 0) return KDF_OK;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->up_done[slot], 0);
+    if (e == hipSuccess && host_wait) e = hipEventSynchronize(h->up_done[slot]);
+    if (e != hipSuccess) return sink(e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "%s: waiting for the copy into slot %d failed: %s", fn, slot, hipGetErrorString(e));
+    return KDF_OK;
+}

@@ -24,29 +24,13 @@
 #include "kdf_depth.h"
 
 #define KH_BLOCK_WORDS 1024               // mask words per workgroup: 4 consecutive words per thread
-#define KH_ROW_WORDS   2                  // hits, distinct (uint32)
+// (KH_ROW_WORDS = 2 -- hits, distinct (uint32) -- and the block scan kh_block_excl: kdf_device.h, shared with kdf_spool.h)
 
 // mask word w with the bits at and past n_bases cleared; n_words = ceil(n_bases / 64)
 __device__ __forceinline__ uint64_t kh_word(const uint64_t *__restrict__ bits, uint64_t w, uint64_t n_words, uint64_t n_bases) {
     if (w >= n_words) return 0;
     const uint64_t rem = n_bases - w * 64;                            // >= 1
     return rem < 64 ? bits[w] & ((1ull << rem) - 1) : bits[w];
-}
-
-// exclusive prefix of v over the 256 threads of the workgroup and their total; ws: 4 words of LDS
-__device__ __forceinline__ uint32_t kh_block_excl(uint32_t v, uint32_t *ws, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const uint32_t s = ws[j]; pre += j < wv ? s : 0; total += s; }
-    __syncthreads();                                                  // (ws is written again by the caller's next scan)
-    return pre + inc - v;
 }
 
 // the read that holds position p: r with offs[r] <= p < offs[r + 1], or -1.  Whatever the offsets hold, the result is

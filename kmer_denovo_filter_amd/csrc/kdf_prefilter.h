@@ -23,11 +23,7 @@
 #define KDF_PF_MIN_LOG2 16
 #define KDF_PF_MAX_LOG2 38
 
-struct KdfPrefilter {
-    unsigned long long *words;   // 2^(log2_cells - 4) words
-    uint32_t log2_cells;
-    uint32_t min_count;          // 2 or 3: the gate admits cells that read >= min_count
-};
+// (struct KdfPrefilter -- words, log2_cells, min_count -- is in kdf_device.h: the engine holds one by value)
 
 __device__ __forceinline__ void kdf_pf_locate(const KdfPrefilter &pf, uint64_t h, uint64_t &word, uint32_t &sh) {
     const uint64_t cell = h >> (64 - pf.log2_cells);

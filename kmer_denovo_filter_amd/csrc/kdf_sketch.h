@@ -36,10 +36,7 @@ __host__ __device__ __forceinline__ uint64_t kdf_sketch_fin(uint64_t x) {
 __host__ __device__ __forceinline__ uint64_t kdf_sketch_g(uint64_t h) { return kdf_sketch_fin(h); }
 __host__ __device__ __forceinline__ uint64_t kdf_sketch_g_wide(uint64_t h, uint64_t hi) { return kdf_sketch_fin(h + hi * KDF_SK_HI_MUL); }
 
-struct KdfSketch {
-    uint32_t *cells;       // 2^p cells, cell j = register j (0 .. 65 - p)
-    uint32_t p;
-};
+// (struct KdfSketch -- cells, p -- is in kdf_device.h: the engine holds one by value)
 
 __device__ __forceinline__ void kdf_sk_locate(uint32_t p, uint64_t g, uint32_t &j, uint32_t &r) {
     j = (uint32_t)(g >> (64 - p));                                        // < 2^p

@@ -1,4 +1,4 @@
-// kdf_spool.h -- the read spool's kernels (kdf.h "read spool"; the host side is in kdf_engine.hip).
+// kdf_spool.h -- the read spool's kernels (kdf.h "read spool"; the host side is in kdf_spool.hip).
 //
 // A spool keeps the batches of a read stream resident, packed as they arrive (3 bits per position), as a list of SEGMENTS.
 // A segment is one read stream in the layout of kdf.h "Read streams"; a batch of n_bases positions occupies
@@ -10,7 +10,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kdf_hits.h"            // kh_block_excl, kh_scan_kernel: the block scan the ks_select_* kernels share with kh_*
+#include "kdf_device.h"          // kh_block_excl: the block scan the ks_select_* kernels share with kh_* (kdf_hits.h, whose
+                                 // kh_scan_kernel belongs to kdf_engine_reads.hip: the spool runs it through kh_scan_launch)
 
 #define KS_THREADS 256
 #define KS_MAX_BLOCKS 2048u      // a streaming copy: 8 workgroups per CU fill the device, the rest is a grid stride

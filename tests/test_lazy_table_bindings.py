@@ -20,7 +20,8 @@ def test_the_engine_knows_the_option_and_the_stats():
     assert f'n == "{OPTION}"' in set_option
     for name in STATS:
         assert f'n == "{name}"' in get_stat, name
-    assert 'getenv("KDF_LAZY_TABLE")' in src
+    # (the option's default is read where struct kdf_engine is declared: the header the engine's units share)
+    assert 'getenv("KDF_LAZY_TABLE")' in src + _read("kmer_denovo_filter_amd", "csrc", "kdf_engine_priv.h")
 
 
 def test_the_header_documents_them():
