@@ -14,7 +14,9 @@
 // the targets gfx950 follows: "no special action is required for coherence between the lanes of a single wavefront").  It
 // is the guarantee a single lane's own store-then-load of one address rests on, at cache-line granularity.  L.sync() is
 // that wavefront-scope fence plus a wave barrier: it keeps the COMPILER from moving accesses across the points where
-// lanes exchange data.  On the GPU the equality with zlib over matches at every distance checks it (test_gpu_bamdev.py).
+// lanes exchange data.  On the GPU the equality with zlib over matches at every distance around the lane count, and over
+// chains of matches that each copy what the one before stored, checks it
+// (test_gpu_bamdev.py::test_lanes_see_the_bytes_other_lanes_stored_at_every_distance).
 //
 // Memory safety is by construction, whatever the bytes say:
 //   * every input read is below `in_len` (the bit reader never looks past it; a code that needs more bits than are

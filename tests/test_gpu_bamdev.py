@@ -81,6 +81,73 @@ def test_corrupt_blocks_get_a_status_and_fail_as_io_errors(corrupt_list):
         assert got[0] == data and st[0] == 0
 
 
+def _check_equal_zlib(eng, cases, slack=0):
+    """cases: [(label, payload, zlib's bytes)], decoded in one call: status 0 and zlib's bytes for each"""
+    got, st = _inflate(eng, [(p, len(d)) for _, p, d in cases], slack=slack)
+    for i, ((label, _, d), g, s) in enumerate(zip(cases, got, st)):
+        assert s == 0 and g == d, (i, label, int(s))
+
+
+def test_inflate_handmade_blocks_equal_zlib_without_fallback():
+    """Legal DEFLATE that zlib's encoder never writes (bamdev_cases.handmade_payloads): the device decoder rejects none"""
+    hs = bc.handmade_payloads()
+    with _engine() as eng:
+        _check_equal_zlib(eng, hs, slack=100)
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+
+
+def test_lanes_see_the_bytes_other_lanes_stored_at_every_distance():
+    """What csrc/kdf_inflate.h rests its one GPU-specific assumption on: a lane's load sees the earlier store of another
+    lane of its wave with no fence instruction.  Matches at every distance 1..130 (and around 192 and 256), shorter than,
+    as long as and longer than the distance, and chains of matches that each copy what the match before stored."""
+    hs = [c for c in bc.handmade_payloads() if c[0].startswith(("every-distance", "match-chains"))]
+    assert sum(c[0].startswith("every-distance") for c in hs) >= 5 and sum(c[0].startswith("match-chains") for c in hs) == 4
+    with _engine() as eng:
+        _check_equal_zlib(eng, hs)
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+
+
+def test_inflate_mutants_zlib_accepts_equal_zlib():
+    """The first 512 mutants of the CPU test's corpus that zlib accepts: still legal streams, nobody's encoder's"""
+    ms = []
+    for p, _, want in bc.mutants():
+        if want is not None:
+            ms.append((len(ms), p, want))
+            if len(ms) == 512:
+                break
+    assert len(ms) == 512
+    with _engine() as eng:
+        _check_equal_zlib(eng, ms)
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+
+
+@pytest.mark.parametrize("n", (1, 3, 4, 5, 257))
+def test_inflate_batches_that_fill_workgroups_unevenly(n):
+    """Four waves of a workgroup hold four table sets: neighbouring waves decode different block types, and the last
+    workgroup is partly empty."""
+    hs = bc.handmade_payloads()
+    batch = [hs[(7 * n + i) % len(hs)] for i in range(n)]
+    with _engine() as eng:
+        _check_equal_zlib(eng, batch)
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+
+
+def test_corrupt_blocks_among_valid_ones_in_one_batch(corrupt_list):
+    from kmer_denovo_filter_amd._native import KdfError
+    cs, cpu_status = corrupt_list
+    hs = bc.handmade_payloads()
+    items = [(cs[(i // 4) % len(cs)][1], cs[(i // 4) % len(cs)][2]) if i % 4 == 3 else (hs[i % len(hs)][1], len(hs[i % len(hs)][2]))
+             for i in range(4 * len(cs) + 2)]
+    with _engine() as eng:
+        with pytest.raises(KdfError) as ei:
+            _inflate(eng, items)
+        assert ei.value.code == KDF_ERR_IO and "file offset 4000 " in str(ei.value)         # block 3: the first bad one
+        assert f"device status {cpu_status[0]}" in str(ei.value)
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+        _check_equal_zlib(eng, hs[:9])                                   # the engine is none the worse
+        assert eng.get_stat("bamdev_fallback_blocks") == 0
+
+
 def test_host_inflate_option_walks_the_patch_path():
     """No block zlib wrote is rejected by the device decoder, so the zlib fallback is reached through the option that
     sends every block there: the patched bytes are zlib's, and the stat counts the blocks."""
