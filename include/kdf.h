@@ -419,7 +419,10 @@ int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out,
  * part p occupies [sum(counts[0..p)), +counts[p]) of the outputs.  The whole dump is in HASH
  * ORDER (grouped by the top log2cap - 6 hash bits, ascending), which is bucket order in every
  * owner table of up to 64x this table's slots per owner: kdf_add_pairs_multi_dev merges it
- * bucket by bucket in LDS.  One stream synchronisation.
+ * bucket by bucket in LDS.  Order and owners follow each key's HASH, not the slot it lies in: on a table with big
+ * buckets (8192 slots for k <= 32: from 2^32 slots on, or option "big_bucket_log2cap") a probe run can carry a key
+ * out of the 4096 slots its hash names, even across an owner boundary that cuts its bucket (parts not a power of two
+ * at 2^28 slots); it is still dumped under its own prefix and to its own owner.  One stream synchronisation.
  * parts <= 64; KDF_ERR_STATE when the table is smaller than 2^28 slots. */
 int kdf_export_parts_dev(kdf_engine *h, uint32_t min_count, uint32_t parts, void *d_keys_lo_out,
                          void *d_keys_hi_out, void *d_counts_out, uint64_t cap,

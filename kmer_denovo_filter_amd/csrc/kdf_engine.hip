@@ -2067,6 +2067,10 @@ static int export_parts(kdf_engine *h, uint32_t min_count, uint32_t parts, bool 
         return fail(h, KDF_ERR_STATE, "%s: table of 2^%u slots is too small for an owner-ordered dump (needs 2^28)", who, h->t.log2cap);
     const bool have_out = d_lo && (packed || h->kw == 1 || d_hi);
     const uint64_t nblk = h->cap / KM_BLOCK_SLOTS;
+    // a big bucket is two dump blocks: its entries are dumped by the block they are homed in (kdf_merge.h, NH)
+    const bool big = (1ull << h->t.bucket_bits) > KM_BLOCK_SLOTS;
+    if (big && (h->kw != 1 || (1ull << h->t.bucket_bits) != 2 * KM_BLOCK_SLOTS))
+        return fail(h, KDF_ERR_STATE, "%s: no owner-ordered dump for buckets of 2^%u slots", who, h->t.bucket_bits);
     // scratch: blk_off u64[nblk + 1] | part_first u64[S] | part_off u64[S + 1] | part_base u64[S + 1] | blk_cnt u32[nblk]
     const size_t off_words = nblk + 1 + KDF_SHARDS + 2 * (KDF_SHARDS + 1);
     int rc = eng_reserve(h, *h->merge_buf, off_words * 8 + nblk * 4, slack_exact);
@@ -2084,19 +2088,21 @@ static int export_parts(kdf_engine *h, uint32_t min_count, uint32_t parts, bool 
     HIPCHK(h, hipMemcpyAsync(part_first, pf.data(), KDF_SHARDS * 8, hipMemcpyHostToDevice, h->stream));
     std::vector<unsigned long long> po(2 * (KDF_SHARDS + 1), 0);
     const uint32_t esz = 8u * h->kw + 4u;
-    by_width(h, [&](auto KWc) {
-        constexpr int KW = decltype(KWc)::value;
-        hipLaunchKernelGGL(km_count_kernel<KW>, dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_cnt);
+    auto dump = [&](auto KWc, auto NHc) {
+        constexpr int KW = decltype(KWc)::value, NH = decltype(NHc)::value;
+        hipLaunchKernelGGL((km_count_kernel<KW, NH>), dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_cnt);
         hipLaunchKernelGGL(km_scan_kernel, dim3(1), dim3(1024), 0, h->stream, blk_cnt, blk_off, nblk, part_first, parts, part_off);
         hipLaunchKernelGGL(km_packbase_kernel, dim3(1), dim3(64), 0, h->stream, part_off, parts, esz, part_base);
         if (have_out && packed)
-            hipLaunchKernelGGL((km_write_kernel<KW, true>), dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_off,
+            hipLaunchKernelGGL((km_write_kernel<KW, true, NH>), dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_off,
                                (uint64_t *)d_lo, (uint64_t *)nullptr, (uint32_t *)nullptr, cap, part_off, part_base, parts);
         else if (have_out)
-            hipLaunchKernelGGL((km_write_kernel<KW, false>), dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_off,
+            hipLaunchKernelGGL((km_write_kernel<KW, false, NH>), dim3((unsigned)nblk), dim3(KM_THREADS), 0, h->stream, h->t, min_count, blk_off,
                                (uint64_t *)d_lo, h->kw == 2 ? (uint64_t *)d_hi : nullptr, (uint32_t *)d_cnt, cap, part_off, part_base, parts);
         return 0;
-    });
+    };
+    if (big) dump(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
+    else by_width(h, [&](auto KWc) { return dump(KWc, std::integral_constant<int, 1>{}); });
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(po.data(), part_off, 2 * (KDF_SHARDS + 1) * 8, hipMemcpyDeviceToHost, h->stream));   // part_off | part_base
     HIPCHK(h, hipStreamSynchronize(h->stream));             // the one synchronisation of the dump (pf / po are pageable)

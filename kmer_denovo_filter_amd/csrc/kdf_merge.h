@@ -5,7 +5,10 @@
 //   P = log2cap - 12 + KM_SUB_BITS bits of the key's hash -- into one contiguous range per owner rank.  Two reads of
 //   the table (count per 4096-slot block, scan, write); inside a block the kept entries are counting-sorted in LDS by
 //   the next KM_SUB_BITS hash bits, because a block of the sender's table covers several buckets of an owner's table
-//   (the owner drops the log2(world) hash bits that name it, KdfTable::hshift).
+//   (the owner drops the log2(world) hash bits that name it, KdfTable::hshift).  An entry belongs to the block it is
+//   HOMED in.  With buckets of one block or less that is the block it lies in (probing wraps inside the bucket); a
+//   big bucket (8192 narrow slots) is NH = 2 blocks, an entry homed in one can lie in the other, and each of the two
+//   workgroups reads the whole bucket and keeps the entries whose hash names its block.
 // OWNER   (kdf_add_pairs_multi_dev): every source's segment arrives grouped by the owner table's buckets, in ascending
 //   order.  km_bounds_kernel finds, per segment, the range of pairs of each bucket (and proves the grouping: one
 //   descending step anywhere raises `flag` and everything falls back to the global-atomic insert, so any input is
@@ -40,18 +43,25 @@ __device__ __forceinline__ bool km_keep(uint64_t lo, uint64_t hi, uint32_t c, ui
     return occ && c >= min_count;
 }
 
-// pass 1 of the ordered dump: kept entries per block of 4096 slots
-template <int KW>
+// the block an entry is homed in: the top log2cap - 12 bits of its stored hash (a dump refuses hshift; log2cap >= 28)
+__device__ __forceinline__ uint64_t km_home_block(const KdfTable &t, uint64_t h) { return h >> (64 - (t.log2cap - 12)); }
+
+// pass 1 of the ordered dump: kept entries per block of 4096 slots (NH = 2: homed in the block, read from its bucket of two)
+template <int KW, int NH = 1>
 __global__ __launch_bounds__(KM_THREADS) void km_count_kernel(KdfTable t, uint32_t min_count, uint32_t *__restrict__ blk_cnt) {
     const uint64_t cap = 1ull << t.log2cap;
-    const uint64_t first = (uint64_t)blockIdx.x * KM_BLOCK_SLOTS;
+    const uint64_t first = NH == 1 ? (uint64_t)blockIdx.x * KM_BLOCK_SLOTS : (uint64_t)(blockIdx.x / NH) * (NH * KM_BLOCK_SLOTS);
     __shared__ uint32_t wsum[KM_THREADS / 64];
     uint32_t mine = 0;
 #pragma unroll 4
-    for (uint32_t r = 0; r < KM_SPT; ++r) {
+    for (uint32_t r = 0; r < KM_SPT * NH; ++r) {
         const uint64_t i = first + r * KM_THREADS + threadIdx.x;
         if (i < cap) {
-            if (min_count >= 1) mine += t.cnt[i] >= min_count ? 1u : 0u;      // count > 0 implies occupied
+            if constexpr (NH > 1) {
+                const uint64_t lo = t.lo[i];
+                mine += (km_keep<KW>(lo, KW == 2 ? t.hi[i] : 0, t.cnt[i], min_count) && km_home_block(t, lo) == blockIdx.x) ? 1u : 0u;
+            }
+            else if (min_count >= 1) mine += t.cnt[i] >= min_count ? 1u : 0u;      // count > 0 implies occupied
             else mine += (KW == 1 ? t.lo[i] != KDF_EMPTY : t.hi[i] != KDF_EMPTY) ? 1u : 0u;
         }
     }
@@ -106,7 +116,8 @@ __global__ void km_packbase_kernel(const unsigned long long *__restrict__ part_o
 
 // pass 2: a block's kept entries, grouped by the KM_SUB_BITS hash bits below the block prefix, at blk_off[block]
 // PACKED: olo is the byte buffer of the packed layout (km_packbase_kernel), out_cap its size in bytes; a block lies in one part.
-template <int KW, bool PACKED>
+// NH = 2: the block's entries are the ones HOMED in it, found anywhere in its bucket of two blocks.
+template <int KW, bool PACKED, int NH = 1>
 __global__ __launch_bounds__(KM_THREADS) void km_write_kernel(KdfTable t, uint32_t min_count, const unsigned long long *__restrict__ blk_off,
                                                               uint64_t *__restrict__ olo, uint64_t *__restrict__ ohi,
                                                               uint32_t *__restrict__ ocnt, uint64_t out_cap,
@@ -131,17 +142,19 @@ __global__ __launch_bounds__(KM_THREADS) void km_write_kernel(KdfTable t, uint32
     __syncthreads();
     // the block prefix is the top (log2cap - 12) hash bits (fewer than 12 bits of table: one block, no prefix)
     const uint32_t pre_bits = t.log2cap > 12 ? t.log2cap - 12 : 0;
-    uint64_t lo[KM_SPT], hi[KM_SPT]; uint32_t c[KM_SPT], sub[KM_SPT], rank[KM_SPT];
+    constexpr uint32_t SPT = KM_SPT * NH;
+    const uint64_t rfirst = NH == 1 ? first : (uint64_t)(blockIdx.x / NH) * (NH * KM_BLOCK_SLOTS);
+    uint64_t lo[SPT], hi[SPT]; uint32_t c[SPT], sub[SPT], rank[SPT];
 #pragma unroll
-    for (uint32_t r = 0; r < KM_SPT; ++r) {
-        const uint64_t i = first + r * KM_THREADS + threadIdx.x;
+    for (uint32_t r = 0; r < SPT; ++r) {
+        const uint64_t i = rfirst + r * KM_THREADS + threadIdx.x;
         lo[r] = KDF_EMPTY; hi[r] = KW == 2 ? KDF_EMPTY : 0; c[r] = 0;
         if (i < cap) { lo[r] = t.lo[i]; if (KW == 2) hi[r] = t.hi[i]; c[r] = t.cnt[i]; }
     }
 #pragma unroll
-    for (uint32_t r = 0; r < KM_SPT; ++r) {
+    for (uint32_t r = 0; r < SPT; ++r) {
         sub[r] = 0xFFFFFFFFu;
-        if (km_keep<KW>(lo[r], hi[r], c[r], min_count)) {
+        if (km_keep<KW>(lo[r], hi[r], c[r], min_count) && (NH == 1 || km_home_block(t, lo[r]) == blockIdx.x)) {
             const uint64_t h = lo[r] << t.hshift;                   // the slot holds the hash (stored form)
             sub[r] = (uint32_t)((h << pre_bits) >> (64 - KM_SUB_BITS));
             rank[r] = atomicAdd(&hist[sub[r]], 1u);
@@ -156,7 +169,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_write_kernel(KdfTable t, uint32
     }
     __syncthreads();
 #pragma unroll
-    for (uint32_t r = 0; r < KM_SPT; ++r) {
+    for (uint32_t r = 0; r < SPT; ++r) {
         if (sub[r] != 0xFFFFFFFFu) {
             const uint64_t pos = base + start[sub[r]] + rank[r];
             if constexpr (PACKED) {

@@ -314,8 +314,9 @@ def test_big_buckets_binned_equals_direct_and_merge(k):
         e.count_dev(ds.packed.data_ptr() + half // 4, ds.invalid.data_ptr() + half // 8, ds.n_bases - half)
         big = dump(e)
         assert e.get_stat("bucket_bits") == (13 if not wide else 12) and e.get_stat("binned_passes") >= 2
-        # the dump in ascending order of the stored form (what the owner-ordered dump of a big table is): the LDS bucket merge
-        # takes segments grouped by table bucket
+        # the dump sorted here by the stored form -- a stand-in: this table is too small for the owner-ordered dump, whose
+        # order on a big-bucket table test_gpu_merge_truth.py checks -- because the LDS bucket merge takes segments
+        # grouped by table bucket
         nd = big[0].numel()
         x = big[0].clone()
         if wide:
