@@ -44,7 +44,9 @@ __device__ __forceinline__ uint64_t *kdf_long_word(const KdfTable &t, int j, uin
 // 1. CAS the top word EMPTY -> top | PENDING; 2. publish h and the middle words with returning atomics (complete at
 // memory before the final store issues); 3. store the final top word.  A prober that matches a PENDING top word
 // returns KDF_BLOCKED and is retried by the caller's wave-uniform loop (kdf_add_long): no lane ever waits inside a
-// divergent loop.  A match needs the top word, h and every middle word to be equal.
+// divergent loop.  A match needs the top word, h and every middle word to be equal.  Two random keys never share h, so
+// the middle-word compares (here and in kdf_find_long) are reachable only with keys written under one h
+// (tests/long_truth.py, used by tests/test_gpu_long_table_truth.py).
 //
 // `pre`: the top word of the home slot loaded earlier by the caller (KDF_EMPTY-safe: a claimed top word never
 // changes, and a stale EMPTY is corrected by the CAS); have_pre = false loads it here.
