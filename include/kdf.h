@@ -164,6 +164,7 @@ int kdf_flush(kdf_engine *h);
  *            sieve kernel, count --if or scan, read the sieve from LDS: 1, or from L2: 0), "last_sieve_rounds" (long engines: tiles per
  *            thread of that kernel, 1 for the L2 form), "long_sieve" (the option; 0 for k <= 63), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
+ *            "join_us" / "join_passes" (the join kernels of kdf_count_join / kdf_export_join* under kdf_profile);
  *            "depth_us" / "depth_passes" (kdf_depth_kernel under kdf_profile: kdf_window_counts* / kdf_read_depth*);
  *            "hits_us" / "hits_passes" (the kh_* kernels of kdf_read_hits* / kdf_hit_list* under kdf_profile, the scan kernel
  *            not included; one pass per call); "coverage_us" / "coverage_passes" (the kc_* kernels of kdf_hit_coverage* /
@@ -411,6 +412,51 @@ int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out,
 int kdf_export_ge_dev(kdf_engine *h, uint32_t min_count, void *d_keys_lo_out,
                       void *d_keys_hi_out, void *d_counts_out, uint64_t cap,
                       int sorted, uint64_t *n_out);
+
+/* Table join: the entries of h's table by their count in other's table -- reference subtraction (`dump -L 3` of the
+ * child, kept where the reference holds nothing) and `dump -L min -U max` in one pass, without a key list in between.
+ * An entry (key, c) of h is SELECTED iff
+ *   - its slot is occupied,
+ *   - min_count <= c <= max_count, and
+ *   - when other != NULL: other_min <= oc <= other_max, where oc is the count kdf_query would return for the key in
+ *     other: 0 when other does not hold the key, and 0 when it holds it with count 0 (the two are not told apart).
+ * Every bound is inclusive; UINT32_MAX as an upper bound means none.  With other == NULL the other_* bounds are
+ * ignored and every oc reads 0: that is `jellyfish dump -L min_count -U max_count`.
+ *
+ * kdf_count_join gives the number of selected entries, for every key width.  The export forms follow
+ * kdf_export_ge_dev / kdf_export_ge_w_dev: ONE pass over h's table, at most `cap` entries written, *n_out = the number
+ * the join holds, KDF_ERR_INVALID when that exceeds cap (*n_out is still set, nothing is written past cap); unsorted
+ * unless sorted != 0, then ascending key order with both count columns following their keys (at most 2^32 entries for
+ * k > 32).  d_keys_hi_out may be NULL for k <= 32; either counts pointer may be NULL.  The host forms write ascending
+ * key order; with 0 < cap < the table's slot count (a cap from kdf_count_join) they stage cap entries and make one pass,
+ * any other cap has a counting pass size the staging first.  The (lo, hi) forms refuse a long engine and name the _w form, the _w forms (rows of W words) refuse an
+ * engine for k <= 63.
+ *
+ * KDF_ERR_INVALID before anything is launched: other == h, engines that differ in k or in device, min_count >
+ * max_count, and with other != NULL other_min > other_max.
+ *
+ * Both engines pass the gate of every table reader first: pending count passes are applied and a table that is still
+ * only logically empty is written (the dump-only flush of kdf_export_ge_dev is not used here).  other's stream is
+ * synchronised before the kernel is queued on h's stream, and the call returns with h's stream synchronised.  Neither
+ * table is modified: keys, counts, kdf_stats and a loaded filter's sieve stay valid.  Works with key_parts on either
+ * side (a table holds the slice it holds), with hash_shift on either side (k <= 63), in insert and in filter mode, and
+ * for any pair of capacities and bucket geometries.  Under kdf_profile(h, 1) the kernel (kdf_join_kernel /
+ * kdf_long_join_kernel, csrc/kdf_join.h) is timed with HIP events: stats "join_us" and "join_passes". */
+int kdf_count_join(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count,
+                   uint32_t other_min, uint32_t other_max, uint64_t *n_out);
+int kdf_export_join_dev(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count,
+                        uint32_t other_min, uint32_t other_max, void *d_keys_lo_out, void *d_keys_hi_out,
+                        void *d_counts_out, void *d_other_counts_out, uint64_t cap, int sorted, uint64_t *n_out);
+int kdf_export_join(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count,
+                    uint32_t other_min, uint32_t other_max, uint64_t *keys_lo_out, uint64_t *keys_hi_out,
+                    uint32_t *counts_out, uint32_t *other_counts_out, uint64_t cap, uint64_t *n_out);
+int kdf_export_join_w_dev(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count,
+                          uint32_t other_min, uint32_t other_max, void *d_keys_out, void *d_counts_out,
+                          void *d_other_counts_out, uint64_t cap, int sorted, uint64_t *n_out);
+int kdf_export_join_w(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count,
+                      uint32_t other_min, uint32_t other_max, uint64_t *keys_out, uint32_t *counts_out,
+                      uint32_t *other_counts_out, uint64_t cap, uint64_t *n_out);
+
 /* The multi-GPU exchange of the full count stage (Jellyfish `merge`,
  * core/jellyfish_wrappers.py:335-366, done over xGMI): dump every (key, count >= min_count)
  * pair to DEVICE arrays grouped by owner rank, owner(key) = ((hash(key) >> 48) * parts) >> 16

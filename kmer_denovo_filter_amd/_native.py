@@ -56,6 +56,11 @@ SYMBOLS = [
     ("kdf_count_stats", c_int, [_P, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_export_ge", c_int, [_P, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_export_ge_dev", c_int, [_P, c_uint32, _P, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
+    ("kdf_count_join", c_int, [_P, _P, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_uint64)]),
+    ("kdf_export_join_dev", c_int, [_P, _P, c_uint32, c_uint32, c_uint32, c_uint32, _P, _P, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
+    ("kdf_export_join", c_int, [_P, _P, c_uint32, c_uint32, c_uint32, c_uint32, _P, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_export_join_w_dev", c_int, [_P, _P, c_uint32, c_uint32, c_uint32, c_uint32, _P, _P, _P, c_uint64, c_int, POINTER(c_uint64)]),
+    ("kdf_export_join_w", c_int, [_P, _P, c_uint32, c_uint32, c_uint32, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_export_parts_dev", c_int, [_P, c_uint32, c_uint32, _P, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_export_parts_packed_dev", c_int, [_P, c_uint32, c_uint32, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_scan_reads", c_int, [_P, _P, _P, c_uint64, _P, c_int64, _P, _P]),

@@ -1,5 +1,5 @@
 // kdf_engine.hip -- libkdf.so, the core unit: the table, the direct kernels, the sieve, the host side of the binned
-// pipeline and the merge, the long-key paths, the counting sieve, the sketch, the device BAM feeder, and the engine's C
+// pipeline and the merge, the long-key paths, the table join, the counting sieve, the sketch, the device BAM feeder, and the engine's C
 // ABI of include/kdf.h (create and destroy, count, count --if, query, export, profile, options and stats).  The
 // per-read consumers live in kdf_engine_reads.hip, the read spool in kdf_spool.hip; kdf_engine_priv.h is what they
 // share.  See DESIGN.md for the data layout and the roofline of each kernel.  No CPU fallback exists in this library:
@@ -23,6 +23,8 @@
 #include "kdf_long.h"
 // ... across ranks: the dump grouped by owner rank, set_counts
 #include "kdf_long_merge.h"
+// table join: one table's entries by their count in another table
+#include "kdf_join.h"
 // the counting sieve of the two-pass count: tally, gate and fill kernels
 #include "kdf_prefilter.h"
 #include "kdf_sketch.h"
@@ -2911,6 +2913,186 @@ int kdf_export_ge_w(kdf_engine *h, uint32_t min_count, uint64_t *keys_out, uint3
     if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_ge_w: NULL pointer");
     KDF_NEED_LONG(h, "kdf_export_ge_w");
     return export_host(h, min_count, keys_out, nullptr, counts_out, cap, n_out, "kdf_export_ge_w", KDF_ERR_INVALID);
+}
+
+// ---- table join (kdf_join.h) -------------------------------------------------------------------------
+// the argument errors of every join entry point, before anything is launched
+static int join_refuse(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, const char *fn) {
+    if (o == h) return fail(h, KDF_ERR_INVALID, "%s: other is the engine itself (a table is not joined with itself)", fn);
+    if (a.min_count > a.max_count) return fail(h, KDF_ERR_INVALID, "%s: min_count %u > max_count %u", fn, a.min_count, a.max_count);
+    if (!o) return KDF_OK;
+    if (o->k != h->k) return fail(h, KDF_ERR_INVALID, "%s: the engines differ in k (%d and %d)", fn, h->k, o->k);
+    if (o->device != h->device) return fail(h, KDF_ERR_INVALID, "%s: the engines are on different devices (%d and %d)", fn, h->device, o->device);
+    if (a.other_min > a.other_max) return fail(h, KDF_ERR_INVALID, "%s: other_min %u > other_max %u", fn, a.other_min, a.other_max);
+    return KDF_OK;
+}
+
+// ONE pass over h's table: the selected entries are counted (write = false) or appended through the cursor (keys: the lo
+// array of k <= 63 or the rows of long keys); *n_out: how many the join holds.  Synchronises h's stream.
+static int join_pass(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, bool write, uint64_t *keys, uint64_t *hi, uint32_t *cnt,
+                     uint32_t *ocnt, uint64_t out_cap, uint64_t *n_out, const char *fn) {
+    int rc;
+    if ((rc = pending_flush(h)) || (rc = materialize(h))) return rc;
+    if (o) {                                                         // the same gate on the table that is probed
+        if ((rc = pending_flush(o)) || (rc = materialize(o))) return fail(h, rc, "%s: other: %s", fn, o->err.c_str());
+        HIPCHK(h, hipStreamSynchronize(o->stream));
+    }
+    HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor
+    const uint64_t per_wg = (uint64_t)KJ_THREADS * kj_rows(h->kw);
+    const unsigned blocks = (unsigned)((h->cap + per_wg - 1) / per_wg);
+    const KdfTable tb = o ? o->t : KdfTable{};
+    EvSpan span(h->timer[T_JOIN], h->prof, h->stream);
+    by_words(h, [&](auto Wc) {
+        constexpr int W = decltype(Wc)::value;
+        if constexpr (W > 2) {
+            if (write) hipLaunchKernelGGL((kdf_long_join_kernel<W, true>), dim3(blocks), dim3(KJ_THREADS), 0, h->stream, h->t, tb, a, h->ctl, keys, cnt, ocnt, out_cap);
+            else hipLaunchKernelGGL((kdf_long_join_kernel<W, false>), dim3(blocks), dim3(KJ_THREADS), 0, h->stream, h->t, tb, a, h->ctl, keys, cnt, ocnt, out_cap);
+        } else {
+            if (write) hipLaunchKernelGGL((kdf_join_kernel<W, true>), dim3(blocks), dim3(KJ_THREADS), 0, h->stream, h->t, tb, a, h->ctl, keys, hi, cnt, ocnt, out_cap);
+            else hipLaunchKernelGGL((kdf_join_kernel<W, false>), dim3(blocks), dim3(KJ_THREADS), 0, h->stream, h->t, tb, a, h->ctl, keys, hi, cnt, ocnt, out_cap);
+        }
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());                                    // (a launch that failed is not timed)
+    span.stop();
+    uint64_t cursor = 0;
+    if ((rc = ctl_sync(h, nullptr, &cursor))) return rc;
+    *n_out = cursor;
+    return KDF_OK;
+}
+
+// the join into device buffers, sorted if asked: the keys are sorted with h's counts, other's counts are looked up
+// again over the sorted keys
+static int join_core(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, uint64_t *keys, uint64_t *hi, uint32_t *cnt, uint32_t *ocnt,
+                     uint64_t cap, bool sorted, uint64_t *n_out, const char *fn) {
+    uint64_t n = 0;
+    int rc = join_pass(h, o, a, true, keys, hi, cnt, sorted ? nullptr : ocnt, cap, &n, fn);
+    if (rc) return rc;
+    *n_out = n;
+    if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
+    if (sorted && n) {
+        if (!cnt && !is_long(h)) {                                   // the pair sort carries a payload: a scratch one
+            if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
+            cnt = (uint32_t *)h->stage[0].p;
+            HIPCHK(h, hipMemsetAsync(cnt, 0, n * 4, h->stream));
+        }
+        std::string serr;
+        if (is_long(h) ? kdf_sort_rows_device(keys, h->kw, cnt, n, h->stream, serr) : kdf_sort_pairs_device(keys, hi, cnt, n, h->stream, serr))
+            return fail(h, KDF_ERR_HIP, "%s: sort failed: %s", fn, serr.c_str());
+        if (ocnt && !o) HIPCHK(h, hipMemsetAsync(ocnt, 0, n * 4, h->stream));
+        if (ocnt && o) {
+            const KdfTable tb = o->t;
+            by_words(h, [&](auto Wc) {
+                constexpr int W = decltype(Wc)::value;
+                for (uint64_t off = 0; off < n; off += 1ull << 30) {         // (a launch holds fewer than 2^32 threads)
+                    const uint64_t m = std::min<uint64_t>(1ull << 30, n - off);
+                    const unsigned blocks = (unsigned)((m + 255) / 256);
+                    if constexpr (W <= 2)
+                        hipLaunchKernelGGL(kdf_query_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, keys + off, W == 2 ? hi + off : nullptr, m, tb, ocnt + off);
+                    else
+                        hipLaunchKernelGGL(kdf_long_query_kernel<W>, dim3(blocks), dim3(256), 0, h->stream, keys + off * W, m, tb, ocnt + off, long_top_bits(h));
+                }
+                return 0;
+            });
+            HIPCHK(h, hipGetLastError());
+        }
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+// the host forms: the join is staged, sorted and copied back.  A cap below the table's slot count sizes the staging
+// buffers itself (the caller has counted: kdf_count_join) and the join is ONE pass; a cap that says nothing about the
+// size of the answer (0, or the slot count and more) has a counting pass size them first
+static int join_host(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, uint64_t *keys_out, uint64_t *hi_out, uint32_t *cnt_out,
+                     uint32_t *ocnt_out, uint64_t cap, uint64_t *n_out, const char *fn) {
+    uint64_t n = 0, room = cap;
+    int rc;
+    if (cap == 0 || cap >= h->cap) {
+        if ((rc = join_pass(h, o, a, false, nullptr, nullptr, nullptr, nullptr, 0, &n, fn))) return rc;
+        *n_out = n;
+        if (n == 0) return KDF_OK;
+        if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
+        room = n;
+    }
+    if (!keys_out || (h->kw == 2 && !hi_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL key output", fn);
+    if ((rc = eng_reserve(h, h->stage[2], room * 8 * lo_words(h)))) return rc;
+    if ((rc = eng_reserve(h, h->stage[0], room * 4))) return rc;
+    if ((rc = eng_reserve(h, h->stage[1], room * 4))) return rc;
+    if (h->kw == 2 && (rc = eng_reserve(h, h->stage[3], room * 8))) return rc;
+    rc = join_core(h, o, a, (uint64_t *)h->stage[2].p, h->kw == 2 ? (uint64_t *)h->stage[3].p : nullptr, (uint32_t *)h->stage[0].p,
+                   (uint32_t *)h->stage[1].p, room, true, &n, fn);
+    *n_out = n;
+    if (rc) return rc;                                               // (more than cap: *n_out says how many)
+    if (n == 0) return KDF_OK;
+    const size_t key_bytes = n * 8 * lo_words(h);
+    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[2].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
+    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
+    else if (hi_out) memset(hi_out, 0, n * 8);
+    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ocnt_out) HIPCHK(h, hipMemcpyAsync(ocnt_out, h->stage[1].p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return KDF_OK;
+}
+
+int kdf_count_join(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,
+                   uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_count_join: NULL pointer");
+    const KdfJoinArgs a{min_count, max_count, other_min, other_max, other ? 1 : 0};
+    int rc = join_refuse(h, other, a, "kdf_count_join");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return join_pass(h, other, a, false, nullptr, nullptr, nullptr, nullptr, 0, n_out, "kdf_count_join");
+}
+
+int kdf_export_join_dev(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,
+                        void *d_keys_lo_out, void *d_keys_hi_out, void *d_counts_out, void *d_other_counts_out, uint64_t cap, int sorted,
+                        uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_join_dev: NULL pointer");
+    KDF_REFUSE_LONG(h, "kdf_export_join_dev", "kdf_export_join_w_dev");
+    const KdfJoinArgs a{min_count, max_count, other_min, other_max, other ? 1 : 0};
+    int rc = join_refuse(h, other, a, "kdf_export_join_dev");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (cap && (!d_keys_lo_out || (h->kw == 2 && !d_keys_hi_out))) return fail(h, KDF_ERR_INVALID, "kdf_export_join_dev: NULL key output");
+    return join_core(h, other, a, (uint64_t *)d_keys_lo_out, h->kw == 2 ? (uint64_t *)d_keys_hi_out : nullptr, (uint32_t *)d_counts_out,
+                     (uint32_t *)d_other_counts_out, cap, sorted != 0, n_out, "kdf_export_join_dev");
+}
+
+int kdf_export_join(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,
+                    uint64_t *keys_lo_out, uint64_t *keys_hi_out, uint32_t *counts_out, uint32_t *other_counts_out, uint64_t cap,
+                    uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_join: NULL pointer");
+    KDF_REFUSE_LONG(h, "kdf_export_join", "kdf_export_join_w");
+    const KdfJoinArgs a{min_count, max_count, other_min, other_max, other ? 1 : 0};
+    int rc = join_refuse(h, other, a, "kdf_export_join");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return join_host(h, other, a, keys_lo_out, keys_hi_out, counts_out, other_counts_out, cap, n_out, "kdf_export_join");
+}
+
+int kdf_export_join_w_dev(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,
+                          void *d_keys_out, void *d_counts_out, void *d_other_counts_out, uint64_t cap, int sorted, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_join_w_dev: NULL pointer");
+    KDF_NEED_LONG(h, "kdf_export_join_w_dev");
+    const KdfJoinArgs a{min_count, max_count, other_min, other_max, other ? 1 : 0};
+    int rc = join_refuse(h, other, a, "kdf_export_join_w_dev");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (cap && !d_keys_out) return fail(h, KDF_ERR_INVALID, "kdf_export_join_w_dev: NULL key output");
+    return join_core(h, other, a, (uint64_t *)d_keys_out, nullptr, (uint32_t *)d_counts_out, (uint32_t *)d_other_counts_out, cap,
+                     sorted != 0, n_out, "kdf_export_join_w_dev");
+}
+
+int kdf_export_join_w(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,
+                      uint64_t *keys_out, uint32_t *counts_out, uint32_t *other_counts_out, uint64_t cap, uint64_t *n_out) {
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "kdf_export_join_w: NULL pointer");
+    KDF_NEED_LONG(h, "kdf_export_join_w");
+    const KdfJoinArgs a{min_count, max_count, other_min, other_max, other ? 1 : 0};
+    int rc = join_refuse(h, other, a, "kdf_export_join_w");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    return join_host(h, other, a, keys_out, nullptr, counts_out, other_counts_out, cap, n_out, "kdf_export_join_w");
 }
 
 // The sender's half of the owner exchange for long keys (kdf_long_merge.h): two passes over the table and one

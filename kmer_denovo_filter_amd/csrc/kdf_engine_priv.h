@@ -25,8 +25,8 @@ enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_stat
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
 enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_BD = BUF_VAR + 5, BUF_COUNT = BUF_BD + 3 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join"};
 struct kdf_engine {
     int device = 0;
     int k = 0;

@@ -107,6 +107,29 @@ def dump_ge(eng, min_count: int, device: int = 0):
     return lo[:n], (hi[:n] if hi is not None else None)
 
 
+def dump_join(eng, other, min_count: int, max_count: Optional[int] = None, other_min: int = 0, other_max: Optional[int] = 0,
+              device: int = 0):
+    """The keys of ``eng`` with min_count <= count <= max_count whose count in ``other`` lies in other_min..other_max
+    (``KmerEngine.count_join``; ``other=None``: ``dump -L min_count -U max_count``) into device tensors, ascending key
+    order like ``dump_ge``.  One pass over ``eng``'s table that probes ``other``'s: nothing but the answer is written."""
+    import torch
+    dev = torch.device("cuda", device)
+    n = eng.count_join(other, min_count, max_count, other_min, other_max)
+    if getattr(eng, "long", False):                      # (n, W) rows, no hi
+        lo = torch.empty((max(n, 1), eng.key_words), dtype=torch.int64, device=dev)
+        hi = None
+    else:
+        lo = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        hi = torch.empty(max(n, 1), dtype=torch.int64, device=dev) if eng.wide else None
+    cnt = torch.empty(max(n, 1), dtype=torch.int32, device=dev)      # (the device sort carries the counts along)
+    torch.cuda.current_stream(dev).synchronize()
+    got = eng.export_join_dev(other, min_count, max_count, other_min, other_max, lo.data_ptr(),
+                              hi.data_ptr() if hi is not None else None, cnt.data_ptr(), None, n, sorted_=True) if n else 0
+    if got != n:
+        raise RuntimeError(f"join dump: {got} entries written, {n} counted")
+    return lo[:n], (hi[:n] if hi is not None else None)
+
+
 def query(eng, lo, hi, device: int = 0):
     """``jellyfish query``: uint32 counts (as int64 values) of the keys, input order, on the device."""
     import torch

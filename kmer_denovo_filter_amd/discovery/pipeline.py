@@ -86,6 +86,11 @@ LAST_CHILD_SKETCH = None
 LAST_CHILD_SKETCH_REGISTERS = None
 
 
+# How the last _filter_parents_discovery took a parent's survivors: "query" (kdf_query_dev and a mask) or "join" (the table
+# join under KDF_DEVICE_JOIN=1); None before the first.  For logs and tests; nothing reads it to decide anything.
+LAST_PARENT_FILTER = None
+
+
 def _sketch_margin(log2_registers):
     """What a table sized from the sketch's estimate adds to it: five standard errors of HyperLogLog (1.04 / sqrt(m):
     8.1 % at p = 12, 2.0 % at p = 16) plus 5 % for the classic estimator's bias between 2.5 m and 5 m (kdf.h)."""
@@ -222,7 +227,8 @@ def _child_prefilter_min(min_child_count, world):
     return min(int(min_child_count), 3)
 
 
-def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start):
+def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start,
+                          dump=None):
     """`jellyfish bc` + `count --bc` made exact: stream the BAM twice -- tally every window into the counting sieve, arm,
     count -- so that only k-mers whose cell was seen >= L times get a table slot, each with its full count; then
     ``dump -L min_child_count`` as usual, one slice.  Returns the candidates (device keys), or None when the sieve plus the
@@ -254,7 +260,7 @@ def _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, thre
                     "%d of %d windows admitted, %d distinct stored, table %d slots)", _format_elapsed(time.monotonic() - extract_start),
                     L, log2_cells, fill[0], fill[1], fill[2], fill[3], windows, eng.get_stat("prefilter_windows"), distinct, cap)
         logger.info("Dumping child k-mers with count >= %d…", min_child_count)
-        dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
+        dlo, dhi = (dump or devkeys.dump_ge)(eng, min_child_count, eng.device)
         LAST_CHILD_COUNT = {"mode": "two_pass", "L": L, "log2_cells": log2_cells, "world": 1}
         return devkeys.select([(dlo, dhi)])
 
@@ -341,18 +347,18 @@ def _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_cou
                 e.close()
 
 
-def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_count, threads, tmpdir,
-                                   jf_hash_size=None):
-    """Module 1: count every canonical child k-mer, keep count >= min_child_count.
-
-    Returns (child_candidates_fa, n_candidates)."""
+def _count_and_dump_child(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, dump=None):
+    """The counting half of Module 1: count every canonical child k-mer (plain, in key slices, two-pass, sharded) and
+    take what ``dump(eng, min_child_count, device)`` gives of every slice's table -- ``devkeys.dump_ge`` (None: looked up
+    when it is called) for Module 1,
+    a join against the reference for the fused stage (_extract_child_non_ref_kmers; one rank only: the sharded paths
+    dump their owner tables with ``dump_ge``).  Returns (device key set, lo, hi, start of the last dump), ascending."""
     global LAST_CHILD_COUNT, LAST_CHILD_SKETCH, LAST_CHILD_SKETCH_REGISTERS
     LAST_CHILD_SKETCH = LAST_CHILD_SKETCH_REGISTERS = None
     if jf_hash_size is None:
         jf_hash_size = _estimate_jf_hash_size(child_bam, kmer_size, default="1G")
     logger.info("Extracting child k-mers from BAM (k=%d, jf hash size=%s)…", kmer_size, jf_hash_size)
     extract_start = time.monotonic()
-    child_candidates_fa = os.path.join(tmpdir, "child_candidates.fa")
     # A 30x human sample has ~10^10 distinct 31-mers (sequencing errors included): more than one table in
     # 288 GB of HBM holds.  KDF_KEY_PARTS = P counts the key space in P slices, one pass over the BAM each
     # (Jellyfish's answer to the same problem is to spill and merge hash files, jellyfish_wrappers.py:335-366).
@@ -364,8 +370,10 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
         cand = None
         LAST_CHILD_COUNT = {"mode": "plain", "L": 0, "log2_cells": 0, "world": world}
         if _child_prefilter_min(min_child_count, world):
-            two_pass = _child_count_two_pass if world == 1 else _child_count_two_pass_sharded
-            cand = two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start)
+            if world == 1:
+                cand = _child_count_two_pass(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start, dump)
+            else:
+                cand = _child_count_two_pass_sharded(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, extract_start)
         if cand is not None:
             lo, hi = devkeys.to_host(*cand)
         else:
@@ -405,7 +413,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
                     # the dump stays in HBM for the next stage (ascending keys: Jellyfish's dump order is not reproducible and
                     # nothing downstream relies on it, but the contract files are then the same bytes on every run)
                     if merger is None:
-                        dlo, dhi = devkeys.dump_ge(eng, min_child_count, eng.device)
+                        dlo, dhi = (dump or devkeys.dump_ge)(eng, min_child_count, eng.device)
                     else:
                         merger.exchange()
                         dlo, dhi = devkeys.dump_ge(owner_eng, min_child_count, eng.device)
@@ -425,6 +433,17 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
         order = keys.order(keys.from_pair(lo, hi, kmer_size))
         lo, hi = lo[order], (hi[order] if hi is not None else None)   # (long keys: rows, no hi)
         cand = devkeys.select([cand], torch.from_numpy(order).to(cand[0].device))
+    return cand, lo, hi, dump_start
+
+
+def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_count, threads, tmpdir,
+                                   jf_hash_size=None):
+    """Module 1: count every canonical child k-mer, keep count >= min_child_count.
+
+    Returns (child_candidates_fa, n_candidates)."""
+    child_candidates_fa = os.path.join(tmpdir, "child_candidates.fa")
+    cand, lo, hi, dump_start = _count_and_dump_child(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size)
+    rank = dist_env.world_rank()[1]
     n_candidates = len(lo)
     if rank == 0:
         write_kmer_fasta(child_candidates_fa, lo, hi, kmer_size)
@@ -483,6 +502,58 @@ def _subtract_reference_kmers(ref_jf, child_candidates_fa, tmpdir):
     devkeys.forget(child_candidates_fa)
     logger.info("Non-reference child k-mers after subtraction: %d", n_non_ref)
     return child_non_ref_fa, n_non_ref
+
+
+def _extract_child_non_ref_kmers(child_bam, ref_fasta, ref_jf, kmer_size, min_child_count, threads, tmpdir,
+                                 jf_hash_size=None):
+    """Module 1 and the reference subtraction in one call (opt-in): the reference index is loaded into
+    an engine first, the child is counted exactly as _extract_child_kmers_discovery counts it, and every slice's table
+    is dumped by a join against the reference's (``devkeys.dump_join``: count >= min_child_count here, count 0 there)
+    in place of ``dump -L``.  ``child_candidates.fa`` is never written; ``child_non_ref_kmers.fa`` is, with the bytes
+    the two stages write.  Several ranks: the two stages run in turn.
+
+    Returns (child_non_ref_fa, n_candidates, n_non_ref)."""
+    world, rank, host = dist_env.world_rank()
+    if world > 1:
+        logger.info("Fused extract-and-subtract stage under %d ranks: running Module 1 and the reference subtraction in turn", world)
+        cand_fa, n_candidates = _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_count, threads, tmpdir,
+                                                               jf_hash_size)
+        child_non_ref_fa, n_non_ref = _subtract_reference_kmers(ref_jf, cand_fa, tmpdir)
+        return child_non_ref_fa, n_candidates, n_non_ref
+    child_non_ref_fa = os.path.join(tmpdir, "child_non_ref_kmers.fa")
+    ref_eng = None
+    try:
+        try:
+            k = _index_k(ref_jf)
+            if k != int(kmer_size):
+                raise ValueError(f"{ref_jf} is an index of {k}-mers, the child is counted at k={kmer_size}")
+            # loaded BEFORE the child is planned: the slice planner and the spool budget read the HBM that is free then,
+            # which no longer holds the reference table's bytes
+            ref_eng = mirror_engine(k, capacity_hint=max(jf_io.index_records(ref_jf), 1), device=_device())
+            jf_io.load_index_into(ref_eng, ref_jf)
+            ref_eng.flush()
+            logger.info("Reference index loaded for the join: %d k-mers, table %d slots", ref_eng.stats()[1], ref_eng.stats()[0])
+        except (KdfError, ValueError, OSError) as e:
+            raise RuntimeError(f"jellyfish query (ref subtraction) failed: {e}") from e
+        seen = {"candidates": 0}
+
+        def dump(eng, min_count, device):
+            n = eng.count_ge(min_count)
+            seen["candidates"] += n
+            logger.info("Child candidate k-mers (count >= %d) in this table: %d; joining against the reference…", min_count, n)
+            return devkeys.dump_join(eng, ref_eng, min_count, None, 0, 0, device)
+
+        cand, lo, hi, dump_start = _count_and_dump_child(child_bam, ref_fasta, kmer_size, min_child_count, threads, jf_hash_size, dump)
+    finally:
+        if ref_eng is not None:
+            ref_eng.close()
+    n_candidates, n_non_ref = seen["candidates"], len(lo)
+    write_kmer_fasta(child_non_ref_fa, lo, hi, kmer_size)
+    devkeys.register(child_non_ref_fa, *cand, kmer_size)
+    logger.info("Child k-mer join complete (%s, %d candidates, FASTA: %s)", _format_elapsed(time.monotonic() - dump_start),
+                n_candidates, _format_file_size(child_non_ref_fa))
+    logger.info("Non-reference child k-mers after subtraction: %d", n_non_ref)
+    return child_non_ref_fa, n_candidates, n_non_ref
 
 
 def _count_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent_dir, threads,
@@ -566,11 +637,21 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
         return 0, None
     logger.info("Filtering %d non-reference k-mers against parents…", n_input)
 
+    global LAST_PARENT_FILTER
+    device_join = os.environ.get("KDF_DEVICE_JOIN") == "1" and dist_env.world_rank()[0] == 1
+    LAST_PARENT_FILTER = "join" if device_join else "query"
+
     def one_parent(bam, label, dlo, dhi):
         os.makedirs(os.path.join(tmpdir, label.lower()), exist_ok=True)
         try:
             eng = _count_parent_on_device(bam, ref_fasta, dlo, dhi, kmer_size, threads, label)
             try:
+                if device_join:
+                    # `dump -U parent_max_count` of the parent's table: it holds exactly the filter keys (never-seen ones with
+                    # count 0), so the join without a second table is the survivors -- in ASCENDING key order, which is the
+                    # input's order whenever the input is a stage's sorted dump; an input in another order (Module 1 in key
+                    # slices, a FASTA written elsewhere) keeps its order only on the default path
+                    return devkeys.select([devkeys.dump_join(eng, None, 0, parent_max_count, device=eng.device)])
                 keep = devkeys.query(eng, dlo, dhi, eng.device) <= parent_max_count
             finally:
                 eng.close()

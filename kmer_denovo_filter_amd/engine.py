@@ -8,6 +8,7 @@ shells out to ("External op" table):
     count_filtered(stream)   jellyfish count -m k -C --if ...
     export_ge(n)             jellyfish dump -c -L n             (ascending keys)
     histogram(high)          jellyfish histo -h high
+    export_join(other, ...)  jellyfish dump -L a -U b, kept by the count in another table (ascending keys)
     count_stats()            jellyfish stats
     prefilter_*()            jellyfish bc + count --bc          (exact: two passes)
     sketch_*()               (no Jellyfish call) distinct k-mers of a stream, estimated without storing them
@@ -503,6 +504,58 @@ class KmerEngine:
                                              c_void_p(d_cnt) if d_cnt else None, int(cap),
                                              1 if sorted_ else 0, byref(n)))
         return n.value
+
+    # -- table join (kdf.h "Table join") -----------------------------------
+    UNBOUNDED = 0xFFFFFFFF     # an upper bound of the join that bounds nothing
+
+    def _join_args(self, other, min_count, max_count, other_min, other_max):
+        if other is not None and not isinstance(other, KmerEngine):
+            raise TypeError("other must be a KmerEngine or None")
+        ub = lambda v: self.UNBOUNDED if v is None else int(v)      # noqa: E731
+        return (self._h, other._h if other is not None else None, int(min_count), ub(max_count), int(other_min), ub(other_max))
+
+    def count_join(self, other: Optional["KmerEngine"], min_count: int = 1, max_count: Optional[int] = None,
+                   other_min: int = 0, other_max: Optional[int] = 0) -> int:
+        """Number of stored keys with min_count <= count <= max_count whose count in ``other`` (0: absent there, or
+        stored with count 0) lies in other_min..other_max; every bound inclusive, None as an upper bound: none.
+        ``other=None``: the other bounds are ignored (``jellyfish dump -L min_count -U max_count``)."""
+        n = c_uint64(0)
+        self._ck(self._lib.kdf_count_join(*self._join_args(other, min_count, max_count, other_min, other_max), byref(n)))
+        return n.value
+
+    def export_join_dev(self, other: Optional["KmerEngine"], min_count: int, max_count: Optional[int], other_min: int,
+                        other_max: Optional[int], d_lo: int, d_hi: Optional[int], d_cnt: Optional[int],
+                        d_other_cnt: Optional[int], cap: int, sorted_: bool = False) -> int:
+        """The join into caller-owned device buffers (the count_join selection; long engines: d_lo holds
+        cap x key_words row-major words, d_hi is ignored); returns the number of entries.  More than ``cap`` raise."""
+        n = c_uint64(0)
+        args = self._join_args(other, min_count, max_count, other_min, other_max)
+        p = lambda v: c_void_p(v) if v else None                    # noqa: E731
+        if self.long:
+            self._ck(self._lib.kdf_export_join_w_dev(*args, p(d_lo), p(d_cnt), p(d_other_cnt), int(cap), 1 if sorted_ else 0, byref(n)))
+        else:
+            self._ck(self._lib.kdf_export_join_dev(*args, p(d_lo), p(d_hi), p(d_cnt), p(d_other_cnt), int(cap), 1 if sorted_ else 0,
+                                                   byref(n)))
+        return n.value
+
+    def export_join(self, other: Optional["KmerEngine"], min_count: int = 1, max_count: Optional[int] = None,
+                    other_min: int = 0, other_max: Optional[int] = 0):
+        """(keys, counts, other_counts) of the join, ascending key order; keys: (lo, hi) for k <= 63, (n, key_words)
+        rows for long engines.  Two passes over the table: count_join sizes the arrays, the host form writes."""
+        args = self._join_args(other, min_count, max_count, other_min, other_max)
+        n = self.count_join(other, min_count, max_count, other_min, other_max)
+        cnt, ocnt = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        got = c_uint64(0)
+        if self.long:
+            keys = np.zeros((n, self.key_words), np.uint64)
+            self._ck(self._lib.kdf_export_join_w(*args, _vp(keys), _vp(cnt), _vp(ocnt), n, byref(got)))
+        else:
+            lo, hi = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+            self._ck(self._lib.kdf_export_join(*args, _vp(lo), _vp(hi), _vp(cnt), _vp(ocnt), n, byref(got)))
+            keys = (lo, hi)
+        if got.value != n:
+            raise _native.KdfError(_native.KDF_ERR_STATE, "join size changed between passes")
+        return keys, cnt, ocnt
 
     def export_parts_dev(self, min_count: int, parts: int, d_lo: int, d_hi: Optional[int], d_cnt: Optional[int],
                          cap: int):
