@@ -363,7 +363,7 @@ __global__ __launch_bounds__(256) void kb_groupsum_kernel(KbPlan plan, KbScratch
     }
     part[threadIdx.x] = acc;
     __syncthreads();
-    if (q == 0 && c < nb) s.gn[(uint64_t)g * nb + c] = part[threadIdx.x] + part[threadIdx.x + 64] + part[threadIdx.x + 128] + part[threadIdx.x + 192];
+    if (q == 0 && c < nb) s.gn[((uint64_t)g << plan.c1) + c] = part[threadIdx.x] + part[threadIdx.x + 64] + part[threadIdx.x + 128] + part[threadIdx.x + 192];
     if (g == 0 && blockIdx.y == 0 && threadIdx.x == 0) s.ovf[0] = 0;
 }
 
@@ -373,11 +373,11 @@ template <int CHUNK>
 __global__ __launch_bounds__(256) void kb_binscan_kernel(KbPlan plan, KbScratch s) {
     __shared__ uint32_t wsum[32];
     __shared__ unsigned long long esum[256];
-    const uint32_t nb = 1u << plan.c1, c = blockIdx.x;
+    const uint32_t c = blockIdx.x;
     uint32_t carry_r = 0; unsigned long long carry_e = 0;
     for (uint32_t g0 = 0; g0 < plan.n_groups; g0 += 256) {
         const uint32_t g = g0 + threadIdx.x;
-        const uint64_t pair = (uint64_t)g * nb + c;
+        const uint64_t pair = ((uint64_t)g << plan.c1) + c;
         const uint32_t n = g < plan.n_groups ? s.gn[pair] : 0u, np = (n + CHUNK - 1) / CHUNK;
         uint32_t tot = 0;
         const uint32_t ex = kb_block_exscan(np, wsum, &tot);
@@ -458,7 +458,7 @@ __device__ __forceinline__ void kb_sort_piece(const KbPlan &plan, const KbScratc
     unsigned long long *rsrc = (unsigned long long *)(wsum + 32);       // [KB_G_MAX] entry index in tmp of the run's first entry MINUS the run's position in the pair
     uint32_t *rpre = (uint32_t *)(rsrc + KB_G_MAX);                     // [KB_G_MAX + 4] position of the run's first entry in the pair's sequence; padded with the total
     const uint32_t nb = 1u << plan.c1;
-    const uint32_t g = pair / nb, c = pair % nb;
+    const uint32_t g = pair >> plan.c1, c = pair & (nb - 1);           // (nb is a power of two; c1 == 0: g = pair, c = 0)
     const uint32_t n_pair = s.gn[pair];
     if (n_pair <= p * (uint32_t)CHUNK) return;                          // an empty pair has no piece (uniform)
     const uint32_t lo_ = p * (uint32_t)CHUNK, len = min((uint32_t)CHUNK, n_pair - lo_);   // the piece is [lo_, lo_ + len) of the pair's entries
@@ -499,8 +499,7 @@ __device__ __forceinline__ void kb_sort_piece(const KbPlan &plan, const KbScratc
         unsigned long long cs = 0;
         if (wbase < len) {
             const uint32_t e = lo_ + wbase;
-            uint32_t gu = (uint32_t)(((unsigned long long)e * ns) / n_pair);           // runs have nearly equal lengths: interpolate, then walk
-            gu = gu < ns ? gu : ns - 1;
+            uint32_t gu = kb_guess_run(e, ns, n_pair);                  // runs have nearly equal lengths: interpolate (kdf_device.h), then walk
             while (rpre[gu] > e) --gu;
             while (rpre[gu + 1] <= e) ++gu;                             // (rpre[ns] = n_pair > e: stops at the last run)
             cr = gu; cnx = rpre[cr + 1]; cs = rsrc[cr];
@@ -689,7 +688,7 @@ struct KbPipe {
         {
             const uint32_t npair = o_ok ? kb_uni(o_npair) : 0u;
             if (npair) {                                                  // (uniform) an empty pair has no piece
-                const uint32_t g = o_pair / nb;
+                const uint32_t g = o_pair >> plan.c1;
                 const uint64_t s0 = (uint64_t)g * plan.group;
                 const uint32_t ns = (uint32_t)min((uint64_t)plan.group, (uint64_t)plan.n_slabs - s0);
                 const uint32_t sa = 2 * tid;                              // this thread's two consecutive slabs
@@ -765,15 +764,17 @@ struct KbPipe {
             const uint32_t pair = xcd * eighth + jj;
             o_ok = i3 >= 0 && i3 < n_it && jj < eighth && pair < n_pairs;
             const uint32_t pc = o_ok ? pair : 0u;                         // (nothing to do: pair 0 is read, and ignored)
-            const uint32_t g = pc / nb, c = pc % nb;
+            const uint32_t g = pc >> plan.c1, c = pc & (nb - 1);
             const uint64_t s0 = (uint64_t)g * plan.group;
             const uint32_t ns = (uint32_t)min((uint64_t)plan.group, (uint64_t)plan.n_slabs - s0);
             o_pair = pc;
             o_npair = s.gn[pc]; o_rowoff = s.gpre_row[pc]; o_entoff = s.gpre_ent[pc];
             o_binrow = P->binrow_first[c]; o_binent = P->binent_first[c];
             const uint32_t ta = 2 * tid < ns ? 2 * tid : 0u, tb = 2 * tid + 1 < ns ? 2 * tid + 1 : 0u;
-            __builtin_memcpy(&o_raw, s.off + (s0 + ta) * (uint64_t)(nb + 1) + c, 4);    // off[c], off[c + 1] of its two slabs: split where they are used
-            __builtin_memcpy(&o_raw2, s.off + (s0 + tb) * (uint64_t)(nb + 1) + c, 4);
+            // (the group's first row is a scalar 64-bit product; ta, tb < KB_G_MAX and nb <= 2^KB_C1_MAX: the lane's part fits 32 bits)
+            const uint16_t *orow = s.off + s0 * (uint64_t)(nb + 1) + c;
+            __builtin_memcpy(&o_raw, orow + ta * (nb + 1), 4);                          // off[c], off[c + 1] of its two slabs: split where they are used
+            __builtin_memcpy(&o_raw2, orow + tb * (nb + 1), 4);
         }
         // ---- (d) gather of piece it + 2 into the registers piece `it` has left: all loads of a lane in flight together
         {
@@ -781,8 +782,7 @@ struct KbPipe {
             uint32_t cr = 0, cnx = 0; unsigned long long cs = 0;
             if (wbase < glen) {
                 const uint32_t e = wbase;
-                uint32_t gu = (uint32_t)(((unsigned long long)e * r_ns) / r_npair);
-                gu = gu < r_ns ? gu : r_ns - 1;
+                uint32_t gu = kb_guess_run(e, r_ns, r_npair);
                 while (rpre[gu] > e) --gu;
                 while (rpre[gu + 1] <= e) ++gu;
                 cr = gu; cnx = rpre[cr + 1]; cs = rsrc[cr];
@@ -1078,7 +1078,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
         }
     }
     KB_T(s.trash, 30);                                        // slice initialised (or its loads issued)
-    const uint32_t n_runs = ri.setup(plan, s, c);             // (barrier inside)
+    const uint32_t n_runs = kb_uni(ri.setup(plan, s, c));     // (barrier inside; an LDS word, the same in every lane: a scalar, like `total` below)
     KB_T(s.trash, 31);                                        // pass descriptors
 
     constexpr uint32_t WQ = QCAP / (CT / 64);
@@ -1099,6 +1099,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
         uint32_t total = 0;
         KB_T(s.trash, 32);                                    // run bounds requested
         const uint32_t ex = kb_block_exscan(len, wsum, &total);
+        total = kb_uni(total);                                // (read from LDS, the same in every lane: a scalar, as the integer division made it)
         KB_T(s.trash, 33);                                    // ... arrived, scanned
         if constexpr (VAR == 2) {
             // A heavy bucket (a few keys of enormous multiplicity) is not for ONE workgroup: it is left untouched here, as
@@ -1130,10 +1131,13 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
         if (threadIdx.x < 3) rpw[RUNS + 1 + threadIdx.x] = total;
         if (threadIdx.x == 0) rpw[0] = 0;
         __syncthreads();
-        const uint32_t nruns = n_runs - rb < (uint32_t)RUNS ? n_runs - rb : (uint32_t)RUNS;
+        const uint32_t nruns = kb_uni(n_runs - rb < (uint32_t)RUNS ? n_runs - rb : (uint32_t)RUNS);
         constexpr int EPB = KW == 2 ? KB_C_EPB_W : KB_C_EPB_N;    // entries per thread per batch: EPB (x KW) loads in flight per lane
-        // (ei * inv_total) >> 32 ~= ei * nruns / total
-        const unsigned long long inv_total = total ? (((unsigned long long)nruns << 32) / total) : 0;
+        // (ei * inv_total) >> 32 ~= ei * nruns / total, from a float reciprocal (kdf_device.h).  The integer division it replaces
+        // was expanded into ~115 instructions, once per round in every wave, nearly all of them on the CU's one scalar unit --
+        // which also kept n_runs, nruns and total in scalar registers: float arithmetic is vector only, so they are made
+        // scalars by hand here (left to the compiler they took up to three vector registers for the whole kernel)
+        const unsigned long long inv_total = kb_uni64(kb_guess_scale(nruns, total));
         for (uint32_t e0 = 0; e0 < total; e0 += CT * EPB) {   // wave-uniform trip count
           uint64_t bklo[EPB], bkhi[KW == 2 ? EPB : 1];
           // Flat index of this thread's q-th entry of the batch.  Narrow keys: a WAVE takes 64 * EPB
@@ -1148,8 +1152,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             uint32_t cr = 0, cpf = 0, cnx = 0;                 // current run: index, first flat entry, first entry of the next run
             if (wbase < total) {
                 const uint32_t ei = wbase;
-                uint32_t gu = (uint32_t)(((unsigned long long)ei * inv_total) >> 32);
-                gu = gu < nruns ? gu : nruns - 1;
+                const uint32_t gu = kb_guess_scaled(ei, inv_total, nruns);
                 const uint32_t w0 = rpw[gu], w1 = rpw[gu + 1], w2 = rpw[gu + 2], w3 = rpw[gu + 3];
                 const uint32_t cnt = (w1 <= ei) + (w2 <= ei) + (w3 <= ei);
                 uint32_t lo_ = gu + cnt - 1;                                 // cnt == 0: the run before the guess
@@ -1189,8 +1192,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const uint32_t ei = wbase + QSTEP * (q0 + g);
-                    uint32_t gu = (uint32_t)(((unsigned long long)ei * inv_total) >> 32);
-                    gu = ei < total ? (gu < nruns ? gu : nruns - 1) : 0;
+                    const uint32_t gu = ei < total ? kb_guess_scaled(ei, inv_total, nruns) : 0;
                     gs[g] = gu;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) w[g][i] = rpw[gu + i];

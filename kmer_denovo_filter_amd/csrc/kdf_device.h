@@ -29,6 +29,46 @@ KDF_HD KdfStreamGeom kdf_stream_geom(uint64_t n_bases) {
     return KdfStreamGeom{T, 2 * T + 4, T + 2};
 }
 
+// Run guesses of the binned path (kdf_binned.h): which of `nruns` runs of nearly equal length holds entry `ei` of the
+// `total` entries they hold together -- about ei * nruns / total.  A guess is only where a search starts (kernel C: a
+// window of four run bounds, then a walk; the piece sort: a walk), so it is taken from a FLOAT reciprocal: the integer
+// divisions this replaces were expanded by the compiler into ~115 instructions per wave and round of kernel C (most of them
+// on the scalar unit) and ~130 per piece in the pipelined piece sort.
+// Error: the conversions, the reciprocal (v_rcp_f32: 1 ulp) and the products are 3 * 2^-23 relative at most, on a
+// quotient below 2^11 -- under 2^-9 of a run, so a guess is the exact quotient's floor or one beside it (checked
+// against integer division, with the reciprocal one ulp off either way: tests/native/run_guess_check.cpp).
+// The *_rcp forms take the reciprocal, for that check; a zero divisor gives 0, never a NaN or an infinity.
+KDF_HD float kdf_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf(x);
+#else
+    return 1.0f / x;
+#endif
+}
+// the 32.32 fixed-point factor nruns / total (nruns <= 2^10: below 2^43)
+KDF_HD unsigned long long kb_guess_scale_rcp(uint32_t nruns, float rcp_total) {
+    const float q = (float)nruns * rcp_total;                              // nruns / total
+    const uint32_t hi = (uint32_t)q;
+    const uint32_t lo = (uint32_t)((q - (float)hi) * 4294967296.0f);     // (the difference is exact and below 1: two 32-bit conversions
+    return ((unsigned long long)hi << 32) | lo;                            // instead of the compiler's float-to-64-bit sequence)
+}
+KDF_HD unsigned long long kb_guess_scale(uint32_t nruns, uint32_t total) {
+    return total ? kb_guess_scale_rcp(nruns, kdf_rcp((float)total)) : 0ull;
+}
+// entry ei < total (nruns >= 1) -> a run in [0, nruns - 1]
+KDF_HD uint32_t kb_guess_scaled(uint32_t ei, unsigned long long scale, uint32_t nruns) {
+    const uint32_t gu = (uint32_t)(((unsigned long long)ei * scale) >> 32);
+    return gu < nruns ? gu : nruns - 1;
+}
+// entry e < n_pair of a pair's ns >= 1 runs (ns <= 2^11) -> a run in [0, ns - 1]
+KDF_HD uint32_t kb_guess_run_rcp(uint32_t e, uint32_t ns, float rcp_npair) {
+    const uint32_t gu = (uint32_t)((float)e * ((float)ns * rcp_npair));
+    return gu < ns ? gu : ns - 1;
+}
+KDF_HD uint32_t kb_guess_run(uint32_t e, uint32_t ns, uint32_t n_pair) {
+    return n_pair ? kb_guess_run_rcp(e, ns, kdf_rcp((float)n_pair)) : 0u;
+}
+
 #if defined(__HIP__)                        // everything below is device code
 
 // ---------------------------------------------------------------------------
