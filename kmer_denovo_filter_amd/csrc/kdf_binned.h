@@ -1561,7 +1561,9 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
 
 // Replay of the buckets kernel C flagged (s.failed): their entries go through the global-atomic path into table t,
 // which the host has grown since.  `plan` is the geometry the failed flush ran with (bucket numbering of s.failed).
-template <int KW>
+// INS = false: the replay of a count --if flush -- the table is as it was (the keys stay put, nothing grows), an entry
+// whose key is not stored counts nothing, exactly as in the direct filtered kernel.
+template <int KW, bool INS = true>
 __global__ __launch_bounds__(256) void kb_replay_kernel(KbPlan plan, KbScratch s, KdfTable t, KdfCtl *ctl) {
     __shared__ __attribute__((aligned(16))) char rmem[KB_RI_LDS_BYTES];
     const uint64_t bucket = blockIdx.x;
@@ -1582,8 +1584,8 @@ __global__ __launch_bounds__(256) void kb_replay_kernel(KbPlan plan, KbScratch s
             if (plan.sub_bits && ((klo >> hsh_r) >> plan.bucket_bits) != bucket) todo = false;   // sibling bucket's entry
             const uint64_t slot = kdf_home(t, klo);
             bool ok = true;
-            if constexpr (KW == 1) { if (todo) ok = kdf_add_narrow<true>(t, klo, 1u, slot, t.lo[slot], claimed); }
-            else ok = kdf_add_wide<true>(t, todo, klo, khi, 1u, slot, claimed);
+            if constexpr (KW == 1) { if (todo) ok = kdf_add_narrow<INS>(t, klo, 1u, slot, t.lo[slot], claimed); }
+            else ok = kdf_add_wide<INS>(t, todo, klo, khi, 1u, slot, claimed);
             if (!ok) failed = true;
         }
     }

@@ -1048,7 +1048,20 @@ static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
     h->stat_heavy_buckets += h->kb_totals_host[4];
     const uint64_t n_failed = h->kb_totals_host[2];
     if (n_failed) {
-        if (filtered) { (void)kb_ring_reset(h); return fail(h, KDF_ERR_STATE, "binned count --if: a bucket failed (corrupt table?)"); }
+        if (filtered) {
+            // count --if: kernel C left these buckets as they were in HBM (a stored wide key whose hash word is the empty
+            // marker; a full bucket probed for an absent key).  Their entries go through the direct filtered probe: the
+            // keys stay put, the table does not grow, absent keys count nothing.
+            h->stat_replayed_buckets += n_failed;
+            by_width(h, [&](auto KWc) {
+                hipLaunchKernelGGL((kb_replay_kernel<decltype(KWc)::value, false>), dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
+                return 0;
+            });
+            HIPCHK(h, hipGetLastError());
+            if ((rc = ctl_sync(h, &full))) { (void)kb_ring_reset(h); return rc; }
+            if (full) { (void)kb_ring_reset(h); return fail(h, KDF_ERR_TABLE_FULL, "binned count --if: bucket overflow during replay (capacity 2^%u)", h->t.log2cap); }
+            return kb_ring_reset(h);
+        }
         // some buckets overflowed: they are untouched in HBM.  Grow the table so
         // that even if every entry of the failed buckets were new the load stays
         // <= 0.5, then replay exactly those buckets through the global-atomic path.

@@ -724,6 +724,64 @@ def test_an_overfull_bucket_is_table_full_and_clear_recovers(k):
         e.close()
 
 
+@pytest.mark.parametrize("k", (47, 63))
+def test_keys_that_share_all_64_hash_bits(k, senders):
+    """Wide keys are stored as (h, hi), and different keys can share h (merge_truth.collision_group): groups of 2, 3 and
+    65 such keys have one owner, one order key and one home slot whatever `parts` and the table are, and only hi tells
+    them apart -- in the dump's compaction, and in the merge kernels' probe (km_probe_wide_once) and claim."""
+    rng = np.random.default_rng(900 + k)
+    groups = []
+    for n in (2, 3, 65):
+        h = int(rng.integers(0, 1 << 63, dtype=np.uint64)) * 2 + 1
+        groups.append(T.collision_group(h, n + 1, k, rng))
+        assert (T.key_hash(*groups[-1]) == np.uint64(h)).all()
+    # the mirror: 40 keys with ONE hi whose hashes differ below their top 28 bits -- one home slot here and in the owner
+    # tables, one owner; only the stored hash word tells them apart
+    groups.append(T.keys_sharing_hi(int(rng.integers(0, 1 << 28)), 28, 41, k, rng))
+    assert len(set(groups[-1][1].tolist())) == 1 and len(set(T.home(T.key_hash(*groups[-1]), 28).tolist())) == 1
+    held = join([(g[0][:1], g[1][:1]) for g in groups])                 # one member of each group is never stored
+    mlo, mhi = join([(g[0][1:], g[1][1:]) for g in groups])
+    plo, phi = random_keys(rng, k, 3000)
+    lo, hi = np.concatenate([mlo, plo]), np.concatenate([mhi, phi])
+    cnt = (1 + np.arange(len(lo)) % 250).astype(np.uint32)              # the members: 1, 2, 3, ...
+    cnt[::11] = 0
+    cnt[1] = U32_MAX
+    e = senders(k)
+    fill(e, lo, hi, cnt)
+    truth = T.merge([(lo, hi, cnt)])
+    assert len(truth[0]) == len(lo) and not e.query(*held).any()
+    for parts in (1, 3, 7, 64):
+        assert all(len(set(T.owner(T.key_hash(*g), parts).tolist())) == 1 for g in groups)
+        for mc in (0, 1, 3):
+            check_dump(e, parts, mc, truth)
+    # the owner's merge: segments that hold different members of each group and repeat some
+    m = len(mlo)
+    pick = lambda idx, pad: (np.concatenate([mlo[idx], plo[pad]]), np.concatenate([mhi[idx], phi[pad]]))   # noqa: E731
+    idx = np.arange(m)
+    parts_ = [pick(idx[idx % 2 == 0], slice(0, 1500)), pick(idx[idx % 2 == 1], slice(1000, 2500)),
+              pick(np.concatenate([idx[idx % 3 == 0], idx[idx % 3 == 0][:7]]), slice(2400, 3000))]            # seven members twice in one segment
+    segs = [(a, b, (1 + (np.arange(len(a)) * (s + 3)) % 97).astype(np.uint32)) for s, (a, b) in enumerate(parts_)]
+    segs[2][2][:5] = 0x60000000
+    own = owner_engine(k, 1 << 13)
+    try:
+        geo = geometry(own)
+        merge_call(own, [in_bucket_order(s, geo) for s in segs])
+        assert geometry(own) == geo and own.get_stat("last_merge_path") == 1
+        fresh = T.merge(segs)
+        check_table(own, fresh, held)
+        more = [(segs[1][0], segs[1][1], np.full(len(segs[1][0]), 0x60000000, np.uint32)), segs[2], segs[0]]
+        merge_call(own, [in_bucket_order(s, geo) for s in more])        # into the live table
+        assert geometry(own) == geo and own.get_stat("last_merge_path") == 1
+        live = T.merge([fresh] + more)
+        assert (live[2] == U32_MAX).any()
+        check_table(own, live, held)
+        merge_call(own, [segs[0]])                                       # as drawn, not grouped: the atomic kernel
+        assert own.get_stat("last_merge_path") == 2
+        check_table(own, T.merge([live, segs[0]]), held)
+    finally:
+        own.close()
+
+
 @pytest.mark.parametrize("world", (2, 3, 4))
 @pytest.mark.parametrize("k", KS)
 def test_a_whole_exchange_on_one_gpu(k, world, senders):

@@ -283,6 +283,35 @@ def test_full_hash_collisions_long(k):
         _check(b, a, tb, ta, ((1, MAX, 0, 0), (1, MAX, 1, MAX)), f"k={k} reversed")
 
 
+@pytest.mark.parametrize("k", (33, 47, 63))
+def test_full_hash_collisions_wide(k):
+    """The wide twin: two groups per k whose members share all 64 bits of the stored hash word and differ in hi only
+    (k = 33: the four keys a hash has; else nine); B lacks one member of each, which A's probe of B must report absent
+    although B holds its h."""
+    rng = np.random.default_rng(k)
+    n = 4 if k == 33 else 9
+    groups = [MT.collision_group(int(T._rand64(rng, 1)[0]), n, k, rng) for _ in range(2)]
+    for lo, hi in groups:
+        assert len(set(MT.key_hash(lo, hi).tolist())) == 1 and len(set(hi.tolist())) == n
+    plo, phi = MT.keys_with_hash(0, 0, 200, k, rng)
+    lo = np.concatenate([g[0] for g in groups] + [plo])
+    hi = np.concatenate([g[1] for g in groups] + [phi])
+    ka = J.keys_of(lo, hi)
+    assert len(set(ka)) == len(ka)
+    miss = {ka[i * n + int(rng.integers(0, n))] for i in range(2)}     # one member of each group is not in B
+    kb = [x for x in ka if x not in miss]
+    ca = (1 + np.arange(len(ka)) % 7).tolist()
+    cb = (1 + np.arange(len(kb)) % 5).tolist()
+    with _from_pairs(k, ka, ca) as a, _from_pairs(k, kb, cb) as b:
+        ta, tb = _table(a), _table(b)
+        assert sorted(ta[0], key=J.key_order) == sorted(ka, key=J.key_order) and dict(zip(*ta)) == dict(zip(ka, ca))
+        assert dict(zip(*tb)) == dict(zip(kb, cb))
+        got = _got(a, b, (1, MAX, 0, 0))
+        assert set(got[0]) == miss and len(got[0]) == len(miss)
+        _check(a, b, ta, tb, ((1, MAX, 0, 0), (1, MAX, 1, MAX), (2, 4, 2, 3)), f"k={k}")
+        _check(b, a, tb, ta, ((1, MAX, 0, 0), (1, MAX, 1, MAX)), f"k={k} reversed")
+
+
 def test_shared_home_slot_wide():
     """k = 63: 40 keys whose hashes share the top 20 bits (one home slot in any table of up to 2^20 slots) and differ in
     hi; B lacks every fourth"""

@@ -89,6 +89,107 @@ def test_is_canonical_is_the_reverse_complement_test():
     assert T.is_canonical([T.M64, 0], [3, 0], 33).tolist() == [False, True]
 
 
+@pytest.mark.parametrize("k", [3, 15, 31, 32, 33, 34, 47, 62, 63])
+def test_is_canonical_numpy_path_is_the_int_rule(k):
+    rng = np.random.default_rng(200 + k)
+    lo, hi = random_keys(rng, k, 400)
+    if k > 32:                                                           # and keys next to their own reverse complement
+        rlo, rhi = T.revcomp_key(lo[:100], hi[:100], k)
+        lo, hi = np.concatenate([lo, rlo]), np.concatenate([hi, rhi])
+    assert np.array_equal(T.is_canonical(lo, hi, k), T.is_canonical_ints(lo, hi, k))
+    rlo, rhi = T.revcomp_key(lo, hi, k)
+    blo, bhi = T.revcomp_key(rlo, rhi, k)                                # an involution
+    assert np.array_equal(blo, lo) and (hi is None or np.array_equal(bhi, hi))
+    for a, b, c, d in list(zip(lo.tolist(), (hi if hi is not None else lo * 0).tolist(), rlo.tolist(), (rhi if rhi is not None else rlo * 0).tolist()))[:20]:
+        s = T.kmer_string(a, b if k > 32 else None, k)
+        assert T.kmer_string(c, d if k > 32 else None, k) == T.revcomp_string(s)
+
+
+WIDE_KS = (33, 37, 41, 47, 63)
+
+
+@pytest.mark.parametrize("canonical", (False, True))
+@pytest.mark.parametrize("k", WIDE_KS)
+def test_collision_groups_share_all_64_hash_bits(k, canonical):
+    import kmer_truth as KT
+    rng = np.random.default_rng(300 + k)
+    space = 1 << (2 * k - 64)
+    hashes = [T.EMPTY, 0] + [int(x) for x in rng.integers(0, 1 << 63, 4, dtype=np.uint64) * np.uint64(2) + np.uint64(1)]
+    for h in hashes:
+        for n in (2, 3, 65, 300):
+            if n > space or (canonical and k < 41):                      # the canonical share of a small space is not known beforehand
+                continue
+            lo, hi = T.collision_group(h, n, k, rng, canonical=canonical)
+            assert lo.dtype == np.uint64 and hi.dtype == np.uint64 and len(lo) == len(hi) == n
+            assert (T.key_hash(lo, hi) == np.uint64(h)).all()
+            assert len(set(hi.tolist())) == n                            # distinct: one key per high word
+            assert T.valid_keys(lo, hi, k).all()
+            if canonical:
+                assert T.is_canonical_ints(lo[:20], hi[:20], k).all() and T.is_canonical(lo, hi, k).all()
+            for a, b in list(zip(lo.tolist(), hi.tolist()))[:5]:
+                assert KT.key_int(T.kmer_string(a, b, k)) == a | (b << 64)
+    # k = 33: four keys per hash and no more
+    lo, hi = T.collision_group(hashes[2], 4, 33, rng)
+    assert sorted(hi.tolist()) == [0, 1, 2, 3]
+    with pytest.raises(AssertionError, match=r"k=33, h=0x[0-9a-f]{16}: 4 keys, 5 wanted"):
+        T.collision_group(hashes[2], 5, 33, rng)
+
+
+@pytest.mark.parametrize("k", (33, 47, 63))
+def test_a_canonical_key_with_the_empty_marker_as_hash_exists(k):
+    """One group with h = EMPTY per k: a canonical member is found among the first candidates (k = 33: among all four)."""
+    rng = np.random.default_rng(400 + k)
+    lo, hi = T.collision_group(T.EMPTY, 1, k, rng, canonical=True)
+    assert int(T.key_hash(lo, hi)[0]) == T.EMPTY and T.is_canonical_ints(lo, hi, k).all() and T.valid_keys(lo, hi, k).all()
+    assert int(lo[0]) == int(T.unmix64(T.EMPTY)) ^ int(T.rot_hi(hi[0]))
+
+
+def test_keys_with_hash_canonical_and_pinned_to_64_bits():
+    import time
+    rng = np.random.default_rng(7)
+    for k, nbits, top in ((31, 20, 5), (32, 12, 9), (33, 20, 77), (47, 28, 1 << 27), (63, 16, 43690)):
+        lo, hi = T.keys_with_hash(top, nbits, 300, k, rng, canonical=True)
+        assert np.all(T.key_hash(lo, hi) >> np.uint64(64 - nbits) == np.uint64(top))
+        assert T.valid_keys(lo, hi, k).all() and T.is_canonical_ints(lo, hi, k).all()
+        assert len({(a, b) for a, b in zip(lo.tolist(), (hi if hi is not None else lo).tolist())}) == 300
+    h = 0x0123456789ABCDEF
+    t0 = time.perf_counter()
+    lo, hi = T.keys_with_hash(h, 64, 2100, 41, rng, canonical=True)    # a full wide bucket and some more, one hash
+    took = time.perf_counter() - t0
+    assert (T.key_hash(lo, hi) == np.uint64(h)).all() and len(set(hi.tolist())) == 2100 and T.is_canonical(lo, hi, 41).all()
+    assert took < 1.0, f"{took:.2f} s"
+    # what canonical=False gives is what it gave before the switch existed: the same draws in the same order
+    a = T.keys_with_hash(3, 8, 50, 47, np.random.default_rng(1))
+    b = T.keys_with_hash(3, 8, 50, 47, np.random.default_rng(1), canonical=False)
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("canonical", (False, True))
+@pytest.mark.parametrize("k", (33, 47, 63))
+def test_keys_sharing_hi_differ_in_lo_and_hash_only(k, canonical):
+    rng = np.random.default_rng(500 + k)
+    for nbits, top in ((20, 0), (20, (1 << 20) - 1), (14, 8191), (28, 12345678)):
+        lo, hi = T.keys_sharing_hi(top, nbits, 40, k, rng, canonical=canonical)
+        assert len(set(hi.tolist())) == 1 and len(set(lo.tolist())) == 40 and T.valid_keys(lo, hi, k).all()
+        h = T.key_hash(lo, hi)
+        assert len(set(h.tolist())) == 40 and np.all(h >> np.uint64(64 - nbits) == np.uint64(top))
+        assert len(set(T.home(h, nbits).tolist())) == 1
+        if canonical:
+            assert T.is_canonical_ints(lo, hi, k).all()
+    lo, hi = T.keys_sharing_hi(5, 20, 10, k, rng, hi=2)                 # a high word of the caller's
+    assert set(hi.tolist()) == {2}
+
+
+def test_kmer_string_by_hand():
+    import kmer_truth as KT
+    assert T.kmer_string(0b000110, None, 3) == "ACG" and T.revcomp_string("ACG") == "CGT"
+    assert T.kmer_string(T.M64, 3, 33) == "T" * 33 and T.kmer_string(0, 1, 33) == "C" + "A" * 32
+    s = "ACGTTGCATGCATGCAAGGCTTAACCGGTTAGCTAGCTAAGCTTCGATCGGATTACA"[:47]
+    v = KT.key_int(s)
+    assert T.kmer_string(v & T.M64, v >> 64, 47) == s
+    assert KT.key_int(T.revcomp_string(s)) == int(T.revcomp_key(v & T.M64, v >> 64, 47)[0]) | (int(T.revcomp_key(v & T.M64, v >> 64, 47)[1]) << 64)
+
+
 def test_merge_saturates_sums_doubles_and_keeps_zero_counts():
     M = T.U32_MAX
     a = {10: M - 2, 11: M - 2, 12: 0x60000000, 13: 0, 14: 7, 16: M}
