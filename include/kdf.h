@@ -157,7 +157,7 @@ int kdf_flush(kdf_engine *h);
  *            KDF_C1 (coarse bits of the partition), KDF_PIECE_FILL (how full the pieces are planned, default 0.98)
  *   stats    "binned_passes" (partition passes), "flushes" (kernel C launches), "pending_passes",
  *            "pending_positions", "ring_bytes", "replayed_buckets", "heavy_buckets" (buckets of skewed flushes that
- *            were shared by several workgroups), "log2cap", "bucket_bits", "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
+ *            were shared by several workgroups), "log2cap", "bucket_bits", "c1" / "c2" (coarse / fine bits of the partition), "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "lazy_table", "dump_only_flushes" (flushes that wrote a dump and no table), "retained_passes" (passes such a flush applied,
  *            kept for the table: no longer "pending_passes"), "materialisations" (tables written later from retained passes),
  *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_sieve_in_lds" (the last

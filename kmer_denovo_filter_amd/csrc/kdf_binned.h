@@ -36,6 +36,7 @@
 // output inside a launch.
 #pragma once
 #include "kdf_device.h"
+#include "kdf_scan.h"
 
 #define KB_THREADS   1024
 #define KB_F_BITS    8                   // fine radix (level 2) of tables of up to 2^16 buckets
@@ -95,7 +96,8 @@ static_assert(KB_C_THREADS % 256 == 0 && KB_C_THREADS <= 1024 && KB_C_THREADS_W 
 #define KB_A_THREADS 1024
 #endif
 #ifndef KB_A_SCAN
-#define KB_A_SCAN 0                      // 1: every wave scans its own 64 bins (measured: slab kernel 3.17 against 3.13 ms); 0: one wave scans them all
+#define KB_A_SCAN 0                      // 1: every wave scans its own 64 bins (measured: slab kernel 3.17 against 3.13 ms; twelve ds_bpermute per wave);
+                                         // 0: one wave scans them all, on DPP (kb_strip_exscan, kdf_scan.h)
 #endif
 #ifndef KB_A_B4
 #define KB_A_B4 1                        // 1: a fourth barrier per slab after the write-out.  Not needed for correctness, but without it the
@@ -205,28 +207,7 @@ __device__ __forceinline__ uint32_t kb_fine(const KbPlan &p, uint64_t h) {
 #define KB_T(tr, n) do {} while (0)
 #endif
 
-// block-wide exclusive scan of n <= KB_THREADS uint32 values held one per
-// thread (threads >= n pass 0); returns the exclusive prefix, total via *tot.
-__device__ __forceinline__ uint32_t kb_block_exscan(uint32_t v, uint32_t *wsum /* >= 17 words LDS */, uint32_t *tot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    if (wave == 0) {
-        uint32_t s = lane < nw ? wsum[lane] : 0, si = s;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { uint32_t t = __shfl_up(si, o); if (lane >= o) si += t; }
-        if (lane < nw) wsum[lane] = si - s;
-        if (lane == nw - 1) wsum[16] = si;
-    }
-    __syncthreads();
-    const uint32_t r = wsum[wave] + inc - v;
-    if (tot) *tot = wsum[16];
-    __syncthreads();
-    return r;
-}
+// (the block scans kb_block_exscan / kb_block_exscan_lds and the wave scans under them: kdf_scan.h)
 
 // ---------------------------------------------------------------------------
 // A: thread -> (tile, part).  A tile = 64 window starts; it is split over
@@ -319,15 +300,6 @@ struct KbWindows {
         h = kdf_hash(lo, hi);
     }
 };
-
-// Barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt(0),
-// i.e. waits for every outstanding global store; in the slab kernel that would
-// serialise a slab's write-out with the next slab's compute.  The barriers there protect LDS data only.
-__device__ __forceinline__ void kb_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // A: the stream is read ONCE.  A workgroup takes slabs_per_wg consecutive slabs; per slab: stored form + coarse bin of
 // every window, rank by LDS atomics, counting sort into an LDS image, the image written out CONTIGUOUSLY to
@@ -608,27 +580,6 @@ __device__ __forceinline__ uint32_t kb_uni(uint32_t v) { return (uint32_t)__buil
 __device__ __forceinline__ unsigned long long kb_uni64(unsigned long long v) {
     return ((unsigned long long)kb_uni((uint32_t)(v >> 32)) << 32) | kb_uni((uint32_t)v);
 }
-__device__ __forceinline__ uint32_t kb_block_exscan_lds(uint32_t v, uint32_t *wsum /* >= 17 words LDS */, uint32_t tid) {
-    const int lane = tid & 63, wave = tid >> 6, nw = KB_THREADS >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wave] = inc;
-    kb_lds_barrier();
-    if (wave == 0) {
-        uint32_t sv = lane < nw ? wsum[lane] : 0, si = sv;
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { uint32_t t = __shfl_up(si, o); if (lane >= o) si += t; }
-        if (lane < nw) wsum[lane] = si - sv;
-    }
-    kb_lds_barrier();
-    const uint32_t r = wsum[wave] + inc - v;
-    kb_lds_barrier();                                  // (not needed by the pipelined piece sort, whose stages put barriers of their own before
-                                                       // wsum is written again -- but without it, and without the barrier that ends an iteration,
-                                                       // the kernel measured 4.65-4.67 against 4.59 ms: waves that stay in phase share the LDS better)
-    return r;
-}
-
 // One iteration of the pipelined piece sort (see kb_piecesort_pipe_kernel) on ONE of its two register sets: piece `it`,
 // whose entries were requested into (klo, khi) two iterations ago, is sorted and written out, and the entries of piece
 // it + 2 are requested into the same registers.  EVERY global load and store of the body is unconditional -- lanes and
@@ -667,7 +618,7 @@ struct KbPipe {
             kb_lds_barrier();
             {
                 const uint32_t v = (int)tid < nf ? hist[tid] : 0;
-                const uint32_t ex = kb_block_exscan_lds(v, wsum, tid);
+                const uint32_t ex = kb_block_exscan_lds<KB_THREADS>(v, wsum, tid);
                 if ((int)tid < nf) { offs[tid] = ex; hist[tid] = 0; }    // (hist: for the next piece)
             }
             kb_lds_barrier();
@@ -694,7 +645,7 @@ struct KbPipe {
                 const uint32_t sa = 2 * tid;                              // this thread's two consecutive slabs
                 const uint32_t o_a0 = o_raw & 0xFFFFu, o_a1 = o_raw >> 16, o_b0 = o_raw2 & 0xFFFFu, o_b1 = o_raw2 >> 16;
                 const uint32_t rl0 = sa < ns ? o_a1 - o_a0 : 0u, rl1 = sa + 1 < ns ? o_b1 - o_b0 : 0u;
-                const uint32_t pre = kb_block_exscan_lds(rl0 + rl1, wsum, tid);
+                const uint32_t pre = kb_block_exscan_lds<KB_THREADS>(rl0 + rl1, wsum, tid);
                 if (sa < ns) {
                     rsrc[sa] = (s0 + sa) * (unsigned long long)SLAB + o_a0 - pre;
                     rpre[sa] = pre;
@@ -875,7 +826,14 @@ struct KbRunIndex {
     }
     // all threads of the workgroup call it (it ends with a barrier); returns the number of runs
     __device__ __forceinline__ uint32_t setup(const KbPlan &plan, const KbScratch &s, uint32_t c) {
-        if (threadIdx.x < 64) {
+        if (plan.n_pass == 1) {                                 // (uniform) one pending pass -- a count followed by its dump: nothing to scan
+            if (threadIdx.x == 0) {
+                const KbPass *P = s.pass;
+                const uint32_t j0 = P->binrow_first[c], j1 = P->binrow_first[c + 1];
+                prow[0] = P->row_base + j0;
+                ppref[0] = 0; ppref[1] = j1 - j0;
+            }
+        } else if (threadIdx.x < 64) {
             uint32_t n = 0;
             if (threadIdx.x < plan.n_pass) {
                 const KbPass *P = s.pass + threadIdx.x;
@@ -883,9 +841,7 @@ struct KbRunIndex {
                 n = j1 - j0;
                 prow[threadIdx.x] = P->row_base + j0;
             }
-            uint32_t inc = n;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if ((int)threadIdx.x >= o) inc += t; }
+            const uint32_t inc = kb_wave_incl_scan(n);              // (all 64 lanes are here)
             if (threadIdx.x < KB_MAX_PASS) ppref[threadIdx.x + 1] = inc;
             if (threadIdx.x == 0) ppref[0] = 0;
         }
@@ -1678,9 +1634,7 @@ __global__ __launch_bounds__(256) void kb_heavy_slice_kernel(KbPlan plan, KbScra
     // stage the private table's pairs: one reservation per workgroup
     uint32_t mine = 0;
     for (uint32_t i = tid; i < B; i += 256) mine += tlo[i] != KDF_EMPTY ? 1u : 0u;
-    uint32_t inc = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if ((int)lane >= o) inc += y; }
+    const uint32_t inc = kb_wave_incl_scan(mine);
     uint32_t wbase = 0;
     if (lane == 63) wbase = atomicAdd(&sh_n, inc);
     wbase = __shfl(wbase, 63);

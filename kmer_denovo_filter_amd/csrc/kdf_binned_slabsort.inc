@@ -45,17 +45,21 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
     for (uint32_t sl = 0; sl < slabs_per_wg; ++sl) {
         const uint64_t slab = slab0 + sl;
         if (slab * TILES_PER_SLAB >= n_tiles) break;                  // uniform
+        // (the thread index is made opaque once per slab, as in KbPipe::iter: the compiler would otherwise keep the per-lane
+        // addresses of the whole loop body in registers of their own across the loop -- and spill: this kernel has 128)
+        uint32_t tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
         KB_T(s.trash, 18);                                               // (loop turn-around: B4, win = nxt)
         KbWindows<KW> nxt;
 #ifdef KB_SLAB_GATED
         // the next slab's admitted windows travel with its prefetched words (out-of-range threads read the last tile, as issue() does)
-        const uint64_t adm_nxt = admit[min((slab + 1) * TILES_PER_SLAB + threadIdx.x / TPT, n_tiles - 1)];
+        const uint64_t adm_nxt = admit[min((slab + 1) * TILES_PER_SLAB + tid / TPT, n_tiles - 1)];
 #endif
         {
             // prefetch of the next slab's words: loads only; (tile >= n_tiles handles "no next slab")
             const bool more = sl + 1 < slabs_per_wg;
-            nxt.issue(packed, invalid, more ? (slab + 1) * TILES_PER_SLAB + threadIdx.x / TPT : n_tiles,
-                      n_tiles, n_end, threadIdx.x % TPT, k);
+            nxt.issue(packed, invalid, more ? (slab + 1) * TILES_PER_SLAB + tid / TPT : n_tiles,
+                      n_tiles, n_end, tid % TPT, k);
         }
         // Branch-free ranking: invalid windows (~4 %) go to a dummy counter
         // hist[DUMMY], so the WPT returning LDS atomics issue back to back with
@@ -67,7 +71,7 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
             uint64_t hsh, hi; win.stored(u, hsh, hi);
             klo[u] = hsh; if constexpr (KW == 2) khi[u] = hi;
             const bool ok = ((win.valid >> u) & 1) && (!SLICED || kdf_slice(hsh, plan.key_parts) == plan.key_part);
-            const uint32_t bin = ok ? kb_coarse(plan, hsh) : (uint32_t)DUMMY + (threadIdx.x & 63u);
+            const uint32_t bin = ok ? kb_coarse(plan, hsh) : (uint32_t)DUMMY + (tid & 63u);
             br[u] = bin << 16;
         }
         if (KB_ABL(plan, 1024)) {                                          // (ablation: counts without ranks -- WRONG results, timing only)
@@ -81,35 +85,25 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
         kb_lds_barrier();                                               // B1: all ranks taken
         KB_T(s.trash, 11);                                               // ... ranks back, barrier
 #if KB_A_SCAN == 0
-        if (threadIdx.x < 64) {
-            // exclusive scan of hist[0..nb) by one wave: each lane owns a contiguous strip
-            const int per = (nb + 63) >> 6;                             // 1..16
-            const int b0 = threadIdx.x * per;
-            uint32_t sum = 0;
-            for (int i = 0; i < per; ++i) sum += (b0 + i < nb) ? hist[b0 + i] : 0;
-            uint32_t inc = sum;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if ((int)threadIdx.x >= o) inc += t; }
-            uint32_t run = inc - sum;
-            for (int i = 0; i < per; ++i) if (b0 + i < nb) { offs[b0 + i] = run; run += hist[b0 + i]; }
-            if (threadIdx.x == 63) offs[nb] = inc;                      // the slab's valid windows
-        }
+        // exclusive scan of hist[0..nb) by one wave: each lane owns a contiguous strip, read and written 16 bytes at a
+        // time; offs[nb] = the slab's valid windows (kdf_scan.h)
+        if (tid < 64) kb_strip_exscan(hist, offs, nb, tid);
 #else
         // exclusive scan of hist[0..nb): wave w owns the bins [64 w, 64 w + 64); what lies below them is summed by the
         // wave itself (lane l adds hist[l + 64 j], j < w: independent reads, one wave reduction) -- no extra barrier, and
         // no wave walks 16 dependent LDS round trips while fifteen wait (the one-wave scan: ~0.5 us per slab)
-        if ((int)threadIdx.x < ((nb + 63) & ~63)) {                     // whole waves
-            const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+        if ((int)tid < ((nb + 63) & ~63)) {                     // whole waves
+            const int w = tid >> 6, l = tid & 63;
             uint32_t below = 0;
             for (int j = 0; j < w; ++j) below += hist[l + 64 * j];      // (w is wave-uniform)
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
-            const uint32_t v = (int)threadIdx.x < nb ? hist[threadIdx.x] : 0u;
+            const uint32_t v = (int)tid < nb ? hist[tid] : 0u;
             uint32_t inc = v;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) { uint32_t t = __shfl_up(inc, o); if (l >= o) inc += t; }
-            if ((int)threadIdx.x < nb) offs[threadIdx.x] = below + inc - v;
-            if ((int)threadIdx.x == nb - 1) offs[nb] = below + inc;   // the slab's valid windows
+            if ((int)tid < nb) offs[tid] = below + inc - v;
+            if ((int)tid == nb - 1) offs[nb] = below + inc;   // the slab's valid windows
         }
 #endif
         KB_T(s.trash, 12);                                               // scan (wave 0)
@@ -132,7 +126,10 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
         // the slab's offset row (coalesced) while the image settles; the histogram is zeroed for the next slab
         {
             uint16_t *orow = s.off + slab * (uint64_t)(nb + 1);
-            for (int i = threadIdx.x; i <= nb; i += NT) { orow[i] = (uint16_t)offs[i]; hist[i] = 0; }
+            // (straight-line: nb + 1 <= NT + 1 words -- the last one of nb = NT goes with thread 0; as a loop the compiler
+            // unrolled it eight times, with 28 address registers)
+            if ((int)tid <= nb) { orow[tid] = (uint16_t)offs[tid]; hist[tid] = 0; }
+            if (nb == NT && tid == 0) { orow[NT] = (uint16_t)offs[NT]; hist[NT] = 0; }
             // (the dummy counters are never read: they may run on)
         }
         // (Measured and dropped, round 3: the NEXT slab's keys computed here, between scatter and B3, with its words
@@ -152,19 +149,22 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
         KB_T(s.trash, 16);
         {
             // ONE contiguous block per slab: 16 bytes per lane and step
+            // (Measured and dropped: all eight ds_read_b128 of a lane first, pinned in registers, then its stores -- no
+            // spill, but 2.541 / 2.535 against 2.544 / 2.510 ms at k = 31 and 4.31 against 4.23 at k = 63, DESIGN.md 3.2: sixteen
+            // waves already cover one another's LDS round trips here.)
             const uint32_t nv = KB_ABL(plan, 256) ? 0u : offs[nb];          // (ablation 256: no write-out -- timing only)
             if constexpr (KW == 2) {
                 KbEnt2 *dst = (KbEnt2 *)s.tmp + slab * (uint64_t)SLAB;
-                for (uint32_t i = threadIdx.x; i < nv; i += NT) dst[i] = s2[i];
+                for (uint32_t i = tid; i < nv; i += NT) dst[i] = s2[i];
             } else {
                 ulonglong2 *dst = (ulonglong2 *)(s.tmp + slab * (uint64_t)SLAB);
                 const ulonglong2 *src = (const ulonglong2 *)slo;
-                for (uint32_t i = threadIdx.x; i < (nv + 1) / 2; i += NT) dst[i] = src[i];      // (SLAB is even: the odd tail stays inside the slab's block)
+                for (uint32_t i = tid; i < (nv + 1) / 2; i += NT) dst[i] = src[i];      // (SLAB is even: the odd tail stays inside the slab's block)
             }
         }
         KB_T(s.trash, 17);                                               // write-out issued
 #ifdef KB_TIMING
-        if (threadIdx.x == 0) atomicAdd((unsigned long long *)&s.trash[8 + 19], 1ull);
+        if (tid == 0) atomicAdd((unsigned long long *)&s.trash[8 + 19], 1ull);
 #endif
 #if KB_A_B4
         kb_lds_barrier();                                               // B4: image free (stores still draining)

@@ -3350,6 +3350,9 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "hash_shift") *value = h->opt_hash_shift;
     else if (n == "log2cap") *value = h->t.log2cap;
     else if (n == "bucket_bits") *value = h->t.bucket_bits;
+    // the binned path's split of the bucket bits: of the pending passes, or what the next pass would be partitioned with
+    else if (n == "c1") *value = (h->n_pass ? h->pend_plan : kb_make_plan(h, h->t)).c1;
+    else if (n == "c2") *value = (h->n_pass ? h->pend_plan : kb_make_plan(h, h->t)).c2;
     else if (n.rfind("trash", 0) == 0 && n.size() > 5 && h->kb_small) {          // (variant builds with -DKB_TIMING: phase cycle sums)
         const int i = atoi(n.c_str() + 5);
         if (i < 0 || i >= 64) return fail(h, KDF_ERR_INVALID, "kdf_get_stat: trash0..trash63");
