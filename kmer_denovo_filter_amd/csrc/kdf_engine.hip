@@ -437,12 +437,17 @@ static uint32_t cap_log2_for(uint64_t n_keys) {
     return std::max<uint32_t>(l, 10);
 }
 
+// bucket bits of a table of 2^log2cap slots: 48 / 40 KB of LDS per bucket; tables of 2^big_bucket_log2cap slots and more:
+// twice that (kdf_binned.h: KB_C_CT_BIG)
+static uint32_t bucket_bits_for(const kdf_engine *h, uint32_t log2cap) {
+    return std::min<uint32_t>(log2cap, KB_BB_SMALL(h->kw) + (log2cap >= h->opt_big_bucket_log2cap ? 1u : 0u));
+}
+
 static int table_alloc(kdf_engine *h, uint32_t log2cap, KdfTable &t, bool clear = true) {
     const uint64_t cap = 1ull << log2cap;
     t = KdfTable{};
     t.log2cap = log2cap;
-    // 48 / 40 KB of LDS per bucket; tables of 2^big_bucket_log2cap slots and more: twice that (kdf_binned.h: KB_C_CT_BIG)
-    t.bucket_bits = std::min<uint32_t>(log2cap, KB_BB_SMALL(h->kw) + (log2cap >= h->opt_big_bucket_log2cap ? 1u : 0u));
+    t.bucket_bits = bucket_bits_for(h, log2cap);
     t.hshift = h->opt_hash_shift;
     {
         hipError_t e = hipMalloc((void **)&t.lo, cap * 8);
@@ -675,6 +680,27 @@ static KbPlan kb_make_plan(const kdf_engine *h, const KdfTable &t) {
     return p;
 }
 
+// Every instantiation of kernel C per key width, written once: f(MODE, VAR, BIG, DUMP, LAZY) -- integral constants, the
+// template arguments of kb_bucket_kernel<KW, ..> -- is called for each in turn until it returns non-zero, which is returned
+// (0: f took them all).  Insert, count --if and the fused dump, each plain (VAR 1) and skewed (VAR 2); the dump-only flush;
+// all with small and with big buckets.  The order is the one the code object has always held them in (another order moves
+// every kernel behind them).  The attribute setter walks them all, the launcher picks the one that matches: a variant that
+// is launched has its LDS limit raised.
+template <typename F>
+static int kb_c_variants(F &&f) {
+    using ins = std::integral_constant<int, KB_MODE_INSERT>; using flt = std::integral_constant<int, KB_MODE_FILTERED>;
+    using no = std::false_type; using yes = std::true_type;
+    int rc = 0;
+    auto one = [&](auto mode, auto var, auto big, auto dump, auto lazy) { return (rc = f(mode, var, big, dump, lazy)) != 0; };
+    auto each = [&](auto var) {
+        return one(ins{}, var, no{}, no{}, no{}) || one(flt{}, var, no{}, no{}, no{}) || one(ins{}, var, yes{}, no{}, no{}) || one(flt{}, var, yes{}, no{}, no{}) ||
+               one(ins{}, var, no{}, yes{}, no{}) || one(ins{}, var, yes{}, yes{}, no{});
+    };
+    const std::integral_constant<int, 1> v1{};
+    (void)(each(v1) || each(std::integral_constant<int, 2>{}) || one(ins{}, v1, no{}, yes{}, yes{}) || one(ins{}, v1, yes{}, yes{}, yes{}));
+    return rc;
+}
+
 template <int KW>
 static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t hv) {
     HIPCHK(h, hipFuncSetAttribute((const void *)(kb_slabsort_kernel<KW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a));
@@ -684,18 +710,12 @@ static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t 
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_piecesort_more_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_piecesort_pipe_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b));
     const size_t cbig = KB_C_LDS(KW, KB_BB_SMALL(KW) + 1);
-#define KB_SETV(V) \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, V, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c)); \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_FILTERED, V, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c)); \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, V, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cbig)); \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_FILTERED, V, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cbig)); \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, V, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c)); \
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, V, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cbig));
-    KB_SETV(1)
-    KB_SETV(2)
-#undef KB_SETV
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, 1, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c));
-    HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, KB_MODE_INSERT, 1, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cbig));
+    if (const int rc = kb_c_variants([&](auto M, auto V, auto B, auto D, auto L) -> int {
+            constexpr bool BIG = decltype(B)::value;
+            HIPCHK(h, hipFuncSetAttribute((const void *)(kb_bucket_kernel<KW, decltype(M)::value, decltype(V)::value, BIG, decltype(D)::value, decltype(L)::value>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BIG ? cbig : c)));
+            return KDF_OK;
+        })) return rc;
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_slice_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_combine_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
     HIPCHK(h, hipFuncSetAttribute((const void *)kb_heavy_filtered_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hv));
@@ -730,48 +750,47 @@ static int kb_scratch(kdf_engine *h, KbScratch &s) {
     s.off = (uint16_t *)h->kb_buf[4].p;
     // row tables of the ring: row_ent u64 | row_len u32, ring_rows of each
     s.row_ent = (unsigned long long *)h->kb_buf[6].p;
-    s.row_len = (uint32_t *)(s.row_ent + h->ring_rows);
+    s.row_len = (uint32_t *)(s.row_ent + h->ring.cap_rows);
     return KDF_OK;
 }
 
 // the ring is empty again: nothing pending, the flush-wide counters zeroed
 static int kb_ring_reset(kdf_engine *h) {
-    h->n_pass = 0; h->ring_used = 0; h->rows_used = 0; h->pend_positions = 0;
-    h->n_dumped = 0; h->dumped_positions = 0; h->acct_entries = 0; h->acct_positions = 0;
+    h->ring.reset();
     if (h->kb_small) HIPCHK(h, hipMemsetAsync(h->kb_small, 0, 16 * 8, h->stream));
     return KDF_OK;
 }
 
-static int kb_flush_ring(kdf_engine *h, bool lazy_ok = false);
+static int kb_flush_ring(kdf_engine *h, KbDump *dump = nullptr);
 
 // Room for a pass of need_e entries (upper bound: its stream positions) in need_r pieces.  A full ring is applied to the
 // table first; a ring that was too small for the pending passes plus this one grows (doubling, up to the budget) while
 // it is empty.
 static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, uint32_t off_stride) {
     int rc;
-    const uint64_t rows_cap = std::min<uint64_t>(h->ring_rows, h->kb_buf[2].bytes / ((uint64_t)off_stride * 4));
+    const uint64_t rows_cap = std::min<uint64_t>(h->ring.cap_rows, h->kb_buf[2].bytes / ((uint64_t)off_stride * 4));
     bool forced = false;
-    if (h->n_pass >= KB_MAX_PASS || h->ring_used + need_e > h->ring_entries || h->rows_used + need_r > rows_cap) {
-        forced = h->n_pass > 0;
-        if (h->n_pass && (rc = kb_flush_ring(h))) return rc;
+    if (h->ring.n_pass >= KB_MAX_PASS || h->ring.used_entries + need_e > h->ring.cap_entries || h->ring.used_rows + need_r > rows_cap) {
+        forced = !h->ring.empty();
+        if (forced && (rc = kb_flush_ring(h))) return rc;
     }
     const uint64_t esz = 8ull * h->kw;
     const uint64_t budget = h->opt_defer_max_bytes ? h->opt_defer_max_bytes : h->dev_total_bytes / 5 * 2;
-    uint64_t want_e = h->ring_entries;
+    uint64_t want_e = h->ring.cap_entries;
     // (at least 128 / 256 MB: small batches never force a flush; with deferral on, room for one more pass like this one)
     if (need_e > want_e) want_e = std::max<uint64_t>(h->opt_defer ? std::max<uint64_t>(need_e, std::min<uint64_t>(2 * need_e, budget / esz)) : need_e, 1ull << 24);
-    if (forced && h->opt_defer && h->ring_entries * esz < budget)
-        want_e = std::max<uint64_t>(want_e, std::min<uint64_t>(2 * h->ring_entries, std::max<uint64_t>(budget / esz, need_e)));
+    if (forced && h->opt_defer && h->ring.cap_entries * esz < budget)
+        want_e = std::max<uint64_t>(want_e, std::min<uint64_t>(2 * h->ring.cap_entries, std::max<uint64_t>(budget / esz, need_e)));
     // pieces: in proportion to the entries (passes of one sample look alike), and never fewer than this pass needs
     const uint64_t want_r = std::max<uint64_t>(need_r, (uint64_t)((double)need_r * ((double)want_e / (double)need_e))) + 4096;
-    if (want_e > h->ring_entries || need_r > rows_cap) {
+    if (want_e > h->ring.cap_entries || need_r > rows_cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if ((rc = eng_reserve(h, h->kb_buf[0], want_e * esz, slack_page))) return rc;
         if ((rc = eng_reserve(h, h->kb_buf[2], want_r * (uint64_t)off_stride * 4, slack_page))) return rc;
         if ((rc = eng_reserve(h, h->kb_buf[6], want_r * 12, slack_page))) return rc;
-        h->ring_entries = std::max(h->ring_entries, want_e); h->ring_rows = std::max(h->ring_rows, want_r);
+        h->ring.cap_entries = std::max(h->ring.cap_entries, want_e); h->ring.cap_rows = std::max(h->ring.cap_rows, want_r);
         // (a buffer only ever grows: the row tables are laid out for ring_rows rows)
-        if (h->kb_buf[6].bytes < h->ring_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
+        if (h->kb_buf[6].bytes < h->ring.cap_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
     }
     return KDF_OK;
 }
@@ -786,9 +805,9 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     if (n_tiles == 0) return KDF_OK;
     int rc;
     // pending passes must share their geometry, key slice and mode (kdf_set_option / a mode change flush first)
-    if (h->n_pass && h->pend_filtered != filtered && (rc = kb_flush_ring(h))) return rc;
-    KbPlan plan = h->n_pass ? h->pend_plan : kb_make_plan(h, h->t);
-    if (h->n_pass == 0) { plan.key_parts = filtered ? 0 : h->t.key_parts; plan.key_part = h->t.key_part; }
+    if (!h->ring.empty() && h->ring.filtered != filtered && (rc = kb_flush_ring(h))) return rc;
+    KbPlan plan = h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan;
+    if (h->ring.empty()) { plan.key_parts = filtered ? 0 : h->t.key_parts; plan.key_part = h->t.key_part; }
     const int nbins = 1 << plan.c1;
     const uint64_t n_slabs = (n_tiles + TILES_PER_SLAB - 1) / TILES_PER_SLAB;
     const uint64_t n_groups = (n_slabs + plan.group - 1) / plan.group;
@@ -796,7 +815,7 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     const uint64_t n_rows_max = n_groups * nbins + n_entries_max / CHUNK + 1;
     if (n_rows_max >= (1ull << 32) || n_slabs >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "binned pass: too many positions for one pass");
     if ((rc = kb_ring_make_room(h, n_entries_max, n_rows_max, plan.off_stride))) return rc;
-    if (h->n_pass == 0) { h->pend_plan = plan; h->pend_filtered = filtered; }
+    if (h->ring.empty()) { h->ring.plan = plan; h->ring.filtered = filtered; }
     plan.dbg = h->opt_debug_flags;
     plan.n_slabs = (uint32_t)n_slabs; plan.n_groups = (uint32_t)n_groups;
     const int nb1 = 1 << KB_C1_MAX;
@@ -820,12 +839,11 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     s.gn = (uint32_t *)(s.bin_ent + nb1); s.gpre_row = s.gn + n_pairs; s.bin_rows = s.gpre_row + n_pairs; s.ovf = s.bin_rows + nb1;
     s.ovf_cap = (uint32_t)ovf_cap;
 
-    std::vector<hipEvent_t> sev;
-    auto stamp = [&]() { if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); } };
+    StageStamps st(h->prof, h->stream);
     EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
-    stamp();                                                   // start of A
+    st.stamp();                                                  // start of A
 
-    const uint32_t pass_idx = h->n_pass;
+    const uint32_t pass_idx = h->ring.n_pass;
     const bool sliced = plan.key_parts > 1;
     // A: a workgroup takes a few consecutive slabs (the next slab's words are prefetched under the current one)
     const uint32_t slabs_per_wg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, n_slabs / ((uint64_t)h->n_cu * 8)));
@@ -834,26 +852,26 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     if (admit) hipLaunchKernelGGL((kb_slabsort_gated_kernel<KW>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg, admit);
     else if (sliced) hipLaunchKernelGGL((kb_slabsort_kernel<KW, true>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
     else hipLaunchKernelGGL((kb_slabsort_kernel<KW, false>), dim3(grid_a), dim3(KB_A_THREADS), lds_a, h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
-    stamp();                                                   // end of A
+    st.stamp();                                                // end of A
     hipLaunchKernelGGL(kb_groupsum_kernel, dim3((unsigned)n_groups, (unsigned)((nbins + 63) / 64)), dim3(256), 0, h->stream, plan, s);
     hipLaunchKernelGGL(kb_binscan_kernel<CHUNK>, dim3((unsigned)nbins), dim3(256), 0, h->stream, plan, s);
-    hipLaunchKernelGGL(kb_binfirst_kernel, dim3(1), dim3(KB_THREADS), 0, h->stream, plan, s, pass_idx, (unsigned long long)h->ring_used,
-                       (unsigned long long)h->rows_used, h->ctl);
+    hipLaunchKernelGGL(kb_binfirst_kernel, dim3(1), dim3(KB_THREADS), 0, h->stream, plan, s, pass_idx, (unsigned long long)h->ring.used_entries,
+                       (unsigned long long)h->ring.used_rows, h->ctl);
     HIPCHK(h, hipGetLastError());
-    stamp();                                                   // end of the planning kernels
+    st.stamp();                                                // end of the planning kernels
     // No host round trip: the pass's share of the ring is sized for one entry per position; B's first launch has one
     // workgroup per (group, bin) pair, its second walks the (usually empty) list of further pieces.
     // (debug flag 64: the one-piece-per-workgroup kernel of round 3's first half, for same-box comparisons)
     if (plan.dbg & 64) hipLaunchKernelGGL(kb_piecesort_kernel<KW>, dim3((unsigned)((n_pairs + 7) / 8 * 8)), dim3(KB_THREADS), lds_b, h->stream, plan, s, pass_idx);
     else hipLaunchKernelGGL(kb_piecesort_pipe_kernel<KW>, dim3((unsigned)std::max(8, h->n_cu / 8 * 8)), dim3(KB_THREADS), lds_b, h->stream, plan, s, pass_idx);
     hipLaunchKernelGGL(kb_piecesort_more_kernel<KW>, dim3((unsigned)std::min<uint64_t>(ovf_cap, (uint64_t)h->n_cu)), dim3(KB_THREADS), lds_b, h->stream, plan, s, pass_idx);
-    stamp();                                                   // end of B
+    st.stamp();                                                // end of B
     HIPCHK(h, hipGetLastError());
     span.stop();
-    if (h->prof) h->prof_stage_ev.push_back(sev);
-    h->n_pass++;
-    h->ring_used += n_entries_max; h->rows_used += n_rows_max;
-    h->pend_positions += n_entries_max;
+    st.commit(h->prof_stage_ev);
+    h->ring.n_pass++;
+    h->ring.used_entries += n_entries_max; h->ring.used_rows += n_rows_max;
+    h->ring.positions += n_entries_max;
     h->stat_binned_passes++;
     h->last_path = 1;
     return KDF_OK;
@@ -905,186 +923,272 @@ static int kb_partition_stream(kdf_engine *h, const uint64_t *d_packed, const ui
     return KDF_OK;
 }
 
-// Kernel C over every pending pass: the ring is applied to the table and emptied.
-// lazy_ok (a dump is waiting and would be this flush's only reader): the dump-only flush is allowed -- the dump and the
-// counters are written, the table is not, and the passes stay in the ring until something needs the table.  Passes a
-// dump-only flush has applied (n_dumped) are applied AGAIN here, dump-only or not: the table is still empty, so the result
-// is what the first application would have left.
-static int kb_flush_ring(kdf_engine *h, bool lazy_ok) {
-    if (h->n_pass == 0) return KDF_OK;
+// ---- the flush: kernel C over every pending pass, the ring applied to the table and emptied -- in steps ------------------
+// What a flush decides before it launches anything (kb_flush_choose)
+struct KbChoice {
+    bool redo;                    // passes a dump-only flush has applied (n_dumped) are applied AGAIN, dump-only or not: the table is
+                                  // still empty, so the result is what the first application would have left
+    bool skewed;                  // VAR 2 of kernel C ...
+    bool heavy;                   // ... with the heavy-bucket kernels behind it, if the buckets are whole at the launch (sub_bits 0)
+    bool grow_first;              // the table doubles before the launch
+    bool dump_only;               // the dump and the counters are written, the table is not, and the passes stay in the ring
+    uint64_t distinct_before;     // keys of the table the flush adds to
+    double est;                   // ... and of the table afterwards, at the last flush's rate of new keys
+};
+// ... and what its steps hand on to each other
+struct KbFlush {
+    KbScratch s{};
+    bool filtered = false;        // count --if passes
+    uint64_t n_entries = 0;       // entries of the pending passes
+    KbChoice c{};
+    KbPlan plan{};                // the partition's geometry on the table as it is at the launch; dump_min: the dump kernel C writes
+    uint64_t nb_table = 0;        // table buckets = workgroups of kernel C
+    int nonempty = 1;             // 0: kernel C rewrites every bucket (this IS the clear)
+};
+
+// A table that grew since the partition has more buckets than the partition made: kernel C resolves the extra bits itself
+static uint32_t kb_sub_bits_now(const kdf_engine *h) { return (h->t.log2cap - h->t.bucket_bits) - h->ring.plan.c1 - h->ring.plan.c2; }
+
+// what the pending passes hold (entries, skew) and what the table holds now; the density accounting
+static int kb_flush_totals(kdf_engine *h, KbFlush &f) {
     int rc;
-    KbScratch s;
-    if ((rc = kb_scratch(h, s))) return rc;
-    const bool filtered = h->pend_filtered;
-    // what the pending passes hold (entries, skew) and what the table holds now
-    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kb_scratch(h, f.s))) return rc;
+    f.filtered = h->ring.filtered;
+    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
     if ((rc = ctl_sync(h, nullptr))) return rc;
-    const uint64_t n_entries = h->kb_totals_host[0];
-    h->dens_windows += n_entries - h->acct_entries; h->dens_positions += h->pend_positions - h->acct_positions;
-    h->acct_entries = n_entries; h->acct_positions = h->pend_positions;
+    f.n_entries = h->kb_totals_host[0];
+    h->dens_windows += f.n_entries - h->ring.acct_entries; h->dens_positions += h->ring.positions - h->ring.acct_positions;
+    h->ring.acct_entries = f.n_entries; h->ring.acct_positions = h->ring.positions;
+    return KDF_OK;
+}
+
+// Which flush this is: reads the engine and the totals, changes nothing.  dump_only_ok (a dump is waiting and would be this
+// flush's only reader): the dump-only flush is allowed.
+static KbChoice kb_flush_choose(const kdf_engine *h, const KbFlush &f, const KbDump *dump, bool dump_only_ok) {
+    KbChoice c{};
     // passes a dump-only flush has applied: kernel C counts their keys again, so the counter restarts at 0 (the table is
-    // empty) -- just before the launch below, after everything that can still fail or return
-    const bool redo = h->n_dumped > 0;
-    const bool skewed = h->kb_totals_host[7] != 0 || (h->opt_debug_flags & 4096);          // (debug flag 4096 forces VAR 2: fuzzing)
-    const uint64_t distinct_before = redo ? 0 : h->distinct;
+    // empty) -- just before the launch (kb_flush_launch), after everything that can still fail or return
+    c.redo = h->ring.n_dumped > 0;
+    c.skewed = h->kb_totals_host[7] != 0 || (h->opt_debug_flags & 4096);          // (debug flag 4096 forces VAR 2: fuzzing)
+    c.heavy = c.skewed && f.s.hv_ctr;
+    c.distinct_before = c.redo ? 0 : h->distinct;
     // Grow BEFORE the flush when the last flush's rate of new keys says the pending entries will not fit: growing now
     // rehashes the smaller table, and kernel C resolves the extra bucket bits itself (sub_bits) -- no failed buckets, no
     // replay through the global-atomic path.  (First flush of a table: the caller's capacity hint is trusted.)
-    const double est = (double)distinct_before + h->grow_ratio * (double)n_entries;
-    const bool grow_first = !filtered && h->grow_ratio > 0.0 && est > 0.6 * (double)h->cap && h->t.log2cap < 40;
+    c.est = (double)c.distinct_before + h->grow_ratio * (double)f.n_entries;
+    c.grow_first = !f.filtered && h->grow_ratio > 0.0 && c.est > 0.6 * (double)h->cap && h->t.log2cap < 40;
     // the dump-only flush: everything that gates the fused dump, an empty table, passes no flush has seen, and nothing that
     // would send a bucket another way (skew: the heavy-bucket split; a table about to grow).  Counts of one key slice
     // (key_parts) and counts behind a prefilter keep the ordinary flush: their dumps are followed by reads of the table.
-    // A table that grew since the partition has more buckets than the partition made: kernel C resolves the extra bits itself
-    // (a per-key test the dump-only instantiation leaves out: such a table takes the ordinary flush).
-    auto sub_bits_now = [&] { return (h->t.log2cap - h->t.bucket_bits) - h->pend_plan.c1 - h->pend_plan.c2; };
-    const bool lazy = lazy_ok && h->opt_lazy_table && h->fuse_min && !filtered && h->lazy_empty && !skewed && !grow_first && sub_bits_now() == 0 &&
-                      h->n_pass > h->n_dumped && h->pend_plan.key_parts <= 1 && h->pf_state == PF_OFF && !(h->opt_debug_flags & 2048);
-    if (grow_first) {
-        while (est > 0.6 * (double)h->cap && h->t.log2cap < 40) {
-            if (h->lazy_empty) {                                  // nothing to carry over: a new table, still to be cleared
-                KdfTable nt;
-                if ((rc = table_alloc(h, h->t.log2cap + 1, nt, false))) break;       // (no room: kernel C will tell what really overflows)
-                HIPCHK(h, hipStreamSynchronize(h->stream));
-                table_free(h->t);
-                h->t = nt; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
-                h->cap = 1ull << h->t.log2cap;
-            } else if ((rc = table_rehash(h, h->t.log2cap + 1))) { (void)hipGetLastError(); h->err.clear(); break; }
-        }
+    // A table that grew since the partition (kb_sub_bits_now): a per-key test the dump-only instantiation leaves out: such
+    // a table takes the ordinary flush.
+    c.dump_only = dump_only_ok && h->opt_lazy_table && dump && dump->min_count && !f.filtered && h->lazy_empty && !c.skewed && !c.grow_first &&
+                  kb_sub_bits_now(h) == 0 && h->ring.undumped_passes() && h->ring.plan.key_parts <= 1 && h->pf_state == PF_OFF &&
+                  !(h->opt_debug_flags & 2048);
+    return c;
+}
+
+// grow-first: the table doubles until est keys sit at load <= 0.6; a step that fails ends the growth, not the flush
+static int kb_grow_first(kdf_engine *h, double est) {
+    int rc;
+    while (est > 0.6 * (double)h->cap && h->t.log2cap < 40) {
+        if (h->lazy_empty) {                                  // nothing to carry over: a new table, still to be cleared
+            KdfTable nt;
+            if ((rc = table_alloc(h, h->t.log2cap + 1, nt, false))) break;       // (no room: kernel C will tell what really overflows)
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            table_free(h->t);
+            h->t = nt; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
+            h->cap = 1ull << h->t.log2cap;
+        } else if ((rc = table_rehash(h, h->t.log2cap + 1))) { (void)hipGetLastError(); h->err.clear(); break; }
     }
-    if (filtered && (rc = materialize(h))) return rc;
-    KbPlan plan = h->pend_plan;
-    plan.n_pass = h->n_pass; plan.dbg = h->opt_debug_flags;
-    plan.log2cap = h->t.log2cap; plan.bucket_bits = h->t.bucket_bits;
-    // a dump is waiting for this flush: kernel C writes it out of the buckets it holds (the request is taken: a second
-    // flush of the same call must not dump again)
-    const uint32_t fuse_min = filtered ? 0u : h->fuse_min;
-    h->fuse_min = 0; h->fuse_done = false;
-    if (fuse_min) {
-        plan.dump_min = fuse_min;
-        s.dump_lo = h->fuse_lo; s.dump_hi = h->fuse_hi; s.dump_cnt = h->fuse_cnt; s.dump_cap = h->fuse_cap;
+    return KDF_OK;
+}
+
+// the plan of kernel C on the table as it is now, the dump it writes and the bitmap of failed buckets
+static int kb_flush_prepare(kdf_engine *h, KbFlush &f, const KbDump *dump) {
+    int rc;
+    if (f.filtered && (rc = materialize(h))) return rc;
+    f.plan = h->ring.plan;
+    f.plan.n_pass = h->ring.n_pass; f.plan.dbg = h->opt_debug_flags;
+    f.plan.log2cap = h->t.log2cap; f.plan.bucket_bits = h->t.bucket_bits;
+    // a dump is waiting for this flush: kernel C writes it out of the buckets it holds
+    if (dump && !f.filtered && dump->min_count) {
+        f.plan.dump_min = dump->min_count;
+        f.s.dump_lo = dump->lo; f.s.dump_hi = dump->hi; f.s.dump_cnt = dump->cnt; f.s.dump_cap = dump->cap;
         HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor: ctl_sync reports their sum (a kdf_count_ge before this leaves its tally behind)
     }
-    plan.sub_bits = sub_bits_now();                   // a table that grew since the partition (just now, perhaps): more sub-buckets
-    const uint64_t nb_table = 1ull << (plan.c1 + plan.c2 + plan.sub_bits);
-    const size_t failed_bytes = (size_t)((nb_table + 31) / 32) * 4;
+    f.plan.sub_bits = kb_sub_bits_now(h);             // a table that grew since the partition (just now, perhaps): more sub-buckets
+    f.nb_table = 1ull << (f.plan.c1 + f.plan.c2 + f.plan.sub_bits);
+    const size_t failed_bytes = (size_t)((f.nb_table + 31) / 32) * 4;
     if ((rc = eng_reserve(h, h->kb_buf[3], failed_bytes, slack_16th))) return rc;
-    s.failed = (uint32_t *)h->kb_buf[3].p;
-    HIPCHK(h, hipMemsetAsync(s.failed, 0, failed_bytes, h->stream));
-    const int nonempty = h->lazy_empty ? 0 : 1;   // 0: kernel C rewrites every bucket (this IS the clear)
-    std::vector<hipEvent_t> sev;
+    f.s.failed = (uint32_t *)h->kb_buf[3].p;
+    HIPCHK(h, hipMemsetAsync(f.s.failed, 0, failed_bytes, h->stream));
+    f.nonempty = h->lazy_empty ? 0 : 1;
+    return KDF_OK;
+}
+
+// kernel C -- the one of kb_c_variants this flush chose -- and, for a skewed flush, the heavy-bucket kernels
+static int kb_flush_launch(kdf_engine *h, const KbFlush &f) {
+    const KbPlan &plan = f.plan;
+    const KbScratch &s = f.s;
+    StageStamps st(h->prof, h->stream);
     EvSpan span(h->timer[T_STREAM], h->prof, h->stream, 0);      // (tag 0: its positions were counted with the partition passes)
-    if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); }
-    if (plan.dbg & 2048) return kb_ring_reset(h);                 // (ablation: the partition passes are timed alone, what they wrote is dropped)
-    const bool heavy = skewed && s.hv_ctr && plan.sub_bits == 0;
+    st.stamp();
+    const bool heavy = f.c.heavy && plan.sub_bits == 0;
     if (heavy) {
         HIPCHK(h, hipMemsetAsync(s.hv_ctr, 0, (4 + 3 * KB_HV_MAX) * 4, h->stream));
     }
-    if (redo) {
+    if (f.c.redo) {
         HIPCHK(h, hipMemsetAsync(h->ctl->distinct, 0, sizeof(h->ctl->distinct), h->stream));
         h->distinct = 0;
-        if (!lazy) h->stat_materialisations++;
+        if (!f.c.dump_only) h->stat_materialisations++;
     }
-    by_width(h, [&](auto KWc) {
+    const int mode = f.filtered ? KB_MODE_FILTERED : KB_MODE_INSERT, var = f.c.skewed ? 2 : 1;
+    const bool dumps = plan.dump_min != 0, dump_only = f.c.dump_only;
+    const int launched = by_width(h, [&](auto KWc) {
         constexpr int KW = decltype(KWc)::value;
         const size_t lds_c = KB_C_LDS(KW, plan.bucket_bits);
         const bool big = plan.bucket_bits > KB_BB_SMALL(KW);
-#define KB_LVL(M, V, D, L) do { if (big) hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, true, D, L>), dim3((unsigned)nb_table), dim3(KB_C_CT_BIG), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); \
-                         else hipLaunchKernelGGL((kb_bucket_kernel<KW, M, V, false, D, L>), dim3((unsigned)nb_table), dim3(KB_C_CT(KW)), lds_c, h->stream, plan, s, h->t, h->ctl, nonempty); } while (0)
-#define KB_LV(M, V, D) KB_LVL(M, V, D, false)
-        if (lazy) KB_LVL(KB_MODE_INSERT, 1, true, true);
-        else if (filtered) { if (skewed) KB_LV(KB_MODE_FILTERED, 2, false); else KB_LV(KB_MODE_FILTERED, 1, false); }
-        else if (fuse_min) { if (skewed) KB_LV(KB_MODE_INSERT, 2, true); else KB_LV(KB_MODE_INSERT, 1, true); }
-        else { if (skewed) KB_LV(KB_MODE_INSERT, 2, false); else KB_LV(KB_MODE_INSERT, 1, false); }
-#undef KB_LV
-#undef KB_LVL
-        return 0;
+        return kb_c_variants([&](auto M, auto V, auto B, auto D, auto L) -> int {
+            constexpr bool BIG = decltype(B)::value;
+            if (decltype(M)::value != mode || decltype(V)::value != var || BIG != big || decltype(D)::value != dumps || decltype(L)::value != dump_only) return 0;
+            hipLaunchKernelGGL((kb_bucket_kernel<KW, decltype(M)::value, decltype(V)::value, BIG, decltype(D)::value, decltype(L)::value>),
+                               dim3((unsigned)f.nb_table), dim3(KB_C_CTB(KW, BIG)), lds_c, h->stream, plan, s, h->t, h->ctl, f.nonempty);
+            return 1;
+        });
     });
+    if (!launched) return fail(h, KDF_ERR_STATE, "binned flush: no kernel C instantiation for mode %d, variant %d", mode, var);
     if (heavy) {
         // the buckets the skewed instantiation left aside
         const size_t lds_h = ((size_t)(8 * h->kw + 4) << plan.bucket_bits) + KB_RI_LDS_BYTES;
         by_width(h, [&](auto KWc) {
             constexpr int KW = decltype(KWc)::value;
-            if (filtered) {                                        // the keys stay put: the slices add to the counts in HBM
+            if (f.filtered) {                                      // the keys stay put: the slices add to the counts in HBM
                 hipLaunchKernelGGL(kb_heavy_filtered_kernel<KW>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t);
             } else {
                 hipLaunchKernelGGL(kb_heavy_slice_kernel<KW>, dim3(KB_HV_SLICES, KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s);
-                hipLaunchKernelGGL(kb_heavy_combine_kernel<KW>, dim3(KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t, h->ctl, nonempty);
+                hipLaunchKernelGGL(kb_heavy_combine_kernel<KW>, dim3(KB_HV_MAX), dim3(256), lds_h, h->stream, plan, s, h->t, h->ctl, f.nonempty);
             }
             return 0;
         });
     }
     HIPCHK(h, hipGetLastError());
-    if (h->prof) { hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, h->stream); sev.push_back(e); h->prof_stage_ev.push_back(sev); }
+    st.stamp(); st.commit(h->prof_stage_ev);
     span.stop();
-    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
-    bool full = false;
-    uint64_t cursor = 0;
-    if ((rc = ctl_sync(h, &full, &cursor))) return rc;
-    if (lazy) {
-        // whole (no bucket failed) and the table need not grow for what comes next: the dump is the caller's, the passes stay
-        if (h->kb_totals_host[2] == 0 && h->distinct * 10 <= h->cap * 7) {
-            h->fuse_done = true; h->fuse_n = cursor; h->stat_fused_dumps++; h->stat_flushes++; h->stat_dump_only++;
-            if (n_entries >= 100000) h->grow_ratio = (double)(h->distinct - distinct_before) / (double)n_entries;
-            h->n_dumped = h->n_pass; h->dumped_positions = h->pend_positions;
-            return KDF_OK;
-        }
-        // otherwise: what the parent path does, from the start -- the ordinary flush of the same passes into the empty table
-        // (it dumps too, replays the failed buckets, grows the table); nothing of this attempt is counted.  Undone here is
-        // EVERYTHING kernel C<.., LAZY> accumulates into (the list at "what a bucket leaves behind" in kdf_binned.h):
-        // totals[2] and ctl->distinct below; s.failed, ctl->tally / cursor and the dump buffers are reset or rewritten on
-        // re-entry.  Under kdf_profile the discarded launch stays in the C stage slot as a second C.
-        HIPCHK(h, hipMemsetAsync(s.totals + 2, 0, 8, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->ctl->distinct, 0, sizeof(h->ctl->distinct), h->stream));
-        h->distinct = 0;
-        h->fuse_min = fuse_min;
-        return kb_flush_ring(h, false);
+    return KDF_OK;
+}
+
+// A dump-only attempt is over (cursor: the keys it dumped).  It stands -- *again stays false -- or is undone for a second,
+// ordinary attempt with the same request.
+static int kb_settle_dump_only(kdf_engine *h, const KbFlush &f, KbDump *dump, uint64_t cursor, bool *again) {
+    // whole (no bucket failed) and the table need not grow for what comes next: the dump is the caller's, the passes stay
+    if (h->kb_totals_host[2] == 0 && h->distinct * 10 <= h->cap * 7) {
+        dump->done = true; dump->n = cursor; h->stat_fused_dumps++; h->stat_flushes++; h->stat_dump_only++;
+        if (f.n_entries >= 100000) h->grow_ratio = (double)(h->distinct - f.c.distinct_before) / (double)f.n_entries;
+        h->ring.n_dumped = h->ring.n_pass; h->ring.dumped_positions = h->ring.positions;
+        return KDF_OK;
     }
+    // otherwise: what the parent path does, from the start -- the ordinary flush of the same passes into the empty table
+    // (it dumps too, replays the failed buckets, grows the table); nothing of this attempt is counted.  Undone here is
+    // EVERYTHING kernel C<.., LAZY> accumulates into (the list at "what a bucket leaves behind" in kdf_binned.h):
+    // totals[2] and ctl->distinct below; s.failed, ctl->tally / cursor and the dump buffers are reset or rewritten by the
+    // second attempt.  Under kdf_profile the discarded launch stays in the C stage slot as a second C.
+    HIPCHK(h, hipMemsetAsync(f.s.totals + 2, 0, 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->ctl->distinct, 0, sizeof(h->ctl->distinct), h->stream));
+    h->distinct = 0;
+    *again = true;
+    return KDF_OK;
+}
+
+// The buckets kernel C flagged as failed go through the global-atomic kernel: INS (the kernel's) inserts their keys --
+// into a table grown to 2^grow_log2 slots first (0: the table stays) -- or, count --if, only probes for them.  who: the
+// message's subject.  *ring_kept: the one failure that leaves the ring as it is (the launch itself).
+template <bool INS>
+static int kb_replay(kdf_engine *h, const KbFlush &f, uint32_t grow_log2, const char *who, bool *ring_kept) {
+    int rc;
+    if (grow_log2 && (rc = table_rehash(h, grow_log2))) return rc;
+    by_width(h, [&](auto KWc) {
+        hipLaunchKernelGGL((kb_replay_kernel<decltype(KWc)::value, INS>), dim3((unsigned)f.nb_table), dim3(256), 0, h->stream, f.plan, f.s, h->t, h->ctl);
+        return 0;
+    });
+    *ring_kept = true;
+    HIPCHK(h, hipGetLastError());
+    *ring_kept = false;
+    bool full = false;
+    if ((rc = ctl_sync(h, &full))) return rc;
+    if (full) return fail(h, KDF_ERR_TABLE_FULL, "%s: bucket overflow during replay (capacity 2^%u)", who, h->t.log2cap);
+    return KDF_OK;
+}
+
+// keep the load <= 0.7 for what comes next (a 2048-slot bucket then holds
+// 1434 +- 38 keys: overflow, which is handled anyway, stays a rare event)
+static int kb_load_rule(kdf_engine *h) {
+    int rc;
+    while (h->distinct * 10 > h->cap * 7)
+        if ((rc = table_rehash(h, h->t.log2cap + 1))) return rc;
+    return KDF_OK;
+}
+
+// An ordinary flush is over: the fused dump, the failed buckets, the ring emptied, the load rule
+static int kb_settle(kdf_engine *h, const KbFlush &f, KbDump *dump, uint64_t cursor) {
+    int rc;
     // the fused dump is whole only if every bucket went through kernel C's write-back (none failed, none was left to the
     // heavy-bucket kernels); otherwise the caller dumps from the table as usual
-    if (fuse_min && h->kb_totals_host[2] == 0 && h->kb_totals_host[4] == 0) { h->fuse_done = true; h->fuse_n = cursor; h->stat_fused_dumps++; }
-    if (h->n_pass > h->n_dumped) h->stat_flushes++;           // (only retained passes: their dump-only flush was counted)
+    if (f.plan.dump_min && h->kb_totals_host[2] == 0 && h->kb_totals_host[4] == 0) { dump->done = true; dump->n = cursor; h->stat_fused_dumps++; }
+    if (h->ring.undumped_passes()) h->stat_flushes++;         // (only retained passes: their dump-only flush was counted)
     h->lazy_empty = false;
     h->stat_heavy_buckets += h->kb_totals_host[4];
     const uint64_t n_failed = h->kb_totals_host[2];
     if (n_failed) {
-        if (filtered) {
+        h->stat_replayed_buckets += n_failed;
+        bool ring_kept = false;
+        if (f.filtered) {
             // count --if: kernel C left these buckets as they were in HBM (a stored wide key whose hash word is the empty
             // marker; a full bucket probed for an absent key).  Their entries go through the direct filtered probe: the
             // keys stay put, the table does not grow, absent keys count nothing.
-            h->stat_replayed_buckets += n_failed;
-            by_width(h, [&](auto KWc) {
-                hipLaunchKernelGGL((kb_replay_kernel<decltype(KWc)::value, false>), dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
-                return 0;
-            });
-            HIPCHK(h, hipGetLastError());
-            if ((rc = ctl_sync(h, &full))) { (void)kb_ring_reset(h); return rc; }
-            if (full) { (void)kb_ring_reset(h); return fail(h, KDF_ERR_TABLE_FULL, "binned count --if: bucket overflow during replay (capacity 2^%u)", h->t.log2cap); }
-            return kb_ring_reset(h);
+            rc = kb_replay<false>(h, f, 0, "binned count --if", &ring_kept);
+        } else {
+            // some buckets overflowed: they are untouched in HBM.  Grow the table so
+            // that even if every entry of the failed buckets were new the load stays
+            // <= 0.5, then replay exactly those buckets through the global-atomic path.
+            const uint64_t worst = h->distinct + std::min<uint64_t>(f.n_entries, n_failed * ((f.n_entries / std::max<uint64_t>(f.nb_table, 1)) * 4 + 4096));
+            rc = kb_replay<true>(h, f, std::max<uint32_t>(h->t.log2cap + 1, cap_log2_for(worst)), "binned count", &ring_kept);
         }
-        // some buckets overflowed: they are untouched in HBM.  Grow the table so
-        // that even if every entry of the failed buckets were new the load stays
-        // <= 0.5, then replay exactly those buckets through the global-atomic path.
-        h->stat_replayed_buckets += n_failed;
-        const uint64_t worst = h->distinct + std::min<uint64_t>(n_entries, n_failed * ((n_entries / std::max<uint64_t>(nb_table, 1)) * 4 + 4096));
-        const uint32_t want = std::max<uint32_t>(h->t.log2cap + 1, cap_log2_for(worst));
-        if ((rc = table_rehash(h, want))) { (void)kb_ring_reset(h); return rc; }
-        by_width(h, [&](auto KWc) {
-            hipLaunchKernelGGL(kb_replay_kernel<decltype(KWc)::value>, dim3((unsigned)nb_table), dim3(256), 0, h->stream, plan, s, h->t, h->ctl);
-            return 0;
-        });
-        HIPCHK(h, hipGetLastError());
-        if ((rc = ctl_sync(h, &full))) { (void)kb_ring_reset(h); return rc; }
-        if (full) { (void)kb_ring_reset(h); return fail(h, KDF_ERR_TABLE_FULL, "binned count: bucket overflow during replay (capacity 2^%u)", h->t.log2cap); }
+        if (rc) {                                              // the one error exit behind the launch that empties the ring
+            if (!ring_kept) (void)kb_ring_reset(h);
+            return rc;
+        }
     }
-    if (!filtered && n_entries >= 100000) h->grow_ratio = (double)(h->distinct - distinct_before) / (double)n_entries;
+    if (!f.filtered && f.n_entries >= 100000) h->grow_ratio = (double)(h->distinct - f.c.distinct_before) / (double)f.n_entries;
     if ((rc = kb_ring_reset(h))) return rc;
-    // keep the load <= 0.7 for what comes next (a 2048-slot bucket then holds
-    // 1434 +- 38 keys: overflow, which is handled anyway, stays a rare event)
-    if (!filtered)
-        while (h->distinct * 10 > h->cap * 7)
-            if ((rc = table_rehash(h, h->t.log2cap + 1))) return rc;
-    return KDF_OK;
+    return f.filtered ? KDF_OK : kb_load_rule(h);
+}
+
+// one attempt at the flush; *again: it was a dump-only attempt that has to be redone the ordinary way
+static int kb_flush_attempt(kdf_engine *h, KbDump *dump, bool dump_only_ok, bool *again) {
+    int rc;
+    KbFlush f;
+    if ((rc = kb_flush_totals(h, f))) return rc;
+    f.c = kb_flush_choose(h, f, dump, dump_only_ok);
+    if (f.c.grow_first && (rc = kb_grow_first(h, f.c.est))) return rc;
+    if ((rc = kb_flush_prepare(h, f, dump))) return rc;
+    if (f.plan.dbg & 2048) return kb_ring_reset(h);               // (ablation: the partition passes are timed alone, what they wrote is dropped)
+    if ((rc = kb_flush_launch(h, f))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
+    bool full = false;
+    uint64_t cursor = 0;
+    if ((rc = ctl_sync(h, &full, &cursor))) return rc;
+    return f.c.dump_only ? kb_settle_dump_only(h, f, dump, cursor, again) : kb_settle(h, f, dump, cursor);
+}
+
+// Kernel C over every pending pass.  dump: a dump is waiting for this flush (the caller's last before it) -- kernel C
+// writes it, and the dump-only flush is allowed; its fallback is a second, ordinary attempt with the same request.
+static int kb_flush_ring(kdf_engine *h, KbDump *dump) {
+    if (h->ring.empty()) return KDF_OK;
+    bool again = false;
+    int rc = kb_flush_attempt(h, dump, dump != nullptr, &again);
+    if (!rc && again) rc = kb_flush_attempt(h, dump, false, &again);
+    return rc;
 }
 
 // can the binned pipeline work on this engine's table at all?
@@ -1097,8 +1201,9 @@ static bool kb_eligible(const kdf_engine *h) {
 
 // Is a flush of n_bases pending positions worth the binned pipeline?  Kernel C reads and rewrites EVERY bucket of the
 // table (0.5 ms per GB), whatever the pending passes hold; the direct kernels cost 0.056 ms per million positions whatever
-// the table.  Crossover (scratch/bigtable_probe.py): ~14 M positions per GB of table.
-static bool use_binned(const kdf_engine *h, uint64_t n_bases, bool filtered) {
+// the table.  Crossover (scratch/bigtable_probe.py): ~14 M positions per GB of table.  table_empty: the table is only
+// logically empty (the engine's lazy_empty, or false to ask what an engine with a live table would do).
+static bool use_binned(const kdf_engine *h, uint64_t n_bases, bool filtered, bool table_empty) {
     if (!kb_eligible(h)) return false;
     if (h->opt_force_path == 2) return true;
     if (n_bases < h->opt_binned_min_positions) return false;
@@ -1107,7 +1212,7 @@ static bool use_binned(const kdf_engine *h, uint64_t n_bases, bool filtered) {
     // (a table that was only `clear`ed: the binned flush is also its clear, the direct path pays a memset first --
     // 0.2 ms per GB -- which moves the crossover to ~8.6 M positions per GB)
     const uint64_t table_bytes = h->cap * (uint64_t)(8 * h->kw + 4);
-    const uint64_t per = h->lazy_empty ? h->opt_binned_bytes_per_position * 5 / 3 : h->opt_binned_bytes_per_position;
+    const uint64_t per = table_empty ? h->opt_binned_bytes_per_position * 5 / 3 : h->opt_binned_bytes_per_position;
     return n_bases * per >= table_bytes;
 }
 
@@ -1150,61 +1255,53 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
 // or a window of this batch's last k - 1 positions would run on into the next batch's first bases.
 static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     const uint64_t n_tiles = n_bases / KDF_TILE + 1;
-    if (h->l1_tiles + n_tiles > h->l1_cap_tiles) {
+    if (h->l1.tiles + n_tiles > h->l1.cap_tiles) {
         // grow (the pending stream moves): up to the size at which it is partitioned anyway
-        const uint64_t target = std::max<uint64_t>((h->opt_l1_positions + h->opt_l1_direct_positions) / KDF_TILE + 1, h->l1_tiles + n_tiles);
-        const uint64_t cap = std::min<uint64_t>(target, std::max<uint64_t>({2 * h->l1_cap_tiles, 4 * (h->l1_tiles + n_tiles), (uint64_t)1 << 18}));
+        const uint64_t target = std::max<uint64_t>((h->opt_l1_positions + h->opt_l1_direct_positions) / KDF_TILE + 1, h->l1.tiles + n_tiles);
+        const uint64_t cap = std::min<uint64_t>(target, std::max<uint64_t>({2 * h->l1.cap_tiles, 4 * (h->l1.tiles + n_tiles), (uint64_t)1 << 18}));
         uint64_t *np = nullptr, *nm = nullptr;
         HIPCHK(h, hipMalloc((void **)&np, (cap * 2 + 4) * 8));
         hipError_t e = hipMalloc((void **)&nm, (cap + 2) * 8);
         if (e != hipSuccess) { (void)hipFree(np); (void)hipGetLastError(); return fail(h, KDF_ERR_NOMEM, "pending stream: %s", hipGetErrorString(e)); }
-        if (h->l1_tiles) {
-            HIPCHK(h, hipMemcpyAsync(np, h->l1_packed, (h->l1_tiles * 2 + 4) * 8, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(nm, h->l1_mask, (h->l1_tiles + 2) * 8, hipMemcpyDeviceToDevice, h->stream));
+        if (h->l1.tiles) {
+            HIPCHK(h, hipMemcpyAsync(np, h->l1.packed, (h->l1.tiles * 2 + 4) * 8, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(nm, h->l1.mask, (h->l1.tiles + 2) * 8, hipMemcpyDeviceToDevice, h->stream));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->l1_packed) (void)hipFree(h->l1_packed);
-        if (h->l1_mask) (void)hipFree(h->l1_mask);
-        h->l1_packed = np; h->l1_mask = nm; h->l1_cap_tiles = cap;
+        if (h->l1.packed) (void)hipFree(h->l1.packed);
+        if (h->l1.mask) (void)hipFree(h->l1.mask);
+        h->l1.packed = np; h->l1.mask = nm; h->l1.cap_tiles = cap;
     }
     const unsigned blocks = (unsigned)((2 * n_tiles + 4 + 255) / 256);               // (covers the kernel's ceil(n_bases / 64) tiles + padding)
-    hipLaunchKernelGGL(kb_append_kernel, dim3(blocks), dim3(256), 0, h->stream, h->l1_packed + 2 * h->l1_tiles, h->l1_mask + h->l1_tiles,
+    hipLaunchKernelGGL(kb_append_kernel, dim3(blocks), dim3(256), 0, h->stream, h->l1.packed + 2 * h->l1.tiles, h->l1.mask + h->l1.tiles,
                        d_packed, d_invalid, n_bases);
     HIPCHK(h, hipGetLastError());
-    h->l1_tiles += n_tiles;
+    h->l1.tiles += n_tiles;
     return KDF_OK;
 }
 
-// everything pending (the concatenated small batches, the partitioned passes) goes into the table
-int pending_flush(kdf_engine *h, bool fuse) {
+// everything pending (the concatenated small batches, the partitioned passes) goes into the table.  dump: a request the
+// LAST flush may serve (earlier ones see counts that are not final)
+int pending_flush(kdf_engine *h, KbDump *dump) {
     int rc;
-    const uint32_t want_fuse = fuse ? h->fuse_min : 0u;
-    h->fuse_min = 0; h->fuse_done = false;                     // (only the LAST flush below may dump: earlier ones see counts that are not final)
-    if (h->l1_tiles && h->n_dumped && h->n_pass == h->n_dumped) {
+    if (h->l1.tiles && h->ring.n_dumped && !h->ring.undumped_passes()) {
         // small batches behind passes that only a dump-only flush has applied: without lazy_table the ring would be empty
         // and the table live here.  Choose as that engine would; a batch it sends through the direct kernels gets the
         // table first (same last_count_path / binned_passes, and no second rewrite of the table for a few reads)
-        const bool le = h->lazy_empty;
-        h->lazy_empty = false;
-        const bool binned = use_binned(h, h->l1_tiles * KDF_TILE, false);
-        h->lazy_empty = le;
-        if (!binned && (rc = kb_flush_ring(h))) return rc;
+        if (!use_binned(h, h->l1.positions(), false, false) && (rc = kb_flush_ring(h))) return rc;
     }
-    if (h->l1_tiles) {
-        const uint64_t n = h->l1_tiles * KDF_TILE;
-        h->l1_tiles = 0;
-        if (h->n_pass > 0 ? kb_eligible(h) : use_binned(h, n, false)) rc = kb_partition_stream(h, h->l1_packed, h->l1_mask, n, false);
-        else rc = direct_insert(h, h->l1_packed, h->l1_mask, n);
+    if (h->l1.tiles) {
+        const bool binned = h->ring.empty() ? use_binned(h, h->l1.positions(), false, h->lazy_empty) : kb_eligible(h);
+        const uint64_t n = h->l1.take();
+        if (binned) rc = kb_partition_stream(h, h->l1.packed, h->l1.mask, n, false);
+        else rc = direct_insert(h, h->l1.packed, h->l1.mask, n);
         if (rc) return rc;
     }
-    h->fuse_min = want_fuse;
-    rc = kb_flush_ring(h, fuse);
-    h->fuse_min = 0;
-    return rc;
+    return kb_flush_ring(h, dump);
 }
 // ... or is forgotten (kdf_clear)
 static int pending_drop(kdf_engine *h) {
-    h->l1_tiles = 0;
+    h->l1.tiles = 0;
     return kb_ring_reset(h);
 }
 
@@ -1226,11 +1323,7 @@ static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint6
     } else if (n_bases >= h->opt_l1_direct_positions) rc = kb_partition_stream(h, d_packed, d_invalid, n_bases, false);   // big enough by itself
     else {
         rc = l1_append(h, d_packed, d_invalid, n_bases);
-        if (!rc && h->l1_tiles * KDF_TILE >= h->opt_l1_positions) {
-            const uint64_t n = h->l1_tiles * KDF_TILE;
-            h->l1_tiles = 0;
-            rc = kb_partition_stream(h, h->l1_packed, h->l1_mask, n, false);
-        }
+        if (!rc && h->l1.positions() >= h->opt_l1_positions) rc = kb_partition_stream(h, h->l1.packed, h->l1.mask, h->l1.take(), false);
     }
     if (rc) return rc;
     if (!h->opt_defer) return pending_flush(h);
@@ -1380,7 +1473,7 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
         return KDF_OK;
     }
     if (h->opt_force_path == 4) return fail(h, KDF_ERR_STATE, "force_path 4 (sieve): no sieve for this filter (it would not fit the caches, or keys were added after kdf_load_filter)");
-    if (use_binned(h, n_bases, true)) {
+    if (use_binned(h, n_bases, true, h->lazy_empty)) {
         int rc = kb_partition_stream(h, d_packed, d_invalid, n_bases, true);
         if (!rc && !h->opt_defer) rc = kb_flush_ring(h);
         return rc;
@@ -1594,8 +1687,8 @@ void kdf_destroy(kdf_engine *h) {
     pf_free(h);
     sk_free(h);
     for (DevBuf &b : h->buf) b.release();
-    if (h->l1_packed) (void)hipFree(h->l1_packed);
-    if (h->l1_mask) (void)hipFree(h->l1_mask);
+    if (h->l1.packed) (void)hipFree(h->l1.packed);
+    if (h->l1.mask) (void)hipFree(h->l1.mask);
     if (h->kb_pass) (void)hipFree(h->kb_pass);
     if (h->kb_heavy) (void)hipFree(h->kb_heavy);
     for (int sl = 0; sl < 2; ++sl) {
@@ -1656,7 +1749,7 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     HIPCHK(h, hipSetDevice(h->device));
     // (passes a dump-only flush has applied: their keys and windows are in the counters already, the table is not needed)
-    if (h->l1_tiles || h->n_pass > h->n_dumped) { int rcf = pending_flush(h); if (rcf) return rcf; }
+    if (h->l1.tiles || h->ring.undumped_passes()) { int rcf = pending_flush(h); if (rcf) return rcf; }
     bool full = false;
     int rc = ctl_sync(h, &full);
     if (rc) return rc;
@@ -2038,10 +2131,10 @@ static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *
                        uint32_t *ocnt, uint64_t out_cap, uint64_t *n_out) {
     // passes pending: the flush that applies them holds every bucket of the table in LDS once -- it writes the dump too
     // (kb_bucket_kernel, KbPlan::dump_min) unless a bucket took another way (overflow replay, heavy-bucket split)
-    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->n_pass > h->n_dumped || h->l1_tiles > 0);
-    if (fuse) { h->fuse_min = min_count; h->fuse_lo = olo; h->fuse_hi = ohi; h->fuse_cnt = ocnt; h->fuse_cap = out_cap; }
-    { int rcf = pending_flush(h, fuse); if (rcf) return rcf; }
-    if (fuse && h->fuse_done) { h->fuse_done = false; *n_out = h->fuse_n; return KDF_OK; }
+    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->ring.undumped_passes() || h->l1.tiles > 0);
+    KbDump dump{min_count, olo, ohi, ocnt, out_cap};
+    { int rcf = pending_flush(h, fuse ? &dump : nullptr); if (rcf) return rcf; }
+    if (dump.done) { *n_out = dump.n; return KDF_OK; }
     { int rc0 = materialize(h); if (rc0) return rc0; }
     HIPCHK(h, hipMemsetAsync(h->ctl->tally, 0, sizeof(h->ctl->tally) + 8, h->stream));   // tally[] + cursor
     const uint64_t waves = (h->cap + KDF_EXPORT_ROWS * 64 - 1) / (KDF_EXPORT_ROWS * 64);
@@ -3242,8 +3335,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     else if (n == "big_bucket_log2cap") {
         if (value < 10 || value > 64) return fail(h, KDF_ERR_INVALID, "big_bucket_log2cap must be 10..64");
         h->opt_big_bucket_log2cap = (uint32_t)value;
-        const uint32_t bb = std::min<uint32_t>(h->t.log2cap, KB_BB_SMALL(h->kw) + (h->t.log2cap >= h->opt_big_bucket_log2cap ? 1u : 0u));
-        if (bb != h->t.bucket_bits) { int rc = table_rehash(h, h->t.log2cap); if (rc) return rc; }     // same slots, other buckets
+        if (bucket_bits_for(h, h->t.log2cap) != h->t.bucket_bits) { int rc = table_rehash(h, h->t.log2cap); if (rc) return rc; }     // same slots, other buckets
     }
     else if (n == "force_path") {
         if (value != 0 && value != 1 && value != 2 && value != 4)
@@ -3330,13 +3422,13 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     // (pending: not yet applied by any flush.  Passes a dump-only flush has applied are kept in the ring -- "retained_passes" --
     // until the table is asked for or cleared)
-    else if (n == "pending_passes") *value = (int64_t)(h->n_pass - h->n_dumped);
-    else if (n == "pending_positions") *value = (int64_t)(h->pend_positions - h->dumped_positions + h->l1_tiles * KDF_TILE);
-    else if (n == "retained_passes") *value = (int64_t)h->n_dumped;
+    else if (n == "pending_passes") *value = (int64_t)h->ring.undumped_passes();
+    else if (n == "pending_positions") *value = (int64_t)(h->ring.undumped_positions() + h->l1.positions());
+    else if (n == "retained_passes") *value = (int64_t)h->ring.n_dumped;
     else if (n == "dump_only_flushes") *value = (int64_t)h->stat_dump_only;
     else if (n == "materialisations") *value = (int64_t)h->stat_materialisations;
     else if (n == "lazy_table") *value = h->opt_lazy_table;
-    else if (n == "ring_bytes") *value = (int64_t)(h->ring_entries * 8 * h->kw);
+    else if (n == "ring_bytes") *value = (int64_t)(h->ring.cap_entries * 8 * h->kw);
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
     else if (n == "last_scan_path") *value = h->last_scan_path;
@@ -3351,8 +3443,8 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "log2cap") *value = h->t.log2cap;
     else if (n == "bucket_bits") *value = h->t.bucket_bits;
     // the binned path's split of the bucket bits: of the pending passes, or what the next pass would be partitioned with
-    else if (n == "c1") *value = (h->n_pass ? h->pend_plan : kb_make_plan(h, h->t)).c1;
-    else if (n == "c2") *value = (h->n_pass ? h->pend_plan : kb_make_plan(h, h->t)).c2;
+    else if (n == "c1") *value = (h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan).c1;
+    else if (n == "c2") *value = (h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan).c2;
     else if (n.rfind("trash", 0) == 0 && n.size() > 5 && h->kb_small) {          // (variant builds with -DKB_TIMING: phase cycle sums)
         const int i = atoi(n.c_str() + 5);
         if (i < 0 || i >= 64) return fail(h, KDF_ERR_INVALID, "kdf_get_stat: trash0..trash63");

@@ -27,6 +27,38 @@ enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = 
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
 enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_COUNT };
 static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join"};
+// The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
+// table is needed or the ring is full (kb_flush_ring).  Reserved by upper bounds (one entry per stream position), so no
+// host round trip sits between the stages.  Host only: what the kernels take of it is KbPlan (kdf_device.h).
+struct KbRing {
+    uint64_t cap_entries = 0, cap_rows = 0;          // capacity: entries (8 B x kw each), rows (pieces); kept over reset()
+    uint64_t used_entries = 0, used_rows = 0;        // reserved by the pending passes
+    uint32_t n_pass = 0;
+    uint32_t n_dumped = 0;                           // pending passes a dump-only flush has applied: kept for the table, reported as flushed
+    uint64_t positions = 0;                          // stream positions of the pending passes (upper bound of their entries)
+    uint64_t dumped_positions = 0;                   // ... and of the first n_dumped of them
+    uint64_t acct_entries = 0, acct_positions = 0;   // what of the pending passes dens_windows / dens_positions already hold
+    KbPlan plan{};                                   // geometry (c1, c2, key slice) the pending passes were partitioned with
+    bool filtered = false;                           // the pending passes are count --if passes
+    bool empty() const { return n_pass == 0; }
+    uint32_t undumped_passes() const { return n_pass - n_dumped; }                 // not yet applied by any flush
+    uint64_t undumped_positions() const { return positions - dumped_positions; }
+    // the only place the ring is emptied (kb_ring_reset: with the flush-wide device counters); plan / filtered are set by the next first pass
+    void reset() { used_entries = used_rows = 0; n_pass = n_dumped = 0; positions = dumped_positions = 0; acct_entries = acct_positions = 0; }
+};
+// L1: small insert batches are concatenated (packed) in a pending stream first; the partition runs over ~2^30 positions
+struct KbPendStream {
+    uint64_t *packed = nullptr, *mask = nullptr;
+    uint64_t cap_tiles = 0, tiles = 0;
+    uint64_t positions() const { return tiles * KDF_TILE; }
+    uint64_t take() { const uint64_t n = positions(); tiles = 0; return n; }      // the stream is handed on (packed, mask: n positions) and empty again
+};
+// The request a dump hands to the LAST flush before it, and what came of it.  It lives on the dump's stack (export_pass):
+// a flush that was not handed one cannot write a dump.
+struct KbDump {
+    uint32_t min_count = 0; uint64_t *lo = nullptr, *hi = nullptr; uint32_t *cnt = nullptr; uint64_t cap = 0;     // the request
+    bool done = false; uint64_t n = 0;                                                                             // the result: written whole, n keys
+};
 struct kdf_engine {
     int device = 0;
     int k = 0;
@@ -52,21 +84,11 @@ struct kdf_engine {
     unsigned long long *kb_totals_host = nullptr;   // pinned [16]
     DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
     KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
-    // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
-    // table is needed or the ring is full (kb_flush).  Reserved by upper bounds (one entry per stream position), so no
-    // host round trip sits between the stages.
-    uint64_t ring_entries = 0, ring_rows = 0;        // capacity: entries (8 B x kw each), rows (pieces)
-    uint64_t ring_used = 0, rows_used = 0;           // reserved by the pending passes
-    uint32_t n_pass = 0;
-    uint64_t pend_positions = 0;                     // stream positions of the pending passes (upper bound of their entries)
-    KbPlan pend_plan{};                              // geometry (c1, c2, key slice) the pending passes were partitioned with
-    bool pend_filtered = false;                      // the pending passes are count --if passes
+    KbRing ring;                                     // the pending passes (above)
     uint64_t stat_flushes = 0;
     double grow_ratio = 0.0;                         // new distinct keys per counted window at the last flush (0: unknown)
     uint64_t dens_windows = 0, dens_positions = 0;   // valid windows / stream positions of every pass this engine has flushed: sizes the piece groups
-    // L1: small insert batches are concatenated (packed) in a pending stream first; the partition runs over ~2^30 positions
-    uint64_t *l1_packed = nullptr, *l1_mask = nullptr;
-    uint64_t l1_cap_tiles = 0, l1_tiles = 0;
+    KbPendStream l1;                                 // small insert batches waiting to be partitioned (above)
     uint32_t opt_key_parts = 0, opt_key_part = 0;    // count only one slice of the key space (KdfTable::key_parts)
     uint64_t opt_binned_min_positions = 1ull << 22;  // fewer pending positions at flush time use the direct global-table kernels
     uint64_t opt_binned_bytes_per_position = 70;     // ... and so does a flush of fewer than table_bytes / 70 positions (use_binned)
@@ -82,18 +104,12 @@ struct kdf_engine {
     // flush itself -- kernel C holds every bucket anyway (kb_bucket_kernel<.., DUMP>), and the dump's pass over the table is
     // saved.  Option "fused_dump" / env KDF_FUSED_DUMP=0 turn it off; long engines have no binned pipeline: 0
     int opt_fused_dump = [] { const char *e = getenv("KDF_FUSED_DUMP"); return e ? atoi(e) != 0 : 1; }();
-    // the request a dump hands to the LAST flush before it (fuse_min > 0), and what came of it
-    uint32_t fuse_min = 0; uint64_t *fuse_lo = nullptr, *fuse_hi = nullptr; uint32_t *fuse_cnt = nullptr; uint64_t fuse_cap = 0;
-    bool fuse_done = false; uint64_t fuse_n = 0;
     uint64_t stat_fused_dumps = 0;
     // 1 (the default): such a dump into a table that is still only logically empty (kdf_clear, nothing applied since) runs the
     // DUMP-ONLY flush -- kb_bucket_kernel<.., DUMP, LAZY> writes the dump and the ctl counters and leaves the table alone.  The
-    // passes stay in the ring (the first n_dumped of n_pass); whatever needs the table later applies them with the ordinary
+    // passes stay in the ring (KbRing: the first n_dumped of n_pass); whatever needs the table later applies them with the ordinary
     // flush, into the still empty table.  Option "lazy_table" / env KDF_LAZY_TABLE=0 turn it off.
     int opt_lazy_table = [] { const char *e = getenv("KDF_LAZY_TABLE"); return e ? atoi(e) != 0 : 1; }();
-    uint32_t n_dumped = 0;                           // pending passes a dump-only flush has applied: kept for the table, reported as flushed
-    uint64_t dumped_positions = 0;                   // ... and their stream positions
-    uint64_t acct_entries = 0, acct_positions = 0;   // what of the pending passes dens_windows / dens_positions already hold
     uint64_t stat_dump_only = 0, stat_materialisations = 0;
     uint64_t opt_l1_positions = 1ull << 30;          // pending-stream size from which it is partitioned
     uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
@@ -166,8 +182,8 @@ extern thread_local std::string g_err;    // the error text of calls without an 
 int fail(kdf_engine *h, int code, const char *fmt, ...);
 // kdf_clear defers the table's memset: everything that reads or probes the table calls this first
 int materialize(kdf_engine *h);
-// everything pending (the concatenated small batches, the partitioned passes) goes into the table
-int pending_flush(kdf_engine *h, bool fuse = false);
+// everything pending (the concatenated small batches, the partitioned passes) goes into the table; dump: the LAST flush may write it
+int pending_flush(kdf_engine *h, KbDump *dump = nullptr);
 // room for `bytes` in one of the engine's buffers whose readers all run on the engine's stream
 int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t) = slack_8th, const char *what = nullptr);
 // host arrays into staging slots 0 / 1 as a padded stream; `bytes` host bytes into staging slot i (stream order)

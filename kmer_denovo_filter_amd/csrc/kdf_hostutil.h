@@ -1,6 +1,7 @@
 // kdf_hostutil.h -- host plumbing the engine and the read spool share (no kernels): a grow-only device buffer, a HIP-event
-// timer and the read-offsets check.  Each takes what differs between its users as a parameter: the slack and the wait
-// before a free (DevBuf), the tag of a timed span (EvTimer), where a message goes (check_read_offsets).
+// timer with the stage stamps of the binned path, and the read-offsets check.  Each takes what differs between its users as a
+// parameter: the slack and the wait before a free (DevBuf), the tag of a timed span (EvTimer), where a message goes
+// (check_read_offsets).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -79,6 +80,27 @@ struct EvSpan {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         e0 = e1 = nullptr;
+    }
+};
+// The stamps between the stages of one launch group on stream s: stamp() records an event (with `on` false: nothing),
+// commit() hands the events over as one record; stamps that go out of scope uncommitted (an error return between the
+// launches) are destroyed.  (Hidden: the library's symbol table gains nothing by it.)
+struct __attribute__((visibility("hidden"))) StageStamps {
+    bool on; hipStream_t s;
+    std::vector<hipEvent_t> ev;
+    StageStamps(bool on_, hipStream_t s_) : on(on_), s(s_) {}
+    StageStamps(const StageStamps &) = delete;
+    StageStamps &operator=(const StageStamps &) = delete;
+    ~StageStamps() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    void stamp() {
+        hipEvent_t e = nullptr;
+        if (!on || hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        ev.push_back(e);
+    }
+    void commit(std::vector<std::vector<hipEvent_t>> &records) {
+        if (on) records.push_back(ev);
+        ev.clear();
     }
 };
 // stat "<name>_us" / "<name>_passes" of a table of timers (names[i] NULL: timer i has no stats of that form) -> the timer

@@ -50,6 +50,8 @@ def main():
     pa, bu = parse(sys.argv[1]), parse(sys.argv[2])
     print("## the three kernels of the flagship step (bench.py, k = 31)")
     for n in FLAG:
+        if n not in pa or n not in bu:                             # (a unit other than the core)
+            continue
         print(line(n, pa[n], bu[n]) + ("   scratch instructions %d -> %d" % (pa[n]["scratch"], bu[n]["scratch"])))
     ch = [n for n in sorted(bu) if n in pa and pa[n]["body"] != bu[n]["body"]]
     print("\n## every function whose instructions changed: %d of %d" % (len(ch), len(bu)))

@@ -57,8 +57,8 @@ def _count(e, which):
     e.count_dev(ds.packed.data_ptr(), ds.invalid.data_ptr(), ds.n_bases)
 
 
-def _raw_dump(e, min_count, cap):
-    """kdf_export_ge_dev into sentinel-filled buffers with 64 words of guard -> (rc, n, lo, hi, cnt) on the host"""
+def _raw_dump_dev(e, min_count, cap):
+    """kdf_export_ge_dev into sentinel-filled buffers with 64 words of guard -> (rc, n, lo, hi, cnt), the buffers still on the device"""
     import torch
     lo = torch.full((cap + 64,), SENT, dtype=torch.int64, device="cuda:0")
     hi = torch.full((cap + 64,), SENT, dtype=torch.int64, device="cuda:0") if e.wide else None
@@ -68,7 +68,13 @@ def _raw_dump(e, min_count, cap):
     rc = e._lib.kdf_export_ge_dev(e._h, int(min_count), c_void_p(lo.data_ptr()), c_void_p(hi.data_ptr()) if e.wide else None,
                                   c_void_p(cnt.data_ptr()), int(cap), 0, byref(n))
     torch.cuda.synchronize()
-    return rc, int(n.value), lo.cpu().numpy(), hi.cpu().numpy() if e.wide else None, cnt.cpu().numpy()
+    return rc, int(n.value), lo, hi, cnt
+
+
+def _raw_dump(e, min_count, cap):
+    """... -> (rc, n, lo, hi, cnt) on the host"""
+    rc, n, lo, hi, cnt = _raw_dump_dev(e, min_count, cap)
+    return rc, n, lo.cpu().numpy(), hi.cpu().numpy() if e.wide else None, cnt.cpu().numpy()
 
 
 def _sorted(lo, hi, cnt):
@@ -387,3 +393,29 @@ def test_a_small_batch_after_the_dump_goes_the_way_it_would_without_lazy_table(k
             res.append({w: e.get_stat(w) for w in WITNESSES})
             _same(_dump(e, 1), tab, 1)
     assert res[0] == res[1], res
+
+
+# ---- a finished dump request is gone ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("lazy", [1, 0])
+@pytest.mark.parametrize("cap", [1 << 17, 100])
+def test_h_a_finished_dump_request_is_gone(k, lazy, cap):
+    """The buffers of a dump belong to that call alone: no later flush, count or dump of the engine writes them again, whether
+    the dump fitted (2^17) or not (100: the call fails).  The first call's device buffers stay alive, so nothing else is
+    allocated where they lie."""
+    import torch
+    ta = _truth(k, ("a",))
+    full = int((ta[2] >= 2).sum())
+    with _engine(k, lazy) as e:
+        e.clear(); _count(e, "a")
+        rc, n, lo, hi, cnt = _raw_dump_dev(e, 2, cap)
+        first = [lo, cnt] + ([hi] if hi is not None else [])
+        copies = [t.cpu().numpy().copy() for t in first]
+        assert n == full and (rc == 0) == (cap >= full)
+        assert e.get_stat("fused_dumps") == 1 and e.get_stat("dump_only_flushes") == lazy
+        _count(e, "b"); e.flush()
+        _count(e, "small"); e.stats()
+        _same(_dump(e, 2), _truth(k, ("a", "b", "small")), 2)
+        torch.cuda.synchronize()
+        for t, c in zip(first, copies):
+            assert t.cpu().numpy().tobytes() == c.tobytes()
