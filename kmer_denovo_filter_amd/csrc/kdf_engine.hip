@@ -1504,24 +1504,31 @@ static int upload_padded(kdf_engine *h, const uint64_t *packed, const uint64_t *
     return KDF_OK;
 }
 
-int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
-                         uint64_t **d_packed, uint64_t **d_invalid) {
-    uint64_t pw, mw;
-    kdf_stream_words(n_bases, &pw, &mw);
-    int rc;
-    if ((rc = eng_reserve(h, h->stage[0], pw * 8))) return rc;
-    if ((rc = eng_reserve(h, h->stage[1], mw * 8))) return rc;
-    *d_packed = (uint64_t *)h->stage[0].p;
-    *d_invalid = (uint64_t *)h->stage[1].p;
-    return upload_padded(h, packed, invalid, n_bases, *d_packed, *d_invalid, h->stream);
-}
-
-// room for, and a copy of, `bytes` host bytes in staging slot i (stream order)
-int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn) {
-    int rc = eng_reserve(h, h->stage[i], bytes);
+// ---- the staging frame of a host form (kdf_engine_priv.h) ----
+int HostCall::commit() {
+    if (h->arena_user) return fail(h, KDF_ERR_STATE, "%s: the staging arena is still held by %s", fn, h->arena_user);
+    const int rc = eng_reserve(h, h->arena, lay.total);
     if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(h->stage[i].p, src, bytes, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "%s: copy of %zu bytes to the device failed: %s", fn, bytes, hipGetErrorString(e));
+    h->arena_user = fn; open = true;
+    for (int i = 0; i < lay.n; ++i) {
+        if (!item[i].src || !lay.size[i]) continue;
+        if (item[i].n_bases) {                                     // a stream: both halves, padded
+            const int rcs = upload_padded(h, (const uint64_t *)item[i].src, (const uint64_t *)item[i + 1].src, item[i].n_bases, dev<uint64_t>(i), dev<uint64_t>(i + 1), h->stream);
+            if (rcs) return rcs;
+            ++i;
+            continue;
+        }
+        const hipError_t e = hipMemcpyAsync(dev(i), item[i].src, lay.size[i], hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "%s: copy of %zu bytes to the device failed: %s", fn, lay.size[i], hipGetErrorString(e));
+    }
+    return KDF_OK;
+}
+int HostCall::fetch(int i, size_t bytes) {
+    if (bytes && item[i].dst) HIPCHK(h, hipMemcpyAsync(item[i].dst, dev(i), bytes, hipMemcpyDeviceToHost, h->stream));
+    return KDF_OK;
+}
+int HostCall::finish() {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
@@ -1532,15 +1539,17 @@ static int src_dev(kdf_engine *h, const char *fn, const void *d_packed, const vo
     return KDF_OK;
 }
 
-// host arrays, staged on the engine's stream (upload_stream); n_bases == 0: an empty source, nothing is asked or touched
-static int src_host(kdf_engine *h, const char *fn, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, StreamSrc &src) {
+// host arrays, staged on the engine's stream in the caller's frame, which stays open while the consumer is launched;
+// n_bases == 0: an empty source, nothing is asked or touched
+static int src_host(HostCall &c, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, StreamSrc &src) {
+    kdf_engine *h = c.h;
     src = StreamSrc{};
     if (n_bases == 0) return KDF_OK;
-    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "%s: NULL stream", fn);
+    if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "%s: NULL stream", c.fn);
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    const int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (!rc) src = StreamSrc{dp, dm, n_bases, -1};
+    const int s = c.stream(packed, invalid, n_bases);
+    const int rc = c.commit();
+    if (!rc) src = StreamSrc{c.dev<uint64_t>(s), c.dev<uint64_t>(s + 1), n_bases, -1};
     return rc;
 }
 
@@ -1627,11 +1636,11 @@ static int sk_pack(kdf_engine *h, uint8_t *d_out) {
     do { if ((h)->pf_state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
                                                        fn, (h)->pf_state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
 
-// n keys of a host form into staging slots 2 (lo, or the rows of long keys) and 3 (hi, k 33..63)
-static int stage_keys(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uint64_t n, const char *fn) {
-    int rc = stage_in(h, 2, lo, n * 8 * lo_words(h), fn);
-    if (!rc && h->kw == 2) rc = stage_in(h, 3, hi, n * 8, fn);
-    return rc;
+// n keys of a host form: the item of lo (or of the rows of long keys); the next one is hi (k 33..63, else empty)
+static int keys_in(HostCall &c, const uint64_t *lo, const uint64_t *hi, uint64_t n) {
+    const int i = c.in(lo, n * 8 * lo_words(c.h));
+    c.in(hi, c.h->kw == 2 ? n * 8 : 0);
+    return i;
 }
 
 // ===========================================================================
@@ -1775,8 +1784,9 @@ int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_inval
 
 int kdf_count_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    HostCall c(h, "kdf_count_reads");
     StreamSrc src;
-    const int rc = src_host(h, "kdf_count_reads", packed, invalid, n_bases, src);
+    const int rc = src_host(c, packed, invalid, n_bases, src);
     return rc || !src.n_bases ? rc : count_insert_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
@@ -1899,9 +1909,10 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
     KDF_REFUSE_LONG(h, "kdf_load_filter", "kdf_load_filter_w");
     if (n && (!keys_lo || (h->kw == 2 && !keys_hi))) return fail(h, KDF_ERR_INVALID, "kdf_load_filter: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if (n && (rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_load_filter"))) return rc;
-    return load_filter_core(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p, n, "kdf_load_filter");
+    HostCall c(h, "kdf_load_filter");
+    const int ik = keys_in(c, keys_lo, keys_hi, n);
+    if (const int rc = c.commit()) return rc;
+    return load_filter_core(h, c.dev<uint64_t>(ik), c.dev<uint64_t>(ik + 1), n, "kdf_load_filter");
 }
 
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n) {
@@ -2033,11 +2044,10 @@ int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_h
     if (n == 0) return KDF_OK;
     if (!keys_lo || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_add_pairs"))) return rc;
-    if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs"))) return rc;
-    return add_pairs_dev(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p,
-                         counts ? (const uint32_t *)h->stage[0].p : nullptr, n, "kdf_add_pairs");
+    HostCall c(h, "kdf_add_pairs");
+    const int ik = keys_in(c, keys_lo, keys_hi, n), ic = c.in(counts, counts ? n * 4 : 0);
+    if (const int rc = c.commit()) return rc;
+    return add_pairs_dev(h, c.dev<uint64_t>(ik), c.dev<uint64_t>(ik + 1), c.dev<uint32_t>(ic), n, "kdf_add_pairs");
 }
 
 int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n) {
@@ -2076,8 +2086,9 @@ int kdf_count_reads_filtered_dev(kdf_engine *h, const void *d_packed, const void
 int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     if (!h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads_filtered: no filter loaded (kdf_load_filter)");
+    HostCall c(h, "kdf_count_reads_filtered");
     StreamSrc src;
-    int rc = src_host(h, "kdf_count_reads_filtered", packed, invalid, n_bases, src);
+    int rc = src_host(c, packed, invalid, n_bases, src);
     if (rc || !src.n_bases || (rc = count_filtered_dev(h, src.packed, src.invalid, src.n_bases))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));   // staging buffers are reused by the next call
     return KDF_OK;
@@ -2118,13 +2129,11 @@ int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi, u
     if (n == 0) return KDF_OK;
     if (!keys_lo || !counts_out || (h->kw == 2 && !keys_hi)) return fail(h, KDF_ERR_INVALID, "kdf_query: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
+    HostCall c(h, "kdf_query");
+    const int ik = keys_in(c, keys_lo, keys_hi, n), io = c.out(counts_out, n * 4);
     int rc;
-    if ((rc = stage_keys(h, keys_lo, keys_hi, n, "kdf_query"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
-    if ((rc = query_core(h, (const uint64_t *)h->stage[2].p, (const uint64_t *)h->stage[3].p, n, (uint32_t *)h->stage[0].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if ((rc = c.commit()) || (rc = query_core(h, c.dev<uint64_t>(ik), c.dev<uint64_t>(ik + 1), n, c.dev<uint32_t>(io))) || (rc = c.fetch(io, n * 4))) return rc;
+    return c.finish();
 }
 
 static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *olo, uint64_t *ohi,
@@ -2289,11 +2298,11 @@ int kdf_histogram(kdf_engine *h, uint32_t high, uint64_t *bins_out) {
     if (high > KH_MAX_HIGH) return fail(h, KDF_ERR_INVALID, "kdf_histogram: high = %u is above the limit of %u", high, KH_MAX_HIGH);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t bytes = ((size_t)high + 2) * 8;
-    int rc = eng_reserve(h, h->stage[1], bytes);
-    if (rc) return rc;
-    if ((rc = histo_pass(h, high, (unsigned long long *)h->stage[1].p, "kdf_histogram"))) return rc;
-    HIPCHK(h, hipMemcpy(bins_out, h->stage[1].p, bytes, hipMemcpyDeviceToHost));
-    return KDF_OK;
+    HostCall c(h, "kdf_histogram");
+    const int ib = c.out(bins_out, bytes);
+    int rc;
+    if ((rc = c.commit()) || (rc = histo_pass(h, high, c.dev<unsigned long long>(ib), "kdf_histogram")) || (rc = c.fetch(ib, bytes))) return rc;
+    return c.finish();
 }
 
 int kdf_count_stats(kdf_engine *h, uint64_t *unique, uint64_t *distinct, uint64_t *total, uint64_t *max_count) {
@@ -2340,21 +2349,16 @@ static int export_host(kdf_engine *h, uint32_t min_count, uint64_t *lo_out, uint
     if (n == 0) return KDF_OK;
     if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
     if (!lo_out || (h->kw == 2 && !hi_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL key output", fn);
-    const size_t lo_bytes = n * 8 * lo_words(h);
-    if ((rc = eng_reserve(h, h->stage[2], lo_bytes))) return rc;
-    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
-    if (h->kw == 2 && (rc = eng_reserve(h, h->stage[3], n * 8))) return rc;
+    HostCall c(h, fn);
+    const size_t lo_bytes = n * 8 * lo_words(h), hi_bytes = h->kw == 2 ? n * 8 : 0;
+    const int ilo = c.out(lo_out, lo_bytes), ihi = c.out(hi_out, hi_bytes), icnt = c.out(cnt_out, n * 4);    // (the sort needs the counts)
+    if ((rc = c.commit())) return rc;
     uint64_t n2 = 0;
-    rc = export_core(h, min_count, (uint64_t *)h->stage[2].p, h->kw == 2 ? (uint64_t *)h->stage[3].p : nullptr, (uint32_t *)h->stage[0].p,
-                     n, true, &n2, fn, sort_err);
-    if (rc) return rc;
+    if ((rc = export_core(h, min_count, c.dev<uint64_t>(ilo), c.dev<uint64_t>(ihi), c.dev<uint32_t>(icnt), n, true, &n2, fn, sort_err))) return rc;
     if (n2 != n) return fail(h, KDF_ERR_STATE, "%s: table changed between passes", fn);
-    HIPCHK(h, hipMemcpyAsync(lo_out, h->stage[2].p, lo_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-    else if (hi_out) memset(hi_out, 0, n * 8);
-    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if (h->kw != 2 && hi_out) memset(hi_out, 0, n * 8);
+    if ((rc = c.fetch(ilo, lo_bytes)) || (rc = c.fetch(ihi, hi_bytes)) || (rc = c.fetch(icnt, n * 4))) return rc;
+    return c.finish();
 }
 
 int kdf_export_ge(kdf_engine *h, uint32_t min_count, uint64_t *keys_lo_out, uint64_t *keys_hi_out,
@@ -2456,14 +2460,13 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     if (n_bases == 0) return KDF_OK;
     if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_scan_reads: NULL stream");
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    if ((rc = eng_reserve(h, h->stage[2], mw * 8))) return rc;
-    if ((rc = kdf_scan_reads_dev(h, dp, dm, n_bases, h->stage[2].p))) return rc;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    HIPCHK(h, hipMemcpyAsync(hit_bits, h->stage[2].p, n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    {
+        HostCall c(h, "kdf_scan_reads");
+        const int is = c.stream(packed, invalid, n_bases), ib = c.out(hit_bits, mw * 8);
+        int rc;
+        if ((rc = c.commit()) || (rc = kdf_scan_reads_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(ib))) || (rc = c.fetch(ib, n_tiles * 8)) || (rc = c.finish())) return rc;
+    }
     if (!read_offsets || !distinct_out) return KDF_OK;
     // distinct hit k-mers per read: only reads with hits are touched
     std::vector<std::array<uint64_t, 7>> keys;
@@ -2536,8 +2539,9 @@ int kdf_prefilter_add_reads_dev(kdf_engine *h, const void *d_packed, const void 
 int kdf_prefilter_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     PF_NEED_TALLYING(h, "kdf_prefilter_add_reads");
+    HostCall c(h, "kdf_prefilter_add_reads");
     StreamSrc src;
-    const int rc = src_host(h, "kdf_prefilter_add_reads", packed, invalid, n_bases, src);
+    const int rc = src_host(c, packed, invalid, n_bases, src);
     return rc ? rc : pf_tally_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
@@ -2778,8 +2782,9 @@ int kdf_sketch_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_
 int kdf_sketch_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     SK_NEED_ON(h, "kdf_sketch_add_reads");
+    HostCall c(h, "kdf_sketch_add_reads");
     StreamSrc src;
-    const int rc = src_host(h, "kdf_sketch_add_reads", packed, invalid, n_bases, src);
+    const int rc = src_host(c, packed, invalid, n_bases, src);
     return rc ? rc : sk_add_dev(h, src.packed, src.invalid, src.n_bases);
 }
 
@@ -2917,10 +2922,12 @@ int kdf_prefilter_merge(kdf_engine *h, uint64_t first_word, uint64_t n_words, ui
     { int rc = pf_merge_check(h, "kdf_prefilter_merge", first_word, n_words, nseg, (const void *const *)segs); if (rc) return rc; }
     if (n_words == 0) return KDF_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    // staged piece by piece (at most 256 MB of staging): segment s of a piece at stage[0] + s * piece words
+    // staged piece by piece (at most 256 MB of staging): segment s of a piece at s * piece words of the one item
     const uint64_t piece = std::max<uint64_t>(2, std::min<uint64_t>(n_words + (n_words & 1), ((1ull << 25) / nseg) & ~1ull));
-    { int rc = eng_reserve(h, h->stage[0], (size_t)piece * nseg * 8); if (rc) return rc; }
-    unsigned long long *st = (unsigned long long *)h->stage[0].p;
+    HostCall c(h, "kdf_prefilter_merge");
+    const int ist = c.out(nullptr, (size_t)piece * nseg * 8);
+    { int rc = c.commit(); if (rc) return rc; }
+    unsigned long long *st = c.dev<unsigned long long>(ist);
     const unsigned long long *d[KDF_PF_MAX_SEGS];
     for (uint64_t w0 = 0; w0 < n_words; w0 += piece) {
         const uint64_t m = std::min<uint64_t>(piece, n_words - w0);
@@ -2931,8 +2938,7 @@ int kdf_prefilter_merge(kdf_engine *h, uint64_t first_word, uint64_t n_words, ui
         int rc = pf_merge_dev(h, first_word + w0, m, nseg, d, replace != 0);
         if (rc) return rc;
     }
-    HIPCHK(h, hipStreamSynchronize(h->stream));                  // (the caller's arrays are free again on return)
-    return KDF_OK;
+    return c.finish();                                           // (the caller's arrays are free again on return)
 }
 
 int kdf_key_words(int k) {
@@ -2956,10 +2962,10 @@ int kdf_add_pairs_w(kdf_engine *h, const uint64_t *keys, const uint32_t *counts,
     if (n == 0) return KDF_OK;
     if (!keys) return fail(h, KDF_ERR_INVALID, "kdf_add_pairs_w: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if ((rc = stage_keys(h, keys, nullptr, n, "kdf_add_pairs_w"))) return rc;
-    if (counts && (rc = stage_in(h, 0, counts, n * 4, "kdf_add_pairs_w"))) return rc;
-    return add_pairs_dev(h, (const uint64_t *)h->stage[2].p, nullptr, counts ? (const uint32_t *)h->stage[0].p : nullptr, n, "kdf_add_pairs_w");
+    HostCall c(h, "kdf_add_pairs_w");
+    const int ik = keys_in(c, keys, nullptr, n), ic = c.in(counts, counts ? n * 4 : 0);
+    if (const int rc = c.commit()) return rc;
+    return add_pairs_dev(h, c.dev<uint64_t>(ik), nullptr, c.dev<uint32_t>(ic), n, "kdf_add_pairs_w");
 }
 
 int kdf_load_filter_w_dev(kdf_engine *h, const void *d_keys, uint64_t n) {
@@ -2975,9 +2981,10 @@ int kdf_load_filter_w(kdf_engine *h, const uint64_t *keys, uint64_t n) {
     KDF_NEED_LONG(h, "kdf_load_filter_w");
     if (n && !keys) return fail(h, KDF_ERR_INVALID, "kdf_load_filter_w: NULL keys");
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
-    if (n && (rc = stage_keys(h, keys, nullptr, n, "kdf_load_filter_w"))) return rc;
-    return load_filter_core(h, (const uint64_t *)h->stage[2].p, nullptr, n, "kdf_load_filter_w");
+    HostCall c(h, "kdf_load_filter_w");
+    const int ik = keys_in(c, keys, nullptr, n);
+    if (const int rc = c.commit()) return rc;
+    return load_filter_core(h, c.dev<uint64_t>(ik), nullptr, n, "kdf_load_filter_w");
 }
 
 int kdf_query_w_dev(kdf_engine *h, const void *d_keys, uint64_t n, void *d_counts_out) {
@@ -2995,13 +3002,11 @@ int kdf_query_w(kdf_engine *h, const uint64_t *keys, uint64_t n, uint32_t *count
     if (n == 0) return KDF_OK;
     if (!keys || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_query_w: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
+    HostCall c(h, "kdf_query_w");
+    const int ik = keys_in(c, keys, nullptr, n), io = c.out(counts_out, n * 4);
     int rc;
-    if ((rc = stage_keys(h, keys, nullptr, n, "kdf_query_w"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
-    if ((rc = query_core(h, (const uint64_t *)h->stage[2].p, nullptr, n, (uint32_t *)h->stage[0].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if ((rc = c.commit()) || (rc = query_core(h, c.dev<uint64_t>(ik), nullptr, n, c.dev<uint32_t>(io))) || (rc = c.fetch(io, n * 4))) return rc;
+    return c.finish();
 }
 
 int kdf_export_ge_w_dev(kdf_engine *h, uint32_t min_count, void *d_keys_out, void *d_counts_out, uint64_t cap,
@@ -3078,8 +3083,8 @@ static int join_core(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, uint64_
     if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
     if (sorted && n) {
         if (!cnt && !is_long(h)) {                                   // the pair sort carries a payload: a scratch one
-            if ((rc = eng_reserve(h, h->stage[0], n * 4))) return rc;
-            cnt = (uint32_t *)h->stage[0].p;
+            if ((rc = eng_reserve(h, *h->merge_buf, n * 4))) return rc;         // (nothing that fills merge_buf runs inside a join)
+            cnt = (uint32_t *)h->merge_buf->p;
             HIPCHK(h, hipMemsetAsync(cnt, 0, n * 4, h->stream));
         }
         std::string serr;
@@ -3122,23 +3127,17 @@ static int join_host(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, uint64_
         room = n;
     }
     if (!keys_out || (h->kw == 2 && !hi_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL key output", fn);
-    if ((rc = eng_reserve(h, h->stage[2], room * 8 * lo_words(h)))) return rc;
-    if ((rc = eng_reserve(h, h->stage[0], room * 4))) return rc;
-    if ((rc = eng_reserve(h, h->stage[1], room * 4))) return rc;
-    if (h->kw == 2 && (rc = eng_reserve(h, h->stage[3], room * 8))) return rc;
-    rc = join_core(h, o, a, (uint64_t *)h->stage[2].p, h->kw == 2 ? (uint64_t *)h->stage[3].p : nullptr, (uint32_t *)h->stage[0].p,
-                   (uint32_t *)h->stage[1].p, room, true, &n, fn);
+    HostCall c(h, fn);
+    const int ik = c.out(keys_out, room * 8 * lo_words(h)), ihi = c.out(hi_out, h->kw == 2 ? room * 8 : 0);
+    const int icnt = c.out(cnt_out, room * 4), iocnt = c.out(ocnt_out, room * 4);
+    if ((rc = c.commit())) return rc;
+    rc = join_core(h, o, a, c.dev<uint64_t>(ik), c.dev<uint64_t>(ihi), c.dev<uint32_t>(icnt), c.dev<uint32_t>(iocnt), room, true, &n, fn);
     *n_out = n;
     if (rc) return rc;                                               // (more than cap: *n_out says how many)
     if (n == 0) return KDF_OK;
-    const size_t key_bytes = n * 8 * lo_words(h);
-    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[2].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
-    if (h->kw == 2) HIPCHK(h, hipMemcpyAsync(hi_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-    else if (hi_out) memset(hi_out, 0, n * 8);
-    if (cnt_out) HIPCHK(h, hipMemcpyAsync(cnt_out, h->stage[0].p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ocnt_out) HIPCHK(h, hipMemcpyAsync(ocnt_out, h->stage[1].p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if (h->kw != 2 && hi_out) memset(hi_out, 0, n * 8);
+    if ((rc = c.fetch(ik, n * 8 * lo_words(h))) || (rc = c.fetch(ihi, h->kw == 2 ? n * 8 : 0)) || (rc = c.fetch(icnt, n * 4)) || (rc = c.fetch(iocnt, n * 4))) return rc;
+    return c.finish();
 }
 
 int kdf_count_join(kdf_engine *h, kdf_engine *other, uint32_t min_count, uint32_t max_count, uint32_t other_min, uint32_t other_max,

@@ -7,6 +7,23 @@
 // no kernel header -- the structs of engine state that kernels take by value are in kdf_device.h -- and a kernel that a
 // second unit needs gets a host launcher declared below (kh_scan_launch).
 #pragma once
+#include <cstddef>
+#include <cstdint>
+
+// Where the temporary device copies of ONE host-form call lie in the engine's staging arena: items side by side in
+// registration order, each at a multiple of 256 bytes (what hipMalloc gave the separate buffers this replaces).  Plain
+// C++, no HIP call: a host compiler includes this part of the header alone (tests/native/stage_layout_check.cpp).
+struct StageLayout {
+    enum : size_t { ALIGN = 256 };
+    enum { MAX_ITEMS = 24 };                         // (the largest host form, kdf_variant_windows, registers 18)
+    size_t off[MAX_ITEMS], size[MAX_ITEMS], total = 0;
+    int n = 0;
+    int add(size_t bytes) { off[n] = total; size[n] = bytes; total += (bytes + ALIGN - 1) / ALIGN * ALIGN; return n++; }
+    // an item of 0 bytes is legal and has no address
+    void *at(void *base, int i) const { return size[i] ? (char *)base + off[i] : nullptr; }
+};
+
+#if defined(__HIP__)                         // everything below needs the HIP runtime
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -23,7 +40,7 @@ struct KbPass;                            // kdf_binned.h (the core)
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 4, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 6, BUF_BD = BUF_VAR + 5, BUF_COUNT = BUF_BD + 3 };
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 1, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 1, BUF_BD = BUF_VAR + 3, BUF_COUNT = BUF_BD + 3 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
 enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_COUNT };
 static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join"};
@@ -78,7 +95,8 @@ struct kdf_engine {
     bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
     bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
     DevBuf buf[BUF_COUNT];                           // released together (kdf_destroy); used through the views below
-    DevBuf *const stage = buf + BUF_STAGE;           // [4] staging for the host-buffer entry points
+    DevBuf &arena = buf[BUF_STAGE];                  // the staging of the host forms: laid out per call by a HostCall (below), touched by nothing else
+    const char *arena_user = nullptr;                // the host form whose HostCall is open (commit() .. its destructor), else NULL
     // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
     unsigned long long *kb_small = nullptr;   // totals[16]
     unsigned long long *kb_totals_host = nullptr;   // pinned [16]
@@ -120,7 +138,7 @@ struct kdf_engine {
     hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr}, use_done[2] = {nullptr, nullptr};
     uint64_t stat_heavy_buckets = 0;
     void *kb_heavy = nullptr;                        // heavy buckets of skewed flushes (kdf_binned.h kb_heavy_slice_kernel)
-    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly)
+    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly); the payload of a sorted join without counts
     uint32_t merge_flag_host = 0;
     int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
     int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
@@ -158,10 +176,10 @@ struct kdf_engine {
     uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
     // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
     DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
-    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch and the staging of the host forms -------------
-    DevBuf *const cov_buf = buf + BUF_COV;           // [6] 0 CIGAR prefix sums, 1 ref_start, 2 cigar, 3 cigar_offsets, 4 kmer_cov, 5 read_cov
-    // ---- VCF mode (kdf_variants.h): grow-only scratch and the staging of the host forms -------------------------------------
-    DevBuf *const var_buf = buf + BUF_VAR;           // [5] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags, 3 / 4 host forms: inputs / outputs
+    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch ------------------------------------------------
+    DevBuf *const cov_buf = buf + BUF_COV;           // [1] CIGAR prefix sums
+    // ---- VCF mode (kdf_variants.h): grow-only scratch ------------------------------------------------------------------------
+    DevBuf *const var_buf = buf + BUF_VAR;           // [3] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags
     // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
     bool sk_on = false;
     KdfSketch sk{};                                  // the register cells (device) and p
@@ -186,12 +204,41 @@ int materialize(kdf_engine *h);
 int pending_flush(kdf_engine *h, KbDump *dump = nullptr);
 // room for `bytes` in one of the engine's buffers whose readers all run on the engine's stream
 int eng_reserve(kdf_engine *h, DevBuf &b, size_t bytes, size_t (*slack)(size_t) = slack_8th, const char *what = nullptr);
-// host arrays into staging slots 0 / 1 as a padded stream; `bytes` host bytes into staging slot i (stream order)
-int upload_stream(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases, uint64_t **d_packed, uint64_t **d_invalid);
-int stage_in(kdf_engine *h, int i, const void *src, size_t bytes, const char *fn);
 // kdf_engine_reads.hip: kh_scan_kernel (kdf_hits.h) on stream s, for the spool's kdf_spool_select_reads
 void kh_scan_launch(hipStream_t s, unsigned long long *sums, uint64_t n);
 #pragma GCC visibility pop
+
+// The staging of ONE host-form call, built on its stack: the form registers every host array it hands to its _dev form
+// (in, stream) or gets back from it (out), commit() reserves the engine's arena once for all of them and copies the
+// inputs to the device, dev() gives the _dev form its pointers, fetch() copies results back and finish() waits for them.
+// All copies run on the engine's stream, in call order.  The arena belongs to the open frame: no code that a _dev entry
+// point reaches touches it, and a second commit() before the first frame is gone is refused (KDF_ERR_STATE).
+struct __attribute__((visibility("hidden"))) HostCall {
+    kdf_engine *const h; const char *const fn;       // fn: the host form, for messages
+    StageLayout lay;
+    struct { const void *src; void *dst; uint64_t n_bases; } item[StageLayout::MAX_ITEMS];   // n_bases > 0: the packed half of a stream (the mask half follows)
+    bool open = false;
+    HostCall(kdf_engine *h_, const char *fn_) : h(h_), fn(fn_) {}
+    HostCall(const HostCall &) = delete;
+    HostCall &operator=(const HostCall &) = delete;
+    ~HostCall() { if (open) h->arena_user = nullptr; }
+    int add(const void *src, void *dst, size_t bytes, uint64_t n_bases = 0) { const int i = lay.add(bytes); item[i] = {src, dst, n_bases}; return i; }
+    int in(const void *src, size_t bytes) { return add(src, nullptr, bytes); }
+    int out(void *dst, size_t bytes) { return add(nullptr, dst, bytes); }            // dst NULL: room only, the form copies by hand
+    int inout(void *p, size_t bytes) { return add(p, p, bytes); }                    // an accumulator: copied in, fetched back
+    // the padded stream of n_bases > 0 positions (upload_padded): the packed words' item, the mask words' is the next one
+    int stream(const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases) {
+        uint64_t pw, mw;
+        kdf_stream_words(n_bases, &pw, &mw);
+        const int i = add(packed, nullptr, pw * 8, n_bases);
+        add(invalid, nullptr, mw * 8);
+        return i;
+    }
+    template <typename T = void> T *dev(int i) const { return (T *)lay.at(h->arena.p, i); }
+    int commit();
+    int fetch(int i, size_t bytes);                  // the first `bytes` of output item i to its destination (it has none: nothing)
+    int finish();                                    // the one synchronisation
+};
 
 #define HIPCHK(h, call)                                                                 \
     do {                                                                                \
@@ -271,3 +318,4 @@ static int src_slot(S &&sink, const char *fn, kdf_engine *h, int slot, bool cons
     if (e != hipSuccess) return sink(e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "%s: waiting for the copy into slot %d failed: %s", fn, slot, hipGetErrorString(e));
     return KDF_OK;
 }
+#endif  // __HIP__

@@ -93,12 +93,6 @@ static int coverage_list_core(kdf_engine *h, const char *fn, const uint32_t *d_k
     return KDF_OK;
 }
 
-// several host arrays side by side in ONE device buffer, each at a multiple of 16 bytes
-struct Arena {
-    size_t off[16]; size_t bytes = 0; int n = 0;
-    int add(size_t b) { off[n] = bytes; bytes += (b + 15) / 16 * 16; return n++; }
-};
-
 // offsets that start at 0, do not decrease and end at `total` (cigar_offsets, qual_offsets, alt_offsets)
 static int check_offsets0(kdf_engine *h, const char *fn, const char *what, const int64_t *o, uint64_t n, uint64_t total) {
     if (!o) return fail(h, KDF_ERR_INVALID, "%s: %s is NULL", fn, what);
@@ -133,17 +127,13 @@ int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *inv
     if (n_bases == 0) return KDF_OK;
     if (!packed || !invalid || !counts_out) return fail(h, KDF_ERR_INVALID, "kdf_window_counts: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if ((rc = eng_reserve(h, h->stage[2], n_bases * 4))) return rc;
-    if (valid_bits_out && (rc = eng_reserve(h, h->stage[3], n_tiles * 8))) return rc;
-    if ((rc = kdf_window_counts_dev(h, dp, dm, n_bases, h->stage[2].p, valid_bits_out ? h->stage[3].p : nullptr))) return rc;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->stage[2].p, n_bases * 4, hipMemcpyDeviceToHost, h->stream));
-    if (valid_bits_out) HIPCHK(h, hipMemcpyAsync(valid_bits_out, h->stage[3].p, n_tiles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    const size_t valid_bytes = valid_bits_out ? (n_bases + KDF_TILE - 1) / KDF_TILE * 8 : 0;
+    HostCall c(h, "kdf_window_counts");
+    const int is = c.stream(packed, invalid, n_bases), ic = c.out(counts_out, n_bases * 4), iv = c.out(valid_bits_out, valid_bytes);
+    int rc;
+    if ((rc = c.commit()) || (rc = kdf_window_counts_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(ic), c.dev(iv))) ||
+        (rc = c.fetch(ic, n_bases * 4)) || (rc = c.fetch(iv, valid_bytes))) return rc;
+    return c.finish();
 }
 
 int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases, const void *d_read_offsets,
@@ -172,15 +162,12 @@ int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
     if (n_bases == 0) { memset(rows_out, 0, row_bytes); return KDF_OK; }
     if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_depth: NULL stream");
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    int rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm);
-    if (rc) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_depth"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
-    if ((rc = kdf_read_depth_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, low_max, h->stage[3].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    HostCall c(h, "kdf_read_depth");
+    const int is = c.stream(packed, invalid, n_bases), io = c.in(read_offsets, (size_t)(n_reads + 1) * 8), ir = c.out(rows_out, row_bytes);
+    int rc;
+    if ((rc = c.commit()) || (rc = kdf_read_depth_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(io), n_reads, low_max, c.dev(ir))) ||
+        (rc = c.fetch(ir, row_bytes))) return rc;
+    return c.finish();
 }
 
 // ------------------------------------------------ per-read hits of the scan (kdf_hits.h) ----
@@ -253,17 +240,13 @@ int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid
     if (!packed || !invalid) return fail(h, KDF_ERR_INVALID, "kdf_read_hits: NULL stream");
     if (n_reads == 0 && !hit_bits) return KDF_OK;
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
-    if (n_reads) {
-        if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_read_hits"))) return rc;
-        if ((rc = eng_reserve(h, h->stage[3], row_bytes))) return rc;
-    }
-    if ((rc = kdf_read_hits_dev(h, dp, dm, n_bases, n_reads ? h->stage[2].p : nullptr, n_reads, nullptr, n_reads ? h->stage[3].p : nullptr))) return rc;
-    if (n_reads) HIPCHK(h, hipMemcpyAsync(rows_out, h->stage[3].p, row_bytes, hipMemcpyDeviceToHost, h->stream));
+    HostCall c(h, "kdf_read_hits");
+    const int is = c.stream(packed, invalid, n_bases), io = c.in(read_offsets, n_reads ? (size_t)(n_reads + 1) * 8 : 0), ir = c.out(rows_out, row_bytes);
+    if ((rc = c.commit()) || (rc = kdf_read_hits_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(io), n_reads, nullptr, c.dev(ir))) ||
+        (rc = c.fetch(ir, row_bytes))) return rc;
+    // the mask is the _dev form's own buffer (it was given none), not staging
     if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0].p, (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    return c.finish();
 }
 
 int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, const void *d_read_offsets, int64_t n_reads,
@@ -302,19 +285,14 @@ int kdf_hit_list(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, cons
     if (n_bases == 0) return KDF_OK;
     if (!hit_bits || (cap && !positions_out)) return fail(h, KDF_ERR_INVALID, "kdf_hit_list: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_list"))) return rc;
-    if (reads_out && (rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_list"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
-    if (reads_out && (rc = eng_reserve(h, h->stage[3], cap * 8))) return rc;
-    const int rcl = kdf_hit_list_dev(h, h->stage[0].p, n_bases, reads_out ? h->stage[2].p : nullptr, reads_out ? n_reads : 0, h->stage[1].p,
-                                     reads_out ? h->stage[3].p : nullptr, cap, n_out);
+    HostCall c(h, "kdf_hit_list");
+    const int ib = c.in(hit_bits, (n_bases + 63) / 64 * 8), io = c.in(read_offsets, reads_out ? (size_t)(n_reads + 1) * 8 : 0);
+    const int ip = c.out(positions_out, cap * 8), ir = c.out(reads_out, reads_out ? cap * 8 : 0);
+    if ((rc = c.commit())) return rc;
+    const int rcl = kdf_hit_list_dev(h, c.dev(ib), n_bases, c.dev(io), reads_out ? n_reads : 0, c.dev(ip), c.dev(ir), cap, n_out);
     if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
     const uint64_t n = std::min<uint64_t>(*n_out, cap);
-    if (n) {
-        HIPCHK(h, hipMemcpyAsync(positions_out, h->stage[1].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (reads_out) HIPCHK(h, hipMemcpyAsync(reads_out, h->stage[3].p, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if (n && ((rc = c.fetch(ip, n * 8)) || (rc = c.fetch(ir, n * 8)) || (rc = c.finish()))) return rc;
     return rcl;
 }
 
@@ -378,20 +356,15 @@ int kdf_hit_coverage(kdf_engine *h, const uint64_t *hit_bits, uint64_t n_bases, 
     if (n_reads == 0 || n_bases == 0 || n_cigar == 0 || span == 0) return KDF_OK;
     if (!hit_bits || !cigar || !kmer_cov || !read_cov) return fail(h, KDF_ERR_INVALID, "kdf_hit_coverage: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
-    if ((rc = stage_in(h, 0, hit_bits, (n_bases + 63) / 64 * 8, "kdf_hit_coverage"))) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, "kdf_hit_coverage"))) return rc;
-    const void *src[5] = {ref_start, cigar, cigar_offsets, kmer_cov, read_cov};
-    const size_t bytes[5] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, (size_t)span * 4, (size_t)span * 4};
-    for (int i = 0; i < 5; ++i) {
-        if ((rc = eng_reserve(h, h->cov_buf[1 + i], bytes[i]))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cov_buf[1 + i].p, src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = kdf_hit_coverage_dev(h, h->stage[0].p, n_bases, h->stage[2].p, n_reads, h->cov_buf[1].p, h->cov_buf[2].p, n_cigar,
-                                   h->cov_buf[3].p, h->cov_buf[4].p, h->cov_buf[5].p, span))) return rc;
-    HIPCHK(h, hipMemcpyAsync(kmer_cov, h->cov_buf[4].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(read_cov, h->cov_buf[5].p, (size_t)span * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    HostCall c(h, "kdf_hit_coverage");
+    const size_t offs_bytes = (size_t)(n_reads + 1) * 8, cov_bytes = (size_t)span * 4;
+    const int ib = c.in(hit_bits, (n_bases + 63) / 64 * 8), io = c.in(read_offsets, offs_bytes), irs = c.in(ref_start, (size_t)n_reads * 8);
+    const int ic = c.in(cigar, (size_t)n_cigar * 4), ico = c.in(cigar_offsets, offs_bytes);
+    const int ik = c.inout(kmer_cov, cov_bytes), ir = c.inout(read_cov, cov_bytes);          // the accumulators
+    if ((rc = c.commit()) || (rc = kdf_hit_coverage_dev(h, c.dev(ib), n_bases, c.dev(io), n_reads, c.dev(irs), c.dev(ic), n_cigar, c.dev(ico),
+                                                        c.dev(ik), c.dev(ir), span)) ||
+        (rc = c.fetch(ik, cov_bytes)) || (rc = c.fetch(ir, cov_bytes))) return rc;
+    return c.finish();
 }
 
 int kdf_coverage_list_dev(kdf_engine *h, const void *d_kmer_cov, const void *d_read_cov, uint64_t first, uint64_t n, uint32_t min_reads,
@@ -413,26 +386,16 @@ int kdf_coverage_list(kdf_engine *h, const uint32_t *kmer_cov, const uint32_t *r
     if (!read_cov || (cap && !pos_out) || (kmer_out && !kmer_cov)) return fail(h, KDF_ERR_INVALID, "kdf_coverage_list: NULL pointer");
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    // the window alone is staged: cov_buf 4 / 5 the sums, stage 1 the positions, stage 0 / 3 the two value columns
-    if ((rc = eng_reserve(h, h->cov_buf[5], (size_t)n * 4))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->cov_buf[5].p, read_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    if (kmer_out) {
-        if ((rc = eng_reserve(h, h->cov_buf[4], (size_t)n * 4))) return rc;
-        HIPCHK(h, hipMemcpyAsync(h->cov_buf[4].p, kmer_cov + first, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-        if ((rc = eng_reserve(h, h->stage[0], cap * 4))) return rc;
-    }
-    if ((rc = eng_reserve(h, h->stage[1], cap * 8))) return rc;
-    if (read_out && (rc = eng_reserve(h, h->stage[3], cap * 4))) return rc;
-    const int rcl = coverage_list_core(h, "kdf_coverage_list", kmer_out ? (const uint32_t *)h->cov_buf[4].p : nullptr, (const uint32_t *)h->cov_buf[5].p,
-                                       first, n, min_reads, h->stage[1].p, kmer_out ? h->stage[0].p : nullptr, read_out ? h->stage[3].p : nullptr, cap, n_out);
+    // the window alone is staged
+    HostCall c(h, "kdf_coverage_list");
+    const int irc = c.in(read_cov + first, (size_t)n * 4), ikc = c.in(kmer_out ? kmer_cov + first : nullptr, kmer_out ? (size_t)n * 4 : 0);
+    const int ip = c.out(pos_out, cap * 8), iko = c.out(kmer_out, kmer_out ? cap * 4 : 0), iro = c.out(read_out, read_out ? cap * 4 : 0);
+    if ((rc = c.commit())) return rc;
+    const int rcl = coverage_list_core(h, "kdf_coverage_list", c.dev<uint32_t>(ikc), c.dev<uint32_t>(irc), first, n, min_reads, c.dev(ip), c.dev(iko),
+                                       c.dev(iro), cap, n_out);
     if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
     const uint64_t m = std::min<uint64_t>(*n_out, cap);
-    if (m) {
-        HIPCHK(h, hipMemcpyAsync(pos_out, h->stage[1].p, m * 8, hipMemcpyDeviceToHost, h->stream));
-        if (kmer_out) HIPCHK(h, hipMemcpyAsync(kmer_out, h->stage[0].p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        if (read_out) HIPCHK(h, hipMemcpyAsync(read_out, h->stage[3].p, m * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
+    if (m && ((rc = c.fetch(ip, m * 8)) || (rc = c.fetch(iko, m * 4)) || (rc = c.fetch(iro, m * 4)) || (rc = c.finish()))) return rc;
     return rcl;
 }
 
@@ -460,16 +423,14 @@ int kdf_hit_keys(kdf_engine *h, const uint64_t *packed, uint64_t n_bases, const 
     kdf_stream_words(n_bases, &pw, &mw);
     const uint64_t pw_in = (n_bases + 31) / 32;
     const size_t key_bytes = (size_t)n * 8 * (size_t)h->kw;
+    HostCall c(h, "kdf_hit_keys");
+    const int is = c.out(nullptr, pw * 8), ip = c.in(positions, (size_t)n * 8), ik = c.out(keys_out, key_bytes);      // is: the packed words alone, zero-padded below
     int rc;
-    if ((rc = eng_reserve(h, h->stage[0], pw * 8))) return rc;
-    HIPCHK(h, hipMemsetAsync(h->stage[0].p, 0, pw * 8, h->stream));
-    if (pw_in) HIPCHK(h, hipMemcpyAsync(h->stage[0].p, packed, pw_in * 8, hipMemcpyHostToDevice, h->stream));
-    if ((rc = stage_in(h, 1, positions, (size_t)n * 8, "kdf_hit_keys"))) return rc;
-    if ((rc = eng_reserve(h, h->stage[3], key_bytes))) return rc;
-    if ((rc = kdf_hit_keys_dev(h, h->stage[0].p, n_bases, h->stage[1].p, n, h->stage[3].p))) return rc;
-    HIPCHK(h, hipMemcpyAsync(keys_out, h->stage[3].p, key_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if ((rc = c.commit())) return rc;
+    HIPCHK(h, hipMemsetAsync(c.dev(is), 0, pw * 8, h->stream));
+    if (pw_in) HIPCHK(h, hipMemcpyAsync(c.dev(is), packed, pw_in * 8, hipMemcpyHostToDevice, h->stream));
+    if ((rc = kdf_hit_keys_dev(h, c.dev(is), n_bases, c.dev(ip), n, c.dev(ik))) || (rc = c.fetch(ik, key_bytes))) return rc;
+    return c.finish();
 }
 
 // ------------------------------------------------ VCF mode on the device (kdf_variants.h) ----
@@ -582,39 +543,24 @@ int kdf_variant_windows(kdf_engine *h, const uint64_t *packed, const uint64_t *i
     if (!packed || !invalid || !cigar || (n_alt && !alt) || (pair_cap && (!pair_read || !pair_var || !pair_flags)) || (entry_cap && (!entry_pos || !entry_pair)))
         return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
     HIPCHK(h, hipSetDevice(h->device));
-    uint64_t *dp, *dm;
-    if ((rc = upload_stream(h, packed, invalid, n_bases, &dp, &dm))) return rc;
-    if ((rc = stage_in(h, 2, read_offsets, (size_t)(n_reads + 1) * 8, fn))) return rc;
     const bool q = qual && min_baseq;
-    const void *src[10] = {ref_start, cigar, cigar_offsets, q ? qual : nullptr, q ? qual_offsets : nullptr, var_pos, var_span, var_ref_len, alt, alt_offsets};
-    const size_t bytes[10] = {(size_t)n_reads * 8, (size_t)n_cigar * 4, (size_t)(n_reads + 1) * 8, q ? (size_t)n_qual : 0, q ? (size_t)(n_reads + 1) * 8 : 0,
-                              (size_t)n_var * 8, (size_t)n_var * 4, (size_t)n_var * 4, (size_t)n_alt, (size_t)(n_var + 1) * 8};
-    Arena in, out;
-    for (int i = 0; i < 10; ++i) in.add(bytes[i]);
-    const size_t obytes[5] = {(size_t)pair_cap * 8, (size_t)pair_cap * 4, (size_t)pair_cap, (size_t)entry_cap * 8, (size_t)entry_cap * 8};
-    for (int i = 0; i < 5; ++i) out.add(obytes[i]);
-    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
-    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
-    for (int i = 0; i < 10; ++i)
-        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    auto ip = [&](int i) -> const void * { return di + in.off[i]; };
-    auto op = [&](int i) -> void * { return obytes[i] ? dout + out.off[i] : nullptr; };
-    const int rcl = kdf_variant_windows_dev(h, dp, dm, n_bases, h->stage[2].p, n_reads, ip(0), ip(1), n_cigar, ip(2), q ? ip(3) : nullptr, q ? n_qual : 0,
-                                            q ? ip(4) : nullptr, min_baseq, ip(5), ip(6), ip(7), n_var, ip(8), n_alt, ip(9), op(0), op(1), op(2), pair_cap,
-                                            op(3), op(4), entry_cap, n_pairs_out, n_entries_out);
+    const size_t offs_bytes = (size_t)(n_reads + 1) * 8;
+    HostCall c(h, fn);
+    const int is = c.stream(packed, invalid, n_bases), io = c.in(read_offsets, offs_bytes), irs = c.in(ref_start, (size_t)n_reads * 8);
+    const int ic = c.in(cigar, (size_t)n_cigar * 4), ico = c.in(cigar_offsets, offs_bytes);
+    const int iq = c.in(qual, q ? (size_t)n_qual : 0), iqo = c.in(qual_offsets, q ? offs_bytes : 0);
+    const int ivp = c.in(var_pos, (size_t)n_var * 8), ivs = c.in(var_span, (size_t)n_var * 4), ivr = c.in(var_ref_len, (size_t)n_var * 4);
+    const int ia = c.in(alt, (size_t)n_alt), iao = c.in(alt_offsets, (size_t)(n_var + 1) * 8);
+    const int opr = c.out(pair_read, (size_t)pair_cap * 8), opv = c.out(pair_var, (size_t)pair_cap * 4), opf = c.out(pair_flags, (size_t)pair_cap);
+    const int oep = c.out(entry_pos, (size_t)entry_cap * 8), oer = c.out(entry_pair, (size_t)entry_cap * 8);
+    if ((rc = c.commit())) return rc;
+    const int rcl = kdf_variant_windows_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(io), n_reads, c.dev(irs), c.dev(ic), n_cigar, c.dev(ico), c.dev(iq),
+                                            q ? n_qual : 0, c.dev(iqo), min_baseq, c.dev(ivp), c.dev(ivs), c.dev(ivr), n_var, c.dev(ia), n_alt, c.dev(iao),
+                                            c.dev(opr), c.dev(opv), c.dev(opf), pair_cap, c.dev(oep), c.dev(oer), entry_cap, n_pairs_out, n_entries_out);
     if (rcl && !(rcl == KDF_ERR_INVALID && (*n_pairs_out > pair_cap || *n_entries_out > entry_cap))) return rcl;
     const uint64_t np = std::min<uint64_t>(*n_pairs_out, pair_cap), ne = std::min<uint64_t>(*n_entries_out, entry_cap);
-    if (np) {
-        HIPCHK(h, hipMemcpyAsync(pair_read, op(0), np * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pair_var, op(1), np * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(pair_flags, op(2), np, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (ne) {
-        HIPCHK(h, hipMemcpyAsync(entry_pos, op(3), ne * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(entry_pair, op(4), ne * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = c.fetch(opr, np * 8)) || (rc = c.fetch(opv, np * 4)) || (rc = c.fetch(opf, np)) || (rc = c.fetch(oep, ne * 8)) || (rc = c.fetch(oer, ne * 8)) ||
+        (rc = c.finish())) return rc;
     return rcl;
 }
 
@@ -667,24 +613,15 @@ int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *en
     if ((n_pairs && (!pair_rows || !pair_var || !pair_flags)) || (n_var && !var_rows) || (n_entries && (!keys || !entry_pair)))
         return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t bytes[4] = {(size_t)n_entries * 8 * (size_t)h->kw, (size_t)n_entries * 8, (size_t)n_pairs * 4, (size_t)n_pairs};
-    const void *src[4] = {keys, entry_pair, pair_var, pair_flags};
-    const size_t obytes[2] = {(size_t)n_pairs * KV_PAIR_WORDS * 4, (size_t)n_var * KV_VAR_WORDS * 8};
-    Arena in, out;
-    for (int i = 0; i < 4; ++i) in.add(bytes[i]);
-    for (int i = 0; i < 2; ++i) out.add(obytes[i]);
+    const size_t pair_bytes = (size_t)n_pairs * KV_PAIR_WORDS * 4, var_bytes = (size_t)n_var * KV_VAR_WORDS * 8;
+    HostCall c(h, fn);
+    const int ik = c.in(keys, (size_t)n_entries * 8 * (size_t)h->kw), iep = c.in(entry_pair, (size_t)n_entries * 8);
+    const int ipv = c.in(pair_var, (size_t)n_pairs * 4), ipf = c.in(pair_flags, (size_t)n_pairs);
+    const int opr = c.out(pair_rows, pair_bytes), ovr = c.out(var_rows, var_bytes);
     int rc;
-    if ((rc = eng_reserve(h, h->var_buf[3], in.bytes))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[4], out.bytes))) return rc;
-    char *di = (char *)h->var_buf[3].p, *dout = (char *)h->var_buf[4].p;
-    for (int i = 0; i < 4; ++i)
-        if (bytes[i]) HIPCHK(h, hipMemcpyAsync(di + in.off[i], src[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    if ((rc = kdf_variant_evidence_dev(h, di + in.off[0], di + in.off[1], n_entries, di + in.off[2], di + in.off[3], n_pairs, n_var,
-                                       obytes[0] ? dout + out.off[0] : nullptr, obytes[1] ? dout + out.off[1] : nullptr))) return rc;
-    if (obytes[0]) HIPCHK(h, hipMemcpyAsync(pair_rows, dout + out.off[0], obytes[0], hipMemcpyDeviceToHost, h->stream));
-    if (obytes[1]) HIPCHK(h, hipMemcpyAsync(var_rows, dout + out.off[1], obytes[1], hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return KDF_OK;
+    if ((rc = c.commit()) || (rc = kdf_variant_evidence_dev(h, c.dev(ik), c.dev(iep), n_entries, c.dev(ipv), c.dev(ipf), n_pairs, n_var, c.dev(opr), c.dev(ovr))) ||
+        (rc = c.fetch(opr, pair_bytes)) || (rc = c.fetch(ovr, var_bytes))) return rc;
+    return c.finish();
 }
 
 }  // extern "C"
