@@ -131,7 +131,15 @@ int kdf_flush(kdf_engine *h);
  *            env KDF_LONG_SIEVE=0 / 1 sets the default; 1: kdf_count_reads_filtered* and kdf_scan_reads* of a long engine go through
  *            the membership sieve where the keys fit one, "last_count_path" / "last_scan_path" 3 -- the sieve is built by
  *            kdf_load_filter_w*, or from the table by the next count --if or scan when there is none, and dropped when keys
- *            join the table; force_path 1 keeps the direct kernels; 0 drops the sieve); "binned_bytes_per_position" (a flush goes
+ *            join the table; force_path 1 keeps the direct kernels; 0 drops the sieve); "sieve_bins" (k <= 63; 0 default, env
+ *            KDF_SIEVE_BINS sets the default; 1, or 4 .. 10 = exactly that many coarse bits; anything else, and any non-zero value
+ *            on a k > 63 engine, is KDF_ERR_INVALID: kdf_count_reads_filtered* and every caller that ends there go through the
+ *            BIN-MAJOR sieve -- the stream is slab-sorted by its top hash bits and one workgroup per bin tests the bin's entries
+ *            against its slice of the sieve in LDS, "last_count_path" 5 -- under force_path 0, without hash_shift, when
+ *            kdf_bin_sieve_geometry accepts the filter; otherwise the selection is what it is with 0, silently.  It wins over
+ *            the other sieve; it is built from the table by the first such call and dropped where that one is, and when
+ *            "sieve_bits" or "sieve_bins" change; the call is eager, pending binned passes are flushed first);
+ *            "binned_bytes_per_position" (a flush goes
  *            binned only when pending positions x this >= table bytes: kernel C rewrites the whole table; default 70);
  *            "defer" (1 default; 0: every count call ends with a flush), "defer_max_bytes" (budget of the ring of
  *            partitioned entries, 0 = 40 % of the device's memory), "l1_positions" (size from which the pending
@@ -160,7 +168,9 @@ int kdf_flush(kdf_engine *h);
  *            were shared by several workgroups), "log2cap", "bucket_bits", "c1" / "c2" (coarse / fine bits of the partition), "hash_shift", "defer", "fused_dump", "fused_dumps" (dumps written by a flush),
  *            "lazy_table", "dump_only_flushes" (flushes that wrote a dump and no table), "retained_passes" (passes such a flush applied,
  *            kept for the table: no longer "pending_passes"), "materialisations" (tables written later from retained passes),
- *            "last_count_path" (0 direct / 1 binned / 3 sieve), "last_scan_path" (0 direct / 3 sieve), "last_sieve_in_lds" (the last
+ *            "last_count_path" (0 direct / 1 binned / 3 sieve / 5 bin-major sieve), "sieve_bins" (the option), "last_sieve_bins" /
+ *            "last_sieve_slice_words" (coarse bits and words per bin of the last bin-major sieve call), "bin_sieve_passes" (its
+ *            passes so far), "last_scan_path" (0 direct / 3 sieve), "last_sieve_in_lds" (the last
  *            sieve kernel, count --if or scan, read the sieve from LDS: 1, or from L2: 0), "last_sieve_rounds" (long engines: tiles per
  *            thread of that kernel, 1 for the L2 form), "long_sieve" (the option; 0 for k <= 63), "last_merge_path" (1 LDS bucket
  *            merge, 2 global atomics); "histo_us" / "histo_passes" (kdf_histo_kernel under kdf_profile);
@@ -784,6 +794,17 @@ int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
  * (ceil(n_bases / 64) + 2).  This is a SIZE: the kernels may read every one of those words, and none beyond; what the
  * words at and past n_bases hold does not matter ("Read streams" points 1-2). */
 void kdf_stream_words(uint64_t n_bases, uint64_t *packed_words, uint64_t *mask_words);
+
+/* The sizing rule of the bin-major sieve (option "sieve_bins"), a pure host function: for a filter of n_keys keys of
+ * key_words (1: k <= 32, 2: k <= 63) words, under option values sieve_bits and sieve_bins (1, or 4 .. 10), the coarse bits
+ * *c1, the 64-bit words per bin *slice_words (a power of two from 128 up to what one compute unit's LDS holds beside the
+ * kernel's queues: 2^14) and the sieve bits per key *bits_per_key (sieve_bits as given; 0: 8, and 4 when 8 does not fit at
+ * c1 = 10).  The sieve has 2^c1 x slice_words words >= n_keys x bits_per_key / 64, rounded up to a power of two.
+ * sieve_bins 1 picks the smallest c1 in 4 .. 10 whose slice fits.  KDF_ERR_INVALID: no bin-major sieve for this filter
+ * (it would need fewer than 4 bits per key or a larger slice than fits) or arguments out of range; the out pointers may
+ * be NULL.  The engine sizes its sieve with this function. */
+int kdf_bin_sieve_geometry(uint64_t n_keys, int key_words, int sieve_bits, int sieve_bins, uint32_t *c1, uint32_t *slice_words,
+                           uint32_t *bits_per_key);
 
 /* Pack ASCII records (A/C/G/T any case; everything else invalid) into a stream
  * with one separator after each record.  offsets[n_reads+1] delimit the records

@@ -88,6 +88,7 @@ SYMBOLS = [
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),
     ("kdf_read_depth", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),
     ("kdf_stream_words", None, [c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_bin_sieve_geometry", c_int, [c_uint64, c_int, c_int, c_int, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
     ("kdf_pack_reads", c_int, [_P, _P, c_int64, _P, _P, _P, POINTER(c_uint64)]),
     ("kdf_canonical", c_int, [c_char_p, c_int, POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_bam_open", c_int, [c_char_p, c_uint32, c_int, c_int, POINTER(_P)]),

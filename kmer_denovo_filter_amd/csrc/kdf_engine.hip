@@ -408,6 +408,8 @@ __global__ __launch_bounds__(KB_THREADS) void kdf_sieve_count_kernel(
 
 // long keys through the same sieve (option "long_sieve")
 #include "kdf_long_sieve.h"
+// k <= 63 behind kernel A through a sieve laid out bin-major (option "sieve_bins")
+#include "kdf_binsieve.h"
 
 __global__ void kdf_ctl_reduce_kernel(KdfCtl *ctl, unsigned long long *out3) {
     // out3 = {distinct, windows, error}; single wave
@@ -524,7 +526,8 @@ static int ctl_reset(kdf_engine *h, bool keep_windows) {
 }
 
 // the sieve no longer describes the table (keys joined it, it was cleared, a new filter, other sizing options)
-static void sieve_drop(kdf_engine *h) { h->sieve_valid = false; h->sieve_unfit = false; }
+static void bin_sieve_drop(kdf_engine *h) { h->bsv_valid = false; h->bsv_unfit = false; }
+static void sieve_drop(kdf_engine *h) { h->sieve_valid = false; h->sieve_unfit = false; bin_sieve_drop(h); }
 
 // Insert-or-add n keys into table t, adding add[i] (NULL: 0).  Caller keys (stored = false) are the (lo, hi) arrays of
 // k <= 63 or the row-major W-word rows at lo of long keys; stored = true: lo / hi are the arrays of the live table,
@@ -722,6 +725,19 @@ static int kb_set_lds_attrs(kdf_engine *h, size_t a, size_t b, size_t c, size_t 
     return KDF_OK;
 }
 
+// dynamic LDS of kernel A and of the piece sort
+template <int KW> static constexpr size_t kb_lds_a() { return (size_t)(KbCfg<KW>::SLAB + 64) * 8 * KW + (size_t)(2 * ((1 << KB_C1_MAX) + 96)) * 4; }
+template <int KW> static constexpr size_t kb_lds_b() { return (size_t)KbCfg<KW>::CHUNK * 8 * KW + (size_t)(2 * KB_F + 32) * 4 + (size_t)KB_G_MAX * 12 + 32; }
+// the LDS limits of the binned path's kernels, raised once per engine and key width
+template <int KW>
+static int kb_ensure_attrs(kdf_engine *h) {
+    if (h->attrs_set[KW]) return KDF_OK;
+    const size_t lds_c = KB_C_LDS(KW, KB_BB_SMALL(KW));
+    if (const int rc = kb_set_lds_attrs<KW>(h, kb_lds_a<KW>(), kb_lds_b<KW>(), lds_c, ((size_t)(8 * KW + 4) << (KB_BB_SMALL(KW) + 1)) + KB_RI_LDS_BYTES)) return rc;
+    h->attrs_set[KW] = true;
+    return KDF_OK;
+}
+
 // the small device arrays of the binned path, allocated once per engine; fills the pointers of `s` from the engine's buffers
 static int kb_scratch(kdf_engine *h, KbScratch &s) {
     if (!h->kb_small) {
@@ -819,13 +835,8 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     plan.dbg = h->opt_debug_flags;
     plan.n_slabs = (uint32_t)n_slabs; plan.n_groups = (uint32_t)n_groups;
     const int nb1 = 1 << KB_C1_MAX;
-    const size_t lds_a = (size_t)(SLAB + 64) * 8 * KW + (size_t)(2 * (nb1 + 96)) * 4;
-    const size_t lds_b = (size_t)CHUNK * 8 * KW + (size_t)(2 * KB_F + 32) * 4 + (size_t)KB_G_MAX * 12 + 32;
-    if (!h->attrs_set[KW]) {                                   // once per engine
-        const size_t lds_c = KB_C_LDS(KW, KB_BB_SMALL(KW));
-        if ((rc = kb_set_lds_attrs<KW>(h, lds_a, lds_b, lds_c, ((size_t)(8 * KW + 4) << (KB_BB_SMALL(KW) + 1)) + KB_RI_LDS_BYTES))) return rc;
-        h->attrs_set[KW] = true;
-    }
+    const size_t lds_a = kb_lds_a<KW>(), lds_b = kb_lds_b<KW>();
+    if ((rc = kb_ensure_attrs<KW>(h))) return rc;
     // the pass's own buffers: slab-sorted entries, offset rows, planning arrays (reused by the next pass: stream order)
     if ((rc = eng_reserve(h, h->kb_buf[1], n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
     if ((rc = eng_reserve(h, h->kb_buf[4], n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
@@ -1448,11 +1459,117 @@ static void launch_long_sieve(kdf_engine *h, const uint64_t *d_packed, const uin
     span.stop();
 }
 
+// ---- count --if through the bin-major sieve (kdf_binsieve.h, option "sieve_bins") ---------------------------------------
+// The sieve over the keys the table holds now, unless there is one; bsv_valid tells whether the sizing rule took them
+// (as long_sieve_ensure does for the other sieve: one host round trip per build, none per call).
+static int bin_sieve_ensure(kdf_engine *h) {
+    if (h->bsv_valid || h->bsv_unfit) return KDF_OK;
+    int rc;
+    if ((rc = ctl_sync(h, nullptr))) return rc;
+    uint32_t c1 = 0, sw = 0, bpk = 0;
+    if (kdf_bs_geometry(h->distinct, h->kw, h->opt_sieve_bits, h->opt_sieve_bins, &c1, &sw, &bpk)) { h->bsv_unfit = true; return KDF_OK; }
+    const uint64_t words = (uint64_t)sw << c1;
+    if (h->bsv_alloc < words) {
+        if (h->bsv) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->bsv); }
+        h->bsv = nullptr; h->bsv_alloc = 0;
+        HIPCHK(h, hipMalloc((void **)&h->bsv, words * 8));
+        h->bsv_alloc = words;
+    }
+    h->bsv_c1 = c1; h->bsv_slice_words = sw;
+    HIPCHK(h, hipMemsetAsync(h->bsv, 0, words * 8, h->stream));
+    KbPlan plan{};
+    plan.c1 = c1;
+    by_width(h, [&](auto KWc) {
+        hipLaunchKernelGGL(kdf_bs_from_table_kernel<decltype(KWc)::value>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, h->stream,
+                           h->t, plan, h->bsv, sw);
+        return 0;
+    });
+    HIPCHK(h, hipGetLastError());
+    h->bsv_valid = true;
+    return KDF_OK;
+}
+
+// ONE pass of at most opt_binned_max_positions positions: kernel A as kb_partition launches it (coarse bits only), the
+// offset rows transposed bin-major, one workgroup of the bin kernel per (bin, share of the slabs).  Eager: no ring.
+template <int KW>
+static int bin_sieve_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, uint64_t n_end) {
+    constexpr int WPT = KbCfg<KW>::WPT, TPT = 64 / WPT, SLAB = KbCfg<KW>::SLAB;
+    constexpr uint32_t TILES_PER_SLAB = KB_A_THREADS / TPT;
+    const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
+    if (n_tiles == 0) return KDF_OK;
+    int rc;
+    KbPlan plan{};
+    plan.c1 = h->bsv_c1; plan.c2 = 0; plan.key_parts = 0;
+    plan.log2cap = h->t.log2cap; plan.bucket_bits = h->t.bucket_bits; plan.off_stride = 2; plan.group = 1;
+    const uint32_t nbins = 1u << plan.c1;
+    const uint64_t n_slabs = (n_tiles + TILES_PER_SLAB - 1) / TILES_PER_SLAB;
+    if (n_slabs >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "bin sieve pass: too many positions for one pass");
+    plan.n_slabs = (uint32_t)n_slabs; plan.n_groups = (uint32_t)n_slabs;
+    if ((rc = kb_ensure_attrs<KW>(h))) return rc;
+    const size_t lds_bin = (size_t)h->bsv_slice_words * 8 + KDF_BS_LDS_OTHER(KW);
+    if (!h->bsv_attr_set[KW]) {
+        HIPCHK(h, hipFuncSetAttribute((const void *)kdf_bin_sieve_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)((size_t)kdf_bs_cap_words() * 8 + KDF_BS_LDS_OTHER(KW))));
+        h->bsv_attr_set[KW] = true;
+    }
+    if ((rc = eng_reserve(h, h->kb_buf[1], n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb_buf[4], n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb_buf[7], n_slabs * (uint64_t)nbins * 4, slack_16th))) return rc;
+    KbScratch s;
+    if ((rc = kb_scratch(h, s))) return rc;
+    uint32_t *runs = (uint32_t *)h->kb_buf[7].p;
+
+    StageStamps st(h->prof, h->stream);
+    EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
+    st.stamp();                                                  // start of A
+    const uint32_t slabs_per_wg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, n_slabs / ((uint64_t)h->n_cu * 8)));
+    const unsigned grid_a = (unsigned)((n_slabs + slabs_per_wg - 1) / slabs_per_wg);
+    hipLaunchKernelGGL((kb_slabsort_kernel<KW, false>), dim3(grid_a), dim3(KB_A_THREADS), kb_lds_a<KW>(), h->stream, d_packed, d_invalid, n_tiles, n_end, h->k, plan, s, slabs_per_wg);
+    st.stamp();                                                  // end of A
+    hipLaunchKernelGGL(kdf_bs_transpose_kernel, dim3((unsigned)((n_slabs + 63) / 64), (nbins + 63) / 64), dim3(256), 0, h->stream,
+                       (const uint16_t *)s.off, runs, (uint32_t)n_slabs, nbins);
+    st.stamp();                                                  // end of the transposer
+    // about four workgroups per CU over all bins, and no share of less than one round of slabs
+    const uint64_t want = std::max<uint64_t>(1, ((uint64_t)h->n_cu * 4 + nbins - 1) / nbins);
+    const uint64_t shares0 = std::min<uint64_t>(want, (n_slabs + KDF_BS_THREADS - 1) / KDF_BS_THREADS);
+    const uint32_t slabs_per_share = (uint32_t)((n_slabs + shares0 - 1) / shares0);
+    const uint32_t shares = (uint32_t)((n_slabs + slabs_per_share - 1) / slabs_per_share);
+    hipLaunchKernelGGL(kdf_bin_sieve_kernel<KW>, dim3(nbins * shares), dim3(KDF_BS_THREADS), lds_bin, h->stream,
+                       (const uint64_t *)s.tmp, (const uint32_t *)runs, (const uint64_t *)h->bsv, h->bsv_slice_words, (uint32_t)n_slabs,
+                       shares, slabs_per_share, h->t, h->ctl);
+    st.stamp();                                                  // end of the bin kernel
+    HIPCHK(h, hipGetLastError());
+    span.stop();
+    st.commit(h->prof_stage_ev);                                 // (kdf_profile_stages: A, transposer, bin kernel in the partition's three slots)
+    h->stat_bin_sieve_passes++;
+    return KDF_OK;
+}
+
+// the whole stream, in passes that start on tile boundaries (as kb_partition_stream cuts them)
+static int count_bin_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
+    int rc;
+    if ((rc = kb_flush_ring(h))) return rc;                       // (binned --if passes pending from earlier batches)
+    const uint64_t step = h->opt_binned_max_positions;
+    for (uint64_t off = 0; off < n_bases; off += step) {
+        const uint64_t len = std::min<uint64_t>(step, n_bases - off);
+        const uint64_t *p = d_packed + off / 32, *m = d_invalid + off / 64;
+        if ((rc = by_width(h, [&](auto KWc) { return bin_sieve_pass<decltype(KWc)::value>(h, p, m, len, n_bases - off); }))) return rc;
+    }
+    h->last_path = 5;
+    h->last_sieve_bins = h->bsv_c1; h->last_sieve_slice_words = h->bsv_slice_words;
+    return KDF_OK;
+}
+
 static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (!h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads_filtered: no filter loaded (kdf_load_filter)");
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
     if (n_tiles == 0) return KDF_OK;
     { int rc0 = materialize(h); if (rc0) return rc0; }
+    if (h->opt_sieve_bins && h->opt_force_path == 0 && !h->opt_hash_shift && !is_long(h)) {
+        int rc = bin_sieve_ensure(h);                              // (the option was set, or keys were added, after the filter was loaded)
+        if (rc) return rc;
+        if (h->bsv_valid) return count_bin_sieve(h, d_packed, d_invalid, n_bases);
+    }
     if (is_long(h)) {
         if (h->opt_long_sieve && h->opt_force_path != 1) {
             int rc = long_sieve_ensure(h);                         // (the option was set, or keys were added, after the filter was loaded)
@@ -1666,6 +1783,7 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     h->device = device; h->k = k; h->kw = k <= 32 ? 1 : k <= 63 ? 2 : (2 * k + 63) / 64;
     if (is_long(h)) { h->opt_fused_dump = 0; h->opt_lazy_table = 0; }
     else h->opt_long_sieve = 0;                      // (KDF_LONG_SIEVE is for long engines: k <= 63 takes its sieve anyway)
+    if (is_long(h)) h->opt_sieve_bins = 0;           // (and KDF_SIEVE_BINS for k <= 63)
     auto bail = [&](int rc) { g_err = h->err; kdf_destroy(h); return rc; };
     if ((e = hipSetDevice(device)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) h->n_cu = ncu; }
@@ -1706,6 +1824,7 @@ void kdf_destroy(kdf_engine *h) {
     }
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->sieve) (void)hipFree(h->sieve);
+    if (h->bsv) (void)hipFree(h->bsv);
     if (h->kb_small) (void)hipFree(h->kb_small);
     if (h->kb_totals_host) (void)hipHostFree(h->kb_totals_host);
     if (h->ctl) (void)hipFree(h->ctl);
@@ -3369,7 +3488,14 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "l1_positions") h->opt_l1_positions = (uint64_t)std::max<int64_t>(value, KDF_TILE);
     else if (n == "l1_direct_positions") h->opt_l1_direct_positions = (uint64_t)std::max<int64_t>(value, 0);
-    else if (n == "sieve_bits") { h->opt_sieve_bits = (int)value; h->sieve_unfit = false; }     // (other sizing: the keys may fit now)
+    else if (n == "sieve_bits") { h->opt_sieve_bits = (int)value; h->sieve_unfit = false; bin_sieve_drop(h); }     // (other sizing: the keys may fit now)
+    else if (n == "sieve_bins") {
+        if (value != 0 && value != 1 && (value < KDF_BS_C1_MIN || value > KDF_BS_C1_MAX))
+            return fail(h, KDF_ERR_INVALID, "sieve_bins %lld: must be 0 (off), 1 (coarse bits by the filter's size) or %d..%d coarse bits", (long long)value, KDF_BS_C1_MIN, KDF_BS_C1_MAX);
+        if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "sieve_bins: not available for k > 63 (no binned pipeline for long keys)");
+        if ((int)value != h->opt_sieve_bins) bin_sieve_drop(h);
+        h->opt_sieve_bins = (int)value;
+    }
     else if (n == "long_sieve") {
         if (!is_long(h)) return fail(h, KDF_ERR_INVALID, "long_sieve: k=%d always takes the sieve where it fits (the option is for k > 63)", h->k);
         if (value != 0 && value != 1) return fail(h, KDF_ERR_INVALID, "long_sieve %lld: must be 0 or 1", (long long)value);
@@ -3431,6 +3557,10 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
     else if (n == "last_scan_path") *value = h->last_scan_path;
+    else if (n == "sieve_bins") *value = h->opt_sieve_bins;
+    else if (n == "last_sieve_bins") *value = h->last_sieve_bins;
+    else if (n == "last_sieve_slice_words") *value = h->last_sieve_slice_words;
+    else if (n == "bin_sieve_passes") *value = (int64_t)h->stat_bin_sieve_passes;
     else if (n == "last_sieve_in_lds") *value = h->last_sieve_in_lds;
     else if (n == "last_sieve_rounds") *value = h->last_sieve_rounds;
     else if (n == "long_sieve") *value = h->opt_long_sieve;

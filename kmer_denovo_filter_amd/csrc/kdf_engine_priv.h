@@ -100,7 +100,7 @@ struct kdf_engine {
     // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
     unsigned long long *kb_small = nullptr;   // totals[16]
     unsigned long long *kb_totals_host = nullptr;   // pinned [16]
-    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables
+    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables, bin-major runs (bin sieve)
     KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
     KbRing ring;                                     // the pending passes (above)
     uint64_t stat_flushes = 0;
@@ -148,13 +148,24 @@ struct kdf_engine {
     int last_sieve_in_lds = 0;                       // the last sieve kernel read the sieve from LDS (1) or from L2 (0)
     bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
     bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
-    int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve
+    int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve, 5 bin-major sieve
     int last_scan_path = 0;                          // kernel of the last kdf_scan_reads_dev: 0 direct, 3 sieve
     uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
     uint64_t sieve_words = 0, sieve_alloc = 0;
     bool sieve_valid = false;
     bool sieve_unfit = false;                        // long_sieve_ensure found the table's keys too many for a sieve: not asked again
                                                      // until the keys, the filter or the sizing options change (sieve_drop)
+    // count --if through the bin-major sieve (kdf_binsieve.h; option "sieve_bins" / env KDF_SIEVE_BINS: 0 off, 1 the sizing rule's
+    // coarse bits, 4 .. 10 exactly those): an allocation of its own, built from the table by the first eligible count --if
+    // (bin_sieve_ensure) and dropped with the other sieve (sieve_drop) and when sieve_bits / sieve_bins change
+    int opt_sieve_bins = [] { const char *e = getenv("KDF_SIEVE_BINS"); const int v = e ? atoi(e) : 0; return v == 1 || (v >= 4 && v <= 10) ? v : 0; }();
+    uint64_t *bsv = nullptr;                         // [2^bsv_c1][bsv_slice_words]
+    uint64_t bsv_alloc = 0;                          // words
+    uint32_t bsv_c1 = 0, bsv_slice_words = 0;
+    bool bsv_valid = false, bsv_unfit = false;       // unfit: the sizing rule refused the table's keys (not asked again until a drop)
+    bool bsv_attr_set[3] = {false, false, false};    // kdf_bin_sieve_kernel's LDS limit raised (per key width)
+    uint32_t last_sieve_bins = 0, last_sieve_slice_words = 0;
+    uint64_t stat_bin_sieve_passes = 0;
     uint32_t last_sieve_rounds = 0;                  // tiles per thread of the last sieve kernel of a long engine (LDS form; L2 form: 1)
     uint32_t opt_debug_flags = 0;                    // experiments only (KbPlan::dbg)
     uint64_t stat_binned_passes = 0, stat_replayed_buckets = 0;

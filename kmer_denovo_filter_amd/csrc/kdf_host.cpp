@@ -23,6 +23,7 @@
 
 #include "kdf.h"
 #include "kdf_device.h"      // KDF_TILE, kdf_stream_geom (host-only here: no device code)
+#include "kdf_binsieve.h"    // the bin-major sieve's sizing rule (its host part)
 
 namespace {
 
@@ -800,6 +801,12 @@ void kdf_stream_words(uint64_t n_bases, uint64_t *packed_words, uint64_t *mask_w
     const KdfStreamGeom g = kdf_stream_geom(n_bases);
     if (packed_words) *packed_words = g.packed_words;
     if (mask_words) *mask_words = g.mask_words;
+}
+
+// the sizing rule of the bin-major sieve (kdf_binsieve.h): no device, no engine
+int kdf_bin_sieve_geometry(uint64_t n_keys, int key_words, int sieve_bits, int sieve_bins, uint32_t *c1, uint32_t *slice_words,
+                           uint32_t *bits_per_key) {
+    return kdf_bs_geometry(n_keys, key_words, sieve_bits, sieve_bins, c1, slice_words, bits_per_key) ? KDF_ERR_INVALID : KDF_OK;
 }
 
 int kdf_canonical(const char *kmer, int k, uint64_t *lo, uint64_t *hi) {

@@ -138,11 +138,11 @@ class KmerEngine:
         self._ck(self._lib.kdf_profile_stages(self._h, ms, byref(n)))
         return list(ms), n.value
 
-    _PATHS = ("direct", "binned", "-", "sieve")
+    _PATHS = ("direct", "binned", "-", "sieve", "-", "bin_sieve")
     _STAGES = ["kb_slabsort_kernel", "kb_groupsum+kb_plan", "kb_piecesort_pipe_kernel", "kb_bucket_kernel"]
 
     def last_count_path(self) -> str:
-        """Which pipeline the last count call took: direct / binned / sieve."""
+        """Which pipeline the last count call took: direct / binned / sieve / bin_sieve (option sieve_bins)."""
         return self._PATHS[self.get_stat("last_count_path")]
 
     def profile_stage_names(self):
@@ -938,6 +938,18 @@ def estimate_from_registers(regs) -> float:
     v = ctypes.c_double(0.0)
     _native.check(_native.load().kdf_sketch_estimate_registers(_vp(regs), m.bit_length() - 1, byref(v)), None)
     return v.value
+
+
+def bin_sieve_geometry(n_keys: int, key_words: int, sieve_bits: int = 0, sieve_bins: int = 1) -> Tuple[int, int, int]:
+    """(c1, slice_words, bits_per_key) of the bin-major sieve (option ``sieve_bins``) for a filter of ``n_keys`` keys of
+    ``key_words`` (1: k <= 32, 2: k <= 63) words -- the engine's own sizing rule, a pure host function of libkdf: no
+    engine, no GPU.  Raises KdfError (KDF_ERR_INVALID) when the rule gives this filter no bin-major sieve."""
+    from ctypes import c_uint32
+    c1, sw, bpk = c_uint32(0), c_uint32(0), c_uint32(0)
+    rc = _native.load().kdf_bin_sieve_geometry(int(n_keys), int(key_words), int(sieve_bits), int(sieve_bins), byref(c1), byref(sw), byref(bpk))
+    if rc != _native.KDF_OK:
+        raise _native.KdfError(rc, f"no bin-major sieve for {n_keys} keys of {key_words} words (sieve_bits {sieve_bits}, sieve_bins {sieve_bins})")
+    return c1.value, sw.value, bpk.value
 
 
 def mirror_engine(k: int, *args, **kwargs) -> KmerEngine:
