@@ -69,6 +69,18 @@
 #ifndef KB_C_WPE
 #define KB_C_WPE 6                       // waves per SIMD the register allocation aims at
 #endif
+// Lanes that share a contiguous sub-block of a wave's entries in a gather (kb_entry_off, kdf_device.h; 64: lane l takes
+// entry 64 q + l).  Measured at bench size, 64 / 32 / 16 / 8: kernel C 4.19 / 4.08 / 4.08 / 4.20 ms, the
+// pipelined piece sort 4.04-4.13 / 4.08-4.14 / 4.14-4.21 / 4.36-4.45 ms -- it keeps the plain mapping.
+#ifndef KB_C_SEG
+#define KB_C_SEG 32                      // narrow keys in kernel C
+#endif
+#ifndef KB_B_SEG
+#define KB_B_SEG 64                      // the pipelined piece sort (KbPipe)
+#endif
+#ifndef KB_A_NT
+#define KB_A_NT 1                        // 1: kernel A writes a slab's block out with streaming stores (2.52 -> 2.51 ms, the step -0.04 ms)
+#endif
 static_assert(KB_C_EPB_N % 4 == 0 && KB_C_EPB_W % 4 == 0, "kernel C resolves entries four at a time");
 static_assert(KB_C_THREADS % 256 == 0 && KB_C_THREADS <= 1024 && KB_C_THREADS_W % 256 == 0 && KB_C_THREADS_W <= KB_C_THREADS, "whole waves on every SIMD");
 #define KB_C_CT(KW) ((KW) == 2 ? KB_C_THREADS_W : KB_C_THREADS)
@@ -300,6 +312,19 @@ struct KbWindows {
         h = kdf_hash(lo, hi);
     }
 };
+
+// 16 bytes of kernel A's write-out, LDS image to tmp: written once, read once by the piece sort after the whole stream
+// has gone through the caches -- a streaming store (KB_A_NT)
+template <typename T>
+__device__ __forceinline__ void kb_store_once16(T *dst, const T *src) {
+    static_assert(sizeof(T) == 16 && alignof(T) == 16, "one 16-byte store");
+    typedef unsigned long long v2 __attribute__((ext_vector_type(2)));
+#if KB_A_NT
+    __builtin_nontemporal_store(*(const v2 *)src, (v2 *)dst);
+#else
+    *dst = *src;
+#endif
+}
 
 // A: the stream is read ONCE.  A workgroup takes slabs_per_wg consecutive slabs; per slab: stored form + coarse bin of
 // every window, rank by LDS atomics, counting sort into an LDS image, the image written out CONTIGUOUSLY to
@@ -604,7 +629,9 @@ struct KbPipe {
         // the loop body in a register of its own across the whole loop -- ~50 VGPRs, i.e. spills at the 128 this kernel has)
         uint32_t tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        const uint32_t wbase = (tid >> 6) * (64 * EPT) + (tid & 63);      // this lane's first entry of a piece
+        // (kb_entry_off, kdf_device.h: KB_B_SEG adjacent lanes share a contiguous KB_B_SEG * EPT entries of the wave's 64 * EPT -- the
+        // same map in the gather (d) and in the tests of (a), so that a register holds the same entry in both)
+        const uint32_t wbase = (tid >> 6) * (64 * EPT) + kb_entry_off<KB_B_SEG>(EPT, tid & 63, 0);      // this lane's first entry of a piece
         // ---- (a) LDS phases of piece `it`
         const uint32_t len = m_len;
         if (len) {                                                        // (uniform; LDS only)
@@ -612,7 +639,7 @@ struct KbPipe {
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
                 uint32_t r = 0;
-                if (wbase + 64 * q < len) r = atomicAdd(&hist[kb_fine(plan, klo[q])], 1u);
+                if (wbase + KB_B_SEG * q < len) r = atomicAdd(&hist[kb_fine(plan, klo[q])], 1u);
                 if (q & 1) rk[q >> 1] |= r << 16; else rk[q >> 1] = r;
             }
             kb_lds_barrier();
@@ -624,7 +651,7 @@ struct KbPipe {
             kb_lds_barrier();
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
-                if (wbase + 64 * q < len) {
+                if (wbase + KB_B_SEG * q < len) {
                     const uint32_t pos = offs[kb_fine(plan, klo[q])] + ((rk[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu);
                     if constexpr (KW == 2) s2[pos] = KbEnt2{klo[q], khi[q]};
                     else slo[pos] = klo[q];
@@ -741,7 +768,7 @@ struct KbPipe {
             const KbEnt2 *tmp2 = (const KbEnt2 *)s.tmp;
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
-                const uint32_t e = wbase + 64 * q;
+                const uint32_t e = wbase + KB_B_SEG * q;
                 unsigned long long src = 0;                               // (lanes past the piece read entry 0, and ignore it)
                 if (e < glen) {
                     if (e >= cnx) {
@@ -1097,13 +1124,21 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
         for (uint32_t e0 = 0; e0 < total; e0 += CT * EPB) {   // wave-uniform trip count
           uint64_t bklo[EPB], bkhi[KW == 2 ? EPB : 1];
           // Flat index of this thread's q-th entry of the batch.  Narrow keys: a WAVE takes 64 * EPB
-          // consecutive entries, lane l's q-th entry is wbase + 64 q -- one load instruction still reads 64
-          // consecutive entries, and a lane's consecutive entries are about one run (64 entries) further on,
-          // so the run is searched once per batch and then only advanced.
-          // Wide keys have 16-entry runs (four runs per step): they keep the per-entry windowed search.
+          // consecutive entries and KB_C_SEG adjacent lanes a contiguous KB_C_SEG * EPB of them (kb_entry_off,
+          // kdf_device.h): a lane's q-th entry is wbase + KB_C_SEG q, and one load instruction reads 64 / KB_C_SEG
+          // segments of KB_C_SEG consecutive entries.  The run is searched once per batch and then only advanced.
+          // A bucket's runs are ~32 entries at bench load (8 + 9 split): with 64-entry steps every lane crossed
+          // about two runs at each step, the wave turning the advance loop for its slowest lane; with 32-entry
+          // steps it is one run at each step, with 16 one at about every other step (the same time, measured).
+          // Wide keys have 16-entry runs: they keep the per-entry windowed search.
           constexpr bool WAVE_SPANS = KW == 1;
-          const uint32_t wbase = WAVE_SPANS ? e0 + (threadIdx.x >> 6) * (64 * EPB) + (threadIdx.x & 63) : e0 + threadIdx.x;
-          constexpr uint32_t QSTEP = WAVE_SPANS ? 64u : (uint32_t)CT;      // flat-index distance between a thread's consecutive entries
+          // First entry of the wave's block, made a scalar by hand: left to the compiler it and the lane's offset took two
+          // more vector registers.  (KB_C_SEG 64, the mapping before kb_entry_off, keeps the expression it had: that
+          // build compiles to the instructions it always had.)
+          const uint32_t lane0 = kb_entry_off<KB_C_SEG>(EPB, threadIdx.x & 63, 0);
+          const uint32_t wblk = KB_C_SEG == 64 ? e0 + (threadIdx.x >> 6) * (64 * EPB) : e0 + kb_uni(threadIdx.x >> 6) * (64 * EPB);
+          const uint32_t wbase = WAVE_SPANS ? wblk + lane0 : e0 + threadIdx.x;
+          constexpr uint32_t QSTEP = WAVE_SPANS ? (uint32_t)KB_C_SEG : (uint32_t)CT;  // flat-index distance between a thread's consecutive entries
           if constexpr (WAVE_SPANS) {
             uint32_t cr = 0, cpf = 0, cnx = 0;                 // current run: index, first flat entry, first entry of the next run
             if (wbase < total) {
@@ -1197,7 +1232,7 @@ __global__ __launch_bounds__(KB_C_CTB(KW, BIG)) __attribute__((amdgpu_waves_per_
             constexpr int G = 4;                                 // keys resolved together: G * KB_C_LA LDS reads in flight
 #pragma unroll
             for (int q0 = 0; q0 < EPB; q0 += G) {
-                if (wbase - (threadIdx.x & 63) + QSTEP * q0 >= total) break;      // wave-uniform: nothing left for this wave in this batch
+                if (wblk + QSTEP * q0 >= total) break;      // wave-uniform: the first entry of step q0 is lane 0's -- nothing left for this wave in this batch
                 uint64_t cur[G][KB_C_LA]; uint32_t sl0[G]; bool td[G];
 #pragma unroll
                 for (int g = 0; g < G; ++g) {

@@ -152,14 +152,17 @@ __global__ __launch_bounds__(KB_A_THREADS) void kb_slabsort_kernel(
             // (Measured and dropped: all eight ds_read_b128 of a lane first, pinned in registers, then its stores -- no
             // spill, but 2.541 / 2.535 against 2.544 / 2.510 ms at k = 31 and 4.31 against 4.23 at k = 63, DESIGN.md 3.2: sixteen
             // waves already cover one another's LDS round trips here.)
+            // Streaming stores (KB_A_NT): the block is read once, by the piece sort, after the whole stream has gone through
+            // the caches -- the step 10.81 -> 10.77 ms, every run below every run without the hint.  (The same hint on the
+            // piece sort's write-out: 4.04 -> 4.51 ms for that kernel; on the dump's dense stores: within the noise.)
             const uint32_t nv = KB_ABL(plan, 256) ? 0u : offs[nb];          // (ablation 256: no write-out -- timing only)
             if constexpr (KW == 2) {
                 KbEnt2 *dst = (KbEnt2 *)s.tmp + slab * (uint64_t)SLAB;
-                for (uint32_t i = tid; i < nv; i += NT) dst[i] = s2[i];
+                for (uint32_t i = tid; i < nv; i += NT) kb_store_once16(&dst[i], &s2[i]);
             } else {
                 ulonglong2 *dst = (ulonglong2 *)(s.tmp + slab * (uint64_t)SLAB);
                 const ulonglong2 *src = (const ulonglong2 *)slo;
-                for (uint32_t i = tid; i < (nv + 1) / 2; i += NT) dst[i] = src[i];      // (SLAB is even: the odd tail stays inside the slab's block)
+                for (uint32_t i = tid; i < (nv + 1) / 2; i += NT) kb_store_once16(&dst[i], &src[i]);      // (SLAB is even: the odd tail stays inside the slab's block)
             }
         }
         KB_T(s.trash, 17);                                               // write-out issued

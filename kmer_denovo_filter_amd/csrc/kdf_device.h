@@ -69,6 +69,20 @@ KDF_HD uint32_t kb_guess_run(uint32_t e, uint32_t ns, uint32_t n_pair) {
     return n_pair ? kb_guess_run_rcp(e, ns, kdf_rcp((float)n_pair)) : 0u;
 }
 
+// Entry map of the two gathers of the binned path (kernel C's narrow path, the pipelined piece sort): a wave takes a block
+// of 64 * E consecutive entries of a flat list, E per lane.  A group of S adjacent lanes owns a contiguous sub-block of
+// S * E of them: lane l = g * S + j reads, at step q, the entry at offset g * (S * E) + q * S + j of the wave's block.  One
+// load instruction reads 64 / S segments of S consecutive entries, and the next step of the same lanes reads the
+// adjacent segments.  A lane's entries span S * E of the list instead of 64 * E: so many fewer runs for its cursor to
+// cross between two steps.  S = 64 is the plain mapping 64 q + l.  The offset is affine in q (S entries per step); the
+// steps with a live lane, for a block cut at `live` entries, are q < ceil(live / S): the first entry of step q is group
+// 0's, offset S * q (tests/native/entry_map_check.cpp).
+template <uint32_t S>
+KDF_HD uint32_t kb_entry_off(uint32_t E, uint32_t l, uint32_t q) {
+    static_assert(S >= 8 && S <= 64 && (S & (S - 1)) == 0, "segments of 8, 16, 32 or 64 lanes");
+    return (l / S) * (S * E) + q * S + (l % S);
+}
+
 #if defined(__HIP__)                        // everything below is device code
 
 // ---------------------------------------------------------------------------
