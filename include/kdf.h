@@ -746,6 +746,72 @@ int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *en
                          const uint32_t *pair_var, const uint8_t *pair_flags, uint64_t n_pairs, uint64_t n_var,
                          uint32_t *pair_rows, uint64_t *var_rows);
 
+/* ------------------------------------------- regions of informative reads ---- */
+
+/* Module 3's step from "the informative reads and where they align" to the rows of discovery.bed: the intervals of the
+ * reads clustered into regions (kdf_cluster_intervals*), and the number of distinct hit k-mers of every region
+ * (kdf_group_distinct*, over the key rows kdf_hit_keys* wrote).  Both take plain arrays and stand on their own.
+ *
+ * Clustering.  chrom, start and end are int64[n], in ANY order.  chrom[i] is a rank the caller defines (the reference
+ * sorts by contig NAME: the rank of the name among the sorted names); an interval with chrom[i] < 0 is skipped and gets
+ * region_of[i] = -1 (the convention of ref_start < 0 in kdf_hit_coverage).
+ *   Rule.   Order the remaining intervals by (chrom, start) ascending; the order of ties does not change the result.
+ *           Let E_i be the maximum `end` over the EARLIER intervals of the same chrom.  Interval i opens a new region
+ *           iff it is the first of its chrom or start_i > E_i + merge_distance; otherwise it joins the open region.
+ *           Regions are numbered 0.. in that order.  Row g of regions_out (cap x 4 int64, row-major) is (chrom, start
+ *           of the region's first interval, maximum end of its members, number of members); region_of[i] is i's region.
+ *   - for end >= start and merge_distance >= 0 this is exactly the sweep of discovery/regions.py:_cluster_read_hits and
+ *     of the reference (discovery/pipeline.py:1111-1144): the sweep keeps the open region's running end, and because the
+ *     order is by start, that running end is the maximum end of EVERY earlier interval of the contig, not only of the
+ *     region's own members (an earlier region ended below this region's first start, so its ends are below too): the
+ *     prefix maximum within the contig.  It restarts at a contig change because the sweep never joins across contigs: a
+ *     long interval at the end of one contig must not swallow the first intervals of the next, whose coordinates start
+ *     over.
+ *   - ranges: chrom < 2^31, 0 <= start <= end < 2^62, 0 <= merge_distance < 2^62, n < 2^32.  The host form returns
+ *     KDF_ERR_INVALID before any device work when an input breaks them (the outputs are then untouched; a skipped
+ *     interval's start and end are not looked at); for the
+ *     device form n and merge_distance are checked and the arrays' contents are preconditions.
+ *   - whatever the device arrays hold, no write lands outside region_of[0 .. n) and the first min(cap, *n_out) rows of
+ *     regions_out.
+ *   - *n_out is always set to the number of regions; when it exceeds cap the call returns KDF_ERR_INVALID with
+ *     region_of complete and the first cap rows written (the convention of kdf_hit_list_dev).  regions_out may be NULL
+ *     with cap == 0: a sizing call.  n == 0 is KDF_OK with *n_out = 0.
+ *   - the table is not touched: no flush, any key width.  All outputs are integers, bit-identical between runs and
+ *     between the two forms.
+ *   - work: a library radix sort by start, then stably by chrom (skipped intervals behind the rest), then two block
+ *     scans over the sorted order -- a prefix MAXIMUM of the pair (chrom, end), which restarts at a contig change by
+ *     itself, and a prefix sum of the boundary flags -- and one pass that writes the rows with one atomic maximum and
+ *     one atomic add per (wave, region).  Scratch: 13 bytes per interval owned by the engine and kept between calls,
+ *     and the sort's own (24 bytes per interval and rocPRIM's), allocated and freed per call.
+ *   - the device form synchronises the engine's stream (the sort, and the number of regions); both outputs are complete
+ *     in stream order when it returns.
+ *   - under kdf_profile(h, 1) the kernels of kdf_cluster_intervals* and kdf_group_distinct* (the sort included) are
+ *     timed with HIP events: stats "regions_us" / "regions_passes" (one pass per call that launches). */
+int kdf_cluster_intervals_dev(kdf_engine *h, const void *d_chrom, const void *d_start, const void *d_end, int64_t n,
+                              int64_t merge_distance, void *d_region_of, void *d_regions_out, uint64_t cap,
+                              uint64_t *n_out);
+int kdf_cluster_intervals(kdf_engine *h, const int64_t *chrom, const int64_t *start, const int64_t *end, int64_t n,
+                          int64_t merge_distance, int64_t *region_of, int64_t *regions_out, uint64_t cap,
+                          uint64_t *n_out);
+
+/* Distinct rows per group.  keys is n x words uint64, rows as kdf_hit_keys* writes them; words is 1..8 and independent
+ * of the engine's own key width (W = 3..7 rows, one-word read-name ids).  group is int64[n].
+ *   Rule.   counts_out[g] (uint64[n_groups], OVERWRITTEN) is the number of distinct rows among the entries e with
+ *           group[e] == g.
+ *   - entries with group[e] < 0 or >= n_groups are ignored, and so is a row of all-ones words: the "no key" row of
+ *     kdf_hit_keys*, as in kdf_variant_evidence*.  The same row in two groups counts in both.
+ *   - the result is exact: the entries are ordered by (group, row) with the library radix sort and a row is compared
+ *     with its predecessor word by word, never a hash of a row in place of the row.  The counts are integer sums.
+ *   - n == 0 writes zeros.  n_groups == 0 is KDF_OK and writes nothing.  n >= 2^32, words outside 1..8 and
+ *     n_groups < 0 are KDF_ERR_INVALID.
+ *   - the table is not touched.  Scratch: 12 bytes per entry owned by the engine, and the sort's own per call.
+ *   - the device form synchronises the engine's stream (the sort); counts_out is complete in stream order when it
+ *     returns.  Timed into "regions_us" / "regions_passes". */
+int kdf_group_distinct_dev(kdf_engine *h, const void *d_group, const void *d_keys, int words, uint64_t n,
+                           int64_t n_groups, void *d_counts_out);
+int kdf_group_distinct(kdf_engine *h, const int64_t *group, const uint64_t *keys, int words, uint64_t n,
+                       int64_t n_groups, uint64_t *counts_out);
+
 /* ------------------------------------------- count profile of a stream ---- */
 
 /* `jellyfish query idx -s reads.fa` over a whole read stream: counts_out[i], 0 <= i < n_bases, is the stored count of

@@ -83,6 +83,11 @@ SYMBOLS = [
                                     _P, c_uint64, _P, _P, _P, _P, c_uint64, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_variant_evidence_dev", c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P]),
     ("kdf_variant_evidence", c_int, [_P, _P, _P, c_uint64, _P, _P, c_uint64, c_uint64, _P, _P]),
+    # regions of informative reads
+    ("kdf_cluster_intervals_dev", c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_cluster_intervals", c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
+    ("kdf_group_distinct_dev", c_int, [_P, _P, _P, c_int, c_uint64, c_int64, _P]),
+    ("kdf_group_distinct", c_int, [_P, _P, _P, c_int, c_uint64, c_int64, _P]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),

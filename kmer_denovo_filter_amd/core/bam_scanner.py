@@ -38,6 +38,7 @@ READER_THREADS = max(1, min(8, os.cpu_count() or 1))
 
 _worker_engine: Optional[KmerEngine] = None
 _worker_kmer_size: Optional[int] = None
+last_ledger = None        # the RegionLedger of the last scan_bam_module3 under KDF_DEVICE_REGIONS=1, else None
 _worker_min_distinct_kmers_per_read = 1
 
 
@@ -259,6 +260,17 @@ def _decode_read(batch, r):
     return chars.tobytes().decode()
 
 
+class RegionLedger:
+    """``KDF_DEVICE_REGIONS=1``: what Module 3 keeps in HBM for the regions' k-mer counts -- for every hit of every KEPT
+    read its key row (``keys``: int64 tensors of ``hits x words`` words, one per batch) and the running ordinal of its
+    read among the kept reads (``ordinals``: int64 tensors, one per batch).  Names stay on the host: which kept reads
+    reach ``read_hits`` is decided there, and ``read_hits`` carries each read's ordinal in place of its k-mer set."""
+
+    def __init__(self, eng: KmerEngine, refs):
+        self.eng, self.refs, self.words = eng, list(refs), eng.key_words
+        self.keys, self.ordinals, self.n_reads = [], [], 0
+
+
 class _DeviceCoverage:
     """``KDF_DEVICE_COVERAGE=1``: Module 3's two coverage sums kept on the device.  Two uint32 accumulators of the
     genome's linear length (contig offsets = running sum of the header's reference lengths); per batch the hit mask,
@@ -266,9 +278,10 @@ class _DeviceCoverage:
     k-mer sets come from ``hit_keys_dev`` (one ``keys_to_kmers`` per distinct key of a read, no read is decoded).  The
     host decides WHICH reads contribute, because it has the names: kept by ``min_dk``, mapped, and the first kept
     record with its (ref_id, name, is_supplementary) in file order -- the reference's de-duplication inside a contig's
-    task; coverage is a commutative sum, so the order of the tasks does not matter."""
+    task; coverage is a commutative sum, so the order of the tasks does not matter.  With a ``ledger``
+    (``KDF_DEVICE_REGIONS=1``) the key rows stay on the device too and no k-mer set is made."""
 
-    def __init__(self, eng: KmerEngine, ref_lengths):
+    def __init__(self, eng: KmerEngine, ref_lengths, ledger: Optional[RegionLedger] = None):
         import torch
         self.eng = eng
         self.torch = torch
@@ -278,6 +291,7 @@ class _DeviceCoverage:
         self.kcov = torch.zeros(max(self.span, 1), dtype=torch.int32, device=self.dev)
         self.rcov = torch.zeros(max(self.span, 1), dtype=torch.int32, device=self.dev)
         self.seen = set()
+        self.ledger = ledger
 
     @staticmethod
     def fits(eng: KmerEngine, ref_lengths) -> bool:
@@ -303,7 +317,8 @@ class _DeviceCoverage:
 
     def batch(self, batch, min_dk: int, k: int):
         """-> (keep int64[m], hit offsets of each kept read relative to its start, k-mer set of each kept read); the
-        contributing reads among them are added to the accumulators."""
+        contributing reads among them are added to the accumulators.  With a ledger the third list holds each kept
+        read's ordinal instead, and the key rows of the kept reads' hits join the ledger."""
         from ..reads import keys_to_kmers
         eng, torch = self.eng, self.torch
         n, nr = int(batch.n_bases), int(batch.n_reads)
@@ -321,8 +336,12 @@ class _DeviceCoverage:
         cap = int(rows[:, 0].sum(dtype=np.int64))
         while True:
             dpos = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev)
+            dreads = torch.empty(max(cap, 1), dtype=torch.int64, device=self.dev) if self.ledger is not None else None   # each hit's read
             torch.cuda.synchronize(self.dev)
-            rc, got = eng._hit_list_dev(dbits.data_ptr(), n, None, 0, dpos.data_ptr(), None, cap)
+            if dreads is None:
+                rc, got = eng._hit_list_dev(dbits.data_ptr(), n, None, 0, dpos.data_ptr(), None, cap)
+            else:
+                rc, got = eng._hit_list_dev(dbits.data_ptr(), n, do.data_ptr(), nr, dpos.data_ptr(), dreads.data_ptr(), cap)
             if got <= cap:
                 eng._ck(rc)
                 break
@@ -333,12 +352,26 @@ class _DeviceCoverage:
         eng.hit_keys_dev(dp.data_ptr(), n, dpos.data_ptr(), got, dkeys.data_ptr())
         eng.synchronize()
         pos = dpos[:got].cpu().numpy()
-        key_rows = dkeys[:got * W].cpu().numpy().view(np.uint64).reshape(got, W)
         lo = np.searchsorted(pos, offs[keep], side="left")
         hi = np.searchsorted(pos, offs[keep + 1] - 1, side="left") if len(keep) else lo
         hit_idx, kmers = [], []
+        led = self.ledger
+        if led is not None:
+            # every hit's read -> that read's ordinal among the kept reads (-1: not kept); the kept hits' rows stay in HBM
+            ordinal = np.full(nr + 1, -1, np.int64)                       # (the last entry serves a hit outside every read)
+            ordinal[keep] = led.n_reads + np.arange(len(keep))
+            hit_ord = torch.from_numpy(ordinal).to(self.dev)[dreads[:got]]
+            sel = hit_ord >= 0
+            led.keys.append(dkeys[:got * W].view(got, W)[sel].reshape(-1))
+            led.ordinals.append(hit_ord[sel])
+            torch.cuda.synchronize(self.dev)
+            kmers = (led.n_reads + np.arange(len(keep))).tolist()
+            led.n_reads += len(keep)
+        key_rows = dkeys[:got * W].cpu().numpy().view(np.uint64).reshape(got, W) if led is None else None
         for a, b, s in zip(lo.tolist(), hi.tolist(), offs[keep].tolist()):
             hit_idx.append(pos[a:b] - s)
+            if led is not None:
+                continue
             if a == b:
                 kmers.append(set())
                 continue
@@ -408,9 +441,15 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
 
     ``KDF_DEVICE_COVERAGE=1``: the two coverage sums and the per-read k-mer sets are made on the device
     (``_DeviceCoverage``); the tuple is the same.
+
+    ``KDF_DEVICE_REGIONS=1`` (implies the former): no per-read k-mer set is made.  The key rows of the kept reads' hits
+    stay in HBM in ``last_ledger`` (``RegionLedger``), and ``unique_in_read`` of a ``read_hits`` entry is the read's
+    ordinal in that ledger; ``discovery.regions._cluster_read_hits_device`` counts the regions' k-mers from it.
     """
     import collections
     from ..kmer_utils import canonicalize
+    global last_ledger
+    last_ledger = None
     eng = engine or _worker_engine
     if eng is None:
         raise RuntimeError("scan worker not initialised (_init_scan_worker)")
@@ -424,10 +463,13 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
     refs = rd.references()
     # KDF_DEVICE_COVERAGE=1, read here at every call (it implies the device hits path): the coverage sums stay in HBM
     dcov = None
-    if os.environ.get("KDF_DEVICE_COVERAGE") == "1":
+    want_regions = os.environ.get("KDF_DEVICE_REGIONS") == "1"       # (read at every call, like the switch it implies)
+    if want_regions or os.environ.get("KDF_DEVICE_COVERAGE") == "1":
         lengths = rd.reference_lengths()
         if _DeviceCoverage.fits(eng, lengths):
-            dcov = _DeviceCoverage(eng, lengths)
+            dcov = _DeviceCoverage(eng, lengths, RegionLedger(eng, refs) if want_regions else None)
+        elif want_regions:
+            logger.info("KDF_DEVICE_REGIONS: without the device coverage path the regions are clustered on the host")
     with rd:
         for batch in rd:
             total_scanned += batch.n_reads
@@ -442,6 +484,8 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
                         "pos": int(batch.positions[r]), "cigar": batch.cigartuples(r), "sa": batch.sa_tag(r),
                         "qlen": int(batch.offsets[r + 1] - batch.offsets[r]) - 1, "hit_idx": idx, "kmers": km,
                     }
+                    if dcov.ledger is not None:                 # km is the read's ordinal in the ledger
+                        rec["kmers"], rec["ordinal"] = None, km
                     per_task.setdefault(rec["ref_id"], []).append(rec)
                 continue
             try:
@@ -497,7 +541,7 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
             if key in reads_seen:                       # already reported by an earlier task
                 continue
             read_hits.append((chrom, rec["pos"], reference_end(rec["pos"], rec["cigar"]), rec["name"],
-                              rec["kmers"], is_supp))
+                              rec["ordinal"] if "ordinal" in rec else rec["kmers"], is_supp))
         reads_seen |= seen_local
     if dcov is not None:
         try:
@@ -508,5 +552,6 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
             kmer_coverage[chrom].update(c)
         for chrom, c in rc.items():
             read_coverage[chrom].update(c)
+        last_ledger = dcov.ledger
     return (read_hits, reads_seen, unmapped_informative, total_scanned, read_sv_meta,
             kmer_coverage, read_coverage)

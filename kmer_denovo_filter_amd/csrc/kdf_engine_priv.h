@@ -40,10 +40,10 @@ struct KbPass;                            // kdf_binned.h (the core)
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 1, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 1, BUF_BD = BUF_VAR + 3, BUF_COUNT = BUF_BD + 3 };
+enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 1, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 1, BUF_BD = BUF_VAR + 3, BUF_REG = BUF_BD + 3, BUF_COUNT = BUF_REG + 2 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions"};
 // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
 // table is needed or the ring is full (kb_flush_ring).  Reserved by upper bounds (one entry per stream position), so no
 // host round trip sits between the stages.  Host only: what the kernels take of it is KbPlan (kdf_device.h).
@@ -191,6 +191,8 @@ struct kdf_engine {
     DevBuf *const cov_buf = buf + BUF_COV;           // [1] CIGAR prefix sums
     // ---- VCF mode (kdf_variants.h): grow-only scratch ------------------------------------------------------------------------
     DevBuf *const var_buf = buf + BUF_VAR;           // [3] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags
+    // ---- regions of informative reads (kdf_regions.h): grow-only scratch ----------------------------------------------------
+    DevBuf *const reg_buf = buf + BUF_REG;           // [2] 0 the sort's top key word, block maxima and boundary flags, 1 the permutation
     // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
     bool sk_on = false;
     KdfSketch sk{};                                  // the register cells (device) and p

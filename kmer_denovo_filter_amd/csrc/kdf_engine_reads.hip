@@ -1,7 +1,7 @@
 // kdf_engine_reads.hip -- libkdf.so, the per-read consumers of a read stream: per-window counts and per-read depth
 // (kdf_depth.h), per-read hits and the hit list of the scan (kdf_hits.h), hits in reference coordinates
-// (kdf_coverage.h) and VCF mode (kdf_variants.h).  They share kh_scan_kernel and the CIGAR prefix sums; the table is
-// only read.  The engine itself is kdf_engine.hip, what this unit uses of it is declared in kdf_engine_priv.h.
+// (kdf_coverage.h), VCF mode (kdf_variants.h) and the regions of informative reads (kdf_regions.h, which takes plain
+// arrays).  They share kh_scan_kernel and the CIGAR prefix sums; the table is only read.  The engine itself is kdf_engine.hip, what this unit uses of it is declared in kdf_engine_priv.h.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstring>
@@ -13,6 +13,8 @@
 #include "kdf_hits.h"
 #include "kdf_coverage.h"
 #include "kdf_variants.h"
+#include "kdf_regions.h"
+#include "kdf_sort.h"
 
 // kh_scan_kernel for a caller in another unit (the spool's kdf_spool_select_reads): a kernel is compiled in one unit only
 void kh_scan_launch(hipStream_t s, unsigned long long *sums, uint64_t n) { hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, s, sums, n); }
@@ -621,6 +623,144 @@ int kdf_variant_evidence(kdf_engine *h, const uint64_t *keys, const uint64_t *en
     int rc;
     if ((rc = c.commit()) || (rc = kdf_variant_evidence_dev(h, c.dev(ik), c.dev(iep), n_entries, c.dev(ipv), c.dev(ipf), n_pairs, n_var, c.dev(opr), c.dev(ovr))) ||
         (rc = c.fetch(opr, pair_bytes)) || (rc = c.fetch(ovr, var_bytes))) return rc;
+    return c.finish();
+}
+
+// ------------------------------------------------ regions of informative reads (kdf_regions.h) ----
+
+int kdf_cluster_intervals_dev(kdf_engine *h, const void *d_chrom, const void *d_start, const void *d_end, int64_t n, int64_t merge_distance,
+                              void *d_region_of, void *d_regions_out, uint64_t cap, uint64_t *n_out) {
+    static const char *const fn = "kdf_cluster_intervals_dev";
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    *n_out = 0;
+    if (n < 0 || (uint64_t)n >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "%s: n = %lld outside 0 .. 2^32 - 1", fn, (long long)n);
+    if (merge_distance < 0 || merge_distance >= (1ll << 62)) return fail(h, KDF_ERR_INVALID, "%s: merge_distance = %lld outside 0 .. 2^62 - 1", fn, (long long)merge_distance);
+    if (n == 0) return KDF_OK;
+    if (!d_chrom || !d_start || !d_end || !d_region_of || (cap && !d_regions_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    const uint64_t un = (uint64_t)n, nb = (un + KR_BLOCK - 1) / KR_BLOCK;
+    // scratch: the chrom word of the sort, then the block maxima, then one flag per entry
+    StageLayout lay;
+    const int ik = lay.add(un * 8), ia = lay.add(nb * sizeof(KrMax)), ifl = lay.add(un);
+    int rc;
+    if ((rc = eng_reserve(h, h->reg_buf[0], lay.total, slack_8th, "interval scratch"))) return rc;
+    if ((rc = eng_reserve(h, h->reg_buf[1], un * 4, slack_8th, "interval order"))) return rc;
+    if ((rc = eng_reserve(h, h->hit_buf[1], (nb + 1) * 8, slack_8th, "block sums"))) return rc;
+    uint64_t *ckey = (uint64_t *)lay.at(h->reg_buf[0].p, ik);
+    KrMax *agg = (KrMax *)lay.at(h->reg_buf[0].p, ia);
+    uint8_t *flags = (uint8_t *)lay.at(h->reg_buf[0].p, ifl);
+    uint32_t *perm = (uint32_t *)h->reg_buf[1].p;
+    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    const int64_t *chrom = (const int64_t *)d_chrom, *start = (const int64_t *)d_start, *end = (const int64_t *)d_end;
+    const unsigned blocks = (unsigned)nb;
+    EvSpan p1(h->timer[T_REG], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
+    hipLaunchKernelGGL(kr_chrom_key_kernel, dim3(blocks), dim3(256), 0, h->stream, chrom, un, ckey);
+    HIPCHK(h, hipGetLastError());
+    {
+        const KdfSortPass passes[2] = {{(const uint64_t *)d_start, 1, 0, 62}, {ckey, 1, 0, 32}};
+        std::string serr;
+        if (kdf_sort_perm_device(passes, 2, un, perm, h->stream, serr)) return fail(h, KDF_ERR_HIP, "%s: sort failed: %s", fn, serr.c_str());
+    }
+    hipLaunchKernelGGL(kr_max_block_kernel, dim3(blocks), dim3(256), 0, h->stream, chrom, end, (const uint32_t *)perm, un, agg);
+    hipLaunchKernelGGL(kr_max_scan_kernel, dim3(1), dim3(256), 0, h->stream, agg, nb);
+    hipLaunchKernelGGL(kr_flag_kernel, dim3(blocks), dim3(256), 0, h->stream, chrom, start, end, (const uint32_t *)perm, un, (uint64_t)merge_distance,
+                       (const KrMax *)agg, flags, sums);
+    hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, nb);
+    p1.stop();
+    HIPCHK(h, hipGetLastError());
+    uint64_t n_regions = 0;
+    if ((rc = hits_total(h, nb, &n_regions))) return rc;             // (synchronises: the caller learns the number of regions)
+    *n_out = n_regions;
+    const uint64_t rows = std::min<uint64_t>(n_regions, cap);
+    EvSpan p2(h->timer[T_REG], h->prof, h->stream, 0);            // (the same call's second group: time only)
+    if (rows) HIPCHK(h, hipMemsetAsync(d_regions_out, 0, rows * 32, h->stream));
+    hipLaunchKernelGGL(kr_regions_kernel, dim3(blocks), dim3(256), 0, h->stream, chrom, start, end, (const uint32_t *)perm, (const uint8_t *)flags, un,
+                       (const unsigned long long *)sums, (int64_t *)d_region_of, (unsigned long long *)d_regions_out, rows);
+    p2.stop();
+    HIPCHK(h, hipGetLastError());
+    if (n_regions > cap)
+        return fail(h, KDF_ERR_INVALID, "%s: %llu regions, the buffer holds %llu", fn, (unsigned long long)n_regions, (unsigned long long)cap);
+    return KDF_OK;
+}
+
+int kdf_cluster_intervals(kdf_engine *h, const int64_t *chrom, const int64_t *start, const int64_t *end, int64_t n, int64_t merge_distance,
+                          int64_t *region_of, int64_t *regions_out, uint64_t cap, uint64_t *n_out) {
+    static const char *const fn = "kdf_cluster_intervals";
+    if (!h || !n_out) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    *n_out = 0;
+    if (n < 0 || (uint64_t)n >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "%s: n = %lld outside 0 .. 2^32 - 1", fn, (long long)n);
+    if (merge_distance < 0 || merge_distance >= (1ll << 62)) return fail(h, KDF_ERR_INVALID, "%s: merge_distance = %lld outside 0 .. 2^62 - 1", fn, (long long)merge_distance);
+    if (n == 0) return KDF_OK;
+    if (!chrom || !start || !end || !region_of || (cap && !regions_out)) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    for (int64_t i = 0; i < n; ++i) {                                 // (before any device work; skipped intervals are not looked at)
+        if (chrom[i] < 0) continue;
+        if (chrom[i] >= (1ll << 31)) return fail(h, KDF_ERR_INVALID, "%s: chrom[%lld] = %lld is not below 2^31", fn, (long long)i, (long long)chrom[i]);
+        if (start[i] < 0 || end[i] < start[i] || end[i] >= (1ll << 62))
+            return fail(h, KDF_ERR_INVALID, "%s: interval %lld = [%lld, %lld) breaks 0 <= start <= end < 2^62", fn, (long long)i, (long long)start[i], (long long)end[i]);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t col = (size_t)n * 8;
+    HostCall c(h, fn);
+    const int ic = c.in(chrom, col), is = c.in(start, col), ie = c.in(end, col), iro = c.out(region_of, col), irg = c.out(regions_out, (size_t)cap * 32);
+    int rc;
+    if ((rc = c.commit())) return rc;
+    const int rcl = kdf_cluster_intervals_dev(h, c.dev(ic), c.dev(is), c.dev(ie), n, merge_distance, c.dev(iro), c.dev(irg), cap, n_out);
+    if (rcl && !(rcl == KDF_ERR_INVALID && *n_out > cap)) return rcl;
+    if ((rc = c.fetch(iro, col)) || (rc = c.fetch(irg, (size_t)std::min<uint64_t>(*n_out, cap) * 32)) || (rc = c.finish())) return rc;
+    return rcl;
+}
+
+int kdf_group_distinct_dev(kdf_engine *h, const void *d_group, const void *d_keys, int words, uint64_t n, int64_t n_groups, void *d_counts_out) {
+    static const char *const fn = "kdf_group_distinct_dev";
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "%s: %llu entries are beyond the 2^32 - 1 a call takes", fn, (unsigned long long)n);
+    if (words < 1 || words > 8) return fail(h, KDF_ERR_INVALID, "%s: words = %d outside 1 .. 8", fn, words);
+    if (n_groups < 0) return fail(h, KDF_ERR_INVALID, "%s: n_groups = %lld is negative", fn, (long long)n_groups);
+    if (n_groups == 0) return KDF_OK;
+    if (!d_counts_out || (n && (!d_group || !d_keys))) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemsetAsync(d_counts_out, 0, (size_t)n_groups * 8, h->stream));
+    if (n == 0) return KDF_OK;
+    int rc;
+    if ((rc = eng_reserve(h, h->reg_buf[0], n * 8, slack_8th, "group words"))) return rc;
+    if ((rc = eng_reserve(h, h->reg_buf[1], n * 4, slack_8th, "row order"))) return rc;
+    uint64_t *gkey = (uint64_t *)h->reg_buf[0].p;
+    uint32_t *perm = (uint32_t *)h->reg_buf[1].p;
+    const uint64_t *keys = (const uint64_t *)d_keys;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    EvSpan p(h->timer[T_REG], h->prof, h->stream, 1);
+    hipLaunchKernelGGL(kr_group_key_kernel, dim3(blocks), dim3(256), 0, h->stream, (const int64_t *)d_group, keys, words, n, (uint64_t)n_groups, gkey);
+    HIPCHK(h, hipGetLastError());
+    {
+        // the group word on top: its values are 0 .. n_groups (n_groups: ignored), so it costs the radix passes of their bits
+        KdfSortPass passes[9];
+        for (int j = 0; j < words; ++j) passes[j] = KdfSortPass{keys + j, (uint64_t)words, 0, 64};
+        passes[words] = KdfSortPass{gkey, 1, 0, (int)std::max<uint32_t>(1, log2ceil((uint64_t)n_groups + 1))};
+        std::string serr;
+        if (kdf_sort_perm_device(passes, words + 1, n, perm, h->stream, serr)) return fail(h, KDF_ERR_HIP, "%s: sort failed: %s", fn, serr.c_str());
+    }
+    hipLaunchKernelGGL(kr_distinct_kernel, dim3(blocks), dim3(256), 0, h->stream, (const uint64_t *)gkey, keys, words, (const uint32_t *)perm, n,
+                       (uint64_t)n_groups, (unsigned long long *)d_counts_out);
+    p.stop();
+    HIPCHK(h, hipGetLastError());
+    return KDF_OK;
+}
+
+int kdf_group_distinct(kdf_engine *h, const int64_t *group, const uint64_t *keys, int words, uint64_t n, int64_t n_groups, uint64_t *counts_out) {
+    static const char *const fn = "kdf_group_distinct";
+    if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
+    if (n >= (1ull << 32)) return fail(h, KDF_ERR_INVALID, "%s: %llu entries are beyond the 2^32 - 1 a call takes", fn, (unsigned long long)n);
+    if (words < 1 || words > 8) return fail(h, KDF_ERR_INVALID, "%s: words = %d outside 1 .. 8", fn, words);
+    if (n_groups < 0) return fail(h, KDF_ERR_INVALID, "%s: n_groups = %lld is negative", fn, (long long)n_groups);
+    if (n_groups == 0) return KDF_OK;
+    if (!counts_out || (n && (!group || !keys))) return fail(h, KDF_ERR_INVALID, "%s: NULL pointer", fn);
+    const size_t count_bytes = (size_t)n_groups * 8;
+    if (n == 0) { memset(counts_out, 0, count_bytes); return KDF_OK; }
+    HIPCHK(h, hipSetDevice(h->device));
+    HostCall c(h, fn);
+    const int ig = c.in(group, (size_t)n * 8), ik = c.in(keys, (size_t)n * 8 * (size_t)words), io = c.out(counts_out, count_bytes);
+    int rc;
+    if ((rc = c.commit()) || (rc = kdf_group_distinct_dev(h, c.dev(ig), c.dev(ik), words, n, n_groups, c.dev(io))) || (rc = c.fetch(io, count_bytes))) return rc;
     return c.finish();
 }
 

@@ -8,6 +8,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <string>
 
+#include "kdf_sort.h"
+
 namespace {
 
 __global__ void iota_kernel(uint32_t *idx, uint64_t n) {
@@ -116,6 +118,47 @@ int kdf_sort_rows_device(uint64_t *d_keys, int words, uint32_t *d_cnt, uint64_t 
         hipLaunchKernelGGL(gather_kernel<uint32_t>, dim3(blocks), dim3(256), 0, stream, (const uint32_t *)d_cnt, (const uint32_t *)idx0, (uint32_t *)b.p[6], n);
         SCHK(hipMemcpyAsync(d_cnt, b.p[6], n * 4, hipMemcpyDeviceToDevice, stream));
     }
+    SCHK(hipGetLastError());
+    SCHK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+namespace {
+// the key word of this pass for the item that idx[i] names
+__global__ void gather_stride_kernel(const uint64_t *__restrict__ keys, uint64_t stride, const uint32_t *__restrict__ idx,
+                                     uint64_t *__restrict__ dst, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = keys[(uint64_t)idx[i] * stride];
+}
+}  // namespace
+
+// The permutation alone (kdf_sort.h): the LSD passes of kdf_sort_rows_device with a bit range per pass, so that a narrow
+// word (a group index, a contig rank) costs the radix passes of its bits, and no gather at the end.
+int kdf_sort_perm_device(const KdfSortPass *passes, int n_passes, uint64_t n, uint32_t *d_perm, hipStream_t stream, std::string &err) {
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull) { err = "a sort of more than 2^32 items"; return 1; }
+    Bufs b;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    uint32_t *idx0 = d_perm, *idx1; uint64_t *k0, *k1;
+    SCHK(hipMalloc(&b.p[1], n * 4)); idx1 = (uint32_t *)b.p[1];
+    SCHK(hipMalloc(&b.p[2], n * 8)); k0 = (uint64_t *)b.p[2];
+    SCHK(hipMalloc(&b.p[3], n * 8)); k1 = (uint64_t *)b.p[3];
+    hipLaunchKernelGGL(iota_kernel, dim3(blocks), dim3(256), 0, stream, idx0, n);
+    size_t tmp = 0;
+    for (int j = 0; j < n_passes; ++j) {       // (the temporary storage may depend on the bit range)
+        size_t t = 0;
+        SCHK(rocprim::radix_sort_pairs(nullptr, t, k0, k1, idx0, idx1, n, passes[j].begin_bit, passes[j].end_bit, stream));
+        tmp = t > tmp ? t : tmp;
+    }
+    SCHK(hipMalloc(&b.p[4], tmp ? tmp : 8));
+    for (int j = 0; j < n_passes; ++j) {       // stable passes carry the permutation: idx0 in, idx1 out, swapped
+        if (passes[j].end_bit <= passes[j].begin_bit) continue;
+        hipLaunchKernelGGL(gather_stride_kernel, dim3(blocks), dim3(256), 0, stream, passes[j].keys, passes[j].stride, (const uint32_t *)idx0, k0, n);
+        size_t t = tmp;
+        SCHK(rocprim::radix_sort_pairs(b.p[4], t, k0, k1, idx0, idx1, n, passes[j].begin_bit, passes[j].end_bit, stream));
+        std::swap(idx0, idx1);
+    }
+    if (idx0 != d_perm) SCHK(hipMemcpyAsync(d_perm, idx0, n * 4, hipMemcpyDeviceToDevice, stream));
     SCHK(hipGetLastError());
     SCHK(hipStreamSynchronize(stream));
     return 0;

@@ -39,6 +39,54 @@ def _cluster_read_hits(read_hits, merge_distance):
     return regions, region_reads, region_kmers
 
 
+def _n_kmers(x):
+    """distinct k-mers of a region: ``region_kmers`` holds their set (host path) or their number (device path)"""
+    return x if isinstance(x, int) else len(x)
+
+
+def _cluster_read_hits_device(eng, read_hits, ledger, merge_distance, refs):
+    """``_cluster_read_hits`` under ``KDF_DEVICE_REGIONS=1``: the sweep is ``cluster_intervals_dev`` over the mapped
+    hits, the k-mers of a region are counted by ``group_distinct_dev`` over the ledger of key rows the scan left in HBM
+    (``bam_scanner.RegionLedger``; a ``read_hits`` entry carries its read's ordinal there in place of a k-mer set).
+    Names stay on the host: ``region_reads`` is built from ``region_of``.  ``region_kmers`` is {region: int}."""
+    import numpy as np
+    import torch
+    regions, region_reads, region_kmers = [], {}, {}
+    if not read_hits:
+        return regions, region_reads, region_kmers
+    # the reference sorts by contig NAME: a contig's rank is its place among the sorted names
+    names = sorted(set(refs) | {h[0] for h in read_hits})
+    rank = {name: i for i, name in enumerate(names)}
+    dev = torch.device("cuda", eng.device)
+    up = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int64)).to(dev)
+    n = len(read_hits)
+    d_chrom, d_start, d_end = up([rank[h[0]] for h in read_hits]), up([h[1] for h in read_hits]), up([h[2] for h in read_hits])
+    d_region_of = torch.empty(n, dtype=torch.int64, device=dev)
+    d_rows = torch.empty((n, 4), dtype=torch.int64, device=dev)          # (at most one region per hit)
+    torch.cuda.synchronize(dev)
+    m = eng.cluster_intervals_dev(d_chrom.data_ptr(), d_start.data_ptr(), d_end.data_ptr(), n, merge_distance,
+                                  d_region_of.data_ptr(), d_rows.data_ptr(), n)
+    eng.synchronize()
+    region_of = d_region_of.cpu().numpy()
+    regions = [(names[c], s, e) for c, s, e, _ in d_rows[:m].cpu().numpy().tolist()]
+    for key in regions:
+        region_reads[key] = set()
+    for h, g in zip(read_hits, region_of.tolist()):
+        region_reads[regions[g]].add(h[3])
+    # every ledger entry's group: the region of its read, -1 for a kept read that did not reach read_hits
+    region_of_read = np.full(max(ledger.n_reads, 1), -1, np.int64)
+    region_of_read[np.asarray([h[4] for h in read_hits], dtype=np.int64)] = region_of
+    d_counts = torch.zeros(m, dtype=torch.int64, device=dev)
+    if ledger.ordinals:
+        d_ord, d_keys = torch.cat(ledger.ordinals), torch.cat(ledger.keys)
+        d_group = up(region_of_read)[d_ord]
+        torch.cuda.synchronize(dev)
+        eng.group_distinct_dev(d_group.data_ptr(), d_keys.data_ptr(), ledger.words, len(d_ord), m, d_counts.data_ptr())
+        eng.synchronize()
+    region_kmers = {key: int(c) for key, c in zip(regions, d_counts.cpu().numpy().tolist())}
+    return regions, region_reads, region_kmers
+
+
 def _anchor_and_cluster(child_bam, ref_fasta, proband_unique_kmers, kmer_size, merge_distance=500, threads=1,
                         min_distinct_kmers_per_read=1, proband_unique_fa=None, proband_jf=None,
                         n_proband_unique=None, tmpdir=None, memory_limit_gb=None):
@@ -46,7 +94,9 @@ def _anchor_and_cluster(child_bam, ref_fasta, proband_unique_kmers, kmer_size, m
     *proband_jf*, *proband_unique_fa* or the k-mer set, as in the reference; the
     scan runs in this process on the GPU (no fork pool: a HIP context must not be
     forked).  Returns (regions, region_reads, total_informative, region_kmers,
-    unmapped_informative, read_sv_meta, kmer_coverage, read_coverage)."""
+    unmapped_informative, read_sv_meta, kmer_coverage, read_coverage).  Under
+    ``KDF_DEVICE_REGIONS=1`` the clustering and the regions' k-mer counts are made on
+    the device and region_kmers holds each region's NUMBER of k-mers, not their set."""
     source = proband_jf or proband_unique_fa or proband_unique_kmers
     if source is None:
         raise ValueError("no proband-unique k-mers supplied")
@@ -56,7 +106,12 @@ def _anchor_and_cluster(child_bam, ref_fasta, proband_unique_kmers, kmer_size, m
     total_informative = len(read_hits) + unmapped_informative
     logger.info("Anchoring complete: %d informative reads (%d mapped, %d unmapped) from %d scanned",
                 total_informative, len(read_hits), unmapped_informative, scanned)
-    regions, region_reads, region_kmers = _cluster_read_hits(read_hits, merge_distance)
+    ledger = bam_scanner.last_ledger                                  # KDF_DEVICE_REGIONS=1 and the device path ran: not None
+    if ledger is not None:
+        regions, region_reads, region_kmers = _cluster_read_hits_device(ledger.eng, read_hits, ledger, merge_distance, ledger.refs)
+        bam_scanner.last_ledger = None                                # (its tensors are HBM: not kept past their one use)
+    else:
+        regions, region_reads, region_kmers = _cluster_read_hits(read_hits, merge_distance)
     logger.info("Clustered %d mapped informative reads into %d regions", len(read_hits), len(regions))
     return (regions, region_reads, total_informative, region_kmers, unmapped_informative, read_sv_meta,
             kmer_coverage, read_coverage)
@@ -69,7 +124,7 @@ def _filter_regions(regions, region_reads, region_kmers, min_supporting_reads=1,
     kept = []
     for key in regions:
         if (len(region_reads.get(key, ())) >= min_supporting_reads
-                and len(region_kmers.get(key, ())) >= min_distinct_kmers):
+                and _n_kmers(region_kmers.get(key, ())) >= min_distinct_kmers):
             kept.append(key)
         else:
             region_reads.pop(key, None)
@@ -173,7 +228,7 @@ def _write_bed(regions, region_reads, region_kmers, bed_path, region_annotations
         for key in regions:
             a = (region_annotations or {}).get(key, {})
             fh.write("\t".join(str(x) for x in (
-                key[0], key[1], key[2], len(region_reads.get(key, ())), len(region_kmers.get(key, ())),
+                key[0], key[1], key[2], len(region_reads.get(key, ())), _n_kmers(region_kmers.get(key, ())),
                 a.get("split_reads", 0), a.get("discordant_pairs", 0), a.get("max_clip_len", 0),
                 a.get("unmapped_mates", 0), a.get("class", "SMALL"))) + "\n")
 

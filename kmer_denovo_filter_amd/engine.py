@@ -16,6 +16,7 @@ shells out to ("External op" table):
     scan(stream)             JellyfishKmerQuery / Module-3 probe
     read_hits(stream)        ... and its per-read hits / distinct on the device
     hit_coverage(...)        ... and its hits in reference coordinates (k-mer / read coverage)
+    cluster_intervals(...)   ... and its regions; group_distinct(...): the distinct k-mers of each
 
 Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
 keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
@@ -885,6 +886,72 @@ class KmerEngine:
         self._ck(self._lib.kdf_variant_evidence_dev(self._h, p(d_keys), p(d_entry_pair), int(n_entries), p(d_pair_var), p(d_pair_flags),
                                                     int(n_pairs), int(n_var), p(d_pair_rows), p(d_var_rows)))
 
+    # -- regions of informative reads ------------------------------------------
+    def _cluster_intervals(self, chrom, start, end, n, merge_distance, region_of, regions, cap):
+        m = c_uint64(0)
+        rc = self._lib.kdf_cluster_intervals(self._h, _vp(chrom), _vp(start), _vp(end), int(n), int(merge_distance),
+                                             _vp(region_of), _vp(regions), int(cap), byref(m))
+        return rc, m.value
+
+    def cluster_intervals(self, chrom: np.ndarray, start: np.ndarray, end: np.ndarray, merge_distance: int):
+        """Cluster intervals into regions (``include/kdf.h``, "regions of informative reads"): ``chrom`` (a rank the
+        caller defines, < 0: the interval is skipped), ``start``, ``end`` int64[n] in any order.  An interval opens a
+        region iff it is the first of its chrom in (chrom, start) order or starts more than ``merge_distance`` past the
+        largest end of the earlier intervals of its chrom.  -> (region_of int64[n], -1 for skipped intervals; regions
+        int64 (m, 4), columns ``REGION_COLUMNS``), regions numbered in (chrom, start) order."""
+        c = np.ascontiguousarray(chrom, dtype=np.int64)
+        s = np.ascontiguousarray(start, dtype=np.int64)
+        e = np.ascontiguousarray(end, dtype=np.int64)
+        if not (c.ndim == s.ndim == e.ndim == 1 and len(c) == len(s) == len(e)):
+            raise ValueError(f"chrom, start and end must be 1-D arrays of one length, not {c.shape}, {s.shape}, {e.shape}")
+        region_of = np.full(len(c), -1, np.int64)
+        rc, m = self._cluster_intervals(c, s, e, len(c), merge_distance, region_of, None, 0)      # the sizing call
+        if m == 0:
+            self._ck(rc)
+            return region_of, np.zeros((0, len(REGION_COLUMNS)), np.int64)
+        regions = np.zeros((m, len(REGION_COLUMNS)), np.int64)
+        rc, m = self._cluster_intervals(c, s, e, len(c), merge_distance, region_of, regions, m)
+        self._ck(rc)
+        return region_of, regions
+
+    def _cluster_intervals_dev(self, d_chrom, d_start, d_end, n, merge_distance, d_region_of, d_regions, cap):
+        m = c_uint64(0)
+        p = lambda x: c_void_p(x) if x else None
+        rc = self._lib.kdf_cluster_intervals_dev(self._h, p(d_chrom), p(d_start), p(d_end), int(n), int(merge_distance),
+                                                 p(d_region_of), p(d_regions), int(cap), byref(m))
+        return rc, m.value
+
+    def cluster_intervals_dev(self, d_chrom: int, d_start: int, d_end: int, n: int, merge_distance: int, d_region_of: int,
+                              d_regions: Optional[int], cap: int) -> int:
+        """The same between device buffers (``d_chrom`` / ``d_start`` / ``d_end`` / ``d_region_of`` int64[n],
+        ``d_regions`` int64[cap x 4] or None with ``cap`` 0 for a sizing call); returns the number of regions and raises
+        when it exceeds ``cap`` (``d_region_of`` is complete then, at most ``cap`` rows are written).  Synchronises."""
+        rc, m = self._cluster_intervals_dev(d_chrom, d_start, d_end, n, merge_distance, d_region_of, d_regions, cap)
+        self._ck(rc)
+        return m
+
+    def group_distinct(self, group: np.ndarray, keys: np.ndarray, n_groups: int) -> np.ndarray:
+        """uint64[n_groups]: the number of distinct rows of ``keys`` (uint64 (n, words), words 1..8, or 1-D for one
+        word; rows as :meth:`hit_keys` returns them) among the entries with ``group[e] == g``.  Entries with a group
+        outside [0, n_groups) and rows of all-ones words are ignored; the same row in two groups counts in both.  Exact."""
+        g = np.ascontiguousarray(group, dtype=np.int64)
+        ks = np.ascontiguousarray(keys, dtype=np.uint64)
+        if ks.ndim == 1:
+            ks = ks.reshape(-1, 1)
+        if g.ndim != 1 or ks.ndim != 2 or len(ks) != len(g):
+            raise ValueError(f"{g.shape} groups for key rows of shape {ks.shape}")
+        counts = np.zeros(max(int(n_groups), 0), np.uint64)
+        v = lambda a: _vp(a) if a.size else None
+        self._ck(self._lib.kdf_group_distinct(self._h, v(g), v(ks), int(ks.shape[1]), len(g), int(n_groups), v(counts)))
+        return counts
+
+    def group_distinct_dev(self, d_group: int, d_keys: int, words: int, n: int, n_groups: int, d_counts: int):
+        """The same between device buffers: ``d_group`` int64[n], ``d_keys`` uint64[n x words], ``d_counts``
+        uint64[n_groups], overwritten.  Synchronises the engine's stream (the sort); the counts are complete in stream
+        order."""
+        p = lambda x: c_void_p(x) if x else None
+        self._ck(self._lib.kdf_group_distinct_dev(self._h, p(d_group), p(d_keys), int(words), int(n), int(n_groups), p(d_counts)))
+
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):
         """`jellyfish query -s reads.fa` over a whole stream: uint32[n_bases], the stored count of the canonical k-mer
@@ -925,6 +992,8 @@ class KmerEngine:
 READ_DEPTH_COLUMNS = ("windows", "present", "low", "min", "max", "sum")
 # columns of KmerEngine.read_hits' rows
 READ_HITS_COLUMNS = ("hits", "distinct")
+# columns of KmerEngine.cluster_intervals' regions
+REGION_COLUMNS = ("chrom", "start", "end", "members")
 
 
 def estimate_from_registers(regs) -> float:
