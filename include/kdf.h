@@ -812,6 +812,68 @@ int kdf_group_distinct_dev(kdf_engine *h, const void *d_group, const void *d_key
 int kdf_group_distinct(kdf_engine *h, const int64_t *group, const uint64_t *keys, int words, uint64_t n,
                        int64_t n_groups, uint64_t *counts_out);
 
+/* ------------------------------------------------------ k-mer FASTA codec ---- */
+
+/* The text of the k-mer files the discovery stages hand on (child_candidates.fa .. proband_unique.fa), made from keys
+ * in device memory and read back into keys there.  The key form follows the call's k, not the engine's (as `words` of
+ * kdf_group_distinct*): any engine on the device formats and parses any stage's set.
+ *     k 1 .. 32        lo[n]
+ *     k 33 .. 63       lo[n] and hi[n]
+ *     odd k 65 .. 201  n x W uint64 rows (W = kdf_key_words(k)) in the lo position, hi NULL
+ * Any other k is KDF_ERR_INVALID.  Bits as everywhere: base i of the k-mer at bits 2(k - 1 - i) of the value, word 0
+ * least significant, A C G T = 0 1 2 3.  The table is not touched: no flush, any engine.
+ *
+ * Format.  layout KDF_TEXT_FASTA: record e is '>' + the decimal digits of first_index + e + '\n' + k upper-case bases
+ * + '\n' (printf(">%llu\n%s\n")).  KDF_TEXT_ROWS: k bases per key and nothing else (first_index is ignored).
+ *   - kdf_kmer_text_bytes is the size of the whole text, a pure host function (no engine, no GPU): records differ in
+ *     length only by the digits of their index, so the text is at most 20 runs of equal records.  It returns 0 for a k
+ *     or layout outside the above, and when first_index + n or the size passes 2^63 (n == 0 is 0 bytes as well).
+ *   - a call writes bytes [byte_first, byte_first + byte_count) of the whole text to text_out[0 .. byte_count) and
+ *     nothing else; the window may begin and end inside a record, a header or a digit string, so a text of any size
+ *     goes through one bounded buffer.  byte_first % 16 != 0, a window that passes kdf_kmer_text_bytes and a (k, layout,
+ *     first_index, n) for which that is 0 are KDF_ERR_INVALID, and nothing is written.  byte_count == 0 and n == 0 are
+ *     KDF_OK.  A window takes fewer than 2^43 bytes.
+ *   - work: one kernel.  A lane owns 16 consecutive output bytes, finds the record of its first byte from the table of
+ *     the runs (kernel arguments) with one multiply-high in place of the division, walks its 16 bytes and stores them
+ *     at once (byte stores: the window's last partial 16 bytes, and every byte when text_out is not 16-byte aligned).
+ *     The keys of a workgroup's 4 KiB of text are staged in LDS with coalesced loads.
+ *   - the device form runs in stream order on the engine's stream and does not synchronise.  The host form stages all
+ *     n keys and the window through the engine's staging arena.
+ *
+ * Parse.  The rule of the reference's readers of these files: lines end at '\n' (with final_chunk a missing last '\n'
+ * is supplied); one trailing '\r' is stripped; empty lines and lines whose first byte is '>' are skipped; every other
+ * line must be exactly k bytes of ACGTacgt.  Its key is the forward value or, with canonical != 0, the numeric minimum
+ * of the forward and the reverse-complement value.  Keys are written in file order.
+ *   - without final_chunk only whole lines are consumed: *consumed_out is the offset behind the last '\n' (0 when the
+ *     chunk holds none) and the caller hands the rest over again in front of the next chunk.  With final_chunk
+ *     *consumed_out is n_bytes.
+ *   - *n_out is always set.  When it exceeds cap the call returns KDF_ERR_INVALID with the first cap rows written (the
+ *     convention of kdf_hit_list_dev); lo / hi may be NULL with cap == 0: a sizing call, which checks the lines as well.
+ *   - a bad line returns KDF_ERR_IO: *bad_offset_out (may be NULL; ~0 when no line is bad) is the offset of the first
+ *     byte of the first bad line of the chunk, and kdf_last_error names the rule that line broke -- its length, or,
+ *     its length being k, a base.  Both are the same from run to run.  *n_out then counts the bad lines too.
+ *   - whatever the text holds, nothing is written outside lo / hi[0 .. min(cap, *n_out)).
+ *   - work: a pass that counts the sequence-line starts of 4 KiB tiles of the text (16-byte loads when the text is
+ *     16-byte aligned), a scan of the tile counts, and a pass over the same tiles in which a lane checks and encodes the
+ *     lines that start in its 16 bytes and stores their rows at their rank.  A chunk takes fewer than 2^43 bytes.
+ *   - both forms synchronise the engine's stream: the caller learns *n_out.
+ *
+ * Under kdf_profile(h, 1) the kernels of both are timed with HIP events: stats "kmerfasta_us" / "kmerfasta_passes"
+ * (one pass per call that launches). */
+#define KDF_TEXT_FASTA 0
+#define KDF_TEXT_ROWS  1
+uint64_t kdf_kmer_text_bytes(int k, int layout, uint64_t first_index, uint64_t n);
+int kdf_format_kmers_dev(kdf_engine *h, const void *d_lo, const void *d_hi, uint64_t n, int k, int layout,
+                         uint64_t first_index, uint64_t byte_first, uint64_t byte_count, void *d_text_out);
+int kdf_format_kmers(kdf_engine *h, const uint64_t *lo, const uint64_t *hi, uint64_t n, int k, int layout,
+                     uint64_t first_index, uint64_t byte_first, uint64_t byte_count, uint8_t *text_out);
+int kdf_parse_kmer_fasta_dev(kdf_engine *h, const void *d_text, uint64_t n_bytes, int k, int canonical, int final_chunk,
+                             void *d_lo, void *d_hi, uint64_t cap, uint64_t *n_out, uint64_t *consumed_out,
+                             uint64_t *bad_offset_out);
+int kdf_parse_kmer_fasta(kdf_engine *h, const uint8_t *text, uint64_t n_bytes, int k, int canonical, int final_chunk,
+                         uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n_out, uint64_t *consumed_out,
+                         uint64_t *bad_offset_out);
+
 /* ------------------------------------------- count profile of a stream ---- */
 
 /* `jellyfish query idx -s reads.fa` over a whole read stream: counts_out[i], 0 <= i < n_bases, is the stored count of

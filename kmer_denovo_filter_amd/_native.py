@@ -88,6 +88,14 @@ SYMBOLS = [
     ("kdf_cluster_intervals", c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, c_uint64, POINTER(c_uint64)]),
     ("kdf_group_distinct_dev", c_int, [_P, _P, _P, c_int, c_uint64, c_int64, _P]),
     ("kdf_group_distinct", c_int, [_P, _P, _P, c_int, c_uint64, c_int64, _P]),
+    # k-mer FASTA codec
+    ("kdf_kmer_text_bytes", c_uint64, [c_int, c_int, c_uint64, c_uint64]),
+    ("kdf_format_kmers_dev", c_int, [_P, _P, _P, c_uint64, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
+    ("kdf_format_kmers", c_int, [_P, _P, _P, c_uint64, c_int, c_int, c_uint64, c_uint64, c_uint64, _P]),
+    ("kdf_parse_kmer_fasta_dev", c_int, [_P, _P, c_uint64, c_int, c_int, c_int, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64),
+                                         POINTER(c_uint64)]),
+    ("kdf_parse_kmer_fasta", c_int, [_P, _P, c_uint64, c_int, c_int, c_int, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64),
+                                     POINTER(c_uint64)]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),

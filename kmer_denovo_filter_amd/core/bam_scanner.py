@@ -25,7 +25,7 @@ import numpy as np
 from .. import jf_io
 from .._native import KDF_ERR_NOMEM, KdfError
 from ..engine import KmerEngine, mirror_engine, hit_positions
-from ..kmer_fasta import read_kmer_fasta_keys
+from ..kmer_fasta import load_kmer_set
 from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys, stream_words
 
 logger = logging.getLogger(__name__)
@@ -72,7 +72,7 @@ def _init_scan_worker(proband_data, kmer_size, min_distinct_kmers_per_read=1, de
             jf_io.load_index_into(eng, proband_data, expect_k=kmer_size)
             lo = None
         elif isinstance(proband_data, str):
-            lo, hi = read_kmer_fasta_keys(proband_data, kmer_size)
+            lo, hi = load_kmer_set(proband_data, kmer_size, device=device)
             cnt = np.ones(len(lo), np.uint32)
         else:
             lo, hi = kmers_to_keys(list(proband_data), kmer_size)

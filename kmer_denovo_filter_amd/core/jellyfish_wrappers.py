@@ -22,7 +22,7 @@ import numpy as np
 from .. import dist_env, jf_io
 from .._native import KdfError
 from ..engine import mirror_engine
-from ..kmer_fasta import read_kmer_fasta_keys
+from ..kmer_fasta import load_kmer_set
 from ..reads import ReadStream, bam_reader, fasta_reader, keys_to_kmers, sketch_batches_overlapped, stream_batches_overlapped
 
 logger = logging.getLogger(__name__)
@@ -185,7 +185,7 @@ def _scan_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent_
     logger.info("Scanning parent BAM (%s): %s", bam_size, parent_bam)
     scan_start = time.monotonic()
     try:
-        lo, hi = read_kmer_fasta_keys(kmer_fasta, kmer_size)
+        lo, hi = load_kmer_set(kmer_fasta, kmer_size, device=_device())
         logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)",
                     kmer_size, threads, len(lo))
         with mirror_engine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:

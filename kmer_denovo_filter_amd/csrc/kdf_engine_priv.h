@@ -1,5 +1,5 @@
 // kdf_engine_priv.h -- what the units of libkdf.so share of the engine (host only, no kernel): kdf_engine.hip (the
-// core, which defines every function declared here unless noted), kdf_engine_reads.hip and kdf_spool.hip.  Nothing
+// core, which defines every function declared here unless noted), kdf_engine_reads.hip, kdf_kmerfasta.hip and kdf_spool.hip.  Nothing
 // here is exported: include/kdf.h is the library's interface.
 //
 // One kernel, one unit: a __global__ function is compiled by exactly one unit (a non-template kernel in a header two
@@ -42,8 +42,8 @@ enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_stat
 // every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
 enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 1, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 1, BUF_BD = BUF_VAR + 3, BUF_REG = BUF_BD + 3, BUF_COUNT = BUF_REG + 2 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta"};
 // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
 // table is needed or the ring is full (kb_flush_ring).  Reserved by upper bounds (one entry per stream position), so no
 // host round trip sits between the stages.  Host only: what the kernels take of it is KbPlan (kdf_device.h).

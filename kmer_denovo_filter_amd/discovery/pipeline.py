@@ -33,7 +33,7 @@ from ..core.jellyfish_wrappers import (
     _stream_bam,
 )
 from ..engine import mirror_engine
-from ..kmer_fasta import read_kmer_fasta_keys, remove_with_sidecar, write_kmer_fasta
+from ..kmer_fasta import (device_fasta, load_kmer_set, read_kmer_fasta_keys_device, remove_with_sidecar, store_kmer_set)
 
 logger = logging.getLogger(__name__)
 
@@ -446,7 +446,7 @@ def _extract_child_kmers_discovery(child_bam, ref_fasta, kmer_size, min_child_co
     rank = dist_env.world_rank()[1]
     n_candidates = len(lo)
     if rank == 0:
-        write_kmer_fasta(child_candidates_fa, lo, hi, kmer_size)
+        store_kmer_set(child_candidates_fa, kmer_size, cand, (lo, hi))
     dist_env.barrier()                                             # the file exists (and has its final size) on every rank
     devkeys.register(child_candidates_fa, *cand, kmer_size)
     logger.info("Child k-mer dump complete (%s, %d candidates, FASTA: %s)",
@@ -469,8 +469,10 @@ def _subtract_reference_kmers(ref_jf, child_candidates_fa, tmpdir):
     try:
         k = _index_k(ref_jf)
         dev = devkeys.lookup(child_candidates_fa, k)             # the candidates are still in HBM when Module 1 ran here
-        if dev is None:
-            lo, hi = read_kmer_fasta_keys(child_candidates_fa, k)
+        if dev is None and device_fasta():                       # (KDF_DEVICE_FASTA=1: parsed where it is used)
+            dev = read_kmer_fasta_keys_device(child_candidates_fa, k, device=_device())
+        elif dev is None:
+            lo, hi = load_kmer_set(child_candidates_fa, k)
             dev = devkeys.from_host(lo, hi, k > 32) if len(lo) else None
         world, rank, host = dist_env.world_rank()
         if dev is not None and dev[0].numel():
@@ -494,7 +496,7 @@ def _subtract_reference_kmers(ref_jf, child_candidates_fa, tmpdir):
     n_non_ref = len(lo)
     dist_env.barrier()                                             # every rank has read what it needs of the input file
     if dist_env.is_root():
-        write_kmer_fasta(child_non_ref_fa, lo, hi, k)
+        store_kmer_set(child_non_ref_fa, k, (dlo, dhi) if dlo is not None else None, (lo, hi), _device())
         remove_with_sidecar(child_candidates_fa)
     dist_env.barrier()
     if dlo is not None:
@@ -548,7 +550,7 @@ def _extract_child_non_ref_kmers(child_bam, ref_fasta, ref_jf, kmer_size, min_ch
         if ref_eng is not None:
             ref_eng.close()
     n_candidates, n_non_ref = seen["candidates"], len(lo)
-    write_kmer_fasta(child_non_ref_fa, lo, hi, kmer_size)
+    store_kmer_set(child_non_ref_fa, kmer_size, cand, (lo, hi))
     devkeys.register(child_non_ref_fa, *cand, kmer_size)
     logger.info("Child k-mer join complete (%s, %d candidates, FASTA: %s)", _format_elapsed(time.monotonic() - dump_start),
                 n_candidates, _format_file_size(child_non_ref_fa))
@@ -565,7 +567,7 @@ def _count_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent
     logger.info("%s: scanning BAM (%s): %s", label, _format_file_size(parent_bam), parent_bam)
     scan_start = time.monotonic()
     try:
-        lo, hi = read_kmer_fasta_keys(kmer_fasta, kmer_size)
+        lo, hi = load_kmer_set(kmer_fasta, kmer_size, device=_device())
         logger.info("  BAM stream -> MI355X count --if (k=%d, threads=%d, filter_kmers=%d)",
                     kmer_size, threads, len(lo))
         with mirror_engine(kmer_size, capacity_hint=max(len(lo), 1), device=_device()) as eng:
@@ -623,8 +625,10 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
     are a device-side mask.  ``after_mother.fa`` and ``proband_unique.fa`` are written as the reference writes them."""
     try:
         dev = devkeys.lookup(child_non_ref_fa, kmer_size)
-        if dev is None:
-            lo, hi = read_kmer_fasta_keys(child_non_ref_fa, kmer_size)
+        if dev is None and device_fasta():
+            dev = read_kmer_fasta_keys_device(child_non_ref_fa, kmer_size, device=_device())
+        elif dev is None:
+            lo, hi = load_kmer_set(child_non_ref_fa, kmer_size)
             if len(lo) == 0:
                 return 0, None
             dev = devkeys.from_host(lo, hi, kmer_size > 32)
@@ -663,7 +667,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
     after_mother_fa = os.path.join(tmpdir, "after_mother.fa")
     n_surviving = int(dlo.shape[0])
     if dist_env.is_root():                                         # (the contract files are written once; every rank holds the same sets)
-        write_kmer_fasta(after_mother_fa, *devkeys.to_host(dlo, dhi), kmer_size)
+        store_kmer_set(after_mother_fa, kmer_size, (dlo, dhi))
     logger.info("Mother: %d / %d non-ref k-mers found (count > %d), %d surviving",
                 n_input - n_surviving, n_input, parent_max_count, n_surviving)
     if n_surviving == 0:
@@ -673,7 +677,7 @@ def _filter_parents_discovery(mother_bam, father_bam, ref_fasta, child_non_ref_f
     proband_unique_fa = os.path.join(tmpdir, "proband_unique.fa")
     n_proband = int(dlo.shape[0])
     if dist_env.is_root():
-        write_kmer_fasta(proband_unique_fa, *devkeys.to_host(dlo, dhi), kmer_size)
+        store_kmer_set(proband_unique_fa, kmer_size, (dlo, dhi))
         remove_with_sidecar(after_mother_fa)
     dist_env.barrier()
     logger.info("Father: %d / %d surviving k-mers found (count > %d), %d proband-unique",

@@ -17,6 +17,7 @@ shells out to ("External op" table):
     read_hits(stream)        ... and its per-read hits / distinct on the device
     hit_coverage(...)        ... and its hits in reference coordinates (k-mer / read coverage)
     cluster_intervals(...)   ... and its regions; group_distinct(...): the distinct k-mers of each
+    format_kmers(keys)       the k-mer files between the stages, `>{i}\\n{KMER}\\n`, as text; parse_kmer_fasta(text): back
 
 Long k-mers (odd k from 65 to 201) get a "long" engine (``engine.long``): its
 keys are ``(n, key_words)`` C-contiguous uint64 arrays, word 0 the least
@@ -48,8 +49,22 @@ def _vp(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
 
 
+# layouts of KmerEngine.format_kmers (KDF_TEXT_FASTA, KDF_TEXT_ROWS)
+TEXT_FASTA, TEXT_ROWS = 0, 1
+
+
+class KmerFastaError(ValueError):
+    """A line of k-mer FASTA text breaks the rule (``KmerEngine.parse_kmer_fasta``): ``offset`` is that of the first byte
+    of the chunk's first bad line, ``rule`` is "length" or "base"."""
+
+    def __init__(self, msg: str, offset: int):
+        super().__init__(msg)
+        self.offset = int(offset)
+        self.rule = "base" if "non-ACGT" in msg else "length"
+
+
 class KmerEngine:
-    MAX_K = 63                 # (lo, hi) keys
+    MAX_K = 63                # (lo, hi) keys
     LONG_MIN_K, LONG_MAX_K = 65, 201   # long engines: odd k only, (n, key_words) keys
 
     def __init__(self, k: int, capacity_hint: int = 1 << 20, device: int = 0):
@@ -951,6 +966,81 @@ class KmerEngine:
         order."""
         p = lambda x: c_void_p(x) if x else None
         self._ck(self._lib.kdf_group_distinct_dev(self._h, p(d_group), p(d_keys), int(words), int(n), int(n_groups), p(d_counts)))
+
+    # -- k-mer FASTA codec -----------------------------------------------------
+    @staticmethod
+    def kmer_text_bytes(k: int, layout: int = TEXT_FASTA, first_index: int = 0, n: int = 0) -> int:
+        """Bytes of the text of ``n`` keys (``include/kdf.h``, "k-mer FASTA codec"): ``TEXT_FASTA`` records
+        ``>{first_index + e}\\n{KMER}\\n`` or ``TEXT_ROWS`` k bases per key.  A pure host function of libkdf: no engine,
+        no GPU.  0 for a k or layout the codec does not take and when the indices or the size pass 2^63."""
+        return int(_native.load().kdf_kmer_text_bytes(int(k), int(layout), int(first_index), int(n)))
+
+    def format_kmers(self, lo: np.ndarray, hi: Optional[np.ndarray], k: int, layout: int = TEXT_FASTA, first_index: int = 0,
+                     byte_first: int = 0, byte_count: Optional[int] = None) -> np.ndarray:
+        """uint8[byte_count]: bytes ``byte_first .. byte_first + byte_count`` (default: to the end) of the text of the
+        keys, whose form follows ``k`` and not the engine's k: ``lo`` uint64[n] (k <= 32), ``lo`` and ``hi`` (k 33..63),
+        (n, W) rows in ``lo`` and ``hi`` None (odd k 65..201).  ``byte_first`` must be a multiple of 16."""
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        hi = None if hi is None or not 33 <= int(k) <= 63 else np.ascontiguousarray(hi, dtype=np.uint64)
+        n = len(lo)
+        if byte_count is None:
+            byte_count = max(self.kmer_text_bytes(k, layout, first_index, n) - int(byte_first), 0)
+        out = np.empty(int(byte_count), np.uint8)
+        v = lambda a: _vp(a) if a is not None and a.size else None
+        self._ck(self._lib.kdf_format_kmers(self._h, v(lo), v(hi), n, int(k), int(layout), int(first_index), int(byte_first),
+                                            int(byte_count), v(out)))
+        return out
+
+    def format_kmers_dev(self, d_lo: int, d_hi: Optional[int], n: int, k: int, layout: int, first_index: int, byte_first: int,
+                         byte_count: int, d_text: int):
+        """The same between device buffers (raw pointers): ``d_text`` takes ``byte_count`` bytes and nothing else.  Stream
+        order on the engine's stream; does not synchronise."""
+        p = lambda x: c_void_p(x) if x else None
+        self._ck(self._lib.kdf_format_kmers_dev(self._h, p(d_lo), p(d_hi), int(n), int(k), int(layout), int(first_index),
+                                                int(byte_first), int(byte_count), p(d_text)))
+
+    def _parse_result(self, rc, n, consumed, bad):
+        """(n keys, consumed bytes) of a parse call, or its error: a bad line raises ``KmerFastaError`` (a ValueError)."""
+        if rc == _native.KDF_ERR_IO:
+            msg = self._lib.kdf_last_error(self._h)
+            raise KmerFastaError(msg.decode(errors="replace") if msg else "bad line", bad.value)
+        self._ck(rc)
+        return n.value, consumed.value
+
+    def parse_kmer_fasta(self, text, k: int, canonical: bool = True, final_chunk: bool = True):
+        """Sequence lines of a chunk of k-mer FASTA text (bytes or uint8 array) -> ``(lo, hi, consumed)``: the keys in
+        file order in the form of ``k`` (hi None unless k is 33..63; long k: (n, W) rows) and the bytes consumed -- all of
+        them with ``final_chunk``, else up to the last ``\\n``.  Lines: ``include/kdf.h``, "k-mer FASTA codec"; a bad
+        line raises ``KmerFastaError`` with its offset."""
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        W = key_words(k)
+        if W == 0:
+            raise ValueError(f"k={k} outside 1..{self.MAX_K} and odd {self.LONG_MIN_K}..{self.LONG_MAX_K}")
+        n, consumed, bad = c_uint64(0), c_uint64(0), c_uint64(0)
+        args = (self._h, _vp(t) if t.size else None, t.size, int(k), int(bool(canonical)), int(bool(final_chunk)))
+        rc = self._lib.kdf_parse_kmer_fasta(*args, None, None, 0, byref(n), byref(consumed), byref(bad))       # the sizing call
+        if rc == _native.KDF_ERR_INVALID and n.value > 0:
+            rc = _native.KDF_OK
+        m = self._parse_result(rc, n, consumed, bad)[0]
+        lo = np.zeros((m, W) if W > 2 else m, np.uint64)
+        hi = np.zeros(m, np.uint64) if W == 2 else None
+        if m:
+            rc = self._lib.kdf_parse_kmer_fasta(*args, _vp(lo), _vp(hi), m, byref(n), byref(consumed), byref(bad))
+            self._parse_result(rc, n, consumed, bad)
+        return lo, hi, consumed.value
+
+    def parse_kmer_fasta_dev(self, d_text: int, n_bytes: int, k: int, canonical: bool, final_chunk: bool, d_lo: Optional[int],
+                             d_hi: Optional[int], cap: int) -> Tuple[int, int]:
+        """The same between device buffers: ``d_lo`` / ``d_hi`` hold ``cap`` rows (None with ``cap`` 0: a sizing call).
+        -> (number of keys, bytes consumed); raises when the keys exceed ``cap`` (the first ``cap`` are written).
+        Synchronises the engine's stream."""
+        p = lambda x: c_void_p(x) if x else None
+        n, consumed, bad = c_uint64(0), c_uint64(0), c_uint64(0)
+        rc = self._lib.kdf_parse_kmer_fasta_dev(self._h, p(d_text), int(n_bytes), int(k), int(bool(canonical)), int(bool(final_chunk)),
+                                                p(d_lo), p(d_hi), int(cap), byref(n), byref(consumed), byref(bad))
+        if rc == _native.KDF_ERR_INVALID and cap == 0 and n.value > 0:      # a sizing call's answer
+            rc = _native.KDF_OK
+        return self._parse_result(rc, n, consumed, bad)
 
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):
