@@ -445,38 +445,39 @@ static uint32_t bucket_bits_for(const kdf_engine *h, uint32_t log2cap) {
     return std::min<uint32_t>(log2cap, KB_BB_SMALL(h->kw) + (log2cap >= h->opt_big_bucket_log2cap ? 1u : 0u));
 }
 
-static int table_alloc(kdf_engine *h, uint32_t log2cap, KdfTable &t, bool clear = true) {
+// A table of 2^log2cap slots that is not the engine's yet: its arrays and the view of them.  It frees itself unless
+// table_adopt takes it.
+struct NewTable { TableMem mem; KdfTable t{}; };
+
+static int table_alloc(kdf_engine *h, uint32_t log2cap, NewTable &nt, bool clear = true) {
     const uint64_t cap = 1ull << log2cap;
+    KdfTable &t = nt.t;
     t = KdfTable{};
+    hipError_t e = nt.mem.lo.alloc(cap * 8);
+    if (e == hipSuccess && h->kw >= 2) e = nt.mem.hi.alloc(cap * 8 * (h->kw - 1));   // long keys: words 1 .. W-1
+    if (e == hipSuccess) e = nt.mem.cnt.alloc(cap * 4);
+    if (e != hipSuccess) {
+        nt.mem = TableMem{};
+        return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP,
+                    "a table of 2^%u slots (%.1f GB) does not fit the device (%s): count the sample in key-space "
+                    "slices (option key_parts / key_part; KDF_KEY_PARTS for the child count)",
+                    log2cap, (double)cap * (8.0 * h->kw + 4.0) / 1e9, hipGetErrorString(e));
+    }
+    t.lo = nt.mem.lo.as<uint64_t>(); t.hi = nt.mem.hi.as<uint64_t>(); t.cnt = nt.mem.cnt.as<uint32_t>();
     t.log2cap = log2cap;
     t.bucket_bits = bucket_bits_for(h, log2cap);
     t.hshift = h->opt_hash_shift;
-    {
-        hipError_t e = hipMalloc((void **)&t.lo, cap * 8);
-        if (e == hipSuccess && h->kw >= 2) e = hipMalloc((void **)&t.hi, cap * 8 * (h->kw - 1));   // long keys: words 1 .. W-1
-        if (e == hipSuccess) e = hipMalloc((void **)&t.cnt, cap * 4);
-        if (e != hipSuccess) {
-            if (t.lo) (void)hipFree(t.lo);
-            if (t.hi) (void)hipFree(t.hi);
-            t = KdfTable{};
-            (void)hipGetLastError();
-            return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP,
-                        "a table of 2^%u slots (%.1f GB) does not fit the device (%s): count the sample in key-space "
-                        "slices (option key_parts / key_part; KDF_KEY_PARTS for the child count)",
-                        log2cap, (double)cap * (8.0 * h->kw + 4.0) / 1e9, hipGetErrorString(e));
-        }
-    }
     if (!clear) return KDF_OK;                       // the caller keeps the engine's deferred-clear flag set
     HIPCHK(h, hipMemsetAsync(t.lo, 0xFF, cap * 8, h->stream));
     if (h->kw >= 2) HIPCHK(h, hipMemsetAsync(t.hi, 0xFF, cap * 8 * (h->kw - 1), h->stream));
     HIPCHK(h, hipMemsetAsync(t.cnt, 0, cap * 4, h->stream));
     return KDF_OK;
 }
-static void table_free(KdfTable &t) {
-    if (t.lo) (void)hipFree(t.lo);
-    if (t.hi) (void)hipFree(t.hi);
-    if (t.cnt) (void)hipFree(t.cnt);
-    t = KdfTable{};
+// nt becomes the engine's table; the old one is freed (the caller has drained the stream that may still read it)
+static void table_adopt(kdf_engine *h, NewTable &nt) {
+    h->t_mem = std::move(nt.mem);
+    h->t = nt.t; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
+    h->cap = 1ull << h->t.log2cap;
 }
 
 // kdf_clear defers the 12 B/slot memset: a binned insert into an empty table
@@ -526,8 +527,8 @@ static int ctl_reset(kdf_engine *h, bool keep_windows) {
 }
 
 // the sieve no longer describes the table (keys joined it, it was cleared, a new filter, other sizing options)
-static void bin_sieve_drop(kdf_engine *h) { h->bsv_valid = false; h->bsv_unfit = false; }
-static void sieve_drop(kdf_engine *h) { h->sieve_valid = false; h->sieve_unfit = false; bin_sieve_drop(h); }
+static void bin_sieve_drop(kdf_engine *h) { h->bsv.valid = false; h->bsv.unfit = false; }
+static void sieve_drop(kdf_engine *h) { h->sieve.valid = false; h->sieve.unfit = false; bin_sieve_drop(h); }
 
 // Insert-or-add n keys into table t, adding add[i] (NULL: 0).  Caller keys (stored = false) are the (lo, hi) arrays of
 // k <= 63 or the row-major W-word rows at lo of long keys; stored = true: lo / hi are the arrays of the live table,
@@ -560,32 +561,27 @@ static int table_rehash(kdf_engine *h, uint32_t new_log2) {
     // (the window counter lives on the device between synchronisations: pending partition passes have added to it)
     { int rc0 = ctl_sync(h, nullptr); if (rc0) return rc0; }
     if (h->lazy_empty || h->distinct == 0) {              // nothing to carry over: a new table (a lazily cleared one stays so)
-        KdfTable nt0;
+        NewTable nt0;
         int rc0 = table_alloc(h, new_log2, nt0, !h->lazy_empty);
         if (rc0) return rc0;
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        table_free(h->t);
-        h->t = nt0; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
-        h->cap = 1ull << new_log2;
+        table_adopt(h, nt0);
         return KDF_OK;
     }
-    KdfTable nt;
+    NewTable nt;
     int rc = table_alloc(h, new_log2, nt);
-    if (rc) { table_free(nt); return rc; }
+    if (rc) return rc;
     const uint64_t windows = h->windows;
     rc = ctl_reset(h, false);
-    if (rc) { table_free(nt); return rc; }
-    insert_keys(h, nt, h->t.lo, h->t.hi, h->t.cnt, h->cap, true);
+    if (rc) return rc;
+    insert_keys(h, nt.t, h->t.lo, h->t.hi, h->t.cnt, h->cap, true);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { table_free(nt); return fail(h, KDF_ERR_HIP, "rehash launch failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(h, KDF_ERR_HIP, "rehash launch failed: %s", hipGetErrorString(e));
     bool full = false;
     rc = ctl_sync(h, &full);
-    if (rc) { table_free(nt); return rc; }
-    if (full) { table_free(nt); return fail(h, KDF_ERR_TABLE_FULL, "rehash: bucket overflow at 2^%u slots", new_log2); }
-    table_free(h->t);
-    h->t = nt;
-    h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
-    h->cap = 1ull << new_log2;
+    if (rc) return rc;
+    if (full) return fail(h, KDF_ERR_TABLE_FULL, "rehash: bucket overflow at 2^%u slots", new_log2);
+    table_adopt(h, nt);
     // restore the window counter (host-side accumulation)
     h->windows = windows;
     HIPCHK(h, hipMemcpyAsync(&h->ctl->windows[0], &h->windows, 8, hipMemcpyHostToDevice, h->stream));
@@ -731,49 +727,50 @@ template <int KW> static constexpr size_t kb_lds_b() { return (size_t)KbCfg<KW>:
 // the LDS limits of the binned path's kernels, raised once per engine and key width
 template <int KW>
 static int kb_ensure_attrs(kdf_engine *h) {
-    if (h->attrs_set[KW]) return KDF_OK;
+    if (h->kb.attrs_set[KW]) return KDF_OK;
     const size_t lds_c = KB_C_LDS(KW, KB_BB_SMALL(KW));
     if (const int rc = kb_set_lds_attrs<KW>(h, kb_lds_a<KW>(), kb_lds_b<KW>(), lds_c, ((size_t)(8 * KW + 4) << (KB_BB_SMALL(KW) + 1)) + KB_RI_LDS_BYTES)) return rc;
-    h->attrs_set[KW] = true;
+    h->kb.attrs_set[KW] = true;
     return KDF_OK;
 }
 
 // the small device arrays of the binned path, allocated once per engine; fills the pointers of `s` from the engine's buffers
 static int kb_scratch(kdf_engine *h, KbScratch &s) {
-    if (!h->kb_small) {
-        HIPCHK(h, hipMalloc((void **)&h->kb_small, (16 + 64) * 8));
-        HIPCHK(h, hipMemsetAsync(h->kb_small, 0, (16 + 64) * 8, h->stream));
-        HIPCHK(h, hipHostMalloc((void **)&h->kb_totals_host, 16 * 8));
-        HIPCHK(h, hipMalloc((void **)&h->kb_pass, sizeof(KbPass) * KB_MAX_PASS));
+    KbState &kb = h->kb;
+    if (!kb.small) {
+        HIPCHK(h, kb.small.alloc((16 + 64) * 8));
+        HIPCHK(h, hipMemsetAsync(kb.small.p, 0, (16 + 64) * 8, h->stream));
     }
+    if (!kb.totals_host) HIPCHK(h, kb.totals_host.alloc(16 * 8));
+    if (!kb.pass) HIPCHK(h, kb.pass.alloc(sizeof(KbPass) * KB_MAX_PASS));
     const size_t hv_pairs = (size_t)KB_HV_MAX * KB_HV_SLICES << (KB_BB_SMALL(h->kw) + 1);   // (room for the buckets of big tables)
     const size_t hv_pair_bytes = 8 * (size_t)h->kw + 4;
-    if (!h->kb_heavy) {                                           // heavy buckets of skewed flushes (kb_heavy_slice_kernel): ~200 MB, once
-        HIPCHK(h, hipMalloc((void **)&h->kb_heavy, hv_pairs * hv_pair_bytes + (4 + 3 * KB_HV_MAX) * 4));
-        HIPCHK(h, hipMemsetAsync((char *)h->kb_heavy + hv_pairs * hv_pair_bytes, 0, (4 + 3 * KB_HV_MAX) * 4, h->stream));
+    if (!kb.heavy) {                                              // heavy buckets of skewed flushes (kb_heavy_slice_kernel): ~200 MB, once
+        HIPCHK(h, kb.heavy.alloc(hv_pairs * hv_pair_bytes + (4 + 3 * KB_HV_MAX) * 4));
+        HIPCHK(h, hipMemsetAsync(kb.heavy.as<char>() + hv_pairs * hv_pair_bytes, 0, (4 + 3 * KB_HV_MAX) * 4, h->stream));
     }
     s = KbScratch{};
-    s.totals = h->kb_small; s.trash = (uint64_t *)(h->kb_small + 16);
-    s.pass = h->kb_pass;
-    if (h->kb_heavy) {
-        s.hv_key = (uint64_t *)h->kb_heavy;
+    s.totals = kb.small.as<unsigned long long>(); s.trash = (uint64_t *)(s.totals + 16);
+    s.pass = kb.pass.as<KbPass>();
+    if (kb.heavy) {
+        s.hv_key = kb.heavy.as<uint64_t>();
         s.hv_khi = h->kw == 2 ? s.hv_key + hv_pairs : nullptr;
         s.hv_cnt = (uint32_t *)(s.hv_key + hv_pairs * h->kw);
         s.hv_ctr = s.hv_cnt + hv_pairs; s.hv_bucket = s.hv_ctr + 4; s.hv_n = s.hv_bucket + KB_HV_MAX; s.hv_failed = s.hv_n + KB_HV_MAX;
     }
-    s.ent = (uint64_t *)h->kb_buf[0].p; s.tmp = (uint64_t *)h->kb_buf[1].p;
-    s.chunk_off = (uint32_t *)h->kb_buf[2].p; s.failed = (uint32_t *)h->kb_buf[3].p;
-    s.off = (uint16_t *)h->kb_buf[4].p;
+    s.ent = h->kb.ent.as<uint64_t>(); s.tmp = h->kb.tmp.as<uint64_t>();
+    s.chunk_off = h->kb.chunk_off.as<uint32_t>(); s.failed = h->kb.failed.as<uint32_t>();
+    s.off = h->kb.off_rows.as<uint16_t>();
     // row tables of the ring: row_ent u64 | row_len u32, ring_rows of each
-    s.row_ent = (unsigned long long *)h->kb_buf[6].p;
-    s.row_len = (uint32_t *)(s.row_ent + h->ring.cap_rows);
+    s.row_ent = h->kb.row_tables.as<unsigned long long>();
+    s.row_len = (uint32_t *)(s.row_ent + h->kb.ring.cap_rows);
     return KDF_OK;
 }
 
 // the ring is empty again: nothing pending, the flush-wide counters zeroed
 static int kb_ring_reset(kdf_engine *h) {
-    h->ring.reset();
-    if (h->kb_small) HIPCHK(h, hipMemsetAsync(h->kb_small, 0, 16 * 8, h->stream));
+    h->kb.ring.reset();
+    if (h->kb.small) HIPCHK(h, hipMemsetAsync(h->kb.small.p, 0, 16 * 8, h->stream));
     return KDF_OK;
 }
 
@@ -784,29 +781,29 @@ static int kb_flush_ring(kdf_engine *h, KbDump *dump = nullptr);
 // it is empty.
 static int kb_ring_make_room(kdf_engine *h, uint64_t need_e, uint64_t need_r, uint32_t off_stride) {
     int rc;
-    const uint64_t rows_cap = std::min<uint64_t>(h->ring.cap_rows, h->kb_buf[2].bytes / ((uint64_t)off_stride * 4));
+    const uint64_t rows_cap = std::min<uint64_t>(h->kb.ring.cap_rows, h->kb.chunk_off.bytes / ((uint64_t)off_stride * 4));
     bool forced = false;
-    if (h->ring.n_pass >= KB_MAX_PASS || h->ring.used_entries + need_e > h->ring.cap_entries || h->ring.used_rows + need_r > rows_cap) {
-        forced = !h->ring.empty();
+    if (h->kb.ring.n_pass >= KB_MAX_PASS || h->kb.ring.used_entries + need_e > h->kb.ring.cap_entries || h->kb.ring.used_rows + need_r > rows_cap) {
+        forced = !h->kb.ring.empty();
         if (forced && (rc = kb_flush_ring(h))) return rc;
     }
     const uint64_t esz = 8ull * h->kw;
     const uint64_t budget = h->opt_defer_max_bytes ? h->opt_defer_max_bytes : h->dev_total_bytes / 5 * 2;
-    uint64_t want_e = h->ring.cap_entries;
+    uint64_t want_e = h->kb.ring.cap_entries;
     // (at least 128 / 256 MB: small batches never force a flush; with deferral on, room for one more pass like this one)
     if (need_e > want_e) want_e = std::max<uint64_t>(h->opt_defer ? std::max<uint64_t>(need_e, std::min<uint64_t>(2 * need_e, budget / esz)) : need_e, 1ull << 24);
-    if (forced && h->opt_defer && h->ring.cap_entries * esz < budget)
-        want_e = std::max<uint64_t>(want_e, std::min<uint64_t>(2 * h->ring.cap_entries, std::max<uint64_t>(budget / esz, need_e)));
+    if (forced && h->opt_defer && h->kb.ring.cap_entries * esz < budget)
+        want_e = std::max<uint64_t>(want_e, std::min<uint64_t>(2 * h->kb.ring.cap_entries, std::max<uint64_t>(budget / esz, need_e)));
     // pieces: in proportion to the entries (passes of one sample look alike), and never fewer than this pass needs
     const uint64_t want_r = std::max<uint64_t>(need_r, (uint64_t)((double)need_r * ((double)want_e / (double)need_e))) + 4096;
-    if (want_e > h->ring.cap_entries || need_r > rows_cap) {
+    if (want_e > h->kb.ring.cap_entries || need_r > rows_cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if ((rc = eng_reserve(h, h->kb_buf[0], want_e * esz, slack_page))) return rc;
-        if ((rc = eng_reserve(h, h->kb_buf[2], want_r * (uint64_t)off_stride * 4, slack_page))) return rc;
-        if ((rc = eng_reserve(h, h->kb_buf[6], want_r * 12, slack_page))) return rc;
-        h->ring.cap_entries = std::max(h->ring.cap_entries, want_e); h->ring.cap_rows = std::max(h->ring.cap_rows, want_r);
+        if ((rc = eng_reserve(h, h->kb.ent, want_e * esz, slack_page))) return rc;
+        if ((rc = eng_reserve(h, h->kb.chunk_off, want_r * (uint64_t)off_stride * 4, slack_page))) return rc;
+        if ((rc = eng_reserve(h, h->kb.row_tables, want_r * 12, slack_page))) return rc;
+        h->kb.ring.cap_entries = std::max(h->kb.ring.cap_entries, want_e); h->kb.ring.cap_rows = std::max(h->kb.ring.cap_rows, want_r);
         // (a buffer only ever grows: the row tables are laid out for ring_rows rows)
-        if (h->kb_buf[6].bytes < h->ring.cap_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
+        if (h->kb.row_tables.bytes < h->kb.ring.cap_rows * 12) return fail(h, KDF_ERR_STATE, "entry ring: row tables out of step");
     }
     return KDF_OK;
 }
@@ -821,9 +818,9 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     if (n_tiles == 0) return KDF_OK;
     int rc;
     // pending passes must share their geometry, key slice and mode (kdf_set_option / a mode change flush first)
-    if (!h->ring.empty() && h->ring.filtered != filtered && (rc = kb_flush_ring(h))) return rc;
-    KbPlan plan = h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan;
-    if (h->ring.empty()) { plan.key_parts = filtered ? 0 : h->t.key_parts; plan.key_part = h->t.key_part; }
+    if (!h->kb.ring.empty() && h->kb.ring.filtered != filtered && (rc = kb_flush_ring(h))) return rc;
+    KbPlan plan = h->kb.ring.empty() ? kb_make_plan(h, h->t) : h->kb.ring.plan;
+    if (h->kb.ring.empty()) { plan.key_parts = filtered ? 0 : h->t.key_parts; plan.key_part = h->t.key_part; }
     const int nbins = 1 << plan.c1;
     const uint64_t n_slabs = (n_tiles + TILES_PER_SLAB - 1) / TILES_PER_SLAB;
     const uint64_t n_groups = (n_slabs + plan.group - 1) / plan.group;
@@ -831,21 +828,21 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     const uint64_t n_rows_max = n_groups * nbins + n_entries_max / CHUNK + 1;
     if (n_rows_max >= (1ull << 32) || n_slabs >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "binned pass: too many positions for one pass");
     if ((rc = kb_ring_make_room(h, n_entries_max, n_rows_max, plan.off_stride))) return rc;
-    if (h->ring.empty()) { h->ring.plan = plan; h->ring.filtered = filtered; }
+    if (h->kb.ring.empty()) { h->kb.ring.plan = plan; h->kb.ring.filtered = filtered; }
     plan.dbg = h->opt_debug_flags;
     plan.n_slabs = (uint32_t)n_slabs; plan.n_groups = (uint32_t)n_groups;
     const int nb1 = 1 << KB_C1_MAX;
     const size_t lds_a = kb_lds_a<KW>(), lds_b = kb_lds_b<KW>();
     if ((rc = kb_ensure_attrs<KW>(h))) return rc;
     // the pass's own buffers: slab-sorted entries, offset rows, planning arrays (reused by the next pass: stream order)
-    if ((rc = eng_reserve(h, h->kb_buf[1], n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
-    if ((rc = eng_reserve(h, h->kb_buf[4], n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.tmp, n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.off_rows, n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
     const uint64_t n_pairs = n_groups * nbins;
     const uint64_t ovf_cap = n_entries_max / CHUNK + 1;       // pieces beyond the first of their pair: sum (np - 1) <= entries / CHUNK
-    if ((rc = eng_reserve(h, h->kb_buf[5], n_pairs * 16 + (size_t)nb1 * 12 + (2 * ovf_cap + 2) * 4 + 64, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.pass_plan, n_pairs * 16 + (size_t)nb1 * 12 + (2 * ovf_cap + 2) * 4 + 64, slack_16th))) return rc;
     KbScratch s;
     if ((rc = kb_scratch(h, s))) return rc;
-    s.gpre_ent = (unsigned long long *)h->kb_buf[5].p;
+    s.gpre_ent = h->kb.pass_plan.as<unsigned long long>();
     s.bin_ent = s.gpre_ent + n_pairs;
     s.gn = (uint32_t *)(s.bin_ent + nb1); s.gpre_row = s.gn + n_pairs; s.bin_rows = s.gpre_row + n_pairs; s.ovf = s.bin_rows + nb1;
     s.ovf_cap = (uint32_t)ovf_cap;
@@ -854,7 +851,7 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
     st.stamp();                                                  // start of A
 
-    const uint32_t pass_idx = h->ring.n_pass;
+    const uint32_t pass_idx = h->kb.ring.n_pass;
     const bool sliced = plan.key_parts > 1;
     // A: a workgroup takes a few consecutive slabs (the next slab's words are prefetched under the current one)
     const uint32_t slabs_per_wg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(8, n_slabs / ((uint64_t)h->n_cu * 8)));
@@ -866,8 +863,8 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     st.stamp();                                                // end of A
     hipLaunchKernelGGL(kb_groupsum_kernel, dim3((unsigned)n_groups, (unsigned)((nbins + 63) / 64)), dim3(256), 0, h->stream, plan, s);
     hipLaunchKernelGGL(kb_binscan_kernel<CHUNK>, dim3((unsigned)nbins), dim3(256), 0, h->stream, plan, s);
-    hipLaunchKernelGGL(kb_binfirst_kernel, dim3(1), dim3(KB_THREADS), 0, h->stream, plan, s, pass_idx, (unsigned long long)h->ring.used_entries,
-                       (unsigned long long)h->ring.used_rows, h->ctl);
+    hipLaunchKernelGGL(kb_binfirst_kernel, dim3(1), dim3(KB_THREADS), 0, h->stream, plan, s, pass_idx, (unsigned long long)h->kb.ring.used_entries,
+                       (unsigned long long)h->kb.ring.used_rows, h->ctl);
     HIPCHK(h, hipGetLastError());
     st.stamp();                                                // end of the planning kernels
     // No host round trip: the pass's share of the ring is sized for one entry per position; B's first launch has one
@@ -880,9 +877,9 @@ static int kb_partition(kdf_engine *h, const uint64_t *d_packed, const uint64_t 
     HIPCHK(h, hipGetLastError());
     span.stop();
     st.commit(h->prof_stage_ev);
-    h->ring.n_pass++;
-    h->ring.used_entries += n_entries_max; h->ring.used_rows += n_rows_max;
-    h->ring.positions += n_entries_max;
+    h->kb.ring.n_pass++;
+    h->kb.ring.used_entries += n_entries_max; h->kb.ring.used_rows += n_rows_max;
+    h->kb.ring.positions += n_entries_max;
     h->stat_binned_passes++;
     h->last_path = 1;
     return KDF_OK;
@@ -893,7 +890,7 @@ static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
     launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, admit,
                  [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *adm) {
         constexpr int W = decltype(Wc)::value;
-#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->pf, h->pf_ctr, adm)
+#define PF_LAUNCH(KRN, G) hipLaunchKernelGGL((KRN<W, G>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->pf.view, h->pf.ctr.as<unsigned long long>(), adm)
         if constexpr (W <= 2) { if (adm) PF_LAUNCH(kdf_pf_stream_kernel, true); else PF_LAUNCH(kdf_pf_stream_kernel, false); }
         else { if (adm) PF_LAUNCH(kdf_pf_long_kernel, true); else PF_LAUNCH(kdf_pf_long_kernel, false); }
 #undef PF_LAUNCH
@@ -904,17 +901,12 @@ static void pf_launch(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
 // order: the buffer is reused by the next gated stream).  Not armed: *admit = NULL, the count is not gated.
 static int pf_gate(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases, const uint64_t **admit) {
     *admit = nullptr;
-    if (h->pf_state != PF_ARMED || n_bases == 0) return KDF_OK;
+    if (h->pf.state != PF_ARMED || n_bases == 0) return KDF_OK;
     const uint64_t n_tiles = (n_bases + KDF_TILE - 1) / KDF_TILE;
-    if (h->pf_admit_words < n_tiles) {
-        if (h->pf_admit) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->pf_admit); h->pf_admit = nullptr; h->pf_admit_words = 0; }
-        const uint64_t want = n_tiles + n_tiles / 8 + 512;
-        HIPCHK(h, hipMalloc((void **)&h->pf_admit, want * 8));
-        h->pf_admit_words = want;
-    }
-    pf_launch(h, d_packed, d_invalid, n_bases, h->pf_admit);
+    if (const int rc = eng_reserve(h, h->pf.admit, n_tiles * 8)) return rc;
+    pf_launch(h, d_packed, d_invalid, n_bases, h->pf.admit.as<uint64_t>());
     HIPCHK(h, hipGetLastError());
-    *admit = h->pf_admit;
+    *admit = h->pf.admit.as<uint64_t>();
     return KDF_OK;
 }
 
@@ -958,18 +950,18 @@ struct KbFlush {
 };
 
 // A table that grew since the partition has more buckets than the partition made: kernel C resolves the extra bits itself
-static uint32_t kb_sub_bits_now(const kdf_engine *h) { return (h->t.log2cap - h->t.bucket_bits) - h->ring.plan.c1 - h->ring.plan.c2; }
+static uint32_t kb_sub_bits_now(const kdf_engine *h) { return (h->t.log2cap - h->t.bucket_bits) - h->kb.ring.plan.c1 - h->kb.ring.plan.c2; }
 
 // what the pending passes hold (entries, skew) and what the table holds now; the density accounting
 static int kb_flush_totals(kdf_engine *h, KbFlush &f) {
     int rc;
     if ((rc = kb_scratch(h, f.s))) return rc;
-    f.filtered = h->ring.filtered;
-    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
+    f.filtered = h->kb.ring.filtered;
+    HIPCHK(h, hipMemcpyAsync(h->kb.totals_host.p, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
     if ((rc = ctl_sync(h, nullptr))) return rc;
-    f.n_entries = h->kb_totals_host[0];
-    h->dens_windows += f.n_entries - h->ring.acct_entries; h->dens_positions += h->ring.positions - h->ring.acct_positions;
-    h->ring.acct_entries = f.n_entries; h->ring.acct_positions = h->ring.positions;
+    f.n_entries = h->kb.total(0);
+    h->dens_windows += f.n_entries - h->kb.ring.acct_entries; h->dens_positions += h->kb.ring.positions - h->kb.ring.acct_positions;
+    h->kb.ring.acct_entries = f.n_entries; h->kb.ring.acct_positions = h->kb.ring.positions;
     return KDF_OK;
 }
 
@@ -979,8 +971,8 @@ static KbChoice kb_flush_choose(const kdf_engine *h, const KbFlush &f, const KbD
     KbChoice c{};
     // passes a dump-only flush has applied: kernel C counts their keys again, so the counter restarts at 0 (the table is
     // empty) -- just before the launch (kb_flush_launch), after everything that can still fail or return
-    c.redo = h->ring.n_dumped > 0;
-    c.skewed = h->kb_totals_host[7] != 0 || (h->opt_debug_flags & 4096);          // (debug flag 4096 forces VAR 2: fuzzing)
+    c.redo = h->kb.ring.n_dumped > 0;
+    c.skewed = h->kb.total(7) != 0 || (h->opt_debug_flags & 4096);          // (debug flag 4096 forces VAR 2: fuzzing)
     c.heavy = c.skewed && f.s.hv_ctr;
     c.distinct_before = c.redo ? 0 : h->distinct;
     // Grow BEFORE the flush when the last flush's rate of new keys says the pending entries will not fit: growing now
@@ -994,7 +986,7 @@ static KbChoice kb_flush_choose(const kdf_engine *h, const KbFlush &f, const KbD
     // A table that grew since the partition (kb_sub_bits_now): a per-key test the dump-only instantiation leaves out: such
     // a table takes the ordinary flush.
     c.dump_only = dump_only_ok && h->opt_lazy_table && dump && dump->min_count && !f.filtered && h->lazy_empty && !c.skewed && !c.grow_first &&
-                  kb_sub_bits_now(h) == 0 && h->ring.undumped_passes() && h->ring.plan.key_parts <= 1 && h->pf_state == PF_OFF &&
+                  kb_sub_bits_now(h) == 0 && h->kb.ring.undumped_passes() && h->kb.ring.plan.key_parts <= 1 && h->pf.state == PF_OFF &&
                   !(h->opt_debug_flags & 2048);
     return c;
 }
@@ -1004,12 +996,10 @@ static int kb_grow_first(kdf_engine *h, double est) {
     int rc;
     while (est > 0.6 * (double)h->cap && h->t.log2cap < 40) {
         if (h->lazy_empty) {                                  // nothing to carry over: a new table, still to be cleared
-            KdfTable nt;
+            NewTable nt;
             if ((rc = table_alloc(h, h->t.log2cap + 1, nt, false))) break;       // (no room: kernel C will tell what really overflows)
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            table_free(h->t);
-            h->t = nt; h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;
-            h->cap = 1ull << h->t.log2cap;
+            table_adopt(h, nt);
         } else if ((rc = table_rehash(h, h->t.log2cap + 1))) { (void)hipGetLastError(); h->err.clear(); break; }
     }
     return KDF_OK;
@@ -1019,8 +1009,8 @@ static int kb_grow_first(kdf_engine *h, double est) {
 static int kb_flush_prepare(kdf_engine *h, KbFlush &f, const KbDump *dump) {
     int rc;
     if (f.filtered && (rc = materialize(h))) return rc;
-    f.plan = h->ring.plan;
-    f.plan.n_pass = h->ring.n_pass; f.plan.dbg = h->opt_debug_flags;
+    f.plan = h->kb.ring.plan;
+    f.plan.n_pass = h->kb.ring.n_pass; f.plan.dbg = h->opt_debug_flags;
     f.plan.log2cap = h->t.log2cap; f.plan.bucket_bits = h->t.bucket_bits;
     // a dump is waiting for this flush: kernel C writes it out of the buckets it holds
     if (dump && !f.filtered && dump->min_count) {
@@ -1031,8 +1021,8 @@ static int kb_flush_prepare(kdf_engine *h, KbFlush &f, const KbDump *dump) {
     f.plan.sub_bits = kb_sub_bits_now(h);             // a table that grew since the partition (just now, perhaps): more sub-buckets
     f.nb_table = 1ull << (f.plan.c1 + f.plan.c2 + f.plan.sub_bits);
     const size_t failed_bytes = (size_t)((f.nb_table + 31) / 32) * 4;
-    if ((rc = eng_reserve(h, h->kb_buf[3], failed_bytes, slack_16th))) return rc;
-    f.s.failed = (uint32_t *)h->kb_buf[3].p;
+    if ((rc = eng_reserve(h, h->kb.failed, failed_bytes, slack_16th))) return rc;
+    f.s.failed = h->kb.failed.as<uint32_t>();
     HIPCHK(h, hipMemsetAsync(f.s.failed, 0, failed_bytes, h->stream));
     f.nonempty = h->lazy_empty ? 0 : 1;
     return KDF_OK;
@@ -1093,10 +1083,10 @@ static int kb_flush_launch(kdf_engine *h, const KbFlush &f) {
 // ordinary attempt with the same request.
 static int kb_settle_dump_only(kdf_engine *h, const KbFlush &f, KbDump *dump, uint64_t cursor, bool *again) {
     // whole (no bucket failed) and the table need not grow for what comes next: the dump is the caller's, the passes stay
-    if (h->kb_totals_host[2] == 0 && h->distinct * 10 <= h->cap * 7) {
+    if (h->kb.total(2) == 0 && h->distinct * 10 <= h->cap * 7) {
         dump->done = true; dump->n = cursor; h->stat_fused_dumps++; h->stat_flushes++; h->stat_dump_only++;
         if (f.n_entries >= 100000) h->grow_ratio = (double)(h->distinct - f.c.distinct_before) / (double)f.n_entries;
-        h->ring.n_dumped = h->ring.n_pass; h->ring.dumped_positions = h->ring.positions;
+        h->kb.ring.n_dumped = h->kb.ring.n_pass; h->kb.ring.dumped_positions = h->kb.ring.positions;
         return KDF_OK;
     }
     // otherwise: what the parent path does, from the start -- the ordinary flush of the same passes into the empty table
@@ -1145,11 +1135,11 @@ static int kb_settle(kdf_engine *h, const KbFlush &f, KbDump *dump, uint64_t cur
     int rc;
     // the fused dump is whole only if every bucket went through kernel C's write-back (none failed, none was left to the
     // heavy-bucket kernels); otherwise the caller dumps from the table as usual
-    if (f.plan.dump_min && h->kb_totals_host[2] == 0 && h->kb_totals_host[4] == 0) { dump->done = true; dump->n = cursor; h->stat_fused_dumps++; }
-    if (h->ring.undumped_passes()) h->stat_flushes++;         // (only retained passes: their dump-only flush was counted)
+    if (f.plan.dump_min && h->kb.total(2) == 0 && h->kb.total(4) == 0) { dump->done = true; dump->n = cursor; h->stat_fused_dumps++; }
+    if (h->kb.ring.undumped_passes()) h->stat_flushes++;         // (only retained passes: their dump-only flush was counted)
     h->lazy_empty = false;
-    h->stat_heavy_buckets += h->kb_totals_host[4];
-    const uint64_t n_failed = h->kb_totals_host[2];
+    h->stat_heavy_buckets += h->kb.total(4);
+    const uint64_t n_failed = h->kb.total(2);
     if (n_failed) {
         h->stat_replayed_buckets += n_failed;
         bool ring_kept = false;
@@ -1185,7 +1175,7 @@ static int kb_flush_attempt(kdf_engine *h, KbDump *dump, bool dump_only_ok, bool
     if ((rc = kb_flush_prepare(h, f, dump))) return rc;
     if (f.plan.dbg & 2048) return kb_ring_reset(h);               // (ablation: the partition passes are timed alone, what they wrote is dropped)
     if ((rc = kb_flush_launch(h, f))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->kb_totals_host, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->kb.totals_host.p, f.s.totals, 16 * 8, hipMemcpyDeviceToHost, h->stream));
     bool full = false;
     uint64_t cursor = 0;
     if ((rc = ctl_sync(h, &full, &cursor))) return rc;
@@ -1195,7 +1185,7 @@ static int kb_flush_attempt(kdf_engine *h, KbDump *dump, bool dump_only_ok, bool
 // Kernel C over every pending pass.  dump: a dump is waiting for this flush (the caller's last before it) -- kernel C
 // writes it, and the dump-only flush is allowed; its fallback is a second, ordinary attempt with the same request.
 static int kb_flush_ring(kdf_engine *h, KbDump *dump) {
-    if (h->ring.empty()) return KDF_OK;
+    if (h->kb.ring.empty()) return KDF_OK;
     bool again = false;
     int rc = kb_flush_attempt(h, dump, dump != nullptr, &again);
     if (!rc && again) rc = kb_flush_attempt(h, dump, false, &again);
@@ -1266,28 +1256,26 @@ static int direct_insert(kdf_engine *h, const uint64_t *d_packed, const uint64_t
 // or a window of this batch's last k - 1 positions would run on into the next batch's first bases.
 static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     const uint64_t n_tiles = n_bases / KDF_TILE + 1;
-    if (h->l1.tiles + n_tiles > h->l1.cap_tiles) {
+    if (h->kb.l1.tiles + n_tiles > h->kb.l1.cap_tiles) {
         // grow (the pending stream moves): up to the size at which it is partitioned anyway
-        const uint64_t target = std::max<uint64_t>((h->opt_l1_positions + h->opt_l1_direct_positions) / KDF_TILE + 1, h->l1.tiles + n_tiles);
-        const uint64_t cap = std::min<uint64_t>(target, std::max<uint64_t>({2 * h->l1.cap_tiles, 4 * (h->l1.tiles + n_tiles), (uint64_t)1 << 18}));
-        uint64_t *np = nullptr, *nm = nullptr;
-        HIPCHK(h, hipMalloc((void **)&np, (cap * 2 + 4) * 8));
-        hipError_t e = hipMalloc((void **)&nm, (cap + 2) * 8);
-        if (e != hipSuccess) { (void)hipFree(np); (void)hipGetLastError(); return fail(h, KDF_ERR_NOMEM, "pending stream: %s", hipGetErrorString(e)); }
-        if (h->l1.tiles) {
-            HIPCHK(h, hipMemcpyAsync(np, h->l1.packed, (h->l1.tiles * 2 + 4) * 8, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(nm, h->l1.mask, (h->l1.tiles + 2) * 8, hipMemcpyDeviceToDevice, h->stream));
+        const uint64_t target = std::max<uint64_t>((h->opt_l1_positions + h->opt_l1_direct_positions) / KDF_TILE + 1, h->kb.l1.tiles + n_tiles);
+        const uint64_t cap = std::min<uint64_t>(target, std::max<uint64_t>({2 * h->kb.l1.cap_tiles, 4 * (h->kb.l1.tiles + n_tiles), (uint64_t)1 << 18}));
+        DevBuf np, nm;                                             // (an error below frees them; the stream stays where it is)
+        HIPCHK(h, np.alloc((cap * 2 + 4) * 8));
+        hipError_t e = nm.alloc((cap + 2) * 8);
+        if (e != hipSuccess) return fail(h, KDF_ERR_NOMEM, "pending stream: %s", hipGetErrorString(e));
+        if (h->kb.l1.tiles) {
+            HIPCHK(h, hipMemcpyAsync(np.p, h->kb.l1.packed.p, (h->kb.l1.tiles * 2 + 4) * 8, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(nm.p, h->kb.l1.mask.p, (h->kb.l1.tiles + 2) * 8, hipMemcpyDeviceToDevice, h->stream));
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (h->l1.packed) (void)hipFree(h->l1.packed);
-        if (h->l1.mask) (void)hipFree(h->l1.mask);
-        h->l1.packed = np; h->l1.mask = nm; h->l1.cap_tiles = cap;
+        h->kb.l1.packed = std::move(np); h->kb.l1.mask = std::move(nm); h->kb.l1.cap_tiles = cap;
     }
     const unsigned blocks = (unsigned)((2 * n_tiles + 4 + 255) / 256);               // (covers the kernel's ceil(n_bases / 64) tiles + padding)
-    hipLaunchKernelGGL(kb_append_kernel, dim3(blocks), dim3(256), 0, h->stream, h->l1.packed + 2 * h->l1.tiles, h->l1.mask + h->l1.tiles,
-                       d_packed, d_invalid, n_bases);
+    hipLaunchKernelGGL(kb_append_kernel, dim3(blocks), dim3(256), 0, h->stream, h->kb.l1.packed.as<uint64_t>() + 2 * h->kb.l1.tiles,
+                       h->kb.l1.mask.as<uint64_t>() + h->kb.l1.tiles, d_packed, d_invalid, n_bases);
     HIPCHK(h, hipGetLastError());
-    h->l1.tiles += n_tiles;
+    h->kb.l1.tiles += n_tiles;
     return KDF_OK;
 }
 
@@ -1295,24 +1283,24 @@ static int l1_append(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_
 // LAST flush may serve (earlier ones see counts that are not final)
 int pending_flush(kdf_engine *h, KbDump *dump) {
     int rc;
-    if (h->l1.tiles && h->ring.n_dumped && !h->ring.undumped_passes()) {
+    if (h->kb.l1.tiles && h->kb.ring.n_dumped && !h->kb.ring.undumped_passes()) {
         // small batches behind passes that only a dump-only flush has applied: without lazy_table the ring would be empty
         // and the table live here.  Choose as that engine would; a batch it sends through the direct kernels gets the
         // table first (same last_count_path / binned_passes, and no second rewrite of the table for a few reads)
-        if (!use_binned(h, h->l1.positions(), false, false) && (rc = kb_flush_ring(h))) return rc;
+        if (!use_binned(h, h->kb.l1.positions(), false, false) && (rc = kb_flush_ring(h))) return rc;
     }
-    if (h->l1.tiles) {
-        const bool binned = h->ring.empty() ? use_binned(h, h->l1.positions(), false, h->lazy_empty) : kb_eligible(h);
-        const uint64_t n = h->l1.take();
-        if (binned) rc = kb_partition_stream(h, h->l1.packed, h->l1.mask, n, false);
-        else rc = direct_insert(h, h->l1.packed, h->l1.mask, n);
+    if (h->kb.l1.tiles) {
+        const bool binned = h->kb.ring.empty() ? use_binned(h, h->kb.l1.positions(), false, h->lazy_empty) : kb_eligible(h);
+        const uint64_t n = h->kb.l1.take();
+        if (binned) rc = kb_partition_stream(h, h->kb.l1.packed.as<uint64_t>(), h->kb.l1.mask.as<uint64_t>(), n, false);
+        else rc = direct_insert(h, h->kb.l1.packed.as<uint64_t>(), h->kb.l1.mask.as<uint64_t>(), n);
         if (rc) return rc;
     }
     return kb_flush_ring(h, dump);
 }
 // ... or is forgotten (kdf_clear)
 static int pending_drop(kdf_engine *h) {
-    h->l1.tiles = 0;
+    h->kb.l1.tiles = 0;
     return kb_ring_reset(h);
 }
 
@@ -1322,7 +1310,7 @@ static int pending_drop(kdf_engine *h) {
 // insert-mode count over a device-resident stream
 static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_bases) {
     if (h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_reads: a filter is loaded; call kdf_clear first");
-    if (h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
+    if (h->pf.state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
     sieve_drop(h);                                   // new keys join the table: a sieve built from it earlier (scan) is stale
     h->t.key_parts = h->opt_key_parts; h->t.key_part = h->opt_key_part;       // (tables are re-created by reserve / rehash: set per call)
     if (n_bases == 0) return KDF_OK;
@@ -1334,7 +1322,7 @@ static int count_insert_dev(kdf_engine *h, const uint64_t *d_packed, const uint6
     } else if (n_bases >= h->opt_l1_direct_positions) rc = kb_partition_stream(h, d_packed, d_invalid, n_bases, false);   // big enough by itself
     else {
         rc = l1_append(h, d_packed, d_invalid, n_bases);
-        if (!rc && h->l1.positions() >= h->opt_l1_positions) rc = kb_partition_stream(h, h->l1.packed, h->l1.mask, h->l1.take(), false);
+        if (!rc && h->kb.l1.positions() >= h->opt_l1_positions) rc = kb_partition_stream(h, h->kb.l1.packed.as<uint64_t>(), h->kb.l1.mask.as<uint64_t>(), h->kb.l1.take(), false);
     }
     if (rc) return rc;
     if (!h->opt_defer) return pending_flush(h);
@@ -1352,7 +1340,7 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
         const uint32_t n_wg = (uint32_t)std::min<uint64_t>(n_slabs, (uint64_t)h->n_cu * 8);
         const uint32_t spw = (uint32_t)((n_slabs + n_wg - 1) / n_wg);
         const unsigned grid = (unsigned)((n_slabs + spw - 1) / spw);
-        KdfSieve sv{h->sieve, h->sieve_words - 1};
+        KdfSieve sv{h->sieve.buf.as<uint64_t>(), h->sieve.words - 1};
         h->last_sieve_in_lds = in_lds;
 #define SV_LAUNCH(L, S) hipLaunchKernelGGL((kdf_sieve_count_kernel<KW, L, S>), dim3(grid), dim3(KB_THREADS), 0, h->stream, \
                                            d_packed, d_invalid, n_tiles, n_bases, h->k, h->t, h->ctl, sv, spw, hits)
@@ -1370,7 +1358,7 @@ static void launch_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t
 // that, and no sieve (the binned path) once even that passes 16 MB.  Up to 64 K keys it is shrunk to the 64 KB that the
 // kernel copies into LDS (no L2 request per window at all: ~700 Gk-mer/s for the filters of VCF mode and Module 3).
 static int sieve_prepare(kdf_engine *h, uint64_t n) {
-    h->sieve_valid = false;
+    h->sieve.valid = false;
     uint64_t bpk = h->opt_sieve_bits ? (uint64_t)h->opt_sieve_bits : 32;
     if (!h->opt_sieve_bits) {
         while (bpk > 8 && n * bpk > (16ull << 20)) bpk >>= 1;
@@ -1379,31 +1367,26 @@ static int sieve_prepare(kdf_engine *h, uint64_t n) {
     if (!(h->opt_sieve_bits || n * bpk <= (128ull << 20))) return KDF_OK;
     const uint64_t bits = n * bpk;
     const uint64_t words = std::max<uint64_t>(1024, 1ull << log2ceil((bits + 63) / 64));
-    if (h->sieve_alloc < words) {
-        if (h->sieve) (void)hipFree(h->sieve);
-        h->sieve = nullptr; h->sieve_alloc = 0;
-        HIPCHK(h, hipMalloc((void **)&h->sieve, words * 8));
-        h->sieve_alloc = words;
-    }
-    h->sieve_words = words;
-    HIPCHK(h, hipMemsetAsync(h->sieve, 0, words * 8, h->stream));
-    h->sieve_valid = true;
+    if (const int rc = eng_reserve(h, h->sieve.buf, words * 8, slack_exact)) return rc;
+    h->sieve.words = words;
+    HIPCHK(h, hipMemsetAsync(h->sieve.buf.p, 0, words * 8, h->stream));
+    h->sieve.valid = true;
     return KDF_OK;
 }
 
 // long engines, option "long_sieve": the sieve over the keys the table holds now (kdf_long_sieve_from_table_kernel)
 // unless there is one; sieve_valid tells whether the keys fit one (sieve_prepare)
 static int long_sieve_ensure(kdf_engine *h) {
-    if (h->sieve_valid || h->sieve_unfit) return KDF_OK;          // (unfit: the direct kernels, without a host round trip per call)
+    if (h->sieve.valid || h->sieve.unfit) return KDF_OK;          // (unfit: the direct kernels, without a host round trip per call)
     int rc;
     if ((rc = ctl_sync(h, nullptr))) return rc;
     if ((rc = sieve_prepare(h, h->distinct))) return rc;
-    if (!h->sieve_valid) { h->sieve_unfit = true; return KDF_OK; }
+    if (!h->sieve.valid) { h->sieve.unfit = true; return KDF_OK; }
     by_words(h, [&](auto Wc) {
         constexpr int W = decltype(Wc)::value;
         if constexpr (W > 2)
             hipLaunchKernelGGL(kdf_long_sieve_from_table_kernel<W>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, h->stream,
-                               h->t, h->sieve, h->sieve_words - 1);
+                               h->t, h->sieve.buf.as<uint64_t>(), h->sieve.words - 1);
         return 0;
     });
     HIPCHK(h, hipGetLastError());
@@ -1419,13 +1402,13 @@ static int long_sieve_ensure(kdf_engine *h) {
 static void launch_long_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d_invalid, uint64_t n_tiles, uint64_t n_bases,
                               uint64_t *hits, bool in_lds) {
     EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
-    KdfSieve sv{h->sieve, h->sieve_words - 1};
+    KdfSieve sv{h->sieve.buf.as<uint64_t>(), h->sieve.words - 1};
     h->last_sieve_in_lds = in_lds;
     h->last_sieve_rounds = 1;
 #define LSV_LAUNCH(L, S, grid, threads, lds, p, m, nt, nb, rounds, hw) \
     hipLaunchKernelGGL((kdf_long_sieve_kernel<W, L, S>), dim3(grid), dim3(threads), lds, h->stream, p, m, nt, nb, h->k, h->t, h->ctl, sv, rounds, hw)
     if (in_lds) {
-        const size_t lds = (size_t)h->sieve_words * 8;
+        const size_t lds = (size_t)h->sieve.words * 8;
         by_words(h, [&](auto Wc) {
             constexpr int W = decltype(Wc)::value;
             if constexpr (W > 2) {
@@ -1463,29 +1446,24 @@ static void launch_long_sieve(kdf_engine *h, const uint64_t *d_packed, const uin
 // The sieve over the keys the table holds now, unless there is one; bsv_valid tells whether the sizing rule took them
 // (as long_sieve_ensure does for the other sieve: one host round trip per build, none per call).
 static int bin_sieve_ensure(kdf_engine *h) {
-    if (h->bsv_valid || h->bsv_unfit) return KDF_OK;
+    if (h->bsv.valid || h->bsv.unfit) return KDF_OK;
     int rc;
     if ((rc = ctl_sync(h, nullptr))) return rc;
     uint32_t c1 = 0, sw = 0, bpk = 0;
-    if (kdf_bs_geometry(h->distinct, h->kw, h->opt_sieve_bits, h->opt_sieve_bins, &c1, &sw, &bpk)) { h->bsv_unfit = true; return KDF_OK; }
+    if (kdf_bs_geometry(h->distinct, h->kw, h->opt_sieve_bits, h->opt_sieve_bins, &c1, &sw, &bpk)) { h->bsv.unfit = true; return KDF_OK; }
     const uint64_t words = (uint64_t)sw << c1;
-    if (h->bsv_alloc < words) {
-        if (h->bsv) { HIPCHK(h, hipStreamSynchronize(h->stream)); (void)hipFree(h->bsv); }
-        h->bsv = nullptr; h->bsv_alloc = 0;
-        HIPCHK(h, hipMalloc((void **)&h->bsv, words * 8));
-        h->bsv_alloc = words;
-    }
-    h->bsv_c1 = c1; h->bsv_slice_words = sw;
-    HIPCHK(h, hipMemsetAsync(h->bsv, 0, words * 8, h->stream));
+    if ((rc = eng_reserve(h, h->bsv.buf, words * 8, slack_exact))) return rc;
+    h->bsv.c1 = c1; h->bsv.slice_words = sw;
+    HIPCHK(h, hipMemsetAsync(h->bsv.buf.p, 0, words * 8, h->stream));
     KbPlan plan{};
     plan.c1 = c1;
     by_width(h, [&](auto KWc) {
         hipLaunchKernelGGL(kdf_bs_from_table_kernel<decltype(KWc)::value>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0, h->stream,
-                           h->t, plan, h->bsv, sw);
+                           h->t, plan, h->bsv.buf.as<uint64_t>(), sw);
         return 0;
     });
     HIPCHK(h, hipGetLastError());
-    h->bsv_valid = true;
+    h->bsv.valid = true;
     return KDF_OK;
 }
 
@@ -1499,25 +1477,25 @@ static int bin_sieve_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_
     if (n_tiles == 0) return KDF_OK;
     int rc;
     KbPlan plan{};
-    plan.c1 = h->bsv_c1; plan.c2 = 0; plan.key_parts = 0;
+    plan.c1 = h->bsv.c1; plan.c2 = 0; plan.key_parts = 0;
     plan.log2cap = h->t.log2cap; plan.bucket_bits = h->t.bucket_bits; plan.off_stride = 2; plan.group = 1;
     const uint32_t nbins = 1u << plan.c1;
     const uint64_t n_slabs = (n_tiles + TILES_PER_SLAB - 1) / TILES_PER_SLAB;
     if (n_slabs >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "bin sieve pass: too many positions for one pass");
     plan.n_slabs = (uint32_t)n_slabs; plan.n_groups = (uint32_t)n_slabs;
     if ((rc = kb_ensure_attrs<KW>(h))) return rc;
-    const size_t lds_bin = (size_t)h->bsv_slice_words * 8 + KDF_BS_LDS_OTHER(KW);
-    if (!h->bsv_attr_set[KW]) {
+    const size_t lds_bin = (size_t)h->bsv.slice_words * 8 + KDF_BS_LDS_OTHER(KW);
+    if (!h->bsv.attr_set[KW]) {
         HIPCHK(h, hipFuncSetAttribute((const void *)kdf_bin_sieve_kernel<KW>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)((size_t)kdf_bs_cap_words() * 8 + KDF_BS_LDS_OTHER(KW))));
-        h->bsv_attr_set[KW] = true;
+        h->bsv.attr_set[KW] = true;
     }
-    if ((rc = eng_reserve(h, h->kb_buf[1], n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
-    if ((rc = eng_reserve(h, h->kb_buf[4], n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
-    if ((rc = eng_reserve(h, h->kb_buf[7], n_slabs * (uint64_t)nbins * 4, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.tmp, n_slabs * (uint64_t)SLAB * 8 * KW, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.off_rows, n_slabs * (uint64_t)(nbins + 1) * 2 + 64, slack_16th))) return rc;
+    if ((rc = eng_reserve(h, h->kb.bin_runs, n_slabs * (uint64_t)nbins * 4, slack_16th))) return rc;
     KbScratch s;
     if ((rc = kb_scratch(h, s))) return rc;
-    uint32_t *runs = (uint32_t *)h->kb_buf[7].p;
+    uint32_t *runs = h->kb.bin_runs.as<uint32_t>();
 
     StageStamps st(h->prof, h->stream);
     EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
@@ -1535,7 +1513,7 @@ static int bin_sieve_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_
     const uint32_t slabs_per_share = (uint32_t)((n_slabs + shares0 - 1) / shares0);
     const uint32_t shares = (uint32_t)((n_slabs + slabs_per_share - 1) / slabs_per_share);
     hipLaunchKernelGGL(kdf_bin_sieve_kernel<KW>, dim3(nbins * shares), dim3(KDF_BS_THREADS), lds_bin, h->stream,
-                       (const uint64_t *)s.tmp, (const uint32_t *)runs, (const uint64_t *)h->bsv, h->bsv_slice_words, (uint32_t)n_slabs,
+                       (const uint64_t *)s.tmp, (const uint32_t *)runs, h->bsv.buf.as<const uint64_t>(), h->bsv.slice_words, (uint32_t)n_slabs,
                        shares, slabs_per_share, h->t, h->ctl);
     st.stamp();                                                  // end of the bin kernel
     HIPCHK(h, hipGetLastError());
@@ -1556,7 +1534,7 @@ static int count_bin_sieve(kdf_engine *h, const uint64_t *d_packed, const uint64
         if ((rc = by_width(h, [&](auto KWc) { return bin_sieve_pass<decltype(KWc)::value>(h, p, m, len, n_bases - off); }))) return rc;
     }
     h->last_path = 5;
-    h->last_sieve_bins = h->bsv_c1; h->last_sieve_slice_words = h->bsv_slice_words;
+    h->last_sieve_bins = h->bsv.c1; h->last_sieve_slice_words = h->bsv.slice_words;
     return KDF_OK;
 }
 
@@ -1568,22 +1546,22 @@ static int count_filtered_dev(kdf_engine *h, const uint64_t *d_packed, const uin
     if (h->opt_sieve_bins && h->opt_force_path == 0 && !h->opt_hash_shift && !is_long(h)) {
         int rc = bin_sieve_ensure(h);                              // (the option was set, or keys were added, after the filter was loaded)
         if (rc) return rc;
-        if (h->bsv_valid) return count_bin_sieve(h, d_packed, d_invalid, n_bases);
+        if (h->bsv.valid) return count_bin_sieve(h, d_packed, d_invalid, n_bases);
     }
     if (is_long(h)) {
         if (h->opt_long_sieve && h->opt_force_path != 1) {
             int rc = long_sieve_ensure(h);                         // (the option was set, or keys were added, after the filter was loaded)
             if (rc) return rc;
-            if (h->sieve_valid) {
-                launch_long_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+            if (h->sieve.valid) {
+                launch_long_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve.words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
                 HIPCHK(h, hipGetLastError());
                 h->last_path = 3;
                 return KDF_OK;
             }
         }
-    } else if (h->sieve_valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
+    } else if (h->sieve.valid && (h->opt_force_path == 0 || h->opt_force_path == 4)) {
         EvSpan span(h->timer[T_STREAM], h->prof, h->stream, n_tiles);
-        launch_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+        launch_sieve(h, d_packed, d_invalid, n_tiles, n_bases, nullptr, h->sieve.words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
         span.stop();
         HIPCHK(h, hipGetLastError());
         h->last_path = 3;
@@ -1672,7 +1650,7 @@ static int src_host(HostCall &c, const uint64_t *packed, const uint64_t *invalid
 
 // behind the consumer's last launch: the slot's next upload waits for this reader
 void src_release(kdf_engine *h, const StreamSrc &src) {
-    if (src.slot >= 0) (void)hipEventRecord(h->use_done[src.slot], h->stream);
+    if (src.slot >= 0) (void)hipEventRecord(h->up.slot[src.slot].use_done, h->stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -1697,21 +1675,15 @@ static int pf_merge_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, ui
     const uint64_t n_pairs = (n_words - head) / 2;
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_pairs + 255) / 256, (uint64_t)h->n_cu * 8));
     EvSpan span(h->timer[T_PFM], h->prof, h->stream);
-    if (replace) hipLaunchKernelGGL(kdf_pf_merge_kernel<true>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
-    else hipLaunchKernelGGL(kdf_pf_merge_kernel<false>, dim3(grid), dim3(256), 0, h->stream, h->pf.words + first_word, sg, n_words, head, n_pairs);
+    if (replace) hipLaunchKernelGGL(kdf_pf_merge_kernel<true>, dim3(grid), dim3(256), 0, h->stream, h->pf.view.words + first_word, sg, n_words, head, n_pairs);
+    else hipLaunchKernelGGL(kdf_pf_merge_kernel<false>, dim3(grid), dim3(256), 0, h->stream, h->pf.view.words + first_word, sg, n_words, head, n_pairs);
     span.stop();
     HIPCHK(h, hipGetLastError());
-    h->stat_pf_merged_words += n_words;
+    h->pf.merged_words += n_words;
     return KDF_OK;
 }
 
-static void pf_free(kdf_engine *h) {
-    if (h->pf.words) (void)hipFree(h->pf.words);
-    if (h->pf_ctr) (void)hipFree(h->pf_ctr);
-    if (h->pf_admit) (void)hipFree(h->pf_admit);
-    h->pf = KdfPrefilter{}; h->pf_ctr = nullptr; h->pf_admit = nullptr; h->pf_admit_words = 0;
-    h->pf_state = PF_OFF;
-}
+static void pf_free(kdf_engine *h) { h->pf = PfState{}; }
 
 // ---------------------------------------------------------------------------
 // distinct k-mer sketch (kdf_sketch.h)
@@ -1722,36 +1694,30 @@ static int sk_add_dev(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
     launch_tiles(h, d_packed, d_invalid, kdf_stream_geom(n_bases).tiles, n_bases, nullptr,
                  [&](auto Wc, unsigned blocks, const uint64_t *p, const uint64_t *m, uint64_t nt, uint64_t nb, uint64_t *) {
         constexpr int W = decltype(Wc)::value;
-        if constexpr (W <= 2) hipLaunchKernelGGL((kdf_sk_stream_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk, h->sk_ctr);
-        else hipLaunchKernelGGL((kdf_sk_long_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk, h->sk_ctr);
+        if constexpr (W <= 2) hipLaunchKernelGGL((kdf_sk_stream_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk.view, h->sk.ctr.as<unsigned long long>());
+        else hipLaunchKernelGGL((kdf_sk_long_kernel<W>), dim3(blocks), dim3(256), 0, h->stream, p, m, nt, nb, h->k, h->sk.view, h->sk.ctr.as<unsigned long long>());
     });
     span.stop();
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
 
-static void sk_free(kdf_engine *h) {
-    if (h->sk.cells) (void)hipFree(h->sk.cells);
-    if (h->sk_bytes) (void)hipFree(h->sk_bytes);
-    if (h->sk_ctr) (void)hipFree(h->sk_ctr);
-    h->sk = KdfSketch{}; h->sk_bytes = nullptr; h->sk_ctr = nullptr;
-    h->sk_on = false;
-}
+static void sk_free(kdf_engine *h) { h->sk = SkState{}; }
 
 // the registers as bytes in `d_out` (device), in stream order
 static int sk_pack(kdf_engine *h, uint8_t *d_out) {
-    const uint32_t m = 1u << h->sk.p;
-    hipLaunchKernelGGL(kdf_sk_pack_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.cells, m, d_out);
+    const uint32_t m = 1u << h->sk.view.p;
+    hipLaunchKernelGGL(kdf_sk_pack_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.view.cells, m, d_out);
     HIPCHK(h, hipGetLastError());
     return KDF_OK;
 }
 
 #define SK_NEED_ON(h, fn) \
-    do { if (!(h)->sk_on) return fail(h, KDF_ERR_STATE, "%s: no sketch is on (kdf_sketch_begin)", fn); } while (0)
+    do { if (!(h)->sk.on) return fail(h, KDF_ERR_STATE, "%s: no sketch is on (kdf_sketch_begin)", fn); } while (0)
 
 #define PF_NEED_TALLYING(h, fn) \
-    do { if ((h)->pf_state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
-                                                       fn, (h)->pf_state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
+    do { if ((h)->pf.state != PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; reads are tallied between kdf_prefilter_begin and kdf_prefilter_arm", \
+                                                       fn, (h)->pf.state == PF_ARMED ? "armed (its sieve is immutable)" : "off"); } while (0)
 
 // n keys of a host form: the item of lo (or of the rows of long keys); the next one is hi (k 33..63, else empty)
 static int keys_in(HostCall &c, const uint64_t *lo, const uint64_t *hi, uint64_t n) {
@@ -1790,46 +1756,33 @@ int kdf_create(int device, int k, uint64_t capacity_hint, kdf_engine **out) {
     { size_t f = 0, tt = 0; if (hipMemGetInfo(&f, &tt) == hipSuccess) h->dev_total_bytes = tt; else (void)hipGetLastError(); }
     if ((e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     h->stream = h->own_stream;
-    if ((e = hipMalloc((void **)&h->ctl, sizeof(KdfCtl))) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_NOMEM); }
-    if ((e = hipMalloc((void **)&h->d_out4, 32)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_NOMEM); }
-    if ((e = hipHostMalloc((void **)&h->h_out4, 32)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_NOMEM); }
+    if ((e = h->ctl_mem.alloc(sizeof(KdfCtl))) != hipSuccess || (e = h->out4_mem.alloc(32)) != hipSuccess || (e = h->out4_pin.alloc(32)) != hipSuccess) {
+        h->err = hipGetErrorString(e); return bail(KDF_ERR_NOMEM);
+    }
+    h->ctl = h->ctl_mem.as<KdfCtl>(); h->d_out4 = h->out4_mem.as<unsigned long long>(); h->h_out4 = h->out4_pin.as<unsigned long long>();
     int rc = ctl_reset(h, false);
     if (rc) return bail(rc);
     if (const char *ev = getenv("KDF_BIG_BUCKET_LOG2CAP")) { const int v = atoi(ev); if (v >= 10 && v <= 64) h->opt_big_bucket_log2cap = (uint32_t)v; }
-    rc = table_alloc(h, cap_log2_for(capacity_hint), h->t);
+    NewTable nt;
+    rc = table_alloc(h, cap_log2_for(capacity_hint), nt);
     if (rc) return bail(rc);
-    h->cap = 1ull << h->t.log2cap;
+    table_adopt(h, nt);
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) { h->err = hipGetErrorString(e); return bail(KDF_ERR_HIP); }
     *out = h;
     return KDF_OK;
 }
 
+// Every buffer of the engine frees itself with it (kdf_devbuf.h), after the streams that may still read it have drained
 void kdf_destroy(kdf_engine *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    table_free(h->t);
+    if (h->up.copy_stream) (void)hipStreamSynchronize(h->up.copy_stream);
     for (EvTimer &t : h->timer) t.collect();
     stage_collect(h);
-    pf_free(h);
-    sk_free(h);
-    for (DevBuf &b : h->buf) b.release();
-    if (h->l1.packed) (void)hipFree(h->l1.packed);
-    if (h->l1.mask) (void)hipFree(h->l1.mask);
-    if (h->kb_pass) (void)hipFree(h->kb_pass);
-    if (h->kb_heavy) (void)hipFree(h->kb_heavy);
-    for (int sl = 0; sl < 2; ++sl) {
-        if (h->up_done[sl]) (void)hipEventDestroy(h->up_done[sl]);
-        if (h->use_done[sl]) (void)hipEventDestroy(h->use_done[sl]);
-    }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->sieve) (void)hipFree(h->sieve);
-    if (h->bsv) (void)hipFree(h->bsv);
-    if (h->kb_small) (void)hipFree(h->kb_small);
-    if (h->kb_totals_host) (void)hipHostFree(h->kb_totals_host);
-    if (h->ctl) (void)hipFree(h->ctl);
-    if (h->d_out4) (void)hipFree(h->d_out4);
-    if (h->h_out4) (void)hipHostFree(h->h_out4);
+    for (UpSlot &sl : h->up.slot)
+        for (hipEvent_t ev : {sl.up_done, sl.use_done}) if (ev) (void)hipEventDestroy(ev);
+    if (h->up.copy_stream) (void)hipStreamDestroy(h->up.copy_stream);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
@@ -1846,7 +1799,7 @@ int kdf_synchronize(kdf_engine *h) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->copy_stream) HIPCHK(h, hipStreamSynchronize(h->copy_stream));      // uploads still in flight read host buffers
+    if (h->up.copy_stream) HIPCHK(h, hipStreamSynchronize(h->up.copy_stream));      // uploads still in flight read host buffers
     return KDF_OK;
 }
 
@@ -1877,7 +1830,7 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
     HIPCHK(h, hipSetDevice(h->device));
     // (passes a dump-only flush has applied: their keys and windows are in the counters already, the table is not needed)
-    if (h->l1.tiles || h->ring.undumped_passes()) { int rcf = pending_flush(h); if (rcf) return rcf; }
+    if (h->kb.l1.tiles || h->kb.ring.undumped_passes()) { int rcf = pending_flush(h); if (rcf) return rcf; }
     bool full = false;
     int rc = ctl_sync(h, &full);
     if (rc) return rc;
@@ -1926,30 +1879,31 @@ int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, cons
     if (slot < 0 || slot > 1) return fail(h, KDF_ERR_INVALID, "kdf_upload_reads_async: slot must be 0 or 1");
     if (n_bases && (!packed || !invalid)) return fail(h, KDF_ERR_INVALID, "kdf_upload_reads_async: NULL stream");
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->copy_stream) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    if (!h->up.copy_stream) {
+        HIPCHK(h, hipStreamCreateWithFlags(&h->up.copy_stream, hipStreamNonBlocking));
         for (int sl = 0; sl < 2; ++sl) {
-            HIPCHK(h, hipEventCreateWithFlags(&h->up_done[sl], hipEventDisableTiming));
-            HIPCHK(h, hipEventCreateWithFlags(&h->use_done[sl], hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->up.slot[sl].up_done, hipEventDisableTiming));
+            HIPCHK(h, hipEventCreateWithFlags(&h->up.slot[sl].use_done, hipEventDisableTiming));
         }
     }
     uint64_t pw, mw;
     kdf_stream_words(n_bases, &pw, &mw);
-    const size_t want[2] = {(size_t)pw * 8, (size_t)mw * 8};
     auto both_streams = [&] {                                  // (the slot's last count may still read the old buffer)
         const hipError_t e = hipStreamSynchronize(h->stream);
-        return e != hipSuccess ? e : hipStreamSynchronize(h->copy_stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(h->up.copy_stream);
     };
-    for (int j = 0; j < 2; ++j) HIPCHK(h, dev_reserve(h->up_buf[slot][j], want[j], slack_8th(want[j]), both_streams));
-    h->up_valid[slot] = false;
-    h->up_n[slot] = n_bases;
-    if (n_bases == 0) { h->up_valid[slot] = true; return KDF_OK; }
-    hipStream_t cs = h->copy_stream;
-    if (h->use_done[slot]) HIPCHK(h, hipStreamWaitEvent(cs, h->use_done[slot], 0));   // the count that last read this slot
-    int rc = upload_padded(h, packed, invalid, n_bases, (uint64_t *)h->up_buf[slot][0].p, (uint64_t *)h->up_buf[slot][1].p, cs);
+    UpSlot &up = h->up.slot[slot];
+    HIPCHK(h, dev_reserve(up.packed, (size_t)pw * 8, slack_8th((size_t)pw * 8), both_streams));
+    HIPCHK(h, dev_reserve(up.mask, (size_t)mw * 8, slack_8th((size_t)mw * 8), both_streams));
+    h->up.slot[slot].valid = false;
+    h->up.slot[slot].n_bases = n_bases;
+    if (n_bases == 0) { h->up.slot[slot].valid = true; return KDF_OK; }
+    hipStream_t cs = h->up.copy_stream;
+    if (h->up.slot[slot].use_done) HIPCHK(h, hipStreamWaitEvent(cs, h->up.slot[slot].use_done, 0));   // the count that last read this slot
+    int rc = upload_padded(h, packed, invalid, n_bases, up.packed.as<uint64_t>(), up.mask.as<uint64_t>(), cs);
     if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->up_done[slot], cs));
-    h->up_valid[slot] = true;
+    HIPCHK(h, hipEventRecord(h->up.slot[slot].up_done, cs));
+    h->up.slot[slot].valid = true;
     return KDF_OK;
 }
 
@@ -1960,9 +1914,9 @@ int kdf_count_uploaded(kdf_engine *h, int slot, int filtered) {
     int rc = src_slot(EngSink{h}, "kdf_count_uploaded", h, slot, true, true, src, [&](const StreamSrc &b) {
         if (!filtered && h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: a filter is loaded; call kdf_clear first");
         if (filtered && !h->filter_mode) return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: no filter loaded (kdf_load_filter)");
-        if (filtered && b.n_bases && h->opt_force_path == 4 && !h->sieve_valid)      // (an empty batch asks nothing of the sieve: kdf_count_reads_filtered*)
+        if (filtered && b.n_bases && h->opt_force_path == 4 && !h->sieve.valid)      // (an empty batch asks nothing of the sieve: kdf_count_reads_filtered*)
             return fail(h, KDF_ERR_STATE, "kdf_count_uploaded: force_path 4 (sieve): no sieve for this filter (keys were added after kdf_load_filter)");
-        if (!filtered && h->pf_state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
+        if (!filtered && h->pf.state == PF_TALLYING) return fail(h, KDF_ERR_STATE, "%s", PF_TALLYING_MSG);
         return (int)KDF_OK;
     });
     if (rc || !src.n_bases) return rc;
@@ -1994,9 +1948,10 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
     const uint32_t want = cap_log2_for(n);
     if (want != h->t.log2cap) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        table_free(h->t);
-        if ((rc = table_alloc(h, want, h->t))) return rc;
-        h->cap = 1ull << want;
+        h->t_mem = TableMem{}; h->t = KdfTable{};      // (freed first: the old and the new table need not fit side by side)
+        NewTable nt;
+        if ((rc = table_alloc(h, want, nt))) return rc;
+        table_adopt(h, nt);
         if ((rc = ctl_reset(h, false))) return rc;
         h->distinct = 0; h->windows = 0; h->lazy_empty = false; h->filter_mode = false;
     } else if ((rc = kdf_clear(h))) return rc;
@@ -2012,10 +1967,10 @@ static int load_filter_core(kdf_engine *h, const uint64_t *d_lo, const uint64_t 
     }
     if (is_long(h)) return h->opt_long_sieve ? long_sieve_ensure(h) : KDF_OK;     // (long keys: from the table just loaded, and only when asked to)
     if ((rc = sieve_prepare(h, n)) != KDF_OK) return rc;
-    if (h->sieve_valid && n) {
+    if (h->sieve.valid && n) {
         by_width(h, [&](auto KWc) {
             hipLaunchKernelGGL(kdf_sieve_build_kernel<decltype(KWc)::value>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                               d_lo, d_hi, n, h->sieve, h->sieve_words - 1);
+                               d_lo, d_hi, n, h->sieve.buf.as<uint64_t>(), h->sieve.words - 1);
             return 0;
         });
         HIPCHK(h, hipGetLastError());
@@ -2079,7 +2034,7 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
         if ((rc = materialize(h))) return rc;
         for (uint32_t s = 0; s < nseg; ++s)
             if (n[s]) insert_keys(h, h->t, d_lo[s], d_hi[s], d_cnt[s], n[s], false);
-        h->last_merge_path = 2;
+        h->merge.last_path = 2;
     } else {
         KmSegs sg{};
         uint32_t m = 0;
@@ -2090,13 +2045,13 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
         sg.nseg = m;
         const uint32_t nb = (uint32_t)(h->cap >> h->t.bucket_bits);
         const size_t words = (size_t)m * nb * 2 + 16;
-        if ((rc = eng_reserve(h, *h->merge_buf, words * 4, slack_exact))) return rc;
-        uint32_t *first = (uint32_t *)h->merge_buf->p, *last = first + (size_t)m * nb, *flag = last + (size_t)m * nb;
-        HIPCHK(h, hipMemsetAsync(h->merge_buf->p, 0, words * 4, h->stream));
+        if ((rc = eng_reserve(h, h->merge.scratch, words * 4, slack_exact))) return rc;
+        uint32_t *first = h->merge.scratch.as<uint32_t>(), *last = first + (size_t)m * nb, *flag = last + (size_t)m * nb;
+        HIPCHK(h, hipMemsetAsync(h->merge.scratch.p, 0, words * 4, h->stream));
         const dim3 pg((unsigned)((nmax + 255) / 256), m);
         const size_t lds_bytes = ((size_t)8 * h->kw + 4) << h->t.bucket_bits;
         const bool fresh = h->lazy_empty;            // the kernel writes every bucket: it IS the deferred clear
-        if (lds_bytes > 65536 && !h->merge_attrs_set[h->kw]) {       // big buckets: past the default limit of dynamic LDS
+        if (lds_bytes > 65536 && !h->merge.attrs_set[h->kw]) {       // big buckets: past the default limit of dynamic LDS
             int rca = by_width(h, [&](auto KWc) {
                 constexpr int KW = decltype(KWc)::value;
                 HIPCHK(h, hipFuncSetAttribute((const void *)(km_merge_kernel<KW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -2104,7 +2059,7 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
                 return KDF_OK;
             });
             if (rca) return rca;
-            h->merge_attrs_set[h->kw] = true;
+            h->merge.attrs_set[h->kw] = true;
         }
         by_width(h, [&](auto KWc) {
             constexpr int KW = decltype(KWc)::value;
@@ -2115,13 +2070,13 @@ static int add_pairs_multi(kdf_engine *h, uint32_t nseg, const uint64_t *const *
             return 0;
         });
         h->lazy_empty = false;
-        h->last_merge_path = 1;
-        HIPCHK(h, hipMemcpyAsync(&h->merge_flag_host, flag, 4, hipMemcpyDeviceToHost, h->stream));
+        h->merge.last_path = 1;
+        HIPCHK(h, hipMemcpyAsync(&h->merge.flag_host, flag, 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipGetLastError());
     bool full = false;
     if ((rc = ctl_sync(h, &full))) return rc;
-    if (h->last_merge_path == 1 && h->merge_flag_host) h->last_merge_path = 2;     // a segment was not grouped: the atomic kernel did the work
+    if (h->merge.last_path == 1 && h->merge.flag_host) h->merge.last_path = 2;     // a segment was not grouped: the atomic kernel did the work
     if ((rc = long_bad_keys(h, fn))) return rc;
     if (full) return fail(h, KDF_ERR_TABLE_FULL, "%s: bucket overflow", fn);
     return KDF_OK;
@@ -2259,7 +2214,7 @@ static int export_pass(kdf_engine *h, uint32_t min_count, bool write, uint64_t *
                        uint32_t *ocnt, uint64_t out_cap, uint64_t *n_out) {
     // passes pending: the flush that applies them holds every bucket of the table in LDS once -- it writes the dump too
     // (kb_bucket_kernel, KbPlan::dump_min) unless a bucket took another way (overflow replay, heavy-bucket split)
-    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->ring.undumped_passes() || h->l1.tiles > 0);
+    const bool fuse = write && min_count >= 1 && h->opt_fused_dump && !h->filter_mode && olo && (h->kw == 1 || ohi) && (h->kb.ring.undumped_passes() || h->kb.l1.tiles > 0);
     KbDump dump{min_count, olo, ohi, ocnt, out_cap};
     { int rcf = pending_flush(h, fuse ? &dump : nullptr); if (rcf) return rcf; }
     if (dump.done) { *n_out = dump.n; return KDF_OK; }
@@ -2309,9 +2264,9 @@ static int export_parts(kdf_engine *h, uint32_t min_count, uint32_t parts, bool 
         return fail(h, KDF_ERR_STATE, "%s: no owner-ordered dump for buckets of 2^%u slots", who, h->t.bucket_bits);
     // scratch: blk_off u64[nblk + 1] | part_first u64[S] | part_off u64[S + 1] | part_base u64[S + 1] | blk_cnt u32[nblk]
     const size_t off_words = nblk + 1 + KDF_SHARDS + 2 * (KDF_SHARDS + 1);
-    int rc = eng_reserve(h, *h->merge_buf, off_words * 8 + nblk * 4, slack_exact);
+    int rc = eng_reserve(h, h->merge.scratch, off_words * 8 + nblk * 4, slack_exact);
     if (rc) return rc;
-    unsigned long long *blk_off = (unsigned long long *)h->merge_buf->p;
+    unsigned long long *blk_off = h->merge.scratch.as<unsigned long long>();
     uint64_t *part_first = (uint64_t *)(blk_off + nblk + 1);
     unsigned long long *part_off = (unsigned long long *)(part_first + KDF_SHARDS);
     unsigned long long *part_base = part_off + KDF_SHARDS + 1;
@@ -2509,10 +2464,10 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
         // long keys (option "long_sieve"): survivors probe in place and the tile's hit word is stored whole -- any stream length
         int rc = long_sieve_ensure(h);
         if (rc) return rc;
-        if (h->sieve_valid) {
+        if (h->sieve.valid) {
             h->last_scan_path = 3;
             launch_long_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, n_bases, (uint64_t *)d_hit_bits,
-                              h->sieve_words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
+                              h->sieve.words <= KDF_SV_LDS_WORDS && !(h->opt_debug_flags & 2048));
             HIPCHK(h, hipGetLastError());
             return KDF_OK;
         }
@@ -2520,23 +2475,23 @@ int kdf_scan_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invali
     if (!is_long(h) && h->opt_force_path != 1 && n_tiles * KDF_TILE < (1ull << 32)) {
         // through the membership sieve (section 3.5 of DESIGN.md): an index that was loaded with kdf_add_pairs has none yet
         int rc;
-        if (!h->sieve_valid) {
+        if (!h->sieve.valid) {
             if ((rc = ctl_sync(h, nullptr))) return rc;
             if ((rc = sieve_prepare(h, h->distinct))) return rc;
-            if (h->sieve_valid) {
+            if (h->sieve.valid) {
                 by_width(h, [&](auto KWc) {
                     hipLaunchKernelGGL(kdf_sieve_from_table_kernel<decltype(KWc)::value>, dim3((unsigned)((h->cap + 255) / 256)), dim3(256), 0,
-                                       h->stream, h->t, h->sieve, h->sieve_words - 1);
+                                       h->stream, h->t, h->sieve.buf.as<uint64_t>(), h->sieve.words - 1);
                     return 0;
                 });
                 HIPCHK(h, hipGetLastError());
             }
         }
-        if (h->sieve_valid) {
+        if (h->sieve.valid) {
             HIPCHK(h, hipMemsetAsync(d_hit_bits, 0, n_tiles * 8, h->stream));
             h->last_scan_path = 3;
             launch_sieve(h, (const uint64_t *)d_packed, (const uint64_t *)d_invalid, n_tiles, n_bases, (unsigned long long *)d_hit_bits,
-                         h->sieve_words <= KDF_SV_LDS_WORDS);
+                         h->sieve.words <= KDF_SV_LDS_WORDS);
             HIPCHK(h, hipGetLastError());
             return KDF_OK;
         }
@@ -2617,8 +2572,8 @@ int kdf_scan_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invali
 
 int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->pf_state != PF_OFF)
-        return fail(h, KDF_ERR_STATE, "kdf_prefilter_begin: a prefilter is already %s; kdf_prefilter_drop first", h->pf_state == PF_ARMED ? "armed" : "tallying");
+    if (h->pf.state != PF_OFF)
+        return fail(h, KDF_ERR_STATE, "kdf_prefilter_begin: a prefilter is already %s; kdf_prefilter_drop first", h->pf.state == PF_ARMED ? "armed" : "tallying");
     if (min_count != 2 && min_count != 3)
         return fail(h, KDF_ERR_INVALID, "kdf_prefilter_begin: min_count %u: must be 2 or 3 (1 is the plain count; a cell saturates at 3: for a dump "
                                         "with -L above 3 ask for 3 and dump with the larger bound)", min_count);
@@ -2630,20 +2585,18 @@ int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells) 
     { int rcf = pending_flush(h); if (rcf) return rcf; }
     if (log2_cells == 0) log2_cells = std::min<uint32_t>(KDF_PF_MAX_LOG2, std::max<uint32_t>(KDF_PF_MIN_LOG2, log2ceil(8 * std::max<uint64_t>(h->capacity_hint, 1))));
     const uint64_t bytes = 1ull << (log2_cells - 1);              // half a byte per cell
-    unsigned long long *words = nullptr, *ctr = nullptr;
-    hipError_t e = hipMalloc((void **)&words, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&ctr, (KDF_SHARDS * 16 + 4) * 8);
+    hipError_t e = h->pf.words.alloc(bytes);
+    if (e == hipSuccess) e = h->pf.ctr.alloc((KDF_SHARDS * 16 + 4) * 8);
     if (e != hipSuccess) {
-        if (words) (void)hipFree(words);
-        (void)hipGetLastError();
+        pf_free(h);
         return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "kdf_prefilter_begin: a sieve of 2^%u cells (%.1f GB) does not fit the device (%s)",
                     log2_cells, (double)bytes / 1e9, hipGetErrorString(e));
     }
-    h->pf.words = words; h->pf.log2_cells = log2_cells; h->pf.min_count = min_count; h->pf_ctr = ctr;
-    HIPCHK(h, hipMemsetAsync(words, 0, bytes, h->stream));
-    HIPCHK(h, hipMemsetAsync(ctr, 0, (KDF_SHARDS * 16 + 4) * 8, h->stream));
-    h->pf_state = PF_TALLYING;
-    h->stat_pf_merged_words = 0;
+    h->pf.view.words = h->pf.words.as<unsigned long long>(); h->pf.view.log2_cells = log2_cells; h->pf.view.min_count = min_count;
+    HIPCHK(h, hipMemsetAsync(h->pf.words.p, 0, bytes, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->pf.ctr.p, 0, (KDF_SHARDS * 16 + 4) * 8, h->stream));
+    h->pf.state = PF_TALLYING;
+    h->pf.merged_words = 0;
     return KDF_OK;
 }
 
@@ -2677,15 +2630,15 @@ int kdf_prefilter_add_uploaded(kdf_engine *h, int slot) {
 
 int kdf_prefilter_arm(kdf_engine *h) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->pf_state != PF_TALLYING)
-        return fail(h, KDF_ERR_STATE, "kdf_prefilter_arm: the prefilter is %s; only a tallying prefilter (kdf_prefilter_begin) is armed", h->pf_state == PF_ARMED ? "armed already" : "off");
-    h->pf_state = PF_ARMED;
+    if (h->pf.state != PF_TALLYING)
+        return fail(h, KDF_ERR_STATE, "kdf_prefilter_arm: the prefilter is %s; only a tallying prefilter (kdf_prefilter_begin) is armed", h->pf.state == PF_ARMED ? "armed already" : "off");
+    h->pf.state = PF_ARMED;
     return KDF_OK;
 }
 
 int kdf_prefilter_drop(kdf_engine *h) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_drop: no prefilter (kdf_prefilter_begin)");
+    if (h->pf.state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_drop: no prefilter (kdf_prefilter_begin)");
     HIPCHK(h, hipSetDevice(h->device));
     { int rcf = pending_flush(h); if (rcf) return rcf; }           // what is pending was admitted under this sieve
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2695,18 +2648,18 @@ int kdf_prefilter_drop(kdf_engine *h) {
 
 int kdf_prefilter_fill(kdf_engine *h, uint64_t cells_by_value[4]) {
     if (!h || !cells_by_value) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_fill: NULL pointer");
-    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_fill: no prefilter (kdf_prefilter_begin)");
+    if (h->pf.state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_fill: no prefilter (kdf_prefilter_begin)");
     HIPCHK(h, hipSetDevice(h->device));
-    unsigned long long *out3 = h->pf_ctr + KDF_SHARDS * 16;
-    const uint64_t n_words = 1ull << (h->pf.log2_cells - 4);
+    unsigned long long *out3 = h->pf.ctr.as<unsigned long long>() + KDF_SHARDS * 16;
+    const uint64_t n_words = 1ull << (h->pf.view.log2_cells - 4);
     HIPCHK(h, hipMemsetAsync(out3, 0, 3 * 8, h->stream));
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_words + 1023) / 1024, (uint64_t)h->n_cu * 8));
-    hipLaunchKernelGGL(kdf_pf_fill_kernel, dim3(grid), dim3(256), 0, h->stream, h->pf.words, n_words, out3);
+    hipLaunchKernelGGL(kdf_pf_fill_kernel, dim3(grid), dim3(256), 0, h->stream, h->pf.view.words, n_words, out3);
     HIPCHK(h, hipGetLastError());
     unsigned long long ge[3] = {0, 0, 0};
     HIPCHK(h, hipMemcpyAsync(ge, out3, sizeof ge, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    cells_by_value[0] = (1ull << h->pf.log2_cells) - ge[0];
+    cells_by_value[0] = (1ull << h->pf.view.log2_cells) - ge[0];
     cells_by_value[1] = ge[0] - ge[1];
     cells_by_value[2] = ge[1] - ge[2];
     cells_by_value[3] = ge[2];
@@ -2748,7 +2701,7 @@ static int bd_fallback(kdf_engine *h, const char *fn, const uint8_t *d_comp, con
                         (unsigned long long)blk.file_off, status[b], zr);
         HIPCHK(h, hipMemcpyAsync(d_out + blk.out_off, data.data(), blk.isize, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));                  // (data is reused by the next block)
-        h->stat_bd_fallback++;
+        h->bd.stat_fallback++;
     }
     return KDF_OK;
 }
@@ -2772,15 +2725,15 @@ int kdf_bgzf_inflate_dev(kdf_engine *h, const void *d_comp, const void *d_blocks
     HIPCHK(h, hipSetDevice(h->device));
     uint32_t *d_status = (uint32_t *)d_block_status;
     if (!d_status) {
-        const int rc = eng_reserve(h, h->bd_buf[1], n_blocks * 4);
+        const int rc = eng_reserve(h, h->bd.status, n_blocks * 4);
         if (rc) return rc;
-        d_status = (uint32_t *)h->bd_buf[1].p;
+        d_status = h->bd.status.as<uint32_t>();
     }
     { const int rc = bd_inflate_launch(h, d_comp, d_blocks, n_blocks, d_out, out_cap, d_status); if (rc) return rc; }
     std::vector<uint32_t> status(n_blocks);
     HIPCHK(h, hipMemcpyAsync(status.data(), d_status, n_blocks * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->opt_bd_host_inflate) for (uint32_t &st : status) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
+    if (h->bd.opt_host_inflate) for (uint32_t &st : status) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
     return bd_fallback(h, "kdf_bgzf_inflate_dev", (const uint8_t *)d_comp, (const kdf_bgzf_block *)d_blocks, n_blocks, (uint8_t *)d_out, status.data());
 }
 
@@ -2801,13 +2754,13 @@ int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_block
     const size_t o_sub = (size_t)((n_blocks * 4 + 15) & ~15ull), o_cnt = o_sub + (size_t)((n_sub * 4 + 15) & ~15ull);
     const size_t o_base = o_cnt + (size_t)n_sub * sizeof(KdfBdSubCount), o_tot = o_base + (size_t)n_sub * sizeof(KdfBdSubCount);
     int rc;
-    if ((rc = eng_reserve(h, h->bd_buf[0], (size_t)out_cap + 8))) return rc;
-    if ((rc = eng_reserve(h, h->bd_buf[1], o_tot + 32))) return rc;
-    if ((rc = eng_reserve(h, h->bd_buf[2], (size_t)(cap_reads + 1) * 8))) return rc;
-    uint8_t *d_out = (uint8_t *)h->bd_buf[0].p, *small = (uint8_t *)h->bd_buf[1].p;
+    if ((rc = eng_reserve(h, h->bd.inflated, (size_t)out_cap + 8))) return rc;
+    if ((rc = eng_reserve(h, h->bd.status, o_tot + 32))) return rc;
+    if ((rc = eng_reserve(h, h->bd.read_offs, (size_t)(cap_reads + 1) * 8))) return rc;
+    uint8_t *d_out = h->bd.inflated.as<uint8_t>(), *small = h->bd.status.as<uint8_t>();
     uint32_t *d_bst = (uint32_t *)small, *d_sst = (uint32_t *)(small + o_sub);
     KdfBdSubCount *d_cnt = (KdfBdSubCount *)(small + o_cnt), *d_base = (KdfBdSubCount *)(small + o_base);
-    uint64_t *d_tot = (uint64_t *)(small + o_tot), *d_src = (uint64_t *)h->bd_buf[2].p;
+    uint64_t *d_tot = (uint64_t *)(small + o_tot), *d_src = h->bd.read_offs.as<uint64_t>();
     const kdf_bgzf_block *blocks = (const kdf_bgzf_block *)d_blocks;
     const kdf_bam_subrange *subs = (const kdf_bam_subrange *)d_subranges;
     std::vector<uint32_t> bst(n_blocks);
@@ -2831,7 +2784,7 @@ int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_block
         HIPCHK(h, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         bool flagged = false;
-        if (turn == 0 && h->opt_bd_host_inflate) for (uint32_t &st : bst) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
+        if (turn == 0 && h->bd.opt_host_inflate) for (uint32_t &st : bst) if (st == KDF_INF_OK) st = KDF_INF_FORCED;
         if (turn == 0) for (uint64_t b = 0; b < n_blocks; ++b) flagged |= bst[b] != KDF_INF_OK;
         if (!flagged) break;
         if ((rc = bd_fallback(h, fn, (const uint8_t *)d_comp, blocks, n_blocks, d_out, bst.data()))) return rc;
@@ -2867,26 +2820,23 @@ int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_block
 
 int kdf_sketch_begin(kdf_engine *h, uint32_t log2_registers) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->sk_on) return fail(h, KDF_ERR_STATE, "kdf_sketch_begin: a sketch is already on (2^%u registers); kdf_sketch_drop first", h->sk.p);
+    if (h->sk.on) return fail(h, KDF_ERR_STATE, "kdf_sketch_begin: a sketch is already on (2^%u registers); kdf_sketch_drop first", h->sk.view.p);
     if (log2_registers == 0) log2_registers = KDF_SK_DEFAULT_LOG2;
     if (log2_registers < KDF_SK_MIN_LOG2 || log2_registers > KDF_SK_MAX_LOG2)
         return fail(h, KDF_ERR_INVALID, "kdf_sketch_begin: log2_registers %u: must be %d..%d, or 0 for %d", log2_registers, KDF_SK_MIN_LOG2, KDF_SK_MAX_LOG2, KDF_SK_DEFAULT_LOG2);
     HIPCHK(h, hipSetDevice(h->device));
     const size_t m = (size_t)1 << log2_registers;
-    uint32_t *cells = nullptr; uint8_t *bytes = nullptr; unsigned long long *ctr = nullptr;
-    hipError_t e = hipMalloc((void **)&cells, m * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&bytes, m);
-    if (e == hipSuccess) e = hipMalloc((void **)&ctr, KDF_SHARDS * 16 * 8);
+    hipError_t e = h->sk.cells.alloc(m * 4);
+    if (e == hipSuccess) e = h->sk.bytes.alloc(m);
+    if (e == hipSuccess) e = h->sk.ctr.alloc(KDF_SHARDS * 16 * 8);
     if (e != hipSuccess) {
-        if (cells) (void)hipFree(cells);
-        if (bytes) (void)hipFree(bytes);
-        (void)hipGetLastError();
+        sk_free(h);
         return fail(h, e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "kdf_sketch_begin: 2^%u registers do not fit the device (%s)", log2_registers, hipGetErrorString(e));
     }
-    h->sk.cells = cells; h->sk.p = log2_registers; h->sk_bytes = bytes; h->sk_ctr = ctr;
-    h->sk_on = true;
-    HIPCHK(h, hipMemsetAsync(cells, 0, m * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(ctr, 0, KDF_SHARDS * 16 * 8, h->stream));
+    h->sk.view.cells = h->sk.cells.as<uint32_t>(); h->sk.view.p = log2_registers;
+    h->sk.on = true;
+    HIPCHK(h, hipMemsetAsync(h->sk.cells.p, 0, m * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(h->sk.ctr.p, 0, KDF_SHARDS * 16 * 8, h->stream));
     return KDF_OK;
 }
 
@@ -2931,8 +2881,8 @@ int kdf_sketch_registers(kdf_engine *h, uint8_t *regs_out) {
     if (!h || !regs_out) return fail(h, KDF_ERR_INVALID, "kdf_sketch_registers: NULL pointer");
     SK_NEED_ON(h, "kdf_sketch_registers");
     HIPCHK(h, hipSetDevice(h->device));
-    { int rc = sk_pack(h, h->sk_bytes); if (rc) return rc; }
-    HIPCHK(h, hipMemcpyAsync(regs_out, h->sk_bytes, (size_t)1 << h->sk.p, hipMemcpyDeviceToHost, h->stream));
+    { int rc = sk_pack(h, h->sk.bytes.as<uint8_t>()); if (rc) return rc; }
+    HIPCHK(h, hipMemcpyAsync(regs_out, h->sk.bytes.p, (size_t)1 << h->sk.view.p, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
@@ -2940,12 +2890,12 @@ int kdf_sketch_registers(kdf_engine *h, uint8_t *regs_out) {
 int kdf_sketch_merge(kdf_engine *h, const uint8_t *regs) {
     if (!h || !regs) return fail(h, KDF_ERR_INVALID, "kdf_sketch_merge: NULL pointer");
     SK_NEED_ON(h, "kdf_sketch_merge");
-    const uint32_t m = 1u << h->sk.p, top = 65 - h->sk.p;
+    const uint32_t m = 1u << h->sk.view.p, top = 65 - h->sk.view.p;
     for (uint32_t i = 0; i < m; ++i)
-        if (regs[i] > top) return fail(h, KDF_ERR_INVALID, "kdf_sketch_merge: register %u reads %u: a sketch of 2^%u registers holds ranks 0..%u", i, (unsigned)regs[i], h->sk.p, top);
+        if (regs[i] > top) return fail(h, KDF_ERR_INVALID, "kdf_sketch_merge: register %u reads %u: a sketch of 2^%u registers holds ranks 0..%u", i, (unsigned)regs[i], h->sk.view.p, top);
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(h->sk_bytes, regs, m, hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(kdf_sk_merge_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.cells, m, (const uint8_t *)h->sk_bytes);
+    HIPCHK(h, hipMemcpyAsync(h->sk.bytes.p, regs, m, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(kdf_sk_merge_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, h->sk.view.cells, m, h->sk.bytes.as<const uint8_t>());
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));                    // (the caller's array is its own again)
     return KDF_OK;
@@ -2963,9 +2913,9 @@ int kdf_sketch_estimate_registers(const uint8_t *regs, uint32_t log2_registers, 
 int kdf_sketch_estimate(kdf_engine *h, double *distinct_out) {
     if (!h || !distinct_out) return fail(h, KDF_ERR_INVALID, "kdf_sketch_estimate: NULL pointer");
     SK_NEED_ON(h, "kdf_sketch_estimate");
-    std::vector<uint8_t> regs((size_t)1 << h->sk.p);
+    std::vector<uint8_t> regs((size_t)1 << h->sk.view.p);
     { int rc = kdf_sketch_registers(h, regs.data()); if (rc) return rc; }
-    if (!kdf_sk_estimate_host(regs.data(), h->sk.p, distinct_out)) return fail(h, KDF_ERR_STATE, "kdf_sketch_estimate: a register is out of range");
+    if (!kdf_sk_estimate_host(regs.data(), h->sk.view.p, distinct_out)) return fail(h, KDF_ERR_STATE, "kdf_sketch_estimate: a register is out of range");
     return KDF_OK;
 }
 
@@ -2980,47 +2930,47 @@ int kdf_sketch_drop(kdf_engine *h) {
 
 // [first_word, first_word + n_words) inside the sieve (the prefilter is not off)
 #define PF_NEED_RANGE(h, fn) \
-    do { const uint64_t total_ = 1ull << ((h)->pf.log2_cells - 4); \
+    do { const uint64_t total_ = 1ull << ((h)->pf.view.log2_cells - 4); \
          if (first_word > total_ || n_words > total_ - first_word) \
              return fail(h, KDF_ERR_INVALID, "%s: words [%llu, +%llu) reach past the sieve's %llu words (kdf_prefilter_words)", fn, \
                          (unsigned long long)first_word, (unsigned long long)n_words, (unsigned long long)total_); } while (0)
 
 int kdf_prefilter_words(kdf_engine *h, uint64_t *n_words) {
     if (!h || !n_words) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_words: NULL pointer");
-    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_words: no prefilter (kdf_prefilter_begin)");
-    *n_words = 1ull << (h->pf.log2_cells - 4);
+    if (h->pf.state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_words: no prefilter (kdf_prefilter_begin)");
+    *n_words = 1ull << (h->pf.view.log2_cells - 4);
     return KDF_OK;
 }
 
 int kdf_prefilter_export_dev(kdf_engine *h, uint64_t first_word, uint64_t n_words, void *d_words_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export_dev: no prefilter (kdf_prefilter_begin)");
+    if (h->pf.state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export_dev: no prefilter (kdf_prefilter_begin)");
     PF_NEED_RANGE(h, "kdf_prefilter_export_dev");
     if (n_words == 0) return KDF_OK;
     if (!d_words_out) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_export_dev: NULL output");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(d_words_out, h->pf.words + first_word, n_words * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_words_out, h->pf.view.words + first_word, n_words * 8, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
 int kdf_prefilter_export(kdf_engine *h, uint64_t first_word, uint64_t n_words, uint64_t *words_out) {
     if (!h) return fail(nullptr, KDF_ERR_INVALID, "NULL engine");
-    if (h->pf_state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export: no prefilter (kdf_prefilter_begin)");
+    if (h->pf.state == PF_OFF) return fail(h, KDF_ERR_STATE, "kdf_prefilter_export: no prefilter (kdf_prefilter_begin)");
     PF_NEED_RANGE(h, "kdf_prefilter_export");
     if (n_words == 0) return KDF_OK;
     if (!words_out) return fail(h, KDF_ERR_INVALID, "kdf_prefilter_export: NULL output");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(words_out, h->pf.words + first_word, n_words * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(words_out, h->pf.view.words + first_word, n_words * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return KDF_OK;
 }
 
 // the checks both merge forms share (nothing is written when one fails)
 static int pf_merge_check(kdf_engine *h, const char *fn, uint64_t first_word, uint64_t n_words, uint32_t nseg, const void *const *segs) {
-    if (h->pf_state != PF_TALLYING)
+    if (h->pf.state != PF_TALLYING)
         return fail(h, KDF_ERR_STATE, "%s: the prefilter is %s; sieves are merged between kdf_prefilter_begin and kdf_prefilter_arm", fn,
-                    h->pf_state == PF_ARMED ? "armed (its sieve is immutable: partition-time gates rely on that)" : "off");
+                    h->pf.state == PF_ARMED ? "armed (its sieve is immutable: partition-time gates rely on that)" : "off");
     PF_NEED_RANGE(h, fn);
     if (nseg == 0 || nseg > KDF_PF_MAX_SEGS) return fail(h, KDF_ERR_INVALID, "%s: nseg %u: must be 1..%d", fn, nseg, KDF_PF_MAX_SEGS);
     if (!segs) return fail(h, KDF_ERR_INVALID, "%s: NULL segment array", fn);
@@ -3202,8 +3152,8 @@ static int join_core(kdf_engine *h, kdf_engine *o, const KdfJoinArgs &a, uint64_
     if (n > cap) return fail(h, KDF_ERR_INVALID, "%s: %llu entries, room for %llu", fn, (unsigned long long)n, (unsigned long long)cap);
     if (sorted && n) {
         if (!cnt && !is_long(h)) {                                   // the pair sort carries a payload: a scratch one
-            if ((rc = eng_reserve(h, *h->merge_buf, n * 4))) return rc;         // (nothing that fills merge_buf runs inside a join)
-            cnt = (uint32_t *)h->merge_buf->p;
+            if ((rc = eng_reserve(h, h->merge.scratch, n * 4))) return rc;         // (nothing that fills merge.scratch runs inside a join)
+            cnt = h->merge.scratch.as<uint32_t>();
             HIPCHK(h, hipMemsetAsync(cnt, 0, n * 4, h->stream));
         }
         std::string serr;
@@ -3331,9 +3281,9 @@ int kdf_export_parts_w_packed_dev(kdf_engine *h, uint32_t min_count, uint32_t pa
     { int rcf = pending_flush(h); if (rcf) return rcf; }
     { int rc0 = materialize(h); if (rc0) return rc0; }
     // scratch: part_cnt u64[64] | cursor u64[64] | part_base u64[64]
-    int rc = eng_reserve(h, *h->merge_buf, 3 * KLM_MAX_PARTS * 8, slack_exact);
+    int rc = eng_reserve(h, h->merge.scratch, 3 * KLM_MAX_PARTS * 8, slack_exact);
     if (rc) return rc;
-    unsigned long long *part_cnt = (unsigned long long *)h->merge_buf->p, *cursor = part_cnt + KLM_MAX_PARTS, *part_base = cursor + KLM_MAX_PARTS;
+    unsigned long long *part_cnt = h->merge.scratch.as<unsigned long long>(), *cursor = part_cnt + KLM_MAX_PARTS, *part_base = cursor + KLM_MAX_PARTS;
     HIPCHK(h, hipMemsetAsync(part_cnt, 0, 2 * KLM_MAX_PARTS * 8, h->stream));        // part_cnt | cursor
     const uint64_t waves = (h->cap + KDF_EXPORT_ROWS * 64 - 1) / (KDF_EXPORT_ROWS * 64);
     const unsigned blocks = (unsigned)((waves + 3) / 4);
@@ -3439,7 +3389,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
         const uint32_t parts = n == "key_parts" ? (uint32_t)value : h->opt_key_parts, part = n == "key_part" ? (uint32_t)value : h->opt_key_part;
         if (value < 0 || parts > 65536 || (n == "key_part" && part >= std::max<uint32_t>(parts, 1)))
             return fail(h, KDF_ERR_INVALID, "key_parts must be 0..65536 and key_part below it");
-        if (parts > 1 && h->pf_state != PF_OFF)
+        if (parts > 1 && h->pf.state != PF_OFF)
             return fail(h, KDF_ERR_STATE, "key_parts = %u with a prefilter: a prefilter counts the whole key space in one table (kdf_prefilter_drop first)", parts);
         h->opt_key_parts = parts; h->opt_key_part = n == "key_parts" ? 0 : part;
     }
@@ -3466,7 +3416,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     else if (n == "hash_shift") {
         if (value > 8) return fail(h, KDF_ERR_INVALID, "hash_shift must be 0..8");
         if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "hash_shift: not available for k > 63 (long keys count on one GPU)");
-        if (value != 0 && h->pf_state != PF_OFF)
+        if (value != 0 && h->pf.state != PF_OFF)
             return fail(h, KDF_ERR_STATE, "hash_shift = %lld with a prefilter: an owner table of the multi-GPU merge takes no prefilter (kdf_prefilter_drop first)", (long long)value);
         if ((uint32_t)value != h->opt_hash_shift) {
             int rc = ctl_sync(h, nullptr);
@@ -3477,7 +3427,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "defer") h->opt_defer = value != 0;
     else if (n == "defer_max_bytes") h->opt_defer_max_bytes = (uint64_t)value;
-    else if (n == "bamdev_host_inflate") h->opt_bd_host_inflate = value != 0;
+    else if (n == "bamdev_host_inflate") h->bd.opt_host_inflate = value != 0;
     else if (n == "fused_dump") {
         if (value != 0 && is_long(h)) return fail(h, KDF_ERR_INVALID, "fused_dump: not available for k > 63 (no binned pipeline for long keys)");
         h->opt_fused_dump = value != 0;
@@ -3488,7 +3438,7 @@ int kdf_set_option(kdf_engine *h, const char *name, int64_t value) {
     }
     else if (n == "l1_positions") h->opt_l1_positions = (uint64_t)std::max<int64_t>(value, KDF_TILE);
     else if (n == "l1_direct_positions") h->opt_l1_direct_positions = (uint64_t)std::max<int64_t>(value, 0);
-    else if (n == "sieve_bits") { h->opt_sieve_bits = (int)value; h->sieve_unfit = false; bin_sieve_drop(h); }     // (other sizing: the keys may fit now)
+    else if (n == "sieve_bits") { h->opt_sieve_bits = (int)value; h->sieve.unfit = false; bin_sieve_drop(h); }     // (other sizing: the keys may fit now)
     else if (n == "sieve_bins") {
         if (value != 0 && value != 1 && (value < KDF_BS_C1_MIN || value > KDF_BS_C1_MAX))
             return fail(h, KDF_ERR_INVALID, "sieve_bins %lld: must be 0 (off), 1 (coarse bits by the filter's size) or %d..%d coarse bits", (long long)value, KDF_BS_C1_MIN, KDF_BS_C1_MAX);
@@ -3514,46 +3464,46 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     if (EvTimer *t = timer_of_stat(h->timer, TIMER_NAME, T_COUNT, n, &us)) *value = us ? t->us() : (t->collect(), (int64_t)t->passes);
     else if (n == "binned_passes") *value = (int64_t)h->stat_binned_passes;
     else if (n == "replayed_buckets") *value = (int64_t)h->stat_replayed_buckets;
-    else if (n == "prefilter_state") *value = h->pf_state;
-    else if (n == "prefilter_min_count") *value = h->pf.min_count;
-    else if (n == "prefilter_log2_cells") *value = h->pf.log2_cells;
-    else if (n == "prefilter_bytes") *value = h->pf_state == PF_OFF ? 0 : (int64_t)(1ull << (h->pf.log2_cells - 1));
+    else if (n == "prefilter_state") *value = h->pf.state;
+    else if (n == "prefilter_min_count") *value = h->pf.view.min_count;
+    else if (n == "prefilter_log2_cells") *value = h->pf.view.log2_cells;
+    else if (n == "prefilter_bytes") *value = h->pf.state == PF_OFF ? 0 : (int64_t)(1ull << (h->pf.view.log2_cells - 1));
     else if (n == "prefilter_windows") {
         *value = 0;
-        if (h->pf_ctr) {                                              // the sharded device counter, summed here
+        if (h->pf.ctr) {                                              // the sharded device counter, summed here
             std::vector<unsigned long long> c(KDF_SHARDS * 16);
             HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, hipMemcpyAsync(c.data(), h->pf_ctr, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(c.data(), h->pf.ctr.p, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             for (int i = 0; i < KDF_SHARDS; ++i) *value += (int64_t)c[i * 16];
         }
     }
-    else if (n == "bamdev_fallback_blocks") *value = (int64_t)h->stat_bd_fallback;
-    else if (n == "sketch_state") *value = h->sk_on ? 1 : 0;
-    else if (n == "sketch_log2_registers") *value = h->sk_on ? (int64_t)h->sk.p : 0;
+    else if (n == "bamdev_fallback_blocks") *value = (int64_t)h->bd.stat_fallback;
+    else if (n == "sketch_state") *value = h->sk.on ? 1 : 0;
+    else if (n == "sketch_log2_registers") *value = h->sk.on ? (int64_t)h->sk.view.p : 0;
     else if (n == "sketch_windows") {
         *value = 0;
-        if (h->sk_on) {                                               // the sharded device counter, summed here
+        if (h->sk.on) {                                               // the sharded device counter, summed here
             HIPCHK(h, hipSetDevice(h->device));
             std::vector<unsigned long long> c(KDF_SHARDS * 16);
-            HIPCHK(h, hipMemcpyAsync(c.data(), h->sk_ctr, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(c.data(), h->sk.ctr.p, c.size() * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             unsigned long long t = 0;
             for (int i = 0; i < KDF_SHARDS; ++i) t += c[(size_t)i * 16];
             *value = (int64_t)t;
         }
     }
-    else if (n == "prefilter_merged_words") *value = h->pf_state == PF_OFF ? 0 : (int64_t)h->stat_pf_merged_words;
+    else if (n == "prefilter_merged_words") *value = h->pf.state == PF_OFF ? 0 : (int64_t)h->pf.merged_words;
     else if (n == "flushes") *value = (int64_t)h->stat_flushes;
     // (pending: not yet applied by any flush.  Passes a dump-only flush has applied are kept in the ring -- "retained_passes" --
     // until the table is asked for or cleared)
-    else if (n == "pending_passes") *value = (int64_t)h->ring.undumped_passes();
-    else if (n == "pending_positions") *value = (int64_t)(h->ring.undumped_positions() + h->l1.positions());
-    else if (n == "retained_passes") *value = (int64_t)h->ring.n_dumped;
+    else if (n == "pending_passes") *value = (int64_t)h->kb.ring.undumped_passes();
+    else if (n == "pending_positions") *value = (int64_t)(h->kb.ring.undumped_positions() + h->kb.l1.positions());
+    else if (n == "retained_passes") *value = (int64_t)h->kb.ring.n_dumped;
     else if (n == "dump_only_flushes") *value = (int64_t)h->stat_dump_only;
     else if (n == "materialisations") *value = (int64_t)h->stat_materialisations;
     else if (n == "lazy_table") *value = h->opt_lazy_table;
-    else if (n == "ring_bytes") *value = (int64_t)(h->ring.cap_entries * 8 * h->kw);
+    else if (n == "ring_bytes") *value = (int64_t)(h->kb.ring.cap_entries * 8 * h->kw);
     else if (n == "defer") *value = h->opt_defer;
     else if (n == "last_count_path") *value = h->last_path;
     else if (n == "last_scan_path") *value = h->last_scan_path;
@@ -3564,7 +3514,7 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "last_sieve_in_lds") *value = h->last_sieve_in_lds;
     else if (n == "last_sieve_rounds") *value = h->last_sieve_rounds;
     else if (n == "long_sieve") *value = h->opt_long_sieve;
-    else if (n == "last_merge_path") *value = h->last_merge_path;
+    else if (n == "last_merge_path") *value = h->merge.last_path;
     else if (n == "heavy_buckets") *value = (int64_t)h->stat_heavy_buckets;
     else if (n == "fused_dumps") *value = (int64_t)h->stat_fused_dumps;
     else if (n == "fused_dump") *value = h->opt_fused_dump;
@@ -3572,14 +3522,14 @@ int kdf_get_stat(kdf_engine *h, const char *name, int64_t *value) {
     else if (n == "log2cap") *value = h->t.log2cap;
     else if (n == "bucket_bits") *value = h->t.bucket_bits;
     // the binned path's split of the bucket bits: of the pending passes, or what the next pass would be partitioned with
-    else if (n == "c1") *value = (h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan).c1;
-    else if (n == "c2") *value = (h->ring.empty() ? kb_make_plan(h, h->t) : h->ring.plan).c2;
-    else if (n.rfind("trash", 0) == 0 && n.size() > 5 && h->kb_small) {          // (variant builds with -DKB_TIMING: phase cycle sums)
+    else if (n == "c1") *value = (h->kb.ring.empty() ? kb_make_plan(h, h->t) : h->kb.ring.plan).c1;
+    else if (n == "c2") *value = (h->kb.ring.empty() ? kb_make_plan(h, h->t) : h->kb.ring.plan).c2;
+    else if (n.rfind("trash", 0) == 0 && n.size() > 5 && h->kb.small) {          // (variant builds with -DKB_TIMING: phase cycle sums)
         const int i = atoi(n.c_str() + 5);
         if (i < 0 || i >= 64) return fail(h, KDF_ERR_INVALID, "kdf_get_stat: trash0..trash63");
         unsigned long long v = 0;
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        HIPCHK(h, hipMemcpy(&v, h->kb_small + 16 + i, 8, hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&v, h->kb.small.as<unsigned long long>() + 16 + i, 8, hipMemcpyDeviceToHost));
         *value = (int64_t)v;
     }
     else return fail(h, KDF_ERR_INVALID, "kdf_get_stat: unknown stat %s", name);

@@ -39,8 +39,6 @@ struct KbPass;                            // kdf_binned.h (the core)
 
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
-// every grow-only device buffer of an engine (DevBuf, kdf_hostutil.h), by group: the first index and, from the next, the size
-enum { BUF_STAGE = 0, BUF_KB = BUF_STAGE + 1, BUF_MERGE = BUF_KB + 8, BUF_HIT = BUF_MERGE + 1, BUF_UP = BUF_HIT + 4, BUF_COV = BUF_UP + 4, BUF_VAR = BUF_COV + 1, BUF_BD = BUF_VAR + 3, BUF_REG = BUF_BD + 3, BUF_COUNT = BUF_REG + 2 };
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
 enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_COUNT };
 static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta"};
@@ -65,7 +63,7 @@ struct KbRing {
 };
 // L1: small insert batches are concatenated (packed) in a pending stream first; the partition runs over ~2^30 positions
 struct KbPendStream {
-    uint64_t *packed = nullptr, *mask = nullptr;
+    DevBuf packed, mask;                             // uint64_t words: cap_tiles tiles of each (l1_append grows the pair together)
     uint64_t cap_tiles = 0, tiles = 0;
     uint64_t positions() const { return tiles * KDF_TILE; }
     uint64_t take() { const uint64_t n = positions(); tiles = 0; return n; }      // the stream is handed on (packed, mask: n positions) and empty again
@@ -76,37 +74,106 @@ struct KbDump {
     uint32_t min_count = 0; uint64_t *lo = nullptr, *hi = nullptr; uint32_t *cnt = nullptr; uint64_t cap = 0;     // the request
     bool done = false; uint64_t n = 0;                                                                             // the result: written whole, n keys
 };
+
+// ---- the engine's state, by feature.  Every allocation is a DevBuf / PinBuf member (kdf_devbuf.h) named for what it holds:
+// it is reserved where it is used (eng_reserve, dev_reserve, alloc) and freed when the engine goes (kdf_destroy drains the
+// streams, then deletes the engine).  The structs kernels take by value (KdfTable, KbScratch, KdfPrefilter, KdfSketch) are
+// views filled from these owners. ----
+struct TableMem { DevBuf lo, hi, cnt; };             // the arrays of one table: keys (hi: words 1 .. W-1 of wide and long keys), counts
+// binned (LDS-bucket) path (kdf_binned.h)
+struct KbState {
+    DevBuf ent, tmp;                                 // the ring's entries; the slab-sorted pass
+    DevBuf chunk_off, failed, off_rows, pass_plan;   // the ring's offset rows, the bitmap of failed buckets; a pass's offset rows and planning arrays
+    DevBuf row_tables, bin_runs;                     // row_ent u64 | row_len u32, ring.cap_rows of each; bin-major runs (bin sieve)
+    DevBuf small, pass, heavy;                       // totals[16] then trash[64]; [KB_MAX_PASS] pass descriptors; heavy buckets of skewed flushes (kb_heavy_slice_kernel)
+    PinBuf totals_host;                              // [16]
+    uint64_t total(int i) const { return totals_host.as<unsigned long long>()[i]; }
+    KbRing ring;                                     // the pending passes (above)
+    KbPendStream l1;                                 // small insert batches waiting to be partitioned (above)
+    bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
+};
+// blocked Bloom filter over the filter keys (count --if, scan)
+struct SieveState {
+    DevBuf buf; uint64_t words = 0;                  // uint64_t words (grow-only); those of the sieve in use
+    bool valid = false, unfit = false;               // unfit: long_sieve_ensure found the table's keys too many for a sieve: not asked again
+                                                     // until the keys, the filter or the sizing options change (sieve_drop)
+};
+// count --if through the bin-major sieve (kdf_binsieve.h; option "sieve_bins" / env KDF_SIEVE_BINS: 0 off, 1 the sizing rule's
+// coarse bits, 4 .. 10 exactly those): an allocation of its own, built from the table by the first eligible count --if
+// (bin_sieve_ensure) and dropped with the other sieve (sieve_drop) and when sieve_bits / sieve_bins change
+struct BinSieveState {
+    DevBuf buf; uint32_t c1 = 0, slice_words = 0;    // uint64_t [2^c1][slice_words] (grow-only)
+    bool valid = false, unfit = false;               // unfit: the sizing rule refused the table's keys (not asked again until a drop)
+    bool attr_set[3] = {false, false, false};        // kdf_bin_sieve_kernel's LDS limit raised (per key width)
+};
+// two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off
+struct PfState {
+    int state = PF_OFF;
+    KdfPrefilter view{};                             // the sieve (words), its size and the gate's threshold
+    DevBuf words, ctr;                               // the counting sieve; sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
+    DevBuf admit;                                    // the gate's output for the stream being counted, one word per tile (grow-only)
+    uint64_t merged_words = 0;                       // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
+};
+// distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream
+struct SkState {
+    bool on = false;
+    KdfSketch view{};                                // the register cells and p
+    DevBuf cells, bytes;                             // bytes: 2^p of them, the exported form on its way out / a merge's input
+    DevBuf ctr;                                      // sharded counter of sketched windows [KDF_SHARDS * 16]
+};
+// double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
+// stream of their own, so the H2D copy of batch i + 1 runs under the count of batch i
+struct UpSlot {
+    DevBuf packed, mask; uint64_t n_bases = 0; bool valid = false;
+    hipEvent_t up_done = nullptr, use_done = nullptr;    // the copy into the slot; the consumer that last read it
+};
+struct UpState { UpSlot slot[2]; hipStream_t copy_stream = nullptr; };
+// grow-only scratch kept between calls, per consumer
+struct HitScratch { DevBuf mask, block_sums, positions, pair_set; };   // kdf_hits.h: hit mask (caller gave none), block sums, hit positions, the (read, slot) set
+struct CovScratch { DevBuf cigar_pre; };                               // kdf_coverage.h: CIGAR prefix sums
+struct VarScratch { DevBuf cigar_pre, ranges, cand_counts; };          // kdf_variants.h: CIGAR prefix sums, per-read ranges, per-candidate counts and flags
+struct RegScratch { DevBuf scratch, perm; };                           // kdf_regions.h: the sort's top key word, block maxima and boundary flags; the permutation
+struct KfScratch { DevBuf block_sums; };                               // kdf_kmerfasta.h: block sums of the record scan and its counters
+struct BdState {                                                       // device BAM feeder (kdf_bamdev.h)
+    DevBuf inflated, status, read_offs;              // inflated span; block / sub-range status, counts, bases and totals; per-read sequence offsets
+    // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
+    // "bamdev_host_inflate": tells a decoder fault from a file fault, and lets the tests walk the patch path, which no file zlib wrote takes)
+    int opt_host_inflate = 0;
+    uint64_t stat_fallback = 0;                      // blocks the device decoder rejected and zlib inflated (stat "bamdev_fallback_blocks")
+};
+struct MergeState {                                  // kdf_merge.h
+    DevBuf scratch;                                  // block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly); the payload of a sorted join without counts
+    uint32_t flag_host = 0; int last_path = 0;       // last_path: 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
+    bool attrs_set[3] = {false, false, false};       // km_merge_kernel's LDS limit raised (big buckets)
+};
+
 struct kdf_engine {
     int device = 0;
     int k = 0;
     int kw = 1;                   // key words: 1 narrow, 2 wide, 3..7 long (kdf_long.h)
     int n_cu = 256;               // compute units of the device (persistent-kernel grids)
     uint64_t dev_total_bytes = 0; // HBM of the device (sizes the entry ring's budget)
-    KdfTable t{};                 // live table
+    TableMem t_mem;               // the live table's arrays ...
+    KdfTable t{};                 // ... and the view of them that kernels take
     uint64_t cap = 0;
-    KdfCtl *ctl = nullptr;        // device
-    unsigned long long *d_out4 = nullptr;   // device scratch for ctl readback
-    unsigned long long *h_out4 = nullptr;   // pinned host mirror
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    DevBuf ctl_mem, out4_mem; PinBuf out4_pin;      // the control block, ctl readback scratch (device) and its pinned host mirror, seen through:
+    KdfCtl *ctl = nullptr; unsigned long long *d_out4 = nullptr, *h_out4 = nullptr;
+    hipStream_t own_stream = nullptr, stream = nullptr;      // stream: the one in use (kdf_set_stream), own_stream unless the caller gave one
     uint64_t distinct = 0;        // host mirror after the last sync
     uint64_t windows = 0;
     bool filter_mode = false;
     bool lazy_empty = false;      // logically empty, HBM slices not yet reset (see kdf_clear)
     bool zero_keys = false;       // the table may hold keys with count 0 (a filter, added pairs, reset / set counts): kdf_histo.h
-    DevBuf buf[BUF_COUNT];                           // released together (kdf_destroy); used through the views below
-    DevBuf &arena = buf[BUF_STAGE];                  // the staging of the host forms: laid out per call by a HostCall (below), touched by nothing else
+    uint64_t capacity_hint = 0;   // kdf_create's: sizes the prefilter's sieve when the caller leaves that to the engine
+    DevBuf arena;                                    // the staging of the host forms: laid out per call by a HostCall (below), touched by nothing else
     const char *arena_user = nullptr;                // the host form whose HostCall is open (commit() .. its destructor), else NULL
-    // ---- binned (LDS-bucket) path: scratch + options -------------------------------------------------------------------
-    unsigned long long *kb_small = nullptr;   // totals[16]
-    unsigned long long *kb_totals_host = nullptr;   // pinned [16]
-    DevBuf *const kb_buf = buf + BUF_KB;             // [8] ring entries, tmp (slab-sorted pass), chunk_off, failed, off rows, pass planning, row tables, bin-major runs (bin sieve)
-    KbPass *kb_pass = nullptr;                       // [KB_MAX_PASS] descriptors of the pending passes (device)
-    KbRing ring;                                     // the pending passes (above)
+    // ---- the features' state (above) ----------------------------------------------------------------------------------
+    KbState kb; SieveState sieve; BinSieveState bsv; PfState pf; SkState sk; UpState up;
+    HitScratch hits; CovScratch cov; VarScratch var; RegScratch reg; KfScratch kf; BdState bd; MergeState merge;
+    // ---- options, statistics and what the last call did ------------------------------------------------------------------
     uint64_t stat_flushes = 0;
     double grow_ratio = 0.0;                         // new distinct keys per counted window at the last flush (0: unknown)
     uint64_t dens_windows = 0, dens_positions = 0;   // valid windows / stream positions of every pass this engine has flushed: sizes the piece groups
-    KbPendStream l1;                                 // small insert batches waiting to be partitioned (above)
     uint32_t opt_key_parts = 0, opt_key_part = 0;    // count only one slice of the key space (KdfTable::key_parts)
     uint64_t opt_binned_min_positions = 1ull << 22;  // fewer pending positions at flush time use the direct global-table kernels
     uint64_t opt_binned_bytes_per_position = 70;     // ... and so does a flush of fewer than table_bytes / 70 positions (use_binned)
@@ -131,39 +198,15 @@ struct kdf_engine {
     uint64_t stat_dump_only = 0, stat_materialisations = 0;
     uint64_t opt_l1_positions = 1ull << 30;          // pending-stream size from which it is partitioned
     uint64_t opt_l1_direct_positions = 1ull << 28;   // batches from this size on are partitioned where they lie (no copy)
-    // double-buffered feeding (kdf_upload_reads_async / kdf_count_uploaded): two device staging slots filled on a copy
-    // stream of their own, so the H2D copy of batch i + 1 runs under the count of batch i
-    DevBuf (*const up_buf)[2] = (DevBuf (*)[2])(buf + BUF_UP);      // [slot][packed, mask]
-    uint64_t up_n[2] = {0, 0}; bool up_valid[2] = {false, false};
-    hipStream_t copy_stream = nullptr; hipEvent_t up_done[2] = {nullptr, nullptr}, use_done[2] = {nullptr, nullptr};
     uint64_t stat_heavy_buckets = 0;
-    void *kb_heavy = nullptr;                        // heavy buckets of skewed flushes (kdf_binned.h kb_heavy_slice_kernel)
-    DevBuf *const merge_buf = buf + BUF_MERGE;       // kdf_merge.h: block counts / offsets of the ordered dump, bucket ranges of a merge (sized exactly); the payload of a sorted join without counts
-    uint32_t merge_flag_host = 0;
-    int last_merge_path = 0;                         // 0 none yet, 1 LDS bucket merge launched, 2 plain atomic insert
     int opt_sieve_bits = 0;                          // sieve bits per filter key (0: 32 up to 2^20 keys, 16 beyond)
     // long engines take the sieve only when asked to (option "long_sieve" / env KDF_LONG_SIEVE=1; k <= 63: always): their
     // count --if and scan then go through kdf_long_sieve_kernel (kdf_long_sieve.h)
     int opt_long_sieve = [] { const char *e = getenv("KDF_LONG_SIEVE"); return e ? atoi(e) != 0 : 0; }();
     int last_sieve_in_lds = 0;                       // the last sieve kernel read the sieve from LDS (1) or from L2 (0)
-    bool merge_attrs_set[3] = {false, false, false};  // km_merge_kernel's LDS limit raised (big buckets)
-    bool attrs_set[4] = {false, false, false, false};   // hipFuncSetAttribute done (per key width)
     int last_path = 0;                               // count path of the last count call: 0 direct, 1 binned, 3 sieve, 5 bin-major sieve
     int last_scan_path = 0;                          // kernel of the last kdf_scan_reads_dev: 0 direct, 3 sieve
-    uint64_t *sieve = nullptr;                       // blocked Bloom filter over the filter keys (count --if)
-    uint64_t sieve_words = 0, sieve_alloc = 0;
-    bool sieve_valid = false;
-    bool sieve_unfit = false;                        // long_sieve_ensure found the table's keys too many for a sieve: not asked again
-                                                     // until the keys, the filter or the sizing options change (sieve_drop)
-    // count --if through the bin-major sieve (kdf_binsieve.h; option "sieve_bins" / env KDF_SIEVE_BINS: 0 off, 1 the sizing rule's
-    // coarse bits, 4 .. 10 exactly those): an allocation of its own, built from the table by the first eligible count --if
-    // (bin_sieve_ensure) and dropped with the other sieve (sieve_drop) and when sieve_bits / sieve_bins change
-    int opt_sieve_bins = [] { const char *e = getenv("KDF_SIEVE_BINS"); const int v = e ? atoi(e) : 0; return v == 1 || (v >= 4 && v <= 10) ? v : 0; }();
-    uint64_t *bsv = nullptr;                         // [2^bsv_c1][bsv_slice_words]
-    uint64_t bsv_alloc = 0;                          // words
-    uint32_t bsv_c1 = 0, bsv_slice_words = 0;
-    bool bsv_valid = false, bsv_unfit = false;       // unfit: the sizing rule refused the table's keys (not asked again until a drop)
-    bool bsv_attr_set[3] = {false, false, false};    // kdf_bin_sieve_kernel's LDS limit raised (per key width)
+    int opt_sieve_bins = [] { const char *e = getenv("KDF_SIEVE_BINS"); const int v = e ? atoi(e) : 0; return v == 1 || (v >= 4 && v <= 10) ? v : 0; }();   // BinSieveState
     uint32_t last_sieve_bins = 0, last_sieve_slice_words = 0;
     uint64_t stat_bin_sieve_passes = 0;
     uint32_t last_sieve_rounds = 0;                  // tiles per thread of the last sieve kernel of a long engine (LDS form; L2 form: 1)
@@ -178,32 +221,6 @@ struct kdf_engine {
     std::vector<std::vector<hipEvent_t>> prof_stage_ev;   // 4 events: a partition (A0, A1, B); 2 events: a flush (C)
     double prof_stage_ms[4] = {0, 0, 0, 0};
     uint64_t prof_stage_passes = 0;
-    // ---- two-pass counting (kdf_prefilter.h): off -> begin -> tallying -> arm -> armed -> drop -> off ------------------------
-    int pf_state = PF_OFF;
-    KdfPrefilter pf{};                               // the sieve (device), its size and the gate's threshold
-    unsigned long long *pf_ctr = nullptr;            // device: sharded counter of tallied windows [KDF_SHARDS * 16], then 3 words of kdf_pf_fill_kernel
-    uint64_t *pf_admit = nullptr; uint64_t pf_admit_words = 0;   // the gate's output for the stream being counted (grow-only)
-    uint64_t capacity_hint = 0;                      // kdf_create's: sizes the sieve when the caller leaves that to the engine
-    uint64_t stat_pf_merged_words = 0;               // words written by kdf_prefilter_merge* since kdf_prefilter_begin (stat "prefilter_merged_words")
-    // ---- per-read reduction of the scan (kdf_hits.h): grow-only scratch kept between calls -------------------------------
-    DevBuf *const hit_buf = buf + BUF_HIT;           // [4] 0 hit mask (caller gave none), 1 block sums, 2 hit positions, 3 the (read, slot) set
-    // ---- hits in reference coordinates (kdf_coverage.h): grow-only scratch ------------------------------------------------
-    DevBuf *const cov_buf = buf + BUF_COV;           // [1] CIGAR prefix sums
-    // ---- VCF mode (kdf_variants.h): grow-only scratch ------------------------------------------------------------------------
-    DevBuf *const var_buf = buf + BUF_VAR;           // [3] 0 CIGAR prefix sums, 1 per-read ranges, 2 per-candidate counts and flags
-    // ---- regions of informative reads (kdf_regions.h): grow-only scratch ----------------------------------------------------
-    DevBuf *const reg_buf = buf + BUF_REG;           // [2] 0 the sort's top key word, block maxima and boundary flags, 1 the permutation
-    // ---- distinct k-mer sketch (kdf_sketch.h): independent of the table, the mode, the prefilter and the stream ------------
-    bool sk_on = false;
-    KdfSketch sk{};                                  // the register cells (device) and p
-    uint8_t *sk_bytes = nullptr;                     // device: 2^p bytes, the exported form on its way out / a merge's input
-    unsigned long long *sk_ctr = nullptr;            // device: sharded counter of sketched windows [KDF_SHARDS * 16]
-    // ---- device BAM feeder (kdf_bamdev.h): grow-only scratch kept between batches ---------------------------------------------
-    DevBuf *const bd_buf = buf + BUF_BD;             // [3] 0 inflated span, 1 block / sub-range status, counts, bases and totals, 2 per-read sequence offsets
-    // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
-    // "bamdev_host_inflate": tells a decoder fault from a file fault, and lets the tests walk the patch path, which no file zlib wrote takes)
-    int opt_bd_host_inflate = 0;
-    uint64_t stat_bd_fallback = 0;                   // blocks the device decoder rejected and zlib inflated (stat "bamdev_fallback_blocks")
     std::string err;
 };
 
@@ -320,14 +337,15 @@ void src_release(kdf_engine *h, const StreamSrc &src);
 // soon as the call returns, and the copy was issued a whole batch ago.  An empty batch (n_bases 0) needs no wait.
 template <typename S, typename R>
 static int src_slot(S &&sink, const char *fn, kdf_engine *h, int slot, bool consume, bool host_wait, StreamSrc &src, R &&also_refuse) {
-    if (slot < 0 || slot > 1 || !h->up_valid[slot]) return sink(KDF_ERR_STATE, "%s: nothing was uploaded into slot %d", fn, slot);
-    src = StreamSrc{(const uint64_t *)h->up_buf[slot][0].p, (const uint64_t *)h->up_buf[slot][1].p, h->up_n[slot], slot};
+    if (slot < 0 || slot > 1 || !h->up.slot[slot].valid) return sink(KDF_ERR_STATE, "%s: nothing was uploaded into slot %d", fn, slot);
+    const UpSlot &up = h->up.slot[slot];
+    src = StreamSrc{up.packed.as<const uint64_t>(), up.mask.as<const uint64_t>(), up.n_bases, slot};
     if (const int rc = also_refuse(src)) return rc;
-    if (consume) h->up_valid[slot] = false;
+    if (consume) h->up.slot[slot].valid = false;
     if (src.n_bases == 0) return KDF_OK;
     hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, h->up_done[slot], 0);
-    if (e == hipSuccess && host_wait) e = hipEventSynchronize(h->up_done[slot]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, up.up_done, 0);
+    if (e == hipSuccess && host_wait) e = hipEventSynchronize(up.up_done);
     if (e != hipSuccess) return sink(e == hipErrorOutOfMemory ? KDF_ERR_NOMEM : KDF_ERR_HIP, "%s: waiting for the copy into slot %d failed: %s", fn, slot, hipGetErrorString(e));
     return KDF_OK;
 }

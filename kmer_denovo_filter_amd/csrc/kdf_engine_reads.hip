@@ -46,15 +46,15 @@ static int depth_pass(kdf_engine *h, const uint64_t *d_packed, const uint64_t *d
     return KDF_OK;
 }
 
-// Steps 1-2 of kdf_hits.h over the mask words of n_bases positions (n_bases >= 1): hit_buf[1] then holds the exclusive
+// Steps 1-2 of kdf_hits.h over the mask words of n_bases positions (n_bases >= 1): hits.block_sums then holds the exclusive
 // prefix of every block of KH_BLOCK_WORDS words and, behind them, the number of set bits below n_bases.
 static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, uint64_t *n_blocks_out) {
     const uint64_t n_words = (n_bases + 63) / 64;
     const uint64_t n_blocks = (n_words + KH_BLOCK_WORDS - 1) / KH_BLOCK_WORDS;
     if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "a hit mask of %llu positions is beyond the 2^47 a call takes", (unsigned long long)n_bases);
-    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
+    int rc = eng_reserve(h, h->hits.block_sums, (n_blocks + 1) * 8, slack_8th, "block sums");
     if (rc) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    unsigned long long *sums = h->hits.block_sums.as<unsigned long long>();
     hipLaunchKernelGGL(kh_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_bits, n_bases, sums);
     hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
     HIPCHK(h, hipGetLastError());
@@ -64,7 +64,7 @@ static int hits_count(kdf_engine *h, const uint64_t *d_bits, uint64_t n_bases, u
 
 // the total hits_count left, on the host (synchronises)
 static int hits_total(kdf_engine *h, uint64_t n_blocks, uint64_t *n_hits) {
-    HIPCHK(h, hipMemcpyAsync(h->h_out4, (unsigned long long *)h->hit_buf[1].p + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_out4, h->hits.block_sums.as<unsigned long long>() + n_blocks, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_hits = h->h_out4[0];
     return KDF_OK;
@@ -75,10 +75,10 @@ static int coverage_list_core(kdf_engine *h, const char *fn, const uint32_t *d_k
                               uint32_t min_reads, void *d_pos_out, void *d_kmer_out, void *d_read_out, uint64_t cap, uint64_t *n_out) {
     const uint64_t n_blocks = (n + KC_BLOCK_ELEMS - 1) / KC_BLOCK_ELEMS;
     if (n_blocks >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "%s: a window of %llu positions is beyond the 2^41 a call takes", fn, (unsigned long long)n);
-    int rc = eng_reserve(h, h->hit_buf[1], (n_blocks + 1) * 8, slack_8th, "block sums");
+    int rc = eng_reserve(h, h->hits.block_sums, (n_blocks + 1) * 8, slack_8th, "block sums");
     if (rc) return rc;
     const uint32_t thr = std::max<uint32_t>(min_reads, 1);
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    unsigned long long *sums = h->hits.block_sums.as<unsigned long long>();
     EvSpan p(h->timer[T_COV], h->prof, h->stream, 1);
     hipLaunchKernelGGL(kc_list_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, d_rc, n, thr, sums);
     hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, n_blocks);
@@ -189,8 +189,8 @@ int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid
     int rc;
     uint64_t *bits = (uint64_t *)d_hit_bits;
     if (!bits) {
-        if ((rc = eng_reserve(h, h->hit_buf[0], (n_bases + 63) / 64 * 8, slack_8th, "hit mask"))) return rc;
-        bits = (uint64_t *)h->hit_buf[0].p;
+        if ((rc = eng_reserve(h, h->hits.mask, (n_bases + 63) / 64 * 8, slack_8th, "hit mask"))) return rc;
+        bits = h->hits.mask.as<uint64_t>();
     }
     if ((rc = kdf_scan_reads_dev(h, d_packed, d_invalid, n_bases, bits))) return rc;     // (applies pending count work)
     if (n_reads == 0) return KDF_OK;
@@ -206,14 +206,14 @@ int kdf_read_hits_dev(kdf_engine *h, const void *d_packed, const void *d_invalid
     if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
     if (n_hits == 0) return KDF_OK;
     uint32_t log2set = log2ceil(2 * n_hits);
-    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
-    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (read, k-mer) pairs"))) return rc;
-    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
-    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
+    if ((rc = eng_reserve(h, h->hits.positions, n_hits * 8, slack_8th, "hit list"))) return rc;
+    if ((rc = eng_reserve(h, h->hits.pair_set, (size_t)8 << log2set, slack_8th, "set of (read, k-mer) pairs"))) return rc;
+    uint64_t *pos = h->hits.positions.as<uint64_t>();
+    unsigned long long *set = h->hits.pair_set.as<unsigned long long>();
     const int64_t *offs = (const int64_t *)d_read_offsets;
     EvSpan p2(h->timer[T_HITS], h->prof, h->stream, 0);           // (the same call's second group: time only)
     HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
-    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, (const unsigned long long *)h->hit_buf[1].p,
+    hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, bits, n_bases, h->hits.block_sums.as<const unsigned long long>(),
                        pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
     hipLaunchKernelGGL(kh_hits_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads,
                        (uint32_t *)d_rows_out);
@@ -247,7 +247,7 @@ int kdf_read_hits(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid
     if ((rc = c.commit()) || (rc = kdf_read_hits_dev(h, c.dev(is), c.dev(is + 1), n_bases, c.dev(io), n_reads, nullptr, c.dev(ir))) ||
         (rc = c.fetch(ir, row_bytes))) return rc;
     // the mask is the _dev form's own buffer (it was given none), not staging
-    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hit_buf[0].p, (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
+    if (hit_bits) HIPCHK(h, hipMemcpyAsync(hit_bits, h->hits.mask.p, (n_bases + 63) / 64 * 8, hipMemcpyDeviceToHost, h->stream));
     return c.finish();
 }
 
@@ -266,7 +266,7 @@ int kdf_hit_list_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases, co
     if ((rc = hits_count(h, (const uint64_t *)d_hit_bits, n_bases, &n_blocks))) return rc;
     if (cap)
         hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_bases,
-                           (const unsigned long long *)h->hit_buf[1].p, (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
+                           h->hits.block_sums.as<const unsigned long long>(), (uint64_t *)d_positions_out, (int64_t *)d_reads_out,
                            (const int64_t *)d_read_offsets, n_reads, cap);
     p.stop();
     HIPCHK(h, hipGetLastError());
@@ -320,15 +320,15 @@ int kdf_hit_coverage_dev(kdf_engine *h, const void *d_hit_bits, uint64_t n_bases
     p1.stop();
     if ((rc = hits_total(h, n_blocks, &n_hits))) return rc;
     if (n_hits == 0) return KDF_OK;
-    if ((rc = eng_reserve(h, h->hit_buf[2], n_hits * 8, slack_8th, "hit list"))) return rc;
-    if ((rc = eng_reserve(h, h->cov_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
-    uint64_t *pos = (uint64_t *)h->hit_buf[2].p;
-    unsigned long long *pre = (unsigned long long *)h->cov_buf[0].p;
+    if ((rc = eng_reserve(h, h->hits.positions, n_hits * 8, slack_8th, "hit list"))) return rc;
+    if ((rc = eng_reserve(h, h->cov.cigar_pre, (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
+    uint64_t *pos = h->hits.positions.as<uint64_t>();
+    unsigned long long *pre = h->cov.cigar_pre.as<unsigned long long>();
     const int64_t *offs = (const int64_t *)d_read_offsets, *rs = (const int64_t *)d_ref_start, *co = (const int64_t *)d_cigar_offsets;
     const uint32_t *cig = (const uint32_t *)d_cigar;
     EvSpan p2(h->timer[T_COV], h->prof, h->stream, 0);            // (the same call's second group: time only)
     hipLaunchKernelGGL(kh_write_kernel, dim3((unsigned)n_blocks), dim3(256), 0, h->stream, (const uint64_t *)d_hit_bits, n_starts,
-                       (const unsigned long long *)h->hit_buf[1].p, pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
+                       h->hits.block_sums.as<const unsigned long long>(), pos, (int64_t *)nullptr, (const int64_t *)nullptr, (int64_t)0, n_hits);
     hipLaunchKernelGGL(kc_prefix_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, offs, n_reads, rs,
                        cig, n_cigar, co, pre);
     hipLaunchKernelGGL(kc_accum_kernel, dim3((unsigned)((n_hits + 255) / 256)), dim3(256), 0, h->stream, pos, n_hits, h->k, offs, n_reads, rs,
@@ -457,12 +457,12 @@ int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_i
     const uint64_t nbr = ((uint64_t)n_reads + 255) / 256;
     if (nbr >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %lld reads are beyond the 2^39 a call takes", (long long)n_reads);
     int rc;
-    if ((rc = eng_reserve(h, h->hit_buf[1], (nbr + 1) * 8, slack_8th, "block sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[0], (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[1], (size_t)(2 * (uint64_t)n_reads + 1) * 8, slack_8th, "candidate ranges"))) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
-    uint64_t *cand_lo = (uint64_t *)h->var_buf[1].p;
-    unsigned long long *cand_off = (unsigned long long *)h->var_buf[1].p + n_reads;
+    if ((rc = eng_reserve(h, h->hits.block_sums, (nbr + 1) * 8, slack_8th, "block sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var.cigar_pre, (size_t)n_cigar * 16, slack_8th, "CIGAR prefix sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var.ranges, (size_t)(2 * (uint64_t)n_reads + 1) * 8, slack_8th, "candidate ranges"))) return rc;
+    unsigned long long *sums = h->hits.block_sums.as<unsigned long long>();
+    uint64_t *cand_lo = h->var.ranges.as<uint64_t>();
+    unsigned long long *cand_off = h->var.ranges.as<unsigned long long>() + n_reads;
     KvArgs a{};
     a.packed = (const uint64_t *)d_packed; a.invalid = (const uint64_t *)d_invalid; a.n_bases = n_bases; a.k = h->k;
     a.offs = (const int64_t *)d_read_offsets; a.n_reads = n_reads; a.ref_start = (const int64_t *)d_ref_start;
@@ -470,10 +470,10 @@ int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_i
     a.qual = min_baseq ? (const uint8_t *)d_qual : nullptr; a.n_qual = n_qual; a.qual_offs = (const int64_t *)d_qual_offsets; a.min_baseq = min_baseq;
     a.var_pos = (const int64_t *)d_var_pos; a.var_span = (const uint32_t *)d_var_span; a.var_ref_len = (const uint32_t *)d_var_ref_len; a.n_var = n_var;
     a.alt = (const uint8_t *)d_alt; a.n_alt = n_alt; a.alt_offs = (const int64_t *)d_alt_offsets;
-    a.pre = (const unsigned long long *)h->var_buf[0].p; a.cand_lo = cand_lo; a.cand_off = cand_off;
+    a.pre = h->var.cigar_pre.as<const unsigned long long>(); a.cand_lo = cand_lo; a.cand_off = cand_off;
     EvSpan p1(h->timer[T_VAR], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
     hipLaunchKernelGGL(kv_range_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, a.ref_start, a.cigar, n_cigar, a.cig_offs, a.var_pos,
-                       n_var, (unsigned long long *)h->var_buf[0].p, cand_lo, cand_off, sums);
+                       n_var, h->var.cigar_pre.as<unsigned long long>(), cand_lo, cand_off, sums);
     hipLaunchKernelGGL(kh_scan_kernel, dim3(1), dim3(256), 0, h->stream, sums, nbr);
     hipLaunchKernelGGL(kv_offsets_kernel, dim3((unsigned)nbr), dim3(256), 0, h->stream, n_reads, (const unsigned long long *)sums, cand_off);
     p1.stop();
@@ -483,11 +483,11 @@ int kdf_variant_windows_dev(kdf_engine *h, const void *d_packed, const void *d_i
     if (n_cand == 0) return KDF_OK;
     const uint64_t nbc = (n_cand + 255) / 256;
     if (nbc >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "kdf_variant_windows_dev: %llu (read, variant) candidates are beyond the 2^39 a call takes", (unsigned long long)n_cand);
-    if ((rc = eng_reserve(h, h->hit_buf[1], 2 * (nbc + 1) * 8, slack_8th, "block sums"))) return rc;
-    if ((rc = eng_reserve(h, h->var_buf[2], (size_t)n_cand * 5, slack_8th, "candidate counts"))) return rc;
-    sums = (unsigned long long *)h->hit_buf[1].p;
+    if ((rc = eng_reserve(h, h->hits.block_sums, 2 * (nbc + 1) * 8, slack_8th, "block sums"))) return rc;
+    if ((rc = eng_reserve(h, h->var.cand_counts, (size_t)n_cand * 5, slack_8th, "candidate counts"))) return rc;
+    sums = h->hits.block_sums.as<unsigned long long>();
     unsigned long long *sums_p = sums, *sums_e = sums + nbc + 1;
-    uint32_t *ent_cnt = (uint32_t *)h->var_buf[2].p;
+    uint32_t *ent_cnt = h->var.cand_counts.as<uint32_t>();
     uint8_t *cflags = (uint8_t *)(ent_cnt + n_cand);
     a.n_cand = n_cand;
     EvSpan p2(h->timer[T_VAR], h->prof, h->stream, 0);            // (the same call's later groups: time only)
@@ -591,8 +591,8 @@ int kdf_variant_evidence_dev(kdf_engine *h, const void *d_keys, const void *d_en
     if (!work) return KDF_OK;
     const uint32_t log2set = log2ceil(4 * n_entries);              // two words per entry at most, load <= 0.5
     int rc;
-    if ((rc = eng_reserve(h, h->hit_buf[3], (size_t)8 << log2set, slack_8th, "set of (variant, k-mer) pairs"))) return rc;
-    unsigned long long *set = (unsigned long long *)h->hit_buf[3].p;
+    if ((rc = eng_reserve(h, h->hits.pair_set, (size_t)8 << log2set, slack_8th, "set of (variant, k-mer) pairs"))) return rc;
+    unsigned long long *set = h->hits.pair_set.as<unsigned long long>();
     EvSpan p(h->timer[T_VAR], h->prof, h->stream, 1);
     HIPCHK(h, hipMemsetAsync(set, 0xFF, (size_t)8 << log2set, h->stream));
     by_words(h, [&](auto Wc) {
@@ -643,14 +643,14 @@ int kdf_cluster_intervals_dev(kdf_engine *h, const void *d_chrom, const void *d_
     StageLayout lay;
     const int ik = lay.add(un * 8), ia = lay.add(nb * sizeof(KrMax)), ifl = lay.add(un);
     int rc;
-    if ((rc = eng_reserve(h, h->reg_buf[0], lay.total, slack_8th, "interval scratch"))) return rc;
-    if ((rc = eng_reserve(h, h->reg_buf[1], un * 4, slack_8th, "interval order"))) return rc;
-    if ((rc = eng_reserve(h, h->hit_buf[1], (nb + 1) * 8, slack_8th, "block sums"))) return rc;
-    uint64_t *ckey = (uint64_t *)lay.at(h->reg_buf[0].p, ik);
-    KrMax *agg = (KrMax *)lay.at(h->reg_buf[0].p, ia);
-    uint8_t *flags = (uint8_t *)lay.at(h->reg_buf[0].p, ifl);
-    uint32_t *perm = (uint32_t *)h->reg_buf[1].p;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p;
+    if ((rc = eng_reserve(h, h->reg.scratch, lay.total, slack_8th, "interval scratch"))) return rc;
+    if ((rc = eng_reserve(h, h->reg.perm, un * 4, slack_8th, "interval order"))) return rc;
+    if ((rc = eng_reserve(h, h->hits.block_sums, (nb + 1) * 8, slack_8th, "block sums"))) return rc;
+    uint64_t *ckey = (uint64_t *)lay.at(h->reg.scratch.p, ik);
+    KrMax *agg = (KrMax *)lay.at(h->reg.scratch.p, ia);
+    uint8_t *flags = (uint8_t *)lay.at(h->reg.scratch.p, ifl);
+    uint32_t *perm = h->reg.perm.as<uint32_t>();
+    unsigned long long *sums = h->hits.block_sums.as<unsigned long long>();
     const int64_t *chrom = (const int64_t *)d_chrom, *start = (const int64_t *)d_start, *end = (const int64_t *)d_end;
     const unsigned blocks = (unsigned)nb;
     EvSpan p1(h->timer[T_REG], h->prof, h->stream, 1);            // (opens the call: counted as its pass)
@@ -722,10 +722,10 @@ int kdf_group_distinct_dev(kdf_engine *h, const void *d_group, const void *d_key
     HIPCHK(h, hipMemsetAsync(d_counts_out, 0, (size_t)n_groups * 8, h->stream));
     if (n == 0) return KDF_OK;
     int rc;
-    if ((rc = eng_reserve(h, h->reg_buf[0], n * 8, slack_8th, "group words"))) return rc;
-    if ((rc = eng_reserve(h, h->reg_buf[1], n * 4, slack_8th, "row order"))) return rc;
-    uint64_t *gkey = (uint64_t *)h->reg_buf[0].p;
-    uint32_t *perm = (uint32_t *)h->reg_buf[1].p;
+    if ((rc = eng_reserve(h, h->reg.scratch, n * 8, slack_8th, "group words"))) return rc;
+    if ((rc = eng_reserve(h, h->reg.perm, n * 4, slack_8th, "row order"))) return rc;
+    uint64_t *gkey = h->reg.scratch.as<uint64_t>();
+    uint32_t *perm = h->reg.perm.as<uint32_t>();
     const uint64_t *keys = (const uint64_t *)d_keys;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     EvSpan p(h->timer[T_REG], h->prof, h->stream, 1);

@@ -1,41 +1,14 @@
-// kdf_hostutil.h -- host plumbing the engine and the read spool share (no kernels): a grow-only device buffer, a HIP-event
-// timer with the stage stamps of the binned path, and the read-offsets check.  Each takes what differs between its users as a
-// parameter: the slack and the wait before a free (DevBuf), the tag of a timed span (EvTimer), where a message goes
-// (check_read_offsets).
+// kdf_hostutil.h -- host plumbing the engine and the read spool share (no kernels): the owning buffers and the grow-only
+// rule (kdf_devbuf.h), a HIP-event timer with the stage stamps of the binned path, and the read-offsets check.  Each takes
+// what differs between its users as a parameter: the slack and the wait before a free (dev_reserve), the tag of a timed
+// span (EvTimer), where a message goes (check_read_offsets).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
 #include <vector>
 
-// ---- grow-only device scratch ---------------------------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-};
-// what a site allocates for a request of b bytes
-static inline size_t slack_8th(size_t b) { return b + b / 8 + 4096; }
-static inline size_t slack_16th(size_t b) { return b + b / 16 + 4096; }
-static inline size_t slack_page(size_t b) { return b + 4096; }
-static inline size_t slack_exact(size_t b) { return b; }
-
-// Room for `bytes` in b.  A buffer that is too small is replaced by one of `want` bytes (>= bytes: the site's slack rule);
-// the old contents are not kept.  quiesce() -> hipError_t waits for whatever may still read the old buffer and is called
-// only when there is one to free; if it fails the buffer stays.  Returns quiesce's or hipMalloc's error (b is then empty).
-template <typename Q>
-static hipError_t dev_reserve(DevBuf &b, size_t bytes, size_t want, Q &&quiesce) {
-    if (b.bytes >= bytes) return hipSuccess;
-    if (b.p) {
-        const hipError_t e = quiesce();
-        if (e != hipSuccess) return e;
-        b.release();
-    }
-    const hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; return e; }
-    b.bytes = want;
-    return hipSuccess;
-}
+#include "kdf_devbuf.h"
 
 // ---- HIP-event timing -------------------------------------------------------------------------------------------------------
 // Pending (start, stop) event pairs with a 64-bit tag each, folded into running totals by collect(): `passes` counts the

@@ -141,8 +141,8 @@ int kdf_parse_kmer_fasta_dev(kdf_engine *h, const void *d_text, uint64_t n_bytes
     if (nb >= (1ull << 31)) return fail(h, KDF_ERR_INVALID, "%s: a chunk of %llu bytes is beyond the 2^43 a call takes", fn, (unsigned long long)n_bytes);
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
-    if ((rc = eng_reserve(h, h->hit_buf[1], (nb + 4) * 8, slack_8th, "block sums"))) return rc;
-    unsigned long long *sums = (unsigned long long *)h->hit_buf[1].p, *ctl = sums + nb + 1;   // sums[nb]: the total; then ctl[3]
+    if ((rc = eng_reserve(h, h->kf.block_sums, (nb + 4) * 8, slack_8th, "block sums"))) return rc;
+    unsigned long long *sums = h->kf.block_sums.as<unsigned long long>(), *ctl = sums + nb + 1;   // sums[nb]: the total; then ctl[3]
     const uint8_t *t = (const uint8_t *)d_text;
     EvSpan span(h->timer[T_KF], h->prof, h->stream, 1);
     hipLaunchKernelGGL(kf_ctl_init_kernel, dim3(1), dim3(1), 0, h->stream, ctl);

@@ -1,6 +1,6 @@
 // kdf_spool.hip -- libkdf.so, the read spool (kdf.h "read spool", kernels in kdf_spool.h): a sample's packed stream
 // kept resident and replayed.  An object of its own: it drives the engine through the public C API and, of the
-// engine's state (kdf_engine_priv.h), touches the device, the stream, the error text, the upload slots and sk_on only.
+// engine's state (kdf_engine_priv.h), touches the device, the stream, the error text, the upload slots and sk.on only.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdarg>
@@ -342,9 +342,9 @@ static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode) {
     const size_t ns = sp->segs.size();
     size_t next_host = ns;                                         // the host-tier segment whose upload comes next
     for (size_t i = 0; i < ns; ++i) if (sp->segs[i].host) { next_host = i; break; }
-    if (next_host < ns && (h->up_valid[0] || h->up_valid[1]))
+    if (next_host < ns && (h->up.slot[0].valid || h->up.slot[1].valid))
         return ks_fail(sp, KDF_ERR_STATE, "%s: host-tier segments go through the engine's upload slots, and slot %d holds a batch "
-                       "that was not counted", fn, h->up_valid[0] ? 0 : 1);
+                       "that was not counted", fn, h->up.slot[0].valid ? 0 : 1);
     KSCHK(sp, hipSetDevice(sp->device));
     if (sp->have_last) {
         KSCHK(sp, hipStreamWaitEvent(h->stream, sp->last, 0));
@@ -352,7 +352,7 @@ static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode) {
     }
     auto pass = [&](size_t i, int rc) {
         if (!rc) return KDF_OK;
-        h->up_valid[0] = h->up_valid[1] = false;                   // (both were free on entry: what they hold is the spool's)
+        h->up.slot[0].valid = h->up.slot[1].valid = false;                   // (both were free on entry: what they hold is the spool's)
         return ks_fail(sp, rc, "%s: segment %zu: %s", fn, i, h->err.c_str());
     };
     auto upload = [&](size_t i, int slot) {
@@ -373,7 +373,7 @@ static int spool_walk(kdf_spool *sp, kdf_engine *h, int mode) {
         size_t j = i + 1;
         while (j < ns && !sp->segs[j].host) ++j;
         if (j < ns && (rc = upload(j, slot ^ 1))) return pass(j, rc);   // its copy runs under this segment's count
-        if (mode == 3) { rc = kdf_sketch_add_uploaded(h, slot); h->up_valid[slot] = false; }   // (the sketch leaves a batch in its slot: this one is the spool's)
+        if (mode == 3) { rc = kdf_sketch_add_uploaded(h, slot); h->up.slot[slot].valid = false; }   // (the sketch leaves a batch in its slot: this one is the spool's)
         else rc = mode == 2 ? kdf_prefilter_add_uploaded(h, slot) : kdf_count_uploaded(h, slot, mode == 1);
         if (rc) return pass(i, rc);
         slot ^= 1;
@@ -664,7 +664,7 @@ int kdf_spool_replay(kdf_spool *sp, kdf_engine *h, int mode) {
 int kdf_spool_sketch(kdf_spool *sp, kdf_engine *h) {
     if (!sp) return ks_fail(nullptr, KDF_ERR_INVALID, "NULL spool");
     if (!h) return ks_fail(sp, KDF_ERR_INVALID, "kdf_spool_sketch: NULL engine");
-    if (!h->sk_on) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_sketch: no sketch is on (kdf_sketch_begin)");
+    if (!h->sk.on) return ks_fail(sp, KDF_ERR_STATE, "kdf_spool_sketch: no sketch is on (kdf_sketch_begin)");
     return spool_walk(sp, h, 3);
 }
 
