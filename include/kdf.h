@@ -1098,6 +1098,71 @@ int kdf_bamdev_decode_dev(kdf_engine *h, const void *d_comp, const void *d_block
                           void *d_packed, void *d_invalid, uint64_t cap_bases, void *d_offsets, uint64_t cap_reads,
                           uint64_t *n_bases, uint64_t *n_reads, uint32_t *sub_status);
 
+/* -------------------------------------------------- device FASTA feeder ---- */
+
+/* The FASTA leg with the parse on the device: the raw text of a (multi-)FASTA lies in HBM, kernels
+ * write the packed stream, the invalid mask and the record offsets in the layout kdf_reader_next produces for a FASTA
+ * file, and the host only moves bytes.  It serves the counting legs: sequence only, no record names.  The table is not
+ * touched and nothing is flushed: any engine, of any k, packs any FASTA.
+ *
+ * THE RULE, per byte (this is the specification; it is what kdf_reader_next does for a FASTA file):
+ *   - a line ends at '\n'; the file's end closes the last line.  All '\r' directly in front of the line's end are dropped.
+ *   - a line whose first byte is '>' is a header line, at any length.  Everything before the first header line is skipped.
+ *   - inside a record every remaining byte of a non-header line is ONE stream position: ACGTacgt valid with codes
+ *     0 .. 3, every other byte (a blank, a tab, an interior '\r', IUPAC codes, '>' away from a line start) an invalid
+ *     position with packed bits 0.
+ *   - every record is followed by one separator position (invalid, bits 0), emitted at the next header line's '>' or, on
+ *     the final chunk, at the end of the file.  A record without bases is a lone separator.
+ * The host reader differs from the rule in one place only: it reads a line longer than its 65 535-byte gzgets buffer in
+ * pieces, so a '\r' or '>' that falls exactly on a piece boundary is taken for a line end or a line start.  The rule
+ * above, not that artefact, is what these entry points implement.
+ *
+ * CHUNKS.  The whole-file stream S is the concatenation of the records' positions and separators; a call emits the
+ * slice of S that belongs to the bytes it consumes.  A call that is not the last consumes everything except a trailing
+ * run of '\r' (whether those are dropped depends on the next byte): *consumed says how much was taken and the caller
+ * hands the rest over again in front of the next chunk.  The final call consumes everything and emits the closing
+ * separator; the state's flags are 0 afterwards.  `state` (zero it before the first chunk) carries the three flags and
+ * the running totals of records (header lines) and of slice positions (carried positions are not counted again).  A
+ * non-empty chunk that is not the last and of which nothing is consumed (only '\r') is KDF_ERR_INVALID.  Lines have no
+ * length limit: an unwrapped chromosome on one line spans many chunks.  A chunk takes at most 2^31 bytes.
+ *
+ * CARRY.  With carry > 0, prev_n_bases > 0, both prev pointers given and the incoming state KDF_FA_IN_RECORD, the call
+ * first copies the last c = min(carry, prev_n_bases) positions of the previous stream (bits and mask bits) to positions
+ * [0, c) of the new one; the slice follows at position c.  The caller passes carry = k - 1: no window lies wholly inside
+ * k - 1 positions, so the batches of a file, counted one after another, hold exactly the valid windows of S, each once
+ * (copying across a separator is harmless for the same reason).  The prev buffers must not overlap the outputs: equal
+ * pointers are KDF_ERR_INVALID.  carry = 0 or NULL prev: a plain slice.
+ *
+ * OUTPUTS.  d_packed / d_invalid hold kdf_stream_words(cap_bases) words.  Every word below kdf_stream_words(*n_bases) is
+ * written -- positions at and past *n_bases are invalid in the mask and zero in the packed array, the guarantee of
+ * kdf_bamdev_decode_dev -- and nothing outside those words.  cap_bases >= n_bytes + carry + 1 always suffices.
+ * d_offsets may be NULL (cap_reads is ignored then); else it is int64[cap_reads + 1] and receives *n_reads + 1 entries:
+ * record r of the call occupies [off[r], off[r + 1]), with its separator when it has one; if the call begins inside a
+ * record, piece 0 starts at offset 0 and includes the carry; off[*n_reads] == *n_bases.  *n_reads is set without
+ * offsets too.  A stream that needs more than cap_bases, or more than cap_reads records when offsets are asked for, is
+ * KDF_ERR_INVALID: nothing is written and `state` is unchanged, as after every refusal.  n_bytes == 0 with final_chunk
+ * closes an open record; n_bytes == 0 without it is KDF_OK, emits nothing and writes nothing.
+ *
+ * WORK.  On the engine's stream, over tiles of KDF_FASTA_TILE_BYTES of text: a pass that summarises each tile (16-byte
+ * loads when the text is 16-byte aligned; any alignment works), one scan of the summaries, a pass over the same tiles
+ * that compacts codes and mask bits in LDS and stores whole 64-bit words (the partial words at a tile's edges by
+ * atomic OR into zeroed words), and a tail kernel for the carry and the words behind *n_bases.  The call synchronises
+ * once, because it learns the sizes.  The host form stages text, previous stream and outputs through the engine's
+ * staging arena.  Under kdf_profile(h, 1): stats "fastafeed_us" / "fastafeed_passes" (one pass per call that launches). */
+typedef struct { uint32_t flags; uint32_t reserved; uint64_t records; uint64_t positions; } kdf_fasta_state;
+#define KDF_FA_IN_RECORD 1u   /* a header line has been seen: sequence bytes emit positions */
+#define KDF_FA_MID_LINE  2u   /* the chunk does not begin at a line start */
+#define KDF_FA_IN_HEADER 4u   /* ... and that line is a header line */
+#define KDF_FASTA_TILE_BYTES 4096   /* text bytes per workgroup of the passes (tests aim at its multiples) */
+int kdf_fasta_pack_dev(kdf_engine *h, const void *d_text, uint64_t n_bytes, int final_chunk, kdf_fasta_state *state,
+                       const void *d_prev_packed, const void *d_prev_invalid, uint64_t prev_n_bases, uint32_t carry,
+                       void *d_packed, void *d_invalid, uint64_t cap_bases, void *d_offsets, uint64_t cap_reads,
+                       uint64_t *n_bases, uint64_t *n_reads, uint64_t *consumed);
+int kdf_fasta_pack(kdf_engine *h, const uint8_t *text, uint64_t n_bytes, int final_chunk, kdf_fasta_state *state,
+                   const uint64_t *prev_packed, const uint64_t *prev_invalid, uint64_t prev_n_bases, uint32_t carry,
+                   uint64_t *packed, uint64_t *invalid, uint64_t cap_bases, int64_t *offsets, uint64_t cap_reads,
+                   uint64_t *n_bases, uint64_t *n_reads, uint64_t *consumed);
+
 /* N4: the informative-reads BAM (discovery/pipeline.py:1979-2079 `_write_informative_reads_discovery`,
  * vcf/pipeline.py:1307-1357 `_write_informative_reads`: pysam write + `samtools sort` + `samtools index`).
  * Copies the records ordinals[0..n) (strictly ascending file record numbers, see

@@ -195,7 +195,23 @@ SYMBOLS = [
     ("kdf_bgzf_inflate_dev", c_int, [_P, _P, _P, c_uint64, _P, c_uint64, _P]),
     ("kdf_bamdev_decode_dev", c_int, [_P, _P, _P, c_uint64, _P, c_uint64, c_uint32, c_int, _P, _P, c_uint64, _P, c_uint64,
                                       POINTER(c_uint64), POINTER(c_uint64), _P]),
+    # device FASTA feeder (the state: FastaState below)
+    ("kdf_fasta_pack_dev", c_int, [_P, _P, c_uint64, c_int, _P, _P, _P, c_uint64, c_uint32, _P, _P, c_uint64, _P, c_uint64,
+                                   POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    ("kdf_fasta_pack", c_int, [_P, _P, c_uint64, c_int, _P, _P, _P, c_uint64, c_uint32, _P, _P, c_uint64, _P, c_uint64,
+                               POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
 ]
+
+KDF_FA_IN_RECORD, KDF_FA_MID_LINE, KDF_FA_IN_HEADER = 1, 2, 4
+KDF_FASTA_TILE_BYTES = 4096
+
+
+class FastaState(ctypes.Structure):
+    """kdf_fasta_state: what the device FASTA feeder carries from chunk to chunk (all zero before the first)."""
+    _fields_ = [("flags", c_uint32), ("reserved", c_uint32), ("records", c_uint64), ("positions", c_uint64)]
+
+    def copy(self) -> "FastaState":
+        return FastaState(self.flags, self.reserved, self.records, self.positions)
 
 _lib = None
 

@@ -239,11 +239,26 @@ def _merge_filter_counts(eng, lo, hi, dlo=None, dhi=None):
     eng.synchronize()
 
 
+LAST_FASTA_FEEDER = None      # the feeder of the last FASTA count: {"path": "host"} or stream_fasta_device's record
+
+
 def _count_fasta_to_index(fasta_path, kmer_size, out_path, capacity_hint, cmdline):
+    global LAST_FASTA_FEEDER
+    device_feeder = os.environ.get("KDF_DEVICE_FASTA_FEEDER", "0") not in ("", "0")
+    if device_feeder and dist_env.world_rank()[0] > 1:
+        logger.info("  KDF_DEVICE_FASTA_FEEDER is ignored under several ranks (the FASTA is not sharded): host reader")
+        device_feeder = False
     with mirror_engine(kmer_size, capacity_hint=capacity_hint) as eng:
-        with fasta_reader(fasta_path, kmer_size, max_bases=BATCH_BASES) as rd:
-            for batch in rd:
-                eng.count(batch)
+        if device_feeder:
+            # opt-in: the text goes to HBM as it is and kernels pack it (reads.stream_fasta_device); the same windows
+            from .. import reads
+            reads.stream_fasta_device(eng, os.fspath(fasta_path), kmer_size)
+            LAST_FASTA_FEEDER = reads.LAST_FASTA_FEEDER
+        else:
+            LAST_FASTA_FEEDER = {"path": "host"}
+            with fasta_reader(fasta_path, kmer_size, max_bases=BATCH_BASES) as rd:
+                for batch in rd:
+                    eng.count(batch)
         lo, hi, cnt = eng.export_ge(0)
     jf_io.write_index_auto(out_path, kmer_size, lo, hi, cnt, cmdline=cmdline)    # (KDF_JF_FORMAT=jellyfish: a real binary/sorted file)
     return len(lo)

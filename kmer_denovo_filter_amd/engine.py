@@ -432,6 +432,44 @@ class KmerEngine:
                                                  c_void_p(d_offsets), int(cap_reads), byref(nb), byref(nr), _vp(status)))
         return nb.value, nr.value, status[:int(n_sub)]
 
+    # -- device FASTA feeder -------------------------------------------------
+    def fasta_pack_dev(self, d_text: Optional[int], n_bytes: int, final_chunk: bool, state: "_native.FastaState", d_packed: int,
+                       d_invalid: int, cap_bases: int, d_offsets: Optional[int] = None, cap_reads: int = 0,
+                       d_prev_packed: Optional[int] = None, d_prev_invalid: Optional[int] = None, prev_n_bases: int = 0,
+                       carry: int = 0) -> Tuple[int, int, int]:
+        """One chunk of raw FASTA text in HBM -> the slice of the file's packed stream that belongs to the bytes the call
+        consumes, in caller-owned HBM (buffers of the ``stream_words(cap_bases)`` sizes; ``d_offsets``: int64[cap_reads +
+        1] or None), behind the last ``min(carry, prev_n_bases)`` positions of the previous stream when the chunk begins
+        inside a record (``carry = k - 1``).  ``state``: a ``FastaState``, zero before the first chunk, updated by the
+        call.  -> (n_bases, n_reads, consumed): a chunk that is not the last leaves a trailing run of '\\r' to the
+        caller.  Synchronises once; the table is not touched."""
+        p = lambda x: c_void_p(x) if x else None
+        nb, nr, used = c_uint64(0), c_uint64(0), c_uint64(0)
+        self._ck(self._lib.kdf_fasta_pack_dev(self._h, p(d_text), int(n_bytes), int(bool(final_chunk)), byref(state), p(d_prev_packed),
+                                              p(d_prev_invalid), int(prev_n_bases), int(carry), p(d_packed), p(d_invalid), int(cap_bases),
+                                              p(d_offsets), int(cap_reads), byref(nb), byref(nr), byref(used)))
+        return nb.value, nr.value, used.value
+
+    def fasta_pack(self, text, final_chunk: bool, state: "_native.FastaState", prev: Optional[ReadStream] = None, carry: int = 0,
+                   want_offsets: bool = True) -> Tuple[ReadStream, int]:
+        """The same from host bytes to a host ``ReadStream`` (offsets: the call's records, piece 0 with the carry),
+        staged through the engine.  -> (stream, consumed)."""
+        raw = np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+        n = len(raw)
+        cap_bases = n + int(carry) + 1
+        cap_reads = n // 2 + 2
+        pw, mw = stream_words(cap_bases)
+        packed, invalid = np.zeros(pw, np.uint64), np.zeros(mw, np.uint64)
+        offs = np.zeros(cap_reads + 1, np.int64) if want_offsets else None
+        nb, nr, used = c_uint64(0), c_uint64(0), c_uint64(0)
+        self._ck(self._lib.kdf_fasta_pack(self._h, _vp(raw) if n else None, n, int(bool(final_chunk)), byref(state),
+                                          _vp(prev.packed) if prev is not None else None, _vp(prev.invalid) if prev is not None else None,
+                                          prev.n_bases if prev is not None else 0, int(carry), _vp(packed), _vp(invalid), cap_bases,
+                                          _vp(offs), cap_reads if want_offsets else 0, byref(nb), byref(nr), byref(used)))
+        pw, mw = stream_words(nb.value)
+        offsets = offs[:nr.value + 1].copy() if want_offsets else np.array([0, nb.value], np.int64)
+        return ReadStream(packed[:pw].copy(), invalid[:mw].copy(), nb.value, offsets), used.value
+
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
         if self.long:

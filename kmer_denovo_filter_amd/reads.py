@@ -764,6 +764,213 @@ def stream_bam_device(engine, path: str, parts_of_this_process, filtered: bool =
     return n_reads
 
 
+LAST_FASTA_FEEDER = None      # what the last stream_fasta_device call did: {"path", "chunks", "bytes", "carries", "compressed", "records"}
+
+
+class _FastaText:
+    """The text of a FASTA file, chunk by chunk into caller buffers: a plain file is read in place, a gzip or BGZF file
+    (found by its magic) is inflated with zlib, member after member."""
+
+    def __init__(self, path: str):
+        self.f = open(path, "rb", buffering=0)
+        magic = self.f.read(2)
+        self.f.seek(0)
+        self.compressed = magic == b"\x1f\x8b"
+        self._z, self._pending = None, b""
+
+    def close(self):
+        self.f.close()
+
+    def readinto(self, buf: np.ndarray) -> int:
+        """Fill ``buf`` (uint8) from its start -> bytes written; fewer than len(buf) only at the file's end."""
+        if not self.compressed:
+            view, n = memoryview(buf), 0
+            while n < len(buf):
+                got = self.f.readinto(view[n:])
+                if not got:
+                    break
+                n += got
+            return n
+        import zlib
+        n = 0
+        while n < len(buf):
+            if self._z is None:                                        # the next member, if the file has one
+                if not self._pending:
+                    self._pending = self.f.read(1 << 20)
+                    if not self._pending:
+                        break
+                self._z = zlib.decompressobj(31)
+            data = self._pending or self.f.read(1 << 20)
+            if not data:
+                raise OSError("compressed FASTA ends inside a gzip member")
+            out = self._z.decompress(data, len(buf) - n)
+            buf[n:n + len(out)] = np.frombuffer(out, np.uint8)
+            n += len(out)
+            if self._z.eof:
+                self._pending, self._z = self._z.unused_data, None
+            else:
+                self._pending = self._z.unconsumed_tail              # (what the output limit kept it from taking)
+        return n
+
+
+def stream_fasta_device(engine, path: str, k: int, filtered: bool = False, tally: bool = False, sketch: bool = False, spool=None,
+                        chunk_bytes: Optional[int] = None) -> int:
+    """Count (``filtered``: count --if; ``tally``: prefilter pass 1; ``sketch``: sizing pass) a (multi-)FASTA through the
+    DEVICE feeder: one reader thread fills two page-locked buffers with the file's text (``chunk_bytes`` each; default
+    KDF_FASTA_FEED_MB MiB, 64), a copy stream uploads chunk i + 1 while the engine packs chunk i on the device
+    (``fasta_pack_dev``) into one of two alternating stream buffers, behind the last k - 1 positions of the other, and
+    takes the stream where it lies in HBM.  The batches hold every valid window of the file's stream exactly once.  A
+    gzip or BGZF file is inflated on the host into the same buffers.  ``spool``: as in ``stream_bam_device``.  For the
+    call's duration the engine runs on a stream of the feeder's.  Returns the number of records; ``LAST_FASTA_FEEDER``
+    records chunks, bytes and carries."""
+    global LAST_FASTA_FEEDER
+    import os
+    import queue
+    import threading
+    import torch
+    if chunk_bytes is None:
+        chunk_bytes = int(float(os.environ.get("KDF_FASTA_FEED_MB", "64")) * (1 << 20))
+    src = _FastaText(path)
+    if not src.compressed:                                       # a small file (proband_unique.fa) pins and allocates no more than it needs
+        chunk_bytes = min(int(chunk_bytes), os.path.getsize(path) + 16)
+    chunk_bytes = max(16, int(chunk_bytes) // 16 * 16)
+    carry = max(int(k) - 1, 0)
+    dev = torch.device("cuda", engine.device)
+    pinned = _pinned_bytes(2, chunk_bytes)
+    free, ready = queue.Queue(), queue.Queue()
+    free.put(0)
+    free.put(1)
+    stop = threading.Event()
+
+    def produce():
+        try:
+            while not stop.is_set():
+                i = free.get()
+                if i is None:
+                    return
+                n = src.readinto(pinned.buffers[i])
+                if n == 0:
+                    break
+                ready.put((i, n))
+            ready.put(None)
+        except BaseException as ex:  # noqa: BLE001 -- handed to the consumer
+            ready.put(ex)
+
+    reader = threading.Thread(target=produce, name="kdf-fasta-text", daemon=True)
+    work, copy_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    engine.synchronize()
+    engine.set_stream(work.cuda_stream)
+    info = {"path": "device", "chunks": 0, "bytes": 0, "carries": 0, "compressed": src.compressed}
+    state = _native.FastaState()
+    spooling = [spool]
+    keep_reads = bool(getattr(spool, "keep_reads", False))
+    text = [torch.empty(chunk_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+    used = [None, None]                                          # recorded on the work stream behind the pack that read the text slot
+    out = [None, None]                                           # (packed, invalid, offsets, cap_bases, cap_reads) of the alternating stream buffers
+    prev = [None]                                                # (slot, n_bases) of the previous stream
+    left = [0]                                                   # trailing '\r' of the previous chunk, handed over again
+
+    def room(j, n_text):
+        cap_bases, cap_reads = n_text + carry + 1, (n_text // 2 + 2 if keep_reads else 0)
+        if out[j] is None or out[j][3] < cap_bases or out[j][4] < cap_reads:
+            pw, mw = stream_words(cap_bases)
+            torch.cuda.current_stream(dev).synchronize()          # (memory the allocator hands out again may still be in use on this stream)
+            out[j] = (torch.empty(pw, dtype=torch.int64, device=dev), torch.empty(mw, dtype=torch.int64, device=dev),
+                      torch.empty(cap_reads + 1, dtype=torch.int64, device=dev) if keep_reads else None, cap_bases, cap_reads)
+        return out[j]
+
+    def pack(t, n_text, final):
+        """pack t[:n_text] into the stream buffer the previous stream does not lie in, hand it to the engine -> consumed"""
+        j = 0 if prev[0] is None else prev[0][0] ^ 1
+        packed, invalid, offs, cap_bases, cap_reads = room(j, n_text)
+        pp = (out[prev[0][0]][0].data_ptr(), out[prev[0][0]][1].data_ptr(), prev[0][1]) if prev[0] is not None else (None, None, 0)
+        in_record = bool(state.flags & _native.KDF_FA_IN_RECORD)
+        nb, nr, consumed = engine.fasta_pack_dev(t.data_ptr() if n_text else None, n_text, final, state, packed.data_ptr(), invalid.data_ptr(),
+                                                 cap_bases, offs.data_ptr() if offs is not None else None, cap_reads, pp[0], pp[1], pp[2], carry)
+        if n_text == 0 and not final:
+            return 0
+        info["carries"] += 1 if (in_record and carry and pp[2]) else 0
+        prev[0] = (j, nb)
+        if nb:
+            dp, dm = packed.data_ptr(), invalid.data_ptr()
+            if spooling[0] is not None:
+                try:
+                    if keep_reads:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream, d_offsets=offs.data_ptr(), n_reads=nr)
+                    else:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream)
+                except _native.KdfError as ex:
+                    if ex.code != _native.KDF_ERR_NOMEM:
+                        raise
+                    spooling[0] = None                               # overflowed: the pass itself goes on
+            if sketch:
+                engine.sketch_add_dev(dp, dm, nb)
+            elif tally:
+                engine.prefilter_add_dev(dp, dm, nb)
+            elif filtered:
+                engine.count_filtered_dev(dp, dm, nb)
+            else:
+                engine.count_dev(dp, dm, nb)
+        return consumed
+
+    def cr_run(n):
+        return torch.full((n,), 13, dtype=torch.uint8, device=dev)
+
+    try:
+        reader.start()
+        pending, cur = None, 0                                       # pending: (text slot, pinned index, bytes, copied event)
+        with torch.cuda.stream(work):
+            def finish(p):
+                slot, i, n, copied = p
+                copied.synchronize()
+                free.put(i)                                          # the copy is done: the pinned buffer goes back to the reader
+                work.wait_event(copied)
+                t, n_text = text[slot], n
+                if left[0]:                                          # the '\r' the last chunk left, in front of this one
+                    t, n_text = torch.cat((cr_run(left[0]), text[slot][:n])), n + left[0]
+                consumed = pack(t, n_text, False)
+                left[0] = n_text - consumed
+                used[slot] = torch.cuda.Event()
+                used[slot].record(work)
+                info["chunks"] += 1
+                info["bytes"] += n
+            while True:
+                item = ready.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                i, n = item
+                with torch.cuda.stream(copy_stream):
+                    if used[cur] is not None:
+                        copy_stream.wait_event(used[cur])            # the pack that read this slot's last chunk
+                    text[cur][:n].copy_(torch.from_numpy(pinned.buffers[i][:n]), non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(copy_stream)
+                if pending is not None:
+                    finish(pending)
+                pending = (cur, i, n, copied)
+                cur ^= 1
+            if pending is not None:
+                finish(pending)
+            pack(cr_run(left[0]) if left[0] else text[0], left[0], True)     # the file's end: the closing separator
+    finally:
+        stop.set()
+        free.put(None)
+        if reader.ident is not None:
+            reader.join()
+        try:
+            engine.synchronize()
+        finally:
+            engine.set_stream(None)
+            copy_stream.synchronize()                                # no copy may still read a pinned buffer the next caller will fill
+            src.close()
+    info["records"] = int(state.records)
+    info["positions"] = int(state.positions)
+    LAST_FASTA_FEEDER = info
+    return int(state.records)
+
+
 def write_bam_subset(src_bam: str, dst_bam: str, ordinals, aux_fields=None, sort_and_index: bool = True,
                      threads: int = 1) -> int:
     """Copy the records ``ordinals`` (ReadStream.ordinals values) of ``src_bam`` into
