@@ -113,7 +113,10 @@ int kdf_stats(kdf_engine *h, uint64_t *capacity, uint64_t *distinct, uint64_t *w
  * kdf_read_depth*, kdf_add_pairs*, kdf_reserve, kdf_set_option
  * -- or when the pending work fills its budget, so that a sample streamed in hundreds of batches pays the table rewrite of the binned pipeline
  * once per flush, not once per batch (`jellyfish count` over the whole `samtools fasta` pipe,
- * discovery/pipeline.py:106-172).  kdf_flush applies everything pending now; errors of deferred work (a table that
+ * discovery/pipeline.py:106-172).  Such a call runs in stream order and does not synchronise.  A count that goes through
+ * the direct kernels is not deferred -- option force_path 1, every long engine, an owner table (hash_shift), a table of a
+ * single bucket -- and it SYNCHRONISES the engine's stream after every chunk it inserts: the host must learn the number
+ * of distinct keys to grow the table before the next chunk.  kdf_flush applies everything pending now; errors of deferred work (a table that
  * cannot grow ...) surface there or in the call that triggered the flush.  kdf_clear drops pending work. */
 int kdf_flush(kdf_engine *h);
 
@@ -207,7 +210,10 @@ int kdf_count_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *inval
 /* Same with the stream already resident in HBM (device pointers to buffers of the kdf_stream_words(n_bases) sizes).
  * The words at and past n_bases may hold anything ("Read streams", points 1-2): the last k - 1 positions before
  * n_bases start no window, on every path (pending stream, direct, binned, key_parts, long keys), so a batch small
- * enough to wait in the pending stream and one that is partitioned where it lies give the same table. */
+ * enough to wait in the pending stream and one that is partitioned where it lies give the same table.
+ * Ordering: the deferred forms run in stream order and do not synchronise; whatever is deferred never reads the caller's
+ * buffers after the call has returned in stream order (the pending stream is a copy, a batch partitioned where it lies is
+ * partitioned by the call).  Through the direct kernels the call synchronises (see "Count calls ... are DEFERRED"). */
 int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid,
                         uint64_t n_bases);
 
@@ -222,7 +228,11 @@ int kdf_count_reads_dev(kdf_engine *h, const void *d_packed, const void *d_inval
  * count --if without a filter or under force_path 4 without a sieve) leaves the batch in the slot.  An empty batch
  * (n_bases = 0) asks nothing of the sieve, here as in kdf_count_reads_filtered*: it is KDF_OK under force_path 4 too.  kdf_clear,
  * kdf_load_filter* and kdf_set_stream do not touch the slots: a batch uploaded before kdf_set_stream is counted on the new
- * stream, after its copy. */
+ * stream, after its copy.
+ * Ordering: kdf_count_uploaded waits ON THE HOST for the slot's copy (that is what frees the batch's host arrays) and makes
+ * the engine's stream wait for it; it does not synchronise the engine's stream unless the count itself does (direct
+ * kernels, see "Count calls ... are DEFERRED").  A copy into a slot waits, on the copy stream, for the slot's last reader:
+ * a count of the slot's NEXT batch therefore returns only when the count of the batch before has run. */
 int kdf_host_alloc(uint64_t bytes, void **out);
 int kdf_host_free(void *p);
 int kdf_upload_reads_async(kdf_engine *h, int slot, const uint64_t *packed, const uint64_t *invalid,
@@ -237,7 +247,9 @@ int kdf_count_uploaded(kdf_engine *h, int slot, int filtered);
  * 2^32 - 1.  Works in insert and in filter mode, is never gated by key_parts or an armed prefilter, and leaves `windows`
  * alone.  Keys added while a filter is loaded are filter keys like the others (kdf_count_reads_filtered* counts them on
  * every path); the filter's sieve does not know them, so option force_path 4 is KDF_ERR_STATE from then on, until
- * kdf_scan_reads* has rebuilt the sieve from the table or a filter is loaded again. */
+ * kdf_scan_reads* has rebuilt the sieve from the table or a filter is loaded again.
+ * The _dev forms (kdf_add_pairs_multi_dev and the _w form too) read the caller's arrays in stream order and SYNCHRONISE
+ * the engine's stream: the host learns the new number of distinct keys and whether a bucket overflowed. */
 int kdf_add_pairs(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi,
                   const uint32_t *counts, uint64_t n);
 int kdf_add_pairs_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi,
@@ -303,7 +315,8 @@ int kdf_add_pairs_multi_dev(kdf_engine *h, uint32_t nseg, const void *const *d_k
 int kdf_prefilter_begin(kdf_engine *h, uint32_t min_count, uint32_t log2_cells);
 /* Tally one batch of the read stream (host buffers / device buffers of the kdf_stream_words(n_bases) sizes / the batch
  * an upload slot holds, kdf_upload_reads_async).  The stream is read exactly as the count reads it ("Read streams":
- * positions at or past n_bases are invalid whatever the buffers hold). */
+ * positions at or past n_bases are invalid whatever the buffers hold).  The _dev and the uploaded form run in stream order
+ * and do not synchronise the engine's stream (the uploaded form waits on the host for the slot's copy, as a count does). */
 int kdf_prefilter_add_reads(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases);
 int kdf_prefilter_add_reads_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases);
 int kdf_prefilter_add_uploaded(kdf_engine *h, int slot);
@@ -349,7 +362,8 @@ int kdf_load_filter(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys
                     uint64_t n);
 /* The same with the keys already resident in HBM (device pointers): the hand-off between the discovery stages
  * (child candidates -> reference subtraction -> parent filter, discovery/pipeline.py:207-226,286-304,515-532)
- * without a host round trip. */
+ * without a host round trip.  Reads the keys in stream order and SYNCHRONISES the engine's stream (table size, bucket
+ * overflow); the _w form does the same. */
 int kdf_load_filter_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, uint64_t n);
 /* Zero every count, keep the keys (and the filter mode): the same filter counted against the next parent
  * (discovery/pipeline.py:462-612 builds a fresh --if table per parent).  `windows` reads 0 and pending count --if work is
@@ -365,7 +379,8 @@ int kdf_reset_counts(kdf_engine *h);
 int kdf_count_reads_filtered(kdf_engine *h, const uint64_t *packed,
                              const uint64_t *invalid, uint64_t n_bases);
 /* (device form: buffers of the kdf_stream_words(n_bases) sizes whose words at and past n_bases may hold anything,
- * "Read streams" points 1-2 -- through the sieve, the binned pipeline and the direct kernel alike) */
+ * "Read streams" points 1-2 -- through the sieve, the binned pipeline and the direct kernel alike; nothing is inserted, so
+ * the host has nothing to learn: stream order on every path, does not synchronise) */
 int kdf_count_reads_filtered_dev(kdf_engine *h, const void *d_packed,
                                  const void *d_invalid, uint64_t n_bases);
 
@@ -377,7 +392,8 @@ int kdf_count_reads_filtered_dev(kdf_engine *h, const void *d_packed,
 int kdf_query(kdf_engine *h, const uint64_t *keys_lo, const uint64_t *keys_hi,
               uint64_t n, uint32_t *counts_out);
 /* device-pointer form: d_counts_out can be a torch tensor that is then
- * all-reduced over RCCL (multi-GPU merge of per-rank filter counts). */
+ * all-reduced over RCCL (multi-GPU merge of per-rank filter counts).  Stream order on the engine's stream; does not
+ * synchronise once pending count work is applied (the _w form too). */
 int kdf_query_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi,
                   uint64_t n, void *d_counts_out);
 
@@ -492,7 +508,8 @@ int kdf_export_parts_packed_dev(kdf_engine *h, uint32_t min_count, uint32_t part
 
 /* The count of every listed key becomes counts[i] (device pointers; every key must be stored: KDF_ERR_INVALID
  * otherwise).  How the sum of the ranks' `count --if` tallies goes back into each rank's table after the all-reduce
- * (kmer_denovo_filter_amd/distributed.py; the reference's parent scan is one process, discovery/pipeline.py:377-443). */
+ * (kmer_denovo_filter_amd/distributed.py; the reference's parent scan is one process, discovery/pipeline.py:377-443).
+ * Reads keys and counts in stream order and SYNCHRONISES the engine's stream: the host learns whether a key was missing. */
 int kdf_set_counts_dev(kdf_engine *h, const void *d_keys_lo, const void *d_keys_hi, const void *d_counts, uint64_t n);
 
 /* ------------------------------------------------------ Module-3 scan ---- */
@@ -909,7 +926,8 @@ int kdf_window_counts(kdf_engine *h, const uint64_t *packed, const uint64_t *inv
  * the host and device forms.
  * Host form: n_reads < 0, a negative offset or offsets that decrease are KDF_ERR_INVALID before any device work.
  * Device form: the offsets are a precondition, but whatever they hold no write lands outside the n_reads rows.
- * n_reads == 0 is KDF_OK.  Same widths, modes, tables and single-GPU note as kdf_window_counts. */
+ * n_reads == 0 is KDF_OK.  Same widths, modes, tables and single-GPU note as kdf_window_counts; the device form runs in
+ * stream order and does not synchronise either. */
 int kdf_read_depth_dev(kdf_engine *h, const void *d_packed, const void *d_invalid, uint64_t n_bases,
                        const void *d_read_offsets, int64_t n_reads, uint32_t low_max, void *d_rows_out);
 int kdf_read_depth(kdf_engine *h, const uint64_t *packed, const uint64_t *invalid, uint64_t n_bases,
@@ -1261,7 +1279,8 @@ int kdf_set_counts_w_dev(kdf_engine *h, const void *d_keys, const void *d_counts
  * kdf_spool_append_uploaded on the engine's stream, behind the slot's copy, and the slot KEEPS its batch: the caller
  * then counts or tallies it as before.  kdf_spool_append (host arrays) returns when the arrays may be reused.  Every
  * append is ordered behind the one before it, whatever streams they ran on, and the spool records an event behind each.
- * kdf_spool_replay makes the engine's stream wait for the last such event -- no host synchronisation for the HBM tier --
+ * kdf_spool_replay makes the engine's stream wait for the last such event -- no host synchronisation of its own for the HBM
+ * tier: the replay is as synchronous as the entry point it calls (a count through the direct kernels synchronises) --
  * and calls, for every segment in order, kdf_count_reads_dev (mode 0), kdf_count_reads_filtered_dev (mode 1) or
  * kdf_prefilter_add_reads_dev (mode 2).  Host-tier segments go through the engine's two upload slots
  * (kdf_upload_reads_async, then kdf_count_uploaded / kdf_prefilter_add_uploaded): the copy of the next host-tier segment

@@ -71,6 +71,7 @@ def call(eng, text, final, state, prev=None, carry=0, shift=0, cap_bases=None, c
     invalid = torch.full((mw + GUARD_WORDS,), fill, dtype=torch.int64, device="cuda")
     offs = torch.full((cap_reads + 1 + GUARD_WORDS,), fill, dtype=torch.int64, device="cuda")
     ptr, keep = dev_text(text, shift)
+    torch.cuda.synchronize()                                 # (torch filled the buffers on ITS stream; the engine launches on its own)
     before = state.copy()
     o = Out()
     o.error = None
