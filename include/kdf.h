@@ -891,6 +891,80 @@ int kdf_parse_kmer_fasta(kdf_engine *h, const uint8_t *text, uint64_t n_bytes, i
                          uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n_out, uint64_t *consumed_out,
                          uint64_t *bad_offset_out);
 
+/* ------------------------------------------------------ index record codec ---- */
+
+/* The records of the index files the stages hand on ({ref}.k{k}.jf, proband_unique.jf, merged chunks: "kdf/sorted" and
+ * Jellyfish's "binary/sorted"), made from keys and counts in device memory and read back into them there.  A record is
+ * kb = ceil(2k / 8) little-endian key bytes followed by counter_len little-endian count bytes.  The key form follows the
+ * call's k, not the engine's, as in the k-mer FASTA codec:
+ *     k 1 .. 32        lo[n]
+ *     k 33 .. 63       lo[n] and hi[n]
+ *     odd k 65 .. 201  n x W uint64 rows (W = kdf_key_words(k)) in the lo position, hi NULL
+ * Any other k is KDF_ERR_INVALID.  The table is not touched: no flush, any engine.
+ *
+ * Each entry point is ONE function with a `mem` argument in place of a host / device pair: with KDF_MEM_HOST the array
+ * arguments are host pointers, staged through the engine's staging arena as the other host forms do (the call
+ * synchronises); with KDF_MEM_DEVICE they are device pointers, used in place in stream order on the engine's stream.
+ * Any other mem is KDF_ERR_INVALID.  `columns` and the scalar results are host memory with both.  With KDF_MEM_HOST an
+ * encode call stages all n keys, counts and perm values whatever its window, so a caller that cuts a large body into
+ * windows keeps its keys in device memory.
+ *
+ * kdf_index_record_bytes: kb + counter_len, a pure host function (no engine, no GPU); 0 for a k outside the above or a
+ * counter_len outside 1 .. 16.
+ *
+ * Encode (4-byte counters: what this package writes).
+ *   - record e of the body is the kb key bytes of key (perm ? perm[e] : e) and the 4 bytes of its count; with
+ *     R = kb + 4 it begins at byte e * R.  perm is uint32[n] (values below n: a precondition), counts uint32[n]; a NULL
+ *     counts writes count 0.
+ *   - a call writes bytes [byte_first, byte_first + byte_count) of the body to bytes_out[0 .. byte_count) and nothing
+ *     else; the window may begin and end inside a record, so a body of any size goes through one bounded buffer.
+ *     bytes_out may have any alignment.
+ *   - byte_first % 16 != 0, a window that passes n * R, n * R >= 2^63 and, with perm, n >= 2^32 are KDF_ERR_INVALID,
+ *     and nothing is written.  byte_count == 0 and n == 0 are KDF_OK.  A window takes fewer than 2^43 bytes.
+ *   - work: one kernel.  A lane owns 16 consecutive output bytes, finds the record of its first byte with one
+ *     multiply-high in place of the division, walks its 16 bytes and stores them at once (byte stores: the window's
+ *     last partial 16 bytes, and every byte when bytes_out is not 16-byte aligned).  The keys and counts of a
+ *     workgroup's 4 KiB of body are staged in LDS, gathered through perm when given.
+ *   - device memory: stream order, no synchronisation.
+ *
+ * Decode.
+ *   - bytes holds n whole records of kb + counter_len bytes at any alignment.  The key is the kb bytes little-endian,
+ *     zero-extended to the key form's words; the count is the first min(counter_len, 8) bytes little-endian, saturated
+ *     at 2^32 - 1, and 2^32 - 1 as well when any byte past the eighth is non-zero (the rule of jf_io._decode).
+ *   - hi may be NULL for k <= 32 (given, it is filled with zeros) and is ignored for k > 63; counts may be NULL.
+ *   - a record whose key has a bit at or above 2k returns KDF_ERR_IO: *bad_record_out (may be NULL; ~0 when none) is
+ *     the index of the first such record, the same from run to run.  The rows are still written as read.
+ *   - loads touch only the aligned 16-byte words that enclose the first and the last byte of bytes; nothing is stored
+ *     outside lo / hi / counts[0 .. n).  n == 0 is KDF_OK.  A call takes fewer than 2^39 records.
+ *   - work: one kernel.  A workgroup stages the 16-byte words that enclose 256 records in LDS, a lane assembles one
+ *     record's key words and count from there; rows of long keys leave through LDS in whole lines; the first bad record
+ *     is one atomic minimum per workgroup.
+ *   - the call synchronises the engine's stream with both memory kinds: the caller learns the bad record.
+ *
+ * Jellyfish's order (k <= 63 only; any other k is KDF_ERR_INVALID).  columns is a HOST array of 2k words with both
+ * memory kinds (the header's matrix1.columns), size a power of two (else KDF_ERR_INVALID).
+ *   - kdf_jf_positions: pos_out[i] (uint64) is the XOR of columns[j] over the set bits 2k - 1 - j of key i, ANDed with
+ *     size - 1.  Work: one kernel; a workgroup builds one table of 256 words per key byte in LDS from the columns, a
+ *     position is then the XOR of kb table reads.  Device memory: stream order, no synchronisation.
+ *   - kdf_jf_order: perm_out (uint32[n]) is the permutation that puts the keys in ascending (position, key) order --
+ *     the record order of a binary/sorted file; equal (position, key) pairs keep their input order.  The positions go
+ *     to scratch the engine owns (8 bytes per key), the order is the library radix sort over the key words and the
+ *     position.  n >= 2^32 is KDF_ERR_INVALID.  The call synchronises the engine's stream (the sort).
+ *
+ * Under kdf_profile(h, 1) the kernels of all four are timed with HIP events: stats "indexcodec_us" /
+ * "indexcodec_passes" (one pass per timed span: a kernel, and the sort of kdf_jf_order). */
+#define KDF_MEM_HOST   0
+#define KDF_MEM_DEVICE 1
+uint64_t kdf_index_record_bytes(int k, int counter_len);
+int kdf_index_encode(kdf_engine *h, int mem, const void *lo, const void *hi, const void *counts, const void *perm,
+                     uint64_t n, int k, uint64_t byte_first, uint64_t byte_count, void *bytes_out);
+int kdf_index_decode(kdf_engine *h, int mem, const void *bytes, uint64_t n, int k, int counter_len,
+                     void *lo, void *hi, void *counts, uint64_t *bad_record_out);
+int kdf_jf_positions(kdf_engine *h, int mem, const void *lo, const void *hi, uint64_t n, int k,
+                     const uint64_t *columns, uint64_t size, void *pos_out);
+int kdf_jf_order(kdf_engine *h, int mem, const void *lo, const void *hi, uint64_t n, int k,
+                 const uint64_t *columns, uint64_t size, void *perm_out);
+
 /* ------------------------------------------- count profile of a stream ---- */
 
 /* `jellyfish query idx -s reads.fa` over a whole read stream: counts_out[i], 0 <= i < n_bases, is the stored count of

@@ -96,6 +96,12 @@ SYMBOLS = [
                                          POINTER(c_uint64)]),
     ("kdf_parse_kmer_fasta", c_int, [_P, _P, c_uint64, c_int, c_int, c_int, _P, _P, c_uint64, POINTER(c_uint64), POINTER(c_uint64),
                                      POINTER(c_uint64)]),
+    # index record codec: one function per operation, `mem` says where the arrays lie
+    ("kdf_index_record_bytes", c_uint64, [c_int, c_int]),
+    ("kdf_index_encode", c_int, [_P, c_int, _P, _P, _P, _P, c_uint64, c_int, c_uint64, c_uint64, _P]),
+    ("kdf_index_decode", c_int, [_P, c_int, _P, c_uint64, c_int, c_int, _P, _P, _P, POINTER(c_uint64)]),
+    ("kdf_jf_positions", c_int, [_P, c_int, _P, _P, c_uint64, c_int, POINTER(c_uint64), c_uint64, _P]),
+    ("kdf_jf_order", c_int, [_P, c_int, _P, _P, c_uint64, c_int, POINTER(c_uint64), c_uint64, _P]),
     ("kdf_window_counts_dev", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_window_counts", c_int, [_P, _P, _P, c_uint64, _P, _P]),
     ("kdf_read_depth_dev", c_int, [_P, _P, _P, c_uint64, _P, c_int64, c_uint32, _P]),
@@ -202,6 +208,7 @@ SYMBOLS = [
                                POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
 ]
 
+KDF_MEM_HOST, KDF_MEM_DEVICE = 0, 1          # the `mem` argument of the index record codec
 KDF_FA_IN_RECORD, KDF_FA_MID_LINE, KDF_FA_IN_HEADER = 1, 2, 4
 KDF_FASTA_TILE_BYTES = 4096
 

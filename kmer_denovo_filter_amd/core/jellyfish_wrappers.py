@@ -19,7 +19,7 @@ import time
 
 import numpy as np
 
-from .. import dist_env, jf_io
+from .. import devkeys, dist_env, jf_io
 from .._native import KdfError
 from ..engine import mirror_engine
 from ..kmer_fasta import load_kmer_set
@@ -259,9 +259,11 @@ def _count_fasta_to_index(fasta_path, kmer_size, out_path, capacity_hint, cmdlin
             with fasta_reader(fasta_path, kmer_size, max_bases=BATCH_BASES) as rd:
                 for batch in rd:
                     eng.count(batch)
-        lo, hi, cnt = eng.export_ge(0)
-    jf_io.write_index_auto(out_path, kmer_size, lo, hi, cnt, cmdline=cmdline)    # (KDF_JF_FORMAT=jellyfish: a real binary/sorted file)
-    return len(lo)
+        on_device = jf_io.device_index()                 # opt-in: the dump stays in HBM and the records are made there
+        dump = devkeys.dump_ge_counts(eng, 0, eng.device) if on_device else eng.export_ge(0)
+    writer = jf_io.write_index_auto_device if on_device else jf_io.write_index_auto
+    writer(out_path, kmer_size, *dump, cmdline=cmdline)    # (KDF_JF_FORMAT=jellyfish: a real binary/sorted file)
+    return len(dump[0])
 
 
 def _ensure_ref_jf(ref_fasta, kmer_size, threads, ref_jf=None):
@@ -295,14 +297,22 @@ def _merge_jf_files(jf_files, merged_path, threads=4):
     logger.info("Merging %d Jellyfish chunks into %s…", len(jf_files), merged_path)
     merge_start = time.monotonic()
     try:
-        k0, lo, hi, cnt = jf_io.read_index(jf_files[0])
-        with mirror_engine(k0, capacity_hint=max(len(lo), 1)) as eng:
-            eng.add_pairs(lo, hi, cnt)
-            for f in jf_files[1:]:
-                k1, lo, hi, cnt = jf_io.read_index(f, expect_k=k0)
+        if jf_io.device_index():                         # opt-in: records decoded, summed and encoded in HBM
+            k0 = jf_io.read_header(jf_files[0])[0]["key_len"] // 2
+            with mirror_engine(k0, capacity_hint=max(jf_io.index_records(jf_files[0]), 1)) as eng:
+                for f in jf_files:
+                    jf_io.load_index_into_device(eng, f, expect_k=k0)
+                dlo, dhi, dcnt = devkeys.dump_ge_counts(eng, 0, eng.device)
+            jf_io.write_index_device(merged_path, k0, dlo, dhi, dcnt, cmdline=["merge", "-o", merged_path, *jf_files])
+        else:
+            k0, lo, hi, cnt = jf_io.read_index(jf_files[0])
+            with mirror_engine(k0, capacity_hint=max(len(lo), 1)) as eng:
                 eng.add_pairs(lo, hi, cnt)
-            lo, hi, cnt = eng.export_ge(0)
-        jf_io.write_index(merged_path, k0, lo, hi, cnt, cmdline=["merge", "-o", merged_path, *jf_files])
+                for f in jf_files[1:]:
+                    k1, lo, hi, cnt = jf_io.read_index(f, expect_k=k0)
+                    eng.add_pairs(lo, hi, cnt)
+                lo, hi, cnt = eng.export_ge(0)
+            jf_io.write_index(merged_path, k0, lo, hi, cnt, cmdline=["merge", "-o", merged_path, *jf_files])
     except (KdfError, ValueError, OSError) as e:
         raise RuntimeError(f"jellyfish merge failed: {e}") from e
     for f in jf_files:

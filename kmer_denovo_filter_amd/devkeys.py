@@ -86,9 +86,9 @@ def select(sets, idx=None):
     return tuple(out)
 
 
-def dump_ge(eng, min_count: int, device: int = 0):
-    """``jellyfish dump -c -L min_count`` into device tensors, ascending key order (the reference does not rely on
-    the order, but a sorted dump makes the contract FASTA files byte-reproducible from run to run)."""
+def dump_ge_counts(eng, min_count: int, device: int = 0):
+    """``jellyfish dump -c -L min_count`` into device tensors, ascending key order, WITH the counts: -> (lo, hi or None,
+    counts int32 holding the uint32 values) -- what the device index writers take (``jf_io.write_index_device``)."""
     import torch
     dev = torch.device("cuda", device)
     n = eng.count_ge(min_count)
@@ -104,7 +104,13 @@ def dump_ge(eng, min_count: int, device: int = 0):
                             sorted_=True) if n else 0
     if got != n:
         raise RuntimeError(f"dump -L {min_count}: {got} entries written, {n} counted")
-    return lo[:n], (hi[:n] if hi is not None else None)
+    return lo[:n], (hi[:n] if hi is not None else None), cnt[:n]
+
+
+def dump_ge(eng, min_count: int, device: int = 0):
+    """``jellyfish dump -c -L min_count`` into device tensors, ascending key order (the reference does not rely on
+    the order, but a sorted dump makes the contract FASTA files byte-reproducible from run to run)."""
+    return dump_ge_counts(eng, min_count, device)[:2]
 
 
 def dump_join(eng, other, min_count: int, max_count: Optional[int] = None, other_min: int = 0, other_max: Optional[int] = 0,

@@ -574,10 +574,13 @@ def _count_parent_jellyfish(parent_bam, ref_fasta, kmer_fasta, kmer_size, parent
             eng.load_filter(lo, hi)
             _stream_bam(eng, parent_bam, ref_fasta, threads, filtered=True)
             _merge_filter_counts(eng, lo, hi)                  # (several ranks: the sum of their shards' counts)
-            flo, fhi, fcnt = eng.export_ge(0)
+            if jf_io.device_index():                           # opt-in: the dump stays in HBM and the records are made there
+                dump = devkeys.dump_ge_counts(eng, 0, _device())
+            else:
+                dump = eng.export_ge(0)
         if dist_env.is_root():
-            jf_io.write_index(jf_output, kmer_size, flo, fhi, fcnt,
-                              cmdline=["count", "-m", str(kmer_size), "-C", "--if", kmer_fasta, "-o", jf_output])
+            (jf_io.write_index_device if jf_io.device_index() else jf_io.write_index)(
+                jf_output, kmer_size, *dump, cmdline=["count", "-m", str(kmer_size), "-C", "--if", kmer_fasta, "-o", jf_output])
         dist_env.barrier()
     except (KdfError, ValueError, OSError) as e:
         raise RuntimeError(f"jellyfish count ({label}) failed: {e}") from e

@@ -35,7 +35,7 @@ raises.
 """
 from __future__ import annotations
 
-from ctypes import byref, c_uint64, c_void_p
+from ctypes import POINTER, byref, c_uint64, c_void_p
 from typing import Optional, Tuple
 
 import numpy as np
@@ -61,6 +61,15 @@ class KmerFastaError(ValueError):
         super().__init__(msg)
         self.offset = int(offset)
         self.rule = "base" if "non-ACGT" in msg else "length"
+
+
+class IndexRecordError(ValueError):
+    """A record of an index holds a key with a bit at or above 2k (``KmerEngine.index_decode``): ``record`` is the index
+    of the first such record of the decoded block."""
+
+    def __init__(self, msg: str, record: int):
+        super().__init__(msg)
+        self.record = int(record)
 
 
 class KmerEngine:
@@ -1079,6 +1088,132 @@ class KmerEngine:
         if rc == _native.KDF_ERR_INVALID and cap == 0 and n.value > 0:      # a sizing call's answer
             rc = _native.KDF_OK
         return self._parse_result(rc, n, consumed, bad)
+
+    # -- index record codec ---------------------------------------------------
+    @staticmethod
+    def index_record_bytes(k: int, counter_len: int = 4) -> int:
+        """Bytes of one index record (``include/kdf.h``, "index record codec"): ceil(2k / 8) key bytes and
+        ``counter_len`` count bytes.  A pure host function of libkdf: no engine, no GPU.  0 for a k the codec does not
+        take or a ``counter_len`` outside 1..16."""
+        return int(_native.load().kdf_index_record_bytes(int(k), int(counter_len)))
+
+    def _index_key_form(self, lo, hi, k):
+        """(lo, hi, n) as contiguous uint64 arrays in the form of ``k`` (hi None unless k is 33..63; long k: (n, W) rows)."""
+        W = key_words(k)
+        if W == 0:
+            raise ValueError(f"k={k} outside 1..{self.MAX_K} and odd {self.LONG_MIN_K}..{self.LONG_MAX_K}")
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        if W > 2:
+            lo = lo.reshape(-1, W)
+        if W == 2:
+            hi = np.zeros(len(lo), np.uint64) if hi is None else np.ascontiguousarray(hi, dtype=np.uint64)
+            if len(hi) != len(lo):
+                raise ValueError(f"{len(hi)} hi words for {len(lo)} lo words")
+        else:
+            hi = None
+        return lo, hi, len(lo)
+
+    def index_encode(self, lo: np.ndarray, hi: Optional[np.ndarray], counts: Optional[np.ndarray], k: int, perm: Optional[np.ndarray] = None,
+                     byte_first: int = 0, byte_count: Optional[int] = None) -> np.ndarray:
+        """uint8[byte_count]: bytes ``byte_first .. byte_first + byte_count`` (default: to the end) of the record body
+        of an index of the keys -- record e = the key bytes of key ``perm[e]`` (``perm`` None: e), little-endian, and the
+        4 little-endian bytes of its count (``counts`` None: 0).  The key form follows ``k``, not the engine's k: ``lo``
+        uint64[n] (k <= 32), ``lo`` and ``hi`` (k 33..63), (n, W) rows in ``lo`` and ``hi`` None (odd k 65..201).
+        ``byte_first`` must be a multiple of 16."""
+        lo, hi, n = self._index_key_form(lo, hi, k)
+        counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        perm = None if perm is None else np.ascontiguousarray(perm, dtype=np.uint32)
+        for name, a in (("counts", counts), ("perm", perm)):
+            if a is not None and len(a) != n:
+                raise ValueError(f"{len(a)} {name} for {n} keys")
+        if byte_count is None:
+            byte_count = max(n * self.index_record_bytes(k) - int(byte_first), 0)
+        out = np.empty(int(byte_count), np.uint8)
+        v = lambda a: _vp(a) if a is not None and a.size else None
+        self._ck(self._lib.kdf_index_encode(self._h, _native.KDF_MEM_HOST, v(lo), v(hi), v(counts), v(perm), n, int(k), int(byte_first),
+                                            int(byte_count), v(out)))
+        return out
+
+    def index_encode_dev(self, d_lo: int, d_hi: Optional[int], d_counts: Optional[int], d_perm: Optional[int], n: int, k: int,
+                         byte_first: int, byte_count: int, d_bytes: int):
+        """The same between device buffers (raw pointers; ``d_counts`` uint32[n], ``d_perm`` uint32[n] or None):
+        ``d_bytes`` takes ``byte_count`` bytes at any alignment and nothing else.  Stream order on the engine's stream;
+        does not synchronise."""
+        p = lambda x: c_void_p(x) if x else None
+        self._ck(self._lib.kdf_index_encode(self._h, _native.KDF_MEM_DEVICE, p(d_lo), p(d_hi), p(d_counts), p(d_perm), int(n), int(k),
+                                            int(byte_first), int(byte_count), p(d_bytes)))
+
+    def _index_decoded(self, rc, bad):
+        """Nothing, or the error of a decode call: a record whose key has a bit at or above 2k raises ``IndexRecordError``."""
+        if rc == _native.KDF_ERR_IO:
+            msg = self._lib.kdf_last_error(self._h)
+            raise IndexRecordError(msg.decode(errors="replace") if msg else "bad record", bad.value)
+        self._ck(rc)
+
+    def index_decode(self, data, k: int, counter_len: int = 4):
+        """Record bytes (bytes or a uint8 array of whole records of ceil(2k / 8) + ``counter_len`` bytes) ->
+        ``(lo, hi, counts)``: the keys in the form of ``k`` (hi None unless k is 33..63; long k: (n, W) rows) and the
+        counts as uint32, saturated at 2^32 - 1 (the rule of ``jf_io._decode``).  A key with a bit at or above 2k raises
+        ``IndexRecordError`` with the index of the first such record."""
+        t = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+        rd = self.index_record_bytes(k, counter_len)
+        if rd == 0:
+            raise ValueError(f"k={k} or counter_len={counter_len}: no index record of that shape")
+        if t.size % rd:
+            raise ValueError(f"{t.size} bytes are no whole records of {rd} bytes")
+        n, W = t.size // rd, key_words(k)
+        lo = np.zeros((n, W) if W > 2 else n, np.uint64)
+        hi = np.zeros(n, np.uint64) if W == 2 else None
+        counts = np.zeros(n, np.uint32)
+        bad = c_uint64(0)
+        v = lambda a: _vp(a) if a is not None and a.size else None
+        rc = self._lib.kdf_index_decode(self._h, _native.KDF_MEM_HOST, v(t), n, int(k), int(counter_len), v(lo), v(hi), v(counts), byref(bad))
+        self._index_decoded(rc, bad)
+        return lo, hi, counts
+
+    def index_decode_dev(self, d_bytes: int, n: int, k: int, counter_len: int, d_lo: int, d_hi: Optional[int], d_counts: Optional[int]):
+        """The same between device buffers: ``d_bytes`` holds ``n`` records at any alignment, ``d_lo`` / ``d_hi`` /
+        ``d_counts`` (uint32) take ``n`` rows (``d_hi`` may be None for k <= 32, ``d_counts`` may be None).  Synchronises
+        the engine's stream; a bad record raises ``IndexRecordError`` after the rows were written as read."""
+        p = lambda x: c_void_p(x) if x else None
+        bad = c_uint64(0)
+        rc = self._lib.kdf_index_decode(self._h, _native.KDF_MEM_DEVICE, p(d_bytes), int(n), int(k), int(counter_len), p(d_lo), p(d_hi),
+                                        p(d_counts), byref(bad))
+        self._index_decoded(rc, bad)
+
+    @staticmethod
+    def _jf_columns(columns, k):
+        cols = np.ascontiguousarray([int(c) for c in columns], dtype=np.uint64)
+        if len(cols) != 2 * int(k):
+            raise ValueError(f"{len(cols)} matrix columns for key_len {2 * int(k)}")
+        return cols
+
+    def jf_positions(self, lo: np.ndarray, hi: Optional[np.ndarray], k: int, columns, size: int) -> np.ndarray:
+        """uint64[n]: the hash position of every key under a Jellyfish header's ``matrix1.columns`` and ``size`` (a
+        power of two): ``jf_io.jf_positions(columns, 2k, lo, hi) & (size - 1)``.  k <= 63."""
+        lo, hi, n = self._index_key_form(lo, hi, k)
+        cols = self._jf_columns(columns, k)
+        pos = np.zeros(n, np.uint64)
+        v = lambda a: _vp(a) if a is not None and a.size else None
+        self._ck(self._lib.kdf_jf_positions(self._h, _native.KDF_MEM_HOST, v(lo), v(hi), n, int(k), cols.ctypes.data_as(POINTER(c_uint64)),
+                                            int(size), v(pos)))
+        return pos
+
+    def jf_positions_dev(self, d_lo: int, d_hi: Optional[int], n: int, k: int, columns, size: int, d_pos: int):
+        """The same between device buffers: ``d_pos`` takes ``n`` uint64 positions; ``columns`` stays a host sequence
+        (it travels as kernel data).  Stream order on the engine's stream; does not synchronise."""
+        p = lambda x: c_void_p(x) if x else None
+        cols = self._jf_columns(columns, k)
+        self._ck(self._lib.kdf_jf_positions(self._h, _native.KDF_MEM_DEVICE, p(d_lo), p(d_hi), int(n), int(k),
+                                            cols.ctypes.data_as(POINTER(c_uint64)), int(size), p(d_pos)))
+
+    def jf_order_dev(self, d_lo: int, d_hi: Optional[int], n: int, k: int, columns, size: int, d_perm: int):
+        """The record order of a Jellyfish ``binary/sorted`` file: ``d_perm`` (uint32[n]) takes the permutation that
+        puts the keys in ascending (hash position, key) order.  n < 2^32, k <= 63.  Synchronises the engine's stream."""
+        p = lambda x: c_void_p(x) if x else None
+        cols = self._jf_columns(columns, k)
+        self._ck(self._lib.kdf_jf_order(self._h, _native.KDF_MEM_DEVICE, p(d_lo), p(d_hi), int(n), int(k),
+                                        cols.ctypes.data_as(POINTER(c_uint64)), int(size), p(d_perm)))
 
     # -- count profile of a stream -------------------------------------------
     def window_counts(self, stream: ReadStream, want_valid: bool = False):
