@@ -14,7 +14,7 @@
 //       (190 MB for 1.5 G positions), piece -> row of the offset table, compact piece -> ring position, per-bin piece lists.
 //   B   kb_piecesort_pipe_kernel: a piece's runs (one per slab of the group) are gathered, sorted in LDS by the next c2
 //       hash bits and appended, with the piece's offset row, to the engine's entry RING -- by one persistent workgroup
-//       per CU that keeps four pieces in flight at different stages (kb_piecesort_kernel: a workgroup per piece, for
+//       per CU that keeps five pieces in flight at different stages (kb_piecesort_kernel: a workgroup per piece, for
 //       comparison; kb_piecesort_more_kernel: the further pieces of a skewed pair).
 //
 // Rounds 1-2 read the stream twice (a histogram pass A0 fixed an exact place for every (workgroup, bin) run before the
@@ -588,13 +588,17 @@ __global__ __launch_bounds__(KB_THREADS) void kb_piecesort_kernel(KbPlan plan, K
     if (pair >= n_pairs) return;
     kb_sort_piece<KW>(plan, s, s.pass + pass_idx, smem, pair, 0);
 }
-// first launch, PIPELINED (the default): one persistent workgroup per CU walks its share of the pairs, three pieces in
+// first launch, PIPELINED (the default): one persistent workgroup per CU walks its share of the pairs, five pieces in
 // flight at different stages --
-//   piece i + 3: the loads of its slabs' bin offsets and of its place in the ring are issued;
-//   piece i + 2: run table from those offsets (block scan), then all EPT gather loads of every lane are issued into a
-//                SECOND set of registers;
-//   piece i + 1: its entries have arrived and wait in registers;
-//   piece i:     rank by fine bin, scan, scatter into the LDS image, write-out.
+//   piece i + 4: the loads of its slabs' bin offsets and of its place in the ring are issued;
+//   piece i + 3: run table from those offsets (block scan of the run lengths);
+//   piece i + 2: all EPT gather loads of every lane are issued into the register set piece i has just left; fine histogram
+//                as they arrive;
+//   piece i + 1: its entries wait in the other register set; block scan of its histogram into offs[];
+//   piece i:     one returning atomic per entry on offs[] IS its place in the LDS image; scatter; write-out.
+// The histogram of a piece is taken and scanned ONE PIECE AHEAD, so the rank needs no barrier between itself and the
+// scatter, and the two block scans (histogram, run lengths) share one barrier: THREE barriers per piece (KbPipe::iter),
+// where ranking, scanning and scattering the same piece took nine.
 // With one workgroup per CU (the image is 128 KB) kb_piecesort_kernel pays, piece after piece, a global latency for the
 // offsets, another for the gather and the drain of 128 KB of stores, with the vector units idle meanwhile (7.6 us of issue
 // in 24.6 us per piece); here the gather of the next piece is in flight under the LDS phases of this one and the stores
@@ -605,13 +609,45 @@ __device__ __forceinline__ uint32_t kb_uni(uint32_t v) { return (uint32_t)__buil
 __device__ __forceinline__ unsigned long long kb_uni64(unsigned long long v) {
     return ((unsigned long long)kb_uni((uint32_t)(v >> 32)) << 32) | kb_uni((uint32_t)v);
 }
-// One iteration of the pipelined piece sort (see kb_piecesort_pipe_kernel) on ONE of its two register sets: piece `it`,
-// whose entries were requested into (klo, khi) two iterations ago, is sorted and written out, and the entries of piece
-// it + 2 are requested into the same registers.  EVERY global load and store of the body is unconditional -- lanes and
-// whole iterations that have nothing to do read a valid dummy address and re-store a value to where it already is (or
-// to the trash words) -- so that the number of vector-memory instructions between a request and its use is the same on
-// every path: vmcnt retires in issue order, and only then can the compiler wait for "all but the N youngest" instead of
-// for everything (which would include the gather just issued).
+// Where the fine histogram of a piece is taken (both one piece ahead of its rank).  1: after B2 of the iteration that
+// requested the piece, from the SAME register set, beside the write-out -- the adds wait for the gather issued at T0 of
+// that iteration, behind the write-out's stores and the offset requests (a counted vmcnt).  0: at T0 of the next iteration,
+// from the OTHER register set, beside the rank and scatter of the piece before it.  Measured at bench size, five runs each,
+// interleaved: the kernel 3.712-3.718 ms with 1, 3.730-3.732 with 0 (4.013-4.064 with nine barriers), the step 10.38-10.46
+// against 10.42-10.46; k = 63: 5.47-5.77 against 5.48-5.78 ms
+#ifndef KB_B_HIST_T2
+#define KB_B_HIST_T2 1
+#endif
+// Phase timing of the pipelined kernel (variant builds, -DKB_TIMING): every wave sums the cycles of its phases and of its
+// waits at B1, B2, B3 in scalars -- no memory instruction inside the loop, whose vmcnt order stays what it is -- and thread 0
+// adds its sums to trash[8 + 20 .. 8 + 25] at the end (trash[8 + 26]: its pieces).
+#ifdef KB_TIMING
+#define KB_PT(n) do { const unsigned long long kb_pt_now = __builtin_readcyclecounter(); t_acc[n] += kb_pt_now - t_prev; t_prev = kb_pt_now; } while (0)
+#else
+#define KB_PT(n) do {} while (0)
+#endif
+// One iteration of the pipelined piece sort (see kb_piecesort_pipe_kernel): piece `it` lives in the register set
+// (klo, khi), requested two iterations ago; piece it + 1 in the other set (nlo).  Three phases, a barrier after each:
+//   T0  rank + scatter of piece `it`: pos = atomicAdd(&offs[fine], 1) on the piece's scanned histogram (made during
+//       iteration it - 1) is the entry's place in the image; gather of piece it + 2, whose run table was written during
+//       iteration it - 1, into the registers piece `it` has left
+//   B1
+//   T1  threads < nf: o_end = offs[t] -- after the atomics the END of fine bin t, i.e. the piece's offset row shifted
+//       by one; h = hist[t], zeroed; wave scan of h, and of the run lengths of piece it + 3 (offsets requested one
+//       iteration ago); both wave sums published (wsum[0 .. 16), wsum[16 .. 32))
+//   B2
+//   T2  offs[t] = exclusive prefix of h (piece it + 1); rsrc / rpre of piece it + 3; write-out of piece `it` (image,
+//       row_ent, row_len, offset row: [0] = 0, [t + 1] = o_end(t)); the offsets of piece it + 4 are requested; histogram
+//       of piece it + 2 (non-returning adds into the hist[] that T1 has just zeroed; KB_B_HIST_T2 0: at T0 of the next
+//       iteration instead)
+//   B3
+// hist, offs, the run table and the image stay single: each is written and read on opposite sides of a barrier (offs:
+// atomics T0, read T1, written T2; hist: adds T2 (or T0), read + zeroed T1; run table: read T0, written T2; image: written T0,
+// read T2; wsum: written T1, read T2).
+// EVERY global load and store of the body is unconditional -- lanes and whole iterations that have nothing to do read a
+// valid dummy address and store to the trash words -- so that the number of vector-memory instructions between a request
+// and its use is the same on every path: vmcnt retires in issue order, and only then can the compiler wait for "all but
+// the N youngest" instead of for everything (which would include the gather just issued).
 template <int KW>
 struct KbPipe {
     static constexpr int CHUNK = KbCfg<KW>::CHUNK, EPT = CHUNK / KB_THREADS, SLAB = KbCfg<KW>::SLAB;
@@ -619,81 +655,121 @@ struct KbPipe {
     uint64_t *slo; KbEnt2 *s2; uint32_t *hist, *offs, *wsum, *rpre; unsigned long long *rsrc;
     // loop invariants
     const KbPass *P; uint32_t nb, n_pairs, eighth, xcd, j0, nj; int n_it, nf; unsigned long long row_base, ent_base;
-    // O -> R: what was loaded for the piece whose run table comes next (raw: made scalars where they are used)
+    // what was loaded for the piece whose run table comes next (raw: made scalars where they are used)
     uint32_t o_pair = 0, o_npair = 0, o_raw = 0, o_raw2 = 0, o_rowoff = 0, o_binrow = 0; bool o_ok = false;
     unsigned long long o_entoff = 0, o_binent = 0;
+    // the pieces it, it + 1, it + 2 (uniform): entries, row, first entry in the ring; slabs and entries of the pair of it + 2
+    uint32_t len0 = 0, len1 = 0, len2 = 0, g_ns = 1, g_npair = 1;
+    unsigned long long row0 = 0, row1 = 0, row2 = 0, dst0 = 0, dst1 = 0, dst2 = 0;
+#ifdef KB_TIMING
+    unsigned long long t_prev = 0, t_acc[7] = {0, 0, 0, 0, 0, 0, 0};
+#endif
 
     __device__ __forceinline__ void iter(const KbPlan &plan, const KbScratch &s, int it, uint64_t (&klo)[EPT], uint64_t (&khi)[KW == 2 ? EPT : 1],
-                                         uint32_t &m_len, unsigned long long &m_row, unsigned long long &m_dst0) {
+                                         const uint64_t (&nlo)[EPT]) {
         // (the thread index is made opaque once per iteration: the compiler would otherwise keep every per-lane address of
         // the loop body in a register of its own across the whole loop -- ~50 VGPRs, i.e. spills at the 128 this kernel has)
         uint32_t tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         // (kb_entry_off, kdf_device.h: KB_B_SEG adjacent lanes share a contiguous KB_B_SEG * EPT entries of the wave's 64 * EPT -- the
-        // same map in the gather (d) and in the tests of (a), so that a register holds the same entry in both)
+        // same map in the gather, the histogram and the rank, so that a register holds the same entry in all three)
         const uint32_t wbase = (tid >> 6) * (64 * EPT) + kb_entry_off<KB_B_SEG>(EPT, tid & 63, 0);      // this lane's first entry of a piece
-        // ---- (a) LDS phases of piece `it`
-        const uint32_t len = m_len;
-        if (len) {                                                        // (uniform; LDS only)
-            uint32_t rk[EPT / 2];                                         // ranks inside the fine bin, two to a register
-#pragma unroll
-            for (int q = 0; q < EPT; ++q) {
-                uint32_t r = 0;
-                if (wbase + KB_B_SEG * q < len) r = atomicAdd(&hist[kb_fine(plan, klo[q])], 1u);
-                if (q & 1) rk[q >> 1] |= r << 16; else rk[q >> 1] = r;
-            }
-            kb_lds_barrier();
-            {
-                const uint32_t v = (int)tid < nf ? hist[tid] : 0;
-                const uint32_t ex = kb_block_exscan_lds<KB_THREADS>(v, wsum, tid);
-                if ((int)tid < nf) { offs[tid] = ex; hist[tid] = 0; }    // (hist: for the next piece)
-            }
-            kb_lds_barrier();
+        // ---- T0: rank + scatter of piece `it` (LDS only; uniform test)
+        const uint32_t len = len0;
+        if (len) {
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
                 if (wbase + KB_B_SEG * q < len) {
-                    const uint32_t pos = offs[kb_fine(plan, klo[q])] + ((rk[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu);
+                    const uint32_t pos = atomicAdd(&offs[kb_fine(plan, klo[q])], 1u);
                     if constexpr (KW == 2) s2[pos] = KbEnt2{klo[q], khi[q]};
                     else slo[pos] = klo[q];
                 }
             }
-            kb_lds_barrier();
         }
-        const unsigned long long w_row = m_row, w_dst0 = m_dst0;
-        // ---- (b) run table of piece it + 2 (its offsets were requested one iteration ago; LDS only)
-        m_len = 0;
-        uint32_t r_ns = 1, r_npair = 1;
+#if !KB_B_HIST_T2
+        // ... histogram of piece it + 1
+        if (len1) {
+#pragma unroll
+            for (int q = 0; q < EPT; ++q)
+                if (wbase + KB_B_SEG * q < len1) atomicAdd(&hist[kb_fine(plan, nlo[q])], 1u);
+        }
+#endif
+        // ... gather of piece it + 2 into the registers piece `it` has left: all loads of a lane in flight together
         {
-            const uint32_t npair = o_ok ? kb_uni(o_npair) : 0u;
-            if (npair) {                                                  // (uniform) an empty pair has no piece
-                const uint32_t g = o_pair >> plan.c1;
-                const uint64_t s0 = (uint64_t)g * plan.group;
-                const uint32_t ns = (uint32_t)min((uint64_t)plan.group, (uint64_t)plan.n_slabs - s0);
-                const uint32_t sa = 2 * tid;                              // this thread's two consecutive slabs
-                const uint32_t o_a0 = o_raw & 0xFFFFu, o_a1 = o_raw >> 16, o_b0 = o_raw2 & 0xFFFFu, o_b1 = o_raw2 >> 16;
-                const uint32_t rl0 = sa < ns ? o_a1 - o_a0 : 0u, rl1 = sa + 1 < ns ? o_b1 - o_b0 : 0u;
-                const uint32_t pre = kb_block_exscan_lds<KB_THREADS>(rl0 + rl1, wsum, tid);
-                if (sa < ns) {
-                    rsrc[sa] = (s0 + sa) * (unsigned long long)SLAB + o_a0 - pre;
-                    rpre[sa] = pre;
+            const uint32_t glen = len2;
+            uint32_t cr = 0, cnx = 0; unsigned long long cs = 0;
+            if (wbase < glen) {
+                const uint32_t e = wbase;
+                uint32_t gu = kb_guess_run(e, g_ns, g_npair);
+                while (rpre[gu] > e) --gu;
+                while (rpre[gu + 1] <= e) ++gu;
+                cr = gu; cnx = rpre[cr + 1]; cs = rsrc[cr];
+            }
+            const KbEnt2 *tmp2 = (const KbEnt2 *)s.tmp;
+#pragma unroll
+            for (int q = 0; q < EPT; ++q) {
+                const uint32_t e = wbase + KB_B_SEG * q;
+                unsigned long long src = 0;                               // (lanes past the piece read entry 0, and ignore it)
+                if (e < glen) {
+                    if (e >= cnx) {
+                        do { ++cr; cnx = rpre[cr + 1]; } while (e >= cnx);
+                        cs = rsrc[cr];
+                    }
+                    src = cs + e;
                 }
-                if (sa + 1 < ns) {
-                    rsrc[sa + 1] = (s0 + sa + 1) * (unsigned long long)SLAB + o_b0 - (pre + rl0);
-                    rpre[sa + 1] = pre + rl0;
-                }
-                if (tid < 4) rpre[ns + tid] = npair;
-                m_row = row_base + kb_uni(o_binrow) + kb_uni(o_rowoff);
-                m_dst0 = ent_base + kb_uni64(o_binent) + kb_uni64(o_entoff);
-                m_len = min((uint32_t)CHUNK, npair);                     // its first piece; the others: kb_piecesort_more_kernel
-                r_ns = ns; r_npair = npair;
-                kb_lds_barrier();
+                if constexpr (KW == 2) { const KbEnt2 v = tmp2[src]; klo[q] = v.lo; khi[q] = v.hi; }
+                else klo[q] = s.tmp[src];
             }
         }
-        // ---- (c) write-out of piece `it`: its row of run offsets, its place in the ring, the image
+        KB_PT(0);
+        kb_lds_barrier();                                                 // B1: image, offs and hist complete; run table read
+        KB_PT(1);
+        // ---- T1: the offset row of piece `it`; wave scans of the histogram of piece it + 1 and of the run lengths of piece it + 3
+        const bool fb = (int)tid < nf;
+        uint32_t o_end = 0, h = 0;
+        if (fb) { o_end = offs[tid]; h = hist[tid]; hist[tid] = 0; }
+        const uint32_t npair = o_ok ? kb_uni(o_npair) : 0u;             // (0: an empty pair has no piece, and iterations past the end none)
+        const uint32_t r_g = o_pair >> plan.c1;
+        const uint64_t r_s0 = (uint64_t)r_g * plan.group;
+        const uint32_t r_ns = npair ? (uint32_t)min((uint64_t)plan.group, (uint64_t)plan.n_slabs - r_s0) : 0u;
+        const uint32_t sa = 2 * tid;                                      // this thread's two consecutive slabs
+        const uint32_t o_a0 = o_raw & 0xFFFFu, o_a1 = o_raw >> 16, o_b0 = o_raw2 & 0xFFFFu, o_b1 = o_raw2 >> 16;
+        const uint32_t rl0 = sa < r_ns ? o_a1 - o_a0 : 0u, rl1 = sa + 1 < r_ns ? o_b1 - o_b0 : 0u;
+        const uint32_t h_inc = kb_block_exscan_publish(h, wsum, tid);
+        const uint32_t r_inc = kb_block_exscan_publish(rl0 + rl1, wsum + 16, tid);
+        KB_PT(2);
+        kb_lds_barrier();                                                 // B2: wave sums published; offs and hist read
+        KB_PT(3);
+        // ---- T2: offs of piece it + 1
         {
+            const uint32_t ex = kb_block_exscan_finish<KB_THREADS>(h, h_inc, wsum, tid);
+            if (fb) offs[tid] = ex;
+        }
+        // ... run table of piece it + 3 (LDS only; uniform test)
+        uint32_t n_len = 0; unsigned long long n_row = 0, n_dst = 0;
+        {
+            const uint32_t pre = kb_block_exscan_finish<KB_THREADS>(rl0 + rl1, r_inc, wsum + 16, tid);
+            if (npair) {
+                if (sa < r_ns) {
+                    rsrc[sa] = (r_s0 + sa) * (unsigned long long)SLAB + o_a0 - pre;
+                    rpre[sa] = pre;
+                }
+                if (sa + 1 < r_ns) {
+                    rsrc[sa + 1] = (r_s0 + sa + 1) * (unsigned long long)SLAB + o_b0 - (pre + rl0);
+                    rpre[sa + 1] = pre + rl0;
+                }
+                if (tid < 4) rpre[r_ns + tid] = npair;                   // padding: the run search stops there
+                n_row = row_base + kb_uni(o_binrow) + kb_uni(o_rowoff);
+                n_dst = ent_base + kb_uni64(o_binent) + kb_uni64(o_entoff);
+                n_len = min((uint32_t)CHUNK, npair);                     // its first piece; the others: kb_piecesort_more_kernel
+            }
+        }
+        // ... write-out of piece `it`: its row of run offsets, its place in the ring, the image
+        {
+            const unsigned long long w_row = row0, w_dst0 = dst0;
             uint32_t *co = len ? s.chunk_off + w_row * plan.off_stride : (uint32_t *)s.trash;
-            const uint32_t ci = len ? min(tid, (uint32_t)nf) : 0u;
-            co[ci] = (int)tid < nf ? offs[ci] : len;                     // (lanes past the row all store its last word)
+            const uint32_t ci = len && fb ? tid + 1 : 0u;                 // (lanes past the row all store its first word)
+            co[ci] = fb ? o_end : 0u;
             unsigned long long *re = len ? s.row_ent + w_row : (unsigned long long *)s.trash + 1;
             uint32_t *rl_ = len ? s.row_len + w_row : (uint32_t *)s.trash + 4;
             *re = w_dst0; *rl_ = len;
@@ -735,12 +811,12 @@ struct KbPipe {
                 d[0] = slo[0]; d[last] = slo[last];
             }
         }
-        // ---- (e) offsets of piece it + 3
+        // ... offsets of piece it + 4
         {
-            const int i3 = it + 3;
-            const uint32_t jj = j0 + (uint32_t)i3 * nj;
+            const int i4 = it + 4;
+            const uint32_t jj = j0 + (uint32_t)i4 * nj;
             const uint32_t pair = xcd * eighth + jj;
-            o_ok = i3 >= 0 && i3 < n_it && jj < eighth && pair < n_pairs;
+            o_ok = i4 >= 0 && i4 < n_it && jj < eighth && pair < n_pairs;
             const uint32_t pc = o_ok ? pair : 0u;                         // (nothing to do: pair 0 is read, and ignored)
             const uint32_t g = pc >> plan.c1, c = pc & (nb - 1);
             const uint64_t s0 = (uint64_t)g * plan.group;
@@ -754,36 +830,25 @@ struct KbPipe {
             __builtin_memcpy(&o_raw, orow + ta * (nb + 1), 4);                          // off[c], off[c + 1] of its two slabs: split where they are used
             __builtin_memcpy(&o_raw2, orow + tb * (nb + 1), 4);
         }
-        // ---- (d) gather of piece it + 2 into the registers piece `it` has left: all loads of a lane in flight together
-        {
-            const uint32_t glen = m_len;
-            uint32_t cr = 0, cnx = 0; unsigned long long cs = 0;
-            if (wbase < glen) {
-                const uint32_t e = wbase;
-                uint32_t gu = kb_guess_run(e, r_ns, r_npair);
-                while (rpre[gu] > e) --gu;
-                while (rpre[gu + 1] <= e) ++gu;
-                cr = gu; cnx = rpre[cr + 1]; cs = rsrc[cr];
-            }
-            const KbEnt2 *tmp2 = (const KbEnt2 *)s.tmp;
+#if KB_B_HIST_T2
+        // ... histogram of piece it + 2, whose entries were requested at T0 (hist was read and zeroed before B2)
+        if (len2) {
 #pragma unroll
-            for (int q = 0; q < EPT; ++q) {
-                const uint32_t e = wbase + KB_B_SEG * q;
-                unsigned long long src = 0;                               // (lanes past the piece read entry 0, and ignore it)
-                if (e < glen) {
-                    if (e >= cnx) {
-                        do { ++cr; cnx = rpre[cr + 1]; } while (e >= cnx);
-                        cs = rsrc[cr];
-                    }
-                    src = cs + e;
-                }
-                if constexpr (KW == 2) { const KbEnt2 v = tmp2[src]; klo[q] = v.lo; khi[q] = v.hi; }
-                else klo[q] = s.tmp[src];
-            }
+            for (int q = 0; q < EPT; ++q)
+                if (wbase + KB_B_SEG * q < len2) atomicAdd(&hist[kb_fine(plan, klo[q])], 1u);
         }
-        // (the image is read by (c) and written by the next (a) after its two barriers; the run table is read by (d) and
-        // written by the next (b) after the barriers of (a) or of its own scan)
-        kb_lds_barrier();
+#endif
+#ifdef KB_TIMING
+        t_acc[6] += len ? 1u : 0u;
+#endif
+        // the pieces move up by one
+        len0 = len1; row0 = row1; dst0 = dst1;
+        len1 = len2; row1 = row2; dst1 = dst2;
+        len2 = n_len; row2 = n_row; dst2 = n_dst;
+        g_ns = npair ? r_ns : 1u; g_npair = npair ? npair : 1u;
+        KB_PT(4);
+        kb_lds_barrier();                                                 // B3: image written out; offs and run table ready
+        KB_PT(5);
     }
 };
 
@@ -791,13 +856,13 @@ template <int KW>
 __global__ __launch_bounds__(KB_THREADS) void kb_piecesort_pipe_kernel(KbPlan plan, KbScratch s, uint32_t pass_idx)
 {
     constexpr int CHUNK = KbCfg<KW>::CHUNK, EPT = CHUNK / KB_THREADS;
-    static_assert(EPT % 2 == 0 && CHUNK <= 65536, "ranks are kept two to a register");
+    static_assert(EPT % 2 == 0, "the image goes out two entries to a store");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     KbPipe<KW> p;
     p.slo = (uint64_t *)smem; p.s2 = (KbEnt2 *)smem;
     p.hist = (uint32_t *)(smem + (size_t)CHUNK * 8 * KW);               // [KB_F]
     p.offs = p.hist + KB_F;                                              // [KB_F]
-    p.wsum = p.offs + KB_F;                                              // [32]
+    p.wsum = p.offs + KB_F;                                              // [32]: two scans' wave sums
     p.rsrc = (unsigned long long *)(p.wsum + 32);                       // [KB_G_MAX]
     p.rpre = (uint32_t *)(p.rsrc + KB_G_MAX);                           // [KB_G_MAX + 4]
     p.P = s.pass + pass_idx;
@@ -807,17 +872,24 @@ __global__ __launch_bounds__(KB_THREADS) void kb_piecesort_pipe_kernel(KbPlan pl
     p.n_it = p.j0 < p.eighth ? (int)((p.eighth - p.j0 + p.nj - 1) / p.nj) : 0;
     p.nf = 1 << plan.c2;
     p.row_base = p.P->row_base; p.ent_base = p.P->ent_base;
-    for (int i = threadIdx.x; i < KB_F; i += KB_THREADS) p.hist[i] = 0;
+    for (int i = threadIdx.x; i < KB_F; i += KB_THREADS) { p.hist[i] = 0; p.offs[i] = 0; }
     kb_lds_barrier();
-    // two register sets: piece k lives in set k & 1 from the iteration that requests it (k - 2) to the one that sorts it (k)
+    // two register sets: piece k lives in set k & 1 from the iteration that requests it (k - 2) to the one that ranks it (k).
+    // Piece 0 is requested by iteration -4 (offsets), -3 (run table), -2 (gather), -1 (histogram).
     uint64_t alo[EPT], ahi[KW == 2 ? EPT : 1], blo[EPT], bhi[KW == 2 ? EPT : 1];
-    uint32_t a_len = 0, b_len = 0; unsigned long long a_row = 0, a_dst0 = 0, b_row = 0, b_dst0 = 0;
 #pragma unroll
     for (int q = 0; q < EPT; ++q) { alo[q] = 0; blo[q] = 0; if constexpr (KW == 2) { ahi[q] = 0; bhi[q] = 0; } }
+#ifdef KB_TIMING
+    p.t_prev = __builtin_readcyclecounter();
+#endif
     for (int it = -4; it < p.n_it; it += 2) {
-        p.iter(plan, s, it, alo, ahi, a_len, a_row, a_dst0);
-        p.iter(plan, s, it + 1, blo, bhi, b_len, b_row, b_dst0);
+        p.iter(plan, s, it, alo, ahi, blo);
+        p.iter(plan, s, it + 1, blo, bhi, alo);
     }
+#ifdef KB_TIMING
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 7; ++i) atomicAdd((unsigned long long *)&s.trash[8 + 20 + i], p.t_acc[i]);
+#endif
 }
 
 // second launch: the pieces beyond a pair's first (skewed input only); a few persistent workgroups walk the list

@@ -80,6 +80,21 @@ __device__ __forceinline__ uint32_t kb_block_exscan_lds(uint32_t v, uint32_t *ws
     return r;
 }
 
+// The same scan in two halves around a barrier that the CALLER places, for a loop whose stages have barriers of their own
+// (the pipelined piece sort, kdf_binned.h): kb_block_exscan_publish before the barrier (returns the lane's inclusive wave
+// prefix, which the caller keeps), kb_block_exscan_finish after it.  No barrier inside: the caller's barriers also keep
+// wsum from being written again before every wave has read it.  Several scans share one barrier, each with its own wsum.
+__device__ __forceinline__ uint32_t kb_block_exscan_publish(uint32_t v, uint32_t *wsum /* >= 16 words LDS */, uint32_t tid) {
+    const uint32_t inc = kb_wave_incl_scan(v);
+    if ((tid & 63u) == 63u) wsum[tid >> 6] = inc;
+    return inc;
+}
+template <int NT>
+__device__ __forceinline__ uint32_t kb_block_exscan_finish(uint32_t v, uint32_t inc, const uint32_t *wsum, uint32_t tid) {
+    uint32_t total;
+    return kb_wave_sums_before(wsum, tid, NT >> 6, total) + inc - v;
+}
+
 // Kernel A's strip scan, by ONE wave with all its lanes (lane = 0 .. 63): offs[0 .. nb) = the exclusive prefix of
 // hist[0 .. nb), offs[nb] = the total.  nb = 1, 2, 4 .. 1024; hist and offs are 16-byte aligned.  A lane owns
 // per = max(1, nb / 64) consecutive bins: 16-byte LDS reads and writes from per = 4 on.  Its first four bins stay in
