@@ -1255,6 +1255,91 @@ int kdf_fasta_pack(kdf_engine *h, const uint8_t *text, uint64_t n_bytes, int fin
                    uint64_t *packed, uint64_t *invalid, uint64_t cap_bases, int64_t *offsets, uint64_t cap_reads,
                    uint64_t *n_bases, uint64_t *n_reads, uint64_t *consumed);
 
+/* -------------------------------------------------- device FASTQ feeder ---- */
+
+/* The FASTQ leg with the parse on the device: the raw text of a four-line FASTQ lies in HBM (or, with
+ * KDF_MEM_HOST, in host memory and is staged), kernels write the packed stream, the invalid mask and the record offsets in
+ * the layout kdf_reader_next and ReadStream.from_strings produce, and mask the bases whose quality is below min_qual.
+ * Sequence and quality only, no read names.  The table is not touched and nothing is flushed: any engine, of any k, packs
+ * any FASTQ.  ONE function with a `mem` argument, as the index record codec's.
+ *
+ * THE RULE, per byte (this is the specification):
+ *   - LINES.  A line ends at '\n'.  All '\r' directly in front of a line's end are dropped.
+ *   - RECORDS.  Lines are taken four at a time: line 0 must begin with '@' (the rest is ignored, at any length), line 1 is
+ *     the sequence, line 2 must begin with '+' (the rest is ignored), line 3 is the quality.  Only four-line records are
+ *     accepted: a sequence wrapped over several lines is an error by the rules below, never guessed at.
+ *   - POSITIONS.  Every byte of the sequence line is ONE stream position: ACGTacgt valid with codes 0 .. 3, every other
+ *     byte (N, IUPAC codes, a blank, an interior '\r') an invalid position with packed bits 0.  With min_qual > 0,
+ *     position j is also invalid, with bits 0, when byte j of the quality line is below min_qual (an unsigned byte
+ *     compare; `jellyfish count -Q` / --min-qual-char: the base becomes N).  min_qual == 0 never looks at quality values;
+ *     min_qual > 255 is KDF_ERR_INVALID.
+ *   - SEPARATOR.  Every record is followed by one separator position (invalid, bits 0); a record without bases is a lone
+ *     separator.
+ *   - SPANS.  Record r of the call occupies [off[r], off[r + 1]), its separator included; off[0] == 0 and
+ *     off[*n_reads] == *n_bases.
+ *   - A call that is NOT the last consumes whole records only: *consumed is the end of the last record whose four lines
+ *     are all terminated by '\n', and only those records are examined and emitted.  The caller hands the rest over again
+ *     in front of the next chunk; no window spans a call, so there is no carry.  Of the trailing bytes of its text that
+ *     are only '\n' / '\r' such a call sees the first line end and leaves the rest: whether they are blank lines at the
+ *     file's end (which the final call drops) or a blank line between records (an error) is for the call that sees what
+ *     follows them.  A non-empty chunk without a complete record is KDF_OK with *consumed == 0, *n_reads == 0,
+ *     *n_bases == 0 and writes nothing; so does n_bytes == 0.
+ *   - The FINAL call first drops the trailing bytes that are only '\n' / '\r' behind the last byte that is neither; then
+ *     the text's end closes the last line; then a last record of exactly three lines whose sequence line is empty gets an
+ *     empty quality line.  Everything is consumed (*consumed == n_bytes).  An empty text is zero records.
+ *   - FORMAT ERRORS return KDF_ERR_IO, and *bad_rule says which rule the record breaks:
+ *       KDF_FQ_BAD_HEADER  line 0 does not begin with '@' (an empty line 0 -- a blank line between records -- included)
+ *       KDF_FQ_BAD_PLUS    line 2 does not begin with '+'
+ *       KDF_FQ_LENGTH      the sequence and quality lines differ in length after the '\r' rule
+ *       KDF_FQ_TRUNCATED   on the final call the last record has fewer than four lines
+ *     *bad_offset is the offset within this call's text of the first byte of the FIRST offending record: with several bad
+ *     records the lowest, and *bad_rule the lowest-numbered rule that record breaks (a rule about a line the record does
+ *     not have is not broken) -- the same from run to run.  Nothing usable is promised in the outputs, nothing is written,
+ *     `state` is unchanged and *consumed is 0.  Without an error *bad_offset is ~0 and *bad_rule 0.
+ *
+ * OUTPUTS.  packed / invalid hold kdf_stream_words(cap_bases) words.  Every word below kdf_stream_words(*n_bases) is
+ * written -- positions at and past *n_bases are invalid in the mask and zero in the packed array, the guarantee of the
+ * FASTA feeder -- and nothing outside those words.  `offsets` may be NULL (cap_reads is ignored then); else it is
+ * int64[cap_reads + 1] and receives *n_reads + 1 entries.  *n_reads is set without offsets too.  A stream that needs more
+ * than cap_bases positions, or more than cap_reads records when offsets are asked for, is KDF_ERR_INVALID.  The format
+ * comes first: only the first cap records are examined (cap: cap_bases, and cap_reads with offsets), a bad one among
+ * them is KDF_ERR_IO, and more records than cap, or more positions than cap_bases, are KDF_ERR_INVALID after that.
+ * Nothing is written and `state` is unchanged, as after every refusal.  A record of s bases takes at least 2 s + 6 bytes (2 s + 4 as the last
+ * of a final call) and s + 1 positions, so *n_bases <= n_bytes / 2 and *n_reads <= n_bytes / 4:
+ * cap_bases >= n_bytes / 2 and cap_reads >= n_bytes / 4 always suffice.  `state` (zeroed before the first chunk) carries
+ * the running totals of records, positions and consumed bytes; the call reads nothing from it.  A chunk takes at most
+ * 2^31 bytes.
+ *
+ * MEMORY.  KDF_MEM_DEVICE: text, packed, invalid and offsets are device pointers, used in place on the engine's stream.
+ * KDF_MEM_HOST: they are host arrays, staged through the engine's staging arena as the other host forms do.  The scalar
+ * results and `state` are host memory with both.  Any other mem is KDF_ERR_INVALID.  The call synchronises once, because
+ * it learns the sizes and a possible error.
+ *
+ * WORK.  On the engine's stream: (1) one workgroup finds the end of the text in front of the trailing line ends;
+ * (2) a pass over tiles of KDF_FASTQ_TILE_BYTES of text (aligned 16-byte loads at any alignment of the text: the tiles
+ * are laid over the memory) counts line ends per tile; (3) one workgroup scans the counts and fixes the number of records; (4) a pass over
+ * the same tiles writes the line ends' offsets into engine-owned scratch; (5) a thread per record checks the four rules,
+ * takes an atomic minimum of (offset, rule) for the first bad record and writes the record's positions; (6) a scan of
+ * those (block sums, one workgroup over them, a pass that adds them back) gives the offsets and, per 64 positions, the
+ * record their first one lies in; (7) the pack kernel is output-driven: a wave owns 64 consecutive stream positions,
+ * each lane finds its record from the offsets, loads its base byte and -- with min_qual -- its quality byte, one ballot
+ * is the mask word and two more, interleaved, are the two packed words, so every output word is stored whole: no
+ * atomics, no zeroing pass, reads of any length.  The last two passes read the verdict and do nothing after a
+ * refusal.  The scratch is 16 bytes per record the capacities admit (at most n_bytes / 6 + 1) for the line ends
+ * and 8 for the offsets.  Under kdf_profile(h, 1): stats "fastqfeed_us" / "fastqfeed_passes" (one pass per call that
+ * launches). */
+typedef struct { uint64_t records, positions, bytes; } kdf_fastq_state;
+#define KDF_FQ_BAD_HEADER 1u
+#define KDF_FQ_BAD_PLUS   2u
+#define KDF_FQ_LENGTH     3u
+#define KDF_FQ_TRUNCATED  4u
+#define KDF_FASTQ_TILE_BYTES 4096   /* text bytes per workgroup of the line-end passes (tests aim at its multiples) */
+int kdf_fastq_pack(kdf_engine *h, int mem, const void *text, uint64_t n_bytes, int final_chunk, uint32_t min_qual,
+                   kdf_fastq_state *state, void *packed, void *invalid, uint64_t cap_bases,
+                   void *offsets, uint64_t cap_reads,
+                   uint64_t *n_bases, uint64_t *n_reads, uint64_t *consumed,
+                   uint64_t *bad_offset, uint32_t *bad_rule);
+
 /* N4: the informative-reads BAM (discovery/pipeline.py:1979-2079 `_write_informative_reads_discovery`,
  * vcf/pipeline.py:1307-1357 `_write_informative_reads`: pysam write + `samtools sort` + `samtools index`).
  * Copies the records ordinals[0..n) (strictly ascending file record numbers, see

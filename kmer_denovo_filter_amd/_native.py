@@ -206,9 +206,12 @@ SYMBOLS = [
                                    POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     ("kdf_fasta_pack", c_int, [_P, _P, c_uint64, c_int, _P, _P, _P, c_uint64, c_uint32, _P, _P, c_uint64, _P, c_uint64,
                                POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+    # device FASTQ feeder (the state: FastqState below): one function with a `mem` argument
+    ("kdf_fastq_pack", c_int, [_P, c_int, _P, c_uint64, c_int, c_uint32, _P, _P, _P, c_uint64, _P, c_uint64,
+                               POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32)]),
 ]
 
-KDF_MEM_HOST, KDF_MEM_DEVICE = 0, 1          # the `mem` argument of the index record codec
+KDF_MEM_HOST, KDF_MEM_DEVICE = 0, 1          # the `mem` argument of the index record codec and of the FASTQ feeder
 KDF_FA_IN_RECORD, KDF_FA_MID_LINE, KDF_FA_IN_HEADER = 1, 2, 4
 KDF_FASTA_TILE_BYTES = 4096
 
@@ -220,6 +223,19 @@ class FastaState(ctypes.Structure):
     def copy(self) -> "FastaState":
         return FastaState(self.flags, self.reserved, self.records, self.positions)
 
+
+KDF_FQ_BAD_HEADER, KDF_FQ_BAD_PLUS, KDF_FQ_LENGTH, KDF_FQ_TRUNCATED = 1, 2, 3, 4
+KDF_FASTQ_TILE_BYTES = 4096
+
+
+class FastqState(ctypes.Structure):
+    """kdf_fastq_state: the running totals the device FASTQ feeder keeps from chunk to chunk (all zero before the first)."""
+    _fields_ = [("records", c_uint64), ("positions", c_uint64), ("bytes", c_uint64)]
+
+    def copy(self) -> "FastqState":
+        return FastqState(self.records, self.positions, self.bytes)
+
+
 _lib = None
 
 
@@ -229,6 +245,15 @@ class KdfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"kdf engine failed ({code}): {msg}")
         self.code = code
+
+
+class FastqFormatError(KdfError):
+    """A text that is no four-line FASTQ (KDF_ERR_IO of kdf_fastq_pack).  ``offset``: the first byte of the first bad record
+    -- within the call's text, or within the file when ``reads.stream_fastq_device`` raises it; ``rule``: KDF_FQ_*."""
+
+    def __init__(self, code: int, msg: str, offset: int, rule: int):
+        super().__init__(code, msg)
+        self.offset, self.rule = int(offset), int(rule)
 
 
 def _preload_torch_hip():

@@ -28,6 +28,7 @@ _SOURCES = [
     ("kdf_spool.hip", _ENGINE_FLAGS),
     ("kdf_kmerfasta.hip", _ENGINE_FLAGS),
     ("kdf_fastafeed.hip", _ENGINE_FLAGS),
+    ("kdf_fastqfeed.hip", _ENGINE_FLAGS),
     ("kdf_indexcodec.hip", _ENGINE_FLAGS),
     ("kdf_sort.hip", ["--offload-arch=gfx950", "-O3"]),
     ("kdf_host.cpp", ["-O2", "-x", "c++"]),          # host only: no device pass

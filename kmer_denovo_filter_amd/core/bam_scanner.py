@@ -26,7 +26,7 @@ from .. import jf_io
 from .._native import KDF_ERR_NOMEM, KdfError
 from ..engine import KmerEngine, mirror_engine, hit_positions
 from ..kmer_fasta import load_kmer_set
-from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys, stream_words
+from ..reads import FLAG_OFF_MODULE3, bam_reader, kmers_to_keys, refuse_fastq, stream_words
 
 logger = logging.getLogger(__name__)
 
@@ -114,6 +114,7 @@ def scan_bam_for_hits(child_bam, engine: Optional[KmerEngine] = None, min_dk_per
     BAM ordinals, so that another k-mer set is evaluated over the same reads by
     ``spool.read_hits`` / ``select_reads`` and not by a second pass over the BAM
     (a spool that overflows stops taking batches; ``spool.stat("overflowed")``)."""
+    refuse_fastq(child_bam, "scan_bam_for_hits (the Module 3 scan)")
     eng = engine or _worker_engine
     if eng is None:
         raise RuntimeError("scan worker not initialised (_init_scan_worker)")
@@ -446,6 +447,7 @@ def scan_bam_module3(child_bam, kmer_size=None, min_dk_per_read=None, engine=Non
     stay in HBM in ``last_ledger`` (``RegionLedger``), and ``unique_in_read`` of a ``read_hits`` entry is the read's
     ordinal in that ledger; ``discovery.regions._cluster_read_hits_device`` counts the regions' k-mers from it.
     """
+    refuse_fastq(child_bam, "scan_bam_module3 (Module 3)")
     import collections
     from ..kmer_utils import canonicalize
     global last_ledger

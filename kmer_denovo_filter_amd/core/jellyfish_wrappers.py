@@ -64,11 +64,28 @@ def _find_jf_files(base_path):
     return ([base_path] if os.path.exists(base_path) else []) + chunks
 
 
+def _fastq_bases(path):
+    """Bases of a FASTQ sample (one path, a comma-separated list or a sequence), from its size: a record is its bases twice
+    and little else, so a plain file holds bytes / 2; a gzip file is taken to inflate fourfold -- bytes x 2 -- which is an
+    UNMEASURED rule of thumb.  Tables grow either way."""
+    from .. import reads
+    return sum(os.path.getsize(p) * 2 if p.lower().endswith(".gz") else os.path.getsize(p) // 2 for p in reads.fastq_paths(path))
+
+
+def _sample_bytes(path):
+    """The size of a sample as the BAM rules of thumb count it: a BAM's bytes; a FASTQ sample is sized from its bases, at
+    the 0.6 BAM bytes per base those rules assume (discovery/pipeline.py ``_child_key_parts``).  OSError as getsize."""
+    from .. import reads
+    if reads.is_fastq_path(path):
+        return _fastq_bases(path) * 6 // 10
+    return os.path.getsize(path)
+
+
 def _estimate_jf_hash_size(bam_path, kmer_size, default="1G"):
     """The reference's ``-s`` heuristic (:73-107): 0.3 table entries per BAM byte, held between 100 M and 4 G,
-    printed in whole G from 10^9 entries on, else in whole M."""
+    printed in whole G from 10^9 entries on, else in whole M.  A FASTQ sample: ``_sample_bytes``."""
     try:
-        entries = os.path.getsize(bam_path) * 3 // 10
+        entries = _sample_bytes(bam_path) * 3 // 10
     except OSError:
         return default
     entries = min(max(entries, 100_000_000), 4_000_000_000)
@@ -96,7 +113,7 @@ def _engine_capacity_hint(hash_size, bam_path=None):
     want = _parse_hash_size(hash_size)
     if bam_path is not None:
         try:
-            want = min(want, max(1 << 20, os.path.getsize(bam_path) * 3 // 10))
+            want = min(want, max(1 << 20, _sample_bytes(bam_path) * 3 // 10))
         except OSError:
             pass
     return max(1 << 16, want)
@@ -116,7 +133,25 @@ def _sketch_bam(engine, bam_path, ref_fasta, threads, spool=None):
     return _stream_bam_pass(engine, bam_path, threads, False, False, spool, True)
 
 
+def _stream_fastq_pass(engine, paths, filtered, tally, spool, sketch):
+    """A sample given as FASTQ (a path that ends in .fastq / .fq / .fastq.gz / .fq.gz, or a comma-separated list of such):
+    the text goes to HBM as it is and kernels pack it (``reads.stream_fastq_device``).  KDF_FASTQ_MIN_QUAL (a character or
+    a number; default off) masks the bases of a lower quality, as `jellyfish count -Q`.  Not sharded: several ranks refuse."""
+    global LAST_FEEDER
+    from .. import reads
+    world, rank, _ = dist_env.world_rank()
+    if world > 1:
+        raise ValueError(f"a FASTQ sample ({paths}) is not sharded over ranks: count it in one process, or align it and pass the BAM")
+    n = reads.stream_fastq_device(engine, reads.fastq_paths(paths), filtered=filtered, tally=tally, sketch=sketch, spool=spool,
+                                  min_qual=reads.fastq_min_qual())
+    LAST_FEEDER = dict(reads.LAST_FASTQ_FEEDER, path="fastq")
+    return n
+
+
 def _stream_bam_pass(engine, bam_path, threads, filtered, tally, spool, sketch):
+    from .. import reads
+    if reads.is_fastq_path(bam_path):
+        return _stream_fastq_pass(engine, bam_path, filtered, tally, spool, sketch)
     if str(bam_path).endswith(".cram"):
         raise RuntimeError(
             "jellyfish count failed: CRAM input needs htslib, which the MI355X engine does not link; "

@@ -1,5 +1,5 @@
 // kdf_engine_priv.h -- what the units of libkdf.so share of the engine (host only, no kernel): kdf_engine.hip (the
-// core, which defines every function declared here unless noted), kdf_engine_reads.hip, kdf_kmerfasta.hip, kdf_fastafeed.hip, kdf_indexcodec.hip and kdf_spool.hip.  Nothing
+// core, which defines every function declared here unless noted), kdf_engine_reads.hip, kdf_kmerfasta.hip, kdf_fastafeed.hip, kdf_fastqfeed.hip, kdf_indexcodec.hip and kdf_spool.hip.  Nothing
 // here is exported: include/kdf.h is the library's interface.
 //
 // One kernel, one unit: a __global__ function is compiled by exactly one unit (a non-template kernel in a header two
@@ -40,8 +40,8 @@ struct KbPass;                            // kdf_binned.h (the core)
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_FA, T_IX, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta", "fastafeed", "indexcodec"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_FA, T_IX, T_FQ, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta", "fastafeed", "indexcodec", "fastqfeed"};
 // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
 // table is needed or the ring is full (kb_flush_ring).  Reserved by upper bounds (one entry per stream position), so no
 // host round trip sits between the stages.  Host only: what the kernels take of it is KbPlan (kdf_device.h).
@@ -136,6 +136,7 @@ struct RegScratch { DevBuf scratch, perm; };                           // kdf_re
 struct KfScratch { DevBuf block_sums; };                               // kdf_kmerfasta.h: block sums of the record scan and its counters
 struct FaScratch { DevBuf scratch; };                                  // kdf_fastafeed.h: tile summaries, tile offsets and the control words
 struct IxScratch { DevBuf pos, ctl; };                                 // kdf_indexcodec.h: hash positions of kdf_jf_order; the first bad record of a decode
+struct FqScratch { DevBuf scratch; };                                  // kdf_fastqfeed.h: control words, tile counts, line ends, record offsets, block sums, the word index
 struct BdState {                                                       // device BAM feeder (kdf_bamdev.h)
     DevBuf inflated, status, read_offs;              // inflated span; block / sub-range status, counts, bases and totals; per-read sequence offsets
     // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option
@@ -171,7 +172,7 @@ struct kdf_engine {
     const char *arena_user = nullptr;                // the host form whose HostCall is open (commit() .. its destructor), else NULL
     // ---- the features' state (above) ----------------------------------------------------------------------------------
     KbState kb; SieveState sieve; BinSieveState bsv; PfState pf; SkState sk; UpState up;
-    HitScratch hits; CovScratch cov; VarScratch var; RegScratch reg; KfScratch kf; FaScratch fa; IxScratch ix; BdState bd; MergeState merge;
+    HitScratch hits; CovScratch cov; VarScratch var; RegScratch reg; KfScratch kf; FaScratch fa; IxScratch ix; FqScratch fq; BdState bd; MergeState merge;
     // ---- options, statistics and what the last call did ------------------------------------------------------------------
     uint64_t stat_flushes = 0;
     double grow_ratio = 0.0;                         // new distinct keys per counted window at the last flush (0: unknown)

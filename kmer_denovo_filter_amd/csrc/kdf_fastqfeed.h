@@ -1,0 +1,302 @@
+// kdf_fastqfeed.h -- the device FASTQ feeder (include/kdf.h, "device FASTQ feeder"): the raw text of a four-line FASTQ in
+// HBM -> the packed 2-bit stream, its invalid mask (low qualities included) and the record offsets, by the per-byte rule
+// of the header.  A line's role follows only from its number, and '@' and '+' are legal quality bytes, so nothing is
+// classified byte-locally: the line ends are numbered first, the records are read off them, and the pack is driven by
+// the OUTPUT:
+//   1. kfq_end_kernel      one workgroup: the end of the text in front of its trailing '\n' / '\r' (a call that is not the
+//                          last keeps the first line end of them); resets the control words
+//   2. kfq_count_kernel    per tile of KDF_FASTQ_TILE_BYTES = 256 lanes x 16 bytes (aligned 16-byte loads at any alignment of
+//                          the text: the tiles are laid over the memory, not over the text): its line ends
+//   3. kfq_scan_kernel     one workgroup: the tiles' first line numbers, the number of lines and of records, and how many
+//                          of the records the capacities admit: those are examined
+//   4. kfq_lines_kernel    per tile: nl[i] = the offset of line end i (the final call's text end closes the last line)
+//   5. kfq_records_kernel  a thread per record: the four rules, an atomic minimum of (offset << 3 | rule) over the bad
+//                          records, the record's positions (bases + separator) and their sum per block of 256 records
+//   6. kfq_total_kernel    one workgroup: scans the block sums, decides the verdict, writes the results
+//   7. kfq_offsets_kernel  per block of 256 records: the offsets (to the scratch and the caller), and word_rec[w] = the
+//                          record that position 64 w lies in -- a record of more than 8 words is spread by its whole block
+//   8. kfq_pack_kernel     a wave per 64 positions: record of the first position from word_rec, the next 64 offsets in
+//                          the lanes (offsets rise by >= 1: a record's separator), an OR over the wave marks the positions
+//                          where records begin, a popcount gives each lane its record; base byte and quality byte are
+//                          loaded; three ballots are the mask word and, interleaved, the two packed words.  The waves
+//                          behind the last position write the padding words of kdf_stream_words.
+// 7 and 8 read the verdict of 6 and do nothing after a refusal, so the host synchronises once.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kdf.h"
+#include "kdf_scan.h"
+
+#define KFQ_TILE KDF_FASTQ_TILE_BYTES
+static_assert(KFQ_TILE == 256 * 16, "a tile is 256 lanes of 16 bytes");
+#define KFQ_REC_BLOCK 256                      // records per workgroup of the record passes
+#define KFQ_SELF_WORDS 8                       // a record of more words of 64 positions is spread over word_rec by its block
+// control words (uint64)
+enum { KFQ_N_EFF = 0, KFQ_NL, KFQ_LINES, KFQ_N_REC, KFQ_N_CHK, KFQ_FIRST_BAD, KFQ_ROOM, KFQ_RES = 8, KFQ_CTL_WORDS = 12 };
+// the results, ctl[KFQ_RES ..]: [0] n_bases [1] n_reads [2] consumed [3] verdict | (offset << 3 | rule) << 8
+enum { KFQ_OK = 0, KFQ_ERR_ROOM = 1, KFQ_ERR_FORMAT = 2, KFQ_NOTHING = 3 };
+
+// the arrays of one call in the engine's scratch
+struct KfqScratchView {
+    unsigned long long *ctl;                   // [KFQ_CTL_WORDS]
+    uint32_t *tile_nl;                         // [tiles]: line ends of a tile, then the number of the tile's first
+    uint32_t *nl;                              // [4 r_cap]: offsets of the line ends
+    unsigned long long *off;                   // [r_cap + 1]: positions of a record, then its offset
+    unsigned long long *bsum;                  // [ceil(r_cap / KFQ_REC_BLOCK)]: positions of a block of records, then its offset
+    uint32_t *word_rec;                        // [ceil(pos_cap / 64)]
+};
+
+// The text as 16-byte granules of the memory it lies in: granule g holds the text offsets [16 g - skew, 16 g - skew + 16),
+// skew = the text's address mod 16, so a granule that lies wholly inside the text is ONE aligned 16-byte load at any
+// alignment of the text; the first and the last granule are read byte by byte.  s0: the text offset of the granule's first
+// byte (negative in the first granule of a skewed text).  -> bit i: byte s0 + i is a '\n' below n_eff
+__device__ __forceinline__ uint32_t kfq_line_ends(const uint8_t *__restrict__ t, uint64_t n, uint64_t n_eff, int64_t s0) {
+    if (s0 >= (int64_t)n_eff) return 0;
+    uint32_t w[4];
+    if (s0 >= 0 && (uint64_t)s0 + 16 <= n) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(t + s0);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else {
+        w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (s0 + i >= 0 && s0 + i < (int64_t)n_eff) w[i >> 2] |= (uint32_t)t[s0 + i] << (8 * (i & 3));
+    }
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t x = w[j] ^ 0x0A0A0A0Au;                         // a zero byte where a '\n' was
+        const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu) >> 7;      // bit 0 / 8 / 16 / 24
+        m |= ((z | z >> 7 | z >> 14 | z >> 21) & 0xFu) << (4 * j);
+    }
+    const int64_t left = (int64_t)n_eff - s0;
+    return left >= 16 ? m : m & ((1u << left) - 1u);
+}
+
+__global__ __launch_bounds__(256) void kfq_end_kernel(const uint8_t *__restrict__ t, uint64_t n, int final_chunk, unsigned long long *__restrict__ ctl) {
+    __shared__ unsigned long long last_other;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) last_other = 0;
+    __syncthreads();
+    for (uint64_t end = n; end > 0; end -= end < 256 ? end : 256) {
+        if (tid < end) {
+            const uint8_t c = t[end - 1 - tid];
+            if (c != '\n' && c != '\r') atomicMax(&last_other, (unsigned long long)(end - tid));
+        }
+        __syncthreads();
+        const unsigned long long found = last_other;
+        __syncthreads();                                               // (nobody raises it again before everybody has read it)
+        if (found) break;
+    }
+    // the final call's text ends there; a call that is not the last sees the first line end behind it
+    uint64_t n_eff = last_other;
+    if (!final_chunk) {
+        while (n_eff < n && t[n_eff] == '\r') ++n_eff;
+        n_eff = min(n_eff + 1, n);
+    }
+    if (tid < KFQ_CTL_WORDS) ctl[tid] = tid == KFQ_N_EFF ? n_eff : tid == KFQ_FIRST_BAD ? ~0ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void kfq_count_kernel(const uint8_t *__restrict__ t, uint64_t n, uint32_t skew, const unsigned long long *__restrict__ ctl,
+                                                        uint32_t *__restrict__ tile_nl) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t tid = threadIdx.x;
+    uint32_t v = (uint32_t)__popc(kfq_line_ends(t, n, ctl[KFQ_N_EFF], (int64_t)((uint64_t)blockIdx.x * KFQ_TILE + 16u * tid) - skew));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) wsum[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) tile_nl[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One workgroup of 256; thread i owns the tiles [i * per, (i + 1) * per).  cap_rec: the records the caller's buffers admit;
+// r_cap: the records the scratch admits (<= cap_rec; a well-formed text has no more, see kdf_fastqfeed.hip).
+__global__ __launch_bounds__(256) void kfq_scan_kernel(uint32_t *__restrict__ tile_nl, uint64_t nt, int final_chunk, uint64_t cap_rec, uint64_t r_cap,
+                                                       unsigned long long *__restrict__ ctl) {
+    __shared__ uint32_t ws[17];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t per = (nt + 255) / 256, b = min(nt, tid * per), e = min(nt, b + per);
+    uint32_t sum = 0;
+    for (uint64_t i = b; i < e; ++i) sum += tile_nl[i];
+    uint32_t total;
+    uint32_t run = kb_block_exscan(sum, ws, &total);                   // (a chunk has at most 2^31 bytes)
+    for (uint64_t i = b; i < e; ++i) { const uint32_t c = tile_nl[i]; tile_nl[i] = run; run += c; }
+    if (tid == 0) {
+        const uint64_t n_eff = ctl[KFQ_N_EFF];
+        const uint64_t lines = final_chunk ? (n_eff ? (uint64_t)total + 1 : 0) : total;      // (the text's end closes the last line)
+        const uint64_t n_rec = final_chunk ? (lines + 3) / 4 : lines / 4;
+        ctl[KFQ_NL] = total; ctl[KFQ_LINES] = lines; ctl[KFQ_N_REC] = n_rec;
+        ctl[KFQ_N_CHK] = min(n_rec, r_cap);
+        ctl[KFQ_ROOM] = n_rec > cap_rec;
+    }
+}
+
+__global__ __launch_bounds__(256) void kfq_lines_kernel(const uint8_t *__restrict__ t, uint64_t n, uint32_t skew, int final_chunk,
+                                                        const unsigned long long *__restrict__ ctl, const uint32_t *__restrict__ tile_nl,
+                                                        uint32_t *__restrict__ nl) {
+    __shared__ uint32_t ws[17];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_eff = ctl[KFQ_N_EFF], keep = 4 * ctl[KFQ_N_CHK];
+    const int64_t s0 = (int64_t)((uint64_t)blockIdx.x * KFQ_TILE + 16u * tid) - skew;
+    uint32_t m = kfq_line_ends(t, n, n_eff, s0);
+    uint64_t idx = (uint64_t)tile_nl[blockIdx.x] + kb_block_exscan((uint32_t)__popc(m), ws, nullptr);
+    for (; m && idx < keep; m &= m - 1, ++idx) nl[idx] = (uint32_t)(s0 + (uint32_t)(__ffs(m) - 1));
+    if (blockIdx.x == 0 && tid == 0 && final_chunk && n_eff && ctl[KFQ_NL] < keep) nl[ctl[KFQ_NL]] = (uint32_t)n_eff;
+}
+
+// the line [s, e) without the '\r' directly in front of its end
+__device__ __forceinline__ uint32_t kfq_strip(const uint8_t *__restrict__ t, uint32_t s, uint32_t e) {
+    while (e > s && t[e - 1] == '\r') --e;
+    return e;
+}
+
+__global__ __launch_bounds__(KFQ_REC_BLOCK) void kfq_records_kernel(const uint8_t *__restrict__ t, int final_chunk, unsigned long long *__restrict__ ctl,
+                                                                    const uint32_t *__restrict__ nl, unsigned long long *__restrict__ off,
+                                                                    unsigned long long *__restrict__ bsum) {
+    __shared__ uint32_t wsum[KFQ_REC_BLOCK / 64];
+    const uint64_t n_chk = ctl[KFQ_N_CHK], lines = ctl[KFQ_LINES], r = (uint64_t)blockIdx.x * KFQ_REC_BLOCK + threadIdx.x;
+    if ((uint64_t)blockIdx.x * KFQ_REC_BLOCK >= n_chk) return;
+    uint32_t positions = 0;
+    if (r < n_chk) {
+        const uint32_t have = final_chunk && lines - 4 * r < 4 ? (uint32_t)(lines - 4 * r) : 4u;       // lines of the record: 1 .. 4
+        const uint32_t s0 = r ? nl[4 * r - 1] + 1 : 0, e0 = nl[4 * r];
+        uint32_t rule = (s0 < e0 && t[s0] == '@') ? 0u : KDF_FQ_BAD_HEADER, len = 0;
+        if (have >= 2) {
+            const uint32_t s1 = e0 + 1, e1 = nl[4 * r + 1];
+            len = kfq_strip(t, s1, e1) - s1;
+            if (have >= 3) {
+                const uint32_t s2 = e1 + 1, e2 = nl[4 * r + 2];
+                if (!rule && !(s2 < e2 && t[s2] == '+')) rule = KDF_FQ_BAD_PLUS;
+                if (have == 4) {
+                    const uint32_t s3 = e2 + 1;
+                    if (!rule && kfq_strip(t, s3, nl[4 * r + 3]) - s3 != len) rule = KDF_FQ_LENGTH;
+                }
+            }
+        }
+        if (!rule && have < 4 && !(have == 3 && len == 0)) rule = KDF_FQ_TRUNCATED;      // (three lines and no bases: the quality line is empty)
+        if (rule) atomicMin(&ctl[KFQ_FIRST_BAD], (unsigned long long)s0 << 3 | rule);
+        positions = len + 1;
+        off[r] = positions;
+    }
+    uint32_t v = positions;                                            // (the text of a call has fewer than 2^31 bases)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) bsum[blockIdx.x] = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One workgroup of 256 behind the record pass.  nothing: a call that is not the last and has no complete record writes nothing.
+__global__ __launch_bounds__(256) void kfq_total_kernel(uint64_t n, int final_chunk, uint64_t cap_bases, const uint32_t *__restrict__ nl,
+                                                        unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ ctl) {
+    __shared__ unsigned long long a[256];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_rec = ctl[KFQ_N_REC], n_chk = ctl[KFQ_N_CHK], room = ctl[KFQ_ROOM];
+    const uint64_t nb = (n_chk + KFQ_REC_BLOCK - 1) / KFQ_REC_BLOCK, per = (nb + 255) / 256, b = min(nb, tid * per), e = min(nb, b + per);
+    unsigned long long sum = 0;
+    for (uint64_t i = b; i < e; ++i) sum += bsum[i];
+    a[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < 256; o <<= 1) {
+        const unsigned long long v = tid >= o ? a[tid - o] : 0ull;
+        __syncthreads();
+        a[tid] += v;
+        __syncthreads();
+    }
+    unsigned long long run = a[tid] - sum;
+    for (uint64_t i = b; i < e; ++i) { const unsigned long long c = bsum[i]; bsum[i] = run; run += c; }
+    if (tid == 0) {
+        const uint64_t n_bases = a[255], bad = ctl[KFQ_FIRST_BAD];
+        uint64_t verdict = KFQ_OK;
+        if (bad != ~0ull) verdict = KFQ_ERR_FORMAT | bad << 8;                      // (among the records the capacities admit)
+        else if (room || n_chk < n_rec || n_bases > cap_bases) verdict = KFQ_ERR_ROOM;      // (n_chk < n_rec without room or a bad record cannot be: a guard)
+        else if (!final_chunk && n_rec == 0) verdict = KFQ_NOTHING;
+        ctl[KFQ_RES + 0] = n_bases; ctl[KFQ_RES + 1] = n_rec;
+        ctl[KFQ_RES + 2] = final_chunk ? n : (n_rec && verdict == KFQ_OK ? (uint64_t)nl[4 * n_rec - 1] + 1 : 0);
+        ctl[KFQ_RES + 3] = verdict;
+    }
+}
+
+__global__ __launch_bounds__(KFQ_REC_BLOCK) void kfq_offsets_kernel(const unsigned long long *__restrict__ ctl, const unsigned long long *__restrict__ bsum,
+                                                                    unsigned long long *__restrict__ off, uint32_t *__restrict__ word_rec,
+                                                                    int64_t *__restrict__ offsets) {
+    __shared__ uint32_t ws[17];
+    __shared__ uint32_t n_long, long_rec[KFQ_REC_BLOCK];
+    __shared__ unsigned long long long_w0[KFQ_REC_BLOCK], long_w1[KFQ_REC_BLOCK];
+    if (ctl[KFQ_RES + 3] != KFQ_OK) return;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_rec = ctl[KFQ_RES + 1], n_bases = ctl[KFQ_RES + 0], r0 = (uint64_t)blockIdx.x * KFQ_REC_BLOCK, r = r0 + tid;
+    if (blockIdx.x == 0 && tid == 0) {
+        off[n_rec] = n_bases;
+        if (offsets) offsets[n_rec] = (int64_t)n_bases;
+    }
+    if (r0 >= n_rec) return;
+    if (tid == 0) n_long = 0;
+    const uint32_t positions = r < n_rec ? (uint32_t)off[r] : 0u;
+    const uint64_t o = bsum[blockIdx.x] + kb_block_exscan(positions, ws, nullptr);     // (its barriers publish n_long)
+    if (r < n_rec) {
+        off[r] = o;
+        if (offsets) offsets[r] = (int64_t)o;
+        const uint64_t w0 = (o + 63) / 64, w1 = (o + positions + 63) / 64;             // the words whose first position is the record's
+        if (w1 - w0 <= KFQ_SELF_WORDS) {
+            for (uint64_t w = w0; w < w1; ++w) word_rec[w] = (uint32_t)r;
+        } else {
+            const uint32_t i = atomicAdd(&n_long, 1u);
+            long_rec[i] = (uint32_t)r; long_w0[i] = w0; long_w1[i] = w1;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = 0; i < n_long; ++i)
+        for (uint64_t w = long_w0[i] + tid; w < long_w1[i]; w += KFQ_REC_BLOCK) word_rec[w] = long_rec[i];
+}
+
+// bit i of x -> bit 2 i
+__device__ __forceinline__ uint64_t kfq_spread(uint64_t x) {
+    x = (x | x << 16) & 0x0000FFFF0000FFFFull;
+    x = (x | x << 8) & 0x00FF00FF00FF00FFull;
+    x = (x | x << 4) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | x << 2) & 0x3333333333333333ull;
+    x = (x | x << 1) & 0x5555555555555555ull;
+    return x;
+}
+
+// A/C/G/T in either case -> 0 .. 3, anything else -> 4
+__device__ __forceinline__ uint32_t kfq_code(uint32_t c) {
+    const uint32_t u = c & 0xDFu, x = (u >> 1) & 3u;
+    return (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? x ^ (x >> 1) : 4u;
+}
+
+// A workgroup of 4 waves; wave w of the grid owns the positions [64 w, 64 w + 64): mask word w, packed words 2 w and 2 w + 1.
+template <bool QUAL>
+__global__ __launch_bounds__(256) void kfq_pack_kernel(const uint8_t *__restrict__ t, uint32_t min_qual, const unsigned long long *__restrict__ ctl,
+                                                       const uint32_t *__restrict__ nl, const unsigned long long *__restrict__ off,
+                                                       const uint32_t *__restrict__ word_rec, uint64_t *__restrict__ packed, uint64_t *__restrict__ invalid) {
+    if (ctl[KFQ_RES + 3] != KFQ_OK) return;
+    const uint64_t n_bases = ctl[KFQ_RES + 0], n_rec = ctl[KFQ_RES + 1], words = (n_bases + 63) / 64;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= words + 2) return;                                        // (wave-uniform)
+    uint32_t code = 4;
+    if (w < words) {
+        const uint64_t base = 64 * w, p = base + lane, r0 = word_rec[w];
+        // lane j: the start of record r0 + 1 + j; those inside the wave's positions mark where records begin
+        const uint64_t next = r0 + 1 + lane <= n_rec ? off[r0 + 1 + lane] : ~0ull;
+        unsigned long long starts = next - base < 64 ? 1ull << (next - base) : 0ull;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) starts |= __shfl_xor(starts, o);
+        const uint32_t ahead = (uint32_t)__popcll(starts & (~0ull >> (63 - lane)));      // records that begin in (base, p]
+        const uint64_t first = off[r0];
+        const uint64_t prev_start = __shfl((unsigned long long)next, ahead ? (int)ahead - 1 : 0), end = __shfl((unsigned long long)next, (int)ahead);
+        const uint64_t start = ahead ? prev_start : first, rec = r0 + ahead;
+        if (p < n_bases && p + 1 < end) {                              // (p + 1 == end: the separator)
+            const uint32_t j = (uint32_t)(p - start);
+            code = kfq_code(t[nl[4 * rec] + 1 + j]);
+            if (QUAL && t[nl[4 * rec + 2] + 1 + j] < min_qual) code = 4;
+        }
+    }
+    const unsigned long long inv = __ballot(code > 3), lo = __ballot(code & 1u), hi = __ballot((code >> 1) & 1u);      // (4: bits 0)
+    if (lane < 2) packed[2 * w + lane] = kfq_spread((lo >> (32 * lane)) & 0xFFFFFFFFull) | kfq_spread((hi >> (32 * lane)) & 0xFFFFFFFFull) << 1;
+    else if (lane == 2) invalid[w] = inv;
+}
+

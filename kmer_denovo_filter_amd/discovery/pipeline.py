@@ -26,6 +26,7 @@ from ..core.jellyfish_wrappers import (
     _device,
     _engine_capacity_hint,
     _estimate_jf_hash_size,
+    _sample_bytes,
     _format_elapsed,
     _format_file_size,
     _merge_filter_counts,
@@ -34,6 +35,7 @@ from ..core.jellyfish_wrappers import (
 )
 from ..engine import mirror_engine
 from ..kmer_fasta import (device_fasta, load_kmer_set, read_kmer_fasta_keys_device, remove_with_sidecar, store_kmer_set)
+from ..reads import refuse_fastq
 
 logger = logging.getLogger(__name__)
 
@@ -62,7 +64,7 @@ def _device_free_bytes(device):
 
 def _child_table_bytes(child_bam, world=1, kmer_size=31):
     """Table bytes the rule of thumb of _child_key_parts plans for the whole key space of one rank."""
-    need = 4.6 * os.path.getsize(child_bam) / max(1, world)      # (several ranks: every rank holds its share of the keys twice -- local + owned)
+    need = 4.6 * _sample_bytes(child_bam) / max(1, world)      # (several ranks: every rank holds its share of the keys twice -- local + owned)
     W = keys.key_words(kmer_size)
     if W > 2:
         need *= (8 * W + 4) / 12.0
@@ -700,6 +702,7 @@ def _write_informative_reads_discovery(child_bam, ref_fasta, proband_unique_kmer
     on the same three input kinds); the copy, sort and index are
     ``kdf_bam_write_subset`` instead of pysam / ``samtools sort`` / ``samtools index``.
     Returns the number of records written."""
+    refuse_fastq(child_bam, "the informative-reads BAM of discovery mode")
     from ..core import bam_scanner
     from ..reads import bam_reader, write_bam_subset
     bam_scanner._init_scan_worker(proband_unique_kmers_or_path or set(), kmer_size)

@@ -35,7 +35,7 @@ raises.
 """
 from __future__ import annotations
 
-from ctypes import POINTER, byref, c_uint64, c_void_p
+from ctypes import POINTER, byref, c_uint32, c_uint64, c_void_p
 from typing import Optional, Tuple
 
 import numpy as np
@@ -475,6 +475,53 @@ class KmerEngine:
                                           _vp(prev.packed) if prev is not None else None, _vp(prev.invalid) if prev is not None else None,
                                           prev.n_bases if prev is not None else 0, int(carry), _vp(packed), _vp(invalid), cap_bases,
                                           _vp(offs), cap_reads if want_offsets else 0, byref(nb), byref(nr), byref(used)))
+        pw, mw = stream_words(nb.value)
+        offsets = offs[:nr.value + 1].copy() if want_offsets else np.array([0, nb.value], np.int64)
+        return ReadStream(packed[:pw].copy(), invalid[:mw].copy(), nb.value, offsets), used.value
+
+    # -- device FASTQ feeder -------------------------------------------------
+    def _fastq_packed(self, rc, nb, nr, used, bad, rule):
+        """(n_bases, n_reads, consumed) of a kdf_fastq_pack call, or its error: a text that is no FASTQ raises
+        ``FastqFormatError`` with the offset of the first bad record within the call's text and the rule it breaks."""
+        if rc == _native.KDF_ERR_IO and rule.value:
+            msg = self._lib.kdf_last_error(self._h)
+            raise _native.FastqFormatError(rc, msg.decode(errors="replace") if msg else "bad record", bad.value, rule.value)
+        self._ck(rc)
+        return nb.value, nr.value, used.value
+
+    def fastq_pack_dev(self, d_text: Optional[int], n_bytes: int, final_chunk: bool, state: "_native.FastqState", d_packed: int,
+                       d_invalid: int, cap_bases: int, d_offsets: Optional[int] = None, cap_reads: int = 0,
+                       min_qual: int = 0) -> Tuple[int, int, int]:
+        """One chunk of raw four-line FASTQ text in HBM -> the packed stream of the whole records it holds, in
+        caller-owned HBM (buffers of the ``stream_words(cap_bases)`` sizes, ``cap_bases >= n_bytes // 2`` always
+        suffices; ``d_offsets``: int64[cap_reads + 1] or None).  A base whose quality byte is below ``min_qual`` (0: off)
+        is an invalid position.  ``state``: a ``FastqState``, zero before the first chunk, updated by the call.
+        -> (n_bases, n_reads, consumed): a chunk that is not the last leaves its incomplete last record to the caller.
+        Synchronises once; the table is not touched."""
+        p = lambda x: c_void_p(x) if x else None
+        nb, nr, used, bad, rule = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0), c_uint32(0)
+        rc = self._lib.kdf_fastq_pack(self._h, _native.KDF_MEM_DEVICE, p(d_text), int(n_bytes), int(bool(final_chunk)), int(min_qual), byref(state),
+                                      p(d_packed), p(d_invalid), int(cap_bases), p(d_offsets), int(cap_reads), byref(nb), byref(nr), byref(used),
+                                      byref(bad), byref(rule))
+        return self._fastq_packed(rc, nb, nr, used, bad, rule)
+
+    def fastq_pack(self, text, final_chunk: bool, state: "_native.FastqState", min_qual: int = 0,
+                   want_offsets: bool = True) -> Tuple[ReadStream, int]:
+        """The same from host bytes to a host ``ReadStream`` (offsets: the call's records), staged through the engine.
+        -> (stream, consumed)."""
+        raw = np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+        n = len(raw)
+        cap_bases, cap_reads = n // 2, n // 4
+        pw, mw = stream_words(cap_bases)
+        packed, invalid = np.zeros(pw, np.uint64), np.zeros(mw, np.uint64)
+        offs = np.zeros(cap_reads + 1, np.int64) if want_offsets else None
+        nb, nr, used, bad, rule = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0), c_uint32(0)
+        rc = self._lib.kdf_fastq_pack(self._h, _native.KDF_MEM_HOST, _vp(raw) if n else None, n, int(bool(final_chunk)), int(min_qual), byref(state),
+                                      _vp(packed), _vp(invalid), cap_bases, _vp(offs), cap_reads if want_offsets else 0, byref(nb), byref(nr),
+                                      byref(used), byref(bad), byref(rule))
+        self._fastq_packed(rc, nb, nr, used, bad, rule)
+        if not final_chunk and used.value == 0:                       # no complete record: nothing was written
+            return ReadStream(np.zeros(stream_words(0)[0], np.uint64), np.full(stream_words(0)[1], ~np.uint64(0)), 0, np.zeros(1, np.int64)), 0
         pw, mw = stream_words(nb.value)
         offsets = offs[:nr.value + 1].copy() if want_offsets else np.array([0, nb.value], np.int64)
         return ReadStream(packed[:pw].copy(), invalid[:mw].copy(), nb.value, offsets), used.value

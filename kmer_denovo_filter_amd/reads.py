@@ -971,6 +971,236 @@ def stream_fasta_device(engine, path: str, k: int, filtered: bool = False, tally
     return int(state.records)
 
 
+LAST_FASTQ_FEEDER = None      # what the last stream_fastq_device call did: {"path", "files", "chunks", "bytes", "records", "positions", "compressed", "min_qual"}
+FASTQ_SUFFIXES = (".fastq", ".fq", ".fastq.gz", ".fq.gz")
+
+
+def is_fastq_path(path) -> bool:
+    """The name says FASTQ: one path that ends in .fastq / .fq / .fastq.gz / .fq.gz, or a comma-separated list of such."""
+    if path is None:
+        return False
+    parts = fastq_paths(path)
+    return bool(parts) and all(p.lower().endswith(FASTQ_SUFFIXES) for p in parts)
+
+
+def fastq_paths(paths) -> List[str]:
+    """One path, a comma-separated list of paths or a sequence of paths -> the list of paths (R1, R2, ...)."""
+    import os
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        return [p for p in os.fsdecode(os.fspath(paths)).split(",") if p]
+    return [os.fsdecode(os.fspath(p)) for p in paths]
+
+
+def refuse_fastq(path, what: str):
+    """The paths that need an alignment name a FASTQ child and refuse it."""
+    if is_fastq_path(path):
+        raise ValueError(f"{what} needs aligned reads (a BAM): {path} is FASTQ, which only the alignment-free counting legs take")
+
+
+def fastq_min_qual(value=None) -> int:
+    """``KDF_FASTQ_MIN_QUAL`` (or ``value``) -> the byte below which a quality masks its base (`jellyfish count -Q`): a
+    string of digits is that number (0 .. 255), any other single character is its code; unset, empty or 0: off."""
+    import os
+    v = os.environ.get("KDF_FASTQ_MIN_QUAL", "") if value is None else value
+    if isinstance(v, int):
+        q = v
+    elif v == "":
+        q = 0
+    elif v.isdigit():
+        q = int(v)
+    elif len(v) == 1:
+        q = ord(v)
+    else:
+        raise ValueError(f"KDF_FASTQ_MIN_QUAL={v!r}: one character or a number 0 .. 255")
+    if not 0 <= q <= 255:
+        raise ValueError(f"KDF_FASTQ_MIN_QUAL={v!r}: outside 0 .. 255")
+    return q
+
+
+def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = False, sketch: bool = False, spool=None, min_qual: int = 0,
+                        chunk_bytes: Optional[int] = None) -> int:
+    """Count (``filtered``: count --if; ``tally``: prefilter pass 1; ``sketch``: sizing pass) four-line FASTQ files through
+    the DEVICE feeder.  ``paths``: one path or a sequence of paths (R1, R2, ...), streamed one after the other; a gzip or
+    multi-member gzip file is inflated on the host.  One reader thread fills two page-locked buffers with the text
+    (``chunk_bytes`` each; default KDF_FASTQ_FEED_MB MiB, 64), a copy stream uploads chunk i + 1 while the engine packs chunk
+    i on the device (``fastq_pack_dev``) into one of two alternating stream buffers and takes the stream where it lies in
+    HBM.  A call consumes whole records; the unconsumed tail of a chunk is copied in front of the next on the device.
+    ``min_qual`` > 0 masks the bases of a lower quality byte (`jellyfish count -Q`).  ``spool``: as in
+    ``stream_bam_device``; with ``spool.keep_reads`` the records' offsets are kept.  For the call's duration the engine runs
+    on a stream of the feeder's.  Returns the number of records; ``LAST_FASTQ_FEEDER`` records files, chunks, bytes, records
+    and positions.  A text that is no FASTQ raises ``FastqFormatError`` with the offset within its file."""
+    global LAST_FASTQ_FEEDER
+    import os
+    import queue
+    import threading
+    import torch
+    files = fastq_paths(paths)
+    if not files:
+        raise ValueError("stream_fastq_device: no path")
+    if chunk_bytes is None:
+        chunk_bytes = int(float(os.environ.get("KDF_FASTQ_FEED_MB", "64")) * (1 << 20))
+    srcs = [_FastaText(p) for p in files]                         # (the text of a file, plain or gzip: nothing of it is FASTA's)
+    if not any(s.compressed for s in srcs):                       # small files pin and allocate no more than they need
+        chunk_bytes = min(int(chunk_bytes), max(os.path.getsize(p) for p in files) + 16)
+    chunk_bytes = max(16, int(chunk_bytes) // 16 * 16)
+    dev = torch.device("cuda", engine.device)
+    pinned = _pinned_bytes(2, chunk_bytes)
+    free, ready = queue.Queue(), queue.Queue()
+    free.put(0)
+    free.put(1)
+    stop = threading.Event()
+
+    def produce():
+        try:
+            for f, src in enumerate(srcs):
+                while not stop.is_set():
+                    i = free.get()
+                    if i is None:
+                        return
+                    n = src.readinto(pinned.buffers[i])
+                    if n == 0:
+                        free.put(i)
+                        break
+                    ready.put((f, i, n))
+                ready.put((f, None, 0))                              # the file's end
+            ready.put(None)
+        except BaseException as ex:  # noqa: BLE001 -- handed to the consumer
+            ready.put(ex)
+
+    reader = threading.Thread(target=produce, name="kdf-fastq-text", daemon=True)
+    work, copy_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    engine.synchronize()
+    engine.set_stream(work.cuda_stream)
+    info = {"path": "device", "files": len(files), "chunks": 0, "bytes": 0, "compressed": any(s.compressed for s in srcs), "min_qual": int(min_qual)}
+    state = _native.FastqState()
+    spooling = [spool]
+    keep_reads = bool(getattr(spool, "keep_reads", False))
+    # a text slot: the chunk at [chunk_bytes, 2 chunk_bytes), and directly in front of it the tail the call on the OTHER
+    # slot left (at most chunk_bytes): the copy stream writes the upper half only, the work stream the lower
+    text = [torch.empty(2 * chunk_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+    used = [None, None]                                          # recorded on the work stream behind the last reader of the slot's chunk
+    out = [None, None]                                           # (packed, invalid, offsets, cap_bases, cap_reads) of the alternating stream buffers
+    turn = [0]
+    left = [0, 0]                                                # (text slot, bytes) of the unconsumed tail: it ends at the slot's chunk_bytes
+    file_base = [0]                                              # bytes of the current file that earlier calls consumed
+    cur_file = [0]
+
+    def room(j, n_text):
+        cap_bases, cap_reads = n_text // 2, (n_text // 4 if keep_reads else 0)
+        if out[j] is None or out[j][3] < cap_bases or out[j][4] < cap_reads:
+            pw, mw = stream_words(cap_bases)
+            torch.cuda.current_stream(dev).synchronize()          # (memory the allocator hands out again may still be in use on this stream)
+            out[j] = (torch.empty(pw, dtype=torch.int64, device=dev), torch.empty(mw, dtype=torch.int64, device=dev),
+                      torch.empty(cap_reads + 1, dtype=torch.int64, device=dev) if keep_reads else None, cap_bases, cap_reads)
+        return out[j]
+
+    def pack(t, n_text, final):
+        """pack t[:n_text] into the stream buffer the previous stream does not lie in, hand it to the engine -> consumed"""
+        j = turn[0]
+        turn[0] ^= 1
+        packed, invalid, offs, cap_bases, cap_reads = room(j, n_text)
+        try:
+            nb, nr, consumed = engine.fastq_pack_dev(t.data_ptr() if n_text else None, n_text, final, state, packed.data_ptr(), invalid.data_ptr(),
+                                                     cap_bases, offs.data_ptr() if offs is not None else None, cap_reads, min_qual)
+        except _native.FastqFormatError as ex:
+            raise _native.FastqFormatError(ex.code, f"{files[cur_file[0]]}: byte {file_base[0] + ex.offset}: {ex}", file_base[0] + ex.offset, ex.rule) from None
+        file_base[0] += consumed
+        if nb:
+            dp, dm = packed.data_ptr(), invalid.data_ptr()
+            if spooling[0] is not None:
+                try:
+                    if keep_reads:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream, d_offsets=offs.data_ptr(), n_reads=nr)
+                    else:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream)
+                except _native.KdfError as ex:
+                    if ex.code != _native.KDF_ERR_NOMEM:
+                        raise
+                    spooling[0] = None                               # overflowed: the pass itself goes on
+            if sketch:
+                engine.sketch_add_dev(dp, dm, nb)
+            elif tally:
+                engine.prefilter_add_dev(dp, dm, nb)
+            elif filtered:
+                engine.count_filtered_dev(dp, dm, nb)
+            else:
+                engine.count_dev(dp, dm, nb)
+        return consumed
+
+    try:
+        reader.start()
+        pending, cur = None, 0                                       # pending: (text slot, pinned index, bytes, copied event)
+        with torch.cuda.stream(work):
+            def finish(p):
+                slot, i, n, copied = p
+                copied.synchronize()
+                free.put(i)                                          # the copy is done: the pinned buffer goes back to the reader
+                work.wait_event(copied)
+                start = chunk_bytes - left[1]                        # (the tail was put in front of this slot's chunk)
+                n_text = left[1] + n
+                consumed = pack(text[slot][start:start + n_text], n_text, False)
+                rest = n_text - consumed
+                if rest > chunk_bytes:
+                    raise ValueError(f"stream_fastq_device: {files[cur_file[0]]}: {rest} bytes behind byte {file_base[0]} hold no complete FASTQ "
+                                     f"record and a chunk is {chunk_bytes} bytes: raise KDF_FASTQ_FEED_MB (a chunk must hold the longest record)")
+                if rest:                                             # in front of the other slot's chunk, where the next call reads
+                    text[slot ^ 1][chunk_bytes - rest:chunk_bytes].copy_(text[slot][start + consumed:start + n_text])
+                left[0], left[1] = slot ^ 1, rest
+                used[slot] = torch.cuda.Event()
+                used[slot].record(work)
+                info["chunks"] += 1
+                info["bytes"] += n
+
+            def close_file():
+                """the file's end: what the last call left is the final call's text"""
+                slot, m = left
+                if m:
+                    pack(text[slot][chunk_bytes - m:chunk_bytes], m, True)
+                left[1] = 0
+                file_base[0] = 0
+
+            while True:
+                item = ready.get()
+                if item is None:
+                    break
+                if isinstance(item, BaseException):
+                    raise item
+                f, i, n = item
+                cur_file[0] = f
+                if i is None:                                        # the end of file f
+                    if pending is not None:
+                        finish(pending)
+                        pending = None
+                    close_file()
+                    continue
+                with torch.cuda.stream(copy_stream):
+                    if used[cur] is not None:
+                        copy_stream.wait_event(used[cur])            # the pack and the tail copy that read this slot's last chunk
+                    text[cur][chunk_bytes:chunk_bytes + n].copy_(torch.from_numpy(pinned.buffers[i][:n]), non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record(copy_stream)
+                if pending is not None:
+                    finish(pending)
+                pending = (cur, i, n, copied)
+                cur ^= 1
+    finally:
+        stop.set()
+        free.put(None)
+        if reader.ident is not None:
+            reader.join()
+        try:
+            engine.synchronize()
+        finally:
+            engine.set_stream(None)
+            copy_stream.synchronize()                                # no copy may still read a pinned buffer the next caller will fill
+            for s in srcs:
+                s.close()
+    info["records"] = int(state.records)
+    info["positions"] = int(state.positions)
+    LAST_FASTQ_FEEDER = info
+    return int(state.records)
+
+
 def write_bam_subset(src_bam: str, dst_bam: str, ordinals, aux_fields=None, sort_and_index: bool = True,
                      threads: int = 1) -> int:
     """Copy the records ``ordinals`` (ReadStream.ordinals values) of ``src_bam`` into

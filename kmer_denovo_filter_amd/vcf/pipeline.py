@@ -25,7 +25,7 @@ import numpy as np
 from ..alignment import reads_from_batch
 from ..core.jellyfish_wrappers import _scan_parent_jellyfish
 from ..kmer_utils import _is_symbolic, extract_variant_spanning_kmers, read_supports_alt
-from ..reads import bam_reader
+from ..reads import bam_reader, refuse_fastq
 
 logger = logging.getLogger(__name__)
 
@@ -122,6 +122,7 @@ def _collect_child_kmers(child_bam, ref_fasta, variants, kmer_size, min_baseq, m
                          flush_threshold=500_000):
     """Variant-spanning child k-mers -> ``kmer_fasta`` (``>{i}\\n{KMER}\\n``, de-duplicated
     per flush batch).  Returns (total_written, {variant key: [(read name, k-mers, supports_alt)]})."""
+    refuse_fastq(child_bam, "VCF mode")
     _require_vcf_k(kmer_size)
     by_chrom = collections.defaultdict(list)
     for v in variants:
@@ -236,6 +237,7 @@ def _write_informative_reads(child_bam, ref_fasta, informative_reads_by_variant,
     record it meets per read name; the same record is picked here from one pass
     over the file: smallest (region rank, file order) among the records of that
     name overlapping a variant position."""
+    refuse_fastq(child_bam, "the informative-reads BAM of VCF mode")
     from ..reads import write_bam_subset
     read_to_variants = {}
     for var_key, names in informative_reads_by_variant.items():
