@@ -1340,6 +1340,73 @@ int kdf_fastq_pack(kdf_engine *h, int mem, const void *text, uint64_t n_bytes, i
                    uint64_t *n_bases, uint64_t *n_reads, uint64_t *consumed,
                    uint64_t *bad_offset, uint32_t *bad_rule);
 
+/* --------------------------------------------------- FASTQ record extract ---- */
+
+/* The records of a FASTQ chunk that the caller chose, back out as text: the raw text lies in HBM (or, with
+ * KDF_MEM_HOST, in host memory and is staged), `keep` holds one flag per record, and a kernel writes the kept records one
+ * behind the other, byte for byte.  It is the last step of "count, find the informative reads, hand only those on" for a
+ * sample that starts from FASTQ: kdf_fastq_pack gives the stream and the record offsets of a chunk, kdf_read_hits_dev the
+ * hits per record, and this call the text of the records that qualify, while the chunk is still in HBM.  The table is not
+ * touched and nothing is flushed.  ONE function with a `mem` argument.  (Its name carries the prefix of the KDF_FQ_*
+ * constants: the prefix kdf_fastq belongs to the feeder's one entry point.)
+ *
+ * RECORDS.  The records are delimited by THE RULE of kdf_fastq_pack (LINES, RECORDS, what a call that is not the last
+ * consumes, what the final call drops and completes).  For the same (text, n_bytes, final_chunk) the records, *consumed,
+ * the format errors (KDF_ERR_IO, *bad_offset, *bad_rule: the lowest record, its lowest rule) and their precedence are
+ * those of kdf_fastq_pack with capacities that suffice.  The call is self-contained: it finds the lines itself and relies
+ * on nothing that an earlier call left in the engine.  It neither takes nor changes a kdf_fastq_state.
+ *
+ * KEEP.  `keep` is uint8[n_reads]: a nonzero byte keeps record r of the call.  n_reads must be the number of records
+ * the call holds -- what kdf_fastq_pack returns in *n_reads for the same arguments; any other value is KDF_ERR_INVALID and
+ * nothing is written (the caller's flags and text have drifted apart).  A NULL keep with n_reads > 0 is KDF_ERR_INVALID.
+ *
+ * OUTPUT, per byte (this is the specification):
+ *   - out[0 .. *out_bytes) is the concatenation, in record order, of the kept records.
+ *   - A kept record is the bytes of the text from the first byte of its line 0 through the '\n' that ends its line 3,
+ *     verbatim: the header's text, every '\r', the text behind '+' and the quality line are copied unchanged.
+ *   - On the FINAL call the last record ends where the text ends in front of its trailing '\n' / '\r' bytes.  If a '\n'
+ *     is among those trailing bytes, the record runs on, verbatim, through the first of them (so "IIII\r\n\n\n" gives
+ *     "IIII\r\n").  If there is none -- the text's end closes the line -- the trailing '\r' are dropped and a '\n' is
+ *     written behind the line.  A last record of three lines with an empty sequence, whose quality line the rule
+ *     supplies, gets that line as "\n" behind its '+' line.  Trailing blank lines are dropped.  No other byte of the
+ *     output is not a byte of the text.
+ *   - Therefore *out_bytes <= *consumed + 2, and cap_out >= n_bytes + 2 always suffices.
+ *   - `out_offsets` may be NULL; else it is int64[n_reads + 1] and receives *n_kept + 1 entries: the byte offset in `out`
+ *     of each kept record, in order, and *out_bytes.
+ *   - Nothing outside out[0 .. *out_bytes) and those entries is written.  `out` and `text` may lie at any byte alignment.
+ *   - Needing more than cap_out bytes is KDF_ERR_INVALID -- after the format check and the check of n_reads -- and
+ *     nothing is written.
+ *   - A call that is not the last and holds no complete record is KDF_OK with *out_bytes == *n_kept == *consumed == 0 and
+ *     writes nothing (n_reads must be 0); so does n_bytes == 0, final or not.  A final call of a text of only '\n' / '\r'
+ *     holds no records either: *consumed == n_bytes.
+ *   - After every refusal the three results are 0.  Without a format error *bad_offset is ~0 and *bad_rule 0.
+ *   - A chunk takes at most 2^31 bytes.  Any mem other than KDF_MEM_HOST / KDF_MEM_DEVICE is KDF_ERR_INVALID.
+ *
+ * MEMORY.  KDF_MEM_DEVICE: text, keep, out and out_offsets are device pointers, used in place on the engine's stream.
+ * KDF_MEM_HOST: they are host arrays, staged through the engine's staging arena.  The scalar results are host memory with
+ * both.  The call synchronises once, because it learns the sizes and a possible error.
+ *
+ * WORK.  On the engine's stream: passes (1)-(5) of kdf_fastq_pack (the end of the text, line ends per tile, their scan,
+ * the line offsets, the rule check per record) by the same kernels; (6) a thread per record writes (kept, bytes in the
+ * output) -- 0 for a dropped record -- and the values are scanned as the feeder scans its positions (block sums, one
+ * workgroup over them, a pass that adds them back), which gives every record its offset in the output, the caller's
+ * offsets, and per tile of KDF_FASTQ_TILE_BYTES of OUTPUT the record its first byte lies in; (7) the copy kernel is
+ * output-driven: the tiles are laid over the 16-byte granules of the memory `out` lies in, a workgroup owns a tile and a
+ * lane a granule.  The lane finds its record by a binary search between the first records of its tile and of the next
+ * (the offsets do not fall, a dropped record shares its successor's, a kept record has 6 bytes or more: the last record at
+ * or below the byte is the kept one).  A granule inside one record's text is assembled from aligned 16-byte loads of the
+ * unaligned source, shifted in registers, and stored whole; a granule that spans a record boundary, holds a supplied
+ * '\n', or is the partial first or last granule of `out` is written byte by byte.  No atomics decide placement: the
+ * output is the same from run to run.  The grid of (7) is bounded and its workgroups stride over the tiles below
+ * *out_bytes, so the work is the records scanned plus the bytes kept.  Scratch: that of kdf_fastq_pack for
+ * n_bytes / 6 + 1 records, and 4 bytes per output tile.  Under kdf_profile(h, 1): stats "fastqextract_us" /
+ * "fastqextract_passes" (one pass per call that launches). */
+int kdf_fq_extract(kdf_engine *h, int mem, const void *text, uint64_t n_bytes, int final_chunk,
+                      const void *keep, uint64_t n_reads,
+                      void *out, uint64_t cap_out, void *out_offsets,
+                      uint64_t *out_bytes, uint64_t *n_kept, uint64_t *consumed,
+                      uint64_t *bad_offset, uint32_t *bad_rule);
+
 /* N4: the informative-reads BAM (discovery/pipeline.py:1979-2079 `_write_informative_reads_discovery`,
  * vcf/pipeline.py:1307-1357 `_write_informative_reads`: pysam write + `samtools sort` + `samtools index`).
  * Copies the records ordinals[0..n) (strictly ascending file record numbers, see

@@ -209,9 +209,12 @@ SYMBOLS = [
     # device FASTQ feeder (the state: FastqState below): one function with a `mem` argument
     ("kdf_fastq_pack", c_int, [_P, c_int, _P, c_uint64, c_int, c_uint32, _P, _P, _P, c_uint64, _P, c_uint64,
                                POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32)]),
+    # FASTQ record extract: the kept records of a chunk back out as text, one function with a `mem` argument
+    ("kdf_fq_extract", c_int, [_P, c_int, _P, c_uint64, c_int, _P, c_uint64, _P, c_uint64, _P,
+                                  POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32)]),
 ]
 
-KDF_MEM_HOST, KDF_MEM_DEVICE = 0, 1          # the `mem` argument of the index record codec and of the FASTQ feeder
+KDF_MEM_HOST, KDF_MEM_DEVICE = 0, 1          # the `mem` argument of the index record codec, the FASTQ feeder and the FASTQ record extract
 KDF_FA_IN_RECORD, KDF_FA_MID_LINE, KDF_FA_IN_HEADER = 1, 2, 4
 KDF_FASTA_TILE_BYTES = 4096
 

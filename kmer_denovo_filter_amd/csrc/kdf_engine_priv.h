@@ -40,8 +40,8 @@ struct KbPass;                            // kdf_binned.h (the core)
 #define KDF_MERGE_MIN_PAIRS (1u << 16)
 enum { PF_OFF = 0, PF_TALLYING = 1, PF_ARMED = 2 };      // stat "prefilter_state"
 // the timers of kdf_profile (EvTimer); stats "<name>_us" / "<name>_passes", the stream timer through kdf_profile_read
-enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_FA, T_IX, T_FQ, T_COUNT };
-static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta", "fastafeed", "indexcodec", "fastqfeed"};
+enum { T_STREAM = 0, T_PF, T_PFM, T_DEPTH, T_HITS, T_SK, T_HISTO, T_COV, T_VAR, T_BD_INF, T_BD_WALK, T_BD_PACK, T_JOIN, T_REG, T_KF, T_FA, T_IX, T_FQ, T_FX, T_COUNT };
+static const char *const TIMER_NAME[T_COUNT] = {nullptr, "prefilter", "prefilter_merge", "depth", "hits", "sketch", "histo", "coverage", "variants", "bamdev_inflate", "bamdev_walk", "bamdev_pack", "join", "regions", "kmerfasta", "fastafeed", "indexcodec", "fastqfeed", "fastqextract"};
 // The entry ring: A0/A1/B append a partitioned pass per call; kernel C applies all pending passes at once when the
 // table is needed or the ring is full (kb_flush_ring).  Reserved by upper bounds (one entry per stream position), so no
 // host round trip sits between the stages.  Host only: what the kernels take of it is KbPlan (kdf_device.h).
@@ -136,7 +136,7 @@ struct RegScratch { DevBuf scratch, perm; };                           // kdf_re
 struct KfScratch { DevBuf block_sums; };                               // kdf_kmerfasta.h: block sums of the record scan and its counters
 struct FaScratch { DevBuf scratch; };                                  // kdf_fastafeed.h: tile summaries, tile offsets and the control words
 struct IxScratch { DevBuf pos, ctl; };                                 // kdf_indexcodec.h: hash positions of kdf_jf_order; the first bad record of a decode
-struct FqScratch { DevBuf scratch; };                                  // kdf_fastqfeed.h: control words, tile counts, line ends, record offsets, block sums, the word index
+struct FqScratch { DevBuf scratch; };                                  // kdf_fastqfeed.h: control words, tile counts, line ends, record offsets, block sums, the word index (kdf_fq_extract: the output tiles' records)
 struct BdState {                                                       // device BAM feeder (kdf_bamdev.h)
     DevBuf inflated, status, read_offs;              // inflated span; block / sub-range status, counts, bases and totals; per-read sequence offsets
     // 1: every block of a batch is inflated by zlib and patched in as if the device decoder had rejected it (option

@@ -21,6 +21,18 @@
 //                          loaded; three ballots are the mask word and, interleaved, the two packed words.  The waves
 //                          behind the last position write the padding words of kdf_stream_words.
 // 7 and 8 read the verdict of 6 and do nothing after a refusal, so the host synchronises once.
+//
+// kdf_fq_extract (include/kdf.h, "FASTQ record extract") shares 1 .. 5 -- the records are the feeder's -- and goes on with
+//   6x. kfx_len_kernel     a thread per record: (kept << 32 | bytes the record takes in the output), 0 for a dropped one,
+//                          and their sum per block of 256 records; the last record of a final call fixes where its text ends
+//   7x. kfx_total_kernel   one workgroup: scans the block sums, decides the verdict, writes the results
+//   8x. kfx_offsets_kernel per block of 256 records: the byte offset of every record in the output (a plateau over dropped
+//                          records), the caller's offsets of the kept ones, and tile_rec[T] = the record that the first
+//                          byte of output tile T lies in
+//   9x. kfx_copy_kernel    output-driven: a workgroup per tile of 256 granules of 16 bytes of the OUTPUT's memory, a lane
+//                          per granule; the record by a binary search between tile_rec[T] and tile_rec[T + 1]; a granule
+//                          inside one record's text is two aligned 16-byte loads shifted together and ONE 16-byte store,
+//                          any other granule goes byte by byte
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,9 +45,11 @@ static_assert(KFQ_TILE == 256 * 16, "a tile is 256 lanes of 16 bytes");
 #define KFQ_REC_BLOCK 256                      // records per workgroup of the record passes
 #define KFQ_SELF_WORDS 8                       // a record of more words of 64 positions is spread over word_rec by its block
 // control words (uint64)
-enum { KFQ_N_EFF = 0, KFQ_NL, KFQ_LINES, KFQ_N_REC, KFQ_N_CHK, KFQ_FIRST_BAD, KFQ_ROOM, KFQ_RES = 8, KFQ_CTL_WORDS = 12 };
+// (KFX_LAST_END: kdf_fq_extract's, the end of the last record's text on a final call)
+enum { KFQ_N_EFF = 0, KFQ_NL, KFQ_LINES, KFQ_N_REC, KFQ_N_CHK, KFQ_FIRST_BAD, KFQ_ROOM, KFX_LAST_END, KFQ_RES = 8, KFQ_CTL_WORDS = 12 };
 // the results, ctl[KFQ_RES ..]: [0] n_bases [1] n_reads [2] consumed [3] verdict | (offset << 3 | rule) << 8
-enum { KFQ_OK = 0, KFQ_ERR_ROOM = 1, KFQ_ERR_FORMAT = 2, KFQ_NOTHING = 3 };
+// (kdf_fq_extract: [0] out_bytes [1] n_kept | records << 32); KFX_ERR_COUNT: the caller's n_reads is not the records'
+enum { KFQ_OK = 0, KFQ_ERR_ROOM = 1, KFQ_ERR_FORMAT = 2, KFQ_NOTHING = 3, KFX_ERR_COUNT = 4 };
 
 // the arrays of one call in the engine's scratch
 struct KfqScratchView {
@@ -44,7 +58,8 @@ struct KfqScratchView {
     uint32_t *nl;                              // [4 r_cap]: offsets of the line ends
     unsigned long long *off;                   // [r_cap + 1]: positions of a record, then its offset
     unsigned long long *bsum;                  // [ceil(r_cap / KFQ_REC_BLOCK)]: positions of a block of records, then its offset
-    uint32_t *word_rec;                        // [ceil(pos_cap / 64)]
+    uint32_t *word_rec;                        // [ceil(pos_cap / 64)] (kdf_fastq_pack)
+    uint32_t *tile_rec;                        // [output tiles + 1] (kdf_fq_extract), in the place of word_rec: a call has one or the other
 };
 
 // The text as 16-byte granules of the memory it lies in: granule g holds the text offsets [16 g - skew, 16 g - skew + 16),
@@ -298,5 +313,180 @@ __global__ __launch_bounds__(256) void kfq_pack_kernel(const uint8_t *__restrict
     const unsigned long long inv = __ballot(code > 3), lo = __ballot(code & 1u), hi = __ballot((code >> 1) & 1u);      // (4: bits 0)
     if (lane < 2) packed[2 * w + lane] = kfq_spread((lo >> (32 * lane)) & 0xFFFFFFFFull) | kfq_spread((hi >> (32 * lane)) & 0xFFFFFFFFull) << 1;
     else if (lane == 2) invalid[w] = inv;
+}
+
+// ---- kdf_fq_extract: the kept records back out as text -------------------------------------------------------------
+// A record's value in the scans: kept << 32 | bytes.  An output has at most 2^31 + 2 bytes and a call fewer than 2^29
+// records, so the two halves never carry into each other and one 64-bit sum scans both.
+
+// Behind kfq_records_kernel, which has checked record r; off and bsum are written again with the extract's values.  A
+// record's text is [s0, end): through the '\n' of line 3.  The last record of a final call ends at n_eff, where only '\r' and
+// '\n' follow: it goes on through the first '\n' when there is one, else a '\n' is supplied; a record of three lines is
+// given its quality line, one more '\n'.  keep is read below the caller's n_reads only (a wrong n_reads is refused later).
+__global__ __launch_bounds__(KFQ_REC_BLOCK) void kfx_len_kernel(const uint8_t *__restrict__ t, uint64_t n, int final_chunk, const uint8_t *__restrict__ keep,
+                                                                uint64_t n_reads, unsigned long long *__restrict__ ctl, const uint32_t *__restrict__ nl,
+                                                                unsigned long long *__restrict__ off, unsigned long long *__restrict__ bsum) {
+    __shared__ unsigned long long wsum[KFQ_REC_BLOCK / 64];
+    const uint64_t n_chk = ctl[KFQ_N_CHK], n_rec = ctl[KFQ_N_REC], lines = ctl[KFQ_LINES], r = (uint64_t)blockIdx.x * KFQ_REC_BLOCK + threadIdx.x;
+    if ((uint64_t)blockIdx.x * KFQ_REC_BLOCK >= n_chk) return;
+    unsigned long long v = 0;
+    if (r < n_chk) {
+        const uint64_t s0 = r ? (uint64_t)nl[4 * r - 1] + 1 : 0;
+        uint64_t end, supplied = 0;
+        if (final_chunk && r + 1 == n_rec) {
+            const uint64_t n_eff = ctl[KFQ_N_EFF];
+            uint64_t p = n_eff;
+            while (p < n && t[p] == '\r') ++p;
+            if (p < n) end = p + 1;                                    // (behind n_eff lie only '\r' and '\n': t[p] is a '\n')
+            else { end = n_eff; supplied = 1; }
+            if (lines - 4 * r == 3) ++supplied;
+            ctl[KFX_LAST_END] = end;
+        } else {
+            end = (uint64_t)nl[4 * r + 3] + 1;
+        }
+        if (r < n_reads && keep[r]) v = 1ull << 32 | (end - s0 + supplied);
+        off[r] = v;
+    }
+    unsigned long long s = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) bsum[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// One workgroup of 256 behind kfx_len_kernel.  The format comes first, then the caller's record count, then the room.
+__global__ __launch_bounds__(256) void kfx_total_kernel(uint64_t n, int final_chunk, uint64_t n_reads, uint64_t cap_out, const uint32_t *__restrict__ nl,
+                                                        unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ ctl) {
+    __shared__ unsigned long long a[256];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t n_rec = ctl[KFQ_N_REC], n_chk = ctl[KFQ_N_CHK];
+    const uint64_t nb = (n_chk + KFQ_REC_BLOCK - 1) / KFQ_REC_BLOCK, per = (nb + 255) / 256, b = min(nb, tid * per), e = min(nb, b + per);
+    unsigned long long sum = 0;
+    for (uint64_t i = b; i < e; ++i) sum += bsum[i];
+    a[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < 256; o <<= 1) {
+        const unsigned long long v = tid >= o ? a[tid - o] : 0ull;
+        __syncthreads();
+        a[tid] += v;
+        __syncthreads();
+    }
+    unsigned long long run = a[tid] - sum;
+    for (uint64_t i = b; i < e; ++i) { const unsigned long long c = bsum[i]; bsum[i] = run; run += c; }
+    if (tid == 0) {
+        const uint64_t out_bytes = a[255] & 0xFFFFFFFFull, n_kept = a[255] >> 32, bad = ctl[KFQ_FIRST_BAD];
+        uint64_t verdict = KFQ_OK;
+        if (bad != ~0ull) verdict = KFQ_ERR_FORMAT | bad << 8;
+        else if (n_rec != n_reads || n_chk < n_rec) verdict = KFX_ERR_COUNT;      // (n_chk < n_rec without a bad record cannot be: a guard)
+        else if (out_bytes > cap_out) verdict = KFQ_ERR_ROOM;
+        else if (!final_chunk && n_rec == 0) verdict = KFQ_NOTHING;
+        ctl[KFQ_RES + 0] = out_bytes; ctl[KFQ_RES + 1] = n_kept | n_rec << 32;
+        ctl[KFQ_RES + 2] = final_chunk ? n : (n_rec && verdict == KFQ_OK ? (uint64_t)nl[4 * n_rec - 1] + 1 : 0);
+        ctl[KFQ_RES + 3] = verdict;
+    }
+}
+
+// oskew: the output's address mod 16.  Output tile T holds the output offsets [KFQ_TILE T - oskew, KFQ_TILE (T + 1) - oskew).
+__global__ __launch_bounds__(KFQ_REC_BLOCK) void kfx_offsets_kernel(const unsigned long long *__restrict__ ctl, const unsigned long long *__restrict__ bsum,
+                                                                    uint32_t oskew, unsigned long long *__restrict__ off, uint32_t *__restrict__ tile_rec,
+                                                                    int64_t *__restrict__ offsets) {
+    __shared__ uint32_t ws[17];
+    __shared__ uint32_t n_long, long_rec[KFQ_REC_BLOCK];
+    __shared__ unsigned long long long_t0[KFQ_REC_BLOCK], long_t1[KFQ_REC_BLOCK];
+    if (ctl[KFQ_RES + 3] != KFQ_OK) return;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t total = ctl[KFQ_RES + 0], n_kept = ctl[KFQ_RES + 1] & 0xFFFFFFFFull, n_rec = ctl[KFQ_RES + 1] >> 32;
+    const uint64_t r0 = (uint64_t)blockIdx.x * KFQ_REC_BLOCK, r = r0 + tid;
+    if (blockIdx.x == 0 && tid == 0) {
+        off[n_rec] = total;
+        if (offsets) offsets[n_kept] = (int64_t)total;
+        if (oskew) tile_rec[0] = 0;                                    // (its first byte is output byte 0; without a skew the record at 0 writes it)
+    }
+    if (r0 >= n_rec) return;
+    if (tid == 0) n_long = 0;
+    const unsigned long long v = r < n_rec ? off[r] : 0ull;
+    const uint32_t len = (uint32_t)v, kept = (uint32_t)(v >> 32);
+    const unsigned long long before = bsum[blockIdx.x];
+    const uint64_t o = (before & 0xFFFFFFFFull) + kb_block_exscan(len, ws, nullptr);
+    const uint64_t rank = (before >> 32) + kb_block_exscan(kept, ws, nullptr);       // (the scans' barriers publish n_long)
+    if (r < n_rec) {
+        off[r] = o;
+        if (kept) {
+            if (offsets) offsets[rank] = (int64_t)o;
+            // the tiles whose first byte is the record's
+            const uint64_t t0 = (o + oskew + KFQ_TILE - 1) / KFQ_TILE, t1 = (o + len + oskew + KFQ_TILE - 1) / KFQ_TILE;
+            if (t1 - t0 <= KFQ_SELF_WORDS) {
+                for (uint64_t w = t0; w < t1; ++w) tile_rec[w] = (uint32_t)r;
+            } else {
+                const uint32_t i = atomicAdd(&n_long, 1u);
+                long_rec[i] = (uint32_t)r; long_t0[i] = t0; long_t1[i] = t1;
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = 0; i < n_long; ++i)
+        for (uint64_t w = long_t0[i] + tid; w < long_t1[i]; w += KFQ_REC_BLOCK) tile_rec[w] = long_rec[i];
+}
+
+// the last record of [lo, hi] whose offset is <= b (off[lo] <= b).  The offsets do not fall, a dropped record shares its
+// successor's, and a kept record takes 6 bytes or more: the record found is the kept one that byte b lies in.
+__device__ __forceinline__ uint64_t kfx_find(const unsigned long long *__restrict__ off, uint64_t lo, uint64_t hi, uint64_t b) {
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= b) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the 16 bytes at src, at any alignment, from aligned 16-byte loads: the granule src lies in and, unless src is aligned,
+// the next.  Each holds a byte of [src, src + 16), so neither load leaves the pages of the text.
+__device__ __forceinline__ uint4 kfx_load16(const uint8_t *src) {
+    const uint32_t a = (uint32_t)((uintptr_t)src & 15u);
+    const uint4 *p = reinterpret_cast<const uint4 *>(src - a);
+    const uint4 v0 = p[0];
+    if (a == 0) return v0;
+    const uint4 v1 = p[1];
+    uint64_t q0 = v0.x | (uint64_t)v0.y << 32, q1 = v0.z | (uint64_t)v0.w << 32, q2 = v1.x | (uint64_t)v1.y << 32;
+    const uint64_t q3 = v1.z | (uint64_t)v1.w << 32;
+    uint32_t sh = 8 * a;
+    if (sh >= 64) { q0 = q1; q1 = q2; q2 = q3; sh -= 64; }
+    if (sh) { q0 = q0 >> sh | q1 << (64 - sh); q1 = q1 >> sh | q2 << (64 - sh); }
+    return make_uint4((uint32_t)q0, (uint32_t)(q0 >> 32), (uint32_t)q1, (uint32_t)(q1 >> 32));
+}
+
+// A workgroup takes the output tiles blockIdx.x, blockIdx.x + gridDim.x ... below the output's end: the grid is sized by
+// the capacity, the work by the bytes kept.
+__global__ __launch_bounds__(256) void kfx_copy_kernel(const uint8_t *__restrict__ t, int final_chunk, uint32_t oskew, const unsigned long long *__restrict__ ctl,
+                                                       const uint32_t *__restrict__ nl, const unsigned long long *__restrict__ off,
+                                                       const uint32_t *__restrict__ tile_rec, uint8_t *__restrict__ out) {
+    if (ctl[KFQ_RES + 3] != KFQ_OK) return;
+    const uint64_t total = ctl[KFQ_RES + 0], n_rec = ctl[KFQ_RES + 1] >> 32, last_end = ctl[KFX_LAST_END];
+    if (total == 0) return;
+    const uint64_t n_tiles = (total + oskew + KFQ_TILE - 1) / KFQ_TILE;
+    for (uint64_t T = blockIdx.x; T < n_tiles; T += gridDim.x) {
+        const int64_t b0 = (int64_t)(T * KFQ_TILE + 16u * threadIdx.x) - (int64_t)oskew;      // the output offset of the granule's first byte
+        if (b0 >= (int64_t)total || b0 + 16 <= 0) continue;
+        const uint64_t hi = T + 1 < n_tiles ? tile_rec[T + 1] : n_rec - 1;
+        uint64_t r = kfx_find(off, tile_rec[T], hi, b0 > 0 ? (uint64_t)b0 : 0);
+        uint64_t o = off[r], next = off[r + 1], s0 = r ? (uint64_t)nl[4 * r - 1] + 1 : 0;
+        uint64_t text = (final_chunk && r + 1 == n_rec ? last_end : (uint64_t)nl[4 * r + 3] + 1) - s0;      // bytes of the record that are the text's
+        if (b0 >= 0 && (uint64_t)b0 + 16 <= total && (uint64_t)b0 + 16 - o <= text) {
+            *reinterpret_cast<uint4 *>(out + b0) = kfx_load16(t + s0 + ((uint64_t)b0 - o));
+            continue;
+        }
+        for (int i = 0; i < 16; ++i) {
+            const int64_t bb = b0 + i;
+            if (bb < 0) continue;
+            if (bb >= (int64_t)total) break;
+            if ((uint64_t)bb >= next) {
+                r = kfx_find(off, r + 1, hi, (uint64_t)bb);
+                o = off[r]; next = off[r + 1]; s0 = (uint64_t)nl[4 * r - 1] + 1;
+                text = (final_chunk && r + 1 == n_rec ? last_end : (uint64_t)nl[4 * r + 3] + 1) - s0;
+            }
+            const uint64_t j = (uint64_t)bb - o;
+            out[bb] = j < text ? t[s0 + j] : (uint8_t)'\n';
+        }
+    }
 }
 

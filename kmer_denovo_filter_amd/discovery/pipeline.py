@@ -725,3 +725,40 @@ def _write_informative_reads_discovery(child_bam, ref_fasta, proband_unique_kmer
         raise RuntimeError(f"informative reads BAM failed: {e}") from e
     logger.info("Informative reads BAM written: %s (%d reads)", output_bam, n)
     return n
+
+
+def _write_informative_reads_fastq(child_fastq, proband_unique_kmers, kmer_size, out_prefix, min_distinct_kmers_per_read=1,
+                                   paired=None):
+    """The alignment-free end of the chain for a child given as FASTQ: the records that carry at least
+    ``min_distinct_kmers_per_read`` distinct proband-unique k-mers, written as FASTQ text, byte for byte
+    (``reads.informative_fastq``: selection and extraction on the device).  ``child_fastq``: one path, a comma-separated
+    list or a sequence of paths whose names say FASTQ -- anything else is refused by name.  ``proband_unique_kmers``: what
+    the Module 3 paths take (a set of k-mers, a k-mer FASTA or an index), loaded into an engine the same way, at k <= 63 and
+    odd k 65 .. 201.  ``paired``: as in ``informative_fastq`` (``None``: two files are a pair).  Writes
+    ``{out_prefix}.fastq``, or ``{out_prefix}.R1.fastq`` / ``{out_prefix}.R2.fastq`` for a pair (several unpaired files:
+    ``{out_prefix}.{i}.fastq``).  Returns the number of records written per file."""
+    from .. import reads
+    from ..core import bam_scanner
+    files = reads.fastq_paths(child_fastq) if child_fastq is not None else []
+    if not files or not reads.is_fastq_path(files):
+        raise ValueError(f"the informative reads of a FASTQ child need FASTQ files (.fastq / .fq / .fastq.gz / .fq.gz): {child_fastq} is not")
+    pair = len(files) == 2 if paired is None else bool(paired)
+    if pair and len(files) != 2:
+        raise ValueError(f"the informative reads of a FASTQ pair need two files (R1, R2): {child_fastq} names {len(files)}")
+    if pair:
+        outs = [f"{out_prefix}.R1.fastq", f"{out_prefix}.R2.fastq"]
+    elif len(files) == 1:
+        outs = [f"{out_prefix}.fastq"]
+    else:
+        outs = [f"{out_prefix}.{i + 1}.fastq" for i in range(len(files))]
+    bam_scanner._init_scan_worker(proband_unique_kmers or set(), kmer_size)
+    eng = bam_scanner._worker_engine
+    try:
+        res = reads.informative_fastq(eng, files, outs, min_distinct=min_distinct_kmers_per_read, paired=paired, min_qual=reads.fastq_min_qual())
+    except KdfError as e:
+        if isinstance(e, reads._native.FastqFormatError):
+            raise
+        raise RuntimeError(f"informative reads FASTQ failed: {e}") from e
+    kept = [r["kept"] for r in res]
+    logger.info("Informative reads FASTQ written: %s (%s of %s records)", ", ".join(outs), kept, [r["records"] for r in res])
+    return kept

@@ -526,6 +526,35 @@ class KmerEngine:
         offsets = offs[:nr.value + 1].copy() if want_offsets else np.array([0, nb.value], np.int64)
         return ReadStream(packed[:pw].copy(), invalid[:mw].copy(), nb.value, offsets), used.value
 
+    # -- FASTQ record extract ------------------------------------------------
+    def fastq_extract_dev(self, d_text: Optional[int], n_bytes: int, final_chunk: bool, d_keep: Optional[int], n_reads: int, d_out: Optional[int],
+                          cap_out: int, d_out_offsets: Optional[int] = None) -> Tuple[int, int, int]:
+        """The records of one chunk of raw FASTQ text in HBM whose flag in ``d_keep`` (uint8[n_reads], ``n_reads`` as
+        ``fastq_pack_dev`` returned it for the same chunk) is nonzero, byte for byte and one behind the other, into
+        caller-owned HBM of ``cap_out`` bytes (``n_bytes + 2`` always suffices; ``d_out_offsets``: int64[n_reads + 1] or
+        None).  -> (out_bytes, n_kept, consumed).  A text that is no FASTQ raises ``FastqFormatError`` as ``fastq_pack_dev``
+        does.  Synchronises once; the table is not touched."""
+        p = lambda x: c_void_p(x) if x else None
+        ob, nk, used, bad, rule = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0), c_uint32(0)
+        rc = self._lib.kdf_fq_extract(self._h, _native.KDF_MEM_DEVICE, p(d_text), int(n_bytes), int(bool(final_chunk)), p(d_keep), int(n_reads),
+                                         p(d_out), int(cap_out), p(d_out_offsets), byref(ob), byref(nk), byref(used), byref(bad), byref(rule))
+        return self._fastq_packed(rc, ob, nk, used, bad, rule)
+
+    def fastq_extract(self, text, final_chunk: bool, keep, want_offsets: bool = False):
+        """The same from host bytes and a host array of flags, staged through the engine.  -> (bytes, consumed), or
+        (bytes, offsets int64[n_kept + 1], consumed) with ``want_offsets``."""
+        raw = np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else np.ascontiguousarray(text, np.uint8)
+        flags = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        n, nr = len(raw), len(flags)
+        out = np.zeros(n + 2, np.uint8)
+        offs = np.zeros(nr + 1, np.int64) if want_offsets else None
+        ob, nk, used, bad, rule = c_uint64(0), c_uint64(0), c_uint64(0), c_uint64(0), c_uint32(0)
+        rc = self._lib.kdf_fq_extract(self._h, _native.KDF_MEM_HOST, _vp(raw) if n else None, n, int(bool(final_chunk)), _vp(flags) if nr else None, nr,
+                                         _vp(out), n + 2, _vp(offs), byref(ob), byref(nk), byref(used), byref(bad), byref(rule))
+        self._fastq_packed(rc, ob, nk, used, bad, rule)
+        data = out[:ob.value].tobytes()
+        return (data, offs[:nk.value + 1].copy(), used.value) if want_offsets else (data, used.value)
+
     # -- query / dump ------------------------------------------------------
     def query(self, lo: np.ndarray, hi: Optional[np.ndarray] = None) -> np.ndarray:
         if self.long:

@@ -1017,26 +1017,20 @@ def fastq_min_qual(value=None) -> int:
     return q
 
 
-def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = False, sketch: bool = False, spool=None, min_qual: int = 0,
-                        chunk_bytes: Optional[int] = None) -> int:
-    """Count (``filtered``: count --if; ``tally``: prefilter pass 1; ``sketch``: sizing pass) four-line FASTQ files through
-    the DEVICE feeder.  ``paths``: one path or a sequence of paths (R1, R2, ...), streamed one after the other; a gzip or
-    multi-member gzip file is inflated on the host.  One reader thread fills two page-locked buffers with the text
-    (``chunk_bytes`` each; default KDF_FASTQ_FEED_MB MiB, 64), a copy stream uploads chunk i + 1 while the engine packs chunk
-    i on the device (``fastq_pack_dev``) into one of two alternating stream buffers and takes the stream where it lies in
-    HBM.  A call consumes whole records; the unconsumed tail of a chunk is copied in front of the next on the device.
-    ``min_qual`` > 0 masks the bases of a lower quality byte (`jellyfish count -Q`).  ``spool``: as in
-    ``stream_bam_device``; with ``spool.keep_reads`` the records' offsets are kept.  For the call's duration the engine runs
-    on a stream of the feeder's.  Returns the number of records; ``LAST_FASTQ_FEEDER`` records files, chunks, bytes, records
-    and positions.  A text that is no FASTQ raises ``FastqFormatError`` with the offset within its file."""
-    global LAST_FASTQ_FEEDER
+def _walk_fastq_chunks(engine, files, chunk_bytes, what: str, consume):
+    """The text of the FASTQ ``files``, one after the other, through HBM in chunks of whole records: the part that
+    ``stream_fastq_device`` and ``informative_fastq`` share.  One reader thread fills two page-locked buffers with the text
+    (``chunk_bytes`` each; default KDF_FASTQ_FEED_MB MiB, 64; a gzip or multi-member gzip file is inflated on the host), a
+    copy stream uploads chunk i + 1 while the consumer works on chunk i, and the unconsumed tail of a chunk is copied in front
+    of the next on the device.  ``consume(f, text, n_text, final, work) -> consumed`` is handed the index of the file, a view
+    of the text in HBM, its length, whether this is the file's final call, and the stream it runs on (the current torch
+    stream, and the engine's for the walk's duration); it returns what a ``fastq_*_dev`` call consumed.  A
+    ``FastqFormatError`` it raises is raised again with the file's name and the offset within the file.
+    -> {"files", "chunks", "bytes", "compressed"}."""
     import os
     import queue
     import threading
     import torch
-    files = fastq_paths(paths)
-    if not files:
-        raise ValueError("stream_fastq_device: no path")
     if chunk_bytes is None:
         chunk_bytes = int(float(os.environ.get("KDF_FASTQ_FEED_MB", "64")) * (1 << 20))
     srcs = [_FastaText(p) for p in files]                         # (the text of a file, plain or gzip: nothing of it is FASTA's)
@@ -1071,60 +1065,22 @@ def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = Fal
     work, copy_stream = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
     engine.synchronize()
     engine.set_stream(work.cuda_stream)
-    info = {"path": "device", "files": len(files), "chunks": 0, "bytes": 0, "compressed": any(s.compressed for s in srcs), "min_qual": int(min_qual)}
-    state = _native.FastqState()
-    spooling = [spool]
-    keep_reads = bool(getattr(spool, "keep_reads", False))
+    info = {"files": len(files), "chunks": 0, "bytes": 0, "compressed": any(s.compressed for s in srcs)}
     # a text slot: the chunk at [chunk_bytes, 2 chunk_bytes), and directly in front of it the tail the call on the OTHER
     # slot left (at most chunk_bytes): the copy stream writes the upper half only, the work stream the lower
     text = [torch.empty(2 * chunk_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
     used = [None, None]                                          # recorded on the work stream behind the last reader of the slot's chunk
-    out = [None, None]                                           # (packed, invalid, offsets, cap_bases, cap_reads) of the alternating stream buffers
-    turn = [0]
     left = [0, 0]                                                # (text slot, bytes) of the unconsumed tail: it ends at the slot's chunk_bytes
     file_base = [0]                                              # bytes of the current file that earlier calls consumed
     cur_file = [0]
 
-    def room(j, n_text):
-        cap_bases, cap_reads = n_text // 2, (n_text // 4 if keep_reads else 0)
-        if out[j] is None or out[j][3] < cap_bases or out[j][4] < cap_reads:
-            pw, mw = stream_words(cap_bases)
-            torch.cuda.current_stream(dev).synchronize()          # (memory the allocator hands out again may still be in use on this stream)
-            out[j] = (torch.empty(pw, dtype=torch.int64, device=dev), torch.empty(mw, dtype=torch.int64, device=dev),
-                      torch.empty(cap_reads + 1, dtype=torch.int64, device=dev) if keep_reads else None, cap_bases, cap_reads)
-        return out[j]
-
-    def pack(t, n_text, final):
-        """pack t[:n_text] into the stream buffer the previous stream does not lie in, hand it to the engine -> consumed"""
-        j = turn[0]
-        turn[0] ^= 1
-        packed, invalid, offs, cap_bases, cap_reads = room(j, n_text)
+    def take(t, n_text, final):
+        """hand t[:n_text] to the consumer -> consumed"""
         try:
-            nb, nr, consumed = engine.fastq_pack_dev(t.data_ptr() if n_text else None, n_text, final, state, packed.data_ptr(), invalid.data_ptr(),
-                                                     cap_bases, offs.data_ptr() if offs is not None else None, cap_reads, min_qual)
+            consumed = consume(cur_file[0], t, n_text, final, work)
         except _native.FastqFormatError as ex:
             raise _native.FastqFormatError(ex.code, f"{files[cur_file[0]]}: byte {file_base[0] + ex.offset}: {ex}", file_base[0] + ex.offset, ex.rule) from None
         file_base[0] += consumed
-        if nb:
-            dp, dm = packed.data_ptr(), invalid.data_ptr()
-            if spooling[0] is not None:
-                try:
-                    if keep_reads:
-                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream, d_offsets=offs.data_ptr(), n_reads=nr)
-                    else:
-                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream)
-                except _native.KdfError as ex:
-                    if ex.code != _native.KDF_ERR_NOMEM:
-                        raise
-                    spooling[0] = None                               # overflowed: the pass itself goes on
-            if sketch:
-                engine.sketch_add_dev(dp, dm, nb)
-            elif tally:
-                engine.prefilter_add_dev(dp, dm, nb)
-            elif filtered:
-                engine.count_filtered_dev(dp, dm, nb)
-            else:
-                engine.count_dev(dp, dm, nb)
         return consumed
 
     try:
@@ -1138,10 +1094,10 @@ def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = Fal
                 work.wait_event(copied)
                 start = chunk_bytes - left[1]                        # (the tail was put in front of this slot's chunk)
                 n_text = left[1] + n
-                consumed = pack(text[slot][start:start + n_text], n_text, False)
+                consumed = take(text[slot][start:start + n_text], n_text, False)
                 rest = n_text - consumed
                 if rest > chunk_bytes:
-                    raise ValueError(f"stream_fastq_device: {files[cur_file[0]]}: {rest} bytes behind byte {file_base[0]} hold no complete FASTQ "
+                    raise ValueError(f"{what}: {files[cur_file[0]]}: {rest} bytes behind byte {file_base[0]} hold no complete FASTQ "
                                      f"record and a chunk is {chunk_bytes} bytes: raise KDF_FASTQ_FEED_MB (a chunk must hold the longest record)")
                 if rest:                                             # in front of the other slot's chunk, where the next call reads
                     text[slot ^ 1][chunk_bytes - rest:chunk_bytes].copy_(text[slot][start + consumed:start + n_text])
@@ -1155,7 +1111,7 @@ def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = Fal
                 """the file's end: what the last call left is the final call's text"""
                 slot, m = left
                 if m:
-                    pack(text[slot][chunk_bytes - m:chunk_bytes], m, True)
+                    take(text[slot][chunk_bytes - m:chunk_bytes], m, True)
                 left[1] = 0
                 file_base[0] = 0
 
@@ -1195,10 +1151,250 @@ def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = Fal
             copy_stream.synchronize()                                # no copy may still read a pinned buffer the next caller will fill
             for s in srcs:
                 s.close()
-    info["records"] = int(state.records)
-    info["positions"] = int(state.positions)
+    return info
+
+
+def stream_fastq_device(engine, paths, filtered: bool = False, tally: bool = False, sketch: bool = False, spool=None, min_qual: int = 0,
+                        chunk_bytes: Optional[int] = None) -> int:
+    """Count (``filtered``: count --if; ``tally``: prefilter pass 1; ``sketch``: sizing pass) four-line FASTQ files through
+    the DEVICE feeder.  ``paths``: one path or a sequence of paths (R1, R2, ...), streamed one after the other; a gzip or
+    multi-member gzip file is inflated on the host.  One reader thread fills two page-locked buffers with the text
+    (``chunk_bytes`` each; default KDF_FASTQ_FEED_MB MiB, 64), a copy stream uploads chunk i + 1 while the engine packs chunk
+    i on the device (``fastq_pack_dev``) into one of two alternating stream buffers and takes the stream where it lies in
+    HBM.  A call consumes whole records; the unconsumed tail of a chunk is copied in front of the next on the device
+    (``_walk_fastq_chunks``).  ``min_qual`` > 0 masks the bases of a lower quality byte (`jellyfish count -Q`).  ``spool``: as in
+    ``stream_bam_device``; with ``spool.keep_reads`` the records' offsets are kept.  For the call's duration the engine runs
+    on a stream of the feeder's.  Returns the number of records; ``LAST_FASTQ_FEEDER`` records files, chunks, bytes, records
+    and positions.  A text that is no FASTQ raises ``FastqFormatError`` with the offset within its file."""
+    global LAST_FASTQ_FEEDER
+    import torch
+    files = fastq_paths(paths)
+    if not files:
+        raise ValueError("stream_fastq_device: no path")
+    dev = torch.device("cuda", engine.device)
+    state = _native.FastqState()
+    spooling = [spool]
+    keep_reads = bool(getattr(spool, "keep_reads", False))
+    out = [None, None]                                           # (packed, invalid, offsets, cap_bases, cap_reads) of the alternating stream buffers
+    turn = [0]
+
+    def room(j, n_text):
+        cap_bases, cap_reads = n_text // 2, (n_text // 4 if keep_reads else 0)
+        if out[j] is None or out[j][3] < cap_bases or out[j][4] < cap_reads:
+            pw, mw = stream_words(cap_bases)
+            torch.cuda.current_stream(dev).synchronize()          # (memory the allocator hands out again may still be in use on this stream)
+            out[j] = (torch.empty(pw, dtype=torch.int64, device=dev), torch.empty(mw, dtype=torch.int64, device=dev),
+                      torch.empty(cap_reads + 1, dtype=torch.int64, device=dev) if keep_reads else None, cap_bases, cap_reads)
+        return out[j]
+
+    def pack(f, t, n_text, final, work):
+        """pack t[:n_text] into the stream buffer the previous stream does not lie in, hand it to the engine -> consumed"""
+        j = turn[0]
+        turn[0] ^= 1
+        packed, invalid, offs, cap_bases, cap_reads = room(j, n_text)
+        nb, nr, consumed = engine.fastq_pack_dev(t.data_ptr() if n_text else None, n_text, final, state, packed.data_ptr(), invalid.data_ptr(),
+                                                 cap_bases, offs.data_ptr() if offs is not None else None, cap_reads, min_qual)
+        if nb:
+            dp, dm = packed.data_ptr(), invalid.data_ptr()
+            if spooling[0] is not None:
+                try:
+                    if keep_reads:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream, d_offsets=offs.data_ptr(), n_reads=nr)
+                    else:
+                        spooling[0].append_dev(dp, dm, nb, work.cuda_stream)
+                except _native.KdfError as ex:
+                    if ex.code != _native.KDF_ERR_NOMEM:
+                        raise
+                    spooling[0] = None                               # overflowed: the pass itself goes on
+            if sketch:
+                engine.sketch_add_dev(dp, dm, nb)
+            elif tally:
+                engine.prefilter_add_dev(dp, dm, nb)
+            elif filtered:
+                engine.count_filtered_dev(dp, dm, nb)
+            else:
+                engine.count_dev(dp, dm, nb)
+        return consumed
+
+    walked = _walk_fastq_chunks(engine, files, chunk_bytes, "stream_fastq_device", pack)
+    info = {"path": "device", "files": walked["files"], "chunks": walked["chunks"], "bytes": walked["bytes"], "compressed": walked["compressed"],
+            "min_qual": int(min_qual), "records": int(state.records), "positions": int(state.positions)}
     LAST_FASTQ_FEEDER = info
     return int(state.records)
+
+
+LAST_FASTQ_SUBSET = None      # what the last informative_fastq call did: {"files", "paired", "passes", "chunks", "bytes_read", "bytes_written", "records", "kept", "min_distinct", "min_qual", "compressed"}
+
+
+def informative_fastq(engine, paths, out_paths, min_distinct: int = 1, paired: Optional[bool] = None, min_qual: int = 0,
+                      chunk_bytes: Optional[int] = None):
+    """The records of four-line FASTQ files that carry at least ``min_distinct`` distinct k-mers of the engine's table,
+    written as FASTQ text, byte for byte: Module 3's read selection for a sample that starts from FASTQ, without an alignment
+    and without a host pass over the text.  The caller has loaded the candidate k-mer set into ``engine`` (as for
+    ``scan_bam_module3``: keys with a count > 0).  ``paths`` / ``out_paths``: one path per input and one output per input (a
+    ``.gz`` output name is refused: compressing the small output is the caller's).
+
+    Per chunk (``_walk_fastq_chunks``): ``fastq_pack_dev`` with the record offsets, ``read_hits_dev`` against the table,
+    ``keep = distinct >= min_distinct`` as a torch op on the device (``min_distinct <= 0`` keeps every record), and
+    ``fastq_extract_dev`` on the same chunk while its text is still in HBM; the kept bytes go through a page-locked buffer to
+    ``write()``.  ``min_qual`` masks low-quality bases for the scan as in ``stream_fastq_device``; the text written is
+    the file's.
+
+    Unpaired (one file; several files with ``paired=False``; ``paired=None`` with other than two files): one pass, every
+    file on its own.  Paired (``paired=True``, or ``None`` with exactly two files): pass 1 keeps one uint32 ``distinct`` per
+    record per file on the device -- 4 bytes per record, about 3.6 GB for a 30x human pair of 2 x 450 M reads --, the two
+    files must hold the same number of records (``ValueError`` naming both counts otherwise; names are not compared), a
+    pair is kept when either mate qualifies, and pass 2 streams both files again and extracts with the flags of the records
+    [records so far, + the chunk's), so the outputs stay in step: record i of R1 with record i of R2.  The flags are
+    complete on the device before pass 2 starts (the call waits for them), and a file that changed between the passes is
+    refused, not written wrongly.
+
+    An output is opened at its first write, or at the end when nothing of its file was kept: unequal record counts of a
+    pair leave no output behind, and an error later in the text leaves what was written before it.
+
+    -> a list with one dict per file: ``records``, ``kept``, ``ordinals`` (int64, the ascending record numbers within the
+    file of the records written) and ``distinct`` (uint32 of those records, a mate's own value).  ``LAST_FASTQ_SUBSET``
+    records files, chunks, passes, bytes read and written.  A text that is no FASTQ raises ``FastqFormatError`` with the
+    offset within its file.  For the call's duration the engine runs on a stream of the walker's."""
+    global LAST_FASTQ_SUBSET
+    import torch
+    from . import dist_env
+    files, outs = fastq_paths(paths), fastq_paths(out_paths)
+    if not files:
+        raise ValueError("informative_fastq: no path")
+    if dist_env.world_rank()[0] > 1:
+        raise ValueError(f"a FASTQ sample ({','.join(files)}) is not sharded over ranks: select its reads in one process")
+    if len(outs) != len(files):
+        raise ValueError(f"informative_fastq: {len(files)} inputs and {len(outs)} outputs: one output per input")
+    for o in outs:
+        if o.lower().endswith(".gz"):
+            raise ValueError(f"informative_fastq: {o}: the output is written as plain text (compress the small output afterwards)")
+    if paired and len(files) != 2:
+        raise ValueError(f"informative_fastq: paired=True takes two files (R1, R2), not {len(files)}")
+    pair = len(files) == 2 if paired is None else bool(paired)
+    min_distinct = int(min_distinct)
+    dev = torch.device("cuda", engine.device)
+    state = _native.FastqState()
+    buf = {}                                                     # the buffers of a chunk, grown when a chunk needs more
+    n_files = len(files)
+    records, kept, written = [0] * n_files, [0] * n_files, [0] * n_files
+    scores = [[] for _ in files]                                 # per file: the uint32 `distinct` of every chunk, on the device
+    chosen = [[] for _ in files]                                 # per file: (ordinals, distinct) of the kept records of every chunk, on the host
+    sinks = [None] * n_files
+    flags = [None]                                               # paired, pass 2: uint8 per record of a file
+    done = [0] * n_files                                         # pass 2: records of the file that earlier calls held
+    calls, turn = [[] for _ in files], [0] * n_files             # pass 1: the records of every call on a file; pass 2: the call it is at
+
+    def room(n_text):
+        cap_bases, cap_reads = n_text // 2, n_text // 4
+        if not buf or buf["cap_bases"] < cap_bases:
+            pw, mw = stream_words(cap_bases)
+            torch.cuda.current_stream(dev).synchronize()          # (memory the allocator hands out again may still be in use on this stream)
+            buf.update(packed=torch.empty(pw, dtype=torch.int64, device=dev), invalid=torch.empty(mw, dtype=torch.int64, device=dev),
+                       offs=torch.empty(cap_reads + 1, dtype=torch.int64, device=dev), rows=torch.empty((cap_reads + 1, 2), dtype=torch.int32, device=dev),
+                       cap_bases=cap_bases, cap_reads=cap_reads)
+        return buf
+
+    def out_room(n_text):
+        if buf.get("cap_out", -1) < n_text + 2:
+            torch.cuda.current_stream(dev).synchronize()
+            buf.update(out=torch.empty(n_text + 2, dtype=torch.uint8, device=dev), host=torch.empty(n_text + 2, dtype=torch.uint8).pin_memory(),
+                       cap_out=n_text + 2)
+        return buf
+
+    def score(t, n_text, final):
+        """-> (records, consumed, uint32 `distinct` per record as an int32 tensor view on the device)"""
+        b = room(n_text)
+        nb, nr, consumed = engine.fastq_pack_dev(t.data_ptr() if n_text else None, n_text, final, state, b["packed"].data_ptr(), b["invalid"].data_ptr(),
+                                                 b["cap_bases"], b["offs"].data_ptr(), b["cap_reads"], min_qual)
+        if nr:
+            engine.read_hits_dev(b["packed"].data_ptr(), b["invalid"].data_ptr(), nb, b["offs"].data_ptr(), nr, None, b["rows"].data_ptr())
+        return nr, consumed, b["rows"][:nr, 1]
+
+    def extract(f, t, n_text, final, keep, nr, distinct, first):
+        """write the records of the chunk whose flag is set; note their ordinals and `distinct`"""
+        b = out_room(n_text)
+        ob, nk, consumed = engine.fastq_extract_dev(t.data_ptr() if n_text else None, n_text, final, keep.data_ptr() if nr else None, nr,
+                                                    b["out"].data_ptr(), b["cap_out"])
+        if nk:
+            idx = torch.nonzero(keep, as_tuple=False).flatten()
+            chosen[f].append(((idx + first).cpu().numpy().astype(np.int64), distinct[idx].cpu().numpy().view(np.uint32)))
+            b["host"][:ob].copy_(b["out"][:ob], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+            if sinks[f] is None:                                     # opened at the first write: a refusal before it leaves no file behind
+                sinks[f] = open(outs[f], "wb")
+            sinks[f].write(memoryview(b["host"].numpy())[:ob])
+        kept[f] += nk
+        written[f] += ob
+        return consumed
+
+    def one_pass(f, t, n_text, final, work):
+        nr, consumed, distinct = score(t, n_text, final)
+        keep = (distinct >= min_distinct).to(torch.uint8) if min_distinct > 0 else torch.ones(nr, dtype=torch.uint8, device=dev)
+        used = extract(f, t, n_text, final, keep, nr, distinct, records[f])
+        assert used == consumed, "the feeder and the extract read the same records"
+        records[f] += nr
+        return consumed
+
+    def pass_1(f, t, n_text, final, work):
+        nr, consumed, distinct = score(t, n_text, final)
+        if nr:
+            scores[f].append(distinct.clone())
+        calls[f].append(nr)
+        records[f] += nr
+        return consumed
+
+    def pass_2(f, t, n_text, final, work):
+        # The same file in the same chunks holds the same records per call as in pass 1.  Should the text have changed in
+        # between, kdf_fq_extract refuses the call: its n_reads must be the records the chunk holds.
+        changed = f"informative_fastq: {files[f]} does not hold the records it held in the first pass: the file changed between the two passes"
+        if turn[f] >= len(calls[f]):
+            raise ValueError(changed)
+        nr = calls[f][turn[f]]
+        turn[f] += 1
+        try:
+            used = extract(f, t, n_text, final, flags[0][done[f]:done[f] + nr], nr, own[f][done[f]:done[f] + nr], done[f])
+        except _native.FastqFormatError:
+            raise
+        except _native.KdfError as ex:
+            if ex.code != _native.KDF_ERR_INVALID:
+                raise
+            raise ValueError(f"{changed} ({ex})") from None
+        done[f] += nr
+        return used
+
+    passes, chunks, bytes_read, compressed = 0, 0, 0, False
+    try:
+        if not pair:
+            w = _walk_fastq_chunks(engine, files, chunk_bytes, "informative_fastq", one_pass)
+            passes, chunks, bytes_read, compressed = 1, w["chunks"], w["bytes"], w["compressed"]
+        else:
+            w = _walk_fastq_chunks(engine, files, chunk_bytes, "informative_fastq", pass_1)
+            if records[0] != records[1]:
+                raise ValueError(f"informative_fastq: {files[0]} holds {records[0]} records and {files[1]} holds {records[1]}: a pair has the same number in both")
+            own = [torch.cat(s) if s else torch.zeros(0, dtype=torch.int32, device=dev) for s in scores]
+            either = torch.maximum(own[0], own[1]) >= min_distinct if min_distinct > 0 else torch.ones(records[0], dtype=torch.bool, device=dev)
+            flags[0] = either.to(torch.uint8)
+            # The scores and the flags are made on the caller's current stream; pass 2 reads them on the walker's own
+            # stream, which nothing orders behind that one: they are complete before pass 2 starts.
+            torch.cuda.current_stream(dev).synchronize()
+            w2 = _walk_fastq_chunks(engine, files, chunk_bytes, "informative_fastq", pass_2)
+            passes, chunks, bytes_read, compressed = 2, w["chunks"] + w2["chunks"], w["bytes"] + w2["bytes"], w["compressed"]
+        for i, o in enumerate(outs):                                 # a file of which nothing was kept gets its empty output
+            if sinks[i] is None:
+                sinks[i] = open(o, "wb")
+    finally:
+        for s in sinks:
+            if s is not None:
+                s.close()
+    result = []
+    for f in range(n_files):
+        ords = np.concatenate([c[0] for c in chosen[f]]) if chosen[f] else np.zeros(0, np.int64)
+        dist = np.concatenate([c[1] for c in chosen[f]]) if chosen[f] else np.zeros(0, np.uint32)
+        result.append({"records": records[f], "kept": kept[f], "ordinals": ords, "distinct": dist})
+    LAST_FASTQ_SUBSET = {"files": n_files, "paired": pair, "passes": passes, "chunks": chunks, "bytes_read": bytes_read, "bytes_written": sum(written),
+                         "records": sum(records), "kept": sum(kept), "min_distinct": min_distinct, "min_qual": int(min_qual), "compressed": compressed}
+    return result
 
 
 def write_bam_subset(src_bam: str, dst_bam: str, ordinals, aux_fields=None, sort_and_index: bool = True,
