@@ -100,12 +100,12 @@ __global__ __launch_bounds__(256) void kc_accum_kernel(
 // block_sums[block] = positions g of the block's KC_BLOCK_ELEMS with rc[g] >= thr; rc: the n words of the window
 __global__ __launch_bounds__(256) void kc_list_count_kernel(const uint32_t *__restrict__ rc, uint64_t n, uint32_t thr,
                                                             unsigned long long *__restrict__ block_sums) {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t g0 = (uint64_t)blockIdx.x * KC_BLOCK_ELEMS + threadIdx.x * 4;
     uint32_t c = 0, total;
 #pragma unroll
     for (int j = 0; j < 4; ++j) c += g0 + j < n && rc[g0 + j] >= thr;
-    kh_block_excl(c, ws, total);
+    kb_block_exscan(c, ws, &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
@@ -115,12 +115,12 @@ __global__ __launch_bounds__(256) void kc_list_write_kernel(
     const unsigned long long *__restrict__ block_off, uint64_t *__restrict__ pos_out, uint32_t *__restrict__ kmer_out,
     uint32_t *__restrict__ read_out, uint64_t cap)
 {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t g0 = (uint64_t)blockIdx.x * KC_BLOCK_ELEMS + threadIdx.x * 4;
     uint32_t v[4], c = 0, total;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[j] = g0 + j < n ? rc[g0 + j] : 0u; c += g0 + j < n && v[j] >= thr; }
-    uint64_t o = block_off[blockIdx.x] + kh_block_excl(c, ws, total);
+    uint64_t o = block_off[blockIdx.x] + kb_block_exscan(c, ws, &total);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (g0 + j >= n || v[j] < thr) continue;

@@ -1,6 +1,6 @@
 // kdf_device.h -- device-side primitives shared by the kernels of libkdf.so:
-// key type, hash, window extraction from the 2-bit stream, table views.
-// gfx950 only (wave = 64 lanes).
+// key type, hash, window extraction from the 2-bit stream, table views, runs of equal lanes in a wave.
+// (Block scans and sums: kdf_scan.h; what the text kernels share: kdf_text.h.)  gfx950 only (wave = 64 lanes).
 #pragma once
 #include <stdint.h>
 #if defined(__HIP__)
@@ -212,21 +212,14 @@ struct KdfSketch {
 #define KD_ROW_WORDS  6                   // kdf_depth.h (uint64): windows, present, low, min, max, sum
 #define KH_ROW_WORDS   2                  // kdf_hits.h (uint32): hits, distinct
 
-// exclusive prefix of v over the 256 threads of the workgroup and their total; ws: 4 words of LDS
-// (the block scan of the kh_* kernels of kdf_hits.h and the ks_select_* kernels of kdf_spool.h)
-__device__ __forceinline__ uint32_t kh_block_excl(uint32_t v, uint32_t *ws, uint32_t &total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    uint32_t pre = 0;
-    total = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const uint32_t s = ws[j]; pre += j < wv ? s : 0; total += s; }
-    __syncthreads();                                                  // (ws is written again by the caller's next scan)
-    return pre + inc - v;
+// Runs of neighbouring lanes that share a value (a sorted order: the read of a hit, the region of an interval): `heads`
+// is the ballot of the lanes that differ from their predecessor, lane 0 among them.  For a head lane: the lanes of its
+// run and their number.  The run's first lane then speaks for the run -- one atomic per (wave, run).
+struct KdfWaveRun { unsigned long long mask; int len; };
+__device__ __forceinline__ KdfWaveRun kdf_wave_run(unsigned long long heads, int lane) {
+    const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
+    return KdfWaveRun{(len >= 64 ? ~0ull : ((1ull << len) - 1)) << lane, len};
 }
 
 __device__ __forceinline__ uint64_t kdf_home(const KdfTable &t, uint64_t h) {

@@ -28,6 +28,7 @@
 
 #include "kdf.h"
 #include "kdf_scan.h"
+#include "kdf_text.h"
 
 #define KFA_TILE KDF_FASTA_TILE_BYTES
 static_assert(KFA_TILE == 256 * 16, "a tile is 256 lanes of 16 bytes");
@@ -46,12 +47,6 @@ enum { KFA_ERR_ROOM = 1, KFA_ERR_STUCK = 2 };
 #define KFA_IN_REC (1ull << 63)
 
 struct KfaText { const uint8_t *t; uint64_t n; uint32_t flags; int aligned; };
-
-// A/C/G/T in either case -> 0 .. 3, anything else -> 4
-__device__ __forceinline__ uint32_t kfa_code(uint32_t c) {
-    const uint32_t u = c & 0xDFu, x = (u >> 1) & 3u;
-    return (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? x ^ (x >> 1) : 4u;
-}
 
 // only '\r' between byte p and the next '\n' or the text's end
 __device__ __forceinline__ uint32_t kfa_walk(const KfaText &x, uint64_t p) {
@@ -75,15 +70,8 @@ struct KfaShared { uint32_t wv[4][5]; };
 __device__ __forceinline__ void kfa_classify(const KfaText &x, uint64_t t0, KfaShared &sh, KfaLane &L) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint64_t s0 = t0 + 16u * tid;
-    if (x.aligned && s0 + 16 <= x.n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(x.t + s0);
-        L.w[0] = v.x; L.w[1] = v.y; L.w[2] = v.z; L.w[3] = v.w;
-    } else {
-        L.w[0] = L.w[1] = L.w[2] = L.w[3] = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (s0 + i < x.n) L.w[i >> 2] |= (uint32_t)x.t[s0 + i] << (8 * (i & 3));
-    }
+    const uint4 v = kt_load_granule(x.t, (int64_t)s0, 0, (int64_t)x.n, x.aligned, 0u);
+    L.w[0] = v.x; L.w[1] = v.y; L.w[2] = v.z; L.w[3] = v.w;
     uint32_t prev = __shfl_up(L.w[3] >> 24, 1);                       // the byte in front of the lane
     if (lane == 0) prev = s0 == 0 ? ((x.flags & KDF_FA_MID_LINE) ? 0u : '\n') : (s0 <= x.n ? x.t[s0 - 1] : 0u);
     uint32_t live = 0, nl = 0, cr = 0, gt = 0;
@@ -166,12 +154,8 @@ __global__ __launch_bounds__(256) void kfa_count_kernel(const uint8_t *__restric
     kfa_emit_masks(L, ma, mb, mc, ms);
     unsigned long long v = (unsigned long long)__popc(ma) | (unsigned long long)__popc(mb) << KFA_F | (unsigned long long)__popc(mc) << (2 * KFA_F) |
                            (unsigned long long)__popc(L.hs) << (3 * KFA_F) | (ms ? KFA_SUM_SEP : 0ull);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3] + (L.tile_ls ? KFA_SUM_LS : 0ull) + (L.tile_lhdr ? KFA_SUM_LHDR : 0ull);
+    v = kb_block_sum(v, wsum);
+    if (threadIdx.x == 0) sums[blockIdx.x] = v + (L.tile_ls ? KFA_SUM_LS : 0ull) + (L.tile_lhdr ? KFA_SUM_LHDR : 0ull);
 }
 
 // positions a tile emits, given its carried-in states
@@ -190,24 +174,12 @@ __global__ __launch_bounds__(256) void kfa_scan_kernel(const unsigned long long 
                                                        unsigned long long *__restrict__ ctl) {
     __shared__ uint32_t ws[17];
     __shared__ uint32_t line_of[256];                                  // 0: the thread's tiles have no line start; 1 / 2: the last one starts a sequence / header line
-    __shared__ unsigned long long last_other;
     __shared__ uint32_t end_hdr;
     const uint32_t tid = threadIdx.x;
     const uint64_t per = (nt + 255) / 256, b = min(nt, tid * per), e = min(nt, b + per);
-    if (tid == 0) { last_other = 0; end_hdr = (flags & KDF_FA_IN_HEADER) != 0; }
-    __syncthreads();
+    if (tid == 0) end_hdr = (flags & KDF_FA_IN_HEADER) != 0;           // (published by the barriers of the scans below)
     // consumed: everything (the last chunk), else everything in front of the trailing run of '\r'
-    uint64_t m = n;
-    if (!final_chunk) {
-        for (uint64_t end = n; end > 0; end -= end < 256 ? end : 256) {
-            if (tid < end && t[end - 1 - tid] != '\r') atomicMax(&last_other, (unsigned long long)(end - tid));
-            __syncthreads();
-            const unsigned long long found = last_other;
-            __syncthreads();                                           // (nobody raises it again before everybody has read it)
-            if (found) break;
-        }
-        m = last_other;
-    }
+    const uint64_t m = final_chunk ? n : kt_last_outside(t, n, [](uint8_t c) { return c == '\r'; });
     uint32_t my_line = 0, my_hs = 0;
     for (uint64_t i = b; i < e; ++i) {
         const unsigned long long s = sums[i];
@@ -300,7 +272,7 @@ __global__ __launch_bounds__(256) void kfa_write_kernel(const uint8_t *__restric
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             if (!((emit >> i) & 1u)) continue;
-            const uint32_t code = kfa_code((L.w[i >> 2] >> (8 * (i & 3))) & 0xFFu);   // ('>': a separator is an invalid position)
+            const uint32_t code = kdf_base_code((L.w[i >> 2] >> (8 * (i & 3))) & 0xFFu);   // ('>': a separator is an invalid position)
             codes |= (uint64_t)(code & 3u) << (2 * j);
             inv |= (uint64_t)(code > 3) << j;
             ++j;

@@ -25,7 +25,7 @@
 // kdf_fq_extract (include/kdf.h, "FASTQ record extract") shares 1 .. 5 -- the records are the feeder's -- and goes on with
 //   6x. kfx_len_kernel     a thread per record: (kept << 32 | bytes the record takes in the output), 0 for a dropped one,
 //                          and their sum per block of 256 records; the last record of a final call fixes where its text ends
-//   7x. kfx_total_kernel   one workgroup: scans the block sums, decides the verdict, writes the results
+//   7x. kfq_total_kernel   its EXTRACT form: scans the block sums, decides the verdict, writes the results
 //   8x. kfx_offsets_kernel per block of 256 records: the byte offset of every record in the output (a plateau over dropped
 //                          records), the caller's offsets of the kept ones, and tile_rec[T] = the record that the first
 //                          byte of output tile T lies in
@@ -39,6 +39,7 @@
 
 #include "kdf.h"
 #include "kdf_scan.h"
+#include "kdf_text.h"
 
 #define KFQ_TILE KDF_FASTQ_TILE_BYTES
 static_assert(KFQ_TILE == 256 * 16, "a tile is 256 lanes of 16 bytes");
@@ -68,16 +69,8 @@ struct KfqScratchView {
 // byte (negative in the first granule of a skewed text).  -> bit i: byte s0 + i is a '\n' below n_eff
 __device__ __forceinline__ uint32_t kfq_line_ends(const uint8_t *__restrict__ t, uint64_t n, uint64_t n_eff, int64_t s0) {
     if (s0 >= (int64_t)n_eff) return 0;
-    uint32_t w[4];
-    if (s0 >= 0 && (uint64_t)s0 + 16 <= n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(t + s0);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-        w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (s0 + i >= 0 && s0 + i < (int64_t)n_eff) w[i >> 2] |= (uint32_t)t[s0 + i] << (8 * (i & 3));
-    }
+    const uint4 v = kt_load_granule(t, s0, 0, (int64_t)n, true, 0u);   // (the bytes from n_eff on are masked off below)
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
     uint32_t m = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -90,22 +83,9 @@ __device__ __forceinline__ uint32_t kfq_line_ends(const uint8_t *__restrict__ t,
 }
 
 __global__ __launch_bounds__(256) void kfq_end_kernel(const uint8_t *__restrict__ t, uint64_t n, int final_chunk, unsigned long long *__restrict__ ctl) {
-    __shared__ unsigned long long last_other;
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) last_other = 0;
-    __syncthreads();
-    for (uint64_t end = n; end > 0; end -= end < 256 ? end : 256) {
-        if (tid < end) {
-            const uint8_t c = t[end - 1 - tid];
-            if (c != '\n' && c != '\r') atomicMax(&last_other, (unsigned long long)(end - tid));
-        }
-        __syncthreads();
-        const unsigned long long found = last_other;
-        __syncthreads();                                               // (nobody raises it again before everybody has read it)
-        if (found) break;
-    }
     // the final call's text ends there; a call that is not the last sees the first line end behind it
-    uint64_t n_eff = last_other;
+    uint64_t n_eff = kt_last_outside(t, n, [](uint8_t c) { return c == '\n' || c == '\r'; });
     if (!final_chunk) {
         while (n_eff < n && t[n_eff] == '\r') ++n_eff;
         n_eff = min(n_eff + 1, n);
@@ -117,12 +97,9 @@ __global__ __launch_bounds__(256) void kfq_count_kernel(const uint8_t *__restric
                                                         uint32_t *__restrict__ tile_nl) {
     __shared__ uint32_t wsum[4];
     const uint32_t tid = threadIdx.x;
-    uint32_t v = (uint32_t)__popc(kfq_line_ends(t, n, ctl[KFQ_N_EFF], (int64_t)((uint64_t)blockIdx.x * KFQ_TILE + 16u * tid) - skew));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) tile_nl[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t v = (uint32_t)__popc(kfq_line_ends(t, n, ctl[KFQ_N_EFF], (int64_t)((uint64_t)blockIdx.x * KFQ_TILE + 16u * tid) - skew));
+    const uint32_t sum = kb_block_sum(v, wsum);
+    if (tid == 0) tile_nl[blockIdx.x] = sum;
 }
 
 // One workgroup of 256; thread i owns the tiles [i * per, (i + 1) * per).  cap_rec: the records the caller's buffers admit;
@@ -194,51 +171,58 @@ __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfq_records_kernel(const uint8_
         positions = len + 1;
         off[r] = positions;
     }
-    uint32_t v = positions;                                            // (the text of a call has fewer than 2^31 bases)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = (unsigned long long)wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const uint32_t sum = kb_block_sum(positions, wsum);                // (a 32-bit sum: the text of a call has fewer than 2^31 bytes, so a block's positions cannot wrap it)
+    if (threadIdx.x == 0) bsum[blockIdx.x] = sum;
 }
 
-// One workgroup of 256 behind the record pass.  nothing: a call that is not the last and has no complete record writes nothing.
-__global__ __launch_bounds__(256) void kfq_total_kernel(uint64_t n, int final_chunk, uint64_t cap_bases, const uint32_t *__restrict__ nl,
+// One workgroup of 256 behind the record pass (the feeder) or behind kfx_len_kernel (EXTRACT, below): scans the block sums
+// and decides the verdict.  The format comes first (among the records the capacities admit); then, for the extract, the
+// caller's record count; then the room, cap: the bases (the feeder) or output bytes (the extract) the caller's buffers
+// admit.  nothing: a call that is not the last and has no complete record writes nothing.
+template <bool EXTRACT>
+__global__ __launch_bounds__(256) void kfq_total_kernel(uint64_t n, int final_chunk, uint64_t n_reads, uint64_t cap, const uint32_t *__restrict__ nl,
                                                         unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ ctl) {
-    __shared__ unsigned long long a[256];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n_rec = ctl[KFQ_N_REC], n_chk = ctl[KFQ_N_CHK], room = ctl[KFQ_ROOM];
-    const uint64_t nb = (n_chk + KFQ_REC_BLOCK - 1) / KFQ_REC_BLOCK, per = (nb + 255) / 256, b = min(nb, tid * per), e = min(nb, b + per);
-    unsigned long long sum = 0;
-    for (uint64_t i = b; i < e; ++i) sum += bsum[i];
-    a[tid] = sum;
+    __shared__ unsigned long long ws[4];
+    const uint64_t n_rec = ctl[KFQ_N_REC], n_chk = ctl[KFQ_N_CHK], room = ctl[KFQ_ROOM], bad = ctl[KFQ_FIRST_BAD];
+    const unsigned long long total = kb_sums_exscan(bsum, (n_chk + KFQ_REC_BLOCK - 1) / KFQ_REC_BLOCK, ws);
+    if (threadIdx.x) return;
+    const uint64_t size = EXTRACT ? total & 0xFFFFFFFFull : total;    // EXTRACT: kept << 32 | bytes
+    uint64_t verdict = KFQ_OK;
+    if (bad != ~0ull) verdict = KFQ_ERR_FORMAT | bad << 8;
+    else if (EXTRACT && (n_rec != n_reads || n_chk < n_rec)) verdict = KFX_ERR_COUNT;      // (n_chk < n_rec without room or a bad record cannot be: a guard,
+    else if ((!EXTRACT && (room || n_chk < n_rec)) || size > cap) verdict = KFQ_ERR_ROOM;  // here and below)
+    else if (!final_chunk && n_rec == 0) verdict = KFQ_NOTHING;
+    ctl[KFQ_RES + 0] = size; ctl[KFQ_RES + 1] = EXTRACT ? total >> 32 | n_rec << 32 : n_rec;
+    ctl[KFQ_RES + 2] = final_chunk ? n : (n_rec && verdict == KFQ_OK ? (uint64_t)nl[4 * n_rec - 1] + 1 : 0);
+    ctl[KFQ_RES + 3] = verdict;
+}
+
+// owner[w] = r for the slots w0 <= w < w1 that record r owns (index words of 64 positions: the feeder; output tiles: the
+// extract), by a workgroup of KFQ_REC_BLOCK records.  A record of up to KFQ_SELF_WORDS slots marks them itself, a longer
+// one is handed to the whole block.  mine: the thread has a record to mark.  REQUIRES blockDim.x == KFQ_REC_BLOCK and a
+// block-uniform call that every thread reaches (barriers inside); the LDS is the function's own: one call per kernel.
+__device__ __forceinline__ void kfq_mark_owner(bool mine, uint32_t r, uint64_t w0, uint64_t w1, uint32_t *__restrict__ owner) {
+    __shared__ uint32_t n_long, long_rec[KFQ_REC_BLOCK];
+    __shared__ unsigned long long long_w0[KFQ_REC_BLOCK], long_w1[KFQ_REC_BLOCK];
+    if (threadIdx.x == 0) n_long = 0;
     __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const unsigned long long v = tid >= o ? a[tid - o] : 0ull;
-        __syncthreads();
-        a[tid] += v;
-        __syncthreads();
+    if (mine) {
+        if (w1 - w0 <= KFQ_SELF_WORDS) {
+            for (uint64_t w = w0; w < w1; ++w) owner[w] = r;
+        } else {
+            const uint32_t i = atomicAdd(&n_long, 1u);
+            long_rec[i] = r; long_w0[i] = w0; long_w1[i] = w1;
+        }
     }
-    unsigned long long run = a[tid] - sum;
-    for (uint64_t i = b; i < e; ++i) { const unsigned long long c = bsum[i]; bsum[i] = run; run += c; }
-    if (tid == 0) {
-        const uint64_t n_bases = a[255], bad = ctl[KFQ_FIRST_BAD];
-        uint64_t verdict = KFQ_OK;
-        if (bad != ~0ull) verdict = KFQ_ERR_FORMAT | bad << 8;                      // (among the records the capacities admit)
-        else if (room || n_chk < n_rec || n_bases > cap_bases) verdict = KFQ_ERR_ROOM;      // (n_chk < n_rec without room or a bad record cannot be: a guard)
-        else if (!final_chunk && n_rec == 0) verdict = KFQ_NOTHING;
-        ctl[KFQ_RES + 0] = n_bases; ctl[KFQ_RES + 1] = n_rec;
-        ctl[KFQ_RES + 2] = final_chunk ? n : (n_rec && verdict == KFQ_OK ? (uint64_t)nl[4 * n_rec - 1] + 1 : 0);
-        ctl[KFQ_RES + 3] = verdict;
-    }
+    __syncthreads();
+    for (uint32_t i = 0; i < n_long; ++i)
+        for (uint64_t w = long_w0[i] + threadIdx.x; w < long_w1[i]; w += KFQ_REC_BLOCK) owner[w] = long_rec[i];
 }
 
 __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfq_offsets_kernel(const unsigned long long *__restrict__ ctl, const unsigned long long *__restrict__ bsum,
                                                                     unsigned long long *__restrict__ off, uint32_t *__restrict__ word_rec,
                                                                     int64_t *__restrict__ offsets) {
     __shared__ uint32_t ws[17];
-    __shared__ uint32_t n_long, long_rec[KFQ_REC_BLOCK];
-    __shared__ unsigned long long long_w0[KFQ_REC_BLOCK], long_w1[KFQ_REC_BLOCK];
     if (ctl[KFQ_RES + 3] != KFQ_OK) return;
     const uint32_t tid = threadIdx.x;
     const uint64_t n_rec = ctl[KFQ_RES + 1], n_bases = ctl[KFQ_RES + 0], r0 = (uint64_t)blockIdx.x * KFQ_REC_BLOCK, r = r0 + tid;
@@ -247,23 +231,14 @@ __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfq_offsets_kernel(const unsign
         if (offsets) offsets[n_rec] = (int64_t)n_bases;
     }
     if (r0 >= n_rec) return;
-    if (tid == 0) n_long = 0;
     const uint32_t positions = r < n_rec ? (uint32_t)off[r] : 0u;
-    const uint64_t o = bsum[blockIdx.x] + kb_block_exscan(positions, ws, nullptr);     // (its barriers publish n_long)
+    const uint64_t o = bsum[blockIdx.x] + kb_block_exscan(positions, ws, nullptr);
     if (r < n_rec) {
         off[r] = o;
         if (offsets) offsets[r] = (int64_t)o;
-        const uint64_t w0 = (o + 63) / 64, w1 = (o + positions + 63) / 64;             // the words whose first position is the record's
-        if (w1 - w0 <= KFQ_SELF_WORDS) {
-            for (uint64_t w = w0; w < w1; ++w) word_rec[w] = (uint32_t)r;
-        } else {
-            const uint32_t i = atomicAdd(&n_long, 1u);
-            long_rec[i] = (uint32_t)r; long_w0[i] = w0; long_w1[i] = w1;
-        }
     }
-    __syncthreads();
-    for (uint32_t i = 0; i < n_long; ++i)
-        for (uint64_t w = long_w0[i] + tid; w < long_w1[i]; w += KFQ_REC_BLOCK) word_rec[w] = long_rec[i];
+    // the words whose first position is the record's
+    kfq_mark_owner(r < n_rec, (uint32_t)r, (o + 63) / 64, (o + positions + 63) / 64, word_rec);
 }
 
 // bit i of x -> bit 2 i
@@ -274,12 +249,6 @@ __device__ __forceinline__ uint64_t kfq_spread(uint64_t x) {
     x = (x | x << 2) & 0x3333333333333333ull;
     x = (x | x << 1) & 0x5555555555555555ull;
     return x;
-}
-
-// A/C/G/T in either case -> 0 .. 3, anything else -> 4
-__device__ __forceinline__ uint32_t kfq_code(uint32_t c) {
-    const uint32_t u = c & 0xDFu, x = (u >> 1) & 3u;
-    return (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? x ^ (x >> 1) : 4u;
 }
 
 // A workgroup of 4 waves; wave w of the grid owns the positions [64 w, 64 w + 64): mask word w, packed words 2 w and 2 w + 1.
@@ -306,7 +275,7 @@ __global__ __launch_bounds__(256) void kfq_pack_kernel(const uint8_t *__restrict
         const uint64_t start = ahead ? prev_start : first, rec = r0 + ahead;
         if (p < n_bases && p + 1 < end) {                              // (p + 1 == end: the separator)
             const uint32_t j = (uint32_t)(p - start);
-            code = kfq_code(t[nl[4 * rec] + 1 + j]);
+            code = kdf_base_code(t[nl[4 * rec] + 1 + j]);
             if (QUAL && t[nl[4 * rec + 2] + 1 + j] < min_qual) code = 4;
         }
     }
@@ -347,44 +316,8 @@ __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfx_len_kernel(const uint8_t *_
         if (r < n_reads && keep[r]) v = 1ull << 32 | (end - s0 + supplied);
         off[r] = v;
     }
-    unsigned long long s = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-// One workgroup of 256 behind kfx_len_kernel.  The format comes first, then the caller's record count, then the room.
-__global__ __launch_bounds__(256) void kfx_total_kernel(uint64_t n, int final_chunk, uint64_t n_reads, uint64_t cap_out, const uint32_t *__restrict__ nl,
-                                                        unsigned long long *__restrict__ bsum, unsigned long long *__restrict__ ctl) {
-    __shared__ unsigned long long a[256];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n_rec = ctl[KFQ_N_REC], n_chk = ctl[KFQ_N_CHK];
-    const uint64_t nb = (n_chk + KFQ_REC_BLOCK - 1) / KFQ_REC_BLOCK, per = (nb + 255) / 256, b = min(nb, tid * per), e = min(nb, b + per);
-    unsigned long long sum = 0;
-    for (uint64_t i = b; i < e; ++i) sum += bsum[i];
-    a[tid] = sum;
-    __syncthreads();
-    for (uint32_t o = 1; o < 256; o <<= 1) {
-        const unsigned long long v = tid >= o ? a[tid - o] : 0ull;
-        __syncthreads();
-        a[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long run = a[tid] - sum;
-    for (uint64_t i = b; i < e; ++i) { const unsigned long long c = bsum[i]; bsum[i] = run; run += c; }
-    if (tid == 0) {
-        const uint64_t out_bytes = a[255] & 0xFFFFFFFFull, n_kept = a[255] >> 32, bad = ctl[KFQ_FIRST_BAD];
-        uint64_t verdict = KFQ_OK;
-        if (bad != ~0ull) verdict = KFQ_ERR_FORMAT | bad << 8;
-        else if (n_rec != n_reads || n_chk < n_rec) verdict = KFX_ERR_COUNT;      // (n_chk < n_rec without a bad record cannot be: a guard)
-        else if (out_bytes > cap_out) verdict = KFQ_ERR_ROOM;
-        else if (!final_chunk && n_rec == 0) verdict = KFQ_NOTHING;
-        ctl[KFQ_RES + 0] = out_bytes; ctl[KFQ_RES + 1] = n_kept | n_rec << 32;
-        ctl[KFQ_RES + 2] = final_chunk ? n : (n_rec && verdict == KFQ_OK ? (uint64_t)nl[4 * n_rec - 1] + 1 : 0);
-        ctl[KFQ_RES + 3] = verdict;
-    }
+    const unsigned long long sum = kb_block_sum(v, wsum);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = sum;
 }
 
 // oskew: the output's address mod 16.  Output tile T holds the output offsets [KFQ_TILE T - oskew, KFQ_TILE (T + 1) - oskew).
@@ -392,8 +325,6 @@ __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfx_offsets_kernel(const unsign
                                                                     uint32_t oskew, unsigned long long *__restrict__ off, uint32_t *__restrict__ tile_rec,
                                                                     int64_t *__restrict__ offsets) {
     __shared__ uint32_t ws[17];
-    __shared__ uint32_t n_long, long_rec[KFQ_REC_BLOCK];
-    __shared__ unsigned long long long_t0[KFQ_REC_BLOCK], long_t1[KFQ_REC_BLOCK];
     if (ctl[KFQ_RES + 3] != KFQ_OK) return;
     const uint32_t tid = threadIdx.x;
     const uint64_t total = ctl[KFQ_RES + 0], n_kept = ctl[KFQ_RES + 1] & 0xFFFFFFFFull, n_rec = ctl[KFQ_RES + 1] >> 32;
@@ -404,29 +335,15 @@ __global__ __launch_bounds__(KFQ_REC_BLOCK) void kfx_offsets_kernel(const unsign
         if (oskew) tile_rec[0] = 0;                                    // (its first byte is output byte 0; without a skew the record at 0 writes it)
     }
     if (r0 >= n_rec) return;
-    if (tid == 0) n_long = 0;
     const unsigned long long v = r < n_rec ? off[r] : 0ull;
-    const uint32_t len = (uint32_t)v, kept = (uint32_t)(v >> 32);
+    const uint32_t len = (uint32_t)v, kept = (uint32_t)(v >> 32);     // (kept: 0 at and past n_rec)
     const unsigned long long before = bsum[blockIdx.x];
     const uint64_t o = (before & 0xFFFFFFFFull) + kb_block_exscan(len, ws, nullptr);
-    const uint64_t rank = (before >> 32) + kb_block_exscan(kept, ws, nullptr);       // (the scans' barriers publish n_long)
-    if (r < n_rec) {
-        off[r] = o;
-        if (kept) {
-            if (offsets) offsets[rank] = (int64_t)o;
-            // the tiles whose first byte is the record's
-            const uint64_t t0 = (o + oskew + KFQ_TILE - 1) / KFQ_TILE, t1 = (o + len + oskew + KFQ_TILE - 1) / KFQ_TILE;
-            if (t1 - t0 <= KFQ_SELF_WORDS) {
-                for (uint64_t w = t0; w < t1; ++w) tile_rec[w] = (uint32_t)r;
-            } else {
-                const uint32_t i = atomicAdd(&n_long, 1u);
-                long_rec[i] = (uint32_t)r; long_t0[i] = t0; long_t1[i] = t1;
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = 0; i < n_long; ++i)
-        for (uint64_t w = long_t0[i] + tid; w < long_t1[i]; w += KFQ_REC_BLOCK) tile_rec[w] = long_rec[i];
+    const uint64_t rank = (before >> 32) + kb_block_exscan(kept, ws, nullptr);
+    if (r < n_rec) off[r] = o;
+    if (kept && offsets) offsets[rank] = (int64_t)o;
+    // the tiles whose first byte is a kept record's
+    kfq_mark_owner(kept, (uint32_t)r, (o + oskew + KFQ_TILE - 1) / KFQ_TILE, (o + len + oskew + KFQ_TILE - 1) / KFQ_TILE, tile_rec);
 }
 
 // the last record of [lo, hi] whose offset is <= b (off[lo] <= b).  The offsets do not fall, a dropped record shares its

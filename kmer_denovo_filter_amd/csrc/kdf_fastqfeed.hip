@@ -65,7 +65,7 @@ static int fq_core(kdf_engine *h, const void *d_text, uint64_t n_bytes, int fina
     const dim3 wg(256);
     EvSpan span(h->timer[T_FQ], h->prof, h->stream, 1);
     fq_records(h, v, t, n_bytes, final_chunk, cap_rec, r_cap, nt, rec_blocks);
-    hipLaunchKernelGGL(kfq_total_kernel, dim3(1), wg, 0, h->stream, n_bytes, final_chunk, cap_bases, (const uint32_t *)v.nl, v.bsum, v.ctl);
+    hipLaunchKernelGGL((kfq_total_kernel<false>), dim3(1), wg, 0, h->stream, n_bytes, final_chunk, (uint64_t)0, cap_bases, (const uint32_t *)v.nl, v.bsum, v.ctl);
     hipLaunchKernelGGL(kfq_offsets_kernel, dim3((unsigned)rec_blocks), dim3(KFQ_REC_BLOCK), 0, h->stream, (const unsigned long long *)v.ctl,
                        (const unsigned long long *)v.bsum, v.off, v.word_rec, (int64_t *)d_offsets);
     if (min_qual)
@@ -98,7 +98,7 @@ static int fx_core(kdf_engine *h, const void *d_text, uint64_t n_bytes, int fina
     fq_records(h, v, t, n_bytes, final_chunk, ~0ull, r_cap, nt, rec_blocks);
     hipLaunchKernelGGL(kfx_len_kernel, dim3((unsigned)rec_blocks), dim3(KFQ_REC_BLOCK), 0, h->stream, t, n_bytes, final_chunk, (const uint8_t *)d_keep, n_reads, v.ctl,
                        (const uint32_t *)v.nl, v.off, v.bsum);
-    hipLaunchKernelGGL(kfx_total_kernel, dim3(1), wg, 0, h->stream, n_bytes, final_chunk, n_reads, cap_out, (const uint32_t *)v.nl, v.bsum, v.ctl);
+    hipLaunchKernelGGL((kfq_total_kernel<true>), dim3(1), wg, 0, h->stream, n_bytes, final_chunk, n_reads, cap_out, (const uint32_t *)v.nl, v.bsum, v.ctl);
     hipLaunchKernelGGL(kfx_offsets_kernel, dim3((unsigned)rec_blocks), dim3(KFQ_REC_BLOCK), 0, h->stream, (const unsigned long long *)v.ctl,
                        (const unsigned long long *)v.bsum, oskew, v.off, v.tile_rec, (int64_t *)d_out_offsets);
     hipLaunchKernelGGL(kfx_copy_kernel, dim3((unsigned)copy_blocks), wg, 0, h->stream, t, final_chunk, oskew, (const unsigned long long *)v.ctl, (const uint32_t *)v.nl,

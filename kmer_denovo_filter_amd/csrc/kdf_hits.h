@@ -22,9 +22,10 @@
 // does not depend on which lane wins a CAS.  No lane waits for another inside the probe loop.
 #pragma once
 #include "kdf_depth.h"
+#include "kdf_scan.h"
 
 #define KH_BLOCK_WORDS 1024               // mask words per workgroup: 4 consecutive words per thread
-// (KH_ROW_WORDS = 2 -- hits, distinct (uint32) -- and the block scan kh_block_excl: kdf_device.h, shared with kdf_spool.h)
+// (KH_ROW_WORDS = 2 -- hits, distinct (uint32): kdf_device.h, shared with kdf_spool.h; the block scan kb_block_exscan: kdf_scan.h)
 
 // mask word w with the bits at and past n_bases cleared; n_words = ceil(n_bases / 64)
 __device__ __forceinline__ uint64_t kh_word(const uint64_t *__restrict__ bits, uint64_t w, uint64_t n_words, uint64_t n_bases) {
@@ -44,37 +45,21 @@ __device__ __forceinline__ int64_t kh_read_of(const int64_t *__restrict__ offs, 
 
 __global__ __launch_bounds__(256) void kh_count_kernel(const uint64_t *__restrict__ bits, uint64_t n_bases,
                                                        unsigned long long *__restrict__ block_sums) {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t n_words = (n_bases + 63) / 64;
     const uint64_t w0 = (uint64_t)blockIdx.x * KH_BLOCK_WORDS + threadIdx.x * 4;
     uint32_t c = 0, total;
 #pragma unroll
     for (int j = 0; j < 4; ++j) c += (uint32_t)__popcll(kh_word(bits, w0 + j, n_words, n_bases));
-    kh_block_excl(c, ws, total);
+    kb_block_exscan(c, ws, &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
 // sums[0 .. n) -> their exclusive prefix sums, sums[n] = the total; ONE workgroup
 __global__ __launch_bounds__(256) void kh_scan_kernel(unsigned long long *__restrict__ sums, uint64_t n) {
     __shared__ unsigned long long ws[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned long long carry = 0;
-    for (uint64_t base = 0; base < n; base += 256) {
-        const uint64_t i = base + threadIdx.x;
-        const unsigned long long v = i < n ? sums[i] : 0;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(inc, o); if (lane >= o) inc += y; }
-        if (lane == 63) ws[wv] = inc;
-        __syncthreads();
-        unsigned long long pre = 0, total = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const unsigned long long s = ws[j]; pre += j < wv ? s : 0; total += s; }
-        if (i < n) sums[i] = carry + pre + inc - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[n] = carry;
+    const unsigned long long total = kb_sums_exscan(sums, n, ws);
+    if (threadIdx.x == 0) sums[n] = total;
 }
 
 // entry e of the list, e < cap: pos_out[e] = position of the e-th set bit, reads_out[e] (may be NULL) = its read or -1
@@ -82,14 +67,14 @@ __global__ __launch_bounds__(256) void kh_write_kernel(
     const uint64_t *__restrict__ bits, uint64_t n_bases, const unsigned long long *__restrict__ block_off,
     uint64_t *__restrict__ pos_out, int64_t *__restrict__ reads_out, const int64_t *__restrict__ offs, int64_t n_reads, uint64_t cap)
 {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t n_words = (n_bases + 63) / 64;
     const uint64_t w0 = (uint64_t)blockIdx.x * KH_BLOCK_WORDS + threadIdx.x * 4;
     uint64_t x[4];
     uint32_t c = 0, total;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { x[j] = kh_word(bits, w0 + j, n_words, n_bases); c += (uint32_t)__popcll(x[j]); }
-    uint64_t o = block_off[blockIdx.x] + kh_block_excl(c, ws, total);
+    uint64_t o = block_off[blockIdx.x] + kb_block_exscan(c, ws, &total);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         uint64_t y = x[j];
@@ -167,10 +152,7 @@ __global__ __launch_bounds__(256) void kh_distinct_kernel(
     const bool head = lane == 0 || prev != r;
     const unsigned long long heads = __ballot(head), news = __ballot(isnew);
     if (head && r >= 0) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        const unsigned long long run = (len >= 64 ? ~0ull : ((1ull << len) - 1)) << lane;
-        const uint32_t c = (uint32_t)__popcll(news & run);
+        const uint32_t c = (uint32_t)__popcll(news & kdf_wave_run(heads, lane).mask);
         if (c) atomicAdd(&rows[(uint64_t)r * KH_ROW_WORDS + 1], c);
     }
 }

@@ -24,6 +24,8 @@
 // nothing and raises a flag that takes it off the count.
 #pragma once
 #include "kdf_tilewalk.h"
+#include "kdf_scan.h"
+#include "kdf_text.h"
 
 #define KF_TILE_BYTES 4096                 // text bytes per workgroup: 256 lanes x 16
 #define KF_MAX_CLASSES 20
@@ -144,19 +146,8 @@ template <int HALO>
 __device__ __forceinline__ void kf_load_tile(const KfText &x, uint64_t t0, uint8_t *buf) {
     for (uint32_t c = threadIdx.x; c < (KF_TILE_BYTES + HALO) / 16; c += 256) {
         const uint64_t p = t0 + 16 * c;
-        uint4 v;
-        if (x.aligned && p + 16 <= x.n) v = *reinterpret_cast<const uint4 *>(x.t + p);
-        else {
-            uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const uint64_t q = p + i;
-                const uint32_t ch = q < x.n ? x.t[q] : (q == x.n && x.supply ? '\n' : 0);
-                w[i >> 2] |= ch << (8 * (i & 3));
-            }
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        *reinterpret_cast<uint4 *>(buf + KF_PRE + 16 * c) = v;
+        *reinterpret_cast<uint4 *>(buf + KF_PRE + 16 * c) = kt_load_granule(x.t, (int64_t)p, 0, (int64_t)x.n, x.aligned, 0u);
+        if (x.supply && x.n - p < 16) buf[KF_PRE + 16 * c + (uint32_t)(x.n - p)] = '\n';      // (x.n < p wraps: no byte of this granule)
     }
     if (threadIdx.x == 0) buf[KF_PRE - 1] = t0 ? x.t[t0 - 1] : '\n';
     __syncthreads();
@@ -181,33 +172,23 @@ __global__ void kf_ctl_init_kernel(unsigned long long *ctl) { ctl[0] = ~0ull; ct
 __global__ __launch_bounds__(256) void kf_count_kernel(const uint8_t *__restrict__ t, uint64_t n, int final_chunk,
                                                        unsigned long long *__restrict__ block_sums, unsigned long long *__restrict__ ctl) {
     __shared__ __align__(16) uint8_t buf[KF_PRE + KF_TILE_BYTES + 16];
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     __shared__ unsigned long long nl[4];
     const KfText x = kf_text(t, n, final_chunk);
     const uint64_t t0 = (uint64_t)blockIdx.x * KF_TILE_BYTES, s0 = t0 + threadIdx.x * 16u;
     kf_load_tile<16>(x, t0, buf);
     const uint32_t j0 = KF_PRE + threadIdx.x * 16u;
     uint32_t total;
-    kh_block_excl((uint32_t)__popc(kf_lane_starts(buf, j0, s0, n)), ws, total);
+    kb_block_exscan((uint32_t)__popc(kf_lane_starts(buf, j0, s0, n)), ws, &total);
     unsigned long long last = 0;                                      // behind the lane's last '\n'
 #pragma unroll
     for (int i = 0; i < 16; ++i)
         if (buf[j0 + i] == '\n' && s0 + i < n) last = s0 + i + 1;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_xor(last, o); last = y > last ? y : last; }
-    if ((threadIdx.x & 63) == 0) nl[threadIdx.x >> 6] = last;
-    __syncthreads();
+    last = kb_block_max(last, nl);
     if (threadIdx.x == 0) {
         block_sums[blockIdx.x] = total;
-        for (int j = 0; j < 4; ++j) last = nl[j] > last ? nl[j] : last;
         if (last) atomicMax(&ctl[1], last);
     }
-}
-
-// A/C/G/T in either case -> 0 .. 3, anything else -> 4
-__device__ __forceinline__ uint32_t kf_code(uint8_t c) {
-    const uint32_t u = c & 0xDFu, x = (u >> 1) & 3u;
-    return (u == 'A' || u == 'C' || u == 'G' || u == 'T') ? x ^ (x >> 1) : 4u;
 }
 
 // KW 1: k <= 32 -> lo; 2: k 33 .. 63 -> lo, hi; 3 .. 7: odd k 65 .. 201 -> rows of KW words in lo.  Rows rank < cap only.
@@ -216,14 +197,14 @@ __global__ __launch_bounds__(256) void kf_parse_kernel(const uint8_t *__restrict
                                                        const unsigned long long *__restrict__ block_off, unsigned long long *__restrict__ ctl,
                                                        uint64_t *__restrict__ lo, uint64_t *__restrict__ hi, uint64_t cap) {
     __shared__ __align__(16) uint8_t buf[KF_PRE + KF_TILE_BYTES + KF_HALO];
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const KfText x = kf_text(t, n, final_chunk);
     const uint64_t t0 = (uint64_t)blockIdx.x * KF_TILE_BYTES, s0 = t0 + threadIdx.x * 16u;
     kf_load_tile<KF_HALO>(x, t0, buf);
     const uint64_t whole = final_chunk ? n : ctl[1];                  // lines that start below it have their '\n'
     const uint32_t j0 = KF_PRE + threadIdx.x * 16u;
-    uint32_t starts = kf_lane_starts(buf, j0, s0, n), total;
-    uint64_t rank = block_off[blockIdx.x] + kh_block_excl((uint32_t)__popc(starts), ws, total);
+    uint32_t starts = kf_lane_starts(buf, j0, s0, n);
+    uint64_t rank = block_off[blockIdx.x] + kb_block_exscan((uint32_t)__popc(starts), ws, nullptr);
     for (; starts; starts &= starts - 1, ++rank) {
         const int i = __ffs(starts) - 1;
         const uint64_t s = s0 + i;
@@ -239,7 +220,7 @@ __global__ __launch_bounds__(256) void kf_parse_kernel(const uint8_t *__restrict
         for (int b = 0; b < k; ++b) {
             const uint8_t c = line[b];
             if (c == '\n') { bad_len = true; break; }
-            uint32_t code = kf_code(c);
+            uint32_t code = kdf_base_code(c);
             if (code > 3) { bad_base = true; code = 0; }
             if constexpr (KW > 2) roll.push(code, false, tb);
             else if (KW == 2 && b >= 32) e1 |= (uint64_t)code << (2 * b - 64);

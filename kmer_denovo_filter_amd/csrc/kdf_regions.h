@@ -27,6 +27,7 @@
 // All results are integer sums and maxima: they do not depend on the order the atomics land in.
 #pragma once
 #include "kdf_device.h"
+#include "kdf_scan.h"
 
 #define KR_BLOCK 256                      // sorted entries per workgroup, one per thread
 
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256) void kr_flag_kernel(const int64_t *__restrict_
                                                       uint64_t merge_distance, const KrMax *__restrict__ agg, uint8_t *__restrict__ flags,
                                                       unsigned long long *__restrict__ block_sums) {
     __shared__ KrMax ws[4];
-    __shared__ uint32_t wc[4];
+    __shared__ uint32_t wc[17];
     const uint64_t i = (uint64_t)blockIdx.x * KR_BLOCK + threadIdx.x;
     const KrMax v = kr_load(chrom, end, perm, n, i);
     KrMax total;
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void kr_flag_kernel(const int64_t *__restrict_
     uint32_t f = 0, nf;
     if (v.c) f = ex.c != v.c || (unsigned long long)start[perm[i]] > ex.e + merge_distance;
     if (i < n) flags[i] = (uint8_t)f;
-    kh_block_excl(f, wc, nf);
+    kb_block_exscan(f, wc, &nf);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = nf;
 }
 
@@ -113,12 +114,12 @@ __global__ __launch_bounds__(256) void kr_regions_kernel(const int64_t *__restri
                                                          const uint8_t *__restrict__ flags, uint64_t n,
                                                          const unsigned long long *__restrict__ block_off, int64_t *__restrict__ region_of,
                                                          unsigned long long *__restrict__ regions, uint64_t cap) {
-    __shared__ uint32_t wc[4];
+    __shared__ uint32_t wc[17];
     const int lane = threadIdx.x & 63;
     const uint64_t i = (uint64_t)blockIdx.x * KR_BLOCK + threadIdx.x;
     const uint32_t f = i < n ? flags[i] : 0;
     uint32_t nf;
-    const uint32_t before = kh_block_excl(f, wc, nf);
+    const uint32_t before = kb_block_exscan(f, wc, &nf);
     long long g = -1;
     unsigned long long en = 0;
     if (i < n) {
@@ -142,10 +143,8 @@ __global__ __launch_bounds__(256) void kr_regions_kernel(const int64_t *__restri
     }
     const unsigned long long heads = __ballot(head);
     if (head && g >= 0 && (uint64_t)g < cap) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
         atomicMax(&regions[(uint64_t)g * 4 + 2], en);
-        atomicAdd(&regions[(uint64_t)g * 4 + 3], (unsigned long long)len);
+        atomicAdd(&regions[(uint64_t)g * 4 + 3], (unsigned long long)kdf_wave_run(heads, lane).len);
     }
 }
 
@@ -187,10 +186,7 @@ __global__ __launch_bounds__(256) void kr_distinct_kernel(const uint64_t *__rest
     const bool head = lane == 0 || gl != g;
     const unsigned long long heads = __ballot(head), news = __ballot(counted);
     if (head && g < n_groups) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        const unsigned long long run = (len >= 64 ? ~0ull : ((1ull << len) - 1)) << lane;
-        const unsigned long long c = (unsigned long long)__popcll(news & run);
+        const unsigned long long c = (unsigned long long)__popcll(news & kdf_wave_run(heads, lane).mask);
         if (c) atomicAdd(&counts[g], c);
     }
 }

@@ -1,5 +1,7 @@
-// kdf_scan.h -- wave and block prefix sums of the binned pipeline (kdf_binned.h) on DPP.  Self-contained (HIP runtime
-// only), so that a stand-alone program can include it: tests/native/block_scan_check.hip.
+// kdf_scan.h -- the block-level sums of every kernel: wave and block prefix sums on DPP (the binned pipeline, kdf_binned.h,
+// the feeders, and the list kernels of hits, coverage, regions, the spool and the k-mer FASTA parse), block sums, and the
+// single-workgroup scan of 64-bit block sums.  Self-contained (HIP runtime only), so that a stand-alone program can include
+// it: tests/native/block_scan_check.hip.
 //
 // A wave64 scan by __shfl_up is six ds_bpermute_b32, each a dependent round trip through the LDS pipe -- the pipe the
 // partition kernels are bound by.  The same scan on DPP is six v_add_u32_dpp and no LDS traffic: row_shr:1/2/4/8 inside
@@ -130,4 +132,52 @@ __device__ __forceinline__ void kb_strip_exscan(const uint32_t *hist, uint32_t *
         if ((int)lane < nb) offs[lane] = inc - v;
         if (lane == 63) offs[nb] = inc;                                 // (the lanes from nb on added nothing)
     }
+}
+
+// Sum of v over the workgroup, to every thread.  ONE barrier: the caller puts a barrier of its own before wsum is written
+// again.  uint32 on the DPP scan (every lane active, blockDim.x a multiple of 64, at most 1024; the sum wraps); 64-bit
+// values, which DPP does not add, on a butterfly of shuffles -- also in max form.
+__device__ __forceinline__ uint32_t kb_block_sum(uint32_t v, uint32_t *wsum /* blockDim.x / 64 words LDS */) {
+    const uint32_t inc = kb_wave_incl_scan(v);
+    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint32_t total;
+    kb_wave_sums_before(wsum, threadIdx.x, blockDim.x >> 6, total);
+    return total;
+}
+template <bool MAX>
+__device__ __forceinline__ unsigned long long kb_block_reduce64(unsigned long long v, unsigned long long *wsum /* blockDim.x / 64 words LDS */) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_xor(v, o); v = MAX ? (y > v ? y : v) : v + y; }
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = wsum[0];
+    for (uint32_t j = 1; j < blockDim.x >> 6; ++j) { const unsigned long long y = wsum[j]; v = MAX ? (y > v ? y : v) : v + y; }
+    return v;
+}
+__device__ __forceinline__ unsigned long long kb_block_sum(unsigned long long v, unsigned long long *wsum) { return kb_block_reduce64<false>(v, wsum); }
+__device__ __forceinline__ unsigned long long kb_block_max(unsigned long long v, unsigned long long *wsum) { return kb_block_reduce64<true>(v, wsum); }
+
+// The scan of the 64-bit sums of a grid's workgroups by ONE workgroup of 256 threads: sums[0 .. n) -> their exclusive
+// prefix sums, in place, 256 at a time; returns the total to every thread.  Writes nothing but sums[0 .. n).  Sums of two
+// 32-bit halves that never carry into each other (kdf_fastqfeed.h: kept << 32 | bytes) scan as two independent sums.
+__device__ __forceinline__ unsigned long long kb_sums_exscan(unsigned long long *__restrict__ sums, uint64_t n, unsigned long long *ws /* 4 words LDS */) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned long long carry = 0;
+    for (uint64_t base = 0; base < n; base += 256) {
+        const uint64_t i = base + threadIdx.x;
+        const unsigned long long v = i < n ? sums[i] : 0;
+        unsigned long long inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(inc, o); if (lane >= o) inc += y; }
+        if (lane == 63) ws[wv] = inc;
+        __syncthreads();
+        unsigned long long pre = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const unsigned long long s = ws[j]; pre += j < wv ? s : 0; total += s; }
+        if (i < n) sums[i] = carry + pre + inc - v;
+        carry += total;
+        __syncthreads();
+    }
+    return carry;
 }

@@ -10,8 +10,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "kdf_device.h"          // kh_block_excl: the block scan the ks_select_* kernels share with kh_* (kdf_hits.h, whose
-                                 // kh_scan_kernel belongs to kdf_engine_reads.hip: the spool runs it through kh_scan_launch)
+#include "kdf_device.h"
+#include "kdf_scan.h"            // kb_block_exscan: the block scan of the ks_select_* kernels (their scan of the block sums,
+                                 // kh_scan_kernel of kdf_hits.h, belongs to kdf_engine_reads.hip: the spool runs it through kh_scan_launch)
 
 #define KS_THREADS 256
 #define KS_MAX_BLOCKS 2048u      // a streaming copy: 8 workgroups per CU fill the device, the rest is a grid stride
@@ -96,21 +97,21 @@ __device__ __forceinline__ uint32_t ks_select_mask(const uint64_t *__restrict__ 
 
 __global__ __launch_bounds__(256) void ks_select_count_kernel(const uint64_t *__restrict__ rows, uint64_t n_rows, uint32_t min_distinct,
                                                               int rows16, unsigned long long *__restrict__ block_sums) {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t r0 = (uint64_t)blockIdx.x * KS_SELECT_ROWS + threadIdx.x * 4;
     uint32_t total;
-    kh_block_excl((uint32_t)__popc(ks_select_mask(rows, r0, n_rows, min_distinct, rows16)), ws, total);
+    kb_block_exscan((uint32_t)__popc(ks_select_mask(rows, r0, n_rows, min_distinct, rows16)), ws, &total);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void ks_select_write_kernel(const uint64_t *__restrict__ rows, uint64_t n_rows, uint32_t min_distinct,
                                                               int rows16, const unsigned long long *__restrict__ block_off,
                                                               uint64_t *__restrict__ out, uint64_t cap) {
-    __shared__ uint32_t ws[4];
+    __shared__ uint32_t ws[17];
     const uint64_t r0 = (uint64_t)blockIdx.x * KS_SELECT_ROWS + threadIdx.x * 4;
     const uint32_t m = ks_select_mask(rows, r0, n_rows, min_distinct, rows16);
     uint32_t total;
-    uint64_t o = block_off[blockIdx.x] + kh_block_excl((uint32_t)__popc(m), ws, total);
+    uint64_t o = block_off[blockIdx.x] + kb_block_exscan((uint32_t)__popc(m), ws, &total);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (m >> j & 1) { if (o < cap) out[o] = r0 + j; ++o; }

@@ -29,6 +29,7 @@
 //     minima and maxima: the result does not depend on which lane wins a CAS.
 #pragma once
 #include "kdf_coverage.h"
+#include "kdf_text.h"
 
 #define KV_VAR_WORDS  8                   // n, sum, min, max, n_alt, sum_alt, min_alt, max_alt (uint64)
 #define KV_PAIR_WORDS 2                   // windows, absent (uint32)
@@ -126,11 +127,6 @@ struct KvArgs {
     const uint64_t *cand_lo; const unsigned long long *cand_off; uint64_t n_cand;
 };
 
-// 0..3 for ACGT in either case, 4 for everything else
-__device__ __forceinline__ uint32_t kv_base_code(uint8_t c) {
-    switch (c | 0x20) { case 'a': return 0; case 'c': return 1; case 'g': return 2; case 't': return 3; default: return 4; }
-}
-
 // What candidate c comes to.  Returns false when it has no read or variant to speak of.  Otherwise r, v and n_ent (the
 // number of entries) are set; WRITE: the entries go to entry_pos / entry_pair [eo ..) below entry_cap, with pair index pi;
 // !WRITE: flags is set for a pair (n_ent > 0).
@@ -209,7 +205,7 @@ __device__ __forceinline__ bool kv_candidate(const KvArgs &a, uint64_t c, int64_
         if (qe - at != alen || b + qe > lim) return true;
         for (int64_t i = 0; i < alen; ++i) {
             const uint64_t q = (uint64_t)(b + at + i);
-            if (bad(at + i) || ((a.packed[q >> 5] >> (2 * (q & 31))) & 3) != kv_base_code(a.alt[ao + i])) return true;
+            if (bad(at + i) || ((a.packed[q >> 5] >> (2 * (q & 31))) & 3) != kdf_base_code(a.alt[ao + i])) return true;
         }
         flags = 1;
     }
@@ -309,11 +305,9 @@ __global__ __launch_bounds__(256) void kv_evidence_kernel(
     const bool head = lane == 0 || prev != pr;
     const unsigned long long heads = __ballot(head), abs_ = __ballot(absent);
     if (head && pr >= 0) {
-        const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
-        const int len = rest ? __builtin_ctzll(rest) + 1 : 64 - lane;
-        const unsigned long long run = (len >= 64 ? ~0ull : ((1ull << len) - 1)) << lane;
-        const uint32_t na = (uint32_t)__popcll(abs_ & run);
-        atomicAdd(&pair_rows[(uint64_t)pr * KV_PAIR_WORDS], (uint32_t)len);
+        const KdfWaveRun run = kdf_wave_run(heads, lane);
+        const uint32_t na = (uint32_t)__popcll(abs_ & run.mask);
+        atomicAdd(&pair_rows[(uint64_t)pr * KV_PAIR_WORDS], (uint32_t)run.len);
         if (na) atomicAdd(&pair_rows[(uint64_t)pr * KV_PAIR_WORDS + 1], na);
     }
 }

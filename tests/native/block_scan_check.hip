@@ -8,6 +8,8 @@
 // Strip scan, kb_strip_exscan by wave 0 of a 1024-thread workgroup as in kb_slabsort_kernel: nb = 1, 2, 4 .. 1024; all
 // zeros, all ones, a slab's 16 384 windows in the first bin / in the last bin / spread at random / at random over every
 // third bin; nothing past offs[nb] may be written.
+// Block sums, kb_block_sum (uint32 and 64-bit) and kb_block_max, workgroups of 64, 256 and 1024 threads; the scan of 64-bit
+// block sums by one workgroup, kb_sums_exscan: see check_sums and check_sums_scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -104,6 +106,111 @@ static long check_blocks(int nt, long &wrong) {
     return (long)nc * 2;
 }
 
+// one workgroup per case; every thread writes what it got
+__global__ void k_sum32(const uint32_t *in, uint32_t *out) {
+    __shared__ uint32_t wsum[16];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    out[i] = kb_block_sum(in[i], wsum);
+}
+__global__ void k_sum64(const unsigned long long *in, unsigned long long *out, unsigned long long *out_max) {
+    __shared__ unsigned long long wsum[16], wmax[16];
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    out[i] = kb_block_sum(in[i], wsum);
+    out_max[i] = kb_block_max(in[i], wmax);
+}
+
+// kb_block_sum (uint32 and 64-bit; the 64-bit cases also through kb_block_max): all zeros, all ones, one non-zero value at
+// lane 0 and at lane 63 of the first and of the last wave, a 32-bit sum that wraps, a 64-bit sum beyond 2^32
+static long check_sums(int nt, long &wrong) {
+    const int spots[4] = {0, 63, nt - 64, nt - 1};
+    std::vector<std::vector<uint32_t>> c32;
+    std::vector<std::vector<unsigned long long>> c64;
+    c32.emplace_back(nt, 0u); c32.emplace_back(nt, 1u);
+    c64.emplace_back(nt, 0ull); c64.emplace_back(nt, 1ull);
+    for (int s = 0; s < 4; ++s) {
+        std::vector<uint32_t> a(nt, 0u); a[spots[s]] = 0x9E3779B1u; c32.push_back(a);
+        std::vector<unsigned long long> b(nt, 0ull); b[spots[s]] = 0x9E3779B97F4A7C15ull; c64.push_back(b);
+    }
+    { std::vector<uint32_t> a(nt); for (int i = 0; i < nt; ++i) a[i] = rnd() | 0x80000000u; c32.push_back(a); }                  // wraps from the second value on
+    { std::vector<unsigned long long> b(nt); for (int i = 0; i < nt; ++i) b[i] = (unsigned long long)rnd() << 8 | 0x8000000000ull; c64.push_back(b); }   // 2^39 and more each
+    const size_t n32 = c32.size(), n64 = c64.size();
+    std::vector<uint32_t> in32(n32 * nt), out32(n32 * nt);
+    std::vector<unsigned long long> in64(n64 * nt), out64(n64 * nt), max64(n64 * nt);
+    for (size_t c = 0; c < n32; ++c) for (int i = 0; i < nt; ++i) in32[c * nt + i] = c32[c][i];
+    for (size_t c = 0; c < n64; ++c) for (int i = 0; i < nt; ++i) in64[c * nt + i] = c64[c][i];
+    uint32_t *d_in32, *d_out32;
+    unsigned long long *d_in64, *d_out64, *d_max64;
+    CK(hipMalloc(&d_in32, in32.size() * 4)); CK(hipMalloc(&d_out32, in32.size() * 4));
+    CK(hipMalloc(&d_in64, in64.size() * 8)); CK(hipMalloc(&d_out64, in64.size() * 8)); CK(hipMalloc(&d_max64, in64.size() * 8));
+    CK(hipMemcpy(d_in32, in32.data(), in32.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(d_in64, in64.data(), in64.size() * 8, hipMemcpyHostToDevice));
+    CK(hipMemset(d_out32, 0xA5, in32.size() * 4)); CK(hipMemset(d_out64, 0xA5, in64.size() * 8)); CK(hipMemset(d_max64, 0xA5, in64.size() * 8));
+    hipLaunchKernelGGL(k_sum32, dim3((unsigned)n32), dim3(nt), 0, 0, d_in32, d_out32);
+    hipLaunchKernelGGL(k_sum64, dim3((unsigned)n64), dim3(nt), 0, 0, d_in64, d_out64, d_max64);
+    CK(hipGetLastError()); CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out32.data(), d_out32, in32.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(out64.data(), d_out64, in64.size() * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(max64.data(), d_max64, in64.size() * 8, hipMemcpyDeviceToHost));
+    CK(hipFree(d_in32)); CK(hipFree(d_out32)); CK(hipFree(d_in64)); CK(hipFree(d_out64)); CK(hipFree(d_max64));
+    for (size_t c = 0; c < n32; ++c) {
+        uint32_t sum = 0;                                                // (wraps, as the device sum does)
+        for (int i = 0; i < nt; ++i) sum += c32[c][i];
+        for (int i = 0; i < nt; ++i)
+            if (out32[c * nt + i] != sum && ++wrong <= 10) printf("block sum, %d threads, case %zu, thread %d: %u, expected %u\n", nt, c, i, out32[c * nt + i], sum);
+    }
+    for (size_t c = 0; c < n64; ++c) {
+        unsigned long long sum = 0, mx = 0;
+        for (int i = 0; i < nt; ++i) { sum += c64[c][i]; mx = c64[c][i] > mx ? c64[c][i] : mx; }
+        for (int i = 0; i < nt; ++i) {
+            if (out64[c * nt + i] != sum && ++wrong <= 10) printf("block sum (64), %d threads, case %zu, thread %d: %llu, expected %llu\n", nt, c, i, out64[c * nt + i], sum);
+            if (max64[c * nt + i] != mx && ++wrong <= 10) printf("block max (64), %d threads, case %zu, thread %d: %llu, expected %llu\n", nt, c, i, max64[c * nt + i], mx);
+        }
+    }
+    return (long)(n32 + n64);
+}
+
+// kb_sums_exscan by one workgroup of 256: the total comes back through every thread
+constexpr int SUMS_GUARD = 8;
+__global__ __launch_bounds__(256) void k_sums(unsigned long long *sums, uint64_t n, unsigned long long *tot) {
+    __shared__ unsigned long long ws[4];
+    tot[threadIdx.x] = kb_sums_exscan(sums, n, ws);
+}
+
+// n = 0, 1, 255, 256, 257, 511, 513, 65 537; random values below 2^40, and values 1 << 32 | len, len < 2^20, as the FASTQ
+// extract scans them (records in the high half, bytes in the low half: the halves scan independently while the lengths
+// sum to less than 2^32, which they do up to n = 513).  Nothing at or past sums[n] may be written.
+static long check_sums_scan(long &wrong) {
+    static const uint64_t NS[8] = {0, 1, 255, 256, 257, 511, 513, 65537};
+    long cases = 0;
+    for (int form = 0; form < 2; ++form) {
+        for (int c = 0; c < 8; ++c, ++cases) {
+            const uint64_t n = NS[c];
+            std::vector<unsigned long long> in(n + SUMS_GUARD, 0xFEEDF00DFEEDF00Dull), out(n + SUMS_GUARD), tot(256);
+            for (uint64_t i = 0; i < n; ++i)
+                in[i] = form ? 1ull << 32 | (rnd() >> 12) : (unsigned long long)rnd() << 8 | (rnd() & 0xFFu);
+            unsigned long long *d_s, *d_t;
+            CK(hipMalloc(&d_s, in.size() * 8)); CK(hipMalloc(&d_t, 256 * 8));
+            CK(hipMemcpy(d_s, in.data(), in.size() * 8, hipMemcpyHostToDevice)); CK(hipMemset(d_t, 0xA5, 256 * 8));
+            hipLaunchKernelGGL(k_sums, dim3(1), dim3(256), 0, 0, d_s, n, d_t);
+            CK(hipGetLastError()); CK(hipDeviceSynchronize());
+            CK(hipMemcpy(out.data(), d_s, in.size() * 8, hipMemcpyDeviceToHost)); CK(hipMemcpy(tot.data(), d_t, 256 * 8, hipMemcpyDeviceToHost));
+            CK(hipFree(d_s)); CK(hipFree(d_t));
+            unsigned long long run = 0, bytes = 0;
+            for (uint64_t i = 0; i < n; ++i) {
+                if (out[i] != run && ++wrong <= 10) printf("sums scan, form %d, n %llu: [%llu] = %llu, expected %llu\n", form, (unsigned long long)n, (unsigned long long)i, out[i], run);
+                if (form && n <= 513 && (out[i] >> 32 != i || (out[i] & 0xFFFFFFFFull) != bytes) && ++wrong <= 10)
+                    printf("sums scan, n %llu: the halves of [%llu] = %llx are not (%llu, %llu)\n", (unsigned long long)n, (unsigned long long)i, out[i], (unsigned long long)i, bytes);
+                run += in[i]; bytes += in[i] & 0xFFFFFFFFull;
+            }
+            for (int i = 0; i < SUMS_GUARD; ++i)
+                if (out[n + i] != 0xFEEDF00DFEEDF00Dull && ++wrong <= 10) printf("sums scan, form %d, n %llu: [n + %d] was written\n", form, (unsigned long long)n, i);
+            for (int i = 0; i < 256; ++i)
+                if (tot[i] != run && ++wrong <= 10) printf("sums scan, form %d, n %llu: thread %d got the total %llu, expected %llu\n", form, (unsigned long long)n, i, tot[i], run);
+        }
+    }
+    return cases;
+}
+
 static long check_strips(long &wrong) {
     constexpr uint32_t SLAB = 16384;
     std::vector<int> nbs; std::vector<std::vector<uint32_t>> cases;
@@ -151,6 +258,10 @@ int main() {
     static const int NTS[6] = {64, 128, 256, 512, 768, 1024};
     for (int i = 0; i < 6; ++i) nblock += check_blocks(NTS[i], wrong);
     const long nstrip = check_strips(wrong);
-    printf("block scans: %ld cases\nstrip scans: %ld cases\n%ld wrong\n", nblock, nstrip, wrong);
+    long nsum = 0;
+    static const int SUM_NTS[3] = {64, 256, 1024};
+    for (int i = 0; i < 3; ++i) nsum += check_sums(SUM_NTS[i], wrong);
+    const long nscan = check_sums_scan(wrong);
+    printf("block scans: %ld cases\nstrip scans: %ld cases\nblock sums: %ld cases\nsums scans: %ld cases\n%ld wrong\n", nblock, nstrip, nsum, nscan, wrong);
     return wrong ? 1 : 0;
 }
